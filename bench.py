@@ -20,12 +20,18 @@ all-gather is pre-sized from the setup's key counts, so with N > 1 the keys that
 travel are the setup's (the per-step key extraction would need the counts of
 every rank on the host first: one more collective and a host wait per step).
 
-Besides the timed step, rank 0 of a single-GPU run measures (untimed, after the
-step loop): the same closed step over 200 steps when the timed region was
-shorter (`long_run`), the open step of rounds 1-2 (`open_loop`), the comparator alone at
-BASELINE configs[2] and configs[3] scale (`compare`, `compare_c4`), the scan at
-the configs[4] shape (`scan_c5`) and the file-to-file drivers end to end
-(`end_to_end`), each beside the oracle.
+A plain run sets up, warms up, times --steps steps and prints the line.  With
+--full, rank 0 of a single-GPU run also measures (untimed, after the step loop):
+the same closed step over 200 steps when the timed region was shorter
+(`long_run`), the open step of rounds 1-2 (`open_loop`), the dense kernel alone
+and the measured HBM rates (`roofline`), the comparator alone at BASELINE
+configs[2] and configs[3] scale (`compare`, `compare_c4`), the scan at the
+configs[4] shape (`scan_c5`) and the file-to-file drivers end to end
+(`end_to_end`), each beside the oracle; with N > 1 it checks the exchange and
+runs the multi-rank configs[3] leg.
+
+--dump-outputs DIR writes what the last timed step computed as .npy files
+(dump_outputs), so that two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -163,6 +169,11 @@ def main():
     ap.add_argument("--mode", choices=["default", "direct", "filter", "pair"], default="default")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the `compare` (config 3) and `end_to_end` objects")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline: the long and open runs of the step, "
+                         "the roofline's own launches, the checks against the oracle and the CPU baselines, the BASELINE legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; see dump_outputs)")
     ap.add_argument("--experiment", action="store_true",
                     help="honour the schedule / analysis knobs (EXPERIMENT_KNOBS below); without it they are ignored, so that the "
                          "headline path is the code as written with its defaults, whatever the environment holds")
@@ -547,7 +558,7 @@ def main():
             sl.keys_job[kcur] = True
             sl.scan._reader = sl.keys[kcur]
             sl.kv ^= 1
-            last["n_out"], last["slot"] = n_out, sl
+            last["n_out"], last["d_out"], last["slot"] = n_out, d_out, sl
             last["n_out_batch"][sl.batch] = n_out
             return
         if exchange_kind == "slots":
@@ -558,7 +569,7 @@ def main():
                 sl.cmp.compare_end()
             if exchange_kind == "gather":
                 sl.exchange.collect_rows(sl.d_inter)      # strips -> rank 0, on stream B
-        last["n_out"], last["slot"] = n_out, sl
+        last["n_out"], last["d_out"], last["slot"] = n_out, d_out, sl
         last["n_out_batch"][sl.batch] = n_out
 
     def run_steps(n):
@@ -582,7 +593,7 @@ def main():
                     ctx.compare_device(K, mn_ptr, lo_ptr, None, sk_off, n_total, row_args[0], row_args[1], sl.d_inter.data_ptr(), n_query=row_args[2])
                     if exchange_kind == "gather":
                         sl.exchange.collect_rows(sl.d_inter)
-                last["n_out"], last["slot"] = n_out, sl
+                last["n_out"], last["d_out"], last["slot"] = n_out, d_out, sl
                 last["n_out_batch"][sl.batch] = n_out
             return
         import collections
@@ -606,7 +617,7 @@ def main():
         while pending:
             collect_step(pending.popleft())
 
-    last = {"n_out": 0, "slot": slots[0], "n_out_batch": {}}
+    last = {"n_out": 0, "d_out": None, "slot": slots[0], "n_out_batch": {}}
     host_detail = {}                        # closed step: host seconds per call of a visit
     host = {"queue": 0.0, "collect": 0.0}   # host seconds spent queueing / waiting (pipelined mode)
 
@@ -615,6 +626,24 @@ def main():
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
+
+    def finish_queued():
+        """closed step: collect what the last visit of every slot left queued (its comparison, its key extraction);
+        -> the keys of the last step's scan as (context, sketch_keys_device_end()), or None"""
+        keys_last = None
+        for sl in slots:
+            if getattr(sl, "compare_queued", False):
+                sl.cmp.compare_end()
+                sl.compare_queued = False
+            for j in (0, 1):
+                if sl.keys_job[j]:
+                    got = sl.keys[j].sketch_keys_device_end()
+                    sl.keys_job[j] = False
+                    if sl is last["slot"]:
+                        keys_last = (sl.keys[j], got)
+            for c in getattr(sl, "scans", [sl.scan]):
+                c._reader = None
+        return keys_last
 
     # Clocks and caches: the GPU has idled through the setup above (host-side synthesis, uploads) and takes ~100 steps
     # to come back to its sustained clocks (200 timed steps: 0.124-0.127 ms each; 600: 0.117).  An untimed run-in of the
@@ -664,13 +693,16 @@ def main():
             for key in tm:
                 tm[key] += t[key]
     inter_nonzero_main = int(torch.count_nonzero(d_inter).item())
+    keys_last = finish_queued() if device_keys else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx_full, last, keys_last, d_inter)
     # Second, shorter timed region (single GPU): the OPEN step of rounds 1-2 -- the same scans, the comparison working on the
     # keys of the setup's sketches (the same every step), no key extraction in the loop.  Reported beside the headline as
     # `open_loop`: what the two kernels chains do when the hand-off between them is left out.
     # The same closed step over a longer run (single GPU, when the timed region was short -- the driver's --steps 20): what
     # filling and draining the pipeline once costs a 20-step region.  Reported beside the headline.
     long_run = None
-    if device_keys and args.steps < 200:
+    if args.full and device_keys and args.steps < 200:
         try:
             for c in all_ctx:                             # the same event brackets as a --steps 200 run has (every 8th dense pass)
                 c.timing_enable(True, kinds)
@@ -690,18 +722,9 @@ def main():
         except Exception as e:  # noqa: BLE001
             long_run = {"error": repr(e)}
     open_loop = None
-    if device_keys:
+    if args.full and device_keys:
         try:
-            for sl in slots:                              # finish what the closed steps left queued
-                if getattr(sl, "compare_queued", False):
-                    sl.cmp.compare_end()
-                    sl.compare_queued = False
-                for j in (0, 1):
-                    if sl.keys_job[j]:
-                        sl.keys[j].sketch_keys_device_end()
-                        sl.keys_job[j] = False
-                for c in getattr(sl, "scans", [sl.scan]):
-                    c._reader = None
+            finish_queued()                               # what the closed steps of long_run left queued, if it ran
             closed_keys_total = last.get("keys_total")
             device_keys = False
             n_open = min(args.steps, 200)
@@ -740,7 +763,7 @@ def main():
     # untimed cross-check of the two exchange forms: the key-partitioned result must equal the
     # all-gather + owned-rows result on every rank count
     exchange_check = None
-    if exchange_kind == "slots":
+    if args.full and exchange_kind == "slots":
         try:
             if exchange.overflowed(d_inter):
                 exchange_check = "slot overflow"
@@ -755,7 +778,7 @@ def main():
                 exchange_check = "equal to all-gather form" if bool(torch.equal(d_ref, d_inter)) else "MISMATCH"
         except Exception as e:  # noqa: BLE001 -- the check must not take the bench line down
             exchange_check = "check failed: %r" % (e,)
-    elif exchange_kind == "gather":
+    elif args.full and exchange_kind == "gather":
         # untimed: the strips collected on rank 0 (every rank's own rows) must equal ONE device's comparison of all rows
         # over the gathered keys (that single-device result is what the gpu tests hold against the oracle)
         try:
@@ -773,7 +796,7 @@ def main():
 
     # BASELINE configs[3] over the ranks of this job (every rank takes part; rank 0 reports)
     c4_dist = None
-    if use_dist and not args.no_extras:          # (BENCH_FORCE_DIST=1: also with ONE rank -- the RCCL calls of the leg on a one-GPU box)
+    if args.full and use_dist and not args.no_extras:          # (BENCH_FORCE_DIST=1: also with ONE rank -- the RCCL calls of the leg on a one-GPU machine)
         try:
             c4_dist = compare_config4_dist(ctx_full, dev, full_stream, rank, world, backend)
         except Exception as e:  # noqa: BLE001
@@ -850,117 +873,118 @@ def main():
                          "step_achieved": step_achieved, "step_frac": step_achieved / HBM_PEAK_GBS},
         }
         out["roofline"].update(pmc_traffic(args, "k_dense_pair"))
-        # the same kernel with the GPU to itself (dense stage only, untimed extra): what the kernel reaches when nothing
-        # shares its CUs -- `achieved` above is measured inside the pipelined step, beside the other streams' kernels.
-        # Like the steps, consecutive launches read different batches.
-        n_b = d_bases.numel()
-        try:
-            ctx.timing_enable(True, sp.TIME_DENSE)
-            ctx.timing_read()
-            for i in range(21):
-                ctx.scan_hits_device(p, d_batches[i % n_batches].data_ptr(), n_b)
-            ta = ctx.timing_read()
-            ctx.timing_enable(False)
-            alone_ms = ta["dense_ms"] / max(1, ta["dense_launches"])
-            out["roofline"]["alone"] = {"dense_kernel_ms": alone_ms, "achieved": n_b / 1e9 / (alone_ms / 1e3),
-                                        "frac": n_b / 1e9 / (alone_ms / 1e3) / HBM_PEAK_GBS, "launches": int(ta["dense_launches"])}
-        except Exception as e:  # noqa: BLE001
-            out["roofline"]["alone"] = {"error": repr(e)}
-        # ... on the whole chip (context without CU mask), ASCII and 2-bit input (SURVEY.md 8d's second byte model: the
-        # same positions from a quarter of the bytes -- that form is bound by the LDS table reads, not by HBM)
-        try:
-            out["roofline"]["whole_chip"] = {}
-            ctx_full.set_cu_count(0, 2)
-            torch.cuda.synchronize()
-            packed = []                                   # one packed copy per batch (125 MB each: ONE would sit in the Infinity Cache)
-            for t in d_batches:
-                d_pk = ctx_full.pack_bases_device(t.data_ptr(), n_b)
-                packed.append(device_bytes_as_tensor(d_pk, (n_b + 15) // 16 * 4 + 256, dev).clone())
-            torch.cuda.synchronize()
-            for name, srcs, flg, bpp in (("ascii", [t.data_ptr() for t in d_batches], 0, 1.0),
-                                         ("packed_2bit", [t.data_ptr() for t in packed], sp.SPSP_SCAN_PACKED_INPUT, 0.25)):
-                pw = sp.make_params(K, M, S, flags=flags | flg)
-                ctx_full.scan_hits_device(pw, srcs[0], n_b)
-                ctx_full.timing_enable(True, sp.TIME_DENSE)
-                ctx_full.timing_read()
-                for i in range(21):
-                    ctx_full.scan_hits_device(pw, srcs[i % len(srcs)], n_b)
-                tw = ctx_full.timing_read()
-                ctx_full.timing_enable(False)
-                ms_w = tw["dense_ms"] / max(1, tw["dense_launches"])
-                gbs = bpp * n_b / 1e9 / (ms_w / 1e3)
-                out["roofline"]["whole_chip"][name] = {"dense_kernel_ms": ms_w, "positions_per_s": n_b / (ms_w / 1e3),
-                                                       "byte_model": "%g B per m-mer position" % bpp, "achieved": gbs, "frac": gbs / HBM_PEAK_GBS}
-            del packed
-            ctx_full.set_cu_count(0, 1)
-        except Exception as e:  # noqa: BLE001
-            out["roofline"]["whole_chip"] = {"error": repr(e)}
-        # the roofline's denominator measured on this box in this process: streaming copy and streaming read
-        # of 2 x 1 GiB on the whole chip, and on the CUs the dense stream owns inside the step
-        try:
-            torch.cuda.synchronize()
-            pm = ctx_full.measure_hbm(1 << 30, 10)
-            rl = out["roofline"]
-            rl["peak_measured"] = {"copy_GBps": pm["copy_GBps"], "read_GBps": pm["read_GBps"], "bytes_per_buffer": pm["bytes"], "launches": pm["reps"],
-                                   "kernels": "k_measure_copy / k_measure_read (non-temporal 16-byte loads and stores, 2 x 1024 lanes per CU), "
-                                              "HIP events, after two warm-up launches; copy counts bytes read + written"}
-            if schedule == "partition" and pipelined:
-                pd = ctx.measure_hbm(1 << 30, 10)
-                rl["peak_measured"]["dense_stream"] = {"n_cu": pd["n_cu"], "copy_GBps": pd["copy_GBps"], "read_GBps": pd["read_GBps"]}
-            rl["frac_of_measured_copy"] = achieved / pm["copy_GBps"]
-            rl["frac_of_measured_read"] = achieved / pm["read_GBps"]
-            rl["step_frac_of_measured_read"] = step_achieved / pm["read_GBps"]
-        except Exception as e:  # noqa: BLE001
-            out["roofline"]["peak_measured"] = {"error": repr(e)}
         out["roofline"].update(sq_counters("k_dense_pair", dense_avg_ms, dense_cus if (schedule == "partition" and pipelined) else 0))
-        d_parity = d_inter
-        if device_keys:
-            # untimed: the step's own path once more over batch 0 -- scan -> keys on the device -> comparison -- on the whole-device
-            # context; its keys must equal those parsed from the setup's sketch payloads (what the comparator reads from files)
-            # and its pair matrix goes to the oracle check below
+        if args.full:
+            # the same kernel with the GPU to itself (dense stage only, untimed extra): what the kernel reaches when nothing
+            # shares its CUs -- `achieved` above is measured inside the pipelined step, beside the other streams' kernels.
+            # Like the steps, consecutive launches read different batches.
+            n_b = d_bases.numel()
+            try:
+                ctx.timing_enable(True, sp.TIME_DENSE)
+                ctx.timing_read()
+                for i in range(21):
+                    ctx.scan_hits_device(p, d_batches[i % n_batches].data_ptr(), n_b)
+                ta = ctx.timing_read()
+                ctx.timing_enable(False)
+                alone_ms = ta["dense_ms"] / max(1, ta["dense_launches"])
+                out["roofline"]["alone"] = {"dense_kernel_ms": alone_ms, "achieved": n_b / 1e9 / (alone_ms / 1e3),
+                                            "frac": n_b / 1e9 / (alone_ms / 1e3) / HBM_PEAK_GBS, "launches": int(ta["dense_launches"])}
+            except Exception as e:  # noqa: BLE001
+                out["roofline"]["alone"] = {"error": repr(e)}
+            # ... on the whole chip (context without CU mask), ASCII and 2-bit input (SURVEY.md 8d's second byte model: the
+            # same positions from a quarter of the bytes -- that form is bound by the LDS table reads, not by HBM)
+            try:
+                out["roofline"]["whole_chip"] = {}
+                ctx_full.set_cu_count(0, 2)
+                torch.cuda.synchronize()
+                packed = []                                   # one packed copy per batch (125 MB each: ONE would sit in the Infinity Cache)
+                for t in d_batches:
+                    d_pk = ctx_full.pack_bases_device(t.data_ptr(), n_b)
+                    packed.append(device_bytes_as_tensor(d_pk, (n_b + 15) // 16 * 4 + 256, dev).clone())
+                torch.cuda.synchronize()
+                for name, srcs, flg, bpp in (("ascii", [t.data_ptr() for t in d_batches], 0, 1.0),
+                                             ("packed_2bit", [t.data_ptr() for t in packed], sp.SPSP_SCAN_PACKED_INPUT, 0.25)):
+                    pw = sp.make_params(K, M, S, flags=flags | flg)
+                    ctx_full.scan_hits_device(pw, srcs[0], n_b)
+                    ctx_full.timing_enable(True, sp.TIME_DENSE)
+                    ctx_full.timing_read()
+                    for i in range(21):
+                        ctx_full.scan_hits_device(pw, srcs[i % len(srcs)], n_b)
+                    tw = ctx_full.timing_read()
+                    ctx_full.timing_enable(False)
+                    ms_w = tw["dense_ms"] / max(1, tw["dense_launches"])
+                    gbs = bpp * n_b / 1e9 / (ms_w / 1e3)
+                    out["roofline"]["whole_chip"][name] = {"dense_kernel_ms": ms_w, "positions_per_s": n_b / (ms_w / 1e3),
+                                                           "byte_model": "%g B per m-mer position" % bpp, "achieved": gbs, "frac": gbs / HBM_PEAK_GBS}
+                del packed
+                ctx_full.set_cu_count(0, 1)
+            except Exception as e:  # noqa: BLE001
+                out["roofline"]["whole_chip"] = {"error": repr(e)}
+            # the roofline's denominator measured on this GPU in this process: streaming copy and streaming read
+            # of 2 x 1 GiB on the whole chip, and on the CUs the dense stream owns inside the step
             try:
                 torch.cuda.synchronize()
-                d_o, n_o = ctx_full.scan_device(*scan_args[0])
-                # (sorted form here: the arrays can be held against the parsed sketches element by element)
-                kmn, klo, _, koff = ctx_full.sketch_keys_device(p, scan_args[0][1], scan_args[0][2], d_off.data_ptr(), d_o, n_o, first_rec)
-                same = bool((koff == sk_off).all())
-                if same:
-                    tot = int(koff[-1])
-                    same = bool(torch.equal(device_bytes_as_tensor(kmn, 4 * tot, dev), d_all_min.view(torch.uint8)) and
-                                torch.equal(device_bytes_as_tensor(klo, 8 * tot, dev), d_all_lo.view(torch.uint8)))
-                d_parity = torch.zeros_like(d_inter)
-                torch.cuda.synchronize()
-                ctx_full.compare_device(K, kmn, klo, None, koff, n_total, 0, 1, d_parity.data_ptr())
-                torch.cuda.synchronize()
-                out["device_keys"] = {"in_timed_step": True, "keys_per_step": last.get("keys_total"),
-                                      "equal_to_keys_parsed_from_sketch_payloads": same,
-                                      "what": "spsp_sketch_keys_device: scan output -> sorted distinct (minimizer, canonical k-mer) keys per genome "
-                                              "(handle_superkmer's uint8 counts, the emission / reader round trip and canonize composed, "
-                                              "SubSampler.cpp:243-302,458-620, Comparator.cpp:186-260); the comparison of a step works on the "
-                                              "keys of the scan this slot collected two steps earlier"}
+                pm = ctx_full.measure_hbm(1 << 30, 10)
+                rl = out["roofline"]
+                rl["peak_measured"] = {"copy_GBps": pm["copy_GBps"], "read_GBps": pm["read_GBps"], "bytes_per_buffer": pm["bytes"], "launches": pm["reps"],
+                                       "kernels": "k_measure_copy / k_measure_read (non-temporal 16-byte loads and stores, 2 x 1024 lanes per CU), "
+                                                  "HIP events, after two warm-up launches; copy counts bytes read + written"}
+                if schedule == "partition" and pipelined:
+                    pd = ctx.measure_hbm(1 << 30, 10)
+                    rl["peak_measured"]["dense_stream"] = {"n_cu": pd["n_cu"], "copy_GBps": pd["copy_GBps"], "read_GBps": pd["read_GBps"]}
+                rl["frac_of_measured_copy"] = achieved / pm["copy_GBps"]
+                rl["frac_of_measured_read"] = achieved / pm["read_GBps"]
+                rl["step_frac_of_measured_read"] = step_achieved / pm["read_GBps"]
             except Exception as e:  # noqa: BLE001
-                out["device_keys"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(recs, payloads, p, int(n_out), d_parity)
-        if world == 1 and not args.no_extras:
-            try:
-                out["compare"] = compare_config3(ctx_full, dev, args.no_cpu_baseline)
-            except Exception as e:  # noqa: BLE001 -- an extra must not take the headline down
-                out["compare"] = {"error": repr(e)}
-            try:
-                out["end_to_end"] = end_to_end(ctx_full, args.no_cpu_baseline, genomes)
-            except Exception as e:  # noqa: BLE001
-                out["end_to_end"] = {"error": repr(e)}
-            del d_batches[1:]                              # room (and a quiet card) for the two large legs
-            pk = out["roofline"].get("peak_measured", {})
-            try:
-                out["compare_c4"] = compare_config4(ctx_full, dev, args.no_cpu_baseline, pk)
-            except Exception as e:  # noqa: BLE001
-                out["compare_c4"] = {"error": repr(e)}
-            try:
-                out["scan_c5"] = scan_config5(ctx_full, dev, args.no_cpu_baseline, pk)
-            except Exception as e:  # noqa: BLE001
-                out["scan_c5"] = {"error": repr(e)}
+                out["roofline"]["peak_measured"] = {"error": repr(e)}
+            d_parity = d_inter
+            if device_keys:
+                # untimed: the step's own path once more over batch 0 -- scan -> keys on the device -> comparison -- on the whole-device
+                # context; its keys must equal those parsed from the setup's sketch payloads (what the comparator reads from files)
+                # and its pair matrix goes to the oracle check below
+                try:
+                    torch.cuda.synchronize()
+                    d_o, n_o = ctx_full.scan_device(*scan_args[0])
+                    # (sorted form here: the arrays can be held against the parsed sketches element by element)
+                    kmn, klo, _, koff = ctx_full.sketch_keys_device(p, scan_args[0][1], scan_args[0][2], d_off.data_ptr(), d_o, n_o, first_rec)
+                    same = bool((koff == sk_off).all())
+                    if same:
+                        tot = int(koff[-1])
+                        same = bool(torch.equal(device_bytes_as_tensor(kmn, 4 * tot, dev), d_all_min.view(torch.uint8)) and
+                                    torch.equal(device_bytes_as_tensor(klo, 8 * tot, dev), d_all_lo.view(torch.uint8)))
+                    d_parity = torch.zeros_like(d_inter)
+                    torch.cuda.synchronize()
+                    ctx_full.compare_device(K, kmn, klo, None, koff, n_total, 0, 1, d_parity.data_ptr())
+                    torch.cuda.synchronize()
+                    out["device_keys"] = {"in_timed_step": True, "keys_per_step": last.get("keys_total"),
+                                          "equal_to_keys_parsed_from_sketch_payloads": same,
+                                          "what": "spsp_sketch_keys_device: scan output -> sorted distinct (minimizer, canonical k-mer) keys per genome "
+                                                  "(handle_superkmer's uint8 counts, the emission / reader round trip and canonize composed, "
+                                                  "SubSampler.cpp:243-302,458-620, Comparator.cpp:186-260); the comparison of a step works on the "
+                                                  "keys of the scan this slot collected two steps earlier"}
+                except Exception as e:  # noqa: BLE001
+                    out["device_keys"] = {"error": repr(e)}
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(recs, payloads, p, int(n_out), d_parity)
+            if world == 1 and not args.no_extras:
+                try:
+                    out["compare"] = compare_config3(ctx_full, dev, args.no_cpu_baseline)
+                except Exception as e:  # noqa: BLE001 -- an extra must not take the headline down
+                    out["compare"] = {"error": repr(e)}
+                try:
+                    out["end_to_end"] = end_to_end(ctx_full, args.no_cpu_baseline, genomes)
+                except Exception as e:  # noqa: BLE001
+                    out["end_to_end"] = {"error": repr(e)}
+                del d_batches[1:]                              # room (and a quiet card) for the two large legs
+                pk = out["roofline"].get("peak_measured", {})
+                try:
+                    out["compare_c4"] = compare_config4(ctx_full, dev, args.no_cpu_baseline, pk)
+                except Exception as e:  # noqa: BLE001
+                    out["compare_c4"] = {"error": repr(e)}
+                try:
+                    out["scan_c5"] = scan_config5(ctx_full, dev, args.no_cpu_baseline, pk)
+                except Exception as e:  # noqa: BLE001
+                    out["scan_c5"] = {"error": repr(e)}
         if c4_dist is not None:
             out["compare_c4"] = c4_dist
         sys.stdout.flush()
@@ -985,6 +1009,43 @@ def device_bytes_as_tensor(ptr, nbytes, dev):
     class _Arr:
         __cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
     return torch.as_tensor(_Arr(), device=dev)
+
+
+def rows_within(a, max_bytes, seed):
+    """`a`, or a fixed, seeded sample of its rows (kept in their order) when it is larger than max_bytes"""
+    keep = max(1, max_bytes // max(1, a.nbytes // max(1, len(a))))
+    if len(a) <= keep:
+        return a
+    return a[np.sort(np.random.default_rng(seed).choice(len(a), size=keep, replace=False))]
+
+
+def dump_outputs(out_dir, ctx, last, keys_last, d_inter):
+    """--dump-outputs: what the last timed step computed, as a caller of the step's path receives it, in float64 (every
+    value is an integer below 2^53, so exact; a 62-bit k-mer goes as two 32-bit halves):
+      superkmers.npy       [n, 5]  the scan's super-k-mers of the step's batch: rec, minimizer, start, len, rev, in (rec, start) order
+      keys.npy             [n, 4]  the comparator's keys made on the device from that scan (closed step only): genome, minimizer,
+                                   kmer_lo >> 32, kmer_lo & 0xffffffff -- distinct per genome in no set order, so sorted here
+      keys_per_genome.npy  [G]     the number of keys of every genome (closed step only)
+      pair_matrix.npy      [N, N]  the pair matrix of the step's comparison (cell i < j: keys sketches i and j share)
+    At most 64 MB in all: an array beyond its share is a fixed, seeded sample of its rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    sk = ctx.to_host(last["d_out"], int(last["n_out"]), sp.SUPERKMER_DTYPE) if last["d_out"] else np.zeros(0, sp.SUPERKMER_DTYPE)
+    sk = sk[np.lexsort((sk["start"], sk["rec"]))]
+    arrays["superkmers"] = rows_within(np.stack([sk[f].astype(np.float64) for f in sk.dtype.names], 1), 16 << 20, 1)
+    if keys_last is not None:
+        kctx, (d_mn, d_lo, _, koff) = keys_last
+        tot = int(koff[-1])
+        mn, lo = kctx.to_host(d_mn, tot, np.uint32), kctx.to_host(d_lo, tot, np.uint64)
+        genome = np.repeat(np.arange(len(koff) - 1), np.diff(koff.astype(np.int64)))
+        o = np.lexsort((lo, mn, genome))
+        keys = np.stack([genome[o], mn[o], lo[o] >> np.uint64(32), lo[o] & np.uint64(0xFFFFFFFF)], 1).astype(np.float64)
+        arrays["keys"] = rows_within(keys, 30 << 20, 2)
+        arrays["keys_per_genome"] = rows_within(np.diff(koff.astype(np.int64)).astype(np.float64), 1 << 20, 3)
+    arrays["pair_matrix"] = rows_within(d_inter.cpu().numpy().view(np.uint32).astype(np.float64), 16 << 20, 4)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs of the last step -> %s: %s" % (out_dir, ", ".join("%s %s" % (n, list(a.shape)) for n, a in arrays.items())))
 
 
 def sq_counters(kernel, kernel_ms, n_cu, default_file="r05_pmc_sq_bench.json"):

@@ -79,7 +79,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     # the PLAIN command of the driver (`python bench.py --gpus N ...`, no WORLD_SIZE): bench.py starts its two ranks itself,
     # as child processes through torch.distributed.run, before it touches the GPU
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--genomes", "6", "--length", "300000", "--no-cpu-baseline"]
+           "--genomes", "6", "--length", "300000", "--no-cpu-baseline", "--full"]
     env["BENCH_C4_SKETCHES"] = "400"                         # the multi-rank configs[3] leg at a rehearsal's size
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]

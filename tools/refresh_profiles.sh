@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX (via gpurun) from the repo root: refreshes gpurun_out/prof_<tag>/ with
-#   bench    bench line (plain run), kernel-trace summary of the same command, bench line under rocprof,
+#   bench    bench line (--full run), kernel-trace summary of the same command, bench line under rocprof,
 #            FETCH_SIZE / WRITE_SIZE PMC passes (separate runs), the SQ counters of the dense kernel
 #   compare  the same for the comparator at BASELINE configs[2], true shape (tools/c3_compare.py 1000)
 #   c4       ... at configs[3] scale on one GPU (tools/c4_compare.py 10000)
@@ -33,7 +33,7 @@ sq_sets() {
   done
 }
 if [ "$what" = all ] || [ "$what" = bench ]; then
-timeout -k 10 900 python3 $R/bench.py > $out/bench_line.json 2> $out/bench.err || exit 1
+timeout -k 10 900 python3 $R/bench.py --full > $out/bench_line.json 2> $out/bench.err || exit 1
 echo "bench line done"
 rm -rf /tmp/kt && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o r -- python3 $R/bench.py --no-cpu-baseline --no-extras > $out/bench_line_under_rocprof.json 2>/dev/null || exit 1
 kt=$(find /tmp/kt -name "*kernel_trace.csv"); ks=$(find /tmp/kt -name "*kernel_stats.csv")
