@@ -1649,14 +1649,12 @@ static int launch_accumulate_sparse(spsp_ctx* ctx, const ComparePlan& P, uint32_
     uint32_t copies_log2 = 0;                                // as many copies of the counters as 64 KiB of LDS hold, up to 16
     while (copies_log2 < 4 && ((size_t)cols << (copies_log2 + 1)) * 4 <= (size_t)kSparseCols * 4) ++copies_log2;
     // rows of one family behind one L2 (see the kernel): when a row is ONE workgroup and there are rows enough to fill the chip
-    static const char* dbg_xcd = getenv("SPSP_DEBUG_ACC_XCD");     // "0": rows in launch order (A/B, profiles/r04_acc_xcd.md)
     const uint32_t col_blocks = (P.n + cols - 1) / cols;
-    const bool by_xcd = col_blocks == 1 && split == 1 && P.n_own >= 512 && !(dbg_xcd && dbg_xcd[0] == '0');
+    const bool by_xcd = col_blocks == 1 && split == 1 && P.n_own >= 512;
     const uint32_t xcd_rows = by_xcd ? (P.n_own + 7) / 8 : 0u;
     // 16-bit counters when no row can make one overflow: half the LDS per workgroup -> twice the rows in flight per CU (the
     // kernel waits on two dependent random reads per key: more rows in flight is more of them in flight)
-    static const char* dbg_half = getenv("SPSP_DEBUG_ACC_HALF");   // "0": 32-bit counters (A/B)
-    const bool half = split == 1 && P.max_row > 0 && (P.max_row <= kLongRow || long_limit) && !(dbg_half && dbg_half[0] == '0');
+    const bool half = split == 1 && P.max_row > 0 && (P.max_row <= kLongRow || long_limit);
     // (256-lane workgroups for short rows were measured for the key-partitioned ranks' ~600-key rows: 0.178 -> 0.192 ms -- a row's fixed
     // cost is clearing and scanning its N counters, which takes four times as many rounds with a quarter of the lanes; not kept)
     auto kern = half ? &k_accumulate_sparse<true, false, kSparseThreads> : &k_accumulate_sparse<false, false, kSparseThreads>;
@@ -1666,9 +1664,10 @@ static int launch_accumulate_sparse(spsp_ctx* ctx, const ComparePlan& P, uint32_
     // ... and, when the rows are SHORT (a key-partitioned rank's: ~600 keys of each of 10 000 sketches), by workgroups of 256 lanes
     // that stay and take row after row, a row costing what it touches (TOUCH, see the kernel): 0.204 -> 0.161 ms for such a rank.
     // Long rows keep a workgroup each: noting first touches takes LDS adds that RETURN, ~20 per key, and a 4 800-key row's clear
-    // and scan are little beside its keys (configs[3] all-vs-all as cells: 0.775 ms against 0.95 with 1 024 lanes staying, 1.14 with 256)
-    static const char* dbg_touch = getenv("SPSP_DEBUG_ACC_TOUCH");   // "0": never; "s" / "l": always, 256 / 1 024 lanes (A/B, tests)
-    const bool touch_forced = dbg_touch && (dbg_touch[0] == 's' || dbg_touch[0] == 'l');
+    // and scan are little beside its keys (configs[3] all-vs-all as cells: 0.775 ms against 0.95 with 1 024 lanes staying, 1.14 with 256;
+    // the 1 024-lane staying form has since been removed)
+    static const char* dbg_touch = getenv("SPSP_DEBUG_ACC_TOUCH");   // "0": never; "s": always (A/B, tests)
+    const bool touch_forced = dbg_touch && dbg_touch[0] == 's';
     const bool touch = direct && half && col_blocks == 1 && !(dbg_touch && dbg_touch[0] == '0') && (per_row <= 2048 || touch_forced);
     const uint32_t rows_y = by_xcd ? xcd_rows * 8 : P.n_own;
     uint32_t grid_y = rows_y, threads = kSparseThreads;
@@ -1679,12 +1678,11 @@ static int launch_accumulate_sparse(spsp_ctx* ctx, const ComparePlan& P, uint32_
         copies_log2 = 0;
         while (copies_log2 < 4 && ((size_t)cols << (copies_log2 + 1)) * 2 <= 32u * 1024u) ++copies_log2;
         lds = ((size_t)cols << copies_log2) * 2;
-        const bool small_wg = !(dbg_touch && dbg_touch[0] == 'l');
-        threads = small_wg ? 256 : kSparseThreads;
-        const uint32_t per_cu = small_wg ? (uint32_t)std::min<size_t>(8, (160u * 1024u) / (lds + kTouchCap * 4 + 512)) : 2u;
+        threads = 256;
+        const uint32_t per_cu = (uint32_t)std::min<size_t>(8, (160u * 1024u) / (lds + kTouchCap * 4 + 512));
         grid_y = std::min(rows_y, std::max(8u, (uint32_t)ctx->n_cu * std::max(1u, per_cu)) & ~7u);
         if (grid_y < 8 || (grid_y & 7u)) grid_y = rows_y;                                        // (fewer than eight rows: one workgroup each)
-        kern = small_wg ? &k_accumulate_sparse<true, true, 256> : &k_accumulate_sparse<true, true, kSparseThreads>;
+        kern = &k_accumulate_sparse<true, true, 256>;
     }
     hipLaunchKernelGGL(kern, dim3(col_blocks, grid_y, split), dim3(threads), lds, ctx->stream,
                        P.list_ref ? P.list_ref : ctx->c_row.as<uint32_t>(), P.where, ctx->c_matrix.as<uint16_t>(), P.sk_begin, P.sk_end,
@@ -1730,15 +1728,12 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
                        J.small ? J.P.d_inter : (uint32_t*)nullptr, J.small ? J.P.n : 0u,
                        J.filtered ? ctx->c_filter.as<uint4>() : (uint4*)nullptr, filter_vec);
     SPSP_HIP(hipGetLastError());
-    // analysis hook (results are wrong with it): leave stages out to see what each costs a kernel of another stream
-    static const int skip = getenv("SPSP_DEBUG_SKIP_STAGES") ? atoi(getenv("SPSP_DEBUG_SKIP_STAGES")) : 0;
     if ((rc = ctx->ev_begin(kEvScatter))) return rc;
     if (J.filtered && (rc = J.build_filter(J.filter_words - 1))) return rc;
     if (J.spill.room && !J.small && (rc = J.spill_parts(J.n_parts, J.spill, 0, J.classes, J.cls))) return rc;
     // rows of similar sketches side by side for the row sums (their holder lists meet in one L2), whatever order the sketches
     // came in: every sketch's smallest key hash from the records of the first parts (k_row_signature), the order they give
-    // (k_row_order).  SPSP_DEBUG_ROW_ORDER=0: launch order, 2: an order for every comparison
-    static const char* dbg_order = getenv("SPSP_DEBUG_ROW_ORDER");
+    // (k_row_order).
     const bool all_rows = J.P.row_first == 0 && J.P.row_stride == 1 && J.P.row_limit >= J.P.n && J.P.n_own == J.P.n;
     // (what a context learnt holds for the collection it learnt it on: another one -- other offsets -- is looked at afresh)
     if (ctx->h_skoff) {
@@ -1746,13 +1741,13 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
                             ctx->h_skoff[J.P.n / 2] * 0x27D4EB2F165667C5ULL ^ ctx->h_skoff[J.P.n - J.P.n / 3] * 0x85EBCA77C2B2AE63ULL;
         if (fp != ctx->learnt_on) { ctx->learnt_on = fp; ctx->order_quiet = 0; ctx->multi_quiet = 0; }   // (spsp_compare_forget resets all of it)
     }
-    bool ordered = !J.small && all_rows && J.P.n >= (dbg_order && dbg_order[0] == '2' ? 512u : 2048u) && J.P.n <= (uint32_t)kSparseCols && !(dbg_order && dbg_order[0] == '0');
+    bool ordered = !J.small && all_rows && J.P.n >= 2048u && J.P.n <= (uint32_t)kSparseCols;
     // (a context whose last comparison came in a good order of its own -- k_row_order's verdict, read back with the job -- skips
     // the making of the order for the next 63: collections are compared batch after batch of the same kind)
-    if (ordered && ctx->order_quiet > 0 && !(dbg_order && dbg_order[0] == '2')) { --ctx->order_quiet; ordered = false; }
+    if (ordered && ctx->order_quiet > 0) { --ctx->order_quiet; ordered = false; }
     J.ordered = ordered;
     if (ordered && ((rc = ctx->c_sig.reserve((size_t)J.P.n * 8)) || (rc = ctx->c_order.reserve((size_t)J.P.n * 4)))) return rc;
-    if (!(skip & 1) && (rc = J.scatter_parts(J.n_parts, J.small, J.filtered, J.filter_words - 1, J.classes, J.cls))) return rc;
+    if ((rc = J.scatter_parts(J.n_parts, J.small, J.filtered, J.filter_words - 1, J.classes, J.cls))) return rc;
     if (ordered) {
         const hipStream_t side = ctx->stream;          // (on a stream of their own, beside the grouping kernel, these three short launches cost the same 0.06 ms: measured)
         SPSP_HIP(hipMemsetAsync(ctx->c_sig.p, 0xff, (size_t)J.P.n * 8, side));
@@ -1778,7 +1773,7 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
     if (dbg_multi && dbg_multi[0] == '0') J.want_multi = false;
     else if (dbg_multi && dbg_multi[0] == '1') {}
     else if (J.want_multi && ctx->multi_quiet > 0) { --ctx->multi_quiet; J.want_multi = false; }
-    if (!(skip & 2) && (rc = J.small ? J.group_small(J.n_parts) : J.group_parts(J.n_parts, J.spill, J.want_multi))) return rc;
+    if ((rc = J.small ? J.group_small(J.n_parts) : J.group_parts(J.n_parts, J.spill, J.want_multi))) return rc;
     if (J.spill.room && !J.small && (rc = J.spill_parts(J.n_parts, J.spill, 1, J.classes, J.cls))) return rc;
     if ((rc = ctx->ev_end(kEvGroup))) return rc;
     if (J.small) return job_queue_flags(ctx);             // (no later kernel forwards the flags)
@@ -1791,7 +1786,7 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
     // (an attempt whose parts overflow leaves this kernel at its first line, before any cell is emitted: the retry emits them once)
     // (with a spill the keys that have columns add into the dense matrix behind the row sums: no cells straight from them)
     //  -- nor with key classes: a pair's count comes in several parts)
-    if (!(skip & 4) && (rc = launch_accumulate_sparse(ctx, PP, flags, J.spill.room == 0 && J.classes == 1, J.cls > 0))) return rc;
+    if ((rc = launch_accumulate_sparse(ctx, PP, flags, J.spill.room == 0 && J.classes == 1, J.cls > 0))) return rc;
     if (J.spill.room && J.spill.t_bits != 0xffffffffu) {
         const uint32_t tiles = (J.P.n + kPairTile - 1) / kPairTile;
         hipLaunchKernelGGL(k_spill_pairs, dim3((tiles * (tiles + 1) / 2 + 7) / 8 * 8), dim3(kPairThreads), 0, ctx->stream, ctx->c_bits.as<unsigned long long>(),

@@ -380,8 +380,7 @@ int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, con
         struct Run { const uint8_t* host; uint64_t dev, bytes; };
         std::vector<Run> runs;
         {
-            static const bool allow = getenv("SPSP_DEBUG_DECODE_GATHER") == nullptr;
-            bool ok = allow;
+            bool ok = true;
             for (uint32_t i = 0; i < n && ok; ++i) {
                 if (!lens[i]) continue;
                 if (!runs.empty() && payloads[i] == runs.back().host + (text_off_dev[i] - runs.back().dev)) runs.back().bytes = text_off_dev[i] + lens[i] - runs.back().dev;

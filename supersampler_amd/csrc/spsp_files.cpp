@@ -68,37 +68,23 @@ int spsp_sketch_file(spsp_ctx* ctx, const spsp_params* p, double rate, const cha
     uint8_t* text = nullptr; uint64_t tlen = 0;
     bool text_owned = false;
     double t0 = now_s();
-    static const bool host_ingest = getenv("SPSP_HOST_INGEST") != nullptr;   // A/B switch: clean on the host, scan on the GPU
-    int rc;
-    if (host_ingest) { rc = spsp_read_file_host(fasta_path, &text, &tlen); text_owned = true; }
-    else {
-        SPSP_HIP(hipSetDevice(ctx->device));
-        rc = slurp_pinned(ctx, fasta_path, &tlen);
-        if (rc == 1) {                                               // packed: inflate out of the pinned copy
-            std::vector<uint8_t> plain;
-            rc = inflate_all(ctx->h_text, tlen, plain);
-            if (!rc) {
-                text = (uint8_t*)malloc(plain.size() + 64);
-                if (!text) { set_error("out of host memory"); rc = SPSP_ERR_NOMEM; }
-                else { if (!plain.empty()) memcpy(text, plain.data(), plain.size()); tlen = plain.size(); text_owned = true; }
-            }
-        } else if (rc == 0) text = ctx->h_text;
-    }
+    SPSP_HIP(hipSetDevice(ctx->device));
+    int rc = slurp_pinned(ctx, fasta_path, &tlen);
+    if (rc == 1) {                                                   // packed: inflate out of the pinned copy
+        std::vector<uint8_t> plain;
+        rc = inflate_all(ctx->h_text, tlen, plain);
+        if (!rc) {
+            text = (uint8_t*)malloc(plain.size() + 64);
+            if (!text) { set_error("out of host memory"); rc = SPSP_ERR_NOMEM; }
+            else { if (!plain.empty()) memcpy(text, plain.data(), plain.size()); tlen = plain.size(); text_owned = true; }
+        }
+    } else if (rc == 0) text = ctx->h_text;
     if (rc) return rc;
     ctx->stages.read_s += now_s() - t0;
     ctx->stages.sketch_files += 1;
     uint8_t* payload = nullptr; uint64_t plen = 0;
-    if (host_ingest) {
-        uint8_t* bases = nullptr; uint64_t* off = nullptr; uint32_t n_rec = 0;
-        rc = spsp_fasta_clean_host((const char*)text, tlen, &bases, &off, &n_rec);
-        spsp_superkmer* sk = nullptr; uint64_t n_sk = 0;
-        if (!rc) rc = spsp_scan(ctx, p, bases, off, n_rec, &sk, &n_sk);
-        if (!rc) rc = spsp_sketch_build_host(p, rate, bases, off, n_rec, sk, n_sk, &payload, &plen, stats);
-        free(bases); free(off); free(sk);
-    } else {
-        // ingest (getLineFasta + clean_dna), scan and super-k-mer gather all run on the GPU
-        rc = spsp_sketch_text(ctx, p, rate, (const char*)text, tlen, &payload, &plen, stats);
-    }
+    // ingest (getLineFasta + clean_dna), scan and super-k-mer gather all run on the GPU
+    rc = spsp_sketch_text(ctx, p, rate, (const char*)text, tlen, &payload, &plen, stats);
     if (text_owned) free(text);
     if (rc) { free(payload); return rc; }
     t0 = now_s();
@@ -108,8 +94,8 @@ int spsp_sketch_file(spsp_ctx* ctx, const spsp_params* p, double rate, const cha
     return rc;
 }
 
-// File-of-files loop, one context per worker and one GPU job per file (spsp_sketch_file): the form used with -a > 1 (the
-// abundance pass counts k-mers per file) and as the A/B partner of the batched pipeline below (SPSP_FILES_PER_WORKER=1).
+// File-of-files loop, one context per worker and one GPU job per file (spsp_sketch_file): the form for an empty list, and
+// for -a > 1 under SPSP_DEBUG_ABUND_PER_FILE (the abundance pass counts k-mers per file, as it did until round 5).
 static int sketch_files_per_worker(const std::vector<int>& devices, const spsp_params* p, double rate, const char* const* fasta_paths, const char* const* out_paths,
                       uint32_t n, uint32_t threads, spsp_file_callback cb, void* user, spsp_stage_times* times) {
     if (!p || (n && (!fasta_paths || !out_paths))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
@@ -438,8 +424,8 @@ private:
         // PCIe copy runs beside the reads of the other tasks instead of behind all of them (one 4 GB FASTA file: 0.078 s of reading
         // and 0.076 s of copying, one after the other)
         s.d_text = nullptr;
-        static const bool copy_late = getenv("SPSP_DEBUG_COPY_LATE") != nullptr;     // A/B: one copy per batch, in the GPU stage
-        if (s.total && !copy_late) {
+        // (when the room cannot be had, the GPU stage copies the whole batch itself)
+        if (s.total) {
             (void)hipSetDevice(s.device);
             if (s.ctx->i_text.reserve((size_t)s.total + 64) == SPSP_OK) s.d_text = s.ctx->i_text.as<uint8_t>();
         }
@@ -766,9 +752,8 @@ int spsp_sketch_files_multi(const int* devices, uint32_t n_dev, const spsp_param
     const int rc0 = spsp::check_params(p);
     if (rc0) return rc0;
     if (threads == 0) threads = 1;
-    static const bool per_worker = getenv("SPSP_FILES_PER_WORKER") != nullptr;   // A/B switch: one GPU job per file
     static const bool abund_per_file = getenv("SPSP_DEBUG_ABUND_PER_FILE") != nullptr;   // A/B: -a > 1 as one GPU job per file (the form until round 5)
-    if (per_worker || (p->abundance > 1 && abund_per_file) || n == 0)
+    if ((p->abundance > 1 && abund_per_file) || n == 0)
         return sketch_files_per_worker(device, p, rate, fasta_paths, out_paths, n, threads, cb, user, times);
     if (times) memset(times, 0, sizeof *times);
     FilePipeline pipe(device, p, rate, fasta_paths, out_paths, n, threads, cb, user);

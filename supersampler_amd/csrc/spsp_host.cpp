@@ -1427,7 +1427,6 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
     double t0 = now_s(), t1;
     const double t_start = t0;
     ctx->stages.compare_calls += 1;
-    static const bool host_decode = getenv("SPSP_HOST_DECODE") != nullptr;   // A/B switch: decode + sort on host threads
     std::vector<uint8_t*> datas(n, nullptr);
     std::vector<uint64_t> lens(n, 0);
     std::vector<int> rcs(n, SPSP_OK);
@@ -1565,54 +1564,7 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
     std::vector<uint64_t> cells;                              // ... or no matrix at all: a large comparison comes back as its non-zero cells
     bool as_cells = false;
     std::vector<uint64_t> card(n, 0);
-    if (!rc && host_decode) {
-        // round-1 path: every sketch decoded and sorted by spsp_sketch_parse_host on the host threads, keys uploaded by spsp_compare
-        std::vector<spsp_sketch_view> views(n);
-        std::vector<void*> owned((size_t)n * 3, nullptr);
-        // decode + sort on the host threads (one sketch per task), then the checks in file order
-        std::vector<uint32_t> kks(n, 0), mms(n, 0);
-        std::vector<uint64_t> cnts(n, 0);
-        {
-            std::fill(rcs.begin(), rcs.end(), SPSP_OK);
-            std::atomic<uint32_t> next(0);
-            auto work = [&]() {
-                for (;;) {
-                    const uint32_t i = next.fetch_add(1);
-                    if (i >= n) break;
-                    uint32_t* mn = nullptr; uint64_t *lo = nullptr, *hi = nullptr;
-                    rcs[i] = spsp_sketch_parse_host(datas[i], lens[i], &kks[i], &mms[i], &mn, &lo, &hi, &cnts[i]);
-                    if (rcs[i]) { errs[i] = spsp_last_error(); continue; }
-                    owned[3 * (size_t)i] = mn; owned[3 * (size_t)i + 1] = lo; owned[3 * (size_t)i + 2] = hi;
-                }
-            };
-            std::vector<std::thread> pool;
-            for (unsigned w = 1; w < workers; ++w) pool.emplace_back(work);
-            work();
-            for (auto& th : pool) th.join();
-            for (uint32_t i = 0; i < n && !rc; ++i)
-                if (rcs[i]) { set_error("%s", errs[i].c_str()); rc = rcs[i]; }
-        }
-        for (uint32_t i = 0; i < n && !rc; ++i) {
-            const uint32_t kk = kks[i], mm2 = mms[i];
-            uint32_t* mn = (uint32_t*)owned[3 * (size_t)i]; uint64_t *lo = (uint64_t*)owned[3 * (size_t)i + 1], *hi = (uint64_t*)owned[3 * (size_t)i + 2];
-            uint64_t cnt = cnts[i];
-            if (kk != k0 || mm2 != m0) { set_error("'%s' was sketched with k=%u m=%u, expected k=%u m=%u", paths[i], kk, mm2, k0, m0); rc = SPSP_ERR_FORMAT; break; }
-            if (extra_has[i] && cnt == 0) {
-                int has = 0; char tmp[16]; memset(tmp, 'A', sizeof tmp);
-                // (recomputed from the stored minimizer: k == m, the k-mer is the minimizer's canonical form)
-                uint64_t v = extra_mn[i], r = 0;
-                for (uint32_t j = 0; j < m0; ++j) r |= (uint64_t)(((v >> (2 * j)) & 3u) ^ 2u) << (2 * (m0 - 1 - j));
-                mn[0] = extra_mn[i]; lo[0] = v < r ? v : r; hi[0] = 0; cnt = 1; (void)has; (void)tmp;
-            }
-            views[i].minimizer = mn; views[i].kmer_lo = lo; views[i].kmer_hi = k0 > 32 ? hi : nullptr; views[i].n = cnt;
-        }
-        free_datas();
-        if (!rc && chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }   // :56
-        t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
-        if (!rc && (rc = inter.zero((size_t)n * n))) set_error("out of host memory");
-        if (!rc) rc = spsp_compare(ctx, views.data(), n, n_query, inter.data(), card.data());
-        for (void* p : owned) free(p);
-    } else if (!rc) {
+    if (!rc) {
         if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }   // :56
         t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
         uint32_t kk = 0, mm2 = 0;

@@ -481,8 +481,7 @@ bool build_on_device(uint64_t places) {
     return places >= 500000;
 }
 bool ingest_packs(const spsp_params* p) {
-    static const bool ascii = getenv("SPSP_INGEST_ASCII") != nullptr;
-    return !ascii && !(p->flags & SPSP_SCAN_PACKED_INPUT) && scan_reads_packed(p);
+    return !(p->flags & SPSP_SCAN_PACKED_INPUT) && scan_reads_packed(p);
 }
 
 }  // namespace spsp
@@ -525,7 +524,7 @@ int spsp_sketch_text(spsp_ctx* ctx, const spsp_params* p, double rate, const cha
     if ((rc = ctx->i_text.reserve((size_t)n_text + 64))) return rc;
     if (n_text) SPSP_HIP(hipMemcpyAsync(ctx->i_text.p, text, (size_t)n_text, hipMemcpyHostToDevice, ctx->stream));
     uint8_t* d_bases = nullptr; uint64_t* d_off = nullptr; uint64_t n_bases = 0; uint32_t n_rec = 0;
-    // the ingest writes 2-bit words when the dense pass of these parameters reads them (SPSP_INGEST_ASCII=1: A/B switch)
+    // the ingest writes 2-bit words when the dense pass of these parameters reads them
     const bool packed = ingest_packs(p);
     if ((rc = clean_device_impl(ctx, ctx->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed))) return rc;
     t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
@@ -579,10 +578,9 @@ int spsp_sketch_text(spsp_ctx* ctx, const spsp_params* p, double rate, const cha
     uint8_t* compact = nullptr; uint32_t* coff = nullptr;
     if ((rc = gather_superkmers_impl(ctx, d_bases, d_off, d_sk, n_sk, &compact, &coff, packed))) return rc;   // synchronises the stream
     // -a > 1: the k-mers are counted here, over the gathered super-k-mers still on the device, and the host builder
-    // indexes the usable ones only (SPSP_HOST_ABUNDANCE=1 leaves the counting to the builder, as round 1 did)
+    // indexes the usable ones only (the builder counts when the device cannot: see below)
     uint8_t* kflags = nullptr; uint64_t n_occ = 0;
-    static const bool host_abundance = getenv("SPSP_HOST_ABUNDANCE") != nullptr;
-    if (p->abundance > 1 && !host_abundance) {
+    if (p->abundance > 1) {
         rc = abundance_flags_impl(ctx, p, d_sk, n_sk, &kflags, &n_occ);
         if (rc == SPSP_ERR_OVERFLOW) { rc = SPSP_OK; kflags = nullptr; }   // too many occurrences for 32-bit numbering: the host counts
         if (rc) { free(compact); free(coff); return rc; }

@@ -14,7 +14,7 @@
 // genome g = records [first_rec[g], first_rec[g+1]) of one scan -- producing the arrays spsp_compare_device takes:
 //
 //   k_keys_sizes    k-mers per selected super-k-mer -> (scan) first raw key of each
-//   k_keys_emit     one lane per super-k-mer: rolls the k-mers and their reverse complements from the bases (ASCII or
+//   k_keys_emit_places  one lane per k-mer place: cuts the k-mer and its reverse complement out of the bases (ASCII or
 //                   2-bit words) -> raw keys (minimizer, canonical k-mer, "the oriented form is the reverse complement")
 //   k_keys_ranges   one lane per genome: its super-k-mers (binary search on the record numbers) -> its raw key range
 //   k_keys_sort     one workgroup per genome: bitonic sort in LDS by (minimizer, k-mer, orientation); occurrences per
@@ -43,36 +43,6 @@ constexpr uint32_t kKeyCapLo = 8192, kKeyCapHi = 4096;
 __global__ void k_keys_sizes(const spsp_superkmer* __restrict__ sk, uint32_t n_sk, uint32_t k, uint32_t* __restrict__ cnt) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_sk) cnt[i] = sk[i].len >= k ? sk[i].len - k + 1 : 0u;
-}
-
-__global__ __launch_bounds__(256) void k_keys_emit(const uint8_t* __restrict__ bases, bool packed, const uint64_t* __restrict__ rec_off,
-                                                  const spsp_superkmer* __restrict__ sk, const uint32_t* __restrict__ raw_first,
-                                                  uint32_t n_sk, uint32_t k, uint32_t* __restrict__ r_mn, uint64_t* __restrict__ r_lo,
-                                                  uint64_t* __restrict__ r_hi) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_sk) return;
-    const spsp_superkmer e = sk[i];
-    if (e.len < k) return;
-    const uint64_t src = rec_off[e.rec] + e.start;
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(bases);
-    const u128d mask = k == 64 ? ~(u128d)0 : (((u128d)1 << (2 * k)) - 1);
-    u128d fwd = 0, rc = 0;
-    uint32_t o = raw_first[i];
-    for (uint32_t t = 0; t < e.len; ++t) {
-        const uint64_t q = src + t;
-        const uint32_t c = packed ? (words[q >> 4] >> (30u - 2u * (uint32_t)(q & 15u))) & 3u : ((uint32_t)bases[q] >> 1) & 3u;
-        fwd = ((fwd << 2) | c) & mask;
-        rc = (rc >> 2) | ((u128d)(c ^ 2u) << (2 * (k - 1)));
-        if (t + 1 < k) continue;
-        // handle_superkmer stores the k-mer as it reads in the super-k-mer's orientation (reverse complemented when the
-        // minimizer reads reversed, SubSampler.cpp:246-249); the comparator canonises (utils.cpp:470-472)
-        const u128d canon = fwd < rc ? fwd : rc;
-        const u128d oriented = e.rev ? rc : fwd;
-        r_mn[o] = e.minimizer | (oriented != canon ? 0x80000000u : 0u);   // bit 31: "the oriented form is the reverse complement"
-        r_lo[o] = (uint64_t)canon;
-        if (r_hi) r_hi[o] = (uint64_t)(canon >> 64);
-        ++o;
-    }
 }
 
 // genome g = records [first_rec[g], first_rec[g + 1]); the stream is in record order
@@ -278,7 +248,9 @@ __device__ __noinline__ void roll_places(const uint8_t* __restrict__ bases, bool
         fwd = ((fwd << 2) | c) & mask;
         rc = (rc >> 2) | ((u128d)(c ^ 2u) << (2 * (k - 1)));
         if (t + 1 < k) continue;
-        const u128d canon = fwd < rc ? fwd : rc;                   // (orientation as in k_keys_emit)
+        // handle_superkmer stores the k-mer as it reads in the super-k-mer's orientation (reverse complemented when the
+        // minimizer reads reversed, SubSampler.cpp:246-249); the comparator canonises (utils.cpp:470-472)
+        const u128d canon = fwd < rc ? fwd : rc;
         const u128d oriented = e.rev ? rc : fwd;
         r_mn[place0 + made] = e.minimizer | (oriented != canon ? 0x80000000u : 0u);
         r_lo[place0 + made] = (uint64_t)canon;
@@ -650,14 +622,8 @@ int sketch_keys_begin_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d
         }
         if ((rc = launch_scan_u32(ctx, ctx->a_cnt.as<uint32_t>(), ctx->a_off.as<uint32_t>(), n, ctx->h_scalar + 7))) return rc;
         if (n) {
-            // one lane per place from a few places per super-k-mer on (SPSP_DEBUG_KEYS_EMIT=sk: one lane per super-k-mer always)
-            static const char* dbg_emit = getenv("SPSP_DEBUG_KEYS_EMIT");
-            if (dbg_emit && dbg_emit[0] == 's')
-                hipLaunchKernelGGL(k_keys_emit, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_bases, packed, d_rec_off, d_sk, ctx->a_off.as<uint32_t>(), n, p->k,
-                                   a_mn, a_lo, a_hi);
-            else
-                hipLaunchKernelGGL(k_keys_emit_places, dim3((uint32_t)((bound + kPlaceTile - 1) / kPlaceTile)), dim3(kPlaceThreads), 0, ctx->stream, d_bases, packed,
-                                   d_rec_off, d_sk, ctx->a_off.as<uint32_t>(), ctx->a_cnt.as<uint32_t>(), n, p->k, a_mn, a_lo, a_hi);
+            hipLaunchKernelGGL(k_keys_emit_places, dim3((uint32_t)((bound + kPlaceTile - 1) / kPlaceTile)), dim3(kPlaceThreads), 0, ctx->stream, d_bases, packed,
+                               d_rec_off, d_sk, ctx->a_off.as<uint32_t>(), ctx->a_cnt.as<uint32_t>(), n, p->k, a_mn, a_lo, a_hi);
             SPSP_HIP(hipGetLastError());
         }
         hipLaunchKernelGGL(k_keys_ranges, dim3((n_genomes + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_sk, n, ctx->a_off.as<uint32_t>(), d_first_rec,
@@ -677,8 +643,7 @@ int sketch_keys_begin_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d
     // both forms), then the compaction.  A context whose last extraction met no such genome leaves the two table kernels
     // out -- a key extraction per 0.1 ms step pays for every launch on its stream -- and runs them from _end in the call
     // that does meet one; from then on they are queued here, behind a gate word that lets them leave at once.
-    static const char* force = getenv("SPSP_DEBUG_KEYS_BIG");      // test hook: "early" / "late" pins the choice
-    const bool early = force ? force[0] == 'e' : ctx->keys_expect_big;
+    const bool early = ctx->keys_expect_big;
     if ((rc = keys_finish_queue(ctx, early, early ? d_flags : nullptr))) return rc;
     ctx->keys_job.big_queued = early;
     if (!ctx->keys_done) SPSP_HIP(hipEventCreateWithFlags(&ctx->keys_done, hipEventDisableTiming));

@@ -1608,12 +1608,11 @@ struct ListPlan { uint32_t grid, n_lists, cap; uint64_t n_rows, rows_per_wave; }
 static int plan_lists(spsp_ctx* ctx, const spsp_params* p, int variant, uint64_t n_bases, ListPlan* P) {
     P->n_rows = (n_bases + kRowPosPair63 - 1) / kRowPosPair63;
     const uint64_t want = (P->n_rows + kPairWaves - 1) / kPairWaves;
-    static const int per_cu_env = getenv("SPSP_PAIR_BLOCKS_PER_CU") ? atoi(getenv("SPSP_PAIR_BLOCKS_PER_CU")) : 0;  // tuning knob
     // One 1024-lane workgroup per CU unless the caller says its stream owns its CUs (spsp_set_cu_count).  k_dense_pair
     // (80 KiB of LDS) fits twice, and alone it runs 3-4 % faster that way (more loads in flight); with one, the other
     // half of the CU's wave slots and LDS stays free for the kernels of other streams that share the CU (a pipelined step
     // on unpartitioned streams: 0.158 vs 0.185 ms)
-    const int per_cu = per_cu_env > 0 ? per_cu_env : ctx->dense_blocks_per_cu;
+    const int per_cu = ctx->dense_blocks_per_cu;
     const uint64_t cap_blocks = (uint64_t)ctx->n_cu * (per_cu > 0 ? per_cu : 1);
     P->grid = (uint32_t)(want < cap_blocks ? want : cap_blocks);
     P->n_lists = P->grid * kPairWaves;

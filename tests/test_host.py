@@ -38,6 +38,23 @@ def test_header_symbols_all_exported():
     assert b"gfx950" in L.spsp_version()
 
 
+def test_environment_variables_are_the_documented_ones():
+    """every SPSP_* variable the library and the CLIs read is a row of DESIGN.md's variables table (§6e), and every name
+    there is still read: a switch cannot be added, or left behind, unnoticed."""
+    csrc = os.path.join(ROOT, "supersampler_amd", "csrc")
+    read = set()
+    for name in os.listdir(csrc):
+        if name.endswith((".hip", ".cpp", ".h")):
+            read |= set(re.findall(r'getenv\(\s*"(SPSP_[A-Z0-9_]+)"', open(os.path.join(csrc, name)).read()))
+    design = open(os.path.join(ROOT, "DESIGN.md"), encoding="utf-8").read()
+    section = design[design.index("\n## 6e."):]
+    section = section[:section.index("\n## ", 1)]
+    table = "\n".join(line for line in section.splitlines() if line.startswith("|"))
+    documented = set(re.findall(r"SPSP_[A-Z0-9_]+", table))
+    assert read and read == documented, ("read, not documented: %s; documented, not read: %s"
+                                         % (sorted(read - documented), sorted(documented - read)))
+
+
 def test_library_carries_gfx950_code_object():
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--list", "--type=o",
                           "--input=" + sp.LIB_PATH], capture_output=True, text=True)

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""spsp_compare_files over N sketch files on tmpfs: GPU bulk decode (default) against the host decoder (SPSP_HOST_DECODE=1,
-set before the library is first used), with the library's stage times.
+"""spsp_compare_files over N sketch files on tmpfs (GPU bulk decode), with the library's stage times.
 usage (GPU box): python tools/decode_bench.py [N=1000]"""
 import gzip
 import os
@@ -41,8 +40,7 @@ try:
     ctx.compare_files(paths, os.path.join(tmp, "res"))
     wall = time.perf_counter() - t0
     st = ctx.stage_times(reset=True)
-    print("%s decode: %d sketches, compare_files %.3f s: load(read+gunzip%s) %.3f, decode+compare+D2H %.3f, csv %.3f, csv gzip %.3f"
-          % ("host" if os.environ.get("SPSP_HOST_DECODE") else "GPU", N, wall, "+decode+sort" if os.environ.get("SPSP_HOST_DECODE") else "",
-             st["load_s"], st["compare_s"], st["csv_s"], st["csv_gzip_s"]))
+    print("GPU decode: %d sketches, compare_files %.3f s: load(read+gunzip) %.3f, decode+compare+D2H %.3f, csv %.3f, csv gzip %.3f"
+          % (N, wall, st["load_s"], st["compare_s"], st["csv_s"], st["csv_gzip_s"]))
 finally:
     shutil.rmtree(tmp, ignore_errors=True)

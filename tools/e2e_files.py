@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """End-to-end sketching rate of spsp_sketch_files: N synthetic genomes as FASTA files on tmpfs -> sketch files, for a list
-of worker counts; payloads of the first files checked against the oracle.  SPSP_FILES_PER_WORKER=1 in the environment
-selects the one-GPU-job-per-file form (A/B).
+of worker counts; payloads of the first files checked against the oracle.
 usage: tools/e2e_files.py [n_files=100] [length=5000000] [threads=1,8,16] [reps=3]"""
 import json
 import os
@@ -36,7 +35,7 @@ try:
     kmers = sum(len(g) - K + 1 for g in gs)
     outs = [os.path.join(tmp, "s%03d.gz" % i) for i in range(n)]
     sp.sketch_files(ins[:8], outs[:8], K, M, S, threads=8)      # HIP modules, page cache
-    doc = {"files": n, "length": length, "kmers": kmers, "mode": "per-worker" if os.environ.get("SPSP_FILES_PER_WORKER") else "batched", "runs": {}}
+    doc = {"files": n, "length": length, "kmers": kmers, "mode": "batched", "runs": {}}
     for T in threads:
         best = None
         for _ in range(reps):

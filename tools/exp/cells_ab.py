@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """the all-vs-all comparison of N configs[3]-shaped sketches returned as CELLS (what spsp_compare_files takes from 1 024 files on),
-timed by host wall clock and kernel brackets; run under SPSP_DEBUG_ACC_TOUCH=0 / l / s for the A/B.  usage: cells_ab.py [N=10000] [fam=20]"""
+timed by host wall clock and kernel brackets; run under SPSP_DEBUG_ACC_TOUCH=0 / s for the A/B.  usage: cells_ab.py [N=10000] [fam=20]"""
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
