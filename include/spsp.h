@@ -292,6 +292,20 @@ int spsp_fasta_clean_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, 
 int spsp_fasta_clean_packed_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_packed, uint64_t* n_bases,
                                    void** d_rec_off, uint32_t* n_rec);
 
+/* FASTQ read sets.  A text whose first byte is '@' is FASTQ: records of exactly four lines -- '@' header, sequence, '+'
+ * separator, quality as long as the sequence (lengths counted without a trailing '\r'; the last record may lack its
+ * newline; blank lines may follow the last record).  Each read is one record; its bases are the sequence line cleaned as
+ * clean_dna cleans FASTA.  Sketching FASTQ text T is sketching the FASTA text that holds ">" + header[1:] + "\n" + seq +
+ * "\n" per record.  Wrapped (multi-line) FASTQ is not read.  The two calls below mirror spsp_fasta_clean_device and
+ * spsp_fasta_clean_packed_device (same arguments, output layout and ownership); a malformed record is SPSP_ERR_FORMAT
+ * and spsp_last_error() names its 0-based index and the rule it breaks.  spsp_sketch_text, spsp_sketch_file(s) and
+ * spsp_sketch_files_multi tell the format from the first byte of each (gunzipped) text or file; in a batch a malformed
+ * FASTQ file fails alone. */
+int spsp_fastq_clean_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_bases, uint64_t* n_bases,
+                            void** d_rec_off, uint32_t* n_rec);
+int spsp_fastq_clean_packed_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_packed, uint64_t* n_bases,
+                                   void** d_rec_off, uint32_t* n_rec);
+
 typedef struct spsp_sketch_stats {
     uint64_t read_kmer, selected_kmer_number, selected_superkmer_number, count_maximal_skmer;
     uint64_t seen_kmers_at_reconstruction, seen_superkmers_at_reconstruction;
@@ -310,7 +324,7 @@ int spsp_sketch_build_host(const spsp_params* p, double rate, const uint8_t* bas
                            uint64_t n_sk, uint8_t** payload, uint64_t* payload_len,
                            spsp_sketch_stats* stats);
 
-/* FASTA text (host) -> sketch payload with ingest, scan and super-k-mer gather on the GPU: what
+/* FASTA (or FASTQ: see above) text (host) -> sketch payload with ingest, scan and super-k-mer gather on the GPU: what
  * parse_fasta_test does between openFile and the gzip writer (SubSampler.cpp:306-504). */
 int spsp_sketch_text(spsp_ctx* ctx, const spsp_params* p, double rate, const char* text, uint64_t n_text,
                      uint8_t** payload, uint64_t* payload_len, spsp_sketch_stats* stats);

@@ -168,6 +168,11 @@ struct PipeFile {
     int rc = SPSP_OK;
     std::string err;
     bool packed = false, force_header = false;
+    bool fastq = false;                  // first byte '@': read as FASTQ (no forced header; its tiles are described to the ingest)
+    bool laid = false;                   // has a place in the slab
+    uint64_t fq_end = 0;                 // FASTQ: end of the content (the text less its trailing blank lines)
+    bool fq_blank = false;               // FASTQ: a blank line follows the content
+    std::string fmt_err;                 // FASTQ: the ingest found a malformed record (the file fails once the batch is through)
     std::vector<uint8_t> inflated;       // gunzipped text of a packed file
     uint64_t text_len = 0, off = 0;      // place in the slab (off is a multiple of kSlabAlign)
     uint32_t first_rec = 0, n_rec = 0;
@@ -386,10 +391,12 @@ private:
                 else f.inflated.swap(raw);
                 f.packed = true;                            // "text is in f.inflated"
                 f.text_len = f.inflated.size();
-                f.force_header = f.text_len == 0 || !(f.inflated[0] == '>' || f.inflated[0] == 0xFF);
+                f.fastq = f.text_len && f.inflated[0] == '@';
+                f.force_header = !f.fastq && (f.text_len == 0 || !(f.inflated[0] == '>' || f.inflated[0] == 0xFF));
             } else {
                 f.text_len = (uint64_t)st.st_size;
-                f.force_header = got < 1 || !(head[0] == '>' || head[0] == 0xFF);
+                f.fastq = got >= 1 && head[0] == '@';
+                f.force_header = !f.fastq && (got < 1 || !(head[0] == '>' || head[0] == 0xFF));
             }
             close(fd);
         }
@@ -405,6 +412,7 @@ private:
         for (auto& f : s.files) {
             if (f.rc) continue;
             f.off = at;
+            f.laid = true;
             at = (at + (f.force_header ? 1 : 0) + f.text_len + 1 + kSlabAlign - 1) / kSlabAlign * kSlabAlign;   // >= 1 newline behind every file
         }
         s.total = at;
@@ -489,6 +497,8 @@ private:
                     memset(s.slab + f.off, '\n', (size_t)(f.force_header ? 1 : 0) + f.text_len);
                 }
             }
+            // a FASTQ file's content ends behind its last non-blank line (the ingest reads no further)
+            if (f.fastq && !f.rc) spsp::fastq_tail(s.slab + f.off, f.text_len, &f.fq_end, &f.fq_blank);
             // the gap up to the next file's tile: newlines (empty lines: no bases, no record)
             const uint64_t end = f.off + (f.force_header ? 1 : 0) + f.text_len;
             const uint64_t next = (end + 1 + kSlabAlign - 1) / kSlabAlign * kSlabAlign;
@@ -526,10 +536,42 @@ private:
                 SPSP_HIP(hipMemcpyAsync(ctx->i_text.p, s.slab, (size_t)s.total, hipMemcpyHostToDevice, ctx->stream));
             uint8_t* d_bases = nullptr; uint64_t* d_off = nullptr; uint64_t n_bases = 0; uint32_t n_rec = 0;
             const bool packed = spsp::ingest_packs(&p_);           // the ingest writes the 2-bit words the dense pass reads
-            if ((r = spsp::clean_device_impl(ctx, ctx->i_text.as<uint8_t>(), s.total, &d_bases, &n_bases, &d_off, &n_rec, packed))) return r;
-            // records in front of every file: the ingest's per-tile record base at the file's first tile, less the file's own
-            // first record (counted with the newline in front of its header line, i.e. in the tile before)
             const uint64_t n_tiles = (s.total + kSlabAlign - 1) / kSlabAlign;
+            // a batch with FASTQ in it: every tile is described to the ingest (format, file start, content), each file then
+            // starts afresh; a batch of FASTA alone goes through the FASTA form
+            std::vector<uint32_t> tinfo;
+            std::vector<uint64_t> bad;
+            spsp::FastqLayout fq;
+            if (std::any_of(s.files.begin(), s.files.end(), [](const PipeFile& f) { return !f.rc && f.fastq; })) {
+                tinfo.assign((size_t)n_tiles, 0u);
+                bad.assign(s.files.size(), ~0ull);
+                for (size_t j = 0; j < s.files.size(); ++j) {
+                    const PipeFile& f = s.files[j];
+                    if (!f.laid) continue;
+                    uint64_t stop = s.total;                          // the next laid file's place
+                    for (size_t q = j + 1; q < s.files.size(); ++q) if (s.files[q].laid) { stop = s.files[q].off; break; }
+                    const uint64_t t_a = f.off / kSlabAlign, t_b = stop / kSlabAlign;
+                    const uint32_t id = (uint32_t)j << spsp::kTiFileShift;
+                    // a file that failed to read is all newlines by now: described as FASTQ without content, it holds no record
+                    const bool as_fq = f.rc || f.fastq;
+                    const uint64_t e = f.rc ? 0 : f.fq_end;
+                    for (uint64_t t = t_a; t < t_b; ++t) {
+                        uint32_t w = id | (t == t_a ? spsp::kTiStart : 0u);
+                        if (as_fq) {
+                            const uint64_t r0 = (t - t_a) * kSlabAlign;
+                            w |= spsp::kTiFastq | (f.fq_blank ? spsp::kTiBlankTail : 0u) |
+                                 (uint32_t)(e <= r0 ? 0 : std::min<uint64_t>(kSlabAlign, e - r0)) |
+                                 (e > r0 && e <= r0 + kSlabAlign ? spsp::kTiEnd : 0u);
+                        }
+                        tinfo[(size_t)t] = w;
+                    }
+                }
+                fq.tile_info = tinfo.data(); fq.n_files = (uint32_t)s.files.size(); fq.bad = bad.data();
+            }
+            if ((r = spsp::clean_device_impl(ctx, ctx->i_text.as<uint8_t>(), s.total, &d_bases, &n_bases, &d_off, &n_rec, packed, fq.tile_info ? &fq : nullptr))) return r;
+            // records in front of every file: the ingest's per-tile record base at the file's first tile, less the file's own
+            // first record (counted with the newline in front of its header line, i.e. in the tile before; in the described
+            // form, with the file's start)
             std::vector<uint32_t> rec_base((size_t)n_tiles);
             SPSP_HIP(hipMemcpyAsync(rec_base.data(), ctx->i_recbase.p, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, ctx->stream));
             s.rec_off.resize((size_t)n_rec + 1);
@@ -548,6 +590,15 @@ private:
                 prev = &f;
             }
             if (prev) prev->n_rec = n_rec - prev->first_rec;
+            // a malformed FASTQ file keeps its records (and its range of the stream) through the batch and fails at the end
+            for (size_t j = 0; j < bad.size(); ++j) {
+                PipeFile& f = s.files[j];
+                if (f.rc || bad[j] == ~0ull) continue;
+                char msg[256];
+                snprintf(msg, sizeof msg, "malformed FASTQ '%s': record %llu (0-based): %s", in_[f.index],
+                         (unsigned long long)((bad[j] >> 8) - f.first_rec), spsp::fastq_rule_name((uint32_t)(bad[j] & 0xFFu)));
+                f.fmt_err = msg;
+            }
             s.sk.resize((size_t)n_sk);
             if (n_sk) SPSP_HIP(hipMemcpyAsync(s.sk.data(), d_sk, (size_t)n_sk * sizeof(spsp_superkmer), hipMemcpyDeviceToHost, ctx->stream));
             SPSP_HIP(hipStreamSynchronize(ctx->stream));                      // (the stream's copy above: the files' ranges and the choice below come from it)
@@ -632,6 +683,8 @@ private:
             return SPSP_OK;
         };
         rc = run();
+        if (rc == SPSP_OK)
+            for (auto& f : s.files) if (!f.rc && !f.fmt_err.empty()) { f.rc = SPSP_ERR_FORMAT; f.err = f.fmt_err; }
         if (rc == SPSP_ERR_OVERFLOW) {
             // together the files exceed a limit of ONE job (32-bit offsets of the gathered super-k-mers at -s near 1, say):
             // one job per file on this slot's context instead, the way spsp_sketch_file would have run them

@@ -17,6 +17,7 @@
 //                   into output / record offsets
 //   k_clean_write   per tile: compacts through LDS, coalesced stores, rec_off[]
 // 1 B read + 1 B written per input byte, twice over the input (L2-friendly).
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 
@@ -268,6 +269,74 @@ __global__ __launch_bounds__(1024) void k_clean_scan(const TileSummary* __restri
     if (t == 0) { totals[0] = c_k; totals[1] = c_h; }
 }
 
+// One lane's survivors -> the tile's LDS staging buffer, in order from LDS offset sh + at; a record starts behind every
+// byte set in rs (rec_off[hr++] = where the next survivor will land).
+__device__ __forceinline__ void stage_survivors(uint8_t* s_out, uint32_t sh, uint32_t at, const uint32_t (&bytes)[4], uint32_t valid,
+                                                uint32_t keep, uint32_t rs, uint64_t obase, uint32_t hr, uint64_t* __restrict__ rec_off) {
+    uint8_t* dst = s_out + sh + at;
+    const uint64_t lo = (((uint64_t)bytes[1] << 32) | bytes[0]) & 0xDFDFDFDFDFDFDFDFull;   // survivors are ACGTacgt:
+    const uint64_t hi = (((uint64_t)bytes[3] << 32) | bytes[2]) & 0xDFDFDFDFDFDFDFDFull;   // clearing bit 5 upper-cases them
+    if (keep == 0xFFFFu && !rs) {
+        // four lanes out of five: the whole chunk survives -- one (unaligned) 16-byte LDS store
+        const uint64_t both[2] = {lo, hi};
+        __builtin_memcpy(dst, both, 16);
+    } else if (valid == kCleanChunk && __popc(keep) == 15 && !rs) {
+        // most of the rest: one byte (the newline) goes -- close the gap in registers, store 8 + 4 + 2 + 1 bytes
+        const uint32_t j = __ffs(~keep & 0xFFFFu) - 1;
+        uint64_t l2 = lo, h2 = hi >> 8;
+        if (j < 8) {
+            const uint64_t m = (1ull << (8 * j)) - 1ull;
+            l2 = (lo & m) | (((lo >> 8) | (hi << 56)) & ~m);
+        } else {
+            const uint64_t m = (1ull << (8 * (j - 8))) - 1ull;
+            h2 = (hi & m) | ((hi >> 8) & ~m);
+        }
+        const uint32_t h4 = (uint32_t)h2;
+        const uint16_t h2b = (uint16_t)(h2 >> 32);
+        __builtin_memcpy(dst, &l2, 8);
+        __builtin_memcpy(dst + 8, &h4, 4);
+        __builtin_memcpy(dst + 12, &h2b, 2);
+        dst[14] = (uint8_t)(h2 >> 48);
+    } else {
+        uint32_t todo = keep | rs;
+        while (todo) {                                  // header lines, N runs, the end of the text: byte by byte
+            const uint32_t j = __ffs(todo) - 1;
+            todo &= todo - 1;
+            if (keep & (1u << j)) s_out[sh + at++] = (uint8_t)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))) & 0xFFu);
+            if (rs & (1u << j)) rec_off[hr++] = obase + at;   // the record begins where the next survivor will land
+        }
+    }
+}
+
+// The staged tile (LDS [sh, sh + tile_keep)) -> the output at obase: whole aligned 16-byte groups are stored, the first and
+// last group of the tile (shared with the neighbouring tiles) byte by byte (ASCII) or ORed into the zeroed words (PACK).
+template <bool PACK>
+__device__ __forceinline__ void store_tile(const uint8_t* s_out, uint32_t sh, uint32_t tile_keep, uint64_t obase, uint8_t* __restrict__ bases) {
+    const uint32_t end = sh + tile_keep;                // LDS range [sh, end) holds this tile's output
+    if (PACK) {
+        uint32_t* words = reinterpret_cast<uint32_t*>(bases) + ((obase - sh) >> 4);
+        for (uint32_t g = threadIdx.x; g * 16 < end; g += kCleanThreads) {
+            const uint32_t lo = g * 16, hi = lo + 16;
+            if (lo >= sh && hi <= end) words[g] = pack16(*reinterpret_cast<const uint4*>(s_out + lo));
+            else {
+                uint32_t w = 0;
+                for (uint32_t x = lo < sh ? sh : lo; x < (hi < end ? hi : end); ++x) w |= (((uint32_t)s_out[x] >> 1) & 3u) << (30u - 2u * (x - lo));
+                if (w) atomicOr(&words[g], w);
+            }
+        }
+        return;
+    }
+    uint8_t* gbase = bases + (obase - sh);              // 16-byte aligned
+    for (uint32_t g = threadIdx.x; g * 16 < end; g += kCleanThreads) {
+        const uint32_t lo = g * 16, hi = lo + 16;
+        if (lo >= sh && hi <= end) {
+            *reinterpret_cast<uint4*>(gbase + lo) = *reinterpret_cast<const uint4*>(s_out + lo);
+        } else {                                        // first / last group of the tile: shared with the neighbours
+            for (uint32_t x = lo < sh ? sh : lo; x < (hi < end ? hi : end); ++x) gbase[x] = s_out[x];
+        }
+    }
+}
+
 // PACK: the survivors leave as 2-bit words -- 16 bases per dword, first base in bits 31:30, the layout the dense pass
 // reads with SPSP_SCAN_PACKED_INPUT (N1 of SURVEY.md 8f: "2-bit packing + non-ACGT compaction").  The tile's survivors
 // sit in LDS at the output's alignment modulo 16, so an aligned 16-byte group of the staging buffer IS one output word:
@@ -295,66 +364,396 @@ __global__ __launch_bounds__(kCleanThreads) void k_clean_write(const uint8_t* __
     // survivors -> LDS in order, shifted so that LDS offset and global address agree modulo 16: the tile then
     // leaves as aligned 16-byte stores; record starts -> rec_off
     const uint32_t sh = (uint32_t)(obase & 15u);
-    uint32_t at = koff, hr = rec_base[blockIdx.x] + hoff;
-    uint8_t* dst = s_out + sh + at;
-    const uint64_t lo = (((uint64_t)c.bytes[1] << 32) | c.bytes[0]) & 0xDFDFDFDFDFDFDFDFull;   // survivors are ACGTacgt:
-    const uint64_t hi = (((uint64_t)c.bytes[3] << 32) | c.bytes[2]) & 0xDFDFDFDFDFDFDFDFull;   // clearing bit 5 upper-cases them
-    if (keep == 0xFFFFu && !c.drop_after) {
-        // four lanes out of five: the whole chunk survives -- one (unaligned) 16-byte LDS store
-        const uint64_t both[2] = {lo, hi};
-        __builtin_memcpy(dst, both, 16);
-    } else if (c.valid == kCleanChunk && __popc(keep) == 15 && !c.drop_after) {
-        // most of the rest: one byte (the newline) goes -- close the gap in registers, store 8 + 4 + 2 + 1 bytes
-        const uint32_t j = __ffs(~keep & 0xFFFFu) - 1;
-        uint64_t l2 = lo, h2 = hi >> 8;
-        if (j < 8) {
-            const uint64_t m = (1ull << (8 * j)) - 1ull;
-            l2 = (lo & m) | (((lo >> 8) | (hi << 56)) & ~m);
-        } else {
-            const uint64_t m = (1ull << (8 * (j - 8))) - 1ull;
-            h2 = (hi & m) | ((hi >> 8) & ~m);
-        }
-        const uint32_t h4 = (uint32_t)h2;
-        const uint16_t h2b = (uint16_t)(h2 >> 32);
-        __builtin_memcpy(dst, &l2, 8);
-        __builtin_memcpy(dst + 8, &h4, 4);
-        __builtin_memcpy(dst + 12, &h2b, 2);
-        dst[14] = (uint8_t)(h2 >> 48);
+    stage_survivors(s_out, sh, koff, c.bytes, c.valid, keep, c.drop_after, obase, rec_base[blockIdx.x] + hoff, rec_off);
+    __syncthreads();
+    store_tile<PACK>(s_out, sh, tile_keep, obase, bases);
+    if (blockIdx.x == 0 && threadIdx.x == 0) rec_off[0] = 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// FASTQ, and batches that mix FASTQ and FASTA files.  A FASTQ text is records of four lines (@header, sequence, +separator,
+// quality); a line's ROLE is (newlines in front of it in its file) mod 4, so the line state of a span is the number of its
+// newlines mod 4 and spans compose by addition.  The survivors are the ACGTacgt bytes of role-1 lines, a record starts at
+// every role-0 line.  Each tile is told what it holds (TileInfo: the format of its file, whether the file starts there,
+// how many of its bytes belong to the file's content); a tile that starts a file resets the state, so FASTA and FASTQ
+// files share a batch.  The same three launches as above, over a state that covers both formats:
+//   state       bit 3: constant, bit 2: FASTQ, bits 1:0 the FASTQ role (FASTA: 0 = data line, 1 = drop line)
+//   transform   8 | state: "ends in this state"; 0..3: "adds this many lines" (FASTQ; 0 is the identity)
+// Validation runs inside the write pass: the first byte of role-0 ('@') and role-2 ('+') lines, and per record the
+// sequence length against the quality length through D = (content bytes of role-1 lines) - (those of role-3 lines), a
+// running sum that restarts at every file: every record is balanced iff D is 0 at every record start and at the file's end.
+// A failure is the smallest (record << 8 | rule) of the file, kept with an atomic min.
+// (the tile words kTi* and the rules kFq*: spsp_internal.h)
+
+__device__ __forceinline__ uint32_t mcompose(uint32_t f, uint32_t g) {
+    if (g & 8u) return g;
+    if (f & 8u) return (f & ~3u) | ((f + g) & 3u);
+    return (f + g) & 3u;
+}
+
+// One word per tile: from the batch's table, or (a whole text that is one FASTQ file) from the content end
+__device__ __forceinline__ uint32_t tile_info(const uint32_t* __restrict__ info, uint64_t tile, uint64_t fq_end, uint32_t fq_flags) {
+    if (info) return info[tile];
+    const uint64_t t0 = tile * kCleanTile;
+    const uint32_t lim = fq_end <= t0 ? 0u : (fq_end - t0 >= (uint64_t)kCleanTile ? (uint32_t)kCleanTile : (uint32_t)(fq_end - t0));
+    return lim | kTiFastq | fq_flags | (tile == 0 ? kTiStart : 0u) | (fq_end > t0 && fq_end <= t0 + kCleanTile ? kTiEnd : 0u);
+}
+
+struct FqChunk {
+    uint32_t bytes[4];
+    uint32_t valid;       // bytes inside the file's content
+    uint32_t base;        // bit j: byte j is one of ACGTacgt
+    uint32_t nl;          // bit j: byte j is '\n'
+    uint32_t content;     // bit j: byte j counts towards its line's length (not '\n', not a '\r' right before one)
+    uint32_t fol_at;      // bit j: byte j is '\n' and the next byte is '@'
+    uint32_t fol_plus;    // bit j: byte j is '\n' and the next byte is '+'
+};
+
+// end: where the tile's share of the content ends (the text's bytes up to n may be read behind it)
+__device__ __forceinline__ FqChunk load_fq_chunk(const uint8_t* __restrict__ text, uint64_t n, uint64_t end, uint64_t p0) {
+    FqChunk c;
+    c.valid = p0 >= end ? 0u : (uint32_t)((end - p0) < (uint64_t)kCleanChunk ? (end - p0) : (uint64_t)kCleanChunk);
+    if (c.valid == kCleanChunk) {
+        const uint4 v = *reinterpret_cast<const uint4*>(text + p0);
+        c.bytes[0] = v.x; c.bytes[1] = v.y; c.bytes[2] = v.z; c.bytes[3] = v.w;
     } else {
-        uint32_t todo = keep | c.drop_after;
-        while (todo) {                                  // header lines, N runs, the end of the text: byte by byte
-            const uint32_t j = __ffs(todo) - 1;
-            todo &= todo - 1;
-            if (keep & (1u << j)) s_out[sh + at++] = (uint8_t)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))) & 0xFFu);
-            if (c.drop_after & (1u << j)) rec_off[hr++] = obase + at;   // the record begins where the next survivor will land
-        }
+        c.bytes[0] = c.bytes[1] = c.bytes[2] = c.bytes[3] = 0;
+        for (uint32_t j = 0; j < c.valid; ++j) c.bytes[j >> 2] |= (uint32_t)text[p0 + j] << (8 * (j & 3));
+    }
+    const uint32_t in_mask = c.valid >= 16 ? 0xFFFFu : ((1u << c.valid) - 1u);
+    uint32_t base = 0, nl = 0, cr = 0, at = 0, plus = 0;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const uint32_t w = c.bytes[d];
+        base |= pack_flags(base_bytes(w)) << (4 * d);
+        nl |= pack_flags(zero_bytes(w ^ 0x0A0A0A0Au)) << (4 * d);
+        cr |= pack_flags(zero_bytes(w ^ 0x0D0D0D0Du)) << (4 * d);
+        at |= pack_flags(zero_bytes(w ^ 0x40404040u)) << (4 * d);
+        plus |= pack_flags(zero_bytes(w ^ 0x2B2B2B2Bu)) << (4 * d);
+    }
+    // the byte behind the chunk, for a newline or '\r' in its last byte: the content never ends in one, so that byte is
+    // content too (possibly in the next tile)
+    const uint32_t next = (c.valid == kCleanChunk && p0 + kCleanChunk < n) ? text[p0 + kCleanChunk] : 0x100u;
+    const uint32_t nx = (next == '\n' ? 1u : 0u), na = (next == '@' ? 1u : 0u), np = (next == '+' ? 1u : 0u);
+    nl &= in_mask;
+    c.base = base & in_mask;
+    c.nl = nl;
+    c.content = in_mask & ~nl & ~(cr & ((nl >> 1) | (nx << 15)));
+    c.fol_at = nl & ((at >> 1) | (na << 15));
+    c.fol_plus = nl & ((plus >> 1) | (np << 15));
+    return c;
+}
+
+// Walk of a chunk's lines, the first in role `role`: survivors (bases of role-1 lines), record starts (newlines behind a
+// role-3 line), D of the chunk
+struct FqWalk { uint32_t keep, rs; int32_t d; };
+__device__ __forceinline__ FqWalk fq_walk(const FqChunk& c, uint32_t role) {
+    FqWalk w{0u, 0u, 0};
+    uint32_t from = 0, rem = c.nl;
+    while (rem) {
+        const uint32_t j = __ffs(rem) - 1;
+        rem &= rem - 1;
+        const uint32_t seg = ((2u << j) - 1u) & ~((1u << from) - 1u);
+        if (role == 1u) { w.keep |= c.base & seg; w.d += __popc(c.content & seg); }
+        else if (role == 3u) { w.d -= __popc(c.content & seg); w.rs |= 1u << j; }
+        role = (role + 1u) & 3u;
+        from = j + 1;
+    }
+    const uint32_t seg = 0xFFFFu & ~((1u << from) - 1u);
+    if (role == 1u) { w.keep |= c.base & seg; w.d += __popc(c.content & seg); }
+    else if (role == 3u) w.d -= __popc(c.content & seg);
+    return w;
+}
+
+// per tile, indexed by the low two bits of the state the tile is entered in (a tile that starts a file: all four alike)
+struct MixedTileSummary {
+    uint32_t transform;
+    uint32_t start;        // bit 0: a file starts here (D restarts), bit 1: ... and its first record with it
+    uint32_t keep[4], hdr[4];
+    int32_t d[4];
+};
+
+// three sums over the workgroup with one pair of barriers
+__device__ __forceinline__ void block_sum3_u64(unsigned long long (&v)[3], unsigned long long (*s_tot)[kCleanThreads / 64]) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+        for (int d = 32; d; d >>= 1) v[q] += __shfl_xor(v[q], d);
+        if ((threadIdx.x & 63) == 0) s_tot[q][threadIdx.x >> 6] = v[q];
     }
     __syncthreads();
-    const uint32_t end = sh + tile_keep;                // LDS range [sh, end) holds this tile's output
-    if (PACK) {
-        uint32_t* words = reinterpret_cast<uint32_t*>(bases) + ((obase - sh) >> 4);
-        for (uint32_t g = threadIdx.x; g * 16 < end; g += kCleanThreads) {
-            const uint32_t lo = g * 16, hi = lo + 16;
-            if (lo >= sh && hi <= end) words[g] = pack16(*reinterpret_cast<const uint4*>(s_out + lo));
-            else {
-                uint32_t w = 0;
-                for (uint32_t x = lo < sh ? sh : lo; x < (hi < end ? hi : end); ++x) w |= (((uint32_t)s_out[x] >> 1) & 3u) << (30u - 2u * (x - lo));
-                if (w) atomicOr(&words[g], w);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        v[q] = 0;
+        for (int w = 0; w < kCleanThreads / 64; ++w) v[q] += s_tot[q][w];
+    }
+    __syncthreads();
+}
+// exclusive scan of 64-bit values over the workgroup (lane order = byte order)
+__device__ __forceinline__ unsigned long long block_scan_add_u64(unsigned long long v, unsigned long long* s_wave, unsigned long long* total) {
+    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned long long x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long y = __shfl_up(x, d);
+        if (lane >= (uint32_t)d) x += y;
+    }
+    if (lane == 63) s_wave[wid] = x;
+    __syncthreads();
+    unsigned long long pre = 0, all = 0;
+    for (uint32_t w = 0; w < kCleanThreads / 64; ++w) { if (w < wid) pre += s_wave[w]; all += s_wave[w]; }
+    *total = all;
+    __syncthreads();
+    return pre + x - v;
+}
+
+__global__ __launch_bounds__(kCleanThreads) void k_mixed_tiles(const uint8_t* __restrict__ text, uint64_t n, uint64_t n_tiles,
+                                                              const uint32_t* __restrict__ info, uint64_t fq_end, uint32_t fq_flags,
+                                                              MixedTileSummary* __restrict__ tiles) {
+    __shared__ uint32_t s_wave[kCleanThreads / 64];
+    __shared__ unsigned long long s_tot[3][kCleanThreads / 64];
+    const uint32_t ti = tile_info(info, blockIdx.x, fq_end, fq_flags);
+    const bool start = ti & kTiStart;
+    const uint64_t t0 = (uint64_t)blockIdx.x * kCleanTile, p0 = t0 + (uint64_t)threadIdx.x * kCleanChunk;
+    MixedTileSummary out;
+    if (!(ti & kTiFastq)) {
+        // FASTA, as k_clean_tiles; a file that starts at the next tile is counted there (its first record) -- not here
+        ChunkInfo c = load_chunk(text, n, p0);
+        const bool next_starts = blockIdx.x + 1 < n_tiles && (tile_info(info, blockIdx.x + 1, fq_end, fq_flags) & kTiStart);
+        if (threadIdx.x == kCleanThreads - 1 && next_starts) c.drop_after &= 0x7FFFu;
+        uint32_t tile_t;
+        const uint32_t pre = block_scan_transform(chunk_transform(c), s_wave, &tile_t);
+        const uint32_t fixed = pre ? __popc(chunk_keep(c, pre & 1u)) : __popc(chunk_keep(c, 1u));
+        const uint32_t extra = (pre || start) ? 0u : __popc(chunk_keep(c, 0u)) - fixed;   // a file's first line is its header
+        unsigned long long sums[3] = {(unsigned long long)fixed | ((unsigned long long)extra << 20) |
+                                      ((unsigned long long)__popc(c.drop_after) << 40), 0ull, 0ull};
+        block_sum3_u64(sums, s_tot);
+        const unsigned long long all = sums[0];
+        const uint32_t mt = tile_t ? (8u | (tile_t & 1u)) : (start ? 9u : 0u);
+        out.transform = mt;
+        out.start = start ? 3u : 0u;
+        for (int e = 0; e < 4; ++e) {
+            out.keep[e] = (uint32_t)(all & 0xFFFFFu) + (e == 0 ? (uint32_t)((all >> 20) & 0xFFFFFu) : 0u);
+            out.hdr[e] = (uint32_t)(all >> 40);
+            out.d[e] = 0;
+        }
+    } else {
+        const FqChunk c = load_fq_chunk(text, n, t0 + (ti & kTiLim), p0);
+        uint32_t nl_tile;
+        const uint32_t rel = block_scan_add(__popc(c.nl), s_wave, &nl_tile) & 3u;   // role relative to the tile's entry
+        // counts by relative role, four 16-bit fields each: survivors, content bytes, line starts
+        unsigned long long K = 0, C = 0, H = 0;
+        uint32_t role = rel, from = 0, rem = c.nl;
+        while (rem) {
+            const uint32_t j = __ffs(rem) - 1;
+            rem &= rem - 1;
+            const uint32_t seg = ((2u << j) - 1u) & ~((1u << from) - 1u);
+            K += (unsigned long long)__popc(c.base & seg) << (16 * role);
+            C += (unsigned long long)__popc(c.content & seg) << (16 * role);
+            role = (role + 1u) & 3u;
+            H += 1ull << (16 * role);
+            from = j + 1;
+        }
+        const uint32_t seg = 0xFFFFu & ~((1u << from) - 1u);
+        K += (unsigned long long)__popc(c.base & seg) << (16 * role);
+        C += (unsigned long long)__popc(c.content & seg) << (16 * role);
+        unsigned long long sums[3] = {K, C, H};
+        block_sum3_u64(sums, s_tot);
+        K = sums[0]; C = sums[1]; H = sums[2];
+        auto f = [](unsigned long long x, uint32_t r) { return (uint32_t)((x >> (16 * (r & 3u))) & 0xFFFFu); };
+        out.transform = start ? (12u | (nl_tile & 3u)) : (nl_tile & 3u);
+        out.start = start ? (1u | ((ti & kTiLim) ? 2u : 0u)) : 0u;
+        for (uint32_t e = 0; e < 4; ++e) {
+            const uint32_t en = start ? 0u : e;           // true role = relative role + entry role
+            out.keep[e] = f(K, 1u - en);
+            out.hdr[e] = f(H, 0u - en);
+            out.d[e] = (int32_t)f(C, 1u - en) - (int32_t)f(C, 3u - en);
+        }
+    }
+    if (threadIdx.x == 0) tiles[blockIdx.x] = out;
+}
+
+// one workgroup, as k_clean_scan: the state each tile is entered in, its output offset, its record base (records whose
+// first line begins before the tile ends... as for FASTA: rec_base - 1 is the record the tile's first byte belongs to) and
+// the D the tile is entered with
+__global__ __launch_bounds__(1024) void k_mixed_scan(const MixedTileSummary* __restrict__ tiles, uint64_t n_tiles,
+                                                    uint32_t* __restrict__ entry_state, uint64_t* __restrict__ out_off,
+                                                    uint32_t* __restrict__ rec_base, long long* __restrict__ d_base,
+                                                    uint64_t* __restrict__ totals) {
+    __shared__ uint32_t s_t[16];
+    __shared__ unsigned long long s_k[16];
+    __shared__ uint32_t s_h[16];
+    __shared__ long long s_d[16];
+    __shared__ uint32_t s_r[16];
+    __shared__ uint32_t c_t;
+    __shared__ unsigned long long c_k;
+    __shared__ uint32_t c_h;
+    __shared__ long long c_d;
+    const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    if (t == 0) { c_t = 9u; c_k = 0; c_h = 0; c_d = 0; }   // (tile 0 starts a file: it sets the state itself)
+    __syncthreads();
+    for (uint64_t base = 0; base < n_tiles; base += 1024ull * kScanTiles) {
+        const uint64_t i0 = base + (uint64_t)t * kScanTiles;
+        MixedTileSummary me[kScanTiles];
+        uint32_t tl = 0;
+#pragma unroll
+        for (int u = 0; u < kScanTiles; ++u) {
+            if (i0 + u < n_tiles) me[u] = tiles[i0 + u];
+            else me[u] = MixedTileSummary{0u, 0u, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0, 0, 0, 0}};
+            tl = mcompose(tl, me[u].transform);
+        }
+        uint32_t x = tl;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d);
+            if (lane >= (uint32_t)d) x = mcompose(y, x);
+        }
+        if (lane == 63) s_t[wid] = x;
+        __syncthreads();
+        uint32_t pre = c_t;
+        for (uint32_t w = 0; w < wid; ++w) pre = mcompose(pre, s_t[w]);
+        uint32_t excl = __shfl_up(x, 1);
+        if (lane == 0) excl = 0;
+        uint32_t state = mcompose(pre, excl);
+        uint32_t entry[kScanTiles];
+        unsigned long long keep[kScanTiles], ksum = 0;
+        uint32_t hsum = 0, dres = 0;
+        int32_t dd[kScanTiles];
+        long long dsum = 0;                                 // the lane's D transform: (dres ? restart : add) dsum
+#pragma unroll
+        for (int u = 0; u < kScanTiles; ++u) {
+            entry[u] = state;
+            const uint32_t e = state & 3u;
+            keep[u] = me[u].keep[e];
+            dd[u] = me[u].d[e];
+            ksum += keep[u]; hsum += me[u].hdr[e] + ((me[u].start >> 1) & 1u);
+            if (me[u].start & 1u) { dres = 1; dsum = dd[u]; } else dsum += dd[u];
+            state = mcompose(state, me[u].transform);
+        }
+        unsigned long long kx = ksum;
+        uint32_t hx = hsum, rx = dres;
+        long long dx = dsum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long ky = __shfl_up(kx, d);
+            const uint32_t hy = __shfl_up(hx, d), ry = __shfl_up(rx, d);
+            const long long dy = __shfl_up(dx, d);
+            if (lane >= (uint32_t)d) { kx += ky; hx += hy; if (!rx) dx += dy; rx |= ry; }
+        }
+        if (lane == 63) { s_k[wid] = kx; s_h[wid] = hx; s_d[wid] = dx; s_r[wid] = rx; }
+        __syncthreads();
+        unsigned long long kpre = c_k, kall = 0;
+        uint32_t hpre = c_h, hall = 0, tall = 0;
+        long long dpre = c_d, dall = c_d;
+        for (uint32_t w = 0; w < 16; ++w) {
+            if (w < wid) { kpre += s_k[w]; hpre += s_h[w]; dpre = s_r[w] ? s_d[w] : dpre + s_d[w]; }
+            kall += s_k[w]; hall += s_h[w]; tall = mcompose(tall, s_t[w]);
+            dall = s_r[w] ? s_d[w] : dall + s_d[w];
+        }
+        // D entering this lane: the waves before, then the lanes of this wave before this one
+        long long dex = __shfl_up(dx, 1);
+        uint32_t rex = __shfl_up(rx, 1);
+        if (lane == 0) { dex = 0; rex = 0; }
+        long long dcur = rex ? dex : dpre + dex;
+        unsigned long long ko = kpre + kx - ksum;
+        uint32_t ho = hpre + hx - hsum;
+#pragma unroll
+        for (int u = 0; u < kScanTiles; ++u) {
+            const uint32_t st = me[u].start;
+            if (st & 1u) dcur = 0;
+            if (i0 + u < n_tiles) { entry_state[i0 + u] = entry[u]; out_off[i0 + u] = ko; rec_base[i0 + u] = ho + ((st >> 1) & 1u); d_base[i0 + u] = dcur; }
+            ko += keep[u]; ho += me[u].hdr[entry[u] & 3u] + ((st >> 1) & 1u); dcur += dd[u];
+        }
+        __syncthreads();
+        if (t == 0) { c_t = mcompose(c_t, tall); c_k += kall; c_h += hall; c_d = dall; }
+        __syncthreads();
+    }
+    if (t == 0) { totals[0] = c_k; totals[1] = c_h; }
+}
+
+template <bool PACK>
+__global__ __launch_bounds__(kCleanThreads) void k_mixed_write(const uint8_t* __restrict__ text, uint64_t n, uint64_t n_tiles,
+                                                              const uint32_t* __restrict__ info, uint64_t fq_end, uint32_t fq_flags,
+                                                              const uint32_t* __restrict__ entry_state,
+                                                              const uint64_t* __restrict__ out_off,
+                                                              const uint32_t* __restrict__ rec_base,
+                                                              const long long* __restrict__ d_base,
+                                                              uint8_t* __restrict__ bases, uint64_t* __restrict__ rec_off,
+                                                              unsigned long long* __restrict__ bad) {
+    __shared__ uint32_t s_wave[kCleanThreads / 64];
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[kCleanTile + 16];
+    const uint32_t ti = tile_info(info, blockIdx.x, fq_end, fq_flags);
+    const bool start = ti & kTiStart;
+    const uint64_t t0 = (uint64_t)blockIdx.x * kCleanTile, p0 = t0 + (uint64_t)threadIdx.x * kCleanChunk;
+    const uint64_t obase = out_off[blockIdx.x];
+    const uint32_t sh = (uint32_t)(obase & 15u);
+    const uint32_t rb = rec_base[blockIdx.x];
+    uint32_t tile_keep;
+    if (!(ti & kTiFastq)) {
+        ChunkInfo c = load_chunk(text, n, p0);
+        const bool next_starts = blockIdx.x + 1 < n_tiles && (tile_info(info, blockIdx.x + 1, fq_end, fq_flags) & kTiStart);
+        if (threadIdx.x == kCleanThreads - 1 && next_starts) c.drop_after &= 0x7FFFu;
+        uint32_t tile_t;
+        const uint32_t pre = block_scan_transform(chunk_transform(c), s_wave, &tile_t);
+        const uint32_t entry = pre ? (pre & 1u) : (start ? 1u : (entry_state[blockIdx.x] & 1u));
+        const uint32_t keep = chunk_keep(c, entry);
+        uint32_t tile_both;
+        const uint32_t both = block_scan_add(__popc(keep) | (__popc(c.drop_after) << 16), s_wave, &tile_both);
+        tile_keep = tile_both & 0xFFFFu;
+        stage_survivors(s_out, sh, both & 0xFFFFu, c.bytes, c.valid, keep, c.drop_after, obase, rb + (both >> 16), rec_off);
+    } else {
+        const uint64_t end = t0 + (ti & kTiLim);
+        const FqChunk c = load_fq_chunk(text, n, end, p0);
+        __shared__ unsigned long long s_wave64[kCleanThreads / 64];
+        uint32_t nl_tile;
+        const uint32_t role0 = ((start ? 0u : entry_state[blockIdx.x]) + block_scan_add(__popc(c.nl), s_wave, &nl_tile)) & 3u;
+        const FqWalk w = fq_walk(c, role0);
+        // survivors, record starts and D before this lane: one scan (D in the high half, two's complement)
+        unsigned long long tile_all;
+        const unsigned long long all = block_scan_add_u64((unsigned long long)(__popc(w.keep) | (__popc(w.rs) << 16)) |
+                                                          ((unsigned long long)(uint32_t)w.d << 32), s_wave64, &tile_all);
+        const uint32_t both = (uint32_t)all;
+        const int32_t dlane = (int32_t)(uint32_t)(all >> 32);
+        tile_keep = (uint32_t)tile_all & 0xFFFFu;
+        stage_survivors(s_out, sh, both & 0xFFFFu, c.bytes, c.valid, w.keep, w.rs, obase, rb + (both >> 16), rec_off);
+        // validation: the lines that begin in this chunk, and the file's end if it lies here
+        const bool at_end = (ti & kTiEnd) && p0 < end && end <= p0 + kCleanChunk;
+        if (c.nl || at_end || (start && threadIdx.x == 0 && end > t0)) {
+            unsigned long long* my_bad = bad + ((ti >> kTiFileShift) & 0xFFu);
+            uint32_t cur = rb + (both >> 16) - 1;              // the record this chunk begins in
+            if (start && threadIdx.x == 0 && end > t0 && (c.bytes[0] & 0xFFu) != '@') atomicMin(my_bad, ((unsigned long long)cur << 8) | kFqBadHeader);
+            long long D = d_base[blockIdx.x] + dlane;
+            uint32_t role = role0, from = 0, rem = c.nl;
+            while (rem) {
+                const uint32_t j = __ffs(rem) - 1;
+                rem &= rem - 1;
+                const uint32_t seg = ((2u << j) - 1u) & ~((1u << from) - 1u);
+                if (role == 1u) {
+                    D += __popc(c.content & seg);
+                    if (!((c.fol_plus >> j) & 1u)) atomicMin(my_bad, ((unsigned long long)cur << 8) | kFqBadSeparator);
+                } else if (role == 3u) {
+                    D -= __popc(c.content & seg);
+                    if (D != 0) atomicMin(my_bad, ((unsigned long long)cur << 8) | kFqBadLength);
+                    ++cur;
+                    if (!((c.fol_at >> j) & 1u)) atomicMin(my_bad, ((unsigned long long)cur << 8) | kFqBadHeader);
+                }
+                role = (role + 1u) & 3u;
+                from = j + 1;
+            }
+            if (at_end) {
+                const uint32_t seg = 0xFFFFu & ~((1u << from) - 1u);
+                if (role == 1u) D += __popc(c.content & seg);
+                else if (role == 3u) D -= __popc(c.content & seg);
+                // the last record needs its quality line: the last non-blank line is one, or a blank line behind a
+                // separator is (an empty read)
+                if (!(role == 3u || (role == 2u && (ti & kTiBlankTail)))) atomicMin(my_bad, ((unsigned long long)cur << 8) | kFqTruncated);
+                else if (D != 0) atomicMin(my_bad, ((unsigned long long)cur << 8) | kFqBadLength);
             }
         }
-        if (blockIdx.x == 0 && threadIdx.x == 0) rec_off[0] = 0;
-        return;
     }
-    uint8_t* gbase = bases + (obase - sh);              // 16-byte aligned
-    for (uint32_t g = threadIdx.x; g * 16 < end; g += kCleanThreads) {
-        const uint32_t lo = g * 16, hi = lo + 16;
-        if (lo >= sh && hi <= end) {
-            *reinterpret_cast<uint4*>(gbase + lo) = *reinterpret_cast<const uint4*>(s_out + lo);
-        } else {                                        // first / last group of the tile: shared with the neighbours
-            for (uint32_t x = lo < sh ? sh : lo; x < (hi < end ? hi : end); ++x) gbase[x] = s_out[x];
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) rec_off[0] = 0;
+    if (start && threadIdx.x == 0 && (ti & kTiFastq ? (ti & kTiLim) != 0 : true)) rec_off[rb - 1] = obase;   // the file's first record
+    __syncthreads();
+    store_tile<PACK>(s_out, sh, tile_keep, obase, bases);
 }
 
 // copy the bases of every selected super-k-mer into one compact buffer (dst offsets = prefix sums of len)
@@ -386,8 +785,85 @@ __global__ void k_sk_lens(const spsp_superkmer* __restrict__ sk, uint32_t n_sk, 
     if (i < n_sk) lens[i] = sk[i].len;
 }
 
+void fastq_tail(const uint8_t* text, uint64_t n, uint64_t* content_end, bool* blank_tail) {
+    uint64_t e = n;
+    while (e && (text[e - 1] == '\n' || text[e - 1] == '\r')) --e;
+    // the first newline behind the content ends its last line; anything behind that newline is one blank line at least
+    const uint8_t* nl = e < n ? (const uint8_t*)memchr(text + e, '\n', (size_t)(n - e)) : nullptr;
+    *content_end = e;
+    *blank_tail = nl && (uint64_t)(nl - text) + 1 < n;
+}
+const char* fastq_rule_name(uint32_t rule) {
+    switch (rule) {
+        case kFqBadHeader: return "its header line does not start with '@'";
+        case kFqBadSeparator: return "its separator line does not start with '+'";
+        case kFqBadLength: return "its sequence and quality lines differ in length";
+        case kFqTruncated: return "it is truncated (fewer than four lines)";
+        default: return "malformed";
+    }
+}
+
+// FASTQ, or a batch that mixes FASTQ and FASTA files: the k_mixed_* launches (see above); same outputs as the FASTA form
+static int clean_mixed_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t n_tiles, bool pack, const FastqLayout* fq,
+                            uint64_t* kept_out, uint64_t* recs_out) {
+    int rc;
+    const uint32_t n_files = fq->tile_info ? fq->n_files : 1u;
+    if (n_files > 256) { set_error("too many files in one ingest"); return SPSP_ERR_ARG; }
+    if ((rc = ctx->i_tiles.reserve((size_t)(n_tiles + 1) * sizeof(MixedTileSummary)))) return rc;
+    if ((rc = ctx->i_dbase.reserve((size_t)(n_tiles + 1) * 8))) return rc;
+    if ((rc = ctx->i_fqbad.reserve((size_t)n_files * 8))) return rc;
+    const uint32_t* d_info = nullptr;
+    if (fq->tile_info) {
+        if ((rc = ctx->i_tinfo.reserve((size_t)(n_tiles + 1) * 4))) return rc;
+        if (n_tiles) SPSP_HIP(hipMemcpyAsync(ctx->i_tinfo.p, fq->tile_info, (size_t)n_tiles * 4, hipMemcpyHostToDevice, ctx->stream));
+        d_info = ctx->i_tinfo.as<uint32_t>();
+    }
+    const uint32_t fq_flags = fq->blank_tail ? kTiBlankTail : 0u;
+    SPSP_HIP(hipMemsetAsync(ctx->i_fqbad.p, 0xFF, (size_t)n_files * 8, ctx->stream));
+    uint64_t* totals = ctx->h_scalar + 4;
+    if (n_tiles) {
+        hipLaunchKernelGGL(k_mixed_tiles, dim3((uint32_t)n_tiles), dim3(kCleanThreads), 0, ctx->stream, d_text, n_text, n_tiles, d_info,
+                           fq->content_end, fq_flags, ctx->i_tiles.as<MixedTileSummary>());
+        SPSP_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_mixed_scan, dim3(1), dim3(1024), 0, ctx->stream, ctx->i_tiles.as<MixedTileSummary>(), n_tiles,
+                       ctx->i_entry.as<uint32_t>(), ctx->i_outoff.as<uint64_t>(), ctx->i_recbase.as<uint32_t>(),
+                       ctx->i_dbase.as<long long>(), totals);
+    SPSP_HIP(hipGetLastError());
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));
+    const uint64_t kept = totals[0], recs = totals[1];
+    if (recs > 0xfffffff0ull) { set_error("too many records for one call"); return SPSP_ERR_OVERFLOW; }
+    if ((rc = ctx->rec_off.reserve((size_t)(recs + 1) * 8))) return rc;
+    if (n_tiles) {
+        uint8_t* out = pack ? ctx->packed.as<uint8_t>() : ctx->bases.as<uint8_t>();
+        if (pack) hipLaunchKernelGGL(k_mixed_write<true>, dim3((uint32_t)n_tiles), dim3(kCleanThreads), 0, ctx->stream, d_text, n_text, n_tiles,
+                                     d_info, fq->content_end, fq_flags, ctx->i_entry.as<uint32_t>(), ctx->i_outoff.as<uint64_t>(),
+                                     ctx->i_recbase.as<uint32_t>(), ctx->i_dbase.as<long long>(), out, ctx->rec_off.as<uint64_t>(),
+                                     ctx->i_fqbad.as<unsigned long long>());
+        else hipLaunchKernelGGL(k_mixed_write<false>, dim3((uint32_t)n_tiles), dim3(kCleanThreads), 0, ctx->stream, d_text, n_text, n_tiles,
+                                d_info, fq->content_end, fq_flags, ctx->i_entry.as<uint32_t>(), ctx->i_outoff.as<uint64_t>(),
+                                ctx->i_recbase.as<uint32_t>(), ctx->i_dbase.as<long long>(), out, ctx->rec_off.as<uint64_t>(),
+                                ctx->i_fqbad.as<unsigned long long>());
+        SPSP_HIP(hipGetLastError());
+    }
+    // the closing offset (rec_off[0] too when there is no record); the verdicts come back with the same wait
+    const uint64_t ends[1] = {kept};
+    SPSP_HIP(hipMemcpyAsync(ctx->rec_off.as<uint64_t>() + recs, ends, 8, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<uint64_t> bad(n_files);
+    SPSP_HIP(hipMemcpyAsync(bad.data(), ctx->i_fqbad.p, (size_t)n_files * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));
+    *kept_out = kept; *recs_out = recs;
+    if (fq->tile_info) {
+        if (fq->bad) memcpy(fq->bad, bad.data(), (size_t)n_files * 8);
+    } else if (bad[0] != ~0ull) {
+        set_error("malformed FASTQ: record %llu (0-based): %s", (unsigned long long)(bad[0] >> 8), fastq_rule_name((uint32_t)(bad[0] & 0xFFu)));
+        return SPSP_ERR_FORMAT;
+    }
+    return SPSP_OK;
+}
+
 int clean_device_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint8_t** d_bases, uint64_t* n_bases,
-                      uint64_t** d_rec_off, uint32_t* n_rec, bool pack) {
+                      uint64_t** d_rec_off, uint32_t* n_rec, bool pack, const FastqLayout* fq) {
     if (((uintptr_t)d_text & 15u) != 0) { set_error("d_text must be 16-byte aligned"); return SPSP_ERR_ARG; }
     const uint64_t n_tiles = (n_text + kCleanTile - 1) / kCleanTile;
     if (n_tiles > 0x7fffffffull) { set_error("text too large for one call"); return SPSP_ERR_OVERFLOW; }
@@ -402,6 +878,13 @@ int clean_device_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uin
         SPSP_HIP(hipMemsetAsync(ctx->packed.p, 0, packed_bytes, ctx->stream));   // tile seams are ORed in; tail and halo stay zero
     } else if ((rc = ctx->bases.reserve((size_t)n_text + 64))) return rc;  // survivors never outnumber the input
     if ((rc = ctx->d_scalar.reserve(64))) return rc;
+    if (fq) {
+        uint64_t kept = 0, recs = 0;
+        if ((rc = clean_mixed_impl(ctx, d_text, n_text, n_tiles, pack, fq, &kept, &recs))) return rc;
+        *d_bases = pack ? ctx->packed.as<uint8_t>() : ctx->bases.as<uint8_t>(); *n_bases = kept;
+        *d_rec_off = ctx->rec_off.as<uint64_t>(); *n_rec = (uint32_t)recs;
+        return SPSP_OK;
+    }
     uint64_t* totals = ctx->h_scalar + 4;
     if (n_tiles) {
         hipLaunchKernelGGL(k_clean_tiles, dim3((uint32_t)n_tiles), dim3(kCleanThreads), 0, ctx->stream, d_text, n_text,
@@ -512,7 +995,47 @@ int spsp_fasta_clean_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, 
     return rc;
 }
 
-// FASTA text (host, gunzipped) -> sketch payload with ingest, scan and super-k-mer gather on the GPU:
+// FASTQ text already in HBM: its content end is found from the tail, copied back a window at a time (only the trailing
+// blank lines are looked at -- the text itself is read by the kernels alone)
+static int fastq_device_layout(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, FastqLayout* fq) {
+    uint64_t win = std::min<uint64_t>(n_text, 4096);
+    std::vector<uint8_t> tail;
+    for (;;) {
+        tail.resize((size_t)win);
+        if (win) SPSP_HIP(hipMemcpyAsync(tail.data(), d_text + (n_text - win), (size_t)win, hipMemcpyDeviceToHost, ctx->stream));
+        SPSP_HIP(hipStreamSynchronize(ctx->stream));
+        uint64_t e = 0; bool blank = false;
+        fastq_tail(tail.data(), win, &e, &blank);
+        if (e > 0 || win == n_text) { fq->content_end = n_text - win + e; fq->blank_tail = blank; return SPSP_OK; }
+        win = std::min<uint64_t>(n_text, win * 4);
+    }
+}
+
+static int fastq_clean_entry(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_out, uint64_t* n_bases, void** d_rec_off,
+                             uint32_t* n_rec, bool pack) {
+    if (!ctx || !d_out || !n_bases || !d_rec_off || !n_rec || (n_text && !d_text)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    SPSP_HIP(hipSetDevice(ctx->device));
+    if (((uintptr_t)d_text & 15u) != 0) { set_error("d_text must be 16-byte aligned"); return SPSP_ERR_ARG; }
+    FastqLayout fq;
+    int rc = fastq_device_layout(ctx, (const uint8_t*)d_text, n_text, &fq);
+    if (rc) return rc;
+    uint8_t* b = nullptr; uint64_t* o = nullptr;
+    rc = clean_device_impl(ctx, (const uint8_t*)d_text, n_text, &b, n_bases, &o, n_rec, pack, &fq);
+    *d_out = b; *d_rec_off = o;
+    return rc;
+}
+
+// FASTQ text in HBM -> the cleaned reads, one record each: the layout of spsp_fasta_clean_device / _packed_device
+int spsp_fastq_clean_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_bases, uint64_t* n_bases,
+                            void** d_rec_off, uint32_t* n_rec) {
+    return fastq_clean_entry(ctx, d_text, n_text, d_bases, n_bases, d_rec_off, n_rec, false);
+}
+int spsp_fastq_clean_packed_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_packed, uint64_t* n_bases,
+                                   void** d_rec_off, uint32_t* n_rec) {
+    return fastq_clean_entry(ctx, d_text, n_text, d_packed, n_bases, d_rec_off, n_rec, true);
+}
+
+// FASTA or FASTQ text (host, gunzipped) -> sketch payload with ingest, scan and super-k-mer gather on the GPU:
 // only the selected super-k-mers' bases (~0.2 % of the genome at -s 1000) ever come back to the host.
 int spsp_sketch_text(spsp_ctx* ctx, const spsp_params* p, double rate, const char* text, uint64_t n_text,
                      uint8_t** payload, uint64_t* payload_len, spsp_sketch_stats* stats) {
@@ -526,7 +1049,11 @@ int spsp_sketch_text(spsp_ctx* ctx, const spsp_params* p, double rate, const cha
     uint8_t* d_bases = nullptr; uint64_t* d_off = nullptr; uint64_t n_bases = 0; uint32_t n_rec = 0;
     // the ingest writes 2-bit words when the dense pass of these parameters reads them
     const bool packed = ingest_packs(p);
-    if ((rc = clean_device_impl(ctx, ctx->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed))) return rc;
+    // a text whose first byte is '@' is FASTQ: one record per read
+    FastqLayout fq;
+    const bool fastq = n_text && text[0] == '@';
+    if (fastq) fastq_tail((const uint8_t*)text, n_text, &fq.content_end, &fq.blank_tail);
+    if ((rc = clean_device_impl(ctx, ctx->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed, fastq ? &fq : nullptr))) return rc;
     t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
     spsp_superkmer* d_sk = nullptr; uint64_t n_sk = 0;
     spsp_params ps = *p;

@@ -163,6 +163,7 @@ struct spsp_ctx {
     bool pair_valid = false;
     // ingest workspace (GPU-side getLineFasta + clean_dna)
     spsp::DevBuf i_text, i_tiles, i_entry, i_outoff, i_recbase, i_lens, i_dst, i_compact;
+    spsp::DevBuf i_tinfo, i_dbase, i_fqbad;   // FASTQ / mixed batches: tile words, D at every tile, first malformed record per file
     // compare workspace
     spsp::DevBuf c_min, c_lo, c_hi, c_table, c_owner, c_rowid, c_row, c_matrix, c_inter, c_flags, c_skoff, c_slot_lo, c_slot_hi, c_slot_mn, c_part_cnt, c_recs, c_where, c_lref, c_filter, c_bits, c_sig, c_order, c_multi, scan_blocks;
     uint64_t spill_expect = 0;     // records the last unfiltered partition-form comparison had in overflowed parts (0: none) -- see spill_plan
@@ -238,8 +239,29 @@ int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, con
 // ingest (spsp_ingest.hip)
 // pack: the cleaned bases leave as 2-bit words (ctx->packed: 16 bases per dword, first base in bits 31:30, zero-filled tail
 // + 256 readable bytes) instead of ASCII (ctx->bases); *d_bases then points at the words
+// FASTQ: how the ingest reads a text that holds FASTQ (spsp_ingest.hip).  tile_info == nullptr: the whole text is one FASTQ
+// file whose content -- the text less its trailing blank lines -- ends at content_end, and a malformed record is an
+// SPSP_ERR_FORMAT of the call.  Otherwise one word per 4 KiB tile describes a batch of files (FASTA and FASTQ, each starting
+// a tile) and bad[f] receives, per file, ~0 or (the first malformed record, numbered in the batch) << 8 | rule.
+constexpr uint32_t kTiLim = 0x1FFFu;          // FASTQ: bytes of the tile that belong to the file's content (0..4096)
+constexpr uint32_t kTiFastq = 1u << 13;
+constexpr uint32_t kTiStart = 1u << 14;       // a file starts at the tile's first byte
+constexpr uint32_t kTiBlankTail = 1u << 15;   // FASTQ: a blank line follows the file's last non-blank line
+constexpr int kTiFileShift = 16;              // bits 16..23: the file's index in the batch
+constexpr uint32_t kTiEnd = 1u << 24;         // FASTQ: the file's content ends inside the tile
+enum { kFqBadHeader = 1, kFqBadSeparator = 2, kFqBadLength = 3, kFqTruncated = 4 };
+struct FastqLayout {
+    const uint32_t* tile_info = nullptr;      // host
+    uint64_t content_end = 0;
+    bool blank_tail = false;
+    uint32_t n_files = 1;
+    uint64_t* bad = nullptr;                  // host, n_files words
+};
+// the content end of a FASTQ text (behind its last byte that is neither '\n' nor '\r') and whether a blank line follows it
+void fastq_tail(const uint8_t* text, uint64_t n, uint64_t* content_end, bool* blank_tail);
+const char* fastq_rule_name(uint32_t rule);
 int clean_device_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint8_t** d_bases, uint64_t* n_bases,
-                      uint64_t** d_rec_off, uint32_t* n_rec, bool pack = false);
+                      uint64_t** d_rec_off, uint32_t* n_rec, bool pack = false, const FastqLayout* fq = nullptr);
 // does the dense pass chosen for these parameters read 2-bit input directly? (spsp_scan.hip)
 bool scan_reads_packed(const spsp_params* p);
 bool build_on_device(uint64_t places);    // the sketch builder on the device from 5 x 10^5 k-mer places on (SPSP_BUILD=device / host pins it)
