@@ -24,16 +24,11 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <vector>
 
 #include "spsp_internal.h"
 #include "spsp_device.h"
-
-#ifndef SPSP_EXP
-#define SPSP_EXP 0          // timing experiments (tools/exp/build_variant.sh): kernels with parts of their work left out; 0 in the product
-#endif
 
 namespace spsp {
 
@@ -321,7 +316,7 @@ __global__ void k_fill_sparse(Keys K, const uint64_t* __restrict__ sk_off, uint3
 
 constexpr int kSparseCols = 16384;
 constexpr int kFlags = 8;   // [0] unsorted input, [1] fingerprint collision, [2] n_rows (dictionary forms) / records of overflowed parts (partition
-                            // form: sizes the spill), [3] malformed slot, [4] slot overflow, [5] table full, [6] a key part overflowed its
+                            // form: sizes the spill), [3] / [4] unused, [5] table full, [6] a key part overflowed its
                             // capacity (partition form), [7] records dealt into parts -- these eight travel to the host with every job.
                             // Device-side words behind them (16 in all, cleared by k_parts_prepare): [8] u16 of spilled lists handed out,
                             // [9] bit columns handed out, [10] / [11] k_row_order's verdict, [12] / [13] records with a list / records in a
@@ -400,19 +395,8 @@ __global__ __launch_bounds__(T) void k_accumulate_sparse(const uint32_t* __restr
         for (uint32_t x = threadIdx.x; x < ((cols << copies_log2) >> (HALF ? 1 : 0)); x += T) s_cnt[x] = 0;
         __syncthreads();
     }
-#if SPSP_EXP & 8
-    uint32_t exp_chk = 0;
-#endif
     const uint32_t lane = threadIdx.x & 63u;
     auto count = [&](uint32_t jj) {
-#if SPSP_EXP & 8
-        exp_chk += jj;                                        // (timing experiment: the lists are read, nothing is added in LDS)
-        return;
-#endif
-#if SPSP_EXP & 64
-        if (jj > i && jj - col0 < cols) { atomicAdd(&s_cnt[(threadIdx.x * 33u + jj) & 4095u], 1u); }   // (timing experiment: adds without same-address conflicts)
-        return;
-#endif
         if (jj > i && jj - col0 < cols) {
             const uint32_t idx = ((jj - col0) << copies_log2) + mine;
             if (TOUCH) {
@@ -447,14 +431,7 @@ __global__ __launch_bounds__(T) void k_accumulate_sparse(const uint32_t* __restr
                 // (multi: a bit per record slot of the parts -- has the key a list? -- in front of the list reference's miss)
                 bool fetch = at[r] != kNoWhere;
                 if (fetch && use_multi && at[r] < (multi_slots & 0x7fffffffu)) fetch = (multi[at[r] >> 5] >> (at[r] & 31u)) & 1u;
-#if SPSP_EXP & 32
-                refs[r] = fetch && at[r] == 0xfffffff1u ? list_of_entry[at[r]] : kNoList;   // (timing experiment: no reference read)
-#else
                 refs[r] = fetch ? list_of_entry[at[r]] : kNoList;
-#endif
-#if SPSP_EXP & 16
-                if (refs[r] != 0xfffffff2u) refs[r] = kNoList;                              // (timing experiment: no list read)
-#endif
             }
         } else {
 #pragma unroll
@@ -534,9 +511,6 @@ __global__ __launch_bounds__(T) void k_accumulate_sparse(const uint32_t* __restr
         }
         }
     }
-#if SPSP_EXP & 8
-    if (exp_chk == 0x12345u) s_cnt[1] = exp_chk;
-#endif
     __syncthreads();
     if (TOUCH) {
         const uint32_t nt = s_nt;
@@ -1023,24 +997,15 @@ __global__ __launch_bounds__(kScatThreads, 4) void k_parts_scatter_tiles(Keys K,
         __syncthreads();
         for (uint32_t p = t; p < n_parts; p += kScatThreads) {
             const uint32_t c = hist[p];
-#if SPSP_EXP & 1
-            if (c) hist[p] = (blockIdx.x * 29u) % (cap / 2);     // (timing experiment: no reservation -- results are wrong)
-#else
             if (c) hist[p] = atomicAdd(&part_cnt[p], c);
-#endif
         }
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < E; ++u) {
             if (!keep[u]) continue;
             const uint32_t part = pr[u] & 0x7fffu, at = hist[part] + (pr[u] >> 15);
-#if !(SPSP_EXP & 4)
             where[ent[u]] = at < cap ? part * cap + at : kNoWhere;
-#endif
             if (at >= cap) continue;
-#if SPSP_EXP & 2
-            continue;
-#endif
             uint64_t* r = recs + ((uint64_t)part * cap + at) * W;
             if (HAS_HI) { r[0] = lo[u]; r[1] = (uint64_t)mn[u] | ((uint64_t)sk_of[u] << 32); r[2] = hi[u]; }
             else *reinterpret_cast<ulonglong2*>(r) = make_ulonglong2(lo[u], (uint64_t)mn[u] | ((uint64_t)sk_of[u] << 32));
@@ -1570,11 +1535,17 @@ struct ComparePlan {
     const uint32_t* row_order = nullptr; // rows in the order of their sketches' min-hash (k_row_order), or null
     const uint32_t* multi = nullptr;     // partition form: one bit per record slot -- has the record's key a list? (k_parts_group)
     uint32_t multi_slots = 0;
+    // the keys and the launch geometry over them (compare_device_begin_inner); the device offsets at sk_begin are followed by
+    // the sub-chunk table and the tile table (stage_sk_off)
+    Keys K{};
+    dim3 grid_all;                       // one thread per entry of the longest sketch, one row of workgroups per sketch
+    const uint32_t* sub_sk = nullptr;    // sketch holding entry c * kScatSub
+    const uint64_t* tile_info = nullptr; // k_parts_scatter_tiles: n_tiles tiles over blocks of tile_sk sketches
+    uint32_t n_tiles = 0, tile_sk = 0;
+    uint64_t e_own = 0;                  // first entry the scatter deals: the chunk of the first owned row
 };
 struct CompareJob {
     ComparePlan P;
-    std::function<int(uint64_t seed, uint64_t fp_mask, uint32_t log2cap, uint32_t passes, uint32_t pass)> insert;
-    std::function<int(uint64_t seed, uint64_t fp_mask, uint32_t log2cap, uint32_t W, bool direct_rows, uint32_t passes, uint32_t pass)> fill;
     uint32_t log2cap = 0, W = 0, lanes_per_key = 64, sblocks = 0;
     uint64_t cap = 0, seed = 0x5350535053505350ULL;
     bool speculative = false;
@@ -1582,20 +1553,15 @@ struct CompareJob {
     bool clear_all_flags = false;   // no pass before the first attempt has written flags
     bool direct_rows = false;   // speculative and every row owned from entry 0: row id = the owner's entry index
     int attempt = 0;
-    // sparse form (many sketches, all rows owned): set by the flat entry point, see k_insert_sparse
-    std::function<int(uint64_t seed, uint64_t fp_mask, uint32_t log2cap)> insert_sparse;
-    std::function<int()> fill_sparse;
+    bool empty = false;             // the begin call had nothing to compare: the end call only drops the job
+    // sparse form (many sketches, all rows owned): see k_insert_sparse
     bool sparse = false;
     uint32_t passes = 1, pass = 0;  // large builds: the keys are split into classes and the dictionary + colour
                                     // matrix are built class by class, so the matrix never exceeds its budget
-    // partition form (flat entry point): see k_parts_scatter
-    std::function<int(uint32_t n_parts, bool small, bool filtered, uint32_t fmask, uint32_t classes, uint32_t cls)> scatter_parts;
-    std::function<int(uint32_t n_parts, const SpillPlan&, bool want_multi)> group_parts;
-    std::function<int(uint32_t n_parts)> group_small;     // small problems: grouping + counting in one kernel (k_parts_group_small)
+    // partition form: see k_parts_scatter; small problems: grouping + counting in one kernel (k_parts_group_small)
     bool parts = false, small = false;
     uint32_t n_parts = 0, parts_attempt = 0, n_sub = 0;
     // filtered form (row-partitioned calls): Bloom filter over the owned sketches' keys in front of the scatter
-    std::function<int(uint32_t fmask)> build_filter;
     bool filtered = false;
     uint32_t filter_words = 0;
     uint64_t parts_entries = 0;     // records the parts are sized for
@@ -1609,9 +1575,8 @@ struct CompareJob {
     uint64_t S_behind = 0;          // keys of the first owned row and later sketches: what the scatter deals
     // spill (partition form, unfiltered): the records of parts that overflow are grouped in a table in HBM (k_spill_insert)
     SpillPlan spill;                // room = 0: not part of this attempt
-    std::function<int(uint32_t n_parts, const SpillPlan&, int phase, uint32_t classes, uint32_t cls)> spill_parts;   // phase 0: buffers cleared (in front of the scatter), 1: the kernels (behind the grouping)
 };
-// flags: [0] unsorted input, [1] fingerprint collision, [2] n_rows, [3] malformed slot, [4] slot overflow, [5] table full
+// flags: [0] unsorted input, [1] fingerprint collision, [2] n_rows, [5] table full (see kFlags)
 static uint64_t job_fp_mask(const CompareJob& J) {
     // test hook: fingerprints of the first attempt cut to a few bits, so distinct keys collide and the retry runs
     static const char* dbg_fp = getenv("SPSP_DEBUG_FP_BITS");
@@ -1709,6 +1674,169 @@ static int launch_accumulate_sparse(spsp_ctx* ctx, const ComparePlan& P, uint32_
     if (direct) SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + 12, ctx->cells_req.count, 8, hipMemcpyDeviceToHost, ctx->stream));
     return SPSP_OK;
 }
+
+// The launches of the forms below.  Each takes the key geometry from the plan, this attempt's choices from the job, and the
+// buffers as the context holds them now (an attempt may have grown them).
+static SlotKeys slot_keys(spsp_ctx* ctx) {
+    return SlotKeys{ctx->c_slot_lo.as<uint64_t>(), ctx->c_slot_hi.as<uint64_t>(), ctx->c_slot_mn.as<uint32_t>()};
+}
+static int launch_insert(spsp_ctx* ctx, const CompareJob& J) {
+    const ComparePlan& P = J.P;
+    Keys K = P.K; K.fp_mask = job_fp_mask(J);
+    hipLaunchKernelGGL(k_insert, P.grid_all, dim3(256), 0, ctx->stream, K, P.sk_begin, P.n, P.S_entries, P.row_first, P.row_stride,
+                       P.row_limit, J.seed, ctx->c_table.as<uint64_t>(), J.log2cap, ctx->c_owner.as<uint32_t>(), slot_keys(ctx),
+                       ctx->c_flags.as<uint32_t>(), J.passes, J.pass);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+static int launch_fill(spsp_ctx* ctx, const CompareJob& J) {
+    const ComparePlan& P = J.P;
+    Keys K = P.K; K.fp_mask = job_fp_mask(J);
+    hipLaunchKernelGGL(k_fill, P.grid_all, dim3(256), 0, ctx->stream, K, P.sk_begin, P.n, P.S_entries, P.row_first, P.row_stride,
+                       P.row_limit, J.seed, ctx->c_table.as<uint64_t>(), J.log2cap, ctx->c_owner.as<uint32_t>(),
+                       J.direct_rows ? (const uint32_t*)nullptr : ctx->c_rowid.as<uint32_t>(), slot_keys(ctx), J.W,
+                       ctx->c_matrix.as<unsigned long long>(), ctx->c_row.as<uint32_t>(), ctx->c_flags.as<uint32_t>(), J.passes, J.pass);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+static int launch_insert_sparse(spsp_ctx* ctx, const CompareJob& J) {
+    const ComparePlan& P = J.P;
+    Keys K = P.K; K.fp_mask = job_fp_mask(J);
+    hipLaunchKernelGGL(k_insert_sparse, P.grid_all, dim3(256), 0, ctx->stream, K, P.sk_begin, J.seed, ctx->c_table.as<uint64_t>(),
+                       J.log2cap, ctx->c_owner.as<uint32_t>(), slot_keys(ctx), ctx->c_row.as<uint32_t>(), ctx->c_flags.as<uint32_t>());
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+static int launch_fill_sparse(spsp_ctx* ctx, const CompareJob& J) {
+    const ComparePlan& P = J.P;
+    hipLaunchKernelGGL(k_fill_sparse, P.grid_all, dim3(256), 0, ctx->stream, P.K, P.sk_begin, ctx->c_row.as<uint32_t>(), slot_keys(ctx),
+                       ctx->c_owner.as<uint32_t>(), ctx->c_rowid.as<uint32_t>(), ctx->c_matrix.as<uint16_t>(), ctx->c_flags.as<uint32_t>());
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+// filtered form: the Bloom filter over the owned sketches' keys
+static int launch_filter(spsp_ctx* ctx, const CompareJob& J) {
+    const ComparePlan& P = J.P;
+    uint64_t max_own = 0;
+    for (uint32_t i = P.row_first; i < P.row_limit; i += P.row_stride) max_own = std::max(max_own, ctx->h_skoff[i + 1] - ctx->h_skoff[i]);
+    const dim3 grid((uint32_t)std::max<uint64_t>(1, (max_own + 255) / 256), P.n_own);
+    auto kern = J.has_hi ? &k_parts_filter<true> : &k_parts_filter<false>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, ctx->stream, P.K, P.sk_begin, P.n, P.row_first, P.row_stride, P.row_limit,
+                       ctx->c_filter.as<uint32_t>(), J.filter_words - 1);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+static int launch_scatter(spsp_ctx* ctx, const CompareJob& J) {
+    const ComparePlan& P = J.P;
+    const uint32_t n_parts = J.n_parts, cap = J.small ? (uint32_t)kSmallCap : (uint32_t)kPartCap;
+    int rc;
+    if ((rc = ctx->c_recs.reserve((size_t)n_parts * cap * (J.has_hi ? 24 : 16)))) return rc;
+    if (!J.small && (rc = ctx->c_where.reserve((size_t)P.S_entries * 4 + 16))) return rc;
+    if (!J.small && (rc = ctx->c_lref.reserve((size_t)n_parts * kPartCap * 4))) return rc;
+    uint32_t* where = J.small ? nullptr : ctx->c_where.as<uint32_t>();
+    uint32_t* flags = ctx->c_flags.as<uint32_t>();
+    static_assert(kMaxKeyParts < (1 << 15), "k_parts_scatter keeps the part in 15 bits of its (part, rank) word");
+    if (n_parts > (uint32_t)kMaxKeyParts) { set_error("internal: %u key parts exceed the scatter's limit of %d", n_parts, kMaxKeyParts); return SPSP_ERR_ARG; }
+    // tiles: the general partition form (a filtered call's scatter starts at its first owned row's chunk and drops most of
+    // what it reads; the small form keeps no `where` and its 100 sketches are one block anyway)
+    if (!J.small && !J.filtered && P.n_tiles) {
+        const size_t lds_t = (size_t)n_parts * 4;
+        if (lds_t > 48 * 1024 && !ctx->attr_scatter_tiles_set) {
+            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter_tiles<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
+            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter_tiles<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
+            ctx->attr_scatter_tiles_set = true;
+        }
+        auto kern = J.has_hi ? &k_parts_scatter_tiles<true> : &k_parts_scatter_tiles<false>;
+        hipLaunchKernelGGL(kern, dim3(P.n_tiles), dim3(kScatThreads), lds_t, ctx->stream, P.K, P.sk_begin, P.n, P.tile_info, P.tile_sk, n_parts,
+                           cap, ctx->c_part_cnt.as<uint32_t>(), ctx->c_recs.as<uint64_t>(), where, flags, !ctx->keys_unordered, P.row_first, J.classes, J.cls);
+        SPSP_HIP(hipGetLastError());
+        return SPSP_OK;
+    }
+    const uint32_t per_wg = 4u * kScatThreads;
+    const dim3 grid((uint32_t)((P.S_entries - P.e_own + per_wg - 1) / per_wg));
+    const uint32_t* filter = J.filtered ? ctx->c_filter.as<uint32_t>() : nullptr;
+    const size_t lds = (size_t)n_parts * 4;
+    if (lds > 48 * 1024 && !ctx->attr_scatter_set) {
+        SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
+        SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
+        ctx->attr_scatter_set = true;
+    }
+    auto kern = J.has_hi ? &k_parts_scatter<true, 4> : &k_parts_scatter<false, 4>;
+    hipLaunchKernelGGL(kern, grid, dim3(kScatThreads), lds, ctx->stream, P.K, P.sk_begin, P.n, P.sub_sk, P.S_entries, n_parts, cap,
+                       ctx->c_part_cnt.as<uint32_t>(), ctx->c_recs.as<uint64_t>(), where, flags, !ctx->keys_unordered, filter,
+                       J.filter_words - 1, P.e_own, P.row_first, P.row_stride, P.row_limit, J.classes, J.cls);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+static int launch_group(spsp_ctx* ctx, const CompareJob& J) {
+    const SpillPlan& sp = J.spill;
+    const size_t lds = (size_t)kPartCap * (8 + (J.has_hi ? 8 : 0) + 4) + (size_t)kPartSlots * 4 + 16;
+    // (a spill attempt: keys of many holders get columns here too -- a part they do not overflow would otherwise list them)
+    const uint32_t t_bits = sp.room ? sp.t_bits : 0xffffffffu, max_cols = sp.room ? sp.max_cols : 0u;
+    unsigned long long* bits = (sp.room && sp.max_cols) ? ctx->c_bits.as<unsigned long long>() : (unsigned long long*)nullptr;
+    if (J.want_multi) { const int rm = ctx->c_multi.reserve((size_t)J.n_parts * kPartCap / 8 + 64); if (rm) return rm; }
+    unsigned long long* multi = J.want_multi ? ctx->c_multi.as<unsigned long long>() : (unsigned long long*)nullptr;
+    auto kern = J.has_hi ? &k_parts_group<true> : &k_parts_group<false>;
+    bool& attr_set = J.has_hi ? ctx->attr_group_hi_set : ctx->attr_group_set;
+    if (!attr_set) {
+        SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(J.n_parts), dim3(kGroupThreads), lds, ctx->stream, ctx->c_recs.as<uint64_t>(), ctx->c_part_cnt.as<uint32_t>(),
+                       ctx->c_matrix.as<uint16_t>(), ctx->c_lref.as<uint32_t>(), ctx->c_flags.as<uint32_t>(), t_bits, max_cols, bits, J.P.n, multi);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+// k <= 32 only
+static int launch_group_small(spsp_ctx* ctx, const CompareJob& J) {
+    const size_t lds = (size_t)kSmallCap * (8 + 4) + (size_t)kSmallHl + (size_t)kSmallSlots * 4 + (size_t)kSmallN * kSmallN * 2 + 16;
+    if (!ctx->attr_small_set) {
+        SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_group_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ctx->attr_small_set = true;
+    }
+    hipLaunchKernelGGL(k_parts_group_small, dim3(J.n_parts), dim3(kGroupThreads), lds, ctx->stream, ctx->c_recs.as<uint64_t>(),
+                       ctx->c_part_cnt.as<uint32_t>(), J.P.n, J.P.d_inter, ctx->c_flags.as<uint32_t>());
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+// the spill of this attempt: phase 0 clears its buffers (in front of the scatter), phase 1 queues its kernels (behind the grouping)
+static int launch_spill(spsp_ctx* ctx, const CompareJob& J, int phase) {
+    const ComparePlan& P = J.P;
+    const SpillPlan& sp = J.spill;
+    const uint64_t slots = 1ull << sp.log2cap;
+    int rc;
+    if (phase == 0) {
+        if ((rc = ctx->c_table.reserve((size_t)slots * 4)) || (rc = ctx->c_owner.reserve((size_t)slots * 4)) || (rc = ctx->c_rowid.reserve((size_t)slots * 4))) return rc;
+        SPSP_HIP(hipMemsetAsync(ctx->c_table.p, 0, (size_t)slots * 4, ctx->stream));
+        SPSP_HIP(hipMemsetAsync(ctx->c_owner.p, 0, (size_t)slots * 4, ctx->stream));
+        if (sp.max_cols) {
+            const size_t bytes = (size_t)((sp.max_cols + 63) / 64) * P.n * 8;
+            if ((rc = ctx->c_bits.reserve(bytes))) return rc;
+            SPSP_HIP(hipMemsetAsync(ctx->c_bits.p, 0, bytes, ctx->stream));
+        }
+        return SPSP_OK;
+    }
+    const dim3 grid((uint32_t)((P.S_entries - P.e_own + kSpillThreads - 1) / kSpillThreads));
+    uint32_t *tbl = ctx->c_table.as<uint32_t>(), *cnt = ctx->c_owner.as<uint32_t>(), *off = ctx->c_rowid.as<uint32_t>();
+    uint32_t *where = ctx->c_where.as<uint32_t>(), *rank_of = ctx->c_row.as<uint32_t>(), *flags = ctx->c_flags.as<uint32_t>();
+    const uint32_t* part_cnt = ctx->c_part_cnt.as<uint32_t>();
+    const uint32_t room = (uint32_t)sp.room;
+    auto insert = J.has_hi ? &k_spill_insert<true> : &k_spill_insert<false>;
+    hipLaunchKernelGGL(insert, grid, dim3(kSpillThreads), 0, ctx->stream, P.K, P.sk_begin, P.n, P.S_entries, P.e_own, P.row_first, J.n_parts,
+                       part_cnt, tbl, sp.log2cap, cnt, where, rank_of, room, flags, J.classes, J.cls, P.sub_sk);
+    SPSP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_spill_ranges, dim3((uint32_t)((slots + (uint64_t)kRowThreads * kRowSlots - 1) / ((uint64_t)kRowThreads * kRowSlots))), dim3(kRowThreads), 0, ctx->stream,
+                       (const uint32_t*)cnt, slots, off, ctx->c_matrix.as<uint16_t>(), sp.ids_base, sp.ids_room, ctx->c_lref.as<uint32_t>() + sp.lref_base, sp.t_bits, sp.max_cols, room, flags);
+    SPSP_HIP(hipGetLastError());
+    unsigned long long* bits = sp.max_cols ? ctx->c_bits.as<unsigned long long>() : (unsigned long long*)nullptr;
+    auto fill = J.has_hi ? &k_spill_fill<true> : &k_spill_fill<false>;
+    hipLaunchKernelGGL(fill, grid, dim3(kSpillThreads), 0, ctx->stream, P.K, P.sk_begin, P.n, P.S_entries, P.e_own, P.row_first, J.n_parts,
+                       part_cnt, cnt, (const uint32_t*)off, ctx->c_matrix.as<uint16_t>(), sp.ids_base, sp.lref_base, bits, where,
+                       (const uint32_t*)rank_of, room, (const uint32_t*)flags, J.classes, J.cls, P.sub_sk);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+
 static int job_queue_flags(spsp_ctx* ctx);
 // partition form: prepare -> scatter -> group -> row sums, queued in one go (small problems: prepare -> scatter -> group + count)
 static int job_parts(spsp_ctx* ctx, CompareJob& J) {
@@ -1729,8 +1857,8 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
                        J.filtered ? ctx->c_filter.as<uint4>() : (uint4*)nullptr, filter_vec);
     SPSP_HIP(hipGetLastError());
     if ((rc = ctx->ev_begin(kEvScatter))) return rc;
-    if (J.filtered && (rc = J.build_filter(J.filter_words - 1))) return rc;
-    if (J.spill.room && !J.small && (rc = J.spill_parts(J.n_parts, J.spill, 0, J.classes, J.cls))) return rc;
+    if (J.filtered && (rc = launch_filter(ctx, J))) return rc;
+    if (J.spill.room && !J.small && (rc = launch_spill(ctx, J, 0))) return rc;
     // rows of similar sketches side by side for the row sums (their holder lists meet in one L2), whatever order the sketches
     // came in: every sketch's smallest key hash from the records of the first parts (k_row_signature), the order they give
     // (k_row_order).
@@ -1747,14 +1875,14 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
     if (ordered && ctx->order_quiet > 0) { --ctx->order_quiet; ordered = false; }
     J.ordered = ordered;
     if (ordered && ((rc = ctx->c_sig.reserve((size_t)J.P.n * 8)) || (rc = ctx->c_order.reserve((size_t)J.P.n * 4)))) return rc;
-    if ((rc = J.scatter_parts(J.n_parts, J.small, J.filtered, J.filter_words - 1, J.classes, J.cls))) return rc;
+    if ((rc = launch_scatter(ctx, J))) return rc;
     if (ordered) {
         const hipStream_t side = ctx->stream;          // (on a stream of their own, beside the grouping kernel, these three short launches cost the same 0.06 ms: measured)
         SPSP_HIP(hipMemsetAsync(ctx->c_sig.p, 0xff, (size_t)J.P.n * 8, side));
         unsigned long long* sig = ctx->c_sig.as<unsigned long long>();
         const uint32_t sp = std::min<uint32_t>(J.n_parts, kSigParts);
-        if (J.has_hi) hipLaunchKernelGGL(k_row_signature<true>, dim3(sp), dim3(1024), 0, side, ctx->c_recs.as<uint64_t>(), ctx->c_part_cnt.as<uint32_t>(), (uint32_t)kPartCap, sig);
-        else hipLaunchKernelGGL(k_row_signature<false>, dim3(sp), dim3(1024), 0, side, ctx->c_recs.as<uint64_t>(), ctx->c_part_cnt.as<uint32_t>(), (uint32_t)kPartCap, sig);
+        auto signature = J.has_hi ? &k_row_signature<true> : &k_row_signature<false>;
+        hipLaunchKernelGGL(signature, dim3(sp), dim3(1024), 0, side, ctx->c_recs.as<uint64_t>(), ctx->c_part_cnt.as<uint32_t>(), (uint32_t)kPartCap, sig);
         static_assert(kOrderMost == kSparseCols, "the order is made for comparisons of one column block");
         if (!ctx->attr_order_set) {
             SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_row_order), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((kOrderBuckets + kOrderMost) * 4)));
@@ -1773,8 +1901,8 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
     if (dbg_multi && dbg_multi[0] == '0') J.want_multi = false;
     else if (dbg_multi && dbg_multi[0] == '1') {}
     else if (J.want_multi && ctx->multi_quiet > 0) { --ctx->multi_quiet; J.want_multi = false; }
-    if ((rc = J.small ? J.group_small(J.n_parts) : J.group_parts(J.n_parts, J.spill, J.want_multi))) return rc;
-    if (J.spill.room && !J.small && (rc = J.spill_parts(J.n_parts, J.spill, 1, J.classes, J.cls))) return rc;
+    if ((rc = J.small ? launch_group_small(ctx, J) : launch_group(ctx, J))) return rc;
+    if (J.spill.room && !J.small && (rc = launch_spill(ctx, J, 1))) return rc;
     if ((rc = ctx->ev_end(kEvGroup))) return rc;
     if (J.small) return job_queue_flags(ctx);             // (no later kernel forwards the flags)
     if ((rc = ctx->ev_begin(kEvAccumulate))) return rc;
@@ -1810,11 +1938,11 @@ static int job_sparse(spsp_ctx* ctx, CompareJob& J) {
                        (J.attempt == 0 && J.clear_all_flags) ? 16u : 3u,
                        (const uint64_t*)ctx->h_skoff, ctx->c_skoff.as<uint64_t>(), J.n_skoff);
     SPSP_HIP(hipGetLastError());
-    if ((rc = J.insert_sparse(J.seed, job_fp_mask(J), J.log2cap))) return rc;
+    if ((rc = launch_insert_sparse(ctx, J))) return rc;
     hipLaunchKernelGGL(k_assign_ranges, dim3(J.sblocks), dim3(kRowThreads), 0, ctx->stream, ctx->c_owner.as<uint32_t>(), J.cap,
                        ctx->c_rowid.as<uint32_t>(), ctx->c_matrix.as<uint16_t>(), flags + 2);
     SPSP_HIP(hipGetLastError());
-    if ((rc = J.fill_sparse())) return rc;
+    if ((rc = launch_fill_sparse(ctx, J))) return rc;
     if ((rc = ctx->ev_begin(kEvAccumulate))) return rc;
     if ((rc = launch_accumulate_sparse(ctx, P, flags))) return rc;
     if ((rc = ctx->ev_end(kEvAccumulate))) return rc;
@@ -1833,10 +1961,10 @@ static int job_front(spsp_ctx* ctx, CompareJob& J) {
     const uint64_t want = (t_vec + m_vec + 255) / 256, cap_blocks = (uint64_t)ctx->n_cu * 8;
     hipLaunchKernelGGL(k_prepare, dim3((uint32_t)std::max<uint64_t>(1, std::min(want, cap_blocks))), dim3(256), 0, ctx->stream,
                        ctx->c_table.as<uint4>(), t_vec, ctx->c_matrix.as<uint4>(), m_vec, flags,
-                       (J.attempt == 0 && J.clear_all_flags) ? 16u : 3u,    // [3], [4] belong to the slot index pass
+                       (J.attempt == 0 && J.clear_all_flags) ? 16u : 3u,    // a retry clears the words the build writes again
                        (const uint64_t*)ctx->h_skoff, ctx->c_skoff.as<uint64_t>(), J.n_skoff);
     SPSP_HIP(hipGetLastError());
-    if ((rc = J.insert(J.seed, job_fp_mask(J), J.log2cap, J.passes, J.pass))) return rc;
+    if ((rc = launch_insert(ctx, J))) return rc;
     if (!J.direct_rows) {
         hipLaunchKernelGGL(k_assign_rows, dim3(J.sblocks), dim3(kRowThreads), 0, ctx->stream, ctx->c_table.as<uint64_t>(), J.cap,
                            ctx->c_rowid.as<uint32_t>(), flags + 2);
@@ -1852,7 +1980,7 @@ static int job_back(spsp_ctx* ctx, CompareJob& J, uint64_t rows) {
         if ((rc = ctx->c_matrix.reserve((size_t)rows * J.W * 8))) return rc;
         SPSP_HIP(hipMemsetAsync(ctx->c_matrix.p, 0, (size_t)rows * J.W * 8, ctx->stream));
     }
-    if ((rc = J.fill(J.seed, job_fp_mask(J), J.log2cap, J.W, J.direct_rows, J.passes, J.pass))) return rc;
+    if ((rc = launch_fill(ctx, J))) return rc;
     if ((rc = ctx->ev_begin(kEvAccumulate))) return rc;
     hipLaunchKernelGGL(k_accumulate, dim3((J.W + 63) / 64, P.n_own), dim3(kAccThreads), 0, ctx->stream,
                        ctx->c_row.as<uint32_t>(), ctx->c_matrix.as<uint64_t>(), J.W, J.lanes_per_key, P.sk_begin, P.sk_end,
@@ -1873,8 +2001,6 @@ static int job_wait_flags(spsp_ctx* ctx, uint32_t* h_flags) {
     SPSP_HIP(hipEventSynchronize(ctx->compare_done));
     memcpy(h_flags, ctx->h_scalar + 8, kFlags * sizeof(uint32_t));
     if (h_flags[5]) { set_error("dictionary table overflow (internal sizing error)"); return SPSP_ERR_HIP; }
-    if (h_flags[3]) { set_error("malformed exchange slot (header, sketch count or key count does not match)"); return SPSP_ERR_FORMAT; }
-    if (h_flags[4]) { set_error("an exchange slot overflowed its capacity: partition again with a larger slot_cap"); return SPSP_ERR_OVERFLOW; }
     if (h_flags[0] && !ctx->keys_unordered) { set_error("sketch keys must be strictly increasing by (minimizer, kmer_hi, kmer_lo)"); return SPSP_ERR_ARG; }
     return SPSP_OK;
 }
@@ -1894,7 +2020,7 @@ static int job_begin_dictionary(spsp_ctx* ctx, CompareJob* J) {
     // many sketches, every row owned: sketch lists instead of colour rows (SPSP_DEBUG_SPARSE=1/0 forces the choice)
     static const char* dbg_sparse = getenv("SPSP_DEBUG_SPARSE");
     const bool all_owned = P.row_stride == 1 && P.row_first == 0 && P.row_limit >= P.n && P.n_own == P.n;
-    J->sparse = J->insert_sparse && all_owned && 8 * P.S_entries < (1ull << 29) &&
+    J->sparse = all_owned && 8 * P.S_entries < (1ull << 29) &&
                 (dbg_sparse ? atoi(dbg_sparse) != 0 : (J->W >= 64 && !dbg_budget));
     if (J->sparse) J->speculative = true;       // queued in one go, checked once
     // Large builds: the colour matrix is rows x N bits and grows with N * (distinct keys) -- at tens of thousands of
@@ -1961,7 +2087,7 @@ static bool spill_enabled() {
 }
 static bool spill_plan(const CompareJob& J, uint64_t records, SpillPlan* sp) {
     if (!spill_enabled()) return false;
-    if (!J.spill_parts || J.small || J.filtered || records == 0) return false;
+    if (J.small || J.filtered || records == 0) return false;
     SpillPlan P;
     P.room = std::min<uint64_t>(records, J.P.S_entries);
     P.log2cap = 10;
@@ -1992,7 +2118,7 @@ static int compare_job_begin(spsp_ctx* ctx, CompareJob* job) {
     // (with several classes, half the parts a single one may take: the lists of a spill fit behind them, spill_plan)
     J->classes = dbg_classes ? (uint32_t)std::max(1, atoi(dbg_classes))
                              : parts_for(P.S_entries, 0) <= (uint32_t)kMaxKeyParts ? 1u : (uint32_t)((parts_for(P.S_entries, 0) + kMaxKeyParts / 2 - 1) / (kMaxKeyParts / 2));
-    J->parts = J->scatter_parts && (dbg_parts ? atoi(dbg_parts) != 0 : !hooks) && J->classes <= 256;
+    J->parts = (dbg_parts ? atoi(dbg_parts) != 0 : !hooks) && J->classes <= 256;
     if (J->parts) {
         J->speculative = true;                      // queued in one go, checked once
         // small problems (bench.py's 100 sketches): one kernel groups and counts.  Every row must be owned (the parts
@@ -2001,7 +2127,7 @@ static int compare_job_begin(spsp_ctx* ctx, CompareJob* job) {
         // ... and its parts are half the size, so the part count is checked on its own: the scatter's LDS counters and
         // the 15 part bits of its (part, rank) word hold kMaxKeyParts parts, not more (two sketches of 3 x 10^7 keys each
         // would otherwise ask for 41 000)
-        J->small = J->group_small && !small_off && !dbg_mean_set() && P.n <= (uint32_t)kSmallN && P.n_own == P.n && P.row_first == 0 && P.row_stride == 1 &&
+        J->small = !J->has_hi && !small_off && !dbg_mean_set() && P.n <= (uint32_t)kSmallN && P.n_own == P.n && P.row_first == 0 && P.row_stride == 1 &&
                    P.row_limit >= P.n && parts_small(P.S_entries) <= (uint32_t)kMaxKeyParts;
         if (ctx->spill_expect) J->small = false;     // (the context's last comparison overflowed its parts: straight to the form that spills)
         // row-partitioned call that owns at most 3/4 of the keys: the other sketches' keys go through a filter first
@@ -2012,7 +2138,7 @@ static int compare_job_begin(spsp_ctx* ctx, CompareJob* job) {
         static const char* dbg_filter = getenv("SPSP_DEBUG_FILTER");
         const uint64_t S_behind = P.S_entries - ctx->h_skoff[std::min(P.row_first, P.n)];   // keys of the first owned row and later sketches
         const bool pays = ctx->filter_ratio * (double)P.S_own <= 0.5 * (double)S_behind || (++ctx->filter_skipped & 255u) == 0;
-        J->filtered = !J->small && J->build_filter && P.n_own < P.n &&
+        J->filtered = !J->small && P.n_own < P.n &&
                       (dbg_filter ? atoi(dbg_filter) != 0 : (4 * P.S_own <= 3 * S_behind && pays));
         J->parts_entries = S_behind;
         if (J->filtered) {
@@ -2037,6 +2163,43 @@ static int compare_job_begin(spsp_ctx* ctx, CompareJob* job) {
     } else if ((rc = job_begin_dictionary(ctx, J.get()))) return rc;
     ctx->compare_job = J.release();
     return SPSP_OK;
+}
+
+// A part of the partition form overflowed (many sketches share their keys): the same parts once more with the records of
+// the overflowed ones grouped in HBM (spill); where that does not apply, parts half the size, then the global-dictionary
+// forms, which have no such limit.  Returns 0 when another partition attempt is queued, 1 when the global dictionary
+// takes over, < 0 on error.
+static int job_parts_retry(spsp_ctx* ctx, CompareJob& J, const uint32_t* h_flags) {
+    J.bracket_closed = true;
+    if (J.filtered && h_flags[7] > J.parts_entries) {   // more keys passed the filter than the parts were sized for: now the count is known
+        J.parts_entries = (uint64_t)h_flags[7] + (uint64_t)h_flags[7] / 64 + 2900;
+        if (parts_for(J.parts_entries, J.parts_attempt) <= (uint32_t)kMaxKeyParts) {
+            J.n_parts = parts_for(J.parts_entries, J.parts_attempt);
+            return job_parts(ctx, J);
+        }
+    }
+    if (J.small) {                              // the small-problem form's parts are half the size: the general form next
+        J.small = false;
+        J.n_parts = parts_for(J.P.S_entries, 0);
+        const int rc = ctx->c_row.reserve((size_t)J.P.S_entries * 4);
+        return rc ? rc : job_parts(ctx, J);
+    }
+    if (h_flags[2] > J.spill.room && spill_plan(J, h_flags[2], &J.spill)) return job_parts(ctx, J);   // (the count is exact: the same parts overflow again)
+    J.spill = SpillPlan{};
+    // no room for the spilled keys' lists behind this many parts (list references address 2^29 u16): twice the classes,
+    // so half the parts -- everything starts over, a key's class changes
+    if (!J.filtered && spill_enabled() && J.n_parts > 4096 && J.classes <= 128 && h_flags[2] > 0) {
+        J.classes *= 2; J.cls = 0;
+        J.parts_entries = J.S_behind / J.classes + J.S_behind / J.classes / 32 + 65536;
+        J.n_parts = parts_for(J.parts_entries, 0);
+        return job_parts(ctx, J);
+    }
+    if (J.parts_attempt == 0 && parts_for(J.parts_entries, 1) <= (uint32_t)kMaxKeyParts) {
+        J.parts_attempt = 1;
+        J.n_parts = parts_for(J.parts_entries, 1);
+        return job_parts(ctx, J);
+    }
+    return 1;
 }
 
 int compare_job_end(spsp_ctx* ctx) {
@@ -2072,48 +2235,12 @@ int compare_job_end(spsp_ctx* ctx) {
             }
             return SPSP_OK;
         }
-        // a part overflowed (many sketches share their keys): the same parts once more with the records of the
-        // overflowed ones grouped in HBM (spill); where that does not apply, parts half the size, then the
-        // global-dictionary forms, which have no such limit
-        J->bracket_closed = true;
-        if (J->filtered && h_flags[7] > J->parts_entries) {   // more keys passed the filter than the parts were sized for: now the count is known
-            J->parts_entries = (uint64_t)h_flags[7] + (uint64_t)h_flags[7] / 64 + 2900;
-            if (parts_for(J->parts_entries, J->parts_attempt) <= (uint32_t)kMaxKeyParts) {
-                J->n_parts = parts_for(J->parts_entries, J->parts_attempt);
-                if ((rc = job_parts(ctx, *J))) return rc;
-                continue;
-            }
+        if ((rc = job_parts_retry(ctx, *J, h_flags)) < 0) return rc;
+        if (rc == 1) {
+            J->parts = false;
+            J->clear_all_flags = true;
+            if ((rc = job_begin_dictionary(ctx, J.get()))) return rc;
         }
-        if (J->small) {                             // the small-problem form's parts are half the size: the general form next
-            J->small = false;
-            J->n_parts = parts_for(J->P.S_entries, 0);
-            if ((rc = ctx->c_row.reserve((size_t)J->P.S_entries * 4))) return rc;
-            if ((rc = job_parts(ctx, *J))) return rc;
-            continue;
-        }
-        if (!J->small && h_flags[2] > J->spill.room && spill_plan(*J, h_flags[2], &J->spill)) {   // (the count is exact: the same parts overflow again)
-            if ((rc = job_parts(ctx, *J))) return rc;
-            continue;
-        }
-        J->spill = SpillPlan{};
-        // no room for the spilled keys' lists behind this many parts (list references address 2^29 u16): twice the classes,
-        // so half the parts -- everything starts over, a key's class changes
-        if (!J->filtered && spill_enabled() && J->spill_parts && J->n_parts > 4096 && J->classes <= 128 && h_flags[2] > 0) {
-            J->classes *= 2; J->cls = 0;
-            J->parts_entries = J->S_behind / J->classes + J->S_behind / J->classes / 32 + 65536;
-            J->n_parts = parts_for(J->parts_entries, 0);
-            if ((rc = job_parts(ctx, *J))) return rc;
-            continue;
-        }
-        if (J->parts_attempt == 0 && parts_for(J->parts_entries, 1) <= (uint32_t)kMaxKeyParts) {
-            J->parts_attempt = 1;
-            J->n_parts = parts_for(J->parts_entries, 1);
-            if ((rc = job_parts(ctx, *J))) return rc;
-            continue;
-        }
-        J->parts = false;
-        J->clear_all_flags = true;
-        if ((rc = job_begin_dictionary(ctx, J.get()))) return rc;
     }
     for (;;) {
         uint32_t h_flags[kFlags];
@@ -2232,183 +2359,26 @@ static int compare_device_begin_inner(spsp_ctx* ctx, uint32_t k, const uint32_t*
     uint32_t n_tiles = 0, tile_sk = 0;
     if ((rc = stage_sk_off(ctx, h_sk_off, n, row_first, &n_tiles, &tile_sk))) return rc;
     if ((rc = ctx->c_flags.reserve(256))) return rc;
-    Keys K{d_min, d_lo, (k > 32) ? d_hi : nullptr, ~0ull};
     const uint64_t* sk = ctx->c_skoff.as<uint64_t>();
-    uint32_t* flags = ctx->c_flags.as<uint32_t>();
     uint64_t max_all = 0;
     for (uint32_t i = 0; i < n; ++i) max_all = std::max(max_all, h_sk_off[i + 1] - h_sk_off[i]);
-    const dim3 grid_all((uint32_t)((max_all + 255) / 256), n);
+    const uint32_t sub_words = ((uint32_t)((S + kScatSub - 1) / kScatSub) + 1) / 2;   // u64 words of the sub-chunk table
     CompareJob* J = new CompareJob;
-    J->P = ComparePlan{S_own, S, n, n_own, row_first, row_stride, row_limit, sk, sk + 1, d_inter};
-    J->P.max_row = max_all;
+    ComparePlan& P = J->P;
+    P = ComparePlan{S_own, S, n, n_own, row_first, row_stride, row_limit, sk, sk + 1, d_inter};
+    P.max_row = max_all;
+    P.K = Keys{d_min, d_lo, (k > 32) ? d_hi : nullptr, ~0ull};
+    P.grid_all = dim3((uint32_t)((max_all + 255) / 256), n);
+    P.sub_sk = reinterpret_cast<const uint32_t*>(sk + n + 1);
+    P.tile_info = sk + n + 1 + sub_words;
+    P.n_tiles = n_tiles;
+    P.tile_sk = tile_sk;
+    // (nothing of the sketches in front of the first owned row is dealt: the grid starts at that row's chunk)
+    P.e_own = h_sk_off[row_first] / (4u * kScatThreads) * (4u * kScatThreads);
+    J->has_hi = P.K.hi != nullptr;
     J->clear_all_flags = true;
     J->n_skoff = n + 1;
-    J->insert = [=](uint64_t seed, uint64_t fp_mask, uint32_t log2cap, uint32_t passes, uint32_t pass) -> int {
-        Keys Km = K; Km.fp_mask = fp_mask;
-        hipLaunchKernelGGL(k_insert, grid_all, dim3(256), 0, ctx->stream, Km, sk, n, S, row_first, row_stride, row_limit,
-                           seed, ctx->c_table.as<uint64_t>(), log2cap, ctx->c_owner.as<uint32_t>(),
-                           SlotKeys{ctx->c_slot_lo.as<uint64_t>(), ctx->c_slot_hi.as<uint64_t>(), ctx->c_slot_mn.as<uint32_t>()}, flags,
-                           passes, pass);
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
-    J->fill = [=](uint64_t seed, uint64_t fp_mask, uint32_t log2cap, uint32_t W, bool direct_rows, uint32_t passes, uint32_t pass) -> int {
-        Keys Km = K; Km.fp_mask = fp_mask;
-        hipLaunchKernelGGL(k_fill, grid_all, dim3(256), 0, ctx->stream, Km, sk, n, S, row_first, row_stride, row_limit, seed,
-                           ctx->c_table.as<uint64_t>(), log2cap, ctx->c_owner.as<uint32_t>(),
-                           direct_rows ? (const uint32_t*)nullptr : ctx->c_rowid.as<uint32_t>(),
-                           SlotKeys{ctx->c_slot_lo.as<uint64_t>(), ctx->c_slot_hi.as<uint64_t>(), ctx->c_slot_mn.as<uint32_t>()},
-                           W, ctx->c_matrix.as<unsigned long long>(), ctx->c_row.as<uint32_t>(), flags, passes, pass);
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
-    J->insert_sparse = [=](uint64_t seed, uint64_t fp_mask, uint32_t log2cap) -> int {
-        Keys Km = K; Km.fp_mask = fp_mask;
-        hipLaunchKernelGGL(k_insert_sparse, grid_all, dim3(256), 0, ctx->stream, Km, sk, seed, ctx->c_table.as<uint64_t>(), log2cap,
-                           ctx->c_owner.as<uint32_t>(),
-                           SlotKeys{ctx->c_slot_lo.as<uint64_t>(), ctx->c_slot_hi.as<uint64_t>(), ctx->c_slot_mn.as<uint32_t>()},
-                           ctx->c_row.as<uint32_t>(), flags);
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
-    J->fill_sparse = [=]() -> int {
-        hipLaunchKernelGGL(k_fill_sparse, grid_all, dim3(256), 0, ctx->stream, K, sk, ctx->c_row.as<uint32_t>(),
-                           SlotKeys{ctx->c_slot_lo.as<uint64_t>(), ctx->c_slot_hi.as<uint64_t>(), ctx->c_slot_mn.as<uint32_t>()},
-                           ctx->c_owner.as<uint32_t>(), ctx->c_rowid.as<uint32_t>(), ctx->c_matrix.as<uint16_t>(), flags);
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
-    const bool has_hi = K.hi != nullptr;
-    J->has_hi = has_hi;
-    const uint32_t* sub_sk = reinterpret_cast<const uint32_t*>(sk + n + 1);
-    const uint32_t n_sub_real = (uint32_t)((S + kScatSub - 1) / kScatSub);
-    const uint32_t sub_words = (n_sub_real + 1) / 2;
     J->n_sub = 2 * (sub_words + n_tiles);                        // u32 words behind the offsets that k_parts_prepare brings over: sub-chunk sketches, then the tile table
-    const uint64_t* tile_info = sk + n + 1 + sub_words;
-    J->build_filter = [=](uint32_t fmask) -> int {
-        uint64_t max_own = 0;
-        for (uint32_t i = row_first; i < row_limit; i += row_stride) max_own = std::max(max_own, ctx->h_skoff[i + 1] - ctx->h_skoff[i]);
-        const dim3 grid((uint32_t)std::max<uint64_t>(1, (max_own + 255) / 256), n_own);
-        if (has_hi) hipLaunchKernelGGL(k_parts_filter<true>, grid, dim3(256), 0, ctx->stream, K, sk, n, row_first, row_stride, row_limit, ctx->c_filter.as<uint32_t>(), fmask);
-        else hipLaunchKernelGGL(k_parts_filter<false>, grid, dim3(256), 0, ctx->stream, K, sk, n, row_first, row_stride, row_limit, ctx->c_filter.as<uint32_t>(), fmask);
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
-    // (nothing of the sketches in front of the first owned row is dealt: the grid starts at that row's chunk)
-    const uint64_t e_own = h_sk_off[row_first] / (4u * kScatThreads) * (4u * kScatThreads);
-    J->scatter_parts = [=](uint32_t n_parts, bool small, bool filtered, uint32_t fmask, uint32_t classes, uint32_t cls) -> int {
-        const uint32_t cap = small ? (uint32_t)kSmallCap : (uint32_t)kPartCap;
-        int r2 = ctx->c_recs.reserve((size_t)n_parts * cap * (has_hi ? 24 : 16));
-        if (r2) return r2;
-        if (!small && (r2 = ctx->c_where.reserve((size_t)S * 4 + 16))) return r2;
-        if (!small && (r2 = ctx->c_lref.reserve((size_t)n_parts * kPartCap * 4))) return r2;
-        uint32_t* where = small ? nullptr : ctx->c_where.as<uint32_t>();
-        static_assert(kMaxKeyParts < (1 << 15), "k_parts_scatter keeps the part in 15 bits of its (part, rank) word");
-        if (n_parts > (uint32_t)kMaxKeyParts) { set_error("internal: %u key parts exceed the scatter's limit of %d", n_parts, kMaxKeyParts); return SPSP_ERR_ARG; }
-        // tiles: the general partition form (a filtered call's scatter starts at its first owned row's chunk and drops most of
-        // what it reads; the small form keeps no `where` and its 100 sketches are one block anyway)
-        if (!small && !filtered && n_tiles) {
-            const size_t lds_t = (size_t)n_parts * 4;
-            if (lds_t > 48 * 1024 && !ctx->attr_scatter_tiles_set) {
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter_tiles<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter_tiles<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
-                ctx->attr_scatter_tiles_set = true;
-            }
-            if (has_hi) hipLaunchKernelGGL(k_parts_scatter_tiles<true>, dim3(n_tiles), dim3(kScatThreads), lds_t, ctx->stream, K, sk, n, tile_info, tile_sk, n_parts,
-                                           cap, ctx->c_part_cnt.as<uint32_t>(), ctx->c_recs.as<uint64_t>(), where, flags, !ctx->keys_unordered, row_first, classes, cls);
-            else hipLaunchKernelGGL(k_parts_scatter_tiles<false>, dim3(n_tiles), dim3(kScatThreads), lds_t, ctx->stream, K, sk, n, tile_info, tile_sk, n_parts,
-                                    cap, ctx->c_part_cnt.as<uint32_t>(), ctx->c_recs.as<uint64_t>(), where, flags, !ctx->keys_unordered, row_first, classes, cls);
-            SPSP_HIP(hipGetLastError());
-            return SPSP_OK;
-        }
-        const uint32_t per_wg = 4u * kScatThreads;
-        const uint64_t e_first = e_own;
-        const dim3 grid((uint32_t)((S - e_first + per_wg - 1) / per_wg));
-        const uint32_t* filter = filtered ? ctx->c_filter.as<uint32_t>() : nullptr;
-        const size_t lds = (size_t)n_parts * 4;
-        if (lds > 48 * 1024 && !ctx->attr_scatter_set) {
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
-            ctx->attr_scatter_set = true;
-        }
-#define SPSP_SCATTER(HI, E) hipLaunchKernelGGL((k_parts_scatter<HI, E>), grid, dim3(kScatThreads), lds, ctx->stream, K, sk, n, sub_sk, S, \
-                                               n_parts, cap, ctx->c_part_cnt.as<uint32_t>(), ctx->c_recs.as<uint64_t>(), where, flags, !ctx->keys_unordered, \
-                                               filter, fmask, e_first, row_first, row_stride, row_limit, classes, cls)
-        if (has_hi) SPSP_SCATTER(true, 4);
-        else SPSP_SCATTER(false, 4);
-#undef SPSP_SCATTER
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
-    J->group_parts = [=](uint32_t n_parts, const SpillPlan& sp, bool want_multi) -> int {
-        const size_t lds = (size_t)kPartCap * (8 + (has_hi ? 8 : 0) + 4) + (size_t)kPartSlots * 4 + 16;
-        // (a spill attempt: keys of many holders get columns here too -- a part they do not overflow would otherwise list them)
-        const uint32_t t_bits = sp.room ? sp.t_bits : 0xffffffffu, max_cols = sp.room ? sp.max_cols : 0u;
-        unsigned long long* bits = (sp.room && sp.max_cols) ? ctx->c_bits.as<unsigned long long>() : (unsigned long long*)nullptr;
-        if (want_multi) { const int rm = ctx->c_multi.reserve((size_t)n_parts * kPartCap / 8 + 64); if (rm) return rm; }
-        unsigned long long* multi = want_multi ? ctx->c_multi.as<unsigned long long>() : (unsigned long long*)nullptr;
-        if (has_hi) {
-            if (!ctx->attr_group_hi_set) {
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_group<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                ctx->attr_group_hi_set = true;
-            }
-            hipLaunchKernelGGL(k_parts_group<true>, dim3(n_parts), dim3(kGroupThreads), lds, ctx->stream, ctx->c_recs.as<uint64_t>(),
-                               ctx->c_part_cnt.as<uint32_t>(), ctx->c_matrix.as<uint16_t>(), ctx->c_lref.as<uint32_t>(), flags, t_bits, max_cols, bits, n, multi);
-        } else {
-            if (!ctx->attr_group_set) {
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_group<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                ctx->attr_group_set = true;
-            }
-            hipLaunchKernelGGL(k_parts_group<false>, dim3(n_parts), dim3(kGroupThreads), lds, ctx->stream, ctx->c_recs.as<uint64_t>(),
-                               ctx->c_part_cnt.as<uint32_t>(), ctx->c_matrix.as<uint16_t>(), ctx->c_lref.as<uint32_t>(), flags, t_bits, max_cols, bits, n, multi);
-        }
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
-    J->spill_parts = [=](uint32_t n_parts, const SpillPlan& sp, int phase, uint32_t classes, uint32_t cls) -> int {
-        const uint64_t slots = 1ull << sp.log2cap;
-        int r2;
-        if (phase == 0) {
-            if ((r2 = ctx->c_table.reserve((size_t)slots * 4)) || (r2 = ctx->c_owner.reserve((size_t)slots * 4)) || (r2 = ctx->c_rowid.reserve((size_t)slots * 4))) return r2;
-            SPSP_HIP(hipMemsetAsync(ctx->c_table.p, 0, (size_t)slots * 4, ctx->stream));
-            SPSP_HIP(hipMemsetAsync(ctx->c_owner.p, 0, (size_t)slots * 4, ctx->stream));
-            if (sp.max_cols) {
-                const size_t bytes = (size_t)((sp.max_cols + 63) / 64) * n * 8;
-                if ((r2 = ctx->c_bits.reserve(bytes))) return r2;
-                SPSP_HIP(hipMemsetAsync(ctx->c_bits.p, 0, bytes, ctx->stream));
-            }
-            return SPSP_OK;
-        }
-        const dim3 grid((uint32_t)((S - e_own + kSpillThreads - 1) / kSpillThreads));
-        uint32_t *tbl = ctx->c_table.as<uint32_t>(), *cnt = ctx->c_owner.as<uint32_t>(), *off = ctx->c_rowid.as<uint32_t>();
-        uint32_t *where = ctx->c_where.as<uint32_t>(), *rank_of = ctx->c_row.as<uint32_t>();
-        const uint32_t* part_cnt = ctx->c_part_cnt.as<uint32_t>();
-        const uint32_t room = (uint32_t)sp.room;
-        if (has_hi) hipLaunchKernelGGL(k_spill_insert<true>, grid, dim3(kSpillThreads), 0, ctx->stream, K, sk, n, S, e_own, row_first, n_parts, part_cnt, tbl, sp.log2cap, cnt, where, rank_of, room, flags, classes, cls, sub_sk);
-        else hipLaunchKernelGGL(k_spill_insert<false>, grid, dim3(kSpillThreads), 0, ctx->stream, K, sk, n, S, e_own, row_first, n_parts, part_cnt, tbl, sp.log2cap, cnt, where, rank_of, room, flags, classes, cls, sub_sk);
-        SPSP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_spill_ranges, dim3((uint32_t)((slots + (uint64_t)kRowThreads * kRowSlots - 1) / ((uint64_t)kRowThreads * kRowSlots))), dim3(kRowThreads), 0, ctx->stream,
-                           (const uint32_t*)cnt, slots, off, ctx->c_matrix.as<uint16_t>(), sp.ids_base, sp.ids_room, ctx->c_lref.as<uint32_t>() + sp.lref_base, sp.t_bits, sp.max_cols, room, flags);
-        SPSP_HIP(hipGetLastError());
-        unsigned long long* bits = sp.max_cols ? ctx->c_bits.as<unsigned long long>() : (unsigned long long*)nullptr;
-        if (has_hi) hipLaunchKernelGGL(k_spill_fill<true>, grid, dim3(kSpillThreads), 0, ctx->stream, K, sk, n, S, e_own, row_first, n_parts, part_cnt, cnt, (const uint32_t*)off,
-                                       ctx->c_matrix.as<uint16_t>(), sp.ids_base, sp.lref_base, bits, where, (const uint32_t*)rank_of, room, (const uint32_t*)flags, classes, cls, sub_sk);
-        else hipLaunchKernelGGL(k_spill_fill<false>, grid, dim3(kSpillThreads), 0, ctx->stream, K, sk, n, S, e_own, row_first, n_parts, part_cnt, cnt, (const uint32_t*)off,
-                                ctx->c_matrix.as<uint16_t>(), sp.ids_base, sp.lref_base, bits, where, (const uint32_t*)rank_of, room, (const uint32_t*)flags, classes, cls, sub_sk);
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
-    if (!has_hi) J->group_small = [=](uint32_t n_parts) -> int {
-        const size_t lds = (size_t)kSmallCap * (8 + 4) + (size_t)kSmallHl + (size_t)kSmallSlots * 4 + (size_t)kSmallN * kSmallN * 2 + 16;
-        if (!ctx->attr_small_set) {
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_group_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ctx->attr_small_set = true;
-        }
-        hipLaunchKernelGGL(k_parts_group_small, dim3(n_parts), dim3(kGroupThreads), lds, ctx->stream, ctx->c_recs.as<uint64_t>(),
-                           ctx->c_part_cnt.as<uint32_t>(), n, d_inter, flags);
-        SPSP_HIP(hipGetLastError());
-        return SPSP_OK;
-    };
     return compare_job_begin(ctx, J);
 }
 
@@ -2580,16 +2550,15 @@ int compare_device_begin_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_min, 
     if (rc < 0) return rc;
     if (rc == 1) {                       // nothing to compare: leave an empty job so that begin/end stay paired
         CompareJob* J = new CompareJob;
-        J->speculative = true;
         J->P = ComparePlan{};
+        J->empty = true;
         ctx->compare_job = J;
-        J->attempt = -1;
     }
     return rc2;
 }
 
 int compare_end_impl(spsp_ctx* ctx) {
-    if (ctx->compare_job && ctx->compare_job->attempt == -1) { compare_job_drop(ctx); return SPSP_OK; }
+    if (ctx->compare_job && ctx->compare_job->empty) { compare_job_drop(ctx); return SPSP_OK; }
     return compare_job_end(ctx);
 }
 
