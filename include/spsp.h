@@ -497,6 +497,49 @@ int spsp_compare_files_chatty(spsp_ctx* ctx, const char* const* paths, uint32_t 
 int spsp_compare_files_multi(const int* devices, uint32_t n_dev, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
                              double min_threshold, const char* out_prefix, int chatter, struct spsp_stage_times* times);
 
+/* Sketches of different sampling rates (not in the reference, which keeps the last header's rate in a member nobody reads,
+ * Comparator.cpp:23-37, and so compares a -s 100 sketch with its -s 1000 twin at a Jaccard index near 0.1).  A k-mer is
+ * selected iff XXH64 (seed 1312) of its canonical minimizer is <= spsp_threshold_host(k, m, s), and nothing else in the scan
+ * depends on the threshold: the keys of the sketch at a coarser rate s' >= s are exactly the keys of the sketch at s whose
+ * minimizer passes the threshold of s'.  Opt-in: without a rate everything below behaves as the reference does.
+ *
+ * spsp_keys_downsample_device keeps the keys whose minimizer passes `threshold`: sketches stay back to back, each one's
+ * surviving keys in their old order (sorted input stays sorted, SPSP_KEYS_UNORDERED input stays distinct).  Input: the
+ * concatenated key arrays every comparison entry point takes (they may be this context's own, e.g. what
+ * spsp_sketch_decode_device or spsp_sketch_keys_device returned, or the result of the previous downsample call).  Output:
+ * arrays OWNED BY THE CONTEXT, valid until the next downsample call but one on it (two sets are used in turn), ready for
+ * spsp_compare_device / spsp_compare_cells_device / spsp_partition_keys_device; sk_off_out gets n + 1 offsets starting at 0.
+ * A fixed chain of launches whatever n is and one host synchronisation (the one that reads the offsets back). */
+int spsp_keys_downsample_device(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const void* d_minimizer, const void* d_kmer_lo,
+                                const void* d_kmer_hi /* NULL if k <= 32 */, const uint64_t* h_sk_off, uint32_t n,
+                                void** d_out_minimizer, void** d_out_kmer_lo, void** d_out_kmer_hi, uint64_t* sk_off_out /* n + 1 */);
+/* The four fields of a sketch's header line "<2k-m> <m> <count> <rate>\n" (rate by strtod: -s is a float, printed with %f).
+ * A header without a rate field is SPSP_ERR_FORMAT. */
+int spsp_sketch_header_host(const uint8_t* payload, uint64_t len, uint32_t* k, uint32_t* m, uint64_t* n_kmers, double* rate);
+/* A sketch payload brought down to the coarser `rate`: the buckets whose minimizer passes spsp_threshold_host(k, m, rate),
+ * copied as they are and in their order, behind a new header line that names `rate`.  The header's third field -- read by
+ * nobody (Comparator.cpp:31); the sketcher writes its selected k-mer occurrences there -- is the number of DISTINCT keys the
+ * kept buckets decode to (what spsp_sketch_parse_host returns for the result).  Rates are compared as the thresholds they
+ * stand for: a `rate` finer than the sketch's own is SPSP_ERR_ARG ("cannot upsample"), one equal to it returns the payload
+ * unchanged.  *out is released with spsp_free(). */
+int spsp_sketch_downsample_host(const uint8_t* payload, uint64_t len, double rate, uint8_t** out, uint64_t* out_len);
+/* The comparator drivers with a common sampling rate.  rate = SPSP_RATE_AS_IS: spsp_compare_files(_chatty) / _multi, which are
+ * calls of these.  Otherwise every header's rate is read, and the decoded keys are brought down to the common rate ON THE
+ * DEVICE, between the decoder and the comparison (between each context's decode and its key partition in the multi form: a
+ * filtered key never crosses the fabric); card[i] counts the surviving keys, so both CSVs are those of sketches made at the
+ * common rate directly.  "Coarser" and "already there" are decided on spsp_threshold_host(k, m, rate) of the rates, not on
+ * the floats as printed; when every sketch is already at the common rate the pass is skipped.  A sketch coarser than the
+ * common rate is SPSP_ERR_ARG naming the file and both rates, before any kernel runs; files of differing k or m are
+ * SPSP_ERR_FORMAT naming the file; k == m collections (the phantom key of spsp_sketch_chain_host has no meaning under a
+ * filter) are SPSP_ERR_ARG.  chatter: 0 silent, 1 / 2 the reference's stdout lines of an all-versus-all / a query run, and
+ * behind them one line that names the common rate and how many sketches were brought down to it. */
+#define SPSP_RATE_AS_IS 0.0       /* the headers' rates are ignored, as the reference does */
+#define SPSP_RATE_COARSEST (-1.0) /* the largest rate any of the n headers names */
+int spsp_compare_files_rate(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, double min_threshold,
+                            const char* out_prefix, int chatter, double rate);
+int spsp_compare_files_multi_rate(const int* devices, uint32_t n_dev, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
+                                  double min_threshold, const char* out_prefix, int chatter, struct spsp_stage_times* times, double rate);
+
 /* A pair matrix in sparse form: the non-zero cells (i, j > i) of rows row_first <= i < row_limit of the dense n x n
  * matrix d_inter as packed 64-bit words  i << 48 | j << 32 | count  (n <= 65535, the reference's bound: Comparator.h:26),
  * in no particular order, in d_cells (room for `cap` words).  *n_cells = how many there are; SPSP_ERR_OVERFLOW when

@@ -35,6 +35,8 @@ class SpspError(RuntimeError):
 
 ERR_OVERFLOW = -7
 KEYS_UNORDERED = 1
+ERR_ARG, ERR_FORMAT = -1, -6
+RATE_AS_IS, RATE_COARSEST = 0.0, -1.0      # compare_files(rate=...): the headers' rates ignored / the coarsest of the files' ("auto")
 TIME_DENSE, TIME_SCAN, TIME_ACCUMULATE, TIME_COMPARE, TIME_PARTS, TIME_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -84,6 +86,7 @@ ABI_SYMBOLS = [
     "spsp_timing_enable", "spsp_timing_sample", "spsp_timing_read", "spsp_threshold_host", "spsp_scan", "spsp_scan_device", "spsp_scan_device_begin", "spsp_scan_device_end", "spsp_scan_tail_stream", "spsp_wait_dense", "spsp_wait_stream", "spsp_scan_hits_device", "spsp_count_superkmers_device", "spsp_compare",
     "spsp_compare_device", "spsp_slot_bytes", "spsp_partition_keys_device", "spsp_compare_slots_device", "spsp_compare_device_begin", "spsp_compare_slots_device_begin", "spsp_compare_end", "spsp_fasta_clean_host", "spsp_fasta_clean_device", "spsp_fasta_clean_packed_device", "spsp_fastq_clean_device", "spsp_fastq_clean_packed_device", "spsp_sketch_text", "spsp_sketch_build_host", "spsp_sketch_parse_host", "spsp_sketch_decode_device", "spsp_sketch_keys_device", "spsp_sketch_keys_device_begin", "spsp_sketch_keys_device_end", "spsp_sketch_keys_big_genomes", "spsp_scan_output_wait", "spsp_compare_keys_unordered", "spsp_compare_forget", "spsp_sketch_chain_host",
     "spsp_csv_host", "spsp_csv_cells_host", "spsp_csv_cells_gz_host", "spsp_sort_csv_host", "spsp_read_file_host", "spsp_write_gz_host", "spsp_sketch_file", "spsp_compare_files", "spsp_compare_files_chatty", "spsp_stage_times_read", "spsp_measure_hbm_device", "spsp_sketch_files", "spsp_sketch_files_multi", "spsp_sketch_files_release", "spsp_compare_files_multi", "spsp_matrix_cells_device", "spsp_matrix_add_cells_device", "spsp_compare_cells_device", "spsp_compare_slots_cells_device",
+    "spsp_keys_downsample_device", "spsp_sketch_header_host", "spsp_sketch_downsample_host", "spsp_compare_files_rate", "spsp_compare_files_multi_rate",
 ]
 
 _lib = None
@@ -200,6 +203,15 @@ def lib():
     L.spsp_compare_cells_device.restype = i32; L.spsp_compare_cells_device.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, u64, P(u64)]
     L.spsp_compare_slots_cells_device.restype = i32; L.spsp_compare_slots_cells_device.argtypes = [vp, u32, vp, u32, u32, u32, vp, vp, u64, P(u64)]
     L.spsp_matrix_add_cells_device.restype = i32; L.spsp_matrix_add_cells_device.argtypes = [vp, vp, u32, vp, u64]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_keys_downsample_device"):      # (an older build named by SPSP_LIB for an A/B run has none of these)
+        L.spsp_keys_downsample_device.restype = i32
+        L.spsp_keys_downsample_device.argtypes = [vp, u32, u64, vp, vp, vp, vp, u32, P(vp), P(vp), P(vp), vp]
+        L.spsp_sketch_header_host.restype = i32; L.spsp_sketch_header_host.argtypes = [cp, u64, P(u32), P(u32), P(u64), P(dbl)]
+        L.spsp_sketch_downsample_host.restype = i32; L.spsp_sketch_downsample_host.argtypes = [cp, u64, dbl, P(vp), P(u64)]
+        L.spsp_compare_files_rate.restype = i32
+        L.spsp_compare_files_rate.argtypes = [vp, P(cp), u32, u32, i32, dbl, cp, i32, dbl]
+        L.spsp_compare_files_multi_rate.restype = i32
+        L.spsp_compare_files_multi_rate.argtypes = [P(i32), u32, P(cp), u32, u32, i32, dbl, cp, i32, P(StageTimes), dbl]
     _lib = L
     return L
 
@@ -284,6 +296,30 @@ def sketch_parse(payload):
     b = np.frombuffer(_take(lo, 8 * c), dtype=np.uint64).copy()
     d = np.frombuffer(_take(hi, 8 * c), dtype=np.uint64).copy()
     return Sketch(k.value, m.value, a, b, d)
+
+
+def sketch_header(payload):
+    """header line of a gunzipped sketch payload -> (k, m, k-mer count, sampling rate)"""
+    k, m, n, r = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_double()
+    _check(lib().spsp_sketch_header_host(payload, len(payload), C.byref(k), C.byref(m), C.byref(n), C.byref(r)))
+    return k.value, m.value, n.value, r.value
+
+
+def sketch_downsample(payload, rate):
+    """a sketch payload brought down to the coarser sampling rate `rate` (spsp_sketch_downsample_host): the buckets whose
+    minimizer passes, as they are, behind a header that names `rate` and the distinct keys left"""
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_sketch_downsample_host(payload, len(payload), float(rate), C.byref(out), C.byref(n)))
+    return _take(out, n.value)
+
+
+def _rate_arg(rate):
+    """rate keyword of the comparator drivers: 0.0 (the headers' rates ignored), a rate, or "auto" (the coarsest of the files')"""
+    if isinstance(rate, str):
+        if rate != "auto":
+            raise ValueError("rate: a number or \"auto\", not %r" % rate)
+        return RATE_COARSEST
+    return float(rate)
 
 
 def csv(jaccard, names, inter, card, n_query=None, precision=6, min_threshold=0.0):
@@ -416,14 +452,20 @@ def _paths_array(paths):
     return arr, (arr,)
 
 
-def compare_files_multi(devices, paths, out_prefix, n_query=None, precision=6, min_threshold=0.0):
-    """spsp_compare_files_multi: the comparator split by key over one context per entry of `devices` -> stage seconds"""
+def compare_files_multi(devices, paths, out_prefix, n_query=None, precision=6, min_threshold=0.0, rate=0.0):
+    """spsp_compare_files_multi(_rate): the comparator split by key over one context per entry of `devices` -> stage seconds.
+    rate: 0.0 = the headers' sampling rates are ignored; a rate or "auto" = every sketch is brought down to it on its device first"""
     n = len(paths)
     devs = (C.c_int * len(devices))(*devices)
     arr, _alive = _paths_array(paths)
     st = StageTimes()
-    _check(lib().spsp_compare_files_multi(devs, len(devices), arr, n, n if n_query is None else n_query, precision, float(min_threshold),
-                                          out_prefix.encode(), 0, C.byref(st)))
+    r = _rate_arg(rate)
+    if r == RATE_AS_IS:
+        _check(lib().spsp_compare_files_multi(devs, len(devices), arr, n, n if n_query is None else n_query, precision, float(min_threshold),
+                                              out_prefix.encode(), 0, C.byref(st)))
+    else:
+        _check(lib().spsp_compare_files_multi_rate(devs, len(devices), arr, n, n if n_query is None else n_query, precision, float(min_threshold),
+                                                   out_prefix.encode(), 0, C.byref(st), r))
     return {f: getattr(st, f) for f, _ in StageTimes._fields_}
 
 
@@ -725,8 +767,25 @@ class Context:
     def matrix_add_cells_device(self, d_inter, n, d_cells, n_cells):
         _check(lib().spsp_matrix_add_cells_device(self._h, d_inter, n, d_cells, n_cells))
 
-    def compare_files(self, paths, out_prefix, n_query=None, precision=6, min_threshold=0.0):
+    def compare_files(self, paths, out_prefix, n_query=None, precision=6, min_threshold=0.0, rate=0.0):
+        """rate: 0.0 = the headers' sampling rates are ignored (the reference's behaviour); a rate, or "auto" for the coarsest
+        of the files', = every sketch is brought down to it on the device before the comparison"""
         n = len(paths)
         nq = n if n_query is None else n_query
         arr, _alive = _paths_array(paths)
-        _check(lib().spsp_compare_files(self._h, arr, n, nq, precision, float(min_threshold), out_prefix.encode()))
+        r = _rate_arg(rate)
+        if r == RATE_AS_IS:
+            _check(lib().spsp_compare_files(self._h, arr, n, nq, precision, float(min_threshold), out_prefix.encode()))
+        else:
+            _check(lib().spsp_compare_files_rate(self._h, arr, n, nq, precision, float(min_threshold), out_prefix.encode(), 0, r))
+
+    def keys_downsample_device(self, k, threshold_value, d_min, d_lo, d_hi, sk_off):
+        """concatenated key arrays on the device -> (d_minimizer, d_kmer_lo, d_kmer_hi or None, sk_off np.uint64[n + 1]): the keys
+        whose minimizer passes `threshold_value` (threshold(k, m, rate)), order kept, in arrays the context owns"""
+        sk_off = np.ascontiguousarray(sk_off, dtype=np.uint64)
+        n = len(sk_off) - 1
+        o_mn, o_lo, o_hi = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        out = np.zeros(n + 1, dtype=np.uint64)
+        _check(lib().spsp_keys_downsample_device(self._h, k, threshold_value, d_min, d_lo, d_hi, sk_off.ctypes.data, n,
+                                                 C.byref(o_mn), C.byref(o_lo), C.byref(o_hi), out.ctypes.data))
+        return o_mn.value, o_lo.value, o_hi.value, out

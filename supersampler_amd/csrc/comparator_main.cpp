@@ -32,6 +32,7 @@ int main(int argc, char** argv) {
     string inputfof, query, output_name("results");
     uint64_t p = 6;
     double min_threshold = 0;
+    double rate = SPSP_RATE_AS_IS;   // -s <rate> / -s auto: compare at a common sampling rate (not in the reference, which parses and ignores -s)
     while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:")) != -1) {
         switch (ch) {
             case 'f': inputfof = optarg; break;
@@ -39,6 +40,14 @@ int main(int argc, char** argv) {
             case 'p': p = stoi(optarg); break;
             case 'm': min_threshold = stod(optarg); break;
             case 'o': output_name = optarg; break;
+            case 's':
+                if (string(optarg) == "auto") rate = SPSP_RATE_COARSEST;
+                else {
+                    char* e = nullptr;
+                    rate = strtod(optarg, &e);
+                    if (e == optarg || *e || !(rate > 0)) { cout << "-s takes a sampling rate > 0 or \"auto\", not '" << optarg << "'" << endl; return 1; }
+                }
+                break;
         }
     }
     if (inputfof == "") {
@@ -87,8 +96,8 @@ int main(int argc, char** argv) {
     }
     // the progress lines of the reference (Comparator.cpp:56,69,364,414,503,509) are printed by the driver where the
     // reference prints them
-    const int rc = spsp_compare_files_multi(devices.data(), (uint32_t)devices.size(), paths.data(), (uint32_t)paths.size(), n_query, (int)p,
-                                            min_threshold, output_name.c_str(), query == "" ? 1 : 2, nullptr);
+    const int rc = spsp_compare_files_multi_rate(devices.data(), (uint32_t)devices.size(), paths.data(), (uint32_t)paths.size(), n_query, (int)p,
+                                                 min_threshold, output_name.c_str(), query == "" ? 1 : 2, nullptr, rate);
     if (rc != SPSP_OK) { cout << "Comparison failed: " << spsp_last_error() << endl; return 1; }
     return 0;
 }

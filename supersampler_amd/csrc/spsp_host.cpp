@@ -754,6 +754,110 @@ int spsp_sketch_chain_host(const uint8_t* payload, uint64_t len, uint32_t k, uin
     return SPSP_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// XXH64 of one little-endian 64-bit word, seed 1312: the host's copy of xxh64_u64 (spsp_device.h; Subsampler::unrevhash,
+// SubSampler.cpp:64-67 -> include/xxhash64.h:100-150)
+inline uint64_t rotl64_host(uint64_t x, int b) { return (x << b) | (x >> (64 - b)); }
+uint64_t xxh64_u64_host(uint64_t x) {
+    constexpr uint64_t P1 = 11400714785074694791ULL, P2 = 14029467366897019727ULL, P3 = 1609587929392839161ULL,
+                       P4 = 9650029242287828579ULL, P5 = 2870177450012600261ULL;
+    uint64_t h = 1312ULL + P5 + 8ULL;
+    h ^= rotl64_host(x * P2, 31) * P1;
+    h = rotl64_host(h, 27) * P1 + P4;
+    h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
+    return h;
+}
+
+// the four header fields "<2k-m> <m> <n> <rate>\n" (SubSampler.cpp:458-470 writes them, Comparator.cpp:23-37 reads them);
+// *body = offset of the first byte behind the header line
+int sketch_header_fields(const uint8_t* payload, uint64_t len, uint32_t* k, uint32_t* m, uint64_t* n_kmers, double* rate, uint64_t* body) {
+    const uint8_t* nl = (payload && len) ? (const uint8_t*)memchr(payload, '\n', len) : nullptr;
+    if (!nl) { set_error("sketch has no header line"); return SPSP_ERR_FORMAT; }
+    const std::string header((const char*)payload, nl - payload);
+    char* e = nullptr;
+    const long skm = strtol(header.c_str(), &e, 10);
+    const long mm = strtol(e, &e, 10);
+    if (skm <= 0 || skm > 126 || mm <= 0 || mm > 15 || (skm + mm) / 2 > 63 || (skm + mm) / 2 < mm) { set_error("bad sketch header '%.60s'", header.c_str()); return SPSP_ERR_FORMAT; }
+    char* e3 = nullptr;
+    const unsigned long long cnt = strtoull(e, &e3, 10);
+    if (e3 == e) { set_error("sketch header '%.60s' has no k-mer count", header.c_str()); return SPSP_ERR_FORMAT; }
+    char* e4 = nullptr;
+    const double r = strtod(e3, &e4);                              // (-s is a float, printed with %f: strtod, not stoi)
+    if (e4 == e3 || !(r == r)) { set_error("sketch header '%.60s' has no sampling rate", header.c_str()); return SPSP_ERR_FORMAT; }
+    *m = (uint32_t)mm; *k = (uint32_t)((skm + mm) / 2); *n_kmers = cnt; *rate = r;
+    if (body) *body = (uint64_t)(nl - payload) + 1;
+    return SPSP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int spsp_sketch_header_host(const uint8_t* payload, uint64_t len, uint32_t* k, uint32_t* m, uint64_t* n_kmers, double* rate) {
+    if (!payload || !k || !m || !n_kmers || !rate) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    return sketch_header_fields(payload, len, k, m, n_kmers, rate, nullptr);
+}
+
+int spsp_sketch_downsample_host(const uint8_t* payload, uint64_t len, double rate, uint8_t** out, uint64_t* out_len) {
+    if (!payload || !out || !out_len) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    *out = nullptr; *out_len = 0;
+    if (!(rate > 0)) { set_error("sampling rate %g: must be positive", rate); return SPSP_ERR_ARG; }
+    uint32_t k = 0, m = 0; uint64_t n_old = 0, pos = 0; double own = 0;
+    int rc = sketch_header_fields(payload, len, &k, &m, &n_old, &own, &pos);
+    if (rc) return rc;
+    // rates are compared as the thresholds they stand for, not as the floats the header prints
+    const uint64_t thr_own = spsp_threshold_host(k, m, own), thr = spsp_threshold_host(k, m, rate);
+    if (thr > thr_own) { set_error("cannot upsample: the sketch was made at rate %g, asked for %g", own, rate); return SPSP_ERR_ARG; }
+    auto give = [&](const std::string& s) {
+        *out = (uint8_t*)malloc(s.size() + 1);
+        if (!*out) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+        memcpy(*out, s.data(), s.size());
+        *out_len = s.size();
+        return SPSP_OK;
+    };
+    if (thr == thr_own) return give(std::string((const char*)payload, (size_t)len));   // already there: the sketch as it is
+    // the bucket walk of sketch_parse_structure_host: [m ASCII][u32 n][blob]["prefix\nsuffix\n" ...]["\n\n"]; a bucket stays, byte
+    // for byte and in its place, iff its minimizer passes
+    const std::string old_header((const char*)payload, (size_t)pos);
+    std::string body;
+    while (pos + m <= len) {
+        const uint64_t start = pos;
+        uint32_t mn = 0;
+        for (uint32_t j = 0; j < m; ++j) mn = (mn << 2) | code_of(payload[pos + j]);
+        pos += m;
+        uint32_t nbytes = 0;
+        if (pos + 4 > len) break;
+        memcpy(&nbytes, payload + pos, 4);
+        pos += 4;
+        if (pos + nbytes > len) { set_error("bucket blob runs past the end of the sketch"); return SPSP_ERR_FORMAT; }
+        pos += nbytes;
+        for (;;) {
+            if (pos >= len) break;
+            const uint8_t* e1 = (const uint8_t*)memchr(payload + pos, '\n', len - pos);
+            const uint64_t l1 = e1 ? (uint64_t)(e1 - payload) - pos : len - pos;
+            pos = e1 ? pos + l1 + 1 : len;
+            const uint8_t* e2 = pos < len ? (const uint8_t*)memchr(payload + pos, '\n', len - pos) : nullptr;
+            const uint64_t l2 = pos < len ? (e2 ? (uint64_t)(e2 - payload) - pos : len - pos) : 0;
+            pos = e2 ? pos + l2 + 1 : len;
+            if (l1 == 0 && l2 == 0) break;
+        }
+        if (xxh64_u64_host(mn) <= thr) body.append((const char*)payload + start, (size_t)(pos - start));
+    }
+    // the header's third field is read by nobody (Comparator.cpp:31): the DISTINCT keys the kept buckets decode to
+    uint64_t n_keys = 0;
+    {
+        const std::string probe = old_header + body;
+        uint32_t kk = 0, mm = 0; uint32_t* a = nullptr; uint64_t *b = nullptr, *c = nullptr;
+        if ((rc = spsp_sketch_parse_host((const uint8_t*)probe.data(), probe.size(), &kk, &mm, &a, &b, &c, &n_keys))) return rc;
+        free(a); free(b); free(c);
+    }
+    std::string res;
+    spsp::sketch_header_line(k, m, n_keys, rate, res);
+    res += body;
+    return give(res);
+}
+
 // print_containment / print_jaccard (Comparator.cpp:362-460); operator<<(double)
 // with setprecision(p) in the default float format is printf's %.*g.
 // sortCSV (sort_csv.cpp:26-111): put the rows and columns of a (symmetric, all-vs-all) Jaccard CSV into the order of
@@ -1421,9 +1525,12 @@ int spsp_stage_times_read(spsp_ctx* ctx, spsp_stage_times* out, int reset) {
 // chatter: 0 = silent; 1 = the stdout lines of the reference's all-versus-all run (Comparator.cpp:56,69,364,414,
 // 503,509); 2 = those of its query run (:56,69,364,414)
 static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
-                              double min_threshold, const char* out_prefix, int chatter, spsp_ctx* const* more = nullptr, uint32_t n_more = 0) {
+                              double min_threshold, const char* out_prefix, int chatter, double rate, spsp_ctx* const* more = nullptr, uint32_t n_more = 0) {
     // more / n_more: all contexts of a multi-device call (more[0] == ctx): the comparison is then split by key over them
+    // rate: SPSP_RATE_AS_IS = the headers' rates are ignored, as the reference does; SPSP_RATE_COARSEST or a rate = every sketch
+    // is brought down to it on the device first
     if (!ctx || !paths || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (rate != SPSP_RATE_AS_IS && rate != SPSP_RATE_COARSEST && !(rate > 0)) { set_error("sampling rate %g: must be positive", rate); return SPSP_ERR_ARG; }
     double t0 = now_s(), t1;
     const double t_start = t0;
     ctx->stages.compare_calls += 1;
@@ -1557,6 +1664,37 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
         }
     }
     if (load_times) fprintf(stderr, "[load] ... with the first-read chain %.4f s\n", now_s() - t0);
+    // a common sampling rate: the headers' rates (read here, where the payloads lie anyway), as the thresholds they stand for
+    bool ds_on = false;
+    uint64_t ds_thr = 0;
+    double ds_rate = 0;
+    uint32_t ds_brought = 0;
+    if (!rc && n && rate != SPSP_RATE_AS_IS) {
+        if (k0 == m0) { set_error("a common sampling rate cannot be applied to k == m sketches (k = m = %u)", k0); rc = SPSP_ERR_ARG; }
+        std::vector<uint64_t> thr(n, 0);
+        std::vector<double> own(n, 0);
+        double last_rate = 0; uint64_t last_thr = 0; bool have_last = false;
+        for (uint32_t i = 0; i < n && !rc; ++i) {
+            uint32_t ki = 0, mi = 0; uint64_t cnt = 0;
+            rc = sketch_header_fields(datas[i], lens[i], &ki, &mi, &cnt, &own[i], nullptr);
+            if (rc) { const std::string why = spsp_last_error(); set_error("'%s': %s", paths[i], why.c_str()); break; }
+            if (ki != k0 || mi != m0) { set_error("'%s' was made with k=%u m=%u, the first sketch with k=%u m=%u", paths[i], ki, mi, k0, m0); rc = SPSP_ERR_FORMAT; break; }
+            if (!have_last || own[i] != last_rate) { last_rate = own[i]; last_thr = spsp_threshold_host(k0, m0, own[i]); have_last = true; }   // (powl once per run of equal rates)
+            thr[i] = last_thr;
+        }
+        if (!rc) {
+            if (rate == SPSP_RATE_COARSEST) {
+                uint32_t at = 0;
+                for (uint32_t i = 1; i < n; ++i) if (thr[i] < thr[at]) at = i;
+                ds_thr = thr[at]; ds_rate = own[at];
+            } else { ds_thr = spsp_threshold_host(k0, m0, rate); ds_rate = rate; }
+            for (uint32_t i = 0; i < n && !rc; ++i) {
+                if (thr[i] < ds_thr) { set_error("cannot upsample: '%s' was sketched at rate %g, coarser than the common rate %g", paths[i], own[i], ds_rate); rc = SPSP_ERR_ARG; }
+                else if (thr[i] > ds_thr) ++ds_brought;
+            }
+            ds_on = !rc && ds_brought > 0;                         // (every sketch already there: no pass)
+        }
+    }
     // the pair matrix: zero pages from calloc (400 MB at 10^4 sketches: touched only where a row is written or read)
     struct Matrix { uint32_t* p = nullptr; ~Matrix() { free(p); } uint32_t* data() { return p; }
                     int zero(size_t cells) { free(p); p = (uint32_t*)calloc(cells ? cells : 1, 4); return p ? SPSP_OK : SPSP_ERR_NOMEM; } } inter;
@@ -1569,7 +1707,8 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
         t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
         uint32_t kk = 0, mm2 = 0;
         as_cells = n >= 1024 && n <= 65535;                    // (the printers then work from the cells: no n x n matrix on the host)
-        if (!as_cells && (rc = inter.zero((size_t)n * n))) set_error("out of host memory");
+        ctx->ds_armed = ds_on; ctx->ds_threshold = ds_thr;     // (read and cleared by the call below)
+        if (!as_cells && (rc = inter.zero((size_t)n * n))) { ctx->ds_armed = false; set_error("out of host memory"); }
         else if (n_more > 1) rc = spsp::compare_payloads_multi(more, n_more, datas.data(), lens.data(), n, extra_has.data(), extra_mn.data(), n_query, &kk, &mm2,
                                                                inter.data(), card.data(), &mirrored, as_cells ? &cells : nullptr);
         else rc = spsp::compare_payloads_impl(ctx, datas.data(), lens.data(), n, extra_has.data(), extra_mn.data(), n_query, &kk, &mm2,
@@ -1605,20 +1744,31 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
         free(text);
     }
     if (!rc && chatter == 1) std::cout << "Jaccard output lasted " << (now_s() - t_middle) << " sec" << std::endl;   // :509
+    // (not the reference's: behind its own lines, and only when a common rate was asked for)
+    if (!rc && chatter && n && rate != SPSP_RATE_AS_IS) { printf("Sketches compared at sampling rate %g: %u of %u brought down to it\n", ds_rate, ds_brought, n); fflush(stdout); }
     return rc;
 }
 
+int spsp_compare_files_rate(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, double min_threshold,
+                            const char* out_prefix, int chatter, double rate) {
+    return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, chatter < 0 ? 0 : (chatter > 2 ? 2 : chatter), rate);
+}
 int spsp_compare_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
                        double min_threshold, const char* out_prefix) {
-    return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, 0);
+    return spsp_compare_files_rate(ctx, paths, n, n_query, precision, min_threshold, out_prefix, 0, SPSP_RATE_AS_IS);
 }
 int spsp_compare_files_chatty(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
                               double min_threshold, const char* out_prefix, int all_versus_all) {
-    return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, all_versus_all ? 1 : 2);
+    return spsp_compare_files_rate(ctx, paths, n, n_query, precision, min_threshold, out_prefix, all_versus_all ? 1 : 2, SPSP_RATE_AS_IS);
 }
 
 int spsp_compare_files_multi(const int* devices, uint32_t n_dev, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
                              double min_threshold, const char* out_prefix, int chatter, spsp_stage_times* times) {
+    return spsp_compare_files_multi_rate(devices, n_dev, paths, n, n_query, precision, min_threshold, out_prefix, chatter, times, SPSP_RATE_AS_IS);
+}
+
+int spsp_compare_files_multi_rate(const int* devices, uint32_t n_dev, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
+                                  double min_threshold, const char* out_prefix, int chatter, spsp_stage_times* times, double rate) {
     if (!devices || n_dev == 0 || n_dev > 64 || !paths || !out_prefix) { set_error("1..64 devices, file list and output prefix"); return SPSP_ERR_ARG; }
     std::vector<spsp_ctx*> ctxs;
     int rc = SPSP_OK;
@@ -1632,7 +1782,7 @@ int spsp_compare_files_multi(const int* devices, uint32_t n_dev, const char* con
         rc = spsp_create(devices[d], nullptr, &c);
         if (!rc) ctxs.push_back(c);
     }
-    if (!rc) rc = compare_files_impl(ctxs[0], paths, n, n_query, precision, min_threshold, out_prefix, chatter < 0 ? 0 : (chatter > 2 ? 2 : chatter), ctxs.data(), (uint32_t)ctxs.size());
+    if (!rc) rc = compare_files_impl(ctxs[0], paths, n, n_query, precision, min_threshold, out_prefix, chatter < 0 ? 0 : (chatter > 2 ? 2 : chatter), rate, ctxs.data(), (uint32_t)ctxs.size());
     if (!rc && times) *times = ctxs[0]->stages;
     const std::string err = rc ? spsp_last_error() : "";
     for (spsp_ctx* c : ctxs) spsp_destroy(c);

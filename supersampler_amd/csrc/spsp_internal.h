@@ -181,6 +181,11 @@ struct spsp_ctx {
     bool m_slots_job = false;                                 // the pending comparison came from exchange slots: its record check is read behind compare_end
     spsp::DevBuf m_send, m_recv, m_cells, m_mn, m_lo, m_hi;   // key-partitioned split (spsp_multi.hip): slots out / in, sparse cells, unpacked keys
     uint32_t big_epoch = 0;
+    // key downsampling (spsp_downsample.hip): two sets of output arrays used in turn (ds_flip: the set the next call fills), work area
+    spsp::DevBuf ds_mn[2], ds_lo[2], ds_hi[2], ds_work;
+    int ds_flip = 0;
+    bool ds_armed = false;             // the next compare_payloads_impl / _multi call brings the decoded keys down to ds_threshold first
+    uint64_t ds_threshold = 0;
 };
 
 namespace spsp {
@@ -230,9 +235,15 @@ struct ParsedSketch {
 int sketch_parse_structure_host(const uint8_t* payload, uint64_t len, ParsedSketch* P);
 // decode on the GPU + all-vs-all + copy back: the device half of spsp_compare_files (spsp_decode.hip)
 // (inter: n x n, zero on entry; *mirrored = every written cell (i, j > i) was also stored at (j, i))
+// (here and in compare_payloads_multi: with ctx->ds_armed -- ctxs[0]'s there -- the decoded keys are brought down to the selection
+// threshold ctx->ds_threshold on the device before they are compared / dealt into exchange slots; card = the surviving keys.
+// The request holds for that one call.)
 int compare_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, const int* extra_has,
                           const uint32_t* extra_mn, uint32_t n_query, uint32_t* k_out, uint32_t* m_out, uint32_t* inter, uint64_t* card,
                           bool* mirrored = nullptr, std::vector<uint64_t>* cells_out = nullptr);
+// spsp_downsample.hip: the keys whose minimizer's hash is <= threshold, sketches back to back, order kept, in context-owned arrays
+int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
+                         const uint64_t* h_sk_off, uint32_t n, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out);
 // (cells_out, for 1024 <= n <= 65535: the non-zero cells i << 48 | j << 32 | count, every pair once, INSTEAD of the matrix: inter may be null)
 int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
                               const int* extra_has, const uint32_t* extra_mn, uint32_t* k_out, uint32_t* m_out, uint64_t* sk_off);

@@ -240,6 +240,9 @@ int run_stage(uint32_t n_ctx, MultiShared& S, F&& body) {
 int compare_payloads_multi(spsp_ctx* const* ctxs, uint32_t n_ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
                            const int* extra_has, const uint32_t* extra_mn, uint32_t n_query, uint32_t* k_out, uint32_t* m_out,
                            uint32_t* inter, uint64_t* card, bool* mirrored, std::vector<uint64_t>* cells_out) {
+    const bool ds_on = n_ctx && ctxs[0]->ds_armed;
+    const uint64_t ds_threshold = n_ctx ? ctxs[0]->ds_threshold : 0;
+    if (n_ctx) ctxs[0]->ds_armed = false;
     if (mirrored) *mirrored = false;
     if (cells_out) cells_out->clear();
     if (n_ctx == 0 || n_ctx > kMaxParts) { set_error("1..%u contexts", kMaxParts); return SPSP_ERR_ARG; }
@@ -256,6 +259,8 @@ int compare_payloads_multi(spsp_ctx* const* ctxs, uint32_t n_ctx, const uint8_t*
     S.sk_off.assign(n_ctx, std::vector<uint64_t>((size_t)S.per + 1, 0));
     S.rc.assign(n_ctx, SPSP_OK); S.err.assign(n_ctx, std::string());
     std::vector<uint32_t> ks(n_ctx, 0), ms(n_ctx, 0);
+    struct Keys { const uint32_t* mn = nullptr; const uint64_t *lo = nullptr, *hi = nullptr; };
+    std::vector<Keys> keys(n_ctx);                                  // what every context deals into the slots: its decoded keys, or those brought down
     // (inter is zero on entry)
     // peers: every context's device reads the others' slots
     for (uint32_t a = 0; a < n_ctx; ++a)
@@ -277,6 +282,16 @@ int compare_payloads_multi(spsp_ctx* const* ctxs, uint32_t n_ctx, const uint8_t*
             const int r = sketch_decode_device_impl(c, payloads + b0, lens + b0, b1 - b0, extra_has ? extra_has + b0 : nullptr, extra_mn ? extra_mn + b0 : nullptr,
                                                     &ks[d], &ms[d], off.data());
             if (r) return r;
+            keys[d].mn = c->c_min.as<uint32_t>(); keys[d].lo = c->c_lo.as<uint64_t>(); keys[d].hi = ks[d] > 32 ? c->c_hi.as<uint64_t>() : nullptr;
+            if (ds_on && off.back()) {
+                // mixed sampling rates: this context's keys brought down before they are dealt -- a filtered key never crosses the fabric
+                uint32_t* f_mn = nullptr; uint64_t *f_lo = nullptr, *f_hi = nullptr;
+                std::vector<uint64_t> kept(off.size(), 0);
+                const int r2 = keys_downsample_impl(c, ks[d], ds_threshold, keys[d].mn, keys[d].lo, keys[d].hi, off.data(), b1 - b0, &f_mn, &f_lo, &f_hi, kept.data());
+                if (r2) return r2;
+                keys[d].mn = f_mn; keys[d].lo = f_lo; keys[d].hi = f_hi;
+                off.swap(kept);
+            }
         }
         for (uint32_t j = 0; j <= S.per; ++j) S.sk_off[d][j] = off[std::min<size_t>(j, off.size() - 1)];
         for (uint32_t i = b0; i < b1; ++i) card[i] = off[i - b0 + 1] - off[i - b0];
@@ -305,7 +320,7 @@ int compare_payloads_multi(spsp_ctx* const* ctxs, uint32_t n_ctx, const uint8_t*
             SPSP_HIP(hipSetDevice(c->device));
             int r;
             if ((r = c->m_send.reserve((size_t)slot_sz * n_ctx + 64)) || (r = c->m_recv.reserve((size_t)slot_sz * n_ctx + 64))) return r;
-            if ((r = partition_keys_impl(c, S.k, c->c_min.as<uint32_t>(), c->c_lo.as<uint64_t>(), has_hi ? c->c_hi.as<uint64_t>() : nullptr, S.sk_off[d].data(), S.per,
+            if ((r = partition_keys_impl(c, S.k, keys[d].mn, keys[d].lo, has_hi ? keys[d].hi : nullptr, S.sk_off[d].data(), S.per,
                                          n_ctx, S.cap, c->m_send.as<uint8_t>()))) return r;
             // how full did the slots get? (header word 2 = keys that wanted in) -- the WHOLE headers come back in this wait: the
             // receivers take them from here (hdrs[sender][destination]) instead of reading them back once more
