@@ -560,6 +560,54 @@ int spsp_compare_slots_cells_device(spsp_ctx* ctx, uint32_t k, const void* d_slo
 /* d_inter[i][j] += count for every packed cell (the collecting side of the above) */
 int spsp_matrix_add_cells_device(spsp_ctx* ctx, void* d_inter, uint32_t n, const void* d_cells, uint64_t n_cells);
 
+/* ------------------------------------------------------------- gather ---- */
+/* Which references make up a query sketch (not in the reference, whose comparator -q stops at one row of containment numbers:
+ * ten strains that share their k-mers with the one strain in the sample all score 0.9 there).  Greedy, on sets of the
+ * comparator's keys, integers only.  Q = the keys of one query, R_0 .. R_{N-1} those of the references in list order, A_0 = Q;
+ * round r = 1, 2, ...: u_j = |R_j n A_{r-1}|; j* = the SMALLEST j among those with the largest u_j; stop if u_j* < min_keys,
+ * or if max_rounds > 0 and r > max_rounds; else emit the row below and A_r = A_{r-1} \ R_j*.  A reference is named at most
+ * once, unique <= intersect, `unique` never grows down a query's rows, and |Q| - sum(unique) = the last row's `remaining`.
+ * Several queries are gathered independently against the same references. */
+typedef struct spsp_gather_row {
+    uint32_t query;      /* index of the query sketch (< n_query) */
+    uint32_t rank;       /* r: 1 for the query's first row */
+    uint32_t match;      /* j* as the sketch's index in the call's list (>= n_query) */
+    uint32_t reserved;   /* 0 */
+    uint64_t intersect;  /* |R_j* n Q| */
+    uint64_t unique;     /* u_j*: keys nobody named before it explains */
+    uint64_t remaining;  /* |A_{r-1}| - u_j*: keys of the query still unexplained behind this row */
+} spsp_gather_row;
+
+/* Input: the concatenated key arrays every comparison entry point takes, SORTED per sketch as the decoder leaves them
+ * ((minimizer, kmer_hi, kmer_lo) ascending: the match is a binary search), the n_query queries first, the references behind
+ * them -- the layout of query mode.  The arrays are only read (the decoder's and the downsampler's stay as they are); the
+ * work buffers belong to the context and are reused call after call.  Rows come back ordered by (query, rank); a query that
+ * names nobody has none.  More rows than `cap`: SPSP_ERR_OVERFLOW with *n_rows = the room needed and `rows` untouched.
+ * SPSP_ERR_ARG for n_query == 0, n_query >= n, min_keys == 0, n > 65535, keys that are not strictly increasing inside a
+ * sketch, and on a context switched to unordered keys (spsp_compare_keys_unordered).  Launches: one match pass over the
+ * reference keys per query (one launch), two scans, one fill, then two small launches per round queued in batches of 32,
+ * 64, 128, ... rounds for all queries at once; the host waits once for the match count and once per batch, never per round. */
+int spsp_gather_device(spsp_ctx* ctx, uint32_t k, const void* d_minimizer, const void* d_kmer_lo, const void* d_kmer_hi /* NULL if k <= 32 */,
+                       const uint64_t* h_sk_off, uint32_t n, uint32_t n_query, uint64_t min_keys, uint32_t max_rounds,
+                       spsp_gather_row* rows, uint64_t cap, uint64_t* n_rows);
+/* The rows as text: the line "query,rank,match,intersect,unique,f_unique_query,f_match,remaining", then one line per row --
+ * names[query] and names[match] as they stand, the integers in decimal, f_unique_query = unique / card[query] and f_match =
+ * intersect / card[match] as IEEE double divisions printed as the matrices print a score (%.<precision>g).  card[i] = the key
+ * count of sketch i as the gather saw it.  No rows: the header line alone.  A row that names a sketch outside the lists, or a
+ * query as a match, is SPSP_ERR_ARG.  *text is released with spsp_free(). */
+int spsp_gather_csv_host(const spsp_gather_row* rows, uint64_t n_rows, const char* const* names, uint32_t n, uint32_t n_query,
+                         const uint64_t* card, int precision, char** text, uint64_t* len);
+/* The whole-file driver: the files are read, inflated and decoded as spsp_compare_files_rate does it (the same code), with the
+ * same `rate` argument -- SPSP_RATE_AS_IS, a rate, or SPSP_RATE_COARSEST; the downsampling pass then runs between the decoder
+ * and the match, and card counts the surviving keys -- and the same refusals (a file coarser than the common rate, differing k
+ * or m); k == m collections are SPSP_ERR_ARG with and without a rate (their phantom key has no meaning here).  Writes ONE file,
+ * <out_prefix>_gather.csv.gz (gzip level 1, as the matrices), and no matrices.  chatter != 0: the reference's "kmers evaluated"
+ * line, then one line per query -- how many references were named, how many keys remain -- and the common-rate line when a
+ * rate was asked for.  rows (may be NULL) receives a copy of the rows, released with spsp_free(); n_rows may be NULL. */
+int spsp_gather_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, uint64_t min_keys,
+                      uint32_t max_rounds, const char* out_prefix, int chatter, double rate,
+                      spsp_gather_row** rows /* may be NULL; spsp_free */, uint64_t* n_rows);
+
 #ifdef __cplusplus
 }
 #endif

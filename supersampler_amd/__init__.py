@@ -75,6 +75,15 @@ class HbmRates(C.Structure):
                 ("bytes", C.c_uint64), ("reps", C.c_uint32), ("n_cu", C.c_uint32)]
 
 
+class GatherRow(C.Structure):
+    """spsp_gather_row: one named reference of one query (include/spsp.h)"""
+    _fields_ = [("query", C.c_uint32), ("rank", C.c_uint32), ("match", C.c_uint32), ("reserved", C.c_uint32),
+                ("intersect", C.c_uint64), ("unique", C.c_uint64), ("remaining", C.c_uint64)]
+
+
+GATHER_ROW_DTYPE = np.dtype([("query", "<u4"), ("rank", "<u4"), ("match", "<u4"), ("reserved", "<u4"), ("intersect", "<u8"), ("unique", "<u8"),
+                             ("remaining", "<u8")])
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -87,6 +96,7 @@ ABI_SYMBOLS = [
     "spsp_compare_device", "spsp_slot_bytes", "spsp_partition_keys_device", "spsp_compare_slots_device", "spsp_compare_device_begin", "spsp_compare_slots_device_begin", "spsp_compare_end", "spsp_fasta_clean_host", "spsp_fasta_clean_device", "spsp_fasta_clean_packed_device", "spsp_fastq_clean_device", "spsp_fastq_clean_packed_device", "spsp_sketch_text", "spsp_sketch_build_host", "spsp_sketch_parse_host", "spsp_sketch_decode_device", "spsp_sketch_keys_device", "spsp_sketch_keys_device_begin", "spsp_sketch_keys_device_end", "spsp_sketch_keys_big_genomes", "spsp_scan_output_wait", "spsp_compare_keys_unordered", "spsp_compare_forget", "spsp_sketch_chain_host",
     "spsp_csv_host", "spsp_csv_cells_host", "spsp_csv_cells_gz_host", "spsp_sort_csv_host", "spsp_read_file_host", "spsp_write_gz_host", "spsp_sketch_file", "spsp_compare_files", "spsp_compare_files_chatty", "spsp_stage_times_read", "spsp_measure_hbm_device", "spsp_sketch_files", "spsp_sketch_files_multi", "spsp_sketch_files_release", "spsp_compare_files_multi", "spsp_matrix_cells_device", "spsp_matrix_add_cells_device", "spsp_compare_cells_device", "spsp_compare_slots_cells_device",
     "spsp_keys_downsample_device", "spsp_sketch_header_host", "spsp_sketch_downsample_host", "spsp_compare_files_rate", "spsp_compare_files_multi_rate",
+    "spsp_gather_device", "spsp_gather_csv_host", "spsp_gather_files",
 ]
 
 _lib = None
@@ -212,6 +222,13 @@ def lib():
         L.spsp_compare_files_rate.argtypes = [vp, P(cp), u32, u32, i32, dbl, cp, i32, dbl]
         L.spsp_compare_files_multi_rate.restype = i32
         L.spsp_compare_files_multi_rate.argtypes = [P(i32), u32, P(cp), u32, u32, i32, dbl, cp, i32, P(StageTimes), dbl]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_gather_device"):
+        L.spsp_gather_device.restype = i32
+        L.spsp_gather_device.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, u64, u32, vp, u64, P(u64)]
+        L.spsp_gather_csv_host.restype = i32
+        L.spsp_gather_csv_host.argtypes = [vp, u64, P(cp), u32, u32, vp, i32, P(vp), P(u64)]
+        L.spsp_gather_files.restype = i32
+        L.spsp_gather_files.argtypes = [vp, P(cp), u32, u32, i32, u64, u32, cp, i32, dbl, P(vp), P(u64)]
     _lib = L
     return L
 
@@ -356,6 +373,18 @@ def csv_cells_gz(jaccard, names, cells, card, gz_path, n_query=None, precision=6
     arr = (C.c_char_p * n)(*[s.encode() for s in names])
     _check(lib().spsp_csv_cells_gz_host(1 if jaccard else 0, arr, n, nq, cells.ctypes.data, len(cells), card.ctypes.data, precision,
                                         float(min_threshold), gz_path.encode()))
+
+
+def gather_csv(rows, names, card, n_query, precision=6):
+    """spsp_gather_csv_host: gather rows (GATHER_ROW_DTYPE array) -> the text of <prefix>_gather.csv.gz; card[i] = key count of
+    sketch i as the gather saw it, names = the n_query queries' names, then the references'"""
+    rows = np.ascontiguousarray(rows, dtype=GATHER_ROW_DTYPE)
+    card = np.ascontiguousarray(card, dtype=np.uint64)
+    n = len(names)
+    arr = (C.c_char_p * n)(*[s.encode() for s in names])
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_gather_csv_host(rows.ctypes.data, len(rows), arr, n, n_query, card.ctypes.data, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
 
 
 def sketches_from_payloads(payloads):
@@ -789,3 +818,29 @@ class Context:
         _check(lib().spsp_keys_downsample_device(self._h, k, threshold_value, d_min, d_lo, d_hi, sk_off.ctypes.data, n,
                                                  C.byref(o_mn), C.byref(o_lo), C.byref(o_hi), out.ctypes.data))
         return o_mn.value, o_lo.value, o_hi.value, out
+
+    def gather_device(self, k, d_min, d_lo, d_hi, sk_off, n, n_query, min_keys, max_rounds=0):
+        """spsp_gather_device: greedy gather of the first n_query sketches against the others over concatenated sorted key
+        arrays on the device -> rows (GATHER_ROW_DTYPE array ordered by (query, rank)); the room grows here on overflow"""
+        sk_off = np.ascontiguousarray(sk_off, dtype=np.uint64)
+        cap = 64
+        for _ in range(2):
+            rows = np.zeros(cap, dtype=GATHER_ROW_DTYPE)
+            cnt = C.c_uint64()
+            rc = lib().spsp_gather_device(self._h, k, d_min, d_lo, d_hi, sk_off.ctypes.data, n, n_query, min_keys, max_rounds,
+                                          rows.ctypes.data, cap, C.byref(cnt))
+            if rc != ERR_OVERFLOW or cnt.value <= cap:
+                break
+            cap = cnt.value
+        _check(rc)
+        return rows[:cnt.value].copy()
+
+    def gather_files(self, paths, out_prefix, n_query, min_keys, max_rounds=0, precision=6, rate=0.0):
+        """spsp_gather_files: sketch files (the n_query queries first) -> <out_prefix>_gather.csv.gz and the rows.
+        rate: as compare_files (0.0, a rate, or "auto")"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        out, cnt = C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_gather_files(self._h, arr, n, n_query, precision, min_keys, max_rounds, out_prefix.encode(), 0, _rate_arg(rate),
+                                       C.byref(out), C.byref(cnt)))
+        return np.frombuffer(_take(out, cnt.value * GATHER_ROW_DTYPE.itemsize), dtype=GATHER_ROW_DTYPE).copy()

@@ -1,6 +1,7 @@
 // comparator -- drop-in command line of the reference's comparator
 // (Comparator.cpp:464-521) over libspsp: same flags, defaults, messages and
-// output files (<o>_containment.csv.gz, <o>_jaccard.csv.gz).
+// output files (<o>_containment.csv.gz, <o>_jaccard.csv.gz).  One addition: -g <min_keys> with -q gathers instead --
+// which references make up each query, greedily (spsp_gather_files) -> <o>_gather.csv.gz.
 #include <getopt.h>
 
 #include <chrono>
@@ -33,6 +34,8 @@ int main(int argc, char** argv) {
     uint64_t p = 6;
     double min_threshold = 0;
     double rate = SPSP_RATE_AS_IS;   // -s <rate> / -s auto: compare at a common sampling rate (not in the reference, which parses and ignores -s)
+    bool gather = false;             // -g <min_keys>: the reference parses -g and ignores it
+    uint64_t min_keys = 0;
     while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:")) != -1) {
         switch (ch) {
             case 'f': inputfof = optarg; break;
@@ -40,6 +43,13 @@ int main(int argc, char** argv) {
             case 'p': p = stoi(optarg); break;
             case 'm': min_threshold = stod(optarg); break;
             case 'o': output_name = optarg; break;
+            case 'g': {
+                char* e = nullptr;
+                const long long v = strtoll(optarg, &e, 10);
+                if (e == optarg || *e || v < 1) { cout << "-g takes the smallest number of new keys a reference is named for, an integer >= 1, not '" << optarg << "'" << endl; return 1; }
+                gather = true; min_keys = (uint64_t)v;
+                break;
+            }
             case 's':
                 if (string(optarg) == "auto") rate = SPSP_RATE_COARSEST;
                 else {
@@ -60,6 +70,7 @@ int main(int argc, char** argv) {
              << "-o output prefix (results)" << endl;
         return 0;
     }
+    if (gather && query == "") { cout << "-g gathers the queries of -q against the index: it needs -q" << endl; return 1; }
     vector<string> names;
     uint32_t n_query = 0;
     if (query == "") {
@@ -93,6 +104,16 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (gather) {
+        // one device: the first of SPSP_DEVICES, else device 0
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_gather_files(ctx, paths.data(), (uint32_t)paths.size(), n_query, (int)p, min_keys, 0, output_name.c_str(), 1, rate, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Gather failed: " << err << endl; return 1; }
+        return 0;
     }
     // the progress lines of the reference (Comparator.cpp:56,69,364,414,503,509) are printed by the driver where the
     // reference prints them

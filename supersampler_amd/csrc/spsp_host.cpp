@@ -1524,8 +1524,12 @@ int spsp_stage_times_read(spsp_ctx* ctx, spsp_stage_times* out, int reset) {
 
 // chatter: 0 = silent; 1 = the stdout lines of the reference's all-versus-all run (Comparator.cpp:56,69,364,414,
 // 503,509); 2 = those of its query run (:56,69,364,414)
+// gather: instead of the comparison and its two matrices, the greedy gather of the first n_query sketches against the others
+// (GatherReq::device_half: spsp_gather.hip) and <out_prefix>_gather.csv.gz; everything in front of the comparison -- reading, inflating, the headers'
+// rates, the refusals -- is the same code
 static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
-                              double min_threshold, const char* out_prefix, int chatter, double rate, spsp_ctx* const* more = nullptr, uint32_t n_more = 0) {
+                              double min_threshold, const char* out_prefix, int chatter, double rate, spsp_ctx* const* more = nullptr, uint32_t n_more = 0,
+                              spsp::GatherReq* gather = nullptr) {
     // more / n_more: all contexts of a multi-device call (more[0] == ctx): the comparison is then split by key over them
     // rate: SPSP_RATE_AS_IS = the headers' rates are ignored, as the reference does; SPSP_RATE_COARSEST or a rate = every sketch
     // is brought down to it on the device first
@@ -1651,6 +1655,7 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
         if (!nl || skm <= 0 || skm > 126 || mm <= 0 || mm > 15 || (skm + mm) / 2 > 63 || (skm + mm) / 2 < mm) { set_error("bad sketch header in '%s'", paths[0]); rc = SPSP_ERR_FORMAT; }
         else { m0 = (uint32_t)mm; k0 = (uint32_t)((skm + mm) / 2); }
     }
+    if (!rc && n && gather && k0 == m0) { set_error("gather is not defined for k == m sketches (k = m = %u)", k0); rc = SPSP_ERR_ARG; }
     // the merge's shared first-read buffer, in file order (see spsp_sketch_chain_host): phantom keys of empty sketches
     std::vector<int> extra_has(n, 0);
     std::vector<uint32_t> extra_mn(n, 0);
@@ -1702,6 +1707,33 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
     std::vector<uint64_t> cells;                              // ... or no matrix at all: a large comparison comes back as its non-zero cells
     bool as_cells = false;
     std::vector<uint64_t> card(n, 0);
+    if (!rc && gather) {
+        if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }
+        t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
+        uint32_t kk = 0, mm2 = 0;
+        ctx->ds_armed = ds_on; ctx->ds_threshold = ds_thr;     // (read and cleared by the call below)
+        rc = gather->device_half(ctx, datas.data(), lens.data(), n, n_query, gather->min_keys, gather->max_rounds, &kk, &mm2, card.data(), &gather->rows);
+        free_datas();
+        t1 = now_s(); ctx->stages.compare_s += t1 - t0; t0 = t1;
+        if (rc) return rc;
+        char* text = nullptr; uint64_t len = 0;
+        if ((rc = spsp_gather_csv_host(gather->rows.data(), gather->rows.size(), paths, n, n_query, card.data(), precision, &text, &len))) return rc;
+        t1 = now_s(); ctx->stages.csv_s += t1 - t0;
+        rc = spsp_write_gz_host((std::string(out_prefix) + "_gather.csv.gz").c_str(), (const uint8_t*)text, len, 1);
+        ctx->stages.csv_gzip_s += now_s() - t1;
+        free(text);
+        if (!rc && chatter) {
+            size_t at = 0;
+            for (uint32_t q = 0; q < n_query && q < n; ++q) {
+                uint64_t named = 0, left = card[q];
+                for (; at < gather->rows.size() && gather->rows[at].query == q; ++at) { ++named; left = gather->rows[at].remaining; }
+                printf("%s: %llu reference(s) named, %llu of %llu keys remain\n", paths[q], (unsigned long long)named, (unsigned long long)left, (unsigned long long)card[q]);
+            }
+            if (n && rate != SPSP_RATE_AS_IS) printf("Sketches compared at sampling rate %g: %u of %u brought down to it\n", ds_rate, ds_brought, n);
+            fflush(stdout);
+        }
+        return rc;
+    }
     if (!rc) {
         if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }   // :56
         t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
@@ -1749,6 +1781,30 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
     return rc;
 }
 
+int spsp_gather_csv_host(const spsp_gather_row* rows, uint64_t n_rows, const char* const* names, uint32_t n, uint32_t n_query,
+                         const uint64_t* card, int precision, char** text, uint64_t* len) {
+    if (!text || !len || (n_rows && (!rows || !names || !card))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    std::string out = "query,rank,match,intersect,unique,f_unique_query,f_match,remaining\n";
+    char num[64];
+    for (uint64_t i = 0; i < n_rows; ++i) {
+        const spsp_gather_row& r = rows[i];
+        if (r.query >= n_query || r.match < n_query || r.match >= n) { set_error("gather row %llu names a sketch outside the lists", (unsigned long long)i); return SPSP_ERR_ARG; }
+        out += names[r.query]; out += ',';
+        out += std::to_string(r.rank); out += ',';
+        out += names[r.match]; out += ',';
+        out += std::to_string(r.intersect); out += ',';
+        out += std::to_string(r.unique); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, (double)r.unique / (double)card[r.query])); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, (double)r.intersect / (double)card[r.match])); out += ',';
+        out += std::to_string(r.remaining); out += '\n';
+    }
+    char* buf = (char*)malloc(out.size() ? out.size() : 1);
+    if (!buf) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    memcpy(buf, out.data(), out.size());
+    *text = buf; *len = out.size();
+    return SPSP_OK;
+}
+
 int spsp_compare_files_rate(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, double min_threshold,
                             const char* out_prefix, int chatter, double rate) {
     return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, chatter < 0 ? 0 : (chatter > 2 ? 2 : chatter), rate);
@@ -1791,3 +1847,10 @@ int spsp_compare_files_multi_rate(const int* devices, uint32_t n_dev, const char
 }
 
 }  // extern "C"
+
+namespace spsp {
+int gather_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, const char* out_prefix, int chatter,
+                      double rate, GatherReq* G) {
+    return compare_files_impl(ctx, paths, n, n_query, precision, 0.0, out_prefix, chatter ? 2 : 0, rate, nullptr, 0, G);
+}
+}  // namespace spsp

@@ -184,6 +184,9 @@ struct spsp_ctx {
     // key downsampling (spsp_downsample.hip): two sets of output arrays used in turn (ds_flip: the set the next call fills), work area
     spsp::DevBuf ds_mn[2], ds_lo[2], ds_hi[2], ds_work;
     int ds_flip = 0;
+    // gather (spsp_gather.hip): sketch offsets, per-(query, reference) counters / their scan / fill places, per-query-key counts
+    // (the rounds' dead flags) / their scan, edge list, edges by reference, holders by query key, counters, round state, a batch's rows
+    spsp::DevBuf g_off, g_u, g_roff, g_rfill, g_qcnt, g_qoff, g_edges, g_byref, g_hold, g_count, g_state, g_rows;
     bool ds_armed = false;             // the next compare_payloads_impl / _multi call brings the decoded keys down to ds_threshold first
     uint64_t ds_threshold = 0;
 };
@@ -244,6 +247,25 @@ int compare_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const u
 // spsp_downsample.hip: the keys whose minimizer's hash is <= threshold, sketches back to back, order kept, in context-owned arrays
 int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
                          const uint64_t* h_sk_off, uint32_t n, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out);
+// spsp_gather.hip: greedy gather of the first n_query sketches against the others over concatenated sorted key arrays; rows ordered by
+// (query, rank).  gather_payloads_impl: decode (+ the downsampling pass when ctx->ds_armed, as compare_payloads_impl) + gather;
+// card = the key counts the gather saw
+int gather_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
+                       uint32_t n, uint32_t nq, uint64_t min_keys, uint32_t max_rounds, std::vector<spsp_gather_row>* rows);
+// spsp_gather_files: the request that travels through the comparator's file driver (spsp_host.cpp: reading, inflating, the headers'
+// rates and the refusals are compare_files_impl's); device_half is gather_payloads_impl -- a pointer, so that the host translation
+// unit links without the device code (the sanitizer harness builds it alone)
+struct GatherReq {
+    uint64_t min_keys = 1;
+    uint32_t max_rounds = 0;
+    std::vector<spsp_gather_row> rows;
+    int (*device_half)(spsp_ctx*, const uint8_t* const*, const uint64_t*, uint32_t, uint32_t, uint64_t, uint32_t, uint32_t*, uint32_t*, uint64_t*,
+                       std::vector<spsp_gather_row>*) = nullptr;
+};
+int gather_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, const char* out_prefix, int chatter,
+                      double rate, GatherReq* G);
+int gather_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, uint32_t n_query, uint64_t min_keys,
+                         uint32_t max_rounds, uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_gather_row>* rows);
 // (cells_out, for 1024 <= n <= 65535: the non-zero cells i << 48 | j << 32 | count, every pair once, INSTEAD of the matrix: inter may be null)
 int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
                               const int* extra_has, const uint32_t* extra_mn, uint32_t* k_out, uint32_t* m_out, uint64_t* sk_off);
