@@ -54,6 +54,13 @@ void devbuf_flush_retired() {
     for (auto& q : now) (void)hipFree(q.first);
 }
 
+int lds_opt_in(spsp_ctx* ctx, const void* kernel, size_t bytes) {
+    for (const void* k : ctx->lds_kernels) if (k == kernel) return SPSP_OK;
+    SPSP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    ctx->lds_kernels.push_back(kernel);
+    return SPSP_OK;
+}
+
 int DevBuf::reserve(size_t bytes) {
     if (bytes <= cap && p) return SPSP_OK;
     static const bool dbg = getenv("SPSP_DEBUG_ALLOC_TIMES") != nullptr;   // analysis: what growing a buffer costs (stderr)
@@ -192,9 +199,9 @@ int spsp_create(int device, void* hip_stream, spsp_ctx** out) {
         if (e != hipSuccess) { delete c; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
         c->own_stream = true;
     }
-    e = hipHostMalloc((void**)&c->h_scalar, 16 * sizeof(uint64_t), hipHostMallocDefault);
+    e = hipHostMalloc((void**)&c->h_scalar, kHostSlots * sizeof(uint64_t), hipHostMallocDefault);
     if (e != hipSuccess) { if (c->own_stream) (void)hipStreamDestroy(c->stream); delete c; return hip_fail(e, "hipHostMalloc", __FILE__, __LINE__); }
-    memset(c->h_scalar, 0, 16 * sizeof(uint64_t));
+    memset(c->h_scalar, 0, kHostSlots * sizeof(uint64_t));
     *out = c;
     return SPSP_OK;
 }

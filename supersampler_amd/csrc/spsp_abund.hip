@@ -119,9 +119,9 @@ int abundance_flags_impl(spsp_ctx* ctx, const spsp_params* p, const spsp_superkm
     if ((rc = ctx->a_cnt.reserve((size_t)n * 4)) || (rc = ctx->a_off.reserve((size_t)(n + 1) * 4))) return rc;
     hipLaunchKernelGGL(k_abund_sizes, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_sk, n, p->k, ctx->a_cnt.as<uint32_t>());
     SPSP_HIP(hipGetLastError());
-    if ((rc = launch_scan_u32(ctx, ctx->a_cnt.as<uint32_t>(), ctx->a_off.as<uint32_t>(), n, ctx->h_scalar + 7))) return rc;
+    if ((rc = launch_scan_u32(ctx, ctx->a_cnt.as<uint32_t>(), ctx->a_off.as<uint32_t>(), n, ctx->h_scalar + kHsScanTotalB))) return rc;
     SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    const uint64_t n_occ = ctx->h_scalar[7];
+    const uint64_t n_occ = ctx->h_scalar[kHsScanTotalB];
     *n_occ_out = n_occ;
     uint8_t* out = (uint8_t*)malloc((size_t)n_occ + 1);
     if (!out) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }

@@ -448,12 +448,12 @@ int sketch_build_device_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t*
     if ((rc = radix_sort_pairs(ctx, &ks, &vs, keys + n_sk, vals + n_sk, n_sk, 30 + file_bits))) return rc;
     if (ks != keys) { keys = ks; vals = vs; }                              // (the sorted arrays: whichever half the last pass wrote)
     hipLaunchKernelGGL(k_bld_counts, dim3(gsk), dim3(256), 0, ctx->stream, d_sk, (const uint64_t*)keys, (const uint32_t*)vals, n_sk, k, cnt, opens);
-    if ((rc = launch_scan_u32(ctx, cnt, place_first, n_sk, ctx->h_scalar + 6))) return rc;
-    if ((rc = launch_scan_u32(ctx, opens, open_off, n_sk, ctx->h_scalar + 7))) return rc;
+    if ((rc = launch_scan_u32(ctx, cnt, place_first, n_sk, ctx->h_scalar + kHsScanTotalA))) return rc;
+    if ((rc = launch_scan_u32(ctx, opens, open_off, n_sk, ctx->h_scalar + kHsScanTotalB))) return rc;
     hipLaunchKernelGGL(k_bld_buckets, dim3(gsk), dim3(256), 0, ctx->stream, (const uint32_t*)opens, (const uint32_t*)open_off, n_sk, bucket_sk, bucket_of);
     SPSP_HIP(hipGetLastError());
     SPSP_HIP(hipStreamSynchronize(ctx->stream));                           // the totals size everything behind this point
-    const uint64_t n_places = ctx->h_scalar[6], n_buckets = ctx->h_scalar[7];
+    const uint64_t n_places = ctx->h_scalar[kHsScanTotalA], n_buckets = ctx->h_scalar[kHsScanTotalB];
     if (n_places == 0) return SPSP_OK;
     if (n_places > 0x7ffffff0ull) { set_error("too many k-mer places for the device builder"); return SPSP_ERR_OVERFLOW; }
     uint64_t slots = 1024;
@@ -492,14 +492,14 @@ int sketch_build_device_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t*
     if (has_hi) { SPSP_BLD(true); } else { SPSP_BLD(false); }
 #undef SPSP_BLD
     hipLaunchKernelGGL(k_bld_sizes, dim3((uint32_t)((n_buckets + 255) / 256)), dim3(256), 0, ctx->stream, (const BldOut*)outs, (uint32_t)n_buckets, m, out_len);
-    if ((rc = launch_scan_u32(ctx, out_len, out_off, n_buckets, ctx->h_scalar + 6))) return rc;
+    if ((rc = launch_scan_u32(ctx, out_len, out_off, n_buckets, ctx->h_scalar + kHsScanTotalA))) return rc;
     hipLaunchKernelGGL(k_bld_file_stats, dim3((uint32_t)((n_buckets + 255) / 256)), dim3(256), 0, ctx->stream, (const BldOut*)outs, (const uint64_t*)keys,
                        (const uint32_t*)bucket_sk, (uint32_t)n_buckets, d_fstats);
     SPSP_HIP(hipGetLastError());
     // first bucket of every file, for the split of the output: bucket_of at the file's first sorted super-k-mer -- the files'
     // super-k-mers are contiguous in the sorted order too (the file is the key's top), in file order
     SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    const uint64_t total = ctx->h_scalar[6];
+    const uint64_t total = ctx->h_scalar[kHsScanTotalA];
     if (total > 0xfffffff0ull) { set_error("sketch payloads of one batch exceed 4 GiB"); return SPSP_ERR_OVERFLOW; }
     if ((rc = ctx->bl_out.reserve((size_t)total + 64))) return rc;
     hipLaunchKernelGGL(k_bld_assemble, dim3((uint32_t)n_buckets), dim3(64), 0, ctx->stream, (const BldOut*)outs, (const uint32_t*)out_off, (const uint32_t*)bucket_sk,

@@ -32,6 +32,39 @@
 
 namespace spsp {
 
+// The comparison's flag block: uint32_t words of ctx->c_flags.  The kernels of a job raise and count in them, the first kFlags
+// travel to the host with every job (k_accumulate / k_accumulate_sparse forward them to the pinned slots kHsCompareFlags, or
+// job_queue_flags copies them) and compare_end_impl decides by them.  A job that needs one more word takes a free one HERE.
+enum CompareFlag : uint32_t {
+    kCfUnsorted = 0,        // input not strictly sorted inside a sketch (k_insert, k_insert_sparse, the scatters)
+    kCfCollision = 1,       // fingerprint collision (k_fill, k_fill_sparse): two distinct keys, one fingerprint -- the host rebuilds with another seed
+    kCfRows = 2,            // dictionary forms: n_rows, k_assign_rows' counter (sizes the colour matrix)
+    kCfSpillRecs = 2,       // partition form: records of all overflowed parts (k_parts_group; sizes the spill)
+                            // ([3], [4]: unused)
+    kCfTableFull = 5,       // a table, or the spill's list space / bit columns, overflowed (internal sizing error)
+    kCfPartOverflow = 6,    // a key part overflowed its capacity (partition form): the row sums do not run, the host repeats the call
+    kCfDealt = 7,           // records dealt into parts: sizes the parts of a filtered call's next attempt
+    // device-side words, which do not travel with the first kFlags
+    kCfListsOut = 8,        // u16 of spilled lists handed out (k_spill_ranges)
+    kCfColsOut = 9,         // bit columns handed out (k_parts_group, k_spill_ranges)
+    kCfOrderNew = 10,       // k_row_order's verdict: sketches with a sketch of the same signature close in front of them in the new order
+    kCfOrderIn = 11,        // ... in the input's order
+    kCfMultiListed = 12,    // k_parts_group, in a sample of the parts: records that have a list
+    kCfMultiSampled = 13,   // ... and records
+    kCfWords = 14           // words a comparison's kernels may touch; behind them kCfCellCount and kCfKeysFlags (spsp_internal.h)
+};
+constexpr int kFlags = 8;               // words that travel to the host with every job
+constexpr uint32_t kCfClearFirst = 16;  // words cleared in front of a first attempt (k_prepare, k_parts_prepare): all of them, the cell count included
+constexpr uint32_t kCfClearRetry = 3;   // words k_prepare clears in front of a retry: those the build writes again
+static_assert(kCfDealt < kFlags && kFlags <= kCfListsOut, "the host reads words [0, kFlags)");
+static_assert(kCfWords <= kCfCellCount && kCfCellCount + 2 <= kCfClearFirst && kCfClearFirst <= kCfKeysFlags, "a first attempt clears the comparison's words and no one else's");
+static_assert(kCfRows < kCfClearRetry && kCfCollision < kCfClearRetry && kCfClearRetry <= kCfTableFull, "a retry clears what the dictionary build writes again");
+static_assert(kFlags * sizeof(uint32_t) <= (kHsCells - kHsCompareFlags) * sizeof(uint64_t), "the host's copy of the flags ends in front of the next pinned slot");
+// the verdicts travel as one copy of four words into two pinned slots (job_parts)
+static_assert(kCfOrderIn == kCfOrderNew + 1 && kCfMultiListed == kCfOrderNew + 2 && kCfMultiSampled == kCfOrderNew + 3, "order verdict, then multi verdict");
+// the pinned copy of words [0, kFlags)
+static inline uint32_t* compare_host_flags(spsp_ctx* ctx) { return reinterpret_cast<uint32_t*>(ctx->h_scalar + kHsCompareFlags); }
+
 struct Keys {
     const uint32_t* mn;
     const uint64_t* lo;
@@ -103,7 +136,6 @@ __global__ __launch_bounds__(256) void k_prepare(uint4* __restrict__ table, uint
     for (uint64_t i = t; i < n_skoff; i += stride) dev_skoff[i] = host_skoff[i];
 }
 
-// flags[0]: input not strictly sorted inside a sketch; flags[1]: fingerprint collision
 // rows a call owns: row_first, row_first + row_stride, ... below row_limit (strided over ranks: first < stride; a block
 // of rows: stride 1)
 __host__ __device__ __forceinline__ bool owned_row(uint32_t j, uint32_t row_first, uint32_t row_stride, uint32_t row_limit) {
@@ -118,7 +150,7 @@ __global__ void k_insert(Keys K, const uint64_t* __restrict__ sk_off, uint32_t n
     const uint32_t j = blockIdx.y;
     const uint64_t e = sk_off[j] + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= sk_off[j + 1]) return;
-    if (e > sk_off[j] && !key_less(K, e - 1, e)) atomicOr(&flags[0], 1u);
+    if (e > sk_off[j] && !key_less(K, e - 1, e)) atomicOr(&flags[kCfUnsorted], 1u);
     if (!owned_row(j, row_first, row_stride, row_limit)) return;   // not an owned (and printed) row
     if (passes > 1 && pass_of(K.lo[e], K.mn[e], K.hi ? K.hi[e] : 0, K.hi != nullptr, passes) != pass) return;
     const uint64_t fp = fingerprint(K, e, seed);
@@ -133,7 +165,7 @@ __global__ void k_insert(Keys K, const uint64_t* __restrict__ sk_off, uint32_t n
             break;
         }
         if (old == fp) break;
-        if (probes > mask) { atomicOr(&flags[5], 1u); break; }   // table full (cannot happen at load <= 1/2): never spin
+        if (probes > mask) { atomicOr(&flags[kCfTableFull], 1u); break; }   // table full (cannot happen at load <= 1/2): never spin
         pos = (pos + 1) & mask;
     }
 }
@@ -194,7 +226,7 @@ __global__ void k_fill(Keys K, const uint64_t* __restrict__ sk_off, uint32_t n, 
     const uint64_t mask = (1ull << log2cap) - 1;
     uint64_t pos = home_slot(fp, log2cap);
     for (uint64_t probes = 0;; ++probes) {
-        if (probes > mask) { atomicOr(&flags[5], 1u); return; }
+        if (probes > mask) { atomicOr(&flags[kCfTableFull], 1u); return; }
         const uint64_t v = table[pos];
         if (v == 0) return;  // key not held by any owned sketch: contributes to no owned row
         if (v == fp) {
@@ -207,7 +239,7 @@ __global__ void k_fill(Keys K, const uint64_t* __restrict__ sk_off, uint32_t n, 
             } else if (own) {
                 // an owned key was inserted under this fingerprint, so this IS its slot: a different full key
                 // here means two distinct keys share a fingerprint -> the host rebuilds with another seed
-                atomicOr(&flags[1], 1u);
+                atomicOr(&flags[kCfCollision], 1u);
             }
             return;  // equal keys share the first slot with this fingerprint; nothing further down matches
         }
@@ -242,7 +274,7 @@ __global__ void k_insert_sparse(Keys K, const uint64_t* __restrict__ sk_off, uin
     const uint32_t j = blockIdx.y;
     const uint64_t e = sk_off[j] + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= sk_off[j + 1]) return;
-    if (e > sk_off[j] && !key_less(K, e - 1, e)) atomicOr(&flags[0], 1u);
+    if (e > sk_off[j] && !key_less(K, e - 1, e)) atomicOr(&flags[kCfUnsorted], 1u);
     const uint64_t fp = fingerprint(K, e, seed);
     const uint64_t mask = (1ull << log2cap) - 1;
     uint64_t pos = home_slot(fp, log2cap);
@@ -254,7 +286,7 @@ __global__ void k_insert_sparse(Keys K, const uint64_t* __restrict__ sk_off, uin
             break;
         }
         if (old == fp) break;
-        if (probes > mask) { atomicOr(&flags[5], 1u); slot_of_entry[e] = 0xffffffffu; return; }   // later passes skip the entry
+        if (probes > mask) { atomicOr(&flags[kCfTableFull], 1u); slot_of_entry[e] = 0xffffffffu; return; }   // later passes skip the entry
         pos = (pos + 1) & mask;
     }
     atomicAdd(&cnt[pos], 1u);                   // result unused: a returning atomic here costs 60 % more (measured)
@@ -307,7 +339,7 @@ __global__ void k_fill_sparse(Keys K, const uint64_t* __restrict__ sk_off, uint3
     const uint32_t pos = slot_of_entry[e];
     if (pos == 0xffffffffu) return;             // table overflow was flagged by the insert pass
     const bool same = SK.lo[pos] == K.lo[e] && SK.mn[pos] == K.mn[e] && (!K.hi || SK.hi[pos] == K.hi[e]);
-    if (!same) atomicOr(&flags[1], 1u);         // two distinct keys, one fingerprint: the host rebuilds with another seed
+    if (!same) atomicOr(&flags[kCfCollision], 1u);         // two distinct keys, one fingerprint: the host rebuilds with another seed
     const uint32_t o = off[pos];
     const uint32_t idx = atomicSub(&cnt[pos], 1u);   // counts down c .. 1: the places behind the length word
     ids[o + idx] = (uint16_t)j;
@@ -315,12 +347,6 @@ __global__ void k_fill_sparse(Keys K, const uint64_t* __restrict__ sk_off, uint3
 }
 
 constexpr int kSparseCols = 16384;
-constexpr int kFlags = 8;   // [0] unsorted input, [1] fingerprint collision, [2] n_rows (dictionary forms) / records of overflowed parts (partition
-                            // form: sizes the spill), [3] / [4] unused, [5] table full, [6] a key part overflowed its
-                            // capacity (partition form), [7] records dealt into parts -- these eight travel to the host with every job.
-                            // Device-side words behind them (16 in all, cleared by k_parts_prepare): [8] u16 of spilled lists handed out,
-                            // [9] bit columns handed out, [10] / [11] k_row_order's verdict, [12] / [13] records with a list / records in a
-                            // sample of the parts (k_parts_group), [14..15] the cell count of a comparison returned as cells
 // grid.y = owned row (sketch row_first + y * row_stride), grid.x = block of `cols` columns, grid.z = slice of the
 // row's keys (split > 1: the slices add into cells zeroed by k_zero_rows).  Counters live in dynamic LDS,
 // `copies` of each, interleaved (counter c of copy k at c * copies + k): the lists of one row's keys name the
@@ -357,7 +383,7 @@ __global__ __launch_bounds__(T) void k_accumulate_sparse(const uint32_t* __restr
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < kFlags) host_flags[threadIdx.x] = flags[threadIdx.x];
     // a part overflowed: its workgroup of k_parts_group left without writing list references, so the ones in place are
     // whatever the buffer held before -- nothing may be followed from them (the host repeats the call with more parts)
-    if (flags[6]) return;
+    if (flags[kCfPartOverflow]) return;
     // Which row: workgroups go to the 8 XCDs round-robin by their flat number, so consecutive rows -- the members of a family,
     // which hold the same keys and therefore fetch the SAME holder lists -- would run on eight different L2s.  With xcd_rows
     // (= rows per XCD; grids of one column block and one slice only) XCD x takes the rows [x xcd_rows, (x + 1) xcd_rows) in
@@ -377,9 +403,8 @@ __global__ __launch_bounds__(T) void k_accumulate_sparse(const uint32_t* __restr
     uint32_t r = by;
     if (xcd_rows) { r = (by & 7u) * xcd_rows + (by >> 3); if ((by >> 3) >= xcd_rows) continue; }
     if (row_order && r >= n) continue;
-    // (row_order: every row owned; flags[10] / flags[11] = sketches with a sketch of the same signature close in front of them in the
-    // new order / in the input's: the new order is taken when the input keeps fewer than half as many together)
-    const bool reorder = row_order && 2u * flags[11] < flags[10];
+    // (row_order: every row owned; the new order is taken when the input's keeps fewer than half as many sketches of one signature together)
+    const bool reorder = row_order && 2u * flags[kCfOrderIn] < flags[kCfOrderNew];
     const uint32_t i = reorder ? row_order[r] : row_first + r * row_stride, col0 = TOUCH ? 0u : blockIdx.x * cols;
     if (i >= n || i >= row_limit) continue;
     if (col0 + cols <= i + 1 || i + 1 >= n) continue;       // no column > i in this block / at all
@@ -418,7 +443,7 @@ __global__ __launch_bounds__(T) void k_accumulate_sparse(const uint32_t* __restr
     auto counter = [&](uint32_t idx) { return HALF ? (s_cnt[idx >> 1] >> ((idx & 1u) << 4)) & 0xffffu : s_cnt[idx]; };
     // kAccR list references are fetched together (the partition form reaches them through `where`: two dependent
     // loads, the second scattered -- eight of each in flight per thread hide the extra hop), then the lists kAccU at a time
-    const bool use_multi = multi && (multi_slots >> 31 ? true : 5u * flags[12] < 2u * flags[13]);   // (top bit of multi_slots: the host insists, SPSP_DEBUG_MULTI=1)     // (records with a list / records, in a sample of the parts: k_parts_group)
+    const bool use_multi = multi && (multi_slots >> 31 ? true : 5u * flags[kCfMultiListed] < 2u * flags[kCfMultiSampled]);   // (top bit of multi_slots: the host insists, SPSP_DEBUG_MULTI=1)     // (records with a list / records, in a sample of the parts: k_parts_group)
     for (uint64_t eb = e0; eb < e1; eb += (uint64_t)kAccR * T) {     // (every lane makes every round: the waves pool their long lists, below)
         const uint64_t e = eb + threadIdx.x;
         uint32_t refs[kAccR];
@@ -658,7 +683,7 @@ __global__ __launch_bounds__(256) void k_zero_rows(uint32_t n, uint32_t row_firs
 //                     themselves in with an exchange); every chain head then writes the key's sketch list
 //                     (length + u16 ids) into the part's slice of `ids` and the list's place for each of its entries
 //   k_accumulate_sparse  as in the sketch-list form above: row sums by walking the lists
-// Parts have a fixed capacity; one that overflows (heavily duplicated keys) raises flags[6] and the host
+// Parts have a fixed capacity; one that overflows (heavily duplicated keys) raises kCfPartOverflow and the host
 // falls back to the global-dictionary forms.
 constexpr uint32_t kColFlag = 0x80000000u;      // in place of a list offset: the key has a column of the bit matrix, not a list (k_spill_pairs)
 constexpr int kPartCap = 4096, kPartSlots = 7936, kGroupThreads = 1024;   // (record index + 1 fits the 13 low bits of a slot word)
@@ -770,7 +795,7 @@ __global__ __launch_bounds__(1024) void k_row_order(const unsigned long long* __
     }
 #pragma unroll
     for (int d = 32; d; d >>= 1) { near_new += __shfl_xor(near_new, d); near_in += __shfl_xor(near_in, d); }
-    if (lane == 0) { if (near_new) atomicAdd(&stats[0], near_new); if (near_in) atomicAdd(&stats[1], near_in); }
+    if (lane == 0) { if (near_new) atomicAdd(&stats[0], near_new); if (near_in) atomicAdd(&stats[kCfOrderIn - kCfOrderNew], near_in); }
 }
 
 // sub_sk[c] = sketch holding entry c * kScatSub (worked out by the host, which has the offsets anyway)
@@ -786,7 +811,7 @@ __global__ __launch_bounds__(256) void k_parts_prepare(uint32_t* __restrict__ pa
     // form of the comparison owns -- start from zero; the diagonal and the lower triangle stay the caller's (spsp.h)
     for (uint32_t i = t; i < zero_n * zero_n; i += stride)
         if (i % zero_n > i / zero_n) zero_inter[i] = 0;
-    if (t < 16) flags[t] = 0;
+    if (t < kCfClearFirst) flags[t] = 0;
     for (uint32_t i = t; i < n_skoff; i += stride) dev_skoff[i] = host_skoff[i];
     for (uint32_t i = t; i < n_sub; i += stride) dev_sub[i] = host_sub[i];
 }
@@ -851,7 +876,7 @@ __global__ __launch_bounds__(kScatThreads, 4) void k_parts_scatter(Keys K, const
         sk_of[u] = j;
         if (check_order && e > sk_off[j]) {               // strictly increasing inside a sketch (spsp_compare_keys_unordered: the caller vouches
             const bool less = pmn != mn[u] ? pmn < mn[u] : (HAS_HI && phi != hi[u]) ? phi < hi[u] : plo < lo[u];   // for distinct keys instead)
-            if (!less) atomicOr(&flags[0], 1u);
+            if (!less) atomicOr(&flags[kCfUnsorted], 1u);
         }
     }
     // an owned row i counts holders j > i only: nothing of the sketches in front of the first owned row is dealt.
@@ -979,7 +1004,7 @@ __global__ __launch_bounds__(kScatThreads, 4) void k_parts_scatter_tiles(Keys K,
             if (check_order && valid && e > sk_off[sk_of[u]]) {   // strictly increasing inside a sketch (spsp_compare_keys_unordered: the caller vouches for distinct keys instead)
                 if (lane == 0 || first_of_run[u]) { plo = K.lo[e - 1]; pmn = K.mn[e - 1]; if (HAS_HI) phi = K.hi[e - 1]; }
                 const bool less = pmn != mn[u] ? pmn < mn[u] : (HAS_HI && phi != hi[u]) ? phi < hi[u] : plo < lo[u];
-                if (!less) atomicOr(&flags[0], 1u);
+                if (!less) atomicOr(&flags[kCfUnsorted], 1u);
             }
             hsh[u] = key_hash(lo[u], mn[u], hi[u], HAS_HI);
             keep[u] = valid && sk_of[u] >= row_first;     // (sketches in front of the first owned row are never counted by an owned row)
@@ -1035,8 +1060,8 @@ __global__ __launch_bounds__(kGroupThreads) void k_parts_group(const uint64_t* _
     uint32_t* cursor = slot + kPartSlots;
     const uint32_t p = blockIdx.x, t = threadIdx.x;
     const uint32_t n = part_cnt[p];
-    if (t == 0) atomicAdd(&flags[7], n);                  // records in all parts: sizes the parts of a filtered call's next attempt
-    if (n > (uint32_t)kPartCap) { if (t == 0) { atomicOr(&flags[6], 1u); atomicAdd(&flags[2], n); } return; }   // ([2]: records of all overflowed parts -- sizes the spill)
+    if (t == 0) atomicAdd(&flags[kCfDealt], n);                  // records in all parts: sizes the parts of a filtered call's next attempt
+    if (n > (uint32_t)kPartCap) { if (t == 0) { atomicOr(&flags[kCfPartOverflow], 1u); atomicAdd(&flags[kCfSpillRecs], n); } return; }
     for (uint32_t x = t; x < (uint32_t)kPartSlots; x += kGroupThreads) slot[x] = 0;
     if (t == 0) { cursor[0] = 0; cursor[1] = 0; }
     const uint64_t* base = recs + (uint64_t)p * kPartCap * W;
@@ -1086,7 +1111,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_parts_group(const uint64_t* _
     // multi: one bit per record slot -- does the record's key have a list?  The row sums look here (8.7 MB at configs[3]: it
     // stays in the L2s) before they fetch a list reference (70 MB, a line from HBM each): a key held by one sketch costs them
     // no miss.  A wave's 64 consecutive slots are one 8-byte store.
-    // (flags[12] / flags[13] = records that have a list / records, of every 64th part: the row sums use the bits only when fewer than 2 in 5 do -- with more, the extra
+    // (kCfMultiListed / kCfMultiSampled, of every 64th part: the row sums use the bits only when fewer than 2 in 5 do -- with more, the extra
     // dependent read costs more than the misses it saves: 0.84 -> 0.99 ms at configs[3], 0.84 -> 0.32 for unrelated sketches)
     if (multi) {                                          // (not made when the context's last comparison had no use for it: job_parts)
         uint32_t listed = 0;
@@ -1099,7 +1124,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_parts_group(const uint64_t* _
         if ((p & 63u) == 0) {                             // (a sample: one part in 64 -- an atomic per workgroup on one word was 0.15 ms)
             if ((t & 63u) == 0 && listed) atomicAdd(cursor + 1, listed);      // (the word behind the list cursor: summed per workgroup)
             __syncthreads();
-            if (t == 0) { atomicAdd(&flags[12], cursor[1]); atomicAdd(&flags[13], n); }
+            if (t == 0) { atomicAdd(&flags[kCfMultiListed], cursor[1]); atomicAdd(&flags[kCfMultiSampled], n); }
         }
     }
     __syncthreads();                                      // (every count has been read: the slots are reused for the list places)
@@ -1108,8 +1133,8 @@ __global__ __launch_bounds__(kGroupThreads) void k_parts_group(const uint64_t* _
     for (uint32_t u = 0; u < R; ++u) {
         if (!claimer[u] || cnt[u] < 2) continue;          // one thread per key held by >= 2 sketches
         if (cnt[u] >= t_bits) {                           // spill attempts only (else t_bits = 0xffffffff): a column instead of a list, see k_spill_pairs
-            const uint32_t col = atomicAdd(&flags[9], 1u);
-            if (col >= max_cols) atomicOr(&flags[5], 1u);
+            const uint32_t col = atomicAdd(&flags[kCfColsOut], 1u);
+            if (col >= max_cols) atomicOr(&flags[kCfTableFull], 1u);
             slot[hs[u]] = kColFlag | (col < max_cols ? col : 0u);
             continue;
         }
@@ -1167,7 +1192,7 @@ __global__ __launch_bounds__(kSpillThreads) void k_spill_insert(Keys K, const ui
                                                                uint32_t* __restrict__ where, uint32_t* __restrict__ rank_of, uint32_t room,
                                                                uint32_t* __restrict__ flags, uint32_t classes, uint32_t cls,
                                                                const uint32_t* __restrict__ sub_sk) {
-    if (flags[2] > room) return;                          // more records than this attempt has room for: the host repeats it with the count
+    if (flags[kCfSpillRecs] > room) return;                          // more records than this attempt has room for: the host repeats it with the count
     const uint64_t e = e_first + (uint64_t)blockIdx.x * kSpillThreads + threadIdx.x;
     if (e >= S) return;
     const uint64_t lo = K.lo[e], hi = HAS_HI ? K.hi[e] : 0ull;
@@ -1184,7 +1209,7 @@ __global__ __launch_bounds__(kSpillThreads) void k_spill_insert(Keys K, const ui
         if (cur == 0) break;                              // claimed
         const uint64_t c = cur - 1u;
         if (K.lo[c] == lo && K.mn[c] == mn && (!HAS_HI || K.hi[c] == hi)) break;
-        if (probes > mask) { atomicOr(&flags[5], 1u); where[e] = kNoWhere; return; }
+        if (probes > mask) { atomicOr(&flags[kCfTableFull], 1u); where[e] = kNoWhere; return; }
         pos = (pos + 1u) & mask;
     }
     atomicAdd(&cnt[pos], 1u);                             // (result unused: the keys that nearly every sketch holds put thousands of these on one word, and
@@ -1192,13 +1217,12 @@ __global__ __launch_bounds__(kSpillThreads) void k_spill_insert(Keys K, const ui
     where[e] = pos;                                       // (until k_spill_fill has run)
 }
 
-// flags[8] = u16 of lists handed out, flags[9] = columns handed out
 __global__ __launch_bounds__(kRowThreads) void k_spill_ranges(const uint32_t* __restrict__ cnt, uint64_t cap, uint32_t* __restrict__ off,
                                                              uint16_t* __restrict__ ids, uint32_t ids_base, uint32_t ids_room,
                                                              uint32_t* __restrict__ lref, uint32_t t_bits, uint32_t max_cols, uint32_t room,
                                                              uint32_t* __restrict__ flags) {
-    if (flags[2] > room) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) flags[6] = 0;           // the overflowed parts are taken care of: the row sums may run
+    if (flags[kCfSpillRecs] > room) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) flags[kCfPartOverflow] = 0;           // the overflowed parts are taken care of: the row sums may run
     __shared__ uint32_t wave_sum[kRowThreads / 64], wave_cols[kRowThreads / 64];
     __shared__ uint32_t s_base, s_cols;
     const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
@@ -1225,10 +1249,10 @@ __global__ __launch_bounds__(kRowThreads) void k_spill_ranges(const uint32_t* __
         if (w < wid) { pre += wave_sum[w]; pre_c += wave_cols[w]; }
         all += wave_sum[w]; all_c += wave_cols[w];
     }
-    if (t == 0) { s_base = all ? atomicAdd(&flags[8], all) : 0u; s_cols = all_c ? atomicAdd(&flags[9], all_c) : 0u; }
+    if (t == 0) { s_base = all ? atomicAdd(&flags[kCfListsOut], all) : 0u; s_cols = all_c ? atomicAdd(&flags[kCfColsOut], all_c) : 0u; }
     __syncthreads();
     uint32_t at = s_base + pre + x - sum, col = s_cols + pre_c + y - cols;
-    if ((all && s_base + all > ids_room) || (all_c && s_cols + all_c > max_cols)) { if (t == 0) atomicOr(&flags[5], 1u); return; }   // (cannot happen: sized from the count)
+    if ((all && s_base + all > ids_room) || (all_c && s_cols + all_c > max_cols)) { if (t == 0) atomicOr(&flags[kCfTableFull], 1u); return; }   // (cannot happen: sized from the count)
 #pragma unroll
     for (int u = 0; u < kRowSlots; ++u) {
         const uint64_t sl = base_slot + u;
@@ -1249,7 +1273,7 @@ __global__ __launch_bounds__(kSpillThreads) void k_spill_fill(Keys K, const uint
                                                              unsigned long long* __restrict__ bits, uint32_t* __restrict__ where,
                                                              const uint32_t* __restrict__ rank_of, uint32_t room, const uint32_t* __restrict__ flags,
                                                              uint32_t classes, uint32_t cls, const uint32_t* __restrict__ sub_sk) {
-    if (flags[2] > room || flags[5]) return;
+    if (flags[kCfSpillRecs] > room || flags[kCfTableFull]) return;
     const uint64_t e = e_first + (uint64_t)blockIdx.x * kSpillThreads + threadIdx.x;
     if (e >= S) return;
     const uint64_t h = key_hash(K.lo[e], K.mn[e], HAS_HI ? K.hi[e] : 0ull, HAS_HI);
@@ -1282,8 +1306,8 @@ constexpr int kPairTile = 64, kPairWords = 16, kPairThreads = 256, kPairR = kPai
 __global__ __launch_bounds__(kPairThreads) void k_spill_pairs(const unsigned long long* __restrict__ bits, uint32_t n, uint32_t tiles,
                                                              uint32_t row_first, uint32_t row_stride, uint32_t row_limit,
                                                              uint32_t* __restrict__ inter, const uint32_t* __restrict__ flags) {
-    const uint32_t words = (flags[9] + 63u) >> 6;
-    if (words == 0 || flags[6] || flags[5]) return;
+    const uint32_t words = (flags[kCfColsOut] + 63u) >> 6;
+    if (words == 0 || flags[kCfPartOverflow] || flags[kCfTableFull]) return;
     const uint32_t total = tiles * (tiles + 1) / 2, per_xcd = gridDim.x >> 3;          // (the grid is a multiple of 8)
     uint32_t left = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
     if (left >= total) return;
@@ -1347,7 +1371,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_parts_group_small(const uint6
     uint32_t* cursor = reinterpret_cast<uint32_t*>(hl + kSmallHl);          // holder, every list on a 4-byte boundary (read a word at a time)
     const uint32_t p = blockIdx.x, t = threadIdx.x;
     const uint32_t n = part_cnt[p];
-    if (n > (uint32_t)kSmallCap) { if (t == 0) atomicOr(&flags[6], 1u); return; }
+    if (n > (uint32_t)kSmallCap) { if (t == 0) atomicOr(&flags[kCfPartOverflow], 1u); return; }
     for (uint32_t x = t; x < (uint32_t)kSmallSlots; x += kGroupThreads) slot[x] = 0;
     for (uint32_t x = t; x < (uint32_t)(kSmallN * kSmallN / 2); x += kGroupThreads) mat[x] = 0;
     if (t == 0) *cursor = 0;
@@ -1576,7 +1600,6 @@ struct CompareJob {
     // spill (partition form, unfiltered): the records of parts that overflow are grouped in a table in HBM (k_spill_insert)
     SpillPlan spill;                // room = 0: not part of this attempt
 };
-// flags: [0] unsorted input, [1] fingerprint collision, [2] n_rows, [5] table full (see kFlags)
 static uint64_t job_fp_mask(const CompareJob& J) {
     // test hook: fingerprints of the first attempt cut to a few bits, so distinct keys collide and the retry runs
     static const char* dbg_fp = getenv("SPSP_DEBUG_FP_BITS");
@@ -1652,7 +1675,7 @@ static int launch_accumulate_sparse(spsp_ctx* ctx, const ComparePlan& P, uint32_
     hipLaunchKernelGGL(kern, dim3(col_blocks, grid_y, split), dim3(threads), lds, ctx->stream,
                        P.list_ref ? P.list_ref : ctx->c_row.as<uint32_t>(), P.where, ctx->c_matrix.as<uint16_t>(), P.sk_begin, P.sk_end,
                        P.n, P.row_first, P.row_stride, P.row_limit, cols, copies_log2, split, P.d_inter, flags,
-                       reinterpret_cast<uint32_t*>(ctx->h_scalar + 8),
+                       compare_host_flags(ctx),
                        direct ? ctx->cells_req.cells : (unsigned long long*)nullptr,
                        (unsigned long long)ctx->cells_req.cap, ctx->cells_req.count, xcd_rows, add, by_xcd ? P.row_order : (const uint32_t*)nullptr, long_limit, P.multi, P.multi_slots, rows_y);
     SPSP_HIP(hipGetLastError());
@@ -1665,13 +1688,13 @@ static int launch_accumulate_sparse(spsp_ctx* ctx, const ComparePlan& P, uint32_
         }
         hipLaunchKernelGGL((k_accumulate_sparse<false, false, kSparseThreads>), dim3(col_blocks, 1, slices), dim3(kSparseThreads), ((size_t)cols << copies_log2) * 4, ctx->stream,
                            P.list_ref ? P.list_ref : ctx->c_row.as<uint32_t>(), P.where, ctx->c_matrix.as<uint16_t>(), P.sk_begin, P.sk_end,
-                           P.n, i, 1u, i + 1, cols, copies_log2, slices, P.d_inter, flags, reinterpret_cast<uint32_t*>(ctx->h_scalar + 8),
+                           P.n, i, 1u, i + 1, cols, copies_log2, slices, P.d_inter, flags, compare_host_flags(ctx),
                            (unsigned long long*)nullptr, 0ull, (unsigned long long*)nullptr, 0u, add, (const uint32_t*)nullptr, 0u, P.multi, P.multi_slots, 1u);
         SPSP_HIP(hipGetLastError());
     }
     ctx->cells_req.direct = direct;
     // the number of cells travels to pinned memory behind the kernel: whoever waits for the job (compare_end) has it, no round trip of its own
-    if (direct) SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + 12, ctx->cells_req.count, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (direct) SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCells, ctx->cells_req.count, 8, hipMemcpyDeviceToHost, ctx->stream));
     return SPSP_OK;
 }
 
@@ -1741,11 +1764,8 @@ static int launch_scatter(spsp_ctx* ctx, const CompareJob& J) {
     // what it reads; the small form keeps no `where` and its 100 sketches are one block anyway)
     if (!J.small && !J.filtered && P.n_tiles) {
         const size_t lds_t = (size_t)n_parts * 4;
-        if (lds_t > 48 * 1024 && !ctx->attr_scatter_tiles_set) {
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter_tiles<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter_tiles<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
-            ctx->attr_scatter_tiles_set = true;
-        }
+        // (the limit is raised to the most parts there can be, not to this call's)
+        if (lds_t > 48 * 1024 && ((rc = lds_opt_in(ctx, &k_parts_scatter_tiles<true>, kMaxKeyParts * 4)) || (rc = lds_opt_in(ctx, &k_parts_scatter_tiles<false>, kMaxKeyParts * 4)))) return rc;
         auto kern = J.has_hi ? &k_parts_scatter_tiles<true> : &k_parts_scatter_tiles<false>;
         hipLaunchKernelGGL(kern, dim3(P.n_tiles), dim3(kScatThreads), lds_t, ctx->stream, P.K, P.sk_begin, P.n, P.tile_info, P.tile_sk, n_parts,
                            cap, ctx->c_part_cnt.as<uint32_t>(), ctx->c_recs.as<uint64_t>(), where, flags, !ctx->keys_unordered, P.row_first, J.classes, J.cls);
@@ -1756,11 +1776,7 @@ static int launch_scatter(spsp_ctx* ctx, const CompareJob& J) {
     const dim3 grid((uint32_t)((P.S_entries - P.e_own + per_wg - 1) / per_wg));
     const uint32_t* filter = J.filtered ? ctx->c_filter.as<uint32_t>() : nullptr;
     const size_t lds = (size_t)n_parts * 4;
-    if (lds > 48 * 1024 && !ctx->attr_scatter_set) {
-        SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
-        SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_scatter<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeyParts * 4));
-        ctx->attr_scatter_set = true;
-    }
+    if (lds > 48 * 1024 && ((rc = lds_opt_in(ctx, &k_parts_scatter<true, 4>, kMaxKeyParts * 4)) || (rc = lds_opt_in(ctx, &k_parts_scatter<false, 4>, kMaxKeyParts * 4)))) return rc;
     auto kern = J.has_hi ? &k_parts_scatter<true, 4> : &k_parts_scatter<false, 4>;
     hipLaunchKernelGGL(kern, grid, dim3(kScatThreads), lds, ctx->stream, P.K, P.sk_begin, P.n, P.sub_sk, P.S_entries, n_parts, cap,
                        ctx->c_part_cnt.as<uint32_t>(), ctx->c_recs.as<uint64_t>(), where, flags, !ctx->keys_unordered, filter,
@@ -1777,11 +1793,7 @@ static int launch_group(spsp_ctx* ctx, const CompareJob& J) {
     if (J.want_multi) { const int rm = ctx->c_multi.reserve((size_t)J.n_parts * kPartCap / 8 + 64); if (rm) return rm; }
     unsigned long long* multi = J.want_multi ? ctx->c_multi.as<unsigned long long>() : (unsigned long long*)nullptr;
     auto kern = J.has_hi ? &k_parts_group<true> : &k_parts_group<false>;
-    bool& attr_set = J.has_hi ? ctx->attr_group_hi_set : ctx->attr_group_set;
-    if (!attr_set) {
-        SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    if (const int rc = lds_opt_in(ctx, kern, lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(J.n_parts), dim3(kGroupThreads), lds, ctx->stream, ctx->c_recs.as<uint64_t>(), ctx->c_part_cnt.as<uint32_t>(),
                        ctx->c_matrix.as<uint16_t>(), ctx->c_lref.as<uint32_t>(), ctx->c_flags.as<uint32_t>(), t_bits, max_cols, bits, J.P.n, multi);
     SPSP_HIP(hipGetLastError());
@@ -1790,10 +1802,7 @@ static int launch_group(spsp_ctx* ctx, const CompareJob& J) {
 // k <= 32 only
 static int launch_group_small(spsp_ctx* ctx, const CompareJob& J) {
     const size_t lds = (size_t)kSmallCap * (8 + 4) + (size_t)kSmallHl + (size_t)kSmallSlots * 4 + (size_t)kSmallN * kSmallN * 2 + 16;
-    if (!ctx->attr_small_set) {
-        SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_parts_group_small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ctx->attr_small_set = true;
-    }
+    if (const int rc = lds_opt_in(ctx, &k_parts_group_small, lds)) return rc;
     hipLaunchKernelGGL(k_parts_group_small, dim3(J.n_parts), dim3(kGroupThreads), lds, ctx->stream, ctx->c_recs.as<uint64_t>(),
                        ctx->c_part_cnt.as<uint32_t>(), J.P.n, J.P.d_inter, ctx->c_flags.as<uint32_t>());
     SPSP_HIP(hipGetLastError());
@@ -1884,11 +1893,8 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
         auto signature = J.has_hi ? &k_row_signature<true> : &k_row_signature<false>;
         hipLaunchKernelGGL(signature, dim3(sp), dim3(1024), 0, side, ctx->c_recs.as<uint64_t>(), ctx->c_part_cnt.as<uint32_t>(), (uint32_t)kPartCap, sig);
         static_assert(kOrderMost == kSparseCols, "the order is made for comparisons of one column block");
-        if (!ctx->attr_order_set) {
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_row_order), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((kOrderBuckets + kOrderMost) * 4)));
-            ctx->attr_order_set = true;
-        }
-        hipLaunchKernelGGL(k_row_order, dim3(1), dim3(1024), (size_t)(kOrderBuckets + J.P.n) * 4, side, (const unsigned long long*)sig, J.P.n, ctx->c_order.as<uint32_t>(), flags + 10);
+        if ((rc = lds_opt_in(ctx, &k_row_order, (kOrderBuckets + kOrderMost) * 4))) return rc;
+        hipLaunchKernelGGL(k_row_order, dim3(1), dim3(1024), (size_t)(kOrderBuckets + J.P.n) * 4, side, (const unsigned long long*)sig, J.P.n, ctx->c_order.as<uint32_t>(), flags + kCfOrderNew);
         SPSP_HIP(hipGetLastError());
     }
     if ((rc = ctx->ev_end(kEvScatter))) return rc;
@@ -1910,7 +1916,7 @@ static int job_parts(spsp_ctx* ctx, CompareJob& J) {
     PP.list_ref = ctx->c_lref.as<uint32_t>(); PP.where = ctx->c_where.as<uint32_t>();
     if (J.want_multi) { PP.multi = ctx->c_multi.as<uint32_t>(); PP.multi_slots = J.n_parts * (uint32_t)kPartCap | ((dbg_multi && dbg_multi[0] == '1') ? 0x80000000u : 0u); }
     if (ordered) PP.row_order = ctx->c_order.as<uint32_t>();
-    if (ordered || J.want_multi) SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + 14, flags + 10, 16, hipMemcpyDeviceToHost, ctx->stream));   // the verdicts, for compare_job_end
+    if (ordered || J.want_multi) SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsOrderVerdict, flags + kCfOrderNew, 16, hipMemcpyDeviceToHost, ctx->stream));   // the verdicts, for compare_job_end
     // (an attempt whose parts overflow leaves this kernel at its first line, before any cell is emitted: the retry emits them once)
     // (with a spill the keys that have columns add into the dense matrix behind the row sums: no cells straight from them)
     //  -- nor with key classes: a pair's count comes in several parts)
@@ -1935,12 +1941,12 @@ static int job_sparse(spsp_ctx* ctx, CompareJob& J) {
     const uint64_t want = (t_vec + c_vec + 255) / 256, cap_blocks = (uint64_t)ctx->n_cu * 8;
     hipLaunchKernelGGL(k_prepare, dim3((uint32_t)std::max<uint64_t>(1, std::min(want, cap_blocks))), dim3(256), 0, ctx->stream,
                        ctx->c_table.as<uint4>(), t_vec, ctx->c_owner.as<uint4>(), c_vec, flags,
-                       (J.attempt == 0 && J.clear_all_flags) ? 16u : 3u,
+                       (J.attempt == 0 && J.clear_all_flags) ? kCfClearFirst : kCfClearRetry,
                        (const uint64_t*)ctx->h_skoff, ctx->c_skoff.as<uint64_t>(), J.n_skoff);
     SPSP_HIP(hipGetLastError());
     if ((rc = launch_insert_sparse(ctx, J))) return rc;
     hipLaunchKernelGGL(k_assign_ranges, dim3(J.sblocks), dim3(kRowThreads), 0, ctx->stream, ctx->c_owner.as<uint32_t>(), J.cap,
-                       ctx->c_rowid.as<uint32_t>(), ctx->c_matrix.as<uint16_t>(), flags + 2);
+                       ctx->c_rowid.as<uint32_t>(), ctx->c_matrix.as<uint16_t>(), flags + kCfRows);
     SPSP_HIP(hipGetLastError());
     if ((rc = launch_fill_sparse(ctx, J))) return rc;
     if ((rc = ctx->ev_begin(kEvAccumulate))) return rc;
@@ -1961,13 +1967,13 @@ static int job_front(spsp_ctx* ctx, CompareJob& J) {
     const uint64_t want = (t_vec + m_vec + 255) / 256, cap_blocks = (uint64_t)ctx->n_cu * 8;
     hipLaunchKernelGGL(k_prepare, dim3((uint32_t)std::max<uint64_t>(1, std::min(want, cap_blocks))), dim3(256), 0, ctx->stream,
                        ctx->c_table.as<uint4>(), t_vec, ctx->c_matrix.as<uint4>(), m_vec, flags,
-                       (J.attempt == 0 && J.clear_all_flags) ? 16u : 3u,    // a retry clears the words the build writes again
+                       (J.attempt == 0 && J.clear_all_flags) ? kCfClearFirst : kCfClearRetry,    // a retry clears the words the build writes again
                        (const uint64_t*)ctx->h_skoff, ctx->c_skoff.as<uint64_t>(), J.n_skoff);
     SPSP_HIP(hipGetLastError());
     if ((rc = launch_insert(ctx, J))) return rc;
     if (!J.direct_rows) {
         hipLaunchKernelGGL(k_assign_rows, dim3(J.sblocks), dim3(kRowThreads), 0, ctx->stream, ctx->c_table.as<uint64_t>(), J.cap,
-                           ctx->c_rowid.as<uint32_t>(), flags + 2);
+                           ctx->c_rowid.as<uint32_t>(), flags + kCfRows);
         SPSP_HIP(hipGetLastError());
     }
     return SPSP_OK;
@@ -1985,23 +1991,23 @@ static int job_back(spsp_ctx* ctx, CompareJob& J, uint64_t rows) {
     hipLaunchKernelGGL(k_accumulate, dim3((J.W + 63) / 64, P.n_own), dim3(kAccThreads), 0, ctx->stream,
                        ctx->c_row.as<uint32_t>(), ctx->c_matrix.as<uint64_t>(), J.W, J.lanes_per_key, P.sk_begin, P.sk_end,
                        P.n, P.row_first, P.row_stride, P.row_limit, P.d_inter, ctx->c_flags.as<uint32_t>(),
-                       reinterpret_cast<uint32_t*>(ctx->h_scalar + 8), J.pass > 0);
+                       compare_host_flags(ctx), J.pass > 0);
     SPSP_HIP(hipGetLastError());
     if ((rc = ctx->ev_end(kEvAccumulate))) return rc;
     return job_mark_done(ctx);
 }
 // the flags travel to pinned host memory as the last item of whatever has been queued ...
 static int job_queue_flags(spsp_ctx* ctx) {
-    uint32_t* pinned = reinterpret_cast<uint32_t*>(ctx->h_scalar + 8);
+    uint32_t* pinned = compare_host_flags(ctx);
     SPSP_HIP(hipMemcpyAsync(pinned, ctx->c_flags.p, kFlags * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     return job_mark_done(ctx);
 }
 // ... and are read after the one synchronisation
 static int job_wait_flags(spsp_ctx* ctx, uint32_t* h_flags) {
     SPSP_HIP(hipEventSynchronize(ctx->compare_done));
-    memcpy(h_flags, ctx->h_scalar + 8, kFlags * sizeof(uint32_t));
-    if (h_flags[5]) { set_error("dictionary table overflow (internal sizing error)"); return SPSP_ERR_HIP; }
-    if (h_flags[0] && !ctx->keys_unordered) { set_error("sketch keys must be strictly increasing by (minimizer, kmer_hi, kmer_lo)"); return SPSP_ERR_ARG; }
+    memcpy(h_flags, compare_host_flags(ctx), kFlags * sizeof(uint32_t));
+    if (h_flags[kCfTableFull]) { set_error("dictionary table overflow (internal sizing error)"); return SPSP_ERR_HIP; }
+    if (h_flags[kCfUnsorted] && !ctx->keys_unordered) { set_error("sketch keys must be strictly increasing by (minimizer, kmer_hi, kmer_lo)"); return SPSP_ERR_ARG; }
     return SPSP_OK;
 }
 
@@ -2171,8 +2177,8 @@ static int compare_job_begin(spsp_ctx* ctx, CompareJob* job) {
 // takes over, < 0 on error.
 static int job_parts_retry(spsp_ctx* ctx, CompareJob& J, const uint32_t* h_flags) {
     J.bracket_closed = true;
-    if (J.filtered && h_flags[7] > J.parts_entries) {   // more keys passed the filter than the parts were sized for: now the count is known
-        J.parts_entries = (uint64_t)h_flags[7] + (uint64_t)h_flags[7] / 64 + 2900;
+    if (J.filtered && h_flags[kCfDealt] > J.parts_entries) {   // more keys passed the filter than the parts were sized for: now the count is known
+        J.parts_entries = (uint64_t)h_flags[kCfDealt] + (uint64_t)h_flags[kCfDealt] / 64 + 2900;
         if (parts_for(J.parts_entries, J.parts_attempt) <= (uint32_t)kMaxKeyParts) {
             J.n_parts = parts_for(J.parts_entries, J.parts_attempt);
             return job_parts(ctx, J);
@@ -2184,11 +2190,11 @@ static int job_parts_retry(spsp_ctx* ctx, CompareJob& J, const uint32_t* h_flags
         const int rc = ctx->c_row.reserve((size_t)J.P.S_entries * 4);
         return rc ? rc : job_parts(ctx, J);
     }
-    if (h_flags[2] > J.spill.room && spill_plan(J, h_flags[2], &J.spill)) return job_parts(ctx, J);   // (the count is exact: the same parts overflow again)
+    if (h_flags[kCfSpillRecs] > J.spill.room && spill_plan(J, h_flags[kCfSpillRecs], &J.spill)) return job_parts(ctx, J);   // (the count is exact: the same parts overflow again)
     J.spill = SpillPlan{};
     // no room for the spilled keys' lists behind this many parts (list references address 2^29 u16): twice the classes,
     // so half the parts -- everything starts over, a key's class changes
-    if (!J.filtered && spill_enabled() && J.n_parts > 4096 && J.classes <= 128 && h_flags[2] > 0) {
+    if (!J.filtered && spill_enabled() && J.n_parts > 4096 && J.classes <= 128 && h_flags[kCfSpillRecs] > 0) {
         J.classes *= 2; J.cls = 0;
         J.parts_entries = J.S_behind / J.classes + J.S_behind / J.classes / 32 + 65536;
         J.n_parts = parts_for(J.parts_entries, 0);
@@ -2210,15 +2216,15 @@ int compare_job_end(spsp_ctx* ctx) {
     while (J->parts) {
         uint32_t h_flags[kFlags];
         if ((rc = job_wait_flags(ctx, h_flags))) return rc;
-        if (J->filtered && h_flags[7]) ctx->filter_ratio = (double)h_flags[7] / (double)J->P.S_own;
-        if (!h_flags[6]) {
-            if (!J->filtered && !J->small) ctx->spill_expect = h_flags[2];
+        if (J->filtered && h_flags[kCfDealt]) ctx->filter_ratio = (double)h_flags[kCfDealt] / (double)J->P.S_own;
+        if (!h_flags[kCfPartOverflow]) {
+            if (!J->filtered && !J->small) ctx->spill_expect = h_flags[kCfSpillRecs];
             if (J->ordered) {
-                const uint32_t near_new = (uint32_t)ctx->h_scalar[14], near_in = (uint32_t)(ctx->h_scalar[14] >> 32);
+                const uint32_t near_new = (uint32_t)ctx->h_scalar[kHsOrderVerdict], near_in = (uint32_t)(ctx->h_scalar[kHsOrderVerdict] >> 32);
                 ctx->order_quiet = 2 * near_in >= near_new ? 63 : 0;
             }
             if (J->want_multi) {
-                const uint64_t listed = (uint32_t)ctx->h_scalar[15], sampled = (uint32_t)(ctx->h_scalar[15] >> 32);
+                const uint64_t listed = (uint32_t)ctx->h_scalar[kHsMultiVerdict], sampled = (uint32_t)(ctx->h_scalar[kHsMultiVerdict] >> 32);
                 ctx->multi_quiet = (sampled && 5 * listed >= 2 * sampled) ? 63 : 0;
             }
             static const bool trace = getenv("SPSP_DEBUG_SPILL_TRACE") != nullptr;     // test hook: which way the comparison went
@@ -2226,7 +2232,7 @@ int compare_job_end(spsp_ctx* ctx) {
                                J->small ? "small" : (J->filtered ? "filtered" : "partition"), J->n_parts, J->classes, J->ordered ? "made" : "as given",
                                J->want_multi ? "made" : "left out", J->spill.room ? "yes" : "no");
             if (trace && J->spill.room) fprintf(stderr, "spsp spill: %u records of overflowed parts grouped in HBM (room %llu, %u parts, columns from %u holders)\n",
-                                                h_flags[2], (unsigned long long)J->spill.room, J->n_parts, J->spill.t_bits);
+                                                h_flags[kCfSpillRecs], (unsigned long long)J->spill.room, J->n_parts, J->spill.t_bits);
             if (J->cls + 1 < J->classes) {              // the next class of keys through the same parts; its row sums add
                 ++J->cls;
                 J->bracket_closed = true;
@@ -2247,14 +2253,14 @@ int compare_job_end(spsp_ctx* ctx) {
         bool collided = false;
         if (J->speculative) {
             if ((rc = job_wait_flags(ctx, h_flags))) return rc;              // collisions surface in the fill pass
-            collided = h_flags[1] != 0;
+            collided = h_flags[kCfCollision] != 0;
         } else {
             for (;;) {   // key class by key class; the first class (front part) was queued by the begin call / the retry below
                 if ((rc = job_wait_flags(ctx, h_flags))) return rc;          // the row count sizes the colour matrix
-                if ((rc = job_back(ctx, *J, h_flags[2]))) return rc;
+                if ((rc = job_back(ctx, *J, h_flags[kCfRows]))) return rc;
                 if (J->attempt == 0 && J->pass + 1 == J->passes && !J->bracket_closed && (rc = ctx->ev_end(kEvCompare))) return rc;   // bracket of the begin call
                 if ((rc = job_wait_flags(ctx, h_flags))) return rc;          // collisions of this class
-                if (h_flags[1]) { collided = true; break; }
+                if (h_flags[kCfCollision]) { collided = true; break; }
                 if (++J->pass == J->passes) break;
                 if ((rc = job_front(ctx, *J))) return rc;
                 if ((rc = job_queue_flags(ctx))) return rc;

@@ -641,11 +641,9 @@ int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, con
                            ctx->dc_desc.as<DecDesc>(), (uint32_t)n_desc_all, k, m, ctx->dc_mn.as<uint32_t>(), ctx->dc_lo.as<uint64_t>(),
                            has_hi ? ctx->dc_hi.as<uint64_t>() : (uint64_t*)nullptr);
     }
-    if (!ctx->attr_sort_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_sort<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)kSortCapHi * 20));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_sort<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)kSortCapLo * 12));
-        ctx->attr_sort_set = true;
-    }
+    // (a refusal is not an error of its own here: the launch below then fails and reports)
+    (void)lds_opt_in(ctx, &k_decode_sort<true>, (size_t)kSortCapHi * 20);
+    (void)lds_opt_in(ctx, &k_decode_sort<false>, (size_t)kSortCapLo * 12);
     static const char* dbg_sort = getenv("SPSP_DEBUG_DECODE_SORT");     // "network": every sketch through the bitonic network (A/B, tests)
     const uint32_t force_network = dbg_sort && dbg_sort[0] == 'n' ? 1u : 0u;
     // the first launch's arrays hold the largest sketch it sorts, as it is (see the kernel); the second has them in full
@@ -668,7 +666,7 @@ int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, con
     if (any_big && (rc = big_dedupe_launch(ctx, has_hi, ctx->dc_mn.as<uint32_t>(), ctx->dc_lo.as<uint64_t>(), has_hi ? ctx->dc_hi.as<uint64_t>() : nullptr,
                                            d_first32, d_raw_cnt, d_big, n, R, nullptr, 0u, ctx->b_mn.as<uint32_t>(), ctx->b_lo.as<uint64_t>(),
                                            has_hi ? ctx->b_hi.as<uint64_t>() : nullptr, d_distinct))) return fail(rc);
-    if ((rc = launch_scan_u32(ctx, d_distinct, d_out_off, n, ctx->h_scalar + 7))) return fail(rc);
+    if ((rc = launch_scan_u32(ctx, d_distinct, d_out_off, n, ctx->h_scalar + kHsScanTotalB))) return fail(rc);
     const uint32_t gx = (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(8, R / n / 2048));   // (more workgroups per sketch when sketches are huge)
     hipLaunchKernelGGL(k_decode_compact, dim3(gx, n), dim3(256), 0, ctx->stream, ctx->dc_mn.as<uint32_t>(), ctx->dc_lo.as<uint64_t>(),
                        has_hi ? ctx->dc_hi.as<uint64_t>() : (const uint64_t*)nullptr, ctx->b_mn.as<uint32_t>(), ctx->b_lo.as<uint64_t>(),

@@ -134,7 +134,7 @@ int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const ui
     SPSP_HIP(hipMemcpyAsync(d_off_in, rel.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_ds_flag, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, (uint32_t)R, threshold, d_mask, d_tile_cnt);
     SPSP_HIP(hipGetLastError());
-    if ((rc = launch_scan_u32(ctx, d_tile_cnt, d_tile_off, n_tiles, ctx->h_scalar + 13))) return rc;
+    if ((rc = launch_scan_u32(ctx, d_tile_cnt, d_tile_off, n_tiles, ctx->h_scalar + kHsDownsampleTotal))) return rc;
     if (has_hi) hipLaunchKernelGGL(k_ds_move<true>, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, d_lo, d_hi, (const unsigned long long*)d_mask,
                                    (const uint32_t*)d_tile_off, *out_mn, *out_lo, *out_hi);
     else hipLaunchKernelGGL(k_ds_move<false>, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, d_lo, (const uint64_t*)nullptr,

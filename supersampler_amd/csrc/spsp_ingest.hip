@@ -266,7 +266,7 @@ __global__ __launch_bounds__(1024) void k_clean_scan(const TileSummary* __restri
         if (t == 0) { c_t = compose(c_t, tall); c_k += kall; c_h += hall; }
         __syncthreads();
     }
-    if (t == 0) { totals[0] = c_k; totals[1] = c_h; }
+    if (t == 0) { totals[0] = c_k; totals[kHsIngestRecs - kHsIngestKept] = c_h; }
 }
 
 // One lane's survivors -> the tile's LDS staging buffer, in order from LDS offset sh + at; a record starts behind every
@@ -668,7 +668,7 @@ __global__ __launch_bounds__(1024) void k_mixed_scan(const MixedTileSummary* __r
         if (t == 0) { c_t = mcompose(c_t, tall); c_k += kall; c_h += hall; c_d = dall; }
         __syncthreads();
     }
-    if (t == 0) { totals[0] = c_k; totals[1] = c_h; }
+    if (t == 0) { totals[0] = c_k; totals[kHsIngestRecs - kHsIngestKept] = c_h; }
 }
 
 template <bool PACK>
@@ -820,7 +820,7 @@ static int clean_mixed_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_tex
     }
     const uint32_t fq_flags = fq->blank_tail ? kTiBlankTail : 0u;
     SPSP_HIP(hipMemsetAsync(ctx->i_fqbad.p, 0xFF, (size_t)n_files * 8, ctx->stream));
-    uint64_t* totals = ctx->h_scalar + 4;
+    uint64_t* totals = ctx->h_scalar + kHsIngestKept;
     if (n_tiles) {
         hipLaunchKernelGGL(k_mixed_tiles, dim3((uint32_t)n_tiles), dim3(kCleanThreads), 0, ctx->stream, d_text, n_text, n_tiles, d_info,
                            fq->content_end, fq_flags, ctx->i_tiles.as<MixedTileSummary>());
@@ -831,7 +831,7 @@ static int clean_mixed_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_tex
                        ctx->i_dbase.as<long long>(), totals);
     SPSP_HIP(hipGetLastError());
     SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    const uint64_t kept = totals[0], recs = totals[1];
+    const uint64_t kept = ctx->h_scalar[kHsIngestKept], recs = ctx->h_scalar[kHsIngestRecs];
     if (recs > 0xfffffff0ull) { set_error("too many records for one call"); return SPSP_ERR_OVERFLOW; }
     if ((rc = ctx->rec_off.reserve((size_t)(recs + 1) * 8))) return rc;
     if (n_tiles) {
@@ -885,7 +885,7 @@ int clean_device_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uin
         *d_rec_off = ctx->rec_off.as<uint64_t>(); *n_rec = (uint32_t)recs;
         return SPSP_OK;
     }
-    uint64_t* totals = ctx->h_scalar + 4;
+    uint64_t* totals = ctx->h_scalar + kHsIngestKept;
     if (n_tiles) {
         hipLaunchKernelGGL(k_clean_tiles, dim3((uint32_t)n_tiles), dim3(kCleanThreads), 0, ctx->stream, d_text, n_text,
                            ctx->i_tiles.as<TileSummary>());
@@ -895,7 +895,7 @@ int clean_device_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uin
                        ctx->i_entry.as<uint32_t>(), ctx->i_outoff.as<uint64_t>(), ctx->i_recbase.as<uint32_t>(), totals);
     SPSP_HIP(hipGetLastError());
     SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    const uint64_t kept = totals[0], recs = totals[1];
+    const uint64_t kept = ctx->h_scalar[kHsIngestKept], recs = ctx->h_scalar[kHsIngestRecs];
     if (recs > 0xfffffff0ull) { set_error("too many FASTA records for one call"); return SPSP_ERR_OVERFLOW; }
     if ((rc = ctx->rec_off.reserve((size_t)(recs + 1) * 8))) return rc;
     if (n_tiles) {
@@ -932,10 +932,10 @@ int gather_superkmers_impl(spsp_ctx* ctx, const uint8_t* d_bases, const uint64_t
     if ((rc = ctx->i_lens.reserve((size_t)n_sk * 4)) || (rc = ctx->i_dst.reserve((size_t)(n_sk + 1) * 4))) { free(off); return rc; }
     hipLaunchKernelGGL(k_sk_lens, dim3((uint32_t)((n_sk + 255) / 256)), dim3(256), 0, ctx->stream, d_sk, (uint32_t)n_sk,
                        ctx->i_lens.as<uint32_t>());
-    if ((rc = launch_scan_u32(ctx, ctx->i_lens.as<uint32_t>(), ctx->i_dst.as<uint32_t>(), n_sk, ctx->h_scalar + 6))) { free(off); return rc; }
+    if ((rc = launch_scan_u32(ctx, ctx->i_lens.as<uint32_t>(), ctx->i_dst.as<uint32_t>(), n_sk, ctx->h_scalar + kHsScanTotalA))) { free(off); return rc; }
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { free(off); return hip_fail(e, "gather sizes", __FILE__, __LINE__); }
-    const uint64_t total = ctx->h_scalar[6];
+    const uint64_t total = ctx->h_scalar[kHsScanTotalA];
     if ((rc = ctx->i_compact.reserve((size_t)total + 64))) { free(off); return rc; }
     if (packed) hipLaunchKernelGGL(k_gather_superkmers_packed, dim3((uint32_t)((n_sk + 3) / 4)), dim3(256), 0, ctx->stream,
                                    reinterpret_cast<const uint32_t*>(d_bases), d_rec_off, d_sk, ctx->i_dst.as<uint32_t>(), (uint32_t)n_sk,

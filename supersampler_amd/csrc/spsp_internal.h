@@ -81,6 +81,46 @@ struct KeysJob {
 };
 }  // namespace spsp
 
+namespace spsp {
+// spsp_ctx::h_scalar: the pinned uint64_t slots through which the kernel chains report to the host.  A slot is written by a
+// kernel or an async copy queued on the context's stream and read by the host once it has waited for that work; a 32-bit value
+// sits in the slot's low half.  A chain that needs one more word takes a free slot HERE.
+enum HostSlot {
+    kHsScanHits = 0,        // k_compact / k_expand / k_sum_counts / k_scan_top write the hit total (u64); scan_end_impl, scan_hits_impl read
+    kHsSegEmitted = 0,      // ... the scan by segments instead: launch_scan_u32's total of super-k-mers (u64); scan_end_impl reads
+    kHsScanEmitted = 1,     // k_resolve<true> writes the super-k-mers it emitted (u64); scan_end_impl reads
+    kHsSegLeftTile = 1,     // ... the scan by segments instead: seg_scan_count copies the chains that left their tile (u32); scan_end_impl reads
+    kHsScanFullest = 2,     // k_compact writes the fullest hit list (u64; k_compact reaches it from kHsScanHits), scan_enqueue zeroes it; scan_end_impl reads
+    kHsStatChains = 3,      // count_superkmers_impl copies the chains that left their tile (u32) and reads it
+    kHsIngestKept = 4,      // k_clean_scan / k_mixed_scan write the bases kept (u64); clean_device_impl / clean_mixed_impl read
+    kHsIngestRecs = 5,      // ... and the records (u64), reached from kHsIngestKept: kIngestTotals slots in all
+    kHsScanTotalA = 6,      // launch_scan_u32's total (u64) of gather_superkmers_impl (bases) and sketch_build_device_impl (places, then output bytes)
+    kHsScanTotalB = 7,      // ... of sketch_build_device_impl (buckets, beside A's places), abundance_flags_impl (occurrences), the decoder and
+                            // the key extraction (written, not read: they take the total from the scan's out[n])
+    kHsCompareFlags = 8,    // 8..11: words [0, kFlags) of the comparison's flag block as uint32_t (spsp_compare.hip: compare_host_flags)
+    kHsCells = 12,          // the cell count (u64) of a comparison returned as cells: copied behind the row sums (launch_accumulate_sparse) and
+                            // read by compare_cells_run after compare_end_impl, or copied and read inside matrix_cells_impl
+    kHsCellsBad = 12,       // spsp_matrix_add_cells_device copies k_matrix_add_cells' bad-cell word (u32) and reads it, in one call.  Shares the
+                            // slot: compare_cells_run holds the context from its begin to its read, and the other two wait before they return.
+                            // Nothing checks it: a caller must not add cells on a context between a cells comparison's begin and end
+    kHsSlotsBad = 13,       // compare_slots_begin_impl copies k_slot_unpack's bad-record word (u32); slots_bad_record reads behind compare_end_impl
+    kHsDownsampleTotal = 13,   // launch_scan_u32's total (u64) in keys_downsample_impl (written, never read).  Shares the slot: the drivers
+                            // downsample (and wait) in front of the comparison they feed.  Nothing checks it: a downsampling pass queued on
+                            // a context between a slot comparison's begin and end would overwrite that comparison's record check
+    kHsOrderVerdict = 14,   // k_row_order's two u32 (sketches kept together in the new order | in the input's << 32); compare_end_impl reads
+    kHsMultiVerdict = 15,   // k_parts_group's two u32 (records with a list | records sampled << 32), copied with the order verdict
+    kHostSlots = 16
+};
+constexpr int kIngestTotals = 2;
+static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
+static_assert(kHsIngestRecs == kHsIngestKept + 1 && kHsMultiVerdict == kHsOrderVerdict + 1 && kHsMultiVerdict < kHostSlots, "slots reached from their neighbour");
+// ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
+// of a comparison returned as cells (spsp_multi.hip)
+constexpr uint32_t kCfCellCount = 14;
+// ... and behind those, two words of the key extraction (spsp_keys.hip names them): no clearing kernel of a comparison reaches them
+constexpr uint32_t kCfKeysFlags = 16;
+}  // namespace spsp
+
 struct spsp_ctx {
     bool timing = false;          // any kind enabled
     uint32_t timing_mask = 0;     // bit k: regions of kind k (kEvDense ...) are bracketed by events
@@ -102,7 +142,7 @@ struct spsp_ctx {
     hipStream_t tail_stream = nullptr;   // sparse stages of the scan (spsp_scan_tail_stream); nullptr = the main stream
     bool own_tail_stream = false;
     hipStream_t sparse_stream() const { return tail_stream ? tail_stream : stream; }
-    uint64_t* h_scalar = nullptr;  // pinned, 16 slots: [0] hits, [1] super-k-mers (scan); [4..6] ingest totals; [8..10] compare flags
+    uint64_t* h_scalar = nullptr;  // pinned, spsp::kHostSlots slots: what each holds is spsp::HostSlot
     hipEvent_t dense_done = nullptr;   // recorded behind every dense pass (unless a timing event already is)
     hipEvent_t dense_marker = nullptr; // what spsp_wait_dense waits on
     hipEvent_t tail_event = nullptr;   // spsp_wait_stream: marks the current end of this context's stream
@@ -111,11 +151,11 @@ struct spsp_ctx {
     uint64_t learnt_on = 0;            // offsets' fingerprint of the collection order_quiet / multi_quiet were learnt on
     uint32_t multi_quiet = 0;          // comparisons that leave out the has-a-list bits (the last one had lists for most records)
     uint32_t order_quiet = 0;          // comparisons that skip the making of a row order (the last one came in a good order of its own)
-    bool attr_pair_set = false, attr_single_set = false, attr_bloom_set = false, attr_small_set = false, attr_group_set = false, attr_group_hi_set = false, attr_scatter_set = false, attr_scatter_tiles_set = false, attr_sort_set = false, attr_order_set = false;   // dynamic-LDS attributes set on this context's device
+    std::vector<const void*> lds_kernels;   // kernels whose dynamic-LDS limit this context has raised (lds_opt_in)
     spsp::ScanJob scan_job;
     spsp::CompareJob* compare_job = nullptr;
     // spsp_sketch_keys_device_begin / _end (spsp_keys.hip)
-    bool keys_pending = false, keys_has_hi = false, attr_keys_set = false, keys_flags_clear = false, attr_dedupe_set = false;
+    bool keys_pending = false, keys_has_hi = false, keys_flags_clear = false;
     bool keys_unordered = false;       // spsp_compare_keys_unordered: the comparisons of this context do not insist on sorted sketches
     uint32_t keys_genomes = 0;
     bool keys_sorted = false;          // the pending extraction promised sorted sketches (its big genomes are sorted in _end)
@@ -192,6 +232,9 @@ struct spsp_ctx {
 };
 
 namespace spsp {
+// more dynamic LDS than the default limit allows: hipFuncSetAttribute(MaxDynamicSharedMemorySize), once per kernel and context (spsp_abi.hip)
+int lds_opt_in(spsp_ctx* ctx, const void* kernel, size_t bytes);
+template <class... A> int lds_opt_in(spsp_ctx* ctx, void (*kernel)(A...), size_t bytes) { return lds_opt_in(ctx, reinterpret_cast<const void*>(kernel), bytes); }
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // scan pipeline (spsp_scan.hip)
 int scan_device_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_bases, uint64_t n_bases,

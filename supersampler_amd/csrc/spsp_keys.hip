@@ -38,6 +38,9 @@ namespace spsp {
 
 typedef unsigned __int128 u128d;
 constexpr int kKeySortThreads = 1024;
+// the extraction's flag words: ctx->c_flags + kCfKeysFlags.  Raised by the LDS kernels (k_keys_sort, k_keys_fused) for a genome beyond
+// their capacity, read by the table kernels of spsp_bigkeys.hip (the gate), reported and cleared by k_keys_compact
+enum { kKfBigGate = 0, kKfBigCount = 1, kKeysFlagWords = 2 };   // some genome goes through the table in HBM; how many do
 constexpr uint32_t kKeyCapLo = 8192, kKeyCapHi = 4096;
 
 __global__ void k_keys_sizes(const spsp_superkmer* __restrict__ sk, uint32_t n_sk, uint32_t k, uint32_t* __restrict__ cnt) {
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(kKeySortThreads) void k_keys_sort(uint32_t* __restr
     if (t == 0) { raw_cnt[g] = n; big[g] = n > CAP ? 1u : 0u; }
     if (n == 0) { if (t == 0) distinct[g] = 0; return; }
     // more than the LDS holds: the global-memory stages queued behind this kernel take the genome (spsp_bigkeys.hip)
-    if (n > CAP) { if (t == 0) { distinct[g] = 0; atomicOr(&flags[0], 1u); atomicAdd(&flags[1], 1u); } return; }
+    if (n > CAP) { if (t == 0) { distinct[g] = 0; atomicOr(&flags[kKfBigGate], 1u); atomicAdd(&flags[kKfBigCount], 1u); } return; }
     uint32_t n2 = 1;
     while (n2 < n) n2 <<= 1;
     for (uint32_t i = t; i < n2; i += kKeySortThreads) {
@@ -313,9 +316,9 @@ __global__ __launch_bounds__(kKeySortThreads) void k_keys_fused(const uint8_t* _
     // more k-mer places (or super-k-mers) than this workgroup's LDS holds: the table in HBM (spsp_bigkeys.hip) takes the
     // genome.  Its raw records are written here, into the genome's slice of the context's staging arrays, so that those
     // stages read nothing of the caller's -- they may be queued right behind this kernel or, the first time a context
-    // meets such a genome, from _end.  flags[0] is their gate, flags[1] counts such genomes for the report.
+    // meets such a genome, from _end.  kKfBigGate is their gate, kKfBigCount counts such genomes for the report.
     if (too_big) {
-        if (t == 0) { distinct[seg] = 0; atomicOr(&flags[0], 1u); atomicAdd(&flags[1], 1u); }
+        if (t == 0) { distinct[seg] = 0; atomicOr(&flags[kKfBigGate], 1u); atomicAdd(&flags[kKfBigCount], 1u); }
         for (uint32_t q = q0 + t; q < q1; q += kKeySortThreads) roll_places(bases, packed, rec_off, sk[q], k, w, q * w, r_mn, r_lo, HAS_HI ? r_hi : nullptr);
         return;
     }
@@ -503,8 +506,8 @@ __global__ __launch_bounds__(256) void k_keys_compact(const uint32_t* __restrict
         if (g == n_genomes - 1) {
             host_out[n_genomes] = o0 + n;
             // (zeroed by the host at _begin; a second run queued from _end finds the word reported and cleared: it stays)
-            if (flags[1]) host_out[n_genomes + 1] = flags[1];
-            flags[0] = 0; flags[1] = 0;                         // for the next extraction on this context (every reader of this one has finished)
+            if (flags[kKfBigCount]) host_out[n_genomes + 1] = flags[kKfBigCount];
+            flags[kKfBigGate] = 0; flags[kKfBigCount] = 0;                         // for the next extraction on this context (every reader of this one has finished)
         }
     }
 }
@@ -520,7 +523,7 @@ static int keys_finish_queue(spsp_ctx* ctx, bool with_big, const uint32_t* d_gat
     uint32_t* d_out_off = d_distinct + (ng + 2);
     uint32_t* d_raw_cnt = d_out_off + (ng + 2);
     uint32_t* d_big = d_raw_cnt + (ng + 2);
-    uint32_t* d_flags = ctx->c_flags.as<uint32_t>() + 16;
+    uint32_t* d_flags = ctx->c_flags.as<uint32_t>() + kCfKeysFlags;
     uint32_t* h_out = ctx->h_keys + (ng + 1);
     uint32_t* a_mn = ctx->a_mn.as<uint32_t>();
     uint64_t *a_lo = ctx->a_lo.as<uint64_t>(), *a_hi = J.has_hi ? ctx->a_hi.as<uint64_t>() : (uint64_t*)nullptr;
@@ -529,7 +532,7 @@ static int keys_finish_queue(spsp_ctx* ctx, bool with_big, const uint32_t* d_gat
     int rc;
     if (with_big && J.bound &&
         (rc = big_dedupe_launch(ctx, J.has_hi, a_mn, a_lo, a_hi, d_raw_off, d_raw_cnt, d_big, ng, J.bound, d_gate, J.abundance, b_mn, b_lo, b_hi, d_distinct))) return rc;
-    if (J.flat && (rc = launch_scan_u32(ctx, d_distinct, d_out_off, ng, ctx->h_scalar + 7))) return rc;
+    if (J.flat && (rc = launch_scan_u32(ctx, d_distinct, d_out_off, ng, ctx->h_scalar + kHsScanTotalB))) return rc;
     // (8 workgroups of 256 copy a genome's few thousand keys; a call with few, huge genomes gets as many as its keys need)
     const uint32_t gx = (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(8, J.bound / ng / 2048));
     hipLaunchKernelGGL(k_keys_compact, dim3(gx, ng), dim3(256), 0, ctx->stream, a_mn, a_lo, a_hi, b_mn, b_lo, b_hi, d_raw_off, d_distinct, d_big,
@@ -582,7 +585,7 @@ int sketch_keys_begin_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d
     uint32_t* d_raw_cnt = d_out_off + (n_genomes + 2);
     uint32_t* d_big = d_raw_cnt + (n_genomes + 2);
     if ((rc = ctx->c_flags.reserve(256))) return rc;
-    uint32_t* d_flags = ctx->c_flags.as<uint32_t>() + 16;          // two words of its own behind the comparison's sixteen (which k_parts_prepare clears and k_parts_group counts in)
+    uint32_t* d_flags = ctx->c_flags.as<uint32_t>() + kCfKeysFlags;   // two words of its own behind the comparison's sixteen (which k_parts_prepare clears and k_parts_group counts in)
     // The unordered form runs on a stream that carries a key extraction per step: its workgroups read their two record
     // bounds straight from the pinned staging block (no copy packet in front), and the gate words are cleared by the
     // compaction kernel that reports them (no fill packet either; cleared here after a call that did not get that far).
@@ -590,7 +593,7 @@ int sketch_keys_begin_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d
     const bool flat_front = !unordered || bound > (uint64_t)n_genomes * 32768ull;   // (see below)
     if (flat_front) SPSP_HIP(hipMemcpyAsync(d_first_rec, ctx->h_keys, (size_t)(n_genomes + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     else d_first_rec = ctx->h_keys;
-    if (!ctx->keys_flags_clear) SPSP_HIP(hipMemsetAsync(d_flags, 0, 8, ctx->stream));
+    if (!ctx->keys_flags_clear) SPSP_HIP(hipMemsetAsync(d_flags, 0, kKeysFlagWords * 4, ctx->stream));
     ctx->keys_flags_clear = false;
     // k == m: a bucket's only k-mer is its minimizer, and the reader takes the minimizer of EVERY bucket that exists for a
     // k-mer (an empty blob reads as the bare minimizer, Comparator.cpp:88-90,193-198) -- also of one whose k-mer stayed below
@@ -605,11 +608,8 @@ int sketch_keys_begin_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d
     ctx->keys_job = KeysJob{has_hi, flat, n_genomes, bound, ab, false};
     if (!flat) {
         const size_t lds_d = (has_hi ? (size_t)kDedupCapHi * 28 : (size_t)kDedupCapLo * 20) + kDedupSkmWords * 4;
-        if (!ctx->attr_dedupe_set) {
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_keys_fused<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)kDedupCapHi * 28 + kDedupSkmWords * 4)));
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_keys_fused<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)kDedupCapLo * 20 + kDedupSkmWords * 4)));
-            ctx->attr_dedupe_set = true;
-        }
+        if ((rc = lds_opt_in(ctx, &k_keys_fused<true>, (size_t)kDedupCapHi * 28 + kDedupSkmWords * 4)) ||
+            (rc = lds_opt_in(ctx, &k_keys_fused<false>, (size_t)kDedupCapLo * 20 + kDedupSkmWords * 4))) return rc;
         if (has_hi) hipLaunchKernelGGL((k_keys_fused<true>), dim3(n_genomes), dim3(kKeySortThreads), lds_d, ctx->stream, d_bases, packed, n_bases_readable, d_rec_off,
                                        d_sk, n, d_first_rec, p->k, w, ab, a_mn, a_lo, a_hi, d_raw_off, d_distinct, d_raw_cnt, d_big, d_flags);
         else hipLaunchKernelGGL((k_keys_fused<false>), dim3(n_genomes), dim3(kKeySortThreads), lds_d, ctx->stream, d_bases, packed, n_bases_readable, d_rec_off,
@@ -620,7 +620,7 @@ int sketch_keys_begin_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d
             hipLaunchKernelGGL(k_keys_sizes, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_sk, n, p->k, ctx->a_cnt.as<uint32_t>());
             SPSP_HIP(hipGetLastError());
         }
-        if ((rc = launch_scan_u32(ctx, ctx->a_cnt.as<uint32_t>(), ctx->a_off.as<uint32_t>(), n, ctx->h_scalar + 7))) return rc;
+        if ((rc = launch_scan_u32(ctx, ctx->a_cnt.as<uint32_t>(), ctx->a_off.as<uint32_t>(), n, ctx->h_scalar + kHsScanTotalB))) return rc;
         if (n) {
             hipLaunchKernelGGL(k_keys_emit_places, dim3((uint32_t)((bound + kPlaceTile - 1) / kPlaceTile)), dim3(kPlaceThreads), 0, ctx->stream, d_bases, packed,
                                d_rec_off, d_sk, ctx->a_off.as<uint32_t>(), ctx->a_cnt.as<uint32_t>(), n, p->k, a_mn, a_lo, a_hi);
@@ -630,11 +630,7 @@ int sketch_keys_begin_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d
                            n_genomes, d_raw_off);
         SPSP_HIP(hipGetLastError());
         const size_t lds = has_hi ? (size_t)kKeyCapHi * 21 : (size_t)kKeyCapLo * 13;
-        if (!ctx->attr_keys_set) {
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_keys_sort<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)kKeyCapHi * 21)));
-            SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_keys_sort<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)kKeyCapLo * 13)));
-            ctx->attr_keys_set = true;
-        }
+        if ((rc = lds_opt_in(ctx, &k_keys_sort<true>, (size_t)kKeyCapHi * 21)) || (rc = lds_opt_in(ctx, &k_keys_sort<false>, (size_t)kKeyCapLo * 13))) return rc;
         if (has_hi) hipLaunchKernelGGL(k_keys_sort<true>, dim3(n_genomes), dim3(kKeySortThreads), lds, ctx->stream, a_mn, a_lo, a_hi, d_raw_off, ab, d_distinct, d_raw_cnt, d_big, d_flags);
         else hipLaunchKernelGGL(k_keys_sort<false>, dim3(n_genomes), dim3(kKeySortThreads), lds, ctx->stream, a_mn, a_lo, (uint64_t*)nullptr, d_raw_off, ab, d_distinct, d_raw_cnt, d_big, d_flags);
         SPSP_HIP(hipGetLastError());

@@ -92,14 +92,14 @@ int matrix_cells_impl(spsp_ctx* ctx, const uint32_t* d_inter, uint32_t n, uint32
     if (row_limit > n) row_limit = n;
     int rc;
     if ((rc = ctx->c_flags.reserve(256))) return rc;
-    unsigned long long* d_count = reinterpret_cast<unsigned long long*>(ctx->c_flags.as<uint32_t>() + 14);   // two words of the flag block nobody else uses
+    unsigned long long* d_count = reinterpret_cast<unsigned long long*>(ctx->c_flags.as<uint32_t>() + kCfCellCount);
     SPSP_HIP(hipMemsetAsync(d_count, 0, 8, ctx->stream));
     hipLaunchKernelGGL(k_matrix_cells, dim3((n + 1023) / 1024, row_limit - row_first), dim3(256), 0, ctx->stream, d_inter, n, row_first, row_limit,
                        reinterpret_cast<unsigned long long*>(d_cells), (unsigned long long)cap, d_count);
     SPSP_HIP(hipGetLastError());
-    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + 12, d_count, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCells, d_count, 8, hipMemcpyDeviceToHost, ctx->stream));
     SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    *n_cells = ctx->h_scalar[12];
+    *n_cells = ctx->h_scalar[kHsCells];
     if (*n_cells > cap) { set_error("the matrix has %llu non-zero cells, room was given for %llu", (unsigned long long)*n_cells, (unsigned long long)cap); return SPSP_ERR_OVERFLOW; }
     return SPSP_OK;
 }
@@ -110,7 +110,7 @@ int matrix_cells_impl(spsp_ctx* ctx, const uint32_t* d_inter, uint32_t n, uint32
 int slots_bad_record(spsp_ctx* ctx) {
     if (!ctx->m_slots_job) return SPSP_OK;
     ctx->m_slots_job = false;
-    if ((uint32_t)ctx->h_scalar[13]) { set_error("an exchange slot is malformed (a record names a sketch its position does not belong to)"); return SPSP_ERR_FORMAT; }
+    if ((uint32_t)ctx->h_scalar[kHsSlotsBad]) { set_error("an exchange slot is malformed (a record names a sketch its position does not belong to)"); return SPSP_ERR_FORMAT; }
     return SPSP_OK;
 }
 
@@ -122,7 +122,7 @@ int compare_cells_run(spsp_ctx* ctx, const std::function<int()>& begin, uint32_t
     *n_cells = 0;
     int rc;
     if ((rc = ctx->c_flags.reserve(256))) return rc;
-    unsigned long long* d_count = reinterpret_cast<unsigned long long*>(ctx->c_flags.as<uint32_t>() + 14);
+    unsigned long long* d_count = reinterpret_cast<unsigned long long*>(ctx->c_flags.as<uint32_t>() + kCfCellCount);
     SPSP_HIP(hipMemsetAsync(d_count, 0, 8, ctx->stream));
     ctx->cells_req.cells = reinterpret_cast<unsigned long long*>(d_cells); ctx->cells_req.cap = cap; ctx->cells_req.count = d_count;
     ctx->cells_req.armed = row_limit >= n;                         // (query mode: rows are limited by the sparsifier, through the dense matrix)
@@ -142,7 +142,7 @@ int compare_cells_run(spsp_ctx* ctx, const std::function<int()>& begin, uint32_t
         }
         return rc;
     }
-    *n_cells = ctx->h_scalar[12];                                  // (copied to pinned memory behind the row sums: compare_end has waited for it)
+    *n_cells = ctx->h_scalar[kHsCells];                                  // (copied to pinned memory behind the row sums: compare_end has waited for it)
     if (*n_cells > cap) { set_error("the matrix has %llu non-zero cells, room was given for %llu", (unsigned long long)*n_cells, (unsigned long long)cap); return SPSP_ERR_OVERFLOW; }
     return SPSP_OK;
 }
@@ -201,7 +201,7 @@ int compare_slots_begin_impl(spsp_ctx* ctx, uint32_t k, const uint8_t* d_slots, 
         hipLaunchKernelGGL(k_slot_unpack, dim3(gx, parts), dim3(256), 0, ctx->stream, d_slots, slot_sz, hdr, words, (const uint32_t*)d_tot, (const uint32_t*)(d_tot + parts), n,
                            (const uint64_t*)ctx->x_begin.p, d_bad, ctx->m_mn.as<uint32_t>(), ctx->m_lo.as<uint64_t>(), has_hi ? ctx->m_hi.as<uint64_t>() : (uint64_t*)nullptr);
         SPSP_HIP(hipGetLastError());
-        SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + 13, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));   // read by slots_bad_record() once the job has been waited for
+        SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsSlotsBad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));   // read by slots_bad_record() once the job has been waited for
     }
     const int rc2 = compare_device_begin_impl(ctx, k, ctx->m_mn.as<uint32_t>(), ctx->m_lo.as<uint64_t>(), has_hi ? ctx->m_hi.as<uint64_t>() : nullptr, sk_off.data(),
                                               (uint32_t)N, (uint32_t)N, 0, 1, d_inter);
@@ -476,14 +476,14 @@ int spsp_matrix_add_cells_device(spsp_ctx* ctx, void* d_inter, uint32_t n, const
     SPSP_HIP(hipSetDevice(ctx->device));
     int rc;
     if ((rc = ctx->c_flags.reserve(256))) return rc;
-    uint32_t* d_bad = ctx->c_flags.as<uint32_t>() + 14;
+    uint32_t* d_bad = ctx->c_flags.as<uint32_t>() + kCfCellCount;   // (no cell count is under way: the word serves as the bad-cell flag)
     SPSP_HIP(hipMemsetAsync(d_bad, 0, 4, ctx->stream));
     hipLaunchKernelGGL(k_matrix_add_cells, dim3((uint32_t)std::min<uint64_t>(4096, (n_cells + 255) / 256)), dim3(256), 0, ctx->stream, (uint32_t*)d_inter, n,
                        (const unsigned long long*)d_cells, (unsigned long long)n_cells, d_bad);
     SPSP_HIP(hipGetLastError());
-    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + 12, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCellsBad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
     SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    if ((uint32_t)ctx->h_scalar[12]) { set_error("a cell names a sketch outside the matrix (or a pair that is not i < j)"); return SPSP_ERR_FORMAT; }
+    if ((uint32_t)ctx->h_scalar[kHsCellsBad]) { set_error("a cell names a sketch outside the matrix (or a pair that is not i < j)"); return SPSP_ERR_FORMAT; }
     return SPSP_OK;
 }
 

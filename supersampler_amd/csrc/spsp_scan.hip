@@ -1165,7 +1165,7 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(WaveLists L, uint32
     const uint32_t mine = s_pre[kCompactWaves];
     if (blockIdx.x == gridDim.x - 1 && t == 0) {    // the hit total and the fullest list, for the host and for k_resolve
         total_host[0] = (uint64_t)base + mine;
-        total_host[2] = gmax;
+        total_host[kHsScanFullest - kHsScanHits] = gmax;
         *total_dev = base + mine;
     }
     const uint32_t rec_lo = s_rec[0], rec_hi = s_rec[1];
@@ -1693,12 +1693,8 @@ static int launch_dense(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_ba
         const WaveLists L{ctx->wave_hits.as<Hit>(), ctx->wave_cnt.as<uint32_t>(), LP->cap, LP->rows_per_wave};
         if (variant == kDensePair) {
             const size_t lds = (size_t)kPairWaves * kQueueCap * 16;                // + 64 KiB static table
-            if (!ctx->attr_pair_set) {
-                const void* ks[4] = {reinterpret_cast<const void*>(&k_dense_pair<false, false>), reinterpret_cast<const void*>(&k_dense_pair<true, false>),
-                                     reinterpret_cast<const void*>(&k_dense_pair<false, true>), reinterpret_cast<const void*>(&k_dense_pair<true, true>)};
-                for (const void* kf : ks) SPSP_HIP(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                ctx->attr_pair_set = true;
-            }
+            if ((rc = lds_opt_in(ctx, &k_dense_pair<false, false>, lds)) || (rc = lds_opt_in(ctx, &k_dense_pair<true, false>, lds)) ||
+                (rc = lds_opt_in(ctx, &k_dense_pair<false, true>, lds)) || (rc = lds_opt_in(ctx, &k_dense_pair<true, true>, lds))) return rc;
 #define SPSP_PAIR(MIDV, PK) hipExtLaunchKernelGGL((k_dense_pair<MIDV, PK>), dim3(LP->grid), dim3(64 * kPairWaves), lds, ctx->stream, ev_start, ev_stop, 0, \
                                                   d_bases, n_bases, p->m, p->threshold, ctx->pairtab.as<uint8_t>(), LP->n_rows, L)
             if (packed_in) { if (p->m >= 10) SPSP_PAIR(true, true); else SPSP_PAIR(false, true); }
@@ -1706,13 +1702,8 @@ static int launch_dense(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_ba
 #undef SPSP_PAIR
         } else if (variant == kDenseBloom) {
             const size_t lds = (size_t)kBloomBytes + (size_t)kPairWaves * kQueueCap1 * 8;
-            if (!ctx->attr_bloom_set) {
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_bloom<15, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_bloom<13, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_bloom<15, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_bloom<13, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                ctx->attr_bloom_set = true;
-            }
+            if ((rc = lds_opt_in(ctx, &k_dense_bloom<15, false>, lds)) || (rc = lds_opt_in(ctx, &k_dense_bloom<13, false>, lds)) ||
+                (rc = lds_opt_in(ctx, &k_dense_bloom<15, true>, lds)) || (rc = lds_opt_in(ctx, &k_dense_bloom<13, true>, lds))) return rc;
 #define SPSP_BLOOM(MV, PK) hipExtLaunchKernelGGL((k_dense_bloom<MV, PK>), dim3(LP->grid), dim3(64 * kPairWaves), lds, ctx->stream, ev_start, ev_stop, 0, d_bases, n_bases, \
                                                  p->threshold, ctx->bloom.as<uint32_t>(), LP->n_rows, L)
             if (packed_in) { if (p->m == 15) SPSP_BLOOM(15, true); else SPSP_BLOOM(13, true); }
@@ -1720,11 +1711,7 @@ static int launch_dense(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_ba
 #undef SPSP_BLOOM
         } else {
             const size_t lds = (size_t)kKey10Bytes + (size_t)kPairWaves * kQueueCap1 * 8;
-            if (!ctx->attr_single_set) {
-                SPSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_single),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                ctx->attr_single_set = true;
-            }
+            if ((rc = lds_opt_in(ctx, &k_dense_single, lds))) return rc;
             hipExtLaunchKernelGGL(k_dense_single, dim3(LP->grid), dim3(64 * kPairWaves), lds, ctx->stream, ev_start, ev_stop, 0, d_bases, n_bases, p->m,
                                p->threshold, ctx->filter.as<uint8_t>(), LP->n_rows, L);
         }
@@ -1768,17 +1755,17 @@ int scan_hits_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_bases, 
     if ((rc = launch_dense(ctx, p, d_bases, n_bases, n_tiles, false, &LP, &lists))) return rc;
     if (lists) {
         hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(1024), 0, ctx->stream, ctx->wave_cnt.as<uint32_t>(), LP.n_lists,
-                           ctx->h_scalar + 0);
+                           ctx->h_scalar + kHsScanHits);
     } else {
         if ((rc = launch_tile_scan(ctx, n_tiles, ctx->stream))) return rc;
         const uint32_t seg_shift = seg_shift_for(n_tiles);
         const uint32_t n_seg = (uint32_t)((n_tiles + (1ull << seg_shift) - 1) >> seg_shift);
         hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(64), 0, ctx->stream, ctx->seg_a.as<uint32_t>(),
-                           ctx->seg_a.as<uint32_t>() + n_seg, n_seg, ctx->h_scalar + 0, ctx->d_scalar.as<uint32_t>() + 0);
+                           ctx->seg_a.as<uint32_t>() + n_seg, n_seg, ctx->h_scalar + kHsScanHits, ctx->d_scalar.as<uint32_t>() + 0);
     }
     SPSP_HIP(hipGetLastError());
     SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    *n_hits = ctx->h_scalar[0];
+    *n_hits = ctx->h_scalar[kHsScanHits];
     return SPSP_OK;
 }
 
@@ -1827,15 +1814,15 @@ static int scan_enqueue(spsp_ctx* ctx) {
             const WaveLists L{ctx->wave_hits.as<Hit>(), ctx->wave_cnt.as<uint32_t>(), J.list_cap, J.rows_per_wave};
             hipLaunchKernelGGL(k_compact, dim3((J.n_lists + kCompactWaves - 1) / kCompactWaves), dim3(kCompactThreads), 0, sparse,
                                L, J.n_lists, J.n_bases, p->k, p->m, J.d_rec_off, J.n_rec, ctx->hits.as<Hit>(), hits_cap,
-                               ctx->h_scalar + 0, d_sc + 0, chunk_sum, n_chunks);
+                               ctx->h_scalar + kHsScanHits, d_sc + 0, chunk_sum, n_chunks);
         } else {
-            ctx->h_scalar[2] = 0;   // no lists: nothing can overflow them (no kernel of this attempt writes the slot)
+            ctx->h_scalar[kHsScanFullest] = 0;   // no lists: nothing can overflow them (no kernel of this attempt writes the slot)
             const uint32_t seg_shift = seg_shift_for(J.n_tiles);
             const uint32_t n_seg_t = (uint32_t)((J.n_tiles + (1ull << seg_shift) - 1) >> seg_shift);
             hipLaunchKernelGGL(k_expand, dim3((uint32_t)((J.n_tiles + kExpandTilesPerWg - 1) / kExpandTilesPerWg)),
                                dim3(kThreads), 0, sparse, J.d_bases, J.n_bases, p->k, p->m, ctx->bitmap.as<uint32_t>(),
                                ctx->tile_count.as<uint32_t>(), ctx->tile_off.as<uint32_t>(), ctx->seg_a.as<uint32_t>(),
-                               n_seg_t, seg_shift, J.n_tiles, J.d_rec_off, J.n_rec, ctx->hits.as<Hit>(), hits_cap, ctx->h_scalar + 0, d_sc + 0,
+                               n_seg_t, seg_shift, J.n_tiles, J.d_rec_off, J.n_rec, ctx->hits.as<Hit>(), hits_cap, ctx->h_scalar + kHsScanHits, d_sc + 0,
                                chunk_sum, n_chunks);
         }
         SPSP_HIP(hipGetLastError());
@@ -1847,7 +1834,7 @@ static int scan_enqueue(spsp_ctx* ctx) {
     }
     hipLaunchKernelGGL(k_resolve<true>, dim3(rblocks), dim3(kResolveThreads), 0, sparse, ctx->hits.as<Hit>(), d_sc + 0,
                        hits_cap, J.d_rec_off, p->k, p->m, ctx->emit_count.as<uint32_t>(), wave_sum, chunk_sum, n_chunks,
-                       ctx->h_scalar + 1, ctx->scan_tmp.as<spsp_superkmer>(), out_cap, n_super);
+                       ctx->h_scalar + kHsScanEmitted, ctx->scan_tmp.as<spsp_superkmer>(), out_cap, n_super);
     SPSP_HIP(hipGetLastError());
     // what scan_end waits on: this job's last kernel, not the whole stream (a caller may already have queued
     // the next batch's work behind it)
@@ -1926,8 +1913,8 @@ int scan_end_impl(spsp_ctx* ctx, spsp_superkmer** d_out, uint64_t* n_out) {
     int rc;
     if (J.segments) {
         SPSP_HIP(hipEventSynchronize(ctx->scan_done));
-        const uint64_t n_em = (uint32_t)ctx->h_scalar[0];
-        const uint32_t left_halo = (uint32_t)ctx->h_scalar[1];
+        const uint64_t n_em = (uint32_t)ctx->h_scalar[kHsSegEmitted];
+        const uint32_t left_halo = (uint32_t)ctx->h_scalar[kHsSegLeftTile];
         if (left_halo == 0) {
             if (n_em == 0) return SPSP_OK;
             if ((rc = ctx->scan_tmp.reserve((size_t)n_em * sizeof(spsp_superkmer) + 64))) return rc;
@@ -1944,7 +1931,7 @@ int scan_end_impl(spsp_ctx* ctx, spsp_superkmer** d_out, uint64_t* n_out) {
     }
     for (int attempt = 0; attempt < 5; ++attempt) {
         SPSP_HIP(hipEventSynchronize(ctx->scan_done));
-        const uint64_t n_hits = ctx->h_scalar[0], n_em = ctx->h_scalar[1], fullest = J.lists ? ctx->h_scalar[2] : 0;
+        const uint64_t n_hits = ctx->h_scalar[kHsScanHits], n_em = ctx->h_scalar[kHsScanEmitted], fullest = J.lists ? ctx->h_scalar[kHsScanFullest] : 0;
         if (fullest > J.list_cap) {
             // a wave found more hits than its list holds (it kept counting): run the dense pass again with lists
             // that fit -- unless they would be out of proportion (an input that is nearly all hits in places),

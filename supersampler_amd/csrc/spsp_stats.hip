@@ -756,10 +756,10 @@ int count_superkmers_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_
         SPSP_HIP(hipGetLastError());
         std::vector<unsigned long long> back(n_files);
         SPSP_HIP(hipMemcpyAsync(back.data(), d_total, (size_t)n_files * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + 3, d_over_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+        SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsStatChains, d_over_n, 4, hipMemcpyDeviceToHost, ctx->stream));
         SPSP_HIP(hipStreamSynchronize(ctx->stream));
         const uint32_t tail_lanes = dbg_stats && dbg_stats[0] == 't' ? 1u : kSegOverCap / 64;   // ("tiny": the hand-over to the chunk kernels, for tests)
-        if ((uint32_t)ctx->h_scalar[3] <= tail_lanes) {          // (every chain handed on had its lane)
+        if ((uint32_t)ctx->h_scalar[kHsStatChains] <= tail_lanes) {          // (every chain handed on had its lane)
             for (uint32_t f = 0; f < n_files; ++f) total[f] = back[f];
             return SPSP_OK;
         }
@@ -783,7 +783,7 @@ int count_superkmers_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_
 
 
 // the scan by segments (see k_seg_scan).  _count: queues the counting launch, the prefix over the tiles and the copies of the total and of
-// the number of chains that left their tile to h_scalar[0] / [1]; _emit (after the caller has waited and reserved `out`): the writing launch
+// the number of chains that left their tile to the pinned slots kHsSegEmitted / kHsSegLeftTile; _emit (after the caller has waited and reserved `out`): the writing launch
 int seg_scan_count(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_bases, bool packed, uint64_t n_bases, const uint64_t* d_rec_off, uint32_t n_rec) {
     const uint64_t n_tiles = (n_bases + kSegIter - 1) / kSegIter;
     if (n_tiles > 0x7ffffff0ull) { set_error("input too large for one call"); return SPSP_ERR_OVERFLOW; }
@@ -800,8 +800,8 @@ int seg_scan_count(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_bases, 
     hipLaunchKernelGGL(k_seg_scan<false>, dim3((uint32_t)n_tiles), dim3(kSegThreads), 0, ctx->stream, d_bases, packed, n_bases, d_rec_off, n_rec, p->k, p->m, p->threshold,
                        d_cnt, (const uint32_t*)nullptr, (spsp_superkmer*)nullptr, 0ull, d_over_n, slow_budget);
     SPSP_HIP(hipGetLastError());
-    if ((rc = launch_scan_u32(ctx, d_cnt, d_off, n_tiles, ctx->h_scalar + 0))) return rc;      // (the total to h_scalar[0])
-    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + 1, d_over_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = launch_scan_u32(ctx, d_cnt, d_off, n_tiles, ctx->h_scalar + kHsSegEmitted))) return rc;
+    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsSegLeftTile, d_over_n, 4, hipMemcpyDeviceToHost, ctx->stream));
     return SPSP_OK;
 }
 int seg_scan_emit(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_bases, bool packed, uint64_t n_bases, const uint64_t* d_rec_off, uint32_t n_rec,
