@@ -608,6 +608,58 @@ int spsp_gather_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint3
                       uint32_t max_rounds, const char* out_prefix, int chatter, double rate,
                       spsp_gather_row** rows /* may be NULL; spsp_free */, uint64_t* n_rows);
 
+/* ------------------------------------------------------------ cluster ---- */
+/* Which sketches of a collection are the same thing, and which one to keep of each group (not in the reference, whose end
+ * product is the two n x n matrices).  Single linkage, on the comparator's keys, integers only.  Sketches are 0 .. n-1 in list
+ * order, c_i = the key count of sketch i, x_ij = the keys i and j share; the threshold is the fraction num / den with
+ * 1 <= num <= den <= 1 000 000.  i < j are LINKED iff x_ij >= 1 and
+ *     SPSP_CLUSTER_JACCARD      x_ij * den >= num * (c_i + c_j - x_ij)
+ *     SPSP_CLUSTER_CONTAINMENT  x_ij * den >= num * min(c_i, c_j)            (the larger of the two containment indices)
+ * (equality passes; no floating point takes part).  A cluster is a connected component of that graph.  Clusters are numbered
+ * 0, 1, 2, ... in the order of their first-listed member (sketch 0 is in cluster 0); a sketch without an edge is a cluster of
+ * one; two empty sketches are never linked (no cell names them).  The representative of a cluster is its member with the most
+ * keys, the first listed among equals. */
+#define SPSP_CLUSTER_JACCARD 0
+#define SPSP_CLUSTER_CONTAINMENT 1
+typedef struct spsp_cluster_row {   /* one per sketch, in list order; 24 bytes */
+    uint32_t cluster;         /* number of the sketch's cluster */
+    uint32_t representative;  /* index of that cluster's representative */
+    uint32_t size;            /* members of the cluster */
+    uint32_t reserved;        /* 0 */
+    uint64_t shared;          /* x_{i,representative}; c_i for the representative itself.  May be 0: single linkage chains, and
+                                 a member need not touch its representative */
+} spsp_cluster_row;
+
+/* d_cells: n_cells packed words i << 48 | j << 32 | count on the device, what spsp_compare_cells_device or
+ * spsp_matrix_cells_device leaves there (every pair at most once, any order, i < j < n <= 65535, count <= min(c_i, c_j)); they
+ * are only read.  h_card: the n key counts (host), each below 2^47.  rows receives n rows; *n_clusters the number of clusters,
+ * *n_edges the number of pairs that passed the threshold.  The work buffers belong to the context and are reused call after
+ * call.  A fixed chain of launches whatever n and n_cells are -- init, link (a lock-free union per edge), flatten, a scan over
+ * the "is a root" flags, a second pass over the cells for `shared`, rows -- and ONE host wait at the end.  SPSP_ERR_ARG, before
+ * any kernel runs, for n == 0, n > 65535, a metric other than the two, num == 0, num > den, den > 1 000 000 and a key count of
+ * 2^47 or more; SPSP_ERR_ARG also for a cell with i >= j or j >= n (found by the link kernel, which never indexes with such a
+ * pair).  n_cells == 0 is valid: n clusters of one. */
+int spsp_cluster_cells_device(spsp_ctx* ctx, const void* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n,
+                              int metric, uint32_t num, uint32_t den,
+                              spsp_cluster_row* rows /* n */, uint64_t* n_clusters, uint64_t* n_edges);
+/* The rows as text: the line "sketch,cluster,representative,size,keys,shared,score", then one line per sketch in list order --
+ * names[i], cluster, names[representative], size, card[i], shared in decimal, and score = the metric's value for (i,
+ * representative) as an IEEE double division (shared / (card[i] + card[representative] - shared), or shared / min of the two
+ * counts; 0 when shared is 0) printed as the matrices print a score (%.<precision>g); a representative's own row prints 1.
+ * The score is only printed: it never decided anything.  A row that names a representative >= n, or one outside its own
+ * cluster, is SPSP_ERR_ARG.  *text is released with spsp_free(). */
+int spsp_cluster_csv_host(const spsp_cluster_row* rows, const char* const* names, uint32_t n, const uint64_t* card,
+                          int metric, int precision, char** text, uint64_t* len);
+/* The whole-file driver: the files are read, inflated and decoded as spsp_compare_files_rate does it (the same code), with the
+ * same `rate` argument (SPSP_RATE_AS_IS, a rate, or SPSP_RATE_COARSEST) and the same refusals; then the all-vs-all as cells, for
+ * every n, and the cluster pass.  The cells never leave the device: the n rows and the two counts come back.  Writes ONE file,
+ * <out_prefix>_clusters.csv.gz (gzip level 1, as the matrices), and no matrices.  k == m collections are SPSP_ERR_ARG.
+ * chatter != 0: the reference's "kmers evaluated" line, one line with sketches, edges, clusters and the largest cluster, and
+ * the common-rate line when a rate was asked for.  One device: there is no multi-device form. */
+int spsp_cluster_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, int metric, uint32_t num, uint32_t den,
+                       const char* out_prefix, int chatter, double rate,
+                       spsp_cluster_row** rows /* may be NULL; spsp_free */, uint64_t* n_clusters /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

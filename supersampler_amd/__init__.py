@@ -84,6 +84,14 @@ class GatherRow(C.Structure):
 GATHER_ROW_DTYPE = np.dtype([("query", "<u4"), ("rank", "<u4"), ("match", "<u4"), ("reserved", "<u4"), ("intersect", "<u8"), ("unique", "<u8"),
                              ("remaining", "<u8")])
 
+class ClusterRow(C.Structure):
+    """spsp_cluster_row: one sketch's place in the clustering of its collection (include/spsp.h)"""
+    _fields_ = [("cluster", C.c_uint32), ("representative", C.c_uint32), ("size", C.c_uint32), ("reserved", C.c_uint32), ("shared", C.c_uint64)]
+
+
+CLUSTER_ROW_DTYPE = np.dtype([("cluster", "<u4"), ("representative", "<u4"), ("size", "<u4"), ("reserved", "<u4"), ("shared", "<u8")])
+CLUSTER_JACCARD, CLUSTER_CONTAINMENT = 0, 1
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -97,6 +105,7 @@ ABI_SYMBOLS = [
     "spsp_csv_host", "spsp_csv_cells_host", "spsp_csv_cells_gz_host", "spsp_sort_csv_host", "spsp_read_file_host", "spsp_write_gz_host", "spsp_sketch_file", "spsp_compare_files", "spsp_compare_files_chatty", "spsp_stage_times_read", "spsp_measure_hbm_device", "spsp_sketch_files", "spsp_sketch_files_multi", "spsp_sketch_files_release", "spsp_compare_files_multi", "spsp_matrix_cells_device", "spsp_matrix_add_cells_device", "spsp_compare_cells_device", "spsp_compare_slots_cells_device",
     "spsp_keys_downsample_device", "spsp_sketch_header_host", "spsp_sketch_downsample_host", "spsp_compare_files_rate", "spsp_compare_files_multi_rate",
     "spsp_gather_device", "spsp_gather_csv_host", "spsp_gather_files",
+    "spsp_cluster_cells_device", "spsp_cluster_csv_host", "spsp_cluster_files",
 ]
 
 _lib = None
@@ -229,6 +238,13 @@ def lib():
         L.spsp_gather_csv_host.argtypes = [vp, u64, P(cp), u32, u32, vp, i32, P(vp), P(u64)]
         L.spsp_gather_files.restype = i32
         L.spsp_gather_files.argtypes = [vp, P(cp), u32, u32, i32, u64, u32, cp, i32, dbl, P(vp), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_cluster_cells_device"):
+        L.spsp_cluster_cells_device.restype = i32
+        L.spsp_cluster_cells_device.argtypes = [vp, vp, u64, vp, u32, i32, u32, u32, vp, P(u64), P(u64)]
+        L.spsp_cluster_csv_host.restype = i32
+        L.spsp_cluster_csv_host.argtypes = [vp, P(cp), u32, vp, i32, i32, P(vp), P(u64)]
+        L.spsp_cluster_files.restype = i32
+        L.spsp_cluster_files.argtypes = [vp, P(cp), u32, i32, i32, u32, u32, cp, i32, dbl, P(vp), P(u64)]
     _lib = L
     return L
 
@@ -384,6 +400,20 @@ def gather_csv(rows, names, card, n_query, precision=6):
     arr = (C.c_char_p * n)(*[s.encode() for s in names])
     out, ln = C.c_void_p(), C.c_uint64()
     _check(lib().spsp_gather_csv_host(rows.ctypes.data, len(rows), arr, n, n_query, card.ctypes.data, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def cluster_csv(rows, names, card, metric, precision=6):
+    """spsp_cluster_csv_host: cluster rows (CLUSTER_ROW_DTYPE array, one per sketch in list order) -> the text of
+    <prefix>_clusters.csv.gz; card[i] = key count of sketch i as the clustering saw it"""
+    rows = np.ascontiguousarray(rows, dtype=CLUSTER_ROW_DTYPE)
+    card = np.ascontiguousarray(card, dtype=np.uint64)
+    n = len(names)
+    if len(rows) != n or len(card) != n:
+        raise ValueError("cluster_csv: one row and one key count per name")
+    arr = (C.c_char_p * n)(*[s.encode() for s in names])
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_cluster_csv_host(rows.ctypes.data, arr, n, card.ctypes.data, metric, precision, C.byref(out), C.byref(ln)))
     return _take(out, ln.value)
 
 
@@ -844,3 +874,23 @@ class Context:
         _check(lib().spsp_gather_files(self._h, arr, n, n_query, precision, min_keys, max_rounds, out_prefix.encode(), 0, _rate_arg(rate),
                                        C.byref(out), C.byref(cnt)))
         return np.frombuffer(_take(out, cnt.value * GATHER_ROW_DTYPE.itemsize), dtype=GATHER_ROW_DTYPE).copy()
+
+    def cluster_cells_device(self, d_cells, n_cells, card, n, metric, num, den):
+        """spsp_cluster_cells_device: single-linkage clusters of sketches 0 .. n-1 from the packed cells (i << 48 | j << 32 | count)
+        of their pair matrix on the device and the n key counts -> (rows: CLUSTER_ROW_DTYPE array of n, n_clusters, n_edges);
+        linked iff count * den >= num * (c_i + c_j - count) (metric 0) or >= num * min(c_i, c_j) (metric 1)"""
+        card = np.ascontiguousarray(card, dtype=np.uint64)
+        if len(card) != n:
+            raise ValueError("cluster_cells_device: one key count per sketch")
+        rows = np.zeros(n, dtype=CLUSTER_ROW_DTYPE)
+        nc, ne = C.c_uint64(), C.c_uint64()
+        _check(lib().spsp_cluster_cells_device(self._h, d_cells, n_cells, card.ctypes.data, n, metric, num, den, rows.ctypes.data, C.byref(nc), C.byref(ne)))
+        return rows, nc.value, ne.value
+
+    def cluster_files(self, paths, out_prefix, metric, num, den, precision=6, rate=0.0):
+        """spsp_cluster_files: sketch files -> <out_prefix>_clusters.csv.gz and (rows, n_clusters).  rate: as compare_files"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        out, nc = C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_cluster_files(self._h, arr, n, precision, metric, num, den, out_prefix.encode(), 0, _rate_arg(rate), C.byref(out), C.byref(nc)))
+        return np.frombuffer(_take(out, n * CLUSTER_ROW_DTYPE.itemsize), dtype=CLUSTER_ROW_DTYPE).copy(), nc.value

@@ -1,7 +1,9 @@
 // comparator -- drop-in command line of the reference's comparator
 // (Comparator.cpp:464-521) over libspsp: same flags, defaults, messages and
 // output files (<o>_containment.csv.gz, <o>_jaccard.csv.gz).  One addition: -g <min_keys> with -q gathers instead --
-// which references make up each query, greedily (spsp_gather_files) -> <o>_gather.csv.gz.
+// which references make up each query, greedily (spsp_gather_files) -> <o>_gather.csv.gz.  Another: -c <t> / -C <t> without -q
+// clusters the index instead -- single linkage on Jaccard / on the larger containment at threshold t (spsp_cluster_files) ->
+// <o>_clusters.csv.gz.
 #include <getopt.h>
 
 #include <chrono>
@@ -28,6 +30,24 @@ static bool read_names(const string& fof, vector<string>& out) {
     return true;
 }
 
+// -c / -C <t>: a decimal in (0, 1] with at most six digits behind the point, read as TEXT into num / 10^digits ("0.95" = 95 / 100,
+// "1" = 1 / 1): the threshold takes part in integer comparisons only
+static bool parse_fraction(const char* t, uint32_t* num, uint32_t* den) {
+    if ((t[0] != '0' && t[0] != '1') || (t[1] != 0 && t[1] != '.')) return false;
+    uint64_t n = (uint64_t)(t[0] - '0'), d = 1;
+    if (t[1] == '.') {
+        const char* f = t + 2;
+        if (*f == 0) return false;
+        for (; *f; ++f) {
+            if (*f < '0' || *f > '9' || d >= 1000000) return false;
+            n = n * 10 + (uint64_t)(*f - '0'); d *= 10;
+        }
+    }
+    if (n < 1 || n > d) return false;
+    *num = (uint32_t)n; *den = (uint32_t)d;
+    return true;
+}
+
 int main(int argc, char** argv) {
     int ch;
     string inputfof, query, output_name("results");
@@ -36,8 +56,19 @@ int main(int argc, char** argv) {
     double rate = SPSP_RATE_AS_IS;   // -s <rate> / -s auto: compare at a common sampling rate (not in the reference, which parses and ignores -s)
     bool gather = false;             // -g <min_keys>: the reference parses -g and ignores it
     uint64_t min_keys = 0;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:")) != -1) {
+    int cluster_opts = 0, cluster_metric = SPSP_CLUSTER_JACCARD;   // -c <t> / -C <t>: neither letter is in the reference's option string
+    uint32_t cluster_num = 0, cluster_den = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:")) != -1) {
         switch (ch) {
+            case 'c':
+            case 'C':
+                if (!parse_fraction(optarg, &cluster_num, &cluster_den)) {
+                    cout << "-" << (char)ch << " takes a threshold in (0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
+                    return 1;
+                }
+                cluster_metric = ch == 'c' ? SPSP_CLUSTER_JACCARD : SPSP_CLUSTER_CONTAINMENT;
+                ++cluster_opts;
+                break;
             case 'f': inputfof = optarg; break;
             case 'q': query = optarg; break;
             case 'p': p = stoi(optarg); break;
@@ -60,6 +91,8 @@ int main(int argc, char** argv) {
                 break;
         }
     }
+    if (cluster_opts > 1) { cout << "-c (Jaccard) and -C (containment) cluster the index: one of them, once" << endl; return 1; }
+    if (cluster_opts && (query != "" || gather)) { cout << "-c / -C cluster the index all versus all: not together with -q or -g" << endl; return 1; }
     if (inputfof == "") {
         cout << "Core arguments:" << endl
              << "-f Index file of files (mandatory)" << endl
@@ -104,6 +137,17 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (cluster_opts) {
+        // one device, as gather
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_cluster_files(ctx, paths.data(), (uint32_t)paths.size(), (int)p, cluster_metric, cluster_num, cluster_den, output_name.c_str(), 1,
+                                                   rate, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Clustering failed: " << err << endl; return 1; }
+        return 0;
     }
     if (gather) {
         // one device: the first of SPSP_DEVICES, else device 0

@@ -1527,9 +1527,10 @@ int spsp_stage_times_read(spsp_ctx* ctx, spsp_stage_times* out, int reset) {
 // gather: instead of the comparison and its two matrices, the greedy gather of the first n_query sketches against the others
 // (GatherReq::device_half: spsp_gather.hip) and <out_prefix>_gather.csv.gz; everything in front of the comparison -- reading, inflating, the headers'
 // rates, the refusals -- is the same code
+// cluster: likewise, the single-linkage clusters of the n sketches (ClusterReq::device_half: spsp_cluster.hip) and <out_prefix>_clusters.csv.gz
 static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
                               double min_threshold, const char* out_prefix, int chatter, double rate, spsp_ctx* const* more = nullptr, uint32_t n_more = 0,
-                              spsp::GatherReq* gather = nullptr) {
+                              spsp::GatherReq* gather = nullptr, spsp::ClusterReq* cluster = nullptr) {
     // more / n_more: all contexts of a multi-device call (more[0] == ctx): the comparison is then split by key over them
     // rate: SPSP_RATE_AS_IS = the headers' rates are ignored, as the reference does; SPSP_RATE_COARSEST or a rate = every sketch
     // is brought down to it on the device first
@@ -1656,6 +1657,7 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
         else { m0 = (uint32_t)mm; k0 = (uint32_t)((skm + mm) / 2); }
     }
     if (!rc && n && gather && k0 == m0) { set_error("gather is not defined for k == m sketches (k = m = %u)", k0); rc = SPSP_ERR_ARG; }
+    if (!rc && n && cluster && k0 == m0) { set_error("clustering is not defined for k == m sketches (k = m = %u)", k0); rc = SPSP_ERR_ARG; }
     // the merge's shared first-read buffer, in file order (see spsp_sketch_chain_host): phantom keys of empty sketches
     std::vector<int> extra_has(n, 0);
     std::vector<uint32_t> extra_mn(n, 0);
@@ -1734,6 +1736,31 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
         }
         return rc;
     }
+    if (!rc && cluster) {
+        if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }
+        t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
+        uint32_t kk = 0, mm2 = 0;
+        ctx->ds_armed = ds_on; ctx->ds_threshold = ds_thr;     // (read and cleared by the call below)
+        rc = cluster->device_half(ctx, datas.data(), lens.data(), n, cluster->metric, cluster->num, cluster->den, &kk, &mm2, card.data(), &cluster->rows,
+                                  &cluster->n_clusters, &cluster->n_edges);
+        free_datas();
+        t1 = now_s(); ctx->stages.compare_s += t1 - t0; t0 = t1;
+        if (rc) return rc;
+        char* text = nullptr; uint64_t len = 0;
+        if ((rc = spsp_cluster_csv_host(cluster->rows.data(), paths, n, card.data(), cluster->metric, precision, &text, &len))) return rc;
+        t1 = now_s(); ctx->stages.csv_s += t1 - t0;
+        rc = spsp_write_gz_host((std::string(out_prefix) + "_clusters.csv.gz").c_str(), (const uint8_t*)text, len, 1);
+        ctx->stages.csv_gzip_s += now_s() - t1;
+        free(text);
+        if (!rc && chatter) {
+            uint32_t largest = 0;
+            for (const spsp_cluster_row& r : cluster->rows) largest = std::max(largest, r.size);
+            printf("%u sketches, %llu edges, %llu clusters, the largest of %u\n", n, (unsigned long long)cluster->n_edges, (unsigned long long)cluster->n_clusters, largest);
+            if (n && rate != SPSP_RATE_AS_IS) printf("Sketches compared at sampling rate %g: %u of %u brought down to it\n", ds_rate, ds_brought, n);
+            fflush(stdout);
+        }
+        return rc;
+    }
     if (!rc) {
         if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }   // :56
         t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
@@ -1805,6 +1832,39 @@ int spsp_gather_csv_host(const spsp_gather_row* rows, uint64_t n_rows, const cha
     return SPSP_OK;
 }
 
+int spsp_cluster_csv_host(const spsp_cluster_row* rows, const char* const* names, uint32_t n, const uint64_t* card, int metric, int precision,
+                          char** text, uint64_t* len) {
+    if (!text || !len || (n && (!rows || !names || !card))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (metric != SPSP_CLUSTER_JACCARD && metric != SPSP_CLUSTER_CONTAINMENT) { set_error("cluster metric %d: 0 (Jaccard) or 1 (containment)", metric); return SPSP_ERR_ARG; }
+    std::string out = "sketch,cluster,representative,size,keys,shared,score\n";
+    char num[64];
+    for (uint32_t i = 0; i < n; ++i) {
+        const spsp_cluster_row& r = rows[i];
+        if (r.representative >= n || rows[r.representative].cluster != r.cluster) {
+            set_error("cluster row %u names a representative outside %s", i, r.representative >= n ? "the list" : "its own cluster");
+            return SPSP_ERR_ARG;
+        }
+        const uint64_t ci = card[i], cr = card[r.representative];
+        double score = 1.0;                                    // (printed only: the integer test has decided)
+        if (r.representative != i) {
+            const double under = metric == SPSP_CLUSTER_JACCARD ? (double)(ci + cr - r.shared) : (double)std::min(ci, cr);
+            score = r.shared ? (double)r.shared / under : 0.0;
+        }
+        out += names[i]; out += ',';
+        out += std::to_string(r.cluster); out += ',';
+        out += names[r.representative]; out += ',';
+        out += std::to_string(r.size); out += ',';
+        out += std::to_string(ci); out += ',';
+        out += std::to_string(r.shared); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, score)); out += '\n';
+    }
+    char* buf = (char*)malloc(out.size() ? out.size() : 1);
+    if (!buf) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    memcpy(buf, out.data(), out.size());
+    *text = buf; *len = out.size();
+    return SPSP_OK;
+}
+
 int spsp_compare_files_rate(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, double min_threshold,
                             const char* out_prefix, int chatter, double rate) {
     return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, chatter < 0 ? 0 : (chatter > 2 ? 2 : chatter), rate);
@@ -1852,5 +1912,9 @@ namespace spsp {
 int gather_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, const char* out_prefix, int chatter,
                       double rate, GatherReq* G) {
     return compare_files_impl(ctx, paths, n, n_query, precision, 0.0, out_prefix, chatter ? 2 : 0, rate, nullptr, 0, G);
+}
+int cluster_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, const char* out_prefix, int chatter, double rate,
+                       ClusterReq* Q) {
+    return compare_files_impl(ctx, paths, n, n, precision, 0.0, out_prefix, chatter ? 1 : 0, rate, nullptr, 0, nullptr, Q);
 }
 }  // namespace spsp

@@ -109,7 +109,10 @@ enum HostSlot {
                             // a context between a slot comparison's begin and end would overwrite that comparison's record check
     kHsOrderVerdict = 14,   // k_row_order's two u32 (sketches kept together in the new order | in the input's << 32); compare_end_impl reads
     kHsMultiVerdict = 15,   // k_parts_group's two u32 (records with a list | records sampled << 32), copied with the order verdict
-    kHostSlots = 16
+    kHsClusterEdges = 16,   // spsp_cluster.hip: the copy of k_cl_link's edge count (u64); cluster_cells_impl reads behind its one wait
+    kHsClusterBad = 17,     // ... of k_cl_link's bad-cell word (u32), in the same wait
+    kHsClusterCount = 18,   // ... and launch_scan_u32's total over the "is a root" flags: the number of clusters (u64)
+    kHostSlots = 19
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
@@ -227,6 +230,8 @@ struct spsp_ctx {
     // gather (spsp_gather.hip): sketch offsets, per-(query, reference) counters / their scan / fill places, per-query-key counts
     // (the rounds' dead flags) / their scan, edge list, edges by reference, holders by query key, counters, round state, a batch's rows
     spsp::DevBuf g_off, g_u, g_roff, g_rfill, g_qcnt, g_qoff, g_edges, g_byref, g_hold, g_count, g_state, g_rows;
+    // clustering (spsp_cluster.hip): the per-sketch arrays and the counter words in one work area, the rows
+    spsp::DevBuf cl_work, cl_rows;
     bool ds_armed = false;             // the next compare_payloads_impl / _multi call brings the decoded keys down to ds_threshold first
     uint64_t ds_threshold = 0;
 };
@@ -309,6 +314,27 @@ int gather_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint3
                       double rate, GatherReq* G);
 int gather_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, uint32_t n_query, uint64_t min_keys,
                          uint32_t max_rounds, uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_gather_row>* rows);
+// spsp_cluster.hip: single-linkage clusters of the sketches 0 .. n-1 from the packed cells of their pair matrix (on the device, only
+// read); cluster_payloads_impl: decode (+ the downsampling pass when ctx->ds_armed) + the all-vs-all as cells + the cluster pass:
+// the cells stay on the device; card = the key counts the comparison saw
+int cluster_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n, int metric, uint32_t num,
+                       uint32_t den, spsp_cluster_row* rows, uint64_t* n_clusters, uint64_t* n_edges);
+int cluster_check_args(uint32_t n, int metric, uint32_t num, uint32_t den);
+// spsp_cluster_files: the request that travels through the comparator's file driver, as GatherReq does (device_half is
+// cluster_payloads_impl -- a pointer, so that the host translation unit links without the device code)
+struct ClusterReq {
+    int metric = 0;
+    uint32_t num = 1, den = 1;
+    std::vector<spsp_cluster_row> rows;
+    uint64_t n_clusters = 0, n_edges = 0;
+    int (*device_half)(spsp_ctx*, const uint8_t* const*, const uint64_t*, uint32_t, int, uint32_t, uint32_t, uint32_t*, uint32_t*, uint64_t*,
+                       std::vector<spsp_cluster_row>*, uint64_t*, uint64_t*) = nullptr;
+};
+int cluster_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, const char* out_prefix, int chatter, double rate,
+                       ClusterReq* Q);
+int cluster_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, int metric, uint32_t num, uint32_t den,
+                          uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_cluster_row>* rows, uint64_t* n_clusters,
+                          uint64_t* n_edges);
 // (cells_out, for 1024 <= n <= 65535: the non-zero cells i << 48 | j << 32 | count, every pair once, INSTEAD of the matrix: inter may be null)
 int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
                               const int* extra_has, const uint32_t* extra_mn, uint32_t* k_out, uint32_t* m_out, uint64_t* sk_off);
