@@ -225,47 +225,48 @@ int cluster_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells,
 }
 
 int cluster_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, int metric, uint32_t num, uint32_t den,
-                          uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_cluster_row>* rows, uint64_t* n_clusters,
-                          uint64_t* n_edges) {
-    const bool ds_on = ctx->ds_armed;
-    const uint64_t ds_threshold = ctx->ds_threshold;
-    ctx->ds_armed = false;
+                          const uint64_t* ds_threshold, uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_cluster_row>* rows,
+                          uint64_t* n_clusters, uint64_t* n_edges) {
     rows->clear();
     *n_clusters = 0; *n_edges = 0;
     int rc;
     if ((rc = cluster_check_args(n, metric, num, den))) return rc;
-    std::vector<uint64_t> sk_off((size_t)n + 1, 0);
-    if ((rc = sketch_decode_device_impl(ctx, payloads, lens, n, nullptr, nullptr, k_out, m_out, sk_off.data()))) return rc;
-    const uint32_t k = *k_out;
-    const uint32_t* d_mn = ctx->c_min.as<uint32_t>();
-    const uint64_t* d_lo = ctx->c_lo.as<uint64_t>();
-    const uint64_t* d_hi = k > 32 ? ctx->c_hi.as<uint64_t>() : nullptr;
-    if (ds_on && sk_off[n]) {
-        uint32_t* f_mn = nullptr; uint64_t *f_lo = nullptr, *f_hi = nullptr;
-        std::vector<uint64_t> kept((size_t)n + 1, 0);
-        if ((rc = keys_downsample_impl(ctx, k, ds_threshold, d_mn, d_lo, d_hi, sk_off.data(), n, &f_mn, &f_lo, &f_hi, kept.data()))) return rc;
-        d_mn = f_mn; d_lo = f_lo; d_hi = f_hi;
-        sk_off.swap(kept);
-    }
-    for (uint32_t i = 0; i < n; ++i) card[i] = sk_off[i + 1] - sk_off[i];
+    DecodedKeys keys;
+    rc = decode_keys_impl(ctx, payloads, lens, n, nullptr, nullptr, ds_threshold, &keys, card);
+    *k_out = keys.k; *m_out = keys.m;
+    if (rc) return rc;
     uint64_t n_cells = 0;
-    if (sk_off[n] && n > 1) {
-        // the all-vs-all as cells for every n (compare_cells_run goes through the dense scratch matrix where the form needs it);
-        // more cells than the room first offered: the room grows and the comparison is repeated
-        if ((rc = ctx->c_inter.reserve((size_t)n * n * 4))) return rc;
-        uint64_t cap = std::max<uint64_t>(1u << 16, (uint64_t)n * 32);
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if ((rc = ctx->m_cells.reserve((size_t)cap * 8))) return rc;
-            if (n < 1024) SPSP_HIP(hipMemsetAsync(ctx->c_inter.p, 0, (size_t)n * n * 4, ctx->stream));
-            rc = compare_cells_run(ctx, [&]() { return compare_device_begin_impl(ctx, k, d_mn, d_lo, d_hi, sk_off.data(), n, n, 0, 1, ctx->c_inter.as<uint32_t>()); },
-                                   n, n, ctx->c_inter.as<uint32_t>(), ctx->m_cells.as<uint64_t>(), cap, &n_cells, &ctx->m_cells);
-            if (rc != SPSP_ERR_OVERFLOW) break;
-            cap = n_cells;
-        }
-        if (rc) return rc;
-    }
+    // the all-vs-all as cells for every n
+    if (keys.sk_off[n] && n > 1 && (rc = compare_keys_cells(ctx, keys, n, n, &n_cells))) return rc;
     rows->resize(n);
     return cluster_cells_impl(ctx, ctx->m_cells.as<uint64_t>(), n_cells, card, n, metric, num, den, rows->data(), n_clusters, n_edges);
+}
+
+// spsp_cluster_files behind its argument checks: the sketches loaded (spsp_host.cpp), the clusters, <out_prefix>_clusters.csv.gz
+static int cluster_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, int metric, uint32_t num, uint32_t den, const char* out_prefix,
+                         int chatter, double rate, std::vector<spsp_cluster_row>* rows, uint64_t* n_clusters) {
+    LoadedSketches L;
+    int rc = load_sketch_files(ctx, paths, n, rate, &L);
+    if (L.k && L.k == L.m) { set_error("clustering is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
+    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
+    const double t0 = files_loaded(ctx, L, n, chatter);
+    uint32_t k = 0, m = 0;
+    uint64_t n_edges = 0;
+    std::vector<uint64_t> card(n, 0);
+    rc = cluster_payloads_impl(ctx, L.data.data(), L.len.data(), n, metric, num, den, L.threshold(), &k, &m, card.data(), rows, n_clusters, &n_edges);
+    L.release();
+    const double t1 = now_s();
+    ctx->stages.compare_s += t1 - t0;
+    if (rc) return rc;
+    char* text = nullptr; uint64_t len = 0;
+    if ((rc = spsp_cluster_csv_host(rows->data(), paths, n, card.data(), metric, precision, &text, &len))) return rc;
+    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_clusters.csv.gz", t1)) || !chatter) return rc;
+    uint32_t largest = 0;
+    for (const spsp_cluster_row& r : *rows) largest = std::max(largest, r.size);
+    printf("%u sketches, %llu edges, %llu clusters, the largest of %u\n", n, (unsigned long long)n_edges, (unsigned long long)*n_clusters, largest);
+    say_common_rate(L, n);
+    fflush(stdout);
+    return SPSP_OK;
 }
 
 }  // namespace spsp
@@ -287,14 +288,14 @@ extern "C" int spsp_cluster_files(spsp_ctx* ctx, const char* const* paths, uint3
     int rc;
     if ((rc = cluster_check_args(n, metric, num, den))) return rc;
     SPSP_HIP(hipSetDevice(ctx->device));
-    ClusterReq Q;
-    Q.metric = metric; Q.num = num; Q.den = den; Q.device_half = cluster_payloads_impl;
-    if ((rc = cluster_files_impl(ctx, paths, n, precision, out_prefix, chatter, rate, &Q))) return rc;
-    if (n_clusters) *n_clusters = Q.n_clusters;
+    std::vector<spsp_cluster_row> got;
+    uint64_t count = 0;
+    if ((rc = cluster_files(ctx, paths, n, precision, metric, num, den, out_prefix, chatter, rate, &got, &count))) return rc;
+    if (n_clusters) *n_clusters = count;
     if (rows) {
-        *rows = (spsp_cluster_row*)malloc(Q.rows.size() ? Q.rows.size() * sizeof(spsp_cluster_row) : 1);
+        *rows = (spsp_cluster_row*)malloc(got.size() ? got.size() * sizeof(spsp_cluster_row) : 1);
         if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        if (!Q.rows.empty()) memcpy(*rows, Q.rows.data(), Q.rows.size() * sizeof(spsp_cluster_row));
+        if (!got.empty()) memcpy(*rows, got.data(), got.size() * sizeof(spsp_cluster_row));
     }
     return SPSP_OK;
 }

@@ -691,45 +691,41 @@ int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, con
     return SPSP_OK;
 }
 
-int compare_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, const int* extra_has,
-                          const uint32_t* extra_mn, uint32_t n_query, uint32_t* k_out, uint32_t* m_out, uint32_t* inter, uint64_t* card, bool* mirrored,
-                          std::vector<uint64_t>* cells_out) {
-    const bool ds_on = ctx->ds_armed;
-    const uint64_t ds_threshold = ctx->ds_threshold;
-    ctx->ds_armed = false;
-    if (mirrored) *mirrored = false;
-    if (cells_out) cells_out->clear();
-    std::vector<uint64_t> sk_off((size_t)n + 1, 0);
-    int rc = sketch_decode_device_impl(ctx, payloads, lens, n, extra_has, extra_mn, k_out, m_out, sk_off.data());
-    if (rc || n == 0) return rc;
-    const uint32_t k = *k_out;
-    const uint32_t* d_mn = ctx->c_min.as<uint32_t>();
-    const uint64_t* d_lo = ctx->c_lo.as<uint64_t>();
-    const uint64_t* d_hi = k > 32 ? ctx->c_hi.as<uint64_t>() : nullptr;
-    if (ds_on && sk_off[n]) {
-        // sketches of mixed sampling rates: all brought down to one threshold where they lie, between the decoder and the comparison
+int decode_keys_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, const int* extra_has, const uint32_t* extra_mn,
+                     const uint64_t* ds_threshold, DecodedKeys* keys, uint64_t* card) {
+    std::vector<uint64_t>& sk_off = keys->sk_off;
+    sk_off.assign((size_t)n + 1, 0);
+    int rc = sketch_decode_device_impl(ctx, payloads, lens, n, extra_has, extra_mn, &keys->k, &keys->m, sk_off.data());
+    if (rc) return rc;
+    keys->mn = ctx->c_min.as<uint32_t>();
+    keys->lo = ctx->c_lo.as<uint64_t>();
+    keys->hi = keys->k > 32 ? ctx->c_hi.as<uint64_t>() : nullptr;
+    if (ds_threshold && sk_off[n]) {
+        // sketches of mixed sampling rates: all brought down to one threshold where they lie, between the decoder and what reads the keys
         uint32_t* f_mn = nullptr; uint64_t *f_lo = nullptr, *f_hi = nullptr;
         std::vector<uint64_t> kept((size_t)n + 1, 0);
-        if ((rc = keys_downsample_impl(ctx, k, ds_threshold, d_mn, d_lo, d_hi, sk_off.data(), n, &f_mn, &f_lo, &f_hi, kept.data()))) return rc;
-        d_mn = f_mn; d_lo = f_lo; d_hi = f_hi;
+        if ((rc = keys_downsample_impl(ctx, keys->k, *ds_threshold, keys->mn, keys->lo, keys->hi, sk_off.data(), n, &f_mn, &f_lo, &f_hi, kept.data()))) return rc;
+        keys->mn = f_mn; keys->lo = f_lo; keys->hi = f_hi;
         sk_off.swap(kept);
     }
     for (uint32_t i = 0; i < n; ++i) card[i] = sk_off[i + 1] - sk_off[i];
-    if (sk_off[n] == 0) return SPSP_OK;                            // (inter is zero on entry)
-    if ((rc = ctx->c_inter.reserve((size_t)n * n * 4))) return rc;
+    return SPSP_OK;
+}
+
+int compare_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, const int* extra_has,
+                          const uint32_t* extra_mn, uint32_t n_query, const uint64_t* ds_threshold, uint32_t* k_out, uint32_t* m_out, uint32_t* inter,
+                          uint64_t* card, bool* mirrored, std::vector<uint64_t>* cells_out) {
+    if (mirrored) *mirrored = false;
+    if (cells_out) cells_out->clear();
+    DecodedKeys keys;
+    int rc = decode_keys_impl(ctx, payloads, lens, n, extra_has, extra_mn, ds_threshold, &keys, card);
+    *k_out = keys.k; *m_out = keys.m;
+    if (rc || keys.sk_off[n] == 0) return rc;                      // (inter is zero on entry)
     if (n >= 1024 && n <= 65535) {
         // a large matrix is mostly zeros (sketches of different species share no k-mer) and 4 n^2 bytes would cross PCIe:
         // the non-zero cells come back instead, straight from the row sums (spsp_multi.hip: compare_cells_run)
-        uint64_t cap = std::max<uint64_t>(1u << 16, (uint64_t)n * 32), n_cells = 0;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if ((rc = ctx->m_cells.reserve((size_t)cap * 8))) return rc;
-            rc = compare_cells_run(ctx, [&]() { return compare_device_begin_impl(ctx, k, d_mn, d_lo, d_hi,
-                                                                                  sk_off.data(), n, n_query, 0, 1, ctx->c_inter.as<uint32_t>()); },
-                                   n, n_query < n ? n_query : n, ctx->c_inter.as<uint32_t>(), ctx->m_cells.as<uint64_t>(), cap, &n_cells, &ctx->m_cells);
-            if (rc != SPSP_ERR_OVERFLOW) break;
-            cap = n_cells;
-        }
-        if (rc) return rc;
+        uint64_t n_cells = 0;
+        if ((rc = compare_keys_cells(ctx, keys, n, n_query, &n_cells))) return rc;
         std::vector<uint64_t> cells((size_t)n_cells);
         if (n_cells) {
             SPSP_HIP(hipMemcpyAsync(cells.data(), ctx->m_cells.p, (size_t)n_cells * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -744,9 +740,9 @@ int compare_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const u
         if (mirrored) *mirrored = true;
         return SPSP_OK;
     }
+    if ((rc = ctx->c_inter.reserve((size_t)n * n * 4))) return rc;
     SPSP_HIP(hipMemsetAsync(ctx->c_inter.p, 0, (size_t)n * n * 4, ctx->stream));
-    if ((rc = compare_device_impl(ctx, k, d_mn, d_lo, d_hi,
-                                  sk_off.data(), n, n_query, 0, 1, ctx->c_inter.as<uint32_t>()))) return rc;
+    if ((rc = compare_device_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n, n_query, 0, 1, ctx->c_inter.as<uint32_t>()))) return rc;
     SPSP_HIP(hipMemcpyAsync(inter, ctx->c_inter.p, (size_t)n * n * 4, hipMemcpyDeviceToHost, ctx->stream));
     SPSP_HIP(hipStreamSynchronize(ctx->stream));
     return SPSP_OK;

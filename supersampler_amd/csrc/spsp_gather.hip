@@ -295,27 +295,43 @@ int gather_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const ui
 }
 
 int gather_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, uint32_t n_query, uint64_t min_keys,
-                         uint32_t max_rounds, uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_gather_row>* rows) {
-    const bool ds_on = ctx->ds_armed;
-    const uint64_t ds_threshold = ctx->ds_threshold;
-    ctx->ds_armed = false;
+                         uint32_t max_rounds, const uint64_t* ds_threshold, uint32_t* k_out, uint32_t* m_out, uint64_t* card,
+                         std::vector<spsp_gather_row>* rows) {
     rows->clear();
-    std::vector<uint64_t> sk_off((size_t)n + 1, 0);
-    int rc = sketch_decode_device_impl(ctx, payloads, lens, n, nullptr, nullptr, k_out, m_out, sk_off.data());
+    DecodedKeys keys;
+    const int rc = decode_keys_impl(ctx, payloads, lens, n, nullptr, nullptr, ds_threshold, &keys, card);
+    *k_out = keys.k; *m_out = keys.m;
     if (rc || n == 0) return rc;
-    const uint32_t k = *k_out;
-    const uint32_t* d_mn = ctx->c_min.as<uint32_t>();
-    const uint64_t* d_lo = ctx->c_lo.as<uint64_t>();
-    const uint64_t* d_hi = k > 32 ? ctx->c_hi.as<uint64_t>() : nullptr;
-    if (ds_on && sk_off[n]) {
-        uint32_t* f_mn = nullptr; uint64_t *f_lo = nullptr, *f_hi = nullptr;
-        std::vector<uint64_t> kept((size_t)n + 1, 0);
-        if ((rc = keys_downsample_impl(ctx, k, ds_threshold, d_mn, d_lo, d_hi, sk_off.data(), n, &f_mn, &f_lo, &f_hi, kept.data()))) return rc;
-        d_mn = f_mn; d_lo = f_lo; d_hi = f_hi;
-        sk_off.swap(kept);
+    return gather_device_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n, n_query, min_keys, max_rounds, rows);
+}
+
+// spsp_gather_files behind its argument checks: the sketches loaded (spsp_host.cpp), the gather, <out_prefix>_gather.csv.gz
+static int gather_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, uint64_t min_keys, uint32_t max_rounds,
+                        const char* out_prefix, int chatter, double rate, std::vector<spsp_gather_row>* rows) {
+    LoadedSketches L;
+    int rc = load_sketch_files(ctx, paths, n, rate, &L);
+    if (L.k && L.k == L.m) { set_error("gather is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
+    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
+    const double t0 = files_loaded(ctx, L, n, chatter);
+    uint32_t k = 0, m = 0;
+    std::vector<uint64_t> card(n, 0);
+    rc = gather_payloads_impl(ctx, L.data.data(), L.len.data(), n, n_query, min_keys, max_rounds, L.threshold(), &k, &m, card.data(), rows);
+    L.release();
+    const double t1 = now_s();
+    ctx->stages.compare_s += t1 - t0;
+    if (rc) return rc;
+    char* text = nullptr; uint64_t len = 0;
+    if ((rc = spsp_gather_csv_host(rows->data(), rows->size(), paths, n, n_query, card.data(), precision, &text, &len))) return rc;
+    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_gather.csv.gz", t1)) || !chatter) return rc;
+    size_t at = 0;
+    for (uint32_t q = 0; q < n_query; ++q) {
+        uint64_t named = 0, left = card[q];
+        for (; at < rows->size() && (*rows)[at].query == q; ++at) { ++named; left = (*rows)[at].remaining; }
+        printf("%s: %llu reference(s) named, %llu of %llu keys remain\n", paths[q], (unsigned long long)named, (unsigned long long)left, (unsigned long long)card[q]);
     }
-    for (uint32_t i = 0; i < n; ++i) card[i] = sk_off[i + 1] - sk_off[i];
-    return gather_device_impl(ctx, k, d_mn, d_lo, d_hi, sk_off.data(), n, n_query, min_keys, max_rounds, rows);
+    say_common_rate(L, n);
+    fflush(stdout);
+    return SPSP_OK;
 }
 
 }  // namespace spsp
@@ -346,15 +362,14 @@ extern "C" int spsp_gather_files(spsp_ctx* ctx, const char* const* paths, uint32
     if (n > 65535) { set_error("gather takes at most 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
     if (min_keys == 0) { set_error("min_keys must be >= 1"); return SPSP_ERR_ARG; }
     SPSP_HIP(hipSetDevice(ctx->device));
-    GatherReq G;
-    G.min_keys = min_keys; G.max_rounds = max_rounds; G.device_half = gather_payloads_impl;
-    const int rc = gather_files_impl(ctx, paths, n, n_query, precision, out_prefix, chatter, rate, &G);
+    std::vector<spsp_gather_row> got;
+    const int rc = gather_files(ctx, paths, n, n_query, precision, min_keys, max_rounds, out_prefix, chatter, rate, &got);
     if (rc) return rc;
-    if (n_rows) *n_rows = G.rows.size();
+    if (n_rows) *n_rows = got.size();
     if (rows) {
-        *rows = (spsp_gather_row*)malloc(G.rows.size() ? G.rows.size() * sizeof(spsp_gather_row) : 1);
+        *rows = (spsp_gather_row*)malloc(got.size() ? got.size() * sizeof(spsp_gather_row) : 1);
         if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        if (!G.rows.empty()) memcpy(*rows, G.rows.data(), G.rows.size() * sizeof(spsp_gather_row));
+        if (!got.empty()) memcpy(*rows, got.data(), got.size() * sizeof(spsp_gather_row));
     }
     return SPSP_OK;
 }

@@ -1522,25 +1522,21 @@ int spsp_stage_times_read(spsp_ctx* ctx, spsp_stage_times* out, int reset) {
     return SPSP_OK;
 }
 
-// chatter: 0 = silent; 1 = the stdout lines of the reference's all-versus-all run (Comparator.cpp:56,69,364,414,
-// 503,509); 2 = those of its query run (:56,69,364,414)
-// gather: instead of the comparison and its two matrices, the greedy gather of the first n_query sketches against the others
-// (GatherReq::device_half: spsp_gather.hip) and <out_prefix>_gather.csv.gz; everything in front of the comparison -- reading, inflating, the headers'
-// rates, the refusals -- is the same code
-// cluster: likewise, the single-linkage clusters of the n sketches (ClusterReq::device_half: spsp_cluster.hip) and <out_prefix>_clusters.csv.gz
-static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
-                              double min_threshold, const char* out_prefix, int chatter, double rate, spsp_ctx* const* more = nullptr, uint32_t n_more = 0,
-                              spsp::GatherReq* gather = nullptr, spsp::ClusterReq* cluster = nullptr) {
-    // more / n_more: all contexts of a multi-device call (more[0] == ctx): the comparison is then split by key over them
-    // rate: SPSP_RATE_AS_IS = the headers' rates are ignored, as the reference does; SPSP_RATE_COARSEST or a rate = every sketch
-    // is brought down to it on the device first
-    if (!ctx || !paths || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+}  // extern "C"
+
+namespace spsp {
+void LoadedSketches::release() {
+    for (size_t i = 0; i < data.size(); ++i) { if (own[i]) free(data[i]); data[i] = nullptr; }
+}
+
+int load_sketch_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, double rate, LoadedSketches* L) {
+    const double t0 = L->t0 = now_s();
     if (rate != SPSP_RATE_AS_IS && rate != SPSP_RATE_COARSEST && !(rate > 0)) { set_error("sampling rate %g: must be positive", rate); return SPSP_ERR_ARG; }
-    double t0 = now_s(), t1;
-    const double t_start = t0;
     ctx->stages.compare_calls += 1;
-    std::vector<uint8_t*> datas(n, nullptr);
-    std::vector<uint64_t> lens(n, 0);
+    L->data.assign(n, nullptr); L->len.assign(n, 0); L->own.assign(n, 1);
+    std::vector<uint8_t*>& datas = L->data;
+    std::vector<uint64_t>& lens = L->len;
+    std::vector<uint8_t>& own = L->own;
     std::vector<int> rcs(n, SPSP_OK);
     std::vector<std::string> errs(n);
     // Many sketch files: every reader thread takes a RANGE of the files and lays their payloads down back to back (each at the
@@ -1550,8 +1546,6 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
     // tools/exp/open_scaling.sh), the inflating does -- so a file is inflated by the thread that read it while the others wait for
     // the kernel (two passes, all reads then all inflates into one block by the trailers' lengths, were 13 + 12 ms).
     // datas[i] then points INTO a region (own[i] == 0).
-    std::vector<uint8_t> own(n, 1);
-    auto free_datas = [&]() { for (uint32_t i = 0; i < n; ++i) { if (own[i]) free(datas[i]); datas[i] = nullptr; } };   // (the regions stay with the context)
     unsigned workers = std::thread::hardware_concurrency();
     if (workers == 0) workers = 1;
     if (workers > 16) workers = 16;
@@ -1656,129 +1650,116 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
         if (!nl || skm <= 0 || skm > 126 || mm <= 0 || mm > 15 || (skm + mm) / 2 > 63 || (skm + mm) / 2 < mm) { set_error("bad sketch header in '%s'", paths[0]); rc = SPSP_ERR_FORMAT; }
         else { m0 = (uint32_t)mm; k0 = (uint32_t)((skm + mm) / 2); }
     }
-    if (!rc && n && gather && k0 == m0) { set_error("gather is not defined for k == m sketches (k = m = %u)", k0); rc = SPSP_ERR_ARG; }
-    if (!rc && n && cluster && k0 == m0) { set_error("clustering is not defined for k == m sketches (k = m = %u)", k0); rc = SPSP_ERR_ARG; }
+    L->k = k0; L->m = m0;
     // the merge's shared first-read buffer, in file order (see spsp_sketch_chain_host): phantom keys of empty sketches
-    std::vector<int> extra_has(n, 0);
-    std::vector<uint32_t> extra_mn(n, 0);
+    L->extra_has.assign(n, 0); L->extra_mn.assign(n, 0);
     if (!rc && n) {
         char buffer[16];
         memset(buffer, 'A', sizeof buffer);
         for (uint32_t i = 0; i < n && !rc; ++i) {
             int has = 0; uint32_t mn = 0; uint64_t lo = 0, hi = 0;
             rc = spsp_sketch_chain_host(datas[i], lens[i], k0, m0, buffer, &has, &mn, &lo, &hi);
-            if (!rc && has) { extra_has[i] = 1; extra_mn[i] = mn; }
+            if (!rc && has) { L->extra_has[i] = 1; L->extra_mn[i] = mn; }
         }
     }
     if (load_times) fprintf(stderr, "[load] ... with the first-read chain %.4f s\n", now_s() - t0);
     // a common sampling rate: the headers' rates (read here, where the payloads lie anyway), as the thresholds they stand for
-    bool ds_on = false;
-    uint64_t ds_thr = 0;
-    double ds_rate = 0;
-    uint32_t ds_brought = 0;
-    if (!rc && n && rate != SPSP_RATE_AS_IS) {
+    L->rate_asked = rate != SPSP_RATE_AS_IS;
+    if (!rc && n && L->rate_asked) {
         if (k0 == m0) { set_error("a common sampling rate cannot be applied to k == m sketches (k = m = %u)", k0); rc = SPSP_ERR_ARG; }
         std::vector<uint64_t> thr(n, 0);
-        std::vector<double> own(n, 0);
+        std::vector<double> rates(n, 0);
         double last_rate = 0; uint64_t last_thr = 0; bool have_last = false;
         for (uint32_t i = 0; i < n && !rc; ++i) {
             uint32_t ki = 0, mi = 0; uint64_t cnt = 0;
-            rc = sketch_header_fields(datas[i], lens[i], &ki, &mi, &cnt, &own[i], nullptr);
+            rc = sketch_header_fields(datas[i], lens[i], &ki, &mi, &cnt, &rates[i], nullptr);
             if (rc) { const std::string why = spsp_last_error(); set_error("'%s': %s", paths[i], why.c_str()); break; }
             if (ki != k0 || mi != m0) { set_error("'%s' was made with k=%u m=%u, the first sketch with k=%u m=%u", paths[i], ki, mi, k0, m0); rc = SPSP_ERR_FORMAT; break; }
-            if (!have_last || own[i] != last_rate) { last_rate = own[i]; last_thr = spsp_threshold_host(k0, m0, own[i]); have_last = true; }   // (powl once per run of equal rates)
+            if (!have_last || rates[i] != last_rate) { last_rate = rates[i]; last_thr = spsp_threshold_host(k0, m0, rates[i]); have_last = true; }   // (powl once per run of equal rates)
             thr[i] = last_thr;
         }
         if (!rc) {
             if (rate == SPSP_RATE_COARSEST) {
                 uint32_t at = 0;
                 for (uint32_t i = 1; i < n; ++i) if (thr[i] < thr[at]) at = i;
-                ds_thr = thr[at]; ds_rate = own[at];
-            } else { ds_thr = spsp_threshold_host(k0, m0, rate); ds_rate = rate; }
+                L->ds_threshold = thr[at]; L->ds_rate = rates[at];
+            } else { L->ds_threshold = spsp_threshold_host(k0, m0, rate); L->ds_rate = rate; }
             for (uint32_t i = 0; i < n && !rc; ++i) {
-                if (thr[i] < ds_thr) { set_error("cannot upsample: '%s' was sketched at rate %g, coarser than the common rate %g", paths[i], own[i], ds_rate); rc = SPSP_ERR_ARG; }
-                else if (thr[i] > ds_thr) ++ds_brought;
+                if (thr[i] < L->ds_threshold) { set_error("cannot upsample: '%s' was sketched at rate %g, coarser than the common rate %g", paths[i], rates[i], L->ds_rate); rc = SPSP_ERR_ARG; }
+                else if (thr[i] > L->ds_threshold) ++L->ds_brought;
             }
-            ds_on = !rc && ds_brought > 0;                         // (every sketch already there: no pass)
+            L->ds_on = !rc && L->ds_brought > 0;                   // (every sketch already there: no pass)
         }
     }
+    return rc;
+}
+
+double files_loaded(spsp_ctx* ctx, const LoadedSketches& L, uint32_t n, int chatter) {
+    if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", L.k, L.m); fflush(stdout); }   // :56
+    const double t = now_s();
+    ctx->stages.load_s += t - L.t0;
+    return t;
+}
+
+int write_csv_gz(spsp_ctx* ctx, char* text, uint64_t len, const char* out_prefix, const char* suffix, double t_csv) {
+    const double t = now_s();
+    ctx->stages.csv_s += t - t_csv;
+    const int rc = spsp_write_gz_host((std::string(out_prefix) + suffix).c_str(), (const uint8_t*)text, len, 1);   // level 1: Comparator.cpp:363,413
+    ctx->stages.csv_gzip_s += now_s() - t;
+    free(text);
+    return rc;
+}
+
+void say_common_rate(const LoadedSketches& L, uint32_t n) {
+    if (n && L.rate_asked) { printf("Sketches compared at sampling rate %g: %u of %u brought down to it\n", L.ds_rate, L.ds_brought, n); fflush(stdout); }
+}
+}  // namespace spsp
+
+namespace {
+int clamp_chatter(int chatter) { return chatter < 0 ? 0 : (chatter > 2 ? 2 : chatter); }
+
+// a CSV writer's text as the caller's to spsp_free
+int text_out(const std::string& out, char** text, uint64_t* len) {
+    char* buf = (char*)malloc(out.size() ? out.size() : 1);
+    if (!buf) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    memcpy(buf, out.data(), out.size());
+    *text = buf; *len = out.size();
+    return SPSP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// chatter: 0 = silent; 1 = the stdout lines of the reference's all-versus-all run (Comparator.cpp:56,69,364,414,
+// 503,509); 2 = those of its query run (:56,69,364,414)
+// more / n_more: all contexts of a multi-device call (more[0] == ctx): the comparison is then split by key over them
+// rate: as load_sketch_files takes it
+static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
+                              double min_threshold, const char* out_prefix, int chatter, double rate, spsp_ctx* const* more = nullptr, uint32_t n_more = 0) {
+    if (!ctx || !paths || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    spsp::LoadedSketches L;
+    int rc = spsp::load_sketch_files(ctx, paths, n, rate, &L);
+    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
+    double t0 = spsp::files_loaded(ctx, L, n, chatter), t1;
     // the pair matrix: zero pages from calloc (400 MB at 10^4 sketches: touched only where a row is written or read)
     struct Matrix { uint32_t* p = nullptr; ~Matrix() { free(p); } uint32_t* data() { return p; }
                     int zero(size_t cells) { free(p); p = (uint32_t*)calloc(cells ? cells : 1, 4); return p ? SPSP_OK : SPSP_ERR_NOMEM; } } inter;
     bool mirrored = false;                                    // both triangles filled
     std::vector<uint64_t> cells;                              // ... or no matrix at all: a large comparison comes back as its non-zero cells
-    bool as_cells = false;
+    const bool as_cells = n >= 1024 && n <= 65535;            // (the printers then work from the cells: no n x n matrix on the host)
     std::vector<uint64_t> card(n, 0);
-    if (!rc && gather) {
-        if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }
-        t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
-        uint32_t kk = 0, mm2 = 0;
-        ctx->ds_armed = ds_on; ctx->ds_threshold = ds_thr;     // (read and cleared by the call below)
-        rc = gather->device_half(ctx, datas.data(), lens.data(), n, n_query, gather->min_keys, gather->max_rounds, &kk, &mm2, card.data(), &gather->rows);
-        free_datas();
-        t1 = now_s(); ctx->stages.compare_s += t1 - t0; t0 = t1;
-        if (rc) return rc;
-        char* text = nullptr; uint64_t len = 0;
-        if ((rc = spsp_gather_csv_host(gather->rows.data(), gather->rows.size(), paths, n, n_query, card.data(), precision, &text, &len))) return rc;
-        t1 = now_s(); ctx->stages.csv_s += t1 - t0;
-        rc = spsp_write_gz_host((std::string(out_prefix) + "_gather.csv.gz").c_str(), (const uint8_t*)text, len, 1);
-        ctx->stages.csv_gzip_s += now_s() - t1;
-        free(text);
-        if (!rc && chatter) {
-            size_t at = 0;
-            for (uint32_t q = 0; q < n_query && q < n; ++q) {
-                uint64_t named = 0, left = card[q];
-                for (; at < gather->rows.size() && gather->rows[at].query == q; ++at) { ++named; left = gather->rows[at].remaining; }
-                printf("%s: %llu reference(s) named, %llu of %llu keys remain\n", paths[q], (unsigned long long)named, (unsigned long long)left, (unsigned long long)card[q]);
-            }
-            if (n && rate != SPSP_RATE_AS_IS) printf("Sketches compared at sampling rate %g: %u of %u brought down to it\n", ds_rate, ds_brought, n);
-            fflush(stdout);
-        }
-        return rc;
-    }
-    if (!rc && cluster) {
-        if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }
-        t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
-        uint32_t kk = 0, mm2 = 0;
-        ctx->ds_armed = ds_on; ctx->ds_threshold = ds_thr;     // (read and cleared by the call below)
-        rc = cluster->device_half(ctx, datas.data(), lens.data(), n, cluster->metric, cluster->num, cluster->den, &kk, &mm2, card.data(), &cluster->rows,
-                                  &cluster->n_clusters, &cluster->n_edges);
-        free_datas();
-        t1 = now_s(); ctx->stages.compare_s += t1 - t0; t0 = t1;
-        if (rc) return rc;
-        char* text = nullptr; uint64_t len = 0;
-        if ((rc = spsp_cluster_csv_host(cluster->rows.data(), paths, n, card.data(), cluster->metric, precision, &text, &len))) return rc;
-        t1 = now_s(); ctx->stages.csv_s += t1 - t0;
-        rc = spsp_write_gz_host((std::string(out_prefix) + "_clusters.csv.gz").c_str(), (const uint8_t*)text, len, 1);
-        ctx->stages.csv_gzip_s += now_s() - t1;
-        free(text);
-        if (!rc && chatter) {
-            uint32_t largest = 0;
-            for (const spsp_cluster_row& r : cluster->rows) largest = std::max(largest, r.size);
-            printf("%u sketches, %llu edges, %llu clusters, the largest of %u\n", n, (unsigned long long)cluster->n_edges, (unsigned long long)cluster->n_clusters, largest);
-            if (n && rate != SPSP_RATE_AS_IS) printf("Sketches compared at sampling rate %g: %u of %u brought down to it\n", ds_rate, ds_brought, n);
-            fflush(stdout);
-        }
-        return rc;
-    }
-    if (!rc) {
-        if (chatter && n) { printf("kmers evaluated are of length: %u minimizer size is %u\n", k0, m0); fflush(stdout); }   // :56
-        t1 = now_s(); ctx->stages.load_s += t1 - t0; t0 = t1;
-        uint32_t kk = 0, mm2 = 0;
-        as_cells = n >= 1024 && n <= 65535;                    // (the printers then work from the cells: no n x n matrix on the host)
-        ctx->ds_armed = ds_on; ctx->ds_threshold = ds_thr;     // (read and cleared by the call below)
-        if (!as_cells && (rc = inter.zero((size_t)n * n))) { ctx->ds_armed = false; set_error("out of host memory"); }
-        else if (n_more > 1) rc = spsp::compare_payloads_multi(more, n_more, datas.data(), lens.data(), n, extra_has.data(), extra_mn.data(), n_query, &kk, &mm2,
-                                                               inter.data(), card.data(), &mirrored, as_cells ? &cells : nullptr);
-        else rc = spsp::compare_payloads_impl(ctx, datas.data(), lens.data(), n, extra_has.data(), extra_mn.data(), n_query, &kk, &mm2,
-                                              inter.data(), card.data(), &mirrored, as_cells ? &cells : nullptr);
-    }
-    free_datas();
+    uint32_t kk = 0, mm2 = 0;
+    if (!as_cells && (rc = inter.zero((size_t)n * n))) set_error("out of host memory");
+    else if (n_more > 1) rc = spsp::compare_payloads_multi(more, n_more, L.data.data(), L.len.data(), n, L.extra_has.data(), L.extra_mn.data(), n_query, L.threshold(),
+                                                           &kk, &mm2, inter.data(), card.data(), &mirrored, as_cells ? &cells : nullptr);
+    else rc = spsp::compare_payloads_impl(ctx, L.data.data(), L.len.data(), n, L.extra_has.data(), L.extra_mn.data(), n_query, L.threshold(), &kk, &mm2,
+                                          inter.data(), card.data(), &mirrored, as_cells ? &cells : nullptr);
+    L.release();
     t1 = now_s(); ctx->stages.compare_s += t1 - t0;
     if (rc) return rc;
     if (chatter) {
         printf("Comparisons done\n");                                                         // :69
-        if (chatter == 1) std::cout << "Comparisons lasted " << (t1 - t_start) << " sec" << std::endl;   // :503 (cout's default float format)
+        if (chatter == 1) std::cout << "Comparisons lasted " << (t1 - L.t0) << " sec" << std::endl;   // :503 (cout's default float format)
         fflush(stdout);
     }
     const double t_middle = t1;
@@ -1786,25 +1767,20 @@ static int compare_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t 
         char* text = nullptr; uint64_t len = 0;
         t0 = now_s();
         if (chatter) { printf(jac ? "Jackard index dump\n" : "Containement index dump \n"); fflush(stdout); }   // :364, :414
-        const std::string out_gz = std::string(out_prefix) + (jac ? "_jaccard.csv.gz" : "_containment.csv.gz");
+        const char* suffix = jac ? "_jaccard.csv.gz" : "_containment.csv.gz";
         if (as_cells) {
             // rows formatted from the cells and deflated block by block on the workers, level 1 (Comparator.cpp:363,413)
             double tt[2] = {0, 0};
-            rc = csv_cells_impl(jac, paths, n, n_query, cells, card.data(), precision, min_threshold, nullptr, nullptr, out_gz.c_str(), 1, tt);
+            rc = csv_cells_impl(jac, paths, n, n_query, cells, card.data(), precision, min_threshold, nullptr, nullptr, (std::string(out_prefix) + suffix).c_str(), 1, tt);
             ctx->stages.csv_s += tt[0]; ctx->stages.csv_gzip_s += tt[1];
             continue;
         }
         rc = csv_impl(jac, paths, n, n_query, inter.data(), card.data(), precision, min_threshold, &text, &len, mirrored);
-        t1 = now_s(); ctx->stages.csv_s += t1 - t0;
-        if (rc) break;
-        const std::string out = std::string(out_prefix) + (jac ? "_jaccard.csv.gz" : "_containment.csv.gz");
-        rc = spsp_write_gz_host(out.c_str(), (const uint8_t*)text, len, 1);  // level 1: Comparator.cpp:363,413
-        ctx->stages.csv_gzip_s += now_s() - t1;
-        free(text);
+        if (rc) { ctx->stages.csv_s += now_s() - t0; break; }
+        rc = spsp::write_csv_gz(ctx, text, len, out_prefix, suffix, t0);
     }
     if (!rc && chatter == 1) std::cout << "Jaccard output lasted " << (now_s() - t_middle) << " sec" << std::endl;   // :509
-    // (not the reference's: behind its own lines, and only when a common rate was asked for)
-    if (!rc && chatter && n && rate != SPSP_RATE_AS_IS) { printf("Sketches compared at sampling rate %g: %u of %u brought down to it\n", ds_rate, ds_brought, n); fflush(stdout); }
+    if (!rc && chatter) spsp::say_common_rate(L, n);
     return rc;
 }
 
@@ -1825,11 +1801,7 @@ int spsp_gather_csv_host(const spsp_gather_row* rows, uint64_t n_rows, const cha
         out.append(num, format_g(num, sizeof num, precision, (double)r.intersect / (double)card[r.match])); out += ',';
         out += std::to_string(r.remaining); out += '\n';
     }
-    char* buf = (char*)malloc(out.size() ? out.size() : 1);
-    if (!buf) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-    memcpy(buf, out.data(), out.size());
-    *text = buf; *len = out.size();
-    return SPSP_OK;
+    return text_out(out, text, len);
 }
 
 int spsp_cluster_csv_host(const spsp_cluster_row* rows, const char* const* names, uint32_t n, const uint64_t* card, int metric, int precision,
@@ -1858,16 +1830,12 @@ int spsp_cluster_csv_host(const spsp_cluster_row* rows, const char* const* names
         out += std::to_string(r.shared); out += ',';
         out.append(num, format_g(num, sizeof num, precision, score)); out += '\n';
     }
-    char* buf = (char*)malloc(out.size() ? out.size() : 1);
-    if (!buf) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-    memcpy(buf, out.data(), out.size());
-    *text = buf; *len = out.size();
-    return SPSP_OK;
+    return text_out(out, text, len);
 }
 
 int spsp_compare_files_rate(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, double min_threshold,
                             const char* out_prefix, int chatter, double rate) {
-    return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, chatter < 0 ? 0 : (chatter > 2 ? 2 : chatter), rate);
+    return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, clamp_chatter(chatter), rate);
 }
 int spsp_compare_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision,
                        double min_threshold, const char* out_prefix) {
@@ -1898,7 +1866,7 @@ int spsp_compare_files_multi_rate(const int* devices, uint32_t n_dev, const char
         rc = spsp_create(devices[d], nullptr, &c);
         if (!rc) ctxs.push_back(c);
     }
-    if (!rc) rc = compare_files_impl(ctxs[0], paths, n, n_query, precision, min_threshold, out_prefix, chatter < 0 ? 0 : (chatter > 2 ? 2 : chatter), rate, ctxs.data(), (uint32_t)ctxs.size());
+    if (!rc) rc = compare_files_impl(ctxs[0], paths, n, n_query, precision, min_threshold, out_prefix, clamp_chatter(chatter), rate, ctxs.data(), (uint32_t)ctxs.size());
     if (!rc && times) *times = ctxs[0]->stages;
     const std::string err = rc ? spsp_last_error() : "";
     for (spsp_ctx* c : ctxs) spsp_destroy(c);
@@ -1907,14 +1875,3 @@ int spsp_compare_files_multi_rate(const int* devices, uint32_t n_dev, const char
 }
 
 }  // extern "C"
-
-namespace spsp {
-int gather_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, const char* out_prefix, int chatter,
-                      double rate, GatherReq* G) {
-    return compare_files_impl(ctx, paths, n, n_query, precision, 0.0, out_prefix, chatter ? 2 : 0, rate, nullptr, 0, G);
-}
-int cluster_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, const char* out_prefix, int chatter, double rate,
-                       ClusterReq* Q) {
-    return compare_files_impl(ctx, paths, n, n, precision, 0.0, out_prefix, chatter ? 1 : 0, rate, nullptr, 0, nullptr, Q);
-}
-}  // namespace spsp

@@ -232,8 +232,6 @@ struct spsp_ctx {
     spsp::DevBuf g_off, g_u, g_roff, g_rfill, g_qcnt, g_qoff, g_edges, g_byref, g_hold, g_count, g_state, g_rows;
     // clustering (spsp_cluster.hip): the per-sketch arrays and the counter words in one work area, the rows
     spsp::DevBuf cl_work, cl_rows;
-    bool ds_armed = false;             // the next compare_payloads_impl / _multi call brings the decoded keys down to ds_threshold first
-    uint64_t ds_threshold = 0;
 };
 
 namespace spsp {
@@ -284,58 +282,74 @@ struct ParsedSketch {
 };
 // structure of one payload: header + bucket boundaries + line ends (spsp_host.cpp: pure host code, fuzzed under ASan)
 int sketch_parse_structure_host(const uint8_t* payload, uint64_t len, ParsedSketch* P);
-// decode on the GPU + all-vs-all + copy back: the device half of spsp_compare_files (spsp_decode.hip)
-// (inter: n x n, zero on entry; *mirrored = every written cell (i, j > i) was also stored at (j, i))
-// (here and in compare_payloads_multi: with ctx->ds_armed -- ctxs[0]'s there -- the decoded keys are brought down to the selection
-// threshold ctx->ds_threshold on the device before they are compared / dealt into exchange slots; card = the surviving keys.
-// The request holds for that one call.)
-int compare_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, const int* extra_has,
-                          const uint32_t* extra_mn, uint32_t n_query, uint32_t* k_out, uint32_t* m_out, uint32_t* inter, uint64_t* card,
-                          bool* mirrored = nullptr, std::vector<uint64_t>* cells_out = nullptr);
 // spsp_downsample.hip: the keys whose minimizer's hash is <= threshold, sketches back to back, order kept, in context-owned arrays
 int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
                          const uint64_t* h_sk_off, uint32_t n, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out);
+// the sorted distinct keys of n sketch payloads on the device, sketches back to back: the decoder's arrays, or the downsampling
+// pass's (spsp_decode.hip).  ds_threshold: null = the keys as the files hold them; else only the keys whose minimizer passes that
+// selection threshold, brought down on the device behind the decoder.  card[i] = the keys of sketch i that are left
+struct DecodedKeys {
+    uint32_t k = 0, m = 0;
+    const uint32_t* mn = nullptr;
+    const uint64_t *lo = nullptr, *hi = nullptr;                   // hi: null unless k > 32
+    std::vector<uint64_t> sk_off;
+};
+int decode_keys_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, const int* extra_has, const uint32_t* extra_mn,
+                     const uint64_t* ds_threshold, DecodedKeys* keys, uint64_t* card);
+// decode_keys_impl + all-vs-all + copy back: the device half of spsp_compare_files (spsp_decode.hip)
+// (inter: n x n, zero on entry; *mirrored = every written cell (i, j > i) was also stored at (j, i))
+// (cells_out, for 1024 <= n <= 65535: the non-zero cells i << 48 | j << 32 | count, every pair once, INSTEAD of the matrix: inter may be null)
+int compare_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, const int* extra_has,
+                          const uint32_t* extra_mn, uint32_t n_query, const uint64_t* ds_threshold, uint32_t* k_out, uint32_t* m_out, uint32_t* inter,
+                          uint64_t* card, bool* mirrored = nullptr, std::vector<uint64_t>* cells_out = nullptr);
 // spsp_gather.hip: greedy gather of the first n_query sketches against the others over concatenated sorted key arrays; rows ordered by
-// (query, rank).  gather_payloads_impl: decode (+ the downsampling pass when ctx->ds_armed, as compare_payloads_impl) + gather;
-// card = the key counts the gather saw
+// (query, rank).  gather_payloads_impl: decode_keys_impl + gather; card = the key counts the gather saw
 int gather_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
                        uint32_t n, uint32_t nq, uint64_t min_keys, uint32_t max_rounds, std::vector<spsp_gather_row>* rows);
-// spsp_gather_files: the request that travels through the comparator's file driver (spsp_host.cpp: reading, inflating, the headers'
-// rates and the refusals are compare_files_impl's); device_half is gather_payloads_impl -- a pointer, so that the host translation
-// unit links without the device code (the sanitizer harness builds it alone)
-struct GatherReq {
-    uint64_t min_keys = 1;
-    uint32_t max_rounds = 0;
-    std::vector<spsp_gather_row> rows;
-    int (*device_half)(spsp_ctx*, const uint8_t* const*, const uint64_t*, uint32_t, uint32_t, uint64_t, uint32_t, uint32_t*, uint32_t*, uint64_t*,
-                       std::vector<spsp_gather_row>*) = nullptr;
-};
-int gather_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, const char* out_prefix, int chatter,
-                      double rate, GatherReq* G);
 int gather_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, uint32_t n_query, uint64_t min_keys,
-                         uint32_t max_rounds, uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_gather_row>* rows);
+                         uint32_t max_rounds, const uint64_t* ds_threshold, uint32_t* k_out, uint32_t* m_out, uint64_t* card,
+                         std::vector<spsp_gather_row>* rows);
 // spsp_cluster.hip: single-linkage clusters of the sketches 0 .. n-1 from the packed cells of their pair matrix (on the device, only
-// read); cluster_payloads_impl: decode (+ the downsampling pass when ctx->ds_armed) + the all-vs-all as cells + the cluster pass:
-// the cells stay on the device; card = the key counts the comparison saw
+// read); cluster_payloads_impl: decode_keys_impl + the all-vs-all as cells + the cluster pass: the cells stay on the device;
+// card = the key counts the comparison saw
 int cluster_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n, int metric, uint32_t num,
                        uint32_t den, spsp_cluster_row* rows, uint64_t* n_clusters, uint64_t* n_edges);
 int cluster_check_args(uint32_t n, int metric, uint32_t num, uint32_t den);
-// spsp_cluster_files: the request that travels through the comparator's file driver, as GatherReq does (device_half is
-// cluster_payloads_impl -- a pointer, so that the host translation unit links without the device code)
-struct ClusterReq {
-    int metric = 0;
-    uint32_t num = 1, den = 1;
-    std::vector<spsp_cluster_row> rows;
-    uint64_t n_clusters = 0, n_edges = 0;
-    int (*device_half)(spsp_ctx*, const uint8_t* const*, const uint64_t*, uint32_t, int, uint32_t, uint32_t, uint32_t*, uint32_t*, uint64_t*,
-                       std::vector<spsp_cluster_row>*, uint64_t*, uint64_t*) = nullptr;
-};
-int cluster_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, const char* out_prefix, int chatter, double rate,
-                       ClusterReq* Q);
 int cluster_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, int metric, uint32_t num, uint32_t den,
-                          uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_cluster_row>* rows, uint64_t* n_clusters,
-                          uint64_t* n_edges);
-// (cells_out, for 1024 <= n <= 65535: the non-zero cells i << 48 | j << 32 | count, every pair once, INSTEAD of the matrix: inter may be null)
+                          const uint64_t* ds_threshold, uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_cluster_row>* rows,
+                          uint64_t* n_clusters, uint64_t* n_edges);
+// the front half of every file driver (spsp_host.cpp): the payloads of n sketch files, in file order, and what their headers say
+struct LoadedSketches {
+    std::vector<uint8_t*> data;                                    // into the context's read regions, or owned (own[i])
+    std::vector<uint64_t> len;
+    std::vector<uint8_t> own;
+    uint32_t k = 0, m = 0;                                         // of the first header (0 until it has been read)
+    std::vector<int> extra_has;                                    // the first-read chain (spsp_sketch_chain_host)
+    std::vector<uint32_t> extra_mn;
+    // a common sampling rate was asked for (rate_asked): the rate, its selection threshold, the sketches finer than it, and whether
+    // there are any (ds_on: the device has something to bring down)
+    bool rate_asked = false, ds_on = false;
+    uint64_t ds_threshold = 0;
+    double ds_rate = 0;
+    uint32_t ds_brought = 0;
+    double t0 = 0;                                                 // when the loading began
+    const uint64_t* threshold() const { return ds_on ? &ds_threshold : nullptr; }   // what the *_payloads_impl take
+    void release();                                                // frees the payloads it owns (the regions stay with the context)
+    LoadedSketches() = default;
+    LoadedSketches(const LoadedSketches&) = delete;
+    LoadedSketches& operator=(const LoadedSketches&) = delete;
+    ~LoadedSketches() { release(); }
+};
+// rate: SPSP_RATE_AS_IS = the headers' rates are ignored, as the reference does; SPSP_RATE_COARSEST or a rate = every header's rate
+// is read and held against it (a coarser sketch is refused), and the device half is to bring the finer ones down
+int load_sketch_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, double rate, LoadedSketches* L);
+// what the file drivers' tails share (spsp_host.cpp).  files_loaded: the reference's first line (Comparator.cpp:56) and the
+// loading booked to load_s; returns the time the device half starts at
+double files_loaded(spsp_ctx* ctx, const LoadedSketches& L, uint32_t n, int chatter);
+// text (taken over: freed here) -> <out_prefix><suffix> at gzip level 1; csv_s is booked from t_csv to here, csv_gzip_s from here on
+int write_csv_gz(spsp_ctx* ctx, char* text, uint64_t len, const char* out_prefix, const char* suffix, double t_csv);
+// the line that names the common rate, where one was asked for (not the reference's: behind its own lines)
+void say_common_rate(const LoadedSketches& L, uint32_t n);
 int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
                               const int* extra_has, const uint32_t* extra_mn, uint32_t* k_out, uint32_t* m_out, uint64_t* sk_off);
 // ingest (spsp_ingest.hip)
@@ -405,10 +419,14 @@ int matrix_cells_impl(spsp_ctx* ctx, const uint32_t* d_inter, uint32_t n, uint32
 // it (d_scratch then stays unwritten), else through the dense matrix in d_scratch (n x n uint32) and k_matrix_cells
 int compare_cells_run(spsp_ctx* ctx, const std::function<int()>& begin, uint32_t n, uint32_t row_limit, uint32_t* d_scratch, uint64_t* d_cells,
                       uint64_t cap, uint64_t* n_cells, DevBuf* grow = nullptr);
+// the all-vs-all of decoded keys as cells in ctx->m_cells (rows below row_limit): room for max(2^16, 32 n) cells first, and once
+// more with the exact room where that was too little
+int compare_keys_cells(spsp_ctx* ctx, const DecodedKeys& keys, uint32_t n, uint32_t row_limit, uint64_t* n_cells);
 // decode + all-vs-all over several contexts (one per device, or several on one): the device half of spsp_compare_files_multi
+// (ds_threshold as in decode_keys_impl: every context brings its own block down before the keys are dealt into exchange slots)
 int compare_payloads_multi(spsp_ctx* const* ctxs, uint32_t n_ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
-                           const int* extra_has, const uint32_t* extra_mn, uint32_t n_query, uint32_t* k_out, uint32_t* m_out,
-                           uint32_t* inter, uint64_t* card, bool* mirrored = nullptr, std::vector<uint64_t>* cells_out = nullptr);
+                           const int* extra_has, const uint32_t* extra_mn, uint32_t n_query, const uint64_t* ds_threshold, uint32_t* k_out,
+                           uint32_t* m_out, uint32_t* inter, uint64_t* card, bool* mirrored = nullptr, std::vector<uint64_t>* cells_out = nullptr);
 // spsp_bigkeys.hip: distinct keys of flagged segments through one table in HBM (queued, no host wait); segments sorted in place
 int big_dedupe_launch(spsp_ctx* ctx, bool has_hi, const uint32_t* raw_mn, const uint64_t* raw_lo, const uint64_t* raw_hi,
                       const uint32_t* d_seg_first, const uint32_t* d_seg_cnt, const uint32_t* d_seg_big, uint32_t n_seg, uint64_t n_places,

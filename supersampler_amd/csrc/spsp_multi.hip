@@ -147,6 +147,23 @@ int compare_cells_run(spsp_ctx* ctx, const std::function<int()>& begin, uint32_t
     return SPSP_OK;
 }
 
+int compare_keys_cells(spsp_ctx* ctx, const DecodedKeys& keys, uint32_t n, uint32_t row_limit, uint64_t* n_cells) {
+    int rc;
+    if ((rc = ctx->c_inter.reserve((size_t)n * n * 4))) return rc;
+    uint32_t* d_scratch = ctx->c_inter.as<uint32_t>();
+    uint64_t cap = std::max<uint64_t>(1u << 16, (uint64_t)n * 32);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if ((rc = ctx->m_cells.reserve((size_t)cap * 8))) return rc;
+        // (below 1024 sketches compare_cells_run goes through the dense scratch matrix where the form needs it: zero on entry)
+        if (n < 1024) SPSP_HIP(hipMemsetAsync(d_scratch, 0, (size_t)n * n * 4, ctx->stream));
+        rc = compare_cells_run(ctx, [&]() { return compare_device_begin_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n, row_limit, 0, 1, d_scratch); },
+                               n, std::min(row_limit, n), d_scratch, ctx->m_cells.as<uint64_t>(), cap, n_cells, &ctx->m_cells);
+        if (rc != SPSP_ERR_OVERFLOW) break;
+        cap = *n_cells;                                            // more cells than the room first offered: repeated with the exact room
+    }
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Receiver of the key-partitioned split.  The slot headers (magic, geometry, keys per sketch) go to the host first: the
 // flat form needs the sketch offsets there, and a malformed or overflowed slot is refused before any kernel reads it.
@@ -238,11 +255,8 @@ int run_stage(uint32_t n_ctx, MultiShared& S, F&& body) {
 }  // namespace
 
 int compare_payloads_multi(spsp_ctx* const* ctxs, uint32_t n_ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
-                           const int* extra_has, const uint32_t* extra_mn, uint32_t n_query, uint32_t* k_out, uint32_t* m_out,
-                           uint32_t* inter, uint64_t* card, bool* mirrored, std::vector<uint64_t>* cells_out) {
-    const bool ds_on = n_ctx && ctxs[0]->ds_armed;
-    const uint64_t ds_threshold = n_ctx ? ctxs[0]->ds_threshold : 0;
-    if (n_ctx) ctxs[0]->ds_armed = false;
+                           const int* extra_has, const uint32_t* extra_mn, uint32_t n_query, const uint64_t* ds_threshold, uint32_t* k_out,
+                           uint32_t* m_out, uint32_t* inter, uint64_t* card, bool* mirrored, std::vector<uint64_t>* cells_out) {
     if (mirrored) *mirrored = false;
     if (cells_out) cells_out->clear();
     if (n_ctx == 0 || n_ctx > kMaxParts) { set_error("1..%u contexts", kMaxParts); return SPSP_ERR_ARG; }
@@ -258,9 +272,7 @@ int compare_payloads_multi(spsp_ctx* const* ctxs, uint32_t n_ctx, const uint8_t*
     if (NP > 65535) { set_error("at most 65535 sketches (the reference's uint32 pair key, Comparator.h:26)"); return SPSP_ERR_ARG; }
     S.sk_off.assign(n_ctx, std::vector<uint64_t>((size_t)S.per + 1, 0));
     S.rc.assign(n_ctx, SPSP_OK); S.err.assign(n_ctx, std::string());
-    std::vector<uint32_t> ks(n_ctx, 0), ms(n_ctx, 0);
-    struct Keys { const uint32_t* mn = nullptr; const uint64_t *lo = nullptr, *hi = nullptr; };
-    std::vector<Keys> keys(n_ctx);                                  // what every context deals into the slots: its decoded keys, or those brought down
+    std::vector<DecodedKeys> keys(n_ctx);                           // what every context deals into the slots: its decoded keys, or those brought down
     // (inter is zero on entry)
     // peers: every context's device reads the others' slots
     for (uint32_t a = 0; a < n_ctx; ++a)
@@ -277,32 +289,21 @@ int compare_payloads_multi(spsp_ctx* const* ctxs, uint32_t n_ctx, const uint8_t*
         spsp_ctx* c = ctxs[d];
         SPSP_HIP(hipSetDevice(c->device));
         const uint32_t b0 = std::min<uint64_t>((uint64_t)d * S.per, n), b1 = std::min<uint64_t>((uint64_t)(d + 1) * S.per, n);
-        std::vector<uint64_t> off((size_t)(b1 - b0) + 1, 0);
-        if (b1 > b0) {
-            const int r = sketch_decode_device_impl(c, payloads + b0, lens + b0, b1 - b0, extra_has ? extra_has + b0 : nullptr, extra_mn ? extra_mn + b0 : nullptr,
-                                                    &ks[d], &ms[d], off.data());
-            if (r) return r;
-            keys[d].mn = c->c_min.as<uint32_t>(); keys[d].lo = c->c_lo.as<uint64_t>(); keys[d].hi = ks[d] > 32 ? c->c_hi.as<uint64_t>() : nullptr;
-            if (ds_on && off.back()) {
-                // mixed sampling rates: this context's keys brought down before they are dealt -- a filtered key never crosses the fabric
-                uint32_t* f_mn = nullptr; uint64_t *f_lo = nullptr, *f_hi = nullptr;
-                std::vector<uint64_t> kept(off.size(), 0);
-                const int r2 = keys_downsample_impl(c, ks[d], ds_threshold, keys[d].mn, keys[d].lo, keys[d].hi, off.data(), b1 - b0, &f_mn, &f_lo, &f_hi, kept.data());
-                if (r2) return r2;
-                keys[d].mn = f_mn; keys[d].lo = f_lo; keys[d].hi = f_hi;
-                off.swap(kept);
-            }
-        }
+        // (mixed sampling rates: this context's keys are brought down before they are dealt -- a filtered key never crosses the fabric)
+        std::vector<uint64_t>& off = keys[d].sk_off;
+        off.assign(1, 0);
+        int r;
+        if (b1 > b0 && (r = decode_keys_impl(c, payloads + b0, lens + b0, b1 - b0, extra_has ? extra_has + b0 : nullptr, extra_mn ? extra_mn + b0 : nullptr,
+                                             ds_threshold, &keys[d], card + b0))) return r;
         for (uint32_t j = 0; j <= S.per; ++j) S.sk_off[d][j] = off[std::min<size_t>(j, off.size() - 1)];
-        for (uint32_t i = b0; i < b1; ++i) card[i] = off[i - b0 + 1] - off[i - b0];
         return SPSP_OK;
     });
     if (rc) return rc;
     for (uint32_t d = 0; d < n_ctx; ++d) {
         const uint32_t b0 = std::min<uint64_t>((uint64_t)d * S.per, n), b1 = std::min<uint64_t>((uint64_t)(d + 1) * S.per, n);
         if (b1 == b0) continue;
-        if (!S.k) { S.k = ks[d]; S.m = ms[d]; }
-        else if (ks[d] != S.k || ms[d] != S.m) { set_error("sketches were made with different k / m (k=%u m=%u and k=%u m=%u)", S.k, S.m, ks[d], ms[d]); return SPSP_ERR_FORMAT; }
+        if (!S.k) { S.k = keys[d].k; S.m = keys[d].m; }
+        else if (keys[d].k != S.k || keys[d].m != S.m) { set_error("sketches were made with different k / m (k=%u m=%u and k=%u m=%u)", S.k, S.m, keys[d].k, keys[d].m); return SPSP_ERR_FORMAT; }
     }
     *k_out = S.k; *m_out = S.m;
     uint64_t most = 0, all = 0;

@@ -829,6 +829,7 @@ def test_pair_matrix_as_cells_straight_from_the_row_sums(ctx, tmp_path):
         return out
     scratch = torch.full((n, n), 7, dtype=torch.int32, device=dev)
     cells = torch.zeros(1 << 20, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()                                                # (the fills run on torch's stream, the comparison on the context's own)
     cnt = ctx.compare_cells_device(31, D.minimizer.data_ptr(), D.kmer_lo.data_ptr(), None, D.sk_off, n, scratch.data_ptr(), cells.data_ptr(), cells.numel())
     assert cnt == np.count_nonzero(want) and (unpack(cells, cnt, n) == want).all()
     assert int((scratch != 7).sum().item()) == 0                            # the dense matrix was never written
