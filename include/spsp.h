@@ -660,6 +660,71 @@ int spsp_cluster_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int 
                        const char* out_prefix, int chatter, double rate,
                        spsp_cluster_row** rows /* may be NULL; spsp_free */, uint64_t* n_clusters /* may be NULL */);
 
+/* --------------------------------------------------------- neighbours ---- */
+/* What the closest things to a sketch are: per sketch (or per query against a bank) the best few partners at or above a
+ * threshold, best first (not in the reference, whose end product is the two n x n matrices).  On the comparator's keys,
+ * integers only.  Sketches are 0 .. n-1 in list order, c_i = the key count of sketch i, x = the keys two sketches share.
+ * ROWS AND PARTNERS.  n_query == n: every sketch is a row and all other sketches are its partners (one cell serves both of its
+ * ends).  1 <= n_query < n, the queries listed first: the rows are the queries 0 .. n_query-1, their partners the references
+ * n_query .. n-1; a cell between two queries (or between two references) is ignored.
+ * SCORE of partner p for row r, the fraction x / u:
+ *     SPSP_NEIGHBOUR_JACCARD      u = c_r + c_p - x
+ *     SPSP_NEIGHBOUR_CONTAINMENT  u = min(c_r, c_p)      (the larger of the two containment indices, as clustering takes it)
+ *     SPSP_NEIGHBOUR_CONTAINED    u = c_r                (the row's containment in the partner: what the containment CSV
+ *                                                         prints at (r, p); not symmetric: one cell, two scores)
+ * PASS.  A partner passes for a row iff x >= 1 and x * den >= num * u, with 0 <= num <= den <= 1 000 000 (num == 0: any shared
+ * key passes; equality passes).
+ * ORDER.  p comes before q for row r iff x_p * u_q > x_q * u_p (128-bit products); where the two are equal, the partner listed
+ * first.  That is a strict total order: a row's answer is a property of the set of its passing partners.  No floating point
+ * takes part: two different fractions that round to one double are still told apart. */
+#define SPSP_NEIGHBOUR_JACCARD 0
+#define SPSP_NEIGHBOUR_CONTAINMENT 1
+#define SPSP_NEIGHBOUR_CONTAINED 2
+typedef struct spsp_neighbour_row {   /* 24 bytes */
+    uint32_t sketch;     /* the row: a sketch (n_query == n) or a query (< n_query) */
+    uint32_t rank;       /* 1 for the row's best partner */
+    uint32_t neighbour;  /* the partner's index in the call's list */
+    uint32_t reserved;   /* 0 */
+    uint64_t shared;     /* x: the keys the two share */
+} spsp_neighbour_row;
+
+/* d_cells: n_cells packed words i << 48 | j << 32 | count on the device, what spsp_compare_cells_device or
+ * spsp_matrix_cells_device leaves there (every pair at most once, any order, i < j < n <= 65535, count <= min(c_i, c_j)); they
+ * are only read.  h_card: the n key counts (host), each below 2^47.  Per row the first `top` (1 .. 64) passing partners in the
+ * order above; rows come back sorted by (sketch, rank), a row without a passing partner has none.  passing (min(n, n_query)
+ * words, may be NULL) receives per row how many partners passed -- more than `top` says the list was cut; *n_pairs the cells
+ * with at least one passing end, each counted once.  More rows than `cap`: SPSP_ERR_OVERFLOW with *n_rows = the room needed
+ * and `rows` untouched (passing and *n_pairs are already right).  The work buffers belong to the context and are reused call
+ * after call.  A fixed chain of launches whatever n, n_cells and top are -- init, count, cap, two scans, fill, select -- and
+ * TWO host waits: one for the two totals that size the candidate list and the rows, one for the rows.
+ * SPSP_ERR_ARG, before any kernel runs, for n == 0, n > 65535, n_query == 0, n_query > n, a metric other than the three,
+ * num > den, den > 1 000 000, top == 0, top > 64, a key count of 2^47 or more, and for a cell list long enough that the
+ * candidates of all rows could number 2^32 or more (n_cells >= 2^31 all versus all, >= 2^32 in query mode: their places come
+ * from a 32-bit scan, which must not wrap).  SPSP_ERR_ARG also for a cell with i >= j or j >= n (found by the count kernel,
+ * which never indexes with such a pair); the `cap` rows and `passing` are then zeroed.  n_cells == 0 is valid: no rows. */
+int spsp_neighbours_cells_device(spsp_ctx* ctx, const void* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n,
+                                 uint32_t n_query, int metric, uint32_t num, uint32_t den, uint32_t top,
+                                 spsp_neighbour_row* rows, uint64_t cap, uint64_t* n_rows,
+                                 uint32_t* passing /* min(n, n_query) words, may be NULL */, uint64_t* n_pairs);
+/* The rows as text: the line "sketch,rank,neighbour,shared,keys,neighbour_keys,score,passing", then one line per row --
+ * names[sketch], rank, names[neighbour], shared, card[sketch], card[neighbour] and passing[sketch] in decimal, and score =
+ * shared / u as an IEEE double division printed as the matrices print a score (%.<precision>g).  The score is only printed: it
+ * never decided anything.  passing == NULL prints 0 there.  No rows: the header line alone.  A row that names a sketch outside
+ * the lists (sketch >= n_query, neighbour >= n), a query as a neighbour in query mode, or neighbour == sketch, is
+ * SPSP_ERR_ARG; so is a metric other than the three.  *text is released with spsp_free(). */
+int spsp_neighbours_csv_host(const spsp_neighbour_row* rows, uint64_t n_rows, const uint32_t* passing, const char* const* names,
+                             uint32_t n, uint32_t n_query, const uint64_t* card, int metric, int precision, char** text,
+                             uint64_t* len);
+/* The whole-file driver: the files are read, inflated and decoded as spsp_compare_files_rate does it (the same code), with the
+ * same `rate` argument (SPSP_RATE_AS_IS, a rate, or SPSP_RATE_COARSEST) and the same refusals; then the rows of the first
+ * n_query sketches (n_query == n: all versus all) as cells, and the neighbours pass.  The cells never leave the device.  Writes
+ * ONE file, <out_prefix>_neighbours.csv.gz (gzip level 1, as the matrices), and no matrices.  k == m collections are
+ * SPSP_ERR_ARG.  chatter != 0: the reference's "kmers evaluated" line, one line with sketches, passing pairs and rows written,
+ * and the common-rate line when a rate was asked for.  One device: there is no multi-device form. */
+int spsp_neighbours_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, int metric,
+                          uint32_t num, uint32_t den, uint32_t top, const char* out_prefix, int chatter, double rate,
+                          spsp_neighbour_row** rows /* may be NULL; spsp_free */, uint64_t* n_rows /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,15 @@ class ClusterRow(C.Structure):
 CLUSTER_ROW_DTYPE = np.dtype([("cluster", "<u4"), ("representative", "<u4"), ("size", "<u4"), ("reserved", "<u4"), ("shared", "<u8")])
 CLUSTER_JACCARD, CLUSTER_CONTAINMENT = 0, 1
 
+
+class NeighbourRow(C.Structure):
+    """spsp_neighbour_row: one partner in one sketch's list of best matches (include/spsp.h)"""
+    _fields_ = [("sketch", C.c_uint32), ("rank", C.c_uint32), ("neighbour", C.c_uint32), ("reserved", C.c_uint32), ("shared", C.c_uint64)]
+
+
+NEIGHBOUR_ROW_DTYPE = np.dtype([("sketch", "<u4"), ("rank", "<u4"), ("neighbour", "<u4"), ("reserved", "<u4"), ("shared", "<u8")])
+NEIGHBOUR_JACCARD, NEIGHBOUR_CONTAINMENT, NEIGHBOUR_CONTAINED = 0, 1, 2
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -106,6 +115,7 @@ ABI_SYMBOLS = [
     "spsp_keys_downsample_device", "spsp_sketch_header_host", "spsp_sketch_downsample_host", "spsp_compare_files_rate", "spsp_compare_files_multi_rate",
     "spsp_gather_device", "spsp_gather_csv_host", "spsp_gather_files",
     "spsp_cluster_cells_device", "spsp_cluster_csv_host", "spsp_cluster_files",
+    "spsp_neighbours_cells_device", "spsp_neighbours_csv_host", "spsp_neighbours_files",
 ]
 
 _lib = None
@@ -245,6 +255,13 @@ def lib():
         L.spsp_cluster_csv_host.argtypes = [vp, P(cp), u32, vp, i32, i32, P(vp), P(u64)]
         L.spsp_cluster_files.restype = i32
         L.spsp_cluster_files.argtypes = [vp, P(cp), u32, i32, i32, u32, u32, cp, i32, dbl, P(vp), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_neighbours_cells_device"):
+        L.spsp_neighbours_cells_device.restype = i32
+        L.spsp_neighbours_cells_device.argtypes = [vp, vp, u64, vp, u32, u32, i32, u32, u32, u32, vp, u64, P(u64), vp, P(u64)]
+        L.spsp_neighbours_csv_host.restype = i32
+        L.spsp_neighbours_csv_host.argtypes = [vp, u64, vp, P(cp), u32, u32, vp, i32, i32, P(vp), P(u64)]
+        L.spsp_neighbours_files.restype = i32
+        L.spsp_neighbours_files.argtypes = [vp, P(cp), u32, u32, i32, i32, u32, u32, u32, cp, i32, dbl, P(vp), P(u64)]
     _lib = L
     return L
 
@@ -414,6 +431,27 @@ def cluster_csv(rows, names, card, metric, precision=6):
     arr = (C.c_char_p * n)(*[s.encode() for s in names])
     out, ln = C.c_void_p(), C.c_uint64()
     _check(lib().spsp_cluster_csv_host(rows.ctypes.data, arr, n, card.ctypes.data, metric, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def neighbours_csv(rows, passing, names, card, metric, n_query=None, precision=6):
+    """spsp_neighbours_csv_host: neighbour rows (NEIGHBOUR_ROW_DTYPE array) and the per-row passing counts -> the text of
+    <prefix>_neighbours.csv.gz; card[i] = key count of sketch i as the comparison saw it, names = the queries' names first in
+    query mode (n_query < len(names))"""
+    rows = np.ascontiguousarray(rows, dtype=NEIGHBOUR_ROW_DTYPE)
+    card = np.ascontiguousarray(card, dtype=np.uint64)
+    n = len(names)
+    nq = n if n_query is None else n_query
+    if len(card) != n:
+        raise ValueError("neighbours_csv: one key count per name")
+    if passing is not None:
+        passing = np.ascontiguousarray(passing, dtype=np.uint32)
+        if len(passing) != min(n, nq):
+            raise ValueError("neighbours_csv: one passing count per row sketch")
+    arr = (C.c_char_p * n)(*[s.encode() for s in names])
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_neighbours_csv_host(rows.ctypes.data, len(rows), passing.ctypes.data if passing is not None else None, arr, n, nq,
+                                          card.ctypes.data, metric, precision, C.byref(out), C.byref(ln)))
     return _take(out, ln.value)
 
 
@@ -894,3 +932,35 @@ class Context:
         out, nc = C.c_void_p(), C.c_uint64()
         _check(lib().spsp_cluster_files(self._h, arr, n, precision, metric, num, den, out_prefix.encode(), 0, _rate_arg(rate), C.byref(out), C.byref(nc)))
         return np.frombuffer(_take(out, n * CLUSTER_ROW_DTYPE.itemsize), dtype=CLUSTER_ROW_DTYPE).copy(), nc.value
+
+    def neighbours_cells_device(self, d_cells, n_cells, card, n, metric, num, den, top, n_query=None):
+        """spsp_neighbours_cells_device: per row sketch (every sketch, or the first n_query) the best `top` partners at or above
+        num / den from the packed cells (i << 48 | j << 32 | count) of the pair matrix on the device and the n key counts ->
+        (rows: NEIGHBOUR_ROW_DTYPE array ordered by (sketch, rank), passing: np.uint32 per row sketch, n_pairs); the room grows
+        here on overflow"""
+        card = np.ascontiguousarray(card, dtype=np.uint64)
+        if len(card) != n:
+            raise ValueError("neighbours_cells_device: one key count per sketch")
+        nq = n if n_query is None else n_query
+        passing = np.zeros(max(min(n, nq), 1), dtype=np.uint32)
+        cap = max(1, min(min(n, nq) * top, 2 * n_cells, 1 << 21))         # (every row there can be, up to 48 MB of them)
+        for _ in range(2):
+            rows = np.zeros(cap, dtype=NEIGHBOUR_ROW_DTYPE)
+            cnt, pairs = C.c_uint64(), C.c_uint64()
+            rc = lib().spsp_neighbours_cells_device(self._h, d_cells, n_cells, card.ctypes.data, n, nq, metric, num, den, top,
+                                                    rows.ctypes.data, cap, C.byref(cnt), passing.ctypes.data, C.byref(pairs))
+            if rc != ERR_OVERFLOW or cnt.value <= cap:
+                break
+            cap = cnt.value
+        _check(rc)
+        return rows[:cnt.value].copy(), passing[:min(n, nq)], pairs.value
+
+    def neighbours_files(self, paths, out_prefix, top, metric=0, num=0, den=1, n_query=None, precision=6, rate=0.0):
+        """spsp_neighbours_files: sketch files (the n_query queries first, or all versus all) -> <out_prefix>_neighbours.csv.gz
+        and the rows.  rate: as compare_files (0.0, a rate, or "auto")"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        out, cnt = C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_neighbours_files(self._h, arr, n, n if n_query is None else n_query, precision, metric, num, den, top,
+                                           out_prefix.encode(), 0, _rate_arg(rate), C.byref(out), C.byref(cnt)))
+        return np.frombuffer(_take(out, cnt.value * NEIGHBOUR_ROW_DTYPE.itemsize), dtype=NEIGHBOUR_ROW_DTYPE).copy()

@@ -3,7 +3,9 @@
 // output files (<o>_containment.csv.gz, <o>_jaccard.csv.gz).  One addition: -g <min_keys> with -q gathers instead --
 // which references make up each query, greedily (spsp_gather_files) -> <o>_gather.csv.gz.  Another: -c <t> / -C <t> without -q
 // clusters the index instead -- single linkage on Jaccard / on the larger containment at threshold t (spsp_cluster_files) ->
-// <o>_clusters.csv.gz.
+// <o>_clusters.csv.gz.  A third: -N <top> [-J <t> | -K <t> | -I <t>], with or without -q, lists each sketch's (each query's) best
+// <top> partners at or above threshold t instead -- on Jaccard, on the larger containment, on the row's containment in the
+// partner; Jaccard at 0 with none of the three (spsp_neighbours_files) -> <o>_neighbours.csv.gz.
 #include <getopt.h>
 
 #include <chrono>
@@ -31,8 +33,8 @@ static bool read_names(const string& fof, vector<string>& out) {
 }
 
 // -c / -C <t>: a decimal in (0, 1] with at most six digits behind the point, read as TEXT into num / 10^digits ("0.95" = 95 / 100,
-// "1" = 1 / 1): the threshold takes part in integer comparisons only
-static bool parse_fraction(const char* t, uint32_t* num, uint32_t* den) {
+// "1" = 1 / 1): the threshold takes part in integer comparisons only.  -J / -K / -I <t> admit 0 as well (zero_ok)
+static bool parse_fraction(const char* t, uint32_t* num, uint32_t* den, bool zero_ok = false) {
     if ((t[0] != '0' && t[0] != '1') || (t[1] != 0 && t[1] != '.')) return false;
     uint64_t n = (uint64_t)(t[0] - '0'), d = 1;
     if (t[1] == '.') {
@@ -43,7 +45,7 @@ static bool parse_fraction(const char* t, uint32_t* num, uint32_t* den) {
             n = n * 10 + (uint64_t)(*f - '0'); d *= 10;
         }
     }
-    if (n < 1 || n > d) return false;
+    if ((n < 1 && !zero_ok) || n > d) return false;
     *num = (uint32_t)n; *den = (uint32_t)d;
     return true;
 }
@@ -58,7 +60,12 @@ int main(int argc, char** argv) {
     uint64_t min_keys = 0;
     int cluster_opts = 0, cluster_metric = SPSP_CLUSTER_JACCARD;   // -c <t> / -C <t>: neither letter is in the reference's option string
     uint32_t cluster_num = 0, cluster_den = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:")) != -1) {
+    // -N <top> and -J / -K / -I <t>: none of the four letters is in the reference's option string
+    bool neighbours = false;
+    long long top = 0;
+    int nb_opts = 0, nb_metric = SPSP_NEIGHBOUR_JACCARD;
+    uint32_t nb_num = 0, nb_den = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:")) != -1) {
         switch (ch) {
             case 'c':
             case 'C':
@@ -68,6 +75,23 @@ int main(int argc, char** argv) {
                 }
                 cluster_metric = ch == 'c' ? SPSP_CLUSTER_JACCARD : SPSP_CLUSTER_CONTAINMENT;
                 ++cluster_opts;
+                break;
+            case 'N': {
+                char* e = nullptr;
+                top = strtoll(optarg, &e, 10);
+                if (e == optarg || *e || top < 1 || top > 64) { cout << "-N takes the number of neighbours listed per sketch, an integer in 1 .. 64, not '" << optarg << "'" << endl; return 1; }
+                neighbours = true;
+                break;
+            }
+            case 'J':
+            case 'K':
+            case 'I':
+                if (!parse_fraction(optarg, &nb_num, &nb_den, true)) {
+                    cout << "-" << (char)ch << " takes a threshold in [0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
+                    return 1;
+                }
+                nb_metric = ch == 'J' ? SPSP_NEIGHBOUR_JACCARD : ch == 'K' ? SPSP_NEIGHBOUR_CONTAINMENT : SPSP_NEIGHBOUR_CONTAINED;
+                ++nb_opts;
                 break;
             case 'f': inputfof = optarg; break;
             case 'q': query = optarg; break;
@@ -93,6 +117,9 @@ int main(int argc, char** argv) {
     }
     if (cluster_opts > 1) { cout << "-c (Jaccard) and -C (containment) cluster the index: one of them, once" << endl; return 1; }
     if (cluster_opts && (query != "" || gather)) { cout << "-c / -C cluster the index all versus all: not together with -q or -g" << endl; return 1; }
+    if (nb_opts > 1) { cout << "-J (Jaccard), -K (the larger containment) and -I (the row's containment) set the threshold of -N: one of them, once" << endl; return 1; }
+    if (nb_opts && !neighbours) { cout << "-J / -K / -I set the threshold of the neighbour lists: they need -N" << endl; return 1; }
+    if (neighbours && (gather || cluster_opts)) { cout << "-N lists neighbours: not together with -g, -c or -C" << endl; return 1; }
     if (inputfof == "") {
         cout << "Core arguments:" << endl
              << "-f Index file of files (mandatory)" << endl
@@ -137,6 +164,17 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (neighbours) {
+        // one device, as gather
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_neighbours_files(ctx, paths.data(), (uint32_t)paths.size(), n_query, (int)p, nb_metric, nb_num, nb_den, (uint32_t)top,
+                                                      output_name.c_str(), 1, rate, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Neighbours failed: " << err << endl; return 1; }
+        return 0;
     }
     if (cluster_opts) {
         // one device, as gather

@@ -1833,6 +1833,36 @@ int spsp_cluster_csv_host(const spsp_cluster_row* rows, const char* const* names
     return text_out(out, text, len);
 }
 
+int spsp_neighbours_csv_host(const spsp_neighbour_row* rows, uint64_t n_rows, const uint32_t* passing, const char* const* names, uint32_t n,
+                             uint32_t n_query, const uint64_t* card, int metric, int precision, char** text, uint64_t* len) {
+    if (!text || !len || (n_rows && (!rows || !names || !card))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (metric != SPSP_NEIGHBOUR_JACCARD && metric != SPSP_NEIGHBOUR_CONTAINMENT && metric != SPSP_NEIGHBOUR_CONTAINED) {
+        set_error("neighbour metric %d: 0 (Jaccard), 1 (the larger containment) or 2 (the row's containment in the partner)", metric);
+        return SPSP_ERR_ARG;
+    }
+    std::string out = "sketch,rank,neighbour,shared,keys,neighbour_keys,score,passing\n";
+    char num[64];
+    const bool all = n_query == n;
+    for (uint64_t i = 0; i < n_rows; ++i) {
+        const spsp_neighbour_row& r = rows[i];
+        if (r.sketch >= n_query || r.sketch >= n || r.neighbour >= n || (!all && r.neighbour < n_query) || r.neighbour == r.sketch) {
+            set_error("neighbour row %llu names a sketch outside the lists (or a query, or the sketch itself, as the neighbour)", (unsigned long long)i);
+            return SPSP_ERR_ARG;
+        }
+        const uint64_t cr = card[r.sketch], cp = card[r.neighbour];
+        const uint64_t under = metric == SPSP_NEIGHBOUR_JACCARD ? cr + cp - r.shared : metric == SPSP_NEIGHBOUR_CONTAINMENT ? std::min(cr, cp) : cr;
+        out += names[r.sketch]; out += ',';
+        out += std::to_string(r.rank); out += ',';
+        out += names[r.neighbour]; out += ',';
+        out += std::to_string(r.shared); out += ',';
+        out += std::to_string(cr); out += ',';
+        out += std::to_string(cp); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, (double)r.shared / (double)under)); out += ',';   // (printed only: the integer order has decided)
+        out += std::to_string(passing ? passing[r.sketch] : 0u); out += '\n';
+    }
+    return text_out(out, text, len);
+}
+
 int spsp_compare_files_rate(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, double min_threshold,
                             const char* out_prefix, int chatter, double rate) {
     return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, clamp_chatter(chatter), rate);

@@ -112,11 +112,16 @@ enum HostSlot {
     kHsClusterEdges = 16,   // spsp_cluster.hip: the copy of k_cl_link's edge count (u64); cluster_cells_impl reads behind its one wait
     kHsClusterBad = 17,     // ... of k_cl_link's bad-cell word (u32), in the same wait
     kHsClusterCount = 18,   // ... and launch_scan_u32's total over the "is a root" flags: the number of clusters (u64)
-    kHostSlots = 19
+    kHsNbCands = 19,        // spsp_neighbours.hip: launch_scan_u32's total over the rows' passing partners: the candidates (u64)
+    kHsNbRows = 20,         // ... its total over min(passing, top): the rows the call returns (u64)
+    kHsNbPairs = 21,        // ... the copy of k_nb_count's count of cells with a passing end (u64)
+    kHsNbBad = 22,          // ... and of its bad-cell word (u32): neighbours_cells_impl reads all four behind its first wait
+    kHostSlots = 23
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
 static_assert(kHsIngestRecs == kHsIngestKept + 1 && kHsMultiVerdict == kHsOrderVerdict + 1 && kHsMultiVerdict < kHostSlots, "slots reached from their neighbour");
+static_assert(kHsNbCands == kHsClusterCount + 1 && kHsNbBad + 1 == kHostSlots, "the neighbours' four slots are the last ones");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -232,6 +237,8 @@ struct spsp_ctx {
     spsp::DevBuf g_off, g_u, g_roff, g_rfill, g_qcnt, g_qoff, g_edges, g_byref, g_hold, g_count, g_state, g_rows;
     // clustering (spsp_cluster.hip): the per-sketch arrays and the counter words in one work area, the rows
     spsp::DevBuf cl_work, cl_rows;
+    // neighbours (spsp_neighbours.hip): the per-row arrays and the counter words in one work area, the candidate list, the rows
+    spsp::DevBuf nb_work, nb_cand, nb_rows;
 };
 
 namespace spsp {
@@ -318,6 +325,11 @@ int cluster_check_args(uint32_t n, int metric, uint32_t num, uint32_t den);
 int cluster_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, int metric, uint32_t num, uint32_t den,
                           const uint64_t* ds_threshold, uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_cluster_row>* rows,
                           uint64_t* n_clusters, uint64_t* n_edges);
+// spsp_neighbours.hip: each row sketch's best `top` partners at or above num / den from the packed cells (on the device, only read)
+int neighbours_check_args(uint32_t n, uint32_t n_query, int metric, uint32_t num, uint32_t den, uint32_t top);
+int neighbours_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n, uint32_t n_query, int metric,
+                          uint32_t num, uint32_t den, uint32_t top, spsp_neighbour_row* rows, uint64_t cap, uint64_t* n_rows, uint32_t* passing,
+                          uint64_t* n_pairs);
 // the front half of every file driver (spsp_host.cpp): the payloads of n sketch files, in file order, and what their headers say
 struct LoadedSketches {
     std::vector<uint8_t*> data;                                    // into the context's read regions, or owned (own[i])
