@@ -725,6 +725,66 @@ int spsp_neighbours_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, u
                           uint32_t num, uint32_t den, uint32_t top, const char* out_prefix, int chatter, double rate,
                           spsp_neighbour_row** rows /* may be NULL; spsp_free */, uint64_t* n_rows /* may be NULL */);
 
+/* --------------------------------------------------------- prevalence ---- */
+/* How many of the sketches hold each key (not in the reference, whose end product is the two n x n matrices: they say nothing
+ * about whether one key is in 3 or in 9 000 sketches).  On the comparator's keys, integers only.  Sketches are 0 .. n-1 in list
+ * order, K_i the keys of sketch i, c_i = |K_i|.  n_query == 0: all versus all -- every sketch is a row and a reference, R = n.
+ * n_query > 0, the layout of query mode: the first n_query sketches are rows only, the R = n - n_query sketches behind them the
+ * references.
+ * HOLDER COUNT.  h(x) = the number of references j with x in K_j (all versus all: >= 1 for a row's own keys; query mode: may be 0).
+ * CLASSES, exclusive, in this order, for the threshold num / den with 1 <= num <= den <= 1 000 000:
+ *     absent  h == 0                                   (query mode only)
+ *     core    h >= 1 and h * den >= num * R            (equality passes; 64-bit products; no floating point takes part)
+ *     unique  not core and h == 1
+ *     shell   everything else
+ * PER ROW SKETCH i (every sketch, or every query): how many keys of K_i fall in each class -- they sum to c_i -- and
+ * holders = the sum of h(x) over K_i.  All versus all, holders - c_i is row i's sum of the comparison's pair matrix; in query
+ * mode holders is that row sum over the references.
+ * SPECTRUM.  S[t], t = 1 .. R = the distinct keys of the references' union with h == t (queries take no part): sum S[t] = the
+ * size of the union, sum t * S[t] = the references' key counts added up. */
+typedef struct spsp_prevalence_row {   /* 40 bytes */
+    uint64_t core, shell, unique, absent;   /* keys of the row sketch per class */
+    uint64_t holders;                       /* sum of h over the row sketch's keys */
+} spsp_prevalence_row;
+
+/* Input: the concatenated key arrays spsp_gather_device takes, sorted per sketch ((minimizer, kmer_hi, kmer_lo) strictly
+ * ascending), the queries first when there are any.  The arrays are only read; the work buffers belong to the context and are
+ * reused call after call.  rows receives n_query rows (n rows when n_query == 0), spectrum R + 1 words with [0] = 0.
+ * d_holders (may be NULL) receives a context-owned uint32 array on the device, parallel to the key arrays: h of every key
+ * occurrence (entry e of the key arrays at word e).  It stays valid until the next prevalence call on the context.
+ * SPSP_ERR_ARG for n == 0, n_query >= n, n > 65535, num == 0, num > den, den > 1 000 000, keys that are not strictly
+ * increasing inside a sketch, and on a context switched to unordered keys (spsp_compare_keys_unordered); rows and spectrum are
+ * zeroed when the keys are refused.  Launches, the same chain whatever n and the keys are: count (a lane per reference key: its
+ * slot in one table in HBM, claimed by entry number and compared by the full key, plus one on the slot's counter), read back (a
+ * lane per key: holders[]), rows (a workgroup per row sketch), spectrum (over the table's slots), and ONE host wait, at the
+ * end, for the rows, the spectrum and the order check.  The table's size follows from the number of reference keys alone: no
+ * attempt is ever repeated. */
+int spsp_prevalence_device(spsp_ctx* ctx, uint32_t k, const void* d_minimizer, const void* d_kmer_lo, const void* d_kmer_hi /* NULL if k <= 32 */,
+                           const uint64_t* h_sk_off, uint32_t n, uint32_t n_query /* 0: all versus all */, uint32_t num, uint32_t den,
+                           spsp_prevalence_row* rows /* n_query ? n_query : n */, uint64_t* spectrum /* R + 1 words, [0] = 0 */,
+                           void** d_holders /* may be NULL */);
+/* The rows as text: the line "sketch,keys,core,shell,unique,absent,f_core,mean_holders", then one line per row sketch in list
+ * order -- names[i], card[i] and the four class counts in decimal, f_core = core / card[i] and mean_holders = holders / card[i]
+ * as IEEE double divisions printed as the matrices print a score (%.<precision>g); both print 0 when card[i] == 0.  card[i] =
+ * the key count of sketch i as the prevalence pass saw it: a row whose classes do not add up to it is SPSP_ERR_ARG.  *text is
+ * released with spsp_free(). */
+int spsp_prevalence_csv_host(const spsp_prevalence_row* rows, uint32_t n_rows, const char* const* names, const uint64_t* card,
+                             int precision, char** text, uint64_t* len);
+/* The spectrum (n_ref + 1 words, [0] ignored) as text: the line "holders,keys,cumulative", then one line per t with S[t] > 0,
+ * ascending -- t, S[t] and cumulative = the sum of S[u] over u >= t (64 bit): the core's size at any threshold can be read off
+ * it.  *text is released with spsp_free(). */
+int spsp_spectrum_csv_host(const uint64_t* spectrum, uint32_t n_ref, char** text, uint64_t* len);
+/* The whole-file driver: the files are read, inflated and decoded as spsp_compare_files_rate does it (the same code), with the
+ * same `rate` argument (SPSP_RATE_AS_IS, a rate, or SPSP_RATE_COARSEST) and the same refusals (a file coarser than the common
+ * rate, differing k or m); k == m collections are SPSP_ERR_ARG.  Then the prevalence pass.  Writes TWO files,
+ * <out_prefix>_prevalence.csv.gz and <out_prefix>_spectrum.csv.gz (gzip level 1, as the matrices), and no matrices.
+ * chatter != 0: the reference's "kmers evaluated" line, one line with the references, the size of their union and the size of
+ * the core, and the common-rate line when a rate was asked for.  rows (n_query ? n_query : n) and spectrum (n - n_query + 1
+ * words) receive copies, released with spsp_free(); either may be NULL.  One device: there is no multi-device form. */
+int spsp_prevalence_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, uint32_t num, uint32_t den,
+                          const char* out_prefix, int chatter, double rate,
+                          spsp_prevalence_row** rows /* may be NULL; spsp_free */, uint64_t** spectrum /* may be NULL; spsp_free */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,9 @@ class NeighbourRow(C.Structure):
 NEIGHBOUR_ROW_DTYPE = np.dtype([("sketch", "<u4"), ("rank", "<u4"), ("neighbour", "<u4"), ("reserved", "<u4"), ("shared", "<u8")])
 NEIGHBOUR_JACCARD, NEIGHBOUR_CONTAINMENT, NEIGHBOUR_CONTAINED = 0, 1, 2
 
+# spsp_prevalence_row: a row sketch's keys by class of holder count, and the sum of the holder counts (include/spsp.h)
+PREVALENCE_ROW_DTYPE = np.dtype([("core", "<u8"), ("shell", "<u8"), ("unique", "<u8"), ("absent", "<u8"), ("holders", "<u8")])
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -116,6 +119,7 @@ ABI_SYMBOLS = [
     "spsp_gather_device", "spsp_gather_csv_host", "spsp_gather_files",
     "spsp_cluster_cells_device", "spsp_cluster_csv_host", "spsp_cluster_files",
     "spsp_neighbours_cells_device", "spsp_neighbours_csv_host", "spsp_neighbours_files",
+    "spsp_prevalence_device", "spsp_prevalence_csv_host", "spsp_spectrum_csv_host", "spsp_prevalence_files",
 ]
 
 _lib = None
@@ -262,6 +266,15 @@ def lib():
         L.spsp_neighbours_csv_host.argtypes = [vp, u64, vp, P(cp), u32, u32, vp, i32, i32, P(vp), P(u64)]
         L.spsp_neighbours_files.restype = i32
         L.spsp_neighbours_files.argtypes = [vp, P(cp), u32, u32, i32, i32, u32, u32, u32, cp, i32, dbl, P(vp), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_prevalence_device"):
+        L.spsp_prevalence_device.restype = i32
+        L.spsp_prevalence_device.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, P(vp)]
+        L.spsp_prevalence_csv_host.restype = i32
+        L.spsp_prevalence_csv_host.argtypes = [vp, u32, P(cp), vp, i32, P(vp), P(u64)]
+        L.spsp_spectrum_csv_host.restype = i32
+        L.spsp_spectrum_csv_host.argtypes = [vp, u32, P(vp), P(u64)]
+        L.spsp_prevalence_files.restype = i32
+        L.spsp_prevalence_files.argtypes = [vp, P(cp), u32, u32, i32, u32, u32, cp, i32, dbl, P(vp), P(vp)]
     _lib = L
     return L
 
@@ -452,6 +465,31 @@ def neighbours_csv(rows, passing, names, card, metric, n_query=None, precision=6
     out, ln = C.c_void_p(), C.c_uint64()
     _check(lib().spsp_neighbours_csv_host(rows.ctypes.data, len(rows), passing.ctypes.data if passing is not None else None, arr, n, nq,
                                           card.ctypes.data, metric, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def prevalence_csv(rows, names, card, precision=6):
+    """spsp_prevalence_csv_host: prevalence rows (PREVALENCE_ROW_DTYPE array, one per row sketch in list order) -> the text of
+    <prefix>_prevalence.csv.gz; names[i], card[i] = the name and the key count of row sketch i as the prevalence pass saw it"""
+    rows = np.ascontiguousarray(rows, dtype=PREVALENCE_ROW_DTYPE)
+    card = np.ascontiguousarray(card, dtype=np.uint64)
+    n = len(rows)
+    if len(names) < n or len(card) < n:
+        raise ValueError("prevalence_csv: a name and a key count per row")
+    arr = (C.c_char_p * max(n, 1))(*[s.encode() for s in names[:n]])
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_prevalence_csv_host(rows.ctypes.data, n, arr, card.ctypes.data, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def spectrum_csv(spectrum):
+    """spsp_spectrum_csv_host: spectrum[t] = the distinct keys held by exactly t references, t = 0 .. R ([0] ignored) -> the text
+    of <prefix>_spectrum.csv.gz"""
+    spectrum = np.ascontiguousarray(spectrum, dtype=np.uint64)
+    if len(spectrum) < 1:
+        raise ValueError("spectrum_csv: R + 1 words")
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_spectrum_csv_host(spectrum.ctypes.data, len(spectrum) - 1, C.byref(out), C.byref(ln)))
     return _take(out, ln.value)
 
 
@@ -964,3 +1002,30 @@ class Context:
         _check(lib().spsp_neighbours_files(self._h, arr, n, n if n_query is None else n_query, precision, metric, num, den, top,
                                            out_prefix.encode(), 0, _rate_arg(rate), C.byref(out), C.byref(cnt)))
         return np.frombuffer(_take(out, cnt.value * NEIGHBOUR_ROW_DTYPE.itemsize), dtype=NEIGHBOUR_ROW_DTYPE).copy()
+
+    def prevalence_device(self, k, d_min, d_lo, d_hi, sk_off, n, num, den, n_query=0, want_holders=False):
+        """spsp_prevalence_device: how many references hold each key, over concatenated sorted key arrays on the device ->
+        (rows: PREVALENCE_ROW_DTYPE array, one per row sketch -- every sketch, or the first n_query --, spectrum: np.uint64[R + 1]
+        [, d_holders: the device address of the context's uint32 array of h per key occurrence, valid until the next call])"""
+        sk_off = np.ascontiguousarray(sk_off, dtype=np.uint64)
+        if len(sk_off) != n + 1:
+            raise ValueError("prevalence_device: n + 1 sketch offsets")
+        rows = np.zeros(max(n_query if n_query else n, 1), dtype=PREVALENCE_ROW_DTYPE)
+        spectrum = np.zeros(max(n - n_query, 0) + 1, dtype=np.uint64)
+        held = C.c_void_p()
+        _check(lib().spsp_prevalence_device(self._h, k, d_min, d_lo, d_hi, sk_off.ctypes.data, n, n_query, num, den, rows.ctypes.data,
+                                            spectrum.ctypes.data, C.byref(held) if want_holders else None))
+        rows = rows[:n_query if n_query else n]
+        return (rows, spectrum, held.value) if want_holders else (rows, spectrum)
+
+    def prevalence_files(self, paths, out_prefix, num, den, n_query=0, precision=6, rate=0.0):
+        """spsp_prevalence_files: sketch files (the n_query queries first, or all versus all) -> <out_prefix>_prevalence.csv.gz,
+        <out_prefix>_spectrum.csv.gz and (rows, spectrum).  rate: as compare_files (0.0, a rate, or "auto")"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        rows, spec = C.c_void_p(), C.c_void_p()
+        _check(lib().spsp_prevalence_files(self._h, arr, n, n_query, precision, num, den, out_prefix.encode(), 0, _rate_arg(rate),
+                                           C.byref(rows), C.byref(spec)))
+        n_rows = n_query if n_query else n
+        return (np.frombuffer(_take(rows, n_rows * PREVALENCE_ROW_DTYPE.itemsize), dtype=PREVALENCE_ROW_DTYPE).copy(),
+                np.frombuffer(_take(spec, (n - n_query + 1) * 8), dtype=np.uint64).copy())

@@ -5,7 +5,10 @@
 // clusters the index instead -- single linkage on Jaccard / on the larger containment at threshold t (spsp_cluster_files) ->
 // <o>_clusters.csv.gz.  A third: -N <top> [-J <t> | -K <t> | -I <t>], with or without -q, lists each sketch's (each query's) best
 // <top> partners at or above threshold t instead -- on Jaccard, on the larger containment, on the row's containment in the
-// partner; Jaccard at 0 with none of the three (spsp_neighbours_files) -> <o>_neighbours.csv.gz.
+// partner; Jaccard at 0 with none of the three (spsp_neighbours_files) -> <o>_neighbours.csv.gz.  A fourth: -P <t>, with or
+// without -q, counts instead how many of the index's sketches hold each key -- per sketch (per query) the keys that are core (held
+// by a share t of the index or more), shell, unique and absent, and the spectrum of the index's union (spsp_prevalence_files) ->
+// <o>_prevalence.csv.gz and <o>_spectrum.csv.gz.
 #include <getopt.h>
 
 #include <chrono>
@@ -65,7 +68,9 @@ int main(int argc, char** argv) {
     long long top = 0;
     int nb_opts = 0, nb_metric = SPSP_NEIGHBOUR_JACCARD;
     uint32_t nb_num = 0, nb_den = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:")) != -1) {
+    bool prevalence = false;         // -P <t>: the letter is not in the reference's option string
+    uint32_t pv_num = 0, pv_den = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:")) != -1) {
         switch (ch) {
             case 'c':
             case 'C':
@@ -75,6 +80,13 @@ int main(int argc, char** argv) {
                 }
                 cluster_metric = ch == 'c' ? SPSP_CLUSTER_JACCARD : SPSP_CLUSTER_CONTAINMENT;
                 ++cluster_opts;
+                break;
+            case 'P':
+                if (!parse_fraction(optarg, &pv_num, &pv_den)) {
+                    cout << "-P takes a threshold in (0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
+                    return 1;
+                }
+                prevalence = true;
                 break;
             case 'N': {
                 char* e = nullptr;
@@ -120,6 +132,7 @@ int main(int argc, char** argv) {
     if (nb_opts > 1) { cout << "-J (Jaccard), -K (the larger containment) and -I (the row's containment) set the threshold of -N: one of them, once" << endl; return 1; }
     if (nb_opts && !neighbours) { cout << "-J / -K / -I set the threshold of the neighbour lists: they need -N" << endl; return 1; }
     if (neighbours && (gather || cluster_opts)) { cout << "-N lists neighbours: not together with -g, -c or -C" << endl; return 1; }
+    if (prevalence && (gather || cluster_opts || neighbours)) { cout << "-P counts the holders of every key: not together with -g, -c, -C or -N" << endl; return 1; }
     if (inputfof == "") {
         cout << "Core arguments:" << endl
              << "-f Index file of files (mandatory)" << endl
@@ -164,6 +177,17 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (prevalence) {
+        // one device, as gather; the rows are every sketch of the index (n_query 0) or the queries
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_prevalence_files(ctx, paths.data(), (uint32_t)paths.size(), query == "" ? 0u : n_query, (int)p, pv_num, pv_den,
+                                                      output_name.c_str(), 1, rate, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Prevalence failed: " << err << endl; return 1; }
+        return 0;
     }
     if (neighbours) {
         // one device, as gather

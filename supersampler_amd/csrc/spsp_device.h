@@ -59,4 +59,31 @@ __device__ __forceinline__ uint32_t pack16(uint4 v) {
     return (a << 15) | (b >> 1);
 }
 
+// The comparator's keys as gather and prevalence read them: concatenated arrays, every sketch sorted by (minimizer, kmer_hi, kmer_lo);
+// off[j] = the first entry of sketch j.
+struct SortedKeys { const uint32_t* mn; const uint64_t* lo; const uint64_t* hi; };
+
+template <bool HAS_HI>
+__device__ __forceinline__ bool keys_less(const SortedKeys& K, uint64_t i, uint32_t mn, uint64_t hi, uint64_t lo) {   // key i < (mn, hi, lo)
+    const uint32_t a = K.mn[i];
+    if (a != mn) return a < mn;
+    if (HAS_HI) { const uint64_t h = K.hi[i]; if (h != hi) return h < hi; }
+    return K.lo[i] < lo;
+}
+
+// the sketch that holds entry e: the last j in [j0, j1) with off[j] <= e (sketches without keys are stepped over)
+__device__ __forceinline__ uint32_t sorted_sketch_of(const uint64_t* __restrict__ off, uint32_t j0, uint32_t j1, uint64_t e) {
+    uint32_t a = j0, b = j1;                               // first j in [j0, j1] with off[j] > e
+    while (a < b) { const uint32_t mid = a + ((b - a) >> 1); if (off[mid] <= e) a = mid + 1; else b = mid; }
+    return a - 1;
+}
+
+// flag[0] |= 1 when entry e does not come strictly after e - 1 inside its sketch (sketches [j0, j1) own entries [off[j0], off[j1]))
+template <bool HAS_HI>
+__device__ __forceinline__ void sorted_check_order(const SortedKeys& K, const uint64_t* __restrict__ off, uint32_t j0, uint32_t j1, uint64_t e,
+                                              uint32_t mn, uint64_t hi, uint64_t lo, uint32_t* __restrict__ flag) {
+    if (e == off[j0] || keys_less<HAS_HI>(K, e - 1, mn, hi, lo)) return;
+    if (e != off[sorted_sketch_of(off, j0, j1, e)]) atomicOr(flag, 1u);   // (the first key of a sketch may be anything)
+}
+
 }  // namespace spsp

@@ -38,45 +38,20 @@ constexpr uint32_t kGwMaxBlocks = 64;                      // k_g_walk: workgrou
 constexpr uint32_t kNoWinner = 0xffffffffu;
 constexpr uint32_t kBatchFirst = 32, kBatchMax = 128;      // rounds queued per host wait: 32, 64, 128, 128, ...
 
-struct GKeys { const uint32_t* mn; const uint64_t* lo; const uint64_t* hi; };
-
 // per-query words the round kernels keep (one host copy in, one per batch out)
 struct GState { unsigned long long alive; uint32_t stopped, n_rows, winner, pad; };
 
 template <bool HAS_HI>
-__device__ __forceinline__ bool g_less(const GKeys& K, uint64_t i, uint32_t mn, uint64_t hi, uint64_t lo) {   // key i < (mn, hi, lo)
-    const uint32_t a = K.mn[i];
-    if (a != mn) return a < mn;
-    if (HAS_HI) { const uint64_t h = K.hi[i]; if (h != hi) return h < hi; }
-    return K.lo[i] < lo;
-}
-
-// the sketch that holds entry e: the last j in [j0, j1) with off[j] <= e (sketches without keys are stepped over)
-__device__ __forceinline__ uint32_t g_sketch_of(const uint64_t* __restrict__ off, uint32_t j0, uint32_t j1, uint64_t e) {
-    uint32_t a = j0, b = j1;                               // first j in [j0, j1] with off[j] > e
-    while (a < b) { const uint32_t mid = a + ((b - a) >> 1); if (off[mid] <= e) a = mid + 1; else b = mid; }
-    return a - 1;
-}
-
-// flag[0] |= 1 when entry e does not come strictly after e - 1 inside its sketch (sketches [j0, j1) own entries [off[j0], off[j1]))
-template <bool HAS_HI>
-__device__ __forceinline__ void g_check_order(const GKeys& K, const uint64_t* __restrict__ off, uint32_t j0, uint32_t j1, uint64_t e,
-                                              uint32_t mn, uint64_t hi, uint64_t lo, uint32_t* __restrict__ flag) {
-    if (e == off[j0] || g_less<HAS_HI>(K, e - 1, mn, hi, lo)) return;
-    if (e != off[g_sketch_of(off, j0, j1, e)]) atomicOr(flag, 1u);   // (the first key of a sketch may be anything)
-}
-
-template <bool HAS_HI>
-__global__ __launch_bounds__(256) void k_g_check_queries(GKeys K, const uint64_t* __restrict__ off, uint32_t nq, uint32_t* __restrict__ flag) {
+__global__ __launch_bounds__(256) void k_g_check_queries(SortedKeys K, const uint64_t* __restrict__ off, uint32_t nq, uint32_t* __restrict__ flag) {
     const uint64_t e = off[0] + (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (e >= off[nq]) return;
-    g_check_order<HAS_HI>(K, off, 0, nq, e, K.mn[e], HAS_HI ? K.hi[e] : 0ull, K.lo[e], flag);
+    sorted_check_order<HAS_HI>(K, off, 0, nq, e, K.mn[e], HAS_HI ? K.hi[e] : 0ull, K.lo[e], flag);
 }
 
 // grid.x = tile of reference keys, grid.y = query.  edges[i] = reference (relative to nq) << 48 | query << 32 | query key
 // (relative to off[0]); *n_edges counts every match, also those beyond `cap` (the host then makes room and runs this again).
 template <bool HAS_HI>
-__global__ __launch_bounds__(kGmThreads) void k_g_match(GKeys K, const uint64_t* __restrict__ off, uint32_t n, uint32_t nq,
+__global__ __launch_bounds__(kGmThreads) void k_g_match(SortedKeys K, const uint64_t* __restrict__ off, uint32_t n, uint32_t nq,
                                                         unsigned long long* __restrict__ edges, unsigned long long cap,
                                                         unsigned long long* __restrict__ n_edges, uint32_t* __restrict__ u,
                                                         uint32_t* __restrict__ qcnt, uint32_t* __restrict__ flag) {
@@ -92,9 +67,9 @@ __global__ __launch_bounds__(kGmThreads) void k_g_match(GKeys K, const uint64_t*
         if (valid) {
             const uint32_t mn = K.mn[e];
             const uint64_t lo = K.lo[e], hi = HAS_HI ? K.hi[e] : 0ull;
-            if (q == 0) g_check_order<HAS_HI>(K, off, nq, n, e, mn, hi, lo, flag);
+            if (q == 0) sorted_check_order<HAS_HI>(K, off, nq, n, e, mn, hi, lo, flag);
             uint64_t a = qs, b = qe;                       // first query key that is not below this one
-            while (a < b) { const uint64_t mid = a + ((b - a) >> 1); if (g_less<HAS_HI>(K, mid, mn, hi, lo)) a = mid + 1; else b = mid; }
+            while (a < b) { const uint64_t mid = a + ((b - a) >> 1); if (keys_less<HAS_HI>(K, mid, mn, hi, lo)) a = mid + 1; else b = mid; }
             at = a;
             found = a < qe && K.mn[a] == mn && K.lo[a] == lo && (!HAS_HI || K.hi[a] == hi);
         }
@@ -104,7 +79,7 @@ __global__ __launch_bounds__(kGmThreads) void k_g_match(GKeys K, const uint64_t*
         if (lane == (uint32_t)__ffsll((long long)word) - 1u) base = atomicAdd(n_edges, (unsigned long long)__popcll(word));
         base = __shfl(base, __ffsll((long long)word) - 1);
         if (!found) continue;
-        const uint32_t jr = g_sketch_of(off, nq, n, e) - nq;
+        const uint32_t jr = sorted_sketch_of(off, nq, n, e) - nq;
         const uint32_t qi = (uint32_t)(at - q_first);
         const unsigned long long pos = base + (unsigned long long)__popcll(word & ((1ull << lane) - 1ull));
         if (pos < cap) edges[pos] = (unsigned long long)jr << 48 | (unsigned long long)q << 32 | qi;
@@ -202,7 +177,7 @@ int gather_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const ui
     if (Qk > 0xfffffff0ull || Rk > 0xfffffff0ull) { set_error("too many sketch k-mers for one call"); return SPSP_ERR_OVERFLOW; }
     if (Qk == 0 || Rk == 0) return SPSP_OK;                // nothing can match: no rows
     if (!d_mn || !d_lo || (has_hi && !d_hi)) { set_error("NULL key array"); return SPSP_ERR_ARG; }
-    const GKeys K{d_mn, d_lo, d_hi};
+    const SortedKeys K{d_mn, d_lo, d_hi};
     int rc;
     // counters: [0] edges (64 bit), [2] order flag
     if ((rc = ctx->g_off.reserve(((size_t)n + 1) * 8)) || (rc = ctx->g_u.reserve((cells + 1) * 4)) || (rc = ctx->g_roff.reserve((cells + 1) * 4)) ||

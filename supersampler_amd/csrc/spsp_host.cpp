@@ -1863,6 +1863,39 @@ int spsp_neighbours_csv_host(const spsp_neighbour_row* rows, uint64_t n_rows, co
     return text_out(out, text, len);
 }
 
+int spsp_prevalence_csv_host(const spsp_prevalence_row* rows, uint32_t n_rows, const char* const* names, const uint64_t* card, int precision,
+                             char** text, uint64_t* len) {
+    if (!text || !len || (n_rows && (!rows || !names || !card))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    std::string out = "sketch,keys,core,shell,unique,absent,f_core,mean_holders\n";
+    char num[64];
+    for (uint32_t i = 0; i < n_rows; ++i) {
+        const spsp_prevalence_row& r = rows[i];
+        const uint64_t keys = card[i];
+        if (r.core + r.shell + r.unique + r.absent != keys) { set_error("prevalence row %u: its classes do not add up to the sketch's %llu keys", i, (unsigned long long)keys); return SPSP_ERR_ARG; }
+        out += names[i]; out += ',';
+        out += std::to_string(keys); out += ',';
+        out += std::to_string(r.core); out += ',';
+        out += std::to_string(r.shell); out += ',';
+        out += std::to_string(r.unique); out += ',';
+        out += std::to_string(r.absent); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, keys ? (double)r.core / (double)keys : 0.0)); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, keys ? (double)r.holders / (double)keys : 0.0)); out += '\n';
+    }
+    return text_out(out, text, len);
+}
+
+int spsp_spectrum_csv_host(const uint64_t* spectrum, uint32_t n_ref, char** text, uint64_t* len) {
+    if (!text || !len || !spectrum) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    uint64_t cumulative = 0;
+    for (uint32_t t = 1; t <= n_ref; ++t) cumulative += spectrum[t];
+    std::string out = "holders,keys,cumulative\n";
+    for (uint32_t t = 1; t <= n_ref; ++t) {
+        if (spectrum[t]) { out += std::to_string(t); out += ','; out += std::to_string(spectrum[t]); out += ','; out += std::to_string(cumulative); out += '\n'; }
+        cumulative -= spectrum[t];
+    }
+    return text_out(out, text, len);
+}
+
 int spsp_compare_files_rate(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, double min_threshold,
                             const char* out_prefix, int chatter, double rate) {
     return compare_files_impl(ctx, paths, n, n_query, precision, min_threshold, out_prefix, clamp_chatter(chatter), rate);

@@ -116,12 +116,14 @@ enum HostSlot {
     kHsNbRows = 20,         // ... its total over min(passing, top): the rows the call returns (u64)
     kHsNbPairs = 21,        // ... the copy of k_nb_count's count of cells with a passing end (u64)
     kHsNbBad = 22,          // ... and of its bad-cell word (u32): neighbours_cells_impl reads all four behind its first wait
-    kHostSlots = 23
+    kHsPvBad = 23,          // spsp_prevalence.hip: the copy of the count / read-back kernels' two u32 (keys out of order | a probe sequence
+                            // that went round the table << 32); prevalence_device_impl reads it behind its one wait
+    kHostSlots = 24
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
 static_assert(kHsIngestRecs == kHsIngestKept + 1 && kHsMultiVerdict == kHsOrderVerdict + 1 && kHsMultiVerdict < kHostSlots, "slots reached from their neighbour");
-static_assert(kHsNbCands == kHsClusterCount + 1 && kHsNbBad + 1 == kHostSlots, "the neighbours' four slots are the last ones");
+static_assert(kHsNbCands == kHsClusterCount + 1 && kHsPvBad == kHsNbBad + 1 && kHsPvBad + 1 == kHostSlots, "the neighbours' four slots, then the prevalence pass's one: the last ones");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -239,6 +241,10 @@ struct spsp_ctx {
     spsp::DevBuf cl_work, cl_rows;
     // neighbours (spsp_neighbours.hip): the per-row arrays and the counter words in one work area, the candidate list, the rows
     spsp::DevBuf nb_work, nb_cand, nb_rows;
+    // prevalence (spsp_prevalence.hip): sketch offsets, the key table in HBM (one 64-bit word per slot: claimer | counter << 32), h of
+    // every key occurrence, the rows, the flag words with the spectrum behind them
+    spsp::DevBuf pv_off, pv_table, pv_hold, pv_rows, pv_spec;
+    uint32_t pv_log2cap = 0;             // slots of the table the last prevalence call used, as a power of two
 };
 
 namespace spsp {
@@ -330,6 +336,11 @@ int neighbours_check_args(uint32_t n, uint32_t n_query, int metric, uint32_t num
 int neighbours_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n, uint32_t n_query, int metric,
                           uint32_t num, uint32_t den, uint32_t top, spsp_neighbour_row* rows, uint64_t cap, uint64_t* n_rows, uint32_t* passing,
                           uint64_t* n_pairs);
+// spsp_prevalence.hip: per row sketch the keys by class of holder count and the sum of the counts, the spectrum of the references'
+// union, h of every key occurrence (context-owned, on the device) -- over concatenated sorted key arrays, n_query == 0: all versus all
+int prevalence_check_args(uint32_t n, uint32_t n_query, uint32_t num, uint32_t den);
+int prevalence_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
+                           uint32_t n, uint32_t n_query, uint32_t num, uint32_t den, spsp_prevalence_row* rows, uint64_t* spectrum, uint32_t** d_holders);
 // the front half of every file driver (spsp_host.cpp): the payloads of n sketch files, in file order, and what their headers say
 struct LoadedSketches {
     std::vector<uint8_t*> data;                                    // into the context's read regions, or owned (own[i])
