@@ -660,6 +660,50 @@ int spsp_cluster_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int 
                        const char* out_prefix, int chatter, double rate,
                        spsp_cluster_row** rows /* may be NULL; spsp_free */, uint64_t* n_clusters /* may be NULL */);
 
+/* ---------------------------------------------------- representatives ---- */
+/* Greedy dereplication: the other answer to "which one do I keep" (not in the reference).  Single linkage chains, and a member
+ * need not touch its representative; this rule promises that NO TWO REPRESENTATIVES ARE LINKED and that EVERY MEMBER IS LINKED
+ * TO THE REPRESENTATIVE IT IS FILED UNDER.  On the comparator's keys, integers only.  Sketches are 0 .. n-1 in list order, c_i =
+ * the key count of sketch i, x_ij = the keys i and j share, the threshold is num / den with 1 <= num <= den <= 1 000 000, and
+ * w_i is a caller-given weight, 0 <= w_i < 2^47 (genome quality, say); without weights w_i = c_i.
+ *   1. LINK: the cluster pass's rule, to the letter (SPSP_CLUSTER_JACCARD / SPSP_CLUSTER_CONTAINMENT above; equality passes; two
+ *      empty sketches are never linked).
+ *   2. ORDER: a comes before b iff w_a > w_b, or w_a == w_b and a < b.
+ *   3. REPRESENTATIVES: going through the sketches in that order, a sketch is a representative iff it is linked to no
+ *      representative before it.  (The lexicographically first maximal independent set of the link graph: unique.)
+ *   4. ASSIGNMENT: a sketch that is not a representative goes to the best of the representatives it is linked to: p is better
+ *      than q iff x_p * u_q > x_q * u_p (128-bit products), u = c_i + c_p - x or min(c_i, c_p), the metric's denominator for the
+ *      pair; where the two fractions are equal, the representative that comes first in the order of 2.  At least one of the
+ *      representatives it is linked to comes before it; the best one need not.
+ *   5. ROWS: one spsp_cluster_row per sketch.  Clusters are numbered 0, 1, 2, ... in the order of their first-listed member;
+ *      size = the members filed under the representative, itself included; shared = x_{i,representative}, here always >= 1, and
+ *      c_i for the representative itself.
+ *
+ * d_cells, h_card: as spsp_cluster_cells_device takes them; the cells are only read.  h_weight: n weights (host), or NULL for the
+ * key counts.  rows receives n rows, *n_clusters the number of representatives, *n_edges the number of links, *n_rounds (may be
+ * NULL) the rounds the selection took.  Launches: init, edges (the links as one 32-bit word each, appended per wave), rounds of
+ * two small launches each (over the edges: a representative puts its later neighbours out, an undecided sketch blocks them;
+ * over the sketches: undecided and not blocked becomes a representative) queued in batches of 32, 64, ..., 1024 with ONE host
+ * wait per batch, then assign (a second pass over the cells: the best candidate per member by a 64-bit CAS), number, scan, rows
+ * and one last wait.  The rounds needed are the depth of the order's dependency chain: about ten on random graphs, up to n on a
+ * path that follows the order.  The work buffers belong to the context and are reused call after call.
+ * SPSP_ERR_ARG, before any kernel runs, for what spsp_cluster_cells_device refuses and for a weight of 2^47 or more;
+ * SPSP_ERR_ARG also for a cell with i >= j or j >= n (found by the edge kernel, which never indexes with such a pair): the rows
+ * are then zeroed.  n_cells == 0 is valid: n clusters of one. */
+int spsp_representatives_cells_device(spsp_ctx* ctx, const void* d_cells, uint64_t n_cells, const uint64_t* h_card,
+                                      const uint64_t* h_weight /* NULL: the key counts */, uint32_t n, int metric, uint32_t num,
+                                      uint32_t den, spsp_cluster_row* rows /* n */, uint64_t* n_clusters, uint64_t* n_edges,
+                                      uint32_t* n_rounds /* may be NULL */);
+/* The whole-file driver: spsp_cluster_files with this rule in place of single linkage -- the same loading, rate argument and
+ * refusals (k == m collections are SPSP_ERR_ARG), the all-vs-all as cells, the pass above, and spsp_cluster_csv_host for the text:
+ * the same columns.  Writes ONE file, <out_prefix>_representatives.csv.gz (gzip level 1).  h_weight: n weights, or NULL.
+ * chatter != 0: the reference's "kmers evaluated" line, one line with sketches, edges, representatives, the largest cluster and
+ * the rounds, and the common-rate line when a rate was asked for.  One device: there is no multi-device form. */
+int spsp_representatives_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, int metric, uint32_t num,
+                               uint32_t den, const uint64_t* h_weight /* NULL or n */, const char* out_prefix, int chatter,
+                               double rate, spsp_cluster_row** rows /* may be NULL; spsp_free */,
+                               uint64_t* n_clusters /* may be NULL */);
+
 /* --------------------------------------------------------- neighbours ---- */
 /* What the closest things to a sketch are: per sketch (or per query against a bank) the best few partners at or above a
  * threshold, best first (not in the reference, whose end product is the two n x n matrices).  On the comparator's keys,

@@ -118,6 +118,7 @@ ABI_SYMBOLS = [
     "spsp_keys_downsample_device", "spsp_sketch_header_host", "spsp_sketch_downsample_host", "spsp_compare_files_rate", "spsp_compare_files_multi_rate",
     "spsp_gather_device", "spsp_gather_csv_host", "spsp_gather_files",
     "spsp_cluster_cells_device", "spsp_cluster_csv_host", "spsp_cluster_files",
+    "spsp_representatives_cells_device", "spsp_representatives_files",
     "spsp_neighbours_cells_device", "spsp_neighbours_csv_host", "spsp_neighbours_files",
     "spsp_prevalence_device", "spsp_prevalence_csv_host", "spsp_spectrum_csv_host", "spsp_prevalence_files",
 ]
@@ -259,6 +260,11 @@ def lib():
         L.spsp_cluster_csv_host.argtypes = [vp, P(cp), u32, vp, i32, i32, P(vp), P(u64)]
         L.spsp_cluster_files.restype = i32
         L.spsp_cluster_files.argtypes = [vp, P(cp), u32, i32, i32, u32, u32, cp, i32, dbl, P(vp), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_representatives_cells_device"):
+        L.spsp_representatives_cells_device.restype = i32
+        L.spsp_representatives_cells_device.argtypes = [vp, vp, u64, vp, vp, u32, i32, u32, u32, vp, P(u64), P(u64), P(u32)]
+        L.spsp_representatives_files.restype = i32
+        L.spsp_representatives_files.argtypes = [vp, P(cp), u32, i32, i32, u32, u32, vp, cp, i32, dbl, P(vp), P(u64)]
     if not LIB_OVERRIDDEN or hasattr(L, "spsp_neighbours_cells_device"):
         L.spsp_neighbours_cells_device.restype = i32
         L.spsp_neighbours_cells_device.argtypes = [vp, vp, u64, vp, u32, u32, i32, u32, u32, u32, vp, u64, P(u64), vp, P(u64)]
@@ -969,6 +975,37 @@ class Context:
         arr, _alive = _paths_array(paths)
         out, nc = C.c_void_p(), C.c_uint64()
         _check(lib().spsp_cluster_files(self._h, arr, n, precision, metric, num, den, out_prefix.encode(), 0, _rate_arg(rate), C.byref(out), C.byref(nc)))
+        return np.frombuffer(_take(out, n * CLUSTER_ROW_DTYPE.itemsize), dtype=CLUSTER_ROW_DTYPE).copy(), nc.value
+
+    def representatives_cells_device(self, d_cells, n_cells, card, n, metric, num, den, weight=None):
+        """spsp_representatives_cells_device: greedy representatives of sketches 0 .. n-1 from the packed cells (i << 48 | j << 32 |
+        count) of their pair matrix on the device, the n key counts and, optionally, n weights (each below 2^47; None: the key
+        counts) -> (rows: CLUSTER_ROW_DTYPE array of n, n_clusters, n_edges, rounds).  The link test is cluster_cells_device's"""
+        card = np.ascontiguousarray(card, dtype=np.uint64)
+        if len(card) != n:
+            raise ValueError("representatives_cells_device: one key count per sketch")
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, dtype=np.uint64)
+            if len(weight) != n:
+                raise ValueError("representatives_cells_device: one weight per sketch")
+        rows = np.zeros(n, dtype=CLUSTER_ROW_DTYPE)
+        nc, ne, nr = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        _check(lib().spsp_representatives_cells_device(self._h, d_cells, n_cells, card.ctypes.data, weight.ctypes.data if weight is not None else None,
+                                                       n, metric, num, den, rows.ctypes.data, C.byref(nc), C.byref(ne), C.byref(nr)))
+        return rows, nc.value, ne.value, nr.value
+
+    def representatives_files(self, paths, out_prefix, metric, num, den, weight=None, precision=6, rate=0.0):
+        """spsp_representatives_files: sketch files -> <out_prefix>_representatives.csv.gz and (rows, n_clusters).  weight: one per
+        file, or None for the key counts.  rate: as compare_files"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, dtype=np.uint64)
+            if len(weight) != n:
+                raise ValueError("representatives_files: one weight per file")
+        out, nc = C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_representatives_files(self._h, arr, n, precision, metric, num, den, weight.ctypes.data if weight is not None else None,
+                                                out_prefix.encode(), 0, _rate_arg(rate), C.byref(out), C.byref(nc)))
         return np.frombuffer(_take(out, n * CLUSTER_ROW_DTYPE.itemsize), dtype=CLUSTER_ROW_DTYPE).copy(), nc.value
 
     def neighbours_cells_device(self, d_cells, n_cells, card, n, metric, num, den, top, n_query=None):

@@ -8,7 +8,9 @@
 // partner; Jaccard at 0 with none of the three (spsp_neighbours_files) -> <o>_neighbours.csv.gz.  A fourth: -P <t>, with or
 // without -q, counts instead how many of the index's sketches hold each key -- per sketch (per query) the keys that are core (held
 // by a share t of the index or more), shell, unique and absent, and the spectrum of the index's union (spsp_prevalence_files) ->
-// <o>_prevalence.csv.gz and <o>_spectrum.csv.gz.
+// <o>_prevalence.csv.gz and <o>_spectrum.csv.gz.  A fifth: -r <t> / -R <t> without -q picks representatives of the index instead --
+// greedy dereplication on Jaccard / on the larger containment at threshold t, best sketch first: by the weights of -w <file> (one
+// unsigned integer per sketch of -f, in list order), else by key count (spsp_representatives_files) -> <o>_representatives.csv.gz.
 #include <getopt.h>
 
 #include <chrono>
@@ -53,6 +55,28 @@ static bool parse_fraction(const char* t, uint32_t* num, uint32_t* den, bool zer
     return true;
 }
 
+// -w <file>: one unsigned decimal integer below 2^47 per sketch, in list order (blank lines are skipped)
+static bool read_weights(const string& path, size_t n, vector<uint64_t>& out, string& why) {
+    uint8_t* data = nullptr; uint64_t len = 0;
+    if (spsp_read_file_host(path.c_str(), &data, &len) != SPSP_OK) { why = "can't open it"; return false; }
+    istringstream is(string((const char*)data, len));
+    spsp_free(data);
+    string line;
+    while (getline(is, line)) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (line.empty()) continue;
+        uint64_t v = 0;
+        for (char c : line) {
+            if (c < '0' || c > '9') { why = "'" + line + "' is not an unsigned integer"; return false; }
+            v = v * 10 + (uint64_t)(c - '0');
+            if (v >> 47) { why = "'" + line + "' is not below 2^47"; return false; }
+        }
+        out.push_back(v);
+    }
+    if (out.size() != n) { why = to_string(out.size()) + " weights for " + to_string(n) + " sketches"; return false; }
+    return true;
+}
+
 int main(int argc, char** argv) {
     int ch;
     string inputfof, query, output_name("results");
@@ -70,7 +94,10 @@ int main(int argc, char** argv) {
     uint32_t nb_num = 0, nb_den = 1;
     bool prevalence = false;         // -P <t>: the letter is not in the reference's option string
     uint32_t pv_num = 0, pv_den = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:")) != -1) {
+    int rep_opts = 0, rep_metric = SPSP_CLUSTER_JACCARD;   // -r <t> / -R <t>, -w <file>: none of the three letters is in the reference's option string
+    uint32_t rep_num = 0, rep_den = 1;
+    string weights_file;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:")) != -1) {
         switch (ch) {
             case 'c':
             case 'C':
@@ -81,6 +108,16 @@ int main(int argc, char** argv) {
                 cluster_metric = ch == 'c' ? SPSP_CLUSTER_JACCARD : SPSP_CLUSTER_CONTAINMENT;
                 ++cluster_opts;
                 break;
+            case 'r':
+            case 'R':
+                if (!parse_fraction(optarg, &rep_num, &rep_den)) {
+                    cout << "-" << (char)ch << " takes a threshold in (0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
+                    return 1;
+                }
+                rep_metric = ch == 'r' ? SPSP_CLUSTER_JACCARD : SPSP_CLUSTER_CONTAINMENT;
+                ++rep_opts;
+                break;
+            case 'w': weights_file = optarg; break;
             case 'P':
                 if (!parse_fraction(optarg, &pv_num, &pv_den)) {
                     cout << "-P takes a threshold in (0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
@@ -133,6 +170,19 @@ int main(int argc, char** argv) {
     if (nb_opts && !neighbours) { cout << "-J / -K / -I set the threshold of the neighbour lists: they need -N" << endl; return 1; }
     if (neighbours && (gather || cluster_opts)) { cout << "-N lists neighbours: not together with -g, -c or -C" << endl; return 1; }
     if (prevalence && (gather || cluster_opts || neighbours)) { cout << "-P counts the holders of every key: not together with -g, -c, -C or -N" << endl; return 1; }
+    if (rep_opts > 1) { cout << "-r (Jaccard) and -R (containment) pick representatives of the index: one of them, once" << endl; return 1; }
+    if (rep_opts && (cluster_opts || query != "" || gather || neighbours || prevalence)) {
+        cout << "-r / -R pick representatives of the index all versus all: not together with -c, -C, -q, -g, -N or -P" << endl;
+        return 1;
+    }
+    if (weights_file != "" && !rep_opts) { cout << "-w gives the weights -r / -R order the sketches by: it needs one of them" << endl; return 1; }
+    vector<uint64_t> weights;
+    if (weights_file != "" && inputfof != "") {
+        vector<string> listed;
+        if (!read_names(inputfof, listed)) return 1;
+        string why;
+        if (!read_weights(weights_file, listed.size(), weights, why)) { cout << "-w " << weights_file << ": " << why << endl; return 1; }
+    }
     if (inputfof == "") {
         cout << "Core arguments:" << endl
              << "-f Index file of files (mandatory)" << endl
@@ -198,6 +248,17 @@ int main(int argc, char** argv) {
         const string err = rc != SPSP_OK ? spsp_last_error() : "";
         if (ctx) spsp_destroy(ctx);
         if (rc != SPSP_OK) { cout << "Neighbours failed: " << err << endl; return 1; }
+        return 0;
+    }
+    if (rep_opts) {
+        // one device, as gather
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_representatives_files(ctx, paths.data(), (uint32_t)paths.size(), (int)p, rep_metric, rep_num, rep_den,
+                                                           weights.empty() ? nullptr : weights.data(), output_name.c_str(), 1, rate, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Representatives failed: " << err << endl; return 1; }
         return 0;
     }
     if (cluster_opts) {

@@ -86,4 +86,14 @@ __device__ __forceinline__ void sorted_check_order(const SortedKeys& K, const ui
     if (e != off[sorted_sketch_of(off, j0, j1, e)]) atomicOr(flag, 1u);   // (the first key of a sketch may be anything)
 }
 
+// The order of two fractions x_a / u_a and x_b / u_b without a division: x_a * u_b against x_b * u_a as 128-bit products.
+// > 0: a is the larger fraction, < 0: b, 0: equal (two different fractions that round to one double are still told apart).
+// The neighbours pass orders a row's partners by it, the representatives pass a member's candidates.
+__device__ __forceinline__ int fraction_cmp(unsigned long long x_a, unsigned long long u_a, unsigned long long x_b, unsigned long long u_b) {
+    const unsigned long long lo_a = x_a * u_b, hi_a = __umul64hi(x_a, u_b), lo_b = x_b * u_a, hi_b = __umul64hi(x_b, u_a);
+    if (hi_a != hi_b) return hi_a > hi_b ? 1 : -1;
+    if (lo_a != lo_b) return lo_a > lo_b ? 1 : -1;
+    return 0;
+}
+
 }  // namespace spsp

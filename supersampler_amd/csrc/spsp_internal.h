@@ -118,12 +118,19 @@ enum HostSlot {
     kHsNbBad = 22,          // ... and of its bad-cell word (u32): neighbours_cells_impl reads all four behind its first wait
     kHsPvBad = 23,          // spsp_prevalence.hip: the copy of the count / read-back kernels' two u32 (keys out of order | a probe sequence
                             // that went round the table << 32); prevalence_device_impl reads it behind its one wait
-    kHostSlots = 24
+    kHsRpUndecided = 24,    // spsp_representatives.hip: the copy of the sketches still undecided behind a batch of rounds (u32), queued behind
+                            // the batch; representatives_cells_impl reads it behind that batch's wait
+    kHsRpEdges = 25,        // ... of k_rp_edges' edge count (u64), in the same wait: sizes the later batches' grids, and is *n_edges
+    kHsRpBad = 26,          // ... and of two u32 (k_rp_edges' bad-cell word | the round that decided the last sketch << 32), in the same wait
+    kHsRpCount = 27,        // ... launch_scan_u32's total over the "is its cluster's first member" flags: the representatives (u64);
+                            // representatives_cells_impl reads it behind its last wait
+    kHostSlots = 28
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
 static_assert(kHsIngestRecs == kHsIngestKept + 1 && kHsMultiVerdict == kHsOrderVerdict + 1 && kHsMultiVerdict < kHostSlots, "slots reached from their neighbour");
-static_assert(kHsNbCands == kHsClusterCount + 1 && kHsPvBad == kHsNbBad + 1 && kHsPvBad + 1 == kHostSlots, "the neighbours' four slots, then the prevalence pass's one: the last ones");
+static_assert(kHsNbCands == kHsClusterCount + 1 && kHsPvBad == kHsNbBad + 1 && kHsPvBad + 1 == kHsRpUndecided, "the neighbours' four slots, then the prevalence pass's one");
+static_assert(kHsRpCount == kHsRpUndecided + 3 && kHsRpCount + 1 == kHostSlots, "the representatives pass's four slots: the last ones");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -245,6 +252,9 @@ struct spsp_ctx {
     // every key occurrence, the rows, the flag words with the spectrum behind them
     spsp::DevBuf pv_off, pv_table, pv_hold, pv_rows, pv_spec;
     uint32_t pv_log2cap = 0;             // slots of the table the last prevalence call used, as a power of two
+    // representatives (spsp_representatives.hip): the per-sketch arrays and the counter words in one work area, the edge list (one
+    // 32-bit word per link, room for one per cell), the rows
+    spsp::DevBuf rp_work, rp_edges, rp_rows;
 };
 
 namespace spsp {
@@ -331,6 +341,10 @@ int cluster_check_args(uint32_t n, int metric, uint32_t num, uint32_t den);
 int cluster_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n, int metric, uint32_t num, uint32_t den,
                           const uint64_t* ds_threshold, uint32_t* k_out, uint32_t* m_out, uint64_t* card, std::vector<spsp_cluster_row>* rows,
                           uint64_t* n_clusters, uint64_t* n_edges);
+// spsp_representatives.hip: greedy representatives of the sketches 0 .. n-1 from the packed cells (on the device, only read);
+// h_weight: null = the key counts
+int representatives_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, const uint64_t* h_weight, uint32_t n,
+                               int metric, uint32_t num, uint32_t den, spsp_cluster_row* rows, uint64_t* n_clusters, uint64_t* n_edges, uint32_t* n_rounds);
 // spsp_neighbours.hip: each row sketch's best `top` partners at or above num / den from the packed cells (on the device, only read)
 int neighbours_check_args(uint32_t n, uint32_t n_query, int metric, uint32_t num, uint32_t den, uint32_t top);
 int neighbours_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n, uint32_t n_query, int metric,

@@ -140,11 +140,8 @@ constexpr unsigned long long kNbEmpty = 0xFFFFull;
 
 // a strictly in front of b: x_a * u_b > x_b * u_a in 128 bits, the smaller partner where the products are equal
 __device__ __forceinline__ bool nb_before(const NbCand& a, const NbCand& b) {
-    const unsigned long long xa = a.w >> 16, xb = b.w >> 16;
-    const unsigned long long lo_a = xa * b.u, hi_a = __umul64hi(xa, b.u), lo_b = xb * a.u, hi_b = __umul64hi(xb, a.u);
-    if (hi_a != hi_b) return hi_a > hi_b;
-    if (lo_a != lo_b) return lo_a > lo_b;
-    return (a.w & 0xFFFFull) < (b.w & 0xFFFFull);
+    const int cmp = fraction_cmp(a.w >> 16, a.u, b.w >> 16, b.u);
+    return cmp ? cmp > 0 : (a.w & 0xFFFFull) < (b.w & 0xFFFFull);
 }
 
 __device__ __forceinline__ NbCand nb_from(const NbCand& v, uint32_t src_lane) {
