@@ -829,6 +829,76 @@ int spsp_prevalence_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, u
                           const char* out_prefix, int chatter, double rate,
                           spsp_prevalence_row** rows /* may be NULL; spsp_free */, uint64_t** spectrum /* may be NULL; spsp_free */);
 
+/* ------------------------------------------------------- linkage tree ---- */
+/* The single-linkage hierarchy of a collection, once, instead of one clustering per guessed threshold (not in the reference).
+ * The single-linkage hierarchy of a graph is its maximum spanning forest: the forest's edges, best score first, are the merges,
+ * and cutting them at a threshold t leaves the connected components of ALL links at t -- what spsp_cluster_cells_device reports
+ * at t.  On the comparator's keys, integers only.  Sketches are 0 .. n-1 in list order, c_i = the key count of sketch i, x = the
+ * keys two sketches share.
+ *   1. CANDIDATES.  A cell (i < j, x) is a candidate edge iff x >= 1 and x * den >= num * u, u = c_i + c_j - x
+ *      (SPSP_CLUSTER_JACCARD) or min(c_i, c_j) (SPSP_CLUSTER_CONTAINMENT): the cluster pass's link test, to the letter, at the
+ *      FLOOR num / den with 0 <= num <= den <= 1 000 000, den >= 1 (num == 0: every cell that shares a key).
+ *   2. ORDER.  Edge a comes before edge b iff x_a * u_b > x_b * u_a (128-bit products); where the two fractions are equal, iff
+ *      (i_a, j_a) < (i_b, j_b).  A strict total order: the forest is unique, a property of the SET of cells.
+ *   3. FOREST.  Going through the candidates in that order, an edge is kept iff its two ends are not yet connected by kept
+ *      edges (Kruskal).  The kept edges number n - (the clusters spsp_cluster_cells_device reports at the floor).
+ *   4. ROWS.  One spsp_tree_row per kept edge, in that order: the best merge first. */
+typedef struct spsp_tree_row {   /* 24 bytes */
+    uint32_t a, b;       /* the cell's two sketches, a < b */
+    uint32_t size;       /* sketches in the merged cluster after this merge */
+    uint32_t reserved;   /* 0 */
+    uint64_t shared;     /* x: the keys the two share */
+} spsp_tree_row;
+
+/* d_cells, h_card: as spsp_cluster_cells_device takes them (key counts below 2^47); the cells are only read.  rows has room for
+ * n - 1 rows (may be NULL when n == 1); *n_rows receives how many there are, *n_edges the candidate edges, *n_rounds (may be
+ * NULL) the rounds that merged anything.  Boruvka's algorithm in the order of 2: init, edges (the candidates appended to a
+ * list, one atomic per workgroup and tile), then floor(log2 n) rounds of three small launches -- pick (every edge still between two
+ * components is offered to both components' best-edge words by a 64-bit CAS, and moves on to the next round's list), hook (a
+ * component's best edge is written down once and the two components are united), flatten (every sketch's root) -- all queued
+ * at once, and ONE host wait at the end; a round with nothing left returns at its first load.  The forest's at most n - 1
+ * edges are put into the order of 2 on the host.  The work buffers belong to the context and are reused call after call.
+ * SPSP_ERR_ARG, before any kernel runs, for n == 0, n > 65535, a metric other than the two, num > den, den == 0,
+ * den > 1 000 000 and a key count of 2^47 or more; SPSP_ERR_ARG also for a cell with i >= j or j >= n (found by the edge kernel,
+ * which never indexes with such a pair): the n - 1 rows are then zeroed.  n_cells == 0 is valid: no rows. */
+int spsp_tree_cells_device(spsp_ctx* ctx, const void* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n, int metric,
+                           uint32_t num, uint32_t den, spsp_tree_row* rows /* n - 1 */, uint64_t* n_rows, uint64_t* n_edges,
+                           uint32_t* n_rounds /* may be NULL */);
+/* The clustering at a threshold, from the rows alone.  The rows of a tree built at the floor floor_num / floor_den that pass the
+ * candidate test at num / den (num == 0: all of them) are taken, and their connected components numbered 0, 1, 2, ... in the
+ * order of their first-listed member: cluster[i] (n words) and *n_clusters are the `cluster` column and the count of
+ * spsp_cluster_cells_device at num / den on the cells the tree was built from (the cut property of a maximum spanning forest).
+ * SPSP_ERR_ARG for a cut below the floor (num * floor_den < floor_num * den), either fraction outside 0 <= num <= den <=
+ * 1 000 000, den >= 1, and a row that does not name a < b < n. */
+int spsp_tree_cut_host(const spsp_tree_row* rows, uint64_t n_rows, uint32_t n, const uint64_t* card, int metric,
+                       uint32_t floor_num, uint32_t floor_den, uint32_t num, uint32_t den, uint32_t* cluster /* n */,
+                       uint64_t* n_clusters);
+/* The rows as text: the line "step,a,b,shared,keys_a,keys_b,score,size,clusters", then one line per row -- step counts from 1,
+ * names[a], names[b], shared, card[a], card[b] in decimal, score = shared / u as an IEEE double division printed as the matrices
+ * print a score (%.<precision>g; only printed: the integer order has decided), size, and clusters = n - step: what is left after
+ * the merge.  A row that does not name a < b < n, or more than n - 1 rows, is SPSP_ERR_ARG.  *text is released with spsp_free(). */
+int spsp_tree_csv_host(const spsp_tree_row* rows, uint64_t n_rows, const char* const* names, uint32_t n, const uint64_t* card,
+                       int metric, int precision, char** text, uint64_t* len);
+/* The rows as ONE Newick tree.  A leaf is names[i] inside single quotes, an inner ' doubled, at height 0; row r's node joins the
+ * clusters its two sketches are in at height h = 1.0 - (double)shared / (double)u (IEEE doubles: printed, they decide nothing);
+ * a branch length is h_parent - h_child, formed in double and printed with %.<precision>g (never negative: the rows come best
+ * first and correctly rounded division is monotone).  Of a node's two children the one whose subtree holds the smaller sketch
+ * index comes first.  Components that never merge are joined at height 1.0 one after another in first-member order -- ((A,B),C)
+ * for three of them.  n == 1: 'name';  The text ends with ";\n".  No recursion: a path of 65 535 sketches is a legal input.  A row
+ * that does not name a < b < n, or one whose two sketches are joined already, is SPSP_ERR_ARG.  *text is released with
+ * spsp_free(). */
+int spsp_tree_newick_host(const spsp_tree_row* rows, uint64_t n_rows, const char* const* names, uint32_t n, const uint64_t* card,
+                          int metric, int precision, char** text, uint64_t* len);
+/* The whole-file driver: spsp_cluster_files' loading, rate argument and refusals (k == m collections are SPSP_ERR_ARG), the
+ * all-vs-all as cells, the pass above.  Writes TWO files, <out_prefix>_tree.csv.gz (spsp_tree_csv_host, gzip level 1) and
+ * <out_prefix>_tree.nwk (spsp_tree_newick_host, plain text), and no matrices.  chatter != 0: the reference's "kmers evaluated"
+ * line, one line with sketches, candidate edges, forest rows, the components left and the rounds, and the common-rate line when
+ * a rate was asked for.  rows (may be NULL) receives a copy of the rows, released with spsp_free(); n_rows may be NULL.  One
+ * device: there is no multi-device form. */
+int spsp_tree_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, int metric, uint32_t num, uint32_t den,
+                    const char* out_prefix, int chatter, double rate, spsp_tree_row** rows /* may be NULL; spsp_free */,
+                    uint64_t* n_rows /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,13 @@ class NeighbourRow(C.Structure):
 NEIGHBOUR_ROW_DTYPE = np.dtype([("sketch", "<u4"), ("rank", "<u4"), ("neighbour", "<u4"), ("reserved", "<u4"), ("shared", "<u8")])
 NEIGHBOUR_JACCARD, NEIGHBOUR_CONTAINMENT, NEIGHBOUR_CONTAINED = 0, 1, 2
 
+class TreeRow(C.Structure):
+    """spsp_tree_row: one merge of a collection's single-linkage tree (include/spsp.h)"""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("size", C.c_uint32), ("reserved", C.c_uint32), ("shared", C.c_uint64)]
+
+
+TREE_ROW_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("size", "<u4"), ("reserved", "<u4"), ("shared", "<u8")])
+
 # spsp_prevalence_row: a row sketch's keys by class of holder count, and the sum of the holder counts (include/spsp.h)
 PREVALENCE_ROW_DTYPE = np.dtype([("core", "<u8"), ("shell", "<u8"), ("unique", "<u8"), ("absent", "<u8"), ("holders", "<u8")])
 
@@ -121,6 +128,7 @@ ABI_SYMBOLS = [
     "spsp_representatives_cells_device", "spsp_representatives_files",
     "spsp_neighbours_cells_device", "spsp_neighbours_csv_host", "spsp_neighbours_files",
     "spsp_prevalence_device", "spsp_prevalence_csv_host", "spsp_spectrum_csv_host", "spsp_prevalence_files",
+    "spsp_tree_cells_device", "spsp_tree_cut_host", "spsp_tree_csv_host", "spsp_tree_newick_host", "spsp_tree_files",
 ]
 
 _lib = None
@@ -281,6 +289,17 @@ def lib():
         L.spsp_spectrum_csv_host.argtypes = [vp, u32, P(vp), P(u64)]
         L.spsp_prevalence_files.restype = i32
         L.spsp_prevalence_files.argtypes = [vp, P(cp), u32, u32, i32, u32, u32, cp, i32, dbl, P(vp), P(vp)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_tree_cells_device"):
+        L.spsp_tree_cells_device.restype = i32
+        L.spsp_tree_cells_device.argtypes = [vp, vp, u64, vp, u32, i32, u32, u32, vp, P(u64), P(u64), P(u32)]
+        L.spsp_tree_cut_host.restype = i32
+        L.spsp_tree_cut_host.argtypes = [vp, u64, u32, vp, i32, u32, u32, u32, u32, vp, P(u64)]
+        L.spsp_tree_csv_host.restype = i32
+        L.spsp_tree_csv_host.argtypes = [vp, u64, P(cp), u32, vp, i32, i32, P(vp), P(u64)]
+        L.spsp_tree_newick_host.restype = i32
+        L.spsp_tree_newick_host.argtypes = [vp, u64, P(cp), u32, vp, i32, i32, P(vp), P(u64)]
+        L.spsp_tree_files.restype = i32
+        L.spsp_tree_files.argtypes = [vp, P(cp), u32, i32, i32, u32, u32, cp, i32, dbl, P(vp), P(u64)]
     _lib = L
     return L
 
@@ -451,6 +470,43 @@ def cluster_csv(rows, names, card, metric, precision=6):
     out, ln = C.c_void_p(), C.c_uint64()
     _check(lib().spsp_cluster_csv_host(rows.ctypes.data, arr, n, card.ctypes.data, metric, precision, C.byref(out), C.byref(ln)))
     return _take(out, ln.value)
+
+
+def tree_cut(rows, card, metric, floor_num, floor_den, num, den):
+    """spsp_tree_cut_host: the rows of a linkage tree built at the floor floor_num / floor_den (TREE_ROW_DTYPE array), cut at
+    num / den (not below the floor) -> (cluster: np.uint32 per sketch, numbered by first-listed member, n_clusters): what
+    cluster_cells_device reports at num / den on the same cells"""
+    rows = np.ascontiguousarray(rows, dtype=TREE_ROW_DTYPE)
+    card = np.ascontiguousarray(card, dtype=np.uint64)
+    n = len(card)
+    cluster = np.zeros(n, dtype=np.uint32)
+    nc = C.c_uint64()
+    _check(lib().spsp_tree_cut_host(rows.ctypes.data, len(rows), n, card.ctypes.data, metric, floor_num, floor_den, num, den, cluster.ctypes.data, C.byref(nc)))
+    return cluster, nc.value
+
+
+def _tree_text(call, what, rows, names, card, metric, precision):
+    rows = np.ascontiguousarray(rows, dtype=TREE_ROW_DTYPE)
+    card = np.ascontiguousarray(card, dtype=np.uint64)
+    n = len(names)
+    if len(card) != n:
+        raise ValueError("%s: one key count per name" % what)
+    arr = (C.c_char_p * n)(*[s.encode() for s in names])
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(call(rows.ctypes.data, len(rows), arr, n, card.ctypes.data, metric, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def tree_csv(rows, names, card, metric, precision=6):
+    """spsp_tree_csv_host: linkage-tree rows (TREE_ROW_DTYPE array, best merge first) -> the text of <prefix>_tree.csv.gz;
+    card[i] = key count of sketch i as the comparison saw it"""
+    return _tree_text(lib().spsp_tree_csv_host, "tree_csv", rows, names, card, metric, precision)
+
+
+def tree_newick(rows, names, card, metric, precision=6):
+    """spsp_tree_newick_host: linkage-tree rows -> the text of <prefix>_tree.nwk: one Newick tree, quoted names, node height
+    1 - score, what never merged joined at height 1"""
+    return _tree_text(lib().spsp_tree_newick_host, "tree_newick", rows, names, card, metric, precision)
 
 
 def neighbours_csv(rows, passing, names, card, metric, n_query=None, precision=6):
@@ -1007,6 +1063,28 @@ class Context:
         _check(lib().spsp_representatives_files(self._h, arr, n, precision, metric, num, den, weight.ctypes.data if weight is not None else None,
                                                 out_prefix.encode(), 0, _rate_arg(rate), C.byref(out), C.byref(nc)))
         return np.frombuffer(_take(out, n * CLUSTER_ROW_DTYPE.itemsize), dtype=CLUSTER_ROW_DTYPE).copy(), nc.value
+
+    def tree_cells_device(self, d_cells, n_cells, card, n, metric, num, den):
+        """spsp_tree_cells_device: the single-linkage tree of sketches 0 .. n-1 from the packed cells (i << 48 | j << 32 | count) of
+        their pair matrix on the device and the n key counts, over the cells that pass cluster_cells_device's link test at the
+        floor num / den (num == 0: every cell that shares a key) -> (rows: TREE_ROW_DTYPE array, best merge first, n_edges: the
+        candidate edges, rounds: the rounds that merged anything)"""
+        card = np.ascontiguousarray(card, dtype=np.uint64)
+        if len(card) != n:
+            raise ValueError("tree_cells_device: one key count per sketch")
+        rows = np.zeros(max(n, 1) - 1, dtype=TREE_ROW_DTYPE)
+        nr, ne, rounds = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        _check(lib().spsp_tree_cells_device(self._h, d_cells, n_cells, card.ctypes.data, n, metric, num, den, rows.ctypes.data if len(rows) else None,
+                                            C.byref(nr), C.byref(ne), C.byref(rounds)))
+        return rows[:nr.value].copy(), ne.value, rounds.value
+
+    def tree_files(self, paths, out_prefix, metric, num, den, precision=6, rate=0.0):
+        """spsp_tree_files: sketch files -> <out_prefix>_tree.csv.gz, <out_prefix>_tree.nwk and the rows.  rate: as compare_files"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        out, nr = C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_tree_files(self._h, arr, n, precision, metric, num, den, out_prefix.encode(), 0, _rate_arg(rate), C.byref(out), C.byref(nr)))
+        return np.frombuffer(_take(out, nr.value * TREE_ROW_DTYPE.itemsize), dtype=TREE_ROW_DTYPE).copy()
 
     def neighbours_cells_device(self, d_cells, n_cells, card, n, metric, num, den, top, n_query=None):
         """spsp_neighbours_cells_device: per row sketch (every sketch, or the first n_query) the best `top` partners at or above

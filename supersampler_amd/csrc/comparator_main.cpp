@@ -11,6 +11,8 @@
 // <o>_prevalence.csv.gz and <o>_spectrum.csv.gz.  A fifth: -r <t> / -R <t> without -q picks representatives of the index instead --
 // greedy dereplication on Jaccard / on the larger containment at threshold t, best sketch first: by the weights of -w <file> (one
 // unsigned integer per sketch of -f, in list order), else by key count (spsp_representatives_files) -> <o>_representatives.csv.gz.
+// A sixth: -l <floor> / -L <floor> without -q builds the index's single-linkage tree instead -- on Jaccard / on the larger containment,
+// over the pairs at or above the floor, 0 for every pair that shares a key (spsp_tree_files) -> <o>_tree.csv.gz and <o>_tree.nwk.
 #include <getopt.h>
 
 #include <chrono>
@@ -97,8 +99,19 @@ int main(int argc, char** argv) {
     int rep_opts = 0, rep_metric = SPSP_CLUSTER_JACCARD;   // -r <t> / -R <t>, -w <file>: none of the three letters is in the reference's option string
     uint32_t rep_num = 0, rep_den = 1;
     string weights_file;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:")) != -1) {
+    int tree_opts = 0, tree_metric = SPSP_CLUSTER_JACCARD;   // -l <floor> / -L <floor>: neither letter is in the reference's option string
+    uint32_t tree_num = 0, tree_den = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:")) != -1) {
         switch (ch) {
+            case 'l':
+            case 'L':
+                if (!parse_fraction(optarg, &tree_num, &tree_den, true)) {
+                    cout << "-" << (char)ch << " takes a floor in [0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
+                    return 1;
+                }
+                tree_metric = ch == 'l' ? SPSP_CLUSTER_JACCARD : SPSP_CLUSTER_CONTAINMENT;
+                ++tree_opts;
+                break;
             case 'c':
             case 'C':
                 if (!parse_fraction(optarg, &cluster_num, &cluster_den)) {
@@ -175,6 +188,11 @@ int main(int argc, char** argv) {
         cout << "-r / -R pick representatives of the index all versus all: not together with -c, -C, -q, -g, -N or -P" << endl;
         return 1;
     }
+    if (tree_opts > 1) { cout << "-l (Jaccard) and -L (containment) build the index's linkage tree: one of them, once" << endl; return 1; }
+    if (tree_opts && (cluster_opts || query != "" || gather || neighbours || prevalence || rep_opts)) {
+        cout << "-l / -L build the linkage tree of the index all versus all: not together with -q, -g, -c, -C, -N, -P, -r or -R" << endl;
+        return 1;
+    }
     if (weights_file != "" && !rep_opts) { cout << "-w gives the weights -r / -R order the sketches by: it needs one of them" << endl; return 1; }
     vector<uint64_t> weights;
     if (weights_file != "" && inputfof != "") {
@@ -227,6 +245,17 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (tree_opts) {
+        // one device, as gather
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_tree_files(ctx, paths.data(), (uint32_t)paths.size(), (int)p, tree_metric, tree_num, tree_den, output_name.c_str(), 1, rate,
+                                                nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Linkage tree failed: " << err << endl; return 1; }
+        return 0;
     }
     if (prevalence) {
         // one device, as gather; the rows are every sketch of the index (n_query 0) or the queries

@@ -45,34 +45,7 @@ constexpr int kClCardBits = 47;
 // the counter words at the head of the work area
 enum ClWord : uint32_t { kClwEdges = 0 /* u64: words 0-1 */, kClwBad = 2 /* u32 */, kClwWords = 4 };
 
-__device__ __forceinline__ uint32_t cl_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x, whose parent word was just read as p; every second node on the way is handed to its grandparent
-__device__ __forceinline__ uint32_t cl_find(uint32_t* __restrict__ parent, uint32_t x, uint32_t p) {
-    while (p != x) {
-        const uint32_t g = cl_load(parent + p);
-        if (g == p) return p;
-        atomicMin(parent + x, g);                          // (never back to a farther ancestor, whoever else halves here)
-        x = g;
-        p = cl_load(parent + x);
-    }
-    return x;
-}
-
-__device__ __forceinline__ void cl_union(uint32_t* __restrict__ parent, uint32_t a, uint32_t b) {
-    uint32_t pa = cl_load(parent + a), pb = cl_load(parent + b);
-    for (;;) {
-        if (pa == pb) return;                              // two loads say "one tree already": the common case of a large component
-        a = cl_find(parent, a, pa);
-        b = cl_find(parent, b, pb);
-        if (a == b) return;
-        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const uint32_t was = atomicCAS(parent + hi, hi, lo);
-        if (was == hi) return;
-        a = was; pa = cl_load(parent + a);                 // hi was hooked by somebody else meanwhile: on from where it hangs now
-        b = lo; pb = cl_load(parent + b);
-    }
-}
+// cl_load / cl_find / cl_union: spsp_device.h (the linkage tree hooks with the same three)
 
 __global__ __launch_bounds__(256) void k_cl_init(uint32_t n, uint32_t* __restrict__ parent, uint32_t* __restrict__ size,
                                                  unsigned long long* __restrict__ best, unsigned long long* __restrict__ shared,

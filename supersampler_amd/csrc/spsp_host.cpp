@@ -1728,6 +1728,69 @@ int text_out(const std::string& out, char** text, uint64_t* len) {
 }
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ the linkage tree's helpers
+namespace {
+inline uint64_t tree_under(int metric, const uint64_t* card, uint32_t a, uint32_t b, uint64_t x) {
+    return metric == SPSP_CLUSTER_JACCARD ? card[a] + card[b] - x : std::min(card[a], card[b]);
+}
+int tree_check_metric(int metric) {
+    if (metric == SPSP_CLUSTER_JACCARD || metric == SPSP_CLUSTER_CONTAINMENT) return SPSP_OK;
+    set_error("tree metric %d: 0 (Jaccard) or 1 (containment)", metric);
+    return SPSP_ERR_ARG;
+}
+int tree_check_rows(const spsp_tree_row* rows, uint64_t n_rows, uint32_t n) {
+    if (n_rows >= n) { set_error("%llu tree rows over %u sketches: a forest has n - 1 at the most", (unsigned long long)n_rows, n); return SPSP_ERR_ARG; }
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (rows[r].a >= rows[r].b || rows[r].b >= n) { set_error("tree row %llu does not name two sketches a < b < n", (unsigned long long)r); return SPSP_ERR_ARG; }
+    return SPSP_OK;
+}
+// union-find over the sketches on the host: the root of a set is its first-listed member
+struct TreeSets {
+    std::vector<uint32_t> up;
+    explicit TreeSets(uint32_t n) : up(n) { for (uint32_t i = 0; i < n; ++i) up[i] = i; }
+    uint32_t find(uint32_t x) {
+        uint32_t r = x;
+        while (up[r] != r) r = up[r];
+        while (up[x] != r) { const uint32_t next = up[x]; up[x] = r; x = next; }
+        return r;
+    }
+    uint32_t unite(uint32_t a, uint32_t b) { if (a > b) std::swap(a, b); up[b] = a; return a; }   // of two roots -> the new root
+};
+void newick_leaf(std::string& out, const char* name) {
+    out += '\'';
+    for (const char* c = name; *c; ++c) { if (*c == '\'') out += '\''; out += *c; }
+    out += '\'';
+}
+}  // namespace
+
+// the forest's cell words in any order -> the rows in the rule's order (the better fraction first by 128-bit cross products, then
+// the smaller (i, j)), each with the size of the cluster its merge makes
+int spsp::tree_rows_host(const uint64_t* forest, uint64_t n_forest, const uint64_t* card, uint32_t n, int metric, spsp_tree_row* rows) {
+    struct Edge { uint64_t word, u; };
+    std::vector<Edge> edges(n_forest);
+    for (uint64_t e = 0; e < n_forest; ++e) {
+        const uint64_t c = forest[e];
+        const uint32_t a = (uint32_t)(c >> 48), b = (uint32_t)(c >> 32) & 0xffffu;
+        if (a >= b || b >= n) { set_error("forest edge %llu does not name two sketches a < b < n", (unsigned long long)e); return SPSP_ERR_ARG; }
+        edges[e] = Edge{c, tree_under(metric, card, a, b, c & 0xffffffffull)};
+    }
+    std::sort(edges.begin(), edges.end(), [](const Edge& p, const Edge& q) {
+        const u128 l = (u128)(p.word & 0xffffffffull) * q.u, r = (u128)(q.word & 0xffffffffull) * p.u;
+        return l != r ? l > r : (p.word >> 32) < (q.word >> 32);
+    });
+    TreeSets sets(n);
+    std::vector<uint32_t> size(n, 1);
+    for (uint64_t e = 0; e < n_forest; ++e) {
+        const uint64_t c = edges[e].word;
+        const uint32_t a = (uint32_t)(c >> 48), b = (uint32_t)(c >> 32) & 0xffffu, ra = sets.find(a), rb = sets.find(b);
+        if (ra == rb) { set_error("forest edge (%u, %u) closes a cycle", a, b); return SPSP_ERR_ARG; }
+        const uint32_t total = size[ra] + size[rb];
+        size[sets.unite(ra, rb)] = total;
+        rows[e].a = a; rows[e].b = b; rows[e].size = total; rows[e].reserved = 0; rows[e].shared = c & 0xffffffffull;
+    }
+    return SPSP_OK;
+}
+
 extern "C" {
 
 // chatter: 0 = silent; 1 = the stdout lines of the reference's all-versus-all run (Comparator.cpp:56,69,364,414,
@@ -1893,6 +1956,121 @@ int spsp_spectrum_csv_host(const uint64_t* spectrum, uint32_t n_ref, char** text
         if (spectrum[t]) { out += std::to_string(t); out += ','; out += std::to_string(spectrum[t]); out += ','; out += std::to_string(cumulative); out += '\n'; }
         cumulative -= spectrum[t];
     }
+    return text_out(out, text, len);
+}
+
+// ------------------------------------------------------------------------------------------------ the linkage tree
+int spsp_tree_cut_host(const spsp_tree_row* rows, uint64_t n_rows, uint32_t n, const uint64_t* card, int metric, uint32_t floor_num, uint32_t floor_den,
+                       uint32_t num, uint32_t den, uint32_t* cluster, uint64_t* n_clusters) {
+    if (!cluster || !n_clusters || !card || (n_rows && !rows)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    *n_clusters = 0;
+    int rc;
+    if ((rc = tree_check_metric(metric))) return rc;
+    if (n == 0 || n > 65535) { set_error("a tree is over 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
+    if (floor_den == 0 || floor_num > floor_den || floor_den > 1000000u || den == 0 || num > den || den > 1000000u) {
+        set_error("tree cut %u / %u at floor %u / %u: both need 0 <= num <= den, 1 <= den <= 1000000", num, den, floor_num, floor_den);
+        return SPSP_ERR_ARG;
+    }
+    if ((uint64_t)num * floor_den < (uint64_t)floor_num * den) {
+        set_error("tree cut %u / %u is below the floor %u / %u the tree was built at", num, den, floor_num, floor_den);
+        return SPSP_ERR_ARG;
+    }
+    if ((rc = tree_check_rows(rows, n_rows, n))) return rc;
+    const uint64_t u_max = num ? ~0ull / num : ~0ull;      // the link test's guard
+    TreeSets sets(n);
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        const uint64_t x = rows[r].shared, u = tree_under(metric, card, rows[r].a, rows[r].b, x);
+        if (!(x >= 1 && u <= u_max && (u128)x * den >= (u128)num * u)) continue;
+        const uint32_t ra = sets.find(rows[r].a), rb = sets.find(rows[r].b);
+        if (ra != rb) sets.unite(ra, rb);
+    }
+    uint32_t count = 0;
+    for (uint32_t i = 0; i < n; ++i) {                     // a root is its set's first-listed member: numbered before its members are
+        const uint32_t r = sets.find(i);
+        cluster[i] = r == i ? count++ : cluster[r];
+    }
+    *n_clusters = count;
+    return SPSP_OK;
+}
+
+int spsp_tree_csv_host(const spsp_tree_row* rows, uint64_t n_rows, const char* const* names, uint32_t n, const uint64_t* card, int metric, int precision,
+                       char** text, uint64_t* len) {
+    if (!text || !len || (n_rows && (!rows || !names || !card))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    int rc;
+    if ((rc = tree_check_metric(metric)) || (rc = tree_check_rows(rows, n_rows, std::max(n, 1u)))) return rc;
+    std::string out = "step,a,b,shared,keys_a,keys_b,score,size,clusters\n";
+    char num[64];
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        const spsp_tree_row& t = rows[r];
+        const uint64_t under = tree_under(metric, card, t.a, t.b, t.shared);
+        out += std::to_string(r + 1); out += ',';
+        out += names[t.a]; out += ',';
+        out += names[t.b]; out += ',';
+        out += std::to_string(t.shared); out += ',';
+        out += std::to_string(card[t.a]); out += ',';
+        out += std::to_string(card[t.b]); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, (double)t.shared / (double)under)); out += ',';   // (printed only: the integer order has decided)
+        out += std::to_string(t.size); out += ',';
+        out += std::to_string(n - (r + 1)); out += '\n';
+    }
+    return text_out(out, text, len);
+}
+
+int spsp_tree_newick_host(const spsp_tree_row* rows, uint64_t n_rows, const char* const* names, uint32_t n, const uint64_t* card, int metric, int precision,
+                          char** text, uint64_t* len) {
+    if (!text || !len || !names || (n_rows && (!rows || !card))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    int rc;
+    if ((rc = tree_check_metric(metric))) return rc;
+    if (n == 0 || n > 65535) { set_error("a tree is over 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
+    if ((rc = tree_check_rows(rows, n_rows, n))) return rc;
+    // nodes: 0 .. n-1 the leaves, then one per row, then one per join of two components that never merged: 2 n - 1 in all
+    const uint32_t kNone = 0xFFFFFFFFu;
+    std::vector<uint32_t> left(2 * (size_t)n - 1, kNone), right(2 * (size_t)n - 1, kNone), above(2 * (size_t)n - 1, kNone);
+    std::vector<double> height(2 * (size_t)n - 1, 0.0);
+    std::vector<uint32_t> node_of(n);                      // a set's root sketch (its first-listed member) -> the node on top of the set
+    for (uint32_t i = 0; i < n; ++i) node_of[i] = i;
+    TreeSets sets(n);
+    uint32_t nodes = n;
+    auto join = [&](uint32_t ra, uint32_t rb, double h) {  // two roots: the set with the smaller first member comes first
+        if (ra > rb) std::swap(ra, rb);
+        left[nodes] = node_of[ra]; right[nodes] = node_of[rb]; height[nodes] = h;
+        above[node_of[ra]] = nodes; above[node_of[rb]] = nodes;
+        node_of[sets.unite(ra, rb)] = nodes++;
+    };
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        const uint32_t ra = sets.find(rows[r].a), rb = sets.find(rows[r].b);
+        if (ra == rb) { set_error("tree row %llu joins two sketches that are joined already", (unsigned long long)r); return SPSP_ERR_ARG; }
+        join(ra, rb, 1.0 - (double)rows[r].shared / (double)tree_under(metric, card, rows[r].a, rows[r].b, rows[r].shared));
+    }
+    for (uint32_t i = 1; i < n; ++i)                       // what never merged: at height 1, one after another (sketch 0 is in the first)
+        if (sets.find(i) == i) join(0, i, 1.0);
+    // written by an explicit stack (a path of 65 535 sketches is 65 534 levels deep): a node, or what follows a node
+    enum : uint32_t { kOpen = 0, kComma = 1, kClose = 2, kLength = 3 };
+    struct Item { uint32_t node, what; };
+    std::vector<Item> stack;
+    std::string out;
+    char num[64];
+    stack.push_back(Item{nodes - 1, kOpen});
+    while (!stack.empty()) {
+        const Item it = stack.back();
+        stack.pop_back();
+        if (it.what == kComma) { out += ','; continue; }
+        if (it.what == kClose) { out += ')'; continue; }
+        if (it.what == kLength) {
+            out += ':';
+            out.append(num, format_g(num, sizeof num, precision, height[above[it.node]] - height[it.node]));
+            continue;
+        }
+        if (it.node < n) { newick_leaf(out, names[it.node]); continue; }
+        out += '(';
+        stack.push_back(Item{0, kClose});
+        stack.push_back(Item{right[it.node], kLength});
+        stack.push_back(Item{right[it.node], kOpen});
+        stack.push_back(Item{0, kComma});
+        stack.push_back(Item{left[it.node], kLength});
+        stack.push_back(Item{left[it.node], kOpen});
+    }
+    out += ";\n";
     return text_out(out, text, len);
 }
 

@@ -124,13 +124,17 @@ enum HostSlot {
     kHsRpBad = 26,          // ... and of two u32 (k_rp_edges' bad-cell word | the round that decided the last sketch << 32), in the same wait
     kHsRpCount = 27,        // ... launch_scan_u32's total over the "is its cluster's first member" flags: the representatives (u64);
                             // representatives_cells_impl reads it behind its last wait
-    kHostSlots = 28
+    kHsTrEdges = 28,        // spsp_tree.hip: the copy of the candidate-edge count k_tr_pick's first round wrote down (u64)
+    kHsTrBad = 29,          // ... of two u32 (k_tr_edges' bad-cell word | the forest's edge count << 32)
+    kHsTrRounds = 30,       // ... and of the rounds that hooked anything (u32): tree_cells_impl reads all three behind its one wait
+    kHostSlots = 31
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
 static_assert(kHsIngestRecs == kHsIngestKept + 1 && kHsMultiVerdict == kHsOrderVerdict + 1 && kHsMultiVerdict < kHostSlots, "slots reached from their neighbour");
 static_assert(kHsNbCands == kHsClusterCount + 1 && kHsPvBad == kHsNbBad + 1 && kHsPvBad + 1 == kHsRpUndecided, "the neighbours' four slots, then the prevalence pass's one");
-static_assert(kHsRpCount == kHsRpUndecided + 3 && kHsRpCount + 1 == kHostSlots, "the representatives pass's four slots: the last ones");
+static_assert(kHsRpCount == kHsRpUndecided + 3 && kHsRpCount + 1 == kHsTrEdges, "the representatives pass's four slots, then the linkage tree's");
+static_assert(kHsTrRounds == kHsTrEdges + 2 && kHsTrRounds + 1 == kHostSlots, "the linkage tree's three slots: the last ones");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -255,6 +259,9 @@ struct spsp_ctx {
     // representatives (spsp_representatives.hip): the per-sketch arrays and the counter words in one work area, the edge list (one
     // 32-bit word per link, room for one per cell), the rows
     spsp::DevBuf rp_work, rp_edges, rp_rows;
+    // linkage tree (spsp_tree.hip): the per-sketch arrays and the counter words in one work area, the two lists of live edges (one
+    // cell word per candidate, room for one per cell in each), the forest's cell words
+    spsp::DevBuf tr_work, tr_edges, tr_forest;
 };
 
 namespace spsp {
@@ -345,6 +352,13 @@ int cluster_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const u
 // h_weight: null = the key counts
 int representatives_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, const uint64_t* h_weight, uint32_t n,
                                int metric, uint32_t num, uint32_t den, spsp_cluster_row* rows, uint64_t* n_clusters, uint64_t* n_edges, uint32_t* n_rounds);
+// spsp_tree.hip: the single-linkage tree (the maximum spanning forest in the order of include/spsp.h) of the sketches 0 .. n-1 from
+// the packed cells (on the device, only read); num == 0 is a floor.  tree_rows_host (spsp_host.cpp): the forest's cell words, in
+// any order -> the rows in the rule's order, with their sizes
+int tree_check_args(uint32_t n, int metric, uint32_t num, uint32_t den);
+int tree_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n, int metric, uint32_t num, uint32_t den,
+                    spsp_tree_row* rows, uint64_t* n_rows, uint64_t* n_edges, uint32_t* n_rounds);
+int tree_rows_host(const uint64_t* forest, uint64_t n_forest, const uint64_t* card, uint32_t n, int metric, spsp_tree_row* rows);
 // spsp_neighbours.hip: each row sketch's best `top` partners at or above num / den from the packed cells (on the device, only read)
 int neighbours_check_args(uint32_t n, uint32_t n_query, int metric, uint32_t num, uint32_t den, uint32_t top);
 int neighbours_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, const uint64_t* h_card, uint32_t n, uint32_t n_query, int metric,
