@@ -899,6 +899,69 @@ int spsp_tree_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int pre
                     const char* out_prefix, int chatter, double rate, spsp_tree_row** rows /* may be NULL; spsp_free */,
                     uint64_t* n_rows /* may be NULL */);
 
+/* ---------------------------------------------------------- selection ---- */
+/* The keys of a collection whose holder count lies in a band, as sketches again (not in the reference): what the prevalence pass
+ * counts -- core, shell, unique, absent -- and the union and the intersection beside them, written so that every comparison above
+ * can read them.  Notation as for the prevalence pass: sketches 0 .. n-1, n_query == 0: every sketch is a row and a reference
+ * (R = n); n_query > 0: the first n_query sketches are rows only, the R = n - n_query behind them the references; h(x) = the
+ * references that hold key x.
+ * BAND.  A pair h_min, h_max of unsigned 32-bit numbers: a key passes iff h_min <= h(x) <= h_max.  h_min > h_max is a valid, empty
+ * band.  Nothing else decides.
+ * EACH (merged == 0).  Every row sketch keeps its passing keys in their old order: n_rows = (n_query ? n_query : n) sketches back
+ * to back and n_rows + 1 offsets.
+ * MERGED (merged != 0).  The distinct keys of the references' union that pass, strictly increasing by (minimizer, kmer_hi,
+ * kmer_lo): ONE sketch, two offsets.  Queries take no part (n_query must be 0) and h == 0 cannot occur.
+ *
+ * Input: the concatenated sorted key arrays every comparison takes (the decoder's, the downsampler's, or an earlier selection's);
+ * they are only read.  Output: arrays OWNED BY THE CONTEXT, valid until the next select call but one on it (two sets are used in
+ * turn: a selection may read the one before it), distinct from the decoder's, the downsampler's and the prevalence pass's
+ * buffers, ready for spsp_compare_device, spsp_gather_device, spsp_prevalence_device and a further select.  The call uses the
+ * prevalence pass's table and holders[] (a d_holders pointer obtained earlier is overwritten).
+ * SPSP_ERR_ARG for n == 0, n > 65535, n_query >= n, merged with n_query > 0, a context switched to unordered keys, and keys that
+ * are not strictly increasing inside a sketch (sk_off_out is then zeroed); SPSP_ERR_OVERFLOW beyond 0xfffffff0 keys.  Launches,
+ * the same chain whatever the keys are: the prevalence pass's table fill (memset, count, read back), a flag kernel over holders[]
+ * (one ballot word per 64 keys, one count per tile of 2048), the downsampling pass's compaction (scan, move, offsets) and ONE host
+ * wait for the offsets; merged: the read-back also marks the one occurrence that claimed each key's slot, only those are flagged,
+ * and the compacted keys are sorted as one segment behind that wait (the count sizes the sort), with the sort's own wait. */
+int spsp_keys_select_device(spsp_ctx* ctx, uint32_t k, const void* d_minimizer, const void* d_kmer_lo, const void* d_kmer_hi /* NULL if k <= 32 */,
+                            const uint64_t* h_sk_off, uint32_t n, uint32_t n_query, uint32_t h_min, uint32_t h_max, int merged,
+                            void** d_out_minimizer, void** d_out_kmer_lo, void** d_out_kmer_hi,
+                            uint64_t* sk_off_out /* each: n_rows + 1; merged: 2 */);
+/* A band from a word, for R >= 1 references (bin/comparator -S / -E and the Python interface read the same text).  Each named
+ * class is the class of that name the prevalence pass counts at threshold <t>, with core_min = ceil(num * R / den):
+ *     union, present   [1, R]
+ *     absent           [0, 0]                                   (meaningful with queries)
+ *     all              [R, R]                                   (the intersection)
+ *     core=<t>         [core_min, R]
+ *     unique=<t>       [1, 1] if core_min > 1, else empty
+ *     shell=<t>        [2, core_min - 1], empty when core_min <= 2
+ *     <a>..<b>         [a, b], plain unsigned 32-bit integers   (a > b: empty)
+ * <t> is a decimal in (0, 1] with at most six digits behind the point, read as text into num / 10^digits as -c and -P read
+ * theirs.  An empty band is returned as [1, 0].  Anything else is SPSP_ERR_ARG. */
+int spsp_select_band_host(const char* what, uint32_t R, uint32_t* h_min, uint32_t* h_max);
+/* A sketch payload from n keys, sorted and distinct ((minimizer, kmer_hi, kmer_lo) strictly increasing; k-mers canonical, as every
+ * key array above holds them).  Header "<2k-m> <m> <n> <rate>\n" with the rate printed as the sketcher prints it; one bucket per
+ * distinct minimizer, ascending: its m letters, a zero blob size (no maximal super-k-mers), per key ONE non-maximal super-k-mer of
+ * exactly k bases as "prefix\nsuffix\n", and the closing "\n\n".  A k-mer is written in the orientation in which the minimizer's
+ * value occurs literally (the canonical one when both hold it), split at its first occurrence there, so that the reader rebuilds
+ * exactly that k-mer: spsp_sketch_parse_host of the payload returns the keys that went in.  About k - m + 2 bytes per key before
+ * gzip; keys are NOT compacted into maximal super-k-mers.  SPSP_ERR_ARG for k == m, for keys out of order, and for a key whose
+ * minimizer occurs in neither orientation of its k-mer (the message names the key's index).  *payload is released with
+ * spsp_free(). */
+int spsp_sketch_from_keys_host(uint32_t k, uint32_t m, double rate, const uint32_t* minimizer, const uint64_t* kmer_lo,
+                               const uint64_t* kmer_hi /* NULL if k <= 32 */, uint64_t n, uint8_t** payload, uint64_t* len);
+/* The whole-file driver: the files are read, inflated and decoded as spsp_prevalence_files does it, with the same `rate` argument
+ * and refusals (k == m collections are SPSP_ERR_ARG), the band `what` is read by spsp_select_band_host for R = n - n_query, the
+ * selection runs, and the selected keys are written by spsp_sketch_from_keys_host at gzip level 9, as the sketcher writes.
+ * each == 0 (merged; n_query must be 0): ONE file, <out_prefix>_select.gz.  each != 0: one file per row sketch i,
+ * <out_prefix>_<i>_<basename of paths[i]>, and <out_prefix>_select.txt, which lists them in order -- a file of files for -f / -q.
+ * The rate written into the headers: the common rate when one was asked for; else the headers' own rate if they all stand for one
+ * selection threshold; else SPSP_ERR_ARG ("sketches of different rates: give a rate").  chatter != 0: the reference's "kmers
+ * evaluated" line, one line with R, the band, keys in and keys written, and the common-rate line when a rate was asked for.
+ * *keys_in (the rows' keys; merged: the references') and *keys_out may be NULL.  One device: there is no multi-device form. */
+int spsp_select_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, const char* what, int each,
+                      const char* out_prefix, int chatter, double rate, uint64_t* keys_in /* may be NULL */, uint64_t* keys_out /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,7 @@ ABI_SYMBOLS = [
     "spsp_neighbours_cells_device", "spsp_neighbours_csv_host", "spsp_neighbours_files",
     "spsp_prevalence_device", "spsp_prevalence_csv_host", "spsp_spectrum_csv_host", "spsp_prevalence_files",
     "spsp_tree_cells_device", "spsp_tree_cut_host", "spsp_tree_csv_host", "spsp_tree_newick_host", "spsp_tree_files",
+    "spsp_keys_select_device", "spsp_select_band_host", "spsp_sketch_from_keys_host", "spsp_select_files",
 ]
 
 _lib = None
@@ -300,6 +301,15 @@ def lib():
         L.spsp_tree_newick_host.argtypes = [vp, u64, P(cp), u32, vp, i32, i32, P(vp), P(u64)]
         L.spsp_tree_files.restype = i32
         L.spsp_tree_files.argtypes = [vp, P(cp), u32, i32, i32, u32, u32, cp, i32, dbl, P(vp), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_keys_select_device"):
+        L.spsp_keys_select_device.restype = i32
+        L.spsp_keys_select_device.argtypes = [vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, i32, P(vp), P(vp), P(vp), vp]
+        L.spsp_select_band_host.restype = i32
+        L.spsp_select_band_host.argtypes = [cp, u32, P(u32), P(u32)]
+        L.spsp_sketch_from_keys_host.restype = i32
+        L.spsp_sketch_from_keys_host.argtypes = [u32, u32, dbl, vp, vp, vp, u64, P(vp), P(u64)]
+        L.spsp_select_files.restype = i32
+        L.spsp_select_files.argtypes = [vp, P(cp), u32, u32, cp, i32, cp, i32, dbl, P(u64), P(u64)]
     _lib = L
     return L
 
@@ -399,6 +409,29 @@ def sketch_downsample(payload, rate):
     out, n = C.c_void_p(), C.c_uint64()
     _check(lib().spsp_sketch_downsample_host(payload, len(payload), float(rate), C.byref(out), C.byref(n)))
     return _take(out, n.value)
+
+
+def sketch_from_keys(k, m, rate, mn, lo, hi=None):
+    """spsp_sketch_from_keys_host: sorted distinct keys (minimizer, kmer_lo[, kmer_hi for k > 32]) -> an uncompressed sketch payload
+    that sketch_parse reads back as exactly those keys: one non-maximal super-k-mer of k bases per key"""
+    mn = np.ascontiguousarray(mn, dtype=np.uint32)
+    lo = np.ascontiguousarray(lo, dtype=np.uint64)
+    if len(lo) != len(mn) or (hi is not None and len(hi) != len(mn)):
+        raise ValueError("sketch_from_keys: one kmer_lo (and kmer_hi) per minimizer")
+    if hi is not None:
+        hi = np.ascontiguousarray(hi, dtype=np.uint64)
+    out, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_sketch_from_keys_host(k, m, float(rate), mn.ctypes.data, lo.ctypes.data, hi.ctypes.data if hi is not None else None,
+                                            len(mn), C.byref(out), C.byref(n)))
+    return _take(out, n.value)
+
+
+def select_band(what, R):
+    """spsp_select_band_host: a band word (union, present, absent, all, core=<t>, unique=<t>, shell=<t>, <a>..<b>) among R
+    references -> (h_min, h_max); an empty band is (1, 0)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_select_band_host(str(what).encode(), R, C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def _rate_arg(rate):
@@ -1144,3 +1177,28 @@ class Context:
         n_rows = n_query if n_query else n
         return (np.frombuffer(_take(rows, n_rows * PREVALENCE_ROW_DTYPE.itemsize), dtype=PREVALENCE_ROW_DTYPE).copy(),
                 np.frombuffer(_take(spec, (n - n_query + 1) * 8), dtype=np.uint64).copy())
+
+    def select_device(self, k, d_min, d_lo, d_hi, sk_off, n, h_min, h_max, merged=False, n_query=0):
+        """spsp_keys_select_device: the keys whose number of holders among the references lies in [h_min, h_max], over concatenated
+        sorted key arrays on the device -> (d_minimizer, d_kmer_lo, d_kmer_hi or None, sk_off np.uint64): every row sketch's own,
+        order kept (n_rows + 1 offsets), or merged=True the distinct keys of the references' union, sorted, as one sketch (two
+        offsets) -- in arrays the context owns, valid until the next select call but one"""
+        sk_off = np.ascontiguousarray(sk_off, dtype=np.uint64)
+        if len(sk_off) != n + 1:
+            raise ValueError("select_device: n + 1 sketch offsets")
+        o_mn, o_lo, o_hi = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        out = np.zeros(2 if merged else max(n_query if n_query else n, 1) + 1, dtype=np.uint64)
+        _check(lib().spsp_keys_select_device(self._h, k, d_min, d_lo, d_hi, sk_off.ctypes.data, n, n_query, h_min, h_max, 1 if merged else 0,
+                                             C.byref(o_mn), C.byref(o_lo), C.byref(o_hi), out.ctypes.data))
+        return o_mn.value, o_lo.value, o_hi.value, out
+
+    def select_files(self, paths, prefix, what, each=False, n_query=0, rate=None):
+        """spsp_select_files: sketch files (the n_query queries first, or none) -> the keys in the band `what` (select_band's words)
+        as sketch files: <prefix>_select.gz, or each=True one <prefix>_<i>_<basename> per row sketch and the list
+        <prefix>_select.txt -> (keys in, keys written).  rate: None or 0.0 (the headers' rates, which must agree), a rate, or "auto" for the coarsest of the files'"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        k_in, k_out = C.c_uint64(), C.c_uint64()
+        _check(lib().spsp_select_files(self._h, arr, n, n_query, str(what).encode(), 1 if each else 0, prefix.encode(), 0,
+                                       _rate_arg(0.0 if rate is None else rate), C.byref(k_in), C.byref(k_out)))
+        return k_in.value, k_out.value

@@ -13,6 +13,10 @@
 // unsigned integer per sketch of -f, in list order), else by key count (spsp_representatives_files) -> <o>_representatives.csv.gz.
 // A sixth: -l <floor> / -L <floor> without -q builds the index's single-linkage tree instead -- on Jaccard / on the larger containment,
 // over the pairs at or above the floor, 0 for every pair that shares a key (spsp_tree_files) -> <o>_tree.csv.gz and <o>_tree.nwk.
+// A seventh: -S <what> without -q / -E <what> with or without -q writes SKETCHES instead -- the keys whose number of holders in the
+// index lies in the band <what> names (union, present, absent, all, core=<t>, unique=<t>, shell=<t>, <a>..<b>): -S the distinct
+// keys of the index as one sketch, <o>_select.gz; -E every sketch's (every query's) own, <o>_<i>_<its file name>, listed in
+// <o>_select.txt (spsp_select_files).
 #include <getopt.h>
 
 #include <chrono>
@@ -101,8 +105,23 @@ int main(int argc, char** argv) {
     string weights_file;
     int tree_opts = 0, tree_metric = SPSP_CLUSTER_JACCARD;   // -l <floor> / -L <floor>: neither letter is in the reference's option string
     uint32_t tree_num = 0, tree_den = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:")) != -1) {
+    int select_opts = 0;             // -S <what> / -E <what>: neither letter is in the reference's option string
+    bool select_each = false;
+    string select_what;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:")) != -1) {
         switch (ch) {
+            case 'S':
+            case 'E': {
+                uint32_t a = 0, b = 0;
+                if (spsp_select_band_host(optarg, 1, &a, &b) != SPSP_OK) {   // (the words are checked here; the band itself needs the number of references)
+                    cout << "-" << (char)ch << " takes a band of holder counts: " << spsp_last_error() << endl;
+                    return 1;
+                }
+                select_each = ch == 'E';
+                select_what = optarg;
+                ++select_opts;
+                break;
+            }
             case 'l':
             case 'L':
                 if (!parse_fraction(optarg, &tree_num, &tree_den, true)) {
@@ -193,6 +212,12 @@ int main(int argc, char** argv) {
         cout << "-l / -L build the linkage tree of the index all versus all: not together with -q, -g, -c, -C, -N, -P, -r or -R" << endl;
         return 1;
     }
+    if (select_opts > 1) { cout << "-S (one merged sketch) and -E (every sketch's own) write the selected keys: one of them, once" << endl; return 1; }
+    if (select_opts && (gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts)) {
+        cout << "-S / -E write sketches: not together with -g, -c, -C, -N, -P, -r, -R, -l or -L" << endl;
+        return 1;
+    }
+    if (select_opts && !select_each && query != "") { cout << "-S writes the index's keys as one sketch: not together with -q (-E selects from the queries)" << endl; return 1; }
     if (weights_file != "" && !rep_opts) { cout << "-w gives the weights -r / -R order the sketches by: it needs one of them" << endl; return 1; }
     vector<uint64_t> weights;
     if (weights_file != "" && inputfof != "") {
@@ -245,6 +270,17 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (select_opts) {
+        // one device, as gather; the rows of -E are every sketch of the index (n_query 0) or the queries
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_select_files(ctx, paths.data(), (uint32_t)paths.size(), query == "" ? 0u : n_query, select_what.c_str(), select_each ? 1 : 0,
+                                                  output_name.c_str(), 1, rate, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Select failed: " << err << endl; return 1; }
+        return 0;
     }
     if (tree_opts) {
         // one device, as gather

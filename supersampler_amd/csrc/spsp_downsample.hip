@@ -11,7 +11,8 @@
 //   k_ds_move     one workgroup per tile: the tile's 32 ballot words -> a prefix per word; lane l of a kept key writes at
 //                 tile offset + word prefix + popcount(word below l): neighbouring survivors land side by side
 //   k_ds_offsets  one thread per sketch boundary: survivors in front of it = its tile's offset + the bits in front of it
-// and ONE host wait, the one that reads the new offsets back.  No host path.
+// and ONE host wait, the one that reads the new offsets back.  No host path.  Everything behind the flags is ds_compact_launch
+// (spsp_internal.h): the selection (spsp_select.hip) makes its own keep mask in the same layout and runs the same three launches.
 #include <algorithm>
 
 #include "spsp_device.h"
@@ -20,10 +21,6 @@
 namespace spsp {
 
 namespace {
-
-constexpr uint32_t kDsThreads = 256;                       // 4 waves
-constexpr uint32_t kDsTile = 2048;                         // keys per workgroup: 8 rounds of 256
-constexpr uint32_t kDsWords = kDsTile / 64;                // ballot words per tile
 
 // round r of wave w of tile t fills word 32 t + 4 r + w of the keep mask: bit l of word j is key 64 j + l
 __global__ __launch_bounds__(kDsThreads) void k_ds_flag(const uint32_t* __restrict__ mn, uint32_t n_keys, uint64_t threshold,
@@ -102,6 +99,22 @@ __global__ __launch_bounds__(256) void k_ds_offsets(const uint64_t* __restrict__
 
 }  // namespace
 
+// (spsp_internal.h) scan, move, offsets: what follows a keep mask, whoever made it
+int ds_compact_launch(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const unsigned long long* d_mask,
+                      const uint32_t* d_tile_cnt, uint32_t* d_tile_off, uint32_t n_tiles, const uint64_t* d_off_in, uint32_t n_bounds, uint64_t* d_off_out,
+                      uint32_t* out_mn, uint64_t* out_lo, uint64_t* out_hi, uint64_t* total_host) {
+    int rc;
+    if ((rc = launch_scan_u32(ctx, d_tile_cnt, d_tile_off, n_tiles, total_host))) return rc;
+    if (has_hi) hipLaunchKernelGGL(k_ds_move<true>, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, d_lo, d_hi, d_mask, (const uint32_t*)d_tile_off,
+                                   out_mn, out_lo, out_hi);
+    else hipLaunchKernelGGL(k_ds_move<false>, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, d_lo, (const uint64_t*)nullptr, d_mask,
+                            (const uint32_t*)d_tile_off, out_mn, out_lo, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(k_ds_offsets, dim3((n_bounds + 255) / 256), dim3(256), 0, ctx->stream, d_off_in, n_bounds, n_tiles, d_mask, (const uint32_t*)d_tile_off,
+                       d_off_out);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+
 int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
                          const uint64_t* h_sk_off, uint32_t n, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out) {
     const bool has_hi = k > 32;
@@ -134,14 +147,8 @@ int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const ui
     SPSP_HIP(hipMemcpyAsync(d_off_in, rel.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_ds_flag, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, (uint32_t)R, threshold, d_mask, d_tile_cnt);
     SPSP_HIP(hipGetLastError());
-    if ((rc = launch_scan_u32(ctx, d_tile_cnt, d_tile_off, n_tiles, ctx->h_scalar + kHsDownsampleTotal))) return rc;
-    if (has_hi) hipLaunchKernelGGL(k_ds_move<true>, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, d_lo, d_hi, (const unsigned long long*)d_mask,
-                                   (const uint32_t*)d_tile_off, *out_mn, *out_lo, *out_hi);
-    else hipLaunchKernelGGL(k_ds_move<false>, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, d_lo, (const uint64_t*)nullptr,
-                            (const unsigned long long*)d_mask, (const uint32_t*)d_tile_off, *out_mn, *out_lo, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(k_ds_offsets, dim3((n + 1 + 255) / 256), dim3(256), 0, ctx->stream, (const uint64_t*)d_off_in, n + 1, n_tiles,
-                       (const unsigned long long*)d_mask, (const uint32_t*)d_tile_off, d_off_out);
-    SPSP_HIP(hipGetLastError());
+    if ((rc = ds_compact_launch(ctx, has_hi, d_mn, d_lo, d_hi, d_mask, d_tile_cnt, d_tile_off, n_tiles, d_off_in, n + 1, d_off_out, *out_mn, *out_lo, *out_hi,
+                                ctx->h_scalar + kHsDownsampleTotal))) return rc;
     SPSP_HIP(hipMemcpyAsync(sk_off_out, d_off_out, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
     SPSP_HIP(hipStreamSynchronize(ctx->stream));                    // (the one wait; `rel` has been read by then)
     return SPSP_OK;

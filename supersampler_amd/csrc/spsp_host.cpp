@@ -858,6 +858,122 @@ int spsp_sketch_downsample_host(const uint8_t* payload, uint64_t len, double rat
     return give(res);
 }
 
+// A sketch from keys: the writer the selection ends in.  One bucket per distinct minimizer, ascending: the minimizer's m letters, a
+// zero blob size (no maximal super-k-mers), per key ONE non-maximal super-k-mer of exactly k bases as "prefix\nsuffix\n", and the
+// closing "\n\n".  A key's k-mer is written in the orientation in which the minimizer's value occurs literally -- the canonical one
+// when both hold it -- split at the first occurrence there: the reader (the pair walk above, Comparator.cpp:226-260) puts the
+// minimizer back between the two halves and finds exactly one k-mer per pair, whose canonical form is the key's.
+int spsp_sketch_from_keys_host(uint32_t k, uint32_t m, double rate, const uint32_t* minimizer, const uint64_t* kmer_lo, const uint64_t* kmer_hi,
+                               uint64_t n, uint8_t** payload, uint64_t* len) {
+    if (!payload || !len || (n && (!minimizer || !kmer_lo))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    *payload = nullptr; *len = 0;
+    if (k < 1 || k > 63 || m < 1 || m > 15 || m > k) { set_error("k=%u m=%u: needs 1 <= m <= 15, m <= k <= 63", k, m); return SPSP_ERR_ARG; }
+    if (k == m) { set_error("a sketch cannot be written from keys when k == m (k = m = %u): a bucket's key is its bare minimizer", k); return SPSP_ERR_ARG; }
+    if (k > 32 && n && !kmer_hi) { set_error("NULL argument: k > 32 needs kmer_hi"); return SPSP_ERR_ARG; }
+    const uint32_t mmask = (uint32_t)((1ull << (2 * m)) - 1);
+    std::string out;
+    spsp::sketch_header_line(k, m, n, rate, out);
+    out.reserve(out.size() + (size_t)n * (k - m + 2) + 64);
+    char word[64];
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t mn = minimizer[i];
+        const u128 km = ((u128)(k > 32 ? kmer_hi[i] : 0) << 64) | kmer_lo[i];
+        if (i) {
+            const u128 before = ((u128)(k > 32 ? kmer_hi[i - 1] : 0) << 64) | kmer_lo[i - 1];
+            if (minimizer[i - 1] > mn || (minimizer[i - 1] == mn && before >= km)) {
+                set_error("key %llu does not come strictly after key %llu: keys must be strictly increasing by (minimizer, kmer_hi, kmer_lo)",
+                          (unsigned long long)i, (unsigned long long)(i - 1));
+                return SPSP_ERR_ARG;
+            }
+        }
+        // the first place the minimizer's value stands at, in the k-mer as the key holds it (canonical), else in its reverse complement
+        u128 as = km;
+        int at = -1;
+        if ((mn & ~mmask) == 0 && (k == 64 || (km >> (2 * k)) == 0)) {
+            for (int turn = 0; turn < 2 && at < 0; ++turn) {
+                if (turn) as = revcomp_kmer(km, k);
+                for (uint32_t q = 0; q + m <= k; ++q)
+                    if (((uint32_t)(as >> (2 * (k - m - q))) & mmask) == mn) { at = (int)q; break; }
+            }
+        }
+        if (at < 0) {
+            set_error("key %llu: its minimizer (%u) occurs in neither orientation of its k-mer", (unsigned long long)i, mn);
+            return SPSP_ERR_ARG;
+        }
+        if (i == 0 || minimizer[i - 1] != mn) {
+            if (i) out.append("\n\n", 2);
+            for (uint32_t j = 0; j < m; ++j) word[j] = kNuc[(mn >> (2 * (m - 1 - j))) & 3u];
+            out.append(word, m);
+            out.append(4, '\0');                               // the blob's size: no maximal super-k-mers
+        }
+        for (uint32_t j = 0; j < k; ++j) word[j] = kNuc[(uint32_t)(as >> (2 * (k - 1 - j))) & 3u];
+        out.append(word, (size_t)at);
+        out.push_back('\n');
+        out.append(word + at + m, (size_t)(k - m - (uint32_t)at));
+        out.push_back('\n');
+    }
+    if (n) out.append("\n\n", 2);
+    *payload = (uint8_t*)malloc(out.size() + 1);
+    if (!*payload) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    memcpy(*payload, out.data(), out.size());
+    *len = out.size();
+    return SPSP_OK;
+}
+
+// The band of holder counts a word stands for, among R references: the text bin/comparator -S / -E and the Python interface share.
+// <t> is read as -c and -P read theirs (bin/comparator's parse_fraction): a decimal in (0, 1] with at most six digits behind the
+// point, as TEXT into num / 10^digits; core_min = ceil(num * R / den) as the prevalence pass computes it.  An empty band is [1, 0]
+int spsp_select_band_host(const char* what, uint32_t R, uint32_t* h_min, uint32_t* h_max) {
+    if (!what || !h_min || !h_max) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    *h_min = 1; *h_max = 0;
+    if (R == 0) { set_error("a band of holder counts needs at least one reference"); return SPSP_ERR_ARG; }
+    auto fraction = [](const char* t, uint64_t* num, uint64_t* den) {
+        if ((t[0] != '0' && t[0] != '1') || (t[1] != 0 && t[1] != '.')) return false;
+        uint64_t a = (uint64_t)(t[0] - '0'), d = 1;
+        if (t[1] == '.') {
+            const char* f = t + 2;
+            if (*f == 0) return false;
+            for (; *f; ++f) {
+                if (*f < '0' || *f > '9' || d >= 1000000) return false;
+                a = a * 10 + (uint64_t)(*f - '0'); d *= 10;
+            }
+        }
+        if (a < 1 || a > d) return false;
+        *num = a; *den = d;
+        return true;
+    };
+    auto plain = [](const char* b, const char* e, uint32_t* v) {     // [b, e): decimal digits, below 2^32
+        if (b == e || e - b > 10) return false;
+        uint64_t x = 0;
+        for (const char* q = b; q < e; ++q) { if (*q < '0' || *q > '9') return false; x = x * 10 + (uint64_t)(*q - '0'); }
+        if (x > 0xffffffffull) return false;
+        *v = (uint32_t)x;
+        return true;
+    };
+    const std::string w(what);
+    if (w == "union" || w == "present") { *h_min = 1; *h_max = R; return SPSP_OK; }
+    if (w == "absent") { *h_min = 0; *h_max = 0; return SPSP_OK; }
+    if (w == "all") { *h_min = R; *h_max = R; return SPSP_OK; }
+    const size_t eq = w.find('=');
+    if (eq != std::string::npos) {
+        const std::string name = w.substr(0, eq);
+        uint64_t num = 0, den = 1;
+        if ((name == "core" || name == "unique" || name == "shell") && fraction(what + eq + 1, &num, &den)) {
+            const uint32_t core_min = (uint32_t)((num * R + den - 1) / den);
+            if (name == "core") { *h_min = core_min; *h_max = R; }
+            else if (name == "unique") { if (core_min > 1) { *h_min = 1; *h_max = 1; } }
+            else if (core_min > 2) { *h_min = 2; *h_max = core_min - 1; }
+            return SPSP_OK;
+        }
+    }
+    const size_t dots = w.find("..");
+    if (dots != std::string::npos && plain(what, what + dots, h_min) && plain(what + dots + 2, what + w.size(), h_max)) return SPSP_OK;
+    *h_min = 1; *h_max = 0;
+    set_error("'%.60s' is no band of holder counts: union, present, absent, all, core=<t>, unique=<t>, shell=<t> with <t> in (0, 1] and at most six "
+              "digits behind the point, or <a>..<b>", what);
+    return SPSP_ERR_ARG;
+}
+
 // print_containment / print_jaccard (Comparator.cpp:362-460); operator<<(double)
 // with setprecision(p) in the default float format is printf's %.*g.
 // sortCSV (sort_csv.cpp:26-111): put the rows and columns of a (symmetric, all-vs-all) Jaccard CSV into the order of

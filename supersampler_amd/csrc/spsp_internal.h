@@ -127,14 +127,18 @@ enum HostSlot {
     kHsTrEdges = 28,        // spsp_tree.hip: the copy of the candidate-edge count k_tr_pick's first round wrote down (u64)
     kHsTrBad = 29,          // ... of two u32 (k_tr_edges' bad-cell word | the forest's edge count << 32)
     kHsTrRounds = 30,       // ... and of the rounds that hooked anything (u32): tree_cells_impl reads all three behind its one wait
-    kHostSlots = 31
+    kHsSelBad = 31,         // spsp_select.hip: the copy of the table fill's two u32 (keys out of order | a probe sequence that went round
+                            // the table << 32); keys_select_impl reads it behind its first wait
+    kHsSelTotal = 32,       // ... and launch_scan_u32's total over the tiles' survivor counts: the keys selected (u64), in the same wait
+    kHostSlots = 33
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
 static_assert(kHsIngestRecs == kHsIngestKept + 1 && kHsMultiVerdict == kHsOrderVerdict + 1 && kHsMultiVerdict < kHostSlots, "slots reached from their neighbour");
 static_assert(kHsNbCands == kHsClusterCount + 1 && kHsPvBad == kHsNbBad + 1 && kHsPvBad + 1 == kHsRpUndecided, "the neighbours' four slots, then the prevalence pass's one");
 static_assert(kHsRpCount == kHsRpUndecided + 3 && kHsRpCount + 1 == kHsTrEdges, "the representatives pass's four slots, then the linkage tree's");
-static_assert(kHsTrRounds == kHsTrEdges + 2 && kHsTrRounds + 1 == kHostSlots, "the linkage tree's three slots: the last ones");
+static_assert(kHsTrRounds == kHsTrEdges + 2 && kHsTrRounds + 1 == kHsSelBad, "the linkage tree's three slots");
+static_assert(kHsSelTotal == kHsSelBad + 1 && kHsSelTotal + 1 == kHostSlots, "the selection's two slots: the last ones");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -262,6 +266,10 @@ struct spsp_ctx {
     // linkage tree (spsp_tree.hip): the per-sketch arrays and the counter words in one work area, the two lists of live edges (one
     // cell word per candidate, room for one per cell in each), the forest's cell words
     spsp::DevBuf tr_work, tr_edges, tr_forest;
+    // selection (spsp_select.hip): two sets of output arrays used in turn (sel_flip: the set the next call fills -- the result of one
+    // call may be the input of the next), the merged form's sort scratch, and the work area (flag words, keep mask, offsets, tile counts)
+    spsp::DevBuf sel_mn[2], sel_lo[2], sel_hi[2], sel_t_mn, sel_t_lo, sel_t_hi, sel_work;
+    int sel_flip = 0;
 };
 
 namespace spsp {
@@ -315,6 +323,18 @@ int sketch_parse_structure_host(const uint8_t* payload, uint64_t len, ParsedSket
 // spsp_downsample.hip: the keys whose minimizer's hash is <= threshold, sketches back to back, order kept, in context-owned arrays
 int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
                          const uint64_t* h_sk_off, uint32_t n, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out);
+// the tile compaction behind a keep mask, shared by the downsampling pass and the selection (spsp_downsample.hip).  The mask is
+// k_ds_flag's layout: tiles of kDsTile keys, one 64-bit ballot word per 64 keys -- round r of wave w of tile t fills word
+// kDsWords t + 4 r + w, bit l of word j is key 64 j + l -- and d_tile_cnt[t] = the tile's survivors.  Queued on the context's stream:
+// launch_scan_u32 over the tile counts (d_tile_off: n_tiles + 1 words, the last the total, also stored to *total_host), k_ds_move
+// (the kept keys of (d_mn, d_lo, d_hi), order kept, to (out_mn, out_lo, out_hi)), k_ds_offsets (d_off_out[i] = the survivors in
+// front of key d_off_in[i], n_bounds of them).  No host wait.
+constexpr uint32_t kDsThreads = 256;                       // 4 waves
+constexpr uint32_t kDsTile = 2048;                         // keys per workgroup: 8 rounds of 256
+constexpr uint32_t kDsWords = kDsTile / 64;                // ballot words per tile
+int ds_compact_launch(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const unsigned long long* d_mask,
+                      const uint32_t* d_tile_cnt, uint32_t* d_tile_off, uint32_t n_tiles, const uint64_t* d_off_in, uint32_t n_bounds, uint64_t* d_off_out,
+                      uint32_t* out_mn, uint64_t* out_lo, uint64_t* out_hi, uint64_t* total_host);
 // the sorted distinct keys of n sketch payloads on the device, sketches back to back: the decoder's arrays, or the downsampling
 // pass's (spsp_decode.hip).  ds_threshold: null = the keys as the files hold them; else only the keys whose minimizer passes that
 // selection threshold, brought down on the device behind the decoder.  card[i] = the keys of sketch i that are left
@@ -367,6 +387,17 @@ int neighbours_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cel
 // spsp_prevalence.hip: per row sketch the keys by class of holder count and the sum of the counts, the spectrum of the references'
 // union, h of every key occurrence (context-owned, on the device) -- over concatenated sorted key arrays, n_query == 0: all versus all
 int prevalence_check_args(uint32_t n, uint32_t n_query, uint32_t num, uint32_t den);
+// the table fill the prevalence pass and the selection share: the sketch offsets uploaded (ctx->pv_off), the table cleared
+// (ctx->pv_table), k_pv_count over the reference entries, k_pv_read over every entry -> ctx->pv_hold[e] = h of entry e.  claim: bit 31
+// of pv_hold[e] is set as well iff entry e is the one that claimed its key's slot (exactly one occurrence of every distinct reference
+// key; h <= 65535 leaves the bit free).  d_words: two u32 on the device the caller has cleared on the stream (keys out of order | a
+// probe sequence that went round the table).  The caller has checked the arguments and the offsets.  Queued: no host wait
+int prevalence_fill_table(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
+                          uint32_t n, uint32_t nq, bool claim, uint32_t* d_words);
+// spsp_select.hip: the keys whose holder count lies in [h_min, h_max] as sketches again -- each: every row sketch's, order kept;
+// merged: the distinct keys of the references' union, sorted, as ONE sketch -- in context-owned arrays
+int keys_select_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,
+                     uint32_t nq, uint32_t h_min, uint32_t h_max, bool merged, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out);
 int prevalence_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
                            uint32_t n, uint32_t n_query, uint32_t num, uint32_t den, spsp_prevalence_row* rows, uint64_t* spectrum, uint32_t** d_holders);
 // the front half of every file driver (spsp_host.cpp): the payloads of n sketch files, in file order, and what their headers say

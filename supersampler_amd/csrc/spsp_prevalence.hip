@@ -77,7 +77,8 @@ __global__ __launch_bounds__(kPvThreads) void k_pv_count(SortedKeys K, const uin
     atomicAdd(&tbl[pos], 1ull << 32);                      // (result unused: a key of one species puts R of these on one word)
 }
 
-template <bool HAS_HI>
+// CLAIM (the selection's merged form): bit 31 of holders[e] says that e is the entry whose number the slot's low half names
+template <bool HAS_HI, bool CLAIM>
 __global__ __launch_bounds__(kPvThreads) void k_pv_read(SortedKeys K, const uint64_t* __restrict__ off, uint32_t n, uint32_t nq,
                                                         const unsigned long long* __restrict__ tbl, uint32_t log2cap, uint32_t* __restrict__ holders,
                                                         uint32_t* __restrict__ words) {
@@ -92,7 +93,11 @@ __global__ __launch_bounds__(kPvThreads) void k_pv_read(SortedKeys K, const uint
     for (uint64_t probes = 0; probes <= mask; ++probes) {  // (a query key may go round a table without a free slot: h stays 0)
         const unsigned long long cur = tbl[pos];
         if ((uint32_t)cur == 0u) break;
-        if (pv_same<HAS_HI>(K, (uint64_t)((uint32_t)cur - 1u), mn, hi, lo)) { h = (uint32_t)(cur >> 32); break; }
+        if (pv_same<HAS_HI>(K, (uint64_t)((uint32_t)cur - 1u), mn, hi, lo)) {
+            h = (uint32_t)(cur >> 32);
+            if (CLAIM && (uint32_t)cur - 1u == (uint32_t)e) h |= 0x80000000u;   // (a counter is 65 535 at the most)
+            break;
+        }
         pos = (pos + 1ull) & mask;
     }
     holders[e] = h;
@@ -174,6 +179,44 @@ int prevalence_check_args(uint32_t n, uint32_t n_query, uint32_t num, uint32_t d
     return SPSP_OK;
 }
 
+// (spsp_internal.h) offsets, memset, k_pv_count, k_pv_read: what the prevalence pass and the selection both start with
+int prevalence_fill_table(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
+                          uint32_t n, uint32_t nq, bool claim, uint32_t* d_words) {
+    int rc;
+    const uint64_t extent = h_sk_off[n], all_keys = h_sk_off[n] - h_sk_off[0], ref_keys = h_sk_off[n] - h_sk_off[nq];
+    // the table: a power of two of slots, half as many again as there are reference entries (every one of them may be a key of
+    // its own); SPSP_DEBUG_PREVALENCE_TABLE=min: the smallest that holds them, so that probe sequences wrap and chains are long
+    const char* dbg_table = getenv("SPSP_DEBUG_PREVALENCE_TABLE");   // (read per call: a test switches it inside one process)
+    const bool smallest = dbg_table && !strcmp(dbg_table, "min");
+    const uint64_t want = std::max<uint64_t>(2, smallest ? ref_keys : ref_keys + ref_keys / 2);
+    uint32_t log2cap = 1;
+    while (log2cap < kPvLog2CapMax && (1ull << log2cap) < want) ++log2cap;
+    ctx->pv_log2cap = log2cap;
+    const uint64_t cap = 1ull << log2cap;
+    if ((rc = ctx->pv_off.reserve(((size_t)n + 1) * 8)) || (rc = ctx->pv_table.reserve((size_t)cap * 8)) ||
+        (rc = ctx->pv_hold.reserve(std::max<size_t>(extent, 1) * 4))) return rc;
+    uint64_t* d_off = ctx->pv_off.as<uint64_t>();
+    unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
+    uint32_t* d_hold = ctx->pv_hold.as<uint32_t>();
+    const SortedKeys K{d_mn, d_lo, d_hi};
+    SPSP_HIP(hipMemcpyAsync(d_off, h_sk_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (ref_keys) {
+        SPSP_HIP(hipMemsetAsync(d_tbl, 0, (size_t)cap * 8, ctx->stream));
+        const uint32_t gx = (uint32_t)((ref_keys + kPvThreads - 1) / kPvThreads);
+        if (has_hi) hipLaunchKernelGGL(k_pv_count<true>, dim3(gx), dim3(kPvThreads), 0, ctx->stream, K, (const uint64_t*)d_off, n, nq, d_tbl, log2cap, d_words);
+        else hipLaunchKernelGGL(k_pv_count<false>, dim3(gx), dim3(kPvThreads), 0, ctx->stream, K, (const uint64_t*)d_off, n, nq, d_tbl, log2cap, d_words);
+    }
+    if (all_keys) {
+        if (!ref_keys) SPSP_HIP(hipMemsetAsync(d_tbl, 0, (size_t)cap * 8, ctx->stream));   // (queries against references without keys: all absent)
+        const uint32_t gx = (uint32_t)((all_keys + kPvThreads - 1) / kPvThreads);
+        auto read = has_hi ? (claim ? k_pv_read<true, true> : k_pv_read<true, false>) : (claim ? k_pv_read<false, true> : k_pv_read<false, false>);
+        hipLaunchKernelGGL(read, dim3(gx), dim3(kPvThreads), 0, ctx->stream, K, (const uint64_t*)d_off, n, nq, (const unsigned long long*)d_tbl, log2cap, d_hold,
+                           d_words);
+    }
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+
 int prevalence_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
                            uint32_t n, uint32_t nq, uint32_t num, uint32_t den, spsp_prevalence_row* rows, uint64_t* spectrum, uint32_t** d_holders) {
     int rc;
@@ -189,42 +232,17 @@ int prevalence_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, cons
     if (extent > 0xfffffff0ull) { set_error("too many sketch k-mers for one call"); return SPSP_ERR_OVERFLOW; }
     if (all_keys && (!d_mn || !d_lo || (has_hi && !d_hi))) { set_error("NULL key array"); return SPSP_ERR_ARG; }
     const uint32_t core_min = (uint32_t)(((uint64_t)num * R + den - 1) / den);       // h * den >= num * R  <=>  h >= ceil(num * R / den)
-    // the table: a power of two of slots, half as many again as there are reference entries (every one of them may be a key of
-    // its own); SPSP_DEBUG_PREVALENCE_TABLE=min: the smallest that holds them, so that probe sequences wrap and chains are long
-    const char* dbg_table = getenv("SPSP_DEBUG_PREVALENCE_TABLE");   // (read per call: a test switches it inside one process)
-    const bool smallest = dbg_table && !strcmp(dbg_table, "min");
-    const uint64_t want = std::max<uint64_t>(2, smallest ? ref_keys : ref_keys + ref_keys / 2);
-    uint32_t log2cap = 1;
-    while (log2cap < kPvLog2CapMax && (1ull << log2cap) < want) ++log2cap;
-    ctx->pv_log2cap = log2cap;
-    const uint64_t cap = 1ull << log2cap;
     const size_t spec_bytes = (size_t)kPvWords * 4 + ((size_t)R + 1) * 8;
-    if ((rc = ctx->pv_off.reserve(((size_t)n + 1) * 8)) || (rc = ctx->pv_table.reserve((size_t)cap * 8)) ||
-        (rc = ctx->pv_hold.reserve(std::max<size_t>(extent, 1) * 4)) || (rc = ctx->pv_rows.reserve((size_t)n_rows * sizeof(spsp_prevalence_row))) ||
-        (rc = ctx->pv_spec.reserve(spec_bytes))) return rc;
-    uint64_t* d_off = ctx->pv_off.as<uint64_t>();
-    unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
-    uint32_t* d_hold = ctx->pv_hold.as<uint32_t>();
+    if ((rc = ctx->pv_rows.reserve((size_t)n_rows * sizeof(spsp_prevalence_row))) || (rc = ctx->pv_spec.reserve(spec_bytes))) return rc;
     spsp_prevalence_row* d_rows = ctx->pv_rows.as<spsp_prevalence_row>();
     uint32_t* d_words = ctx->pv_spec.as<uint32_t>();
     unsigned long long* d_spec = reinterpret_cast<unsigned long long*>(d_words + kPvWords);
-    const SortedKeys K{d_mn, d_lo, d_hi};
-    SPSP_HIP(hipMemcpyAsync(d_off, h_sk_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     SPSP_HIP(hipMemsetAsync(d_words, 0, spec_bytes, ctx->stream));
-    if (ref_keys) {
-        SPSP_HIP(hipMemsetAsync(d_tbl, 0, (size_t)cap * 8, ctx->stream));
-        const uint32_t gx = (uint32_t)((ref_keys + kPvThreads - 1) / kPvThreads);
-        if (has_hi) hipLaunchKernelGGL(k_pv_count<true>, dim3(gx), dim3(kPvThreads), 0, ctx->stream, K, (const uint64_t*)d_off, n, nq, d_tbl, log2cap, d_words);
-        else hipLaunchKernelGGL(k_pv_count<false>, dim3(gx), dim3(kPvThreads), 0, ctx->stream, K, (const uint64_t*)d_off, n, nq, d_tbl, log2cap, d_words);
-    }
-    if (all_keys) {
-        if (!ref_keys) SPSP_HIP(hipMemsetAsync(d_tbl, 0, (size_t)cap * 8, ctx->stream));   // (queries against references without keys: all absent)
-        const uint32_t gx = (uint32_t)((all_keys + kPvThreads - 1) / kPvThreads);
-        if (has_hi) hipLaunchKernelGGL(k_pv_read<true>, dim3(gx), dim3(kPvThreads), 0, ctx->stream, K, (const uint64_t*)d_off, n, nq,
-                                       (const unsigned long long*)d_tbl, log2cap, d_hold, d_words);
-        else hipLaunchKernelGGL(k_pv_read<false>, dim3(gx), dim3(kPvThreads), 0, ctx->stream, K, (const uint64_t*)d_off, n, nq,
-                                (const unsigned long long*)d_tbl, log2cap, d_hold, d_words);
-    }
+    if ((rc = prevalence_fill_table(ctx, has_hi, d_mn, d_lo, d_hi, h_sk_off, n, nq, false, d_words))) return rc;
+    const uint64_t* d_off = ctx->pv_off.as<uint64_t>();
+    const unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
+    uint32_t* d_hold = ctx->pv_hold.as<uint32_t>();
+    const uint64_t cap = 1ull << ctx->pv_log2cap;
     hipLaunchKernelGGL(k_pv_rows, dim3(n_rows), dim3(kPvThreads), 0, ctx->stream, (const uint32_t*)d_hold, (const uint64_t*)d_off, core_min, d_rows);
     if (ref_keys) {
         const uint32_t gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((cap + kPvThreads - 1) / kPvThreads, (uint64_t)std::max(ctx->n_cu, 1) * kPvSpecBlocksPerCu));
