@@ -962,6 +962,51 @@ int spsp_sketch_from_keys_host(uint32_t k, uint32_t m, double rate, const uint32
 int spsp_select_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, const char* what, int each,
                       const char* out_prefix, int chatter, double rate, uint64_t* keys_in /* may be NULL */, uint64_t* keys_out /* may be NULL */);
 
+/* ------------------------------------------------------- accumulation ---- */
+/* Pan and core curves (not in the reference): how the union and the intersection of a collection move as its sketches are added
+ * one by one, over n_orders orders of them.  Sketches 0 .. n-1 in list order with key sets K_i, 1 <= n <= 65535; there are no
+ * queries.  An order is a permutation pi of 0 .. n-1, pi[j-1] the sketch added at step j = 1 .. n:
+ *   pan(j)  = |K_pi[0] u ... u K_pi[j-1]|        core(j) = |K_pi[0] n ... n K_pi[j-1]|
+ * Row j-1 holds, over the 1 <= n_orders <= 1024 orders, the minimum, the maximum and the 64-bit sum of both at step j, and both
+ * for order 0.  Every value is a count of keys: no floating point decides anything. */
+typedef struct spsp_accumulation_row {   /* 64 bytes */
+    uint64_t pan_min, pan_max, pan_sum, core_min, core_max, core_sum, pan_first, core_first;
+} spsp_accumulation_row;
+/* The orders a seed names, for ever: order 0 is the list order; orders 1 .. n_orders-1 are Fisher-Yates shuffles of the identity
+ * (for i = n-1 down to 1: j = below(i + 1); swap(a[i], a[j])) drawn one after another from ONE splitmix64 stream of state `seed`:
+ * s += 0x9E3779B97F4A7C15; z = s; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^= z >> 31.
+ * below(b) draws again while z >= 2^64 - (2^64 mod b) and returns z mod b.  orders: n_orders x n words, order p at p * n. */
+int spsp_accumulation_orders_host(uint32_t n, uint32_t n_orders, uint64_t seed, uint32_t* orders /* n_orders * n */);
+/* What the device call runs with for n sketches (any pointer may be NULL): the orders one pass over the keys serves (group: a
+ * power of two, 8 at the most), the ranks one window of the first-rank histogram covers (n while group orders and all n bins fit
+ * the LDS, which they do up to n = 25 941; beyond that one order per pass and ceil(n / window) windows), the ranks one pass of a
+ * long list's mex marks, and the list length above which the whole wave walks a list instead of one lane. */
+int spsp_accumulation_plan_host(uint32_t n, uint32_t* group, uint32_t* window, uint32_t* bitmap_bits, uint32_t* cut);
+/* The curves of the sketches 0 .. n-1 over concatenated sorted key arrays on the device (as spsp_prevalence_device takes them; only
+ * read) for the given orders (host, n_orders x n; any permutations: spsp_accumulation_orders_host's or a caller's own).  rows: n
+ * rows, row j-1 is step j.  pan, core (either may be NULL): n_orders x n words, the curve of order p at p * n.  Built once per
+ * call: the prevalence pass's table fill (its table and holders[] are overwritten) and the key-major form of the collection -- per
+ * distinct key the list of its holders; then one streaming pass over that form per group of orders, whose rank tables sit in LDS.
+ * One host wait, at the end.  SPSP_ERR_ARG (rows, pan and core zeroed): n or n_orders out of range, an order that is not a
+ * permutation (the message names the order and the position), k outside 1..63, decreasing offsets, a context switched to
+ * unordered keys, keys out of order or twice inside a sketch; SPSP_ERR_OVERFLOW: an extent above 0xfffffff0. */
+int spsp_accumulation_device(spsp_ctx* ctx, uint32_t k, const void* d_minimizer, const void* d_kmer_lo, const void* d_kmer_hi /* NULL if k <= 32 */,
+                             const uint64_t* sk_off /* n + 1 */, uint32_t n, const uint32_t* orders, uint32_t n_orders,
+                             spsp_accumulation_row* rows /* n: row j-1 is step j */, uint64_t* pan /* NULL or n_orders * n */,
+                             uint64_t* core /* NULL or n_orders * n */);
+/* The text of <prefix>_accumulation.csv.gz: "genomes,pan_min,pan_mean,pan_max,core_min,core_mean,core_max,new_mean,pan_listed,
+ * core_listed" and one line per j = 1 .. n.  pan_mean = pan_sum / n_orders, core_mean likewise, new_mean = (pan_sum(j) -
+ * pan_sum(j-1)) / n_orders with pan_sum(0) = 0: the three are printed as %.<precision>g and decide nothing; the rest are integers.
+ * Rows that cannot be curves are SPSP_ERR_ARG: a minimum above its maximum, a sum outside [n_orders * min, n_orders * max], pan_min
+ * falling or core_max rising with j, pan_first or core_first outside [min, max].  *text is released with spsp_free(). */
+int spsp_accumulation_csv_host(const spsp_accumulation_row* rows, uint32_t n, uint32_t n_orders, int precision, char** text, size_t* len);
+/* The whole-file driver: the files are read, inflated and decoded as spsp_prevalence_files does it, with the same `rate` argument
+ * and refusals (k == m collections are SPSP_ERR_ARG); the orders are spsp_accumulation_orders_host(n, n_orders, seed).  Writes
+ * <out_prefix>_accumulation.csv.gz (gzip level 1, as the matrices) and no matrices.  rows (may be NULL) receives a copy of the n
+ * rows, released with spsp_free().  One device: there is no multi-device form. */
+int spsp_accumulation_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_orders, uint64_t seed, int precision,
+                            const char* out_prefix, int chatter, double rate, spsp_accumulation_row** rows /* may be NULL; spsp_free */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,10 @@ TREE_ROW_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("size", "<u4"), ("reserv
 # spsp_prevalence_row: a row sketch's keys by class of holder count, and the sum of the holder counts (include/spsp.h)
 PREVALENCE_ROW_DTYPE = np.dtype([("core", "<u8"), ("shell", "<u8"), ("unique", "<u8"), ("absent", "<u8"), ("holders", "<u8")])
 
+# spsp_accumulation_row: pan and core at one step of the curves -- minimum, maximum and sum over the orders, and order 0's (include/spsp.h)
+ACCUMULATION_ROW_DTYPE = np.dtype([("pan_min", "<u8"), ("pan_max", "<u8"), ("pan_sum", "<u8"), ("core_min", "<u8"), ("core_max", "<u8"),
+                                   ("core_sum", "<u8"), ("pan_first", "<u8"), ("core_first", "<u8")])
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -130,6 +134,7 @@ ABI_SYMBOLS = [
     "spsp_prevalence_device", "spsp_prevalence_csv_host", "spsp_spectrum_csv_host", "spsp_prevalence_files",
     "spsp_tree_cells_device", "spsp_tree_cut_host", "spsp_tree_csv_host", "spsp_tree_newick_host", "spsp_tree_files",
     "spsp_keys_select_device", "spsp_select_band_host", "spsp_sketch_from_keys_host", "spsp_select_files",
+    "spsp_accumulation_orders_host", "spsp_accumulation_plan_host", "spsp_accumulation_device", "spsp_accumulation_csv_host", "spsp_accumulation_files",
 ]
 
 _lib = None
@@ -310,6 +315,17 @@ def lib():
         L.spsp_sketch_from_keys_host.argtypes = [u32, u32, dbl, vp, vp, vp, u64, P(vp), P(u64)]
         L.spsp_select_files.restype = i32
         L.spsp_select_files.argtypes = [vp, P(cp), u32, u32, cp, i32, cp, i32, dbl, P(u64), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_accumulation_device"):
+        L.spsp_accumulation_orders_host.restype = i32
+        L.spsp_accumulation_orders_host.argtypes = [u32, u32, u64, vp]
+        L.spsp_accumulation_plan_host.restype = i32
+        L.spsp_accumulation_plan_host.argtypes = [u32, P(u32), P(u32), P(u32), P(u32)]
+        L.spsp_accumulation_device.restype = i32
+        L.spsp_accumulation_device.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, u32, vp, vp, vp]
+        L.spsp_accumulation_csv_host.restype = i32
+        L.spsp_accumulation_csv_host.argtypes = [vp, u32, u32, i32, P(vp), P(C.c_size_t)]
+        L.spsp_accumulation_files.restype = i32
+        L.spsp_accumulation_files.argtypes = [vp, P(cp), u32, u32, u64, i32, cp, i32, dbl, P(vp)]
     _lib = L
     return L
 
@@ -585,6 +601,32 @@ def spectrum_csv(spectrum):
         raise ValueError("spectrum_csv: R + 1 words")
     out, ln = C.c_void_p(), C.c_uint64()
     _check(lib().spsp_spectrum_csv_host(spectrum.ctypes.data, len(spectrum) - 1, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def accumulation_orders(n, n_orders, seed):
+    """spsp_accumulation_orders_host: the orders a seed names -> np.uint32[n_orders, n]; order 0 is the list order, the others are
+    Fisher-Yates shuffles drawn from one splitmix64 stream (include/spsp.h spells the rule out)"""
+    out = np.zeros((max(n_orders, 0), max(n, 0)), dtype=np.uint32)
+    _check(lib().spsp_accumulation_orders_host(n, n_orders, seed, out.ctypes.data if out.size else None))
+    return out
+
+
+def accumulation_plan(n):
+    """spsp_accumulation_plan_host: what the device call runs with for n sketches -> dict(group: orders per pass over the keys,
+    window: ranks per window of the first-rank histogram, bitmap_bits: ranks per mex pass of a long list, cut: the list length
+    above which the whole wave walks a list)"""
+    g, w, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_accumulation_plan_host(n, C.byref(g), C.byref(w), C.byref(b), C.byref(c)))
+    return {"group": g.value, "window": w.value, "bitmap_bits": b.value, "cut": c.value}
+
+
+def accumulation_csv(rows, n_orders, precision=6):
+    """spsp_accumulation_csv_host: accumulation rows (ACCUMULATION_ROW_DTYPE array, row j-1 is step j) over n_orders orders -> the
+    text of <prefix>_accumulation.csv.gz"""
+    rows = np.ascontiguousarray(rows, dtype=ACCUMULATION_ROW_DTYPE)
+    out, ln = C.c_void_p(), C.c_size_t()
+    _check(lib().spsp_accumulation_csv_host(rows.ctypes.data if len(rows) else None, len(rows), n_orders, precision, C.byref(out), C.byref(ln)))
     return _take(out, ln.value)
 
 
@@ -1191,6 +1233,37 @@ class Context:
         _check(lib().spsp_keys_select_device(self._h, k, d_min, d_lo, d_hi, sk_off.ctypes.data, n, n_query, h_min, h_max, 1 if merged else 0,
                                              C.byref(o_mn), C.byref(o_lo), C.byref(o_hi), out.ctypes.data))
         return o_mn.value, o_lo.value, o_hi.value, out
+
+    def accumulation_device(self, k, d_min, d_lo, d_hi, sk_off, n, orders, want_curves=False):
+        """spsp_accumulation_device: the pan and core curves of the sketches 0 .. n-1 over concatenated sorted key arrays on the
+        device, for the given orders (P x n, every one a permutation of 0 .. n-1: accumulation_orders' or the caller's own) ->
+        rows (ACCUMULATION_ROW_DTYPE array, row j-1 is step j) [, pan, core: np.uint64[P, n], every order's curves]"""
+        sk_off = np.ascontiguousarray(sk_off, dtype=np.uint64)
+        if len(sk_off) != n + 1:
+            raise ValueError("accumulation_device: n + 1 sketch offsets")
+        orders = np.ascontiguousarray(orders, dtype=np.uint32)
+        if orders.ndim == 1:
+            orders = orders.reshape(1, -1)
+        if orders.ndim != 2 or orders.shape[1] != n:
+            raise ValueError("accumulation_device: orders are P x n")
+        P = orders.shape[0]
+        rows = np.zeros(max(n, 1), dtype=ACCUMULATION_ROW_DTYPE)
+        pan = np.zeros((P, n), dtype=np.uint64) if want_curves else None
+        core = np.zeros((P, n), dtype=np.uint64) if want_curves else None
+        _check(lib().spsp_accumulation_device(self._h, k, d_min, d_lo, d_hi, sk_off.ctypes.data, n, orders.ctypes.data if orders.size else rows.ctypes.data,
+                                              P, rows.ctypes.data, pan.ctypes.data if want_curves and pan.size else None,
+                                              core.ctypes.data if want_curves and core.size else None))
+        rows = rows[:n]
+        return (rows, pan, core) if want_curves else rows
+
+    def accumulation_files(self, paths, prefix, orders=100, seed=1, precision=6, rate=0.0):
+        """spsp_accumulation_files: sketch files -> <prefix>_accumulation.csv.gz and the rows; the curves are taken over `orders`
+        orders, accumulation_orders(n, orders, seed).  rate: as compare_files (0.0, a rate, or "auto")"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        rows = C.c_void_p()
+        _check(lib().spsp_accumulation_files(self._h, arr, n, orders, seed, precision, prefix.encode(), 0, _rate_arg(rate), C.byref(rows)))
+        return np.frombuffer(_take(rows, n * ACCUMULATION_ROW_DTYPE.itemsize), dtype=ACCUMULATION_ROW_DTYPE).copy()
 
     def select_files(self, paths, prefix, what, each=False, n_query=0, rate=None):
         """spsp_select_files: sketch files (the n_query queries first, or none) -> the keys in the band `what` (select_band's words)

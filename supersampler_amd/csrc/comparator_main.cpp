@@ -16,13 +16,16 @@
 // A seventh: -S <what> without -q / -E <what> with or without -q writes SKETCHES instead -- the keys whose number of holders in the
 // index lies in the band <what> names (union, present, absent, all, core=<t>, unique=<t>, shell=<t>, <a>..<b>): -S the distinct
 // keys of the index as one sketch, <o>_select.gz; -E every sketch's (every query's) own, <o>_<i>_<its file name>, listed in
-// <o>_select.txt (spsp_select_files).
+// <o>_select.txt (spsp_select_files).  An eighth: -A <orders> [-z <seed>] without -q draws the index's accumulation curves instead -- the
+// size of the union (pan) and of the intersection (core) of the first j sketches, over <orders> orders of them: the list order and
+// shuffles drawn from the seed, 1 unless -z names it (spsp_accumulation_files) -> <o>_accumulation.csv.gz.
 #include <getopt.h>
 
 #include <chrono>
 #include <iostream>
 #include <sstream>
 #include <algorithm>
+#include <cerrno>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -108,8 +111,26 @@ int main(int argc, char** argv) {
     int select_opts = 0;             // -S <what> / -E <what>: neither letter is in the reference's option string
     bool select_each = false;
     string select_what;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:")) != -1) {
+    long long acc_orders = 0;        // -A <orders> [-z <seed>]: neither letter is in the reference's option string
+    bool accumulation = false, acc_seeded = false;
+    uint64_t acc_seed = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:")) != -1) {
         switch (ch) {
+            case 'A': {
+                char* e = nullptr;
+                acc_orders = strtoll(optarg, &e, 10);
+                if (e == optarg || *e || acc_orders < 1 || acc_orders > 1024) { cout << "-A takes the number of orders the curves are taken over, an integer in 1 .. 1024, not '" << optarg << "'" << endl; return 1; }
+                accumulation = true;
+                break;
+            }
+            case 'z': {
+                char* e = nullptr;
+                errno = 0;
+                acc_seed = strtoull(optarg, &e, 10);
+                if (e == optarg || *e || errno || optarg[0] == '-') { cout << "-z takes the seed of the orders, an unsigned 64-bit integer, not '" << optarg << "'" << endl; return 1; }
+                acc_seeded = true;
+                break;
+            }
             case 'S':
             case 'E': {
                 uint32_t a = 0, b = 0;
@@ -218,6 +239,11 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (select_opts && !select_each && query != "") { cout << "-S writes the index's keys as one sketch: not together with -q (-E selects from the queries)" << endl; return 1; }
+    if (acc_seeded && !accumulation) { cout << "-z seeds the orders of the accumulation curves: it needs -A" << endl; return 1; }
+    if (accumulation && (query != "" || gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts || select_opts)) {
+        cout << "-A draws the pan and core curves of the index: not together with -q, -g, -c, -C, -N, -P, -r, -R, -l, -L, -S or -E" << endl;
+        return 1;
+    }
     if (weights_file != "" && !rep_opts) { cout << "-w gives the weights -r / -R order the sketches by: it needs one of them" << endl; return 1; }
     vector<uint64_t> weights;
     if (weights_file != "" && inputfof != "") {
@@ -270,6 +296,17 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (accumulation) {
+        // one device, as gather
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_accumulation_files(ctx, paths.data(), (uint32_t)paths.size(), (uint32_t)acc_orders, acc_seed, (int)p, output_name.c_str(), 1, rate,
+                                                        nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Accumulation failed: " << err << endl; return 1; }
+        return 0;
     }
     if (select_opts) {
         // one device, as gather; the rows of -E are every sketch of the index (n_query 0) or the queries

@@ -86,6 +86,21 @@ __device__ __forceinline__ void sorted_check_order(const SortedKeys& K, const ui
     if (e != off[sorted_sketch_of(off, j0, j1, e)]) atomicOr(flag, 1u);   // (the first key of a sketch may be anything)
 }
 
+// The prevalence table (spsp_prevalence.hip: one 64-bit word per slot, the claimer's entry number + 1 in the low half): a key's
+// home slot in a table of 2^log2cap slots, and whether entry c holds the key (mn, hi, lo).  The fill, the read-back and the
+// accumulation's transposition (spsp_accumulation.hip) walk the same probe sequence from the same home.
+template <bool HAS_HI>
+__device__ __forceinline__ uint64_t pv_home(uint32_t mn, uint64_t hi, uint64_t lo, uint32_t log2cap) {
+    uint64_t h = xxh64_u64(lo + (uint64_t)(mn + 1u) * 0x9E3779B97F4A7C15ULL);
+    if (HAS_HI) h = xxh64_u64(h ^ hi);
+    return h >> (64u - log2cap);                           // (log2cap >= 1)
+}
+
+template <bool HAS_HI>
+__device__ __forceinline__ bool pv_same(const SortedKeys& K, uint64_t c, uint32_t mn, uint64_t hi, uint64_t lo) {
+    return K.lo[c] == lo && K.mn[c] == mn && (!HAS_HI || K.hi[c] == hi);
+}
+
 // The order of two fractions x_a / u_a and x_b / u_b without a division: x_a * u_b against x_b * u_a as 128-bit products.
 // > 0: a is the larger fraction, < 0: b, 0: equal (two different fractions that round to one double are still told apart).
 // The neighbours pass orders a row's partners by it, the representatives pass a member's candidates.

@@ -2075,6 +2075,90 @@ int spsp_spectrum_csv_host(const uint64_t* spectrum, uint32_t n_ref, char** text
     return text_out(out, text, len);
 }
 
+// ------------------------------------------------------------------------------------------------ accumulation
+// what the pass kernel of spsp_accumulation.hip is launched with for n sketches.  LDS of a workgroup: kAcLdsBytes less a bitmap of
+// kAcBitmapBits per wave; an order costs its rank table (2 bytes per sketch, n rounded up to even) and 4 bytes per rank of the
+// window.  While whole orders fit with a window of all n ranks: as many as fit, rounded down to a power of two, kAcMaxGroup at the
+// most, ONE window.  Beyond that (n > 25 941): one order, and the window is what the rank table leaves
+int spsp_accumulation_plan_host(uint32_t n, uint32_t* group, uint32_t* window, uint32_t* bitmap_bits, uint32_t* cut) {
+    if (n == 0 || n > 65535) { set_error("accumulation takes 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
+    using namespace spsp;
+    const uint32_t budget = kAcLdsBytes - (kAcPassThreads / 64) * (kAcBitmapBits / 8), rank_bytes = 2u * ((n + 1u) & ~1u);
+    const uint32_t fit = budget / (rank_bytes + 4u * n);
+    uint32_t g = 1, w = n;
+    if (fit >= 1) { while (g * 2 <= fit && g * 2 <= kAcMaxGroup) g *= 2; }
+    else w = (budget - rank_bytes) / 4u;
+    if (group) *group = g;
+    if (window) *window = w;
+    if (bitmap_bits) *bitmap_bits = kAcBitmapBits;
+    if (cut) *cut = kAcCut;
+    return SPSP_OK;
+}
+
+int spsp_accumulation_orders_host(uint32_t n, uint32_t n_orders, uint64_t seed, uint32_t* orders) {
+    if (!orders) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n == 0 || n > 65535) { set_error("accumulation takes 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
+    if (n_orders == 0 || n_orders > 1024) { set_error("accumulation takes 1 .. 1024 orders (%u)", n_orders); return SPSP_ERR_ARG; }
+    uint64_t s = seed;
+    const auto draw = [&s]() {                             // splitmix64
+        s += 0x9E3779B97F4A7C15ull;
+        uint64_t z = s;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    };
+    for (uint32_t p = 0; p < n_orders; ++p) {
+        uint32_t* a = orders + (size_t)p * n;
+        for (uint32_t i = 0; i < n; ++i) a[i] = i;
+        if (p == 0) continue;                              // order 0: the list order
+        for (uint32_t i = n - 1; i >= 1; --i) {
+            const uint64_t b = (uint64_t)i + 1, rem = (0ull - b) % b;   // rem = 2^64 mod b: draws from 2^64 - rem on are drawn again
+            uint64_t z = draw();
+            while (rem && z >= 0ull - rem) z = draw();
+            std::swap(a[i], a[z % b]);
+        }
+    }
+    return SPSP_OK;
+}
+
+int spsp_accumulation_csv_host(const spsp_accumulation_row* rows, uint32_t n, uint32_t n_orders, int precision, char** text, size_t* len) {
+    if (!text || !len || !rows) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n == 0 || n > 65535) { set_error("accumulation takes 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
+    if (n_orders == 0 || n_orders > 1024) { set_error("accumulation takes 1 .. 1024 orders (%u)", n_orders); return SPSP_ERR_ARG; }
+    typedef unsigned __int128 u128;
+    const double P = (double)n_orders;
+    std::string out = "genomes,pan_min,pan_mean,pan_max,core_min,core_mean,core_max,new_mean,pan_listed,core_listed\n";
+    char num[64];
+    uint64_t before = 0;                                   // pan_sum(j - 1)
+    for (uint32_t j = 0; j < n; ++j) {
+        const spsp_accumulation_row& r = rows[j];
+        const char* why = nullptr;
+        if (r.pan_min > r.pan_max || r.core_min > r.core_max) why = "a minimum above its maximum";
+        else if ((u128)r.pan_sum < (u128)n_orders * r.pan_min || (u128)r.pan_sum > (u128)n_orders * r.pan_max ||
+                 (u128)r.core_sum < (u128)n_orders * r.core_min || (u128)r.core_sum > (u128)n_orders * r.core_max) why = "a sum that its orders' minimum and maximum do not allow";
+        else if (j && r.pan_min < rows[j - 1].pan_min) why = "pan_min falls";
+        else if (j && r.core_max > rows[j - 1].core_max) why = "core_max rises";
+        else if (r.pan_first < r.pan_min || r.pan_first > r.pan_max || r.core_first < r.core_min || r.core_first > r.core_max) why = "the listed order's value outside [min, max]";
+        if (why) { set_error("accumulation row %u (%u genomes) is not a step of a curve: %s", j, j + 1, why); return SPSP_ERR_ARG; }
+        const double grown = r.pan_sum >= before ? (double)(r.pan_sum - before) : -(double)(before - r.pan_sum);
+        before = r.pan_sum;
+        out += std::to_string(j + 1); out += ',';
+        out += std::to_string(r.pan_min); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, (double)r.pan_sum / P)); out += ',';
+        out += std::to_string(r.pan_max); out += ',';
+        out += std::to_string(r.core_min); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, (double)r.core_sum / P)); out += ',';
+        out += std::to_string(r.core_max); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, grown / P)); out += ',';
+        out += std::to_string(r.pan_first); out += ',';
+        out += std::to_string(r.core_first); out += '\n';
+    }
+    uint64_t l = 0;
+    const int rc = text_out(out, text, &l);
+    *len = (size_t)l;
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------------------ the linkage tree
 int spsp_tree_cut_host(const spsp_tree_row* rows, uint64_t n_rows, uint32_t n, const uint64_t* card, int metric, uint32_t floor_num, uint32_t floor_den,
                        uint32_t num, uint32_t den, uint32_t* cluster, uint64_t* n_clusters) {

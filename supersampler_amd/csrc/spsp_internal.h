@@ -130,7 +130,9 @@ enum HostSlot {
     kHsSelBad = 31,         // spsp_select.hip: the copy of the table fill's two u32 (keys out of order | a probe sequence that went round
                             // the table << 32); keys_select_impl reads it behind its first wait
     kHsSelTotal = 32,       // ... and launch_scan_u32's total over the tiles' survivor counts: the keys selected (u64), in the same wait
-    kHostSlots = 33
+    kHsAcBad = 33,          // spsp_accumulation.hip: the copy of two u32 (the table fill's keys out of order | a probe sequence that went round
+                            // the table or a list place out of range << 32); accumulation_device_impl reads it behind its one wait
+    kHostSlots = 34
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
@@ -138,7 +140,8 @@ static_assert(kHsIngestRecs == kHsIngestKept + 1 && kHsMultiVerdict == kHsOrderV
 static_assert(kHsNbCands == kHsClusterCount + 1 && kHsPvBad == kHsNbBad + 1 && kHsPvBad + 1 == kHsRpUndecided, "the neighbours' four slots, then the prevalence pass's one");
 static_assert(kHsRpCount == kHsRpUndecided + 3 && kHsRpCount + 1 == kHsTrEdges, "the representatives pass's four slots, then the linkage tree's");
 static_assert(kHsTrRounds == kHsTrEdges + 2 && kHsTrRounds + 1 == kHsSelBad, "the linkage tree's three slots");
-static_assert(kHsSelTotal == kHsSelBad + 1 && kHsSelTotal + 1 == kHostSlots, "the selection's two slots: the last ones");
+static_assert(kHsSelTotal == kHsSelBad + 1 && kHsSelTotal + 1 == kHsAcBad, "the selection's two slots");
+static_assert(kHsAcBad + 1 == kHostSlots, "the accumulation's one slot: the last one");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -270,6 +273,10 @@ struct spsp_ctx {
     // call may be the input of the next), the merged form's sort scratch, and the work area (flag words, keep mask, offsets, tile counts)
     spsp::DevBuf sel_mn[2], sel_lo[2], sel_hi[2], sel_t_mn, sel_t_lo, sel_t_hi, sel_work;
     int sel_flip = 0;
+    // accumulation (spsp_accumulation.hip): the work area (flag words, the two scans' inputs and outputs), the key-major form (a start
+    // per distinct key and one more; the holders' sketch numbers, 16 bits each, list behind list), the orders as rank tables, and the two
+    // histograms (first rank, mex) of every order
+    spsp::DevBuf ac_work, ac_keys, ac_list, ac_rank, ac_hist;
 };
 
 namespace spsp {
@@ -400,6 +407,16 @@ int keys_select_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint
                      uint32_t nq, uint32_t h_min, uint32_t h_max, bool merged, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out);
 int prevalence_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
                            uint32_t n, uint32_t n_query, uint32_t num, uint32_t den, spsp_prevalence_row* rows, uint64_t* spectrum, uint32_t** d_holders);
+// spsp_accumulation.hip: pan and core curves over orders of the sketches.  The pass kernel's geometry, which
+// spsp_accumulation_plan_host (spsp_host.cpp) turns into the orders per pass and the window of ranks for a given n
+constexpr uint32_t kAcPassThreads = 512;                   // 8 waves: one workgroup per CU once the rank tables fill its LDS
+constexpr uint32_t kAcLdsBytes = 160 * 1024;               // what one workgroup may take on gfx950
+constexpr uint32_t kAcBitmapBits = 8192;                   // per wave: the ranks one mex pass of a long list marks
+constexpr uint32_t kAcMaxGroup = 8;                        // orders per pass at the most (their minima sit in registers)
+constexpr uint32_t kAcCut = 64;                            // a list of more holders than this is queued for a whole wave (<= 64: the lane's mex mask); measured, DESIGN 6o
+int accumulation_check_args(uint32_t n, uint32_t n_orders);
+int accumulation_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
+                             uint32_t n, const uint32_t* orders, uint32_t n_orders, spsp_accumulation_row* rows, uint64_t* pan, uint64_t* core);
 // the front half of every file driver (spsp_host.cpp): the payloads of n sketch files, in file order, and what their headers say
 struct LoadedSketches {
     std::vector<uint8_t*> data;                                    // into the context's read regions, or owned (own[i])

@@ -40,18 +40,7 @@ constexpr uint32_t kPvMaxDen = 1000000;
 constexpr uint32_t kPvLog2CapMax = 32;                     // (an entry's number + 1 is a 32-bit word: never more entries than that)
 enum { kPvwBad = 0, kPvwWrapped = 1, kPvWords = 4 };       // flag words in front of the spectrum (16 bytes, cleared with it)
 
-template <bool HAS_HI>
-__device__ __forceinline__ uint64_t pv_home(uint32_t mn, uint64_t hi, uint64_t lo, uint32_t log2cap) {
-    uint64_t h = xxh64_u64(lo + (uint64_t)(mn + 1u) * 0x9E3779B97F4A7C15ULL);
-    if (HAS_HI) h = xxh64_u64(h ^ hi);
-    return h >> (64u - log2cap);                           // (log2cap >= 1)
-}
-
-template <bool HAS_HI>
-__device__ __forceinline__ bool pv_same(const SortedKeys& K, uint64_t c, uint32_t mn, uint64_t hi, uint64_t lo) {
-    return K.lo[c] == lo && K.mn[c] == mn && (!HAS_HI || K.hi[c] == hi);
-}
-
+// (pv_home, pv_same: spsp_device.h)
 // a slot word: the claimer's entry number + 1 in the low half (0: free), the holders counted so far in the high half
 template <bool HAS_HI>
 __global__ __launch_bounds__(kPvThreads) void k_pv_count(SortedKeys K, const uint64_t* __restrict__ off, uint32_t n, uint32_t nq,
