@@ -1007,6 +1007,84 @@ int spsp_accumulation_csv_host(const spsp_accumulation_row* rows, uint32_t n, ui
 int spsp_accumulation_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_orders, uint64_t seed, int precision,
                             const char* out_prefix, int chatter, double rate, spsp_accumulation_row** rows /* may be NULL; spsp_free */);
 
+/* ------------------------------------------------------------- groups ---- */
+/* Per-group core, exclusive and marker keys of a partitioned collection (not in the reference): what each group shares, what it
+ * holds that no other group holds, and which keys identify it.  Sketches 0 .. n-1 in list order with key sets K_i, c_i = |K_i|,
+ * 1 <= n <= 65535; there are no queries.  group[i] in 0 .. G-1 with 1 <= G <= n, every group with at least one member; size_c =
+ * the members of group c.  h(x) = the sketches that hold key x, h_c(x) = the members of group c that hold it (sum over c of h_c = h).
+ * THRESHOLDS, read as fractions; no floating point decides anything.
+ *   inside   num / den,   1 <= num <= den <= 1 000 000:                   in_min_c  = ceil(num * size_c / den)          (>= 1)
+ *   outside  onum / oden, 0 <= onum <= oden, 1 <= oden <= 1 000 000:      out_max_c = floor(onum * (n - size_c) / oden)
+ * with 64-bit products, computed once on the host by spsp_groups_bounds_host (the device call uses that very function).
+ * A key x is, for group c (counts, not a partition):
+ *   present    h_c >= 1
+ *   core       h_c >= in_min_c
+ *   exclusive  h_c >= 1 and h_c == h                  (no holder outside c)
+ *   marker     core and h - h_c <= out_max_c
+ * With onum == 0 a marker is a core key nobody outside holds; with onum > 0 one key may be a marker of several groups.
+ * Every number below is a property of the sets and the labels alone. */
+typedef struct spsp_group_row {          /* 48 bytes, one per group */
+    uint64_t members;     /* size_c */
+    uint64_t entries;     /* the members' key counts added up = the sum of h_c over the present keys */
+    uint64_t present, core, exclusive, marker;   /* distinct keys of each kind */
+} spsp_group_row;
+typedef struct spsp_group_member_row {   /* 24 bytes, one per sketch i of group c: the keys of K_i that are core, exclusive, marker of c */
+    uint64_t core, exclusive, marker;
+} spsp_group_member_row;
+/* A labels file: one label per line in list order; "\r\n" is tolerated and the final newline is optional.  Groups are numbered by
+ * first appearance: group[i] = the number of line i + 1's label, *n_groups = G.  *names (may be NULL, with names_len) receives the
+ * G labels NUL-terminated back to back, released with spsp_free().  SPSP_ERR_ARG, the message naming the line: a line count
+ * other than n, an empty label, a label that holds ',', '"' or a control character. */
+int spsp_groups_labels_host(const char* text, uint64_t len, uint32_t n, uint32_t* group /* n */, uint32_t* n_groups, char** names /* may be NULL */,
+                            uint64_t* names_len /* may be NULL */);
+/* The labels and thresholds validated and the bounds above computed: size, in_min, out_max (each n_groups words, each may be NULL).
+ * SPSP_ERR_ARG: n == 0 or n > 65535, n_groups == 0 or n_groups > n, a label >= n_groups, a group without a member (the message
+ * names it), thresholds outside the ranges above. */
+int spsp_groups_bounds_host(const uint32_t* group, uint32_t n, uint32_t n_groups, uint32_t num, uint32_t den, uint32_t onum, uint32_t oden,
+                            uint32_t* size, uint32_t* in_min, uint32_t* out_max);
+/* The rows of the groups and of their members over concatenated sorted key arrays on the device (as spsp_prevalence_device takes
+ * them; only read).  rows: n_groups; members: n, or NULL.  want_markers != 0: the marker keys as n_groups sketches back to back --
+ * group c's at [marker_off[c], marker_off[c + 1]), strictly increasing by (minimizer, kmer_hi, kmer_lo) -- in arrays OWNED BY THE
+ * CONTEXT, valid until the next groups call on it, distinct from the decoder's, the downsampler's, the selection's and the
+ * accumulation's buffers, ready for spsp_compare_device, spsp_gather_device, spsp_prevalence_device and spsp_keys_select_device
+ * (with marker_off as their offsets).  want_markers == 0: the three pointers are set to NULL and marker_off may be NULL.
+ * The call uses the prevalence pass's table and holders[] (a d_holders pointer obtained earlier is overwritten).  Launches, the
+ * same chain whatever the keys are: the prevalence pass's table fill (h per entry), a second table keyed by (key, group) filled
+ * and read back the same way (h_c per entry, the key's four properties for the entry's group, and one bit on the entry that
+ * claimed the cell), one workgroup per sketch that counts its entries, ONE host wait, and the group rows added up on the host.
+ * With markers: a flag kernel over the claimers, the downsampling pass's compaction with the sketch bounds (inside that one
+ * wait), the runs moved to their groups' regions and the regions of more than one run sorted (the sort's own wait).
+ * SPSP_ERR_ARG (rows, members and marker_off zeroed): what spsp_groups_bounds_host refuses, k outside 1..63, decreasing offsets, a
+ * context switched to unordered keys, keys out of order or twice inside a sketch; SPSP_ERR_OVERFLOW: an extent above 0xfffffff0.
+ * A refused call leaves the context usable. */
+int spsp_groups_device(spsp_ctx* ctx, uint32_t k, const void* d_minimizer, const void* d_kmer_lo, const void* d_kmer_hi /* NULL if k <= 32 */,
+                       const uint64_t* h_sk_off /* n + 1 */, uint32_t n, const uint32_t* h_group /* n */, uint32_t n_groups, uint32_t num, uint32_t den,
+                       uint32_t onum, uint32_t oden, spsp_group_row* rows /* n_groups */, spsp_group_member_row* members /* n; may be NULL */,
+                       int want_markers, void** d_out_minimizer, void** d_out_kmer_lo, void** d_out_kmer_hi,
+                       uint64_t* marker_off /* n_groups + 1; may be NULL without markers */);
+/* The text of <prefix>_groups.csv.gz: "group,members,keys,present,core,exclusive,marker,f_core,f_marker" and one line per group;
+ * keys = entries, f_core = core / present, f_marker = marker / core.  The two quotients are IEEE doubles printed as
+ * %.<precision>g, 0 on a zero denominator, and decide nothing.  SPSP_ERR_ARG for a row with core > present, marker > core or
+ * exclusive > present.  *text is released with spsp_free(). */
+int spsp_groups_csv_host(const spsp_group_row* rows, uint32_t n_groups, const char* const* group_names, int precision, char** text, uint64_t* len);
+/* The text of <prefix>_members.csv.gz: "sketch,group,keys,core,exclusive,marker,f_core,f_marker" and one line per sketch;
+ * keys = c_i (card[i]), f_core = core / c_i, f_marker = marker / the group's marker count.  SPSP_ERR_ARG for a label >= n_groups
+ * and for a member row that exceeds c_i (or has marker > core) or its group's row. */
+int spsp_groups_members_csv_host(const spsp_group_member_row* members, uint32_t n, const char* const* sketch_names, const uint32_t* group,
+                                 const uint64_t* card, const spsp_group_row* rows, uint32_t n_groups, const char* const* group_names, int precision,
+                                 char** text, uint64_t* len);
+/* The whole-file driver: the files are read, inflated and decoded as spsp_prevalence_files does it, with the same `rate` argument
+ * and refusals (k == m collections are SPSP_ERR_ARG); labels_path names the labels file (spsp_groups_labels_host).  Writes
+ * <out_prefix>_groups.csv.gz and <out_prefix>_members.csv.gz (gzip level 1, as the matrices) and no matrices.  write_markers != 0:
+ * also one sketch per group, <out_prefix>_markers_<c>.gz with <c> the group's number (spsp_sketch_from_keys_host, gzip level 9; a
+ * group without a marker gets the sketch of no keys), and <out_prefix>_markers.txt, which lists them in group order -- a file of
+ * files for -f / -q.  The rate written into their headers follows spsp_select_files' rule (mixed rates need a rate).  rows,
+ * members (may be NULL) receive copies released with spsp_free(); *n_groups (may be NULL) = G.  One device. */
+int spsp_groups_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, const char* labels_path, int precision, uint32_t num, uint32_t den,
+                      uint32_t onum, uint32_t oden, int write_markers, const char* out_prefix, int chatter, double rate,
+                      spsp_group_row** rows /* may be NULL; spsp_free */, spsp_group_member_row** members /* may be NULL; spsp_free */,
+                      uint32_t* n_groups /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,10 @@ PREVALENCE_ROW_DTYPE = np.dtype([("core", "<u8"), ("shell", "<u8"), ("unique", "
 ACCUMULATION_ROW_DTYPE = np.dtype([("pan_min", "<u8"), ("pan_max", "<u8"), ("pan_sum", "<u8"), ("core_min", "<u8"), ("core_max", "<u8"),
                                    ("core_sum", "<u8"), ("pan_first", "<u8"), ("core_first", "<u8")])
 
+# spsp_group_row / spsp_group_member_row: a group's distinct keys by kind, and a member's own keys by kind (include/spsp.h)
+GROUP_ROW_DTYPE = np.dtype([("members", "<u8"), ("entries", "<u8"), ("present", "<u8"), ("core", "<u8"), ("exclusive", "<u8"), ("marker", "<u8")])
+GROUP_MEMBER_ROW_DTYPE = np.dtype([("core", "<u8"), ("exclusive", "<u8"), ("marker", "<u8")])
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -135,6 +139,7 @@ ABI_SYMBOLS = [
     "spsp_tree_cells_device", "spsp_tree_cut_host", "spsp_tree_csv_host", "spsp_tree_newick_host", "spsp_tree_files",
     "spsp_keys_select_device", "spsp_select_band_host", "spsp_sketch_from_keys_host", "spsp_select_files",
     "spsp_accumulation_orders_host", "spsp_accumulation_plan_host", "spsp_accumulation_device", "spsp_accumulation_csv_host", "spsp_accumulation_files",
+    "spsp_groups_labels_host", "spsp_groups_bounds_host", "spsp_groups_device", "spsp_groups_csv_host", "spsp_groups_members_csv_host", "spsp_groups_files",
 ]
 
 _lib = None
@@ -326,6 +331,19 @@ def lib():
         L.spsp_accumulation_csv_host.argtypes = [vp, u32, u32, i32, P(vp), P(C.c_size_t)]
         L.spsp_accumulation_files.restype = i32
         L.spsp_accumulation_files.argtypes = [vp, P(cp), u32, u32, u64, i32, cp, i32, dbl, P(vp)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_groups_device"):
+        L.spsp_groups_labels_host.restype = i32
+        L.spsp_groups_labels_host.argtypes = [vp, u64, u32, vp, P(u32), P(vp), P(u64)]
+        L.spsp_groups_bounds_host.restype = i32
+        L.spsp_groups_bounds_host.argtypes = [vp, u32, u32, u32, u32, u32, u32, vp, vp, vp]
+        L.spsp_groups_device.restype = i32
+        L.spsp_groups_device.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, u32, u32, u32, u32, u32, vp, vp, i32, P(vp), P(vp), P(vp), vp]
+        L.spsp_groups_csv_host.restype = i32
+        L.spsp_groups_csv_host.argtypes = [vp, u32, P(cp), i32, P(vp), P(u64)]
+        L.spsp_groups_members_csv_host.restype = i32
+        L.spsp_groups_members_csv_host.argtypes = [vp, u32, P(cp), vp, vp, vp, u32, P(cp), i32, P(vp), P(u64)]
+        L.spsp_groups_files.restype = i32
+        L.spsp_groups_files.argtypes = [vp, P(cp), u32, cp, i32, u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(vp), P(u32)]
     _lib = L
     return L
 
@@ -627,6 +645,56 @@ def accumulation_csv(rows, n_orders, precision=6):
     rows = np.ascontiguousarray(rows, dtype=ACCUMULATION_ROW_DTYPE)
     out, ln = C.c_void_p(), C.c_size_t()
     _check(lib().spsp_accumulation_csv_host(rows.ctypes.data if len(rows) else None, len(rows), n_orders, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def groups_labels(text, n):
+    """spsp_groups_labels_host: the text of a labels file (one label per line, in list order) for n sketches -> (group np.uint32[n],
+    names: the G labels in the order of their first appearance)"""
+    if isinstance(text, str):
+        text = text.encode()
+    group = np.zeros(max(n, 1), dtype=np.uint32)
+    G, names, ln = C.c_uint32(), C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_groups_labels_host(text, len(text), n, group.ctypes.data, C.byref(G), C.byref(names), C.byref(ln)))
+    blob = _take(names, ln.value)
+    return group[:n], [x.decode() for x in blob.split(b"\0")[:G.value]]
+
+
+def groups_bounds(group, n_groups, num, den, onum=0, oden=1):
+    """spsp_groups_bounds_host: labels (0 .. n_groups-1 per sketch) and the two thresholds as fractions -> (size, in_min, out_max),
+    np.uint32[n_groups] each: in_min = ceil(num * size / den), out_max = floor(onum * (n - size) / oden)"""
+    group = np.ascontiguousarray(group, dtype=np.uint32)
+    out = [np.zeros(max(n_groups, 1), dtype=np.uint32) for _ in range(3)]
+    _check(lib().spsp_groups_bounds_host(group.ctypes.data if len(group) else None, len(group), n_groups, num, den, onum, oden, *[a.ctypes.data for a in out]))
+    return tuple(a[:n_groups] for a in out)
+
+
+def groups_csv(rows, names, precision=6):
+    """spsp_groups_csv_host: group rows (GROUP_ROW_DTYPE array) and the groups' names -> the text of <prefix>_groups.csv.gz"""
+    rows = np.ascontiguousarray(rows, dtype=GROUP_ROW_DTYPE)
+    if len(names) != len(rows):
+        raise ValueError("groups_csv: one name per group")
+    arr, _alive = _paths_array(names)
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_groups_csv_host(rows.ctypes.data if len(rows) else None, len(rows), arr, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def groups_members_csv(members, sketch_names, group, card, rows, names, precision=6):
+    """spsp_groups_members_csv_host: member rows (GROUP_MEMBER_ROW_DTYPE array), the sketches' names, labels and key counts, the group
+    rows and the groups' names -> the text of <prefix>_members.csv.gz"""
+    members = np.ascontiguousarray(members, dtype=GROUP_MEMBER_ROW_DTYPE)
+    rows = np.ascontiguousarray(rows, dtype=GROUP_ROW_DTYPE)
+    group = np.ascontiguousarray(group, dtype=np.uint32)
+    card = np.ascontiguousarray(card, dtype=np.uint64)
+    n = len(members)
+    if len(sketch_names) != n or len(group) != n or len(card) != n or len(names) != len(rows):
+        raise ValueError("groups_members_csv: one name, label and key count per sketch, one name per group")
+    s_arr, _a = _paths_array(sketch_names)
+    g_arr, _b = _paths_array(names)
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_groups_members_csv_host(members.ctypes.data if n else None, n, s_arr, group.ctypes.data if n else None, card.ctypes.data if n else None,
+                                              rows.ctypes.data if len(rows) else None, len(rows), g_arr, precision, C.byref(out), C.byref(ln)))
     return _take(out, ln.value)
 
 
@@ -1264,6 +1332,41 @@ class Context:
         rows = C.c_void_p()
         _check(lib().spsp_accumulation_files(self._h, arr, n, orders, seed, precision, prefix.encode(), 0, _rate_arg(rate), C.byref(rows)))
         return np.frombuffer(_take(rows, n * ACCUMULATION_ROW_DTYPE.itemsize), dtype=ACCUMULATION_ROW_DTYPE).copy()
+
+    def groups_device(self, k, d_min, d_lo, d_hi, sk_off, n, group, n_groups, num, den, onum=0, oden=1, want_markers=False):
+        """spsp_groups_device: per group of the labelled sketches 0 .. n-1 (concatenated sorted key arrays on the device) the distinct
+        keys present, core (held by ceil(num * size / den) members or more), exclusive (no holder outside) and marker (core, and at
+        most floor(onum * (n - size) / oden) holders outside), and per sketch its own keys of the last three kinds ->
+        (rows GROUP_ROW_DTYPE[n_groups], members GROUP_MEMBER_ROW_DTYPE[n]) [, (d_minimizer, d_kmer_lo, d_kmer_hi or None, marker_off
+        np.uint64[n_groups + 1]): the groups' marker keys as sketches back to back in arrays the context owns, valid until the next
+        groups call]"""
+        sk_off = np.ascontiguousarray(sk_off, dtype=np.uint64)
+        if len(sk_off) != n + 1:
+            raise ValueError("groups_device: n + 1 sketch offsets")
+        group = np.ascontiguousarray(group, dtype=np.uint32)
+        if len(group) != n:
+            raise ValueError("groups_device: one label per sketch")
+        rows = np.zeros(max(n_groups, 1), dtype=GROUP_ROW_DTYPE)
+        members = np.zeros(max(n, 1), dtype=GROUP_MEMBER_ROW_DTYPE)
+        moff = np.zeros(max(n_groups, 0) + 1, dtype=np.uint64)
+        o_mn, o_lo, o_hi = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().spsp_groups_device(self._h, k, d_min, d_lo, d_hi, sk_off.ctypes.data, n, group.ctypes.data if n else rows.ctypes.data, n_groups, num, den,
+                                        onum, oden, rows.ctypes.data, members.ctypes.data, 1 if want_markers else 0, C.byref(o_mn), C.byref(o_lo),
+                                        C.byref(o_hi), moff.ctypes.data))
+        rows, members = rows[:n_groups], members[:n]
+        return (rows, members, (o_mn.value, o_lo.value, o_hi.value, moff)) if want_markers else (rows, members)
+
+    def groups_files(self, paths, prefix, labels, num, den, onum=0, oden=1, markers=False, precision=6, rate=0.0):
+        """spsp_groups_files: sketch files and a labels file (one label per line, in the files' order) -> <prefix>_groups.csv.gz,
+        <prefix>_members.csv.gz and, markers=True, <prefix>_markers_<c>.gz per group with the list <prefix>_markers.txt ->
+        (rows, members).  rate: as compare_files (0.0, a rate, or "auto")"""
+        n = len(paths)
+        arr, _alive = _paths_array(paths)
+        rows, members, G = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        _check(lib().spsp_groups_files(self._h, arr, n, str(labels).encode(), precision, num, den, onum, oden, 1 if markers else 0, prefix.encode(), 0,
+                                       _rate_arg(rate), C.byref(rows), C.byref(members), C.byref(G)))
+        return (np.frombuffer(_take(rows, G.value * GROUP_ROW_DTYPE.itemsize), dtype=GROUP_ROW_DTYPE).copy(),
+                np.frombuffer(_take(members, n * GROUP_MEMBER_ROW_DTYPE.itemsize), dtype=GROUP_MEMBER_ROW_DTYPE).copy())
 
     def select_files(self, paths, prefix, what, each=False, n_query=0, rate=None):
         """spsp_select_files: sketch files (the n_query queries first, or none) -> the keys in the band `what` (select_band's words)

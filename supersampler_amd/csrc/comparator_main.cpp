@@ -18,7 +18,10 @@
 // keys of the index as one sketch, <o>_select.gz; -E every sketch's (every query's) own, <o>_<i>_<its file name>, listed in
 // <o>_select.txt (spsp_select_files).  An eighth: -A <orders> [-z <seed>] without -q draws the index's accumulation curves instead -- the
 // size of the union (pan) and of the intersection (core) of the first j sketches, over <orders> orders of them: the list order and
-// shuffles drawn from the seed, 1 unless -z names it (spsp_accumulation_files) -> <o>_accumulation.csv.gz.
+// shuffles drawn from the seed, 1 unless -z names it (spsp_accumulation_files) -> <o>_accumulation.csv.gz.  A ninth: -G <labels file>
+// [-T <t>] [-U <u>] [-M] without -q reads one group label per sketch of -f and counts, per group, the keys its members hold, share
+// (at least <t> of them, default 1), hold alone, and are identified by (shared, and held by at most <u> of the others, default 0)
+// (spsp_groups_files) -> <o>_groups.csv.gz, <o>_members.csv.gz and, with -M, one marker sketch per group listed in <o>_markers.txt.
 #include <getopt.h>
 
 #include <chrono>
@@ -114,8 +117,28 @@ int main(int argc, char** argv) {
     long long acc_orders = 0;        // -A <orders> [-z <seed>]: neither letter is in the reference's option string
     bool accumulation = false, acc_seeded = false;
     uint64_t acc_seed = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:")) != -1) {
+    string labels_file;              // -G <labels file> [-T <t>] [-U <u>] [-M]: none of the four letters is in the reference's option string
+    bool groups = false, gp_markers = false;
+    int gp_opts = 0;                 // -T, -U or -M seen
+    uint32_t gp_num = 1, gp_den = 1, gp_onum = 0, gp_oden = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:M")) != -1) {
         switch (ch) {
+            case 'G': labels_file = optarg; groups = true; break;
+            case 'T':
+                if (!parse_fraction(optarg, &gp_num, &gp_den)) {
+                    cout << "-T takes the share of a group's members that makes a key core, in (0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
+                    return 1;
+                }
+                ++gp_opts;
+                break;
+            case 'U':
+                if (!parse_fraction(optarg, &gp_onum, &gp_oden, true)) {
+                    cout << "-U takes the share of the other sketches that may hold a marker, in [0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
+                    return 1;
+                }
+                ++gp_opts;
+                break;
+            case 'M': gp_markers = true; ++gp_opts; break;
             case 'A': {
                 char* e = nullptr;
                 acc_orders = strtoll(optarg, &e, 10);
@@ -244,6 +267,11 @@ int main(int argc, char** argv) {
         cout << "-A draws the pan and core curves of the index: not together with -q, -g, -c, -C, -N, -P, -r, -R, -l, -L, -S or -E" << endl;
         return 1;
     }
+    if (gp_opts && !groups) { cout << "-T, -U and -M belong to the groups of -G <labels file>: they need -G" << endl; return 1; }
+    if (groups && (query != "" || gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts || select_opts || accumulation)) {
+        cout << "-G counts the keys of the index's groups: not together with -q, -g, -c, -C, -N, -P, -r, -R, -l, -L, -S, -E or -A" << endl;
+        return 1;
+    }
     if (weights_file != "" && !rep_opts) { cout << "-w gives the weights -r / -R order the sketches by: it needs one of them" << endl; return 1; }
     vector<uint64_t> weights;
     if (weights_file != "" && inputfof != "") {
@@ -296,6 +324,17 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (groups) {
+        // one device, as gather
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_groups_files(ctx, paths.data(), (uint32_t)paths.size(), labels_file.c_str(), (int)p, gp_num, gp_den, gp_onum, gp_oden,
+                                                  gp_markers ? 1 : 0, output_name.c_str(), 1, rate, nullptr, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Groups failed: " << err << endl; return 1; }
+        return 0;
     }
     if (accumulation) {
         // one device, as gather

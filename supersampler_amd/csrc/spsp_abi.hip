@@ -280,7 +280,8 @@ void spsp_destroy(spsp_ctx* c) {
                       &c->g_edges, &c->g_byref, &c->g_hold, &c->g_count, &c->g_state, &c->g_rows, &c->cl_work, &c->cl_rows, &c->nb_work, &c->nb_cand, &c->nb_rows,
                       &c->pv_off, &c->pv_table, &c->pv_hold, &c->pv_rows, &c->pv_spec, &c->rp_work, &c->rp_edges, &c->rp_rows, &c->tr_work, &c->tr_edges, &c->tr_forest,
                       &c->sel_mn[0], &c->sel_mn[1], &c->sel_lo[0], &c->sel_lo[1], &c->sel_hi[0], &c->sel_hi[1], &c->sel_t_mn, &c->sel_t_lo, &c->sel_t_hi, &c->sel_work,
-                      &c->ac_work, &c->ac_keys, &c->ac_list, &c->ac_rank, &c->ac_hist};
+                      &c->ac_work, &c->ac_keys, &c->ac_list, &c->ac_rank, &c->ac_hist,
+                      &c->gp_table, &c->gp_cell, &c->gp_work, &c->gp_mn, &c->gp_lo, &c->gp_hi, &c->gp_t_mn, &c->gp_t_lo, &c->gp_t_hi};
     for (DevBuf* b : bufs) b->release();
     devbuf_flush_retired();
     for (int kind = 0; kind < kEvKinds; ++kind) {

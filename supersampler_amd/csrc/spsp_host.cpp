@@ -2159,6 +2159,128 @@ int spsp_accumulation_csv_host(const spsp_accumulation_row* rows, uint32_t n, ui
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------------ groups
+// a labels file: one label per line in list order, groups numbered by first appearance
+int spsp_groups_labels_host(const char* text, uint64_t len, uint32_t n, uint32_t* group, uint32_t* n_groups, char** names, uint64_t* names_len) {
+    if (names) *names = nullptr;
+    if (names_len) *names_len = 0;
+    if (n_groups) *n_groups = 0;
+    if ((!text && len) || !group || !n_groups) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n == 0 || n > 65535) { set_error("groups take 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
+    std::unordered_map<std::string, uint32_t> seen;
+    std::string blob;
+    uint64_t line = 0, pos = 0;
+    while (pos < len) {
+        uint64_t end = pos;
+        while (end < len && text[end] != '\n') ++end;
+        uint64_t stop = end;
+        if (stop > pos && text[stop - 1] == '\r') --stop;  // ("\r\n" is tolerated)
+        ++line;
+        if (line > n) { set_error("labels: line %llu: more labels than the %u sketches", (unsigned long long)line, n); return SPSP_ERR_ARG; }
+        if (stop == pos) { set_error("labels: line %llu: an empty label", (unsigned long long)line); return SPSP_ERR_ARG; }
+        for (uint64_t q = pos; q < stop; ++q) {
+            const unsigned char c = (unsigned char)text[q];
+            if (c == ',' || c == '"' || c < 0x20 || c == 0x7f) {
+                set_error("labels: line %llu: a label holds ',', '\"' or a control character (byte 0x%02x)", (unsigned long long)line, (unsigned)c);
+                return SPSP_ERR_ARG;
+            }
+        }
+        const std::string label(text + pos, (size_t)(stop - pos));
+        const auto it = seen.find(label);
+        if (it != seen.end()) group[line - 1] = it->second;
+        else {
+            const uint32_t g = (uint32_t)seen.size();
+            seen.emplace(label, g);
+            group[line - 1] = g;
+            blob.append(label); blob.push_back('\0');
+        }
+        pos = end + 1;                                     // (the final newline is optional: nothing behind it is no line)
+    }
+    if (line != n) { set_error("labels: line %llu: the file ends after %llu label(s), %u sketches are listed", (unsigned long long)(line + 1), (unsigned long long)line, n); return SPSP_ERR_ARG; }
+    *n_groups = (uint32_t)seen.size();
+    if (names) {
+        uint64_t l = 0;
+        const int rc = text_out(blob, names, &l);
+        if (rc) return rc;
+        if (names_len) *names_len = l;
+    }
+    return SPSP_OK;
+}
+
+int spsp_groups_bounds_host(const uint32_t* group, uint32_t n, uint32_t n_groups, uint32_t num, uint32_t den, uint32_t onum, uint32_t oden,
+                            uint32_t* size, uint32_t* in_min, uint32_t* out_max) {
+    if (n == 0 || n > 65535) { set_error("groups take 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
+    if (n_groups == 0 || n_groups > n) { set_error("groups: %u groups of %u sketches (1 .. n; every group has a member)", n_groups, n); return SPSP_ERR_ARG; }
+    if (!group) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (num == 0 || num > den || den > 1000000) { set_error("groups: inside threshold %u / %u: needs 1 <= num <= den <= 1000000", num, den); return SPSP_ERR_ARG; }
+    if (onum > oden || oden == 0 || oden > 1000000) { set_error("groups: outside tolerance %u / %u: needs 0 <= onum <= oden, 1 <= oden <= 1000000", onum, oden); return SPSP_ERR_ARG; }
+    std::vector<uint32_t> members(n_groups, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (group[i] >= n_groups) { set_error("groups: sketch %u has label %u, there are %u groups", i, group[i], n_groups); return SPSP_ERR_ARG; }
+        ++members[group[i]];
+    }
+    for (uint32_t c = 0; c < n_groups; ++c)
+        if (members[c] == 0) { set_error("groups: group %u has no member", c); return SPSP_ERR_ARG; }
+    for (uint32_t c = 0; c < n_groups; ++c) {
+        if (size) size[c] = members[c];
+        if (in_min) in_min[c] = (uint32_t)(((uint64_t)num * members[c] + den - 1) / den);     // h_c * den >= num * size_c
+        if (out_max) out_max[c] = (uint32_t)((uint64_t)onum * (n - members[c]) / oden);       // (h - h_c) * oden <= onum * (n - size_c)
+    }
+    return SPSP_OK;
+}
+
+int spsp_groups_csv_host(const spsp_group_row* rows, uint32_t n_groups, const char* const* group_names, int precision, char** text, uint64_t* len) {
+    if (!text || !len || !rows || !group_names) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_groups == 0 || n_groups > 65535) { set_error("groups: %u groups (1 .. 65535)", n_groups); return SPSP_ERR_ARG; }
+    std::string out = "group,members,keys,present,core,exclusive,marker,f_core,f_marker\n";
+    char num[64];
+    for (uint32_t c = 0; c < n_groups; ++c) {
+        const spsp_group_row& r = rows[c];
+        const char* why = r.core > r.present ? "more core keys than present keys" : r.marker > r.core ? "more marker keys than core keys" :
+                          r.exclusive > r.present ? "more exclusive keys than present keys" : nullptr;
+        if (why) { set_error("group row %u cannot be a group's counts: %s", c, why); return SPSP_ERR_ARG; }
+        out += group_names[c]; out += ',';
+        out += std::to_string(r.members); out += ',';
+        out += std::to_string(r.entries); out += ',';
+        out += std::to_string(r.present); out += ',';
+        out += std::to_string(r.core); out += ',';
+        out += std::to_string(r.exclusive); out += ',';
+        out += std::to_string(r.marker); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, r.present ? (double)r.core / (double)r.present : 0.0)); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, r.core ? (double)r.marker / (double)r.core : 0.0)); out += '\n';
+    }
+    return text_out(out, text, len);
+}
+
+int spsp_groups_members_csv_host(const spsp_group_member_row* members, uint32_t n, const char* const* sketch_names, const uint32_t* group,
+                                 const uint64_t* card, const spsp_group_row* rows, uint32_t n_groups, const char* const* group_names, int precision,
+                                 char** text, uint64_t* len) {
+    if (!text || !len || !members || !sketch_names || !group || !card || !rows || !group_names) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n == 0 || n > 65535) { set_error("groups take 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
+    if (n_groups == 0 || n_groups > n) { set_error("groups: %u groups of %u sketches (1 .. n; every group has a member)", n_groups, n); return SPSP_ERR_ARG; }
+    std::string out = "sketch,group,keys,core,exclusive,marker,f_core,f_marker\n";
+    char num[64];
+    for (uint32_t i = 0; i < n; ++i) {
+        const spsp_group_member_row& r = members[i];
+        if (group[i] >= n_groups) { set_error("member row %u has label %u, there are %u groups", i, group[i], n_groups); return SPSP_ERR_ARG; }
+        const spsp_group_row& g = rows[group[i]];
+        const uint64_t keys = card[i];
+        const char* why = (r.core > keys || r.exclusive > keys || r.marker > keys) ? "more keys of a kind than the sketch holds" :
+                          r.marker > r.core ? "more marker keys than core keys" :
+                          (r.core > g.core || r.exclusive > g.exclusive || r.marker > g.marker) ? "more keys of a kind than its group has" : nullptr;
+        if (why) { set_error("member row %u cannot be a sketch's counts: %s", i, why); return SPSP_ERR_ARG; }
+        out += sketch_names[i]; out += ',';
+        out += group_names[group[i]]; out += ',';
+        out += std::to_string(keys); out += ',';
+        out += std::to_string(r.core); out += ',';
+        out += std::to_string(r.exclusive); out += ',';
+        out += std::to_string(r.marker); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, keys ? (double)r.core / (double)keys : 0.0)); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, g.marker ? (double)r.marker / (double)g.marker : 0.0)); out += '\n';
+    }
+    return text_out(out, text, len);
+}
+
 // ------------------------------------------------------------------------------------------------ the linkage tree
 int spsp_tree_cut_host(const spsp_tree_row* rows, uint64_t n_rows, uint32_t n, const uint64_t* card, int metric, uint32_t floor_num, uint32_t floor_den,
                        uint32_t num, uint32_t den, uint32_t* cluster, uint64_t* n_clusters) {

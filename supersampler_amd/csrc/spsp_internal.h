@@ -132,7 +132,11 @@ enum HostSlot {
     kHsSelTotal = 32,       // ... and launch_scan_u32's total over the tiles' survivor counts: the keys selected (u64), in the same wait
     kHsAcBad = 33,          // spsp_accumulation.hip: the copy of two u32 (the table fill's keys out of order | a probe sequence that went round
                             // the table or a list place out of range << 32); accumulation_device_impl reads it behind its one wait
-    kHostSlots = 34
+    kHsGpBad = 34,          // spsp_groups.hip: the copy of the first table fill's two u32 (keys out of order | a probe sequence that went round
+                            // the table << 32); groups_device_impl reads it behind its first wait
+    kHsGpCell = 35,         // ... of the cell table's word (u32: a probe sequence that went round it, or an entry without its cell), in the same wait
+    kHsGpTotal = 36,        // ... and launch_scan_u32's total over the tiles' survivor counts: the marker keys of all groups (u64), in the same wait
+    kHostSlots = 37
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
@@ -141,7 +145,8 @@ static_assert(kHsNbCands == kHsClusterCount + 1 && kHsPvBad == kHsNbBad + 1 && k
 static_assert(kHsRpCount == kHsRpUndecided + 3 && kHsRpCount + 1 == kHsTrEdges, "the representatives pass's four slots, then the linkage tree's");
 static_assert(kHsTrRounds == kHsTrEdges + 2 && kHsTrRounds + 1 == kHsSelBad, "the linkage tree's three slots");
 static_assert(kHsSelTotal == kHsSelBad + 1 && kHsSelTotal + 1 == kHsAcBad, "the selection's two slots");
-static_assert(kHsAcBad + 1 == kHostSlots, "the accumulation's one slot: the last one");
+static_assert(kHsAcBad + 1 == kHsGpBad, "the accumulation's one slot");
+static_assert(kHsGpCell == kHsGpBad + 1 && kHsGpTotal == kHsGpBad + 2 && kHsGpTotal + 1 == kHostSlots, "the groups pass's three slots: the last ones");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -277,6 +282,11 @@ struct spsp_ctx {
     // per distinct key and one more; the holders' sketch numbers, 16 bits each, list behind list), the orders as rank tables, and the two
     // histograms (first rank, mex) of every order
     spsp::DevBuf ac_work, ac_keys, ac_list, ac_rank, ac_hist;
+    // groups (spsp_groups.hip): the cell table in HBM (one 64-bit word per slot: claimer | group << 32 | counter << 48), one word per
+    // key occurrence (h_c and the key's properties for the entry's group), the work area (flag words, the sketches' groups, the
+    // groups' bounds, the per-sketch records, keep mask, offsets, tile counts, destinations), the marker keys, and the compaction's
+    // output, which is the sort's scratch afterwards
+    spsp::DevBuf gp_table, gp_cell, gp_work, gp_mn, gp_lo, gp_hi, gp_t_mn, gp_t_lo, gp_t_hi;
 };
 
 namespace spsp {
@@ -417,6 +427,11 @@ constexpr uint32_t kAcCut = 64;                            // a list of more hol
 int accumulation_check_args(uint32_t n, uint32_t n_orders);
 int accumulation_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
                              uint32_t n, const uint32_t* orders, uint32_t n_orders, spsp_accumulation_row* rows, uint64_t* pan, uint64_t* core);
+// spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
+// groups as n_groups sketches back to back in context-owned arrays
+int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,
+                       const uint32_t* h_group, uint32_t n_groups, uint32_t num, uint32_t den, uint32_t onum, uint32_t oden, spsp_group_row* rows,
+                       spsp_group_member_row* members, bool want_markers, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* marker_off);
 // the front half of every file driver (spsp_host.cpp): the payloads of n sketch files, in file order, and what their headers say
 struct LoadedSketches {
     std::vector<uint8_t*> data;                                    // into the context's read regions, or owned (own[i])
@@ -449,6 +464,9 @@ double files_loaded(spsp_ctx* ctx, const LoadedSketches& L, uint32_t n, int chat
 int write_csv_gz(spsp_ctx* ctx, char* text, uint64_t len, const char* out_prefix, const char* suffix, double t_csv);
 // the line that names the common rate, where one was asked for (not the reference's: behind its own lines)
 void say_common_rate(const LoadedSketches& L, uint32_t n);
+// spsp_select.hip: the rate a driver writes into the headers of the sketches it makes -- the common one where one was asked for, else
+// the headers' own if they all stand for one selection threshold, else SPSP_ERR_ARG ("give a rate")
+int sketches_out_rate(const LoadedSketches& L, const char* const* paths, uint32_t n, double* out_rate);
 int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
                               const int* extra_has, const uint32_t* extra_mn, uint32_t* k_out, uint32_t* m_out, uint64_t* sk_off);
 // ingest (spsp_ingest.hip)

@@ -136,6 +136,22 @@ int keys_select_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint
     return SPSP_OK;
 }
 
+// (spsp_internal.h) the rate the output names: the common one where one was asked for, else the headers' if they all stand for one threshold
+int sketches_out_rate(const LoadedSketches& L, const char* const* paths, uint32_t n, double* out_rate) {
+    *out_rate = L.ds_rate;
+    if (L.rate_asked) return SPSP_OK;
+    uint64_t thr0 = 0; double last = 0; uint64_t last_thr = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t ki = 0, mi = 0; uint64_t cnt = 0; double ri = 0;
+        const int rc = spsp_sketch_header_host(L.data[i], L.len[i], &ki, &mi, &cnt, &ri);
+        if (rc) { const std::string why = spsp_last_error(); set_error("'%s': %s", paths[i], why.c_str()); return rc; }
+        if (i == 0 || ri != last) { last = ri; last_thr = spsp_threshold_host(L.k, L.m, ri); }   // (powl once per run of equal rates)
+        if (i == 0) { thr0 = last_thr; *out_rate = ri; }
+        else if (last_thr != thr0) { set_error("sketches of different rates: give a rate ('%s' was sketched at rate %g, '%s' at %g)", paths[0], *out_rate, paths[i], ri); return SPSP_ERR_ARG; }
+    }
+    return SPSP_OK;
+}
+
 // spsp_select_files behind its argument checks: the sketches loaded (spsp_host.cpp), decoded (and brought down to the common
 // rate), the selection, the selected keys copied back, one sketch file per output sketch (spsp_sketch_from_keys_host, gzip level 9
 // as the sketcher writes) and, for `each`, the list of them
@@ -144,18 +160,8 @@ static int select_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uin
     LoadedSketches L;
     int rc = load_sketch_files(ctx, paths, n, rate, &L);
     if (!rc && L.k && L.k == L.m) { set_error("select is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }
-    // the rate the output names: the common one where one was asked for, else the headers' if they all stand for one threshold
     double out_rate = L.ds_rate;
-    if (!rc && !L.rate_asked) {
-        uint64_t thr0 = 0; double last = 0; uint64_t last_thr = 0;
-        for (uint32_t i = 0; i < n && !rc; ++i) {
-            uint32_t ki = 0, mi = 0; uint64_t cnt = 0; double ri = 0;
-            if ((rc = spsp_sketch_header_host(L.data[i], L.len[i], &ki, &mi, &cnt, &ri))) { const std::string why = spsp_last_error(); set_error("'%s': %s", paths[i], why.c_str()); break; }
-            if (i == 0 || ri != last) { last = ri; last_thr = spsp_threshold_host(L.k, L.m, ri); }   // (powl once per run of equal rates)
-            if (i == 0) { thr0 = last_thr; out_rate = ri; }
-            else if (last_thr != thr0) { set_error("sketches of different rates: give a rate ('%s' was sketched at rate %g, '%s' at %g)", paths[0], out_rate, paths[i], ri); rc = SPSP_ERR_ARG; }
-        }
-    }
+    if (!rc) rc = sketches_out_rate(L, paths, n, &out_rate);
     if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
     const double t0 = files_loaded(ctx, L, n, chatter);
     const uint32_t R = n - n_query, n_out = each ? (n_query ? n_query : n) : 1u;
