@@ -255,14 +255,10 @@ int accumulation_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, co
     const size_t curve_words = (size_t)n_orders * n;
     if (pan) memset(pan, 0, curve_words * 8);
     if (core) memset(core, 0, curve_words * 8);
-    if (ctx->keys_unordered) { set_error("accumulation reads sorted sketches: not on a context switched to unordered keys"); return SPSP_ERR_ARG; }
-    if (k < 1 || k > 63) { set_error("k=%u out of range 1..63", k); return SPSP_ERR_ARG; }
-    for (uint32_t i = 0; i < n; ++i)
-        if (h_sk_off[i + 1] < h_sk_off[i]) { set_error("sketch offsets must not decrease (sketch %u)", i); return SPSP_ERR_ARG; }
-    const bool has_hi = k > 32;
-    const uint64_t first = h_sk_off[0], extent = h_sk_off[n], all_keys = extent - first;
-    if (extent > 0xfffffff0ull) { set_error("too many sketch k-mers for one call"); return SPSP_ERR_OVERFLOW; }
-    if (all_keys && (!d_mn || !d_lo || (has_hi && !d_hi))) { set_error("NULL key array"); return SPSP_ERR_ARG; }
+    KeysShape shape;
+    if ((rc = sorted_keys_front(ctx, "accumulation reads", k, d_mn, d_lo, d_hi, h_sk_off, n, &shape))) return rc;
+    const bool has_hi = shape.has_hi;
+    const uint64_t first = shape.first, all_keys = shape.all_keys;
     uint32_t group = 0, window = 0;
     if ((rc = spsp_accumulation_plan_host(n, &group, &window, nullptr, nullptr))) return rc;
     // the orders as rank tables (the inverse permutations), the last group filled up with copies of the last order
@@ -384,21 +380,16 @@ int accumulation_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, co
 // rate), the orders from the seed, the curves, <out_prefix>_accumulation.csv.gz
 static int accumulation_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_orders, uint64_t seed, int precision, const char* out_prefix,
                               int chatter, double rate, std::vector<spsp_accumulation_row>* rows) {
-    LoadedSketches L;
-    int rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (L.k && L.k == L.m) { set_error("accumulation is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
-    std::vector<uint64_t> card(n, 0);
+    FilesRun run(ctx, paths, n, chatter);
+    int rc = run.begin(run.refuse_k_eq_m(run.load(rate), "accumulation is"));   // (the k == m refusal in front of the rate's own)
+    if (rc) return rc;
     rows->assign(n, spsp_accumulation_row{});
     std::vector<uint32_t> orders((size_t)n_orders * n);
-    DecodedKeys keys;
+    const DecodedKeys& keys = run.keys;
     rc = spsp_accumulation_orders_host(n, n_orders, seed, orders.data());
-    if (!rc) rc = decode_keys_impl(ctx, L.data.data(), L.len.data(), n, nullptr, nullptr, L.threshold(), &keys, card.data());
+    if (!rc) rc = run.decode();
     if (!rc) rc = accumulation_device_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n, orders.data(), n_orders, rows->data(), nullptr, nullptr);
-    L.release();
-    const double t1 = now_s();
-    ctx->stages.compare_s += t1 - t0;
+    const double t1 = run.end();
     if (rc) return rc;
     char* text = nullptr; size_t len = 0;
     if ((rc = spsp_accumulation_csv_host(rows->data(), n, n_orders, precision, &text, &len))) return rc;
@@ -406,7 +397,7 @@ static int accumulation_files(spsp_ctx* ctx, const char* const* paths, uint32_t 
     const spsp_accumulation_row& last = (*rows)[n - 1];
     printf("%u sketch(es) over %u order(s): %llu distinct keys, %llu of them in every sketch\n", n, n_orders, (unsigned long long)last.pan_first,
            (unsigned long long)last.core_first);
-    say_common_rate(L, n);
+    say_common_rate(run.L, n);
     fflush(stdout);
     return SPSP_OK;
 }
@@ -433,10 +424,5 @@ extern "C" int spsp_accumulation_files(spsp_ctx* ctx, const char* const* paths, 
     SPSP_HIP(hipSetDevice(ctx->device));
     std::vector<spsp_accumulation_row> got;
     if ((rc = accumulation_files(ctx, paths, n, n_orders, seed, precision, out_prefix, chatter, rate, &got))) return rc;
-    if (rows) {
-        *rows = (spsp_accumulation_row*)malloc(got.size() * sizeof(spsp_accumulation_row));
-        if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        memcpy(*rows, got.data(), got.size() * sizeof(spsp_accumulation_row));
-    }
-    return SPSP_OK;
+    return rows ? give_rows(got, rows) : SPSP_OK;
 }

@@ -218,18 +218,14 @@ int cluster_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const u
 // spsp_cluster_files behind its argument checks: the sketches loaded (spsp_host.cpp), the clusters, <out_prefix>_clusters.csv.gz
 static int cluster_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, int metric, uint32_t num, uint32_t den, const char* out_prefix,
                          int chatter, double rate, std::vector<spsp_cluster_row>* rows, uint64_t* n_clusters) {
-    LoadedSketches L;
-    int rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (L.k && L.k == L.m) { set_error("clustering is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
+    FilesRun run(ctx, paths, n, chatter);
+    int rc = run.begin(run.refuse_k_eq_m(run.load(rate), "clustering is"));   // (the k == m refusal in front of the rate's own)
+    if (rc) return rc;
     uint32_t k = 0, m = 0;
     uint64_t n_edges = 0;
-    std::vector<uint64_t> card(n, 0);
-    rc = cluster_payloads_impl(ctx, L.data.data(), L.len.data(), n, metric, num, den, L.threshold(), &k, &m, card.data(), rows, n_clusters, &n_edges);
-    L.release();
-    const double t1 = now_s();
-    ctx->stages.compare_s += t1 - t0;
+    std::vector<uint64_t>& card = run.card;
+    rc = cluster_payloads_impl(ctx, run.L.data.data(), run.L.len.data(), n, metric, num, den, run.L.threshold(), &k, &m, card.data(), rows, n_clusters, &n_edges);
+    const double t1 = run.end();
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
     if ((rc = spsp_cluster_csv_host(rows->data(), paths, n, card.data(), metric, precision, &text, &len))) return rc;
@@ -237,7 +233,7 @@ static int cluster_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, in
     uint32_t largest = 0;
     for (const spsp_cluster_row& r : *rows) largest = std::max(largest, r.size);
     printf("%u sketches, %llu edges, %llu clusters, the largest of %u\n", n, (unsigned long long)n_edges, (unsigned long long)*n_clusters, largest);
-    say_common_rate(L, n);
+    say_common_rate(run.L, n);
     fflush(stdout);
     return SPSP_OK;
 }
@@ -265,10 +261,5 @@ extern "C" int spsp_cluster_files(spsp_ctx* ctx, const char* const* paths, uint3
     uint64_t count = 0;
     if ((rc = cluster_files(ctx, paths, n, precision, metric, num, den, out_prefix, chatter, rate, &got, &count))) return rc;
     if (n_clusters) *n_clusters = count;
-    if (rows) {
-        *rows = (spsp_cluster_row*)malloc(got.size() ? got.size() * sizeof(spsp_cluster_row) : 1);
-        if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        if (!got.empty()) memcpy(*rows, got.data(), got.size() * sizeof(spsp_cluster_row));
-    }
-    return SPSP_OK;
+    return rows ? give_rows(got, rows) : SPSP_OK;
 }

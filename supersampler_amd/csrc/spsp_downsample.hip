@@ -12,7 +12,8 @@
 //                 tile offset + word prefix + popcount(word below l): neighbouring survivors land side by side
 //   k_ds_offsets  one thread per sketch boundary: survivors in front of it = its tile's offset + the bits in front of it
 // and ONE host wait, the one that reads the new offsets back.  No host path.  Everything behind the flags is ds_compact_launch
-// (spsp_internal.h): the selection (spsp_select.hip) makes its own keep mask in the same layout and runs the same three launches.
+// (spsp_internal.h).  The selection (spsp_select.hip) and the groups pass (spsp_groups.hip) keep by a word per entry instead of a hash:
+// k_ds_flag_band makes their keep mask in the same layout and ds_flag_compact_launch runs it in front of the same three launches.
 #include <algorithm>
 
 #include "spsp_device.h"
@@ -39,6 +40,35 @@ __global__ __launch_bounds__(kDsThreads) void k_ds_flag(const uint32_t* __restri
     for (uint32_t r = 0; r < kDsTile / kDsThreads; ++r) {
         const uint64_t i = (uint64_t)base + r * kDsThreads;
         const bool keep = i < n_keys && xxh64_u64((uint64_t)v[r]) <= threshold;
+        const unsigned long long word = __ballot(keep);
+        if (lane == 0) mask[(size_t)blockIdx.x * kDsWords + r * (kDsThreads / 64) + w] = word;
+        cnt += (uint32_t)__popcll(word);
+    }
+    if (lane == 0) s_cnt[w] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// keep bit of entry i of [0, n_keys): every bit of `need` set in value[i], and value[i]'s low 31 bits in [h_min, h_max].  The
+// selection: value = holders[] (need = 0x80000000 for the merged form -- only the entry that claimed its key's slot speaks for the
+// key -- else 0).  Round r of wave w of tile t fills word 32 t + 4 r + w (k_ds_flag's layout)
+__global__ __launch_bounds__(kDsThreads) void k_ds_flag_band(const uint32_t* __restrict__ holders, uint32_t n_keys, uint32_t h_min, uint32_t h_max,
+                                                             uint32_t need, unsigned long long* __restrict__ mask, uint32_t* __restrict__ tile_cnt) {
+    __shared__ uint32_t s_cnt[kDsThreads / 64];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint32_t base = blockIdx.x * kDsTile + threadIdx.x;       // (n_keys <= 0xfffffff0 and the last tile starts below it)
+    uint32_t v[kDsTile / kDsThreads];
+#pragma unroll
+    for (uint32_t r = 0; r < kDsTile / kDsThreads; ++r) {
+        const uint64_t i = (uint64_t)base + r * kDsThreads;
+        v[r] = i < n_keys ? holders[i] : 0u;
+    }
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kDsTile / kDsThreads; ++r) {
+        const uint64_t i = (uint64_t)base + r * kDsThreads;
+        const uint32_t h = v[r] & 0x7fffffffu;
+        const bool keep = i < n_keys && (v[r] & need) == need && h >= h_min && h <= h_max;
         const unsigned long long word = __ballot(keep);
         if (lane == 0) mask[(size_t)blockIdx.x * kDsWords + r * (kDsThreads / 64) + w] = word;
         cnt += (uint32_t)__popcll(word);
@@ -115,6 +145,21 @@ int ds_compact_launch(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const ui
     return SPSP_OK;
 }
 
+// (spsp_internal.h) offsets up, k_ds_flag_band, ds_compact_launch, offsets down.  h_rel and h_off_out stay the caller's until its wait
+int ds_flag_compact_launch(spsp_ctx* ctx, const DsWork& W, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint32_t* d_value,
+                           uint32_t n_keys, uint32_t h_min, uint32_t h_max, uint32_t need, const uint64_t* h_rel, uint32_t n_bounds, uint32_t* out_mn,
+                           uint64_t* out_lo, uint64_t* out_hi, uint64_t* total_host, uint64_t* h_off_out) {
+    int rc;
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)n_keys + kDsTile - 1) / kDsTile);
+    SPSP_HIP(hipMemcpyAsync(W.off_in, h_rel, (size_t)n_bounds * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_ds_flag_band, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_value, n_keys, h_min, h_max, need, W.mask, W.tile_cnt);
+    SPSP_HIP(hipGetLastError());
+    if ((rc = ds_compact_launch(ctx, has_hi, d_mn, d_lo, d_hi, W.mask, W.tile_cnt, W.tile_off, n_tiles, W.off_in, n_bounds, W.off_out, out_mn,
+                                out_lo, out_hi, total_host))) return rc;
+    SPSP_HIP(hipMemcpyAsync(h_off_out, W.off_out, (size_t)n_bounds * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return SPSP_OK;
+}
+
 int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
                          const uint64_t* h_sk_off, uint32_t n, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out) {
     const bool has_hi = k > 32;
@@ -134,22 +179,17 @@ int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const ui
     if (R == 0) return SPSP_OK;
     d_mn += first; d_lo += first; if (has_hi) d_hi += first;
     const uint32_t n_tiles = (uint32_t)((R + kDsTile - 1) / kDsTile);
-    // work area: keep mask | offsets in | offsets out | tile counts | tile offsets (+ the total)
-    const size_t mask_bytes = (size_t)n_tiles * kDsWords * 8, off_bytes = ((size_t)n + 1) * 8;
-    if ((rc = ctx->ds_work.reserve(mask_bytes + 2 * off_bytes + ((size_t)2 * n_tiles + 2) * 4 + 64))) return rc;
-    unsigned long long* d_mask = ctx->ds_work.as<unsigned long long>();
-    uint64_t* d_off_in = reinterpret_cast<uint64_t*>(ctx->ds_work.as<uint8_t>() + mask_bytes);
-    uint64_t* d_off_out = d_off_in + n + 1;
-    uint32_t* d_tile_cnt = reinterpret_cast<uint32_t*>(d_off_out + n + 1);
-    uint32_t* d_tile_off = d_tile_cnt + n_tiles;
+    const size_t off_bytes = ((size_t)n + 1) * 8;
+    if ((rc = ctx->ds_work.reserve(DsWork::bytes(n_tiles, n + 1)))) return rc;
+    const DsWork W(ctx->ds_work.p, n_tiles, n + 1);
     std::vector<uint64_t> rel((size_t)n + 1);
     for (uint32_t i = 0; i <= n; ++i) rel[i] = h_sk_off[i] - first;
-    SPSP_HIP(hipMemcpyAsync(d_off_in, rel.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_ds_flag, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, (uint32_t)R, threshold, d_mask, d_tile_cnt);
+    SPSP_HIP(hipMemcpyAsync(W.off_in, rel.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_ds_flag, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, d_mn, (uint32_t)R, threshold, W.mask, W.tile_cnt);
     SPSP_HIP(hipGetLastError());
-    if ((rc = ds_compact_launch(ctx, has_hi, d_mn, d_lo, d_hi, d_mask, d_tile_cnt, d_tile_off, n_tiles, d_off_in, n + 1, d_off_out, *out_mn, *out_lo, *out_hi,
+    if ((rc = ds_compact_launch(ctx, has_hi, d_mn, d_lo, d_hi, W.mask, W.tile_cnt, W.tile_off, n_tiles, W.off_in, n + 1, W.off_out, *out_mn, *out_lo, *out_hi,
                                 ctx->h_scalar + kHsDownsampleTotal))) return rc;
-    SPSP_HIP(hipMemcpyAsync(sk_off_out, d_off_out, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(sk_off_out, W.off_out, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
     SPSP_HIP(hipStreamSynchronize(ctx->stream));                    // (the one wait; `rel` has been read by then)
     return SPSP_OK;
 }

@@ -283,17 +283,13 @@ int gather_payloads_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const ui
 // spsp_gather_files behind its argument checks: the sketches loaded (spsp_host.cpp), the gather, <out_prefix>_gather.csv.gz
 static int gather_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, uint64_t min_keys, uint32_t max_rounds,
                         const char* out_prefix, int chatter, double rate, std::vector<spsp_gather_row>* rows) {
-    LoadedSketches L;
-    int rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (L.k && L.k == L.m) { set_error("gather is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
+    FilesRun run(ctx, paths, n, chatter);
+    int rc = run.begin(run.refuse_k_eq_m(run.load(rate), "gather is"));   // (the k == m refusal in front of the rate's own)
+    if (rc) return rc;
     uint32_t k = 0, m = 0;
-    std::vector<uint64_t> card(n, 0);
-    rc = gather_payloads_impl(ctx, L.data.data(), L.len.data(), n, n_query, min_keys, max_rounds, L.threshold(), &k, &m, card.data(), rows);
-    L.release();
-    const double t1 = now_s();
-    ctx->stages.compare_s += t1 - t0;
+    std::vector<uint64_t>& card = run.card;
+    rc = gather_payloads_impl(ctx, run.L.data.data(), run.L.len.data(), n, n_query, min_keys, max_rounds, run.L.threshold(), &k, &m, card.data(), rows);
+    const double t1 = run.end();
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
     if ((rc = spsp_gather_csv_host(rows->data(), rows->size(), paths, n, n_query, card.data(), precision, &text, &len))) return rc;
@@ -304,7 +300,7 @@ static int gather_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uin
         for (; at < rows->size() && (*rows)[at].query == q; ++at) { ++named; left = (*rows)[at].remaining; }
         printf("%s: %llu reference(s) named, %llu of %llu keys remain\n", paths[q], (unsigned long long)named, (unsigned long long)left, (unsigned long long)card[q]);
     }
-    say_common_rate(L, n);
+    say_common_rate(run.L, n);
     fflush(stdout);
     return SPSP_OK;
 }
@@ -341,10 +337,5 @@ extern "C" int spsp_gather_files(spsp_ctx* ctx, const char* const* paths, uint32
     const int rc = gather_files(ctx, paths, n, n_query, precision, min_keys, max_rounds, out_prefix, chatter, rate, &got);
     if (rc) return rc;
     if (n_rows) *n_rows = got.size();
-    if (rows) {
-        *rows = (spsp_gather_row*)malloc(got.size() ? got.size() * sizeof(spsp_gather_row) : 1);
-        if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        if (!got.empty()) memcpy(*rows, got.data(), got.size() * sizeof(spsp_gather_row));
-    }
-    return SPSP_OK;
+    return rows ? give_rows(got, rows) : SPSP_OK;
 }

@@ -19,8 +19,8 @@
 //   k_gp_rows     a workgroup per sketch over its slice of cell[]: the member row over all its entries, the four group counters
 //                 over its claiming entries; lane 0 writes one record per sketch, no global atomic.  The host adds the records of
 //                 a group's members: which member claimed a cell is a race, the sum over the group is not
-//   markers only  k_gp_flag (claimers whose cell is a marker -> k_ds_flag's keep mask), ds_compact_launch with the sketch bounds
-//                 (every sketch's surviving run), k_gp_regroup (a workgroup per sketch moves its run to its group's region: the
+//   markers only  ds_flag_compact_launch (k_ds_flag_band: claimers whose cell is a marker -> k_ds_flag's keep mask; the compaction with
+//                 the sketch bounds: every sketch's surviving run), k_gp_regroup (a workgroup per sketch moves its run to its group's region: the
 //                 members' runs in list order), big_sort_segments over the regions made of more than one run
 // Host waits: one (records, flag words, and with markers the compacted offsets); with markers the sort's own behind it.  No wait
 // depends on the data beyond sizing the output and the sort, and no workgroup ever waits for another one.
@@ -37,7 +37,6 @@ namespace spsp {
 namespace {
 
 constexpr uint32_t kGpThreads = 256;                       // 4 waves, every kernel
-constexpr uint32_t kGpLog2CapMax = 32;
 enum { kGpwBad = 0, kGpwWrapped = 1, kGpwCell = 2, kGpWords = 4 };   // flag words: the first fill's two, the cell table's, one spare
 constexpr uint32_t kGpCore = 1u << 28, kGpExclusive = 1u << 29, kGpMarker = 1u << 30, kGpClaim = 1u << 31;   // cell[e]: h_c below them
 constexpr uint32_t kGpRecord = 7;                          // u64 per sketch: member core, exclusive, marker | claimed present, core, exclusive, marker
@@ -142,27 +141,6 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_rows(const uint32_t* __restri
     record[(size_t)i * kGpRecord + t] = s;
 }
 
-// keep bit of entry i of [0, n_keys): the entry claimed its cell and the cell is a marker.  k_ds_flag's layout: round r of wave w of
-// tile t fills word 32 t + 4 r + w
-__global__ __launch_bounds__(kDsThreads) void k_gp_flag(const uint32_t* __restrict__ cell, uint32_t n_keys, unsigned long long* __restrict__ mask,
-                                                        uint32_t* __restrict__ tile_cnt) {
-    __shared__ uint32_t s_cnt[kDsThreads / 64];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint32_t base = blockIdx.x * kDsTile + threadIdx.x;       // (n_keys <= 0xfffffff0 and the last tile starts below it)
-    uint32_t cnt = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < kDsTile / kDsThreads; ++r) {
-        const uint64_t i = (uint64_t)base + r * kDsThreads;
-        const uint32_t v = i < n_keys ? cell[i] : 0u;
-        const unsigned long long word = __ballot((v & (kGpClaim | kGpMarker)) == (kGpClaim | kGpMarker));
-        if (lane == 0) mask[(size_t)blockIdx.x * kDsWords + r * (kDsThreads / 64) + w] = word;
-        cnt += (uint32_t)__popcll(word);
-    }
-    if (lane == 0) s_cnt[w] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
 // one workgroup per sketch: its surviving run [run[i], run[i + 1]) of the compacted keys goes to dest[i] .. of the output
 template <bool HAS_HI>
 __global__ __launch_bounds__(kGpThreads) void k_gp_regroup(const uint32_t* __restrict__ mn, const uint64_t* __restrict__ lo, const uint64_t* __restrict__ hi,
@@ -199,14 +177,10 @@ int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const ui
     if (sized) zero_results(rows, n_groups, members, n, marker_off);
     std::vector<uint32_t> size(sized ? n_groups : 0), in_min(size.size()), out_max(size.size());
     if ((rc = spsp_groups_bounds_host(h_group, n, n_groups, num, den, onum, oden, size.data(), in_min.data(), out_max.data()))) return rc;
-    if (ctx->keys_unordered) { set_error("groups read sorted sketches: not on a context switched to unordered keys"); return SPSP_ERR_ARG; }
-    if (k < 1 || k > 63) { set_error("k=%u out of range 1..63", k); return SPSP_ERR_ARG; }
-    for (uint32_t i = 0; i < n; ++i)
-        if (h_sk_off[i + 1] < h_sk_off[i]) { set_error("sketch offsets must not decrease (sketch %u)", i); return SPSP_ERR_ARG; }
-    const bool has_hi = k > 32;
-    const uint64_t first = h_sk_off[0], extent = h_sk_off[n], all_keys = extent - first;
-    if (extent > 0xfffffff0ull) { set_error("too many sketch k-mers for one call"); return SPSP_ERR_OVERFLOW; }
-    if (all_keys && (!d_mn || !d_lo || (has_hi && !d_hi))) { set_error("NULL key array"); return SPSP_ERR_ARG; }
+    KeysShape shape;
+    if ((rc = sorted_keys_front(ctx, "groups read", k, d_mn, d_lo, d_hi, h_sk_off, n, &shape))) return rc;
+    const bool has_hi = shape.has_hi;
+    const uint64_t first = shape.first, extent = shape.extent, all_keys = shape.all_keys;
     for (uint32_t c = 0; c < n_groups; ++c) rows[c].members = size[c];
     for (uint32_t i = 0; i < n; ++i) rows[h_group[i]].entries += h_sk_off[i + 1] - h_sk_off[i];
     if (want_markers) {
@@ -217,35 +191,25 @@ int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const ui
     if (all_keys == 0) return SPSP_OK;
 
     // the cell table: sized as the prevalence pass sizes its own -- the distinct (key, group) cells are never more than the entries
-    const char* dbg_table = getenv("SPSP_DEBUG_PREVALENCE_TABLE");
-    const bool smallest = dbg_table && !strcmp(dbg_table, "min");
-    const uint64_t want = std::max<uint64_t>(2, smallest ? all_keys : all_keys + all_keys / 2);
-    uint32_t log2cap = 1;
-    while (log2cap < kGpLog2CapMax && (1ull << log2cap) < want) ++log2cap;
+    const uint32_t log2cap = pv_table_log2cap(all_keys);
     const uint64_t cap = 1ull << log2cap;
     const uint32_t n_tiles = want_markers ? (uint32_t)((all_keys + kDsTile - 1) / kDsTile) : 0u, n_bounds = n + 1;
-    // work area: flag words | the sketches' groups (16 bits each) | the groups' bounds | records | keep mask | offsets in | offsets out |
-    // destinations | tile counts | tile offsets (+ the total)
+    // work area: flag words | the sketches' groups (16 bits each) | the groups' bounds | records | destinations | the compaction's part
     const size_t words_bytes = 64, grp_bytes = up64((size_t)n * 2), bound_bytes = up64((size_t)n_groups * sizeof(GpBound)),
-                 rec_bytes = up64((size_t)n * kGpRecord * 8), mask_bytes = (size_t)n_tiles * kDsWords * 8, off_bytes = up64((size_t)n_bounds * 8),
-                 dest_bytes = up64((size_t)n * 4);
-    if ((rc = ctx->gp_work.reserve(words_bytes + grp_bytes + bound_bytes + rec_bytes + mask_bytes + 2 * off_bytes + dest_bytes + ((size_t)2 * n_tiles + 2) * 4 + 64)) ||
+                 rec_bytes = up64((size_t)n * kGpRecord * 8), dest_bytes = up64((size_t)n * 4);
+    if ((rc = ctx->gp_work.reserve(words_bytes + grp_bytes + bound_bytes + rec_bytes + dest_bytes + DsWork::bytes(n_tiles, n_bounds))) ||
         (rc = ctx->gp_table.reserve((size_t)cap * 8)) || (rc = ctx->gp_cell.reserve((size_t)extent * 4))) return rc;
     uint8_t* w = ctx->gp_work.as<uint8_t>();
     uint32_t* d_words = reinterpret_cast<uint32_t*>(w); w += words_bytes;
     uint16_t* d_grp = reinterpret_cast<uint16_t*>(w); w += grp_bytes;
     GpBound* d_bound = reinterpret_cast<GpBound*>(w); w += bound_bytes;
     unsigned long long* d_rec = reinterpret_cast<unsigned long long*>(w); w += rec_bytes;
-    unsigned long long* d_mask = reinterpret_cast<unsigned long long*>(w); w += mask_bytes;
-    uint64_t* d_off_in = reinterpret_cast<uint64_t*>(w); w += off_bytes;
-    uint64_t* d_off_out = reinterpret_cast<uint64_t*>(w); w += off_bytes;
     uint32_t* d_dest = reinterpret_cast<uint32_t*>(w); w += dest_bytes;
-    uint32_t* d_tile_cnt = reinterpret_cast<uint32_t*>(w);
-    uint32_t* d_tile_off = d_tile_cnt + n_tiles;
+    const DsWork W(w, n_tiles, n_bounds);
     unsigned long long* d_tbl = ctx->gp_table.as<unsigned long long>();
     uint32_t* d_cell = ctx->gp_cell.as<uint32_t>();
 
-    // (host arrays the copies below read: alive until the wait)
+    // (host arrays the copies below read or write -- rel and run through the launcher's: ours, alive until the wait)
     std::vector<uint16_t> grp16(n);
     std::vector<GpBound> bounds(n_groups);
     std::vector<uint64_t> rel(n_bounds), run(n_bounds, 0);
@@ -281,13 +245,14 @@ int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const ui
         if ((rc = ctx->gp_t_mn.reserve((size_t)all_keys * 4 + 64)) || (rc = ctx->gp_t_lo.reserve((size_t)all_keys * 8 + 64)) ||
             (has_hi && (rc = ctx->gp_t_hi.reserve((size_t)all_keys * 8 + 64)))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
         for (uint32_t i = 0; i < n_bounds; ++i) rel[i] = h_sk_off[i] - first;
-        SPSP_HIP(hipMemcpyAsync(d_off_in, rel.data(), (size_t)n_bounds * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_gp_flag, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, (const uint32_t*)(d_cell + first), (uint32_t)all_keys, d_mask, d_tile_cnt);
-        SPSP_HIP(hipGetLastError());
-        if ((rc = ds_compact_launch(ctx, has_hi, d_mn + first, d_lo + first, has_hi ? d_hi + first : nullptr, d_mask, d_tile_cnt, d_tile_off, n_tiles, d_off_in,
-                                    n_bounds, d_off_out, ctx->gp_t_mn.as<uint32_t>(), ctx->gp_t_lo.as<uint64_t>(), has_hi ? ctx->gp_t_hi.as<uint64_t>() : nullptr,
-                                    ctx->h_scalar + kHsGpTotal))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        SPSP_HIP(hipMemcpyAsync(run.data(), d_off_out, (size_t)n_bounds * 8, hipMemcpyDeviceToHost, ctx->stream));
+        // kept: the entries that claimed their cell and whose cell is a marker.  The band 0 .. 0x7fffffff never cuts: it is tested on
+        // the word's low 31 bits, and the flag bits sit inside them (only kGpClaim lies above) -- every value passes
+        if ((rc = ds_flag_compact_launch(ctx, W, has_hi, d_mn + first, d_lo + first, has_hi ? d_hi + first : nullptr, d_cell + first, (uint32_t)all_keys, 0u,
+                                         0x7fffffffu, kGpClaim | kGpMarker, rel.data(), n_bounds, ctx->gp_t_mn.as<uint32_t>(), ctx->gp_t_lo.as<uint64_t>(),
+                                         has_hi ? ctx->gp_t_hi.as<uint64_t>() : nullptr, ctx->h_scalar + kHsGpTotal, run.data()))) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return rc;
+        }
     }
     SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsGpBad, d_words, 16, hipMemcpyDeviceToHost, ctx->stream));
     SPSP_HIP(hipMemcpyAsync(rec.data(), d_rec, rec.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -334,10 +299,10 @@ int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const ui
     *out_mn = o_mn; *out_lo = o_lo; *out_hi = o_hi;
     SPSP_HIP(hipMemcpyAsync(d_dest, dest.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (has_hi) hipLaunchKernelGGL(k_gp_regroup<true>, dim3(n), dim3(kGpThreads), 0, ctx->stream, (const uint32_t*)ctx->gp_t_mn.as<uint32_t>(),
-                                   (const uint64_t*)ctx->gp_t_lo.as<uint64_t>(), (const uint64_t*)ctx->gp_t_hi.as<uint64_t>(), (const uint64_t*)d_off_out,
+                                   (const uint64_t*)ctx->gp_t_lo.as<uint64_t>(), (const uint64_t*)ctx->gp_t_hi.as<uint64_t>(), (const uint64_t*)W.off_out,
                                    (const uint32_t*)d_dest, (uint32_t)total, o_mn, o_lo, o_hi);
     else hipLaunchKernelGGL(k_gp_regroup<false>, dim3(n), dim3(kGpThreads), 0, ctx->stream, (const uint32_t*)ctx->gp_t_mn.as<uint32_t>(),
-                            (const uint64_t*)ctx->gp_t_lo.as<uint64_t>(), (const uint64_t*)nullptr, (const uint64_t*)d_off_out, (const uint32_t*)d_dest,
+                            (const uint64_t*)ctx->gp_t_lo.as<uint64_t>(), (const uint64_t*)nullptr, (const uint64_t*)W.off_out, (const uint32_t*)d_dest,
                             (uint32_t)total, o_mn, o_lo, (uint64_t*)nullptr);
     SPSP_HIP(hipGetLastError());
     std::vector<std::pair<uint32_t, uint32_t>> segs;
@@ -370,63 +335,41 @@ static int groups_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, con
     { const char* p = names_own.c_str(); for (uint32_t c = 0; c < G; ++c) { gname[c] = p; p += strlen(p) + 1; } }
     if ((rc = spsp_groups_bounds_host(group.data(), n, G, num, den, onum, oden, nullptr, nullptr, nullptr))) return rc;
 
-    LoadedSketches L;
-    rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (!rc && L.k && L.k == L.m) { set_error("groups are not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }
-    double out_rate = L.ds_rate;
-    if (!rc && write_markers) rc = sketches_out_rate(L, paths, n, &out_rate);
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
-    std::vector<uint64_t> card(n, 0), moff((size_t)G + 1, 0);
+    FilesRun run(ctx, paths, n, chatter);
+    rc = run.load(rate);
+    if (!rc) rc = run.refuse_k_eq_m(rc, "groups are");
+    double out_rate = run.L.ds_rate;
+    if (!rc && write_markers) rc = sketches_out_rate(run.L, paths, n, &out_rate);
+    if ((rc = run.begin(rc))) return rc;
+    std::vector<uint64_t> moff((size_t)G + 1, 0);
     rows->assign(G, spsp_group_row{});
     members->assign(n, spsp_group_member_row{});
-    DecodedKeys keys;
+    const DecodedKeys& keys = run.keys;
     uint32_t* d_mn = nullptr; uint64_t *d_lo = nullptr, *d_hi = nullptr;
-    rc = decode_keys_impl(ctx, L.data.data(), L.len.data(), n, nullptr, nullptr, L.threshold(), &keys, card.data());
+    rc = run.decode();
     if (!rc) rc = groups_device_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n, group.data(), G, num, den, onum, oden, rows->data(),
                                      members->data(), write_markers, &d_mn, &d_lo, &d_hi, moff.data());
-    const uint32_t k = keys.k, m = keys.m;
-    const uint64_t total = write_markers ? moff[G] : 0;
-    std::vector<uint32_t> mn(total);
-    std::vector<uint64_t> lo(total), hi(k > 32 ? total : 0);
-    if (!rc && total) {
-        SPSP_HIP(hipMemcpyAsync(mn.data(), d_mn, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SPSP_HIP(hipMemcpyAsync(lo.data(), d_lo, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (k > 32) SPSP_HIP(hipMemcpyAsync(hi.data(), d_hi, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    L.release();
-    const double t1 = now_s();
-    ctx->stages.compare_s += t1 - t0;
+    HostKeys got;
+    if (!rc) rc = fetch_keys(ctx, keys.k, d_mn, d_lo, d_hi, write_markers ? moff[G] : 0, &got);
+    const double t1 = run.end();
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
     if ((rc = spsp_groups_csv_host(rows->data(), G, gname.data(), precision, &text, &len))) return rc;
     if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_groups.csv.gz", t1))) return rc;
     const double t2 = now_s();
-    if ((rc = spsp_groups_members_csv_host(members->data(), n, paths, group.data(), card.data(), rows->data(), G, gname.data(), precision, &text, &len))) return rc;
+    if ((rc = spsp_groups_members_csv_host(members->data(), n, paths, group.data(), run.card.data(), rows->data(), G, gname.data(), precision, &text, &len))) return rc;
     if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_members.csv.gz", t2))) return rc;
     if (write_markers) {
-        std::string list;
-        for (uint32_t c = 0; c < G; ++c) {
-            const std::string path = std::string(out_prefix) + "_markers_" + std::to_string(c) + ".gz";
-            list += path + "\n";
-            uint8_t* payload = nullptr; uint64_t plen = 0;
-            const uint64_t a = moff[c], cnt = moff[c + 1] - moff[c];
-            if ((rc = spsp_sketch_from_keys_host(k, m, out_rate, mn.data() + a, lo.data() + a, k > 32 ? hi.data() + a : nullptr, cnt, &payload, &plen))) return rc;
-            rc = spsp_write_gz_host(path.c_str(), payload, plen, 9);
-            free(payload);
-            if (rc) return rc;
-        }
-        const std::string path = std::string(out_prefix) + "_markers.txt";
-        FILE* f = fopen(path.c_str(), "wb");
-        if (!f || fwrite(list.data(), 1, list.size(), f) != list.size() || fclose(f) != 0) { set_error("cannot write '%s'", path.c_str()); return SPSP_ERR_IO; }
+        const std::string list_path = std::string(out_prefix) + "_markers.txt";
+        const auto name_of = [&](uint32_t c) { return std::string(out_prefix) + "_markers_" + std::to_string(c) + ".gz"; };
+        if ((rc = write_key_sketches(keys.k, keys.m, out_rate, got, moff.data(), G, name_of, list_path.c_str()))) return rc;
     }
     if (chatter) {
         uint64_t core = 0, excl = 0, mark = 0;
         for (const spsp_group_row& r : *rows) { core += r.core; excl += r.exclusive; mark += r.marker; }
         printf("%u sketch(es) in %u group(s): %llu core, %llu exclusive and %llu marker key(s) over the groups\n", n, G, (unsigned long long)core,
                (unsigned long long)excl, (unsigned long long)mark);
-        say_common_rate(L, n);
+        say_common_rate(run.L, n);
         fflush(stdout);
     }
     return SPSP_OK;
@@ -470,15 +413,7 @@ extern "C" int spsp_groups_files(spsp_ctx* ctx, const char* const* paths, uint32
     std::vector<spsp_group_member_row> mem;
     if ((rc = groups_files(ctx, paths, n, labels_path, precision, num, den, onum, oden, write_markers != 0, out_prefix, chatter, rate, &got, &mem))) return rc;
     if (n_groups) *n_groups = (uint32_t)got.size();
-    if (rows) {
-        *rows = (spsp_group_row*)malloc(got.size() * sizeof(spsp_group_row));
-        if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        memcpy(*rows, got.data(), got.size() * sizeof(spsp_group_row));
-    }
-    if (members) {
-        *members = (spsp_group_member_row*)malloc(mem.size() * sizeof(spsp_group_member_row));
-        if (!*members) { set_error("out of host memory"); if (rows) { free(*rows); *rows = nullptr; } return SPSP_ERR_NOMEM; }
-        memcpy(*members, mem.data(), mem.size() * sizeof(spsp_group_member_row));
-    }
+    if (rows && (rc = give_rows(got, rows))) return rc;
+    if (members && (rc = give_rows(mem, members))) { if (rows) { free(*rows); *rows = nullptr; } return rc; }
     return SPSP_OK;
 }

@@ -1829,6 +1829,26 @@ int write_csv_gz(spsp_ctx* ctx, char* text, uint64_t len, const char* out_prefix
 void say_common_rate(const LoadedSketches& L, uint32_t n) {
     if (n && L.rate_asked) { printf("Sketches compared at sampling rate %g: %u of %u brought down to it\n", L.ds_rate, L.ds_brought, n); fflush(stdout); }
 }
+
+int write_key_sketches(uint32_t k, uint32_t m, double rate, const HostKeys& keys, const uint64_t* off, uint32_t n_out,
+                       const std::function<std::string(uint32_t)>& name_of, const char* list_path) {
+    std::string list;
+    for (uint32_t i = 0; i < n_out; ++i) {
+        const std::string path = name_of(i);
+        list += path + "\n";
+        uint8_t* payload = nullptr; uint64_t len = 0;
+        const uint64_t a = off[i], c = off[i + 1] - off[i];
+        int rc = spsp_sketch_from_keys_host(k, m, rate, keys.mn.data() + a, keys.lo.data() + a, k > 32 ? keys.hi.data() + a : nullptr, c, &payload, &len);
+        if (rc) return rc;
+        rc = spsp_write_gz_host(path.c_str(), payload, len, 9);
+        free(payload);
+        if (rc) return rc;
+    }
+    if (!list_path) return SPSP_OK;
+    FILE* f = fopen(list_path, "wb");
+    if (!f || fwrite(list.data(), 1, list.size(), f) != list.size() || fclose(f) != 0) { set_error("cannot write '%s'", list_path); return SPSP_ERR_IO; }
+    return SPSP_OK;
+}
 }  // namespace spsp
 
 namespace {

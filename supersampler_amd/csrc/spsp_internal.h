@@ -6,6 +6,8 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <utility>
@@ -340,7 +342,7 @@ int sketch_parse_structure_host(const uint8_t* payload, uint64_t len, ParsedSket
 // spsp_downsample.hip: the keys whose minimizer's hash is <= threshold, sketches back to back, order kept, in context-owned arrays
 int keys_downsample_impl(spsp_ctx* ctx, uint32_t k, uint64_t threshold, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
                          const uint64_t* h_sk_off, uint32_t n, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi, uint64_t* sk_off_out);
-// the tile compaction behind a keep mask, shared by the downsampling pass and the selection (spsp_downsample.hip).  The mask is
+// the tile compaction behind a keep mask, shared by the downsampling pass, the selection and the groups pass (spsp_downsample.hip).  The mask is
 // k_ds_flag's layout: tiles of kDsTile keys, one 64-bit ballot word per 64 keys -- round r of wave w of tile t fills word
 // kDsWords t + 4 r + w, bit l of word j is key 64 j + l -- and d_tile_cnt[t] = the tile's survivors.  Queued on the context's stream:
 // launch_scan_u32 over the tile counts (d_tile_off: n_tiles + 1 words, the last the total, also stored to *total_host), k_ds_move
@@ -352,6 +354,26 @@ constexpr uint32_t kDsWords = kDsTile / 64;                // ballot words per t
 int ds_compact_launch(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const unsigned long long* d_mask,
                       const uint32_t* d_tile_cnt, uint32_t* d_tile_off, uint32_t n_tiles, const uint64_t* d_off_in, uint32_t n_bounds, uint64_t* d_off_out,
                       uint32_t* out_mn, uint64_t* out_lo, uint64_t* out_hi, uint64_t* total_host);
+// the compaction's part of a work area, written once: keep mask | offsets in | offsets out | tile counts | tile offsets (+ the total).
+// base: 8-byte aligned, bytes() of room behind it
+struct DsWork {
+    unsigned long long* mask;
+    uint64_t *off_in, *off_out;
+    uint32_t *tile_cnt, *tile_off;
+    static size_t bytes(uint32_t n_tiles, uint32_t n_bounds) { return (size_t)n_tiles * kDsWords * 8 + (size_t)2 * n_bounds * 8 + ((size_t)2 * n_tiles + 2) * 4 + 64; }
+    DsWork(void* base, uint32_t n_tiles, uint32_t n_bounds)
+        : mask(reinterpret_cast<unsigned long long*>(base)), off_in(reinterpret_cast<uint64_t*>(mask + (size_t)n_tiles * kDsWords)), off_out(off_in + n_bounds),
+          tile_cnt(reinterpret_cast<uint32_t*>(off_out + n_bounds)), tile_off(tile_cnt + n_tiles) {}
+};
+// flag, then compact: what the selection and the groups pass do with one 32-bit word per entry (spsp_downsample.hip).  Entry i of
+// [0, n_keys) is kept iff (d_value[i] & need) == need and h_min <= (d_value[i] & 0x7fffffff) <= h_max (k_ds_flag_band); the kept keys
+// of (d_mn, d_lo, d_hi) -- the caller's arrays already moved to the first entry -- go to (out_mn, out_lo, out_hi) through
+// ds_compact_launch, W the carved area of (n_keys + kDsTile - 1) / kDsTile tiles and n_bounds offsets.  h_rel: the n_bounds offsets
+// relative to the first entry; h_off_out receives the survivors in front of each.  Both are the CALLER's host arrays, read and
+// written by queued copies: they live until the caller's wait.  Queued on the context's stream: no host wait
+int ds_flag_compact_launch(spsp_ctx* ctx, const DsWork& W, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint32_t* d_value,
+                           uint32_t n_keys, uint32_t h_min, uint32_t h_max, uint32_t need, const uint64_t* h_rel, uint32_t n_bounds, uint32_t* out_mn,
+                           uint64_t* out_lo, uint64_t* out_hi, uint64_t* total_host, uint64_t* h_off_out);
 // the sorted distinct keys of n sketch payloads on the device, sketches back to back: the decoder's arrays, or the downsampling
 // pass's (spsp_decode.hip).  ds_threshold: null = the keys as the files hold them; else only the keys whose minimizer passes that
 // selection threshold, brought down on the device behind the decoder.  card[i] = the keys of sketch i that are left
@@ -404,6 +426,15 @@ int neighbours_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cel
 // spsp_prevalence.hip: per row sketch the keys by class of holder count and the sum of the counts, the spectrum of the references'
 // union, h of every key occurrence (context-owned, on the device) -- over concatenated sorted key arrays, n_query == 0: all versus all
 int prevalence_check_args(uint32_t n, uint32_t n_query, uint32_t num, uint32_t den);
+// the argument front of a pass over concatenated sorted key arrays (prevalence, select, accumulation, groups), in this order: the
+// context not switched to unordered keys ("<who_reads> sorted sketches: ..."), k in 1..63, offsets that do not decrease, an extent
+// of 0xfffffff0 at the most (SPSP_ERR_OVERFLOW), no NULL key array where there are keys.  Touches nothing on the device
+struct KeysShape { bool has_hi; uint64_t first, extent, all_keys; };
+int sorted_keys_front(spsp_ctx* ctx, const char* who_reads, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
+                      const uint64_t* h_sk_off, uint32_t n, KeysShape* shape);
+// slots of a key table for `entries` entries, as a power of two: half as many again as the entries (every one may be a key of its
+// own); SPSP_DEBUG_PREVALENCE_TABLE=min: the smallest that holds them, so that probe sequences wrap and chains are long
+uint32_t pv_table_log2cap(uint64_t entries);
 // the table fill the prevalence pass and the selection share: the sketch offsets uploaded (ctx->pv_off), the table cleared
 // (ctx->pv_table), k_pv_count over the reference entries, k_pv_read over every entry -> ctx->pv_hold[e] = h of entry e.  claim: bit 31
 // of pv_hold[e] is set as well iff entry e is the one that claimed its key's slot (exactly one occurrence of every distinct reference
@@ -467,6 +498,54 @@ void say_common_rate(const LoadedSketches& L, uint32_t n);
 // spsp_select.hip: the rate a driver writes into the headers of the sketches it makes -- the common one where one was asked for, else
 // the headers' own if they all stand for one selection threshold, else SPSP_ERR_ARG ("give a rate")
 int sketches_out_rate(const LoadedSketches& L, const char* const* paths, uint32_t n, double* out_rate);
+// selected keys on their way into sketch files.  fetch_keys (spsp_select.hip): `total` keys of device arrays copied to the host,
+// with its own wait.  write_key_sketches (spsp_host.cpp): segment i = keys [off[i], off[i + 1]) -> a sketch file name_of(i)
+// (spsp_sketch_from_keys_host, gzip level 9 as the sketcher writes); list_path: null, or where the names go, one per line
+struct HostKeys { std::vector<uint32_t> mn; std::vector<uint64_t> lo, hi; };
+int fetch_keys(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, uint64_t total, HostKeys* keys);
+int write_key_sketches(uint32_t k, uint32_t m, double rate, const HostKeys& keys, const uint64_t* off, uint32_t n_out,
+                       const std::function<std::string(uint32_t)>& name_of, const char* list_path);
+// the opening and closing of a file driver behind a collection pass: load, the k == m refusal, the booking of a failed load or
+// files_loaded, the decoding, and release + the booking of compare_s.  A driver calls the steps in ITS order (select and groups
+// refuse k == m only behind a good load; select books and releases by itself, around its writing)
+struct FilesRun {
+    spsp_ctx* ctx;
+    const char* const* paths;
+    uint32_t n;
+    int chatter;
+    LoadedSketches L;
+    std::vector<uint64_t> card;                                    // the key counts the pass saw
+    DecodedKeys keys;
+    double t0 = 0;                                                 // when the device half began
+    FilesRun(spsp_ctx* c, const char* const* p, uint32_t n_, int chat) : ctx(c), paths(p), n(n_), chatter(chat), card(n_, 0) {}
+    int load(double rate) { return load_sketch_files(ctx, paths, n, rate, &L); }
+    // what_is: "clustering is", "neighbours are", ...; rc: the load's, returned where there is nothing to refuse
+    int refuse_k_eq_m(int rc, const char* what_is) {
+        if (!L.k || L.k != L.m) return rc;
+        set_error("%s not defined for k == m sketches (k = m = %u)", what_is, L.k);
+        return SPSP_ERR_ARG;
+    }
+    int begin(int rc) {
+        if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
+        t0 = files_loaded(ctx, L, n, chatter);
+        return SPSP_OK;
+    }
+    int decode() { return decode_keys_impl(ctx, L.data.data(), L.len.data(), n, nullptr, nullptr, L.threshold(), &keys, card.data()); }
+    double end() {
+        L.release();
+        const double t1 = now_s();
+        ctx->stages.compare_s += t1 - t0;
+        return t1;
+    }
+};
+// a driver's rows as the caller's array to spsp_free (one byte for no rows: never NULL on success)
+template <class T> int give_rows(const std::vector<T>& rows, T** out) {
+    const size_t bytes = rows.size() * sizeof(T);
+    *out = (T*)malloc(bytes ? bytes : 1);
+    if (!*out) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    if (bytes) memcpy(*out, rows.data(), bytes);
+    return SPSP_OK;
+}
 int sketch_decode_device_impl(spsp_ctx* ctx, const uint8_t* const* payloads, const uint64_t* lens, uint32_t n,
                               const int* extra_has, const uint32_t* extra_mn, uint32_t* k_out, uint32_t* m_out, uint64_t* sk_off);
 // ingest (spsp_ingest.hip)

@@ -292,16 +292,14 @@ int neighbours_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cel
 // rows) in ctx->m_cells, the neighbours pass over them, <out_prefix>_neighbours.csv.gz
 static int neighbours_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, int metric, uint32_t num, uint32_t den,
                             uint32_t top, const char* out_prefix, int chatter, double rate, std::vector<spsp_neighbour_row>* rows) {
-    LoadedSketches L;
-    int rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (L.k && L.k == L.m) { set_error("neighbours are not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
-    std::vector<uint64_t> card(n, 0);
+    FilesRun run(ctx, paths, n, chatter);
+    int rc = run.begin(run.refuse_k_eq_m(run.load(rate), "neighbours are"));   // (the k == m refusal in front of the rate's own)
+    if (rc) return rc;
+    std::vector<uint64_t>& card = run.card;
     std::vector<uint32_t> passing(n_query, 0);
     uint64_t n_cells = 0, n_rows = 0, n_pairs = 0;
-    DecodedKeys keys;
-    rc = decode_keys_impl(ctx, L.data.data(), L.len.data(), n, nullptr, nullptr, L.threshold(), &keys, card.data());
+    const DecodedKeys& keys = run.keys;
+    rc = run.decode();
     if (!rc && keys.sk_off[n] && n > 1) rc = compare_keys_cells(ctx, keys, n, n_query, &n_cells);
     if (!rc) {
         // room for every row there can be: at most `top` per row sketch, and no more than the cells have ends
@@ -310,15 +308,13 @@ static int neighbours_files(spsp_ctx* ctx, const char* const* paths, uint32_t n,
                                    passing.data(), &n_pairs);
         rows->resize(rc ? 0 : (size_t)n_rows);
     }
-    L.release();
-    const double t1 = now_s();
-    ctx->stages.compare_s += t1 - t0;
+    const double t1 = run.end();
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
     if ((rc = spsp_neighbours_csv_host(rows->data(), n_rows, passing.data(), paths, n, n_query, card.data(), metric, precision, &text, &len))) return rc;
     if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_neighbours.csv.gz", t1)) || !chatter) return rc;
     printf("%u sketches, %llu passing pairs, %llu rows written\n", n, (unsigned long long)n_pairs, (unsigned long long)n_rows);
-    say_common_rate(L, n);
+    say_common_rate(run.L, n);
     fflush(stdout);
     return SPSP_OK;
 }
@@ -347,10 +343,5 @@ extern "C" int spsp_neighbours_files(spsp_ctx* ctx, const char* const* paths, ui
     std::vector<spsp_neighbour_row> got;
     if ((rc = neighbours_files(ctx, paths, n, n_query, precision, metric, num, den, top, out_prefix, chatter, rate, &got))) return rc;
     if (n_rows) *n_rows = got.size();
-    if (rows) {
-        *rows = (spsp_neighbour_row*)malloc(got.size() ? got.size() * sizeof(spsp_neighbour_row) : 1);
-        if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        if (!got.empty()) memcpy(*rows, got.data(), got.size() * sizeof(spsp_neighbour_row));
-    }
-    return SPSP_OK;
+    return rows ? give_rows(got, rows) : SPSP_OK;
 }

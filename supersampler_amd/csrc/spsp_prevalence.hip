@@ -168,19 +168,36 @@ int prevalence_check_args(uint32_t n, uint32_t n_query, uint32_t num, uint32_t d
     return SPSP_OK;
 }
 
+// (spsp_internal.h) the five checks every pass over sorted keys starts with, and what they establish about the arrays
+int sorted_keys_front(spsp_ctx* ctx, const char* who_reads, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi,
+                      const uint64_t* h_sk_off, uint32_t n, KeysShape* shape) {
+    if (ctx->keys_unordered) { set_error("%s sorted sketches: not on a context switched to unordered keys", who_reads); return SPSP_ERR_ARG; }
+    if (k < 1 || k > 63) { set_error("k=%u out of range 1..63", k); return SPSP_ERR_ARG; }
+    for (uint32_t i = 0; i < n; ++i)
+        if (h_sk_off[i + 1] < h_sk_off[i]) { set_error("sketch offsets must not decrease (sketch %u)", i); return SPSP_ERR_ARG; }
+    const KeysShape s{k > 32, h_sk_off[0], h_sk_off[n], h_sk_off[n] - h_sk_off[0]};
+    if (s.extent > 0xfffffff0ull) { set_error("too many sketch k-mers for one call"); return SPSP_ERR_OVERFLOW; }
+    if (s.all_keys && (!d_mn || !d_lo || (s.has_hi && !d_hi))) { set_error("NULL key array"); return SPSP_ERR_ARG; }
+    *shape = s;
+    return SPSP_OK;
+}
+
+// (spsp_internal.h) the slots of a key table, as a power of two
+uint32_t pv_table_log2cap(uint64_t entries) {
+    const char* dbg_table = getenv("SPSP_DEBUG_PREVALENCE_TABLE");   // (read per call: a test switches it inside one process)
+    const bool smallest = dbg_table && !strcmp(dbg_table, "min");
+    const uint64_t want = std::max<uint64_t>(2, smallest ? entries : entries + entries / 2);
+    uint32_t log2cap = 1;
+    while (log2cap < kPvLog2CapMax && (1ull << log2cap) < want) ++log2cap;
+    return log2cap;
+}
+
 // (spsp_internal.h) offsets, memset, k_pv_count, k_pv_read: what the prevalence pass and the selection both start with
 int prevalence_fill_table(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
                           uint32_t n, uint32_t nq, bool claim, uint32_t* d_words) {
     int rc;
     const uint64_t extent = h_sk_off[n], all_keys = h_sk_off[n] - h_sk_off[0], ref_keys = h_sk_off[n] - h_sk_off[nq];
-    // the table: a power of two of slots, half as many again as there are reference entries (every one of them may be a key of
-    // its own); SPSP_DEBUG_PREVALENCE_TABLE=min: the smallest that holds them, so that probe sequences wrap and chains are long
-    const char* dbg_table = getenv("SPSP_DEBUG_PREVALENCE_TABLE");   // (read per call: a test switches it inside one process)
-    const bool smallest = dbg_table && !strcmp(dbg_table, "min");
-    const uint64_t want = std::max<uint64_t>(2, smallest ? ref_keys : ref_keys + ref_keys / 2);
-    uint32_t log2cap = 1;
-    while (log2cap < kPvLog2CapMax && (1ull << log2cap) < want) ++log2cap;
-    ctx->pv_log2cap = log2cap;
+    const uint32_t log2cap = ctx->pv_log2cap = pv_table_log2cap(ref_keys);   // (the table's size follows from the reference entries alone)
     const uint64_t cap = 1ull << log2cap;
     if ((rc = ctx->pv_off.reserve(((size_t)n + 1) * 8)) || (rc = ctx->pv_table.reserve((size_t)cap * 8)) ||
         (rc = ctx->pv_hold.reserve(std::max<size_t>(extent, 1) * 4))) return rc;
@@ -211,15 +228,11 @@ int prevalence_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, cons
     int rc;
     if (d_holders) *d_holders = nullptr;
     if ((rc = prevalence_check_args(n, nq, num, den))) return rc;
-    if (ctx->keys_unordered) { set_error("prevalence reads sorted sketches: not on a context switched to unordered keys"); return SPSP_ERR_ARG; }
-    if (k < 1 || k > 63) { set_error("k=%u out of range 1..63", k); return SPSP_ERR_ARG; }
-    for (uint32_t i = 0; i < n; ++i)
-        if (h_sk_off[i + 1] < h_sk_off[i]) { set_error("sketch offsets must not decrease (sketch %u)", i); return SPSP_ERR_ARG; }
-    const bool has_hi = k > 32;
+    KeysShape shape;
+    if ((rc = sorted_keys_front(ctx, "prevalence reads", k, d_mn, d_lo, d_hi, h_sk_off, n, &shape))) return rc;
+    const bool has_hi = shape.has_hi;
     const uint32_t R = n - nq, n_rows = nq ? nq : n;
-    const uint64_t extent = h_sk_off[n], all_keys = h_sk_off[n] - h_sk_off[0], ref_keys = h_sk_off[n] - h_sk_off[nq];
-    if (extent > 0xfffffff0ull) { set_error("too many sketch k-mers for one call"); return SPSP_ERR_OVERFLOW; }
-    if (all_keys && (!d_mn || !d_lo || (has_hi && !d_hi))) { set_error("NULL key array"); return SPSP_ERR_ARG; }
+    const uint64_t ref_keys = h_sk_off[n] - h_sk_off[nq];
     const uint32_t core_min = (uint32_t)(((uint64_t)num * R + den - 1) / den);       // h * den >= num * R  <=>  h >= ceil(num * R / den)
     const size_t spec_bytes = (size_t)kPvWords * 4 + ((size_t)R + 1) * 8;
     if ((rc = ctx->pv_rows.reserve((size_t)n_rows * sizeof(spsp_prevalence_row))) || (rc = ctx->pv_spec.reserve(spec_bytes))) return rc;
@@ -256,24 +269,19 @@ int prevalence_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, cons
 // rate), the prevalence pass, <out_prefix>_prevalence.csv.gz and <out_prefix>_spectrum.csv.gz
 static int prevalence_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, int precision, uint32_t num, uint32_t den,
                             const char* out_prefix, int chatter, double rate, std::vector<spsp_prevalence_row>* rows, std::vector<uint64_t>* spectrum) {
-    LoadedSketches L;
-    int rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (L.k && L.k == L.m) { set_error("prevalence is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
+    FilesRun run(ctx, paths, n, chatter);
+    int rc = run.begin(run.refuse_k_eq_m(run.load(rate), "prevalence is"));   // (the k == m refusal in front of the rate's own)
+    if (rc) return rc;
     const uint32_t R = n - n_query, n_rows = n_query ? n_query : n;
-    std::vector<uint64_t> card(n, 0);
     rows->assign(n_rows, spsp_prevalence_row{});
     spectrum->assign((size_t)R + 1, 0);
-    DecodedKeys keys;
-    rc = decode_keys_impl(ctx, L.data.data(), L.len.data(), n, nullptr, nullptr, L.threshold(), &keys, card.data());
+    rc = run.decode();
+    const DecodedKeys& keys = run.keys;
     if (!rc) rc = prevalence_device_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n, n_query, num, den, rows->data(), spectrum->data(), nullptr);
-    L.release();
-    const double t1 = now_s();
-    ctx->stages.compare_s += t1 - t0;
+    const double t1 = run.end();
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
-    if ((rc = spsp_prevalence_csv_host(rows->data(), n_rows, paths, card.data(), precision, &text, &len))) return rc;
+    if ((rc = spsp_prevalence_csv_host(rows->data(), n_rows, paths, run.card.data(), precision, &text, &len))) return rc;
     if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_prevalence.csv.gz", t1))) return rc;
     const double t2 = now_s();
     if ((rc = spsp_spectrum_csv_host(spectrum->data(), R, &text, &len))) return rc;
@@ -283,7 +291,7 @@ static int prevalence_files(spsp_ctx* ctx, const char* const* paths, uint32_t n,
     for (uint32_t t = 1; t <= R; ++t) { in_union += (*spectrum)[t]; if (t >= core_min) in_core += (*spectrum)[t]; }
     printf("%u reference(s), %llu distinct keys, %llu of them core (held by %u references or more)\n", R, (unsigned long long)in_union,
            (unsigned long long)in_core, core_min);
-    say_common_rate(L, n);
+    say_common_rate(run.L, n);
     fflush(stdout);
     return SPSP_OK;
 }
@@ -316,15 +324,7 @@ extern "C" int spsp_prevalence_files(spsp_ctx* ctx, const char* const* paths, ui
     std::vector<spsp_prevalence_row> got;
     std::vector<uint64_t> spec;
     if ((rc = prevalence_files(ctx, paths, n, n_query, precision, num, den, out_prefix, chatter, rate, &got, &spec))) return rc;
-    if (rows) {
-        *rows = (spsp_prevalence_row*)malloc(got.size() * sizeof(spsp_prevalence_row));
-        if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        memcpy(*rows, got.data(), got.size() * sizeof(spsp_prevalence_row));
-    }
-    if (spectrum) {
-        *spectrum = (uint64_t*)malloc(spec.size() * 8);
-        if (!*spectrum) { set_error("out of host memory"); if (rows) { free(*rows); *rows = nullptr; } return SPSP_ERR_NOMEM; }
-        memcpy(*spectrum, spec.data(), spec.size() * 8);
-    }
+    if (rows && (rc = give_rows(got, rows))) return rc;
+    if (spectrum && (rc = give_rows(spec, spectrum))) { if (rows) { free(*rows); *rows = nullptr; } return rc; }
     return SPSP_OK;
 }

@@ -323,25 +323,21 @@ int representatives_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t 
 static int representatives_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, int metric, uint32_t num, uint32_t den,
                                  const uint64_t* h_weight, const char* out_prefix, int chatter, double rate, std::vector<spsp_cluster_row>* rows,
                                  uint64_t* n_clusters) {
-    LoadedSketches L;
-    int rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (L.k && L.k == L.m) { set_error("representatives are not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
-    std::vector<uint64_t> card(n, 0);
+    FilesRun run(ctx, paths, n, chatter);
+    int rc = run.begin(run.refuse_k_eq_m(run.load(rate), "representatives are"));   // (the k == m refusal in front of the rate's own)
+    if (rc) return rc;
+    std::vector<uint64_t>& card = run.card;
     uint64_t n_cells = 0, n_edges = 0;
     uint32_t n_rounds = 0;
-    DecodedKeys keys;
-    rc = decode_keys_impl(ctx, L.data.data(), L.len.data(), n, nullptr, nullptr, L.threshold(), &keys, card.data());
+    const DecodedKeys& keys = run.keys;
+    rc = run.decode();
     if (!rc && keys.sk_off[n] && n > 1) rc = compare_keys_cells(ctx, keys, n, n, &n_cells);
     if (!rc) {
         rows->resize(n);
         rc = representatives_cells_impl(ctx, ctx->m_cells.as<uint64_t>(), n_cells, card.data(), h_weight, n, metric, num, den, rows->data(), n_clusters, &n_edges,
                                         &n_rounds);
     }
-    L.release();
-    const double t1 = now_s();
-    ctx->stages.compare_s += t1 - t0;
+    const double t1 = run.end();
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
     if ((rc = spsp_cluster_csv_host(rows->data(), paths, n, card.data(), metric, precision, &text, &len))) return rc;
@@ -350,7 +346,7 @@ static int representatives_files(spsp_ctx* ctx, const char* const* paths, uint32
     for (const spsp_cluster_row& r : *rows) largest = std::max(largest, r.size);
     printf("%u sketches, %llu edges, %llu representatives, the largest cluster of %u, %u rounds\n", n, (unsigned long long)n_edges,
            (unsigned long long)*n_clusters, largest, n_rounds);
-    say_common_rate(L, n);
+    say_common_rate(run.L, n);
     fflush(stdout);
     return SPSP_OK;
 }
@@ -383,10 +379,5 @@ extern "C" int spsp_representatives_files(spsp_ctx* ctx, const char* const* path
     uint64_t count = 0;
     if ((rc = representatives_files(ctx, paths, n, precision, metric, num, den, h_weight, out_prefix, chatter, rate, &got, &count))) return rc;
     if (n_clusters) *n_clusters = count;
-    if (rows) {
-        *rows = (spsp_cluster_row*)malloc(got.size() ? got.size() * sizeof(spsp_cluster_row) : 1);
-        if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        if (!got.empty()) memcpy(*rows, got.data(), got.size() * sizeof(spsp_cluster_row));
-    }
-    return SPSP_OK;
+    return rows ? give_rows(got, rows) : SPSP_OK;
 }

@@ -11,9 +11,9 @@
 // One chain of launches whatever the sketches are:
 //   table fill    prevalence's own (prevalence_fill_table): memset, k_pv_count, k_pv_read -> holders[e] = h of entry e; for the
 //                 merged form k_pv_read also sets bit 31 of the one entry per distinct key that claimed the key's slot
-//   k_sel_flag    one workgroup per tile of 2048 entries: 4 B read per entry, the band test (merged: and the claimer's bit), a wave
-//                 ballot -> k_ds_flag's keep mask and tile counts
-//   compaction    the downsampling pass's (ds_compact_launch): scan, k_ds_move, k_ds_offsets
+//   flag, compact the downsampling unit's (ds_flag_compact_launch): k_ds_flag_band -- one workgroup per tile of 2048 entries: 4 B read
+//                 per entry, the band test (merged: and the claimer's bit), a wave ballot -> k_ds_flag's keep mask and tile counts --
+//                 then scan, k_ds_move, k_ds_offsets
 //   merged only   big_sort_segments over the compacted keys as one segment (entry order is sorted per sketch, not across them)
 // Host waits: one for `each` (the offsets, with the order check); for merged that one (it sizes the sort) and the sort's own.
 // No workgroup ever waits for another one.
@@ -30,34 +30,6 @@ namespace {
 
 constexpr uint32_t kSelWords = 4;                          // flag words in front of the work area: keys out of order | a probe went round | 2 spare
 
-// keep bit of entry i of [0, n_keys): holders[i] in [h_min, h_max]; need = 0x80000000 for the merged form -- only the entry that
-// claimed its key's slot speaks for the key -- else 0.  Round r of wave w of tile t fills word 32 t + 4 r + w (k_ds_flag's layout)
-__global__ __launch_bounds__(kDsThreads) void k_sel_flag(const uint32_t* __restrict__ holders, uint32_t n_keys, uint32_t h_min, uint32_t h_max,
-                                                         uint32_t need, unsigned long long* __restrict__ mask, uint32_t* __restrict__ tile_cnt) {
-    __shared__ uint32_t s_cnt[kDsThreads / 64];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint32_t base = blockIdx.x * kDsTile + threadIdx.x;       // (n_keys <= 0xfffffff0 and the last tile starts below it)
-    uint32_t v[kDsTile / kDsThreads];
-#pragma unroll
-    for (uint32_t r = 0; r < kDsTile / kDsThreads; ++r) {
-        const uint64_t i = (uint64_t)base + r * kDsThreads;
-        v[r] = i < n_keys ? holders[i] : 0u;
-    }
-    uint32_t cnt = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < kDsTile / kDsThreads; ++r) {
-        const uint64_t i = (uint64_t)base + r * kDsThreads;
-        const uint32_t h = v[r] & 0x7fffffffu;
-        const bool keep = i < n_keys && (v[r] & need) == need && h >= h_min && h <= h_max;
-        const unsigned long long word = __ballot(keep);
-        if (lane == 0) mask[(size_t)blockIdx.x * kDsWords + r * (kDsThreads / 64) + w] = word;
-        cnt += (uint32_t)__popcll(word);
-    }
-    if (lane == 0) s_cnt[w] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
 int select_check_args(uint32_t n, uint32_t n_query, bool merged) {
     if (n == 0 || n > 65535) { set_error("select takes 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
     if (n_query >= n) { set_error("select: %u queries of %u sketches (0: every sketch is a row and a reference; else at least one reference behind them)", n_query, n); return SPSP_ERR_ARG; }
@@ -73,15 +45,11 @@ int keys_select_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint
     if ((rc = select_check_args(n, nq, merged))) return rc;
     const uint32_t n_rows = nq ? nq : n, n_out = merged ? 1u : n_rows;
     for (uint32_t i = 0; i <= n_out; ++i) sk_off_out[i] = 0;
-    if (ctx->keys_unordered) { set_error("select reads sorted sketches: not on a context switched to unordered keys"); return SPSP_ERR_ARG; }
-    if (k < 1 || k > 63) { set_error("k=%u out of range 1..63", k); return SPSP_ERR_ARG; }
-    for (uint32_t i = 0; i < n; ++i)
-        if (h_sk_off[i + 1] < h_sk_off[i]) { set_error("sketch offsets must not decrease (sketch %u)", i); return SPSP_ERR_ARG; }
-    const bool has_hi = k > 32;
-    const uint64_t first = h_sk_off[0], extent = h_sk_off[n], all_keys = extent - first;
+    KeysShape shape;
+    if ((rc = sorted_keys_front(ctx, "select reads", k, d_mn, d_lo, d_hi, h_sk_off, n, &shape))) return rc;
+    const bool has_hi = shape.has_hi;
+    const uint64_t first = shape.first, all_keys = shape.all_keys;
     const uint64_t sel_keys = h_sk_off[merged ? n : n_rows] - first;   // the entries that are asked: the rows', or (merged) everybody's
-    if (extent > 0xfffffff0ull) { set_error("too many sketch k-mers for one call"); return SPSP_ERR_OVERFLOW; }
-    if (all_keys && (!d_mn || !d_lo || (has_hi && !d_hi))) { set_error("NULL key array"); return SPSP_ERR_ARG; }
     // two sets of output arrays, used in turn: the result of one call may be the input of the next
     const int set = ctx->sel_flip;
     ctx->sel_flip ^= 1;
@@ -92,28 +60,20 @@ int keys_select_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint
     *out_mn = o_mn; *out_lo = o_lo; *out_hi = o_hi;
     if (all_keys == 0) return SPSP_OK;
     const uint32_t n_tiles = (uint32_t)((sel_keys + kDsTile - 1) / kDsTile), n_bounds = n_out + 1;
-    // work area: flag words | keep mask | offsets in | offsets out | tile counts | tile offsets (+ the total)
-    const size_t words_bytes = 64, mask_bytes = (size_t)n_tiles * kDsWords * 8, off_bytes = (size_t)n_bounds * 8;
-    if ((rc = ctx->sel_work.reserve(words_bytes + mask_bytes + 2 * off_bytes + ((size_t)2 * n_tiles + 2) * 4 + 64))) return rc;
+    // work area: flag words | the compaction's part
+    const size_t words_bytes = 64;
+    if ((rc = ctx->sel_work.reserve(words_bytes + DsWork::bytes(n_tiles, n_bounds)))) return rc;
     uint32_t* d_words = ctx->sel_work.as<uint32_t>();
-    unsigned long long* d_mask = reinterpret_cast<unsigned long long*>(ctx->sel_work.as<uint8_t>() + words_bytes);
-    uint64_t* d_off_in = reinterpret_cast<uint64_t*>(ctx->sel_work.as<uint8_t>() + words_bytes + mask_bytes);
-    uint64_t* d_off_out = d_off_in + n_bounds;
-    uint32_t* d_tile_cnt = reinterpret_cast<uint32_t*>(d_off_out + n_bounds);
-    uint32_t* d_tile_off = d_tile_cnt + n_tiles;
+    const DsWork W(ctx->sel_work.as<uint8_t>() + words_bytes, n_tiles, n_bounds);
     SPSP_HIP(hipMemsetAsync(d_words, 0, kSelWords * 4, ctx->stream));
     if ((rc = prevalence_fill_table(ctx, has_hi, d_mn, d_lo, d_hi, h_sk_off, n, nq, merged, d_words))) return rc;
-    std::vector<uint64_t> rel(n_bounds);                            // (read by the copy below: alive until the wait)
+    std::vector<uint64_t> rel(n_bounds);                            // (ours: the launcher's queued copy reads it, alive until the wait)
     ctx->h_scalar[kHsSelTotal] = 0;
     if (sel_keys) {
         for (uint32_t i = 0; i < n_bounds; ++i) rel[i] = merged ? (i ? sel_keys : 0) : h_sk_off[i] - first;
-        SPSP_HIP(hipMemcpyAsync(d_off_in, rel.data(), off_bytes, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_sel_flag, dim3(n_tiles), dim3(kDsThreads), 0, ctx->stream, (const uint32_t*)(ctx->pv_hold.as<uint32_t>() + first), (uint32_t)sel_keys,
-                           h_min, h_max, merged ? 0x80000000u : 0u, d_mask, d_tile_cnt);
-        SPSP_HIP(hipGetLastError());
-        if ((rc = ds_compact_launch(ctx, has_hi, d_mn + first, d_lo + first, has_hi ? d_hi + first : nullptr, d_mask, d_tile_cnt, d_tile_off, n_tiles, d_off_in,
-                                    n_bounds, d_off_out, o_mn, o_lo, o_hi, ctx->h_scalar + kHsSelTotal))) return rc;
-        SPSP_HIP(hipMemcpyAsync(sk_off_out, d_off_out, off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = ds_flag_compact_launch(ctx, W, has_hi, d_mn + first, d_lo + first, has_hi ? d_hi + first : nullptr, ctx->pv_hold.as<uint32_t>() + first,
+                                         (uint32_t)sel_keys, h_min, h_max, merged ? 0x80000000u : 0u, rel.data(), n_bounds, o_mn, o_lo, o_hi,
+                                         ctx->h_scalar + kHsSelTotal, sk_off_out))) return rc;
     }
     SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsSelBad, d_words, 8, hipMemcpyDeviceToHost, ctx->stream));
     SPSP_HIP(hipStreamSynchronize(ctx->stream));                    // the wait: the offsets, the order check, (merged) the count
@@ -133,6 +93,17 @@ int keys_select_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint
         if ((rc = big_sort_segments(ctx, has_hi, o_mn, o_lo, o_hi, ctx->sel_t_mn.as<uint32_t>(), ctx->sel_t_lo.as<uint64_t>(),
                                     has_hi ? ctx->sel_t_hi.as<uint64_t>() : nullptr, segs))) { sk_off_out[1] = 0; return rc; }
     }
+    return SPSP_OK;
+}
+
+// (spsp_internal.h) the selected keys on the host: three copies and their wait
+int fetch_keys(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, uint64_t total, HostKeys* keys) {
+    keys->mn.resize(total); keys->lo.resize(total); keys->hi.resize(k > 32 ? total : 0);
+    if (!total) return SPSP_OK;
+    SPSP_HIP(hipMemcpyAsync(keys->mn.data(), d_mn, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(keys->lo.data(), d_lo, total * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (k > 32) SPSP_HIP(hipMemcpyAsync(keys->hi.data(), d_hi, total * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));
     return SPSP_OK;
 }
 
@@ -157,61 +128,40 @@ int sketches_out_rate(const LoadedSketches& L, const char* const* paths, uint32_
 // as the sketcher writes) and, for `each`, the list of them
 static int select_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, uint32_t n_query, uint32_t h_min, uint32_t h_max, bool each,
                         const char* out_prefix, int chatter, double rate, uint64_t* keys_in, uint64_t* keys_out) {
-    LoadedSketches L;
-    int rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (!rc && L.k && L.k == L.m) { set_error("select is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }
-    double out_rate = L.ds_rate;
-    if (!rc) rc = sketches_out_rate(L, paths, n, &out_rate);
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
+    FilesRun run(ctx, paths, n, chatter);
+    int rc = run.load(rate);
+    if (!rc) rc = run.refuse_k_eq_m(rc, "select is");
+    double out_rate = run.L.ds_rate;
+    if (!rc) rc = sketches_out_rate(run.L, paths, n, &out_rate);
+    if ((rc = run.begin(rc))) return rc;
     const uint32_t R = n - n_query, n_out = each ? (n_query ? n_query : n) : 1u;
-    std::vector<uint64_t> card(n, 0), off(n_out + 1, 0);
-    DecodedKeys keys;
+    std::vector<uint64_t> off(n_out + 1, 0);
+    const DecodedKeys& keys = run.keys;
     uint32_t* d_mn = nullptr; uint64_t *d_lo = nullptr, *d_hi = nullptr;
-    rc = decode_keys_impl(ctx, L.data.data(), L.len.data(), n, nullptr, nullptr, L.threshold(), &keys, card.data());
+    rc = run.decode();
     if (!rc) rc = keys_select_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n, n_query, h_min, h_max, !each, &d_mn, &d_lo, &d_hi, off.data());
-    const uint32_t k = keys.k, m = keys.m;
     const uint64_t total = off[n_out];
-    std::vector<uint32_t> mn(total);
-    std::vector<uint64_t> lo(total), hi(k > 32 ? total : 0);
-    if (!rc && total) {
-        SPSP_HIP(hipMemcpyAsync(mn.data(), d_mn, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SPSP_HIP(hipMemcpyAsync(lo.data(), d_lo, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (k > 32) SPSP_HIP(hipMemcpyAsync(hi.data(), d_hi, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPSP_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->stages.compare_s += now_s() - t0;
+    HostKeys got;
+    if (!rc) rc = fetch_keys(ctx, keys.k, d_mn, d_lo, d_hi, total, &got);
+    ctx->stages.compare_s += now_s() - run.t0;                      // (booked in front of the writing; the payloads are released behind it)
     if (rc) return rc;
     uint64_t in = 0;
-    for (uint32_t i = each ? 0 : n_query; i < (each ? n_out : n); ++i) in += card[i];
-    std::string list;
-    for (uint32_t i = 0; i < n_out; ++i) {
-        std::string path = out_prefix;
-        if (each) {
-            const char* slash = strrchr(paths[i], '/');
-            path += "_" + std::to_string(i) + "_" + (slash ? slash + 1 : paths[i]);
-            list += path + "\n";
-        } else path += "_select.gz";
-        uint8_t* payload = nullptr; uint64_t len = 0;
-        const uint64_t a = off[i], c = off[i + 1] - off[i];
-        if ((rc = spsp_sketch_from_keys_host(k, m, out_rate, mn.data() + a, lo.data() + a, k > 32 ? hi.data() + a : nullptr, c, &payload, &len))) return rc;
-        rc = spsp_write_gz_host(path.c_str(), payload, len, 9);
-        free(payload);
-        if (rc) return rc;
-    }
-    L.release();
-    if (each) {
-        const std::string path = std::string(out_prefix) + "_select.txt";
-        FILE* f = fopen(path.c_str(), "wb");
-        if (!f || fwrite(list.data(), 1, list.size(), f) != list.size() || fclose(f) != 0) { set_error("cannot write '%s'", path.c_str()); return SPSP_ERR_IO; }
-    }
+    for (uint32_t i = each ? 0 : n_query; i < (each ? n_out : n); ++i) in += run.card[i];
+    const std::string list_path = std::string(out_prefix) + "_select.txt";
+    const auto name_of = [&](uint32_t i) {
+        if (!each) return std::string(out_prefix) + "_select.gz";
+        const char* slash = strrchr(paths[i], '/');
+        return std::string(out_prefix) + "_" + std::to_string(i) + "_" + (slash ? slash + 1 : paths[i]);
+    };
+    if ((rc = write_key_sketches(keys.k, keys.m, out_rate, got, off.data(), n_out, name_of, each ? list_path.c_str() : nullptr))) return rc;
+    run.L.release();
     if (keys_in) *keys_in = in;
     if (keys_out) *keys_out = total;
     if (chatter) {
         if (h_min <= h_max) printf("%u reference(s), holder counts %u .. %u: %llu key(s) in, %llu written to %u sketch(es)\n", R, h_min, h_max,
                                    (unsigned long long)in, (unsigned long long)total, n_out);
         else printf("%u reference(s), an empty band of holder counts: %llu key(s) in, 0 written to %u sketch(es)\n", R, (unsigned long long)in, n_out);
-        say_common_rate(L, n);
+        say_common_rate(run.L, n);
         fflush(stdout);
     }
     return SPSP_OK;

@@ -372,25 +372,21 @@ int tree_cells_impl(spsp_ctx* ctx, const uint64_t* d_cells, uint64_t n_cells, co
 // pass over them, <out_prefix>_tree.csv.gz and <out_prefix>_tree.nwk
 static int tree_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int precision, int metric, uint32_t num, uint32_t den, const char* out_prefix,
                       int chatter, double rate, std::vector<spsp_tree_row>* rows, uint64_t* n_rows) {
-    LoadedSketches L;
-    int rc = load_sketch_files(ctx, paths, n, rate, &L);
-    if (L.k && L.k == L.m) { set_error("the linkage tree is not defined for k == m sketches (k = m = %u)", L.k); rc = SPSP_ERR_ARG; }   // (in front of the rate's own refusal)
-    if (rc) { ctx->stages.compare_s += now_s() - L.t0; return rc; }
-    const double t0 = files_loaded(ctx, L, n, chatter);
-    std::vector<uint64_t> card(n, 0);
+    FilesRun run(ctx, paths, n, chatter);
+    int rc = run.begin(run.refuse_k_eq_m(run.load(rate), "the linkage tree is"));   // (the k == m refusal in front of the rate's own)
+    if (rc) return rc;
+    std::vector<uint64_t>& card = run.card;
     uint64_t n_cells = 0, n_edges = 0;
     uint32_t n_rounds = 0;
-    DecodedKeys keys;
-    rc = decode_keys_impl(ctx, L.data.data(), L.len.data(), n, nullptr, nullptr, L.threshold(), &keys, card.data());
+    const DecodedKeys& keys = run.keys;
+    rc = run.decode();
     if (!rc && keys.sk_off[n] && n > 1) rc = compare_keys_cells(ctx, keys, n, n, &n_cells);
     if (!rc) {
         rows->resize(n - 1);
         rc = tree_cells_impl(ctx, ctx->m_cells.as<uint64_t>(), n_cells, card.data(), n, metric, num, den, rows->data(), n_rows, &n_edges, &n_rounds);
         if (!rc) rows->resize(*n_rows);
     }
-    L.release();
-    const double t1 = now_s();
-    ctx->stages.compare_s += t1 - t0;
+    const double t1 = run.end();
     if (rc) return rc;
     char *csv = nullptr, *nwk = nullptr; uint64_t csv_len = 0, nwk_len = 0;
     if ((rc = spsp_tree_csv_host(rows->data(), *n_rows, paths, n, card.data(), metric, precision, &csv, &csv_len))) return rc;
@@ -404,7 +400,7 @@ static int tree_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, int p
     if ((rc = write_csv_gz(ctx, csv, csv_len, out_prefix, "_tree.csv.gz", t1)) || !chatter) return rc;
     printf("%u sketches, %llu candidate edges, %llu forest rows, %llu components left, %u rounds\n", n, (unsigned long long)n_edges,
            (unsigned long long)*n_rows, (unsigned long long)(n - *n_rows), n_rounds);
-    say_common_rate(L, n);
+    say_common_rate(run.L, n);
     fflush(stdout);
     return SPSP_OK;
 }
@@ -438,10 +434,5 @@ extern "C" int spsp_tree_files(spsp_ctx* ctx, const char* const* paths, uint32_t
     uint64_t count = 0;
     if ((rc = tree_files(ctx, paths, n, precision, metric, num, den, out_prefix, chatter, rate, &got, &count))) return rc;
     if (n_rows) *n_rows = count;
-    if (rows) {
-        *rows = (spsp_tree_row*)malloc(got.size() ? got.size() * sizeof(spsp_tree_row) : 1);
-        if (!*rows) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
-        if (!got.empty()) memcpy(*rows, got.data(), got.size() * sizeof(spsp_tree_row));
-    }
-    return SPSP_OK;
+    return rows ? give_rows(got, rows) : SPSP_OK;
 }
