@@ -1085,6 +1085,85 @@ int spsp_groups_files(spsp_ctx* ctx, const char* const* paths, uint32_t n, const
                       spsp_group_row** rows /* may be NULL; spsp_free */, spsp_group_member_row** members /* may be NULL; spsp_free */,
                       uint32_t* n_groups /* may be NULL */);
 
+/* ------------------------------------------------------------ classify ---- */
+/* The records of a sequence file assigned to the references of an index (not in the reference): which reference each contig or
+ * long read belongs to, record by record.
+ * INDEX: references 0 .. R-1, 1 <= R <= 65535, with sorted distinct key sets K_j: the concatenated arrays every collection pass
+ * takes, refused exactly as there.  (The file driver refuses k == m collections.)
+ * RECORD r has a set Q_r of distinct keys.  In the file driver Q_r is what spsp_sketch_keys_device returns for the genome made of
+ * that one record with abundance = 1, scanned at spsp_threshold_host(k, m, rate): what decoding the sketch that sub_sampler writes
+ * for a FASTA of that record alone would give, uint8 count rule included.  A record shorter than k, or without a selected
+ * minimizer, has no keys.
+ *   shared(r, j) = |Q_r n K_j|          hit_keys(r) = #{x in Q_r : some K_j holds x}
+ * Reference j PASSES for r when shared >= min_keys (min_keys >= 1) and shared * den >= num * |Q_r| (64-bit products; equality
+ * passes; 0 <= num <= den <= 1 000 000, 1 <= den).  passing(r) = the passing references.  The LISTED matches of r are its best
+ * min(top, passing) passing references, 1 <= top <= 64, by shared descending, the lower reference number first among equals: the
+ * order is total, so the answer is a function of the key sets alone.  No floating point decides anything. */
+typedef struct spsp_classify_record {    /* 24 bytes, one per record */
+    uint64_t length;      /* bases of the record: the caller's (the file driver fills it); the device call leaves it alone */
+    uint32_t keys;        /* |Q_r| */
+    uint32_t hit_keys, passing, listed;
+} spsp_classify_record;
+typedef struct spsp_classify_hit {       /* 8 bytes: match i of record r at hits[r * top + i], i < listed; the slots behind are zero */
+    uint32_t reference, shared;
+} spsp_classify_hit;
+/* Builds the index of the references over concatenated sorted key arrays on the device (as spsp_prevalence_device takes them) and
+ * keeps it in the context: the prevalence pass's table, filled with claimers, and the accumulation's key-major lists (per distinct
+ * key the 16-bit numbers of its holders).  The caller's arrays must stay unchanged while the index is in use: the table compares
+ * by full key through them.  The next prevalence, select, accumulation, groups or index call on the context replaces the index.
+ * One host wait.  SPSP_ERR_ARG: n_ref outside 1 .. 65535, k outside 1..63, decreasing offsets, a context switched to unordered
+ * keys, keys out of order or twice inside a reference; SPSP_ERR_OVERFLOW: an extent above 0xfffffff0. */
+int spsp_classify_index_device(spsp_ctx* ctx, uint32_t k, const void* d_minimizer, const void* d_kmer_lo, const void* d_kmer_hi /* NULL if k <= 32 */,
+                               const uint64_t* h_sk_off /* n_ref + 1 */, uint32_t n_ref);
+/* Classifies one batch of records against the context's index.  The records' keys are distinct per record, in any order (the
+ * caller vouches for "distinct"), record r's at entries [h_rec_off[r], h_rec_off[r + 1]) of arrays of the caller's on the device --
+ * the key arrays of another context, a tensor, a slice; only read.  n_records is bounded by the entry extent 0xfffffff0, not by
+ * 65 535.  records: n_records (length is not touched); hits: n_records * top, zero behind each record's `listed`.  Any number of
+ * batches may be classified against one index; each call waits for the device once, at its end.  Launches, the same whatever the
+ * records are: a probe pass (a lane per record key) that also adds up every record's work = the sum over its keys of their holders,
+ * a routing pass, and the two tally-and-select forms the records were routed to by their work (spsp_classify_plan_host).
+ * SPSP_ERR_ARG (records' counts zeroed, and the hits wherever `top` itself is in range): no index on the context, d_q_kmer_hi given for an index of k <= 32 or missing
+ * for one of k > 32, top, min_keys, num or den out of range, decreasing offsets; SPSP_ERR_OVERFLOW: an extent above 0xfffffff0. */
+int spsp_classify_device(spsp_ctx* ctx, const void* d_q_minimizer, const void* d_q_kmer_lo, const void* d_q_kmer_hi /* NULL if k <= 32 */,
+                         const uint64_t* h_rec_off /* n_records + 1 */, uint32_t n_records, uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den,
+                         spsp_classify_record* records /* n_records */, spsp_classify_hit* hits /* n_records * top */);
+/* While the context's timing is on (spsp_timing_enable, any kind) a classify call records events between its launches; this reads
+ * the milliseconds added up since the last read and clears them: ms[0] the probe pass, ms[1] the routing pass, ms[2] the wave form
+ * (tally and selection are one kernel), ms[3] the workgroup form (likewise). */
+int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms /* 4 */);
+/* What routes a record, for n_ref references and `top` matches (any pointer may be NULL).  small_work: a record whose work is at
+ * most this is tallied by one wave, its holder numbers sorted and counted in LDS; a record of more work takes a workgroup with one
+ * 32-bit counter per reference.  lds_refs: up to this many references those counters sit in LDS, beyond it in a row of device
+ * memory per workgroup; *counters_in_lds = n_ref <= lds_refs.  list_cut: in the workgroup form a key's list of more holders than
+ * this is walked by a whole wave instead of one lane.  SPSP_ERR_ARG: n_ref outside 1 .. 65535, top outside 1 .. 64. */
+int spsp_classify_plan_host(uint32_t n_ref, uint32_t top, uint32_t* small_work, uint32_t* lds_refs, uint32_t* counters_in_lds, uint32_t* list_cut);
+/* The text of <prefix>_classify.csv.gz: "record,name,length,keys,hit_keys,rank,match,shared,f_shared,passing" and one line per
+ * listed match, rank from 1; a record without a passing reference gets one line with rank 0, an empty match, shared 0 and
+ * f_shared 0.  record = the record's number from 0, match = ref_names[reference], f_shared = shared / keys as %.<precision>g (0 when
+ * keys == 0; it decides nothing).  Rows that contradict themselves are SPSP_ERR_ARG, the message naming the record: listed >
+ * min(top, passing), hit_keys > keys, shared > hit_keys or shared == 0 in a listed match, matches out of order (or one reference
+ * twice), a reference >= n_ref.  *text is released with spsp_free(). */
+int spsp_classify_csv_host(const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records, const char* const* record_names,
+                           const char* const* ref_names, uint32_t n_ref, uint32_t top, int precision, char** text, uint64_t* len);
+/* The text of <prefix>_classify_summary.csv.gz: "reference,records_best,bases_best,keys_best,records_listed" and one line per
+ * reference -- the records whose rank-1 match it is, their lengths and shared keys added up, and the records that list it at all --
+ * closed by one line named "unclassified": the records without a match, their lengths, 0 and 0.  The same refusals. */
+int spsp_classify_summary_csv_host(const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records, const char* const* ref_names,
+                                   uint32_t n_ref, uint32_t top, char** text, uint64_t* len);
+/* The whole-file driver.  index_paths: n_ref sketch files, read, inflated and decoded as spsp_prevalence_files does it, with the
+ * same `rate` argument and refusals (k == m collections are SPSP_ERR_ARG); sketches of different rates need a rate, because the
+ * records are scanned at ONE threshold: spsp_threshold_host(k, m, the common rate, or the headers' own where they agree).
+ * records_path: a FASTA or FASTQ file (by its first byte), gzip or plain, ingested and scanned once on a second context of the same
+ * device; keys are extracted in batches of at most 65 535 records (spsp_sketch_keys_device over the records' range of the one scan)
+ * and each batch is classified against the index, the two contexts ordered by spsp_wait_stream.  A record's name is the first
+ * whitespace-delimited word of its header line, read on the host; a text whose headers are not as many as the records the device
+ * ingest finds is SPSP_ERR_FORMAT.  Writes <out_prefix>_classify.csv.gz and <out_prefix>_classify_summary.csv.gz (gzip level 1)
+ * and no matrices.  records, hits (may be NULL) receive copies released with spsp_free(); *n_records (may be NULL) their number. */
+int spsp_classify_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                        uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                        spsp_classify_record** records /* may be NULL; spsp_free */, spsp_classify_hit** hits /* may be NULL; spsp_free */,
+                        uint64_t* n_records /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,10 @@ ACCUMULATION_ROW_DTYPE = np.dtype([("pan_min", "<u8"), ("pan_max", "<u8"), ("pan
 GROUP_ROW_DTYPE = np.dtype([("members", "<u8"), ("entries", "<u8"), ("present", "<u8"), ("core", "<u8"), ("exclusive", "<u8"), ("marker", "<u8")])
 GROUP_MEMBER_ROW_DTYPE = np.dtype([("core", "<u8"), ("exclusive", "<u8"), ("marker", "<u8")])
 
+# spsp_classify_record / spsp_classify_hit: a record's counts, and one of its listed matches (include/spsp.h)
+CLASSIFY_RECORD_DTYPE = np.dtype([("length", "<u8"), ("keys", "<u4"), ("hit_keys", "<u4"), ("passing", "<u4"), ("listed", "<u4")])
+CLASSIFY_HIT_DTYPE = np.dtype([("reference", "<u4"), ("shared", "<u4")])
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -140,6 +144,7 @@ ABI_SYMBOLS = [
     "spsp_keys_select_device", "spsp_select_band_host", "spsp_sketch_from_keys_host", "spsp_select_files",
     "spsp_accumulation_orders_host", "spsp_accumulation_plan_host", "spsp_accumulation_device", "spsp_accumulation_csv_host", "spsp_accumulation_files",
     "spsp_groups_labels_host", "spsp_groups_bounds_host", "spsp_groups_device", "spsp_groups_csv_host", "spsp_groups_members_csv_host", "spsp_groups_files",
+    "spsp_classify_index_device", "spsp_classify_device", "spsp_classify_plan_host", "spsp_classify_csv_host", "spsp_classify_summary_csv_host", "spsp_classify_files", "spsp_classify_stage_ms",
 ]
 
 _lib = None
@@ -344,6 +349,21 @@ def lib():
         L.spsp_groups_members_csv_host.argtypes = [vp, u32, P(cp), vp, vp, vp, u32, P(cp), i32, P(vp), P(u64)]
         L.spsp_groups_files.restype = i32
         L.spsp_groups_files.argtypes = [vp, P(cp), u32, cp, i32, u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(vp), P(u32)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_classify_device"):
+        L.spsp_classify_index_device.restype = i32
+        L.spsp_classify_index_device.argtypes = [vp, u32, vp, vp, vp, vp, u32]
+        L.spsp_classify_device.restype = i32
+        L.spsp_classify_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, vp, vp]
+        L.spsp_classify_plan_host.restype = i32
+        L.spsp_classify_plan_host.argtypes = [u32, u32, P(u32), P(u32), P(u32), P(u32)]
+        L.spsp_classify_csv_host.restype = i32
+        L.spsp_classify_csv_host.argtypes = [vp, vp, u64, P(cp), P(cp), u32, u32, i32, P(vp), P(u64)]
+        L.spsp_classify_summary_csv_host.restype = i32
+        L.spsp_classify_summary_csv_host.argtypes = [vp, vp, u64, P(cp), u32, u32, P(vp), P(u64)]
+        L.spsp_classify_stage_ms.restype = i32
+        L.spsp_classify_stage_ms.argtypes = [vp, P(dbl)]
+        L.spsp_classify_files.restype = i32
+        L.spsp_classify_files.argtypes = [vp, P(cp), u32, cp, u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(vp), P(u64)]
     _lib = L
     return L
 
@@ -645,6 +665,47 @@ def accumulation_csv(rows, n_orders, precision=6):
     rows = np.ascontiguousarray(rows, dtype=ACCUMULATION_ROW_DTYPE)
     out, ln = C.c_void_p(), C.c_size_t()
     _check(lib().spsp_accumulation_csv_host(rows.ctypes.data if len(rows) else None, len(rows), n_orders, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def classify_plan(n_ref, top=1):
+    """spsp_classify_plan_host: what routes a record for n_ref references -> dict(small_work: the work (sum of its keys' holders) up
+    to which one wave tallies a record in LDS, lds_refs: the references up to which the workgroup form keeps its counters in LDS,
+    counters_in_lds: whether they do for n_ref, list_cut: the holders above which a whole wave walks a key's list)"""
+    a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_classify_plan_host(n_ref, top, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return {"small_work": a.value, "lds_refs": b.value, "counters_in_lds": bool(c.value), "list_cut": d.value}
+
+
+def _classify_rows(records, hits, top):
+    records = np.ascontiguousarray(records, dtype=CLASSIFY_RECORD_DTYPE)
+    hits = np.ascontiguousarray(hits, dtype=CLASSIFY_HIT_DTYPE).reshape(-1)
+    if len(hits) != len(records) * top:
+        raise ValueError("classification rows: `top` hits per record")
+    return records, hits
+
+
+def classify_csv(records, hits, record_names, ref_names, top, precision=6):
+    """spsp_classify_csv_host: records (CLASSIFY_RECORD_DTYPE), their hits (CLASSIFY_HIT_DTYPE, `top` per record), the records' and
+    the references' names -> the text of <prefix>_classify.csv.gz"""
+    records, hits = _classify_rows(records, hits, top)
+    if len(record_names) != len(records):
+        raise ValueError("classify_csv: one name per record")
+    r_arr, _a = _paths_array(record_names)
+    f_arr, _b = _paths_array(ref_names)
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_classify_csv_host(records.ctypes.data if len(records) else None, hits.ctypes.data if len(hits) else None, len(records), r_arr, f_arr,
+                                        len(ref_names), top, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def classify_summary_csv(records, hits, ref_names, top):
+    """spsp_classify_summary_csv_host: the same rows -> the text of <prefix>_classify_summary.csv.gz"""
+    records, hits = _classify_rows(records, hits, top)
+    f_arr, _b = _paths_array(ref_names)
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_classify_summary_csv_host(records.ctypes.data if len(records) else None, hits.ctypes.data if len(hits) else None, len(records), f_arr,
+                                                len(ref_names), top, C.byref(out), C.byref(ln)))
     return _take(out, ln.value)
 
 
@@ -1367,6 +1428,45 @@ class Context:
                                        _rate_arg(rate), C.byref(rows), C.byref(members), C.byref(G)))
         return (np.frombuffer(_take(rows, G.value * GROUP_ROW_DTYPE.itemsize), dtype=GROUP_ROW_DTYPE).copy(),
                 np.frombuffer(_take(members, n * GROUP_MEMBER_ROW_DTYPE.itemsize), dtype=GROUP_MEMBER_ROW_DTYPE).copy())
+
+    def classify_index_device(self, k, d_min, d_lo, d_hi, sk_off, n_ref):
+        """spsp_classify_index_device: the index of the references 0 .. n_ref-1 (concatenated sorted key arrays on the device, which
+        must stay as they are while the index is in use), kept in the context until its next prevalence, select, accumulation,
+        groups or index call"""
+        sk_off = np.ascontiguousarray(sk_off, dtype=np.uint64)
+        if len(sk_off) != n_ref + 1:
+            raise ValueError("classify_index_device: n_ref + 1 sketch offsets")
+        _check(lib().spsp_classify_index_device(self._h, k, d_min, d_lo, d_hi, sk_off.ctypes.data, n_ref))
+
+    def classify_device(self, d_min, d_lo, d_hi, rec_off, top=1, min_keys=1, num=0, den=1):
+        """spsp_classify_device: the records whose distinct keys sit at [rec_off[r], rec_off[r + 1]) of key arrays on the device,
+        against the context's index -> (records CLASSIFY_RECORD_DTYPE[n] with length 0, hits CLASSIFY_HIT_DTYPE[n, top])"""
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        if len(rec_off) < 1:
+            raise ValueError("classify_device: n_records + 1 record offsets")
+        n = len(rec_off) - 1
+        records = np.zeros(max(n, 1), dtype=CLASSIFY_RECORD_DTYPE)
+        hits = np.zeros((max(n, 1), max(top, 1)), dtype=CLASSIFY_HIT_DTYPE)
+        _check(lib().spsp_classify_device(self._h, d_min, d_lo, d_hi, rec_off.ctypes.data, n, top, min_keys, num, den, records.ctypes.data, hits.ctypes.data))
+        return records[:n], hits[:n]
+
+    def classify_stage_ms(self):
+        """spsp_classify_stage_ms: with timing_enable() on, the milliseconds of the classify calls' launches since the last read ->
+        dict(probe, route, wave_form, workgroup_form); tally and selection are one kernel in each form"""
+        ms = (C.c_double * 4)()
+        _check(lib().spsp_classify_stage_ms(self._h, ms))
+        return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
+
+    def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0):
+        """spsp_classify_files: the sketch files of the references and a FASTA / FASTQ file of records (gzip or plain) ->
+        <prefix>_classify.csv.gz, <prefix>_classify_summary.csv.gz and (records, hits[n, top]).  rate: as compare_files (0.0, a
+        rate, or "auto"); sketches of different rates need one"""
+        arr, _alive = _paths_array(paths)
+        recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_classify_files(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
+                                         _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n)))
+        return (np.frombuffer(_take(recs, n.value * CLASSIFY_RECORD_DTYPE.itemsize), dtype=CLASSIFY_RECORD_DTYPE).copy(),
+                np.frombuffer(_take(hits, n.value * top * CLASSIFY_HIT_DTYPE.itemsize), dtype=CLASSIFY_HIT_DTYPE).copy().reshape(n.value, top))
 
     def select_files(self, paths, prefix, what, each=False, n_query=0, rate=None):
         """spsp_select_files: sketch files (the n_query queries first, or none) -> the keys in the band `what` (select_band's words)

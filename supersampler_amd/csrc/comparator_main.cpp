@@ -121,9 +121,28 @@ int main(int argc, char** argv) {
     bool groups = false, gp_markers = false;
     int gp_opts = 0;                 // -T, -U or -M seen
     uint32_t gp_num = 1, gp_den = 1, gp_onum = 0, gp_oden = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:M")) != -1) {
+    string records_file;             // -X <records file> [-Y <top>] [-V <min_keys>] [-I <t>]: -X, -Y and -V are not in the reference's option string
+    bool classify = false;
+    int cf_opts = 0;                 // -Y or -V seen
+    long long cf_top = 1, cf_min_keys = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:")) != -1) {
         switch (ch) {
             case 'G': labels_file = optarg; groups = true; break;
+            case 'X': records_file = optarg; classify = true; break;
+            case 'Y': {
+                char* e = nullptr;
+                cf_top = strtoll(optarg, &e, 10);
+                if (e == optarg || *e || cf_top < 1 || cf_top > 64) { cout << "-Y takes the number of matches listed per record, an integer in 1 .. 64, not '" << optarg << "'" << endl; return 1; }
+                ++cf_opts;
+                break;
+            }
+            case 'V': {
+                char* e = nullptr;
+                cf_min_keys = strtoll(optarg, &e, 10);
+                if (e == optarg || *e || cf_min_keys < 1 || cf_min_keys > 0xffffffffll) { cout << "-V takes the smallest number of shared keys a match is listed for, an integer >= 1, not '" << optarg << "'" << endl; return 1; }
+                ++cf_opts;
+                break;
+            }
             case 'T':
                 if (!parse_fraction(optarg, &gp_num, &gp_den)) {
                     cout << "-T takes the share of a group's members that makes a key core, in (0, 1] with at most six digits behind the point, not '" << optarg << "'" << endl;
@@ -243,7 +262,13 @@ int main(int argc, char** argv) {
     if (cluster_opts > 1) { cout << "-c (Jaccard) and -C (containment) cluster the index: one of them, once" << endl; return 1; }
     if (cluster_opts && (query != "" || gather)) { cout << "-c / -C cluster the index all versus all: not together with -q or -g" << endl; return 1; }
     if (nb_opts > 1) { cout << "-J (Jaccard), -K (the larger containment) and -I (the row's containment) set the threshold of -N: one of them, once" << endl; return 1; }
-    if (nb_opts && !neighbours) { cout << "-J / -K / -I set the threshold of the neighbour lists: they need -N" << endl; return 1; }
+    if (cf_opts && !classify) { cout << "-Y and -V belong to the classification of -X <records file>: they need -X" << endl; return 1; }
+    if (classify && (query != "" || gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts || select_opts || accumulation || groups ||
+                     (nb_opts && nb_metric != SPSP_NEIGHBOUR_CONTAINED))) {
+        cout << "-X classifies the records of a sequence file against the index: not together with -q, -g, -c, -C, -N, -J, -K, -P, -r, -R, -l, -L, -S, -E, -A or -G" << endl;
+        return 1;
+    }
+    if (nb_opts && !neighbours && !classify) { cout << "-J / -K / -I set the threshold of the neighbour lists: they need -N (-I also serves -X)" << endl; return 1; }
     if (neighbours && (gather || cluster_opts)) { cout << "-N lists neighbours: not together with -g, -c or -C" << endl; return 1; }
     if (prevalence && (gather || cluster_opts || neighbours)) { cout << "-P counts the holders of every key: not together with -g, -c, -C or -N" << endl; return 1; }
     if (rep_opts > 1) { cout << "-r (Jaccard) and -R (containment) pick representatives of the index: one of them, once" << endl; return 1; }
@@ -324,6 +349,17 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (classify) {
+        // one device, as gather (the driver opens a second context on it for the records)
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_classify_files(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den,
+                                                    (int)p, output_name.c_str(), 1, rate, nullptr, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Classification failed: " << err << endl; return 1; }
+        return 0;
     }
     if (groups) {
         // one device, as gather

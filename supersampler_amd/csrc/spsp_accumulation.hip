@@ -7,7 +7,7 @@
 //   pan(j)  = #{x : first(x) < j}      core(j) = #{x : mex(x) >= j}        j = 1 .. n
 // so an order is two histograms, F[r] = #{x : first = r} and M[r] = #{x : mex = r}, and the host's prefix sums over them.
 //
-// Built once per call, whatever the number of orders:
+// Built once per call, whatever the number of orders (key_major_build: the classification's index is the same form, spsp_classify.hip):
 //   table fill    prevalence's own (prevalence_fill_table, claim = true): holders[e] = h of entry e, bit 31 on the one entry per
 //                 distinct key that claimed the key's slot
 //   k_ac_prep     a lane per entry: the two scan inputs -- claimer ? 1 : 0 and claimer ? h : 0
@@ -241,6 +241,44 @@ int ac_launch_pass(spsp_ctx* ctx, dim3 grid, size_t lds, const uint32_t* key_sta
 
 }  // namespace
 
+// (spsp_internal.h) the key-major form of the sketches 0 .. n-1: the table fill with claimers, k_ac_prep, the two scans, k_ac_scatter
+int key_major_build(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,
+                    uint32_t cut, KeyMajor* out) {
+    int rc;
+    const uint64_t first = h_sk_off[0];
+    const uint32_t E = (uint32_t)(h_sk_off[n] - h_sk_off[0]);
+    // work area: flag words | is_key [E] | key_len [E] | key_no [E + 1] | start [E + 1]
+    const size_t words_bytes = 64, arr = ((size_t)E + 2) * 4;
+    if ((rc = ctx->ac_work.reserve(words_bytes + 4 * arr)) || (rc = ctx->ac_keys.reserve(((size_t)E + 1) * 4)) || (rc = ctx->ac_list.reserve((size_t)E * 2 + 64))) return rc;
+    uint32_t* d_words = ctx->ac_work.as<uint32_t>();
+    uint32_t* d_is_key = d_words + words_bytes / 4;
+    uint32_t* d_key_len = d_is_key + arr / 4;
+    uint32_t* d_key_no = d_key_len + arr / 4;
+    uint32_t* d_start = d_key_no + arr / 4;
+    uint32_t* d_key_start = ctx->ac_keys.as<uint32_t>();
+    uint16_t* d_list = ctx->ac_list.as<uint16_t>();
+    SPSP_HIP(hipMemsetAsync(d_words, 0, kAcWords * 4, ctx->stream));
+    SPSP_HIP(hipMemsetAsync(d_list, 0, (size_t)E * 2, ctx->stream));   // (whatever the scatter leaves out, a list names sketches below n)
+    if ((rc = prevalence_fill_table(ctx, has_hi, d_mn, d_lo, d_hi, h_sk_off, n, 0, true, d_words))) return rc;
+    const uint64_t* d_off = ctx->pv_off.as<uint64_t>();
+    unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
+    const uint32_t* d_hold = ctx->pv_hold.as<uint32_t>() + first;
+    const SortedKeys K{d_mn, d_lo, d_hi};
+    uint32_t* d_long = d_is_key;                           // the queue of long lists: the first scan's input, which is spent by then
+    const uint32_t gx = (uint32_t)(((uint64_t)E + kAcThreads - 1) / kAcThreads);
+    hipLaunchKernelGGL(k_ac_prep, dim3(gx), dim3(kAcThreads), 0, ctx->stream, d_hold, E, d_is_key, d_key_len);
+    SPSP_HIP(hipGetLastError());
+    // (the totals stay on the device, in the scans' out[E]: nothing of them comes to the host)
+    if ((rc = launch_scan_u32(ctx, d_is_key, d_key_no, E, nullptr)) || (rc = launch_scan_u32(ctx, d_key_len, d_start, E, nullptr))) return rc;
+    if (has_hi) hipLaunchKernelGGL(k_ac_scatter<true>, dim3(gx), dim3(kAcThreads), 0, ctx->stream, K, d_off, n, d_tbl, ctx->pv_log2cap, d_hold,
+                                   (const uint32_t*)d_key_no, (const uint32_t*)d_start, E, cut, d_key_start, d_list, d_long, d_words);
+    else hipLaunchKernelGGL(k_ac_scatter<false>, dim3(gx), dim3(kAcThreads), 0, ctx->stream, K, d_off, n, d_tbl, ctx->pv_log2cap, d_hold,
+                            (const uint32_t*)d_key_no, (const uint32_t*)d_start, E, cut, d_key_start, d_list, d_long, d_words);
+    SPSP_HIP(hipGetLastError());
+    *out = KeyMajor{d_words, d_key_no, d_key_start, d_list, d_long, E};
+    return SPSP_OK;
+}
+
 int accumulation_check_args(uint32_t n, uint32_t n_orders) {
     if (n == 0 || n > 65535) { set_error("accumulation takes 1 .. 65535 sketches (n = %u)", n); return SPSP_ERR_ARG; }
     if (n_orders == 0 || n_orders > 1024) { set_error("accumulation takes 1 .. 1024 orders (%u)", n_orders); return SPSP_ERR_ARG; }
@@ -258,7 +296,7 @@ int accumulation_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, co
     KeysShape shape;
     if ((rc = sorted_keys_front(ctx, "accumulation reads", k, d_mn, d_lo, d_hi, h_sk_off, n, &shape))) return rc;
     const bool has_hi = shape.has_hi;
-    const uint64_t first = shape.first, all_keys = shape.all_keys;
+    const uint64_t all_keys = shape.all_keys;
     uint32_t group = 0, window = 0;
     if ((rc = spsp_accumulation_plan_host(n, &group, &window, nullptr, nullptr))) return rc;
     // the orders as rank tables (the inverse permutations), the last group filled up with copies of the last order
@@ -283,46 +321,25 @@ int accumulation_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, co
     }
     if (all_keys == 0) return SPSP_OK;                     // (no key anywhere: every curve is 0)
     const uint32_t E = (uint32_t)all_keys;
-    // work area: flag words | is_key [E] | key_len [E] | key_no [E + 1] | start [E + 1]
-    const size_t words_bytes = 64, arr = ((size_t)E + 2) * 4;
     const size_t f_words = (size_t)p_pad * n, m_words = (size_t)p_pad * (n + 1u);
-    if ((rc = ctx->ac_work.reserve(words_bytes + 4 * arr)) || (rc = ctx->ac_keys.reserve(((size_t)E + 1) * 4)) || (rc = ctx->ac_list.reserve((size_t)E * 2 + 64)) ||
-        (rc = ctx->ac_rank.reserve(rank.size() * 2)) || (rc = ctx->ac_hist.reserve((f_words + m_words) * 8))) return rc;
-    uint32_t* d_words = ctx->ac_work.as<uint32_t>();
-    uint32_t* d_is_key = d_words + words_bytes / 4;
-    uint32_t* d_key_len = d_is_key + arr / 4;
-    uint32_t* d_key_no = d_key_len + arr / 4;
-    uint32_t* d_start = d_key_no + arr / 4;
-    uint32_t* d_key_start = ctx->ac_keys.as<uint32_t>();
-    uint16_t* d_list = ctx->ac_list.as<uint16_t>();
+    if ((rc = ctx->ac_rank.reserve(rank.size() * 2)) || (rc = ctx->ac_hist.reserve((f_words + m_words) * 8))) return rc;
     uint16_t* d_rank = ctx->ac_rank.as<uint16_t>();
     unsigned long long* d_F = ctx->ac_hist.as<unsigned long long>();
     unsigned long long* d_M = d_F + f_words;
-    SPSP_HIP(hipMemsetAsync(d_words, 0, kAcWords * 4, ctx->stream));
     SPSP_HIP(hipMemsetAsync(d_F, 0, (f_words + m_words) * 8, ctx->stream));
-    SPSP_HIP(hipMemsetAsync(d_list, 0, (size_t)E * 2, ctx->stream));   // (whatever the scatter leaves out, a list names sketches below n)
     SPSP_HIP(hipMemcpyAsync(d_rank, rank.data(), rank.size() * 2, hipMemcpyHostToDevice, ctx->stream));   // (rank: alive until the wait)
-    if ((rc = prevalence_fill_table(ctx, has_hi, d_mn, d_lo, d_hi, h_sk_off, n, 0, true, d_words))) return rc;
-    const uint64_t* d_off = ctx->pv_off.as<uint64_t>();
-    unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
-    const uint32_t* d_hold = ctx->pv_hold.as<uint32_t>() + first;
-    const SortedKeys K{d_mn, d_lo, d_hi};
     uint32_t cut = kAcCut;
     if (const char* dbg = getenv("SPSP_DEBUG_ACCUMULATION_CUT")) {   // (analysis: where the lane's walk ends and the wave's begins, 0 .. 64)
         const long v = atol(dbg);
         if (v >= 0 && v <= 64) cut = (uint32_t)v;
     }
-    uint32_t* d_long = d_is_key;                           // the queue of long lists: the first scan's input, which is spent by then
-    const uint32_t gx = (uint32_t)(((uint64_t)E + kAcThreads - 1) / kAcThreads);
-    hipLaunchKernelGGL(k_ac_prep, dim3(gx), dim3(kAcThreads), 0, ctx->stream, d_hold, E, d_is_key, d_key_len);
-    SPSP_HIP(hipGetLastError());
-    // (the totals stay on the device, in the scans' out[E]: nothing of them comes to the host)
-    if ((rc = launch_scan_u32(ctx, d_is_key, d_key_no, E, nullptr)) || (rc = launch_scan_u32(ctx, d_key_len, d_start, E, nullptr))) return rc;
-    if (has_hi) hipLaunchKernelGGL(k_ac_scatter<true>, dim3(gx), dim3(kAcThreads), 0, ctx->stream, K, d_off, n, d_tbl, ctx->pv_log2cap, d_hold,
-                                   (const uint32_t*)d_key_no, (const uint32_t*)d_start, E, cut, d_key_start, d_list, d_long, d_words);
-    else hipLaunchKernelGGL(k_ac_scatter<false>, dim3(gx), dim3(kAcThreads), 0, ctx->stream, K, d_off, n, d_tbl, ctx->pv_log2cap, d_hold,
-                            (const uint32_t*)d_key_no, (const uint32_t*)d_start, E, cut, d_key_start, d_list, d_long, d_words);
-    SPSP_HIP(hipGetLastError());
+    KeyMajor km;
+    if ((rc = key_major_build(ctx, has_hi, d_mn, d_lo, d_hi, h_sk_off, n, cut, &km))) return rc;
+    uint32_t* d_words = km.words;
+    const uint32_t* d_key_no = km.key_no;
+    const uint32_t* d_key_start = km.key_start;
+    const uint16_t* d_list = km.list;
+    const uint32_t* d_long = km.long_keys;
     // the passes: one launch per group of orders.  A workgroup per CU and as many as the LDS leaves room for, never more than the
     // keys can feed (there are E of them at the most: the number itself stays on the device)
     const size_t lds = (size_t)group * n_pad * 2 + (size_t)group * window * 4 + (size_t)kAcWaves * kAcMapWords * 4;

@@ -1,0 +1,607 @@
+// Classification on the GPU: which references each record of a sequence file belongs to (not in the reference, whose end product
+// is the two n x n matrices).
+//
+// The index is a collection as every collection pass takes it: references 0 .. R-1 back to back, each sorted by (minimizer, kmer_hi,
+// kmer_lo), with key sets K_j.  A record r has a set Q_r of distinct keys, in any order, in arrays of the caller's.
+//   shared(r, j) = |Q_r n K_j|        hit_keys(r) = #{x in Q_r : some K_j holds x}
+// Reference j passes for r when shared >= min_keys and shared * den >= num * |Q_r|; the matches of r are its best min(top, passing)
+// passing references by the 64-bit word shared << 32 | (0xffffffff - j): more shared keys first, the lower number among equals.  The
+// order is total, so nothing below depends on which lane met what first.  Integers only.
+//
+// The index, built once (spsp_classify_index_device): key_major_build (spsp_accumulation.hip) -- the prevalence table filled with
+// claimers, and the key-major CSR: key_start[0 .. D] and the 16-bit holder numbers, list behind list.  The scatter has spent the
+// slots' counters as cursors; a lookup goes slot -> claimer entry -> key_no -> key_start[kn], key_start[kn + 1] -> list[].
+// Per batch of records (spsp_classify_device), one chain of launches whatever the records are:
+//   k_cf_probe   a lane per record key: the probe sequence of k_pv_read, a miss at the first free slot; kn[e] = the key's number + 1
+//                (0: nobody holds it).  The lane's h goes to its record's work and 1 to its hit keys: one add per wave where the
+//                wave sits inside one record (a contig), one per lane with a hit otherwise (reads: a few lanes per record).
+//                Bound: one random 8-byte slot read and one 20-byte key read per key -- HBM latency under full occupancy.
+//   k_cf_route   a lane per record: no work -> its row is written here; work <= kCfSmallWork -> the queue of the small form; else the
+//                queue of the large form.  The queues' order is a race and no result depends on it.  No host wait: the two forms
+//                below are launched with grids sized by the records there can be and stride over what the queues hold.
+//   k_cf_small   a wave per record: the holder numbers of all its keys gathered into the wave's 4 KiB of LDS (long lists by the
+//                whole wave, as in the large form), sorted there by a
+//                bitonic network, and every run of equal numbers counted by a binary search for its start; the runs are offered
+//                64 at a time to the kept matches.  Bound: LDS traffic of the sort, (log2 P)^2 / 2 steps over P <= 1 024 words.
+//   k_cf_large   a workgroup per record with one 32-bit counter per reference: in LDS while 4 R bytes fit beside the kept matches
+//                (R <= kCfLdsRefs), in a row of HBM per workgroup beyond.  A wave takes 64 keys; a lane walks its own list, lists
+//                of more than kCfListCut holders are walked by the whole wave (coalesced: a contig against its species has
+//                h = R on every key).  Then every wave offers its share of the counters, and wave 0 merges the eight kept lists.
+//                Bound: Sum h atomic adds, on LDS at the LDS atomic rate, beyond kCfLdsRefs on L2.
+// Kept matches: one 64-bit word per lane, best first.  A chunk of 64 candidates that holds nothing in front of the top-th kept word
+// is dropped with one ballot; else it is sorted by the register bitonic network of spsp_neighbours.hip and merged with the kept 64.
+// The host waits once per batch, at the end.  No workgroup ever waits for another one.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "spsp_device.h"
+#include "spsp_internal.h"
+
+namespace spsp {
+
+namespace {
+
+enum { kCfqSmall = 0, kCfqLarge = 1, kCfqBad = 2, kCfqWords = 4 };   // words in front of the queues: their fill, the flag word, one spare
+constexpr uint32_t kCfWaves = kCfThreads / 64, kCfLargeWaves = kCfLargeThreads / 64;
+
+// the wave's LDS words: what its lanes stored in front of this line is what they read behind it
+__device__ __forceinline__ void cf_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ unsigned long long cf_word(uint32_t shared, uint32_t ref) { return (unsigned long long)shared << 32 | (0xffffffffu - ref); }
+
+// one compare-exchange with the lane `j` away: the lane keeps the larger word (front) or the smaller one
+__device__ __forceinline__ void cf_exchange(unsigned long long& v, uint32_t j, bool front) {
+    const unsigned long long o = __shfl_xor(v, (int)j);
+    if (front ? o > v : o < v) v = o;
+}
+
+// kept: the best 64 so far, best first, one per lane (0: none).  v: one candidate per lane (0: none).  Words of real candidates are
+// distinct (a reference is offered once) and only the first `top` kept words are ever read: a chunk that holds nothing in front of
+// the top-th one changes nothing
+__device__ __forceinline__ void cf_offer(unsigned long long& kept, unsigned long long v, uint32_t lane, uint32_t top) {
+    if (!__any(v > __shfl(kept, (int)(top - 1u)))) return;
+#pragma unroll
+    for (uint32_t k = 2; k <= 64u; k <<= 1)
+#pragma unroll
+        for (uint32_t j = k >> 1; j; j >>= 1) cf_exchange(v, j, ((lane & j) == 0) == ((lane & k) == 0));
+    // kept (best first) against the chunk reversed: the larger of every pair -- the best 64 of the 128, as a bitonic run
+    const unsigned long long o = __shfl(v, (int)(63u - lane));
+    if (o > kept) kept = o;
+#pragma unroll
+    for (uint32_t j = 32; j; j >>= 1) cf_exchange(kept, j, (lane & j) == 0);
+}
+
+__device__ __forceinline__ bool cf_passes(uint32_t shared, uint32_t keys, uint32_t min_keys, uint32_t num, uint32_t den) {
+    return shared >= min_keys && (unsigned long long)shared * den >= (unsigned long long)num * keys;
+}
+
+// Q: the records' keys, entries [off[0], off[n_rec]); K, tbl, key_no, key_start: the index (first: its first entry, n_index: its entries)
+template <bool HAS_HI>
+__global__ __launch_bounds__(kCfThreads) void k_cf_probe(SortedKeys Q, const uint64_t* __restrict__ off, uint32_t n_rec, SortedKeys K, uint64_t first,
+                                                         uint32_t n_index, const unsigned long long* __restrict__ tbl, uint32_t log2cap,
+                                                         const uint32_t* __restrict__ key_no, const uint32_t* __restrict__ key_start,
+                                                         uint32_t* __restrict__ kn_out, unsigned long long* __restrict__ work, uint32_t* __restrict__ hit) {
+    const uint64_t q0 = off[0], n_keys = off[n_rec] - q0;
+    const uint64_t i = (uint64_t)blockIdx.x * kCfThreads + threadIdx.x;
+    const bool valid = i < n_keys;
+    uint32_t kn = 0, h = 0, rec = 0xffffffffu;
+    if (valid) {
+        const uint64_t e = q0 + i;
+        const uint32_t mn = Q.mn[e];
+        const uint64_t lo = Q.lo[e], hi = HAS_HI ? Q.hi[e] : 0ull;
+        const uint64_t mask = (1ull << log2cap) - 1ull;
+        uint64_t pos = pv_home<HAS_HI>(mn, hi, lo, log2cap);
+        for (uint64_t probes = 0; probes <= mask; ++probes) {   // (a key nobody holds may go round a table without a free slot)
+            const unsigned long long cur = tbl[pos];
+            if ((uint32_t)cur == 0u) break;
+            const uint64_t c = (uint64_t)((uint32_t)cur - 1u), at = c - first;
+            if (at < n_index && pv_same<HAS_HI>(K, c, mn, hi, lo)) {   // (always inside: the index call filled this table from these entries)
+                const uint32_t number = key_no[at];
+                kn = number + 1u;
+                h = key_start[number + 1u] - key_start[number];
+                break;
+            }
+            pos = (pos + 1ull) & mask;
+        }
+        kn_out[i] = kn;
+        rec = sorted_sketch_of(off, 0, n_rec, e);
+    }
+    // the record's work and hit keys.  Entries are in record order: first and last lane in one record = the whole wave in it
+    const uint32_t r0 = __shfl(rec, 0), r63 = __shfl(rec, 63);
+    if (r0 == r63) {                                       // (uniform.  A wave of lanes beyond the keys: 0xffffffff, nothing to add)
+        unsigned long long w = h;
+        uint32_t c = kn != 0u;
+#pragma unroll
+        for (int d = 32; d; d >>= 1) { w += __shfl_xor(w, d); c += __shfl_xor(c, d); }
+        if ((threadIdx.x & 63u) == 0u && c != 0u) { atomicAdd(&work[r0], w); atomicAdd(&hit[r0], c); }
+    } else if (kn != 0u) {
+        atomicAdd(&work[rec], (unsigned long long)h);
+        atomicAdd(&hit[rec], 1u);
+    }
+}
+
+// rec[r]: keys, hit_keys, passing, listed
+__global__ __launch_bounds__(kCfThreads) void k_cf_route(const uint64_t* __restrict__ off, uint32_t n_rec, const unsigned long long* __restrict__ work,
+                                                         const uint32_t* __restrict__ hit, uint32_t* __restrict__ words, uint32_t* __restrict__ q_small,
+                                                         uint32_t* __restrict__ q_large, uint4* __restrict__ rec) {
+    const uint64_t r = (uint64_t)blockIdx.x * kCfThreads + threadIdx.x;
+    if (r >= n_rec) return;
+    const unsigned long long w = work[r];
+    if (w == 0ull) rec[r] = make_uint4((uint32_t)(off[r + 1] - off[r]), 0u, 0u, 0u);
+    else if (w <= kCfSmallWork) q_small[atomicAdd(words + kCfqSmall, 1u)] = (uint32_t)r;   // (a queue has room for every record)
+    else q_large[atomicAdd(words + kCfqLarge, 1u)] = (uint32_t)r;
+}
+
+// a wave per queued record; kn, and the entries of off, count from the first record key
+__global__ __launch_bounds__(kCfThreads) void k_cf_small(const uint64_t* __restrict__ off, const uint32_t* __restrict__ kn_of, const uint32_t* __restrict__ hit,
+                                                         const uint32_t* __restrict__ key_start, const uint16_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ q_small, uint32_t* __restrict__ words, uint32_t top,
+                                                         uint32_t min_keys, uint32_t num, uint32_t den, uint4* __restrict__ rec, spsp_classify_hit* __restrict__ hits) {
+    __shared__ uint32_t s_all[kCfWaves][kCfSmallWork];
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    uint32_t* s = s_all[wid];
+    const uint32_t n_small = words[kCfqSmall];
+    const uint64_t q0 = off[0];
+    for (uint64_t q = (uint64_t)blockIdx.x * kCfWaves + wid; q < n_small; q += (uint64_t)gridDim.x * kCfWaves) {   // (uniform per wave)
+        const uint32_t r = q_small[q];
+        const uint64_t a = off[r] - q0, z = off[r + 1] - q0;
+        const uint32_t keys = (uint32_t)(z - a);
+        // the holder numbers of all the record's keys, list behind list
+        uint32_t W = 0;
+        bool fits = true;
+        for (uint64_t base = a; base < z; base += 64ull) {
+            const uint64_t i = base + lane;
+            const uint32_t kn = i < z ? kn_of[i] : 0u;
+            const uint32_t ls = kn ? key_start[kn - 1u] : 0u, len = kn ? key_start[kn] - ls : 0u;
+            uint32_t incl = len;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(incl, d); if ((int)lane >= d) incl += t; }
+            const uint32_t total = __shfl(incl, 63);
+            if (total > kCfSmallWork - W) { fits = false; break; }   // (never: the route sent a record of this much work elsewhere.  Uniform)
+            const uint32_t at = W + incl - len;
+            if (len <= kCfListCut)
+                for (uint32_t j = 0; j < len; ++j) s[at + j] = list[ls + j];
+            unsigned long long left = __ballot(len > kCfListCut);
+            while (left) {                                 // the long lists, one after another by the whole wave
+                const int l = __ffsll((long long)left) - 1;
+                const uint32_t s0 = __shfl(ls, l), n0 = __shfl(len, l), a0 = __shfl(at, l);
+                for (uint32_t j = lane; j < n0; j += 64u) s[a0 + j] = list[s0 + j];
+                left &= left - 1ull;
+            }
+            W += total;
+        }
+        if (!fits) { if (lane == 0u) atomicOr(words + kCfqBad, 1u); continue; }
+        uint32_t P = 64;
+        while (P < W) P <<= 1;
+        for (uint32_t i = W + lane; i < P; i += 64u) s[i] = 0xffffffffu;
+        cf_wave_sync();
+        for (uint32_t k = 2; k <= P; k <<= 1)
+            for (uint32_t j = k >> 1; j; j >>= 1) {
+                for (uint32_t t = lane; t < P / 2u; t += 64u) {
+                    const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i + j;
+                    const uint32_t x = s[i], y = s[l];
+                    if ((x > y) == ((i & k) == 0u)) { s[i] = y; s[l] = x; }
+                }
+                cf_wave_sync();
+            }
+        // every run of one number is a reference with shared = the run's length: its last place less the first place of its number
+        unsigned long long kept = 0ull;
+        uint32_t passing = 0;
+        for (uint32_t base = 0; base < W; base += 64u) {   // (uniform)
+            const uint32_t i = base + lane;
+            unsigned long long v = 0ull;
+            if (i < W) {
+                const uint32_t ref = s[i];
+                if (i + 1u == W || s[i + 1u] != ref) {
+                    uint32_t lo = 0, hi = i;               // the first place that holds ref
+                    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (s[mid] < ref) lo = mid + 1u; else hi = mid; }
+                    const uint32_t shared = i - lo + 1u;
+                    if (cf_passes(shared, keys, min_keys, num, den)) v = cf_word(shared, ref);
+                }
+            }
+            passing += (uint32_t)__popcll(__ballot(v != 0ull));
+            cf_offer(kept, v, lane, top);
+        }
+        cf_wave_sync();                                    // (the words are read: the next record may overwrite them)
+        const uint32_t listed = passing < top ? passing : top;
+        if (lane < listed) {
+            spsp_classify_hit o;
+            o.reference = 0xffffffffu - (uint32_t)kept; o.shared = (uint32_t)(kept >> 32);
+            hits[(uint64_t)r * top + lane] = o;
+        }
+        if (lane == 0u) rec[r] = make_uint4(keys, hit[r], passing, listed);
+    }
+}
+
+// a workgroup per queued record.  LDS: [IN_LDS: R_pad counters |] the waves' kept matches | the passing count.  rows: !IN_LDS, a row
+// of R_pad counters per workgroup
+template <bool IN_LDS>
+__global__ __launch_bounds__(kCfLargeThreads) void k_cf_large(const uint64_t* __restrict__ off, const uint32_t* __restrict__ kn_of, const uint32_t* __restrict__ hit,
+                                                              const uint32_t* __restrict__ key_start, const uint16_t* __restrict__ list,
+                                                              const uint32_t* __restrict__ q_large, const uint32_t* __restrict__ words, uint32_t R,
+                                                              uint32_t R_pad, uint32_t* __restrict__ rows, uint32_t top, uint32_t min_keys, uint32_t num,
+                                                              uint32_t den, uint4* __restrict__ rec, spsp_classify_hit* __restrict__ hits) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
+    uint32_t* cnt = IN_LDS ? s_mem : rows + (size_t)blockIdx.x * R_pad;
+    unsigned long long* s_kept = reinterpret_cast<unsigned long long*>(s_mem + (IN_LDS ? R_pad : 0u));
+    uint32_t* s_pass = reinterpret_cast<uint32_t*>(s_kept + kCfLargeWaves * 64u);
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    const uint32_t n_large = words[kCfqLarge];
+    const uint64_t q0 = off[0];
+    for (uint64_t q = blockIdx.x; q < n_large; q += gridDim.x) {   // (uniform per workgroup)
+        const uint32_t r = q_large[q];
+        const uint64_t a = off[r] - q0, z = off[r + 1] - q0;
+        const uint32_t keys = (uint32_t)(z - a);
+        // (the rows in device memory are added to at L2: they are cleared and read there as well, past this CU's L1)
+        for (uint32_t j = threadIdx.x; j < R; j += kCfLargeThreads) {
+            if (IN_LDS) cnt[j] = 0u;
+            else __hip_atomic_store(cnt + j, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (threadIdx.x == 0u) *s_pass = 0u;
+        __syncthreads();
+        for (uint64_t base = a + (uint64_t)wid * 64ull; base < z; base += (uint64_t)kCfLargeWaves * 64ull) {   // (uniform per wave)
+            const uint64_t i = base + lane;
+            const uint32_t kn = i < z ? kn_of[i] : 0u;
+            const uint32_t ls = kn ? key_start[kn - 1u] : 0u, len = kn ? key_start[kn] - ls : 0u;
+            if (len <= kCfListCut)
+                for (uint32_t j = 0; j < len; ++j) { const uint32_t sk = list[ls + j]; if (sk < R) atomicAdd(&cnt[sk], 1u); }
+            unsigned long long left = __ballot(len > kCfListCut);
+            while (left) {                                 // the long lists, one after another by the whole wave
+                const int l = __ffsll((long long)left) - 1;
+                const uint32_t s0 = __shfl(ls, l), n0 = __shfl(len, l);
+                for (uint32_t j = lane; j < n0; j += 64u) { const uint32_t sk = list[s0 + j]; if (sk < R) atomicAdd(&cnt[sk], 1u); }
+                left &= left - 1ull;
+            }
+        }
+        __syncthreads();
+        unsigned long long kept = 0ull;
+        uint32_t passing = 0;
+        for (uint32_t base = wid * 64u; base < R; base += kCfLargeThreads) {   // (uniform per wave)
+            const uint32_t j = base + lane;
+            const uint32_t c = j >= R ? 0u : IN_LDS ? cnt[j] : __hip_atomic_load(cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long v = c != 0u && cf_passes(c, keys, min_keys, num, den) ? cf_word(c, j) : 0ull;
+            passing += (uint32_t)__popcll(__ballot(v != 0ull));
+            cf_offer(kept, v, lane, top);
+        }
+        s_kept[wid * 64u + lane] = kept;
+        if (lane == 0u && passing) atomicAdd(s_pass, passing);
+        __syncthreads();
+        if (wid == 0u) {
+            for (uint32_t w = 1; w < kCfLargeWaves; ++w) {
+                const unsigned long long o = s_kept[w * 64u + 63u - lane];   // (best first there: reversed here)
+                if (!__any(o > kept)) continue;
+                if (o > kept) kept = o;
+#pragma unroll
+                for (uint32_t j = 32; j; j >>= 1) cf_exchange(kept, j, (lane & j) == 0);
+            }
+            const uint32_t all = *s_pass, listed = all < top ? all : top;
+            if (lane < listed) {
+                spsp_classify_hit o;
+                o.reference = 0xffffffffu - (uint32_t)kept; o.shared = (uint32_t)(kept >> 32);
+                hits[(uint64_t)r * top + lane] = o;
+            }
+            if (lane == 0u) rec[r] = make_uint4(keys, hit[r], all, listed);
+        }
+        __syncthreads();                                   // (the counters and the kept words are read: the next record clears them)
+    }
+}
+
+}  // namespace
+
+int classify_index_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n_ref) {
+    int rc;
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    KeysShape shape;
+    if ((rc = sorted_keys_front(ctx, "classification reads", k, d_mn, d_lo, d_hi, h_sk_off, n_ref, &shape))) return rc;
+    spsp_ctx::ClassifyIndex& X = ctx->cf_index;
+    X = spsp_ctx::ClassifyIndex{};
+    if (shape.all_keys) {
+        KeyMajor km;
+        if ((rc = key_major_build(ctx, shape.has_hi, d_mn, d_lo, d_hi, h_sk_off, n_ref, kAcCut, &km))) return rc;
+        SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCfBad, km.words, 8, hipMemcpyDeviceToHost, ctx->stream));
+        SPSP_HIP(hipStreamSynchronize(ctx->stream));       // the index call's wait
+        const uint64_t flags = ctx->h_scalar[kHsCfBad];
+        if ((uint32_t)flags) { set_error("sketch keys must be strictly increasing by (minimizer, kmer_hi, kmer_lo)"); return SPSP_ERR_ARG; }
+        if (flags >> 32) { set_error("classification: a key's list could not be placed (the key arrays changed during the call?)"); return SPSP_ERR_ARG; }
+        X.key_no = km.key_no; X.key_start = km.key_start; X.list = km.list; X.entries = km.entries;
+    }
+    X.has_hi = shape.has_hi; X.n_ref = n_ref; X.first = shape.first;
+    X.mn = d_mn; X.lo = d_lo; X.hi = d_hi;
+    X.valid = true;                                        // (behind the build: the table fill in it drops whatever index there was)
+    return SPSP_OK;
+}
+
+int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
+                         uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, spsp_classify_record* records, spsp_classify_hit* hits) {
+    int rc;
+    // (what is zeroed in front of the refusals: the records' counts always, the hits once `top` says how many there are)
+    for (uint32_t r = 0; r < n_rec; ++r) records[r].keys = records[r].hit_keys = records[r].passing = records[r].listed = 0;
+    if (n_rec && top >= 1 && top <= kCfMaxTop) memset(hits, 0, (size_t)n_rec * top * sizeof(spsp_classify_hit));
+    if ((rc = classify_check_args(top, min_keys, num, den))) return rc;
+    if (n_rec > 0xfffffff0u) { set_error("too many records for one call (%u)", n_rec); return SPSP_ERR_OVERFLOW; }
+    for (uint32_t r = 0; r < n_rec; ++r)
+        if (h_rec_off[r + 1] < h_rec_off[r]) { set_error("record offsets must not decrease (record %u)", r); return SPSP_ERR_ARG; }
+    if (h_rec_off[n_rec] > 0xfffffff0ull) { set_error("too many record keys for one call"); return SPSP_ERR_OVERFLOW; }
+    const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
+    if (!X.valid) { set_error("classification: the context holds no index (spsp_classify_index_device first; a prevalence, select, accumulation or groups call replaces it)"); return SPSP_ERR_ARG; }
+    const uint64_t q0 = h_rec_off[0], all_keys = h_rec_off[n_rec] - q0;
+    if (all_keys && (!q_mn || !q_lo)) { set_error("NULL key array"); return SPSP_ERR_ARG; }
+    if (all_keys && (q_hi != nullptr) != X.has_hi) {
+        set_error("classification: the index was built %s kmer_hi (k %s 32), the records come %s it", X.has_hi ? "with" : "without", X.has_hi ? ">" : "<=",
+                  q_hi ? "with" : "without");
+        return SPSP_ERR_ARG;
+    }
+    for (uint32_t r = 0; r < n_rec; ++r) records[r].keys = (uint32_t)(h_rec_off[r + 1] - h_rec_off[r]);   // (length is the caller's)
+    if (n_rec == 0 || all_keys == 0 || X.entries == 0) return SPSP_OK;   // (no record, no record key or no reference key: nothing is shared)
+
+    const uint32_t R = X.n_ref, R_pad = (R + 3u) & ~3u;
+    const bool in_lds = R <= kCfLdsRefs;
+    const int n_cu = std::max(ctx->n_cu, 1);
+    const size_t lds = kCfLargeFixedLds + (in_lds ? (size_t)R_pad * 4 : 0);
+    const uint32_t large_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2048 / kCfLargeThreads, kAcLdsBytes / lds));
+    const uint32_t g_large = (uint32_t)std::min<uint64_t>(n_rec, (uint64_t)n_cu * (in_lds ? large_per_cu : 1u));
+    const uint32_t g_small = (uint32_t)std::min<uint64_t>(((uint64_t)n_rec + kCfWaves - 1) / kCfWaves, (uint64_t)n_cu * 8u);
+    const size_t work_bytes = (size_t)n_rec * 8, queue_bytes = 64 + (size_t)2 * n_rec * 4;
+    if ((rc = ctx->cf_off.reserve(((size_t)n_rec + 1) * 8)) || (rc = ctx->cf_kn.reserve((size_t)all_keys * 4)) ||
+        (rc = ctx->cf_work.reserve(work_bytes + (size_t)n_rec * 4)) || (rc = ctx->cf_queue.reserve(queue_bytes)) ||
+        (rc = ctx->cf_rec.reserve((size_t)n_rec * 16)) || (rc = ctx->cf_hits.reserve((size_t)n_rec * top * sizeof(spsp_classify_hit))) ||
+        (!in_lds && (rc = ctx->cf_rows.reserve((size_t)g_large * R_pad * 4)))) return rc;
+    uint64_t* d_off = ctx->cf_off.as<uint64_t>();
+    uint32_t* d_kn = ctx->cf_kn.as<uint32_t>();
+    unsigned long long* d_work = ctx->cf_work.as<unsigned long long>();
+    uint32_t* d_hit = reinterpret_cast<uint32_t*>(ctx->cf_work.as<uint8_t>() + work_bytes);
+    uint32_t* d_words = ctx->cf_queue.as<uint32_t>();
+    uint32_t* d_q_small = d_words + 16;
+    uint32_t* d_q_large = d_q_small + n_rec;
+    uint4* d_rec = ctx->cf_rec.as<uint4>();
+    spsp_classify_hit* d_hits = ctx->cf_hits.as<spsp_classify_hit>();
+    uint32_t* d_rows = in_lds ? nullptr : ctx->cf_rows.as<uint32_t>();
+    SPSP_HIP(hipMemcpyAsync(d_off, h_rec_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));   // (the caller's: alive until the wait)
+    SPSP_HIP(hipMemsetAsync(d_work, 0, work_bytes + (size_t)n_rec * 4, ctx->stream));
+    SPSP_HIP(hipMemsetAsync(d_words, 0, kCfqWords * 4, ctx->stream));
+    SPSP_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_rec * 16, ctx->stream));
+    SPSP_HIP(hipMemsetAsync(d_hits, 0, (size_t)n_rec * top * sizeof(spsp_classify_hit), ctx->stream));
+    const SortedKeys Q{q_mn, q_lo, q_hi}, K{X.mn, X.lo, X.hi};
+    const unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
+    const uint32_t gp = (uint32_t)((all_keys + kCfThreads - 1) / kCfThreads), gr = (uint32_t)(((uint64_t)n_rec + kCfThreads - 1) / kCfThreads);
+    hipEvent_t* ev = nullptr;
+    if (ctx->timing) {                                     // spsp_timing_enable: events between the launches (spsp_classify_stage_ms)
+        for (hipEvent_t& e : ctx->cf_events) if (!e) SPSP_HIP(hipEventCreate(&e));
+        ev = ctx->cf_events;
+        SPSP_HIP(hipEventRecord(ev[0], ctx->stream));
+    }
+    if (X.has_hi) hipLaunchKernelGGL(k_cf_probe<true>, dim3(gp), dim3(kCfThreads), 0, ctx->stream, Q, (const uint64_t*)d_off, n_rec, K, X.first, X.entries, d_tbl,
+                                     ctx->pv_log2cap, X.key_no, X.key_start, d_kn, d_work, d_hit);
+    else hipLaunchKernelGGL(k_cf_probe<false>, dim3(gp), dim3(kCfThreads), 0, ctx->stream, Q, (const uint64_t*)d_off, n_rec, K, X.first, X.entries, d_tbl,
+                            ctx->pv_log2cap, X.key_no, X.key_start, d_kn, d_work, d_hit);
+    if (ev) SPSP_HIP(hipEventRecord(ev[1], ctx->stream));
+    hipLaunchKernelGGL(k_cf_route, dim3(gr), dim3(kCfThreads), 0, ctx->stream, (const uint64_t*)d_off, n_rec, (const unsigned long long*)d_work,
+                       (const uint32_t*)d_hit, d_words, d_q_small, d_q_large, d_rec);
+    if (ev) SPSP_HIP(hipEventRecord(ev[2], ctx->stream));
+    hipLaunchKernelGGL(k_cf_small, dim3(g_small), dim3(kCfThreads), 0, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn, (const uint32_t*)d_hit,
+                       X.key_start, X.list, (const uint32_t*)d_q_small, d_words, top, min_keys, num, den, d_rec, d_hits);
+    if (ev) SPSP_HIP(hipEventRecord(ev[3], ctx->stream));
+    if (in_lds) {
+        if ((rc = lds_opt_in(ctx, &k_cf_large<true>, kAcLdsBytes))) return rc;
+        hipLaunchKernelGGL(k_cf_large<true>, dim3(g_large), dim3(kCfLargeThreads), lds, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn,
+                           (const uint32_t*)d_hit, X.key_start, X.list, (const uint32_t*)d_q_large, (const uint32_t*)d_words, R, R_pad, d_rows, top, min_keys,
+                           num, den, d_rec, d_hits);
+    } else {
+        hipLaunchKernelGGL(k_cf_large<false>, dim3(g_large), dim3(kCfLargeThreads), lds, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn,
+                           (const uint32_t*)d_hit, X.key_start, X.list, (const uint32_t*)d_q_large, (const uint32_t*)d_words, R, R_pad, d_rows, top, min_keys,
+                           num, den, d_rec, d_hits);
+    }
+    SPSP_HIP(hipGetLastError());
+    if (ev) SPSP_HIP(hipEventRecord(ev[4], ctx->stream));
+    std::vector<uint32_t> got((size_t)n_rec * 4);
+    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCfBad, d_words + kCfqBad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(got.data(), d_rec, got.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(hits, d_hits, (size_t)n_rec * top * sizeof(spsp_classify_hit), hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));           // the one wait
+    if (ev)
+        for (int i = 0; i < 4; ++i) { float ms = 0; SPSP_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); ctx->cf_ms[i] += ms; }
+    if ((uint32_t)ctx->h_scalar[kHsCfBad]) {
+        set_error("classification: a record's holders did not fit the form it was routed to (the key arrays changed during the call?)");
+        memset(hits, 0, (size_t)n_rec * top * sizeof(spsp_classify_hit));
+        return SPSP_ERR_ARG;
+    }
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        const uint32_t* g = got.data() + (size_t)r * 4;
+        records[r].keys = g[0]; records[r].hit_keys = g[1]; records[r].passing = g[2]; records[r].listed = g[3];
+    }
+    return SPSP_OK;
+}
+
+// the records' names as the host reads them from the text: the first whitespace-delimited word of every header line -- FASTA: the
+// lines that begin with '>'; FASTQ: every fourth line up to the content's end, which begins with '@'
+static void record_names_host(const uint8_t* text, uint64_t n, bool fastq, std::vector<std::string>* names) {
+    uint64_t end = n;
+    while (end && (text[end - 1] == '\n' || text[end - 1] == '\r')) --end;   // (FASTQ: the content without its trailing blank lines)
+    uint64_t line = 0;
+    for (uint64_t pos = 0; pos < (fastq ? end : n); ++line) {
+        uint64_t stop = pos;
+        while (stop < n && text[stop] != '\n') ++stop;
+        const bool header = fastq ? line % 4 == 0 : text[pos] == '>';
+        if (header) {
+            uint64_t a = pos < stop ? pos + 1 : pos, z = a;   // (behind the '>' or '@')
+            while (z < stop && text[z] != ' ' && text[z] != '\t' && text[z] != '\r') ++z;
+            names->emplace_back((const char*)text + a, (size_t)(z - a));
+        }
+        pos = stop + 1;
+    }
+}
+
+// seam[b] = the first super-k-mer of the stream (which is in record order) whose record is want[b] or behind it
+__global__ void k_cf_seams(const spsp_superkmer* __restrict__ sk, uint64_t n_sk, const uint32_t* __restrict__ want, uint32_t n, uint64_t* __restrict__ seam) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    const uint32_t w = want[b];
+    uint64_t lo = 0, hi = n_sk;
+    while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (sk[mid].rec < w) lo = mid + 1; else hi = mid; }
+    seam[b] = lo;
+}
+
+// every batch's stretch of the super-k-mer stream: batch b = records [want[b], want[b + 1]) -> super-k-mers [seam[b], seam[b + 1]).  One launch, one wait
+static int batch_seams(spsp_ctx* ctx, const spsp_superkmer* d_sk, uint64_t n_sk, const std::vector<uint32_t>& want, std::vector<uint64_t>* seam) {
+    int rc;
+    const uint32_t n = (uint32_t)want.size();
+    seam->assign(n, 0);
+    if ((rc = ctx->cf_off.reserve((size_t)n * 12 + 64))) return rc;
+    uint64_t* d_seam = ctx->cf_off.as<uint64_t>();
+    uint32_t* d_want = reinterpret_cast<uint32_t*>(d_seam + n);
+    SPSP_HIP(hipMemcpyAsync(d_want, want.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_cf_seams, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_sk, n_sk, (const uint32_t*)d_want, n, d_seam);
+    SPSP_HIP(hipGetLastError());
+    SPSP_HIP(hipMemcpyAsync(seam->data(), d_seam, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));
+    return SPSP_OK;
+}
+
+// the records of a text, ingested and scanned once on `side` (a second context of ctx's device), their keys extracted batch by batch
+// there and classified against the index on ctx
+static int classify_text(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path, uint32_t top,
+                         uint32_t min_keys, uint32_t num, uint32_t den, std::vector<std::string>* names, std::vector<spsp_classify_record>* recs,
+                         std::vector<spsp_classify_hit>* hits) {
+    int rc;
+    double t0 = now_s(), t1;
+    const bool fastq = n_text && text[0] == '@';
+    record_names_host(text, n_text, fastq, names);
+    if ((rc = side->i_text.reserve((size_t)n_text + 64))) return rc;
+    if (n_text) SPSP_HIP(hipMemcpyAsync(side->i_text.p, text, (size_t)n_text, hipMemcpyHostToDevice, side->stream));
+    uint8_t* d_bases = nullptr; uint64_t* d_off = nullptr; uint64_t n_bases = 0; uint32_t n_rec = 0;
+    const bool packed = ingest_packs(p);
+    FastqLayout fq;
+    if (fastq) fastq_tail(text, n_text, &fq.content_end, &fq.blank_tail);
+    if ((rc = clean_device_impl(side, side->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed, fastq ? &fq : nullptr))) return rc;
+    t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
+    if (names->size() != n_rec) {
+        set_error("'%s': %zu header line(s) on the host, %u record(s) on the device", path, names->size(), n_rec);
+        return SPSP_ERR_FORMAT;
+    }
+    spsp_superkmer* d_sk = nullptr; uint64_t n_sk = 0;
+    spsp_params ps = *p;
+    if (packed) ps.flags |= SPSP_SCAN_PACKED_INPUT;
+    if ((rc = scan_device_impl(side, &ps, d_bases, n_bases, d_off, n_rec, &d_sk, &n_sk))) return rc;
+    t1 = now_s(); ctx->stages.scan_s += t1 - t0; t0 = t1;
+    std::vector<uint64_t> rec_off((size_t)n_rec + 1, 0);
+    SPSP_HIP(hipMemcpyAsync(rec_off.data(), d_off, rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));
+    SPSP_HIP(hipStreamSynchronize(side->stream));
+    recs->assign(n_rec, spsp_classify_record{});
+    hits->assign((size_t)n_rec * top, spsp_classify_hit{});
+    for (uint32_t r = 0; r < n_rec; ++r) (*recs)[r].length = rec_off[r + 1] - rec_off[r];
+    std::vector<uint32_t> first_rec, bounds;
+    std::vector<uint64_t> key_off, seam;
+    for (uint64_t r = 0; r < n_rec; r += 65535u) bounds.push_back((uint32_t)r);
+    bounds.push_back(n_rec);
+    // (the extraction takes any record range of the scan: it looks its genomes' super-k-mers up by record number.  It gets the
+    // batch's own stretch of the stream all the same, so that a batch costs its records and not the file's)
+    if (n_rec && (rc = batch_seams(side, d_sk, n_sk, bounds, &seam))) return rc;
+    for (size_t b = 0; b + 1 < bounds.size(); ++b) {
+        const uint32_t r0 = bounds[b], batch = bounds[b + 1] - r0;
+        const uint64_t q0 = seam[b], q1 = seam[b + 1];
+        first_rec.resize((size_t)batch + 1);
+        for (uint32_t g = 0; g <= batch; ++g) first_rec[g] = r0 + g;
+        key_off.assign((size_t)batch + 1, 0);
+        void *k_mn = nullptr, *k_lo = nullptr, *k_hi = nullptr;
+        if ((rc = spsp_wait_stream(side, ctx)) ||          // (the last batch's keys have been read)
+            (rc = spsp_sketch_keys_device(side, &ps, d_bases, n_bases, d_off, d_sk + q0, q1 - q0, first_rec.data(), batch, 0, &k_mn, &k_lo, &k_hi,
+                                          key_off.data())) ||
+            (rc = spsp_wait_stream(ctx, side)) ||
+            (rc = classify_device_impl(ctx, (const uint32_t*)k_mn, (const uint64_t*)k_lo, (const uint64_t*)k_hi, key_off.data(), batch, top, min_keys, num, den,
+                                       recs->data() + r0, hits->data() + (size_t)r0 * top))) return rc;
+    }
+    return SPSP_OK;
+}
+
+// spsp_classify_files behind its argument checks
+static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys, uint32_t num,
+                          uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_classify_record>* recs,
+                          std::vector<spsp_classify_hit>* hits) {
+    FilesRun run(ctx, paths, n_ref, chatter);
+    int rc = run.load(rate);
+    if (!rc) rc = run.refuse_k_eq_m(rc, "classification is");
+    double rec_rate = run.L.ds_rate;                       // the records are scanned at ONE threshold: mixed rates need a rate, as -S
+    if (!rc) rc = sketches_out_rate(run.L, paths, n_ref, &rec_rate);
+    if ((rc = run.begin(rc))) return rc;
+    const DecodedKeys& keys = run.keys;
+    rc = run.decode();
+    if (!rc) rc = classify_index_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n_ref);
+    std::vector<std::string> names;
+    if (!rc) {
+        uint8_t* text = nullptr; uint64_t n_text = 0;
+        spsp_ctx* side = nullptr;
+        spsp_params p{};
+        p.k = keys.k; p.m = keys.m; p.threshold = spsp_threshold_host(keys.k, keys.m, rec_rate); p.abundance = 1; p.flags = 0;
+        if (!(rc = spsp_read_file_host(records_path, &text, &n_text)) && !(rc = spsp_create(ctx->device, nullptr, &side)))
+            rc = classify_text(ctx, side, &p, text, n_text, records_path, top, min_keys, num, den, &names, recs, hits);
+        if (side) { (void)hipStreamSynchronize(side->stream); spsp_destroy(side); }
+        spsp_free(text);
+    }
+    const double t1 = run.end();
+    if (rc) return rc;
+    std::vector<const char*> name_ptr(names.size());
+    for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
+    char* text = nullptr; uint64_t len = 0;
+    if ((rc = spsp_classify_csv_host(recs->data(), hits->data(), recs->size(), name_ptr.data(), paths, n_ref, top, precision, &text, &len))) return rc;
+    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify.csv.gz", t1))) return rc;
+    const double t2 = now_s();
+    if ((rc = spsp_classify_summary_csv_host(recs->data(), hits->data(), recs->size(), paths, n_ref, top, &text, &len))) return rc;
+    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify_summary.csv.gz", t2)) || !chatter) return rc;
+    uint64_t with = 0;
+    for (const spsp_classify_record& r : *recs) with += r.listed != 0;
+    printf("%zu record(s) against %u reference(s): %llu with a match\n", recs->size(), n_ref, (unsigned long long)with);
+    say_common_rate(run.L, n_ref);
+    fflush(stdout);
+    return SPSP_OK;
+}
+
+}  // namespace spsp
+
+using namespace spsp;
+
+extern "C" int spsp_classify_index_device(spsp_ctx* ctx, uint32_t k, const void* d_minimizer, const void* d_kmer_lo, const void* d_kmer_hi,
+                                          const uint64_t* h_sk_off, uint32_t n_ref) {
+    if (!ctx || !h_sk_off) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    SPSP_HIP(hipSetDevice(ctx->device));
+    return classify_index_impl(ctx, k, (const uint32_t*)d_minimizer, (const uint64_t*)d_kmer_lo, (const uint64_t*)d_kmer_hi, h_sk_off, n_ref);
+}
+
+extern "C" int spsp_classify_device(spsp_ctx* ctx, const void* d_q_minimizer, const void* d_q_kmer_lo, const void* d_q_kmer_hi, const uint64_t* h_rec_off,
+                                    uint32_t n_records, uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, spsp_classify_record* records,
+                                    spsp_classify_hit* hits) {
+    if (!ctx || !h_rec_off || (n_records && (!records || !hits))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    SPSP_HIP(hipSetDevice(ctx->device));
+    return classify_device_impl(ctx, (const uint32_t*)d_q_minimizer, (const uint64_t*)d_q_kmer_lo, (const uint64_t*)d_q_kmer_hi, h_rec_off, n_records, top,
+                                min_keys, num, den, records, hits);
+}
+
+extern "C" int spsp_classify_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                   uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                   spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records) {
+    if (records) *records = nullptr;
+    if (hits) *hits = nullptr;
+    if (n_records) *n_records = 0;
+    if (!ctx || !index_paths || !records_path || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    int rc;
+    if ((rc = classify_check_args(top, min_keys, num, den))) return rc;
+    SPSP_HIP(hipSetDevice(ctx->device));
+    std::vector<spsp_classify_record> got;
+    std::vector<spsp_classify_hit> got_hits;
+    if ((rc = classify_files(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, &got, &got_hits))) return rc;
+    if (n_records) *n_records = got.size();
+    if (records && (rc = give_rows(got, records))) return rc;
+    if (hits && (rc = give_rows(got_hits, hits))) { if (records) { free(*records); *records = nullptr; } return rc; }
+    return SPSP_OK;
+}
+
+extern "C" int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms) {
+    if (!ctx || !ms) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    for (int i = 0; i < 4; ++i) { ms[i] = ctx->cf_ms[i]; ctx->cf_ms[i] = 0; }
+    return SPSP_OK;
+}

@@ -1849,6 +1849,14 @@ int write_key_sketches(uint32_t k, uint32_t m, double rate, const HostKeys& keys
     if (!f || fwrite(list.data(), 1, list.size(), f) != list.size() || fclose(f) != 0) { set_error("cannot write '%s'", list_path); return SPSP_ERR_IO; }
     return SPSP_OK;
 }
+
+// spsp_classify.hip: what a classification call and the file driver refuse before anything else
+int classify_check_args(uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den) {
+    if (top == 0 || top > kCfMaxTop) { set_error("classification lists 1 .. %u matches per record (top = %u)", kCfMaxTop, top); return SPSP_ERR_ARG; }
+    if (min_keys == 0) { set_error("classification: min_keys is 1 at the least"); return SPSP_ERR_ARG; }
+    if (den == 0 || num > den || den > kCfMaxDen) { set_error("classification threshold %u / %u: needs 0 <= num <= den, 1 <= den <= %u", num, den, kCfMaxDen); return SPSP_ERR_ARG; }
+    return SPSP_OK;
+}
 }  // namespace spsp
 
 namespace {
@@ -2298,6 +2306,91 @@ int spsp_groups_members_csv_host(const spsp_group_member_row* members, uint32_t 
         out.append(num, format_g(num, sizeof num, precision, keys ? (double)r.core / (double)keys : 0.0)); out += ',';
         out.append(num, format_g(num, sizeof num, precision, g.marker ? (double)r.marker / (double)g.marker : 0.0)); out += '\n';
     }
+    return text_out(out, text, len);
+}
+
+// ------------------------------------------------------------------------------------------------ classification
+// what routes a record of spsp_classify.hip from one form to the other: the constants of spsp_internal.h
+int spsp_classify_plan_host(uint32_t n_ref, uint32_t top, uint32_t* small_work, uint32_t* lds_refs, uint32_t* counters_in_lds, uint32_t* list_cut) {
+    using namespace spsp;
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    if (top == 0 || top > kCfMaxTop) { set_error("classification lists 1 .. %u matches per record (top = %u)", kCfMaxTop, top); return SPSP_ERR_ARG; }
+    if (small_work) *small_work = kCfSmallWork;
+    if (lds_refs) *lds_refs = kCfLdsRefs;
+    if (counters_in_lds) *counters_in_lds = n_ref <= kCfLdsRefs ? 1u : 0u;
+    if (list_cut) *list_cut = kCfListCut;
+    return SPSP_OK;
+}
+
+// a record's row and matches that cannot be a classification's: why, or null
+static const char* classify_row_wrong(const spsp_classify_record& r, const spsp_classify_hit* h, uint32_t n_ref, uint32_t top) {
+    if (r.listed > top || r.listed > r.passing) return "more matches listed than min(top, passing)";
+    if (r.hit_keys > r.keys) return "more hit keys than keys";
+    for (uint32_t i = 0; i < r.listed; ++i) {
+        if (h[i].reference >= n_ref) return "a match names a reference outside the index";
+        if (h[i].shared > r.hit_keys) return "a match shares more keys than the record has hit keys";
+        if (h[i].shared == 0) return "a listed match shares no key";
+        if (i && (h[i].shared > h[i - 1].shared || (h[i].shared == h[i - 1].shared && h[i].reference <= h[i - 1].reference))) return "matches out of order";
+    }
+    return nullptr;
+}
+
+static int classify_csv_args(const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records, const char* const* ref_names, uint32_t n_ref,
+                             uint32_t top, char** text, uint64_t* len) {
+    if (!text || !len || !ref_names || (n_records && (!records || !hits))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    if (top == 0 || top > spsp::kCfMaxTop) { set_error("classification lists 1 .. %u matches per record (top = %u)", spsp::kCfMaxTop, top); return SPSP_ERR_ARG; }
+    return SPSP_OK;
+}
+
+int spsp_classify_csv_host(const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records, const char* const* record_names,
+                           const char* const* ref_names, uint32_t n_ref, uint32_t top, int precision, char** text, uint64_t* len) {
+    if (const int rc = classify_csv_args(records, hits, n_records, ref_names, n_ref, top, text, len)) return rc;
+    if (n_records && !record_names) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    std::string out = "record,name,length,keys,hit_keys,rank,match,shared,f_shared,passing\n";
+    char num[64];
+    for (uint64_t r = 0; r < n_records; ++r) {
+        const spsp_classify_record& rec = records[r];
+        const spsp_classify_hit* h = hits + r * top;
+        if (const char* why = classify_row_wrong(rec, h, n_ref, top)) { set_error("classification record %llu contradicts itself: %s", (unsigned long long)r, why); return SPSP_ERR_ARG; }
+        const std::string front = std::to_string(r) + ',' + record_names[r] + ',' + std::to_string(rec.length) + ',' + std::to_string(rec.keys) + ',' +
+                                  std::to_string(rec.hit_keys) + ',';
+        const std::string back = ',' + std::to_string(rec.passing) + '\n';
+        if (rec.listed == 0) { out += front; out += "0,,0,0"; out += back; continue; }
+        for (uint32_t i = 0; i < rec.listed; ++i) {
+            out += front;
+            out += std::to_string(i + 1); out += ',';
+            out += ref_names[h[i].reference]; out += ',';
+            out += std::to_string(h[i].shared); out += ',';
+            out.append(num, format_g(num, sizeof num, precision, rec.keys ? (double)h[i].shared / (double)rec.keys : 0.0));
+            out += back;
+        }
+    }
+    return text_out(out, text, len);
+}
+
+int spsp_classify_summary_csv_host(const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records, const char* const* ref_names,
+                                   uint32_t n_ref, uint32_t top, char** text, uint64_t* len) {
+    if (const int rc = classify_csv_args(records, hits, n_records, ref_names, n_ref, top, text, len)) return rc;
+    std::vector<uint64_t> best(n_ref, 0), bases(n_ref, 0), keys(n_ref, 0), listed(n_ref, 0);
+    uint64_t none = 0, none_bases = 0;
+    for (uint64_t r = 0; r < n_records; ++r) {
+        const spsp_classify_record& rec = records[r];
+        const spsp_classify_hit* h = hits + r * top;
+        if (const char* why = classify_row_wrong(rec, h, n_ref, top)) { set_error("classification record %llu contradicts itself: %s", (unsigned long long)r, why); return SPSP_ERR_ARG; }
+        if (rec.listed == 0) { ++none; none_bases += rec.length; continue; }
+        ++best[h[0].reference]; bases[h[0].reference] += rec.length; keys[h[0].reference] += h[0].shared;
+        for (uint32_t i = 0; i < rec.listed; ++i) ++listed[h[i].reference];
+    }
+    std::string out = "reference,records_best,bases_best,keys_best,records_listed\n";
+    for (uint32_t j = 0; j < n_ref; ++j) {
+        out += ref_names[j]; out += ',';
+        out += std::to_string(best[j]); out += ',';
+        out += std::to_string(bases[j]); out += ',';
+        out += std::to_string(keys[j]); out += ',';
+        out += std::to_string(listed[j]); out += '\n';
+    }
+    out += "unclassified," + std::to_string(none) + ',' + std::to_string(none_bases) + ",0,0\n";
     return text_out(out, text, len);
 }
 

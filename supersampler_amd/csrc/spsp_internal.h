@@ -138,7 +138,10 @@ enum HostSlot {
                             // the table << 32); groups_device_impl reads it behind its first wait
     kHsGpCell = 35,         // ... of the cell table's word (u32: a probe sequence that went round it, or an entry without its cell), in the same wait
     kHsGpTotal = 36,        // ... and launch_scan_u32's total over the tiles' survivor counts: the marker keys of all groups (u64), in the same wait
-    kHostSlots = 37
+    kHsCfBad = 37,          // spsp_classify.hip: the copy of two u32 (the index build's keys out of order | a probe sequence that went round
+                            // the table or a list place out of range << 32) behind the index call's wait; behind a classify call's one
+                            // wait the copy of its own word (u32: a record routed to a form its work does not fit)
+    kHostSlots = 38
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
@@ -148,7 +151,8 @@ static_assert(kHsRpCount == kHsRpUndecided + 3 && kHsRpCount + 1 == kHsTrEdges, 
 static_assert(kHsTrRounds == kHsTrEdges + 2 && kHsTrRounds + 1 == kHsSelBad, "the linkage tree's three slots");
 static_assert(kHsSelTotal == kHsSelBad + 1 && kHsSelTotal + 1 == kHsAcBad, "the selection's two slots");
 static_assert(kHsAcBad + 1 == kHsGpBad, "the accumulation's one slot");
-static_assert(kHsGpCell == kHsGpBad + 1 && kHsGpTotal == kHsGpBad + 2 && kHsGpTotal + 1 == kHostSlots, "the groups pass's three slots: the last ones");
+static_assert(kHsGpCell == kHsGpBad + 1 && kHsGpTotal == kHsGpBad + 2 && kHsGpTotal + 1 == kHsCfBad, "the groups pass's three slots");
+static_assert(kHsCfBad + 1 == kHostSlots, "the classification's one slot: the last one");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -289,6 +293,23 @@ struct spsp_ctx {
     // groups' bounds, the per-sketch records, keep mask, offsets, tile counts, destinations), the marker keys, and the compaction's
     // output, which is the sort's scratch afterwards
     spsp::DevBuf gp_table, gp_cell, gp_work, gp_mn, gp_lo, gp_hi, gp_t_mn, gp_t_lo, gp_t_hi;
+    // classification (spsp_classify.hip).  The index IS the prevalence table (pv_table, its counters spent as cursors) and the
+    // accumulation's key-major form (ac_work: key_no per entry; ac_keys: key_start; ac_list) over the caller's reference arrays:
+    // whatever fills that table again (prevalence_fill_table) drops it.  Per call: record offsets, key number + 1 per record key,
+    // work and hit keys per record, the two queues with their counters and the flag word, the records' four words, the hits, and
+    // the counter rows of the large form where they do not fit the LDS
+    struct ClassifyIndex {
+        bool valid = false, has_hi = false;
+        uint32_t n_ref = 0, entries = 0;
+        uint64_t first = 0;
+        const uint32_t* mn = nullptr;
+        const uint64_t *lo = nullptr, *hi = nullptr;
+        const uint32_t *key_no = nullptr, *key_start = nullptr;
+        const uint16_t* list = nullptr;
+    } cf_index;
+    spsp::DevBuf cf_off, cf_kn, cf_work, cf_queue, cf_rec, cf_hits, cf_rows;
+    hipEvent_t cf_events[5] = {};        // while timing is on: in front of the probe, the route, the small form, the large form, and behind it
+    double cf_ms[4] = {};                // ... their milliseconds added up since spsp_classify_stage_ms last read them
 };
 
 namespace spsp {
@@ -458,6 +479,28 @@ constexpr uint32_t kAcCut = 64;                            // a list of more hol
 int accumulation_check_args(uint32_t n, uint32_t n_orders);
 int accumulation_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
                              uint32_t n, const uint32_t* orders, uint32_t n_orders, spsp_accumulation_row* rows, uint64_t* pan, uint64_t* core);
+// the key-major form of a collection, which the accumulation and the classification's index share (spsp_accumulation.hip): the
+// table fill with claimers (prevalence_fill_table, all versus all), k_ac_prep, the two scans and k_ac_scatter, queued on the
+// context's stream without a host wait.  words: the flag words (keys out of order | a probe sequence that went round or a list
+// place out of range | the long lists queued); key_no[i]: the number of entry (first + i)'s key where that entry claimed the slot
+// (the scan's value in front of it otherwise), key_no[E] = D, the distinct keys; key_start[0 .. D]; list: the holders' sketch
+// numbers, list behind list; long_keys: the numbers of the keys with more than `cut` holders.  Behind it the table's counters are
+// zero: a slot's low half still names the claimer.  The caller has been through sorted_keys_front and has at least one key
+struct KeyMajor { uint32_t* words; const uint32_t* key_no; const uint32_t* key_start; const uint16_t* list; const uint32_t* long_keys; uint32_t entries; };
+int key_major_build(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,
+                    uint32_t cut, KeyMajor* out);
+// spsp_classify.hip: the records of a batch against an index.  What routes a record (spsp_classify_plan_host, spsp_host.cpp):
+constexpr uint32_t kCfThreads = 256;                       // probe, route, small form: 4 waves
+constexpr uint32_t kCfSmallWork = 1024;                    // holders one wave of the small form sorts in LDS: a record of more work goes to a workgroup
+constexpr uint32_t kCfLargeThreads = 512;                  // the large form: 8 waves per record
+constexpr uint32_t kCfLargeFixedLds = 8 * 64 * 8 + 64;     // ... its LDS beside the counters: the waves' kept matches and the passing count
+constexpr uint32_t kCfLdsRefs = (kAcLdsBytes - 8192) / 4;  // 38 912: up to this many references the large form's counters stay in LDS
+constexpr uint32_t kCfListCut = 32;                        // the large form: a list of more holders than this is walked by the whole wave
+constexpr uint32_t kCfMaxTop = 64, kCfMaxDen = 1000000;
+int classify_check_args(uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den);
+int classify_index_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n_ref);
+int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
+                         uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, spsp_classify_record* records, spsp_classify_hit* hits);
 // spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
 // groups as n_groups sketches back to back in context-owned arrays
 int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,

@@ -196,6 +196,7 @@ uint32_t pv_table_log2cap(uint64_t entries) {
 int prevalence_fill_table(spsp_ctx* ctx, bool has_hi, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off,
                           uint32_t n, uint32_t nq, bool claim, uint32_t* d_words) {
     int rc;
+    ctx->cf_index.valid = false;                           // (a classification index is this table: it ends here)
     const uint64_t extent = h_sk_off[n], all_keys = h_sk_off[n] - h_sk_off[0], ref_keys = h_sk_off[n] - h_sk_off[nq];
     const uint32_t log2cap = ctx->pv_log2cap = pv_table_log2cap(ref_keys);   // (the table's size follows from the reference entries alone)
     const uint64_t cap = 1ull << log2cap;
