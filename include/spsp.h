@@ -1164,6 +1164,69 @@ int spsp_classify_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t 
                         spsp_classify_record** records /* may be NULL; spsp_free */, spsp_classify_hit** hits /* may be NULL; spsp_free */,
                         uint64_t* n_records /* may be NULL */);
 
+/* --------------------------------------------------------------- depth ---- */
+/* How deep a read set covers each reference of an index (not in the reference): the one pass of the library that counts.
+ * INDEX: what spsp_classify_index_device built on the context -- references 0 .. R-1 with key sets K_j, U their union, D = |U|,
+ * h(x) = the references that hold key x.  The READ SET is a sequence of records r with distinct key sets Q_r, the Q_r of classify.
+ *   c(x) = #{r : x in Q_r} for x in U: the records that hold x.
+ * A key is FOUND at min_count >= 1 when c(x) >= min_count (2 drops the keys only a sequencing error produced).  For reference j,
+ * F_j = {x in K_j : found}:  keys = |K_j|, found = |F_j|, sum = the sum of c over F_j (64 bits), max = the largest c in F_j,
+ * median = the LOWER median of c over F_j: with the values ascending s_0 <= ... <= s_(found-1) it is s_floor((found-1)/2).
+ * sum, max and median are 0 when found == 0.  The unique_ fields are the same five over the reference's UNIQUE keys
+ * {x in K_j : h(x) == 1}: a key two strains share says nothing about which of them is in the sample.
+ * Totals: record_keys = the sum of |Q_r|, hit_keys = the sum of c(x) over U, index_keys = D, index_found = #{x in U : found}.
+ * Integers only: the answer is a function of the multiset of record keys, whatever the batch cuts, key order or arrival order. */
+typedef struct spsp_depth_row {     /* 48 bytes, one per reference */
+    uint64_t sum, unique_sum;
+    uint32_t keys, found, median, max, unique_keys, unique_found, unique_median, unique_max;
+} spsp_depth_row;
+typedef struct spsp_depth_totals { uint64_t record_keys, hit_keys; uint32_t index_keys, index_found; } spsp_depth_totals;   /* 24 bytes */
+/* Makes one 32-bit counter per distinct key of the context's index, cleared, and clears the running totals; also numbers every
+ * index entry's key once (one probe per entry; one host wait, for D).  The counters belong to the index: whatever replaces or drops
+ * the index (a prevalence, select, accumulation, groups or index call) ends them, and spsp_depth_add_device / _read_device are
+ * SPSP_ERR_ARG until the next begin.  SPSP_ERR_ARG: no index on the context. */
+int spsp_depth_begin_device(spsp_ctx* ctx);
+/* Adds the keys of any number of WHOLE records: entries [first, first + n_keys) of arrays of the caller's on the device, distinct
+ * per record (the caller vouches for it, as in spsp_classify_device) and otherwise in any order; no record offsets are needed.
+ * One launch, a lane per record key: the probe of classify's probe pass, and on a hit one atomic add to the key's counter.  It
+ * only QUEUES on the context's stream: no host wait; the arrays must stay until the stream has passed the launch.  Checked before
+ * anything is queued -- SPSP_ERR_ARG: no counters on the context, d_q_kmer_hi given for an index of k <= 32 or missing for one of
+ * k > 32; SPSP_ERR_OVERFLOW: n_keys > 0xfffffff0, or the record keys since begin (kept on the host in 64 bits) would pass
+ * 0xffffffff -- then nothing is added, which keeps every counter from wrapping.  n_keys == 0 or an index without keys: SPSP_OK. */
+int spsp_depth_add_device(spsp_ctx* ctx, const void* d_q_minimizer, const void* d_q_kmer_lo, const void* d_q_kmer_hi /* NULL if k <= 32 */,
+                          uint64_t first, uint64_t n_keys);
+/* The rows (n_ref, as the index has them) and the totals at min_count, with one host wait.  It does not consume the counters: it
+ * may be called again, with another min_count, or between adds.  *d_entry_count (may be NULL) receives the device address of a
+ * context-owned uint32 array parallel to the index's key arrays (entry e of the index at [e - h_sk_off[0]]): c of that entry's key,
+ * valid until the next read, begin or index call.  Launches: a lane per index entry, then a workgroup per reference with two
+ * histograms in LDS (spsp_depth_plan_host); a reference of more than 65 536 keys is reduced by segments, a workgroup each, and
+ * merged.  SPSP_ERR_ARG: no counters on the context, min_count == 0. */
+int spsp_depth_read_device(spsp_ctx* ctx, uint32_t min_count, spsp_depth_row* rows /* n_ref */, spsp_depth_totals* totals /* may be NULL */,
+                           const void** d_entry_count /* may be NULL */);
+/* *bins = the bins of one LDS histogram of the reduction: bin b < bins - 1 holds c == b, the last every c >= bins - 1; a median whose
+ * rank lands in the last bin is resolved exactly by a radix select (four passes of 256 bins). */
+int spsp_depth_plan_host(uint32_t* bins);
+/* While the context's timing is on (spsp_timing_enable, any kind) the depth calls record events around their launches; this reads
+ * the milliseconds added up since the last read and clears them (it waits for the stream where adds are outstanding): ms[0] the
+ * adds, ms[1] the entry pass, ms[2] the reduction. */
+int spsp_depth_stage_ms(spsp_ctx* ctx, double* ms /* 3: add, entry, reduce */);
+/* The text of <prefix>_depth.csv.gz:
+ * "reference,keys,found,f_found,median,mean,max,unique_keys,unique_found,f_unique_found,unique_median,unique_mean,unique_max" and
+ * one line per reference; f_found = found / keys, mean = sum / found (and their unique_ forms) as %.<precision>g, 0 where the
+ * denominator is 0: they decide nothing.  Rows that contradict themselves are SPSP_ERR_ARG, the message naming the reference:
+ * found > keys, unique_keys > keys, unique_found > min(found, unique_keys), median > max, max > sum, found == 0 with a non-zero
+ * sum, max or median, found > 0 with median == 0, sum < found or sum > found * max, the same for the unique five, unique_sum > sum.
+ * *text is released with spsp_free(). */
+int spsp_depth_csv_host(const spsp_depth_row* rows, const char* const* names, uint32_t n_ref, int precision, char** text, uint64_t* len);
+/* The whole-file driver.  index_paths: n_ref sketch files, loaded exactly as spsp_classify_files loads them (the same `rate` rule,
+ * k == m and mixed rates without a rate refused).  reads_paths: n_reads >= 1 FASTA or FASTQ files (R1 / R2, lanes), gzip or plain,
+ * which go one after the other through the records path of spsp_classify_files; every batch's keys go to spsp_depth_add_device,
+ * then there is one read.  Writes <out_prefix>_depth.csv.gz (gzip level 1) and no matrices; nothing on any failure.  rows (may be
+ * NULL) receives a copy released with spsp_free(); totals may be NULL. */
+int spsp_depth_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* const* reads_paths, uint32_t n_reads, uint32_t min_count,
+                     int precision, const char* out_prefix, int chatter, double rate, spsp_depth_row** rows /* may be NULL; spsp_free */,
+                     spsp_depth_totals* totals /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,11 @@ GROUP_MEMBER_ROW_DTYPE = np.dtype([("core", "<u8"), ("exclusive", "<u8"), ("mark
 CLASSIFY_RECORD_DTYPE = np.dtype([("length", "<u8"), ("keys", "<u4"), ("hit_keys", "<u4"), ("passing", "<u4"), ("listed", "<u4")])
 CLASSIFY_HIT_DTYPE = np.dtype([("reference", "<u4"), ("shared", "<u4")])
 
+# spsp_depth_row / spsp_depth_totals: a reference's depth statistics, and the read set's totals (include/spsp.h)
+DEPTH_ROW_DTYPE = np.dtype([("sum", "<u8"), ("unique_sum", "<u8"), ("keys", "<u4"), ("found", "<u4"), ("median", "<u4"), ("max", "<u4"),
+                            ("unique_keys", "<u4"), ("unique_found", "<u4"), ("unique_median", "<u4"), ("unique_max", "<u4")])
+DEPTH_TOTALS_DTYPE = np.dtype([("record_keys", "<u8"), ("hit_keys", "<u8"), ("index_keys", "<u4"), ("index_found", "<u4")])
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -145,6 +150,7 @@ ABI_SYMBOLS = [
     "spsp_accumulation_orders_host", "spsp_accumulation_plan_host", "spsp_accumulation_device", "spsp_accumulation_csv_host", "spsp_accumulation_files",
     "spsp_groups_labels_host", "spsp_groups_bounds_host", "spsp_groups_device", "spsp_groups_csv_host", "spsp_groups_members_csv_host", "spsp_groups_files",
     "spsp_classify_index_device", "spsp_classify_device", "spsp_classify_plan_host", "spsp_classify_csv_host", "spsp_classify_summary_csv_host", "spsp_classify_files", "spsp_classify_stage_ms",
+    "spsp_depth_begin_device", "spsp_depth_add_device", "spsp_depth_read_device", "spsp_depth_plan_host", "spsp_depth_stage_ms", "spsp_depth_csv_host", "spsp_depth_files",
 ]
 
 _lib = None
@@ -364,6 +370,21 @@ def lib():
         L.spsp_classify_stage_ms.argtypes = [vp, P(dbl)]
         L.spsp_classify_files.restype = i32
         L.spsp_classify_files.argtypes = [vp, P(cp), u32, cp, u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(vp), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_depth_read_device"):
+        L.spsp_depth_begin_device.restype = i32
+        L.spsp_depth_begin_device.argtypes = [vp]
+        L.spsp_depth_add_device.restype = i32
+        L.spsp_depth_add_device.argtypes = [vp, vp, vp, vp, u64, u64]
+        L.spsp_depth_read_device.restype = i32
+        L.spsp_depth_read_device.argtypes = [vp, u32, vp, vp, P(vp)]
+        L.spsp_depth_plan_host.restype = i32
+        L.spsp_depth_plan_host.argtypes = [P(u32)]
+        L.spsp_depth_stage_ms.restype = i32
+        L.spsp_depth_stage_ms.argtypes = [vp, P(dbl)]
+        L.spsp_depth_csv_host.restype = i32
+        L.spsp_depth_csv_host.argtypes = [vp, P(cp), u32, i32, P(vp), P(u64)]
+        L.spsp_depth_files.restype = i32
+        L.spsp_depth_files.argtypes = [vp, P(cp), u32, P(cp), u32, u32, i32, cp, i32, dbl, P(vp), vp]
     _lib = L
     return L
 
@@ -675,6 +696,24 @@ def classify_plan(n_ref, top=1):
     a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
     _check(lib().spsp_classify_plan_host(n_ref, top, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
     return {"small_work": a.value, "lds_refs": b.value, "counters_in_lds": bool(c.value), "list_cut": d.value}
+
+
+def depth_plan():
+    """spsp_depth_plan_host: the bins of one LDS histogram of the depth reduction; the last bin holds every count at or above bins - 1"""
+    bins = C.c_uint32()
+    _check(lib().spsp_depth_plan_host(C.byref(bins)))
+    return bins.value
+
+
+def depth_csv(rows, names, precision=6):
+    """spsp_depth_csv_host: rows (DEPTH_ROW_DTYPE, one per reference) and the references' names -> the text of <prefix>_depth.csv.gz"""
+    rows = np.ascontiguousarray(rows, dtype=DEPTH_ROW_DTYPE)
+    if len(names) != len(rows):
+        raise ValueError("depth_csv: one name per row")
+    arr, _alive = _paths_array(names)
+    text, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_depth_csv_host(rows.ctypes.data if len(rows) else None, arr, len(rows), precision, C.byref(text), C.byref(n)))
+    return _take(text, n.value)
 
 
 def _classify_rows(records, hits, top):
@@ -1436,7 +1475,9 @@ class Context:
         sk_off = np.ascontiguousarray(sk_off, dtype=np.uint64)
         if len(sk_off) != n_ref + 1:
             raise ValueError("classify_index_device: n_ref + 1 sketch offsets")
+        self._cf_n_ref = None
         _check(lib().spsp_classify_index_device(self._h, k, d_min, d_lo, d_hi, sk_off.ctypes.data, n_ref))
+        self._cf_n_ref = n_ref
 
     def classify_device(self, d_min, d_lo, d_hi, rec_off, top=1, min_keys=1, num=0, den=1):
         """spsp_classify_device: the records whose distinct keys sit at [rec_off[r], rec_off[r + 1]) of key arrays on the device,
@@ -1463,10 +1504,52 @@ class Context:
         rate, or "auto"); sketches of different rates need one"""
         arr, _alive = _paths_array(paths)
         recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._cf_n_ref = None
         _check(lib().spsp_classify_files(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
                                          _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n)))
         return (np.frombuffer(_take(recs, n.value * CLASSIFY_RECORD_DTYPE.itemsize), dtype=CLASSIFY_RECORD_DTYPE).copy(),
                 np.frombuffer(_take(hits, n.value * top * CLASSIFY_HIT_DTYPE.itemsize), dtype=CLASSIFY_HIT_DTYPE).copy().reshape(n.value, top))
+
+    def depth_begin(self):
+        """spsp_depth_begin_device: one cleared counter per distinct key of the context's index (classify_index_device); they end
+        with that index"""
+        _check(lib().spsp_depth_begin_device(self._h))
+
+    def depth_add(self, d_min, d_lo, d_hi, first, n_keys):
+        """spsp_depth_add_device: the keys of whole records (distinct per record, any order) at entries [first, first + n_keys) of
+        key arrays on the device, counted into the index's counters.  Only queues: the arrays must stay until the next read"""
+        _check(lib().spsp_depth_add_device(self._h, d_min, d_lo, d_hi, first, n_keys))
+
+    def depth_read(self, min_count=1, want_counts=False):
+        """spsp_depth_read_device: -> (rows DEPTH_ROW_DTYPE[n_ref], totals: a DEPTH_TOTALS_DTYPE scalar [, d_counts: the device
+        address of the context's uint32 array of c per index entry, valid until the next read, begin or index call]).  n_ref: the
+        references of the index this context built last.  The counters stay: it may be called again"""
+        n_ref = getattr(self, "_cf_n_ref", None)
+        rows = np.zeros(65535 if n_ref is None else max(n_ref, 1), dtype=DEPTH_ROW_DTYPE)   # (the library writes as many rows as ITS index has references)
+        totals = np.zeros(1, dtype=DEPTH_TOTALS_DTYPE)
+        d = C.c_void_p()
+        _check(lib().spsp_depth_read_device(self._h, min_count, rows.ctypes.data, totals.ctypes.data, C.byref(d) if want_counts else None))
+        rows = rows[:n_ref or 0]
+        return (rows, totals[0], d.value) if want_counts else (rows, totals[0])
+
+    def depth_stage_ms(self):
+        """spsp_depth_stage_ms: with timing_enable() on, the milliseconds of the depth calls' launches since the last read ->
+        dict(add, entry, reduce)"""
+        ms = (C.c_double * 3)()
+        _check(lib().spsp_depth_stage_ms(self._h, ms))
+        return dict(zip(("add", "entry", "reduce"), ms))
+
+    def depth_files(self, paths, reads_paths, prefix, min_count=1, precision=6, rate=0.0):
+        """spsp_depth_files: the sketch files of the references and one or more FASTA / FASTQ files of reads (gzip or plain) ->
+        <prefix>_depth.csv.gz and (rows, totals).  rate: as classify_files (0.0, a rate, or "auto"); sketches of different rates need one"""
+        arr, _alive = _paths_array(paths)
+        reads, _alive2 = _paths_array([str(r) for r in reads_paths])
+        rows = C.c_void_p()
+        totals = np.zeros(1, dtype=DEPTH_TOTALS_DTYPE)
+        self._cf_n_ref = None
+        _check(lib().spsp_depth_files(self._h, arr, len(paths), reads, len(reads_paths), min_count, precision, prefix.encode(), 0, _rate_arg(rate),
+                                      C.byref(rows), totals.ctypes.data))
+        return np.frombuffer(_take(rows, len(paths) * DEPTH_ROW_DTYPE.itemsize), dtype=DEPTH_ROW_DTYPE).copy(), totals[0]
 
     def select_files(self, paths, prefix, what, each=False, n_query=0, rate=None):
         """spsp_select_files: sketch files (the n_query queries first, or none) -> the keys in the band `what` (select_band's words)

@@ -125,8 +125,19 @@ int main(int argc, char** argv) {
     bool classify = false;
     int cf_opts = 0;                 // -Y or -V seen
     long long cf_top = 1, cf_min_keys = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:")) != -1) {
+    vector<string> reads_files;      // -D <reads file> [-D <more> ...] [-W <min_count>]: neither letter is in the reference's option string
+    bool dp_min_seen = false;
+    long long dp_min_count = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:")) != -1) {
         switch (ch) {
+            case 'D': reads_files.push_back(optarg); break;
+            case 'W': {
+                char* e = nullptr;
+                dp_min_count = strtoll(optarg, &e, 10);
+                if (e == optarg || *e || dp_min_count < 1 || dp_min_count > 0xffffffffll) { cout << "-W takes the smallest number of records a found key is held by, an integer in 1 .. 4294967295, not '" << optarg << "'" << endl; return 1; }
+                dp_min_seen = true;
+                break;
+            }
             case 'G': labels_file = optarg; groups = true; break;
             case 'X': records_file = optarg; classify = true; break;
             case 'Y': {
@@ -268,6 +279,12 @@ int main(int argc, char** argv) {
         cout << "-X classifies the records of a sequence file against the index: not together with -q, -g, -c, -C, -N, -J, -K, -P, -r, -R, -l, -L, -S, -E, -A or -G" << endl;
         return 1;
     }
+    const bool depth = !reads_files.empty();
+    if (dp_min_seen && !depth) { cout << "-W belongs to the depth of -D <reads file>: it needs -D" << endl; return 1; }
+    if (depth && (query != "" || gather || cluster_opts || neighbours || nb_opts || prevalence || rep_opts || tree_opts || select_opts || accumulation || groups || classify)) {
+        cout << "-D counts how deep the reads of a sequence file cover the index: not together with -q, -g, -c, -C, -N, -J, -K, -I, -P, -r, -R, -l, -L, -S, -E, -A, -G or -X" << endl;
+        return 1;
+    }
     if (nb_opts && !neighbours && !classify) { cout << "-J / -K / -I set the threshold of the neighbour lists: they need -N (-I also serves -X)" << endl; return 1; }
     if (neighbours && (gather || cluster_opts)) { cout << "-N lists neighbours: not together with -g, -c or -C" << endl; return 1; }
     if (prevalence && (gather || cluster_opts || neighbours)) { cout << "-P counts the holders of every key: not together with -g, -c, -C or -N" << endl; return 1; }
@@ -349,6 +366,19 @@ int main(int argc, char** argv) {
         if (const char* e = getenv("SPSP_PER_DEVICE")) { const long v = atol(e); if (v > 0) per_device = (size_t)v; }
         const int use = (int)std::max<size_t>(1, std::min<size_t>((size_t)visible, names.size() / per_device));
         for (int d = 0; d < use; ++d) devices.push_back(d);
+    }
+    if (depth) {
+        // one device, as -X (the driver opens a second context on it for the reads)
+        vector<const char*> reads;
+        for (auto& r : reads_files) reads.push_back(r.c_str());
+        spsp_ctx* ctx = nullptr;
+        int rc = spsp_create(devices[0], nullptr, &ctx);
+        if (rc == SPSP_OK) rc = spsp_depth_files(ctx, paths.data(), (uint32_t)paths.size(), reads.data(), (uint32_t)reads.size(), (uint32_t)dp_min_count, (int)p,
+                                                 output_name.c_str(), 1, rate, nullptr, nullptr);
+        const string err = rc != SPSP_OK ? spsp_last_error() : "";
+        if (ctx) spsp_destroy(ctx);
+        if (rc != SPSP_OK) { cout << "Depth failed: " << err << endl; return 1; }
+        return 0;
     }
     if (classify) {
         // one device, as gather (the driver opens a second context on it for the records)

@@ -282,9 +282,13 @@ void spsp_destroy(spsp_ctx* c) {
                       &c->sel_mn[0], &c->sel_mn[1], &c->sel_lo[0], &c->sel_lo[1], &c->sel_hi[0], &c->sel_hi[1], &c->sel_t_mn, &c->sel_t_lo, &c->sel_t_hi, &c->sel_work,
                       &c->ac_work, &c->ac_keys, &c->ac_list, &c->ac_rank, &c->ac_hist,
                       &c->gp_table, &c->gp_cell, &c->gp_work, &c->gp_mn, &c->gp_lo, &c->gp_hi, &c->gp_t_mn, &c->gp_t_lo, &c->gp_t_hi,
-                      &c->cf_off, &c->cf_kn, &c->cf_work, &c->cf_queue, &c->cf_rec, &c->cf_hits, &c->cf_rows};
+                      &c->cf_off, &c->cf_kn, &c->cf_work, &c->cf_queue, &c->cf_rec, &c->cf_hits, &c->cf_rows,
+                      &c->dp_count, &c->dp_kn, &c->dp_uniq, &c->dp_entry, &c->dp_rows, &c->dp_words, &c->dp_long, &c->dp_hist};
     for (DevBuf* b : bufs) b->release();
     for (hipEvent_t& e : c->cf_events) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    for (hipEvent_t& e : c->dp_events) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    for (auto* v : {&c->dp_add_used, &c->dp_add_spare})
+        for (auto& ev : *v) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     devbuf_flush_retired();
     for (int kind = 0; kind < kEvKinds; ++kind) {
         for (auto* v : {&c->evlog[kind].used, &c->evlog[kind].spare})

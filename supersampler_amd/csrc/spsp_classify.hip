@@ -94,19 +94,11 @@ __global__ __launch_bounds__(kCfThreads) void k_cf_probe(SortedKeys Q, const uin
         const uint64_t e = q0 + i;
         const uint32_t mn = Q.mn[e];
         const uint64_t lo = Q.lo[e], hi = HAS_HI ? Q.hi[e] : 0ull;
-        const uint64_t mask = (1ull << log2cap) - 1ull;
-        uint64_t pos = pv_home<HAS_HI>(mn, hi, lo, log2cap);
-        for (uint64_t probes = 0; probes <= mask; ++probes) {   // (a key nobody holds may go round a table without a free slot)
-            const unsigned long long cur = tbl[pos];
-            if ((uint32_t)cur == 0u) break;
-            const uint64_t c = (uint64_t)((uint32_t)cur - 1u), at = c - first;
-            if (at < n_index && pv_same<HAS_HI>(K, c, mn, hi, lo)) {   // (always inside: the index call filled this table from these entries)
-                const uint32_t number = key_no[at];
-                kn = number + 1u;
-                h = key_start[number + 1u] - key_start[number];
-                break;
-            }
-            pos = (pos + 1ull) & mask;
+        const uint64_t at = pv_find<HAS_HI>(K, first, n_index, tbl, log2cap, mn, hi, lo);
+        if (at != ~0ull) {
+            const uint32_t number = key_no[at];
+            kn = number + 1u;
+            h = key_start[number + 1u] - key_start[number];
         }
         kn_out[i] = kn;
         rec = sorted_sketch_of(off, 0, n_rec, e);
@@ -312,6 +304,7 @@ int classify_index_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const u
     }
     X.has_hi = shape.has_hi; X.n_ref = n_ref; X.first = shape.first;
     X.mn = d_mn; X.lo = d_lo; X.hi = d_hi;
+    X.off_host.assign(h_sk_off, h_sk_off + n_ref + 1);
     X.valid = true;                                        // (behind the build: the table fill in it drops whatever index there was)
     return SPSP_OK;
 }
@@ -463,14 +456,16 @@ static int batch_seams(spsp_ctx* ctx, const spsp_superkmer* d_sk, uint64_t n_sk,
 }
 
 // the records of a text, ingested and scanned once on `side` (a second context of ctx's device), their keys extracted batch by batch
-// there and classified against the index on ctx
-static int classify_text(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path, uint32_t top,
-                         uint32_t min_keys, uint32_t num, uint32_t den, std::vector<std::string>* names, std::vector<spsp_classify_record>* recs,
-                         std::vector<spsp_classify_hit>* hits) {
+// there and handed to on_batch, which queues its work on ctx (the two contexts are ordered by spsp_wait_stream around it).
+// names: the records' names as the host reads them, held against the device's record count; null: no names, no header count.
+// on_records: once, behind the scan, with the records' base offsets (n_rec + 1)
+int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
+                         std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
+                         const std::function<int(const RecordBatch&)>& on_batch) {
     int rc;
     double t0 = now_s(), t1;
     const bool fastq = n_text && text[0] == '@';
-    record_names_host(text, n_text, fastq, names);
+    if (names) record_names_host(text, n_text, fastq, names);
     if ((rc = side->i_text.reserve((size_t)n_text + 64))) return rc;
     if (n_text) SPSP_HIP(hipMemcpyAsync(side->i_text.p, text, (size_t)n_text, hipMemcpyHostToDevice, side->stream));
     uint8_t* d_bases = nullptr; uint64_t* d_off = nullptr; uint64_t n_bases = 0; uint32_t n_rec = 0;
@@ -479,7 +474,7 @@ static int classify_text(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
     if (fastq) fastq_tail(text, n_text, &fq.content_end, &fq.blank_tail);
     if ((rc = clean_device_impl(side, side->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed, fastq ? &fq : nullptr))) return rc;
     t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
-    if (names->size() != n_rec) {
+    if (names && names->size() != n_rec) {
         set_error("'%s': %zu header line(s) on the host, %u record(s) on the device", path, names->size(), n_rec);
         return SPSP_ERR_FORMAT;
     }
@@ -491,9 +486,7 @@ static int classify_text(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
     std::vector<uint64_t> rec_off((size_t)n_rec + 1, 0);
     SPSP_HIP(hipMemcpyAsync(rec_off.data(), d_off, rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));
     SPSP_HIP(hipStreamSynchronize(side->stream));
-    recs->assign(n_rec, spsp_classify_record{});
-    hits->assign((size_t)n_rec * top, spsp_classify_hit{});
-    for (uint32_t r = 0; r < n_rec; ++r) (*recs)[r].length = rec_off[r + 1] - rec_off[r];
+    if ((rc = on_records(n_rec, rec_off.data()))) return rc;
     std::vector<uint32_t> first_rec, bounds;
     std::vector<uint64_t> key_off, seam;
     for (uint64_t r = 0; r < n_rec; r += 65535u) bounds.push_back((uint32_t)r);
@@ -512,10 +505,27 @@ static int classify_text(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
             (rc = spsp_sketch_keys_device(side, &ps, d_bases, n_bases, d_off, d_sk + q0, q1 - q0, first_rec.data(), batch, 0, &k_mn, &k_lo, &k_hi,
                                           key_off.data())) ||
             (rc = spsp_wait_stream(ctx, side)) ||
-            (rc = classify_device_impl(ctx, (const uint32_t*)k_mn, (const uint64_t*)k_lo, (const uint64_t*)k_hi, key_off.data(), batch, top, min_keys, num, den,
-                                       recs->data() + r0, hits->data() + (size_t)r0 * top))) return rc;
+            (rc = on_batch(RecordBatch{r0, batch, (const uint32_t*)k_mn, (const uint64_t*)k_lo, (const uint64_t*)k_hi, key_off.data()}))) return rc;
     }
     return SPSP_OK;
+}
+
+// the records of a text classified against the index on ctx
+static int classify_text(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path, uint32_t top,
+                         uint32_t min_keys, uint32_t num, uint32_t den, std::vector<std::string>* names, std::vector<spsp_classify_record>* recs,
+                         std::vector<spsp_classify_hit>* hits) {
+    return records_text_batches(
+        ctx, side, p, text, n_text, path, names,
+        [&](uint32_t n_rec, const uint64_t* rec_off) {
+            recs->assign(n_rec, spsp_classify_record{});
+            hits->assign((size_t)n_rec * top, spsp_classify_hit{});
+            for (uint32_t r = 0; r < n_rec; ++r) (*recs)[r].length = rec_off[r + 1] - rec_off[r];
+            return SPSP_OK;
+        },
+        [&](const RecordBatch& B) {
+            return classify_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, top, min_keys, num, den, recs->data() + B.first_record,
+                                        hits->data() + (size_t)B.first_record * top);
+        });
 }
 
 // spsp_classify_files behind its argument checks

@@ -101,6 +101,24 @@ __device__ __forceinline__ bool pv_same(const SortedKeys& K, uint64_t c, uint32_
     return K.lo[c] == lo && K.mn[c] == mn && (!HAS_HI || K.hi[c] == hi);
 }
 
+// The lookup of a key in a table the fill made from entries [first, first + n_index) of K: the probe sequence from the key's home
+// up to the first free slot, or once round a table without one.  -> the claimer's entry number less `first`, or ~0: nobody holds
+// the key.  The classification's probe pass and the depth pass's counting pass walk it.
+template <bool HAS_HI>
+__device__ __forceinline__ uint64_t pv_find(const SortedKeys& K, uint64_t first, uint32_t n_index, const unsigned long long* __restrict__ tbl, uint32_t log2cap,
+                                            uint32_t mn, uint64_t hi, uint64_t lo) {
+    const uint64_t mask = (1ull << log2cap) - 1ull;
+    uint64_t pos = pv_home<HAS_HI>(mn, hi, lo, log2cap);
+    for (uint64_t probes = 0; probes <= mask; ++probes) {   // (a key nobody holds may go round a table without a free slot)
+        const unsigned long long cur = tbl[pos];
+        if ((uint32_t)cur == 0u) break;
+        const uint64_t c = (uint64_t)((uint32_t)cur - 1u), at = c - first;
+        if (at < n_index && pv_same<HAS_HI>(K, c, mn, hi, lo)) return at;   // (always inside: the index call filled this table from these entries)
+        pos = (pos + 1ull) & mask;
+    }
+    return ~0ull;
+}
+
 // The order of two fractions x_a / u_a and x_b / u_b without a division: x_a * u_b against x_b * u_a as 128-bit products.
 // > 0: a is the larger fraction, < 0: b, 0: equal (two different fractions that round to one double are still told apart).
 // The neighbours pass orders a row's partners by it, the representatives pass a member's candidates.

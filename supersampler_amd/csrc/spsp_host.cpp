@@ -2394,6 +2394,56 @@ int spsp_classify_summary_csv_host(const spsp_classify_record* records, const sp
     return text_out(out, text, len);
 }
 
+// ------------------------------------------------------------------------------------------------ depth
+int spsp_depth_plan_host(uint32_t* bins) {
+    if (!bins) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    *bins = spsp::kDpBins;
+    return SPSP_OK;
+}
+
+// five numbers that cannot be the statistics of `found` counts: why, or null
+static const char* depth_five_wrong(uint32_t found, uint64_t sum, uint32_t median, uint32_t max) {
+    if (median > max) return "a median above the maximum";
+    if (max > sum) return "a maximum above the sum";
+    if (found == 0) return sum || max || median ? "nothing found, and a sum, maximum or median all the same" : nullptr;
+    if (median == 0) return "keys found, and a median of 0";
+    if (sum < found || sum > (uint64_t)found * max) return "a sum outside found .. found * max";
+    return nullptr;
+}
+
+static const char* depth_row_wrong(const spsp_depth_row& r) {
+    if (r.found > r.keys) return "more keys found than keys";
+    if (r.unique_keys > r.keys) return "more unique keys than keys";
+    if (r.unique_found > r.found || r.unique_found > r.unique_keys) return "more unique keys found than min(found, unique_keys)";
+    if (const char* why = depth_five_wrong(r.found, r.sum, r.median, r.max)) return why;
+    if (const char* why = depth_five_wrong(r.unique_found, r.unique_sum, r.unique_median, r.unique_max)) return why;
+    if (r.unique_sum > r.sum) return "a unique sum above the sum";
+    return nullptr;
+}
+
+int spsp_depth_csv_host(const spsp_depth_row* rows, const char* const* names, uint32_t n_ref, int precision, char** text, uint64_t* len) {
+    if (!text || !len || (n_ref && (!rows || !names))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    std::string out = "reference,keys,found,f_found,median,mean,max,unique_keys,unique_found,f_unique_found,unique_median,unique_mean,unique_max\n";
+    char num[64];
+    for (uint32_t j = 0; j < n_ref; ++j) {
+        const spsp_depth_row& r = rows[j];
+        if (const char* why = depth_row_wrong(r)) { set_error("depth row of reference %u contradicts itself: %s", j, why); return SPSP_ERR_ARG; }
+        out += names[j];
+        const uint32_t keys[2] = {r.keys, r.unique_keys}, found[2] = {r.found, r.unique_found}, median[2] = {r.median, r.unique_median}, max[2] = {r.max, r.unique_max};
+        const uint64_t sum[2] = {r.sum, r.unique_sum};
+        for (int u = 0; u < 2; ++u) {
+            out += ','; out += std::to_string(keys[u]);
+            out += ','; out += std::to_string(found[u]);
+            out += ','; out.append(num, format_g(num, sizeof num, precision, keys[u] ? (double)found[u] / (double)keys[u] : 0.0));
+            out += ','; out += std::to_string(median[u]);
+            out += ','; out.append(num, format_g(num, sizeof num, precision, found[u] ? (double)sum[u] / (double)found[u] : 0.0));
+            out += ','; out += std::to_string(max[u]);
+        }
+        out += '\n';
+    }
+    return text_out(out, text, len);
+}
+
 // ------------------------------------------------------------------------------------------------ the linkage tree
 int spsp_tree_cut_host(const spsp_tree_row* rows, uint64_t n_rows, uint32_t n, const uint64_t* card, int metric, uint32_t floor_num, uint32_t floor_den,
                        uint32_t num, uint32_t den, uint32_t* cluster, uint64_t* n_clusters) {

@@ -306,8 +306,21 @@ struct spsp_ctx {
         const uint64_t *lo = nullptr, *hi = nullptr;
         const uint32_t *key_no = nullptr, *key_start = nullptr;
         const uint16_t* list = nullptr;
+        bool depth = false;               // spsp_depth_begin_device has made counters for THIS index: they end with it
+        uint32_t distinct = 0;            // ... and read D, its distinct keys
+        std::vector<uint64_t> off_host;   // the references' offsets as the index call got them (n_ref + 1)
     } cf_index;
     spsp::DevBuf cf_off, cf_kn, cf_work, cf_queue, cf_rec, cf_hits, cf_rows;
+    // depth (spsp_depth.hip): one 32-bit counter per distinct key of the index; per index entry its key's number and whether that
+    // key is unique (made once, by begin), and its key's count (made by every read, handed out); the rows; the two total words
+    // (hit keys since begin | the index keys found at the last read)
+    spsp::DevBuf dp_count, dp_kn, dp_uniq, dp_entry, dp_rows, dp_words;
+    spsp::DevBuf dp_long, dp_hist;       // the long references and their segments (made by begin); their sums and histograms in device memory (per read)
+    uint32_t dp_n_long = 0, dp_n_seg = 0;
+    uint64_t dp_record_keys = 0;         // record keys added since begin
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> dp_add_used, dp_add_spare;   // while timing is on: a pair around every add's launch, read by spsp_depth_stage_ms
+    hipEvent_t dp_events[3] = {};        // ... and in front of a read's entry pass, of its reduction, and behind it
+    double dp_ms[3] = {};                // the milliseconds added up since spsp_depth_stage_ms last read them: add, entry, reduce
     hipEvent_t cf_events[5] = {};        // while timing is on: in front of the probe, the route, the small form, the large form, and behind it
     double cf_ms[4] = {};                // ... their milliseconds added up since spsp_classify_stage_ms last read them
 };
@@ -501,6 +514,24 @@ int classify_check_args(uint32_t top, uint32_t min_keys, uint32_t num, uint32_t 
 int classify_index_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n_ref);
 int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
                          uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, spsp_classify_record* records, spsp_classify_hit* hits);
+// the records path the classification and the depth pass share (spsp_classify.hip): a FASTA / FASTQ text ingested and scanned once
+// on `side`, a second context of ctx's device; the records' keys extracted there in batches of at most 65 535 records and handed to
+// on_batch, whose work is queued on ctx (spsp_wait_stream orders the two contexts around every batch: the keys of a batch are read
+// before the next extraction overwrites them).  names: null, or the records' names as the host reads them from the header lines --
+// then a text with another number of header lines than the device finds records is SPSP_ERR_FORMAT.  on_records is called once,
+// behind the scan, with the records' base offsets (n_rec + 1)
+struct RecordBatch { uint32_t first_record, n_records; const uint32_t* mn; const uint64_t *lo, *hi; const uint64_t* key_off; };   // key_off: host, n_records + 1
+int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
+                         std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
+                         const std::function<int(const RecordBatch&)>& on_batch);
+// spsp_depth.hip: how many records hold each key of the index, and the per-reference statistics over those counts
+constexpr uint32_t kDpThreads = 256;                       // every depth kernel: 4 waves
+constexpr uint32_t kDpBins = 4096;                         // bins of one LDS histogram of k_dp_reduce: the last holds every count at or above kDpBins - 1
+constexpr uint32_t kDpLongKeys = 65536;                    // a reference of more entries than this is reduced by segments, a workgroup each, and a merge
+constexpr uint32_t kDpSegKeys = 16384;                     // ... of this many entries
+int depth_begin_impl(spsp_ctx* ctx);
+int depth_add_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, uint64_t first, uint64_t n_keys);
+int depth_read_impl(spsp_ctx* ctx, uint32_t min_count, spsp_depth_row* rows, spsp_depth_totals* totals, const uint32_t** d_entry_count);
 // spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
 // groups as n_groups sketches back to back in context-owned arrays
 int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,
