@@ -1227,6 +1227,62 @@ int spsp_depth_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_r
                      int precision, const char* out_prefix, int chatter, double rate, spsp_depth_row** rows /* may be NULL; spsp_free */,
                      spsp_depth_totals* totals /* may be NULL */);
 
+/* ------------------------------------------------------------- profile ---- */
+/* Which references a read set holds, each shared key counted once, and how deep each one is (not in the reference): the greedy
+ * rounds of gather on the counters of the depth pass.  Index and counts as in the depth section: references 0 .. R-1 with key sets
+ * K_j, U their union, c(x) from the adds since spsp_depth_begin_device.  F = {x in U : c(x) >= min_count}, A_0 = F.
+ * Round r = 1, 2, ...:  u_j = |K_j n A_(r-1)|;  j* = the SMALLEST j among the largest u_j;  stop if u_j* < min_keys, or if
+ * max_rounds > 0 and r > max_rounds;  otherwise emit one row and set A_r = A_(r-1) \ K_j*.
+ * The row of round r (rank = r: rows[r - 1]):  reference = j*,  keys = |K_j*|,  found = |K_j* n F| (depth's found),
+ * assigned = u_j*,  sum (64 bits), median (the LOWER median, as depth defines it) and max of c(x) over x in K_j* n A_(r-1),
+ * remaining = |A_(r-1)| - u_j*.  min_count >= 1 and min_keys >= 1; max_rounds = 0 means no limit; at most R rows.
+ * Totals: found_keys = |F|, found_sum = the sum of c over F, assigned_keys and assigned_sum = the rows' assigned and sum added up.
+ * The answer is a function of the multiset of record keys, min_count, min_keys and max_rounds: not of batch cuts, key order or the
+ * order lanes meet anything in.  Integers only.  What follows, and what spsp_profile_csv_host holds rows to:
+ *   assigned never increases from one row to the next;  1 <= assigned <= found <= keys;  no reference appears twice;
+ *   remaining_r = remaining_(r-1) - assigned_r with remaining_0 = |F|;  assigned <= sum <= assigned * max;  1 <= median <= max;
+ *   with min_keys = 1 and no round limit the last remaining is 0. */
+typedef struct spsp_profile_row {   /* 40 bytes, one per round */
+    uint64_t sum;
+    uint32_t reference, keys, found, assigned, median, max, remaining, reserved;
+} spsp_profile_row;
+typedef struct spsp_profile_totals { uint64_t found_sum, assigned_sum; uint32_t found_keys, assigned_keys; } spsp_profile_totals;   /* 24 bytes */
+/* The rounds on the counters of spsp_depth_begin_device / spsp_depth_add_device.  Like a read it does not consume them: any number
+ * of calls, between adds, with other arguments, and a spsp_depth_read_device before or after it answers as it does without.
+ * rows has room for n_ref rows, *n_rows receives their number.  *d_entry_assigned (may be NULL) receives the device address of a
+ * context-owned byte array parallel to the index's key arrays: 1 where that entry's key was assigned to that entry's reference;
+ * valid until the next profile, begin or index call.  Launches: the entry pass of a read and a count per reference; per round one
+ * workgroup that picks (arg-max over u << 32 | ~j words) and a walk over the winner's entries that marks its live keys dead and
+ * takes one off the counter of every other holder (the index's key-major lists; a list of more than 32 holders by a whole wave;
+ * up to 38 912 references through counters in LDS, flushed once per workgroup);
+ * then ONE run of the depth reduction with the assigned bytes in the place of the unique ones.  Rounds are queued 32, 64, 128,
+ * 128, ... at a time: one host wait per batch and one for the statistics, never one per round.
+ * SPSP_ERR_ARG: no counters on the context, min_count == 0, min_keys == 0.  An index without keys or an empty F: SPSP_OK, no rows. */
+int spsp_profile_device(spsp_ctx* ctx, uint32_t min_count, uint32_t min_keys, uint32_t max_rounds, spsp_profile_row* rows /* n_ref */, uint64_t* n_rows,
+                        spsp_profile_totals* totals /* may be NULL */, const void** d_entry_assigned /* may be NULL */);
+/* While the context's timing is on the profile calls record events around their launches; this reads the milliseconds added up
+ * since the last read and clears them: ms[0] the entry pass and the start, ms[1] the picks, ms[2] the walks, ms[3] the reduction. */
+int spsp_profile_stage_ms(spsp_ctx* ctx, double* ms /* 4: entry + start, picks, walks, reduction */);
+/* What the last spsp_profile_device call on the context did: counts[0] the rounds it queued (a stopped call's later launches
+ * return at their first load), counts[1] its rows, counts[2] its host waits. */
+int spsp_profile_counts(spsp_ctx* ctx, uint32_t* counts /* 3: rounds queued, rows, host waits */);
+/* The text of <prefix>_profile.csv.gz:
+ * "rank,reference,keys,found,f_found,assigned,f_assigned,median,mean,max,f_weighted,remaining" and one line per row, the reference
+ * by its name; f_found = found / keys, f_assigned = assigned / found_keys, mean = sum / assigned, f_weighted = sum / found_sum
+ * (the relative abundance) as %.<precision>g, 0 where the denominator is 0: they decide nothing.  A row that contradicts the facts
+ * above (or names a reference >= n_ref, or n_rows > n_ref) is SPSP_ERR_ARG, the message naming the rank.  *text: spsp_free(). */
+int spsp_profile_csv_host(const spsp_profile_row* rows, uint64_t n_rows, const spsp_profile_totals* totals, const char* const* names, uint32_t n_ref,
+                          int precision, char** text, uint64_t* len);
+/* The whole-file driver: the arguments of spsp_depth_files plus min_keys and max_rounds.  It loads the index and adds the reads as
+ * spsp_depth_files does (the same code), then makes one read and one profile.  Writes <out_prefix>_depth.csv.gz, byte for byte what
+ * spsp_depth_files writes, and <out_prefix>_profile.csv.gz; nothing on any failure.  rows, profile_rows (may be NULL) receive
+ * copies released with spsp_free(); the totals may be NULL. */
+int spsp_profile_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* const* reads_paths, uint32_t n_reads, uint32_t min_count,
+                       uint32_t min_keys, uint32_t max_rounds, int precision, const char* out_prefix, int chatter, double rate,
+                       spsp_depth_row** rows /* may be NULL; spsp_free */, spsp_depth_totals* totals /* may be NULL */,
+                       spsp_profile_row** profile_rows /* may be NULL; spsp_free */, uint64_t* n_profile_rows /* may be NULL */,
+                       spsp_profile_totals* profile_totals /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,11 @@ DEPTH_ROW_DTYPE = np.dtype([("sum", "<u8"), ("unique_sum", "<u8"), ("keys", "<u4
                             ("unique_keys", "<u4"), ("unique_found", "<u4"), ("unique_median", "<u4"), ("unique_max", "<u4")])
 DEPTH_TOTALS_DTYPE = np.dtype([("record_keys", "<u8"), ("hit_keys", "<u8"), ("index_keys", "<u4"), ("index_found", "<u4")])
 
+# spsp_profile_row / spsp_profile_totals: one round of the profile (rank = its place + 1), and the call's totals (include/spsp.h)
+PROFILE_ROW_DTYPE = np.dtype([("sum", "<u8"), ("reference", "<u4"), ("keys", "<u4"), ("found", "<u4"), ("assigned", "<u4"), ("median", "<u4"), ("max", "<u4"),
+                              ("remaining", "<u4"), ("reserved", "<u4")])
+PROFILE_TOTALS_DTYPE = np.dtype([("found_sum", "<u8"), ("assigned_sum", "<u8"), ("found_keys", "<u4"), ("assigned_keys", "<u4")])
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -151,6 +156,7 @@ ABI_SYMBOLS = [
     "spsp_groups_labels_host", "spsp_groups_bounds_host", "spsp_groups_device", "spsp_groups_csv_host", "spsp_groups_members_csv_host", "spsp_groups_files",
     "spsp_classify_index_device", "spsp_classify_device", "spsp_classify_plan_host", "spsp_classify_csv_host", "spsp_classify_summary_csv_host", "spsp_classify_files", "spsp_classify_stage_ms",
     "spsp_depth_begin_device", "spsp_depth_add_device", "spsp_depth_read_device", "spsp_depth_plan_host", "spsp_depth_stage_ms", "spsp_depth_csv_host", "spsp_depth_files",
+    "spsp_profile_device", "spsp_profile_stage_ms", "spsp_profile_counts", "spsp_profile_csv_host", "spsp_profile_files",
 ]
 
 _lib = None
@@ -385,6 +391,17 @@ def lib():
         L.spsp_depth_csv_host.argtypes = [vp, P(cp), u32, i32, P(vp), P(u64)]
         L.spsp_depth_files.restype = i32
         L.spsp_depth_files.argtypes = [vp, P(cp), u32, P(cp), u32, u32, i32, cp, i32, dbl, P(vp), vp]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_profile_device"):
+        L.spsp_profile_device.restype = i32
+        L.spsp_profile_device.argtypes = [vp, u32, u32, u32, vp, P(u64), vp, P(vp)]
+        L.spsp_profile_stage_ms.restype = i32
+        L.spsp_profile_stage_ms.argtypes = [vp, P(dbl)]
+        L.spsp_profile_counts.restype = i32
+        L.spsp_profile_counts.argtypes = [vp, P(u32)]
+        L.spsp_profile_csv_host.restype = i32
+        L.spsp_profile_csv_host.argtypes = [vp, u64, vp, P(cp), u32, i32, P(vp), P(u64)]
+        L.spsp_profile_files.restype = i32
+        L.spsp_profile_files.argtypes = [vp, P(cp), u32, P(cp), u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), vp, P(vp), P(u64), vp]
     _lib = L
     return L
 
@@ -713,6 +730,17 @@ def depth_csv(rows, names, precision=6):
     arr, _alive = _paths_array(names)
     text, n = C.c_void_p(), C.c_uint64()
     _check(lib().spsp_depth_csv_host(rows.ctypes.data if len(rows) else None, arr, len(rows), precision, C.byref(text), C.byref(n)))
+    return _take(text, n.value)
+
+
+def profile_csv(rows, totals, names, precision=6):
+    """spsp_profile_csv_host: rows (PROFILE_ROW_DTYPE, one per round), the call's totals (a PROFILE_TOTALS_DTYPE scalar) and the names
+    of ALL references of the index -> the text of <prefix>_profile.csv.gz"""
+    rows = np.ascontiguousarray(rows, dtype=PROFILE_ROW_DTYPE)
+    totals = np.ascontiguousarray(totals, dtype=PROFILE_TOTALS_DTYPE).reshape(1)
+    arr, _alive = _paths_array(names)
+    text, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_profile_csv_host(rows.ctypes.data if len(rows) else None, len(rows), totals.ctypes.data, arr, len(names), precision, C.byref(text), C.byref(n)))
     return _take(text, n.value)
 
 
@@ -1550,6 +1578,45 @@ class Context:
         _check(lib().spsp_depth_files(self._h, arr, len(paths), reads, len(reads_paths), min_count, precision, prefix.encode(), 0, _rate_arg(rate),
                                       C.byref(rows), totals.ctypes.data))
         return np.frombuffer(_take(rows, len(paths) * DEPTH_ROW_DTYPE.itemsize), dtype=DEPTH_ROW_DTYPE).copy(), totals[0]
+
+    def profile_read(self, min_count=1, min_keys=1, max_rounds=0, want_assigned=False):
+        """spsp_profile_device: the greedy rounds on the counters of depth_begin / depth_add -> (rows PROFILE_ROW_DTYPE, one per
+        round, totals: a PROFILE_TOTALS_DTYPE scalar [, d_assigned: the device address of the context's byte array parallel to the
+        index's key arrays, 1 where the entry's key was assigned to the entry's reference; valid until the next profile, begin or
+        index call]).  The counters stay: it may be called again, and a depth_read before or after it answers as without it"""
+        n_ref = getattr(self, "_cf_n_ref", None)
+        rows = np.zeros(65535 if n_ref is None else max(n_ref, 1), dtype=PROFILE_ROW_DTYPE)   # (the library writes at most as many rows as ITS index has references)
+        totals = np.zeros(1, dtype=PROFILE_TOTALS_DTYPE)
+        d, n = C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_profile_device(self._h, min_count, min_keys, max_rounds, rows.ctypes.data, C.byref(n), totals.ctypes.data,
+                                         C.byref(d) if want_assigned else None))
+        rows = rows[:n.value].copy()
+        return (rows, totals[0], d.value) if want_assigned else (rows, totals[0])
+
+    def profile_stage_ms(self):
+        """spsp_profile_stage_ms and spsp_profile_counts: with timing_enable() on, the milliseconds of the profile calls' launches since
+        the last read -> dict(start, picks, walks, reduction), and what the last call did -> rounds (queued), rows, waits (of the host)"""
+        ms = (C.c_double * 4)()
+        counts = (C.c_uint32 * 3)()
+        _check(lib().spsp_profile_stage_ms(self._h, ms))
+        _check(lib().spsp_profile_counts(self._h, counts))
+        out = dict(zip(("start", "picks", "walks", "reduction"), ms))
+        out.update(zip(("rounds", "rows", "waits"), (int(c) for c in counts)))
+        return out
+
+    def profile_files(self, paths, reads_paths, prefix, min_count=1, min_keys=1, max_rounds=0, precision=6, rate=0.0):
+        """spsp_profile_files: as depth_files, and one profile behind the read -> <prefix>_depth.csv.gz, <prefix>_profile.csv.gz and
+        (depth rows, depth totals, profile rows, profile totals)"""
+        arr, _alive = _paths_array(paths)
+        reads, _alive2 = _paths_array([str(r) for r in reads_paths])
+        rows, prows, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        totals = np.zeros(1, dtype=DEPTH_TOTALS_DTYPE)
+        ptotals = np.zeros(1, dtype=PROFILE_TOTALS_DTYPE)
+        self._cf_n_ref = None
+        _check(lib().spsp_profile_files(self._h, arr, len(paths), reads, len(reads_paths), min_count, min_keys, max_rounds, precision, prefix.encode(), 0,
+                                        _rate_arg(rate), C.byref(rows), totals.ctypes.data, C.byref(prows), C.byref(n), ptotals.ctypes.data))
+        return (np.frombuffer(_take(rows, len(paths) * DEPTH_ROW_DTYPE.itemsize), dtype=DEPTH_ROW_DTYPE).copy(), totals[0],
+                np.frombuffer(_take(prows, n.value * PROFILE_ROW_DTYPE.itemsize), dtype=PROFILE_ROW_DTYPE).copy(), ptotals[0])
 
     def select_files(self, paths, prefix, what, each=False, n_query=0, rate=None):
         """spsp_select_files: sketch files (the n_query queries first, or none) -> the keys in the band `what` (select_band's words)

@@ -128,7 +128,9 @@ int main(int argc, char** argv) {
     vector<string> reads_files;      // -D <reads file> [-D <more> ...] [-W <min_count>]: neither letter is in the reference's option string
     bool dp_min_seen = false;
     long long dp_min_count = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:")) != -1) {
+    bool profile = false;            // -B <min_keys>: the profile behind the depth of -D (not in the reference's option string either)
+    long long pf_min_keys = 1;
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:")) != -1) {
         switch (ch) {
             case 'D': reads_files.push_back(optarg); break;
             case 'W': {
@@ -136,6 +138,13 @@ int main(int argc, char** argv) {
                 dp_min_count = strtoll(optarg, &e, 10);
                 if (e == optarg || *e || dp_min_count < 1 || dp_min_count > 0xffffffffll) { cout << "-W takes the smallest number of records a found key is held by, an integer in 1 .. 4294967295, not '" << optarg << "'" << endl; return 1; }
                 dp_min_seen = true;
+                break;
+            }
+            case 'B': {
+                char* e = nullptr;
+                pf_min_keys = strtoll(optarg, &e, 10);
+                if (e == optarg || *e || pf_min_keys < 1 || pf_min_keys > 0xffffffffll) { cout << "-B takes the smallest number of live keys a named reference has, an integer in 1 .. 4294967295, not '" << optarg << "'" << endl; return 1; }
+                profile = true;
                 break;
             }
             case 'G': labels_file = optarg; groups = true; break;
@@ -281,6 +290,7 @@ int main(int argc, char** argv) {
     }
     const bool depth = !reads_files.empty();
     if (dp_min_seen && !depth) { cout << "-W belongs to the depth of -D <reads file>: it needs -D" << endl; return 1; }
+    if (profile && !depth) { cout << "-B profiles the reads of -D <reads file> (which references they hold, each shared key counted once): it needs -D" << endl; return 1; }
     if (depth && (query != "" || gather || cluster_opts || neighbours || nb_opts || prevalence || rep_opts || tree_opts || select_opts || accumulation || groups || classify)) {
         cout << "-D counts how deep the reads of a sequence file cover the index: not together with -q, -g, -c, -C, -N, -J, -K, -I, -P, -r, -R, -l, -L, -S, -E, -A, -G or -X" << endl;
         return 1;
@@ -373,11 +383,15 @@ int main(int argc, char** argv) {
         for (auto& r : reads_files) reads.push_back(r.c_str());
         spsp_ctx* ctx = nullptr;
         int rc = spsp_create(devices[0], nullptr, &ctx);
-        if (rc == SPSP_OK) rc = spsp_depth_files(ctx, paths.data(), (uint32_t)paths.size(), reads.data(), (uint32_t)reads.size(), (uint32_t)dp_min_count, (int)p,
-                                                 output_name.c_str(), 1, rate, nullptr, nullptr);
+        if (rc == SPSP_OK && profile)
+            rc = spsp_profile_files(ctx, paths.data(), (uint32_t)paths.size(), reads.data(), (uint32_t)reads.size(), (uint32_t)dp_min_count, (uint32_t)pf_min_keys, 0, (int)p,
+                                    output_name.c_str(), 1, rate, nullptr, nullptr, nullptr, nullptr, nullptr);
+        else if (rc == SPSP_OK)
+            rc = spsp_depth_files(ctx, paths.data(), (uint32_t)paths.size(), reads.data(), (uint32_t)reads.size(), (uint32_t)dp_min_count, (int)p,
+                                  output_name.c_str(), 1, rate, nullptr, nullptr);
         const string err = rc != SPSP_OK ? spsp_last_error() : "";
         if (ctx) spsp_destroy(ctx);
-        if (rc != SPSP_OK) { cout << "Depth failed: " << err << endl; return 1; }
+        if (rc != SPSP_OK) { cout << (profile ? "Profile failed: " : "Depth failed: ") << err << endl; return 1; }
         return 0;
     }
     if (classify) {

@@ -29,8 +29,10 @@
 //                such reference finishes the row from them (measured: one workgroup on 4 x 10^6 entries was 93 % of a read).
 // No workgroup waits for another.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "spsp_device.h"
 #include "spsp_internal.h"
@@ -385,6 +387,39 @@ int depth_add_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, co
     return SPSP_OK;
 }
 
+int depth_launch_entry(spsp_ctx* ctx, uint32_t min_count, unsigned long long** d_found) {
+    int rc;
+    const uint32_t E = ctx->cf_index.entries, D = ctx->cf_index.distinct;
+    if ((rc = ctx->dp_entry.reserve((size_t)E * 4 + 64))) return rc;
+    unsigned long long* d_words = ctx->dp_words.as<unsigned long long>();
+    if (d_found) *d_found = d_words + kDpwFound;
+    SPSP_HIP(hipMemsetAsync(d_words + kDpwFound, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(k_dp_entry, dim3((uint32_t)(((uint64_t)E + kDpThreads - 1) / kDpThreads)), dim3(kDpThreads), 0, ctx->stream,
+                       (const uint32_t*)ctx->dp_kn.as<uint32_t>(), E, (const uint32_t*)ctx->dp_count.as<uint32_t>(), D, min_count, ctx->dp_entry.as<uint32_t>(), d_words);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+
+int depth_launch_reduce(spsp_ctx* ctx, const uint8_t* d_class, uint32_t min_count, spsp_depth_row* d_rows) {
+    const uint32_t R = ctx->cf_index.n_ref;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(R, (uint64_t)std::max(ctx->n_cu, 1) * 4u);
+    const uint64_t* d_off = ctx->pv_off.as<uint64_t>();
+    const uint32_t* d_c = ctx->dp_entry.as<uint32_t>();
+    hipLaunchKernelGGL(k_dp_reduce, dim3(grid), dim3(kDpThreads), 0, ctx->stream, d_off, R, d_c, d_class, min_count, d_rows);
+    if (ctx->dp_n_long) {                                  // the long references: their segments, then one merge per reference
+        const size_t nl = ctx->dp_n_long, ns = ctx->dp_n_seg;
+        const uint32_t *d_long = ctx->dp_long.as<uint32_t>(), *d_seg_long = d_long + nl, *d_seg_no = d_seg_long + ns;
+        unsigned long long* d_acc = ctx->dp_hist.as<unsigned long long>();       // (the 64-bit words in front: aligned)
+        uint32_t* d_hist = reinterpret_cast<uint32_t*>(d_acc + nl * kDpAccWords);
+        SPSP_HIP(hipMemsetAsync(d_acc, 0, nl * (2 * kDpBins * 4 + kDpAccWords * 8), ctx->stream));
+        hipLaunchKernelGGL(k_dp_segment, dim3((uint32_t)ns), dim3(kDpThreads), 0, ctx->stream, d_off, d_long, d_seg_long, d_seg_no, d_c, d_class, min_count, d_hist, d_acc);
+        hipLaunchKernelGGL(k_dp_merge, dim3((uint32_t)nl), dim3(kDpThreads), 0, ctx->stream, d_off, d_long, d_c, d_class, min_count, (const uint32_t*)d_hist,
+                           (const unsigned long long*)d_acc, d_rows);
+    }
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+
 int depth_read_impl(spsp_ctx* ctx, uint32_t min_count, spsp_depth_row* rows, spsp_depth_totals* totals, const uint32_t** d_entry_count) {
     int rc;
     const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
@@ -404,26 +439,10 @@ int depth_read_impl(spsp_ctx* ctx, uint32_t min_count, spsp_depth_row* rows, sps
         for (hipEvent_t& e : ctx->dp_events) if (!e) SPSP_HIP(hipEventCreate(&e));
         ev = ctx->dp_events;
     }
-    SPSP_HIP(hipMemsetAsync(d_words + kDpwFound, 0, 8, ctx->stream));
     if (ev) SPSP_HIP(hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_dp_entry, dim3((uint32_t)(((uint64_t)E + kDpThreads - 1) / kDpThreads)), dim3(kDpThreads), 0, ctx->stream,
-                       (const uint32_t*)ctx->dp_kn.as<uint32_t>(), E, (const uint32_t*)ctx->dp_count.as<uint32_t>(), D, min_count, ctx->dp_entry.as<uint32_t>(), d_words);
+    if ((rc = depth_launch_entry(ctx, min_count, nullptr))) return rc;
     if (ev) SPSP_HIP(hipEventRecord(ev[1], ctx->stream));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(R, (uint64_t)std::max(ctx->n_cu, 1) * 4u);
-    const uint64_t* d_off = ctx->pv_off.as<uint64_t>();
-    const uint32_t* d_c = ctx->dp_entry.as<uint32_t>();
-    const uint8_t* d_uniq = ctx->dp_uniq.as<uint8_t>();
-    hipLaunchKernelGGL(k_dp_reduce, dim3(grid), dim3(kDpThreads), 0, ctx->stream, d_off, R, d_c, d_uniq, min_count, ctx->dp_rows.as<spsp_depth_row>());
-    if (ctx->dp_n_long) {                                  // the long references: their segments, then one merge per reference
-        const size_t nl = ctx->dp_n_long, ns = ctx->dp_n_seg;
-        const uint32_t *d_long = ctx->dp_long.as<uint32_t>(), *d_seg_long = d_long + nl, *d_seg_no = d_seg_long + ns;
-        unsigned long long* d_acc = ctx->dp_hist.as<unsigned long long>();       // (the 64-bit words in front: aligned)
-        uint32_t* d_hist = reinterpret_cast<uint32_t*>(d_acc + nl * kDpAccWords);
-        SPSP_HIP(hipMemsetAsync(d_acc, 0, nl * (2 * kDpBins * 4 + kDpAccWords * 8), ctx->stream));
-        hipLaunchKernelGGL(k_dp_segment, dim3((uint32_t)ns), dim3(kDpThreads), 0, ctx->stream, d_off, d_long, d_seg_long, d_seg_no, d_c, d_uniq, min_count, d_hist, d_acc);
-        hipLaunchKernelGGL(k_dp_merge, dim3((uint32_t)nl), dim3(kDpThreads), 0, ctx->stream, d_off, d_long, d_c, d_uniq, min_count, (const uint32_t*)d_hist,
-                           (const unsigned long long*)d_acc, ctx->dp_rows.as<spsp_depth_row>());
-    }
+    if ((rc = depth_launch_reduce(ctx, ctx->dp_uniq.as<uint8_t>(), min_count, ctx->dp_rows.as<spsp_depth_row>()))) return rc;
     SPSP_HIP(hipGetLastError());
     if (ev) SPSP_HIP(hipEventRecord(ev[2], ctx->stream));
     unsigned long long words[kDpWords] = {};
@@ -437,9 +456,8 @@ int depth_read_impl(spsp_ctx* ctx, uint32_t min_count, spsp_depth_row* rows, sps
     return SPSP_OK;
 }
 
-// spsp_depth_files behind its argument checks
-static int depth_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* const* reads_paths, uint32_t n_reads, uint32_t min_count, int precision,
-                       const char* out_prefix, int chatter, double rate, std::vector<spsp_depth_row>* rows, spsp_depth_totals* totals) {
+int depth_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* const* reads_paths, uint32_t n_reads, uint32_t min_count, int precision,
+                     const char* out_prefix, int chatter, double rate, std::vector<spsp_depth_row>* rows, spsp_depth_totals* totals, ProfileAsk* profile) {
     FilesRun run(ctx, paths, n_ref, chatter);
     int rc = run.load(rate);
     if (!rc) rc = run.refuse_k_eq_m(rc, "depth is");
@@ -466,6 +484,12 @@ static int depth_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, 
             spsp_free(text);
         }
         if (!rc) rc = depth_read_impl(ctx, min_count, rows->data(), totals, nullptr);
+        if (!rc && profile) {
+            uint64_t n_rows = 0;
+            profile->rows.assign(n_ref, spsp_profile_row{});
+            rc = profile_impl(ctx, min_count, profile->min_keys, profile->max_rounds, profile->rows.data(), &n_rows, &profile->totals, nullptr);
+            profile->rows.resize(rc ? 0 : (size_t)n_rows);
+        }
         (void)hipStreamSynchronize(ctx->stream);           // (the adds read the side context's key arrays)
         if (side) { (void)hipStreamSynchronize(side->stream); spsp_destroy(side); }
     }
@@ -473,9 +497,22 @@ static int depth_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, 
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
     if ((rc = spsp_depth_csv_host(rows->data(), paths, n_ref, precision, &text, &len))) return rc;
-    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_depth.csv.gz", t1)) || !chatter) return rc;
+    char* ptext = nullptr; uint64_t plen = 0;              // (both texts stand before either file is written)
+    if (profile && (rc = spsp_profile_csv_host(profile->rows.data(), profile->rows.size(), &profile->totals, paths, n_ref, precision, &ptext, &plen))) {
+        spsp_free(text);
+        return rc;
+    }
+    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_depth.csv.gz", t1))) { spsp_free(ptext); return rc; }
+    if (profile && (rc = write_csv_gz(ctx, ptext, plen, out_prefix, "_profile.csv.gz", now_s()))) {
+        remove((std::string(out_prefix) + "_depth.csv.gz").c_str());   // (nothing is written on a failure)
+        return rc;
+    }
+    if (!chatter) return rc;
     printf("%llu record(s) against %u reference(s): %llu record key(s), %llu hit key(s), %u of %u index key(s) found\n", (unsigned long long)n_records, n_ref,
            (unsigned long long)totals->record_keys, (unsigned long long)totals->hit_keys, totals->index_found, totals->index_keys);
+    if (profile)
+        printf("profile: %llu reference(s) named, %u of %u found key(s) assigned, %llu of %llu of their hit key(s)\n", (unsigned long long)profile->rows.size(),
+               profile->totals.assigned_keys, profile->totals.found_keys, (unsigned long long)profile->totals.assigned_sum, (unsigned long long)profile->totals.found_sum);
     say_common_rate(run.L, n_ref);
     fflush(stdout);
     return SPSP_OK;
@@ -537,7 +574,7 @@ extern "C" int spsp_depth_files(spsp_ctx* ctx, const char* const* index_paths, u
     SPSP_HIP(hipSetDevice(ctx->device));
     std::vector<spsp_depth_row> got;
     int rc;
-    if ((rc = depth_files(ctx, index_paths, n_ref, reads_paths, n_reads, min_count, precision, out_prefix, chatter, rate, &got, &mine))) return rc;
+    if ((rc = depth_files_impl(ctx, index_paths, n_ref, reads_paths, n_reads, min_count, precision, out_prefix, chatter, rate, &got, &mine, nullptr))) return rc;
     if (totals) *totals = mine;
     if (rows && (rc = give_rows(got, rows))) return rc;
     return SPSP_OK;

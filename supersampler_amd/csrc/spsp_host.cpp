@@ -2444,6 +2444,55 @@ int spsp_depth_csv_host(const spsp_depth_row* rows, const char* const* names, ui
     return text_out(out, text, len);
 }
 
+// ------------------------------------------------------------------------------------------------ profile
+// a row that cannot be round `rank`'s behind `before` (null for the first): why, or null.  left: |A| in front of the round
+static const char* profile_row_wrong(const spsp_profile_row& r, const spsp_profile_row* before, uint32_t left, uint32_t n_ref) {
+    if (r.reference >= n_ref) return "a reference the index does not have";
+    if (r.assigned == 0) return "no key assigned";
+    if (r.assigned > r.found) return "more keys assigned than found";
+    if (r.found > r.keys) return "more keys found than keys";
+    if (before && r.assigned > before->assigned) return "more keys assigned than in the round before";
+    if (r.assigned > left || r.remaining != left - r.assigned) return "remaining is not what the round before left, less the keys assigned";
+    if (r.median == 0 || r.median > r.max) return "a median outside 1 .. max";
+    if (r.sum < r.assigned || r.sum > (uint64_t)r.assigned * r.max) return "a sum outside assigned .. assigned * max";
+    return nullptr;
+}
+
+int spsp_profile_csv_host(const spsp_profile_row* rows, uint64_t n_rows, const spsp_profile_totals* totals, const char* const* names, uint32_t n_ref,
+                          int precision, char** text, uint64_t* len) {
+    if (!text || !len || !totals || (n_rows && (!rows || !names))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_rows > n_ref) {
+        set_error("profile: %llu rows for %u references (rank %u names a reference twice)", (unsigned long long)n_rows, n_ref, n_ref + 1);
+        return SPSP_ERR_ARG;
+    }
+    std::string out = "rank,reference,keys,found,f_found,assigned,f_assigned,median,mean,max,f_weighted,remaining\n";
+    std::vector<uint8_t> seen(n_ref, 0);
+    char num[64];
+    uint32_t left = totals->found_keys;
+    for (uint64_t i = 0; i < n_rows; ++i) {
+        const spsp_profile_row& r = rows[i];
+        const char* why = profile_row_wrong(r, i ? &rows[i - 1] : nullptr, left, n_ref);
+        if (!why && seen[r.reference]) why = "a reference named before";
+        if (why) { set_error("profile row of rank %llu contradicts the rule: %s", (unsigned long long)(i + 1), why); return SPSP_ERR_ARG; }
+        seen[r.reference] = 1;
+        left = r.remaining;
+        out += std::to_string(i + 1); out += ',';
+        out += names[r.reference];
+        out += ','; out += std::to_string(r.keys);
+        out += ','; out += std::to_string(r.found);
+        out += ','; out.append(num, format_g(num, sizeof num, precision, r.keys ? (double)r.found / (double)r.keys : 0.0));
+        out += ','; out += std::to_string(r.assigned);
+        out += ','; out.append(num, format_g(num, sizeof num, precision, totals->found_keys ? (double)r.assigned / (double)totals->found_keys : 0.0));
+        out += ','; out += std::to_string(r.median);
+        out += ','; out.append(num, format_g(num, sizeof num, precision, r.assigned ? (double)r.sum / (double)r.assigned : 0.0));
+        out += ','; out += std::to_string(r.max);
+        out += ','; out.append(num, format_g(num, sizeof num, precision, totals->found_sum ? (double)r.sum / (double)totals->found_sum : 0.0));
+        out += ','; out += std::to_string(r.remaining);
+        out += '\n';
+    }
+    return text_out(out, text, len);
+}
+
 // ------------------------------------------------------------------------------------------------ the linkage tree
 int spsp_tree_cut_host(const spsp_tree_row* rows, uint64_t n_rows, uint32_t n, const uint64_t* card, int metric, uint32_t floor_num, uint32_t floor_den,
                        uint32_t num, uint32_t den, uint32_t* cluster, uint64_t* n_clusters) {

@@ -321,6 +321,12 @@ struct spsp_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> dp_add_used, dp_add_spare;   // while timing is on: a pair around every add's launch, read by spsp_depth_stage_ms
     hipEvent_t dp_events[3] = {};        // ... and in front of a read's entry pass, of its reduction, and behind it
     double dp_ms[3] = {};                // the milliseconds added up since spsp_depth_stage_ms last read them: add, entry, reduce
+    // profile (spsp_profile.hip), on the depth counters: the live-key counter per reference, a dead byte per distinct key, an
+    // assigned byte per index entry, the state words of the rounds, a batch's round records, the reduced rows
+    spsp::DevBuf pf_u, pf_dead, pf_assigned, pf_state, pf_rounds, pf_rows;
+    std::vector<hipEvent_t> pf_events;   // while timing is on: around the start, every pick and walk of a batch, and the reduction
+    double pf_ms[4] = {};                // ... their milliseconds since spsp_profile_stage_ms last read them: start, picks, walks, reduction
+    uint32_t pf_last[3] = {};            // the last call's rounds queued, rows and host waits (spsp_profile_counts hands them out)
     hipEvent_t cf_events[5] = {};        // while timing is on: in front of the probe, the route, the small form, the large form, and behind it
     double cf_ms[4] = {};                // ... their milliseconds added up since spsp_classify_stage_ms last read them
 };
@@ -532,6 +538,23 @@ constexpr uint32_t kDpSegKeys = 16384;                     // ... of this many e
 int depth_begin_impl(spsp_ctx* ctx);
 int depth_add_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, uint64_t first, uint64_t n_keys);
 int depth_read_impl(spsp_ctx* ctx, uint32_t min_count, spsp_depth_row* rows, spsp_depth_totals* totals, const uint32_t** d_entry_count);
+// the two halves of a read's launches, for the profile as well (the context holds counters and its index has entries; no wait).
+// depth_launch_entry: dp_entry = c per index entry, and the word d_found (64 bits, cleared here) = the index keys found at min_count.
+// depth_launch_reduce: the rows of all references from dp_entry and a class byte per entry in the place of `unique` -> d_rows
+int depth_launch_entry(spsp_ctx* ctx, uint32_t min_count, unsigned long long** d_found);
+int depth_launch_reduce(spsp_ctx* ctx, const uint8_t* d_class, uint32_t min_count, spsp_depth_row* d_rows);
+// spsp_depth_files behind its argument checks; with `profile` one spsp_profile_device call behind the read and
+// <out_prefix>_profile.csv.gz beside the depth file
+struct ProfileAsk { uint32_t min_keys, max_rounds; std::vector<spsp_profile_row> rows; spsp_profile_totals totals; };
+int depth_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* const* reads_paths, uint32_t n_reads, uint32_t min_count, int precision,
+                     const char* out_prefix, int chatter, double rate, std::vector<spsp_depth_row>* rows, spsp_depth_totals* totals, ProfileAsk* profile);
+// spsp_profile.hip: the greedy rounds over the index's holder lists on the counters of the depth pass
+constexpr uint32_t kPfPickThreads = 1024;                  // k_pf_pick: one workgroup
+constexpr uint32_t kPfThreads = 256;                       // start and walk: 4 waves
+constexpr uint32_t kPfListCut = kCfListCut;                // the walk: a list of more holders than this is walked by the whole wave
+constexpr uint32_t kPfBatchFirst = 32, kPfBatchMax = 128;  // rounds queued per host wait: 32, 64, 128, 128, ...
+int profile_impl(spsp_ctx* ctx, uint32_t min_count, uint32_t min_keys, uint32_t max_rounds, spsp_profile_row* rows, uint64_t* n_rows, spsp_profile_totals* totals,
+                 const uint8_t** d_entry_assigned);
 // spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
 // groups as n_groups sketches back to back in context-owned arrays
 int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,
