@@ -1283,6 +1283,114 @@ int spsp_profile_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n
                        spsp_profile_row** profile_rows /* may be NULL; spsp_free */, uint64_t* n_profile_rows /* may be NULL */,
                        spsp_profile_totals* profile_totals /* may be NULL */);
 
+/* ------------------------------------------------------------ taxonomy ---- */
+/* The records of a sequence file assigned to the lowest common ancestor of their keys (not in the reference): classify answers
+ * with a reference, and a record from a region twenty strains share ties twenty ways; this answers with the node of a tree the
+ * record's keys agree on.
+ * TREE.  It has T nodes, with 1 <= T <= 1 048 576, numbered in preorder.  Node 0 is the root.  parent[0] = 0, parent[t] < t, and
+ * every subtree is a run of consecutive numbers [t, t + size[t]).  depth[t] <= 32.  Every reference j sits at a node ref_node[j].
+ * Several references may share a node.  A reference may sit at an inner node or at the root.
+ * anc(a, b) means "a is b or an ancestor of b".  In this numbering that is a <= b < a + size[a].  lca(S) is the deepest node that
+ * is anc of every member of S.
+ * INDEX.  For every distinct key x of the index, node(x) = lca{ ref_node[j] : K_j holds x }.  This is computed once, when the
+ * taxonomy is attached.
+ * RECORD.  Record r has the distinct key set Q_r.  This is exactly the Q_r of classify.
+ *   w(t) = the keys of Q_r found in the index whose node(x) is t.
+ *   hit_keys = Sum_t w(t).
+ *   path(t) = Sum_{a : anc(a, t)} w(a).
+ *   clade(t) = Sum_{d : anc(t, d)} w(d).
+ *   best = max{ path(t) : w(t) > 0 }.
+ *   W = { t : w(t) > 0, path(t) = best }.  winners = |W|.
+ *   start = lca(W).
+ * A node passes when clade(t) >= min_keys and clade(t) * den >= num * |Q_r|.  The products are 64-bit and equality passes.
+ * min_keys >= 1, 0 <= num <= den <= 1 000 000.
+ * The call is the first passing node on the way from start to the root.  If the root does not pass either, or there is no hit, the
+ * record is unclassified.  Its node is then 0xffffffff.
+ * For an unclassified record node = start = 0xffffffff when there is no hit, and clade = direct = 0.  score and winners still
+ * describe W.
+ * Nothing depends on the order of keys in a record, of holders in a list, or of lanes. */
+#define SPSP_TAXONOMY_NONE 0xffffffffu
+#define SPSP_TAXONOMY_MAX_NODES 1048576u
+#define SPSP_TAXONOMY_MAX_DEPTH 32u
+typedef struct spsp_taxonomy_record {    /* 40 bytes, one per record */
+    uint64_t length;      /* bases of the record: the caller's (the file driver fills it); the device call leaves it alone */
+    uint32_t keys;        /* |Q_r| */
+    uint32_t hit_keys;
+    uint32_t node;        /* the call, or SPSP_TAXONOMY_NONE */
+    uint32_t start;       /* lca(W), or SPSP_TAXONOMY_NONE without a hit */
+    uint32_t score;       /* best */
+    uint32_t clade;       /* clade(node) */
+    uint32_t direct;      /* w(node) */
+    uint32_t winners;     /* |W| */
+} spsp_taxonomy_record;
+/* A lineage file: one line per reference, in list order ("\r\n" tolerated, the final newline optional).  Each line is
+ * name;name;... from below the root down to the reference's own node, as GTDB and kraken2-inspect print lineages.  Names are
+ * trimmed of blanks; a name must be non-empty, without ',', '"', ';' or control characters; at most 32 names per line.  An empty
+ * line puts the reference at the root.  A node is a path: the same name under two parents is two nodes.  Nodes are numbered in
+ * preorder, children in order of first appearance in the file.  ref_node: n_ref words of the caller's.  *parent, *depth, *size
+ * (T words each) and *names (the T names back to back, each closed by a 0 byte; node 0 is "root") are released with spsp_free();
+ * any of the four may be NULL.  SPSP_ERR_FORMAT, the message naming the line: a bad name, too many names, more or fewer lines than
+ * n_ref, more than 1 048 576 nodes.  SPSP_ERR_ARG: n_ref outside 1 .. 65535. */
+int spsp_taxonomy_lineages_host(const char* text, uint64_t len, uint32_t n_ref, uint32_t* ref_node /* n_ref */, uint32_t** parent, uint32_t** depth,
+                                uint32_t** size, char** names, uint64_t* names_len, uint32_t* n_nodes);
+/* What spsp_taxonomy_index_device holds arrays of the caller's own to.  SPSP_ERR_ARG, the message naming the node or the
+ * reference: T outside 1 .. 1 048 576, n_ref outside 1 .. 65535, parent[0] != 0, parent[t] >= t, a node deeper than 32,
+ * ref_node[j] >= T, or a numbering that is not a preorder: parent[t] must be t - 1 or an ancestor of t - 1. */
+int spsp_taxonomy_check_host(const uint32_t* parent, uint32_t n_nodes, const uint32_t* ref_node, uint32_t n_ref);
+/* The cuts of the two forms for a tree of n_nodes (any pointer may be NULL).  small_hits: a record of at most this many hit keys
+ * is tallied by one wave, its keys' nodes sorted in LDS; a record of more takes a workgroup with one 32-bit counter per node.
+ * lds_nodes: up to this many nodes those counters sit in LDS, beyond it in a row of device memory per workgroup;
+ * *counters_in_lds = n_nodes <= lds_nodes.  list_cut: when the taxonomy is attached a key's list of more holders than this is
+ * folded by a whole wave instead of one lane (classify's list_cut).  SPSP_ERR_ARG: n_nodes outside 1 .. 1 048 576. */
+int spsp_taxonomy_plan_host(uint32_t n_nodes, uint32_t* small_hits, uint32_t* lds_nodes, uint32_t* counters_in_lds, uint32_t* list_cut);
+/* Attaches a taxonomy to the index spsp_classify_index_device built on the context: checks the arrays
+ * (spsp_taxonomy_check_host), uploads parent, size and ref_node, and one launch writes node(x) for every distinct key from the
+ * 16-bit holder lists -- a lane per key, a list of more than list_cut holders by a whole wave; the fold is the smallest and the
+ * largest ref_node of the list and one climb, because in preorder the lca of a set is the lca of its two extremes.  The taxonomy
+ * lives with the index and ends when the index ends (a prevalence, select, accumulation, groups or index call); a second attach
+ * replaces it.  The counters of a depth pass begun on the index are not touched.  *key_nodes_out (may be NULL) receives the device
+ * address of a context-owned uint32 array parallel to the index's key arrays (entry e at [e - h_sk_off[0]]): node(x) of that
+ * entry's key, valid until the next attach or index call.  One host wait.  SPSP_ERR_ARG: no index on the context, n_ref not the
+ * index's, arrays the check refuses. */
+int spsp_taxonomy_index_device(spsp_ctx* ctx, const uint32_t* parent, uint32_t n_nodes, const uint32_t* ref_node, uint32_t n_ref,
+                               const void** key_nodes_out /* may be NULL */);
+/* Assigns one batch of records, given exactly as spsp_classify_device takes them (any device arrays, distinct keys per record in
+ * any order, n_records bounded by the entry extent).  records: n_records (length is not touched).  Any number of batches on one
+ * index; one host wait per call.  Launches: classify's probe pass, unchanged (a record's hit keys route it; its work is ignored),
+ * a routing pass, and the two forms (spsp_taxonomy_plan_host).  SPSP_ERR_ARG (records zeroed): no index or no taxonomy on the
+ * context, d_q_kmer_hi against the index's k, min_keys, num or den out of range, decreasing offsets; SPSP_ERR_OVERFLOW: an extent
+ * above 0xfffffff0. */
+int spsp_taxonomy_device(spsp_ctx* ctx, const void* d_q_minimizer, const void* d_q_kmer_lo, const void* d_q_kmer_hi /* NULL if k <= 32 */,
+                         const uint64_t* h_rec_off /* n_records + 1 */, uint32_t n_records, uint32_t min_keys, uint32_t num, uint32_t den,
+                         spsp_taxonomy_record* records /* n_records */);
+/* While the context's timing is on a taxonomy call records events between its launches; this reads the milliseconds added up since
+ * the last read and clears them: ms[0] the probe pass, ms[1] the routing pass, ms[2] the wave form, ms[3] the workgroup form. */
+int spsp_taxonomy_stage_ms(spsp_ctx* ctx, double* ms /* 4 */);
+/* The text of <prefix>_taxonomy.csv.gz: "record,name,length,keys,hit_keys,taxon,depth,lineage,score,clade,direct,f_clade,winners"
+ * and one line per record.  taxon = the node's number, depth = its depth, lineage = the names from below the root down to it joined
+ * by ';' (empty for the root); an unclassified record has an empty taxon, depth and lineage.  f_clade = clade / keys as
+ * %.<precision>g (0 when keys == 0 or unclassified; it decides nothing).  node_names: n_nodes names.  A row that contradicts itself
+ * is SPSP_ERR_ARG, the message naming the record: hit_keys > keys, clade > hit_keys, direct > clade, score > hit_keys, node >=
+ * n_nodes and not SPSP_TAXONOMY_NONE, node not anc of start, winners == 0 with hit_keys > 0.  A tree spsp_taxonomy_check_host
+ * refuses is refused here.  *text is released with spsp_free(). */
+int spsp_taxonomy_csv_host(const spsp_taxonomy_record* records, uint64_t n_records, const char* const* record_names, const uint32_t* parent,
+                           uint32_t n_nodes, const char* const* node_names, int precision, char** text, uint64_t* len);
+/* The text of <prefix>_taxonomy_report.csv.gz (the columns of a Kraken report):
+ * "taxon,depth,name,lineage,references,records_clade,records_direct,bases_clade,bases_direct" and one line per node in preorder --
+ * references = the references that sit at the node itself, records_direct and bases_direct = the records called at the node and
+ * their lengths, _clade = the same over the node's subtree -- closed by one line ",,unclassified,,0,n,n,bases,bases".  The same
+ * refusals. */
+int spsp_taxonomy_report_csv_host(const spsp_taxonomy_record* records, uint64_t n_records, const uint32_t* parent, uint32_t n_nodes,
+                                  const char* const* node_names, const uint32_t* ref_node, uint32_t n_ref, char** text, uint64_t* len);
+/* The whole-file driver: spsp_classify_files' road (the same code: loading and `rate` refusals, the second context, one scan,
+ * batches of 65 535 records) with the lineage file read and parsed first, the taxonomy attached behind the index, and every batch
+ * handed to spsp_taxonomy_device.  Writes <out_prefix>_taxonomy.csv.gz and <out_prefix>_taxonomy_report.csv.gz (gzip level 1);
+ * nothing on any failure.  With chatter one line of totals: records, classified, and the share of the classified at depth 0.
+ * records (may be NULL) receives a copy released with spsp_free(); *n_records (may be NULL) their number. */
+int spsp_taxonomy_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                        uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                        spsp_taxonomy_record** records /* may be NULL; spsp_free */, uint64_t* n_records /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,11 @@ PROFILE_ROW_DTYPE = np.dtype([("sum", "<u8"), ("reference", "<u4"), ("keys", "<u
                               ("remaining", "<u4"), ("reserved", "<u4")])
 PROFILE_TOTALS_DTYPE = np.dtype([("found_sum", "<u8"), ("assigned_sum", "<u8"), ("found_keys", "<u4"), ("assigned_keys", "<u4")])
 
+# spsp_taxonomy_record: a record's call in the tree of the index's taxonomy (include/spsp.h)
+TAXONOMY_RECORD_DTYPE = np.dtype([("length", "<u8"), ("keys", "<u4"), ("hit_keys", "<u4"), ("node", "<u4"), ("start", "<u4"), ("score", "<u4"),
+                                  ("clade", "<u4"), ("direct", "<u4"), ("winners", "<u4")])
+TAXONOMY_NONE = 0xffffffff
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -157,6 +162,7 @@ ABI_SYMBOLS = [
     "spsp_classify_index_device", "spsp_classify_device", "spsp_classify_plan_host", "spsp_classify_csv_host", "spsp_classify_summary_csv_host", "spsp_classify_files", "spsp_classify_stage_ms",
     "spsp_depth_begin_device", "spsp_depth_add_device", "spsp_depth_read_device", "spsp_depth_plan_host", "spsp_depth_stage_ms", "spsp_depth_csv_host", "spsp_depth_files",
     "spsp_profile_device", "spsp_profile_stage_ms", "spsp_profile_counts", "spsp_profile_csv_host", "spsp_profile_files",
+    "spsp_taxonomy_lineages_host", "spsp_taxonomy_check_host", "spsp_taxonomy_plan_host", "spsp_taxonomy_index_device", "spsp_taxonomy_device", "spsp_taxonomy_stage_ms", "spsp_taxonomy_csv_host", "spsp_taxonomy_report_csv_host", "spsp_taxonomy_files",
 ]
 
 _lib = None
@@ -402,6 +408,25 @@ def lib():
         L.spsp_profile_csv_host.argtypes = [vp, u64, vp, P(cp), u32, i32, P(vp), P(u64)]
         L.spsp_profile_files.restype = i32
         L.spsp_profile_files.argtypes = [vp, P(cp), u32, P(cp), u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), vp, P(vp), P(u64), vp]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_taxonomy_device"):
+        L.spsp_taxonomy_lineages_host.restype = i32
+        L.spsp_taxonomy_lineages_host.argtypes = [cp, u64, u32, vp, P(vp), P(vp), P(vp), P(vp), P(u64), P(u32)]
+        L.spsp_taxonomy_check_host.restype = i32
+        L.spsp_taxonomy_check_host.argtypes = [vp, u32, vp, u32]
+        L.spsp_taxonomy_plan_host.restype = i32
+        L.spsp_taxonomy_plan_host.argtypes = [u32, P(u32), P(u32), P(u32), P(u32)]
+        L.spsp_taxonomy_index_device.restype = i32
+        L.spsp_taxonomy_index_device.argtypes = [vp, vp, u32, vp, u32, P(vp)]
+        L.spsp_taxonomy_device.restype = i32
+        L.spsp_taxonomy_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, vp]
+        L.spsp_taxonomy_stage_ms.restype = i32
+        L.spsp_taxonomy_stage_ms.argtypes = [vp, P(dbl)]
+        L.spsp_taxonomy_csv_host.restype = i32
+        L.spsp_taxonomy_csv_host.argtypes = [vp, u64, P(cp), vp, u32, P(cp), i32, P(vp), P(u64)]
+        L.spsp_taxonomy_report_csv_host.restype = i32
+        L.spsp_taxonomy_report_csv_host.argtypes = [vp, u64, vp, u32, P(cp), vp, u32, P(vp), P(u64)]
+        L.spsp_taxonomy_files.restype = i32
+        L.spsp_taxonomy_files.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(u64)]
     _lib = L
     return L
 
@@ -773,6 +798,67 @@ def classify_summary_csv(records, hits, ref_names, top):
     out, ln = C.c_void_p(), C.c_uint64()
     _check(lib().spsp_classify_summary_csv_host(records.ctypes.data if len(records) else None, hits.ctypes.data if len(hits) else None, len(records), f_arr,
                                                 len(ref_names), top, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def taxonomy_lineages(text, n_ref):
+    """spsp_taxonomy_lineages_host: the text of a lineage file (one name;name;... line per reference, in list order) for n_ref
+    references -> dict(parent, depth, size: np.uint32[T] in preorder, ref_node: np.uint32[n_ref], names: the T names, node 0 is
+    "root")"""
+    if isinstance(text, str):
+        text = text.encode()
+    ref_node = np.zeros(max(n_ref, 1), dtype=np.uint32)
+    parent, depth, size, names, ln, T = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint32()
+    _check(lib().spsp_taxonomy_lineages_host(text, len(text), n_ref, ref_node.ctypes.data, C.byref(parent), C.byref(depth), C.byref(size), C.byref(names),
+                                             C.byref(ln), C.byref(T)))
+    arrays = [np.frombuffer(_take(p, T.value * 4), dtype=np.uint32).copy() for p in (parent, depth, size)]
+    blob = _take(names, ln.value)
+    return {"parent": arrays[0], "depth": arrays[1], "size": arrays[2], "ref_node": ref_node[:n_ref], "names": [x.decode() for x in blob.split(b"\0")[:T.value]]}
+
+
+def taxonomy_check(parent, ref_node):
+    """spsp_taxonomy_check_host: raises SpspError(ERR_ARG) unless parent is a tree of 1 .. 1 048 576 nodes numbered in preorder, no
+    deeper than 32, and every ref_node names one of its nodes"""
+    parent = np.ascontiguousarray(parent, dtype=np.uint32)
+    ref_node = np.ascontiguousarray(ref_node, dtype=np.uint32)
+    _check(lib().spsp_taxonomy_check_host(parent.ctypes.data if len(parent) else None, len(parent), ref_node.ctypes.data if len(ref_node) else None, len(ref_node)))
+
+
+def taxonomy_plan(n_nodes):
+    """spsp_taxonomy_plan_host: the cuts of the two forms for a tree of n_nodes -> dict(small_hits: the hit keys up to which one wave
+    sorts a record's nodes in LDS, lds_nodes: the nodes up to which the workgroup form keeps its counters in LDS, counters_in_lds:
+    whether they do for n_nodes, list_cut: the holders above which a whole wave folds a key's list when the taxonomy is attached)"""
+    a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_taxonomy_plan_host(n_nodes, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return {"small_hits": a.value, "lds_nodes": b.value, "counters_in_lds": bool(c.value), "list_cut": d.value}
+
+
+def taxonomy_csv(records, record_names, parent, node_names, precision=6):
+    """spsp_taxonomy_csv_host: records (TAXONOMY_RECORD_DTYPE), their names, the tree's parents and its nodes' names -> the text of
+    <prefix>_taxonomy.csv.gz"""
+    records = np.ascontiguousarray(records, dtype=TAXONOMY_RECORD_DTYPE)
+    parent = np.ascontiguousarray(parent, dtype=np.uint32)
+    if len(record_names) != len(records) or len(node_names) != len(parent):
+        raise ValueError("taxonomy_csv: one name per record and per node")
+    r_arr, _a = _paths_array(record_names)
+    n_arr, _b = _paths_array(node_names)
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_taxonomy_csv_host(records.ctypes.data if len(records) else None, len(records), r_arr, parent.ctypes.data if len(parent) else None,
+                                        len(parent), n_arr, precision, C.byref(out), C.byref(ln)))
+    return _take(out, ln.value)
+
+
+def taxonomy_report_csv(records, parent, node_names, ref_node):
+    """spsp_taxonomy_report_csv_host: the same rows and the references' nodes -> the text of <prefix>_taxonomy_report.csv.gz"""
+    records = np.ascontiguousarray(records, dtype=TAXONOMY_RECORD_DTYPE)
+    parent = np.ascontiguousarray(parent, dtype=np.uint32)
+    ref_node = np.ascontiguousarray(ref_node, dtype=np.uint32)
+    if len(node_names) != len(parent):
+        raise ValueError("taxonomy_report_csv: one name per node")
+    n_arr, _b = _paths_array(node_names)
+    out, ln = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_taxonomy_report_csv_host(records.ctypes.data if len(records) else None, len(records), parent.ctypes.data if len(parent) else None,
+                                               len(parent), n_arr, ref_node.ctypes.data if len(ref_node) else None, len(ref_node), C.byref(out), C.byref(ln)))
     return _take(out, ln.value)
 
 
@@ -1537,6 +1623,46 @@ class Context:
                                          _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n)))
         return (np.frombuffer(_take(recs, n.value * CLASSIFY_RECORD_DTYPE.itemsize), dtype=CLASSIFY_RECORD_DTYPE).copy(),
                 np.frombuffer(_take(hits, n.value * top * CLASSIFY_HIT_DTYPE.itemsize), dtype=CLASSIFY_HIT_DTYPE).copy().reshape(n.value, top))
+
+    def taxonomy_index_device(self, parent, ref_node, want_key_nodes=False):
+        """spsp_taxonomy_index_device: a tree (parents in preorder) and the references' nodes attached to the context's index
+        (classify_index_device first); it ends with that index [-> d_key_nodes: the device address of the context's uint32 array
+        of node(x) per index entry, valid until the next attach or index call]"""
+        parent = np.ascontiguousarray(parent, dtype=np.uint32)
+        ref_node = np.ascontiguousarray(ref_node, dtype=np.uint32)
+        d = C.c_void_p()
+        _check(lib().spsp_taxonomy_index_device(self._h, parent.ctypes.data if len(parent) else None, len(parent), ref_node.ctypes.data if len(ref_node) else None,
+                                                len(ref_node), C.byref(d) if want_key_nodes else None))
+        return d.value if want_key_nodes else None
+
+    def taxonomy_device(self, d_min, d_lo, d_hi, rec_off, min_keys=1, num=0, den=1):
+        """spsp_taxonomy_device: the records whose distinct keys sit at [rec_off[r], rec_off[r + 1]) of key arrays on the device,
+        against the taxonomy of the context's index -> records TAXONOMY_RECORD_DTYPE[n] with length 0"""
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        if len(rec_off) < 1:
+            raise ValueError("taxonomy_device: n_records + 1 record offsets")
+        n = len(rec_off) - 1
+        records = np.zeros(max(n, 1), dtype=TAXONOMY_RECORD_DTYPE)
+        _check(lib().spsp_taxonomy_device(self._h, d_min, d_lo, d_hi, rec_off.ctypes.data, n, min_keys, num, den, records.ctypes.data))
+        return records[:n]
+
+    def taxonomy_stage_ms(self):
+        """spsp_taxonomy_stage_ms: with timing_enable() on, the milliseconds of the taxonomy calls' launches since the last read ->
+        dict(probe, route, wave_form, workgroup_form)"""
+        ms = (C.c_double * 4)()
+        _check(lib().spsp_taxonomy_stage_ms(self._h, ms))
+        return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
+
+    def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0):
+        """spsp_taxonomy_files: the sketch files of the references, a FASTA / FASTQ file of records (gzip or plain) and the lineage
+        file of the references -> <prefix>_taxonomy.csv.gz, <prefix>_taxonomy_report.csv.gz and the records.  rate: as
+        classify_files (0.0, a rate, or "auto"); sketches of different rates need one"""
+        arr, _alive = _paths_array(paths)
+        recs, n = C.c_void_p(), C.c_uint64()
+        self._cf_n_ref = None
+        _check(lib().spsp_taxonomy_files(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
+                                         prefix.encode(), 0, _rate_arg(rate), C.byref(recs), C.byref(n)))
+        return np.frombuffer(_take(recs, n.value * TAXONOMY_RECORD_DTYPE.itemsize), dtype=TAXONOMY_RECORD_DTYPE).copy()
 
     def depth_begin(self):
         """spsp_depth_begin_device: one cleared counter per distinct key of the context's index (classify_index_device); they end

@@ -125,12 +125,14 @@ int main(int argc, char** argv) {
     bool classify = false;
     int cf_opts = 0;                 // -Y or -V seen
     long long cf_top = 1, cf_min_keys = 1;
+    string lineages_file;            // -H <lineages file>: with -X, the records go to the lowest common ancestor of their keys (not in the reference's option string)
+    bool taxonomy = false, cf_top_seen = false;
     vector<string> reads_files;      // -D <reads file> [-D <more> ...] [-W <min_count>]: neither letter is in the reference's option string
     bool dp_min_seen = false;
     long long dp_min_count = 1;
     bool profile = false;            // -B <min_keys>: the profile behind the depth of -D (not in the reference's option string either)
     long long pf_min_keys = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:")) != -1) {
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:")) != -1) {
         switch (ch) {
             case 'D': reads_files.push_back(optarg); break;
             case 'W': {
@@ -149,11 +151,13 @@ int main(int argc, char** argv) {
             }
             case 'G': labels_file = optarg; groups = true; break;
             case 'X': records_file = optarg; classify = true; break;
+            case 'H': lineages_file = optarg; taxonomy = true; break;
             case 'Y': {
                 char* e = nullptr;
                 cf_top = strtoll(optarg, &e, 10);
                 if (e == optarg || *e || cf_top < 1 || cf_top > 64) { cout << "-Y takes the number of matches listed per record, an integer in 1 .. 64, not '" << optarg << "'" << endl; return 1; }
                 ++cf_opts;
+                cf_top_seen = true;
                 break;
             }
             case 'V': {
@@ -282,6 +286,8 @@ int main(int argc, char** argv) {
     if (cluster_opts > 1) { cout << "-c (Jaccard) and -C (containment) cluster the index: one of them, once" << endl; return 1; }
     if (cluster_opts && (query != "" || gather)) { cout << "-c / -C cluster the index all versus all: not together with -q or -g" << endl; return 1; }
     if (nb_opts > 1) { cout << "-J (Jaccard), -K (the larger containment) and -I (the row's containment) set the threshold of -N: one of them, once" << endl; return 1; }
+    if (taxonomy && !classify) { cout << "-H gives the lineages of the index for the records of -X <records file>: it needs -X" << endl; return 1; }
+    if (taxonomy && cf_top_seen) { cout << "-H assigns every record to one node of the tree: not together with -Y (-V and -I set its threshold)" << endl; return 1; }
     if (cf_opts && !classify) { cout << "-Y and -V belong to the classification of -X <records file>: they need -X" << endl; return 1; }
     if (classify && (query != "" || gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts || select_opts || accumulation || groups ||
                      (nb_opts && nb_metric != SPSP_NEIGHBOUR_CONTAINED))) {
@@ -336,6 +342,7 @@ int main(int argc, char** argv) {
         cout << "Core arguments:" << endl
              << "-f Index file of files (mandatory)" << endl
              << "-q Query file of files (\"\" for all versus all comparison of the index)" << endl
+             << "-H Lineage file, one name;name;... line per index sketch: with -X <records file>, each record goes to the lowest common ancestor of its keys" << endl
              << "Ouput arguments:" << endl
              << "-m Minimum value to be output (0.0)" << endl
              << "-p Required precision to be output in the CSV (6)" << endl
@@ -398,11 +405,14 @@ int main(int argc, char** argv) {
         // one device, as gather (the driver opens a second context on it for the records)
         spsp_ctx* ctx = nullptr;
         int rc = spsp_create(devices[0], nullptr, &ctx);
-        if (rc == SPSP_OK) rc = spsp_classify_files(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den,
+        if (rc == SPSP_OK && taxonomy)
+            rc = spsp_taxonomy_files(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den, (int)p,
+                                     output_name.c_str(), 1, rate, nullptr, nullptr);
+        else if (rc == SPSP_OK) rc = spsp_classify_files(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den,
                                                     (int)p, output_name.c_str(), 1, rate, nullptr, nullptr, nullptr);
         const string err = rc != SPSP_OK ? spsp_last_error() : "";
         if (ctx) spsp_destroy(ctx);
-        if (rc != SPSP_OK) { cout << "Classification failed: " << err << endl; return 1; }
+        if (rc != SPSP_OK) { cout << (taxonomy ? "Taxonomy failed: " : "Classification failed: ") << err << endl; return 1; }
         return 0;
     }
     if (groups) {

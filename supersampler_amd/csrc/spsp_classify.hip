@@ -309,6 +309,20 @@ int classify_index_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const u
     return SPSP_OK;
 }
 
+int classify_probe_launch(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* d_off, uint32_t n_rec,
+                          uint64_t all_keys, uint32_t* d_kn, unsigned long long* d_work, uint32_t* d_hit) {
+    const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
+    const SortedKeys Q{q_mn, q_lo, q_hi}, K{X.mn, X.lo, X.hi};
+    const unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
+    const uint32_t gp = (uint32_t)((all_keys + kCfThreads - 1) / kCfThreads);
+    if (X.has_hi) hipLaunchKernelGGL(k_cf_probe<true>, dim3(gp), dim3(kCfThreads), 0, ctx->stream, Q, d_off, n_rec, K, X.first, X.entries, d_tbl,
+                                     ctx->pv_log2cap, X.key_no, X.key_start, d_kn, d_work, d_hit);
+    else hipLaunchKernelGGL(k_cf_probe<false>, dim3(gp), dim3(kCfThreads), 0, ctx->stream, Q, d_off, n_rec, K, X.first, X.entries, d_tbl,
+                            ctx->pv_log2cap, X.key_no, X.key_start, d_kn, d_work, d_hit);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
+
 int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
                          uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, spsp_classify_record* records, spsp_classify_hit* hits) {
     int rc;
@@ -359,19 +373,14 @@ int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
     SPSP_HIP(hipMemsetAsync(d_words, 0, kCfqWords * 4, ctx->stream));
     SPSP_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_rec * 16, ctx->stream));
     SPSP_HIP(hipMemsetAsync(d_hits, 0, (size_t)n_rec * top * sizeof(spsp_classify_hit), ctx->stream));
-    const SortedKeys Q{q_mn, q_lo, q_hi}, K{X.mn, X.lo, X.hi};
-    const unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
-    const uint32_t gp = (uint32_t)((all_keys + kCfThreads - 1) / kCfThreads), gr = (uint32_t)(((uint64_t)n_rec + kCfThreads - 1) / kCfThreads);
+    const uint32_t gr = (uint32_t)(((uint64_t)n_rec + kCfThreads - 1) / kCfThreads);
     hipEvent_t* ev = nullptr;
     if (ctx->timing) {                                     // spsp_timing_enable: events between the launches (spsp_classify_stage_ms)
         for (hipEvent_t& e : ctx->cf_events) if (!e) SPSP_HIP(hipEventCreate(&e));
         ev = ctx->cf_events;
         SPSP_HIP(hipEventRecord(ev[0], ctx->stream));
     }
-    if (X.has_hi) hipLaunchKernelGGL(k_cf_probe<true>, dim3(gp), dim3(kCfThreads), 0, ctx->stream, Q, (const uint64_t*)d_off, n_rec, K, X.first, X.entries, d_tbl,
-                                     ctx->pv_log2cap, X.key_no, X.key_start, d_kn, d_work, d_hit);
-    else hipLaunchKernelGGL(k_cf_probe<false>, dim3(gp), dim3(kCfThreads), 0, ctx->stream, Q, (const uint64_t*)d_off, n_rec, K, X.first, X.entries, d_tbl,
-                            ctx->pv_log2cap, X.key_no, X.key_start, d_kn, d_work, d_hit);
+    if ((rc = classify_probe_launch(ctx, q_mn, q_lo, q_hi, d_off, n_rec, all_keys, d_kn, d_work, d_hit))) return rc;
     if (ev) SPSP_HIP(hipEventRecord(ev[1], ctx->stream));
     hipLaunchKernelGGL(k_cf_route, dim3(gr), dim3(kCfThreads), 0, ctx->stream, (const uint64_t*)d_off, n_rec, (const unsigned long long*)d_work,
                        (const uint32_t*)d_hit, d_words, d_q_small, d_q_large, d_rec);
@@ -510,12 +519,42 @@ int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
     return SPSP_OK;
 }
 
-// the records of a text classified against the index on ctx
-static int classify_text(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path, uint32_t top,
-                         uint32_t min_keys, uint32_t num, uint32_t den, std::vector<std::string>* names, std::vector<spsp_classify_record>* recs,
-                         std::vector<spsp_classify_hit>* hits) {
-    return records_text_batches(
-        ctx, side, p, text, n_text, path, names,
+// the road of spsp_classify_files and spsp_taxonomy_files: load, refusals, decode, index, on_index, the records through their batches
+int records_files_road(FilesRun& run, const char* records_path, double rate, const std::function<int()>& on_index, std::vector<std::string>* names,
+                       const std::function<int(uint32_t, const uint64_t*)>& on_records, const std::function<int(const RecordBatch&)>& on_batch, double* t1) {
+    spsp_ctx* ctx = run.ctx;
+    int rc = run.load(rate);
+    if (!rc) rc = run.refuse_k_eq_m(rc, "classification is");
+    double rec_rate = run.L.ds_rate;                       // the records are scanned at ONE threshold: mixed rates need a rate, as -S
+    if (!rc) rc = sketches_out_rate(run.L, run.paths, run.n, &rec_rate);
+    if ((rc = run.begin(rc))) return rc;
+    const DecodedKeys& keys = run.keys;
+    rc = run.decode();
+    if (!rc) rc = classify_index_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), run.n);
+    if (!rc) rc = on_index();
+    if (!rc) {
+        uint8_t* text = nullptr; uint64_t n_text = 0;
+        spsp_ctx* side = nullptr;
+        spsp_params p{};
+        p.k = keys.k; p.m = keys.m; p.threshold = spsp_threshold_host(keys.k, keys.m, rec_rate); p.abundance = 1; p.flags = 0;
+        if (!(rc = spsp_read_file_host(records_path, &text, &n_text)) && !(rc = spsp_create(ctx->device, nullptr, &side)))
+            rc = records_text_batches(ctx, side, &p, text, n_text, records_path, names, on_records, on_batch);
+        if (side) { (void)hipStreamSynchronize(side->stream); spsp_destroy(side); }
+        spsp_free(text);
+    }
+    *t1 = run.end();
+    return rc;
+}
+
+// spsp_classify_files behind its argument checks
+static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys, uint32_t num,
+                          uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_classify_record>* recs,
+                          std::vector<spsp_classify_hit>* hits) {
+    FilesRun run(ctx, paths, n_ref, chatter);
+    std::vector<std::string> names;
+    double t1 = 0;
+    int rc = records_files_road(
+        run, records_path, rate, [] { return SPSP_OK; }, &names,
         [&](uint32_t n_rec, const uint64_t* rec_off) {
             recs->assign(n_rec, spsp_classify_record{});
             hits->assign((size_t)n_rec * top, spsp_classify_hit{});
@@ -525,34 +564,8 @@ static int classify_text(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
         [&](const RecordBatch& B) {
             return classify_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, top, min_keys, num, den, recs->data() + B.first_record,
                                         hits->data() + (size_t)B.first_record * top);
-        });
-}
-
-// spsp_classify_files behind its argument checks
-static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys, uint32_t num,
-                          uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_classify_record>* recs,
-                          std::vector<spsp_classify_hit>* hits) {
-    FilesRun run(ctx, paths, n_ref, chatter);
-    int rc = run.load(rate);
-    if (!rc) rc = run.refuse_k_eq_m(rc, "classification is");
-    double rec_rate = run.L.ds_rate;                       // the records are scanned at ONE threshold: mixed rates need a rate, as -S
-    if (!rc) rc = sketches_out_rate(run.L, paths, n_ref, &rec_rate);
-    if ((rc = run.begin(rc))) return rc;
-    const DecodedKeys& keys = run.keys;
-    rc = run.decode();
-    if (!rc) rc = classify_index_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n_ref);
-    std::vector<std::string> names;
-    if (!rc) {
-        uint8_t* text = nullptr; uint64_t n_text = 0;
-        spsp_ctx* side = nullptr;
-        spsp_params p{};
-        p.k = keys.k; p.m = keys.m; p.threshold = spsp_threshold_host(keys.k, keys.m, rec_rate); p.abundance = 1; p.flags = 0;
-        if (!(rc = spsp_read_file_host(records_path, &text, &n_text)) && !(rc = spsp_create(ctx->device, nullptr, &side)))
-            rc = classify_text(ctx, side, &p, text, n_text, records_path, top, min_keys, num, den, &names, recs, hits);
-        if (side) { (void)hipStreamSynchronize(side->stream); spsp_destroy(side); }
-        spsp_free(text);
-    }
-    const double t1 = run.end();
+        },
+        &t1);
     if (rc) return rc;
     std::vector<const char*> name_ptr(names.size());
     for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();

@@ -1857,6 +1857,13 @@ int classify_check_args(uint32_t top, uint32_t min_keys, uint32_t num, uint32_t 
     if (den == 0 || num > den || den > kCfMaxDen) { set_error("classification threshold %u / %u: needs 0 <= num <= den, 1 <= den <= %u", num, den, kCfMaxDen); return SPSP_ERR_ARG; }
     return SPSP_OK;
 }
+
+// spsp_taxonomy.hip: likewise
+int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den) {
+    if (min_keys == 0) { set_error("taxonomy: min_keys is 1 at the least"); return SPSP_ERR_ARG; }
+    if (den == 0 || num > den || den > kCfMaxDen) { set_error("taxonomy threshold %u / %u: needs 0 <= num <= den, 1 <= den <= %u", num, den, kCfMaxDen); return SPSP_ERR_ARG; }
+    return SPSP_OK;
+}
 }  // namespace spsp
 
 namespace {
@@ -2391,6 +2398,243 @@ int spsp_classify_summary_csv_host(const spsp_classify_record* records, const sp
         out += std::to_string(listed[j]); out += '\n';
     }
     out += "unclassified," + std::to_string(none) + ',' + std::to_string(none_bases) + ",0,0\n";
+    return text_out(out, text, len);
+}
+
+// ------------------------------------------------------------------------------------------------ taxonomy
+// a lineage file: one line per reference, names from below the root down, joined by ';'; a node is a path
+int spsp_taxonomy_lineages_host(const char* text, uint64_t len, uint32_t n_ref, uint32_t* ref_node, uint32_t** parent, uint32_t** depth, uint32_t** size,
+                                char** names, uint64_t* names_len, uint32_t* n_nodes) {
+    using namespace spsp;
+    if (parent) *parent = nullptr;
+    if (depth) *depth = nullptr;
+    if (size) *size = nullptr;
+    if (names) *names = nullptr;
+    if (names_len) *names_len = 0;
+    if (n_nodes) *n_nodes = 0;
+    if ((!text && len) || !ref_node || !n_nodes) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    // the trie in order of appearance: node 0 is the root
+    struct Node { uint32_t parent; std::string name; std::vector<uint32_t> kids; std::unordered_map<std::string, uint32_t> by_name; };
+    std::vector<Node> trie(1);
+    trie[0].parent = 0; trie[0].name = "root";
+    std::vector<uint32_t> at(n_ref, 0);
+    uint64_t line = 0, pos = 0;
+    while (pos < len) {
+        uint64_t end = pos;
+        while (end < len && text[end] != '\n') ++end;
+        uint64_t stop = end;
+        if (stop > pos && text[stop - 1] == '\r') --stop;  // ("\r\n" is tolerated)
+        ++line;
+        const unsigned long long ln = (unsigned long long)line;
+        if (line > n_ref) { set_error("lineages: line %llu: more lines than the %u references", ln, n_ref); return SPSP_ERR_FORMAT; }
+        uint64_t a = pos, z = stop;
+        while (a < z && (text[a] == ' ' || text[a] == '\t')) ++a;
+        while (z > a && (text[z - 1] == ' ' || text[z - 1] == '\t')) --z;
+        uint32_t cur = 0, count = 0;
+        for (uint64_t s0 = a; a < z;) {                    // (an empty line: the reference sits at the root)
+            uint64_t e = s0;
+            while (e < z && text[e] != ';') ++e;
+            uint64_t na = s0, nz = e;
+            while (na < nz && (text[na] == ' ' || text[na] == '\t')) ++na;
+            while (nz > na && (text[nz - 1] == ' ' || text[nz - 1] == '\t')) --nz;
+            if (na == nz) { set_error("lineages: line %llu: an empty name", ln); return SPSP_ERR_FORMAT; }
+            for (uint64_t q = na; q < nz; ++q) {
+                const unsigned char c = (unsigned char)text[q];
+                if (c == ',' || c == '"' || c < 0x20 || c == 0x7f) {
+                    set_error("lineages: line %llu: a name holds ',', '\"' or a control character (byte 0x%02x)", ln, (unsigned)c);
+                    return SPSP_ERR_FORMAT;
+                }
+            }
+            if (++count > kTxMaxDepth) { set_error("lineages: line %llu: more than %u names", ln, kTxMaxDepth); return SPSP_ERR_FORMAT; }
+            const std::string name(text + na, (size_t)(nz - na));
+            const auto it = trie[cur].by_name.find(name);
+            if (it != trie[cur].by_name.end()) cur = it->second;
+            else {
+                if (trie.size() >= kTxMaxNodes) { set_error("lineages: line %llu: more than %u nodes", ln, kTxMaxNodes); return SPSP_ERR_FORMAT; }
+                const uint32_t id = (uint32_t)trie.size();
+                trie[cur].by_name.emplace(name, id);
+                trie[cur].kids.push_back(id);
+                trie.emplace_back();
+                trie.back().parent = cur; trie.back().name = name;
+                cur = id;
+            }
+            if (e == z) break;
+            s0 = e + 1;                                    // (a ';' at the line's end: one more, empty, name)
+        }
+        at[line - 1] = cur;
+        pos = end + 1;                                     // (the final newline is optional: nothing behind it is no line)
+    }
+    if (line != n_ref) {
+        set_error("lineages: line %llu: the file ends after %llu line(s), %u references are listed", (unsigned long long)(line + 1), (unsigned long long)line, n_ref);
+        return SPSP_ERR_FORMAT;
+    }
+    // preorder numbers, children in order of first appearance
+    const uint32_t T = (uint32_t)trie.size();
+    std::vector<uint32_t> number(T, 0), order;
+    order.reserve(T);
+    std::vector<std::pair<uint32_t, uint32_t>> stack{{0u, 0u}};
+    order.push_back(0);
+    while (!stack.empty()) {
+        auto& top = stack.back();
+        if (top.second == trie[top.first].kids.size()) { stack.pop_back(); continue; }
+        const uint32_t kid = trie[top.first].kids[top.second++];
+        number[kid] = (uint32_t)order.size();
+        order.push_back(kid);
+        stack.push_back({kid, 0u});
+    }
+    uint32_t* arr[3] = {nullptr, nullptr, nullptr};
+    for (uint32_t*& p : arr)
+        if (!(p = (uint32_t*)malloc((size_t)T * 4))) { for (uint32_t* q : arr) free(q); set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    std::string blob;
+    for (uint32_t t = 0; t < T; ++t) {
+        const Node& nd = trie[order[t]];
+        arr[0][t] = number[nd.parent];
+        arr[1][t] = t ? arr[1][arr[0][t]] + 1u : 0u;
+        arr[2][t] = 1u;
+        blob.append(nd.name); blob.push_back('\0');
+    }
+    for (uint32_t t = T - 1; t >= 1; --t) arr[2][arr[0][t]] += arr[2][t];
+    for (uint32_t j = 0; j < n_ref; ++j) ref_node[j] = number[at[j]];
+    if (names) {
+        uint64_t l = 0;
+        const int rc = text_out(blob, names, &l);
+        if (rc) { for (uint32_t* q : arr) free(q); return rc; }
+        if (names_len) *names_len = l;
+    }
+    if (parent) *parent = arr[0]; else free(arr[0]);
+    if (depth) *depth = arr[1]; else free(arr[1]);
+    if (size) *size = arr[2]; else free(arr[2]);
+    *n_nodes = T;
+    return SPSP_OK;
+}
+
+// the tree's depths and subtree sizes from its parents, or why the arrays are no preorder tree
+static int taxonomy_tree(const uint32_t* parent, uint32_t T, std::vector<uint32_t>* depth, std::vector<uint32_t>* size) {
+    using namespace spsp;
+    if (!parent) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (T == 0 || T > kTxMaxNodes) { set_error("a taxonomy takes 1 .. %u nodes (T = %u)", kTxMaxNodes, T); return SPSP_ERR_ARG; }
+    if (parent[0] != 0) { set_error("taxonomy: node 0 is the root: its parent is 0, not %u", parent[0]); return SPSP_ERR_ARG; }
+    depth->assign(T, 0);
+    for (uint32_t t = 1; t < T; ++t) {
+        if (parent[t] >= t) { set_error("taxonomy: node %u has parent %u: a parent comes before its children", t, parent[t]); return SPSP_ERR_ARG; }
+        (*depth)[t] = (*depth)[parent[t]] + 1u;
+        if ((*depth)[t] > kTxMaxDepth) { set_error("taxonomy: node %u is deeper than %u", t, kTxMaxDepth); return SPSP_ERR_ARG; }
+        uint32_t a = t - 1u;                               // preorder: the parent is the node in front or one of its ancestors
+        while (a != parent[t] && a != 0u) a = parent[a];
+        if (a != parent[t]) { set_error("taxonomy: node %u is not numbered in preorder: its parent %u is no ancestor of node %u", t, parent[t], t - 1u); return SPSP_ERR_ARG; }
+    }
+    if (size) {
+        size->assign(T, 1);
+        for (uint32_t t = T - 1; t >= 1; --t) (*size)[parent[t]] += (*size)[t];
+    }
+    return SPSP_OK;
+}
+
+int spsp_taxonomy_check_host(const uint32_t* parent, uint32_t n_nodes, const uint32_t* ref_node, uint32_t n_ref) {
+    using namespace spsp;
+    if (!parent || !ref_node) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    std::vector<uint32_t> depth;
+    if (const int rc = taxonomy_tree(parent, n_nodes, &depth, nullptr)) return rc;
+    for (uint32_t j = 0; j < n_ref; ++j)
+        if (ref_node[j] >= n_nodes) { set_error("taxonomy: reference %u sits at node %u, there are %u nodes", j, ref_node[j], n_nodes); return SPSP_ERR_ARG; }
+    return SPSP_OK;
+}
+
+// the cuts of spsp_taxonomy.hip: the constants of spsp_internal.h
+int spsp_taxonomy_plan_host(uint32_t n_nodes, uint32_t* small_hits, uint32_t* lds_nodes, uint32_t* counters_in_lds, uint32_t* list_cut) {
+    using namespace spsp;
+    if (n_nodes == 0 || n_nodes > kTxMaxNodes) { set_error("a taxonomy takes 1 .. %u nodes (T = %u)", kTxMaxNodes, n_nodes); return SPSP_ERR_ARG; }
+    if (small_hits) *small_hits = kTxSmallHits;
+    if (lds_nodes) *lds_nodes = kTxLdsNodes;
+    if (counters_in_lds) *counters_in_lds = n_nodes <= kTxLdsNodes ? 1u : 0u;
+    if (list_cut) *list_cut = kTxListCut;
+    return SPSP_OK;
+}
+
+// a record's row that cannot be a taxonomy call's: why, or null
+static const char* taxonomy_row_wrong(const spsp_taxonomy_record& r, uint32_t T, const std::vector<uint32_t>& size) {
+    if (r.hit_keys > r.keys) return "more hit keys than keys";
+    if (r.clade > r.hit_keys) return "a clade of more keys than the record has hit keys";
+    if (r.direct > r.clade) return "more keys at the node than in its clade";
+    if (r.score > r.hit_keys) return "a score above the hit keys";
+    if (r.node != SPSP_TAXONOMY_NONE && r.node >= T) return "a node outside the tree";
+    if (r.node != SPSP_TAXONOMY_NONE && !(r.node <= r.start && r.start - r.node < size[r.node])) return "a node that is no ancestor of the start";
+    if (r.winners == 0 && r.hit_keys > 0) return "hit keys without a winner";
+    return nullptr;
+}
+
+static void taxonomy_lineage(const uint32_t* parent, const char* const* node_names, uint32_t t, std::string* out) {
+    uint32_t way[spsp::kTxMaxDepth + 1], n = 0;
+    for (; t != 0u; t = parent[t]) way[n++] = t;           // (depth <= 32: the tree was checked)
+    out->clear();
+    while (n) { *out += node_names[way[--n]]; if (n) *out += ';'; }
+}
+
+int spsp_taxonomy_csv_host(const spsp_taxonomy_record* records, uint64_t n_records, const char* const* record_names, const uint32_t* parent,
+                           uint32_t n_nodes, const char* const* node_names, int precision, char** text, uint64_t* len) {
+    if (!text || !len || !node_names || (n_records && (!records || !record_names))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    std::vector<uint32_t> depth, size;
+    if (const int rc = taxonomy_tree(parent, n_nodes, &depth, &size)) return rc;
+    std::string out = "record,name,length,keys,hit_keys,taxon,depth,lineage,score,clade,direct,f_clade,winners\n", lineage;
+    char num[64];
+    for (uint64_t r = 0; r < n_records; ++r) {
+        const spsp_taxonomy_record& rec = records[r];
+        if (const char* why = taxonomy_row_wrong(rec, n_nodes, size)) { set_error("taxonomy record %llu contradicts itself: %s", (unsigned long long)r, why); return SPSP_ERR_ARG; }
+        out += std::to_string(r); out += ',';
+        out += record_names[r]; out += ',';
+        out += std::to_string(rec.length); out += ',';
+        out += std::to_string(rec.keys); out += ',';
+        out += std::to_string(rec.hit_keys); out += ',';
+        const bool called = rec.node != SPSP_TAXONOMY_NONE;
+        if (called) {
+            taxonomy_lineage(parent, node_names, rec.node, &lineage);
+            out += std::to_string(rec.node); out += ',';
+            out += std::to_string(depth[rec.node]); out += ',';
+            out += lineage; out += ',';
+        } else out += ",,,";
+        out += std::to_string(rec.score); out += ',';
+        out += std::to_string(rec.clade); out += ',';
+        out += std::to_string(rec.direct); out += ',';
+        out.append(num, format_g(num, sizeof num, precision, called && rec.keys ? (double)rec.clade / (double)rec.keys : 0.0)); out += ',';
+        out += std::to_string(rec.winners); out += '\n';
+    }
+    return text_out(out, text, len);
+}
+
+int spsp_taxonomy_report_csv_host(const spsp_taxonomy_record* records, uint64_t n_records, const uint32_t* parent, uint32_t n_nodes,
+                                  const char* const* node_names, const uint32_t* ref_node, uint32_t n_ref, char** text, uint64_t* len) {
+    if (!text || !len || !node_names || (n_records && !records)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (const int rc = spsp_taxonomy_check_host(parent, n_nodes, ref_node, n_ref)) return rc;
+    std::vector<uint32_t> depth, size;
+    if (const int rc = taxonomy_tree(parent, n_nodes, &depth, &size)) return rc;
+    const uint32_t T = n_nodes;
+    std::vector<uint64_t> refs(T, 0), rec_direct(T, 0), rec_clade(T, 0), base_direct(T, 0), base_clade(T, 0);
+    uint64_t none = 0, none_bases = 0;
+    for (uint32_t j = 0; j < n_ref; ++j) ++refs[ref_node[j]];
+    for (uint64_t r = 0; r < n_records; ++r) {
+        const spsp_taxonomy_record& rec = records[r];
+        if (const char* why = taxonomy_row_wrong(rec, T, size)) { set_error("taxonomy record %llu contradicts itself: %s", (unsigned long long)r, why); return SPSP_ERR_ARG; }
+        if (rec.node == SPSP_TAXONOMY_NONE) { ++none; none_bases += rec.length; continue; }
+        ++rec_direct[rec.node]; base_direct[rec.node] += rec.length;
+    }
+    rec_clade = rec_direct; base_clade = base_direct;
+    for (uint32_t t = T - 1; t >= 1; --t) { rec_clade[parent[t]] += rec_clade[t]; base_clade[parent[t]] += base_clade[t]; }
+    std::string out = "taxon,depth,name,lineage,references,records_clade,records_direct,bases_clade,bases_direct\n", lineage;
+    for (uint32_t t = 0; t < T; ++t) {
+        taxonomy_lineage(parent, node_names, t, &lineage);
+        out += std::to_string(t); out += ',';
+        out += std::to_string(depth[t]); out += ',';
+        out += node_names[t]; out += ',';
+        out += lineage; out += ',';
+        out += std::to_string(refs[t]); out += ',';
+        out += std::to_string(rec_clade[t]); out += ',';
+        out += std::to_string(rec_direct[t]); out += ',';
+        out += std::to_string(base_clade[t]); out += ',';
+        out += std::to_string(base_direct[t]); out += '\n';
+    }
+    out += ",,unclassified,,0," + std::to_string(none) + ',' + std::to_string(none) + ',' + std::to_string(none_bases) + ',' + std::to_string(none_bases) + '\n';
     return text_out(out, text, len);
 }
 

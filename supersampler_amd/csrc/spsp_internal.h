@@ -141,6 +141,7 @@ enum HostSlot {
     kHsCfBad = 37,          // spsp_classify.hip: the copy of two u32 (the index build's keys out of order | a probe sequence that went round
                             // the table or a list place out of range << 32) behind the index call's wait; behind a classify call's one
                             // wait the copy of its own word (u32: a record routed to a form its work does not fit)
+                            // -- and behind a taxonomy call's one wait (spsp_taxonomy.hip) the copy of that call's word, the same way
     kHostSlots = 38
 };
 constexpr int kIngestTotals = 2;
@@ -309,6 +310,8 @@ struct spsp_ctx {
         bool depth = false;               // spsp_depth_begin_device has made counters for THIS index: they end with it
         uint32_t distinct = 0;            // ... and read D, its distinct keys
         std::vector<uint64_t> off_host;   // the references' offsets as the index call got them (n_ref + 1)
+        bool taxonomy = false;            // spsp_taxonomy_index_device has attached a tree to THIS index: it ends with it
+        uint32_t tx_nodes = 0;            // ... of T nodes
     } cf_index;
     spsp::DevBuf cf_off, cf_kn, cf_work, cf_queue, cf_rec, cf_hits, cf_rows;
     // depth (spsp_depth.hip): one 32-bit counter per distinct key of the index; per index entry its key's number and whether that
@@ -329,6 +332,12 @@ struct spsp_ctx {
     uint32_t pf_last[3] = {};            // the last call's rounds queued, rows and host waits (spsp_profile_counts hands them out)
     hipEvent_t cf_events[5] = {};        // while timing is on: in front of the probe, the route, the small form, the large form, and behind it
     double cf_ms[4] = {};                // ... their milliseconds added up since spsp_classify_stage_ms last read them
+    // taxonomy (spsp_taxonomy.hip), on the classification's index: the tree (parent | size | ref_node), node(x) per distinct key,
+    // the same per index entry where it was asked for; per call the hit keys per record with the flag words and the two queues
+    // behind them, the records' eight words, and the counter rows of the workgroup form where they do not fit the LDS
+    spsp::DevBuf tx_tree, tx_key_node, tx_entry_node, tx_queue, tx_rec, tx_rows;
+    hipEvent_t tx_events[5] = {};        // while timing is on: in front of the probe, the route, the wave form, the workgroup form, and behind it
+    double tx_ms[4] = {};                // ... their milliseconds added up since spsp_taxonomy_stage_ms last read them
 };
 
 namespace spsp {
@@ -555,6 +564,30 @@ constexpr uint32_t kPfListCut = kCfListCut;                // the walk: a list o
 constexpr uint32_t kPfBatchFirst = 32, kPfBatchMax = 128;  // rounds queued per host wait: 32, 64, 128, 128, ...
 int profile_impl(spsp_ctx* ctx, uint32_t min_count, uint32_t min_keys, uint32_t max_rounds, spsp_profile_row* rows, uint64_t* n_rows, spsp_profile_totals* totals,
                  const uint8_t** d_entry_assigned);
+// spsp_taxonomy.hip: the records of a batch assigned to the lowest common ancestor of their keys.  What routes a record
+// (spsp_taxonomy_plan_host, spsp_host.cpp):
+constexpr uint32_t kTxThreads = 256;                       // key nodes, route, wave form: 4 waves
+constexpr uint32_t kTxSmallHits = 1024;                    // hit keys one wave of the wave form sorts in its 4 KiB of LDS: a record of more goes to a workgroup
+constexpr uint32_t kTxLargeThreads = 512;                  // the workgroup form: 8 waves per record
+constexpr uint32_t kTxLargeFixedLds = 1024;                // ... its LDS beside the counters: the reductions' words and the way up
+constexpr uint32_t kTxLdsNodes = (kAcLdsBytes - 8192) / 4; // 38 912: up to this many nodes the workgroup form's counters stay in LDS
+constexpr uint32_t kTxListCut = kCfListCut;                // the key nodes: a list of more holders than this is folded by the whole wave
+constexpr uint32_t kTxMaxNodes = 1048576, kTxMaxDepth = 32;
+constexpr size_t kTxRowsBytes = (size_t)256 << 20;         // the workgroup form's rows in device memory, all of them: the grid is sized to fit
+// classify's probe pass, launched for another caller (spsp_classify.hip): kn[i] = the key number + 1 of record key i (0: nobody
+// holds it), work[r] and hit[r] added up per record.  d_off: the record offsets on the device.  The caller has cleared work and hit
+int classify_probe_launch(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* d_off, uint32_t n_rec,
+                          uint64_t all_keys, uint32_t* d_kn, unsigned long long* d_work, uint32_t* d_hit);
+// the road spsp_classify_files and spsp_taxonomy_files share (spsp_classify.hip): run.load(rate) with classify's refusals, the
+// decoding and the index, on_index behind it, then the records file read and sent through records_text_batches on a second
+// context; *t1 = run.end().  names: the records' names
+struct FilesRun;
+int records_files_road(FilesRun& run, const char* records_path, double rate, const std::function<int()>& on_index, std::vector<std::string>* names,
+                       const std::function<int(uint32_t, const uint64_t*)>& on_records, const std::function<int(const RecordBatch&)>& on_batch, double* t1);
+int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den);
+int taxonomy_index_impl(spsp_ctx* ctx, const uint32_t* parent, uint32_t T, const uint32_t* ref_node, uint32_t n_ref, const uint32_t** key_nodes_out);
+int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
+                         uint32_t min_keys, uint32_t num, uint32_t den, spsp_taxonomy_record* records);
 // spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
 // groups as n_groups sketches back to back in context-owned arrays
 int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,

@@ -1,0 +1,584 @@
+// Taxonomy on the GPU: the records of a sequence file assigned to the lowest common ancestor of their keys (not in the reference,
+// whose end product is the two n x n matrices).
+//
+// The index is the classification's (spsp_classify.hip): the prevalence table names a key's claimer entry, key_no[claimer] the key's
+// number x in 0 .. D-1, and list[key_start[x] .. key_start[x + 1]) the 16-bit numbers of its holders.  The tree has T nodes in
+// preorder: parent[t] < t, the subtree of t is [t, t + size[t]), anc(a, b) = a <= b < a + size[a]; reference j sits at ref_node[j].
+//   node(x)  = lca{ ref_node[j] : K_j holds x }                       (once, when the tree is attached)
+//   w(t)     = the record's hit keys with node(x) = t                  path(t) = Sum w over t and its ancestors
+//   clade(t) = Sum w over the subtree of t                             W = the t with w(t) > 0 of the largest path;  start = lca(W)
+//   the call = the first node on the way from start to the root with clade >= min_keys and clade * den >= num * |Q_r|
+// Integers only.  In preorder the lca of a set is the lca of its smallest and its largest member (every node between two members
+// of one subtree is in that subtree), so both lcas here are a min, a max and one climb of at most 32 parents.
+//
+// attach (spsp_taxonomy_index_device):
+//   k_tx_key_nodes  a lane per distinct key: min and max of ref_node over its list, lists of more than kTxListCut holders by the
+//                   whole wave (coalesced), then the climb.  Bound: 2 bytes per holder and one random 4-byte read of ref_node each.
+//   k_tx_entry_nodes  only where the caller asks for node(x) per index entry: the probe of depth's numbering pass.
+// per batch (spsp_taxonomy_device), one chain of launches whatever the records are, one host wait at its end:
+//   k_cf_probe      classify's, unchanged: kn[e] = the key's number + 1, hit[r] = the record's hit keys (its work is not read)
+//   k_tx_route      a lane per record: no hit -> its row is written here; hits <= kTxSmallHits -> the wave form's queue; else the
+//                   workgroup form's.
+//   k_tx_small      a wave per record: node(x) of its hit keys gathered into the wave's 4 KiB of LDS and sorted by the bitonic steps
+//                   of k_cf_small.  The sorted words ARE the prefix sums: the keys in a range of nodes are the difference of two
+//                   lower bounds, so w(t), clade(t) = the range [t, t + size[t]) and every term of path(t) are two binary searches
+//                   each, and no (node, w) pairs are made.  A lane per run of equal nodes climbs its path; best, min W, max W and
+//                   |W| are wave reductions; the confidence climb is at most 33 uniform steps.
+//                   Bound: LDS traffic of the sort, (log2 P)^2 / 2 steps over P <= 1 024 words.
+//   k_tx_large      a workgroup per record with one 32-bit counter per node: in LDS while 4 T bytes fit beside the fixed words
+//                   (T <= kTxLdsNodes), in a row of device memory per workgroup beyond (added to, cleared and read at L2, as
+//                   k_cf_large's rows).  One atomic add per hit key; then a lane per node with w > 0 climbs its path over the
+//                   counters, and the clades on the way up are range sums that grow from the range below (every counter is read
+//                   once at the most).  Bound: hit keys atomic adds + 2 x 4 T bytes of counters per record.
+// No workgroup ever waits for another one.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "spsp_device.h"
+#include "spsp_internal.h"
+
+namespace spsp {
+
+namespace {
+
+enum { kTxqSmall = 0, kTxqLarge = 1, kTxqBad = 2, kTxqWords = 4 };   // words in front of the queues: their fill, the flag word, one spare
+constexpr uint32_t kTxWaves = kTxThreads / 64, kTxLargeWaves = kTxLargeThreads / 64;
+constexpr uint32_t kTxNone = SPSP_TAXONOMY_NONE;
+static_assert(kTxSmallHits * 4 * kTxWaves <= 64 * 1024 && (kTxSmallHits & (kTxSmallHits - 1)) == 0, "the wave form's LDS: a power of two of words per wave");
+static_assert((size_t)kTxLdsNodes * 4 + kTxLargeFixedLds <= kAcLdsBytes, "the workgroup form's counters beside its fixed words");
+static_assert(kTxLargeFixedLds >= (kTxLargeWaves * 5 + kTxLargeWaves) * 4, "the reductions' words");
+
+// the wave's LDS words: what its lanes stored in front of this line is what they read behind it (cf_wave_sync of spsp_classify.hip)
+__device__ __forceinline__ void tx_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ bool tx_passes(uint32_t clade, uint32_t keys, uint32_t min_keys, uint32_t num, uint32_t den) {
+    return clade >= min_keys && (unsigned long long)clade * den >= (unsigned long long)num * keys;
+}
+
+// the deepest node that is anc of both lo and hi (lo <= hi < T): the first ancestor of lo whose subtree reaches hi
+__device__ __forceinline__ uint32_t tx_lca(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ size, uint32_t lo, uint32_t hi) {
+    uint32_t a = lo;
+    for (uint32_t step = 0; step <= kTxMaxDepth && a != 0u && hi - a >= size[a]; ++step) a = parent[a];   // (the root holds every node)
+    return a;
+}
+
+__device__ __forceinline__ uint32_t tx_wave_min(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(v, d); v = o < v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ uint32_t tx_wave_max(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(v, d); v = o > v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ uint32_t tx_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// what a lane knows of W so far: the best path it met, and of the nodes with that path the smallest, the largest and their number
+struct TxBest { uint32_t best, lo, hi, count; };
+__device__ __forceinline__ void tx_meet(TxBest& b, uint32_t path, uint32_t t) {
+    if (path > b.best) { b.best = path; b.lo = b.hi = t; b.count = 1u; }
+    else if (path == b.best) { b.lo = t < b.lo ? t : b.lo; b.hi = t > b.hi ? t : b.hi; ++b.count; }
+}
+// ... and the wave's: every lane gets it
+__device__ __forceinline__ TxBest tx_wave_best(TxBest b) {
+    const uint32_t best = tx_wave_max(b.best);
+    const bool mine = b.best == best && b.count != 0u;
+    TxBest o;
+    o.best = best;
+    o.lo = tx_wave_min(mine ? b.lo : kTxNone);
+    o.hi = tx_wave_max(mine ? b.hi : 0u);
+    o.count = tx_wave_sum(mine ? b.count : 0u);
+    return o;
+}
+
+// node(x) of every distinct key x < D = key_no[n_index]: the lca of its holders' nodes
+__global__ __launch_bounds__(kTxThreads) void k_tx_key_nodes(const uint32_t* __restrict__ key_no, uint32_t n_index, const uint32_t* __restrict__ key_start,
+                                                             const uint16_t* __restrict__ list, uint32_t R, const uint32_t* __restrict__ ref_node,
+                                                             const uint32_t* __restrict__ parent, const uint32_t* __restrict__ size, uint32_t T,
+                                                             uint32_t* __restrict__ key_node) {
+    const uint32_t D = min(key_no[n_index], n_index);
+    const uint64_t x = (uint64_t)blockIdx.x * kTxThreads + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool valid = x < D;
+    const uint32_t ls = valid ? key_start[x] : 0u, len = valid ? key_start[x + 1u] - ls : 0u;
+    uint32_t lo = kTxNone, hi = 0u;
+    if (len <= kTxListCut)
+        for (uint32_t j = 0; j < len; ++j) {
+            const uint32_t sk = list[ls + j];
+            if (sk < R) { const uint32_t t = ref_node[sk]; lo = t < lo ? t : lo; hi = t > hi ? t : hi; }
+        }
+    unsigned long long left = __ballot(len > kTxListCut);
+    while (left) {                                         // the long lists, one after another by the whole wave
+        const int l = __ffsll((long long)left) - 1;
+        const uint32_t s0 = __shfl(ls, l), n0 = __shfl(len, l);
+        uint32_t a = kTxNone, b = 0u;
+        for (uint32_t j = lane; j < n0; j += 64u) {
+            const uint32_t sk = list[s0 + j];
+            if (sk < R) { const uint32_t t = ref_node[sk]; a = t < a ? t : a; b = t > b ? t : b; }
+        }
+        a = tx_wave_min(a); b = tx_wave_max(b);
+        if ((int)lane == l) { lo = a; hi = b; }
+        left &= left - 1ull;
+    }
+    if (!valid) return;
+    key_node[x] = lo < T && hi < T ? tx_lca(parent, size, lo, hi) : 0u;   // (a key always has a holder, and ref_node < T was checked)
+}
+
+// node(x) per index entry: the entry's own key looked up as depth's numbering pass does it
+template <bool HAS_HI>
+__global__ __launch_bounds__(kTxThreads) void k_tx_entry_nodes(SortedKeys K, uint64_t first, uint32_t n_index, const unsigned long long* __restrict__ tbl,
+                                                               uint32_t log2cap, const uint32_t* __restrict__ key_no, const uint32_t* __restrict__ key_node,
+                                                               uint32_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * kTxThreads + threadIdx.x;
+    if (i >= n_index) return;
+    const uint32_t D = min(key_no[n_index], n_index);
+    const uint64_t e = first + i;
+    const uint64_t at = pv_find<HAS_HI>(K, first, n_index, tbl, log2cap, K.mn[e], HAS_HI ? K.hi[e] : 0ull, K.lo[e]);
+    uint32_t node = kTxNone;
+    if (at != ~0ull) {                                     // (always: the table was filled from these entries)
+        const uint32_t number = key_no[at];
+        if (number < D) node = key_node[number];
+    }
+    out[i] = node;
+}
+
+// a record's eight words: keys, hit_keys, node, start | score, clade, direct, winners
+__device__ __forceinline__ void tx_write(uint4* __restrict__ rec, uint32_t r, uint32_t keys, uint32_t hit_keys, uint32_t node, uint32_t start, uint32_t score,
+                                         uint32_t clade, uint32_t direct, uint32_t winners) {
+    rec[2ull * r] = make_uint4(keys, hit_keys, node, start);
+    rec[2ull * r + 1ull] = make_uint4(score, clade, direct, winners);
+}
+
+__global__ __launch_bounds__(kTxThreads) void k_tx_route(const uint64_t* __restrict__ off, uint32_t n_rec, const uint32_t* __restrict__ hit,
+                                                         uint32_t* __restrict__ words, uint32_t* __restrict__ q_small, uint32_t* __restrict__ q_large,
+                                                         uint4* __restrict__ rec) {
+    const uint64_t r = (uint64_t)blockIdx.x * kTxThreads + threadIdx.x;
+    if (r >= n_rec) return;
+    const uint32_t h = hit[r];
+    if (h == 0u) tx_write(rec, (uint32_t)r, (uint32_t)(off[r + 1] - off[r]), 0u, kTxNone, kTxNone, 0u, 0u, 0u, 0u);
+    else if (h <= kTxSmallHits) q_small[atomicAdd(words + kTxqSmall, 1u)] = (uint32_t)r;   // (a queue has room for every record)
+    else q_large[atomicAdd(words + kTxqLarge, 1u)] = (uint32_t)r;
+}
+
+// the first place of the sorted words s[0 .. n) that holds v or more
+__device__ __forceinline__ uint32_t tx_lower(const uint32_t* s, uint32_t n, uint32_t v) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (s[mid] < v) lo = mid + 1u; else hi = mid; }
+    return lo;
+}
+
+// a wave per queued record; kn, and the entries of off, count from the first record key
+__global__ __launch_bounds__(kTxThreads) void k_tx_small(const uint64_t* __restrict__ off, const uint32_t* __restrict__ kn_of, const uint32_t* __restrict__ key_node,
+                                                         const uint32_t* __restrict__ parent, const uint32_t* __restrict__ size, uint32_t T,
+                                                         const uint32_t* __restrict__ q_small, uint32_t* __restrict__ words, uint32_t min_keys, uint32_t num,
+                                                         uint32_t den, uint4* __restrict__ rec) {
+    __shared__ uint32_t s_all[kTxWaves][kTxSmallHits];
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    uint32_t* s = s_all[wid];
+    const uint32_t n_small = words[kTxqSmall];
+    const uint64_t q0 = off[0];
+    for (uint64_t q = (uint64_t)blockIdx.x * kTxWaves + wid; q < n_small; q += (uint64_t)gridDim.x * kTxWaves) {   // (uniform per wave)
+        const uint32_t r = q_small[q];
+        const uint64_t a = off[r] - q0, z = off[r + 1] - q0;
+        const uint32_t keys = (uint32_t)(z - a);
+        // the nodes of the record's hit keys, packed
+        uint32_t H = 0;
+        bool fits = true;
+        for (uint64_t base = a; base < z; base += 64ull) {
+            const uint64_t i = base + lane;
+            const uint32_t kn = i < z ? kn_of[i] : 0u;
+            const uint32_t node = kn ? key_node[kn - 1u] : kTxNone;
+            const bool has = node < T;
+            const unsigned long long b = __ballot(has);
+            const uint32_t n = (uint32_t)__popcll(b);
+            if (n > kTxSmallHits - H) { fits = false; break; }   // (never: the route sent a record of this many hits elsewhere.  Uniform)
+            if (has) s[H + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = node;
+            H += n;
+        }
+        if (!fits || H == 0u) { if (lane == 0u) atomicOr(words + kTxqBad, 1u); continue; }
+        uint32_t P = 64;
+        while (P < H) P <<= 1;
+        for (uint32_t i = H + lane; i < P; i += 64u) s[i] = kTxNone;
+        tx_wave_sync();
+        for (uint32_t k = 2; k <= P; k <<= 1)
+            for (uint32_t j = k >> 1; j; j >>= 1) {
+                for (uint32_t t = lane; t < P / 2u; t += 64u) {
+                    const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i + j;
+                    const uint32_t x = s[i], y = s[l];
+                    if ((x > y) == ((i & k) == 0u)) { s[i] = y; s[l] = x; }
+                }
+                tx_wave_sync();
+            }
+        // every run of one node t has w(t) > 0: the lane at its last place climbs path(t)
+        TxBest mine{0u, kTxNone, 0u, 0u};
+        for (uint32_t base = 0; base < H; base += 64u) {
+            const uint32_t i = base + lane;
+            if (i < H) {
+                const uint32_t t = s[i];
+                if (i + 1u == H || s[i + 1u] != t) {
+                    uint32_t path = i + 1u - tx_lower(s, i, t), at = t;
+                    for (uint32_t step = 0; step < kTxMaxDepth && at != 0u; ++step) {
+                        at = parent[at];
+                        const uint32_t lo = tx_lower(s, H, at);
+                        path += tx_lower(s, H, at + 1u) - lo;
+                    }
+                    tx_meet(mine, path, t);
+                }
+            }
+        }
+        const TxBest W = tx_wave_best(mine);
+        const uint32_t start = tx_lca(parent, size, W.lo, W.hi);
+        uint32_t node = kTxNone, clade = 0u, direct = 0u, t = start;
+        for (uint32_t step = 0; step <= kTxMaxDepth; ++step) {   // (uniform: every lane walks the same way up)
+            const uint32_t lo = tx_lower(s, H, t), c = tx_lower(s, H, t + size[t]) - lo;
+            if (tx_passes(c, keys, min_keys, num, den)) { node = t; clade = c; direct = tx_lower(s, H, t + 1u) - lo; break; }
+            if (t == 0u) break;
+            t = parent[t];
+        }
+        tx_wave_sync();                                    // (the words are read: the next record may overwrite them)
+        if (lane == 0u) tx_write(rec, r, keys, H, node, start, W.best, clade, direct, W.count);
+    }
+}
+
+// sums over the workgroup: every lane gets the total.  s8: kTxLargeWaves words nobody else uses between the two barriers inside
+__device__ __forceinline__ uint32_t tx_block_sum(uint32_t v, uint32_t* s8, uint32_t lane, uint32_t wid) {
+    v = tx_wave_sum(v);
+    if (lane == 0u) s8[wid] = v;
+    __syncthreads();
+    uint32_t total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kTxLargeWaves; ++w) total += s8[w];
+    __syncthreads();
+    return total;
+}
+
+// a workgroup per queued record.  LDS: [IN_LDS: T_pad counters |] the waves' W words (5 each) | the sums' words.  rows: !IN_LDS, a row
+// of T_pad counters per workgroup
+template <bool IN_LDS>
+__global__ __launch_bounds__(kTxLargeThreads) void k_tx_large(const uint64_t* __restrict__ off, const uint32_t* __restrict__ kn_of,
+                                                              const uint32_t* __restrict__ key_node, const uint32_t* __restrict__ parent,
+                                                              const uint32_t* __restrict__ size, uint32_t T, uint32_t T_pad, const uint32_t* __restrict__ q_large,
+                                                              const uint32_t* __restrict__ words, uint32_t* __restrict__ rows, uint32_t min_keys, uint32_t num,
+                                                              uint32_t den, uint4* __restrict__ rec) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
+    uint32_t* cnt = IN_LDS ? s_mem : rows + (size_t)blockIdx.x * T_pad;
+    uint32_t* s_w = s_mem + (IN_LDS ? T_pad : 0u);         // wave w: best, lo, hi, count, hits at s_w[5 w ..]
+    uint32_t* s8 = s_w + kTxLargeWaves * 5u;
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    const uint32_t n_large = words[kTxqLarge];
+    const uint64_t q0 = off[0];
+    // (the rows in device memory are added to at L2: they are cleared and read there as well, past this CU's L1)
+    auto get = [&](uint32_t j) -> uint32_t { return IN_LDS ? cnt[j] : __hip_atomic_load(cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    for (uint64_t q = blockIdx.x; q < n_large; q += gridDim.x) {   // (uniform per workgroup)
+        const uint32_t r = q_large[q];
+        const uint64_t a = off[r] - q0, z = off[r + 1] - q0;
+        const uint32_t keys = (uint32_t)(z - a);
+        for (uint32_t j = threadIdx.x; j < T; j += kTxLargeThreads) {
+            if (IN_LDS) cnt[j] = 0u;
+            else __hip_atomic_store(cnt + j, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        for (uint64_t i = a + threadIdx.x; i < z; i += kTxLargeThreads) {
+            const uint32_t kn = kn_of[i];
+            if (kn) { const uint32_t t = key_node[kn - 1u]; if (t < T) atomicAdd(&cnt[t], 1u); }
+        }
+        __syncthreads();
+        // a lane per node with w > 0: its path over the counters
+        TxBest mine{0u, kTxNone, 0u, 0u};
+        uint32_t hits = 0;
+        for (uint32_t t = threadIdx.x; t < T; t += kTxLargeThreads) {
+            const uint32_t w = get(t);
+            if (w == 0u) continue;
+            hits += w;
+            uint32_t path = w, at = t;
+            for (uint32_t step = 0; step < kTxMaxDepth && at != 0u; ++step) { at = parent[at]; path += get(at); }
+            tx_meet(mine, path, t);
+        }
+        const TxBest mw = tx_wave_best(mine);
+        hits = tx_wave_sum(hits);
+        if (lane == 0u) { uint32_t* o = s_w + wid * 5u; o[0] = mw.best; o[1] = mw.lo; o[2] = mw.hi; o[3] = mw.count; o[4] = hits; }
+        __syncthreads();
+        TxBest W{0u, kTxNone, 0u, 0u};
+        uint32_t H = 0;
+        for (uint32_t w = 0; w < kTxLargeWaves; ++w) {     // (every lane merges the eight: the same words, the same result)
+            const uint32_t* o = s_w + w * 5u;
+            H += o[4];
+            if (o[3] == 0u || o[0] < W.best) continue;
+            if (o[0] > W.best) { W.best = o[0]; W.lo = o[1]; W.hi = o[2]; W.count = o[3]; }
+            else { W.lo = o[1] < W.lo ? o[1] : W.lo; W.hi = o[2] > W.hi ? o[2] : W.hi; W.count += o[3]; }
+        }
+        uint32_t node = kTxNone, start = kTxNone, clade = 0u, direct = 0u;
+        if (W.count != 0u) {                               // (uniform.  Always: the route saw hit keys)
+            start = tx_lca(parent, size, W.lo, W.hi);
+            // the way up: the clade of a node is its child's and the counters of its range on both sides of the child's
+            uint32_t t = start, lo = start, hi = start, c = 0u;
+            for (uint32_t step = 0; step <= kTxMaxDepth; ++step) {
+                const uint32_t n_lo = t, n_hi = t + size[t];
+                uint32_t part = 0;
+                for (uint32_t j = n_lo + threadIdx.x; j < lo; j += kTxLargeThreads) part += get(j);
+                for (uint32_t j = hi + threadIdx.x; j < n_hi; j += kTxLargeThreads) part += get(j);
+                c += tx_block_sum(part, s8, lane, wid);
+                lo = n_lo; hi = n_hi;
+                if (tx_passes(c, keys, min_keys, num, den)) { node = t; clade = c; direct = get(t); break; }
+                if (t == 0u) break;
+                t = parent[t];
+            }
+        }
+        if (threadIdx.x == 0u) tx_write(rec, r, keys, H, node, start, W.best, clade, direct, W.count);
+        __syncthreads();                                   // (the counters and the waves' words are read: the next record clears them)
+    }
+}
+
+const char* const kNoIndex = "taxonomy: the context holds no index (spsp_classify_index_device first; a prevalence, select, accumulation or groups call replaces it)";
+const char* const kNoTaxonomy = "taxonomy: the index holds no taxonomy (spsp_taxonomy_index_device first; it ends with the index it was attached to)";
+
+}  // namespace
+
+int taxonomy_index_impl(spsp_ctx* ctx, const uint32_t* parent, uint32_t T, const uint32_t* ref_node, uint32_t n_ref, const uint32_t** key_nodes_out) {
+    int rc;
+    if (key_nodes_out) *key_nodes_out = nullptr;
+    spsp_ctx::ClassifyIndex& X = ctx->cf_index;
+    if (!X.valid) { set_error("%s", kNoIndex); return SPSP_ERR_ARG; }
+    if (n_ref != X.n_ref) { set_error("taxonomy: %u references, the index holds %u", n_ref, X.n_ref); return SPSP_ERR_ARG; }
+    if ((rc = spsp_taxonomy_check_host(parent, T, ref_node, n_ref))) return rc;
+    X.taxonomy = false;
+    std::vector<uint32_t> size(T, 1);
+    for (uint32_t t = T - 1; t >= 1; --t) size[parent[t]] += size[t];
+    const uint32_t E = X.entries, T_pad = (T + 3u) & ~3u;
+    if ((rc = ctx->tx_tree.reserve(((size_t)2 * T_pad + n_ref) * 4 + 64)) || (rc = ctx->tx_key_node.reserve((size_t)E * 4 + 64)) ||
+        (key_nodes_out && (rc = ctx->tx_entry_node.reserve((size_t)E * 4 + 64)))) return rc;
+    uint32_t* d_parent = ctx->tx_tree.as<uint32_t>();
+    uint32_t *d_size = d_parent + T_pad, *d_ref = d_size + T_pad;
+    SPSP_HIP(hipMemcpyAsync(d_parent, parent, (size_t)T * 4, hipMemcpyHostToDevice, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(d_size, size.data(), (size_t)T * 4, hipMemcpyHostToDevice, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(d_ref, ref_node, (size_t)n_ref * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (E) {
+        const uint32_t gx = (uint32_t)(((uint64_t)E + kTxThreads - 1) / kTxThreads);   // (D <= E: a grid over the entries covers the keys)
+        hipLaunchKernelGGL(k_tx_key_nodes, dim3(gx), dim3(kTxThreads), 0, ctx->stream, X.key_no, E, X.key_start, X.list, n_ref, (const uint32_t*)d_ref,
+                           (const uint32_t*)d_parent, (const uint32_t*)d_size, T, ctx->tx_key_node.as<uint32_t>());
+        SPSP_HIP(hipGetLastError());
+        if (key_nodes_out) {
+            const SortedKeys K{X.mn, X.lo, X.hi};
+            const unsigned long long* d_tbl = ctx->pv_table.as<unsigned long long>();
+            if (X.has_hi) hipLaunchKernelGGL(k_tx_entry_nodes<true>, dim3(gx), dim3(kTxThreads), 0, ctx->stream, K, X.first, E, d_tbl, ctx->pv_log2cap, X.key_no,
+                                             (const uint32_t*)ctx->tx_key_node.as<uint32_t>(), ctx->tx_entry_node.as<uint32_t>());
+            else hipLaunchKernelGGL(k_tx_entry_nodes<false>, dim3(gx), dim3(kTxThreads), 0, ctx->stream, K, X.first, E, d_tbl, ctx->pv_log2cap, X.key_no,
+                                    (const uint32_t*)ctx->tx_key_node.as<uint32_t>(), ctx->tx_entry_node.as<uint32_t>());
+            SPSP_HIP(hipGetLastError());
+        }
+    }
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));           // the attach's wait (the caller's arrays and `size` live until here)
+    if (key_nodes_out) *key_nodes_out = ctx->tx_entry_node.as<uint32_t>();
+    X.tx_nodes = T;
+    X.taxonomy = true;
+    return SPSP_OK;
+}
+
+int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
+                         uint32_t min_keys, uint32_t num, uint32_t den, spsp_taxonomy_record* records) {
+    int rc;
+    // (what is zeroed in front of the refusals: everything but the caller's lengths)
+    for (uint32_t r = 0; r < n_rec; ++r) { const uint64_t length = records[r].length; records[r] = spsp_taxonomy_record{}; records[r].length = length; }
+    if ((rc = taxonomy_check_args(min_keys, num, den))) return rc;
+    if (n_rec > 0xfffffff0u) { set_error("too many records for one call (%u)", n_rec); return SPSP_ERR_OVERFLOW; }
+    for (uint32_t r = 0; r < n_rec; ++r)
+        if (h_rec_off[r + 1] < h_rec_off[r]) { set_error("record offsets must not decrease (record %u)", r); return SPSP_ERR_ARG; }
+    if (h_rec_off[n_rec] > 0xfffffff0ull) { set_error("too many record keys for one call"); return SPSP_ERR_OVERFLOW; }
+    const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
+    if (!X.valid) { set_error("%s", kNoIndex); return SPSP_ERR_ARG; }
+    if (!X.taxonomy) { set_error("%s", kNoTaxonomy); return SPSP_ERR_ARG; }
+    const uint64_t q0 = h_rec_off[0], all_keys = h_rec_off[n_rec] - q0;
+    if (all_keys && (!q_mn || !q_lo)) { set_error("NULL key array"); return SPSP_ERR_ARG; }
+    if (all_keys && (q_hi != nullptr) != X.has_hi) {
+        set_error("taxonomy: the index was built %s kmer_hi (k %s 32), the records come %s it", X.has_hi ? "with" : "without", X.has_hi ? ">" : "<=",
+                  q_hi ? "with" : "without");
+        return SPSP_ERR_ARG;
+    }
+    for (uint32_t r = 0; r < n_rec; ++r) {                 // (length is the caller's)
+        records[r].keys = (uint32_t)(h_rec_off[r + 1] - h_rec_off[r]);
+        records[r].node = records[r].start = kTxNone;
+    }
+    if (n_rec == 0 || all_keys == 0 || X.entries == 0) return SPSP_OK;   // (no record, no record key or no reference key: no hit)
+
+    const uint32_t T = X.tx_nodes, T_pad = (T + 3u) & ~3u;
+    const bool in_lds = T <= kTxLdsNodes;
+    const int n_cu = std::max(ctx->n_cu, 1);
+    const size_t lds = kTxLargeFixedLds + (in_lds ? (size_t)T_pad * 4 : 0);
+    const uint32_t large_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2048 / kTxLargeThreads, kAcLdsBytes / lds));
+    // (the rows in device memory: as many workgroups as rows fit kTxRowsBytes, one per CU at the most)
+    const uint64_t rows_fit = std::max<uint64_t>(1, kTxRowsBytes / ((size_t)T_pad * 4));
+    const uint32_t g_large = (uint32_t)std::min<uint64_t>(n_rec, in_lds ? (uint64_t)n_cu * large_per_cu : std::min<uint64_t>((uint64_t)n_cu, rows_fit));
+    const uint32_t g_small = (uint32_t)std::min<uint64_t>(((uint64_t)n_rec + kTxWaves - 1) / kTxWaves, (uint64_t)n_cu * 8u);
+    const size_t work_bytes = (size_t)n_rec * 8, queue_bytes = 64 + (size_t)2 * n_rec * 4;
+    if ((rc = ctx->cf_off.reserve(((size_t)n_rec + 1) * 8)) || (rc = ctx->cf_kn.reserve((size_t)all_keys * 4)) ||
+        (rc = ctx->cf_work.reserve(work_bytes + (size_t)n_rec * 4)) || (rc = ctx->tx_queue.reserve(queue_bytes)) ||
+        (rc = ctx->tx_rec.reserve((size_t)n_rec * 32)) || (!in_lds && (rc = ctx->tx_rows.reserve((size_t)g_large * T_pad * 4)))) return rc;
+    uint64_t* d_off = ctx->cf_off.as<uint64_t>();
+    uint32_t* d_kn = ctx->cf_kn.as<uint32_t>();
+    unsigned long long* d_work = ctx->cf_work.as<unsigned long long>();
+    uint32_t* d_hit = reinterpret_cast<uint32_t*>(ctx->cf_work.as<uint8_t>() + work_bytes);
+    uint32_t* d_words = ctx->tx_queue.as<uint32_t>();
+    uint32_t* d_q_small = d_words + 16;
+    uint32_t* d_q_large = d_q_small + n_rec;
+    uint4* d_rec = ctx->tx_rec.as<uint4>();
+    uint32_t* d_rows = in_lds ? nullptr : ctx->tx_rows.as<uint32_t>();
+    const uint32_t* d_parent = ctx->tx_tree.as<uint32_t>();
+    const uint32_t* d_size = d_parent + T_pad;
+    const uint32_t* d_key_node = ctx->tx_key_node.as<uint32_t>();
+    SPSP_HIP(hipMemcpyAsync(d_off, h_rec_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));   // (the caller's: alive until the wait)
+    SPSP_HIP(hipMemsetAsync(d_work, 0, work_bytes + (size_t)n_rec * 4, ctx->stream));
+    SPSP_HIP(hipMemsetAsync(d_words, 0, kTxqWords * 4, ctx->stream));
+    SPSP_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_rec * 32, ctx->stream));
+    const uint32_t gr = (uint32_t)(((uint64_t)n_rec + kTxThreads - 1) / kTxThreads);
+    hipEvent_t* ev = nullptr;
+    if (ctx->timing) {                                     // spsp_timing_enable: events between the launches (spsp_taxonomy_stage_ms)
+        for (hipEvent_t& e : ctx->tx_events) if (!e) SPSP_HIP(hipEventCreate(&e));
+        ev = ctx->tx_events;
+        SPSP_HIP(hipEventRecord(ev[0], ctx->stream));
+    }
+    if ((rc = classify_probe_launch(ctx, q_mn, q_lo, q_hi, d_off, n_rec, all_keys, d_kn, d_work, d_hit))) return rc;
+    if (ev) SPSP_HIP(hipEventRecord(ev[1], ctx->stream));
+    hipLaunchKernelGGL(k_tx_route, dim3(gr), dim3(kTxThreads), 0, ctx->stream, (const uint64_t*)d_off, n_rec, (const uint32_t*)d_hit, d_words, d_q_small, d_q_large,
+                       d_rec);
+    if (ev) SPSP_HIP(hipEventRecord(ev[2], ctx->stream));
+    hipLaunchKernelGGL(k_tx_small, dim3(g_small), dim3(kTxThreads), 0, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn, d_key_node, d_parent, d_size, T,
+                       (const uint32_t*)d_q_small, d_words, min_keys, num, den, d_rec);
+    if (ev) SPSP_HIP(hipEventRecord(ev[3], ctx->stream));
+    if (in_lds) {
+        if ((rc = lds_opt_in(ctx, &k_tx_large<true>, kAcLdsBytes))) return rc;
+        hipLaunchKernelGGL(k_tx_large<true>, dim3(g_large), dim3(kTxLargeThreads), lds, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn, d_key_node,
+                           d_parent, d_size, T, T_pad, (const uint32_t*)d_q_large, (const uint32_t*)d_words, d_rows, min_keys, num, den, d_rec);
+    } else {
+        hipLaunchKernelGGL(k_tx_large<false>, dim3(g_large), dim3(kTxLargeThreads), lds, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn, d_key_node,
+                           d_parent, d_size, T, T_pad, (const uint32_t*)d_q_large, (const uint32_t*)d_words, d_rows, min_keys, num, den, d_rec);
+    }
+    SPSP_HIP(hipGetLastError());
+    if (ev) SPSP_HIP(hipEventRecord(ev[4], ctx->stream));
+    std::vector<uint32_t> got((size_t)n_rec * 8);
+    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCfBad, d_words + kTxqBad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(got.data(), d_rec, got.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));           // the one wait
+    if (ev)
+        for (int i = 0; i < 4; ++i) { float ms = 0; SPSP_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); ctx->tx_ms[i] += ms; }
+    if ((uint32_t)ctx->h_scalar[kHsCfBad]) {
+        set_error("taxonomy: a record's hit keys did not fit the form it was routed to (the key arrays changed during the call?)");
+        for (uint32_t r = 0; r < n_rec; ++r) { const uint64_t length = records[r].length; records[r] = spsp_taxonomy_record{}; records[r].length = length; }
+        return SPSP_ERR_ARG;
+    }
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        const uint32_t* g = got.data() + (size_t)r * 8;
+        spsp_taxonomy_record& o = records[r];
+        o.keys = g[0]; o.hit_keys = g[1]; o.node = g[2]; o.start = g[3]; o.score = g[4]; o.clade = g[5]; o.direct = g[6]; o.winners = g[7];
+    }
+    return SPSP_OK;
+}
+
+// spsp_taxonomy_files behind its argument checks
+static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, const char* lineages_path, uint32_t min_keys,
+                          uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_taxonomy_record>* recs) {
+    int rc;
+    // the lineage file first: a tree that cannot be read costs no loading
+    uint8_t* lin = nullptr; uint64_t n_lin = 0;
+    if ((rc = spsp_read_file_host(lineages_path, &lin, &n_lin))) return rc;
+    std::vector<uint32_t> ref_node(n_ref, 0);
+    uint32_t *parent = nullptr, *depth = nullptr, T = 0;
+    char* blob = nullptr; uint64_t blob_len = 0;
+    rc = spsp_taxonomy_lineages_host((const char*)lin, n_lin, n_ref, ref_node.data(), &parent, &depth, nullptr, &blob, &blob_len, &T);
+    spsp_free(lin);
+    if (rc) return rc;
+    std::vector<const char*> node_names(T);
+    for (uint64_t at = 0, t = 0; t < T; ++t) { node_names[t] = blob + at; at += strlen(blob + at) + 1; }
+    FilesRun run(ctx, paths, n_ref, chatter);
+    std::vector<std::string> names;
+    double t1 = 0;
+    rc = records_files_road(
+        run, records_path, rate, [&] { return taxonomy_index_impl(ctx, parent, T, ref_node.data(), n_ref, nullptr); }, &names,
+        [&](uint32_t n_rec, const uint64_t* rec_off) {
+            recs->assign(n_rec, spsp_taxonomy_record{});
+            for (uint32_t r = 0; r < n_rec; ++r) (*recs)[r].length = rec_off[r + 1] - rec_off[r];
+            return SPSP_OK;
+        },
+        [&](const RecordBatch& B) { return taxonomy_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, min_keys, num, den, recs->data() + B.first_record); },
+        &t1);
+    char *text = nullptr, *report = nullptr; uint64_t len = 0, report_len = 0;
+    if (!rc) {
+        std::vector<const char*> name_ptr(names.size());
+        for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
+        // (both texts before either file: nothing is written where a row is refused)
+        if (!(rc = spsp_taxonomy_csv_host(recs->data(), recs->size(), name_ptr.data(), parent, T, node_names.data(), precision, &text, &len)))
+            rc = spsp_taxonomy_report_csv_host(recs->data(), recs->size(), parent, T, node_names.data(), ref_node.data(), n_ref, &report, &report_len);
+    }
+    if (!rc) {
+        rc = write_csv_gz(ctx, text, len, out_prefix, "_taxonomy.csv.gz", t1);   // (the text is taken over)
+        text = nullptr;
+        const double t2 = now_s();
+        if (!rc) { rc = write_csv_gz(ctx, report, report_len, out_prefix, "_taxonomy_report.csv.gz", t2); report = nullptr; }
+    }
+    if (!rc && chatter) {
+        uint64_t called = 0, at_root = 0;
+        for (const spsp_taxonomy_record& r : *recs) { called += r.node != kTxNone; at_root += r.node == 0u; }
+        printf("%zu record(s) against %u reference(s) at %u node(s): %llu classified, %.3g of them at depth 0\n", recs->size(), n_ref, T, (unsigned long long)called,
+               called ? (double)at_root / (double)called : 0.0);
+        say_common_rate(run.L, n_ref);
+        fflush(stdout);
+    }
+    spsp_free(text); spsp_free(report);
+    spsp_free(parent); spsp_free(depth); spsp_free(blob);
+    return rc;
+}
+
+}  // namespace spsp
+
+using namespace spsp;
+
+extern "C" int spsp_taxonomy_index_device(spsp_ctx* ctx, const uint32_t* parent, uint32_t n_nodes, const uint32_t* ref_node, uint32_t n_ref,
+                                          const void** key_nodes_out) {
+    if (key_nodes_out) *key_nodes_out = nullptr;
+    if (!ctx || !parent || !ref_node) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    SPSP_HIP(hipSetDevice(ctx->device));
+    const uint32_t* out = nullptr;
+    const int rc = taxonomy_index_impl(ctx, parent, n_nodes, ref_node, n_ref, key_nodes_out ? &out : nullptr);
+    if (key_nodes_out) *key_nodes_out = out;
+    return rc;
+}
+
+extern "C" int spsp_taxonomy_device(spsp_ctx* ctx, const void* d_q_minimizer, const void* d_q_kmer_lo, const void* d_q_kmer_hi, const uint64_t* h_rec_off,
+                                    uint32_t n_records, uint32_t min_keys, uint32_t num, uint32_t den, spsp_taxonomy_record* records) {
+    if (!ctx || !h_rec_off || (n_records && !records)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    SPSP_HIP(hipSetDevice(ctx->device));
+    return taxonomy_device_impl(ctx, (const uint32_t*)d_q_minimizer, (const uint64_t*)d_q_kmer_lo, (const uint64_t*)d_q_kmer_hi, h_rec_off, n_records, min_keys,
+                                num, den, records);
+}
+
+extern "C" int spsp_taxonomy_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                   uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                   spsp_taxonomy_record** records, uint64_t* n_records) {
+    if (records) *records = nullptr;
+    if (n_records) *n_records = 0;
+    if (!ctx || !index_paths || !records_path || !lineages_path || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    int rc;
+    if ((rc = taxonomy_check_args(min_keys, num, den))) return rc;
+    SPSP_HIP(hipSetDevice(ctx->device));
+    std::vector<spsp_taxonomy_record> got;
+    if ((rc = taxonomy_files(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, &got))) return rc;
+    if (n_records) *n_records = got.size();
+    if (records && (rc = give_rows(got, records))) return rc;
+    return SPSP_OK;
+}
+
+extern "C" int spsp_taxonomy_stage_ms(spsp_ctx* ctx, double* ms) {
+    if (!ctx || !ms) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    for (int i = 0; i < 4; ++i) { ms[i] = ctx->tx_ms[i]; ctx->tx_ms[i] = 0; }
+    return SPSP_OK;
+}
