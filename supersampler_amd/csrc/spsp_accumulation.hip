@@ -95,19 +95,6 @@ __global__ __launch_bounds__(kAcThreads) void k_ac_scatter(SortedKeys K, const u
     list[at] = (uint16_t)sorted_sketch_of(off, 0, n, e);
 }
 
-// the wave's LDS words: what its lanes stored in front of this line is what they read behind it
-__device__ __forceinline__ void ac_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t ac_wave_min(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
-
 // grid.x = shares of the keys (waves stride over chunks of 64), grid.y = window of `window` ranks of F; LDS: G rank tables of n_pad
 // 16-bit words | G x window bins | a bitmap per wave.  ranks, F, M: the group's G rows.  mex is taken by window 0's workgroups alone
 template <uint32_t G>
@@ -196,7 +183,7 @@ __global__ __launch_bounds__(kAcPassThreads) void k_ac_pass(const uint32_t* __re
         }
 #pragma unroll
         for (uint32_t g = 0; g < G; ++g) {
-            m[g] = ac_wave_min(m[g]);
+            m[g] = wave_min(m[g]);
             const uint32_t b = m[g] - win_first;           // (a rank below the window wraps beyond it)
             if (lane == 0u && b < window && m[g] < n) atomicAdd(&s_bin[g * window + b], 1u);
             if (!with_mex || m[g] != 0u) continue;         // (uniform: the wave's minimum)
@@ -205,19 +192,19 @@ __global__ __launch_bounds__(kAcPassThreads) void k_ac_pass(const uint32_t* __re
             uint32_t mex = n;
             for (uint32_t low = 0; low <= n; low += kAcBitmapBits) {
                 for (uint32_t w = lane; w < kAcMapWords; w += 64u) bm[w] = 0u;
-                ac_wave_sync();
+                wave_lds_sync();
                 for (uint64_t i = (uint64_t)ls + lane; i < le; i += 64ull) {
                     const uint32_t r = (uint32_t)s_rank[g * n_pad + list[i]] - low;   // (a rank below the stretch wraps beyond it)
                     if (r < kAcBitmapBits) atomicOr(&bm[r >> 5], 1u << (r & 31u));
                 }
-                ac_wave_sync();
+                wave_lds_sync();
                 uint32_t cand = 0xffffffffu;
                 for (uint32_t w = lane; w < kAcMapWords; w += 64u) {
                     const uint32_t free_bits = ~bm[w];
                     if (free_bits != 0u && cand == 0xffffffffu) cand = w * 32u + (uint32_t)__ffs((int)free_bits) - 1u;
                 }
-                cand = ac_wave_min(cand);
-                ac_wave_sync();                            // (the words are read: the next stretch may clear them)
+                cand = wave_min(cand);
+                wave_lds_sync();                            // (the words are read: the next stretch may clear them)
                 if (cand != 0xffffffffu) { mex = low + cand; break; }
             }
             if (lane == 0u && mex >= 1u && mex <= n) atomicAdd(&M[(size_t)g * (n + 1u) + mex], 1ull);

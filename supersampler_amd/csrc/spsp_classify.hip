@@ -16,13 +16,14 @@
 //                (0: nobody holds it).  The lane's h goes to its record's work and 1 to its hit keys: one add per wave where the
 //                wave sits inside one record (a contig), one per lane with a hit otherwise (reads: a few lanes per record).
 //                Bound: one random 8-byte slot read and one 20-byte key read per key -- HBM latency under full occupancy.
-//   k_cf_route   a lane per record: no work -> its row is written here; work <= kCfSmallWork -> the queue of the small form; else the
-//                queue of the large form.  The queues' order is a race and no result depends on it.  No host wait: the two forms
-//                below are launched with grids sized by the records there can be and stride over what the queues hold.
+//   k_rec_route  (spsp_device.h) a lane per record: no work -> its row is written there (CfEmptyRow); work <= kCfSmallWork -> the
+//                queue of the small form; else the queue of the large form.  The queues' order is a race and no result depends on
+//                it.  No host wait: the two forms below are launched with grids sized by the records there can be and stride
+//                over what the queues hold.
 //   k_cf_small   a wave per record: the holder numbers of all its keys gathered into the wave's 4 KiB of LDS (long lists by the
-//                whole wave, as in the large form), sorted there by a
-//                bitonic network, and every run of equal numbers counted by a binary search for its start; the runs are offered
-//                64 at a time to the kept matches.  Bound: LDS traffic of the sort, (log2 P)^2 / 2 steps over P <= 1 024 words.
+//                whole wave, as in the large form), sorted there by a bitonic network (wave_sort_lds), and every run of equal
+//                numbers counted by a binary search for its start; the runs are offered 64 at a time to the kept matches.
+//                Bound: LDS traffic of the sort, (log2 P)^2 / 2 steps over P <= 1 024 words.
 //   k_cf_large   a workgroup per record with one 32-bit counter per reference: in LDS while 4 R bytes fit beside the kept matches
 //                (R <= kCfLdsRefs), in a row of HBM per workgroup beyond.  A wave takes 64 keys; a lane walks its own list, lists
 //                of more than kCfListCut holders are walked by the whole wave (coalesced: a contig against its species has
@@ -31,6 +32,8 @@
 // Kept matches: one 64-bit word per lane, best first.  A chunk of 64 candidates that holds nothing in front of the top-th kept word
 // is dropped with one ballot; else it is sorted by the register bitonic network of spsp_neighbours.hip and merged with the kept 64.
 // The host waits once per batch, at the end.  No workgroup ever waits for another one.
+// This file is also the home of what the record passes share on the host (DESIGN "What the record passes share"): the front of a
+// record call, its device arrays and clock, the records of a text in batches, and the road of the four file drivers.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -42,15 +45,8 @@ namespace spsp {
 
 namespace {
 
-enum { kCfqSmall = 0, kCfqLarge = 1, kCfqBad = 2, kCfqWords = 4 };   // words in front of the queues: their fill, the flag word, one spare
 constexpr uint32_t kCfWaves = kCfThreads / 64, kCfLargeWaves = kCfLargeThreads / 64;
-
-// the wave's LDS words: what its lanes stored in front of this line is what they read behind it
-__device__ __forceinline__ void cf_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+static_assert(kCfThreads == kRouteThreads && kCfWaves == kRecordWaves, "the record calls' route and wave-form grids");
 
 __device__ __forceinline__ unsigned long long cf_word(uint32_t shared, uint32_t ref) { return (unsigned long long)shared << 32 | (0xffffffffu - ref); }
 
@@ -74,10 +70,6 @@ __device__ __forceinline__ void cf_offer(unsigned long long& kept, unsigned long
     if (o > kept) kept = o;
 #pragma unroll
     for (uint32_t j = 32; j; j >>= 1) cf_exchange(kept, j, (lane & j) == 0);
-}
-
-__device__ __forceinline__ bool cf_passes(uint32_t shared, uint32_t keys, uint32_t min_keys, uint32_t num, uint32_t den) {
-    return shared >= min_keys && (unsigned long long)shared * den >= (unsigned long long)num * keys;
 }
 
 // Q: the records' keys, entries [off[0], off[n_rec]); K, tbl, key_no, key_start: the index (first: its first entry, n_index: its entries)
@@ -109,7 +101,7 @@ __global__ __launch_bounds__(kCfThreads) void k_cf_probe(SortedKeys Q, const uin
         unsigned long long w = h;
         uint32_t c = kn != 0u;
 #pragma unroll
-        for (int d = 32; d; d >>= 1) { w += __shfl_xor(w, d); c += __shfl_xor(c, d); }
+        for (int d = 32; d; d >>= 1) { w += __shfl_xor(w, d); c += __shfl_xor(c, d); }   // (one loop for both, not two wave_sum: measured)
         if ((threadIdx.x & 63u) == 0u && c != 0u) { atomicAdd(&work[r0], w); atomicAdd(&hit[r0], c); }
     } else if (kn != 0u) {
         atomicAdd(&work[rec], (unsigned long long)h);
@@ -117,17 +109,10 @@ __global__ __launch_bounds__(kCfThreads) void k_cf_probe(SortedKeys Q, const uin
     }
 }
 
-// rec[r]: keys, hit_keys, passing, listed
-__global__ __launch_bounds__(kCfThreads) void k_cf_route(const uint64_t* __restrict__ off, uint32_t n_rec, const unsigned long long* __restrict__ work,
-                                                         const uint32_t* __restrict__ hit, uint32_t* __restrict__ words, uint32_t* __restrict__ q_small,
-                                                         uint32_t* __restrict__ q_large, uint4* __restrict__ rec) {
-    const uint64_t r = (uint64_t)blockIdx.x * kCfThreads + threadIdx.x;
-    if (r >= n_rec) return;
-    const unsigned long long w = work[r];
-    if (w == 0ull) rec[r] = make_uint4((uint32_t)(off[r + 1] - off[r]), 0u, 0u, 0u);
-    else if (w <= kCfSmallWork) q_small[atomicAdd(words + kCfqSmall, 1u)] = (uint32_t)r;   // (a queue has room for every record)
-    else q_large[atomicAdd(words + kCfqLarge, 1u)] = (uint32_t)r;
-}
+// rec[r]: keys, hit_keys, passing, listed.  The row of a record without work, which the route kernel writes
+struct CfEmptyRow {
+    __device__ void operator()(uint4* __restrict__ rec, uint32_t r, uint32_t keys) const { rec[r] = make_uint4(keys, 0u, 0u, 0u); }
+};
 
 // a wave per queued record; kn, and the entries of off, count from the first record key
 __global__ __launch_bounds__(kCfThreads) void k_cf_small(const uint64_t* __restrict__ off, const uint32_t* __restrict__ kn_of, const uint32_t* __restrict__ hit,
@@ -137,7 +122,7 @@ __global__ __launch_bounds__(kCfThreads) void k_cf_small(const uint64_t* __restr
     __shared__ uint32_t s_all[kCfWaves][kCfSmallWork];
     const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
     uint32_t* s = s_all[wid];
-    const uint32_t n_small = words[kCfqSmall];
+    const uint32_t n_small = words[kRqSmall];
     const uint64_t q0 = off[0];
     for (uint64_t q = (uint64_t)blockIdx.x * kCfWaves + wid; q < n_small; q += (uint64_t)gridDim.x * kCfWaves) {   // (uniform per wave)
         const uint32_t r = q_small[q];
@@ -150,37 +135,23 @@ __global__ __launch_bounds__(kCfThreads) void k_cf_small(const uint64_t* __restr
             const uint64_t i = base + lane;
             const uint32_t kn = i < z ? kn_of[i] : 0u;
             const uint32_t ls = kn ? key_start[kn - 1u] : 0u, len = kn ? key_start[kn] - ls : 0u;
-            uint32_t incl = len;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(incl, d); if ((int)lane >= d) incl += t; }
+            const uint32_t incl = wave_prefix_incl(len, lane);
             const uint32_t total = __shfl(incl, 63);
             if (total > kCfSmallWork - W) { fits = false; break; }   // (never: the route sent a record of this much work elsewhere.  Uniform)
             const uint32_t at = W + incl - len;
             if (len <= kCfListCut)
                 for (uint32_t j = 0; j < len; ++j) s[at + j] = list[ls + j];
-            unsigned long long left = __ballot(len > kCfListCut);
-            while (left) {                                 // the long lists, one after another by the whole wave
-                const int l = __ffsll((long long)left) - 1;
-                const uint32_t s0 = __shfl(ls, l), n0 = __shfl(len, l), a0 = __shfl(at, l);
+            wave_long_lists(len > kCfListCut, ls, len, [=](int l, uint32_t s0, uint32_t n0) {
+                const uint32_t a0 = __shfl(at, l);
                 for (uint32_t j = lane; j < n0; j += 64u) s[a0 + j] = list[s0 + j];
-                left &= left - 1ull;
-            }
+            });
             W += total;
         }
-        if (!fits) { if (lane == 0u) atomicOr(words + kCfqBad, 1u); continue; }
+        if (!fits) { if (lane == 0u) atomicOr(words + kRqBad, 1u); continue; }
         uint32_t P = 64;
         while (P < W) P <<= 1;
         for (uint32_t i = W + lane; i < P; i += 64u) s[i] = 0xffffffffu;
-        cf_wave_sync();
-        for (uint32_t k = 2; k <= P; k <<= 1)
-            for (uint32_t j = k >> 1; j; j >>= 1) {
-                for (uint32_t t = lane; t < P / 2u; t += 64u) {
-                    const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i + j;
-                    const uint32_t x = s[i], y = s[l];
-                    if ((x > y) == ((i & k) == 0u)) { s[i] = y; s[l] = x; }
-                }
-                cf_wave_sync();
-            }
+        wave_sort_lds(s, P, lane);
         // every run of one number is a reference with shared = the run's length: its last place less the first place of its number
         unsigned long long kept = 0ull;
         uint32_t passing = 0;
@@ -190,16 +161,14 @@ __global__ __launch_bounds__(kCfThreads) void k_cf_small(const uint64_t* __restr
             if (i < W) {
                 const uint32_t ref = s[i];
                 if (i + 1u == W || s[i + 1u] != ref) {
-                    uint32_t lo = 0, hi = i;               // the first place that holds ref
-                    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (s[mid] < ref) lo = mid + 1u; else hi = mid; }
-                    const uint32_t shared = i - lo + 1u;
-                    if (cf_passes(shared, keys, min_keys, num, den)) v = cf_word(shared, ref);
+                    const uint32_t shared = i + 1u - lds_lower_bound(s, i, ref);
+                    if (passes_threshold(shared, keys, min_keys, num, den)) v = cf_word(shared, ref);
                 }
             }
             passing += (uint32_t)__popcll(__ballot(v != 0ull));
             cf_offer(kept, v, lane, top);
         }
-        cf_wave_sync();                                    // (the words are read: the next record may overwrite them)
+        wave_lds_sync();                                   // (the words are read: the next record may overwrite them)
         const uint32_t listed = passing < top ? passing : top;
         if (lane < listed) {
             spsp_classify_hit o;
@@ -223,7 +192,7 @@ __global__ __launch_bounds__(kCfLargeThreads) void k_cf_large(const uint64_t* __
     unsigned long long* s_kept = reinterpret_cast<unsigned long long*>(s_mem + (IN_LDS ? R_pad : 0u));
     uint32_t* s_pass = reinterpret_cast<uint32_t*>(s_kept + kCfLargeWaves * 64u);
     const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    const uint32_t n_large = words[kCfqLarge];
+    const uint32_t n_large = words[kRqLarge];
     const uint64_t q0 = off[0];
     for (uint64_t q = blockIdx.x; q < n_large; q += gridDim.x) {   // (uniform per workgroup)
         const uint32_t r = q_large[q];
@@ -242,13 +211,9 @@ __global__ __launch_bounds__(kCfLargeThreads) void k_cf_large(const uint64_t* __
             const uint32_t ls = kn ? key_start[kn - 1u] : 0u, len = kn ? key_start[kn] - ls : 0u;
             if (len <= kCfListCut)
                 for (uint32_t j = 0; j < len; ++j) { const uint32_t sk = list[ls + j]; if (sk < R) atomicAdd(&cnt[sk], 1u); }
-            unsigned long long left = __ballot(len > kCfListCut);
-            while (left) {                                 // the long lists, one after another by the whole wave
-                const int l = __ffsll((long long)left) - 1;
-                const uint32_t s0 = __shfl(ls, l), n0 = __shfl(len, l);
+            wave_long_lists(len > kCfListCut, ls, len, [=](int, uint32_t s0, uint32_t n0) {
                 for (uint32_t j = lane; j < n0; j += 64u) { const uint32_t sk = list[s0 + j]; if (sk < R) atomicAdd(&cnt[sk], 1u); }
-                left &= left - 1ull;
-            }
+            });
         }
         __syncthreads();
         unsigned long long kept = 0ull;
@@ -256,7 +221,7 @@ __global__ __launch_bounds__(kCfLargeThreads) void k_cf_large(const uint64_t* __
         for (uint32_t base = wid * 64u; base < R; base += kCfLargeThreads) {   // (uniform per wave)
             const uint32_t j = base + lane;
             const uint32_t c = j >= R ? 0u : IN_LDS ? cnt[j] : __hip_atomic_load(cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long v = c != 0u && cf_passes(c, keys, min_keys, num, den) ? cf_word(c, j) : 0ull;
+            const unsigned long long v = c != 0u && passes_threshold(c, keys, min_keys, num, den) ? cf_word(c, j) : 0ull;
             passing += (uint32_t)__popcll(__ballot(v != 0ull));
             cf_offer(kept, v, lane, top);
         }
@@ -323,93 +288,150 @@ int classify_probe_launch(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q
     return SPSP_OK;
 }
 
+int refuse_no_index(const char* pass) {
+    set_error("%s: the context holds no index (spsp_classify_index_device first; a prevalence, select, accumulation or groups call replaces it)", pass);
+    return SPSP_ERR_ARG;
+}
+
+int record_keys_check(const spsp_ctx* ctx, const char* pass, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, uint64_t n_keys) {
+    const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
+    if (n_keys && (!q_mn || !q_lo)) { set_error("NULL key array"); return SPSP_ERR_ARG; }
+    if (n_keys && (q_hi != nullptr) != X.has_hi) {
+        set_error("%s: the index was built %s kmer_hi (k %s 32), the records come %s it", pass, X.has_hi ? "with" : "without", X.has_hi ? ">" : "<=",
+                  q_hi ? "with" : "without");
+        return SPSP_ERR_ARG;
+    }
+    return SPSP_OK;
+}
+
+int record_call_front(const spsp_ctx* ctx, const char* pass, bool needs_taxonomy, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi,
+                      const uint64_t* h_rec_off, uint32_t n_rec, uint64_t* all_keys) {
+    if (n_rec > 0xfffffff0u) { set_error("too many records for one call (%u)", n_rec); return SPSP_ERR_OVERFLOW; }
+    for (uint32_t r = 0; r < n_rec; ++r)
+        if (h_rec_off[r + 1] < h_rec_off[r]) { set_error("record offsets must not decrease (record %u)", r); return SPSP_ERR_ARG; }
+    if (h_rec_off[n_rec] > 0xfffffff0ull) { set_error("too many record keys for one call"); return SPSP_ERR_OVERFLOW; }
+    const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
+    if (!X.valid) return refuse_no_index(pass);
+    if (needs_taxonomy && !X.taxonomy) {
+        set_error("taxonomy: the index holds no taxonomy (spsp_taxonomy_index_device first; it ends with the index it was attached to)");
+        return SPSP_ERR_ARG;
+    }
+    *all_keys = h_rec_off[n_rec] - h_rec_off[0];
+    return record_keys_check(ctx, pass, q_mn, q_lo, q_hi, *all_keys);
+}
+
+int RecordWork::reserve(spsp_ctx* ctx, uint32_t n, uint64_t keys, size_t row) {
+    int rc;
+    n_rec = n; all_keys = keys; row_bytes = row;
+    const size_t work_bytes = (size_t)n * 8;
+    if ((rc = ctx->cf_off.reserve(((size_t)n + 1) * 8)) || (rc = ctx->cf_kn.reserve((size_t)keys * 4)) || (rc = ctx->cf_work.reserve(work_bytes + (size_t)n * 4)) ||
+        (rc = ctx->cf_queue.reserve(64 + (size_t)2 * n * 4)) || (rc = ctx->cf_rec.reserve((size_t)n * row))) return rc;
+    off = ctx->cf_off.as<uint64_t>();
+    kn = ctx->cf_kn.as<uint32_t>();
+    work = ctx->cf_work.as<unsigned long long>();
+    hit = reinterpret_cast<uint32_t*>(ctx->cf_work.as<uint8_t>() + work_bytes);
+    words = ctx->cf_queue.as<uint32_t>();
+    q_small = words + 16;
+    q_large = q_small + n;
+    rec = ctx->cf_rec.as<uint4>();
+    g_route = (uint32_t)(((uint64_t)n + kRouteThreads - 1) / kRouteThreads);
+    g_small = (uint32_t)std::min<uint64_t>(((uint64_t)n + kRecordWaves - 1) / kRecordWaves, (uint64_t)std::max(ctx->n_cu, 1) * 8u);
+    return SPSP_OK;
+}
+
+int RecordWork::upload(spsp_ctx* ctx, const uint64_t* h_rec_off) {
+    SPSP_HIP(hipMemcpyAsync(off, h_rec_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));   // (the caller's: alive until the wait)
+    return SPSP_OK;
+}
+
+int RecordWork::clear(spsp_ctx* ctx) {
+    SPSP_HIP(hipMemsetAsync(work, 0, (size_t)n_rec * 12, ctx->stream));   // (the hit keys sit behind the work)
+    SPSP_HIP(hipMemsetAsync(words, 0, kRqWords * 4, ctx->stream));
+    SPSP_HIP(hipMemsetAsync(rec, 0, (size_t)n_rec * row_bytes, ctx->stream));
+    return SPSP_OK;
+}
+
+int RecordWork::read_back(spsp_ctx* ctx, std::vector<uint32_t>* rows) {
+    rows->resize((size_t)n_rec * (row_bytes / 4));         // (in front of the copies: the device is still at work while the host clears these)
+    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCfBad, words + kRqBad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipMemcpyAsync(rows->data(), rec, rows->size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return SPSP_OK;
+}
+
+int RecordWork::wait(spsp_ctx* ctx, RecordClock& clock, bool* fitted) {
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));           // the one wait
+    if (clock.on)
+        for (int i = 0; i < 4; ++i) { float ms = 0; SPSP_HIP(hipEventElapsedTime(&ms, clock.ev[i], clock.ev[i + 1])); clock.ms[i] += ms; }
+    *fitted = (uint32_t)ctx->h_scalar[kHsCfBad] == 0u;
+    return SPSP_OK;
+}
+
+int RecordClock::mark(spsp_ctx* ctx, int i) {
+    if (i == 0 && (on = ctx->timing))                      // spsp_timing_enable: events between the launches (the pass's *_stage_ms call)
+        for (hipEvent_t& e : ev) if (!e) SPSP_HIP(hipEventCreate(&e));
+    if (on) SPSP_HIP(hipEventRecord(ev[i], ctx->stream));
+    return SPSP_OK;
+}
+
+void RecordClock::hand_out(double* out) {
+    for (int i = 0; i < 4; ++i) { out[i] = ms[i]; ms[i] = 0; }
+}
+
 int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
                          uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, spsp_classify_record* records, spsp_classify_hit* hits) {
     int rc;
     // (what is zeroed in front of the refusals: the records' counts always, the hits once `top` says how many there are)
     for (uint32_t r = 0; r < n_rec; ++r) records[r].keys = records[r].hit_keys = records[r].passing = records[r].listed = 0;
     if (n_rec && top >= 1 && top <= kCfMaxTop) memset(hits, 0, (size_t)n_rec * top * sizeof(spsp_classify_hit));
-    if ((rc = classify_check_args(top, min_keys, num, den))) return rc;
-    if (n_rec > 0xfffffff0u) { set_error("too many records for one call (%u)", n_rec); return SPSP_ERR_OVERFLOW; }
-    for (uint32_t r = 0; r < n_rec; ++r)
-        if (h_rec_off[r + 1] < h_rec_off[r]) { set_error("record offsets must not decrease (record %u)", r); return SPSP_ERR_ARG; }
-    if (h_rec_off[n_rec] > 0xfffffff0ull) { set_error("too many record keys for one call"); return SPSP_ERR_OVERFLOW; }
+    uint64_t all_keys = 0;
+    if ((rc = classify_check_args(top, min_keys, num, den)) || (rc = record_call_front(ctx, "classification", false, q_mn, q_lo, q_hi, h_rec_off, n_rec, &all_keys)))
+        return rc;
     const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
-    if (!X.valid) { set_error("classification: the context holds no index (spsp_classify_index_device first; a prevalence, select, accumulation or groups call replaces it)"); return SPSP_ERR_ARG; }
-    const uint64_t q0 = h_rec_off[0], all_keys = h_rec_off[n_rec] - q0;
-    if (all_keys && (!q_mn || !q_lo)) { set_error("NULL key array"); return SPSP_ERR_ARG; }
-    if (all_keys && (q_hi != nullptr) != X.has_hi) {
-        set_error("classification: the index was built %s kmer_hi (k %s 32), the records come %s it", X.has_hi ? "with" : "without", X.has_hi ? ">" : "<=",
-                  q_hi ? "with" : "without");
-        return SPSP_ERR_ARG;
-    }
     for (uint32_t r = 0; r < n_rec; ++r) records[r].keys = (uint32_t)(h_rec_off[r + 1] - h_rec_off[r]);   // (length is the caller's)
     if (n_rec == 0 || all_keys == 0 || X.entries == 0) return SPSP_OK;   // (no record, no record key or no reference key: nothing is shared)
 
     const uint32_t R = X.n_ref, R_pad = (R + 3u) & ~3u;
     const bool in_lds = R <= kCfLdsRefs;
     const int n_cu = std::max(ctx->n_cu, 1);
-    const size_t lds = kCfLargeFixedLds + (in_lds ? (size_t)R_pad * 4 : 0);
+    const size_t lds = kCfLargeFixedLds + (in_lds ? (size_t)R_pad * 4 : 0), hits_bytes = (size_t)n_rec * top * sizeof(spsp_classify_hit);
     const uint32_t large_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2048 / kCfLargeThreads, kAcLdsBytes / lds));
     const uint32_t g_large = (uint32_t)std::min<uint64_t>(n_rec, (uint64_t)n_cu * (in_lds ? large_per_cu : 1u));
-    const uint32_t g_small = (uint32_t)std::min<uint64_t>(((uint64_t)n_rec + kCfWaves - 1) / kCfWaves, (uint64_t)n_cu * 8u);
-    const size_t work_bytes = (size_t)n_rec * 8, queue_bytes = 64 + (size_t)2 * n_rec * 4;
-    if ((rc = ctx->cf_off.reserve(((size_t)n_rec + 1) * 8)) || (rc = ctx->cf_kn.reserve((size_t)all_keys * 4)) ||
-        (rc = ctx->cf_work.reserve(work_bytes + (size_t)n_rec * 4)) || (rc = ctx->cf_queue.reserve(queue_bytes)) ||
-        (rc = ctx->cf_rec.reserve((size_t)n_rec * 16)) || (rc = ctx->cf_hits.reserve((size_t)n_rec * top * sizeof(spsp_classify_hit))) ||
+    RecordWork W;
+    if ((rc = W.reserve(ctx, n_rec, all_keys, 16)) || (rc = ctx->cf_hits.reserve(hits_bytes)) ||
         (!in_lds && (rc = ctx->cf_rows.reserve((size_t)g_large * R_pad * 4)))) return rc;
-    uint64_t* d_off = ctx->cf_off.as<uint64_t>();
-    uint32_t* d_kn = ctx->cf_kn.as<uint32_t>();
-    unsigned long long* d_work = ctx->cf_work.as<unsigned long long>();
-    uint32_t* d_hit = reinterpret_cast<uint32_t*>(ctx->cf_work.as<uint8_t>() + work_bytes);
-    uint32_t* d_words = ctx->cf_queue.as<uint32_t>();
-    uint32_t* d_q_small = d_words + 16;
-    uint32_t* d_q_large = d_q_small + n_rec;
-    uint4* d_rec = ctx->cf_rec.as<uint4>();
     spsp_classify_hit* d_hits = ctx->cf_hits.as<spsp_classify_hit>();
     uint32_t* d_rows = in_lds ? nullptr : ctx->cf_rows.as<uint32_t>();
-    SPSP_HIP(hipMemcpyAsync(d_off, h_rec_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));   // (the caller's: alive until the wait)
-    SPSP_HIP(hipMemsetAsync(d_work, 0, work_bytes + (size_t)n_rec * 4, ctx->stream));
-    SPSP_HIP(hipMemsetAsync(d_words, 0, kCfqWords * 4, ctx->stream));
-    SPSP_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_rec * 16, ctx->stream));
-    SPSP_HIP(hipMemsetAsync(d_hits, 0, (size_t)n_rec * top * sizeof(spsp_classify_hit), ctx->stream));
-    const uint32_t gr = (uint32_t)(((uint64_t)n_rec + kCfThreads - 1) / kCfThreads);
-    hipEvent_t* ev = nullptr;
-    if (ctx->timing) {                                     // spsp_timing_enable: events between the launches (spsp_classify_stage_ms)
-        for (hipEvent_t& e : ctx->cf_events) if (!e) SPSP_HIP(hipEventCreate(&e));
-        ev = ctx->cf_events;
-        SPSP_HIP(hipEventRecord(ev[0], ctx->stream));
-    }
-    if ((rc = classify_probe_launch(ctx, q_mn, q_lo, q_hi, d_off, n_rec, all_keys, d_kn, d_work, d_hit))) return rc;
-    if (ev) SPSP_HIP(hipEventRecord(ev[1], ctx->stream));
-    hipLaunchKernelGGL(k_cf_route, dim3(gr), dim3(kCfThreads), 0, ctx->stream, (const uint64_t*)d_off, n_rec, (const unsigned long long*)d_work,
-                       (const uint32_t*)d_hit, d_words, d_q_small, d_q_large, d_rec);
-    if (ev) SPSP_HIP(hipEventRecord(ev[2], ctx->stream));
-    hipLaunchKernelGGL(k_cf_small, dim3(g_small), dim3(kCfThreads), 0, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn, (const uint32_t*)d_hit,
-                       X.key_start, X.list, (const uint32_t*)d_q_small, d_words, top, min_keys, num, den, d_rec, d_hits);
-    if (ev) SPSP_HIP(hipEventRecord(ev[3], ctx->stream));
+    if ((rc = W.upload(ctx, h_rec_off)) || (rc = W.clear(ctx))) return rc;
+    SPSP_HIP(hipMemsetAsync(d_hits, 0, hits_bytes, ctx->stream));
+    RecordClock& clock = ctx->cf_clock;
+    if ((rc = clock.mark(ctx, 0)) || (rc = classify_probe_launch(ctx, q_mn, q_lo, q_hi, W.off, n_rec, all_keys, W.kn, W.work, W.hit)) || (rc = clock.mark(ctx, 1)))
+        return rc;
+    hipLaunchKernelGGL((k_rec_route<unsigned long long, CfEmptyRow>), dim3(W.g_route), dim3(kRouteThreads), 0, ctx->stream, (const uint64_t*)W.off, n_rec,
+                       (const unsigned long long*)W.work, (unsigned long long)kCfSmallWork, W.words, W.q_small, W.q_large, W.rec, CfEmptyRow{});
+    if ((rc = clock.mark(ctx, 2))) return rc;
+    hipLaunchKernelGGL(k_cf_small, dim3(W.g_small), dim3(kCfThreads), 0, ctx->stream, (const uint64_t*)W.off, (const uint32_t*)W.kn, (const uint32_t*)W.hit,
+                       X.key_start, X.list, (const uint32_t*)W.q_small, W.words, top, min_keys, num, den, W.rec, d_hits);
+    if ((rc = clock.mark(ctx, 3))) return rc;
     if (in_lds) {
         if ((rc = lds_opt_in(ctx, &k_cf_large<true>, kAcLdsBytes))) return rc;
-        hipLaunchKernelGGL(k_cf_large<true>, dim3(g_large), dim3(kCfLargeThreads), lds, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn,
-                           (const uint32_t*)d_hit, X.key_start, X.list, (const uint32_t*)d_q_large, (const uint32_t*)d_words, R, R_pad, d_rows, top, min_keys,
-                           num, den, d_rec, d_hits);
+        hipLaunchKernelGGL(k_cf_large<true>, dim3(g_large), dim3(kCfLargeThreads), lds, ctx->stream, (const uint64_t*)W.off, (const uint32_t*)W.kn,
+                           (const uint32_t*)W.hit, X.key_start, X.list, (const uint32_t*)W.q_large, (const uint32_t*)W.words, R, R_pad, d_rows, top, min_keys,
+                           num, den, W.rec, d_hits);
     } else {
-        hipLaunchKernelGGL(k_cf_large<false>, dim3(g_large), dim3(kCfLargeThreads), lds, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn,
-                           (const uint32_t*)d_hit, X.key_start, X.list, (const uint32_t*)d_q_large, (const uint32_t*)d_words, R, R_pad, d_rows, top, min_keys,
-                           num, den, d_rec, d_hits);
+        hipLaunchKernelGGL(k_cf_large<false>, dim3(g_large), dim3(kCfLargeThreads), lds, ctx->stream, (const uint64_t*)W.off, (const uint32_t*)W.kn,
+                           (const uint32_t*)W.hit, X.key_start, X.list, (const uint32_t*)W.q_large, (const uint32_t*)W.words, R, R_pad, d_rows, top, min_keys,
+                           num, den, W.rec, d_hits);
     }
     SPSP_HIP(hipGetLastError());
-    if (ev) SPSP_HIP(hipEventRecord(ev[4], ctx->stream));
-    std::vector<uint32_t> got((size_t)n_rec * 4);
-    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCfBad, d_words + kCfqBad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SPSP_HIP(hipMemcpyAsync(got.data(), d_rec, got.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SPSP_HIP(hipMemcpyAsync(hits, d_hits, (size_t)n_rec * top * sizeof(spsp_classify_hit), hipMemcpyDeviceToHost, ctx->stream));
-    SPSP_HIP(hipStreamSynchronize(ctx->stream));           // the one wait
-    if (ev)
-        for (int i = 0; i < 4; ++i) { float ms = 0; SPSP_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); ctx->cf_ms[i] += ms; }
-    if ((uint32_t)ctx->h_scalar[kHsCfBad]) {
+    if ((rc = clock.mark(ctx, 4))) return rc;
+    std::vector<uint32_t> got;
+    bool fitted = false;
+    if ((rc = W.read_back(ctx, &got))) return rc;
+    SPSP_HIP(hipMemcpyAsync(hits, d_hits, hits_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = W.wait(ctx, clock, &fitted))) return rc;
+    if (!fitted) {
         set_error("classification: a record's holders did not fit the form it was routed to (the key arrays changed during the call?)");
-        memset(hits, 0, (size_t)n_rec * top * sizeof(spsp_classify_hit));
+        memset(hits, 0, hits_bytes);
         return SPSP_ERR_ARG;
     }
     for (uint32_t r = 0; r < n_rec; ++r) {
@@ -519,12 +541,13 @@ int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
     return SPSP_OK;
 }
 
-// the road of spsp_classify_files and spsp_taxonomy_files: load, refusals, decode, index, on_index, the records through their batches
-int records_files_road(FilesRun& run, const char* records_path, double rate, const std::function<int()>& on_index, std::vector<std::string>* names,
-                       const std::function<int(uint32_t, const uint64_t*)>& on_records, const std::function<int(const RecordBatch&)>& on_batch, double* t1) {
+// the road of the four record file drivers: load, refusals, decode, index, on_index, every records file through its batches, on_close
+int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
+                       const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
+                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1) {
     spsp_ctx* ctx = run.ctx;
     int rc = run.load(rate);
-    if (!rc) rc = run.refuse_k_eq_m(rc, "classification is");
+    if (!rc) rc = run.refuse_k_eq_m(rc, what_is);
     double rec_rate = run.L.ds_rate;                       // the records are scanned at ONE threshold: mixed rates need a rate, as -S
     if (!rc) rc = sketches_out_rate(run.L, run.paths, run.n, &rec_rate);
     if ((rc = run.begin(rc))) return rc;
@@ -533,14 +556,19 @@ int records_files_road(FilesRun& run, const char* records_path, double rate, con
     if (!rc) rc = classify_index_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), run.n);
     if (!rc) rc = on_index();
     if (!rc) {
-        uint8_t* text = nullptr; uint64_t n_text = 0;
         spsp_ctx* side = nullptr;
         spsp_params p{};
         p.k = keys.k; p.m = keys.m; p.threshold = spsp_threshold_host(keys.k, keys.m, rec_rate); p.abundance = 1; p.flags = 0;
-        if (!(rc = spsp_read_file_host(records_path, &text, &n_text)) && !(rc = spsp_create(ctx->device, nullptr, &side)))
-            rc = records_text_batches(ctx, side, &p, text, n_text, records_path, names, on_records, on_batch);
+        for (uint32_t f = 0; !rc && f < n_records_paths; ++f) {
+            uint8_t* text = nullptr; uint64_t n_text = 0;
+            if (!(rc = spsp_read_file_host(records_paths[f], &text, &n_text)) && (side || !(rc = spsp_create(ctx->device, nullptr, &side))) &&
+                !(rc = spsp_wait_stream(side, ctx)))       // (the last file's keys have been read)
+                rc = records_text_batches(ctx, side, &p, text, n_text, records_paths[f], names, on_records, on_batch);
+            spsp_free(text);
+        }
+        if (!rc) rc = on_close();
+        (void)hipStreamSynchronize(ctx->stream);           // (what on_batch queued reads the side context's key arrays)
         if (side) { (void)hipStreamSynchronize(side->stream); spsp_destroy(side); }
-        spsp_free(text);
     }
     *t1 = run.end();
     return rc;
@@ -554,7 +582,7 @@ static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
     std::vector<std::string> names;
     double t1 = 0;
     int rc = records_files_road(
-        run, records_path, rate, [] { return SPSP_OK; }, &names,
+        run, "classification is", &records_path, 1, rate, [] { return SPSP_OK; }, &names,
         [&](uint32_t n_rec, const uint64_t* rec_off) {
             recs->assign(n_rec, spsp_classify_record{});
             hits->assign((size_t)n_rec * top, spsp_classify_hit{});
@@ -565,7 +593,7 @@ static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
             return classify_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, top, min_keys, num, den, recs->data() + B.first_record,
                                         hits->data() + (size_t)B.first_record * top);
         },
-        &t1);
+        [] { return SPSP_OK; }, &t1);
     if (rc) return rc;
     std::vector<const char*> name_ptr(names.size());
     for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
@@ -625,6 +653,6 @@ extern "C" int spsp_classify_files(spsp_ctx* ctx, const char* const* index_paths
 
 extern "C" int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms) {
     if (!ctx || !ms) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    for (int i = 0; i < 4; ++i) { ms[i] = ctx->cf_ms[i]; ctx->cf_ms[i] = 0; }
+    ctx->cf_clock.hand_out(ms);
     return SPSP_OK;
 }

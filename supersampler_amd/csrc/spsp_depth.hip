@@ -97,8 +97,7 @@ __global__ __launch_bounds__(kDpThreads) void k_dp_entry(const uint32_t* __restr
 
 // sums over the workgroup: every lane gets the total.  s: kDpWaves words nobody else uses between the two barriers inside
 __device__ __forceinline__ unsigned long long dp_block_sum(unsigned long long v, unsigned long long* s) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    v = wave_sum(v);
     __syncthreads();                                       // (the last use of s is over)
     if ((threadIdx.x & 63u) == 0u) s[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -108,8 +107,7 @@ __device__ __forceinline__ unsigned long long dp_block_sum(unsigned long long v,
     return t;
 }
 __device__ __forceinline__ uint32_t dp_block_max(uint32_t v, unsigned long long* s) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
+    v = wave_max(v);
     __syncthreads();
     if ((threadIdx.x & 63u) == 0u) s[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -121,9 +119,7 @@ __device__ __forceinline__ uint32_t dp_block_max(uint32_t v, unsigned long long*
 // the exclusive prefix of v over the workgroup's lanes in lane order
 __device__ __forceinline__ uint32_t dp_block_prefix(uint32_t v, unsigned long long* s) {
     const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(incl, d); if ((int)lane >= d) incl += t; }
+    const uint32_t incl = wave_prefix_incl(v, lane);
     __syncthreads();
     if (lane == 63u) s[wid] = incl;
     __syncthreads();
@@ -298,7 +294,6 @@ __global__ __launch_bounds__(kDpThreads) void k_dp_merge(const uint64_t* __restr
     if (threadIdx.x == 0u) rows[j] = row;
 }
 
-const char* const kNoIndex = "classification: the context holds no index (spsp_classify_index_device first; a prevalence, select, accumulation or groups call replaces it)";
 const char* const kNoDepth = "depth: the context holds no counters (spsp_depth_begin_device first; they end with the index they were made for)";
 
 }  // namespace
@@ -306,7 +301,7 @@ const char* const kNoDepth = "depth: the context holds no counters (spsp_depth_b
 int depth_begin_impl(spsp_ctx* ctx) {
     int rc;
     spsp_ctx::ClassifyIndex& X = ctx->cf_index;
-    if (!X.valid) { set_error("%s", kNoIndex); return SPSP_ERR_ARG; }
+    if (!X.valid) return refuse_no_index("classification");
     X.depth = false;
     const uint32_t E = X.entries;
     uint32_t D = 0;
@@ -355,12 +350,7 @@ int depth_begin_impl(spsp_ctx* ctx) {
 int depth_add_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, uint64_t first, uint64_t n_keys) {
     const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
     if (!X.valid || !X.depth) { set_error("%s", kNoDepth); return SPSP_ERR_ARG; }
-    if (n_keys && (!q_mn || !q_lo)) { set_error("NULL key array"); return SPSP_ERR_ARG; }
-    if (n_keys && (q_hi != nullptr) != X.has_hi) {
-        set_error("depth: the index was built %s kmer_hi (k %s 32), the records come %s it", X.has_hi ? "with" : "without", X.has_hi ? ">" : "<=",
-                  q_hi ? "with" : "without");
-        return SPSP_ERR_ARG;
-    }
+    if (int rc = record_keys_check(ctx, "depth", q_mn, q_lo, q_hi, n_keys)) return rc;
     if (n_keys > 0xfffffff0ull) { set_error("too many record keys for one call"); return SPSP_ERR_OVERFLOW; }
     if (ctx->dp_record_keys + n_keys > 0xffffffffull) {
         set_error("depth: more than 4 294 967 295 record keys since spsp_depth_begin_device (a 32-bit counter could wrap)");
@@ -459,41 +449,24 @@ int depth_read_impl(spsp_ctx* ctx, uint32_t min_count, spsp_depth_row* rows, sps
 int depth_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* const* reads_paths, uint32_t n_reads, uint32_t min_count, int precision,
                      const char* out_prefix, int chatter, double rate, std::vector<spsp_depth_row>* rows, spsp_depth_totals* totals, ProfileAsk* profile) {
     FilesRun run(ctx, paths, n_ref, chatter);
-    int rc = run.load(rate);
-    if (!rc) rc = run.refuse_k_eq_m(rc, "depth is");
-    double rec_rate = run.L.ds_rate;                       // the reads are scanned at ONE threshold: mixed rates need a rate, as -X
-    if (!rc) rc = sketches_out_rate(run.L, paths, n_ref, &rec_rate);
-    if ((rc = run.begin(rc))) return rc;
-    const DecodedKeys& keys = run.keys;
-    rc = run.decode();
-    if (!rc) rc = classify_index_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), n_ref);
-    if (!rc) rc = depth_begin_impl(ctx);
     uint64_t n_records = 0;
+    double t1 = 0;
     rows->assign(n_ref, spsp_depth_row{});
-    if (!rc) {
-        spsp_ctx* side = nullptr;
-        spsp_params p{};
-        p.k = keys.k; p.m = keys.m; p.threshold = spsp_threshold_host(keys.k, keys.m, rec_rate); p.abundance = 1; p.flags = 0;
-        rc = spsp_create(ctx->device, nullptr, &side);
-        for (uint32_t f = 0; !rc && f < n_reads; ++f) {
-            uint8_t* text = nullptr; uint64_t n_text = 0;
-            if (!(rc = spsp_read_file_host(reads_paths[f], &text, &n_text)) && !(rc = spsp_wait_stream(side, ctx)))   // (the last file's keys have been read)
-                rc = records_text_batches(
-                    ctx, side, &p, text, n_text, reads_paths[f], nullptr, [&](uint32_t n_rec, const uint64_t*) { n_records += n_rec; return SPSP_OK; },
-                    [&](const RecordBatch& B) { return depth_add_impl(ctx, B.mn, B.lo, B.hi, B.key_off[0], B.key_off[B.n_records] - B.key_off[0]); });
-            spsp_free(text);
-        }
-        if (!rc) rc = depth_read_impl(ctx, min_count, rows->data(), totals, nullptr);
-        if (!rc && profile) {
-            uint64_t n_rows = 0;
-            profile->rows.assign(n_ref, spsp_profile_row{});
-            rc = profile_impl(ctx, min_count, profile->min_keys, profile->max_rounds, profile->rows.data(), &n_rows, &profile->totals, nullptr);
-            profile->rows.resize(rc ? 0 : (size_t)n_rows);
-        }
-        (void)hipStreamSynchronize(ctx->stream);           // (the adds read the side context's key arrays)
-        if (side) { (void)hipStreamSynchronize(side->stream); spsp_destroy(side); }
-    }
-    const double t1 = run.end();
+    int rc = records_files_road(
+        run, "depth is", reads_paths, n_reads, rate, [&] { return depth_begin_impl(ctx); }, nullptr,
+        [&](uint32_t n_rec, const uint64_t*) { n_records += n_rec; return SPSP_OK; },
+        [&](const RecordBatch& B) { return depth_add_impl(ctx, B.mn, B.lo, B.hi, B.key_off[0], B.key_off[B.n_records] - B.key_off[0]); },
+        [&] {                                              // the read and, where asked, the profile: in front of the side context's end
+            int rc = depth_read_impl(ctx, min_count, rows->data(), totals, nullptr);
+            if (!rc && profile) {
+                uint64_t n_rows = 0;
+                profile->rows.assign(n_ref, spsp_profile_row{});
+                rc = profile_impl(ctx, min_count, profile->min_keys, profile->max_rounds, profile->rows.data(), &n_rows, &profile->totals, nullptr);
+                profile->rows.resize(rc ? 0 : (size_t)n_rows);
+            }
+            return rc;
+        },
+        &t1);
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
     if ((rc = spsp_depth_csv_host(rows->data(), paths, n_ref, precision, &text, &len))) return rc;

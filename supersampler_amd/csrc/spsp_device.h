@@ -160,4 +160,98 @@ __device__ __forceinline__ void cl_union(uint32_t* __restrict__ parent, uint32_t
     }
 }
 
+// ---- What the record passes share on the device (DESIGN "What the record passes share"): classify, taxonomy, depth, profile and the
+// key-major build of the accumulation.  A wave is 64 lanes; every helper is called by all of them (uniform control flow).
+
+// the wave's LDS words: what its lanes stored in front of this line is what they read behind it
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// reductions over the wave: every lane gets the result
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(v, d); v = o < v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(v, d); v = o > v ? o : v; }
+    return v;
+}
+// the sum of v over the lanes up to and including this one
+__device__ __forceinline__ uint32_t wave_prefix_incl(uint32_t v, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(v, d); if ((int)lane >= d) v += t; }
+    return v;
+}
+
+// the wave's words s[0 .. P) in LDS sorted ascending by a bitonic network; P a power of two >= 64, and what the lanes stored in
+// front of the call is what is sorted.  (log2 P)(log2 P + 1) / 2 steps of P / 2 compare-exchanges, a lane taking every 64th
+__device__ __forceinline__ void wave_sort_lds(uint32_t* s, uint32_t P, uint32_t lane) {
+    wave_lds_sync();
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j; j >>= 1) {
+            for (uint32_t t = lane; t < P / 2u; t += 64u) {
+                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i + j;
+                const uint32_t x = s[i], y = s[l];
+                if ((x > y) == ((i & k) == 0u)) { s[i] = y; s[l] = x; }
+            }
+            wave_lds_sync();
+        }
+}
+
+// the first place of the sorted words s[0 .. n) that holds v or more
+__device__ __forceinline__ uint32_t lds_lower_bound(const uint32_t* s, uint32_t n, uint32_t v) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (s[mid] < v) lo = mid + 1u; else hi = mid; }
+    return lo;
+}
+
+// the threshold rule of classify (shared keys of a reference) and taxonomy (hit keys of a clade) for a record of `keys` keys
+__device__ __forceinline__ bool passes_threshold(uint32_t shared, uint32_t keys, uint32_t min_keys, uint32_t num, uint32_t den) {
+    return shared >= min_keys && (unsigned long long)shared * den >= (unsigned long long)num * keys;
+}
+
+// the long lists among the 64 a wave holds (a lane's: `len` holders from list[ls], is_long: more than the pass's cut), one after
+// another by the whole wave: body(l, s0, n0) for the list of lane l, its start and its length in every lane
+template <class Body>
+__device__ __forceinline__ void wave_long_lists(bool is_long, uint32_t ls, uint32_t len, Body body) {
+    unsigned long long left = __ballot(is_long);
+    while (left) {
+        const int l = __ffsll((long long)left) - 1;
+        body(l, (uint32_t)__shfl(ls, l), (uint32_t)__shfl(len, l));
+        left &= left - 1ull;
+    }
+}
+
+// The route kernel of the two record calls, a lane per record: a record whose measure (classify: the work, the holders of its keys;
+// taxonomy: its hit keys) is zero gets its row written here by empty(rec, r, keys); one of at most `cut` goes to the queue of the
+// wave form, the others to the workgroup form's.  The queues' order is a race and no result depends on it
+constexpr uint32_t kRouteThreads = 256;
+enum { kRqSmall = 0, kRqLarge = 1, kRqBad = 2, kRqWords = 4 };   // words in front of the queues: their fill, the flag word, one spare
+template <class Measure, class Empty>
+__global__ __launch_bounds__(kRouteThreads) void k_rec_route(const uint64_t* __restrict__ off, uint32_t n_rec, const Measure* __restrict__ measure, Measure cut,
+                                                             uint32_t* __restrict__ words, uint32_t* __restrict__ q_small, uint32_t* __restrict__ q_large,
+                                                             uint4* __restrict__ rec, Empty empty) {
+    const uint64_t r = (uint64_t)blockIdx.x * kRouteThreads + threadIdx.x;
+    if (r >= n_rec) return;
+    const Measure w = measure[r];
+    if (w == 0) empty(rec, (uint32_t)r, (uint32_t)(off[r + 1] - off[r]));
+    else if (w <= cut) q_small[atomicAdd(words + kRqSmall, 1u)] = (uint32_t)r;   // (a queue has room for every record)
+    else q_large[atomicAdd(words + kRqLarge, 1u)] = (uint32_t)r;
+}
+
 }  // namespace spsp

@@ -1850,20 +1850,21 @@ int write_key_sketches(uint32_t k, uint32_t m, double rate, const HostKeys& keys
     return SPSP_OK;
 }
 
-// spsp_classify.hip: what a classification call and the file driver refuse before anything else
-int classify_check_args(uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den) {
-    if (top == 0 || top > kCfMaxTop) { set_error("classification lists 1 .. %u matches per record (top = %u)", kCfMaxTop, top); return SPSP_ERR_ARG; }
-    if (min_keys == 0) { set_error("classification: min_keys is 1 at the least"); return SPSP_ERR_ARG; }
-    if (den == 0 || num > den || den > kCfMaxDen) { set_error("classification threshold %u / %u: needs 0 <= num <= den, 1 <= den <= %u", num, den, kCfMaxDen); return SPSP_ERR_ARG; }
+// the threshold rule's arguments as a classification and a taxonomy call take them (what: the pass's name in the texts)
+static int threshold_check(const char* what, uint32_t min_keys, uint32_t num, uint32_t den) {
+    if (min_keys == 0) { set_error("%s: min_keys is 1 at the least", what); return SPSP_ERR_ARG; }
+    if (den == 0 || num > den || den > kCfMaxDen) { set_error("%s threshold %u / %u: needs 0 <= num <= den, 1 <= den <= %u", what, num, den, kCfMaxDen); return SPSP_ERR_ARG; }
     return SPSP_OK;
 }
 
-// spsp_taxonomy.hip: likewise
-int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den) {
-    if (min_keys == 0) { set_error("taxonomy: min_keys is 1 at the least"); return SPSP_ERR_ARG; }
-    if (den == 0 || num > den || den > kCfMaxDen) { set_error("taxonomy threshold %u / %u: needs 0 <= num <= den, 1 <= den <= %u", num, den, kCfMaxDen); return SPSP_ERR_ARG; }
-    return SPSP_OK;
+// spsp_classify.hip: what a classification call and the file driver refuse before anything else
+int classify_check_args(uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den) {
+    if (top == 0 || top > kCfMaxTop) { set_error("classification lists 1 .. %u matches per record (top = %u)", kCfMaxTop, top); return SPSP_ERR_ARG; }
+    return threshold_check("classification", min_keys, num, den);
 }
+
+// spsp_taxonomy.hip: likewise
+int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den) { return threshold_check("taxonomy", min_keys, num, den); }
 }  // namespace spsp
 
 namespace {

@@ -53,6 +53,16 @@ namespace spsp {
 struct EventLog {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> used, spare;
 };
+// the events of one kind of record call (spsp_classify_device, spsp_taxonomy_device) while timing is on: in front of the probe, the
+// route, the wave form, the workgroup form, and behind it; ms: their four spans added up since the pass's *_stage_ms call last read
+// them.  mark(ctx, 0) opens a call (on: the context's timing as that call found it) and makes the events once; the context destroys them
+struct RecordClock {
+    hipEvent_t ev[5] = {};
+    double ms[4] = {};
+    bool on = false;
+    int mark(spsp_ctx* ctx, int i);
+    void hand_out(double* out4);          // -> out4, and ms cleared
+};
 enum { kEvDense = 0, kEvScan = 1, kEvAccumulate = 2, kEvCompare = 3, kEvScatter = 4, kEvGroup = 5, kEvKinds = 6 };
 }  // namespace spsp
 
@@ -296,9 +306,10 @@ struct spsp_ctx {
     spsp::DevBuf gp_table, gp_cell, gp_work, gp_mn, gp_lo, gp_hi, gp_t_mn, gp_t_lo, gp_t_hi;
     // classification (spsp_classify.hip).  The index IS the prevalence table (pv_table, its counters spent as cursors) and the
     // accumulation's key-major form (ac_work: key_no per entry; ac_keys: key_start; ac_list) over the caller's reference arrays:
-    // whatever fills that table again (prevalence_fill_table) drops it.  Per call: record offsets, key number + 1 per record key,
-    // work and hit keys per record, the two queues with their counters and the flag word, the records' four words, the hits, and
-    // the counter rows of the large form where they do not fit the LDS
+    // whatever fills that table again (prevalence_fill_table) drops it.  Per record call, classify's or taxonomy's (RecordWork; every
+    // call waits for the device before it returns, so nothing is in use across calls): record offsets, key number + 1 per record
+    // key, work and hit keys per record, the two queues with their counters and the flag word, the records' rows (four words for
+    // classify, eight for taxonomy), and the counter rows of either workgroup form where they do not fit the LDS; classify's hits
     struct ClassifyIndex {
         bool valid = false, has_hi = false;
         uint32_t n_ref = 0, entries = 0;
@@ -330,14 +341,10 @@ struct spsp_ctx {
     std::vector<hipEvent_t> pf_events;   // while timing is on: around the start, every pick and walk of a batch, and the reduction
     double pf_ms[4] = {};                // ... their milliseconds since spsp_profile_stage_ms last read them: start, picks, walks, reduction
     uint32_t pf_last[3] = {};            // the last call's rounds queued, rows and host waits (spsp_profile_counts hands them out)
-    hipEvent_t cf_events[5] = {};        // while timing is on: in front of the probe, the route, the small form, the large form, and behind it
-    double cf_ms[4] = {};                // ... their milliseconds added up since spsp_classify_stage_ms last read them
     // taxonomy (spsp_taxonomy.hip), on the classification's index: the tree (parent | size | ref_node), node(x) per distinct key,
-    // the same per index entry where it was asked for; per call the hit keys per record with the flag words and the two queues
-    // behind them, the records' eight words, and the counter rows of the workgroup form where they do not fit the LDS
-    spsp::DevBuf tx_tree, tx_key_node, tx_entry_node, tx_queue, tx_rec, tx_rows;
-    hipEvent_t tx_events[5] = {};        // while timing is on: in front of the probe, the route, the wave form, the workgroup form, and behind it
-    double tx_ms[4] = {};                // ... their milliseconds added up since spsp_taxonomy_stage_ms last read them
+    // the same per index entry where it was asked for.  Its calls work in the classification's per-call arrays above
+    spsp::DevBuf tx_tree, tx_key_node, tx_entry_node;
+    spsp::RecordClock cf_clock, tx_clock;   // spsp_classify_stage_ms, spsp_taxonomy_stage_ms
 };
 
 namespace spsp {
@@ -574,16 +581,44 @@ constexpr uint32_t kTxLdsNodes = (kAcLdsBytes - 8192) / 4; // 38 912: up to this
 constexpr uint32_t kTxListCut = kCfListCut;                // the key nodes: a list of more holders than this is folded by the whole wave
 constexpr uint32_t kTxMaxNodes = 1048576, kTxMaxDepth = 32;
 constexpr size_t kTxRowsBytes = (size_t)256 << 20;         // the workgroup form's rows in device memory, all of them: the grid is sized to fit
+// What the two record calls share on the host (spsp_classify.hip; DESIGN "What the record passes share").
+// refuse_no_index: the text of a call that finds no index in the context, under the pass's name.  record_keys_check: the key arrays
+// of n_keys record keys against the index -- a NULL array, kmer_hi against the index's k -- which the depth pass's add has as well.
+// record_call_front: what spsp_classify_device and spsp_taxonomy_device refuse behind their own threshold checks, in this order:
+// the record count, decreasing offsets, the key count, no index, (needs_taxonomy) no taxonomy, and the two of record_keys_check;
+// *all_keys: the keys of all records.  Every pass clears its outputs in front of it
+int refuse_no_index(const char* pass);
+int record_keys_check(const spsp_ctx* ctx, const char* pass, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, uint64_t n_keys);
+int record_call_front(const spsp_ctx* ctx, const char* pass, bool needs_taxonomy, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi,
+                      const uint64_t* h_rec_off, uint32_t n_rec, uint64_t* all_keys);
+// one record call's device arrays, in the context's cf_ buffers: the record offsets, kn per record key, work and hit keys per record,
+// the kRqWords words with the two queues behind them, and a row of row_bytes per record (16: classify, 32: taxonomy); g_route, g_small:
+// the grids of the route kernel and of a wave form of kRecordWaves waves per workgroup.  reserve, then upload (the offsets) and
+// clear (work, hit keys, words, rows) on the stream; read_back: the copies of the flag word and of the rows as 32-bit words, queued
+// behind the last launch; wait: the call's one wait and the clock's spans; *fitted: no record overflowed the form it was routed to
+constexpr uint32_t kRecordWaves = 4;
+struct RecordWork {
+    uint64_t* off; uint32_t* kn; unsigned long long* work; uint32_t *hit, *words, *q_small, *q_large; uint4* rec;
+    uint32_t n_rec, g_route, g_small; uint64_t all_keys; size_t row_bytes;
+    int reserve(spsp_ctx* ctx, uint32_t n_rec, uint64_t all_keys, size_t row_bytes);
+    int upload(spsp_ctx* ctx, const uint64_t* h_rec_off);
+    int clear(spsp_ctx* ctx);
+    int read_back(spsp_ctx* ctx, std::vector<uint32_t>* rows);
+    int wait(spsp_ctx* ctx, RecordClock& clock, bool* fitted);
+};
 // classify's probe pass, launched for another caller (spsp_classify.hip): kn[i] = the key number + 1 of record key i (0: nobody
 // holds it), work[r] and hit[r] added up per record.  d_off: the record offsets on the device.  The caller has cleared work and hit
 int classify_probe_launch(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* d_off, uint32_t n_rec,
                           uint64_t all_keys, uint32_t* d_kn, unsigned long long* d_work, uint32_t* d_hit);
-// the road spsp_classify_files and spsp_taxonomy_files share (spsp_classify.hip): run.load(rate) with classify's refusals, the
-// decoding and the index, on_index behind it, then the records file read and sent through records_text_batches on a second
-// context; *t1 = run.end().  names: the records' names
+// the road of the four record file drivers (spsp_classify.hip): run.load(rate), the k == m refusal in the pass's words (what_is:
+// "classification is", "depth is"), one record rate, the decoding and the index, on_index behind it, then every records file read
+// and sent through records_text_batches on ONE second context (spsp_wait_stream(side, ctx) in front of every file: the last
+// file's keys have been read), on_close where all of that went well, the wait for ctx's stream and the second context's end;
+// *t1 = run.end().  names: null, or the records' names (one records file then)
 struct FilesRun;
-int records_files_road(FilesRun& run, const char* records_path, double rate, const std::function<int()>& on_index, std::vector<std::string>* names,
-                       const std::function<int(uint32_t, const uint64_t*)>& on_records, const std::function<int(const RecordBatch&)>& on_batch, double* t1);
+int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
+                       const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
+                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1);
 int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den);
 int taxonomy_index_impl(spsp_ctx* ctx, const uint32_t* parent, uint32_t T, const uint32_t* ref_node, uint32_t n_ref, const uint32_t** key_nodes_out);
 int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,

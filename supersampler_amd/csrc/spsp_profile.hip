@@ -82,8 +82,7 @@ __global__ __launch_bounds__(kPfThreads) void k_pf_start(const uint64_t* __restr
         const uint32_t j = sorted_sketch_of(off, j0, j1 + 1u, first + i0 + q * kPfThreads + threadIdx.x);
         if (few) atomicAdd(&s_n[j - j0], 1u); else atomicAdd(&u[j], 1u);
     }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) { n += __shfl_xor(n, d); v += __shfl_xor(v, d); }
+    n = wave_sum(n); v = wave_sum(v);
     if ((threadIdx.x & 63u) == 0u) {
         if (n) atomicAdd(&u[j0], n);
         if (v) atomicAdd(&state->found_sum, v);
@@ -175,7 +174,7 @@ __global__ __launch_bounds__(kPfThreads) void k_pf_walk(const uint64_t* __restri
         if (take && len <= kPfListCut)
             for (uint32_t h = 0; h < len; ++h) take_off(list[ls + h]);
         unsigned long long left = __ballot(take && len > kPfListCut);
-        while (left) {                                     // the long lists, one after another by the whole wave
+        while (left) {                                     // the long lists, one after another by the whole wave (wave_long_lists moved its registers: DESIGN 6v)
             const int l = __ffsll((long long)left) - 1;
             const uint32_t s0 = __shfl(ls, l), n0 = __shfl(len, l);
             for (uint32_t h = lane; h < n0; h += 512u) {   // eight loads in flight in front of their eight adds

@@ -17,20 +17,21 @@
 //   k_tx_entry_nodes  only where the caller asks for node(x) per index entry: the probe of depth's numbering pass.
 // per batch (spsp_taxonomy_device), one chain of launches whatever the records are, one host wait at its end:
 //   k_cf_probe      classify's, unchanged: kn[e] = the key's number + 1, hit[r] = the record's hit keys (its work is not read)
-//   k_tx_route      a lane per record: no hit -> its row is written here; hits <= kTxSmallHits -> the wave form's queue; else the
-//                   workgroup form's.
-//   k_tx_small      a wave per record: node(x) of its hit keys gathered into the wave's 4 KiB of LDS and sorted by the bitonic steps
-//                   of k_cf_small.  The sorted words ARE the prefix sums: the keys in a range of nodes are the difference of two
+//   k_rec_route     (spsp_device.h) a lane per record: no hit -> its row is written there (TxEmptyRow); hits <= kTxSmallHits -> the
+//                   wave form's queue; else the workgroup form's.
+//   k_tx_small      a wave per record: node(x) of its hit keys gathered into the wave's 4 KiB of LDS and sorted there
+//                   (wave_sort_lds).  The sorted words ARE the prefix sums: the keys in a range of nodes are the difference of two
 //                   lower bounds, so w(t), clade(t) = the range [t, t + size[t]) and every term of path(t) are two binary searches
 //                   each, and no (node, w) pairs are made.  A lane per run of equal nodes climbs its path; best, min W, max W and
 //                   |W| are wave reductions; the confidence climb is at most 33 uniform steps.
 //                   Bound: LDS traffic of the sort, (log2 P)^2 / 2 steps over P <= 1 024 words.
 //   k_tx_large      a workgroup per record with one 32-bit counter per node: in LDS while 4 T bytes fit beside the fixed words
-//                   (T <= kTxLdsNodes), in a row of device memory per workgroup beyond (added to, cleared and read at L2, as
-//                   k_cf_large's rows).  One atomic add per hit key; then a lane per node with w > 0 climbs its path over the
+//                   (T <= kTxLdsNodes), in a row of device memory per workgroup beyond (added to, cleared and read at L2, past
+//                   the CU's L1).  One atomic add per hit key; then a lane per node with w > 0 climbs its path over the
 //                   counters, and the clades on the way up are range sums that grow from the range below (every counter is read
 //                   once at the most).  Bound: hit keys atomic adds + 2 x 4 T bytes of counters per record.
-// No workgroup ever waits for another one.
+// No workgroup ever waits for another one.  The wave helpers, the route kernel, the call's front and its device arrays are the
+// record passes' common ones: spsp_device.h, spsp_internal.h, DESIGN "What the record passes share".
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -42,45 +43,18 @@ namespace spsp {
 
 namespace {
 
-enum { kTxqSmall = 0, kTxqLarge = 1, kTxqBad = 2, kTxqWords = 4 };   // words in front of the queues: their fill, the flag word, one spare
 constexpr uint32_t kTxWaves = kTxThreads / 64, kTxLargeWaves = kTxLargeThreads / 64;
 constexpr uint32_t kTxNone = SPSP_TAXONOMY_NONE;
 static_assert(kTxSmallHits * 4 * kTxWaves <= 64 * 1024 && (kTxSmallHits & (kTxSmallHits - 1)) == 0, "the wave form's LDS: a power of two of words per wave");
 static_assert((size_t)kTxLdsNodes * 4 + kTxLargeFixedLds <= kAcLdsBytes, "the workgroup form's counters beside its fixed words");
 static_assert(kTxLargeFixedLds >= (kTxLargeWaves * 5 + kTxLargeWaves) * 4, "the reductions' words");
-
-// the wave's LDS words: what its lanes stored in front of this line is what they read behind it (cf_wave_sync of spsp_classify.hip)
-__device__ __forceinline__ void tx_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool tx_passes(uint32_t clade, uint32_t keys, uint32_t min_keys, uint32_t num, uint32_t den) {
-    return clade >= min_keys && (unsigned long long)clade * den >= (unsigned long long)num * keys;
-}
+static_assert(kTxThreads == kRouteThreads && kTxWaves == kRecordWaves, "the record calls' route and wave-form grids");
 
 // the deepest node that is anc of both lo and hi (lo <= hi < T): the first ancestor of lo whose subtree reaches hi
 __device__ __forceinline__ uint32_t tx_lca(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ size, uint32_t lo, uint32_t hi) {
     uint32_t a = lo;
     for (uint32_t step = 0; step <= kTxMaxDepth && a != 0u && hi - a >= size[a]; ++step) a = parent[a];   // (the root holds every node)
     return a;
-}
-
-__device__ __forceinline__ uint32_t tx_wave_min(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(v, d); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t tx_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(v, d); v = o > v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t tx_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // what a lane knows of W so far: the best path it met, and of the nodes with that path the smallest, the largest and their number
@@ -90,14 +64,14 @@ __device__ __forceinline__ void tx_meet(TxBest& b, uint32_t path, uint32_t t) {
     else if (path == b.best) { b.lo = t < b.lo ? t : b.lo; b.hi = t > b.hi ? t : b.hi; ++b.count; }
 }
 // ... and the wave's: every lane gets it
-__device__ __forceinline__ TxBest tx_wave_best(TxBest b) {
-    const uint32_t best = tx_wave_max(b.best);
+__device__ __forceinline__ TxBest tx_best_of_wave(TxBest b) {
+    const uint32_t best = wave_max(b.best);
     const bool mine = b.best == best && b.count != 0u;
     TxBest o;
     o.best = best;
-    o.lo = tx_wave_min(mine ? b.lo : kTxNone);
-    o.hi = tx_wave_max(mine ? b.hi : 0u);
-    o.count = tx_wave_sum(mine ? b.count : 0u);
+    o.lo = wave_min(mine ? b.lo : kTxNone);
+    o.hi = wave_max(mine ? b.hi : 0u);
+    o.count = wave_sum(mine ? b.count : 0u);
     return o;
 }
 
@@ -117,19 +91,15 @@ __global__ __launch_bounds__(kTxThreads) void k_tx_key_nodes(const uint32_t* __r
             const uint32_t sk = list[ls + j];
             if (sk < R) { const uint32_t t = ref_node[sk]; lo = t < lo ? t : lo; hi = t > hi ? t : hi; }
         }
-    unsigned long long left = __ballot(len > kTxListCut);
-    while (left) {                                         // the long lists, one after another by the whole wave
-        const int l = __ffsll((long long)left) - 1;
-        const uint32_t s0 = __shfl(ls, l), n0 = __shfl(len, l);
+    wave_long_lists(len > kTxListCut, ls, len, [=, &lo, &hi](int l, uint32_t s0, uint32_t n0) {
         uint32_t a = kTxNone, b = 0u;
         for (uint32_t j = lane; j < n0; j += 64u) {
             const uint32_t sk = list[s0 + j];
             if (sk < R) { const uint32_t t = ref_node[sk]; a = t < a ? t : a; b = t > b ? t : b; }
         }
-        a = tx_wave_min(a); b = tx_wave_max(b);
+        a = wave_min(a); b = wave_max(b);
         if ((int)lane == l) { lo = a; hi = b; }
-        left &= left - 1ull;
-    }
+    });
     if (!valid) return;
     key_node[x] = lo < T && hi < T ? tx_lca(parent, size, lo, hi) : 0u;   // (a key always has a holder, and ref_node < T was checked)
 }
@@ -159,23 +129,10 @@ __device__ __forceinline__ void tx_write(uint4* __restrict__ rec, uint32_t r, ui
     rec[2ull * r + 1ull] = make_uint4(score, clade, direct, winners);
 }
 
-__global__ __launch_bounds__(kTxThreads) void k_tx_route(const uint64_t* __restrict__ off, uint32_t n_rec, const uint32_t* __restrict__ hit,
-                                                         uint32_t* __restrict__ words, uint32_t* __restrict__ q_small, uint32_t* __restrict__ q_large,
-                                                         uint4* __restrict__ rec) {
-    const uint64_t r = (uint64_t)blockIdx.x * kTxThreads + threadIdx.x;
-    if (r >= n_rec) return;
-    const uint32_t h = hit[r];
-    if (h == 0u) tx_write(rec, (uint32_t)r, (uint32_t)(off[r + 1] - off[r]), 0u, kTxNone, kTxNone, 0u, 0u, 0u, 0u);
-    else if (h <= kTxSmallHits) q_small[atomicAdd(words + kTxqSmall, 1u)] = (uint32_t)r;   // (a queue has room for every record)
-    else q_large[atomicAdd(words + kTxqLarge, 1u)] = (uint32_t)r;
-}
-
-// the first place of the sorted words s[0 .. n) that holds v or more
-__device__ __forceinline__ uint32_t tx_lower(const uint32_t* s, uint32_t n, uint32_t v) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (s[mid] < v) lo = mid + 1u; else hi = mid; }
-    return lo;
-}
+// the row of a record without a hit key, which the route kernel writes
+struct TxEmptyRow {
+    __device__ void operator()(uint4* __restrict__ rec, uint32_t r, uint32_t keys) const { tx_write(rec, r, keys, 0u, kTxNone, kTxNone, 0u, 0u, 0u, 0u); }
+};
 
 // a wave per queued record; kn, and the entries of off, count from the first record key
 __global__ __launch_bounds__(kTxThreads) void k_tx_small(const uint64_t* __restrict__ off, const uint32_t* __restrict__ kn_of, const uint32_t* __restrict__ key_node,
@@ -185,7 +142,7 @@ __global__ __launch_bounds__(kTxThreads) void k_tx_small(const uint64_t* __restr
     __shared__ uint32_t s_all[kTxWaves][kTxSmallHits];
     const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
     uint32_t* s = s_all[wid];
-    const uint32_t n_small = words[kTxqSmall];
+    const uint32_t n_small = words[kRqSmall];
     const uint64_t q0 = off[0];
     for (uint64_t q = (uint64_t)blockIdx.x * kTxWaves + wid; q < n_small; q += (uint64_t)gridDim.x * kTxWaves) {   // (uniform per wave)
         const uint32_t r = q_small[q];
@@ -205,20 +162,11 @@ __global__ __launch_bounds__(kTxThreads) void k_tx_small(const uint64_t* __restr
             if (has) s[H + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = node;
             H += n;
         }
-        if (!fits || H == 0u) { if (lane == 0u) atomicOr(words + kTxqBad, 1u); continue; }
+        if (!fits || H == 0u) { if (lane == 0u) atomicOr(words + kRqBad, 1u); continue; }
         uint32_t P = 64;
         while (P < H) P <<= 1;
         for (uint32_t i = H + lane; i < P; i += 64u) s[i] = kTxNone;
-        tx_wave_sync();
-        for (uint32_t k = 2; k <= P; k <<= 1)
-            for (uint32_t j = k >> 1; j; j >>= 1) {
-                for (uint32_t t = lane; t < P / 2u; t += 64u) {
-                    const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i + j;
-                    const uint32_t x = s[i], y = s[l];
-                    if ((x > y) == ((i & k) == 0u)) { s[i] = y; s[l] = x; }
-                }
-                tx_wave_sync();
-            }
+        wave_sort_lds(s, P, lane);
         // every run of one node t has w(t) > 0: the lane at its last place climbs path(t)
         TxBest mine{0u, kTxNone, 0u, 0u};
         for (uint32_t base = 0; base < H; base += 64u) {
@@ -226,33 +174,33 @@ __global__ __launch_bounds__(kTxThreads) void k_tx_small(const uint64_t* __restr
             if (i < H) {
                 const uint32_t t = s[i];
                 if (i + 1u == H || s[i + 1u] != t) {
-                    uint32_t path = i + 1u - tx_lower(s, i, t), at = t;
+                    uint32_t path = i + 1u - lds_lower_bound(s, i, t), at = t;
                     for (uint32_t step = 0; step < kTxMaxDepth && at != 0u; ++step) {
                         at = parent[at];
-                        const uint32_t lo = tx_lower(s, H, at);
-                        path += tx_lower(s, H, at + 1u) - lo;
+                        const uint32_t lo = lds_lower_bound(s, H, at);
+                        path += lds_lower_bound(s, H, at + 1u) - lo;
                     }
                     tx_meet(mine, path, t);
                 }
             }
         }
-        const TxBest W = tx_wave_best(mine);
+        const TxBest W = tx_best_of_wave(mine);
         const uint32_t start = tx_lca(parent, size, W.lo, W.hi);
         uint32_t node = kTxNone, clade = 0u, direct = 0u, t = start;
         for (uint32_t step = 0; step <= kTxMaxDepth; ++step) {   // (uniform: every lane walks the same way up)
-            const uint32_t lo = tx_lower(s, H, t), c = tx_lower(s, H, t + size[t]) - lo;
-            if (tx_passes(c, keys, min_keys, num, den)) { node = t; clade = c; direct = tx_lower(s, H, t + 1u) - lo; break; }
+            const uint32_t lo = lds_lower_bound(s, H, t), c = lds_lower_bound(s, H, t + size[t]) - lo;
+            if (passes_threshold(c, keys, min_keys, num, den)) { node = t; clade = c; direct = lds_lower_bound(s, H, t + 1u) - lo; break; }
             if (t == 0u) break;
             t = parent[t];
         }
-        tx_wave_sync();                                    // (the words are read: the next record may overwrite them)
+        wave_lds_sync();                                    // (the words are read: the next record may overwrite them)
         if (lane == 0u) tx_write(rec, r, keys, H, node, start, W.best, clade, direct, W.count);
     }
 }
 
 // sums over the workgroup: every lane gets the total.  s8: kTxLargeWaves words nobody else uses between the two barriers inside
 __device__ __forceinline__ uint32_t tx_block_sum(uint32_t v, uint32_t* s8, uint32_t lane, uint32_t wid) {
-    v = tx_wave_sum(v);
+    v = wave_sum(v);
     if (lane == 0u) s8[wid] = v;
     __syncthreads();
     uint32_t total = 0;
@@ -275,7 +223,7 @@ __global__ __launch_bounds__(kTxLargeThreads) void k_tx_large(const uint64_t* __
     uint32_t* s_w = s_mem + (IN_LDS ? T_pad : 0u);         // wave w: best, lo, hi, count, hits at s_w[5 w ..]
     uint32_t* s8 = s_w + kTxLargeWaves * 5u;
     const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    const uint32_t n_large = words[kTxqLarge];
+    const uint32_t n_large = words[kRqLarge];
     const uint64_t q0 = off[0];
     // (the rows in device memory are added to at L2: they are cleared and read there as well, past this CU's L1)
     auto get = [&](uint32_t j) -> uint32_t { return IN_LDS ? cnt[j] : __hip_atomic_load(cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
@@ -304,8 +252,8 @@ __global__ __launch_bounds__(kTxLargeThreads) void k_tx_large(const uint64_t* __
             for (uint32_t step = 0; step < kTxMaxDepth && at != 0u; ++step) { at = parent[at]; path += get(at); }
             tx_meet(mine, path, t);
         }
-        const TxBest mw = tx_wave_best(mine);
-        hits = tx_wave_sum(hits);
+        const TxBest mw = tx_best_of_wave(mine);
+        hits = wave_sum(hits);
         if (lane == 0u) { uint32_t* o = s_w + wid * 5u; o[0] = mw.best; o[1] = mw.lo; o[2] = mw.hi; o[3] = mw.count; o[4] = hits; }
         __syncthreads();
         TxBest W{0u, kTxNone, 0u, 0u};
@@ -329,7 +277,7 @@ __global__ __launch_bounds__(kTxLargeThreads) void k_tx_large(const uint64_t* __
                 for (uint32_t j = hi + threadIdx.x; j < n_hi; j += kTxLargeThreads) part += get(j);
                 c += tx_block_sum(part, s8, lane, wid);
                 lo = n_lo; hi = n_hi;
-                if (tx_passes(c, keys, min_keys, num, den)) { node = t; clade = c; direct = get(t); break; }
+                if (passes_threshold(c, keys, min_keys, num, den)) { node = t; clade = c; direct = get(t); break; }
                 if (t == 0u) break;
                 t = parent[t];
             }
@@ -339,16 +287,13 @@ __global__ __launch_bounds__(kTxLargeThreads) void k_tx_large(const uint64_t* __
     }
 }
 
-const char* const kNoIndex = "taxonomy: the context holds no index (spsp_classify_index_device first; a prevalence, select, accumulation or groups call replaces it)";
-const char* const kNoTaxonomy = "taxonomy: the index holds no taxonomy (spsp_taxonomy_index_device first; it ends with the index it was attached to)";
-
 }  // namespace
 
 int taxonomy_index_impl(spsp_ctx* ctx, const uint32_t* parent, uint32_t T, const uint32_t* ref_node, uint32_t n_ref, const uint32_t** key_nodes_out) {
     int rc;
     if (key_nodes_out) *key_nodes_out = nullptr;
     spsp_ctx::ClassifyIndex& X = ctx->cf_index;
-    if (!X.valid) { set_error("%s", kNoIndex); return SPSP_ERR_ARG; }
+    if (!X.valid) return refuse_no_index("taxonomy");
     if (n_ref != X.n_ref) { set_error("taxonomy: %u references, the index holds %u", n_ref, X.n_ref); return SPSP_ERR_ARG; }
     if ((rc = spsp_taxonomy_check_host(parent, T, ref_node, n_ref))) return rc;
     X.taxonomy = false;
@@ -389,21 +334,9 @@ int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
     int rc;
     // (what is zeroed in front of the refusals: everything but the caller's lengths)
     for (uint32_t r = 0; r < n_rec; ++r) { const uint64_t length = records[r].length; records[r] = spsp_taxonomy_record{}; records[r].length = length; }
-    if ((rc = taxonomy_check_args(min_keys, num, den))) return rc;
-    if (n_rec > 0xfffffff0u) { set_error("too many records for one call (%u)", n_rec); return SPSP_ERR_OVERFLOW; }
-    for (uint32_t r = 0; r < n_rec; ++r)
-        if (h_rec_off[r + 1] < h_rec_off[r]) { set_error("record offsets must not decrease (record %u)", r); return SPSP_ERR_ARG; }
-    if (h_rec_off[n_rec] > 0xfffffff0ull) { set_error("too many record keys for one call"); return SPSP_ERR_OVERFLOW; }
+    uint64_t all_keys = 0;
+    if ((rc = taxonomy_check_args(min_keys, num, den)) || (rc = record_call_front(ctx, "taxonomy", true, q_mn, q_lo, q_hi, h_rec_off, n_rec, &all_keys))) return rc;
     const spsp_ctx::ClassifyIndex& X = ctx->cf_index;
-    if (!X.valid) { set_error("%s", kNoIndex); return SPSP_ERR_ARG; }
-    if (!X.taxonomy) { set_error("%s", kNoTaxonomy); return SPSP_ERR_ARG; }
-    const uint64_t q0 = h_rec_off[0], all_keys = h_rec_off[n_rec] - q0;
-    if (all_keys && (!q_mn || !q_lo)) { set_error("NULL key array"); return SPSP_ERR_ARG; }
-    if (all_keys && (q_hi != nullptr) != X.has_hi) {
-        set_error("taxonomy: the index was built %s kmer_hi (k %s 32), the records come %s it", X.has_hi ? "with" : "without", X.has_hi ? ">" : "<=",
-                  q_hi ? "with" : "without");
-        return SPSP_ERR_ARG;
-    }
     for (uint32_t r = 0; r < n_rec; ++r) {                 // (length is the caller's)
         records[r].keys = (uint32_t)(h_rec_off[r + 1] - h_rec_off[r]);
         records[r].node = records[r].start = kTxNone;
@@ -418,59 +351,35 @@ int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
     // (the rows in device memory: as many workgroups as rows fit kTxRowsBytes, one per CU at the most)
     const uint64_t rows_fit = std::max<uint64_t>(1, kTxRowsBytes / ((size_t)T_pad * 4));
     const uint32_t g_large = (uint32_t)std::min<uint64_t>(n_rec, in_lds ? (uint64_t)n_cu * large_per_cu : std::min<uint64_t>((uint64_t)n_cu, rows_fit));
-    const uint32_t g_small = (uint32_t)std::min<uint64_t>(((uint64_t)n_rec + kTxWaves - 1) / kTxWaves, (uint64_t)n_cu * 8u);
-    const size_t work_bytes = (size_t)n_rec * 8, queue_bytes = 64 + (size_t)2 * n_rec * 4;
-    if ((rc = ctx->cf_off.reserve(((size_t)n_rec + 1) * 8)) || (rc = ctx->cf_kn.reserve((size_t)all_keys * 4)) ||
-        (rc = ctx->cf_work.reserve(work_bytes + (size_t)n_rec * 4)) || (rc = ctx->tx_queue.reserve(queue_bytes)) ||
-        (rc = ctx->tx_rec.reserve((size_t)n_rec * 32)) || (!in_lds && (rc = ctx->tx_rows.reserve((size_t)g_large * T_pad * 4)))) return rc;
-    uint64_t* d_off = ctx->cf_off.as<uint64_t>();
-    uint32_t* d_kn = ctx->cf_kn.as<uint32_t>();
-    unsigned long long* d_work = ctx->cf_work.as<unsigned long long>();
-    uint32_t* d_hit = reinterpret_cast<uint32_t*>(ctx->cf_work.as<uint8_t>() + work_bytes);
-    uint32_t* d_words = ctx->tx_queue.as<uint32_t>();
-    uint32_t* d_q_small = d_words + 16;
-    uint32_t* d_q_large = d_q_small + n_rec;
-    uint4* d_rec = ctx->tx_rec.as<uint4>();
-    uint32_t* d_rows = in_lds ? nullptr : ctx->tx_rows.as<uint32_t>();
+    RecordWork W;
+    if ((rc = W.reserve(ctx, n_rec, all_keys, 32)) || (!in_lds && (rc = ctx->cf_rows.reserve((size_t)g_large * T_pad * 4)))) return rc;
+    uint32_t* d_rows = in_lds ? nullptr : ctx->cf_rows.as<uint32_t>();
     const uint32_t* d_parent = ctx->tx_tree.as<uint32_t>();
     const uint32_t* d_size = d_parent + T_pad;
     const uint32_t* d_key_node = ctx->tx_key_node.as<uint32_t>();
-    SPSP_HIP(hipMemcpyAsync(d_off, h_rec_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));   // (the caller's: alive until the wait)
-    SPSP_HIP(hipMemsetAsync(d_work, 0, work_bytes + (size_t)n_rec * 4, ctx->stream));
-    SPSP_HIP(hipMemsetAsync(d_words, 0, kTxqWords * 4, ctx->stream));
-    SPSP_HIP(hipMemsetAsync(d_rec, 0, (size_t)n_rec * 32, ctx->stream));
-    const uint32_t gr = (uint32_t)(((uint64_t)n_rec + kTxThreads - 1) / kTxThreads);
-    hipEvent_t* ev = nullptr;
-    if (ctx->timing) {                                     // spsp_timing_enable: events between the launches (spsp_taxonomy_stage_ms)
-        for (hipEvent_t& e : ctx->tx_events) if (!e) SPSP_HIP(hipEventCreate(&e));
-        ev = ctx->tx_events;
-        SPSP_HIP(hipEventRecord(ev[0], ctx->stream));
-    }
-    if ((rc = classify_probe_launch(ctx, q_mn, q_lo, q_hi, d_off, n_rec, all_keys, d_kn, d_work, d_hit))) return rc;
-    if (ev) SPSP_HIP(hipEventRecord(ev[1], ctx->stream));
-    hipLaunchKernelGGL(k_tx_route, dim3(gr), dim3(kTxThreads), 0, ctx->stream, (const uint64_t*)d_off, n_rec, (const uint32_t*)d_hit, d_words, d_q_small, d_q_large,
-                       d_rec);
-    if (ev) SPSP_HIP(hipEventRecord(ev[2], ctx->stream));
-    hipLaunchKernelGGL(k_tx_small, dim3(g_small), dim3(kTxThreads), 0, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn, d_key_node, d_parent, d_size, T,
-                       (const uint32_t*)d_q_small, d_words, min_keys, num, den, d_rec);
-    if (ev) SPSP_HIP(hipEventRecord(ev[3], ctx->stream));
+    RecordClock& clock = ctx->tx_clock;
+    if ((rc = W.upload(ctx, h_rec_off)) || (rc = W.clear(ctx)) || (rc = clock.mark(ctx, 0)) ||
+        (rc = classify_probe_launch(ctx, q_mn, q_lo, q_hi, W.off, n_rec, all_keys, W.kn, W.work, W.hit)) || (rc = clock.mark(ctx, 1))) return rc;
+    hipLaunchKernelGGL((k_rec_route<uint32_t, TxEmptyRow>), dim3(W.g_route), dim3(kRouteThreads), 0, ctx->stream, (const uint64_t*)W.off, n_rec, (const uint32_t*)W.hit,
+                       kTxSmallHits, W.words, W.q_small, W.q_large, W.rec, TxEmptyRow{});
+    if ((rc = clock.mark(ctx, 2))) return rc;
+    hipLaunchKernelGGL(k_tx_small, dim3(W.g_small), dim3(kTxThreads), 0, ctx->stream, (const uint64_t*)W.off, (const uint32_t*)W.kn, d_key_node, d_parent, d_size, T,
+                       (const uint32_t*)W.q_small, W.words, min_keys, num, den, W.rec);
+    if ((rc = clock.mark(ctx, 3))) return rc;
     if (in_lds) {
         if ((rc = lds_opt_in(ctx, &k_tx_large<true>, kAcLdsBytes))) return rc;
-        hipLaunchKernelGGL(k_tx_large<true>, dim3(g_large), dim3(kTxLargeThreads), lds, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn, d_key_node,
-                           d_parent, d_size, T, T_pad, (const uint32_t*)d_q_large, (const uint32_t*)d_words, d_rows, min_keys, num, den, d_rec);
+        hipLaunchKernelGGL(k_tx_large<true>, dim3(g_large), dim3(kTxLargeThreads), lds, ctx->stream, (const uint64_t*)W.off, (const uint32_t*)W.kn, d_key_node,
+                           d_parent, d_size, T, T_pad, (const uint32_t*)W.q_large, (const uint32_t*)W.words, d_rows, min_keys, num, den, W.rec);
     } else {
-        hipLaunchKernelGGL(k_tx_large<false>, dim3(g_large), dim3(kTxLargeThreads), lds, ctx->stream, (const uint64_t*)d_off, (const uint32_t*)d_kn, d_key_node,
-                           d_parent, d_size, T, T_pad, (const uint32_t*)d_q_large, (const uint32_t*)d_words, d_rows, min_keys, num, den, d_rec);
+        hipLaunchKernelGGL(k_tx_large<false>, dim3(g_large), dim3(kTxLargeThreads), lds, ctx->stream, (const uint64_t*)W.off, (const uint32_t*)W.kn, d_key_node,
+                           d_parent, d_size, T, T_pad, (const uint32_t*)W.q_large, (const uint32_t*)W.words, d_rows, min_keys, num, den, W.rec);
     }
     SPSP_HIP(hipGetLastError());
-    if (ev) SPSP_HIP(hipEventRecord(ev[4], ctx->stream));
-    std::vector<uint32_t> got((size_t)n_rec * 8);
-    SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsCfBad, d_words + kTxqBad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    SPSP_HIP(hipMemcpyAsync(got.data(), d_rec, got.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SPSP_HIP(hipStreamSynchronize(ctx->stream));           // the one wait
-    if (ev)
-        for (int i = 0; i < 4; ++i) { float ms = 0; SPSP_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); ctx->tx_ms[i] += ms; }
-    if ((uint32_t)ctx->h_scalar[kHsCfBad]) {
+    if ((rc = clock.mark(ctx, 4))) return rc;
+    std::vector<uint32_t> got;
+    bool fitted = false;
+    if ((rc = W.read_back(ctx, &got)) || (rc = W.wait(ctx, clock, &fitted))) return rc;
+    if (!fitted) {
         set_error("taxonomy: a record's hit keys did not fit the form it was routed to (the key arrays changed during the call?)");
         for (uint32_t r = 0; r < n_rec; ++r) { const uint64_t length = records[r].length; records[r] = spsp_taxonomy_record{}; records[r].length = length; }
         return SPSP_ERR_ARG;
@@ -502,14 +411,14 @@ static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
     std::vector<std::string> names;
     double t1 = 0;
     rc = records_files_road(
-        run, records_path, rate, [&] { return taxonomy_index_impl(ctx, parent, T, ref_node.data(), n_ref, nullptr); }, &names,
+        run, "classification is", &records_path, 1, rate, [&] { return taxonomy_index_impl(ctx, parent, T, ref_node.data(), n_ref, nullptr); }, &names,
         [&](uint32_t n_rec, const uint64_t* rec_off) {
             recs->assign(n_rec, spsp_taxonomy_record{});
             for (uint32_t r = 0; r < n_rec; ++r) (*recs)[r].length = rec_off[r + 1] - rec_off[r];
             return SPSP_OK;
         },
         [&](const RecordBatch& B) { return taxonomy_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, min_keys, num, den, recs->data() + B.first_record); },
-        &t1);
+        [] { return SPSP_OK; }, &t1);
     char *text = nullptr, *report = nullptr; uint64_t len = 0, report_len = 0;
     if (!rc) {
         std::vector<const char*> name_ptr(names.size());
@@ -579,6 +488,6 @@ extern "C" int spsp_taxonomy_files(spsp_ctx* ctx, const char* const* index_paths
 
 extern "C" int spsp_taxonomy_stage_ms(spsp_ctx* ctx, double* ms) {
     if (!ctx || !ms) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    for (int i = 0; i < 4; ++i) { ms[i] = ctx->tx_ms[i]; ctx->tx_ms[i] = 0; }
+    ctx->tx_clock.hand_out(ms);
     return SPSP_OK;
 }
