@@ -1391,6 +1391,88 @@ int spsp_taxonomy_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t 
                         uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
                         spsp_taxonomy_record** records /* may be NULL; spsp_free */, uint64_t* n_records /* may be NULL */);
 
+/* ------------------------------------------------------------- extract ---- */
+/* The records a record pass calls, written out again as FASTA / FASTQ (not in the reference): what follows a classify or taxonomy
+ * call -- host depletion, the reads of one species or clade, the contigs a contaminant index claims.
+ * TEXT T of n bytes.  It is FASTQ when n > 0 and T[0] == '@', else FASTA: how every sketch path tells them apart.
+ * FASTA RECORDS.  A line begins at byte 0 and behind every '\n'.  Line 0, and every line whose first byte is '>' or 0xFF, begins a
+ * record (the ingest's rule for a dropped line, to the letter: line 0 is a header whatever it holds).  With b_0 < b_1 < ... the
+ * bytes that begin a record, record r is the byte range [b_r, b_(r+1)) and b_(n_rec) = n.  Every byte of the text lies in exactly
+ * one record: the records concatenated are the text.  n_rec is what spsp_fasta_clean_device reports for the same text; the empty
+ * text is one empty record.
+ * FASTQ RECORDS.  content_end is behind the last byte that is neither '\n' nor '\r'; the blank tail is what follows it.  The lines
+ * of T[0, content_end) are counted and nothing else is checked (the file drivers have ingested, and so validated, the text first):
+ * a line count that is not a multiple of four is SPSP_ERR_FORMAT.  Record r is lines 4r .. 4r+3: from the first byte of line 4r to
+ * one past the '\n' that ends line 4r+3.  For the last record that '\n' is the first one of the blank tail; where the tail has
+ * none the record ends at content_end.  The rest of the blank tail belongs to no record.  A quality line that begins with '@' or
+ * '>' begins nothing.  One content of 4r + 3 lines is a whole record all the same, as the ingest has it: when something follows
+ * the blank tail's first newline, the last record's quality line is the empty line behind that newline, and the record ends behind
+ * the tail's second newline (at n where there is none).  n_rec is what spsp_fastq_clean_device reports.
+ * begin[0 .. n_rec]: record r is [begin[r], begin[r + 1]) in both formats.
+ * OUTPUT.  keep[r] is one byte per record.  The output is the concatenation, in record order, of the byte ranges of the records
+ * with keep[r] != 0, verbatim: '\r' bytes, lower-case bases, wrapped FASTA lines, header comments and quality strings pass through
+ * unchanged.  One exception: a kept range that is not empty and whose last byte is not '\n' gets one '\n' appended; only the last
+ * record of a text can be such a range.  So every output is a well-formed file and outputs can be concatenated.  n_kept = the
+ * records with keep[r] != 0, n_out = the output's bytes.  Extents are 64-bit; the text is bounded by what the ingest accepts.
+ * WHICH RECORDS.  A word `what` and the rows of a pass make the flags, on the host, without floating point.
+ *   classify rows:  matched: listed >= 1.  unmatched: listed == 0.  best=<j>: the rank-1 match is reference <j>.
+ *                   listed=<j>: reference <j> is among the listed matches.  <j> is the 0-based list position.
+ *   taxonomy rows:  classified: node != SPSP_TAXONOMY_NONE.  unclassified: node == SPSP_TAXONOMY_NONE.  taxon=<t>: node == t.
+ *                   clade=<t>: t <= node < t + size[t], the preorder range test.  <t> is the number the taxonomy CSV prints.
+ * Anything else is SPSP_ERR_ARG naming the word; so are <j> >= n_ref, <t> >= n_nodes, a classify word with taxonomy rows and the
+ * reverse.  Numbers are decimal digits only. */
+/* The two constants the kernels cut at (either pointer may be NULL): the bytes of the text one workgroup of the starts pass reads,
+ * and the bytes of the output one workgroup of the copy owns. */
+int spsp_extract_plan_host(uint32_t* tile_bytes, uint32_t* stretch_bytes);
+/* The rule as plain loops on the host.  *begin: n_rec + 1 offsets, released with spsp_free().  SPSP_ERR_FORMAT: a FASTQ content
+ * whose lines are not a multiple of four. */
+int spsp_records_extents_host(const uint8_t* text, uint64_t n_text, uint64_t** begin /* spsp_free */, uint32_t* n_rec);
+/* begin: n_rec + 1 offsets that do not decrease and end inside the text (SPSP_ERR_ARG otherwise) -- the rule's, or any ranges of
+ * the caller's own: then, here and on the device, only the LAST range is looked at for the newline rule.  *out: spsp_free(). */
+int spsp_records_extract_host(const uint8_t* text, uint64_t n_text, const uint64_t* begin, uint32_t n_rec, const uint8_t* keep /* n_rec */,
+                              uint8_t** out /* spsp_free */, uint64_t* n_out, uint64_t* n_kept);
+/* The flags of a word.  hits: n_records * top, as spsp_classify_device fills them; size: the tree's subtree sizes (n_nodes), as
+ * spsp_taxonomy_lineages_host hands them out.  SPSP_ERR_ARG as the rule says, and for a record that lists more than top matches. */
+int spsp_extract_flags_classify_host(const char* what, const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records,
+                                     uint32_t top, uint32_t n_ref, uint8_t* keep /* n_records */);
+int spsp_extract_flags_taxonomy_host(const char* what, const spsp_taxonomy_record* records, uint64_t n_records, const uint32_t* size, uint32_t n_nodes,
+                                     uint8_t* keep /* n_records */);
+/* Only the refusals of a word: taxonomy != 0 asks for a taxonomy word; limit is n_ref or n_nodes (0xffffffff: not known yet). */
+int spsp_extract_word_check_host(const char* what, int taxonomy, uint32_t limit);
+/* The records' starts of a text in HBM (16-byte aligned, as the ingest takes it): *d_begin is a context-owned array of n_rec + 1
+ * uint64, valid until the next extents call or the next extract call that makes its own starts.  Launches: one workgroup that
+ * finds the text's kind, its content end and its last record's end; per 4 KiB tile a count (FASTA: record starts, FASTQ:
+ * newlines); one composing scan; per tile the write.  It reads the text alone, not the ingest's outputs.  One host wait, for n_rec.
+ * SPSP_ERR_FORMAT as above. */
+int spsp_records_extents_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_begin, uint32_t* n_rec);
+/* The kept records of a text in HBM, back to back in a context-owned buffer (*d_out, valid until the next extract call on the
+ * context; spsp_copy_to_host brings it back).  d_begin: the starts on the device, n_rec + 1 of them -- the array of an extents
+ * call may be handed back in -- or NULL: they are made here for n_rec records, without a wait of their own, and a text that holds
+ * another number of records is SPSP_ERR_ARG.  h_keep: n_rec bytes on the host.  Launches: per 2 048 records the kept bytes and
+ * the runs of consecutive kept records, the same scan, the run table (source start, output start); then the copy, balanced by
+ * output bytes: a workgroup owns spsp_extract_plan_host's stretch of the output, finds the runs that cross it by binary search, and
+ * writes aligned 16-byte stores -- from two aligned loads and a byte shift inside a run, byte by byte across runs.  One host wait,
+ * for n_out.  SPSP_ERR_ARG also for starts that decrease or leave the text (nothing is read or written outside the buffers). */
+int spsp_records_extract_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, const void* d_begin /* NULL: made here */, uint32_t n_rec,
+                                const uint8_t* h_keep /* n_rec */, void** d_out, uint64_t* n_out, uint64_t* n_kept);
+/* While the context's timing is on an extract call records events between its launches; this reads the milliseconds added up since
+ * the last read and clears them: ms[0] the starts (0 when they were handed in), ms[1] the offsets and the run table, ms[2] the copy. */
+int spsp_extract_stage_ms(spsp_ctx* ctx, double* ms /* 3: starts, offsets, copy */);
+/* The whole-file drivers with an extraction: the arguments of spsp_classify_files / spsp_taxonomy_files, the same code and the
+ * same CSVs byte for byte, plus the word.  Behind the records file's last batch the flags are made from the rows and the kept
+ * records are extracted on the second context, where the text still sits; only the kept bytes come back.  Writes
+ * <out_prefix>_extract.fa or _extract.fq (by the text's kind), gzip level 1 with ".gz" appended when gz != 0.  A word that is
+ * refused is refused before any file is read (a taxonomy word's node: once the lineage file is).  *n_kept, *bytes_out (may be
+ * NULL): the records kept and the bytes of the output before compression. */
+int spsp_classify_files_extract(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                spsp_classify_record** records /* may be NULL; spsp_free */, spsp_classify_hit** hits /* may be NULL; spsp_free */,
+                                uint64_t* n_records /* may be NULL */, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out);
+int spsp_taxonomy_files_extract(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                spsp_taxonomy_record** records /* may be NULL; spsp_free */, uint64_t* n_records /* may be NULL */, const char* what,
+                                int gz, uint64_t* n_kept, uint64_t* bytes_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,9 @@ ABI_SYMBOLS = [
     "spsp_depth_begin_device", "spsp_depth_add_device", "spsp_depth_read_device", "spsp_depth_plan_host", "spsp_depth_stage_ms", "spsp_depth_csv_host", "spsp_depth_files",
     "spsp_profile_device", "spsp_profile_stage_ms", "spsp_profile_counts", "spsp_profile_csv_host", "spsp_profile_files",
     "spsp_taxonomy_lineages_host", "spsp_taxonomy_check_host", "spsp_taxonomy_plan_host", "spsp_taxonomy_index_device", "spsp_taxonomy_device", "spsp_taxonomy_stage_ms", "spsp_taxonomy_csv_host", "spsp_taxonomy_report_csv_host", "spsp_taxonomy_files",
+    "spsp_extract_plan_host", "spsp_records_extents_host", "spsp_records_extract_host", "spsp_extract_flags_classify_host", "spsp_extract_flags_taxonomy_host",
+    "spsp_extract_word_check_host", "spsp_records_extents_device", "spsp_records_extract_device", "spsp_extract_stage_ms", "spsp_classify_files_extract",
+    "spsp_taxonomy_files_extract",
 ]
 
 _lib = None
@@ -427,6 +430,29 @@ def lib():
         L.spsp_taxonomy_report_csv_host.argtypes = [vp, u64, vp, u32, P(cp), vp, u32, P(vp), P(u64)]
         L.spsp_taxonomy_files.restype = i32
         L.spsp_taxonomy_files.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_records_extract_device"):
+        L.spsp_extract_plan_host.restype = i32
+        L.spsp_extract_plan_host.argtypes = [P(u32), P(u32)]
+        L.spsp_records_extents_host.restype = i32
+        L.spsp_records_extents_host.argtypes = [vp, u64, P(vp), P(u32)]
+        L.spsp_records_extract_host.restype = i32
+        L.spsp_records_extract_host.argtypes = [vp, u64, vp, u32, vp, P(vp), P(u64), P(u64)]
+        L.spsp_extract_flags_classify_host.restype = i32
+        L.spsp_extract_flags_classify_host.argtypes = [cp, vp, vp, u64, u32, u32, vp]
+        L.spsp_extract_flags_taxonomy_host.restype = i32
+        L.spsp_extract_flags_taxonomy_host.argtypes = [cp, vp, u64, vp, u32, vp]
+        L.spsp_extract_word_check_host.restype = i32
+        L.spsp_extract_word_check_host.argtypes = [cp, i32, u32]
+        L.spsp_records_extents_device.restype = i32
+        L.spsp_records_extents_device.argtypes = [vp, vp, u64, P(vp), P(u32)]
+        L.spsp_records_extract_device.restype = i32
+        L.spsp_records_extract_device.argtypes = [vp, vp, u64, vp, u32, vp, P(vp), P(u64), P(u64)]
+        L.spsp_extract_stage_ms.restype = i32
+        L.spsp_extract_stage_ms.argtypes = [vp, P(dbl)]
+        L.spsp_classify_files_extract.restype = i32
+        L.spsp_classify_files_extract.argtypes = [vp, P(cp), u32, cp, u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(vp), P(u64), cp, i32, P(u64), P(u64)]
+        L.spsp_taxonomy_files_extract.restype = i32
+        L.spsp_taxonomy_files_extract.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(u64), cp, i32, P(u64), P(u64)]
     _lib = L
     return L
 
@@ -831,6 +857,65 @@ def taxonomy_plan(n_nodes):
     a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
     _check(lib().spsp_taxonomy_plan_host(n_nodes, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
     return {"small_hits": a.value, "lds_nodes": b.value, "counters_in_lds": bool(c.value), "list_cut": d.value}
+
+
+def extract_plan():
+    """spsp_extract_plan_host: the two constants the extraction's kernels cut at -> dict(tile_bytes: the bytes of the text one
+    workgroup of the starts pass reads, stretch_bytes: the bytes of the output one workgroup of the copy owns)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_extract_plan_host(C.byref(a), C.byref(b)))
+    return {"tile_bytes": a.value, "stretch_bytes": b.value}
+
+
+def records_extents(text):
+    """spsp_records_extents_host: the bytes of a FASTA / FASTQ text (FASTQ: the first byte is '@') -> begin: np.uint64[n_rec + 1];
+    record r is text[begin[r]:begin[r + 1]] (the rule: include/spsp.h, "extract")"""
+    text = np.frombuffer(bytes(text), dtype=np.uint8)
+    out, n = C.c_void_p(), C.c_uint32()
+    _check(lib().spsp_records_extents_host(text.ctypes.data if len(text) else None, len(text), C.byref(out), C.byref(n)))
+    return np.frombuffer(_take(out, (n.value + 1) * 8), dtype=np.uint64).copy()
+
+
+def records_extract(text, keep, begin=None):
+    """spsp_records_extract_host: the records of `text` with keep[r] != 0, back to back, a newline appended to a last record that
+    lacks one -> (bytes, n_kept).  begin: the records' starts (records_extents(text) when None)"""
+    if begin is None:
+        begin = records_extents(text)
+    text = np.frombuffer(bytes(text), dtype=np.uint8)
+    begin = np.ascontiguousarray(begin, dtype=np.uint64)
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    if len(begin) < 1 or len(keep) != len(begin) - 1:
+        raise ValueError("records_extract: one flag per record and n_rec + 1 starts")
+    out, n_out, n_kept = C.c_void_p(), C.c_uint64(), C.c_uint64()
+    _check(lib().spsp_records_extract_host(text.ctypes.data if len(text) else None, len(text), begin.ctypes.data, len(keep), keep.ctypes.data if len(keep) else None,
+                                           C.byref(out), C.byref(n_out), C.byref(n_kept)))
+    return _take(out, n_out.value), n_kept.value
+
+
+def extract_flags_classify(what, records, hits, n_ref):
+    """spsp_extract_flags_classify_host: a word (matched, unmatched, best=<j>, listed=<j>) and classify's rows (records, hits[n, top])
+    -> keep: np.uint8[n]"""
+    records = np.ascontiguousarray(records, dtype=CLASSIFY_RECORD_DTYPE)
+    hits = np.ascontiguousarray(hits, dtype=CLASSIFY_HIT_DTYPE)
+    n = len(records)
+    if hits.ndim != 2 or hits.shape[0] != n:
+        raise ValueError("extract_flags_classify: hits[n_records, top]")
+    keep = np.zeros(max(n, 1), dtype=np.uint8)
+    _check(lib().spsp_extract_flags_classify_host(what.encode(), records.ctypes.data if n else None, hits.ctypes.data if n else None, n, hits.shape[1], n_ref,
+                                                  keep.ctypes.data))
+    return keep[:n]
+
+
+def extract_flags_taxonomy(what, records, size):
+    """spsp_extract_flags_taxonomy_host: a word (classified, unclassified, taxon=<t>, clade=<t>), the taxonomy's rows and the tree's
+    subtree sizes (taxonomy_lineages()["size"]) -> keep: np.uint8[n]"""
+    records = np.ascontiguousarray(records, dtype=TAXONOMY_RECORD_DTYPE)
+    size = np.ascontiguousarray(size, dtype=np.uint32)
+    n = len(records)
+    keep = np.zeros(max(n, 1), dtype=np.uint8)
+    _check(lib().spsp_extract_flags_taxonomy_host(what.encode(), records.ctypes.data if n else None, n, size.ctypes.data if len(size) else None, len(size),
+                                                  keep.ctypes.data))
+    return keep[:n]
 
 
 def taxonomy_csv(records, record_names, parent, node_names, precision=6):
@@ -1612,17 +1697,54 @@ class Context:
         _check(lib().spsp_classify_stage_ms(self._h, ms))
         return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
 
-    def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0):
+    def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True):
         """spsp_classify_files: the sketch files of the references and a FASTA / FASTQ file of records (gzip or plain) ->
         <prefix>_classify.csv.gz, <prefix>_classify_summary.csv.gz and (records, hits[n, top]).  rate: as compare_files (0.0, a
-        rate, or "auto"); sketches of different rates need one"""
+        rate, or "auto"); sketches of different rates need one.  extract: a word (matched, unmatched, best=<j>, listed=<j>) --
+        spsp_classify_files_extract: the records it names are written to <prefix>_extract.fa or .fq (".gz" appended when gz) as
+        well; self.last_extract = dict(n_kept, bytes_out)"""
         arr, _alive = _paths_array(paths)
         recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
         self._cf_n_ref = None
-        _check(lib().spsp_classify_files(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
-                                         _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n)))
+        if extract is not None:
+            kept, out_bytes = C.c_uint64(), C.c_uint64()
+            _check(lib().spsp_classify_files_extract(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
+                                                     _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n), extract.encode(), 1 if gz else 0,
+                                                     C.byref(kept), C.byref(out_bytes)))
+            self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
+        else:
+            _check(lib().spsp_classify_files(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
+                                             _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n)))
         return (np.frombuffer(_take(recs, n.value * CLASSIFY_RECORD_DTYPE.itemsize), dtype=CLASSIFY_RECORD_DTYPE).copy(),
                 np.frombuffer(_take(hits, n.value * top * CLASSIFY_HIT_DTYPE.itemsize), dtype=CLASSIFY_HIT_DTYPE).copy().reshape(n.value, top))
+
+    def records_extents_device(self, d_text, n_text):
+        """spsp_records_extents_device: a FASTA / FASTQ text in HBM (16-byte aligned) -> (d_begin, n_rec): the context's uint64
+        array of n_rec + 1 record starts, valid until the next extents call or the next extract call that makes its own"""
+        d, n = C.c_void_p(), C.c_uint32()
+        _check(lib().spsp_records_extents_device(self._h, d_text, n_text, C.byref(d), C.byref(n)))
+        return d.value, n.value
+
+    def records_extract_device(self, d_text, n_text, keep, d_begin=None, n_rec=None):
+        """spsp_records_extract_device: the records of the text in HBM with keep[r] != 0, back to back -> (np.uint8 array,
+        n_kept).  d_begin: the starts on the device (records_extents_device) or None: they are made in the call, for len(keep)
+        records.  Only the kept bytes cross to the host"""
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if n_rec is None:
+            n_rec = len(keep)
+        if len(keep) != n_rec:
+            raise ValueError("records_extract_device: one flag per record")
+        out, n_out, n_kept = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        _check(lib().spsp_records_extract_device(self._h, d_text, n_text, d_begin, n_rec, keep.ctypes.data if n_rec else None, C.byref(out), C.byref(n_out),
+                                                 C.byref(n_kept)))
+        return self.to_host(out.value, n_out.value, np.uint8), n_kept.value
+
+    def extract_stage_ms(self):
+        """spsp_extract_stage_ms: with timing_enable() on, the milliseconds of the extract calls' launches since the last read ->
+        dict(starts, offsets, copy)"""
+        ms = (C.c_double * 3)()
+        _check(lib().spsp_extract_stage_ms(self._h, ms))
+        return dict(zip(("starts", "offsets", "copy"), ms))
 
     def taxonomy_index_device(self, parent, ref_node, want_key_nodes=False):
         """spsp_taxonomy_index_device: a tree (parents in preorder) and the references' nodes attached to the context's index
@@ -1653,15 +1775,24 @@ class Context:
         _check(lib().spsp_taxonomy_stage_ms(self._h, ms))
         return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
 
-    def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0):
+    def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True):
         """spsp_taxonomy_files: the sketch files of the references, a FASTA / FASTQ file of records (gzip or plain) and the lineage
         file of the references -> <prefix>_taxonomy.csv.gz, <prefix>_taxonomy_report.csv.gz and the records.  rate: as
-        classify_files (0.0, a rate, or "auto"); sketches of different rates need one"""
+        classify_files (0.0, a rate, or "auto"); sketches of different rates need one.  extract: a word (classified, unclassified,
+        taxon=<t>, clade=<t>) -- spsp_taxonomy_files_extract: the records it names are written to <prefix>_extract.fa or .fq (".gz"
+        appended when gz) as well; self.last_extract = dict(n_kept, bytes_out)"""
         arr, _alive = _paths_array(paths)
         recs, n = C.c_void_p(), C.c_uint64()
         self._cf_n_ref = None
-        _check(lib().spsp_taxonomy_files(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
-                                         prefix.encode(), 0, _rate_arg(rate), C.byref(recs), C.byref(n)))
+        if extract is not None:
+            kept, out_bytes = C.c_uint64(), C.c_uint64()
+            _check(lib().spsp_taxonomy_files_extract(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
+                                                     prefix.encode(), 0, _rate_arg(rate), C.byref(recs), C.byref(n), extract.encode(), 1 if gz else 0,
+                                                     C.byref(kept), C.byref(out_bytes)))
+            self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
+        else:
+            _check(lib().spsp_taxonomy_files(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
+                                             prefix.encode(), 0, _rate_arg(rate), C.byref(recs), C.byref(n)))
         return np.frombuffer(_take(recs, n.value * TAXONOMY_RECORD_DTYPE.itemsize), dtype=TAXONOMY_RECORD_DTYPE).copy()
 
     def depth_begin(self):

@@ -127,12 +127,14 @@ int main(int argc, char** argv) {
     long long cf_top = 1, cf_min_keys = 1;
     string lineages_file;            // -H <lineages file>: with -X, the records go to the lowest common ancestor of their keys (not in the reference's option string)
     bool taxonomy = false, cf_top_seen = false;
+    string extract_what;             // -F <what> [-u]: with -X, the records the word names are written out again (neither letter is in the reference's option string)
+    bool extract = false, extract_plain = false;
     vector<string> reads_files;      // -D <reads file> [-D <more> ...] [-W <min_count>]: neither letter is in the reference's option string
     bool dp_min_seen = false;
     long long dp_min_count = 1;
     bool profile = false;            // -B <min_keys>: the profile behind the depth of -D (not in the reference's option string either)
     long long pf_min_keys = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:")) != -1) {
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:u")) != -1) {
         switch (ch) {
             case 'D': reads_files.push_back(optarg); break;
             case 'W': {
@@ -152,6 +154,8 @@ int main(int argc, char** argv) {
             case 'G': labels_file = optarg; groups = true; break;
             case 'X': records_file = optarg; classify = true; break;
             case 'H': lineages_file = optarg; taxonomy = true; break;
+            case 'F': extract_what = optarg; extract = true; break;
+            case 'u': extract_plain = true; break;
             case 'Y': {
                 char* e = nullptr;
                 cf_top = strtoll(optarg, &e, 10);
@@ -288,6 +292,9 @@ int main(int argc, char** argv) {
     if (nb_opts > 1) { cout << "-J (Jaccard), -K (the larger containment) and -I (the row's containment) set the threshold of -N: one of them, once" << endl; return 1; }
     if (taxonomy && !classify) { cout << "-H gives the lineages of the index for the records of -X <records file>: it needs -X" << endl; return 1; }
     if (taxonomy && cf_top_seen) { cout << "-H assigns every record to one node of the tree: not together with -Y (-V and -I set its threshold)" << endl; return 1; }
+    if (extract && !classify) { cout << "-F names the records of -X <records file> to write out again: it needs -X" << endl; return 1; }
+    if (extract_plain && !extract) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
+    if (extract && spsp_extract_word_check_host(extract_what.c_str(), taxonomy ? 1 : 0, 0xffffffffu) != SPSP_OK) { cout << "-F: " << spsp_last_error() << endl; return 1; }
     if (cf_opts && !classify) { cout << "-Y and -V belong to the classification of -X <records file>: they need -X" << endl; return 1; }
     if (classify && (query != "" || gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts || select_opts || accumulation || groups ||
                      (nb_opts && nb_metric != SPSP_NEIGHBOUR_CONTAINED))) {
@@ -343,6 +350,8 @@ int main(int argc, char** argv) {
              << "-f Index file of files (mandatory)" << endl
              << "-q Query file of files (\"\" for all versus all comparison of the index)" << endl
              << "-H Lineage file, one name;name;... line per index sketch: with -X <records file>, each record goes to the lowest common ancestor of its keys" << endl
+             << "-F Records of -X <records file> to write out again as <prefix>_extract.fa.gz / .fq.gz: matched, unmatched, best=<j>, listed=<j>; with -H: classified, unclassified, taxon=<t>, clade=<t>" << endl
+             << "-u Write the records of -F plain, not gzipped" << endl
              << "Ouput arguments:" << endl
              << "-m Minimum value to be output (0.0)" << endl
              << "-p Required precision to be output in the CSV (6)" << endl
@@ -365,6 +374,10 @@ int main(int argc, char** argv) {
     }
     vector<const char*> paths;
     for (auto& s : names) paths.push_back(s.c_str());
+    if (extract && !taxonomy && spsp_extract_word_check_host(extract_what.c_str(), 0, (uint32_t)paths.size()) != SPSP_OK) {   // (<j> against the list: no device yet)
+        cout << "-F: " << spsp_last_error() << endl;
+        return 1;
+    }
     // Devices: every visible GPU when there is enough work to split (the comparison is dealt by key over one context per
     // device, spsp_compare_files_multi), else the first.  SPSP_DEVICES="0,1,2,3" (or "0,0": two contexts on one device)
     // names them explicitly.  The reference has no such notion (one thread, Comparator.cpp:39-74).
@@ -405,9 +418,15 @@ int main(int argc, char** argv) {
         // one device, as gather (the driver opens a second context on it for the records)
         spsp_ctx* ctx = nullptr;
         int rc = spsp_create(devices[0], nullptr, &ctx);
-        if (rc == SPSP_OK && taxonomy)
+        if (rc == SPSP_OK && taxonomy && extract)
+            rc = spsp_taxonomy_files_extract(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den,
+                                             (int)p, output_name.c_str(), 1, rate, nullptr, nullptr, extract_what.c_str(), extract_plain ? 0 : 1, nullptr, nullptr);
+        else if (rc == SPSP_OK && taxonomy)
             rc = spsp_taxonomy_files(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den, (int)p,
                                      output_name.c_str(), 1, rate, nullptr, nullptr);
+        else if (rc == SPSP_OK && extract)
+            rc = spsp_classify_files_extract(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den, (int)p,
+                                             output_name.c_str(), 1, rate, nullptr, nullptr, nullptr, extract_what.c_str(), extract_plain ? 0 : 1, nullptr, nullptr);
         else if (rc == SPSP_OK) rc = spsp_classify_files(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den,
                                                     (int)p, output_name.c_str(), 1, rate, nullptr, nullptr, nullptr);
         const string err = rc != SPSP_OK ? spsp_last_error() : "";

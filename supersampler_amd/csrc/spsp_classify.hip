@@ -492,7 +492,7 @@ static int batch_seams(spsp_ctx* ctx, const spsp_superkmer* d_sk, uint64_t n_sk,
 // on_records: once, behind the scan, with the records' base offsets (n_rec + 1)
 int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
                          std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                         const std::function<int(const RecordBatch&)>& on_batch) {
+                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract) {
     int rc;
     double t0 = now_s(), t1;
     const bool fastq = n_text && text[0] == '@';
@@ -538,13 +538,15 @@ int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
             (rc = spsp_wait_stream(ctx, side)) ||
             (rc = on_batch(RecordBatch{r0, batch, (const uint32_t*)k_mn, (const uint64_t*)k_lo, (const uint64_t*)k_hi, key_off.data()}))) return rc;
     }
+    // (every batch's rows are on the host: each record call waits.  The text still sits in the side context's buffer)
+    if (extract && (rc = extract->on_text(side, side->i_text.as<uint8_t>(), n_text, n_rec))) return rc;
     return SPSP_OK;
 }
 
 // the road of the four record file drivers: load, refusals, decode, index, on_index, every records file through its batches, on_close
 int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
                        const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1) {
+                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1, ExtractRun* extract) {
     spsp_ctx* ctx = run.ctx;
     int rc = run.load(rate);
     if (!rc) rc = run.refuse_k_eq_m(rc, what_is);
@@ -563,7 +565,7 @@ int records_files_road(FilesRun& run, const char* what_is, const char* const* re
             uint8_t* text = nullptr; uint64_t n_text = 0;
             if (!(rc = spsp_read_file_host(records_paths[f], &text, &n_text)) && (side || !(rc = spsp_create(ctx->device, nullptr, &side))) &&
                 !(rc = spsp_wait_stream(side, ctx)))       // (the last file's keys have been read)
-                rc = records_text_batches(ctx, side, &p, text, n_text, records_paths[f], names, on_records, on_batch);
+                rc = records_text_batches(ctx, side, &p, text, n_text, records_paths[f], names, on_records, on_batch, extract);
             spsp_free(text);
         }
         if (!rc) rc = on_close();
@@ -577,10 +579,14 @@ int records_files_road(FilesRun& run, const char* what_is, const char* const* re
 // spsp_classify_files behind its argument checks
 static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys, uint32_t num,
                           uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_classify_record>* recs,
-                          std::vector<spsp_classify_hit>* hits) {
+                          std::vector<spsp_classify_hit>* hits, ExtractRun* extract) {
     FilesRun run(ctx, paths, n_ref, chatter);
     std::vector<std::string> names;
     double t1 = 0;
+    if (extract)
+        extract->flags = [&](uint32_t n_rec, uint8_t* keep) {
+            return spsp_extract_flags_classify_host(extract->what, recs->data(), hits->data(), n_rec, top, n_ref, keep);
+        };
     int rc = records_files_road(
         run, "classification is", &records_path, 1, rate, [] { return SPSP_OK; }, &names,
         [&](uint32_t n_rec, const uint64_t* rec_off) {
@@ -593,7 +599,7 @@ static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
             return classify_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, top, min_keys, num, den, recs->data() + B.first_record,
                                         hits->data() + (size_t)B.first_record * top);
         },
-        [] { return SPSP_OK; }, &t1);
+        [] { return SPSP_OK; }, &t1, extract);
     if (rc) return rc;
     std::vector<const char*> name_ptr(names.size());
     for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
@@ -602,7 +608,8 @@ static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
     if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify.csv.gz", t1))) return rc;
     const double t2 = now_s();
     if ((rc = spsp_classify_summary_csv_host(recs->data(), hits->data(), recs->size(), paths, n_ref, top, &text, &len))) return rc;
-    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify_summary.csv.gz", t2)) || !chatter) return rc;
+    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify_summary.csv.gz", t2)) || (extract && (rc = extract->write(ctx, out_prefix, chatter))) || !chatter)
+        return rc;
     uint64_t with = 0;
     for (const spsp_classify_record& r : *recs) with += r.listed != 0;
     printf("%zu record(s) against %u reference(s): %llu with a match\n", recs->size(), n_ref, (unsigned long long)with);
@@ -631,24 +638,49 @@ extern "C" int spsp_classify_device(spsp_ctx* ctx, const void* d_q_minimizer, co
                                 min_keys, num, den, records, hits);
 }
 
-extern "C" int spsp_classify_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
-                                   uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
-                                   spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records) {
+// spsp_classify_files and spsp_classify_files_extract (what == nullptr: no extraction)
+static int classify_files_entry(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, spsp_classify_record** records,
+                                spsp_classify_hit** hits, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out) {
     if (records) *records = nullptr;
     if (hits) *hits = nullptr;
     if (n_records) *n_records = 0;
+    if (n_kept) *n_kept = 0;
+    if (bytes_out) *bytes_out = 0;
     if (!ctx || !index_paths || !records_path || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
     if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
     int rc;
     if ((rc = classify_check_args(top, min_keys, num, den))) return rc;
+    if (what && (rc = spsp_extract_word_check_host(what, 0, n_ref))) return rc;   // (before any file is read)
     SPSP_HIP(hipSetDevice(ctx->device));
     std::vector<spsp_classify_record> got;
     std::vector<spsp_classify_hit> got_hits;
-    if ((rc = classify_files(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, &got, &got_hits))) return rc;
+    ExtractRun extract;
+    extract.what = what; extract.gz = gz;
+    if ((rc = classify_files(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, &got, &got_hits,
+                             what ? &extract : nullptr))) return rc;
+    if (n_kept) *n_kept = extract.n_kept;
+    if (bytes_out) *bytes_out = extract.out.size();
     if (n_records) *n_records = got.size();
     if (records && (rc = give_rows(got, records))) return rc;
     if (hits && (rc = give_rows(got_hits, hits))) { if (records) { free(*records); *records = nullptr; } return rc; }
     return SPSP_OK;
+}
+
+extern "C" int spsp_classify_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                   uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                   spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records) {
+    return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
+                                nullptr, 1, nullptr, nullptr);
+}
+
+extern "C" int spsp_classify_files_extract(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top,
+                                           uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                           spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records, const char* what, int gz,
+                                           uint64_t* n_kept, uint64_t* bytes_out) {
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
+                                what, gz, n_kept, bytes_out);
 }
 
 extern "C" int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms) {

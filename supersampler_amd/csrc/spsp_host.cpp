@@ -2895,3 +2895,191 @@ int spsp_compare_files_multi_rate(const int* devices, uint32_t n_dev, const char
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------- extract
+// The host forms of the extraction, plain loops straight from the rule of include/spsp.h ("extract"): what the device pass is held
+// against, and what turns a word and a pass's rows into keep flags.
+
+extern "C" int spsp_extract_plan_host(uint32_t* tile_bytes, uint32_t* stretch_bytes) {
+    if (tile_bytes) *tile_bytes = spsp::kExTile;
+    if (stretch_bytes) *stretch_bytes = spsp::kExStretch;
+    return SPSP_OK;
+}
+
+extern "C" int spsp_records_extents_host(const uint8_t* text, uint64_t n, uint64_t** begin, uint32_t* n_rec) {
+    using namespace spsp;
+    if (begin) *begin = nullptr;
+    if (n_rec) *n_rec = 0;
+    if (!begin || !n_rec || (n && !text)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    std::vector<uint64_t> b;
+    if (n > 0 && text[0] == '@') {
+        uint64_t end = n;
+        while (end && (text[end - 1] == '\n' || text[end - 1] == '\r')) --end;   // the content: the text less its blank tail
+        uint64_t lines = 1;
+        b.push_back(0);
+        for (uint64_t p = 0; p < end; ++p)
+            if (text[p] == '\n' && lines++ % 4 == 0) b.push_back(p + 1);         // line `lines` begins behind this newline
+        uint64_t last = end;                               // the last record ends behind the newline of its fourth line, where it has one
+        for (uint64_t p = end; p < n; ++p)
+            if (text[p] == '\n') { last = p + 1; break; }
+        if (lines % 4 == 3 && last > end && last < n) {    // an empty quality line given by the blank tail: the ingest's empty read
+            ++lines;
+            const uint64_t from = last;
+            last = n;
+            for (uint64_t p = from; p < n; ++p)
+                if (text[p] == '\n') { last = p + 1; break; }
+        }
+        if (lines % 4 != 0) { set_error("FASTQ: the content has %llu line(s), which is not a multiple of four", (unsigned long long)lines); return SPSP_ERR_FORMAT; }
+        b.push_back(last);
+    } else {
+        b.push_back(0);                                    // line 0 is a header whatever it holds
+        for (uint64_t p = 1; p < n; ++p)
+            if (text[p - 1] == '\n' && (text[p] == '>' || text[p] == 0xFFu)) b.push_back(p);
+        b.push_back(n);
+    }
+    if (b.size() - 1 > 0xfffffff0ull) { set_error("too many records for one call"); return SPSP_ERR_OVERFLOW; }
+    *begin = (uint64_t*)malloc(b.size() * 8);
+    if (!*begin) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    memcpy(*begin, b.data(), b.size() * 8);
+    *n_rec = (uint32_t)(b.size() - 1);
+    return SPSP_OK;
+}
+
+extern "C" int spsp_records_extract_host(const uint8_t* text, uint64_t n, const uint64_t* begin, uint32_t n_rec, const uint8_t* keep, uint8_t** out,
+                                         uint64_t* n_out, uint64_t* n_kept) {
+    using namespace spsp;
+    if (out) *out = nullptr;
+    if (n_out) *n_out = 0;
+    if (n_kept) *n_kept = 0;
+    if (!out || !n_out || !n_kept || !begin || (n && !text) || (n_rec && !keep)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    uint64_t bytes = 0, kept = 0;
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        if (begin[r] > begin[r + 1] || begin[r + 1] > n) { set_error("extract: begin must not decrease and must end inside the text"); return SPSP_ERR_ARG; }
+        if (!keep[r]) continue;
+        ++kept;
+        bytes += begin[r + 1] - begin[r];
+        if (r + 1 == n_rec && begin[r + 1] > begin[r] && text[begin[r + 1] - 1] != '\n') ++bytes;   // (only the last record can lack its newline)
+    }
+    uint8_t* o = (uint8_t*)malloc(bytes ? bytes : 1);
+    if (!o) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    uint64_t at = 0;
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        const uint64_t len = begin[r + 1] - begin[r];
+        if (!keep[r] || !len) continue;
+        memcpy(o + at, text + begin[r], len);
+        at += len;
+        if (r + 1 == n_rec && o[at - 1] != '\n') o[at++] = '\n';
+    }
+    *out = o; *n_out = at; *n_kept = kept;
+    return SPSP_OK;
+}
+
+namespace {
+
+// "<name>=<number>": the number, decimal digits only, as 32 bits
+bool extract_word_number(const char* what, const char* name, uint32_t* value) {
+    const size_t len = strlen(name);
+    if (strncmp(what, name, len) != 0 || what[len] != '=') return false;
+    const char* p = what + len + 1;
+    if (!*p) return false;
+    uint64_t v = 0;
+    for (; *p; ++p) {
+        if (*p < '0' || *p > '9') return false;
+        v = v * 10 + (uint64_t)(*p - '0');
+        if (v > 0xffffffffull) return false;
+    }
+    *value = (uint32_t)v;
+    return true;
+}
+
+enum ExtractWord { kXwNone = 0, kXwMatched, kXwUnmatched, kXwBest, kXwListed, kXwClassified, kXwUnclassified, kXwTaxon, kXwClade };
+
+ExtractWord extract_word(const char* what, uint32_t* value) {
+    *value = 0;
+    if (!strcmp(what, "matched")) return kXwMatched;
+    if (!strcmp(what, "unmatched")) return kXwUnmatched;
+    if (!strcmp(what, "classified")) return kXwClassified;
+    if (!strcmp(what, "unclassified")) return kXwUnclassified;
+    if (extract_word_number(what, "best", value)) return kXwBest;
+    if (extract_word_number(what, "listed", value)) return kXwListed;
+    if (extract_word_number(what, "taxon", value)) return kXwTaxon;
+    if (extract_word_number(what, "clade", value)) return kXwClade;
+    return kXwNone;
+}
+
+// the word of a call with classify rows (taxonomy == false) or taxonomy rows, or its refusal
+int extract_word_for(const char* what, bool taxonomy, ExtractWord* word, uint32_t* value) {
+    using namespace spsp;
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    *word = extract_word(what, value);
+    if (*word == kXwNone) {
+        set_error("extract: '%.64s' names no records (%s)", what,
+                  taxonomy ? "with a taxonomy: classified, unclassified, taxon=<t>, clade=<t>" : "matched, unmatched, best=<j>, listed=<j>");
+        return SPSP_ERR_ARG;
+    }
+    const bool taxonomy_word = *word >= kXwClassified;
+    if (taxonomy_word != taxonomy) {
+        set_error(taxonomy ? "extract: '%.64s' asks classify's rows, these are a taxonomy's (classified, unclassified, taxon=<t>, clade=<t>)"
+                           : "extract: '%.64s' asks a taxonomy's rows, these are classify's (matched, unmatched, best=<j>, listed=<j>)", what);
+        return SPSP_ERR_ARG;
+    }
+    return SPSP_OK;
+}
+
+}  // namespace
+
+extern "C" int spsp_extract_word_check_host(const char* what, int taxonomy, uint32_t limit) {
+    using namespace spsp;
+    ExtractWord word; uint32_t v = 0;
+    if (const int rc = extract_word_for(what, taxonomy != 0, &word, &v)) return rc;
+    if ((word == kXwBest || word == kXwListed) && v >= limit) { set_error("extract: '%.64s': the index has %u reference(s)", what, limit); return SPSP_ERR_ARG; }
+    if ((word == kXwTaxon || word == kXwClade) && v >= limit) { set_error("extract: '%.64s': the tree has %u node(s)", what, limit); return SPSP_ERR_ARG; }
+    return SPSP_OK;
+}
+
+extern "C" int spsp_extract_flags_classify_host(const char* what, const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records,
+                                                uint32_t top, uint32_t n_ref, uint8_t* keep) {
+    using namespace spsp;
+    if (n_records && (!records || !hits || !keep)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (top == 0 || top > kCfMaxTop) { set_error("top must be 1 .. %u (top = %u)", kCfMaxTop, top); return SPSP_ERR_ARG; }
+    if (const int rc = spsp_extract_word_check_host(what, 0, n_ref)) return rc;
+    ExtractWord word; uint32_t j = 0;
+    (void)extract_word_for(what, false, &word, &j);
+    for (uint64_t r = 0; r < n_records; ++r) {
+        const uint32_t listed = records[r].listed;
+        if (listed > top) { set_error("extract: record %llu lists %u matches, top = %u", (unsigned long long)r, listed, top); return SPSP_ERR_ARG; }
+        const spsp_classify_hit* h = hits + r * top;
+        bool k = false;
+        switch (word) {
+            case kXwMatched: k = listed >= 1; break;
+            case kXwUnmatched: k = listed == 0; break;
+            case kXwBest: k = listed >= 1 && h[0].reference == j; break;
+            default:
+                for (uint32_t i = 0; i < listed; ++i) k = k || h[i].reference == j;
+        }
+        keep[r] = k ? 1 : 0;
+    }
+    return SPSP_OK;
+}
+
+extern "C" int spsp_extract_flags_taxonomy_host(const char* what, const spsp_taxonomy_record* records, uint64_t n_records, const uint32_t* size,
+                                                uint32_t n_nodes, uint8_t* keep) {
+    using namespace spsp;
+    if (!size || (n_records && (!records || !keep))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_nodes == 0 || n_nodes > kTxMaxNodes) { set_error("a taxonomy takes 1 .. %u nodes (T = %u)", kTxMaxNodes, n_nodes); return SPSP_ERR_ARG; }
+    if (const int rc = spsp_extract_word_check_host(what, 1, n_nodes)) return rc;
+    ExtractWord word; uint32_t t = 0;
+    (void)extract_word_for(what, true, &word, &t);
+    for (uint64_t r = 0; r < n_records; ++r) {
+        const uint32_t node = records[r].node;
+        bool k = false;
+        switch (word) {
+            case kXwClassified: k = node != SPSP_TAXONOMY_NONE; break;
+            case kXwUnclassified: k = node == SPSP_TAXONOMY_NONE; break;
+            case kXwTaxon: k = node == t; break;
+            default: k = node != SPSP_TAXONOMY_NONE && t <= node && node - t < size[t];   // the preorder range: t <= node < t + size[t]
+        }
+        keep[r] = k ? 1 : 0;
+    }
+    return SPSP_OK;
+}

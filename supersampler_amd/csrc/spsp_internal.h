@@ -345,6 +345,12 @@ struct spsp_ctx {
     // the same per index entry where it was asked for.  Its calls work in the classification's per-call arrays above
     spsp::DevBuf tx_tree, tx_key_node, tx_entry_node;
     spsp::RecordClock cf_clock, tx_clock;   // spsp_classify_stage_ms, spsp_taxonomy_stage_ms
+    // extraction (spsp_extract.hip): the call's words, the tiles' sums and their scan (the text's tiles, then the records'), the
+    // records' starts, the keep flags, the run table (output starts, then source starts) and the output, which is whole stretches
+    spsp::DevBuf ex_words, ex_tiles, ex_bases, ex_begin, ex_keep, ex_runs, ex_out;
+    hipEvent_t ex_ev[4] = {};            // while timing is on: in front of the starts, the offsets, the copy, and behind it
+    uint32_t ex_marked = 0;              // ... which of them the call in flight has recorded
+    double ex_ms[3] = {};                // their milliseconds since spsp_extract_stage_ms last read them: starts, offsets, copy
 };
 
 namespace spsp {
@@ -543,9 +549,23 @@ int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
 // then a text with another number of header lines than the device finds records is SPSP_ERR_FORMAT.  on_records is called once,
 // behind the scan, with the records' base offsets (n_rec + 1)
 struct RecordBatch { uint32_t first_record, n_records; const uint32_t* mn; const uint64_t *lo, *hi; const uint64_t* key_off; };   // key_off: host, n_records + 1
+// what a record file driver writes beside its CSVs when it is asked to (spsp_extract.hip).  on_text is the road's hook: behind a
+// file's last batch, with the text still in the side context's buffer, it has `flags` (the driver's: its rows -> keep[n_rec]) make
+// the flags, runs the extraction on `side` and brings the kept bytes to `out`.  write: <out_prefix>_extract.fa or .fq (by the
+// text's kind), gzip level 1 with ".gz" appended when gz, and with chatter the line of what was kept
+struct ExtractRun {
+    const char* what = nullptr;
+    int gz = 1;
+    std::function<int(uint32_t, uint8_t*)> flags;
+    bool fastq = false;
+    uint64_t n_rec = 0, n_kept = 0;
+    std::vector<uint8_t> out;
+    int on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_rec);
+    int write(spsp_ctx* ctx, const char* out_prefix, int chatter);
+};
 int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
                          std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                         const std::function<int(const RecordBatch&)>& on_batch);
+                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract = nullptr);
 // spsp_depth.hip: how many records hold each key of the index, and the per-reference statistics over those counts
 constexpr uint32_t kDpThreads = 256;                       // every depth kernel: 4 waves
 constexpr uint32_t kDpBins = 4096;                         // bins of one LDS histogram of k_dp_reduce: the last holds every count at or above kDpBins - 1
@@ -618,11 +638,22 @@ int classify_probe_launch(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q
 struct FilesRun;
 int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
                        const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1);
+                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1,
+                       ExtractRun* extract = nullptr);
 int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den);
 int taxonomy_index_impl(spsp_ctx* ctx, const uint32_t* parent, uint32_t T, const uint32_t* ref_node, uint32_t n_ref, const uint32_t** key_nodes_out);
 int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
                          uint32_t min_keys, uint32_t num, uint32_t den, spsp_taxonomy_record* records);
+// spsp_extract.hip: the records of a text and the kept ones written out again (the rule: include/spsp.h).  What the kernels cut at
+// (spsp_extract_plan_host, spsp_host.cpp):
+constexpr uint32_t kExTile = 4096;                         // bytes of the text per workgroup of the starts pass (the ingest's tile)
+constexpr uint32_t kExStretch = 16384;                     // bytes of the output one workgroup of the copy owns
+// begin[0 .. n_rec] in a context-owned buffer, with one host wait (for n_rec); *fastq (may be null): what the text is
+int records_extents_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t** d_begin, uint32_t* n_rec, bool* fastq);
+// the kept records back to back in a context-owned buffer, with one host wait (for n_out).  d_begin == null: the starts are made
+// here, for n_rec records -- a text that holds another number is SPSP_ERR_ARG behind the wait, nothing having left the buffers
+int records_extract_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const uint64_t* d_begin, uint32_t n_rec, const uint8_t* h_keep,
+                         uint8_t** d_out, uint64_t* n_out, uint64_t* n_kept, bool* fastq);
 // spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
 // groups as n_groups sketches back to back in context-owned arrays
 int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,

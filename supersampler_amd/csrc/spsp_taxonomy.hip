@@ -394,17 +394,23 @@ int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
 
 // spsp_taxonomy_files behind its argument checks
 static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, const char* lineages_path, uint32_t min_keys,
-                          uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_taxonomy_record>* recs) {
+                          uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_taxonomy_record>* recs,
+                          ExtractRun* extract) {
     int rc;
     // the lineage file first: a tree that cannot be read costs no loading
     uint8_t* lin = nullptr; uint64_t n_lin = 0;
     if ((rc = spsp_read_file_host(lineages_path, &lin, &n_lin))) return rc;
     std::vector<uint32_t> ref_node(n_ref, 0);
-    uint32_t *parent = nullptr, *depth = nullptr, T = 0;
+    uint32_t *parent = nullptr, *depth = nullptr, *size = nullptr, T = 0;
     char* blob = nullptr; uint64_t blob_len = 0;
-    rc = spsp_taxonomy_lineages_host((const char*)lin, n_lin, n_ref, ref_node.data(), &parent, &depth, nullptr, &blob, &blob_len, &T);
+    rc = spsp_taxonomy_lineages_host((const char*)lin, n_lin, n_ref, ref_node.data(), &parent, &depth, extract ? &size : nullptr, &blob, &blob_len, &T);
     spsp_free(lin);
     if (rc) return rc;
+    if (extract) {
+        // (the word's node against the tree: still before any sketch is read)
+        if ((rc = spsp_extract_word_check_host(extract->what, 1, T))) { spsp_free(parent); spsp_free(depth); spsp_free(size); spsp_free(blob); return rc; }
+        extract->flags = [&, size, T](uint32_t n_rec, uint8_t* keep) { return spsp_extract_flags_taxonomy_host(extract->what, recs->data(), n_rec, size, T, keep); };
+    }
     std::vector<const char*> node_names(T);
     for (uint64_t at = 0, t = 0; t < T; ++t) { node_names[t] = blob + at; at += strlen(blob + at) + 1; }
     FilesRun run(ctx, paths, n_ref, chatter);
@@ -418,7 +424,7 @@ static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
             return SPSP_OK;
         },
         [&](const RecordBatch& B) { return taxonomy_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, min_keys, num, den, recs->data() + B.first_record); },
-        [] { return SPSP_OK; }, &t1);
+        [] { return SPSP_OK; }, &t1, extract);
     char *text = nullptr, *report = nullptr; uint64_t len = 0, report_len = 0;
     if (!rc) {
         std::vector<const char*> name_ptr(names.size());
@@ -432,6 +438,7 @@ static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
         text = nullptr;
         const double t2 = now_s();
         if (!rc) { rc = write_csv_gz(ctx, report, report_len, out_prefix, "_taxonomy_report.csv.gz", t2); report = nullptr; }
+        if (!rc && extract) rc = extract->write(ctx, out_prefix, chatter);
     }
     if (!rc && chatter) {
         uint64_t called = 0, at_root = 0;
@@ -442,7 +449,7 @@ static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
         fflush(stdout);
     }
     spsp_free(text); spsp_free(report);
-    spsp_free(parent); spsp_free(depth); spsp_free(blob);
+    spsp_free(parent); spsp_free(depth); spsp_free(size); spsp_free(blob);
     return rc;
 }
 
@@ -469,21 +476,46 @@ extern "C" int spsp_taxonomy_device(spsp_ctx* ctx, const void* d_q_minimizer, co
                                 num, den, records);
 }
 
-extern "C" int spsp_taxonomy_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
-                                   uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
-                                   spsp_taxonomy_record** records, uint64_t* n_records) {
+// spsp_taxonomy_files and spsp_taxonomy_files_extract (what == nullptr: no extraction)
+static int taxonomy_files_entry(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                spsp_taxonomy_record** records, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out) {
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
+    if (n_kept) *n_kept = 0;
+    if (bytes_out) *bytes_out = 0;
     if (!ctx || !index_paths || !records_path || !lineages_path || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
     if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
     int rc;
     if ((rc = taxonomy_check_args(min_keys, num, den))) return rc;
+    if (what && (rc = spsp_extract_word_check_host(what, 1, 0xffffffffu))) return rc;   // (the word, before any file is read; its node once the tree is)
     SPSP_HIP(hipSetDevice(ctx->device));
     std::vector<spsp_taxonomy_record> got;
-    if ((rc = taxonomy_files(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, &got))) return rc;
+    ExtractRun extract;
+    extract.what = what; extract.gz = gz;
+    if ((rc = taxonomy_files(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, &got,
+                             what ? &extract : nullptr))) return rc;
+    if (n_kept) *n_kept = extract.n_kept;
+    if (bytes_out) *bytes_out = extract.out.size();
     if (n_records) *n_records = got.size();
     if (records && (rc = give_rows(got, records))) return rc;
     return SPSP_OK;
+}
+
+extern "C" int spsp_taxonomy_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                   uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                   spsp_taxonomy_record** records, uint64_t* n_records) {
+    return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
+                                nullptr, 1, nullptr, nullptr);
+}
+
+extern "C" int spsp_taxonomy_files_extract(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                           uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                           spsp_taxonomy_record** records, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept,
+                                           uint64_t* bytes_out) {
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
+                                what, gz, n_kept, bytes_out);
 }
 
 extern "C" int spsp_taxonomy_stage_ms(spsp_ctx* ctx, double* ms) {
