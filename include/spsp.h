@@ -1473,6 +1473,67 @@ int spsp_taxonomy_files_extract(spsp_ctx* ctx, const char* const* index_paths, u
                                 spsp_taxonomy_record** records /* may be NULL; spsp_free */, uint64_t* n_records /* may be NULL */, const char* what,
                                 int gz, uint64_t* n_kept, uint64_t* bytes_out);
 
+/* ------------------------------------------------------- paired records ---- */
+/* Mate pairs classified and extracted as one record (not in the reference): Illumina data comes as two files, and record p of one
+ * and record p of the other are the two ends of one fragment -- the unit of evidence and of output.
+ * PAIR.  Pair p is record p of the records file (mate 1) together with record p of the mates file (mate 2).  The two files may be
+ * of different kinds (FASTA and FASTQ) and either may be gzip or plain.  Two files with different record counts are
+ * SPSP_ERR_FORMAT, and the error text gives both counts.
+ * KEYS.  Q_p = Q_p^1 u Q_p^2, where Q^i is exactly the record key set classify defines: spsp_sketch_keys_device over the one
+ * record, abundance 1, at the index's threshold.  A key present in both mates counts once (the mates of a short fragment overlap,
+ * and canonical k-mers make the reverse-complement mate produce the same keys).  keys = |Q_p|.  A mate without keys (shorter than
+ * k, or with no selected minimizer) contributes nothing; a pair whose mates both have none has keys = 0, as a record has.
+ * LENGTH.  The bases of mate 1 plus the bases of mate 2.
+ * FROM THERE ON A PAIR IS A RECORD.  Every threshold, tie rule, CSV column and report of classify and taxonomy applies to Q_p to
+ * the letter; the CSVs keep their columns, and `record` is the pair's number.
+ * NAME.  The pair's common name: the first whitespace-delimited word of mate 1's header with one trailing "/1" removed if present.
+ * Mate 2's first word with one trailing "/2" removed must equal it, byte for byte; a pair whose two names differ is
+ * SPSP_ERR_FORMAT, and the error text gives the pair's number and both names (files that have slipped out of step must not
+ * produce a CSV).  Both checks come before anything is computed.
+ * EXTRACT.  The flag functions run on the pairs' rows; the one flag vector cuts both texts, so <out_prefix>_extract_1.fa|fq[.gz]
+ * and <out_prefix>_extract_2.fa|fq[.gz] (each by its own text's kind) hold the same pairs in the same order: a mate is never
+ * kept without the other.
+ * Out of scope: depth and profile over fragments (they stay per record), interleaved single-file pairs, more than two mates. */
+/* The naming rule on the host.  names1 / names2: n first words each, as the headers hold them.  *bad = n and SPSP_OK, or the first
+ * pair whose names differ and SPSP_ERR_FORMAT.  common (may be NULL): the n common names, each ended by a 0 byte, back to back;
+ * spsp_free(). */
+int spsp_pairs_names_host(const char* const* names1, const char* const* names2, uint64_t n, char** common /* may be NULL; spsp_free */, uint64_t* bad);
+/* The constants the union's kernels cut at (either pointer may be NULL): the lanes of a workgroup (a lane per key), and the
+ * entries of B per count of the scan. */
+int spsp_union_plan_host(uint32_t* threads, uint32_t* tile);
+/* Per record r of n_records the union of A_r = entries [h_a_off[r], h_a_off[r + 1]) of the arrays A and B_r likewise: each side
+ * per record distinct and strictly ascending by (minimizer, kmer_hi, kmer_lo), which is what the sorted form of
+ * spsp_sketch_keys_device returns.  The inputs are the caller's (the key arrays of two other contexts, say), only read, and their
+ * offsets need not start at 0; kmer_hi is NULL on both sides iff k <= 32.  The output arrays are the context's, valid until its
+ * next union call: per record the union, distinct and strictly ascending -- a function of the two sets alone, for any call that
+ * wants sorted keys; h_off (n_records + 1, from 0) are its offsets.  A lane per key, never per record: a lane's trip count grows
+ * with a record's keys only through the logarithm of a binary search.  Launches: the flags (per entry of B: its place in A_r and
+ * whether A_r holds it; per entry of either side: its order), one scan over the tiles' counts, the offsets, the write.  One host
+ * wait, at the end.  Refused, in this order: k outside 1..63 (ARG), more than 0xfffffff0 records (OVERFLOW), offsets that decrease
+ * (ARG), more than 0xfffffff0 keys on both sides together (OVERFLOW), a NULL key array, kmer_hi against k (ARG), and, behind the
+ * wait, a record whose keys are not strictly ascending (ARG; the text names the side and the record).  A refused call hands out
+ * NULL arrays and offsets that are all 0. */
+int spsp_records_union_device(spsp_ctx* ctx, uint32_t k, const void* d_a_min, const void* d_a_lo, const void* d_a_hi /* NULL if k <= 32 */,
+                              const uint64_t* h_a_off /* n + 1 */, const void* d_b_min, const void* d_b_lo, const void* d_b_hi,
+                              const uint64_t* h_b_off /* n + 1 */, uint32_t n_records, void** d_min, void** d_lo, void** d_hi, uint64_t* h_off /* n + 1, from 0 */);
+/* While the context's timing is on a union call records events between its launches; this reads the milliseconds added up since
+ * the last read and clears them. */
+int spsp_union_stage_ms(spsp_ctx* ctx, double* ms /* 4: flags, scan, offsets, write */);
+/* The whole-file drivers over pairs: the arguments of spsp_classify_files_extract / spsp_taxonomy_files_extract with the mates
+ * file behind the records file, and what == NULL meaning no extraction.  Each file is ingested and scanned once on a side context
+ * of its own; per batch of at most 65 535 pairs the two key extractions run on the two sides' streams, one union on ctx makes the
+ * pairs' keys, and the unchanged spsp_classify_device / spsp_taxonomy_device work of a batch follows.  *n_records: the pairs;
+ * *n_kept: the pairs kept; *bytes_out: the bytes of both outputs before compression. */
+int spsp_classify_files_paired(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path, uint32_t top,
+                               uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                               const char* what /* NULL: no extraction */, int gz, spsp_classify_record** records /* may be NULL; spsp_free */,
+                               spsp_classify_hit** hits /* may be NULL; spsp_free */, uint64_t* n_records /* may be NULL */, uint64_t* n_kept,
+                               uint64_t* bytes_out);
+int spsp_taxonomy_files_paired(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
+                               const char* lineages_path, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter,
+                               double rate, const char* what /* NULL: no extraction */, int gz, spsp_taxonomy_record** records /* may be NULL; spsp_free */,
+                               uint64_t* n_records /* may be NULL */, uint64_t* n_kept, uint64_t* bytes_out);
+
 #ifdef __cplusplus
 }
 #endif

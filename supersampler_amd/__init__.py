@@ -166,6 +166,7 @@ ABI_SYMBOLS = [
     "spsp_extract_plan_host", "spsp_records_extents_host", "spsp_records_extract_host", "spsp_extract_flags_classify_host", "spsp_extract_flags_taxonomy_host",
     "spsp_extract_word_check_host", "spsp_records_extents_device", "spsp_records_extract_device", "spsp_extract_stage_ms", "spsp_classify_files_extract",
     "spsp_taxonomy_files_extract",
+    "spsp_pairs_names_host", "spsp_union_plan_host", "spsp_records_union_device", "spsp_union_stage_ms", "spsp_classify_files_paired", "spsp_taxonomy_files_paired",
 ]
 
 _lib = None
@@ -453,6 +454,19 @@ def lib():
         L.spsp_classify_files_extract.argtypes = [vp, P(cp), u32, cp, u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(vp), P(u64), cp, i32, P(u64), P(u64)]
         L.spsp_taxonomy_files_extract.restype = i32
         L.spsp_taxonomy_files_extract.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(u64), cp, i32, P(u64), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_records_union_device"):
+        L.spsp_pairs_names_host.restype = i32
+        L.spsp_pairs_names_host.argtypes = [P(cp), P(cp), u64, P(vp), P(u64)]
+        L.spsp_union_plan_host.restype = i32
+        L.spsp_union_plan_host.argtypes = [P(u32), P(u32)]
+        L.spsp_records_union_device.restype = i32
+        L.spsp_records_union_device.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, P(vp), P(vp), P(vp), vp]
+        L.spsp_union_stage_ms.restype = i32
+        L.spsp_union_stage_ms.argtypes = [vp, P(dbl)]
+        L.spsp_classify_files_paired.restype = i32
+        L.spsp_classify_files_paired.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, u32, i32, cp, i32, dbl, cp, i32, P(vp), P(vp), P(u64), P(u64), P(u64)]
+        L.spsp_taxonomy_files_paired.restype = i32
+        L.spsp_taxonomy_files_paired.argtypes = [vp, P(cp), u32, cp, cp, cp, u32, u32, u32, i32, cp, i32, dbl, cp, i32, P(vp), P(u64), P(u64), P(u64)]
     _lib = L
     return L
 
@@ -857,6 +871,36 @@ def taxonomy_plan(n_nodes):
     a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
     _check(lib().spsp_taxonomy_plan_host(n_nodes, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
     return {"small_hits": a.value, "lds_nodes": b.value, "counters_in_lds": bool(c.value), "list_cut": d.value}
+
+
+def union_plan():
+    """spsp_union_plan_host: the constants the union's kernels cut at -> dict(threads: the lanes of a workgroup, a lane per key;
+    tile: the entries of side B per count of the scan)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_union_plan_host(C.byref(a), C.byref(b)))
+    return {"threads": a.value, "tile": b.value}
+
+
+def pairs_names(names1, names2):
+    """spsp_pairs_names_host: the naming rule of paired records (include/spsp.h) over two lists of first words -> the common
+    names (bytes).  Lists of different lengths raise ValueError; the first pair whose names differ raises SpspError
+    (SPSP_ERR_FORMAT) with that pair's number as its .bad"""
+    if len(names1) != len(names2):
+        raise ValueError("pairs_names: one name per mate")
+    n = len(names1)
+    enc = [[x if isinstance(x, bytes) else str(x).encode() for x in names] for names in (names1, names2)]
+    a1, a2 = (C.c_char_p * max(n, 1))(*enc[0]), (C.c_char_p * max(n, 1))(*enc[1])
+    common, bad = C.c_void_p(), C.c_uint64()
+    rc = lib().spsp_pairs_names_host(a1, a2, n, C.byref(common), C.byref(bad))
+    if rc != 0:
+        try:
+            _check(rc)
+        except SpspError as e:
+            e.bad = bad.value
+            raise
+    size = sum(len(x) - (2 if x.endswith(b"/1") else 0) + 1 for x in enc[0])
+    blob = _take(common, size)
+    return bytes(blob).split(b"\0")[:n] if n else []
 
 
 def extract_plan():
@@ -1697,16 +1741,50 @@ class Context:
         _check(lib().spsp_classify_stage_ms(self._h, ms))
         return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
 
-    def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True):
+    def records_union_device(self, k, a_min, a_lo, a_hi, a_off, b_min, b_lo, b_hi, b_off):
+        """spsp_records_union_device: per record the union of two sorted key lists on the device (a_hi / b_hi: None for k <= 32;
+        a_off / b_off: n + 1 offsets each, which need not start at 0) -> (d_min, d_lo, d_hi, off): the context's arrays, valid
+        until its next union call, and np.uint64[n + 1] offsets from 0"""
+        a_off = np.ascontiguousarray(a_off, dtype=np.uint64)
+        b_off = np.ascontiguousarray(b_off, dtype=np.uint64)
+        if len(a_off) < 1 or len(a_off) != len(b_off):
+            raise ValueError("records_union_device: n + 1 offsets on either side")
+        n = len(a_off) - 1
+        off = np.zeros(n + 1, dtype=np.uint64)
+        o_mn, o_lo, o_hi = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().spsp_records_union_device(self._h, k, a_min, a_lo, a_hi, a_off.ctypes.data, b_min, b_lo, b_hi, b_off.ctypes.data, n, C.byref(o_mn),
+                                               C.byref(o_lo), C.byref(o_hi), off.ctypes.data))
+        return o_mn.value, o_lo.value, o_hi.value, off
+
+    def union_stage_ms(self):
+        """spsp_union_stage_ms: with timing_enable() on, the milliseconds of the union calls' launches since the last read ->
+        dict(flags, scan, offsets, write)"""
+        ms = (C.c_double * 4)()
+        _check(lib().spsp_union_stage_ms(self._h, ms))
+        return dict(zip(("flags", "scan", "offsets", "write"), ms))
+
+    union_plan = staticmethod(union_plan)
+    pairs_names = staticmethod(pairs_names)
+
+    def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None):
         """spsp_classify_files: the sketch files of the references and a FASTA / FASTQ file of records (gzip or plain) ->
         <prefix>_classify.csv.gz, <prefix>_classify_summary.csv.gz and (records, hits[n, top]).  rate: as compare_files (0.0, a
         rate, or "auto"); sketches of different rates need one.  extract: a word (matched, unmatched, best=<j>, listed=<j>) --
         spsp_classify_files_extract: the records it names are written to <prefix>_extract.fa or .fq (".gz" appended when gz) as
-        well; self.last_extract = dict(n_kept, bytes_out)"""
+        well; self.last_extract = dict(n_kept, bytes_out).  mates_path: the second file of paired reads -- spsp_classify_files_paired:
+        record p of the two files is one pair, classified by the keys of both mates, and extract writes <prefix>_extract_1.* and
+        <prefix>_extract_2.*"""
         arr, _alive = _paths_array(paths)
         recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
         self._cf_n_ref = None
-        if extract is not None:
+        if mates_path is not None:
+            kept, out_bytes = C.c_uint64(), C.c_uint64()
+            _check(lib().spsp_classify_files_paired(self._h, arr, len(paths), str(records_path).encode(), str(mates_path).encode(), top, min_keys, num, den,
+                                                    precision, prefix.encode(), 0, _rate_arg(rate), None if extract is None else extract.encode(),
+                                                    1 if gz else 0, C.byref(recs), C.byref(hits), C.byref(n), C.byref(kept), C.byref(out_bytes)))
+            if extract is not None:
+                self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
+        elif extract is not None:
             kept, out_bytes = C.c_uint64(), C.c_uint64()
             _check(lib().spsp_classify_files_extract(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
                                                      _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n), extract.encode(), 1 if gz else 0,
@@ -1775,16 +1853,25 @@ class Context:
         _check(lib().spsp_taxonomy_stage_ms(self._h, ms))
         return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
 
-    def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True):
+    def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None):
         """spsp_taxonomy_files: the sketch files of the references, a FASTA / FASTQ file of records (gzip or plain) and the lineage
         file of the references -> <prefix>_taxonomy.csv.gz, <prefix>_taxonomy_report.csv.gz and the records.  rate: as
         classify_files (0.0, a rate, or "auto"); sketches of different rates need one.  extract: a word (classified, unclassified,
         taxon=<t>, clade=<t>) -- spsp_taxonomy_files_extract: the records it names are written to <prefix>_extract.fa or .fq (".gz"
-        appended when gz) as well; self.last_extract = dict(n_kept, bytes_out)"""
+        appended when gz) as well; self.last_extract = dict(n_kept, bytes_out).  mates_path: as classify_files
+        (spsp_taxonomy_files_paired)"""
         arr, _alive = _paths_array(paths)
         recs, n = C.c_void_p(), C.c_uint64()
         self._cf_n_ref = None
-        if extract is not None:
+        if mates_path is not None:
+            kept, out_bytes = C.c_uint64(), C.c_uint64()
+            _check(lib().spsp_taxonomy_files_paired(self._h, arr, len(paths), str(records_path).encode(), str(mates_path).encode(), str(lineages_path).encode(),
+                                                    min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate),
+                                                    None if extract is None else extract.encode(), 1 if gz else 0, C.byref(recs), C.byref(n), C.byref(kept),
+                                                    C.byref(out_bytes)))
+            if extract is not None:
+                self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
+        elif extract is not None:
             kept, out_bytes = C.c_uint64(), C.c_uint64()
             _check(lib().spsp_taxonomy_files_extract(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
                                                      prefix.encode(), 0, _rate_arg(rate), C.byref(recs), C.byref(n), extract.encode(), 1 if gz else 0,

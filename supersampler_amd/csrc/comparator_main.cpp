@@ -123,6 +123,8 @@ int main(int argc, char** argv) {
     uint32_t gp_num = 1, gp_den = 1, gp_onum = 0, gp_oden = 1;
     string records_file;             // -X <records file> [-Y <top>] [-V <min_keys>] [-I <t>]: -X, -Y and -V are not in the reference's option string
     bool classify = false;
+    string mates_file;               // -x <mates file>: with -X, record p of the two files is one pair (not in the reference's option string)
+    bool paired = false;
     int cf_opts = 0;                 // -Y or -V seen
     long long cf_top = 1, cf_min_keys = 1;
     string lineages_file;            // -H <lineages file>: with -X, the records go to the lowest common ancestor of their keys (not in the reference's option string)
@@ -134,7 +136,7 @@ int main(int argc, char** argv) {
     long long dp_min_count = 1;
     bool profile = false;            // -B <min_keys>: the profile behind the depth of -D (not in the reference's option string either)
     long long pf_min_keys = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:u")) != -1) {
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:")) != -1) {
         switch (ch) {
             case 'D': reads_files.push_back(optarg); break;
             case 'W': {
@@ -153,6 +155,7 @@ int main(int argc, char** argv) {
             }
             case 'G': labels_file = optarg; groups = true; break;
             case 'X': records_file = optarg; classify = true; break;
+            case 'x': mates_file = optarg; paired = true; break;
             case 'H': lineages_file = optarg; taxonomy = true; break;
             case 'F': extract_what = optarg; extract = true; break;
             case 'u': extract_plain = true; break;
@@ -292,6 +295,7 @@ int main(int argc, char** argv) {
     if (nb_opts > 1) { cout << "-J (Jaccard), -K (the larger containment) and -I (the row's containment) set the threshold of -N: one of them, once" << endl; return 1; }
     if (taxonomy && !classify) { cout << "-H gives the lineages of the index for the records of -X <records file>: it needs -X" << endl; return 1; }
     if (taxonomy && cf_top_seen) { cout << "-H assigns every record to one node of the tree: not together with -Y (-V and -I set its threshold)" << endl; return 1; }
+    if (paired && !classify) { cout << "-x gives the mates of the records of -X <records file>, pair by pair: it needs -X" << endl; return 1; }
     if (extract && !classify) { cout << "-F names the records of -X <records file> to write out again: it needs -X" << endl; return 1; }
     if (extract_plain && !extract) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
     if (extract && spsp_extract_word_check_host(extract_what.c_str(), taxonomy ? 1 : 0, 0xffffffffu) != SPSP_OK) { cout << "-F: " << spsp_last_error() << endl; return 1; }
@@ -352,6 +356,7 @@ int main(int argc, char** argv) {
              << "-H Lineage file, one name;name;... line per index sketch: with -X <records file>, each record goes to the lowest common ancestor of its keys" << endl
              << "-F Records of -X <records file> to write out again as <prefix>_extract.fa.gz / .fq.gz: matched, unmatched, best=<j>, listed=<j>; with -H: classified, unclassified, taxon=<t>, clade=<t>" << endl
              << "-u Write the records of -F plain, not gzipped" << endl
+             << "-x Mates file: with -X <records file>, record p of the two files is one pair, classified by the keys of both mates; -F then writes <prefix>_extract_1.* and <prefix>_extract_2.*" << endl
              << "Ouput arguments:" << endl
              << "-m Minimum value to be output (0.0)" << endl
              << "-p Required precision to be output in the CSV (6)" << endl
@@ -418,7 +423,15 @@ int main(int argc, char** argv) {
         // one device, as gather (the driver opens a second context on it for the records)
         spsp_ctx* ctx = nullptr;
         int rc = spsp_create(devices[0], nullptr, &ctx);
-        if (rc == SPSP_OK && taxonomy && extract)
+        if (rc == SPSP_OK && paired && taxonomy)
+            rc = spsp_taxonomy_files_paired(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), mates_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys,
+                                            nb_num, nb_den, (int)p, output_name.c_str(), 1, rate, extract ? extract_what.c_str() : nullptr, extract_plain ? 0 : 1, nullptr,
+                                            nullptr, nullptr, nullptr);
+        else if (rc == SPSP_OK && paired)
+            rc = spsp_classify_files_paired(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), mates_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys,
+                                            nb_num, nb_den, (int)p, output_name.c_str(), 1, rate, extract ? extract_what.c_str() : nullptr, extract_plain ? 0 : 1, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr);
+        else if (rc == SPSP_OK && taxonomy && extract)
             rc = spsp_taxonomy_files_extract(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den,
                                              (int)p, output_name.c_str(), 1, rate, nullptr, nullptr, extract_what.c_str(), extract_plain ? 0 : 1, nullptr, nullptr);
         else if (rc == SPSP_OK && taxonomy)

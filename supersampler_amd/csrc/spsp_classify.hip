@@ -543,10 +543,125 @@ int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
     return SPSP_OK;
 }
 
+// One mate's text of the paired form on its side context: what records_text_batches does with its one text, cut where the pair
+// needs its two sides in step -- open (the ingest and the scan, once), seams (every batch's stretch of the stream), and the key
+// extraction of a batch queued (keys_begin) and collected (keys_end), so that the two sides' extractions overlap on their streams
+struct MateSide {
+    spsp_ctx* side = nullptr;
+    spsp_params ps{};
+    uint8_t* d_bases = nullptr;
+    uint64_t* d_off = nullptr;
+    uint64_t n_bases = 0, n_sk = 0;
+    uint32_t n_rec = 0;
+    spsp_superkmer* d_sk = nullptr;
+    std::vector<uint64_t> rec_off, seam, key_off;
+    std::vector<uint32_t> first_rec;
+
+    int open(spsp_ctx* ctx, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path, size_t n_names) {
+        int rc;
+        double t0 = now_s(), t1;
+        const bool fastq = n_text && text[0] == '@';
+        if ((rc = side->i_text.reserve((size_t)n_text + 64))) return rc;
+        if (n_text) SPSP_HIP(hipMemcpyAsync(side->i_text.p, text, (size_t)n_text, hipMemcpyHostToDevice, side->stream));
+        const bool packed = ingest_packs(p);
+        FastqLayout fq;
+        if (fastq) fastq_tail(text, n_text, &fq.content_end, &fq.blank_tail);
+        if ((rc = clean_device_impl(side, side->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed, fastq ? &fq : nullptr))) return rc;
+        t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
+        if (n_names != n_rec) {
+            set_error("'%s': %zu header line(s) on the host, %u record(s) on the device", path, n_names, n_rec);
+            return SPSP_ERR_FORMAT;
+        }
+        ps = *p;
+        if (packed) ps.flags |= SPSP_SCAN_PACKED_INPUT;
+        if ((rc = scan_device_impl(side, &ps, d_bases, n_bases, d_off, n_rec, &d_sk, &n_sk))) return rc;
+        t1 = now_s(); ctx->stages.scan_s += t1 - t0;
+        rec_off.assign((size_t)n_rec + 1, 0);
+        SPSP_HIP(hipMemcpyAsync(rec_off.data(), d_off, rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));
+        SPSP_HIP(hipStreamSynchronize(side->stream));
+        return SPSP_OK;
+    }
+    int keys_begin(uint32_t r0, uint32_t batch, uint64_t q0, uint64_t q1) {
+        first_rec.resize((size_t)batch + 1);
+        for (uint32_t g = 0; g <= batch; ++g) first_rec[g] = r0 + g;
+        key_off.assign((size_t)batch + 1, 0);
+        return spsp_sketch_keys_device_begin(side, &ps, d_bases, n_bases, d_off, d_sk + q0, q1 - q0, first_rec.data(), batch, 0);
+    }
+};
+
+// The paired form of records_text_batches: record p of `text[0]` and record p of `text[1]` are the two mates of pair p (the rule:
+// include/spsp.h, "paired records").  The record counts and the names are held against each other in front of everything else;
+// *names receives the pairs' common names.  Each text is ingested and scanned once on its own side context; per batch of at most
+// 65 535 pairs the two key extractions are queued on the two sides' streams, their union is made on ctx, and on_batch gets the
+// union's arrays as it gets a batch's keys in the unpaired form.  on_records: the pairs' summed base offsets.  extract: null, or
+// one run per mate (extract[1]->flags is not used: both texts are cut by the flags extract[0] makes from the pairs' rows)
+int records_pair_batches(spsp_ctx* ctx, spsp_ctx* const* side, const spsp_params* p, const uint8_t* const* text, const uint64_t* n_text, const char* const* path,
+                         std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
+                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* const* extract) {
+    int rc;
+    std::vector<std::string> mate_names[2];
+    for (int s = 0; s < 2; ++s) record_names_host(text[s], n_text[s], n_text[s] && text[s][0] == '@', &mate_names[s]);
+    if (mate_names[0].size() != mate_names[1].size()) {
+        set_error("paired files must hold as many records: '%s' has %zu, '%s' has %zu", path[0], mate_names[0].size(), path[1], mate_names[1].size());
+        return SPSP_ERR_FORMAT;
+    }
+    {
+        const size_t n = mate_names[0].size();
+        std::vector<const char*> p1(n), p2(n);
+        for (size_t r = 0; r < n; ++r) { p1[r] = mate_names[0][r].c_str(); p2[r] = mate_names[1][r].c_str(); }
+        char* common = nullptr; uint64_t bad = 0;
+        if ((rc = spsp_pairs_names_host(p1.data(), p2.data(), n, &common, &bad))) return rc;
+        names->clear();
+        for (size_t r = 0, at = 0; r < n; ++r) { names->emplace_back(common + at); at += names->back().size() + 1; }
+        spsp_free(common);
+    }
+    MateSide M[2];
+    for (int s = 0; s < 2; ++s) {
+        M[s].side = side[s];
+        if ((rc = M[s].open(ctx, p, text[s], n_text[s], path[s], mate_names[s].size()))) return rc;
+    }
+    const uint32_t n_rec = M[0].n_rec;
+    std::vector<uint64_t> sum_off((size_t)n_rec + 1);
+    for (uint32_t r = 0; r <= n_rec; ++r) sum_off[r] = M[0].rec_off[r] + M[1].rec_off[r];
+    if ((rc = on_records(n_rec, sum_off.data()))) return rc;
+    std::vector<uint32_t> bounds;
+    for (uint64_t r = 0; r < n_rec; r += 65535u) bounds.push_back((uint32_t)r);
+    bounds.push_back(n_rec);
+    for (int s = 0; s < 2; ++s)
+        if (n_rec && (rc = batch_seams(side[s], M[s].d_sk, M[s].n_sk, bounds, &M[s].seam))) return rc;
+    std::vector<uint64_t> key_off;
+    for (size_t b = 0; b + 1 < bounds.size(); ++b) {
+        const uint32_t r0 = bounds[b], batch = bounds[b + 1] - r0;
+        key_off.assign((size_t)batch + 1, 0);
+        void* km[2][3] = {};
+        for (int s = 0; s < 2; ++s)                        // (the last batch's union has read this side's keys)
+            if ((rc = spsp_wait_stream(side[s], ctx)) || (rc = M[s].keys_begin(r0, batch, M[s].seam[b], M[s].seam[b + 1]))) return rc;
+        for (int s = 0; s < 2; ++s)
+            if ((rc = spsp_sketch_keys_device_end(side[s], &km[s][0], &km[s][1], &km[s][2], M[s].key_off.data())) || (rc = spsp_wait_stream(ctx, side[s]))) return rc;
+        uint32_t* u_mn = nullptr;
+        uint64_t *u_lo = nullptr, *u_hi = nullptr;
+        if ((rc = records_union_impl(ctx, p->k, (const uint32_t*)km[0][0], (const uint64_t*)km[0][1], (const uint64_t*)km[0][2], M[0].key_off.data(),
+                                     (const uint32_t*)km[1][0], (const uint64_t*)km[1][1], (const uint64_t*)km[1][2], M[1].key_off.data(), batch, &u_mn, &u_lo,
+                                     &u_hi, key_off.data())) ||
+            (rc = on_batch(RecordBatch{r0, batch, u_mn, u_lo, u_hi, key_off.data()}))) return rc;
+    }
+    if (extract) {
+        // (one flag vector: extract[0] makes it from the pairs' rows, and each text is cut by it where it still sits)
+        std::vector<uint8_t> keep(n_rec ? n_rec : 1, 0);
+        if ((rc = extract[0]->flags(n_rec, keep.data()))) return rc;
+        for (int s = 0; s < 2; ++s) {
+            extract[s]->flags = [keep](uint32_t n, uint8_t* out) { memcpy(out, keep.data(), n); return (int)SPSP_OK; };
+            if ((rc = extract[s]->on_text(side[s], side[s]->i_text.as<uint8_t>(), n_text[s], n_rec))) return rc;
+        }
+    }
+    return SPSP_OK;
+}
+
 // the road of the four record file drivers: load, refusals, decode, index, on_index, every records file through its batches, on_close
 int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
                        const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1, ExtractRun* extract) {
+                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1, ExtractRun* extract,
+                       const char* mates_path, ExtractRun* extract_mates) {
     spsp_ctx* ctx = run.ctx;
     int rc = run.load(rate);
     if (!rc) rc = run.refuse_k_eq_m(rc, what_is);
@@ -561,25 +676,49 @@ int records_files_road(FilesRun& run, const char* what_is, const char* const* re
         spsp_ctx* side = nullptr;
         spsp_params p{};
         p.k = keys.k; p.m = keys.m; p.threshold = spsp_threshold_host(keys.k, keys.m, rec_rate); p.abundance = 1; p.flags = 0;
-        for (uint32_t f = 0; !rc && f < n_records_paths; ++f) {
+        for (uint32_t f = 0; !rc && !mates_path && f < n_records_paths; ++f) {
             uint8_t* text = nullptr; uint64_t n_text = 0;
             if (!(rc = spsp_read_file_host(records_paths[f], &text, &n_text)) && (side || !(rc = spsp_create(ctx->device, nullptr, &side))) &&
                 !(rc = spsp_wait_stream(side, ctx)))       // (the last file's keys have been read)
                 rc = records_text_batches(ctx, side, &p, text, n_text, records_paths[f], names, on_records, on_batch, extract);
             spsp_free(text);
         }
+        spsp_ctx* side2 = nullptr;
+        if (!rc && mates_path) {                           // the paired form: records_paths[0] and mates_path on a side context each
+            const char* path[2] = {records_paths[0], mates_path};
+            uint8_t* text[2] = {nullptr, nullptr}; uint64_t n_text[2] = {0, 0};
+            ExtractRun* ex[2] = {extract, extract_mates};
+            if (!(rc = spsp_read_file_host(path[0], &text[0], &n_text[0])) && !(rc = spsp_read_file_host(path[1], &text[1], &n_text[1])) &&
+                !(rc = spsp_create(ctx->device, nullptr, &side)) && !(rc = spsp_create(ctx->device, nullptr, &side2))) {
+                spsp_ctx* sides[2] = {side, side2};
+                rc = records_pair_batches(ctx, sides, &p, text, n_text, path, names, on_records, on_batch, extract ? ex : nullptr);
+            }
+            spsp_free(text[0]); spsp_free(text[1]);
+        }
         if (!rc) rc = on_close();
         (void)hipStreamSynchronize(ctx->stream);           // (what on_batch queued reads the side context's key arrays)
         if (side) { (void)hipStreamSynchronize(side->stream); spsp_destroy(side); }
+        if (side2) { (void)hipStreamSynchronize(side2->stream); spsp_destroy(side2); }
     }
     *t1 = run.end();
     return rc;
 }
 
-// spsp_classify_files behind its argument checks
+int extract_write(spsp_ctx* ctx, ExtractRun* extract, ExtractRun* extract_mates, const char* out_prefix, int chatter) {
+    if (!extract_mates) return extract->write(ctx, out_prefix, chatter);
+    int rc;
+    if ((rc = extract->write(ctx, out_prefix, 0)) || (rc = extract_mates->write(ctx, out_prefix, 0)) || !chatter) return rc;
+    printf("extract %s: %llu of %llu pair(s) kept, %llu + %llu byte(s) written to %s_extract_1 and _extract_2\n", extract->what,
+           (unsigned long long)extract->n_kept, (unsigned long long)extract->n_rec, (unsigned long long)extract->out.size(),
+           (unsigned long long)extract_mates->out.size(), out_prefix);
+    fflush(stdout);
+    return SPSP_OK;
+}
+
+// spsp_classify_files behind its argument checks (mates_path: null, or the paired form with extract_mates beside extract)
 static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys, uint32_t num,
                           uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_classify_record>* recs,
-                          std::vector<spsp_classify_hit>* hits, ExtractRun* extract) {
+                          std::vector<spsp_classify_hit>* hits, ExtractRun* extract, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr) {
     FilesRun run(ctx, paths, n_ref, chatter);
     std::vector<std::string> names;
     double t1 = 0;
@@ -599,7 +738,7 @@ static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
             return classify_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, top, min_keys, num, den, recs->data() + B.first_record,
                                         hits->data() + (size_t)B.first_record * top);
         },
-        [] { return SPSP_OK; }, &t1, extract);
+        [] { return SPSP_OK; }, &t1, extract, mates_path, extract_mates);
     if (rc) return rc;
     std::vector<const char*> name_ptr(names.size());
     for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
@@ -608,11 +747,12 @@ static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
     if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify.csv.gz", t1))) return rc;
     const double t2 = now_s();
     if ((rc = spsp_classify_summary_csv_host(recs->data(), hits->data(), recs->size(), paths, n_ref, top, &text, &len))) return rc;
-    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify_summary.csv.gz", t2)) || (extract && (rc = extract->write(ctx, out_prefix, chatter))) || !chatter)
+    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify_summary.csv.gz", t2)) || (extract && (rc = extract_write(ctx, extract, extract_mates, out_prefix, chatter))) ||
+        !chatter)
         return rc;
     uint64_t with = 0;
     for (const spsp_classify_record& r : *recs) with += r.listed != 0;
-    printf("%zu record(s) against %u reference(s): %llu with a match\n", recs->size(), n_ref, (unsigned long long)with);
+    printf(mates_path ? "%zu pair(s) against %u reference(s): %llu with a match\n" : "%zu record(s) against %u reference(s): %llu with a match\n", recs->size(), n_ref, (unsigned long long)with);
     say_common_rate(run.L, n_ref);
     fflush(stdout);
     return SPSP_OK;
@@ -638,16 +778,18 @@ extern "C" int spsp_classify_device(spsp_ctx* ctx, const void* d_q_minimizer, co
                                 min_keys, num, den, records, hits);
 }
 
-// spsp_classify_files and spsp_classify_files_extract (what == nullptr: no extraction)
+// spsp_classify_files, spsp_classify_files_extract and spsp_classify_files_paired (what == nullptr: no extraction; mates_path ==
+// nullptr: one records file; paired: the entry is the paired one, which mates_path must not be missing from)
 static int classify_files_entry(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
                                 uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, spsp_classify_record** records,
-                                spsp_classify_hit** hits, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out) {
+                                spsp_classify_hit** hits, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out,
+                                bool paired = false, const char* mates_path = nullptr) {
     if (records) *records = nullptr;
     if (hits) *hits = nullptr;
     if (n_records) *n_records = 0;
     if (n_kept) *n_kept = 0;
     if (bytes_out) *bytes_out = 0;
-    if (!ctx || !index_paths || !records_path || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (!ctx || !index_paths || !records_path || !out_prefix || (paired && !mates_path)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
     if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
     int rc;
     if ((rc = classify_check_args(top, min_keys, num, den))) return rc;
@@ -655,12 +797,13 @@ static int classify_files_entry(spsp_ctx* ctx, const char* const* index_paths, u
     SPSP_HIP(hipSetDevice(ctx->device));
     std::vector<spsp_classify_record> got;
     std::vector<spsp_classify_hit> got_hits;
-    ExtractRun extract;
-    extract.what = what; extract.gz = gz;
+    ExtractRun extract, extract_mates;
+    extract.what = extract_mates.what = what; extract.gz = extract_mates.gz = gz;
+    if (mates_path) { extract.tag = "_1"; extract_mates.tag = "_2"; }
     if ((rc = classify_files(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, &got, &got_hits,
-                             what ? &extract : nullptr))) return rc;
+                             what ? &extract : nullptr, mates_path, what && mates_path ? &extract_mates : nullptr))) return rc;
     if (n_kept) *n_kept = extract.n_kept;
-    if (bytes_out) *bytes_out = extract.out.size();
+    if (bytes_out) *bytes_out = extract.out.size() + extract_mates.out.size();
     if (n_records) *n_records = got.size();
     if (records && (rc = give_rows(got, records))) return rc;
     if (hits && (rc = give_rows(got_hits, hits))) { if (records) { free(*records); *records = nullptr; } return rc; }
@@ -681,6 +824,14 @@ extern "C" int spsp_classify_files_extract(spsp_ctx* ctx, const char* const* ind
     if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
     return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
                                 what, gz, n_kept, bytes_out);
+}
+
+extern "C" int spsp_classify_files_paired(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
+                                          uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter,
+                                          double rate, const char* what, int gz, spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records,
+                                          uint64_t* n_kept, uint64_t* bytes_out) {
+    return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
+                                what, gz, n_kept, bytes_out, true, mates_path);
 }
 
 extern "C" int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms) {

@@ -545,7 +545,7 @@ int ExtractRun::on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, 
 }
 
 int ExtractRun::write(spsp_ctx* ctx, const char* out_prefix, int chatter) {
-    const std::string path = std::string(out_prefix) + (fastq ? "_extract.fq" : "_extract.fa") + (gz ? ".gz" : "");
+    const std::string path = std::string(out_prefix) + "_extract" + tag + (fastq ? ".fq" : ".fa") + (gz ? ".gz" : "");
     const double t = now_s();
     int rc = SPSP_OK;
     if (gz) rc = spsp_write_gz_host(path.c_str(), out.data(), out.size(), 1);

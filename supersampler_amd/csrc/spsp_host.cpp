@@ -2906,6 +2906,39 @@ extern "C" int spsp_extract_plan_host(uint32_t* tile_bytes, uint32_t* stretch_by
     return SPSP_OK;
 }
 
+extern "C" int spsp_union_plan_host(uint32_t* threads, uint32_t* tile) {
+    if (threads) *threads = spsp::kUnThreads;
+    if (tile) *tile = spsp::kUnTile;
+    return SPSP_OK;
+}
+
+// the naming rule of paired records (include/spsp.h): mate 1's word less one trailing "/1" against mate 2's less one trailing "/2"
+extern "C" int spsp_pairs_names_host(const char* const* names1, const char* const* names2, uint64_t n, char** common, uint64_t* bad) {
+    using namespace spsp;
+    if (common) *common = nullptr;
+    if (bad) *bad = n;
+    if (!bad || (n && (!names1 || !names2))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    std::string blob;
+    for (uint64_t p = 0; p < n; ++p) {
+        if (!names1[p] || !names2[p]) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+        size_t l1 = strlen(names1[p]), l2 = strlen(names2[p]);
+        if (l1 >= 2 && names1[p][l1 - 2] == '/' && names1[p][l1 - 1] == '1') l1 -= 2;
+        if (l2 >= 2 && names2[p][l2 - 2] == '/' && names2[p][l2 - 1] == '2') l2 -= 2;
+        if (l1 != l2 || memcmp(names1[p], names2[p], l1) != 0) {
+            *bad = p;
+            set_error("pair %llu: the mates' names differ ('%.200s' and '%.200s'): are the two files in step?", (unsigned long long)p, names1[p], names2[p]);
+            return SPSP_ERR_FORMAT;
+        }
+        if (common) { blob.append(names1[p], l1); blob.push_back('\0'); }
+    }
+    if (common) {
+        *common = (char*)malloc(blob.size() ? blob.size() : 1);
+        if (!*common) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+        memcpy(*common, blob.data(), blob.size());
+    }
+    return SPSP_OK;
+}
+
 extern "C" int spsp_records_extents_host(const uint8_t* text, uint64_t n, uint64_t** begin, uint32_t* n_rec) {
     using namespace spsp;
     if (begin) *begin = nullptr;

@@ -152,7 +152,10 @@ enum HostSlot {
                             // the table or a list place out of range << 32) behind the index call's wait; behind a classify call's one
                             // wait the copy of its own word (u32: a record routed to a form its work does not fit)
                             // -- and behind a taxonomy call's one wait (spsp_taxonomy.hip) the copy of that call's word, the same way
-    kHostSlots = 38
+    kHsUnBad = 38,          // spsp_union.hip: the copy of k_un_flag's word (u64: ~0, or the least side << 32 | record whose keys do not
+                            // ascend strictly); records_union_impl reads it behind its one wait
+    kHsUnNew = 39,          // ... and launch_scan_u32's total over the tiles' counts: the keys of B that A does not hold (u64), in the same wait
+    kHostSlots = 40
 };
 constexpr int kIngestTotals = 2;
 static_assert(kHsIngestKept + kIngestTotals <= kHsScanTotalA, "the ingest totals end in front of the scan totals");
@@ -163,7 +166,7 @@ static_assert(kHsTrRounds == kHsTrEdges + 2 && kHsTrRounds + 1 == kHsSelBad, "th
 static_assert(kHsSelTotal == kHsSelBad + 1 && kHsSelTotal + 1 == kHsAcBad, "the selection's two slots");
 static_assert(kHsAcBad + 1 == kHsGpBad, "the accumulation's one slot");
 static_assert(kHsGpCell == kHsGpBad + 1 && kHsGpTotal == kHsGpBad + 2 && kHsGpTotal + 1 == kHsCfBad, "the groups pass's three slots");
-static_assert(kHsCfBad + 1 == kHostSlots, "the classification's one slot: the last one");
+static_assert(kHsCfBad + 1 == kHsUnBad && kHsUnNew == kHsUnBad + 1 && kHsUnNew + 1 == kHostSlots, "the classification's one slot, then the union's two: the last ones");
 // ctx->c_flags (spsp_compare.hip names its words): the two words behind those a comparison's kernels use hold the cell count (u64)
 // of a comparison returned as cells (spsp_multi.hip)
 constexpr uint32_t kCfCellCount = 14;
@@ -351,6 +354,10 @@ struct spsp_ctx {
     hipEvent_t ex_ev[4] = {};            // while timing is on: in front of the starts, the offsets, the copy, and behind it
     uint32_t ex_marked = 0;              // ... which of them the call in flight has recorded
     double ex_ms[3] = {};                // their milliseconds since spsp_extract_stage_ms last read them: starts, offsets, copy
+    // union of two record batches (spsp_union.hip): the output arrays, and the work area (the flag word, the three offset arrays,
+    // a place in A per entry of B, the "new" ballot words of B's entries, the tiles' counts and their scan)
+    spsp::DevBuf un_mn, un_lo, un_hi, un_work;
+    spsp::RecordClock un_clock;          // spsp_union_stage_ms: flag, scan, offsets, write
 };
 
 namespace spsp {
@@ -552,9 +559,11 @@ struct RecordBatch { uint32_t first_record, n_records; const uint32_t* mn; const
 // what a record file driver writes beside its CSVs when it is asked to (spsp_extract.hip).  on_text is the road's hook: behind a
 // file's last batch, with the text still in the side context's buffer, it has `flags` (the driver's: its rows -> keep[n_rec]) make
 // the flags, runs the extraction on `side` and brings the kept bytes to `out`.  write: <out_prefix>_extract.fa or .fq (by the
-// text's kind), gzip level 1 with ".gz" appended when gz, and with chatter the line of what was kept
+// text's kind), gzip level 1 with ".gz" appended when gz, and with chatter the line of what was kept.  tag: "" for a records file
+// alone; "_1" and "_2" for the two mates of the paired form, whose files are <out_prefix>_extract_1.* and <out_prefix>_extract_2.*
 struct ExtractRun {
     const char* what = nullptr;
+    const char* tag = "";
     int gz = 1;
     std::function<int(uint32_t, uint8_t*)> flags;
     bool fastq = false;
@@ -566,6 +575,14 @@ struct ExtractRun {
 int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
                          std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
                          const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract = nullptr);
+// the paired form (spsp_classify.hip): text[0] and text[1] hold the two mates of every pair, on a side context each; the union of
+// the two mates' keys per pair (spsp_union.hip) is what on_batch gets.  extract: null, or the two mates' runs
+int records_pair_batches(spsp_ctx* ctx, spsp_ctx* const* side, const spsp_params* p, const uint8_t* const* text, const uint64_t* n_text, const char* const* path,
+                         std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
+                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* const* extract);
+// what a driver writes for its extraction: the one file of extract->write, or, with the mates' run, the two files of a paired run
+// and one line for both
+int extract_write(spsp_ctx* ctx, ExtractRun* extract, ExtractRun* extract_mates, const char* out_prefix, int chatter);
 // spsp_depth.hip: how many records hold each key of the index, and the per-reference statistics over those counts
 constexpr uint32_t kDpThreads = 256;                       // every depth kernel: 4 waves
 constexpr uint32_t kDpBins = 4096;                         // bins of one LDS histogram of k_dp_reduce: the last holds every count at or above kDpBins - 1
@@ -634,12 +651,13 @@ int classify_probe_launch(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q
 // "classification is", "depth is"), one record rate, the decoding and the index, on_index behind it, then every records file read
 // and sent through records_text_batches on ONE second context (spsp_wait_stream(side, ctx) in front of every file: the last
 // file's keys have been read), on_close where all of that went well, the wait for ctx's stream and the second context's end;
-// *t1 = run.end().  names: null, or the records' names (one records file then)
+// *t1 = run.end().  names: null, or the records' names (one records file then).  mates_path: null, or the second file of a paired
+// run -- records_paths[0] and it go through records_pair_batches on two side contexts instead, with extract_mates beside extract
 struct FilesRun;
 int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
                        const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
                        const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1,
-                       ExtractRun* extract = nullptr);
+                       ExtractRun* extract = nullptr, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr);
 int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den);
 int taxonomy_index_impl(spsp_ctx* ctx, const uint32_t* parent, uint32_t T, const uint32_t* ref_node, uint32_t n_ref, const uint32_t** key_nodes_out);
 int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
@@ -654,6 +672,14 @@ int records_extents_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, 
 // here, for n_rec records -- a text that holds another number is SPSP_ERR_ARG behind the wait, nothing having left the buffers
 int records_extract_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const uint64_t* d_begin, uint32_t n_rec, const uint8_t* h_keep,
                          uint8_t** d_out, uint64_t* n_out, uint64_t* n_kept, bool* fastq);
+// spsp_union.hip: per record the union of two sorted key lists (the rule: include/spsp.h, "paired records").  What the kernels cut
+// at (spsp_union_plan_host, spsp_host.cpp):
+constexpr uint32_t kUnThreads = 256;                       // every union kernel: 4 waves, a lane per key
+constexpr uint32_t kUnTile = 256;                          // entries of B per count of the scan: one workgroup's, four ballot words
+// the arrays are the context's (valid until its next union call); h_off: n_rec + 1, from 0.  One host wait
+int records_union_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* a_mn, const uint64_t* a_lo, const uint64_t* a_hi, const uint64_t* h_a_off, const uint32_t* b_mn,
+                       const uint64_t* b_lo, const uint64_t* b_hi, const uint64_t* h_b_off, uint32_t n_rec, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi,
+                       uint64_t* h_off);
 // spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
 // groups as n_groups sketches back to back in context-owned arrays
 int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,

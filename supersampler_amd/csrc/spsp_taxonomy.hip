@@ -395,7 +395,7 @@ int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
 // spsp_taxonomy_files behind its argument checks
 static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, const char* lineages_path, uint32_t min_keys,
                           uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_taxonomy_record>* recs,
-                          ExtractRun* extract) {
+                          ExtractRun* extract, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr) {
     int rc;
     // the lineage file first: a tree that cannot be read costs no loading
     uint8_t* lin = nullptr; uint64_t n_lin = 0;
@@ -424,7 +424,7 @@ static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
             return SPSP_OK;
         },
         [&](const RecordBatch& B) { return taxonomy_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, min_keys, num, den, recs->data() + B.first_record); },
-        [] { return SPSP_OK; }, &t1, extract);
+        [] { return SPSP_OK; }, &t1, extract, mates_path, extract_mates);
     char *text = nullptr, *report = nullptr; uint64_t len = 0, report_len = 0;
     if (!rc) {
         std::vector<const char*> name_ptr(names.size());
@@ -438,12 +438,13 @@ static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
         text = nullptr;
         const double t2 = now_s();
         if (!rc) { rc = write_csv_gz(ctx, report, report_len, out_prefix, "_taxonomy_report.csv.gz", t2); report = nullptr; }
-        if (!rc && extract) rc = extract->write(ctx, out_prefix, chatter);
+        if (!rc && extract) rc = extract_write(ctx, extract, extract_mates, out_prefix, chatter);
     }
     if (!rc && chatter) {
         uint64_t called = 0, at_root = 0;
         for (const spsp_taxonomy_record& r : *recs) { called += r.node != kTxNone; at_root += r.node == 0u; }
-        printf("%zu record(s) against %u reference(s) at %u node(s): %llu classified, %.3g of them at depth 0\n", recs->size(), n_ref, T, (unsigned long long)called,
+        printf(mates_path ? "%zu pair(s) against %u reference(s) at %u node(s): %llu classified, %.3g of them at depth 0\n"
+                          : "%zu record(s) against %u reference(s) at %u node(s): %llu classified, %.3g of them at depth 0\n", recs->size(), n_ref, T, (unsigned long long)called,
                called ? (double)at_root / (double)called : 0.0);
         say_common_rate(run.L, n_ref);
         fflush(stdout);
@@ -476,27 +477,30 @@ extern "C" int spsp_taxonomy_device(spsp_ctx* ctx, const void* d_q_minimizer, co
                                 num, den, records);
 }
 
-// spsp_taxonomy_files and spsp_taxonomy_files_extract (what == nullptr: no extraction)
+// spsp_taxonomy_files, spsp_taxonomy_files_extract and spsp_taxonomy_files_paired (what == nullptr: no extraction; mates_path ==
+// nullptr: one records file; paired: the entry is the paired one, which mates_path must not be missing from)
 static int taxonomy_files_entry(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
                                 uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
-                                spsp_taxonomy_record** records, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out) {
+                                spsp_taxonomy_record** records, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out,
+                                bool paired = false, const char* mates_path = nullptr) {
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
     if (n_kept) *n_kept = 0;
     if (bytes_out) *bytes_out = 0;
-    if (!ctx || !index_paths || !records_path || !lineages_path || !out_prefix) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (!ctx || !index_paths || !records_path || !lineages_path || !out_prefix || (paired && !mates_path)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
     if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
     int rc;
     if ((rc = taxonomy_check_args(min_keys, num, den))) return rc;
     if (what && (rc = spsp_extract_word_check_host(what, 1, 0xffffffffu))) return rc;   // (the word, before any file is read; its node once the tree is)
     SPSP_HIP(hipSetDevice(ctx->device));
     std::vector<spsp_taxonomy_record> got;
-    ExtractRun extract;
-    extract.what = what; extract.gz = gz;
+    ExtractRun extract, extract_mates;
+    extract.what = extract_mates.what = what; extract.gz = extract_mates.gz = gz;
+    if (mates_path) { extract.tag = "_1"; extract_mates.tag = "_2"; }
     if ((rc = taxonomy_files(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, &got,
-                             what ? &extract : nullptr))) return rc;
+                             what ? &extract : nullptr, mates_path, what && mates_path ? &extract_mates : nullptr))) return rc;
     if (n_kept) *n_kept = extract.n_kept;
-    if (bytes_out) *bytes_out = extract.out.size();
+    if (bytes_out) *bytes_out = extract.out.size() + extract_mates.out.size();
     if (n_records) *n_records = got.size();
     if (records && (rc = give_rows(got, records))) return rc;
     return SPSP_OK;
@@ -516,6 +520,14 @@ extern "C" int spsp_taxonomy_files_extract(spsp_ctx* ctx, const char* const* ind
     if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
     return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
                                 what, gz, n_kept, bytes_out);
+}
+
+extern "C" int spsp_taxonomy_files_paired(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
+                                          const char* lineages_path, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix,
+                                          int chatter, double rate, const char* what, int gz, spsp_taxonomy_record** records, uint64_t* n_records,
+                                          uint64_t* n_kept, uint64_t* bytes_out) {
+    return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
+                                what, gz, n_kept, bytes_out, true, mates_path);
 }
 
 extern "C" int spsp_taxonomy_stage_ms(spsp_ctx* ctx, double* ms) {
