@@ -1534,6 +1534,88 @@ int spsp_taxonomy_files_paired(spsp_ctx* ctx, const char* const* index_paths, ui
                                double rate, const char* what /* NULL: no extraction */, int gz, spsp_taxonomy_record** records /* may be NULL; spsp_free */,
                                uint64_t* n_records /* may be NULL */, uint64_t* n_kept, uint64_t* bytes_out);
 
+/* --------------------------------------------------------------- split ---- */
+/* Every record written to the file of its reference or taxon, all files in one pass (not in the reference): binning a read set or
+ * the contigs of an assembly, which the extraction does one subset -- and one run -- at a time.
+ * RECORDS.  The text's kind, the records and begin[0 .. n_rec] are exactly what the extract section defines.
+ * BINS.  bin[r] is one uint32 per record.  SPSP_SPLIT_DROP: the record is not written.  Every other value must be < n_bins, else
+ * SPSP_ERR_ARG naming the first such record.  1 <= n_bins <= SPSP_SPLIT_MAX_BINS = 2^24 (a tree has at most 1 048 576 nodes and a
+ * list 65 535 references, so either count + 1 fits); another n_bins is SPSP_ERR_ARG.
+ * OUTPUT.  The slices of bin 0, 1, ..., n_bins - 1 follow one another.  Within a bin the byte ranges of its records come verbatim
+ * and in record order: the split is stable.  The extract section's one exception holds: a range that is not empty and whose last
+ * byte is not '\n' gets one '\n' appended, and only the text's last range can be such a range -- but that range can now land
+ * anywhere in the output, and its bin is one byte longer than its source bytes.  bin_off[0 .. n_bins] are the bins' byte offsets
+ * in the output, from 0; an empty bin repeats the offset; bin_off[n_bins] = n_out.  bin_records[b] = the records with bin[r] == b,
+ * empty ranges included (as n_kept counts flagged records).  With a caller's own begin[] only the last range is looked at for the
+ * newline, as in extract.  So every bin's slice is a well-formed file.
+ * WHICH BIN.  A word `what` and the rows of a pass make the bins, on the host, in integers only.
+ *   classify rows:  best: n_bins = n_ref + 1; bin = the rank-1 match's list position; a record with listed == 0 goes to bin n_ref,
+ *                   "unmatched".
+ *   taxonomy rows:  taxon: n_bins = n_nodes + 1; bin = node; SPSP_TAXONOMY_NONE goes to bin n_nodes, "unclassified".
+ *                   depth=<d>, 1 <= d <= 32 in decimal digits (the depths spsp_taxonomy_lineages_host hands out and the taxonomy
+ *                   CSV prints): a record whose node lies at depth >= d goes to that node's ancestor at depth d -- one file per
+ *                   species when the lineage file's d-th name is the species; a record called above depth d keeps its own node
+ *                   (nothing is lost, nothing is pushed down); unclassified records as in taxon.
+ * Anything else is SPSP_ERR_ARG naming the word; so are a classify word with taxonomy rows and the reverse, d == 0 and d > 32. */
+#define SPSP_SPLIT_DROP 0xffffffffu
+#define SPSP_SPLIT_MAX_BINS 16777216u
+/* What the kernels cut at (any pointer may be NULL): the bytes of the output one workgroup of the copy owns (the extraction's
+ * stretch), the records -- and the sorted runs -- per workgroup of the run table's and the offsets' passes, the pairs per workgroup
+ * of the sort, and SPSP_SPLIT_MAX_BINS. */
+int spsp_split_plan_host(uint32_t* stretch_bytes, uint32_t* record_tile, uint32_t* sort_tile, uint32_t* max_bins);
+/* The rule as plain loops on the host.  begin: as spsp_records_extract_host takes it.  *out, *bin_off (n_bins + 1) and
+ * *bin_records (n_bins) are released with spsp_free(). */
+int spsp_records_split_host(const uint8_t* text, uint64_t n_text, const uint64_t* begin, uint32_t n_rec, const uint32_t* bin /* n_rec */, uint32_t n_bins,
+                            uint8_t** out /* spsp_free */, uint64_t* n_out, uint64_t** bin_off /* spsp_free */, uint64_t** bin_records /* spsp_free */);
+/* The bins of a word.  hits: n_records * top; parent, depth: the tree's arrays (n_nodes), as spsp_taxonomy_lineages_host hands
+ * them out.  SPSP_ERR_ARG as the rule says, for a record that lists more than top matches, and for a reference or node out of range. */
+int spsp_split_bins_classify_host(const char* what, const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records, uint32_t top,
+                                  uint32_t n_ref, uint32_t* bin /* n_records */, uint32_t* n_bins);
+int spsp_split_bins_taxonomy_host(const char* what, const spsp_taxonomy_record* records, uint64_t n_records, const uint32_t* parent, const uint32_t* depth,
+                                  uint32_t n_nodes, uint32_t* bin /* n_records */, uint32_t* n_bins);
+/* Only the refusals of a word: taxonomy != 0 asks for a taxonomy word. */
+int spsp_split_word_check_host(const char* what, int taxonomy);
+/* The text of <prefix>_split.csv.gz: "bin,name,records,bytes,file" and one line per bin with records, in bin order -- with
+ * bin_off_mates, "bin,name,records,bytes_1,file_1,bytes_2,file_2".  bin = the bin's number, or last_name for bin n_bins - 1;
+ * name = names[b], or last_name; file = <file_prefix>_split_<bin><suffix>, paired <file_prefix>_split_<bin>_1<suffix> and
+ * <file_prefix>_split_<bin>_2<suffix_mates>.  names: n_bins - 1.  *text is released with spsp_free(). */
+int spsp_split_csv_host(const char* file_prefix, const char* const* names /* n_bins - 1 */, const char* last_name, uint32_t n_bins,
+                        const uint64_t* bin_records /* n_bins */, const uint64_t* bin_off /* n_bins + 1 */, const char* suffix,
+                        const uint64_t* bin_off_mates /* NULL: not paired */, const char* suffix_mates, char** text, uint64_t* len);
+/* The bins' slices of a text in HBM, back to back in the context's output buffer (*d_out: the extraction's buffer, valid until the
+ * next split or extract call on the context).  The conventions of spsp_records_extract_device: a 16-byte aligned text; d_begin NULL
+ * = the starts are made here for n_rec records, without a wait of their own, and a text that holds another number is SPSP_ERR_ARG;
+ * starts that decrease or leave the text are SPSP_ERR_ARG, and nothing is read or written outside the buffers.  h_bin: n_rec words
+ * on the host; h_bin_off: n_bins + 1, h_bin_records: n_bins, the caller's (zero on a refusal).  Launches: the starts; per 2 048
+ * records the kept bytes and the RUNS -- consecutive records of one bin, neither dropped nor empty -- then the extraction's scan and
+ * the run table; the stable 8-bit LSD radix sort of the runs by bin (spsp_sketch_build_device's), one pass per byte of n_bins - 1,
+ * none for n_bins == 1; a 64-bit scan of the sorted runs' lengths and a lane per bin for bin_off; then the extraction's copy over
+ * runs whose sources lie anywhere in the text, with the appended newline anywhere in the output.  One host wait, at the end. */
+int spsp_records_split_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, const void* d_begin /* NULL: made here */, uint32_t n_rec,
+                              const uint32_t* h_bin /* n_rec */, uint32_t n_bins, void** d_out, uint64_t* n_out, uint64_t* h_bin_off /* n_bins + 1 */,
+                              uint64_t* h_bin_records /* n_bins */);
+/* While the context's timing is on a split call records events between its launches; this reads the milliseconds added up since
+ * the last read and clears them. */
+int spsp_split_stage_ms(spsp_ctx* ctx, double* ms /* 5: starts, runs, order, offsets, copy */);
+/* The whole-file drivers with a split: the arguments of spsp_classify_files_paired / spsp_taxonomy_files_paired (mates_path may be
+ * NULL) with the split word in the place of the extraction's, the same road and the same CSVs byte for byte.  Behind a file's last
+ * batch the bins are made from the rows, the split runs on the second context, where the text still sits, and the output comes back
+ * once and is cut at bin_off on the host.  With mates_path one bin vector, made from the pairs' rows, cuts both texts.  Writes one
+ * file per bin with records, <out_prefix>_split_<b>.fa|fq[.gz] -- <b> the reference's list position or the node's number, the last
+ * bin <out_prefix>_split_unmatched.* or _split_unclassified.* -- paired <out_prefix>_split_<b>_1.* and _2.*, each by its own text's
+ * kind; gzip level 1 when gz != 0; and always <out_prefix>_split.csv.gz (spsp_split_csv_host).  Nothing on any failure; a refused
+ * word is refused before any file is read.  *n_bins_written, *bytes_out (may be NULL): the bins with files, and the bytes of all
+ * slices before compression. */
+int spsp_classify_files_split(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path /* may be NULL */,
+                              uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                              const char* what, int gz, spsp_classify_record** records /* may be NULL; spsp_free */,
+                              spsp_classify_hit** hits /* may be NULL; spsp_free */, uint64_t* n_records /* may be NULL */, uint64_t* n_bins_written,
+                              uint64_t* bytes_out);
+int spsp_taxonomy_files_split(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path /* may be NULL */,
+                              const char* lineages_path, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter,
+                              double rate, const char* what, int gz, spsp_taxonomy_record** records /* may be NULL; spsp_free */,
+                              uint64_t* n_records /* may be NULL */, uint64_t* n_bins_written, uint64_t* bytes_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,8 @@ ABI_SYMBOLS = [
     "spsp_extract_plan_host", "spsp_records_extents_host", "spsp_records_extract_host", "spsp_extract_flags_classify_host", "spsp_extract_flags_taxonomy_host",
     "spsp_extract_word_check_host", "spsp_records_extents_device", "spsp_records_extract_device", "spsp_extract_stage_ms", "spsp_classify_files_extract",
     "spsp_taxonomy_files_extract",
+    "spsp_split_plan_host", "spsp_records_split_host", "spsp_split_bins_classify_host", "spsp_split_bins_taxonomy_host", "spsp_split_word_check_host",
+    "spsp_split_csv_host", "spsp_records_split_device", "spsp_split_stage_ms", "spsp_classify_files_split", "spsp_taxonomy_files_split",
     "spsp_pairs_names_host", "spsp_union_plan_host", "spsp_records_union_device", "spsp_union_stage_ms", "spsp_classify_files_paired", "spsp_taxonomy_files_paired",
 ]
 
@@ -454,6 +456,27 @@ def lib():
         L.spsp_classify_files_extract.argtypes = [vp, P(cp), u32, cp, u32, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(vp), P(u64), cp, i32, P(u64), P(u64)]
         L.spsp_taxonomy_files_extract.restype = i32
         L.spsp_taxonomy_files_extract.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, i32, cp, i32, dbl, P(vp), P(u64), cp, i32, P(u64), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_records_split_device"):
+        L.spsp_split_plan_host.restype = i32
+        L.spsp_split_plan_host.argtypes = [P(u32), P(u32), P(u32), P(u32)]
+        L.spsp_records_split_host.restype = i32
+        L.spsp_records_split_host.argtypes = [vp, u64, vp, u32, vp, u32, P(vp), P(u64), P(vp), P(vp)]
+        L.spsp_split_bins_classify_host.restype = i32
+        L.spsp_split_bins_classify_host.argtypes = [cp, vp, vp, u64, u32, u32, vp, P(u32)]
+        L.spsp_split_bins_taxonomy_host.restype = i32
+        L.spsp_split_bins_taxonomy_host.argtypes = [cp, vp, u64, vp, vp, u32, vp, P(u32)]
+        L.spsp_split_word_check_host.restype = i32
+        L.spsp_split_word_check_host.argtypes = [cp, i32]
+        L.spsp_split_csv_host.restype = i32
+        L.spsp_split_csv_host.argtypes = [cp, P(cp), cp, u32, vp, vp, cp, vp, cp, P(vp), P(u64)]
+        L.spsp_records_split_device.restype = i32
+        L.spsp_records_split_device.argtypes = [vp, vp, u64, vp, u32, vp, u32, P(vp), P(u64), vp, vp]
+        L.spsp_split_stage_ms.restype = i32
+        L.spsp_split_stage_ms.argtypes = [vp, P(dbl)]
+        L.spsp_classify_files_split.restype = i32
+        L.spsp_classify_files_split.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, u32, i32, cp, i32, dbl, cp, i32, P(vp), P(vp), P(u64), P(u64), P(u64)]
+        L.spsp_taxonomy_files_split.restype = i32
+        L.spsp_taxonomy_files_split.argtypes = [vp, P(cp), u32, cp, cp, cp, u32, u32, u32, i32, cp, i32, dbl, cp, i32, P(vp), P(u64), P(u64), P(u64)]
     if not LIB_OVERRIDDEN or hasattr(L, "spsp_records_union_device"):
         L.spsp_pairs_names_host.restype = i32
         L.spsp_pairs_names_host.argtypes = [P(cp), P(cp), u64, P(vp), P(u64)]
@@ -960,6 +983,87 @@ def extract_flags_taxonomy(what, records, size):
     _check(lib().spsp_extract_flags_taxonomy_host(what.encode(), records.ctypes.data if n else None, n, size.ctypes.data if len(size) else None, len(size),
                                                   keep.ctypes.data))
     return keep[:n]
+
+
+SPLIT_DROP = 0xFFFFFFFF
+
+
+def split_plan():
+    """spsp_split_plan_host: what the split's kernels cut at -> dict(stretch_bytes: the bytes of the output one workgroup of the copy
+    owns, record_tile: the records (and the sorted runs) per workgroup of the run table's and the offsets' passes, sort_tile: the
+    pairs per workgroup of the radix sort, max_bins)"""
+    a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_split_plan_host(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return {"stretch_bytes": a.value, "record_tile": b.value, "sort_tile": c.value, "max_bins": d.value}
+
+
+def records_split(text, bins, n_bins, begin=None):
+    """spsp_records_split_host: every record of `text` in the slice of its bin (SPLIT_DROP: nowhere), bin behind bin, record order
+    inside a bin, a newline appended to a last record that lacks one -> (bytes, bin_off: np.uint64[n_bins + 1], bin_records:
+    np.uint64[n_bins]).  begin: the records' starts (records_extents(text) when None)"""
+    if begin is None:
+        begin = records_extents(text)
+    text = np.frombuffer(bytes(text), dtype=np.uint8)
+    begin = np.ascontiguousarray(begin, dtype=np.uint64)
+    bins = np.ascontiguousarray(bins, dtype=np.uint32)
+    if len(begin) < 1 or len(bins) != len(begin) - 1:
+        raise ValueError("records_split: one bin per record and n_rec + 1 starts")
+    out, n_out, off, rec = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_void_p()
+    _check(lib().spsp_records_split_host(text.ctypes.data if len(text) else None, len(text), begin.ctypes.data, len(bins), bins.ctypes.data if len(bins) else None,
+                                         n_bins, C.byref(out), C.byref(n_out), C.byref(off), C.byref(rec)))
+    return (_take(out, n_out.value), np.frombuffer(_take(off, (n_bins + 1) * 8), dtype=np.uint64).copy(),
+            np.frombuffer(_take(rec, n_bins * 8), dtype=np.uint64).copy())
+
+
+def split_bins_classify(what, records, hits, n_ref):
+    """spsp_split_bins_classify_host: the word `best` and classify's rows (records, hits[n, top]) -> (bins: np.uint32[n], n_bins =
+    n_ref + 1): the rank-1 match's list position, n_ref for a record without a match"""
+    records = np.ascontiguousarray(records, dtype=CLASSIFY_RECORD_DTYPE)
+    hits = np.ascontiguousarray(hits, dtype=CLASSIFY_HIT_DTYPE)
+    n = len(records)
+    if hits.ndim != 2 or hits.shape[0] != n:
+        raise ValueError("split_bins_classify: hits[n_records, top]")
+    bins, n_bins = np.zeros(max(n, 1), dtype=np.uint32), C.c_uint32()
+    _check(lib().spsp_split_bins_classify_host(what.encode(), records.ctypes.data if n else None, hits.ctypes.data if n else None, n, hits.shape[1], n_ref,
+                                               bins.ctypes.data, C.byref(n_bins)))
+    return bins[:n], n_bins.value
+
+
+def split_bins_taxonomy(what, records, parent, depth):
+    """spsp_split_bins_taxonomy_host: a word (taxon, depth=<d>), the taxonomy's rows and the tree's parents and depths
+    (taxonomy_lineages()) -> (bins: np.uint32[n], n_bins = n_nodes + 1); unclassified records go to bin n_nodes"""
+    records = np.ascontiguousarray(records, dtype=TAXONOMY_RECORD_DTYPE)
+    parent = np.ascontiguousarray(parent, dtype=np.uint32)
+    depth = np.ascontiguousarray(depth, dtype=np.uint32)
+    if len(parent) != len(depth):
+        raise ValueError("split_bins_taxonomy: one parent and one depth per node")
+    n = len(records)
+    bins, n_bins = np.zeros(max(n, 1), dtype=np.uint32), C.c_uint32()
+    _check(lib().spsp_split_bins_taxonomy_host(what.encode(), records.ctypes.data if n else None, n, parent.ctypes.data if len(parent) else None,
+                                               depth.ctypes.data if len(depth) else None, len(parent), bins.ctypes.data, C.byref(n_bins)))
+    return bins[:n], n_bins.value
+
+
+def split_word_check(what, taxonomy):
+    """spsp_split_word_check_host: only the refusals of a split word (taxonomy: the rows will be a taxonomy's)"""
+    _check(lib().spsp_split_word_check_host(what.encode(), 1 if taxonomy else 0))
+
+
+def split_csv(file_prefix, names, last_name, bin_records, bin_off, suffix, bin_off_mates=None, suffix_mates=None):
+    """spsp_split_csv_host: the text of <prefix>_split.csv.gz -- one line per bin with records; names: n_bins - 1, last_name: the
+    last bin's (unmatched, unclassified); with bin_off_mates the paired columns"""
+    bin_records = np.ascontiguousarray(bin_records, dtype=np.uint64)
+    bin_off = np.ascontiguousarray(bin_off, dtype=np.uint64)
+    n_bins = len(bin_records)
+    if len(bin_off) != n_bins + 1 or len(names) != n_bins - 1:
+        raise ValueError("split_csv: n_bins - 1 names, n_bins counts, n_bins + 1 offsets")
+    arr, _alive = _paths_array(names)
+    mates = None if bin_off_mates is None else np.ascontiguousarray(bin_off_mates, dtype=np.uint64)
+    text, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_split_csv_host(file_prefix.encode(), arr, last_name.encode(), n_bins, bin_records.ctypes.data, bin_off.ctypes.data, suffix.encode(),
+                                     None if mates is None else mates.ctypes.data, None if suffix_mates is None else suffix_mates.encode(), C.byref(text),
+                                     C.byref(n)))
+    return _take(text, n.value)
 
 
 def taxonomy_csv(records, record_names, parent, node_names, precision=6):
@@ -1766,18 +1870,29 @@ class Context:
     union_plan = staticmethod(union_plan)
     pairs_names = staticmethod(pairs_names)
 
-    def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None):
+    def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
+                       split=None):
         """spsp_classify_files: the sketch files of the references and a FASTA / FASTQ file of records (gzip or plain) ->
         <prefix>_classify.csv.gz, <prefix>_classify_summary.csv.gz and (records, hits[n, top]).  rate: as compare_files (0.0, a
         rate, or "auto"); sketches of different rates need one.  extract: a word (matched, unmatched, best=<j>, listed=<j>) --
         spsp_classify_files_extract: the records it names are written to <prefix>_extract.fa or .fq (".gz" appended when gz) as
         well; self.last_extract = dict(n_kept, bytes_out).  mates_path: the second file of paired reads -- spsp_classify_files_paired:
         record p of the two files is one pair, classified by the keys of both mates, and extract writes <prefix>_extract_1.* and
-        <prefix>_extract_2.*"""
+        <prefix>_extract_2.*.  split: the word `best` -- spsp_classify_files_split: every record goes to <prefix>_split_<j>.fa or .fq
+        of its rank-1 match (or _split_unmatched.*; with mates_path _1 and _2 files), <prefix>_split.csv.gz lists them;
+        self.last_split = dict(bins, records, bytes_out).  Not together with extract"""
         arr, _alive = _paths_array(paths)
         recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
         self._cf_n_ref = None
-        if mates_path is not None:
+        if split is not None:
+            if extract is not None:
+                raise ValueError("classify_files: split writes every record and extract one subset: one of the two")
+            written, out_bytes = C.c_uint64(), C.c_uint64()
+            _check(lib().spsp_classify_files_split(self._h, arr, len(paths), str(records_path).encode(), None if mates_path is None else str(mates_path).encode(),
+                                                   top, min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate), split.encode(), 1 if gz else 0,
+                                                   C.byref(recs), C.byref(hits), C.byref(n), C.byref(written), C.byref(out_bytes)))
+            self.last_split = {"bins": written.value, "records": n.value, "bytes_out": out_bytes.value}
+        elif mates_path is not None:
             kept, out_bytes = C.c_uint64(), C.c_uint64()
             _check(lib().spsp_classify_files_paired(self._h, arr, len(paths), str(records_path).encode(), str(mates_path).encode(), top, min_keys, num, den,
                                                     precision, prefix.encode(), 0, _rate_arg(rate), None if extract is None else extract.encode(),
@@ -1817,6 +1932,29 @@ class Context:
                                                  C.byref(n_kept)))
         return self.to_host(out.value, n_out.value, np.uint8), n_kept.value
 
+    def records_split_device(self, d_text, n_text, bins, n_bins, d_begin=None, n_rec=None):
+        """spsp_records_split_device: every record of the text in HBM in the slice of its bin (SPLIT_DROP: nowhere) -> (np.uint8
+        array, bin_off: np.uint64[n_bins + 1], bin_records: np.uint64[n_bins]).  d_begin: the starts on the device
+        (records_extents_device) or None: they are made in the call, for len(bins) records.  Every kept byte crosses to the host once"""
+        bins = np.ascontiguousarray(bins, dtype=np.uint32)
+        if n_rec is None:
+            n_rec = len(bins)
+        if len(bins) != n_rec:
+            raise ValueError("records_split_device: one bin per record")
+        room = n_bins if 0 < n_bins <= 1 << 24 else 0      # (an n_bins the call refuses gets no arrays to fill)
+        off, rec = np.zeros(room + 1, dtype=np.uint64), np.zeros(max(room, 1), dtype=np.uint64)
+        out, n_out = C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_records_split_device(self._h, d_text, n_text, d_begin, n_rec, bins.ctypes.data if n_rec else None, n_bins, C.byref(out), C.byref(n_out),
+                                               off.ctypes.data, rec.ctypes.data))
+        return self.to_host(out.value, n_out.value, np.uint8), off, rec[:n_bins]
+
+    def split_stage_ms(self):
+        """spsp_split_stage_ms: with timing_enable() on, the milliseconds of the split calls' launches since the last read ->
+        dict(starts, runs, order, offsets, copy)"""
+        ms = (C.c_double * 5)()
+        _check(lib().spsp_split_stage_ms(self._h, ms))
+        return dict(zip(("starts", "runs", "order", "offsets", "copy"), ms))
+
     def extract_stage_ms(self):
         """spsp_extract_stage_ms: with timing_enable() on, the milliseconds of the extract calls' launches since the last read ->
         dict(starts, offsets, copy)"""
@@ -1853,17 +1991,27 @@ class Context:
         _check(lib().spsp_taxonomy_stage_ms(self._h, ms))
         return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
 
-    def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None):
+    def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
+                       split=None):
         """spsp_taxonomy_files: the sketch files of the references, a FASTA / FASTQ file of records (gzip or plain) and the lineage
         file of the references -> <prefix>_taxonomy.csv.gz, <prefix>_taxonomy_report.csv.gz and the records.  rate: as
         classify_files (0.0, a rate, or "auto"); sketches of different rates need one.  extract: a word (classified, unclassified,
         taxon=<t>, clade=<t>) -- spsp_taxonomy_files_extract: the records it names are written to <prefix>_extract.fa or .fq (".gz"
         appended when gz) as well; self.last_extract = dict(n_kept, bytes_out).  mates_path: as classify_files
-        (spsp_taxonomy_files_paired)"""
+        (spsp_taxonomy_files_paired).  split: a word (taxon, depth=<d>) -- spsp_taxonomy_files_split: every record goes to
+        <prefix>_split_<t>.fa or .fq of its node (or _split_unclassified.*), as classify_files; self.last_split"""
         arr, _alive = _paths_array(paths)
         recs, n = C.c_void_p(), C.c_uint64()
         self._cf_n_ref = None
-        if mates_path is not None:
+        if split is not None:
+            if extract is not None:
+                raise ValueError("taxonomy_files: split writes every record and extract one subset: one of the two")
+            written, out_bytes = C.c_uint64(), C.c_uint64()
+            _check(lib().spsp_taxonomy_files_split(self._h, arr, len(paths), str(records_path).encode(), None if mates_path is None else str(mates_path).encode(),
+                                                   str(lineages_path).encode(), min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate), split.encode(),
+                                                   1 if gz else 0, C.byref(recs), C.byref(n), C.byref(written), C.byref(out_bytes)))
+            self.last_split = {"bins": written.value, "records": n.value, "bytes_out": out_bytes.value}
+        elif mates_path is not None:
             kept, out_bytes = C.c_uint64(), C.c_uint64()
             _check(lib().spsp_taxonomy_files_paired(self._h, arr, len(paths), str(records_path).encode(), str(mates_path).encode(), str(lineages_path).encode(),
                                                     min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate),

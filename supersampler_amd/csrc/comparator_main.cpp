@@ -131,12 +131,14 @@ int main(int argc, char** argv) {
     bool taxonomy = false, cf_top_seen = false;
     string extract_what;             // -F <what> [-u]: with -X, the records the word names are written out again (neither letter is in the reference's option string)
     bool extract = false, extract_plain = false;
+    string split_what;               // -j <word> [-u]: with -X, every record goes to the file of its reference or taxon (not in the reference's option string)
+    bool split = false;
     vector<string> reads_files;      // -D <reads file> [-D <more> ...] [-W <min_count>]: neither letter is in the reference's option string
     bool dp_min_seen = false;
     long long dp_min_count = 1;
     bool profile = false;            // -B <min_keys>: the profile behind the depth of -D (not in the reference's option string either)
     long long pf_min_keys = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:")) != -1) {
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:j:")) != -1) {
         switch (ch) {
             case 'D': reads_files.push_back(optarg); break;
             case 'W': {
@@ -159,6 +161,7 @@ int main(int argc, char** argv) {
             case 'H': lineages_file = optarg; taxonomy = true; break;
             case 'F': extract_what = optarg; extract = true; break;
             case 'u': extract_plain = true; break;
+            case 'j': split_what = optarg; split = true; break;
             case 'Y': {
                 char* e = nullptr;
                 cf_top = strtoll(optarg, &e, 10);
@@ -297,7 +300,10 @@ int main(int argc, char** argv) {
     if (taxonomy && cf_top_seen) { cout << "-H assigns every record to one node of the tree: not together with -Y (-V and -I set its threshold)" << endl; return 1; }
     if (paired && !classify) { cout << "-x gives the mates of the records of -X <records file>, pair by pair: it needs -X" << endl; return 1; }
     if (extract && !classify) { cout << "-F names the records of -X <records file> to write out again: it needs -X" << endl; return 1; }
-    if (extract_plain && !extract) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
+    if (split && !classify) { cout << "-j splits the records of -X <records file> into one file per reference or taxon: it needs -X" << endl; return 1; }
+    if (split && extract) { cout << "-j writes every record and -F one subset of them: one of the two in a run" << endl; return 1; }
+    if (split && spsp_split_word_check_host(split_what.c_str(), taxonomy ? 1 : 0) != SPSP_OK) { cout << "-j: " << spsp_last_error() << endl; return 1; }
+    if (extract_plain && !extract && !split) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
     if (extract && spsp_extract_word_check_host(extract_what.c_str(), taxonomy ? 1 : 0, 0xffffffffu) != SPSP_OK) { cout << "-F: " << spsp_last_error() << endl; return 1; }
     if (cf_opts && !classify) { cout << "-Y and -V belong to the classification of -X <records file>: they need -X" << endl; return 1; }
     if (classify && (query != "" || gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts || select_opts || accumulation || groups ||
@@ -355,7 +361,8 @@ int main(int argc, char** argv) {
              << "-q Query file of files (\"\" for all versus all comparison of the index)" << endl
              << "-H Lineage file, one name;name;... line per index sketch: with -X <records file>, each record goes to the lowest common ancestor of its keys" << endl
              << "-F Records of -X <records file> to write out again as <prefix>_extract.fa.gz / .fq.gz: matched, unmatched, best=<j>, listed=<j>; with -H: classified, unclassified, taxon=<t>, clade=<t>" << endl
-             << "-u Write the records of -F plain, not gzipped" << endl
+             << "-u Write the records of -F, or the files of -j, plain, not gzipped" << endl
+             << "-j Split the records of -X <records file> into <prefix>_split_<b>.fa.gz / .fq.gz, one file per reference (best; the rest in _split_unmatched) or, with -H, per node (taxon, depth=<d>; the rest in _split_unclassified), and <prefix>_split.csv.gz; with -x <prefix>_split_<b>_1.* and _2.*; -u writes them plain" << endl
              << "-x Mates file: with -X <records file>, record p of the two files is one pair, classified by the keys of both mates; -F then writes <prefix>_extract_1.* and <prefix>_extract_2.*" << endl
              << "Ouput arguments:" << endl
              << "-m Minimum value to be output (0.0)" << endl
@@ -423,7 +430,15 @@ int main(int argc, char** argv) {
         // one device, as gather (the driver opens a second context on it for the records)
         spsp_ctx* ctx = nullptr;
         int rc = spsp_create(devices[0], nullptr, &ctx);
-        if (rc == SPSP_OK && paired && taxonomy)
+        if (rc == SPSP_OK && split && taxonomy)
+            rc = spsp_taxonomy_files_split(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), paired ? mates_file.c_str() : nullptr, lineages_file.c_str(),
+                                           (uint32_t)cf_min_keys, nb_num, nb_den, (int)p, output_name.c_str(), 1, rate, split_what.c_str(), extract_plain ? 0 : 1, nullptr,
+                                           nullptr, nullptr, nullptr);
+        else if (rc == SPSP_OK && split)
+            rc = spsp_classify_files_split(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), paired ? mates_file.c_str() : nullptr, (uint32_t)cf_top,
+                                           (uint32_t)cf_min_keys, nb_num, nb_den, (int)p, output_name.c_str(), 1, rate, split_what.c_str(), extract_plain ? 0 : 1, nullptr,
+                                           nullptr, nullptr, nullptr, nullptr);
+        else if (rc == SPSP_OK && paired && taxonomy)
             rc = spsp_taxonomy_files_paired(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), mates_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys,
                                             nb_num, nb_den, (int)p, output_name.c_str(), 1, rate, extract ? extract_what.c_str() : nullptr, extract_plain ? 0 : 1, nullptr,
                                             nullptr, nullptr, nullptr);

@@ -37,7 +37,7 @@ namespace spsp {
 typedef unsigned __int128 u128b;
 
 // ---------------------------------------------------------------------------------------------- radix sort (keys u64, values u32)
-constexpr uint32_t kRsThreads = 256, kRsPer = 8, kRsTile = kRsThreads * kRsPer;
+static_assert(kRsTile == kRsThreads * kRsPer, "the sort's tile in lanes");
 __global__ __launch_bounds__(kRsThreads) void k_rs_hist(const uint64_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t n_blocks,
                                                        uint32_t* __restrict__ hist) {
     __shared__ uint32_t h[256];
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_scatter(const uint64_t* __res
 }
 
 // sorts (keys, vals) by the low `bits` bits of the keys, stable; the result is in (*keys_io, *vals_io) (buffers may swap)
-static int radix_sort_pairs(spsp_ctx* ctx, uint64_t** keys_io, uint32_t** vals_io, uint64_t* keys_tmp, uint32_t* vals_tmp, uint32_t n, uint32_t bits) {
+int radix_sort_pairs(spsp_ctx* ctx, uint64_t** keys_io, uint32_t** vals_io, uint64_t* keys_tmp, uint32_t* vals_tmp, uint32_t n, uint32_t bits) {
     if (n == 0) return SPSP_OK;
     const uint32_t n_blocks = (n + kRsTile - 1) / kRsTile;
     int rc = ctx->bl_hist.reserve((size_t)(256 * n_blocks + 1) * 4 * 2 + 64);

@@ -645,7 +645,16 @@ int records_pair_batches(spsp_ctx* ctx, spsp_ctx* const* side, const spsp_params
                                      &u_hi, key_off.data())) ||
             (rc = on_batch(RecordBatch{r0, batch, u_mn, u_lo, u_hi, key_off.data()}))) return rc;
     }
-    if (extract) {
+    if (extract && extract[0]->split) {
+        // (one bin vector, likewise)
+        std::vector<uint32_t> bin(n_rec ? n_rec : 1, SPSP_SPLIT_DROP);
+        uint32_t n_bins = 0;
+        if ((rc = extract[0]->bins(n_rec, bin.data(), &n_bins))) return rc;
+        for (int s = 0; s < 2; ++s) {
+            extract[s]->bins = [&bin, n_bins](uint32_t n, uint32_t* out, uint32_t* nb) { memcpy(out, bin.data(), (size_t)n * 4); *nb = n_bins; return (int)SPSP_OK; };
+            if ((rc = extract[s]->on_text(side[s], side[s]->i_text.as<uint8_t>(), n_text[s], n_rec))) return rc;
+        }
+    } else if (extract) {
         // (one flag vector: extract[0] makes it from the pairs' rows, and each text is cut by it where it still sits)
         std::vector<uint8_t> keep(n_rec ? n_rec : 1, 0);
         if ((rc = extract[0]->flags(n_rec, keep.data()))) return rc;
@@ -705,6 +714,7 @@ int records_files_road(FilesRun& run, const char* what_is, const char* const* re
 }
 
 int extract_write(spsp_ctx* ctx, ExtractRun* extract, ExtractRun* extract_mates, const char* out_prefix, int chatter) {
+    if (extract->split) return split_write(ctx, extract, extract_mates, out_prefix, chatter);
     if (!extract_mates) return extract->write(ctx, out_prefix, chatter);
     int rc;
     if ((rc = extract->write(ctx, out_prefix, 0)) || (rc = extract_mates->write(ctx, out_prefix, 0)) || !chatter) return rc;
@@ -726,6 +736,14 @@ static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
         extract->flags = [&](uint32_t n_rec, uint8_t* keep) {
             return spsp_extract_flags_classify_host(extract->what, recs->data(), hits->data(), n_rec, top, n_ref, keep);
         };
+    for (ExtractRun* e : {extract, extract_mates})
+        if (e && e->split) {                               // (the names the summary prints: the references' paths)
+            e->bins = [&](uint32_t n_rec, uint32_t* bin, uint32_t* n_bins) {
+                return spsp_split_bins_classify_host(extract->what, recs->data(), hits->data(), n_rec, top, n_ref, bin, n_bins);
+            };
+            e->bin_names.assign(paths, paths + n_ref);
+            e->last_name = "unmatched";
+        }
     int rc = records_files_road(
         run, "classification is", &records_path, 1, rate, [] { return SPSP_OK; }, &names,
         [&](uint32_t n_rec, const uint64_t* rec_off) {
@@ -783,7 +801,7 @@ extern "C" int spsp_classify_device(spsp_ctx* ctx, const void* d_q_minimizer, co
 static int classify_files_entry(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
                                 uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, spsp_classify_record** records,
                                 spsp_classify_hit** hits, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out,
-                                bool paired = false, const char* mates_path = nullptr) {
+                                bool paired = false, const char* mates_path = nullptr, bool split = false) {
     if (records) *records = nullptr;
     if (hits) *hits = nullptr;
     if (n_records) *n_records = 0;
@@ -793,16 +811,16 @@ static int classify_files_entry(spsp_ctx* ctx, const char* const* index_paths, u
     if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
     int rc;
     if ((rc = classify_check_args(top, min_keys, num, den))) return rc;
-    if (what && (rc = spsp_extract_word_check_host(what, 0, n_ref))) return rc;   // (before any file is read)
+    if (what && (rc = split ? spsp_split_word_check_host(what, 0) : spsp_extract_word_check_host(what, 0, n_ref))) return rc;   // (before any file is read)
     SPSP_HIP(hipSetDevice(ctx->device));
     std::vector<spsp_classify_record> got;
     std::vector<spsp_classify_hit> got_hits;
     ExtractRun extract, extract_mates;
-    extract.what = extract_mates.what = what; extract.gz = extract_mates.gz = gz;
+    extract.what = extract_mates.what = what; extract.gz = extract_mates.gz = gz; extract.split = extract_mates.split = split;
     if (mates_path) { extract.tag = "_1"; extract_mates.tag = "_2"; }
     if ((rc = classify_files(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, &got, &got_hits,
                              what ? &extract : nullptr, mates_path, what && mates_path ? &extract_mates : nullptr))) return rc;
-    if (n_kept) *n_kept = extract.n_kept;
+    if (n_kept) *n_kept = split ? extract.bins_written : extract.n_kept;
     if (bytes_out) *bytes_out = extract.out.size() + extract_mates.out.size();
     if (n_records) *n_records = got.size();
     if (records && (rc = give_rows(got, records))) return rc;
@@ -832,6 +850,15 @@ extern "C" int spsp_classify_files_paired(spsp_ctx* ctx, const char* const* inde
                                           uint64_t* n_kept, uint64_t* bytes_out) {
     return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
                                 what, gz, n_kept, bytes_out, true, mates_path);
+}
+
+extern "C" int spsp_classify_files_split(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
+                                         uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter,
+                                         double rate, const char* what, int gz, spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records,
+                                         uint64_t* n_bins_written, uint64_t* bytes_out) {
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
+                                what, gz, n_bins_written, bytes_out, false, mates_path, true);
 }
 
 extern "C" int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms) {

@@ -254,4 +254,45 @@ __global__ __launch_bounds__(kRouteThreads) void k_rec_route(const uint64_t* __r
     else q_large[atomicAdd(words + kRqLarge, 1u)] = (uint32_t)r;
 }
 
+// ---- What the two copies of records share (spsp_extract.hip: k_ex_copy, spsp_split.hip: k_sp_copy).
+
+// 16 bytes at the 16-byte-aligned a < n: one load where they all lie in the text, the text's last bytes one by one
+__device__ __forceinline__ uint4 ex_load16(const uint8_t* __restrict__ text, uint64_t n, uint64_t a) {
+    if (a + 16 <= n) return *reinterpret_cast<const uint4*>(text + a);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j)
+        if (a + j < n) w[j >> 2] |= (uint32_t)text[a + j] << (8 * (j & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// the largest i of [lo, hi) with dst[i] <= o (dst[lo] <= o is the caller's)
+__device__ __forceinline__ uint32_t ex_find(const uint64_t* __restrict__ dst, uint32_t lo, uint32_t hi, uint64_t o) {
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (dst[mid] <= o) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the 16 bytes of the text from s on (s + 15 < n), for an aligned store: the two aligned groups that hold them and a byte shift
+__device__ __forceinline__ uint4 ex_gather16(const uint8_t* __restrict__ text, uint64_t n, uint64_t s) {
+    const uint64_t a = s & ~15ull;
+    uint32_t sh = (uint32_t)(s & 15ull);
+    const uint4 lo4 = ex_load16(text, n, a);
+    uint4 v;
+    if (sh == 0u) v = lo4;
+    else {
+        const uint4 hi4 = ex_load16(text, n, a + 16ull);   // (holds byte s + 15, which is in the text)
+        unsigned long long q0 = (unsigned long long)lo4.x | ((unsigned long long)lo4.y << 32), q1 = (unsigned long long)lo4.z | ((unsigned long long)lo4.w << 32);
+        unsigned long long q2 = (unsigned long long)hi4.x | ((unsigned long long)hi4.y << 32);
+        const unsigned long long q3 = (unsigned long long)hi4.z | ((unsigned long long)hi4.w << 32);
+        if (sh >= 8u) { q0 = q1; q1 = q2; q2 = q3; sh -= 8u; }
+        const uint32_t r = sh * 8u;
+        const unsigned long long x0 = r ? (q0 >> r) | (q1 << (64u - r)) : q0, x1 = r ? (q1 >> r) | (q2 << (64u - r)) : q1;
+        v = make_uint4((uint32_t)x0, (uint32_t)(x0 >> 32), (uint32_t)x1, (uint32_t)(x1 >> 32));
+    }
+    return v;
+}
+
 }  // namespace spsp

@@ -28,27 +28,8 @@ namespace spsp {
 
 namespace {
 
-constexpr uint32_t kExThreads = 256, kExChunk = 16, kExRecsPerLane = 8, kExRecTile = kExThreads * kExRecsPerLane;
-constexpr uint32_t kExStores = kExStretch / (kExThreads * 16);
+constexpr uint32_t kExChunk = 16;
 static_assert(kExTile == kExThreads * kExChunk && kExStores * kExThreads * 16 == kExStretch, "the tile and the stretch in lanes");
-
-// the words of one call on the device (64 bits each)
-enum ExWord {
-    kExFastq = 0,   // k_ex_tail: 1 when the text is FASTQ
-    kExLimit,       // ... where the content ends (FASTA: n)
-    kExEnd,         // ... where the last record ends: begin[n_rec]
-    kExUnits,       // the first scan's total: FASTA the starts behind byte 0, FASTQ the content's newlines (+ two words of the scan's)
-    kExRecs = 6,    // k_ex_starts: the records
-    kExBad,         // bit 0: a FASTQ content whose lines are not a multiple of four; bit 1: a pair of begin[] out of order or range
-    kExSrc,         // the second scan's totals: the source bytes kept,
-    kExRunsKept,    // ... the runs (low half) and the records kept (high half)
-    kExNl,          // k_ex_rec_write: 1 when the last kept range gets its newline
-    kExBlank,       // k_ex_tail: 1 when something follows the blank tail's first newline (the ingest's blank_tail): a content of
-    kExEndEmpty,    // ... 4r + 3 lines then has an empty quality line, which ends here (behind the tail's second newline, or at n)
-    kExWords = 16
-};
-
-struct ExSum { unsigned long long a; uint32_t b, c; };   // 16 bytes: bytes (or starts), runs, records kept
 
 // bit j: byte j of the 16 equals `byte` (four bytes per register: the exact zero-byte test, then the four flags of a word packed)
 __device__ __forceinline__ uint32_t ex_eq16(const uint32_t (&w)[4], uint32_t byte) {
@@ -330,25 +311,6 @@ __global__ __launch_bounds__(kExThreads) void k_ex_rec_write(const uint8_t* __re
     }
 }
 
-// 16 bytes at the 16-byte-aligned a < n: one load where they all lie in the text, the text's last bytes one by one
-__device__ __forceinline__ uint4 ex_load16(const uint8_t* __restrict__ text, uint64_t n, uint64_t a) {
-    if (a + 16 <= n) return *reinterpret_cast<const uint4*>(text + a);
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (uint32_t j = 0; j < 16; ++j)
-        if (a + j < n) w[j >> 2] |= (uint32_t)text[a + j] << (8 * (j & 3));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// the largest i of [lo, hi) with dst[i] <= o (dst[lo] <= o is the caller's)
-__device__ __forceinline__ uint32_t ex_find(const uint64_t* __restrict__ dst, uint32_t lo, uint32_t hi, uint64_t o) {
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (dst[mid] <= o) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kExThreads) void k_ex_copy(const uint8_t* __restrict__ text, uint64_t n_text, const uint64_t* __restrict__ run_src,
                                                         const uint64_t* __restrict__ run_dst, const unsigned long long* __restrict__ words,
                                                         uint8_t* __restrict__ out) {
@@ -369,21 +331,8 @@ __global__ __launch_bounds__(kExThreads) void k_ex_copy(const uint8_t* __restric
         uint64_t rd = run_dst[i], re = run_dst[i + 1], rs = run_src[i];
         uint4 v;
         if (o + 16ull <= re) {
-            // inside one run: the 16 source bytes from s on, out of the two aligned groups that hold them
-            const uint64_t s = rs + (o - rd), a = s & ~15ull;
-            uint32_t sh = (uint32_t)(s & 15ull);
-            const uint4 lo4 = ex_load16(text, n_text, a);
-            if (sh == 0u) v = lo4;
-            else {
-                const uint4 hi4 = ex_load16(text, n_text, a + 16ull);   // (holds byte s + 15, which is in the text)
-                unsigned long long q0 = (unsigned long long)lo4.x | ((unsigned long long)lo4.y << 32), q1 = (unsigned long long)lo4.z | ((unsigned long long)lo4.w << 32);
-                unsigned long long q2 = (unsigned long long)hi4.x | ((unsigned long long)hi4.y << 32);
-                const unsigned long long q3 = (unsigned long long)hi4.z | ((unsigned long long)hi4.w << 32);
-                if (sh >= 8u) { q0 = q1; q1 = q2; q2 = q3; sh -= 8u; }
-                const uint32_t r = sh * 8u;
-                const unsigned long long x0 = r ? (q0 >> r) | (q1 << (64u - r)) : q0, x1 = r ? (q1 >> r) | (q2 << (64u - r)) : q1;
-                v = make_uint4((uint32_t)x0, (uint32_t)(x0 >> 32), (uint32_t)x1, (uint32_t)(x1 >> 32));
-            }
+            // inside one run: the 16 source bytes, out of the two aligned groups that hold them
+            v = ex_gather16(text, n_text, rs + (o - rd));
         } else {
             // across runs, the appended newline or the output's end: byte by byte (zeros behind the end: the buffer is whole stretches)
             uint32_t w[4] = {0u, 0u, 0u, 0u};
@@ -410,6 +359,8 @@ int ex_mark(spsp_ctx* ctx, int i) {
     ctx->ex_marked |= 1u << i;
     return SPSP_OK;
 }
+
+}  // namespace
 
 int ex_front(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t* n_tiles) {
     if (((uintptr_t)d_text & 15u) != 0) { set_error("d_text must be 16-byte aligned"); return SPSP_ERR_ARG; }
@@ -449,7 +400,11 @@ int ex_refuse_lines(uint64_t lines) {
     return SPSP_ERR_FORMAT;
 }
 
-}  // namespace
+int ex_scan_launch(spsp_ctx* ctx, const ExSum* d_in, uint64_t n_items, ExSum* d_out, unsigned long long* d_totals) {
+    hipLaunchKernelGGL(k_ex_scan, dim3(1), dim3(1024), 0, ctx->stream, d_in, n_items, d_out, d_totals);
+    SPSP_HIP(hipGetLastError());
+    return SPSP_OK;
+}
 
 int records_extents_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t** d_begin, uint32_t* n_rec, bool* fastq) {
     int rc;
@@ -531,6 +486,7 @@ int records_extract_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, 
 
 int ExtractRun::on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_records) {
     int rc;
+    if (split) return split_text(side, d_text, n_text, n_records);
     std::vector<uint8_t> keep(n_records ? n_records : 1, 0);
     if ((rc = flags(n_records, keep.data()))) return rc;
     uint8_t* d_out = nullptr;

@@ -3116,3 +3116,159 @@ extern "C" int spsp_extract_flags_taxonomy_host(const char* what, const spsp_tax
     }
     return SPSP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- split
+// The host forms of the split, plain loops straight from the rule of include/spsp.h ("split"): what the device pass is held
+// against, what turns a word and a pass's rows into bins, and the manifest's text.
+
+extern "C" int spsp_split_plan_host(uint32_t* stretch_bytes, uint32_t* record_tile, uint32_t* sort_tile, uint32_t* max_bins) {
+    if (stretch_bytes) *stretch_bytes = spsp::kExStretch;
+    if (record_tile) *record_tile = spsp::kExRecTile;
+    if (sort_tile) *sort_tile = spsp::kRsTile;
+    if (max_bins) *max_bins = spsp::kSpMaxBins;
+    return SPSP_OK;
+}
+
+extern "C" int spsp_records_split_host(const uint8_t* text, uint64_t n, const uint64_t* begin, uint32_t n_rec, const uint32_t* bin, uint32_t n_bins, uint8_t** out,
+                                       uint64_t* n_out, uint64_t** bin_off, uint64_t** bin_records) {
+    using namespace spsp;
+    if (out) *out = nullptr;
+    if (n_out) *n_out = 0;
+    if (bin_off) *bin_off = nullptr;
+    if (bin_records) *bin_records = nullptr;
+    if (!out || !n_out || !bin_off || !bin_records || !begin || (n && !text) || (n_rec && !bin)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_bins == 0 || n_bins > kSpMaxBins) { set_error("split: n_bins must be 1 .. %u (n_bins = %u)", kSpMaxBins, n_bins); return SPSP_ERR_ARG; }
+    std::vector<uint64_t> bytes(n_bins, 0), records(n_bins, 0);
+    const auto newline = [&](uint32_t r) { return r + 1 == n_rec && begin[r + 1] > begin[r] && text[begin[r + 1] - 1] != '\n'; };   // (only the last record can lack its newline)
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        if (begin[r] > begin[r + 1] || begin[r + 1] > n) { set_error("split: begin must not decrease and must end inside the text"); return SPSP_ERR_ARG; }
+        if (bin[r] == SPSP_SPLIT_DROP) continue;
+        if (bin[r] >= n_bins) { set_error("split: bin[%u] = %u, n_bins = %u", r, bin[r], n_bins); return SPSP_ERR_ARG; }
+        ++records[bin[r]];
+        bytes[bin[r]] += begin[r + 1] - begin[r] + (newline(r) ? 1 : 0);
+    }
+    uint64_t* off = (uint64_t*)malloc(((size_t)n_bins + 1) * 8);
+    uint64_t* rec = (uint64_t*)malloc((size_t)n_bins * 8);
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < n_bins && off; ++b) { off[b] = total; total += bytes[b]; }
+    uint8_t* o = (uint8_t*)malloc(total ? total : 1);
+    if (!off || !rec || !o) { free(off); free(rec); free(o); set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    off[n_bins] = total;
+    memcpy(rec, records.data(), (size_t)n_bins * 8);
+    std::vector<uint64_t> at(off, off + n_bins);           // where the next record of a bin goes
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        const uint64_t len = begin[r + 1] - begin[r];
+        if (bin[r] == SPSP_SPLIT_DROP || !len) continue;
+        uint64_t& a = at[bin[r]];
+        memcpy(o + a, text + begin[r], len);
+        a += len;
+        if (newline(r)) o[a++] = '\n';
+    }
+    *out = o; *n_out = total; *bin_off = off; *bin_records = rec;
+    return SPSP_OK;
+}
+
+namespace {
+
+enum SplitWord { kSwNone = 0, kSwBest, kSwTaxon, kSwDepth };
+
+// the word of a call with classify rows (taxonomy == false) or taxonomy rows, or its refusal; *d: the depth of depth=<d>
+int split_word_for(const char* what, bool taxonomy, SplitWord* word, uint32_t* d) {
+    using namespace spsp;
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    *d = 0;
+    *word = !strcmp(what, "best") ? kSwBest : !strcmp(what, "taxon") ? kSwTaxon : extract_word_number(what, "depth", d) ? kSwDepth : kSwNone;
+    if (*word == kSwNone) {
+        set_error("split: '%.64s' names no bins (%s)", what, taxonomy ? "with a taxonomy: taxon, depth=<d>" : "best");
+        return SPSP_ERR_ARG;
+    }
+    if ((*word != kSwBest) != taxonomy) {
+        set_error(taxonomy ? "split: '%.64s' asks classify's rows, these are a taxonomy's (taxon, depth=<d>)"
+                           : "split: '%.64s' asks a taxonomy's rows, these are classify's (best)", what);
+        return SPSP_ERR_ARG;
+    }
+    if (*word == kSwDepth && (*d == 0 || *d > kTxMaxDepth)) { set_error("split: '%.64s': the depth must be 1 .. %u", what, kTxMaxDepth); return SPSP_ERR_ARG; }
+    return SPSP_OK;
+}
+
+}  // namespace
+
+extern "C" int spsp_split_word_check_host(const char* what, int taxonomy) {
+    SplitWord word; uint32_t d = 0;
+    return split_word_for(what, taxonomy != 0, &word, &d);
+}
+
+extern "C" int spsp_split_bins_classify_host(const char* what, const spsp_classify_record* records, const spsp_classify_hit* hits, uint64_t n_records, uint32_t top,
+                                             uint32_t n_ref, uint32_t* bin, uint32_t* n_bins) {
+    using namespace spsp;
+    if (n_bins) *n_bins = 0;
+    if (!n_bins || (n_records && (!records || !hits || !bin))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (top == 0 || top > kCfMaxTop) { set_error("top must be 1 .. %u (top = %u)", kCfMaxTop, top); return SPSP_ERR_ARG; }
+    if (n_ref == 0 || n_ref > 65535u) { set_error("n_ref must be 1 .. 65535 (n_ref = %u)", n_ref); return SPSP_ERR_ARG; }
+    SplitWord word; uint32_t d = 0;
+    if (const int rc = split_word_for(what, false, &word, &d)) return rc;
+    for (uint64_t r = 0; r < n_records; ++r) {
+        const uint32_t listed = records[r].listed;
+        if (listed > top) { set_error("split: record %llu lists %u matches, top = %u", (unsigned long long)r, listed, top); return SPSP_ERR_ARG; }
+        const uint32_t j = listed ? hits[r * top].reference : n_ref;
+        if (j > n_ref || (listed && j == n_ref)) { set_error("split: record %llu names reference %u, the index has %u", (unsigned long long)r, j, n_ref); return SPSP_ERR_ARG; }
+        bin[r] = j;
+    }
+    *n_bins = n_ref + 1;
+    return SPSP_OK;
+}
+
+extern "C" int spsp_split_bins_taxonomy_host(const char* what, const spsp_taxonomy_record* records, uint64_t n_records, const uint32_t* parent, const uint32_t* depth,
+                                             uint32_t n_nodes, uint32_t* bin, uint32_t* n_bins) {
+    using namespace spsp;
+    if (n_bins) *n_bins = 0;
+    if (!n_bins || !parent || !depth || (n_records && (!records || !bin))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_nodes == 0 || n_nodes > kTxMaxNodes) { set_error("a taxonomy takes 1 .. %u nodes (T = %u)", kTxMaxNodes, n_nodes); return SPSP_ERR_ARG; }
+    SplitWord word; uint32_t d = 0;
+    if (const int rc = split_word_for(what, true, &word, &d)) return rc;
+    for (uint64_t r = 0; r < n_records; ++r) {
+        uint32_t node = records[r].node;
+        if (node == SPSP_TAXONOMY_NONE) { bin[r] = n_nodes; continue; }
+        if (node >= n_nodes) { set_error("split: record %llu names node %u, the tree has %u", (unsigned long long)r, node, n_nodes); return SPSP_ERR_ARG; }
+        if (word == kSwDepth)
+            for (uint32_t steps = 0; depth[node] > d && steps < kTxMaxDepth && parent[node] < node; ++steps) node = parent[node];   // (a tree of the lineages' making ends every climb)
+        bin[r] = node;
+    }
+    *n_bins = n_nodes + 1;
+    return SPSP_OK;
+}
+
+namespace spsp {
+std::string split_file_name(const char* prefix, uint32_t b, uint32_t n_bins, const char* last_name, const char* tag, const char* suffix) {
+    return std::string(prefix) + "_split_" + (b + 1 == n_bins ? std::string(last_name) : std::to_string(b)) + tag + suffix;
+}
+}  // namespace spsp
+
+extern "C" int spsp_split_csv_host(const char* file_prefix, const char* const* names, const char* last_name, uint32_t n_bins, const uint64_t* bin_records,
+                                   const uint64_t* bin_off, const char* suffix, const uint64_t* bin_off_mates, const char* suffix_mates, char** text, uint64_t* len) {
+    using namespace spsp;
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!text || !len || !file_prefix || !last_name || !bin_records || !bin_off || !suffix || (n_bins > 1 && !names) || (bin_off_mates && !suffix_mates)) {
+        set_error("NULL argument");
+        return SPSP_ERR_ARG;
+    }
+    if (n_bins == 0 || n_bins > kSpMaxBins) { set_error("split: n_bins must be 1 .. %u (n_bins = %u)", kSpMaxBins, n_bins); return SPSP_ERR_ARG; }
+    std::string s = bin_off_mates ? "bin,name,records,bytes_1,file_1,bytes_2,file_2\n" : "bin,name,records,bytes,file\n";
+    for (uint32_t b = 0; b < n_bins; ++b) {
+        if (!bin_records[b]) continue;
+        const bool last = b + 1 == n_bins;
+        if (!last && !names[b]) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+        s += last ? std::string(last_name) : std::to_string(b);
+        s += ","; s += last ? last_name : names[b];
+        s += "," + std::to_string(bin_records[b]) + "," + std::to_string(bin_off[b + 1] - bin_off[b]) + ",";
+        s += split_file_name(file_prefix, b, n_bins, last_name, bin_off_mates ? "_1" : "", suffix);
+        if (bin_off_mates) s += "," + std::to_string(bin_off_mates[b + 1] - bin_off_mates[b]) + "," + split_file_name(file_prefix, b, n_bins, last_name, "_2", suffix_mates);
+        s += "\n";
+    }
+    *text = (char*)malloc(s.size() + 1);
+    if (!*text) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    memcpy(*text, s.c_str(), s.size() + 1);
+    *len = s.size();
+    return SPSP_OK;
+}

@@ -354,6 +354,13 @@ struct spsp_ctx {
     hipEvent_t ex_ev[4] = {};            // while timing is on: in front of the starts, the offsets, the copy, and behind it
     uint32_t ex_marked = 0;              // ... which of them the call in flight has recorded
     double ex_ms[3] = {};                // their milliseconds since spsp_extract_stage_ms last read them: starts, offsets, copy
+    // split (spsp_split.hip), in the extraction's words, tiles, starts and output: the records' bins, the run table (the runs'
+    // prefix of kept bytes and source starts in record order, the sort's keys and values twice, the sorted runs' source and output
+    // starts), and the bins' offsets
+    spsp::DevBuf sp_bin, sp_runs, sp_off;
+    hipEvent_t sp_ev[6] = {};            // while timing is on: in front of the starts, the runs, the order, the offsets, the copy, and behind it
+    uint32_t sp_marked = 0;
+    double sp_ms[5] = {};                // spsp_split_stage_ms: starts, runs, order, offsets, copy
     // union of two record batches (spsp_union.hip): the output arrays, and the work area (the flag word, the three offset arrays,
     // a place in A per entry of B, the "new" ballot words of B's entries, the tiles' counts and their scan)
     spsp::DevBuf un_mn, un_lo, un_hi, un_work;
@@ -561,6 +568,10 @@ struct RecordBatch { uint32_t first_record, n_records; const uint32_t* mn; const
 // the flags, runs the extraction on `side` and brings the kept bytes to `out`.  write: <out_prefix>_extract.fa or .fq (by the
 // text's kind), gzip level 1 with ".gz" appended when gz, and with chatter the line of what was kept.  tag: "" for a records file
 // alone; "_1" and "_2" for the two mates of the paired form, whose files are <out_prefix>_extract_1.* and <out_prefix>_extract_2.*
+// The same hook in its second form, the split (spsp_split.hip; `split` set by the entry): `bins` (the driver's: its rows ->
+// bin[n_rec] and n_bins) takes the place of `flags`, on_text runs the split on `side` and brings every bin's slice to `out`, which
+// bin_off cuts.  bin_names (n_bins - 1) and last_name are the driver's, for the manifest.  extract_write then writes one file per
+// bin with records, <out_prefix>_split_<b><tag>.fa|fq[.gz], and <out_prefix>_split.csv.gz
 struct ExtractRun {
     const char* what = nullptr;
     const char* tag = "";
@@ -569,9 +580,20 @@ struct ExtractRun {
     bool fastq = false;
     uint64_t n_rec = 0, n_kept = 0;
     std::vector<uint8_t> out;
+    bool split = false;
+    std::function<int(uint32_t, uint32_t*, uint32_t*)> bins;
+    uint32_t n_bins = 0;
+    std::vector<uint64_t> bin_off, bin_records;
+    std::vector<const char*> bin_names;
+    const char* last_name = "";
+    uint64_t bins_written = 0;
     int on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_rec);
+    int split_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_rec);
     int write(spsp_ctx* ctx, const char* out_prefix, int chatter);
 };
+// spsp_split.hip: the files and the manifest of a split run (mates: null, or the second mate's run); spsp_host.cpp: a bin's file name
+int split_write(spsp_ctx* ctx, ExtractRun* run, ExtractRun* mates, const char* out_prefix, int chatter);
+std::string split_file_name(const char* prefix, uint32_t b, uint32_t n_bins, const char* last_name, const char* tag, const char* suffix);
 int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
                          std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
                          const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract = nullptr);
@@ -666,12 +688,54 @@ int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
 // (spsp_extract_plan_host, spsp_host.cpp):
 constexpr uint32_t kExTile = 4096;                         // bytes of the text per workgroup of the starts pass (the ingest's tile)
 constexpr uint32_t kExStretch = 16384;                     // bytes of the output one workgroup of the copy owns
+constexpr uint32_t kExThreads = 256, kExRecsPerLane = 8, kExRecTile = kExThreads * kExRecsPerLane;   // every kernel: 4 waves; records per workgroup of the run table's passes
+constexpr uint32_t kExStores = kExStretch / (kExThreads * 16);   // rounds of 16-byte stores a workgroup of the copy makes
+// the words of one call on the device (64 bits each), ctx->ex_words.  The split (spsp_split.hip) uses them as the extraction does
+enum ExWord {
+    kExFastq = 0,   // k_ex_tail: 1 when the text is FASTQ
+    kExLimit,       // ... where the content ends (FASTA: n)
+    kExEnd,         // ... where the last record ends: begin[n_rec]
+    kExUnits,       // the first scan's total: FASTA the starts behind byte 0, FASTQ the content's newlines (+ two words of the scan's)
+    kExRecs = 6,    // k_ex_starts: the records
+    kExBad,         // bit 0: a FASTQ content whose lines are not a multiple of four; bit 1: a pair of begin[] out of order or range;
+                    // bit 2 (the split): more runs than the host counted from the bins
+    kExSrc,         // the second scan's totals: the source bytes kept,
+    kExRunsKept,    // ... the runs (low half) and the records kept (high half)
+    kExNl,          // k_ex_rec_write: 1 when the last kept range gets its newline
+    kExBlank,       // k_ex_tail: 1 when something follows the blank tail's first newline (the ingest's blank_tail): a content of
+    kExEndEmpty,    // ... 4r + 3 lines then has an empty quality line, which ends here (behind the tail's second newline, or at n)
+    kSpOut,         // the split's third scan's total: the output's bytes (+ one word of the scan's)
+    kSpNlAt = 15,   // the split: the output byte that is the appended newline, or ~0
+    kExWords = 16
+};
+struct ExSum { unsigned long long a; uint32_t b, c; };   // 16 bytes: bytes (or starts), runs, records kept
+// the launches of the starts, for the extraction and the split (spsp_extract.hip).  ex_front: the text's alignment and its tiles.
+// ex_count_launch: the tail, the tiles' sums and their scan -- everything that does not need n_rec -- with the call's words cleared
+// in front.  ex_starts_launch: begin[0 .. cap] in ctx->ex_begin.  ex_scan_launch: out[i] = the sums of in[0 .. i), totals[0] = all a,
+// totals[1] = all b | all c << 32, by one workgroup.  ex_refuse_lines: the refusal of a FASTQ content of `lines` lines.  No host wait
+int ex_front(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t* n_tiles);
+int ex_count_launch(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t n_tiles);
+int ex_starts_launch(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t n_tiles, uint32_t cap);
+int ex_scan_launch(spsp_ctx* ctx, const ExSum* d_in, uint64_t n_items, ExSum* d_out, unsigned long long* d_totals);
+int ex_refuse_lines(uint64_t lines);
 // begin[0 .. n_rec] in a context-owned buffer, with one host wait (for n_rec); *fastq (may be null): what the text is
 int records_extents_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t** d_begin, uint32_t* n_rec, bool* fastq);
 // the kept records back to back in a context-owned buffer, with one host wait (for n_out).  d_begin == null: the starts are made
 // here, for n_rec records -- a text that holds another number is SPSP_ERR_ARG behind the wait, nothing having left the buffers
 int records_extract_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const uint64_t* d_begin, uint32_t n_rec, const uint8_t* h_keep,
                          uint8_t** d_out, uint64_t* n_out, uint64_t* n_kept, bool* fastq);
+// spsp_build.hip: the stable LSD radix sort of (64-bit key, 32-bit value) pairs by the keys' low `bits` bits, eight bits a pass
+// (k_rs_hist, launch_scan_u32, k_rs_scatter per pass; tiles of kRsTile pairs; the histograms in ctx->bl_hist).  The result is in
+// (*keys_io, *vals_io): the buffers swap with every pass.  bits == 0 launches nothing.  Queued on the context's stream: no host wait
+constexpr uint32_t kRsThreads = 256, kRsPer = 8, kRsTile = kRsThreads * kRsPer;
+int radix_sort_pairs(spsp_ctx* ctx, uint64_t** keys_io, uint32_t** vals_io, uint64_t* keys_tmp, uint32_t* vals_tmp, uint32_t n, uint32_t bits);
+// spsp_split.hip: every record of a text written to the slice of its bin (the rule: include/spsp.h, "split").  What the kernels cut
+// at is the extraction's (kExStretch, kExRecTile) and the sort's (kRsTile): spsp_split_plan_host, spsp_host.cpp
+constexpr uint32_t kSpMaxBins = 1u << 24;
+// the bins' slices back to back in the context's output buffer (the extraction's: a split and an extraction on one context
+// overwrite each other's output), with one host wait.  d_begin == null: the starts are made here, for n_rec records
+int records_split_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, const uint64_t* d_begin, uint32_t n_rec, const uint32_t* h_bin, uint32_t n_bins,
+                       uint8_t** d_out, uint64_t* n_out, uint64_t* h_bin_off, uint64_t* h_bin_records, bool* fastq);
 // spsp_union.hip: per record the union of two sorted key lists (the rule: include/spsp.h, "paired records").  What the kernels cut
 // at (spsp_union_plan_host, spsp_host.cpp):
 constexpr uint32_t kUnThreads = 256;                       // every union kernel: 4 waves, a lane per key

@@ -406,13 +406,21 @@ static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
     rc = spsp_taxonomy_lineages_host((const char*)lin, n_lin, n_ref, ref_node.data(), &parent, &depth, extract ? &size : nullptr, &blob, &blob_len, &T);
     spsp_free(lin);
     if (rc) return rc;
-    if (extract) {
+    if (extract && !extract->split) {
         // (the word's node against the tree: still before any sketch is read)
         if ((rc = spsp_extract_word_check_host(extract->what, 1, T))) { spsp_free(parent); spsp_free(depth); spsp_free(size); spsp_free(blob); return rc; }
         extract->flags = [&, size, T](uint32_t n_rec, uint8_t* keep) { return spsp_extract_flags_taxonomy_host(extract->what, recs->data(), n_rec, size, T, keep); };
     }
     std::vector<const char*> node_names(T);
     for (uint64_t at = 0, t = 0; t < T; ++t) { node_names[t] = blob + at; at += strlen(blob + at) + 1; }
+    for (ExtractRun* e : {extract, extract_mates})
+        if (e && e->split) {                               // (the names the report prints: the nodes')
+            e->bins = [&, parent, depth, T](uint32_t n_rec, uint32_t* bin, uint32_t* n_bins) {
+                return spsp_split_bins_taxonomy_host(extract->what, recs->data(), n_rec, parent, depth, T, bin, n_bins);
+            };
+            e->bin_names = node_names;
+            e->last_name = "unclassified";
+        }
     FilesRun run(ctx, paths, n_ref, chatter);
     std::vector<std::string> names;
     double t1 = 0;
@@ -482,7 +490,7 @@ extern "C" int spsp_taxonomy_device(spsp_ctx* ctx, const void* d_q_minimizer, co
 static int taxonomy_files_entry(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
                                 uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
                                 spsp_taxonomy_record** records, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out,
-                                bool paired = false, const char* mates_path = nullptr) {
+                                bool paired = false, const char* mates_path = nullptr, bool split = false) {
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
     if (n_kept) *n_kept = 0;
@@ -491,15 +499,15 @@ static int taxonomy_files_entry(spsp_ctx* ctx, const char* const* index_paths, u
     if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
     int rc;
     if ((rc = taxonomy_check_args(min_keys, num, den))) return rc;
-    if (what && (rc = spsp_extract_word_check_host(what, 1, 0xffffffffu))) return rc;   // (the word, before any file is read; its node once the tree is)
+    if (what && (rc = split ? spsp_split_word_check_host(what, 1) : spsp_extract_word_check_host(what, 1, 0xffffffffu))) return rc;   // (the word, before any file is read; its node once the tree is)
     SPSP_HIP(hipSetDevice(ctx->device));
     std::vector<spsp_taxonomy_record> got;
     ExtractRun extract, extract_mates;
-    extract.what = extract_mates.what = what; extract.gz = extract_mates.gz = gz;
+    extract.what = extract_mates.what = what; extract.gz = extract_mates.gz = gz; extract.split = extract_mates.split = split;
     if (mates_path) { extract.tag = "_1"; extract_mates.tag = "_2"; }
     if ((rc = taxonomy_files(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, &got,
                              what ? &extract : nullptr, mates_path, what && mates_path ? &extract_mates : nullptr))) return rc;
-    if (n_kept) *n_kept = extract.n_kept;
+    if (n_kept) *n_kept = split ? extract.bins_written : extract.n_kept;
     if (bytes_out) *bytes_out = extract.out.size() + extract_mates.out.size();
     if (n_records) *n_records = got.size();
     if (records && (rc = give_rows(got, records))) return rc;
@@ -528,6 +536,15 @@ extern "C" int spsp_taxonomy_files_paired(spsp_ctx* ctx, const char* const* inde
                                           uint64_t* n_kept, uint64_t* bytes_out) {
     return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
                                 what, gz, n_kept, bytes_out, true, mates_path);
+}
+
+extern "C" int spsp_taxonomy_files_split(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
+                                         const char* lineages_path, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix,
+                                         int chatter, double rate, const char* what, int gz, spsp_taxonomy_record** records, uint64_t* n_records,
+                                         uint64_t* n_bins_written, uint64_t* bytes_out) {
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
+                                what, gz, n_bins_written, bytes_out, false, mates_path, true);
 }
 
 extern "C" int spsp_taxonomy_stage_ms(spsp_ctx* ctx, double* ms) {
