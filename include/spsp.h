@@ -1616,6 +1616,107 @@ int spsp_taxonomy_files_split(spsp_ctx* ctx, const char* const* index_paths, uin
                               double rate, const char* what, int gz, spsp_taxonomy_record** records /* may be NULL; spsp_free */,
                               uint64_t* n_records /* may be NULL */, uint64_t* n_bins_written, uint64_t* bytes_out);
 
+/* ------------------------------------------------------------- windows ---- */
+/* A long record called stretch by stretch (not in the reference): every record is cut into overlapping windows on the device,
+ * between the ingest and the scan; the windows run as records through the unchanged scan, key extraction, classify and taxonomy
+ * kernels; the answer comes back along the record as SEGMENTS and one MOSAIC line per record.
+ * BASES.  A record r has L bases: the bases the ingest keeps (bytes outside ACGTacgt are deleted); `length` and every position
+ * below count what is left.  Coordinates in the raw text where it holds Ns are not kept: that is this pass's limitation.
+ * WINDOWS.  A width W with k <= W <= 0x7fffffff (else SPSP_ERR_ARG); the step is S = W - (k - 1).
+ *   n_win(r) = max(1, ceil((L - k + 1) / S)): a record of at most W bases is one window, a record shorter than k one window
+ *   without keys, an empty record one empty window.
+ *   Window i of r holds the bases [i S, min(i S + W, L)): every window but a record's last has exactly W bases, and the last has
+ *   at least k when L >= k.  Consecutive windows overlap by k - 1 bases, so every k-mer of the record lies in exactly one window.
+ *   Window i OWNS the stretch [i S, (i + 1) S), a record's last window up to L: the owned stretches tile [0, L).
+ *   The windows of all records follow one another in record order; first_win[0 .. n_rec] is each record's first window and
+ *   n_windows = first_win[n_rec].  More than 0xfffffff0 windows is SPSP_ERR_OVERFLOW (the scan numbers records in 32 bits).
+ * KEY SET.  A window's key set is what spsp_sketch_keys_device returns for the genome made of that window's bases alone (the uint8
+ *   count rule included): classify's Q_r with the window in the record's place.  Every threshold and tie rule of classify or
+ *   taxonomy applies to the window to the letter.
+ * CALL.  A window's call is the bin spsp_split_bins_classify_host("best") gives its row -- with taxonomy rows the bin of
+ *   spsp_split_bins_taxonomy_host("taxon" | "depth=<d>").  The last bin (n_ref, or n_nodes) means no call.
+ * SEGMENT.  A maximal run of consecutive windows of ONE record with the same call.  begin = the first window's owned start, end =
+ *   the last window's owned end; the segments of a record tile [0, L).  A segment carries the sums of its windows' keys, hit_keys
+ *   and support (the rank-1 `shared` of classify rows, the taxon's clade keys of taxonomy rows; 0 where there is no call).
+ * MOSAIC.  One line per record: length, windows, segments, called_windows (windows with a call), calls (the distinct calls other
+ *   than "none"); major = the call other than "none" with the most owned bases, among equals the lower number, with its windows
+ *   and owned bases; second likewise among the other calls; SPSP_WINDOWS_ABSENT (and zeros) where there is no such call; the sums
+ *   of keys and hit_keys.  Integers decide everything; the one printed ratio, f_major = major_bases / length (0 for an empty
+ *   record), decides nothing. */
+#define SPSP_WINDOWS_ABSENT 0xffffffffu
+#define SPSP_WINDOWS_MAX_WIDTH 0x7fffffffu
+typedef struct spsp_segment_row {
+    uint64_t begin, end;             /* the owned stretch [begin, end) in the record's bases */
+    uint64_t keys, hit_keys, support;
+    uint32_t record, segment;        /* the record, and the segment's number within it */
+    uint32_t windows, call;          /* call == n_bins - 1: none */
+} spsp_segment_row;                  /* 56 bytes */
+typedef struct spsp_mosaic_row {
+    uint64_t length, major_bases, second_bases, keys, hit_keys;
+    uint32_t windows, segments, called_windows, calls;
+    uint32_t major, major_windows, second, second_windows;
+} spsp_mosaic_row;                   /* 72 bytes */
+/* What the kernels cut at (any pointer may be NULL): the output bases one workgroup of the copy owns in the ASCII form and in the
+ * packed form (16 KiB of output either way), and the records per workgroup of the counting pass. */
+int spsp_windows_plan_host(uint32_t* stretch_bases, uint32_t* stretch_bases_packed, uint32_t* record_tile);
+/* The counting rule from offsets alone.  first_win: n_rec + 1, the caller's; *win_off: n_windows + 1 base offsets of the windows
+ * in the expanded text, spsp_free(); *n_bases = win_off[n_windows].  SPSP_ERR_ARG for a width outside k .. 0x7fffffff and for
+ * offsets that decrease, SPSP_ERR_OVERFLOW as the rule says (nothing is allocated then). */
+int spsp_records_windows_host(const uint64_t* rec_off /* n_rec + 1 */, uint32_t n_rec, uint32_t k, uint64_t window, uint32_t* first_win /* n_rec + 1 */,
+                              uint64_t** win_off /* spsp_free */, uint64_t* n_windows, uint64_t* n_bases);
+/* The expansion as plain loops over ASCII bases: the windows' bases back to back in *out (spsp_free), the rest as above. */
+int spsp_windows_expand_host(const uint8_t* bases, const uint64_t* rec_off /* n_rec + 1 */, uint32_t n_rec, uint32_t k, uint64_t window, uint8_t** out /* spsp_free */,
+                             uint64_t* n_out, uint32_t* first_win /* n_rec + 1 */, uint64_t** win_off /* spsp_free */, uint64_t* n_windows);
+/* Segments and mosaic rows from the windows' calls and addends (n_windows = first_win[n_rec] of each).  *segments: spsp_free();
+ * mosaic: n_rec rows, the caller's.  Rows that contradict themselves are SPSP_ERR_ARG naming the record: a call >= n_bins, or a
+ * first_win that is not what the rule makes of the offsets. */
+int spsp_windows_segments_host(const uint32_t* call, const uint32_t* keys, const uint32_t* hit_keys, const uint32_t* support, const uint32_t* first_win /* n_rec + 1 */,
+                               const uint64_t* rec_off /* n_rec + 1 */, uint32_t n_rec, uint32_t k, uint64_t window, uint32_t n_bins,
+                               spsp_segment_row** segments /* spsp_free */, uint64_t* n_segments, spsp_mosaic_row* mosaic /* n_rec */);
+/* The texts of <prefix>_segments.csv.gz -- "record,name,segment,begin,end,windows,call,call_name,keys,hit_keys,support" -- and of
+ * <prefix>_mosaic.csv.gz -- "record,name,length,windows,segments,called_windows,calls,major,major_name,major_windows,major_bases,
+ * f_major,second,second_name,second_windows,second_bases,keys,hit_keys".  call_names: n_bins - 1 (the references' names or the
+ * nodes'); the last bin prints as last_name ("unmatched", "unclassified") in both columns; an absent major or second prints as
+ * empty fields.  *text is released with spsp_free(). */
+int spsp_segments_csv_host(const spsp_segment_row* segments, uint64_t n_segments, const char* const* record_names, uint32_t n_rec, const char* const* call_names,
+                           const char* last_name, uint32_t n_bins, char** text, uint64_t* len);
+int spsp_mosaic_csv_host(const spsp_mosaic_row* mosaic, uint32_t n_rec, const char* const* record_names, const char* const* call_names, const char* last_name,
+                         uint32_t n_bins, int precision, char** text, uint64_t* len);
+/* Only the refusals of a call word (best; with a taxonomy: taxon, depth=<d>): the split's words. */
+int spsp_windows_word_check_host(const char* what, int taxonomy);
+/* The expansion on the device.  d_bases: the cleaned bases of a text in HBM in either form the ingest writes -- ASCII (packed == 0)
+ * or the 2-bit words of SPSP_SCAN_PACKED_INPUT (16 bases per dword, first base in bits 31:30), 16-byte aligned, the packed form
+ * with its readable bytes behind; d_rec_off: the records' n_rec + 1 base offsets on the device.  *d_out: the windows' bases back to
+ * back in the same form, in a buffer the context owns (valid until its next windows call): zero behind the last base up to a whole
+ * stretch, 256 zero bytes behind that, 16-byte aligned -- what a scan takes.  *d_win_off: the windows' n_windows + 1 base offsets
+ * on the device, the context's as well; h_first_win: n_rec + 1, the caller's.  Launches: per spsp_windows_plan_host's record tile
+ * the windows and the expanded bases; one 64-bit scan; ONE host wait, for the counts; per tile the records' first windows and
+ * output starts; per window its offset and its source; then the copy, balanced by OUTPUT: a workgroup owns a stretch of whole
+ * 16-byte stores, finds the windows that cross it by binary search over the new offsets, and writes every store whole.  ASCII: two
+ * aligned loads and a byte shift inside a window, byte by byte across windows.  Packed: per output dword a funnel shift of two
+ * source dwords by twice the source's offset in its dword, looped where a dword holds bases of several windows.  Nothing is read
+ * or written outside the buffers; no store is shared between workgroups.  Refused: the width (ARG), offsets that decrease or leave
+ * the bases (ARG), too many windows (OVERFLOW). */
+int spsp_records_windows_device(spsp_ctx* ctx, const void* d_bases, uint64_t n_bases, const void* d_rec_off, uint32_t n_rec, uint32_t k, uint64_t window, int packed,
+                                void** d_out, uint64_t* n_out, void** d_win_off, uint32_t* h_first_win /* n_rec + 1 */, uint64_t* n_windows);
+/* While the context's timing is on a windows call records events between its launches; this reads the milliseconds added up since
+ * the last read and clears them. */
+int spsp_windows_stage_ms(spsp_ctx* ctx, double* ms /* 3: count, offsets, copy */);
+/* The whole-file driver over windows: the arguments of spsp_classify_files plus the width and the call word ("best").  Behind the
+ * ingest and in front of the scan the expansion runs on the second context; the scan, the key extraction and spsp_classify_device
+ * then see windows as records, in batches of at most 65 535 windows; the header count is still held against the real records.
+ * Writes <out_prefix>_segments.csv.gz and <out_prefix>_mosaic.csv.gz in the place of the per-record CSVs (the per-record call of a
+ * windowed run is the mosaic line); nothing on any failure; a refused word or width is refused before any file is read.  Handed
+ * out (each may be NULL; spsp_free): the windows' rows and hits, first_win (n_records + 1), the segments and the mosaic rows. */
+int spsp_classify_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window, const char* what,
+                                spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
+                                spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic);
+int spsp_taxonomy_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
+                                const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
+                                spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,14 @@ TAXONOMY_RECORD_DTYPE = np.dtype([("length", "<u8"), ("keys", "<u4"), ("hit_keys
                                   ("clade", "<u4"), ("direct", "<u4"), ("winners", "<u4")])
 TAXONOMY_NONE = 0xffffffff
 
+# spsp_segment_row / spsp_mosaic_row: a stretch of a record with one call, and a record's line of a windowed run (include/spsp.h)
+SEGMENT_ROW_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8"), ("keys", "<u8"), ("hit_keys", "<u8"), ("support", "<u8"), ("record", "<u4"), ("segment", "<u4"),
+                              ("windows", "<u4"), ("call", "<u4")])
+MOSAIC_ROW_DTYPE = np.dtype([("length", "<u8"), ("major_bases", "<u8"), ("second_bases", "<u8"), ("keys", "<u8"), ("hit_keys", "<u8"), ("windows", "<u4"),
+                             ("segments", "<u4"), ("called_windows", "<u4"), ("calls", "<u4"), ("major", "<u4"), ("major_windows", "<u4"), ("second", "<u4"),
+                             ("second_windows", "<u4")])
+WINDOWS_ABSENT = 0xffffffff
+
 FILE_CALLBACK = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(SketchStats), C.c_char_p)
 
 SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8"), ("len", "<u4"), ("rev", "<u4")])
@@ -169,6 +177,8 @@ ABI_SYMBOLS = [
     "spsp_split_plan_host", "spsp_records_split_host", "spsp_split_bins_classify_host", "spsp_split_bins_taxonomy_host", "spsp_split_word_check_host",
     "spsp_split_csv_host", "spsp_records_split_device", "spsp_split_stage_ms", "spsp_classify_files_split", "spsp_taxonomy_files_split",
     "spsp_pairs_names_host", "spsp_union_plan_host", "spsp_records_union_device", "spsp_union_stage_ms", "spsp_classify_files_paired", "spsp_taxonomy_files_paired",
+    "spsp_windows_plan_host", "spsp_records_windows_host", "spsp_windows_expand_host", "spsp_windows_segments_host", "spsp_segments_csv_host", "spsp_mosaic_csv_host",
+    "spsp_windows_word_check_host", "spsp_records_windows_device", "spsp_windows_stage_ms", "spsp_classify_files_windows", "spsp_taxonomy_files_windows",
 ]
 
 _lib = None
@@ -490,6 +500,30 @@ def lib():
         L.spsp_classify_files_paired.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, u32, i32, cp, i32, dbl, cp, i32, P(vp), P(vp), P(u64), P(u64), P(u64)]
         L.spsp_taxonomy_files_paired.restype = i32
         L.spsp_taxonomy_files_paired.argtypes = [vp, P(cp), u32, cp, cp, cp, u32, u32, u32, i32, cp, i32, dbl, cp, i32, P(vp), P(u64), P(u64), P(u64)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_records_windows_device"):
+        L.spsp_windows_plan_host.restype = i32
+        L.spsp_windows_plan_host.argtypes = [P(u32), P(u32), P(u32)]
+        L.spsp_records_windows_host.restype = i32
+        L.spsp_records_windows_host.argtypes = [vp, u32, u32, u64, vp, P(vp), P(u64), P(u64)]
+        L.spsp_windows_expand_host.restype = i32
+        L.spsp_windows_expand_host.argtypes = [vp, vp, u32, u32, u64, P(vp), P(u64), vp, P(vp), P(u64)]
+        L.spsp_windows_segments_host.restype = i32
+        L.spsp_windows_segments_host.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u64, u32, P(vp), P(u64), vp]
+        L.spsp_segments_csv_host.restype = i32
+        L.spsp_segments_csv_host.argtypes = [vp, u64, P(cp), u32, P(cp), cp, u32, P(vp), P(u64)]
+        L.spsp_mosaic_csv_host.restype = i32
+        L.spsp_mosaic_csv_host.argtypes = [vp, u32, P(cp), P(cp), cp, u32, i32, P(vp), P(u64)]
+        L.spsp_windows_word_check_host.restype = i32
+        L.spsp_windows_word_check_host.argtypes = [cp, i32]
+        L.spsp_records_windows_device.restype = i32
+        L.spsp_records_windows_device.argtypes = [vp, vp, u64, vp, u32, u32, u64, i32, P(vp), P(u64), P(vp), vp, P(u64)]
+        L.spsp_windows_stage_ms.restype = i32
+        L.spsp_windows_stage_ms.argtypes = [vp, P(dbl)]
+        L.spsp_classify_files_windows.restype = i32
+        L.spsp_classify_files_windows.argtypes = [vp, P(cp), u32, cp, u32, u32, u32, u32, i32, cp, i32, dbl, u64, cp, P(vp), P(vp), P(u64), P(vp), P(u64), P(vp),
+                                                  P(u64), P(vp)]
+        L.spsp_taxonomy_files_windows.restype = i32
+        L.spsp_taxonomy_files_windows.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, i32, cp, i32, dbl, u64, cp, P(vp), P(u64), P(vp), P(u64), P(vp), P(u64), P(vp)]
     _lib = L
     return L
 
@@ -1064,6 +1098,94 @@ def split_csv(file_prefix, names, last_name, bin_records, bin_off, suffix, bin_o
                                      None if mates is None else mates.ctypes.data, None if suffix_mates is None else suffix_mates.encode(), C.byref(text),
                                      C.byref(n)))
     return _take(text, n.value)
+
+
+def windows_plan():
+    """spsp_windows_plan_host: what the windows' kernels cut at -> dict(stretch_bases, stretch_bases_packed: the output bases one
+    workgroup of the copy owns in the ASCII and in the packed form; record_tile: the records per workgroup of the counting pass)"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_windows_plan_host(C.byref(a), C.byref(b), C.byref(c)))
+    return {"stretch_bases": a.value, "stretch_bases_packed": b.value, "record_tile": c.value}
+
+
+def records_windows(rec_off, k, window):
+    """spsp_records_windows_host: the counting rule from the records' base offsets alone -> (first_win: np.uint32[n_rec + 1],
+    win_off: np.uint64[n_windows + 1], the windows' base offsets in the expanded text)"""
+    rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    if len(rec_off) < 1:
+        raise ValueError("records_windows: n_rec + 1 offsets")
+    n_rec = len(rec_off) - 1
+    first = np.zeros(n_rec + 1, dtype=np.uint32)
+    off, n_win, n_bases = C.c_void_p(), C.c_uint64(), C.c_uint64()
+    _check(lib().spsp_records_windows_host(rec_off.ctypes.data, n_rec, k, window, first.ctypes.data, C.byref(off), C.byref(n_win), C.byref(n_bases)))
+    return first, np.frombuffer(_take(off, (n_win.value + 1) * 8), dtype=np.uint64).copy()
+
+
+def windows_expand(bases, rec_off, k, window):
+    """spsp_windows_expand_host: the windows' bases back to back, as plain loops over ASCII bases -> (np.uint8 array, first_win,
+    win_off): what the device pass is held against"""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    if len(rec_off) < 1 or int(rec_off[-1]) > len(bases):
+        raise ValueError("windows_expand: n_rec + 1 offsets that end inside the bases")
+    n_rec = len(rec_off) - 1
+    first = np.zeros(n_rec + 1, dtype=np.uint32)
+    out, n_out, off, n_win = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_windows_expand_host(bases.ctypes.data if len(bases) else None, rec_off.ctypes.data, n_rec, k, window, C.byref(out), C.byref(n_out),
+                                          first.ctypes.data, C.byref(off), C.byref(n_win)))
+    return (np.frombuffer(_take(out, n_out.value), dtype=np.uint8).copy(), first,
+            np.frombuffer(_take(off, (n_win.value + 1) * 8), dtype=np.uint64).copy())
+
+
+def windows_segments(call, keys, hit_keys, support, first_win, rec_off, k, window, n_bins):
+    """spsp_windows_segments_host: the windows' calls (n_bins - 1: none) and addends -> (segments: SEGMENT_ROW_DTYPE[n_segments],
+    mosaic: MOSAIC_ROW_DTYPE[n_rec]).  A call >= n_bins or a first_win that is not the rule's is refused, naming the record"""
+    call, keys, hit_keys, support, first_win = (np.ascontiguousarray(x, dtype=np.uint32) for x in (call, keys, hit_keys, support, first_win))
+    rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    n_rec = len(rec_off) - 1
+    if n_rec < 0 or len(first_win) != n_rec + 1 or not (len(call) == len(keys) == len(hit_keys) == len(support)) or len(call) < int(first_win[-1]):
+        raise ValueError("windows_segments: n_rec + 1 offsets and first windows, and one call and three addends per window")
+    mosaic = np.zeros(max(n_rec, 1), dtype=MOSAIC_ROW_DTYPE)
+    seg, n_seg = C.c_void_p(), C.c_uint64()
+    ptr = lambda x: x.ctypes.data if len(x) else None
+    _check(lib().spsp_windows_segments_host(ptr(call), ptr(keys), ptr(hit_keys), ptr(support), first_win.ctypes.data, rec_off.ctypes.data, n_rec, k, window, n_bins,
+                                            C.byref(seg), C.byref(n_seg), mosaic.ctypes.data))
+    return np.frombuffer(_take(seg, n_seg.value * SEGMENT_ROW_DTYPE.itemsize), dtype=SEGMENT_ROW_DTYPE).copy(), mosaic[:n_rec]
+
+
+def segments_csv(segments, record_names, call_names, last_name):
+    """spsp_segments_csv_host: the text of <prefix>_segments.csv.gz; call_names: n_bins - 1, last_name: the last bin's"""
+    segments = np.ascontiguousarray(segments, dtype=SEGMENT_ROW_DTYPE)
+    rn, _a = _paths_array(record_names)
+    cn, _b = _paths_array(call_names)
+    text, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_segments_csv_host(segments.ctypes.data if len(segments) else None, len(segments), rn, len(record_names), cn, last_name.encode(),
+                                        len(call_names) + 1, C.byref(text), C.byref(n)))
+    return _take(text, n.value).decode()
+
+
+def mosaic_csv(mosaic, record_names, call_names, last_name, precision=6):
+    """spsp_mosaic_csv_host: the text of <prefix>_mosaic.csv.gz, one line per record"""
+    mosaic = np.ascontiguousarray(mosaic, dtype=MOSAIC_ROW_DTYPE)
+    if len(mosaic) != len(record_names):
+        raise ValueError("mosaic_csv: one name per record")
+    rn, _a = _paths_array(record_names)
+    cn, _b = _paths_array(call_names)
+    text, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_mosaic_csv_host(mosaic.ctypes.data if len(mosaic) else None, len(mosaic), rn, cn, last_name.encode(), len(call_names) + 1, precision,
+                                      C.byref(text), C.byref(n)))
+    return _take(text, n.value).decode()
+
+
+def _windows_result(first, n_rec, seg, n_seg, mos):
+    return {"first_win": np.frombuffer(_take(first, (n_rec + 1) * 4), dtype=np.uint32).copy(),
+            "segments": np.frombuffer(_take(seg, n_seg * SEGMENT_ROW_DTYPE.itemsize), dtype=SEGMENT_ROW_DTYPE).copy(),
+            "mosaic": np.frombuffer(_take(mos, n_rec * MOSAIC_ROW_DTYPE.itemsize), dtype=MOSAIC_ROW_DTYPE).copy()}
+
+
+def windows_word_check(what, taxonomy):
+    """spsp_windows_word_check_host: only the refusals of a windows call word (taxonomy: the rows will be a taxonomy's)"""
+    _check(lib().spsp_windows_word_check_host(what.encode(), 1 if taxonomy else 0))
 
 
 def taxonomy_csv(records, record_names, parent, node_names, precision=6):
@@ -1871,7 +1993,7 @@ class Context:
     pairs_names = staticmethod(pairs_names)
 
     def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
-                       split=None):
+                       split=None, window=None, window_call=None):
         """spsp_classify_files: the sketch files of the references and a FASTA / FASTQ file of records (gzip or plain) ->
         <prefix>_classify.csv.gz, <prefix>_classify_summary.csv.gz and (records, hits[n, top]).  rate: as compare_files (0.0, a
         rate, or "auto"); sketches of different rates need one.  extract: a word (matched, unmatched, best=<j>, listed=<j>) --
@@ -1880,11 +2002,24 @@ class Context:
         record p of the two files is one pair, classified by the keys of both mates, and extract writes <prefix>_extract_1.* and
         <prefix>_extract_2.*.  split: the word `best` -- spsp_classify_files_split: every record goes to <prefix>_split_<j>.fa or .fq
         of its rank-1 match (or _split_unmatched.*; with mates_path _1 and _2 files), <prefix>_split.csv.gz lists them;
-        self.last_split = dict(bins, records, bytes_out).  Not together with extract"""
+        self.last_split = dict(bins, records, bytes_out).  Not together with extract.  window: a width -- spsp_classify_files_windows:
+        every record is cut into windows of that many bases, the returned rows are the WINDOWS', <prefix>_segments.csv.gz and
+        <prefix>_mosaic.csv.gz take the per-record CSVs' place, and self.last_windows = dict(first_win, segments, mosaic);
+        window_call: the call word (best).  Not together with extract, split or mates_path"""
         arr, _alive = _paths_array(paths)
         recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
         self._cf_n_ref = None
-        if split is not None:
+        if window is not None:
+            if extract is not None or split is not None or mates_path is not None:
+                raise ValueError("classify_files: window is not taken with extract, split or mates_path")
+            first, n_rec, seg, n_seg, mos = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_void_p()
+            _check(lib().spsp_classify_files_windows(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
+                                                     _rate_arg(rate), window, (window_call or "best").encode(), C.byref(recs), C.byref(hits), C.byref(n),
+                                                     C.byref(first), C.byref(n_rec), C.byref(seg), C.byref(n_seg), C.byref(mos)))
+            self.last_windows = _windows_result(first, n_rec.value, seg, n_seg.value, mos)
+        elif window_call is not None:
+            raise ValueError("classify_files: window_call needs window")
+        elif split is not None:
             if extract is not None:
                 raise ValueError("classify_files: split writes every record and extract one subset: one of the two")
             written, out_bytes = C.c_uint64(), C.c_uint64()
@@ -1948,6 +2083,25 @@ class Context:
                                                off.ctypes.data, rec.ctypes.data))
         return self.to_host(out.value, n_out.value, np.uint8), off, rec[:n_bins]
 
+    def records_windows_device(self, d_bases, n_bases, d_rec_off, n_rec, k, window, packed=False):
+        """spsp_records_windows_device: the cleaned bases of a text in HBM (ASCII, or with packed the 2-bit words of
+        SPSP_SCAN_PACKED_INPUT) and the records' base offsets on the device -> (d_out, n_out, d_win_off, first_win: np.uint32[n_rec + 1],
+        n_windows): the windows' bases back to back in the same form and their offsets, both the context's until its next windows call"""
+        first = np.zeros(n_rec + 1, dtype=np.uint32)
+        out, n_out, off, n_win = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_records_windows_device(self._h, d_bases, n_bases, d_rec_off, n_rec, k, window, 1 if packed else 0, C.byref(out), C.byref(n_out),
+                                                 C.byref(off), first.ctypes.data, C.byref(n_win)))
+        return out.value, n_out.value, off.value, first, n_win.value
+
+    def windows_stage_ms(self):
+        """spsp_windows_stage_ms: with timing_enable() on, the milliseconds of the windows calls' launches since the last read ->
+        dict(count, offsets, copy)"""
+        ms = (C.c_double * 3)()
+        _check(lib().spsp_windows_stage_ms(self._h, ms))
+        return dict(zip(("count", "offsets", "copy"), ms))
+
+    windows_plan = staticmethod(windows_plan)
+
     def split_stage_ms(self):
         """spsp_split_stage_ms: with timing_enable() on, the milliseconds of the split calls' launches since the last read ->
         dict(starts, runs, order, offsets, copy)"""
@@ -1992,18 +2146,29 @@ class Context:
         return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
 
     def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
-                       split=None):
+                       split=None, window=None, window_call=None):
         """spsp_taxonomy_files: the sketch files of the references, a FASTA / FASTQ file of records (gzip or plain) and the lineage
         file of the references -> <prefix>_taxonomy.csv.gz, <prefix>_taxonomy_report.csv.gz and the records.  rate: as
         classify_files (0.0, a rate, or "auto"); sketches of different rates need one.  extract: a word (classified, unclassified,
         taxon=<t>, clade=<t>) -- spsp_taxonomy_files_extract: the records it names are written to <prefix>_extract.fa or .fq (".gz"
         appended when gz) as well; self.last_extract = dict(n_kept, bytes_out).  mates_path: as classify_files
         (spsp_taxonomy_files_paired).  split: a word (taxon, depth=<d>) -- spsp_taxonomy_files_split: every record goes to
-        <prefix>_split_<t>.fa or .fq of its node (or _split_unclassified.*), as classify_files; self.last_split"""
+        <prefix>_split_<t>.fa or .fq of its node (or _split_unclassified.*), as classify_files; self.last_split.  window,
+        window_call (taxon, depth=<d>): spsp_taxonomy_files_windows, as classify_files; self.last_windows"""
         arr, _alive = _paths_array(paths)
         recs, n = C.c_void_p(), C.c_uint64()
         self._cf_n_ref = None
-        if split is not None:
+        if window is not None:
+            if extract is not None or split is not None or mates_path is not None:
+                raise ValueError("taxonomy_files: window is not taken with extract, split or mates_path")
+            first, n_rec, seg, n_seg, mos = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_void_p()
+            _check(lib().spsp_taxonomy_files_windows(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
+                                                     prefix.encode(), 0, _rate_arg(rate), window, (window_call or "taxon").encode(), C.byref(recs), C.byref(n),
+                                                     C.byref(first), C.byref(n_rec), C.byref(seg), C.byref(n_seg), C.byref(mos)))
+            self.last_windows = _windows_result(first, n_rec.value, seg, n_seg.value, mos)
+        elif window_call is not None:
+            raise ValueError("taxonomy_files: window_call needs window")
+        elif split is not None:
             if extract is not None:
                 raise ValueError("taxonomy_files: split writes every record and extract one subset: one of the two")
             written, out_bytes = C.c_uint64(), C.c_uint64()

@@ -133,12 +133,14 @@ int main(int argc, char** argv) {
     bool extract = false, extract_plain = false;
     string split_what;               // -j <word> [-u]: with -X, every record goes to the file of its reference or taxon (not in the reference's option string)
     bool split = false;
+    string window_arg;               // -y <W>[:<word>]: with -X, every record is cut into windows of W bases and called stretch by stretch (not in the reference's option string)
+    bool windows = false;
     vector<string> reads_files;      // -D <reads file> [-D <more> ...] [-W <min_count>]: neither letter is in the reference's option string
     bool dp_min_seen = false;
     long long dp_min_count = 1;
     bool profile = false;            // -B <min_keys>: the profile behind the depth of -D (not in the reference's option string either)
     long long pf_min_keys = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:j:")) != -1) {
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:j:y:")) != -1) {
         switch (ch) {
             case 'D': reads_files.push_back(optarg); break;
             case 'W': {
@@ -162,6 +164,7 @@ int main(int argc, char** argv) {
             case 'F': extract_what = optarg; extract = true; break;
             case 'u': extract_plain = true; break;
             case 'j': split_what = optarg; split = true; break;
+            case 'y': window_arg = optarg; windows = true; break;
             case 'Y': {
                 char* e = nullptr;
                 cf_top = strtoll(optarg, &e, 10);
@@ -305,6 +308,23 @@ int main(int argc, char** argv) {
     if (split && spsp_split_word_check_host(split_what.c_str(), taxonomy ? 1 : 0) != SPSP_OK) { cout << "-j: " << spsp_last_error() << endl; return 1; }
     if (extract_plain && !extract && !split) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
     if (extract && spsp_extract_word_check_host(extract_what.c_str(), taxonomy ? 1 : 0, 0xffffffffu) != SPSP_OK) { cout << "-F: " << spsp_last_error() << endl; return 1; }
+    long long window_width = 0;
+    string window_word;
+    if (windows && !classify) { cout << "-y cuts the records of -X <records file> into windows and calls them stretch by stretch: it needs -X" << endl; return 1; }
+    if (windows && (cf_top_seen || paired || extract || split)) {
+        cout << "-y calls every window once and writes segments, not records: not together with -Y, -x, -F or -j" << endl;
+        return 1;
+    }
+    if (windows) {
+        char* e = nullptr;
+        window_width = strtoll(window_arg.c_str(), &e, 10);
+        if (e == window_arg.c_str() || (*e && *e != ':') || window_width < 1 || window_width > 0x7fffffffll) {
+            cout << "-y takes <W>[:<word>], the window's width in bases, an integer in k .. 2147483647, and the call word, not '" << window_arg << "'" << endl;
+            return 1;
+        }
+        window_word = *e == ':' ? string(e + 1) : string(taxonomy ? "taxon" : "best");
+        if (spsp_windows_word_check_host(window_word.c_str(), taxonomy ? 1 : 0) != SPSP_OK) { cout << "-y: " << spsp_last_error() << endl; return 1; }
+    }
     if (cf_opts && !classify) { cout << "-Y and -V belong to the classification of -X <records file>: they need -X" << endl; return 1; }
     if (classify && (query != "" || gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts || select_opts || accumulation || groups ||
                      (nb_opts && nb_metric != SPSP_NEIGHBOUR_CONTAINED))) {
@@ -363,6 +383,7 @@ int main(int argc, char** argv) {
              << "-F Records of -X <records file> to write out again as <prefix>_extract.fa.gz / .fq.gz: matched, unmatched, best=<j>, listed=<j>; with -H: classified, unclassified, taxon=<t>, clade=<t>" << endl
              << "-u Write the records of -F, or the files of -j, plain, not gzipped" << endl
              << "-j Split the records of -X <records file> into <prefix>_split_<b>.fa.gz / .fq.gz, one file per reference (best; the rest in _split_unmatched) or, with -H, per node (taxon, depth=<d>; the rest in _split_unclassified), and <prefix>_split.csv.gz; with -x <prefix>_split_<b>_1.* and _2.*; -u writes them plain" << endl
+             << "-y <W>[:<word>] Windows: cut every record of -X <records file> into windows of W bases (overlapping by k - 1), call each as a record (best; with -H: taxon, depth=<d>) and write <prefix>_segments.csv.gz (stretches with one call) and <prefix>_mosaic.csv.gz (one line per record) in the place of the per-record CSVs; positions count the bases A, C, G, T only" << endl
              << "-x Mates file: with -X <records file>, record p of the two files is one pair, classified by the keys of both mates; -F then writes <prefix>_extract_1.* and <prefix>_extract_2.*" << endl
              << "Ouput arguments:" << endl
              << "-m Minimum value to be output (0.0)" << endl
@@ -430,7 +451,15 @@ int main(int argc, char** argv) {
         // one device, as gather (the driver opens a second context on it for the records)
         spsp_ctx* ctx = nullptr;
         int rc = spsp_create(devices[0], nullptr, &ctx);
-        if (rc == SPSP_OK && split && taxonomy)
+        if (rc == SPSP_OK && windows && taxonomy)
+            rc = spsp_taxonomy_files_windows(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den,
+                                             (int)p, output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                             nullptr, nullptr);
+        else if (rc == SPSP_OK && windows)
+            rc = spsp_classify_files_windows(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den, (int)p,
+                                             output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                             nullptr, nullptr);
+        else if (rc == SPSP_OK && split && taxonomy)
             rc = spsp_taxonomy_files_split(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), paired ? mates_file.c_str() : nullptr, lineages_file.c_str(),
                                            (uint32_t)cf_min_keys, nb_num, nb_den, (int)p, output_name.c_str(), 1, rate, split_what.c_str(), extract_plain ? 0 : 1, nullptr,
                                            nullptr, nullptr, nullptr);

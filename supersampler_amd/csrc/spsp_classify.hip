@@ -492,7 +492,7 @@ static int batch_seams(spsp_ctx* ctx, const spsp_superkmer* d_sk, uint64_t n_sk,
 // on_records: once, behind the scan, with the records' base offsets (n_rec + 1)
 int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
                          std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract) {
+                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract, WindowsRun* windows) {
     int rc;
     double t0 = now_s(), t1;
     const bool fastq = n_text && text[0] == '@';
@@ -504,11 +504,22 @@ int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, co
     FastqLayout fq;
     if (fastq) fastq_tail(text, n_text, &fq.content_end, &fq.blank_tail);
     if ((rc = clean_device_impl(side, side->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed, fastq ? &fq : nullptr))) return rc;
-    t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
-    if (names && names->size() != n_rec) {
+    if (names && names->size() != n_rec) {                 // (held against the REAL records, whatever the passes see)
         set_error("'%s': %zu header line(s) on the host, %u record(s) on the device", path, names->size(), n_rec);
         return SPSP_ERR_FORMAT;
     }
+    if (windows) {
+        // the expansion, between the ingest and the scan: from here on the windows are the records (their bases in the side
+        // context's windows buffer, in the form the ingest wrote).  The real records' offsets and first_win stay with the run
+        windows->rec_off.assign((size_t)n_rec + 1, 0);
+        windows->first_win.assign((size_t)n_rec + 1, 0);
+        SPSP_HIP(hipMemcpyAsync(windows->rec_off.data(), d_off, windows->rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));   // (the expansion waits)
+        uint8_t* w_bases = nullptr; uint64_t* w_off = nullptr; uint64_t w_n = 0, n_win = 0;
+        if ((rc = records_windows_impl(side, d_bases, n_bases, d_off, n_rec, p->k, windows->window, packed, &w_bases, &w_n, &w_off, windows->first_win.data(), &n_win)))
+            return rc;
+        d_bases = w_bases; n_bases = w_n; d_off = w_off; n_rec = (uint32_t)n_win;
+    }
+    t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
     spsp_superkmer* d_sk = nullptr; uint64_t n_sk = 0;
     spsp_params ps = *p;
     if (packed) ps.flags |= SPSP_SCAN_PACKED_INPUT;
@@ -670,7 +681,7 @@ int records_pair_batches(spsp_ctx* ctx, spsp_ctx* const* side, const spsp_params
 int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
                        const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
                        const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1, ExtractRun* extract,
-                       const char* mates_path, ExtractRun* extract_mates) {
+                       const char* mates_path, ExtractRun* extract_mates, WindowsRun* windows) {
     spsp_ctx* ctx = run.ctx;
     int rc = run.load(rate);
     if (!rc) rc = run.refuse_k_eq_m(rc, what_is);
@@ -689,7 +700,7 @@ int records_files_road(FilesRun& run, const char* what_is, const char* const* re
             uint8_t* text = nullptr; uint64_t n_text = 0;
             if (!(rc = spsp_read_file_host(records_paths[f], &text, &n_text)) && (side || !(rc = spsp_create(ctx->device, nullptr, &side))) &&
                 !(rc = spsp_wait_stream(side, ctx)))       // (the last file's keys have been read)
-                rc = records_text_batches(ctx, side, &p, text, n_text, records_paths[f], names, on_records, on_batch, extract);
+                rc = records_text_batches(ctx, side, &p, text, n_text, records_paths[f], names, on_records, on_batch, extract, windows);
             spsp_free(text);
         }
         spsp_ctx* side2 = nullptr;
@@ -728,7 +739,8 @@ int extract_write(spsp_ctx* ctx, ExtractRun* extract, ExtractRun* extract_mates,
 // spsp_classify_files behind its argument checks (mates_path: null, or the paired form with extract_mates beside extract)
 static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys, uint32_t num,
                           uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_classify_record>* recs,
-                          std::vector<spsp_classify_hit>* hits, ExtractRun* extract, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr) {
+                          std::vector<spsp_classify_hit>* hits, ExtractRun* extract, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr,
+                          WindowsRun* windows = nullptr, const char* window_word = nullptr) {
     FilesRun run(ctx, paths, n_ref, chatter);
     std::vector<std::string> names;
     double t1 = 0;
@@ -756,8 +768,22 @@ static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
             return classify_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, top, min_keys, num, den, recs->data() + B.first_record,
                                         hits->data() + (size_t)B.first_record * top);
         },
-        [] { return SPSP_OK; }, &t1, extract, mates_path, extract_mates);
+        [] { return SPSP_OK; }, &t1, extract, mates_path, extract_mates, windows);
     if (rc) return rc;
+    if (windows) {
+        // the rows are the windows': their calls are the split's bins, and the two windowed CSVs take the per-record CSVs' place
+        const size_t n_win = recs->size();
+        std::vector<uint32_t> call(n_win ? n_win : 1, n_ref), keys(call.size(), 0), hit_keys(call.size(), 0), support(call.size(), 0);
+        uint32_t n_bins = 0;
+        if ((rc = spsp_split_bins_classify_host(window_word, recs->data(), hits->data(), n_win, top, n_ref, call.data(), &n_bins))) return rc;
+        for (size_t w = 0; w < n_win; ++w) {
+            keys[w] = (*recs)[w].keys; hit_keys[w] = (*recs)[w].hit_keys;
+            support[w] = (*recs)[w].listed ? (*hits)[w * top].shared : 0u;
+        }
+        if ((rc = windows_write(ctx, windows, run.keys.k, call, keys, hit_keys, support, n_bins, names, paths, "unmatched", precision, out_prefix, t1, chatter))) return rc;
+        if (chatter) { say_common_rate(run.L, n_ref); fflush(stdout); }
+        return SPSP_OK;
+    }
     std::vector<const char*> name_ptr(names.size());
     for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
     char* text = nullptr; uint64_t len = 0;
@@ -859,6 +885,51 @@ extern "C" int spsp_classify_files_split(spsp_ctx* ctx, const char* const* index
     if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
     return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
                                 what, gz, n_bins_written, bytes_out, false, mates_path, true);
+}
+
+extern "C" int spsp_classify_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                           uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
+                                           const char* what, spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win,
+                                           uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic) {
+    if (rows) *rows = nullptr;
+    if (hits) *hits = nullptr;
+    if (first_win) *first_win = nullptr;
+    if (segments) *segments = nullptr;
+    if (mosaic) *mosaic = nullptr;
+    if (n_windows) *n_windows = 0;
+    if (n_records) *n_records = 0;
+    if (n_segments) *n_segments = 0;
+    if (!ctx || !index_paths || !records_path || !out_prefix || !what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    int rc;
+    if ((rc = classify_check_args(top, min_keys, num, den)) || (rc = spsp_windows_word_check_host(what, 0))) return rc;   // (before any file is read)
+    if (window == 0 || window > kWnMaxWidth) {             // (against k: once the sketches' headers are read, in front of the records file)
+        set_error("windows: the width must be k .. %llu (width = %llu)", (unsigned long long)kWnMaxWidth, (unsigned long long)window);
+        return SPSP_ERR_ARG;
+    }
+    SPSP_HIP(hipSetDevice(ctx->device));
+    std::vector<spsp_classify_record> got;
+    std::vector<spsp_classify_hit> got_hits;
+    WindowsRun run;
+    run.window = window;
+    if ((rc = classify_files(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, &got, &got_hits, nullptr, nullptr,
+                             nullptr, &run, what))) return rc;
+    if (n_windows) *n_windows = got.size();
+    if (n_records) *n_records = run.mosaic.size();
+    if (n_segments) *n_segments = run.segments.size();
+    void* given[5] = {};
+    if ((rows && (rc = give_rows(got, rows))) || (rows && !(given[0] = *rows)) || (hits && (rc = give_rows(got_hits, hits))) || (hits && !(given[1] = *hits)) ||
+        (first_win && (rc = give_rows(run.first_win, first_win))) || (first_win && !(given[2] = *first_win)) ||
+        (segments && (rc = give_rows(run.segments, segments))) || (segments && !(given[3] = *segments)) || (mosaic && (rc = give_rows(run.mosaic, mosaic)))) {
+        for (void* g : given) free(g);
+        if (rows) *rows = nullptr;
+        if (hits) *hits = nullptr;
+        if (first_win) *first_win = nullptr;
+        if (segments) *segments = nullptr;
+        if (mosaic) *mosaic = nullptr;
+        return rc ? rc : (int)SPSP_ERR_NOMEM;
+    }
+    return SPSP_OK;
 }
 
 extern "C" int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms) {

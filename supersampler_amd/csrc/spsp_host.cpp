@@ -3272,3 +3272,222 @@ extern "C" int spsp_split_csv_host(const char* file_prefix, const char* const* n
     *len = s.size();
     return SPSP_OK;
 }
+
+// -------------------------------------------------------------------------------------------------------------- windows
+// The host forms of the windows pass, plain loops straight from the rule of include/spsp.h ("windows"): the counting rule, the
+// expansion the device pass is held against, what turns the windows' calls into segments and mosaic rows, and the two texts.
+
+extern "C" int spsp_windows_plan_host(uint32_t* stretch_bases, uint32_t* stretch_bases_packed, uint32_t* record_tile) {
+    if (stretch_bases) *stretch_bases = spsp::kWnStretch;
+    if (stretch_bases_packed) *stretch_bases_packed = spsp::kWnStretchPacked;
+    if (record_tile) *record_tile = spsp::kWnRecTile;
+    return SPSP_OK;
+}
+
+namespace {
+
+int windows_width_check(uint32_t k, uint64_t window) {
+    using namespace spsp;
+    if (k == 0 || window < k || window > kWnMaxWidth) {
+        set_error("windows: the width must be k .. %llu (k = %u, width = %llu)", (unsigned long long)kWnMaxWidth, k, (unsigned long long)window);
+        return SPSP_ERR_ARG;
+    }
+    return SPSP_OK;
+}
+
+// first_win[0 .. n_rec] and the totals from the offsets; nothing is allocated
+int windows_count(const uint64_t* rec_off, uint32_t n_rec, uint32_t k, uint64_t window, uint32_t* first_win, uint64_t* n_windows, uint64_t* n_bases) {
+    using namespace spsp;
+    if (const int rc = windows_width_check(k, window)) return rc;
+    const uint64_t S = window - (k - 1);
+    uint64_t wins = 0, bases = 0;
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        if (rec_off[r] > rec_off[r + 1]) { set_error("windows: the offsets must not decrease (record %u)", r); return SPSP_ERR_ARG; }
+        const uint64_t L = rec_off[r + 1] - rec_off[r], n = wn_count(L, k, S);
+        if (first_win) first_win[r] = (uint32_t)wins;
+        if (n > kWnMaxWindows || wins + n > kWnMaxWindows) {
+            set_error("windows: more than %llu windows (at record %u): a wider window, or fewer records per call", (unsigned long long)kWnMaxWindows, r);
+            return SPSP_ERR_OVERFLOW;
+        }
+        wins += n;
+        bases += wn_bases(L, n, k);
+    }
+    if (first_win) first_win[n_rec] = (uint32_t)wins;
+    *n_windows = wins; *n_bases = bases;
+    return SPSP_OK;
+}
+
+int give_text(const std::string& s, char** text, uint64_t* len) {
+    *text = (char*)malloc(s.size() + 1);
+    if (!*text) { spsp::set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    memcpy(*text, s.c_str(), s.size() + 1);
+    *len = s.size();
+    return SPSP_OK;
+}
+
+}  // namespace
+
+extern "C" int spsp_records_windows_host(const uint64_t* rec_off, uint32_t n_rec, uint32_t k, uint64_t window, uint32_t* first_win, uint64_t** win_off,
+                                         uint64_t* n_windows, uint64_t* n_bases) {
+    using namespace spsp;
+    if (win_off) *win_off = nullptr;
+    if (n_windows) *n_windows = 0;
+    if (n_bases) *n_bases = 0;
+    if (!rec_off || !first_win || !win_off || !n_windows || !n_bases) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    uint64_t wins = 0, bases = 0;
+    if (const int rc = windows_count(rec_off, n_rec, k, window, first_win, &wins, &bases)) return rc;
+    uint64_t* off = (uint64_t*)malloc(((size_t)wins + 1) * 8);
+    if (!off) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    const uint64_t S = window - (k - 1);
+    uint64_t at = 0, w = 0;
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        const uint64_t L = rec_off[r + 1] - rec_off[r], n = wn_count(L, k, S);
+        for (uint64_t i = 0; i < n; ++i) { off[w++] = at; at += std::min<uint64_t>(i * S + window, L) - i * S; }
+    }
+    off[wins] = at;
+    *win_off = off; *n_windows = wins; *n_bases = bases;
+    return SPSP_OK;
+}
+
+extern "C" int spsp_windows_expand_host(const uint8_t* bases, const uint64_t* rec_off, uint32_t n_rec, uint32_t k, uint64_t window, uint8_t** out, uint64_t* n_out,
+                                        uint32_t* first_win, uint64_t** win_off, uint64_t* n_windows) {
+    using namespace spsp;
+    if (out) *out = nullptr;
+    if (n_out) *n_out = 0;
+    if (!out || !n_out || !rec_off || (n_rec && rec_off[n_rec] && !bases)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    uint64_t total = 0;
+    if (const int rc = spsp_records_windows_host(rec_off, n_rec, k, window, first_win, win_off, n_windows, &total)) return rc;
+    uint8_t* o = (uint8_t*)malloc(total ? (size_t)total : 1);
+    if (!o) { free(*win_off); *win_off = nullptr; *n_windows = 0; set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    const uint64_t S = window - (k - 1);
+    uint64_t at = 0;
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        const uint64_t L = rec_off[r + 1] - rec_off[r], n = wn_count(L, k, S);
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint64_t p = i * S; p < std::min<uint64_t>(i * S + window, L); ++p) o[at++] = bases[rec_off[r] + p];
+    }
+    *out = o; *n_out = total;
+    return SPSP_OK;
+}
+
+extern "C" int spsp_windows_segments_host(const uint32_t* call, const uint32_t* keys, const uint32_t* hit_keys, const uint32_t* support, const uint32_t* first_win,
+                                          const uint64_t* rec_off, uint32_t n_rec, uint32_t k, uint64_t window, uint32_t n_bins, spsp_segment_row** segments,
+                                          uint64_t* n_segments, spsp_mosaic_row* mosaic) {
+    using namespace spsp;
+    if (segments) *segments = nullptr;
+    if (n_segments) *n_segments = 0;
+    if (!segments || !n_segments || !first_win || !rec_off || (n_rec && (!mosaic || !call || !keys || !hit_keys || !support))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (const int rc = windows_width_check(k, window)) return rc;
+    if (n_bins == 0) { set_error("windows: n_bins must be 1 or more"); return SPSP_ERR_ARG; }
+    const uint64_t S = window - (k - 1);
+    const uint32_t none = n_bins - 1;
+    std::vector<spsp_segment_row> segs;
+    std::vector<std::pair<uint32_t, uint32_t>> order;      // (call, segment) of one record, to add the segments up per call
+    uint64_t expect = 0;
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        if (rec_off[r] > rec_off[r + 1]) { set_error("windows: the offsets must not decrease (record %u)", r); return SPSP_ERR_ARG; }
+        const uint64_t L = rec_off[r + 1] - rec_off[r], n = wn_count(L, k, S);
+        if (first_win[r] != expect || n > kWnMaxWindows - expect || first_win[r + 1] != expect + n) {
+            set_error("windows: record %u has %llu window(s) from %llu on by the rule, first_win says %u .. %u", r, (unsigned long long)n, (unsigned long long)expect,
+                      first_win[r], first_win[r + 1]);
+            return SPSP_ERR_ARG;
+        }
+        expect += n;
+        spsp_mosaic_row m{};
+        m.length = L; m.windows = (uint32_t)n; m.major = m.second = SPSP_WINDOWS_ABSENT;
+        const size_t seg0 = segs.size();
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t w = first_win[r] + i;
+            if (call[w] >= n_bins) { set_error("windows: record %u, window %llu: call %u, n_bins = %u", r, (unsigned long long)i, call[w], n_bins); return SPSP_ERR_ARG; }
+            const uint64_t end = i + 1 == n ? L : (i + 1) * S;
+            if (segs.size() == seg0 || segs.back().call != call[w]) {
+                spsp_segment_row s{};
+                s.begin = i * S; s.record = r; s.segment = (uint32_t)(segs.size() - seg0); s.call = call[w];
+                segs.push_back(s);
+            }
+            spsp_segment_row& s = segs.back();
+            s.end = end; ++s.windows; s.keys += keys[w]; s.hit_keys += hit_keys[w]; s.support += call[w] == none ? 0u : support[w];
+            m.keys += keys[w]; m.hit_keys += hit_keys[w]; m.called_windows += call[w] != none;
+        }
+        m.segments = (uint32_t)(segs.size() - seg0);
+        order.clear();
+        for (size_t s = seg0; s < segs.size(); ++s) if (segs[s].call != none) order.emplace_back(segs[s].call, (uint32_t)(s - seg0));
+        std::sort(order.begin(), order.end());
+        for (size_t a = 0; a < order.size();) {            // one call's segments: its windows and owned bases
+            size_t z = a;
+            uint64_t b = 0; uint32_t w = 0;
+            for (; z < order.size() && order[z].first == order[a].first; ++z) { const spsp_segment_row& s = segs[seg0 + order[z].second]; b += s.end - s.begin; w += s.windows; }
+            const uint32_t c = order[a].first;
+            ++m.calls;
+            // (calls come in ascending order: only MORE bases displace, so among equals the lower number stays)
+            if (m.major == SPSP_WINDOWS_ABSENT || b > m.major_bases) {
+                m.second = m.major; m.second_bases = m.major_bases; m.second_windows = m.major_windows;
+                m.major = c; m.major_bases = b; m.major_windows = w;
+            } else if (m.second == SPSP_WINDOWS_ABSENT || b > m.second_bases) {
+                m.second = c; m.second_bases = b; m.second_windows = w;
+            }
+            a = z;
+        }
+        mosaic[r] = m;
+    }
+    spsp_segment_row* o = (spsp_segment_row*)malloc(segs.empty() ? 1 : segs.size() * sizeof(spsp_segment_row));
+    if (!o) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    if (!segs.empty()) memcpy(o, segs.data(), segs.size() * sizeof(spsp_segment_row));
+    *segments = o; *n_segments = segs.size();
+    return SPSP_OK;
+}
+
+extern "C" int spsp_segments_csv_host(const spsp_segment_row* segments, uint64_t n_segments, const char* const* record_names, uint32_t n_rec,
+                                      const char* const* call_names, const char* last_name, uint32_t n_bins, char** text, uint64_t* len) {
+    using namespace spsp;
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!text || !len || !last_name || (n_segments && (!segments || !record_names)) || (n_bins > 1 && !call_names)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_bins == 0) { set_error("windows: n_bins must be 1 or more"); return SPSP_ERR_ARG; }
+    std::string s = "record,name,segment,begin,end,windows,call,call_name,keys,hit_keys,support\n";
+    for (uint64_t i = 0; i < n_segments; ++i) {
+        const spsp_segment_row& g = segments[i];
+        if (g.record >= n_rec || g.call >= n_bins) { set_error("windows: segment %llu names record %u or call %u out of range", (unsigned long long)i, g.record, g.call); return SPSP_ERR_ARG; }
+        const bool none = g.call + 1 == n_bins;
+        s += std::to_string(g.record) + "," + record_names[g.record] + "," + std::to_string(g.segment) + "," + std::to_string(g.begin) + "," + std::to_string(g.end) + "," +
+             std::to_string(g.windows) + "," + (none ? std::string(last_name) : std::to_string(g.call)) + "," + (none ? last_name : call_names[g.call]) + "," +
+             std::to_string(g.keys) + "," + std::to_string(g.hit_keys) + "," + std::to_string(g.support) + "\n";
+    }
+    return give_text(s, text, len);
+}
+
+extern "C" int spsp_mosaic_csv_host(const spsp_mosaic_row* mosaic, uint32_t n_rec, const char* const* record_names, const char* const* call_names,
+                                    const char* last_name, uint32_t n_bins, int precision, char** text, uint64_t* len) {
+    using namespace spsp;
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!text || !len || !last_name || (n_rec && (!mosaic || !record_names)) || (n_bins > 1 && !call_names)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_bins == 0) { set_error("windows: n_bins must be 1 or more"); return SPSP_ERR_ARG; }
+    std::string s = "record,name,length,windows,segments,called_windows,calls,major,major_name,major_windows,major_bases,f_major,second,second_name,second_windows,"
+                    "second_bases,keys,hit_keys\n";
+    char buf[64];
+    for (uint32_t r = 0; r < n_rec; ++r) {
+        const spsp_mosaic_row& m = mosaic[r];
+        for (const uint32_t c : {m.major, m.second})
+            if (c != SPSP_WINDOWS_ABSENT && c + 1 >= n_bins) { set_error("windows: record %u names call %u, n_bins = %u", r, c, n_bins); return SPSP_ERR_ARG; }
+        s += std::to_string(r) + "," + record_names[r] + "," + std::to_string(m.length) + "," + std::to_string(m.windows) + "," + std::to_string(m.segments) + "," +
+             std::to_string(m.called_windows) + "," + std::to_string(m.calls) + ",";
+        if (m.major != SPSP_WINDOWS_ABSENT) s += std::to_string(m.major) + "," + call_names[m.major] + "," + std::to_string(m.major_windows) + "," + std::to_string(m.major_bases) + ",";
+        else s += ",,0,0,";
+        s.append(buf, (size_t)format_g(buf, sizeof(buf), precision, m.length ? (double)m.major_bases / (double)m.length : 0.0));
+        if (m.second != SPSP_WINDOWS_ABSENT) s += "," + std::to_string(m.second) + "," + call_names[m.second] + "," + std::to_string(m.second_windows) + "," + std::to_string(m.second_bases);
+        else s += ",,,0,0";
+        s += "," + std::to_string(m.keys) + "," + std::to_string(m.hit_keys) + "\n";
+    }
+    return give_text(s, text, len);
+}
+
+extern "C" int spsp_windows_word_check_host(const char* what, int taxonomy) {
+    SplitWord word; uint32_t d = 0;
+    const int rc = split_word_for(what, taxonomy != 0, &word, &d);
+    if (rc && what) {                                      // (the split's refusals, under this pass's name)
+        const std::string said = spsp_last_error();
+        if (said.compare(0, 7, "split: ") == 0) spsp::set_error("windows: %s", said.c_str() + 7);
+    }
+    return rc;
+}

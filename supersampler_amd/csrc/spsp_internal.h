@@ -365,6 +365,11 @@ struct spsp_ctx {
     // a place in A per entry of B, the "new" ballot words of B's entries, the tiles' counts and their scan)
     spsp::DevBuf un_mn, un_lo, un_hi, un_work;
     spsp::RecordClock un_clock;          // spsp_union_stage_ms: flag, scan, offsets, write
+    // windows (spsp_windows.hip): the call's words, the tiles' sums and their scan, per record its first window and output start,
+    // the windows' offsets, their source starts, and the output, which is whole stretches with the scan's readable bytes behind
+    spsp::DevBuf wn_words, wn_tiles, wn_rec, wn_off, wn_src, wn_out;
+    hipEvent_t wn_ev[4] = {};            // while timing is on: in front of the count, the offsets, the copy, and behind it
+    double wn_ms[3] = {};                // spsp_windows_stage_ms: count, offsets, copy
 };
 
 namespace spsp {
@@ -561,7 +566,10 @@ int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
 // on_batch, whose work is queued on ctx (spsp_wait_stream orders the two contexts around every batch: the keys of a batch are read
 // before the next extraction overwrites them).  names: null, or the records' names as the host reads them from the header lines --
 // then a text with another number of header lines than the device finds records is SPSP_ERR_FORMAT.  on_records is called once,
-// behind the scan, with the records' base offsets (n_rec + 1)
+// behind the scan, with the records' base offsets (n_rec + 1).  windows: null, or a windows run (spsp_windows.hip) -- behind the
+// ingest and in front of the scan every record is cut into windows on `side`, and the scan, the seams, the key extraction,
+// on_records and on_batch then see the WINDOWS as records; the header count is still held against the real records, whose offsets
+// and first_win the run keeps for the driver
 struct RecordBatch { uint32_t first_record, n_records; const uint32_t* mn; const uint64_t *lo, *hi; const uint64_t* key_off; };   // key_off: host, n_records + 1
 // what a record file driver writes beside its CSVs when it is asked to (spsp_extract.hip).  on_text is the road's hook: behind a
 // file's last batch, with the text still in the side context's buffer, it has `flags` (the driver's: its rows -> keep[n_rec]) make
@@ -596,7 +604,7 @@ int split_write(spsp_ctx* ctx, ExtractRun* run, ExtractRun* mates, const char* o
 std::string split_file_name(const char* prefix, uint32_t b, uint32_t n_bins, const char* last_name, const char* tag, const char* suffix);
 int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
                          std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract = nullptr);
+                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract = nullptr, struct WindowsRun* windows = nullptr);
 // the paired form (spsp_classify.hip): text[0] and text[1] hold the two mates of every pair, on a side context each; the union of
 // the two mates' keys per pair (spsp_union.hip) is what on_batch gets.  extract: null, or the two mates' runs
 int records_pair_batches(spsp_ctx* ctx, spsp_ctx* const* side, const spsp_params* p, const uint8_t* const* text, const uint64_t* n_text, const char* const* path,
@@ -679,7 +687,7 @@ struct FilesRun;
 int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
                        const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
                        const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1,
-                       ExtractRun* extract = nullptr, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr);
+                       ExtractRun* extract = nullptr, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr, struct WindowsRun* windows = nullptr);
 int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den);
 int taxonomy_index_impl(spsp_ctx* ctx, const uint32_t* parent, uint32_t T, const uint32_t* ref_node, uint32_t n_ref, const uint32_t** key_nodes_out);
 int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
@@ -744,6 +752,36 @@ constexpr uint32_t kUnTile = 256;                          // entries of B per c
 int records_union_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* a_mn, const uint64_t* a_lo, const uint64_t* a_hi, const uint64_t* h_a_off, const uint32_t* b_mn,
                        const uint64_t* b_lo, const uint64_t* b_hi, const uint64_t* h_b_off, uint32_t n_rec, uint32_t** out_mn, uint64_t** out_lo, uint64_t** out_hi,
                        uint64_t* h_off);
+// spsp_windows.hip: every record cut into overlapping windows (the rule: include/spsp.h, "windows").  What the kernels cut at
+// (spsp_windows_plan_host, spsp_host.cpp):
+constexpr uint32_t kWnThreads = 256, kWnRecsPerLane = 8, kWnRecTile = kWnThreads * kWnRecsPerLane;   // every kernel: 4 waves; records per workgroup of the counting pass
+constexpr uint32_t kWnStretchBytes = 16384;                // bytes of the output one workgroup of the copy owns, in either form
+constexpr uint32_t kWnStretch = kWnStretchBytes;           // ... in bases of the ASCII form
+constexpr uint32_t kWnStretchPacked = kWnStretchBytes * 4; // ... and of the packed form: whole dwords, whole 16-byte stores
+constexpr uint32_t kWnStores = kWnStretchBytes / (kWnThreads * 16);   // rounds of 16-byte stores a workgroup of the copy makes
+constexpr uint32_t kWnHalo = 256;                          // zero bytes behind the output's last stretch: what a scan may read
+constexpr uint64_t kWnMaxWindows = 0xfffffff0ull, kWnMaxWidth = 0x7fffffffull;
+// a record of L bases at width W and step S = W - (k - 1): its windows, and the bases of all of them together
+__host__ __device__ inline uint64_t wn_count(uint64_t L, uint32_t k, uint64_t S) { return L < k ? 1ull : (L - k + S) / S; }   // ((L - k + 1) + S - 1) / S >= 1
+__host__ __device__ inline uint64_t wn_bases(uint64_t L, uint64_t n_win, uint32_t k) { return L + (n_win - 1) * (uint64_t)(k - 1); }
+// the windows of a text's records in the context's buffers, with one host wait (for the counts).  h_first_win: n_rec + 1
+int records_windows_impl(spsp_ctx* ctx, const uint8_t* d_bases, uint64_t n_bases, const uint64_t* d_rec_off, uint32_t n_rec, uint32_t k, uint64_t window, bool packed,
+                         uint8_t** d_out, uint64_t* n_out, uint64_t** d_win_off, uint32_t* h_first_win, uint64_t* n_windows);
+// the windows run of a record file driver: the width; what the road leaves behind for the driver (first_win over the file's real
+// records and their offsets, beside the windows the passes saw as records)
+struct WindowsRun {
+    uint64_t window = 0;
+    std::vector<uint32_t> first_win;
+    std::vector<uint64_t> rec_off;
+    std::vector<spsp_segment_row> segments;
+    std::vector<spsp_mosaic_row> mosaic;
+};
+// what a windowed driver does behind the road (spsp_windows.hip): segments and mosaic rows from the windows' calls and addends
+// (spsp_windows_segments_host), both texts made before either file is written, <out_prefix>_segments.csv.gz and
+// <out_prefix>_mosaic.csv.gz, and with chatter the one line.  call_names: n_bins - 1
+int windows_write(spsp_ctx* ctx, WindowsRun* run, uint32_t k, const std::vector<uint32_t>& call, const std::vector<uint32_t>& keys, const std::vector<uint32_t>& hit_keys,
+                  const std::vector<uint32_t>& support, uint32_t n_bins, const std::vector<std::string>& names, const char* const* call_names, const char* last_name,
+                  int precision, const char* out_prefix, double t_csv, int chatter);
 // spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
 // groups as n_groups sketches back to back in context-owned arrays
 int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,

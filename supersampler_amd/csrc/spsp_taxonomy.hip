@@ -395,7 +395,8 @@ int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
 // spsp_taxonomy_files behind its argument checks
 static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, const char* lineages_path, uint32_t min_keys,
                           uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_taxonomy_record>* recs,
-                          ExtractRun* extract, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr) {
+                          ExtractRun* extract, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr, WindowsRun* windows = nullptr,
+                          const char* window_word = nullptr) {
     int rc;
     // the lineage file first: a tree that cannot be read costs no loading
     uint8_t* lin = nullptr; uint64_t n_lin = 0;
@@ -432,8 +433,20 @@ static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_re
             return SPSP_OK;
         },
         [&](const RecordBatch& B) { return taxonomy_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, min_keys, num, den, recs->data() + B.first_record); },
-        [] { return SPSP_OK; }, &t1, extract, mates_path, extract_mates);
+        [] { return SPSP_OK; }, &t1, extract, mates_path, extract_mates, windows);
     char *text = nullptr, *report = nullptr; uint64_t len = 0, report_len = 0;
+    if (!rc && windows) {
+        // the rows are the windows': their calls are the split's bins, and the two windowed CSVs take the per-record CSVs' place
+        const size_t n_win = recs->size();
+        std::vector<uint32_t> call(n_win ? n_win : 1, T), keys(call.size(), 0), hit_keys(call.size(), 0), support(call.size(), 0);
+        uint32_t n_bins = 0;
+        rc = spsp_split_bins_taxonomy_host(window_word, recs->data(), n_win, parent, depth, T, call.data(), &n_bins);
+        for (size_t w = 0; w < n_win; ++w) { keys[w] = (*recs)[w].keys; hit_keys[w] = (*recs)[w].hit_keys; support[w] = (*recs)[w].node != kTxNone ? (*recs)[w].clade : 0u; }
+        if (!rc) rc = windows_write(ctx, windows, run.keys.k, call, keys, hit_keys, support, n_bins, names, node_names.data(), "unclassified", precision, out_prefix, t1, chatter);
+        if (!rc && chatter) { say_common_rate(run.L, n_ref); fflush(stdout); }
+        spsp_free(parent); spsp_free(depth); spsp_free(size); spsp_free(blob);
+        return rc;
+    }
     if (!rc) {
         std::vector<const char*> name_ptr(names.size());
         for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
@@ -511,6 +524,48 @@ static int taxonomy_files_entry(spsp_ctx* ctx, const char* const* index_paths, u
     if (bytes_out) *bytes_out = extract.out.size() + extract_mates.out.size();
     if (n_records) *n_records = got.size();
     if (records && (rc = give_rows(got, records))) return rc;
+    return SPSP_OK;
+}
+
+extern "C" int spsp_taxonomy_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                           uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
+                                           const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
+                                           spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic) {
+    if (rows) *rows = nullptr;
+    if (first_win) *first_win = nullptr;
+    if (segments) *segments = nullptr;
+    if (mosaic) *mosaic = nullptr;
+    if (n_windows) *n_windows = 0;
+    if (n_records) *n_records = 0;
+    if (n_segments) *n_segments = 0;
+    if (!ctx || !index_paths || !records_path || !lineages_path || !out_prefix || !what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
+    int rc;
+    if ((rc = taxonomy_check_args(min_keys, num, den)) || (rc = spsp_windows_word_check_host(what, 1))) return rc;   // (before any file is read)
+    if (window == 0 || window > kWnMaxWidth) {             // (against k: once the sketches' headers are read, in front of the records file)
+        set_error("windows: the width must be k .. %llu (width = %llu)", (unsigned long long)kWnMaxWidth, (unsigned long long)window);
+        return SPSP_ERR_ARG;
+    }
+    SPSP_HIP(hipSetDevice(ctx->device));
+    std::vector<spsp_taxonomy_record> got;
+    WindowsRun run;
+    run.window = window;
+    if ((rc = taxonomy_files(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, &got, nullptr, nullptr,
+                             nullptr, &run, what))) return rc;
+    if (n_windows) *n_windows = got.size();
+    if (n_records) *n_records = run.mosaic.size();
+    if (n_segments) *n_segments = run.segments.size();
+    void* given[3] = {};
+    if ((rows && (rc = give_rows(got, rows))) || (rows && !(given[0] = *rows)) || (first_win && (rc = give_rows(run.first_win, first_win))) ||
+        (first_win && !(given[1] = *first_win)) || (segments && (rc = give_rows(run.segments, segments))) || (segments && !(given[2] = *segments)) ||
+        (mosaic && (rc = give_rows(run.mosaic, mosaic)))) {
+        for (void* g : given) free(g);
+        if (rows) *rows = nullptr;
+        if (first_win) *first_win = nullptr;
+        if (segments) *segments = nullptr;
+        if (mosaic) *mosaic = nullptr;
+        return rc ? rc : (int)SPSP_ERR_NOMEM;
+    }
     return SPSP_OK;
 }
 
