@@ -1992,6 +1992,39 @@ class Context:
     union_plan = staticmethod(union_plan)
     pairs_names = staticmethod(pairs_names)
 
+    def _record_files(self, name, head, rest, outs, extract, gz, mates_path, split, window, window_call, default_call):
+        """the ladder classify_files and taxonomy_files share: the mode's checks, then spsp_<name>_files, _extract, _paired, _split
+        or _windows.  head: (ctx, paths, n_ref, records_path), behind which the mates' path goes; rest: the pass's own arguments up
+        to rate; outs: the rows' outputs, the count last; default_call: the word a windowed run calls by where window_call is None"""
+        who = name + "_files"
+        entry = lambda suffix: getattr(lib(), "spsp_" + who + suffix)
+        refs = [C.byref(o) for o in outs]
+        mates = None if mates_path is None else str(mates_path).encode()
+        gz = 1 if gz else 0
+        kept, out_bytes = C.c_uint64(), C.c_uint64()
+        self._cf_n_ref = None
+        if window is not None:
+            if extract is not None or split is not None or mates_path is not None:
+                raise ValueError("%s: window is not taken with extract, split or mates_path" % who)
+            first, n_rec, seg, n_seg, mos = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_void_p()
+            _check(entry("_windows")(*head, *rest, window, (window_call or default_call).encode(), *refs, C.byref(first), C.byref(n_rec), C.byref(seg), C.byref(n_seg), C.byref(mos)))
+            self.last_windows = _windows_result(first, n_rec.value, seg, n_seg.value, mos)
+        elif window_call is not None:
+            raise ValueError("%s: window_call needs window" % who)
+        elif split is not None:
+            if extract is not None:
+                raise ValueError("%s: split writes every record and extract one subset: one of the two" % who)
+            _check(entry("_split")(*head, mates, *rest, split.encode(), gz, *refs, C.byref(kept), C.byref(out_bytes)))
+            self.last_split = {"bins": kept.value, "records": outs[-1].value, "bytes_out": out_bytes.value}
+        elif mates_path is not None:
+            _check(entry("_paired")(*head, mates, *rest, None if extract is None else extract.encode(), gz, *refs, C.byref(kept), C.byref(out_bytes)))
+        elif extract is not None:
+            _check(entry("_extract")(*head, *rest, *refs, extract.encode(), gz, C.byref(kept), C.byref(out_bytes)))
+        else:
+            _check(entry("")(*head, *rest, *refs))
+        if extract is not None:
+            self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
+
     def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
                        split=None, window=None, window_call=None):
         """spsp_classify_files: the sketch files of the references and a FASTA / FASTQ file of records (gzip or plain) ->
@@ -2008,41 +2041,8 @@ class Context:
         window_call: the call word (best).  Not together with extract, split or mates_path"""
         arr, _alive = _paths_array(paths)
         recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
-        self._cf_n_ref = None
-        if window is not None:
-            if extract is not None or split is not None or mates_path is not None:
-                raise ValueError("classify_files: window is not taken with extract, split or mates_path")
-            first, n_rec, seg, n_seg, mos = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_void_p()
-            _check(lib().spsp_classify_files_windows(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
-                                                     _rate_arg(rate), window, (window_call or "best").encode(), C.byref(recs), C.byref(hits), C.byref(n),
-                                                     C.byref(first), C.byref(n_rec), C.byref(seg), C.byref(n_seg), C.byref(mos)))
-            self.last_windows = _windows_result(first, n_rec.value, seg, n_seg.value, mos)
-        elif window_call is not None:
-            raise ValueError("classify_files: window_call needs window")
-        elif split is not None:
-            if extract is not None:
-                raise ValueError("classify_files: split writes every record and extract one subset: one of the two")
-            written, out_bytes = C.c_uint64(), C.c_uint64()
-            _check(lib().spsp_classify_files_split(self._h, arr, len(paths), str(records_path).encode(), None if mates_path is None else str(mates_path).encode(),
-                                                   top, min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate), split.encode(), 1 if gz else 0,
-                                                   C.byref(recs), C.byref(hits), C.byref(n), C.byref(written), C.byref(out_bytes)))
-            self.last_split = {"bins": written.value, "records": n.value, "bytes_out": out_bytes.value}
-        elif mates_path is not None:
-            kept, out_bytes = C.c_uint64(), C.c_uint64()
-            _check(lib().spsp_classify_files_paired(self._h, arr, len(paths), str(records_path).encode(), str(mates_path).encode(), top, min_keys, num, den,
-                                                    precision, prefix.encode(), 0, _rate_arg(rate), None if extract is None else extract.encode(),
-                                                    1 if gz else 0, C.byref(recs), C.byref(hits), C.byref(n), C.byref(kept), C.byref(out_bytes)))
-            if extract is not None:
-                self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
-        elif extract is not None:
-            kept, out_bytes = C.c_uint64(), C.c_uint64()
-            _check(lib().spsp_classify_files_extract(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
-                                                     _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n), extract.encode(), 1 if gz else 0,
-                                                     C.byref(kept), C.byref(out_bytes)))
-            self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
-        else:
-            _check(lib().spsp_classify_files(self._h, arr, len(paths), str(records_path).encode(), top, min_keys, num, den, precision, prefix.encode(), 0,
-                                             _rate_arg(rate), C.byref(recs), C.byref(hits), C.byref(n)))
+        self._record_files("classify", (self._h, arr, len(paths), str(records_path).encode()), (top, min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate)),
+                           (recs, hits, n), extract, gz, mates_path, split, window, window_call, "best")
         return (np.frombuffer(_take(recs, n.value * CLASSIFY_RECORD_DTYPE.itemsize), dtype=CLASSIFY_RECORD_DTYPE).copy(),
                 np.frombuffer(_take(hits, n.value * top * CLASSIFY_HIT_DTYPE.itemsize), dtype=CLASSIFY_HIT_DTYPE).copy().reshape(n.value, top))
 
@@ -2157,42 +2157,9 @@ class Context:
         window_call (taxon, depth=<d>): spsp_taxonomy_files_windows, as classify_files; self.last_windows"""
         arr, _alive = _paths_array(paths)
         recs, n = C.c_void_p(), C.c_uint64()
-        self._cf_n_ref = None
-        if window is not None:
-            if extract is not None or split is not None or mates_path is not None:
-                raise ValueError("taxonomy_files: window is not taken with extract, split or mates_path")
-            first, n_rec, seg, n_seg, mos = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_void_p()
-            _check(lib().spsp_taxonomy_files_windows(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
-                                                     prefix.encode(), 0, _rate_arg(rate), window, (window_call or "taxon").encode(), C.byref(recs), C.byref(n),
-                                                     C.byref(first), C.byref(n_rec), C.byref(seg), C.byref(n_seg), C.byref(mos)))
-            self.last_windows = _windows_result(first, n_rec.value, seg, n_seg.value, mos)
-        elif window_call is not None:
-            raise ValueError("taxonomy_files: window_call needs window")
-        elif split is not None:
-            if extract is not None:
-                raise ValueError("taxonomy_files: split writes every record and extract one subset: one of the two")
-            written, out_bytes = C.c_uint64(), C.c_uint64()
-            _check(lib().spsp_taxonomy_files_split(self._h, arr, len(paths), str(records_path).encode(), None if mates_path is None else str(mates_path).encode(),
-                                                   str(lineages_path).encode(), min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate), split.encode(),
-                                                   1 if gz else 0, C.byref(recs), C.byref(n), C.byref(written), C.byref(out_bytes)))
-            self.last_split = {"bins": written.value, "records": n.value, "bytes_out": out_bytes.value}
-        elif mates_path is not None:
-            kept, out_bytes = C.c_uint64(), C.c_uint64()
-            _check(lib().spsp_taxonomy_files_paired(self._h, arr, len(paths), str(records_path).encode(), str(mates_path).encode(), str(lineages_path).encode(),
-                                                    min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate),
-                                                    None if extract is None else extract.encode(), 1 if gz else 0, C.byref(recs), C.byref(n), C.byref(kept),
-                                                    C.byref(out_bytes)))
-            if extract is not None:
-                self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
-        elif extract is not None:
-            kept, out_bytes = C.c_uint64(), C.c_uint64()
-            _check(lib().spsp_taxonomy_files_extract(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
-                                                     prefix.encode(), 0, _rate_arg(rate), C.byref(recs), C.byref(n), extract.encode(), 1 if gz else 0,
-                                                     C.byref(kept), C.byref(out_bytes)))
-            self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
-        else:
-            _check(lib().spsp_taxonomy_files(self._h, arr, len(paths), str(records_path).encode(), str(lineages_path).encode(), min_keys, num, den, precision,
-                                             prefix.encode(), 0, _rate_arg(rate), C.byref(recs), C.byref(n)))
+        self._record_files("taxonomy", (self._h, arr, len(paths), str(records_path).encode()),
+                           (str(lineages_path).encode(), min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate)), (recs, n), extract, gz, mates_path, split,
+                           window, window_call, "taxon")
         return np.frombuffer(_take(recs, n.value * TAXONOMY_RECORD_DTYPE.itemsize), dtype=TAXONOMY_RECORD_DTYPE).copy()
 
     def depth_begin(self):

@@ -441,25 +441,6 @@ int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
     return SPSP_OK;
 }
 
-// the records' names as the host reads them from the text: the first whitespace-delimited word of every header line -- FASTA: the
-// lines that begin with '>'; FASTQ: every fourth line up to the content's end, which begins with '@'
-static void record_names_host(const uint8_t* text, uint64_t n, bool fastq, std::vector<std::string>* names) {
-    uint64_t end = n;
-    while (end && (text[end - 1] == '\n' || text[end - 1] == '\r')) --end;   // (FASTQ: the content without its trailing blank lines)
-    uint64_t line = 0;
-    for (uint64_t pos = 0; pos < (fastq ? end : n); ++line) {
-        uint64_t stop = pos;
-        while (stop < n && text[stop] != '\n') ++stop;
-        const bool header = fastq ? line % 4 == 0 : text[pos] == '>';
-        if (header) {
-            uint64_t a = pos < stop ? pos + 1 : pos, z = a;   // (behind the '>' or '@')
-            while (z < stop && text[z] != ' ' && text[z] != '\t' && text[z] != '\r') ++z;
-            names->emplace_back((const char*)text + a, (size_t)(z - a));
-        }
-        pos = stop + 1;
-    }
-}
-
 // seam[b] = the first super-k-mer of the stream (which is in record order) whose record is want[b] or behind it
 __global__ void k_cf_seams(const spsp_superkmer* __restrict__ sk, uint64_t n_sk, const uint32_t* __restrict__ want, uint32_t n, uint64_t* __restrict__ seam) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -486,91 +467,27 @@ static int batch_seams(spsp_ctx* ctx, const spsp_superkmer* d_sk, uint64_t n_sk,
     return SPSP_OK;
 }
 
-// the records of a text, ingested and scanned once on `side` (a second context of ctx's device), their keys extracted batch by batch
-// there and handed to on_batch, which queues its work on ctx (the two contexts are ordered by spsp_wait_stream around it).
-// names: the records' names as the host reads them, held against the device's record count; null: no names, no header count.
-// on_records: once, behind the scan, with the records' base offsets (n_rec + 1)
-int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
-                         std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract, WindowsRun* windows) {
-    int rc;
-    double t0 = now_s(), t1;
-    const bool fastq = n_text && text[0] == '@';
-    if (names) record_names_host(text, n_text, fastq, names);
-    if ((rc = side->i_text.reserve((size_t)n_text + 64))) return rc;
-    if (n_text) SPSP_HIP(hipMemcpyAsync(side->i_text.p, text, (size_t)n_text, hipMemcpyHostToDevice, side->stream));
-    uint8_t* d_bases = nullptr; uint64_t* d_off = nullptr; uint64_t n_bases = 0; uint32_t n_rec = 0;
-    const bool packed = ingest_packs(p);
-    FastqLayout fq;
-    if (fastq) fastq_tail(text, n_text, &fq.content_end, &fq.blank_tail);
-    if ((rc = clean_device_impl(side, side->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed, fastq ? &fq : nullptr))) return rc;
-    if (names && names->size() != n_rec) {                 // (held against the REAL records, whatever the passes see)
-        set_error("'%s': %zu header line(s) on the host, %u record(s) on the device", path, names->size(), n_rec);
-        return SPSP_ERR_FORMAT;
-    }
-    if (windows) {
-        // the expansion, between the ingest and the scan: from here on the windows are the records (their bases in the side
-        // context's windows buffer, in the form the ingest wrote).  The real records' offsets and first_win stay with the run
-        windows->rec_off.assign((size_t)n_rec + 1, 0);
-        windows->first_win.assign((size_t)n_rec + 1, 0);
-        SPSP_HIP(hipMemcpyAsync(windows->rec_off.data(), d_off, windows->rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));   // (the expansion waits)
-        uint8_t* w_bases = nullptr; uint64_t* w_off = nullptr; uint64_t w_n = 0, n_win = 0;
-        if ((rc = records_windows_impl(side, d_bases, n_bases, d_off, n_rec, p->k, windows->window, packed, &w_bases, &w_n, &w_off, windows->first_win.data(), &n_win)))
-            return rc;
-        d_bases = w_bases; n_bases = w_n; d_off = w_off; n_rec = (uint32_t)n_win;
-    }
-    t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
-    spsp_superkmer* d_sk = nullptr; uint64_t n_sk = 0;
-    spsp_params ps = *p;
-    if (packed) ps.flags |= SPSP_SCAN_PACKED_INPUT;
-    if ((rc = scan_device_impl(side, &ps, d_bases, n_bases, d_off, n_rec, &d_sk, &n_sk))) return rc;
-    t1 = now_s(); ctx->stages.scan_s += t1 - t0; t0 = t1;
-    std::vector<uint64_t> rec_off((size_t)n_rec + 1, 0);
-    SPSP_HIP(hipMemcpyAsync(rec_off.data(), d_off, rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));
-    SPSP_HIP(hipStreamSynchronize(side->stream));
-    if ((rc = on_records(n_rec, rec_off.data()))) return rc;
-    std::vector<uint32_t> first_rec, bounds;
-    std::vector<uint64_t> key_off, seam;
-    for (uint64_t r = 0; r < n_rec; r += 65535u) bounds.push_back((uint32_t)r);
-    bounds.push_back(n_rec);
-    // (the extraction takes any record range of the scan: it looks its genomes' super-k-mers up by record number.  It gets the
-    // batch's own stretch of the stream all the same, so that a batch costs its records and not the file's)
-    if (n_rec && (rc = batch_seams(side, d_sk, n_sk, bounds, &seam))) return rc;
-    for (size_t b = 0; b + 1 < bounds.size(); ++b) {
-        const uint32_t r0 = bounds[b], batch = bounds[b + 1] - r0;
-        const uint64_t q0 = seam[b], q1 = seam[b + 1];
-        first_rec.resize((size_t)batch + 1);
-        for (uint32_t g = 0; g <= batch; ++g) first_rec[g] = r0 + g;
-        key_off.assign((size_t)batch + 1, 0);
-        void *k_mn = nullptr, *k_lo = nullptr, *k_hi = nullptr;
-        if ((rc = spsp_wait_stream(side, ctx)) ||          // (the last batch's keys have been read)
-            (rc = spsp_sketch_keys_device(side, &ps, d_bases, n_bases, d_off, d_sk + q0, q1 - q0, first_rec.data(), batch, 0, &k_mn, &k_lo, &k_hi,
-                                          key_off.data())) ||
-            (rc = spsp_wait_stream(ctx, side)) ||
-            (rc = on_batch(RecordBatch{r0, batch, (const uint32_t*)k_mn, (const uint64_t*)k_lo, (const uint64_t*)k_hi, key_off.data()}))) return rc;
-    }
-    // (every batch's rows are on the host: each record call waits.  The text still sits in the side context's buffer)
-    if (extract && (rc = extract->on_text(side, side->i_text.as<uint8_t>(), n_text, n_rec))) return rc;
-    return SPSP_OK;
-}
-
-// One mate's text of the paired form on its side context: what records_text_batches does with its one text, cut where the pair
-// needs its two sides in step -- open (the ingest and the scan, once), seams (every batch's stretch of the stream), and the key
-// extraction of a batch queued (keys_begin) and collected (keys_end), so that the two sides' extractions overlap on their streams
-struct MateSide {
+// One text, ingested and scanned once on its side context: what the unpaired form has one of and the paired form two.  open: the
+// upload, the ingest, the header count held against the REAL records, the windows expansion where there is one, the scan, the
+// two stage times, the records' offsets on the host (one wait).  seams: every batch's stretch of the stream.  keys_begin /
+// keys_end: a batch's key extraction queued and collected, so that two sides' extractions overlap on their streams
+struct TextSide {
     spsp_ctx* side = nullptr;
     spsp_params ps{};
     uint8_t* d_bases = nullptr;
     uint64_t* d_off = nullptr;
-    uint64_t n_bases = 0, n_sk = 0;
+    uint64_t n_text = 0, n_bases = 0, n_sk = 0;
     uint32_t n_rec = 0;
     spsp_superkmer* d_sk = nullptr;
     std::vector<uint64_t> rec_off, seam, key_off;
     std::vector<uint32_t> first_rec;
 
-    int open(spsp_ctx* ctx, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path, size_t n_names) {
+    // t0: where the ingest's stage time begins (the unpaired form counts the reading of the names in).  n_names: null, or the
+    // header lines the host read.  windows: null, or the run that takes the real records' offsets and first_win
+    int open(spsp_ctx* ctx, const spsp_params* p, const uint8_t* text, uint64_t text_bytes, const char* path, double t0, const size_t* n_names, WindowsRun* windows) {
         int rc;
-        double t0 = now_s(), t1;
+        double t1;
+        n_text = text_bytes;
         const bool fastq = n_text && text[0] == '@';
         if ((rc = side->i_text.reserve((size_t)n_text + 64))) return rc;
         if (n_text) SPSP_HIP(hipMemcpyAsync(side->i_text.p, text, (size_t)n_text, hipMemcpyHostToDevice, side->stream));
@@ -578,11 +495,22 @@ struct MateSide {
         FastqLayout fq;
         if (fastq) fastq_tail(text, n_text, &fq.content_end, &fq.blank_tail);
         if ((rc = clean_device_impl(side, side->i_text.as<uint8_t>(), n_text, &d_bases, &n_bases, &d_off, &n_rec, packed, fastq ? &fq : nullptr))) return rc;
-        t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
-        if (n_names != n_rec) {
-            set_error("'%s': %zu header line(s) on the host, %u record(s) on the device", path, n_names, n_rec);
+        if (n_names && *n_names != n_rec) {                // (held against the REAL records, whatever the passes see)
+            set_error("'%s': %zu header line(s) on the host, %u record(s) on the device", path, *n_names, n_rec);
             return SPSP_ERR_FORMAT;
         }
+        if (windows) {
+            // the expansion, between the ingest and the scan: from here on the windows are the records (their bases in the side
+            // context's windows buffer, in the form the ingest wrote).  The real records' offsets and first_win stay with the run
+            windows->rec_off.assign((size_t)n_rec + 1, 0);
+            windows->first_win.assign((size_t)n_rec + 1, 0);
+            SPSP_HIP(hipMemcpyAsync(windows->rec_off.data(), d_off, windows->rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));   // (the expansion waits)
+            uint8_t* w_bases = nullptr; uint64_t* w_off = nullptr; uint64_t w_n = 0, n_win = 0;
+            if ((rc = records_windows_impl(side, d_bases, n_bases, d_off, n_rec, p->k, windows->window, packed, &w_bases, &w_n, &w_off, windows->first_win.data(), &n_win)))
+                return rc;
+            d_bases = w_bases; n_bases = w_n; d_off = w_off; n_rec = (uint32_t)n_win;
+        }
+        t1 = now_s(); ctx->stages.ingest_s += t1 - t0; t0 = t1;
         ps = *p;
         if (packed) ps.flags |= SPSP_SCAN_PACKED_INPUT;
         if ((rc = scan_device_impl(side, &ps, d_bases, n_bases, d_off, n_rec, &d_sk, &n_sk))) return rc;
@@ -592,98 +520,108 @@ struct MateSide {
         SPSP_HIP(hipStreamSynchronize(side->stream));
         return SPSP_OK;
     }
-    int keys_begin(uint32_t r0, uint32_t batch, uint64_t q0, uint64_t q1) {
+    // (the extraction takes any record range of the scan: it looks its genomes' super-k-mers up by record number.  It gets the
+    // batch's own stretch of the stream all the same, so that a batch costs its records and not the file's)
+    int seams(const std::vector<uint32_t>& bounds) { return n_rec ? batch_seams(side, d_sk, n_sk, bounds, &seam) : (int)SPSP_OK; }
+    int keys_begin(uint32_t r0, uint32_t batch, size_t b) {
         first_rec.resize((size_t)batch + 1);
         for (uint32_t g = 0; g <= batch; ++g) first_rec[g] = r0 + g;
         key_off.assign((size_t)batch + 1, 0);
-        return spsp_sketch_keys_device_begin(side, &ps, d_bases, n_bases, d_off, d_sk + q0, q1 - q0, first_rec.data(), batch, 0);
+        return spsp_sketch_keys_device_begin(side, &ps, d_bases, n_bases, d_off, d_sk + seam[b], seam[b + 1] - seam[b], first_rec.data(), batch, 0);
     }
+    int keys_end(void** k) { return spsp_sketch_keys_device_end(side, &k[0], &k[1], &k[2], key_off.data()); }
 };
 
-// The paired form of records_text_batches: record p of `text[0]` and record p of `text[1]` are the two mates of pair p (the rule:
-// include/spsp.h, "paired records").  The record counts and the names are held against each other in front of everything else;
-// *names receives the pairs' common names.  Each text is ingested and scanned once on its own side context; per batch of at most
-// 65 535 pairs the two key extractions are queued on the two sides' streams, their union is made on ctx, and on_batch gets the
-// union's arrays as it gets a batch's keys in the unpaired form.  on_records: the pairs' summed base offsets.  extract: null, or
-// one run per mate (extract[1]->flags is not used: both texts are cut by the flags extract[0] makes from the pairs' rows)
-int records_pair_batches(spsp_ctx* ctx, spsp_ctx* const* side, const spsp_params* p, const uint8_t* const* text, const uint64_t* n_text, const char* const* path,
-                         std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* const* extract) {
+// behind the last batch (every batch's rows are on the host: each record call waits), with the texts still in the side contexts'
+// buffers: the pass makes ONE flag or bin vector from its rows, and every text is cut by it
+static int cut_texts(RecordPass& pass, const RecordsAsk& ask, RecordsOut* out, TextSide* S, int n_sides) {
     int rc;
-    std::vector<std::string> mate_names[2];
-    for (int s = 0; s < 2; ++s) record_names_host(text[s], n_text[s], n_text[s] && text[s][0] == '@', &mate_names[s]);
-    if (mate_names[0].size() != mate_names[1].size()) {
-        set_error("paired files must hold as many records: '%s' has %zu, '%s' has %zu", path[0], mate_names[0].size(), path[1], mate_names[1].size());
-        return SPSP_ERR_FORMAT;
+    const uint32_t n_rec = S[0].n_rec;
+    if (ask.mode == kRmSplit) {
+        std::vector<uint32_t> bin(n_rec ? n_rec : 1, SPSP_SPLIT_DROP);
+        uint32_t n_bins = 0;
+        if ((rc = pass.bins(ask.what, n_rec, bin.data(), &n_bins))) return rc;
+        for (int s = 0; s < n_sides; ++s)
+            if ((rc = out->extract[s].split_text(S[s].side, S[s].side->i_text.as<uint8_t>(), S[s].n_text, n_rec, bin.data(), n_bins))) return rc;
+    } else if (ask.mode == kRmExtract) {
+        std::vector<uint8_t> keep(n_rec ? n_rec : 1, 0);
+        if ((rc = pass.keep_flags(ask.what, n_rec, keep.data()))) return rc;
+        for (int s = 0; s < n_sides; ++s)
+            if ((rc = out->extract[s].on_text(S[s].side, S[s].side->i_text.as<uint8_t>(), S[s].n_text, n_rec, keep.data()))) return rc;
     }
-    {
+    return SPSP_OK;
+}
+
+// the records of n_sides texts (1: a records file; 2: the two mates' files, record p of either being the two mates of pair p --
+// the rule: include/spsp.h, "paired records"), each on its side context, through the pass batch by batch.  The paired form holds
+// the record counts and the names against each other in front of everything else, hands on_records the pairs' summed base
+// offsets, and per batch queues the two key extractions on the two sides' streams before it collects either, makes their union
+// on ctx and hands that to on_batch as the unpaired form hands a batch's keys
+static int records_text_batches(spsp_ctx* ctx, spsp_ctx* const* side, int n_sides, const spsp_params* p, const uint8_t* const* text, const uint64_t* n_text,
+                                const char* const* path, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out) {
+    int rc;
+    const double t0 = now_s();
+    const bool paired = n_sides == 2;
+    std::vector<std::string> mate_names[2];
+    std::vector<std::string>* names[2] = {paired ? &mate_names[0] : &out->names, &mate_names[1]};
+    if (paired || out->want_names)
+        for (int s = 0; s < n_sides; ++s) record_names_host(text[s], n_text[s], n_text[s] && text[s][0] == '@', names[s]);
+    if (paired) {
+        if (mate_names[0].size() != mate_names[1].size()) {
+            set_error("paired files must hold as many records: '%s' has %zu, '%s' has %zu", path[0], mate_names[0].size(), path[1], mate_names[1].size());
+            return SPSP_ERR_FORMAT;
+        }
         const size_t n = mate_names[0].size();
         std::vector<const char*> p1(n), p2(n);
         for (size_t r = 0; r < n; ++r) { p1[r] = mate_names[0][r].c_str(); p2[r] = mate_names[1][r].c_str(); }
         char* common = nullptr; uint64_t bad = 0;
         if ((rc = spsp_pairs_names_host(p1.data(), p2.data(), n, &common, &bad))) return rc;
-        names->clear();
-        for (size_t r = 0, at = 0; r < n; ++r) { names->emplace_back(common + at); at += names->back().size() + 1; }
+        out->names.clear();
+        for (size_t r = 0, at = 0; r < n; ++r) { out->names.emplace_back(common + at); at += out->names.back().size() + 1; }
         spsp_free(common);
     }
-    MateSide M[2];
-    for (int s = 0; s < 2; ++s) {
-        M[s].side = side[s];
-        if ((rc = M[s].open(ctx, p, text[s], n_text[s], path[s], mate_names[s].size()))) return rc;
+    TextSide S[2];
+    for (int s = 0; s < n_sides; ++s) {
+        const size_t n_names = names[s]->size();
+        S[s].side = side[s];
+        if ((rc = S[s].open(ctx, p, text[s], n_text[s], path[s], paired ? now_s() : t0, paired || out->want_names ? &n_names : nullptr,
+                            ask.mode == kRmWindows ? &out->windows : nullptr))) return rc;
     }
-    const uint32_t n_rec = M[0].n_rec;
-    std::vector<uint64_t> sum_off((size_t)n_rec + 1);
-    for (uint32_t r = 0; r <= n_rec; ++r) sum_off[r] = M[0].rec_off[r] + M[1].rec_off[r];
-    if ((rc = on_records(n_rec, sum_off.data()))) return rc;
-    std::vector<uint32_t> bounds;
-    for (uint64_t r = 0; r < n_rec; r += 65535u) bounds.push_back((uint32_t)r);
-    bounds.push_back(n_rec);
-    for (int s = 0; s < 2; ++s)
-        if (n_rec && (rc = batch_seams(side[s], M[s].d_sk, M[s].n_sk, bounds, &M[s].seam))) return rc;
-    std::vector<uint64_t> key_off;
+    const uint32_t n_rec = S[0].n_rec;
+    if (paired) {
+        std::vector<uint64_t> sum_off((size_t)n_rec + 1);
+        for (uint32_t r = 0; r <= n_rec; ++r) sum_off[r] = S[0].rec_off[r] + S[1].rec_off[r];
+        rc = pass.on_records(n_rec, sum_off.data());
+    } else rc = pass.on_records(n_rec, S[0].rec_off.data());
+    if (rc) return rc;
+    const std::vector<uint32_t> bounds = records_batch_bounds(n_rec);
+    for (int s = 0; s < n_sides; ++s)
+        if ((rc = S[s].seams(bounds))) return rc;
+    std::vector<uint64_t> union_off;
     for (size_t b = 0; b + 1 < bounds.size(); ++b) {
         const uint32_t r0 = bounds[b], batch = bounds[b + 1] - r0;
-        key_off.assign((size_t)batch + 1, 0);
         void* km[2][3] = {};
-        for (int s = 0; s < 2; ++s)                        // (the last batch's union has read this side's keys)
-            if ((rc = spsp_wait_stream(side[s], ctx)) || (rc = M[s].keys_begin(r0, batch, M[s].seam[b], M[s].seam[b + 1]))) return rc;
-        for (int s = 0; s < 2; ++s)
-            if ((rc = spsp_sketch_keys_device_end(side[s], &km[s][0], &km[s][1], &km[s][2], M[s].key_off.data())) || (rc = spsp_wait_stream(ctx, side[s]))) return rc;
-        uint32_t* u_mn = nullptr;
-        uint64_t *u_lo = nullptr, *u_hi = nullptr;
-        if ((rc = records_union_impl(ctx, p->k, (const uint32_t*)km[0][0], (const uint64_t*)km[0][1], (const uint64_t*)km[0][2], M[0].key_off.data(),
-                                     (const uint32_t*)km[1][0], (const uint64_t*)km[1][1], (const uint64_t*)km[1][2], M[1].key_off.data(), batch, &u_mn, &u_lo,
-                                     &u_hi, key_off.data())) ||
-            (rc = on_batch(RecordBatch{r0, batch, u_mn, u_lo, u_hi, key_off.data()}))) return rc;
-    }
-    if (extract && extract[0]->split) {
-        // (one bin vector, likewise)
-        std::vector<uint32_t> bin(n_rec ? n_rec : 1, SPSP_SPLIT_DROP);
-        uint32_t n_bins = 0;
-        if ((rc = extract[0]->bins(n_rec, bin.data(), &n_bins))) return rc;
-        for (int s = 0; s < 2; ++s) {
-            extract[s]->bins = [&bin, n_bins](uint32_t n, uint32_t* out, uint32_t* nb) { memcpy(out, bin.data(), (size_t)n * 4); *nb = n_bins; return (int)SPSP_OK; };
-            if ((rc = extract[s]->on_text(side[s], side[s]->i_text.as<uint8_t>(), n_text[s], n_rec))) return rc;
+        for (int s = 0; s < n_sides; ++s)                  // (the last batch's keys, or its union, have been read)
+            if ((rc = spsp_wait_stream(side[s], ctx)) || (rc = S[s].keys_begin(r0, batch, b))) return rc;
+        for (int s = 0; s < n_sides; ++s)
+            if ((rc = S[s].keys_end(km[s])) || (rc = spsp_wait_stream(ctx, side[s]))) return rc;
+        RecordBatch B{r0, batch, (const uint32_t*)km[0][0], (const uint64_t*)km[0][1], (const uint64_t*)km[0][2], S[0].key_off.data()};
+        if (paired) {
+            uint32_t* u_mn = nullptr;
+            uint64_t *u_lo = nullptr, *u_hi = nullptr;
+            union_off.assign((size_t)batch + 1, 0);
+            if ((rc = records_union_impl(ctx, p->k, B.mn, B.lo, B.hi, B.key_off, (const uint32_t*)km[1][0], (const uint64_t*)km[1][1], (const uint64_t*)km[1][2],
+                                         S[1].key_off.data(), batch, &u_mn, &u_lo, &u_hi, union_off.data()))) return rc;
+            B = RecordBatch{r0, batch, u_mn, u_lo, u_hi, union_off.data()};
         }
-    } else if (extract) {
-        // (one flag vector: extract[0] makes it from the pairs' rows, and each text is cut by it where it still sits)
-        std::vector<uint8_t> keep(n_rec ? n_rec : 1, 0);
-        if ((rc = extract[0]->flags(n_rec, keep.data()))) return rc;
-        for (int s = 0; s < 2; ++s) {
-            extract[s]->flags = [keep](uint32_t n, uint8_t* out) { memcpy(out, keep.data(), n); return (int)SPSP_OK; };
-            if ((rc = extract[s]->on_text(side[s], side[s]->i_text.as<uint8_t>(), n_text[s], n_rec))) return rc;
-        }
+        if ((rc = pass.on_batch(B))) return rc;
     }
-    return SPSP_OK;
+    return cut_texts(pass, ask, out, S, n_sides);
 }
 
-// the road of the four record file drivers: load, refusals, decode, index, on_index, every records file through its batches, on_close
-int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
-                       const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1, ExtractRun* extract,
-                       const char* mates_path, ExtractRun* extract_mates, WindowsRun* windows) {
+int records_files_road(FilesRun& run, const char* what_is, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out) {
     spsp_ctx* ctx = run.ctx;
-    int rc = run.load(rate);
+    int rc = run.load(ask.rate);
     if (!rc) rc = run.refuse_k_eq_m(rc, what_is);
     double rec_rate = run.L.ds_rate;                       // the records are scanned at ONE threshold: mixed rates need a rate, as -S
     if (!rc) rc = sketches_out_rate(run.L, run.paths, run.n, &rec_rate);
@@ -691,116 +629,129 @@ int records_files_road(FilesRun& run, const char* what_is, const char* const* re
     const DecodedKeys& keys = run.keys;
     rc = run.decode();
     if (!rc) rc = classify_index_impl(ctx, keys.k, keys.mn, keys.lo, keys.hi, keys.sk_off.data(), run.n);
-    if (!rc) rc = on_index();
+    if (!rc) rc = pass.on_index();
     if (!rc) {
-        spsp_ctx* side = nullptr;
+        spsp_ctx* side[2] = {nullptr, nullptr};
         spsp_params p{};
         p.k = keys.k; p.m = keys.m; p.threshold = spsp_threshold_host(keys.k, keys.m, rec_rate); p.abundance = 1; p.flags = 0;
-        for (uint32_t f = 0; !rc && !mates_path && f < n_records_paths; ++f) {
+        for (uint32_t f = 0; !rc && !ask.mates_path && f < ask.n_records_paths; ++f) {
             uint8_t* text = nullptr; uint64_t n_text = 0;
-            if (!(rc = spsp_read_file_host(records_paths[f], &text, &n_text)) && (side || !(rc = spsp_create(ctx->device, nullptr, &side))) &&
-                !(rc = spsp_wait_stream(side, ctx)))       // (the last file's keys have been read)
-                rc = records_text_batches(ctx, side, &p, text, n_text, records_paths[f], names, on_records, on_batch, extract, windows);
+            if (!(rc = spsp_read_file_host(ask.records_paths[f], &text, &n_text)) && (side[0] || !(rc = spsp_create(ctx->device, nullptr, &side[0]))) &&
+                !(rc = spsp_wait_stream(side[0], ctx)))    // (the last file's keys have been read)
+                rc = records_text_batches(ctx, side, 1, &p, &text, &n_text, &ask.records_paths[f], pass, ask, out);
             spsp_free(text);
         }
-        spsp_ctx* side2 = nullptr;
-        if (!rc && mates_path) {                           // the paired form: records_paths[0] and mates_path on a side context each
-            const char* path[2] = {records_paths[0], mates_path};
+        if (!rc && ask.mates_path) {                       // the paired form: records_paths[0] and mates_path on a side context each
+            const char* path[2] = {ask.records_paths[0], ask.mates_path};
             uint8_t* text[2] = {nullptr, nullptr}; uint64_t n_text[2] = {0, 0};
-            ExtractRun* ex[2] = {extract, extract_mates};
             if (!(rc = spsp_read_file_host(path[0], &text[0], &n_text[0])) && !(rc = spsp_read_file_host(path[1], &text[1], &n_text[1])) &&
-                !(rc = spsp_create(ctx->device, nullptr, &side)) && !(rc = spsp_create(ctx->device, nullptr, &side2))) {
-                spsp_ctx* sides[2] = {side, side2};
-                rc = records_pair_batches(ctx, sides, &p, text, n_text, path, names, on_records, on_batch, extract ? ex : nullptr);
-            }
+                !(rc = spsp_create(ctx->device, nullptr, &side[0])) && !(rc = spsp_create(ctx->device, nullptr, &side[1])))
+                rc = records_text_batches(ctx, side, 2, &p, text, n_text, path, pass, ask, out);
             spsp_free(text[0]); spsp_free(text[1]);
         }
-        if (!rc) rc = on_close();
-        (void)hipStreamSynchronize(ctx->stream);           // (what on_batch queued reads the side context's key arrays)
-        if (side) { (void)hipStreamSynchronize(side->stream); spsp_destroy(side); }
-        if (side2) { (void)hipStreamSynchronize(side2->stream); spsp_destroy(side2); }
+        if (!rc) rc = pass.on_close();
+        (void)hipStreamSynchronize(ctx->stream);           // (what on_batch queued reads the side contexts' key arrays)
+        for (spsp_ctx* s : side)
+            if (s) { (void)hipStreamSynchronize(s->stream); spsp_destroy(s); }
     }
-    *t1 = run.end();
+    out->t1 = run.end();
     return rc;
 }
 
-int extract_write(spsp_ctx* ctx, ExtractRun* extract, ExtractRun* extract_mates, const char* out_prefix, int chatter) {
-    if (extract->split) return split_write(ctx, extract, extract_mates, out_prefix, chatter);
-    if (!extract_mates) return extract->write(ctx, out_prefix, chatter);
+// what a driver writes for its extraction: the split's files and manifest, the one file of extract[0].write, or the two files of a
+// paired run and one line for both
+static int extract_write(spsp_ctx* ctx, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out) {
+    ExtractRun *extract = &out->extract[0], *mates = ask.mates_path ? &out->extract[1] : nullptr;
+    if (ask.mode == kRmSplit) return split_write(ctx, extract, mates, pass.bin_names(), pass.last_name(), ask.out_prefix, ask.chatter);
+    if (!mates) return extract->write(ctx, ask.out_prefix, ask.chatter);
     int rc;
-    if ((rc = extract->write(ctx, out_prefix, 0)) || (rc = extract_mates->write(ctx, out_prefix, 0)) || !chatter) return rc;
-    printf("extract %s: %llu of %llu pair(s) kept, %llu + %llu byte(s) written to %s_extract_1 and _extract_2\n", extract->what,
-           (unsigned long long)extract->n_kept, (unsigned long long)extract->n_rec, (unsigned long long)extract->out.size(),
-           (unsigned long long)extract_mates->out.size(), out_prefix);
+    if ((rc = extract->write(ctx, ask.out_prefix, 0)) || (rc = mates->write(ctx, ask.out_prefix, 0)) || !ask.chatter) return rc;
+    printf("extract %s: %llu of %llu pair(s) kept, %llu + %llu byte(s) written to %s_extract_1 and _extract_2\n", extract->what, (unsigned long long)extract->n_kept,
+           (unsigned long long)extract->n_rec, (unsigned long long)extract->out.size(), (unsigned long long)mates->out.size(), ask.out_prefix);
     fflush(stdout);
     return SPSP_OK;
 }
 
-// spsp_classify_files behind its argument checks (mates_path: null, or the paired form with extract_mates beside extract)
-static int classify_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys, uint32_t num,
-                          uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_classify_record>* recs,
-                          std::vector<spsp_classify_hit>* hits, ExtractRun* extract, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr,
-                          WindowsRun* windows = nullptr, const char* window_word = nullptr) {
-    FilesRun run(ctx, paths, n_ref, chatter);
-    std::vector<std::string> names;
-    double t1 = 0;
-    if (extract)
-        extract->flags = [&](uint32_t n_rec, uint8_t* keep) {
-            return spsp_extract_flags_classify_host(extract->what, recs->data(), hits->data(), n_rec, top, n_ref, keep);
-        };
-    for (ExtractRun* e : {extract, extract_mates})
-        if (e && e->split) {                               // (the names the summary prints: the references' paths)
-            e->bins = [&](uint32_t n_rec, uint32_t* bin, uint32_t* n_bins) {
-                return spsp_split_bins_classify_host(extract->what, recs->data(), hits->data(), n_rec, top, n_ref, bin, n_bins);
-            };
-            e->bin_names.assign(paths, paths + n_ref);
-            e->last_name = "unmatched";
-        }
-    int rc = records_files_road(
-        run, "classification is", &records_path, 1, rate, [] { return SPSP_OK; }, &names,
-        [&](uint32_t n_rec, const uint64_t* rec_off) {
-            recs->assign(n_rec, spsp_classify_record{});
-            hits->assign((size_t)n_rec * top, spsp_classify_hit{});
-            for (uint32_t r = 0; r < n_rec; ++r) (*recs)[r].length = rec_off[r + 1] - rec_off[r];
-            return SPSP_OK;
-        },
-        [&](const RecordBatch& B) {
-            return classify_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, top, min_keys, num, den, recs->data() + B.first_record,
-                                        hits->data() + (size_t)B.first_record * top);
-        },
-        [] { return SPSP_OK; }, &t1, extract, mates_path, extract_mates, windows);
-    if (rc) return rc;
-    if (windows) {
+int record_files_run(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out) {
+    FilesRun run(ctx, index_paths, n_ref, ask.chatter);
+    for (ExtractRun& e : out->extract) { e.what = ask.what; e.gz = ask.gz; }
+    if (ask.mates_path) { out->extract[0].tag = "_1"; out->extract[1].tag = "_2"; }
+    out->windows.window = ask.window;
+    int rc;
+    if ((rc = records_files_road(run, "classification is", pass, ask, out))) return rc;
+    if (ask.mode == kRmWindows) {
         // the rows are the windows': their calls are the split's bins, and the two windowed CSVs take the per-record CSVs' place
-        const size_t n_win = recs->size();
-        std::vector<uint32_t> call(n_win ? n_win : 1, n_ref), keys(call.size(), 0), hit_keys(call.size(), 0), support(call.size(), 0);
+        const size_t n_win = pass.n_rows();
+        std::vector<uint32_t> call(n_win ? n_win : 1, 0), keys(call.size(), 0), hit_keys(call.size(), 0), support(call.size(), 0);
         uint32_t n_bins = 0;
-        if ((rc = spsp_split_bins_classify_host(window_word, recs->data(), hits->data(), n_win, top, n_ref, call.data(), &n_bins))) return rc;
-        for (size_t w = 0; w < n_win; ++w) {
-            keys[w] = (*recs)[w].keys; hit_keys[w] = (*recs)[w].hit_keys;
-            support[w] = (*recs)[w].listed ? (*hits)[w * top].shared : 0u;
-        }
-        if ((rc = windows_write(ctx, windows, run.keys.k, call, keys, hit_keys, support, n_bins, names, paths, "unmatched", precision, out_prefix, t1, chatter))) return rc;
-        if (chatter) { say_common_rate(run.L, n_ref); fflush(stdout); }
-        return SPSP_OK;
+        if ((rc = pass.bins(ask.what, (uint32_t)n_win, call.data(), &n_bins))) return rc;
+        for (size_t w = 0; w < n_win; ++w) pass.window_addends(w, &keys[w], &hit_keys[w], &support[w]);
+        if ((rc = windows_write(ctx, &out->windows, run.keys.k, call, keys, hit_keys, support, n_bins, out->names, pass.bin_names(), pass.last_name(), ask.precision,
+                                ask.out_prefix, out->t1, ask.chatter))) return rc;
+    } else if ((rc = pass.write_rows(run, ask, out->names, out->t1)) || (ask.mode != kRmPlain && (rc = extract_write(ctx, pass, ask, out)))) return rc;
+    if (ask.chatter) {
+        if (ask.mode != kRmWindows) pass.say_rows(run, ask);
+        say_common_rate(run.L, n_ref);
+        fflush(stdout);
     }
-    std::vector<const char*> name_ptr(names.size());
-    for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
-    char* text = nullptr; uint64_t len = 0;
-    if ((rc = spsp_classify_csv_host(recs->data(), hits->data(), recs->size(), name_ptr.data(), paths, n_ref, top, precision, &text, &len))) return rc;
-    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify.csv.gz", t1))) return rc;
-    const double t2 = now_s();
-    if ((rc = spsp_classify_summary_csv_host(recs->data(), hits->data(), recs->size(), paths, n_ref, top, &text, &len))) return rc;
-    if ((rc = write_csv_gz(ctx, text, len, out_prefix, "_classify_summary.csv.gz", t2)) || (extract && (rc = extract_write(ctx, extract, extract_mates, out_prefix, chatter))) ||
-        !chatter)
-        return rc;
-    uint64_t with = 0;
-    for (const spsp_classify_record& r : *recs) with += r.listed != 0;
-    printf(mates_path ? "%zu pair(s) against %u reference(s): %llu with a match\n" : "%zu record(s) against %u reference(s): %llu with a match\n", recs->size(), n_ref, (unsigned long long)with);
-    say_common_rate(run.L, n_ref);
-    fflush(stdout);
     return SPSP_OK;
 }
+
+int record_files_entry(const RecordFront& front, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out) {
+    int rc;
+    if ((rc = record_files_check_args(front, ask))) return rc;
+    SPSP_HIP(hipSetDevice(front.ctx->device));
+    if ((rc = pass.prelude(ask))) return rc;
+    return record_files_run(front.ctx, front.index_paths, front.n_ref, pass, ask, out);
+}
+
+// classify as a record pass: the rows of all records (windows) on the host, a batch's call into its stretch of them
+struct ClassifyPass : RecordPass {
+    spsp_ctx* ctx;
+    const char* const* paths;
+    uint32_t n_ref, top, min_keys, num, den;
+    std::vector<spsp_classify_record> recs;
+    std::vector<spsp_classify_hit> hits;
+    explicit ClassifyPass(const RecordFront& f) : ctx(f.ctx), paths(f.index_paths), n_ref(f.n_ref), top(f.top), min_keys(f.min_keys), num(f.num), den(f.den) {}
+    int on_records(uint32_t n_rec, const uint64_t* rec_off) override {
+        recs.assign(n_rec, spsp_classify_record{});
+        hits.assign((size_t)n_rec * top, spsp_classify_hit{});
+        for (uint32_t r = 0; r < n_rec; ++r) recs[r].length = rec_off[r + 1] - rec_off[r];
+        return SPSP_OK;
+    }
+    int on_batch(const RecordBatch& B) override {
+        return classify_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, top, min_keys, num, den, recs.data() + B.first_record,
+                                    hits.data() + (size_t)B.first_record * top);
+    }
+    int keep_flags(const char* what, uint32_t n, uint8_t* keep) override { return spsp_extract_flags_classify_host(what, recs.data(), hits.data(), n, top, n_ref, keep); }
+    int bins(const char* what, uint32_t n, uint32_t* bin, uint32_t* n_bins) override {
+        return spsp_split_bins_classify_host(what, recs.data(), hits.data(), n, top, n_ref, bin, n_bins);
+    }
+    void window_addends(size_t w, uint32_t* keys, uint32_t* hit_keys, uint32_t* support) override {
+        *keys = recs[w].keys; *hit_keys = recs[w].hit_keys;
+        *support = recs[w].listed ? hits[w * top].shared : 0u;
+    }
+    const char* const* bin_names() override { return paths; }   // (the names the summary prints: the references' paths)
+    const char* last_name() override { return "unmatched"; }
+    size_t n_rows() override { return recs.size(); }
+    int write_rows(FilesRun&, const RecordsAsk& ask, const std::vector<std::string>& names, double t1) override {
+        int rc;
+        std::vector<const char*> name_ptr(names.size());
+        for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
+        char* text = nullptr; uint64_t len = 0;
+        if ((rc = spsp_classify_csv_host(recs.data(), hits.data(), recs.size(), name_ptr.data(), paths, n_ref, top, ask.precision, &text, &len))) return rc;
+        if ((rc = write_csv_gz(ctx, text, len, ask.out_prefix, "_classify.csv.gz", t1))) return rc;
+        const double t2 = now_s();
+        if ((rc = spsp_classify_summary_csv_host(recs.data(), hits.data(), recs.size(), paths, n_ref, top, &text, &len))) return rc;
+        return write_csv_gz(ctx, text, len, ask.out_prefix, "_classify_summary.csv.gz", t2);
+    }
+    void say_rows(FilesRun&, const RecordsAsk& ask) override {
+        uint64_t with = 0;
+        for (const spsp_classify_record& r : recs) with += r.listed != 0;
+        printf(ask.mates_path ? "%zu pair(s) against %u reference(s): %llu with a match\n" : "%zu record(s) against %u reference(s): %llu with a match\n", recs.size(), n_ref,
+               (unsigned long long)with);
+    }
+};
 
 }  // namespace spsp
 
@@ -822,69 +773,59 @@ extern "C" int spsp_classify_device(spsp_ctx* ctx, const void* d_q_minimizer, co
                                 min_keys, num, den, records, hits);
 }
 
-// spsp_classify_files, spsp_classify_files_extract and spsp_classify_files_paired (what == nullptr: no extraction; mates_path ==
-// nullptr: one records file; paired: the entry is the paired one, which mates_path must not be missing from)
-static int classify_files_entry(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
-                                uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, spsp_classify_record** records,
-                                spsp_classify_hit** hits, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out,
-                                bool paired = false, const char* mates_path = nullptr, bool split = false) {
+// spsp_classify_files, _extract, _paired and _split behind the filling of their ask: the outputs cleared, the front and the
+// driver, the rows handed out
+static int classify_files_entry(const RecordFront& front, const RecordsAsk& ask, spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records,
+                                uint64_t* n_kept, uint64_t* bytes_out) {
     if (records) *records = nullptr;
     if (hits) *hits = nullptr;
     if (n_records) *n_records = 0;
     if (n_kept) *n_kept = 0;
     if (bytes_out) *bytes_out = 0;
-    if (!ctx || !index_paths || !records_path || !out_prefix || (paired && !mates_path)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
-    int rc;
-    if ((rc = classify_check_args(top, min_keys, num, den))) return rc;
-    if (what && (rc = split ? spsp_split_word_check_host(what, 0) : spsp_extract_word_check_host(what, 0, n_ref))) return rc;   // (before any file is read)
-    SPSP_HIP(hipSetDevice(ctx->device));
-    std::vector<spsp_classify_record> got;
-    std::vector<spsp_classify_hit> got_hits;
-    ExtractRun extract, extract_mates;
-    extract.what = extract_mates.what = what; extract.gz = extract_mates.gz = gz; extract.split = extract_mates.split = split;
-    if (mates_path) { extract.tag = "_1"; extract_mates.tag = "_2"; }
-    if ((rc = classify_files(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, &got, &got_hits,
-                             what ? &extract : nullptr, mates_path, what && mates_path ? &extract_mates : nullptr))) return rc;
-    if (n_kept) *n_kept = split ? extract.bins_written : extract.n_kept;
-    if (bytes_out) *bytes_out = extract.out.size() + extract_mates.out.size();
-    if (n_records) *n_records = got.size();
-    if (records && (rc = give_rows(got, records))) return rc;
-    if (hits && (rc = give_rows(got_hits, hits))) { if (records) { free(*records); *records = nullptr; } return rc; }
-    return SPSP_OK;
+    ClassifyPass pass(front);
+    RecordsOut out;
+    if (const int rc = record_files_entry(front, pass, ask, &out)) return rc;
+    if (n_kept) *n_kept = out.n_kept(ask);
+    if (bytes_out) *bytes_out = out.bytes_out();
+    if (n_records) *n_records = pass.recs.size();
+    const RowsGift gifts[] = {{(void**)records, pass.recs.data(), pass.recs.size() * sizeof(spsp_classify_record)},
+                              {(void**)hits, pass.hits.data(), pass.hits.size() * sizeof(spsp_classify_hit)}};
+    return give_rows_all(gifts, 2);
 }
 
 extern "C" int spsp_classify_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
                                    uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
                                    spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records) {
-    return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
-                                nullptr, 1, nullptr, nullptr);
+    return classify_files_entry({ctx, index_paths, nullptr, false, false, n_ref, top, min_keys, num, den},
+                                records_ask(&records_path, nullptr, kRmPlain, nullptr, 1, 0, precision, out_prefix, chatter, rate), records, hits, n_records, nullptr, nullptr);
 }
 
 extern "C" int spsp_classify_files_extract(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top,
                                            uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
                                            spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records, const char* what, int gz,
                                            uint64_t* n_kept, uint64_t* bytes_out) {
-    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
-                                what, gz, n_kept, bytes_out);
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }   // (in front of the clearing: DESIGN "What the record file drivers share")
+    return classify_files_entry({ctx, index_paths, nullptr, false, false, n_ref, top, min_keys, num, den},
+                                records_ask(&records_path, nullptr, kRmExtract, what, gz, 0, precision, out_prefix, chatter, rate), records, hits, n_records, n_kept, bytes_out);
 }
 
 extern "C" int spsp_classify_files_paired(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
                                           uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter,
                                           double rate, const char* what, int gz, spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records,
                                           uint64_t* n_kept, uint64_t* bytes_out) {
-    return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
-                                what, gz, n_kept, bytes_out, true, mates_path);
+    return classify_files_entry({ctx, index_paths, nullptr, false, true, n_ref, top, min_keys, num, den},
+                                records_ask(&records_path, mates_path, what ? kRmExtract : kRmPlain, what, gz, 0, precision, out_prefix, chatter, rate), records, hits,
+                                n_records, n_kept, bytes_out);
 }
 
 extern "C" int spsp_classify_files_split(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
                                          uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter,
                                          double rate, const char* what, int gz, spsp_classify_record** records, spsp_classify_hit** hits, uint64_t* n_records,
                                          uint64_t* n_bins_written, uint64_t* bytes_out) {
-    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    return classify_files_entry(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, records, hits, n_records,
-                                what, gz, n_bins_written, bytes_out, false, mates_path, true);
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }   // (likewise)
+    return classify_files_entry({ctx, index_paths, nullptr, false, false, n_ref, top, min_keys, num, den},
+                                records_ask(&records_path, mates_path, kRmSplit, what, gz, 0, precision, out_prefix, chatter, rate), records, hits, n_records,
+                                n_bins_written, bytes_out);
 }
 
 extern "C" int spsp_classify_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
@@ -899,37 +840,20 @@ extern "C" int spsp_classify_files_windows(spsp_ctx* ctx, const char* const* ind
     if (n_windows) *n_windows = 0;
     if (n_records) *n_records = 0;
     if (n_segments) *n_segments = 0;
-    if (!ctx || !index_paths || !records_path || !out_prefix || !what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
-    int rc;
-    if ((rc = classify_check_args(top, min_keys, num, den)) || (rc = spsp_windows_word_check_host(what, 0))) return rc;   // (before any file is read)
-    if (window == 0 || window > kWnMaxWidth) {             // (against k: once the sketches' headers are read, in front of the records file)
-        set_error("windows: the width must be k .. %llu (width = %llu)", (unsigned long long)kWnMaxWidth, (unsigned long long)window);
-        return SPSP_ERR_ARG;
-    }
-    SPSP_HIP(hipSetDevice(ctx->device));
-    std::vector<spsp_classify_record> got;
-    std::vector<spsp_classify_hit> got_hits;
-    WindowsRun run;
-    run.window = window;
-    if ((rc = classify_files(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, &got, &got_hits, nullptr, nullptr,
-                             nullptr, &run, what))) return rc;
-    if (n_windows) *n_windows = got.size();
+    const RecordFront front{ctx, index_paths, nullptr, false, false, n_ref, top, min_keys, num, den};
+    ClassifyPass pass(front);
+    RecordsOut out;
+    if (const int rc = record_files_entry(front, pass, records_ask(&records_path, nullptr, kRmWindows, what, 1, window, precision, out_prefix, chatter, rate), &out)) return rc;
+    const WindowsRun& run = out.windows;
+    if (n_windows) *n_windows = pass.recs.size();
     if (n_records) *n_records = run.mosaic.size();
     if (n_segments) *n_segments = run.segments.size();
-    void* given[5] = {};
-    if ((rows && (rc = give_rows(got, rows))) || (rows && !(given[0] = *rows)) || (hits && (rc = give_rows(got_hits, hits))) || (hits && !(given[1] = *hits)) ||
-        (first_win && (rc = give_rows(run.first_win, first_win))) || (first_win && !(given[2] = *first_win)) ||
-        (segments && (rc = give_rows(run.segments, segments))) || (segments && !(given[3] = *segments)) || (mosaic && (rc = give_rows(run.mosaic, mosaic)))) {
-        for (void* g : given) free(g);
-        if (rows) *rows = nullptr;
-        if (hits) *hits = nullptr;
-        if (first_win) *first_win = nullptr;
-        if (segments) *segments = nullptr;
-        if (mosaic) *mosaic = nullptr;
-        return rc ? rc : (int)SPSP_ERR_NOMEM;
-    }
-    return SPSP_OK;
+    const RowsGift gifts[] = {{(void**)rows, pass.recs.data(), pass.recs.size() * sizeof(spsp_classify_record)},
+                              {(void**)hits, pass.hits.data(), pass.hits.size() * sizeof(spsp_classify_hit)},
+                              {(void**)first_win, run.first_win.data(), run.first_win.size() * sizeof(uint32_t)},
+                              {(void**)segments, run.segments.data(), run.segments.size() * sizeof(spsp_segment_row)},
+                              {(void**)mosaic, run.mosaic.data(), run.mosaic.size() * sizeof(spsp_mosaic_row)}};
+    return give_rows_all(gifts, 5);
 }
 
 extern "C" int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms) {

@@ -446,27 +446,44 @@ int depth_read_impl(spsp_ctx* ctx, uint32_t min_count, spsp_depth_row* rows, sps
     return SPSP_OK;
 }
 
+// depth as a record pass, which serves the profile as well: counters behind the index, a batch's keys added, and at the close --
+// in front of the side context's end -- the read and, where asked, the profile.  No per-record rows: nothing to extract from
+struct DepthPass : RecordPass {
+    spsp_ctx* ctx;
+    uint32_t n_ref, min_count;
+    std::vector<spsp_depth_row>* rows;
+    spsp_depth_totals* totals;
+    ProfileAsk* profile;
+    uint64_t n_records = 0;
+    DepthPass(spsp_ctx* c, uint32_t n, uint32_t min_c, std::vector<spsp_depth_row>* r, spsp_depth_totals* t, ProfileAsk* p)
+        : ctx(c), n_ref(n), min_count(min_c), rows(r), totals(t), profile(p) {}
+    int on_index() override { return depth_begin_impl(ctx); }
+    int on_records(uint32_t n_rec, const uint64_t*) override { n_records += n_rec; return SPSP_OK; }
+    int on_batch(const RecordBatch& B) override { return depth_add_impl(ctx, B.mn, B.lo, B.hi, B.key_off[0], B.key_off[B.n_records] - B.key_off[0]); }
+    int on_close() override {
+        int rc = depth_read_impl(ctx, min_count, rows->data(), totals, nullptr);
+        if (!rc && profile) {
+            uint64_t n_rows = 0;
+            profile->rows.assign(n_ref, spsp_profile_row{});
+            rc = profile_impl(ctx, min_count, profile->min_keys, profile->max_rounds, profile->rows.data(), &n_rows, &profile->totals, nullptr);
+            profile->rows.resize(rc ? 0 : (size_t)n_rows);
+        }
+        return rc;
+    }
+};
+
 int depth_files_impl(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* const* reads_paths, uint32_t n_reads, uint32_t min_count, int precision,
                      const char* out_prefix, int chatter, double rate, std::vector<spsp_depth_row>* rows, spsp_depth_totals* totals, ProfileAsk* profile) {
     FilesRun run(ctx, paths, n_ref, chatter);
-    uint64_t n_records = 0;
-    double t1 = 0;
     rows->assign(n_ref, spsp_depth_row{});
-    int rc = records_files_road(
-        run, "depth is", reads_paths, n_reads, rate, [&] { return depth_begin_impl(ctx); }, nullptr,
-        [&](uint32_t n_rec, const uint64_t*) { n_records += n_rec; return SPSP_OK; },
-        [&](const RecordBatch& B) { return depth_add_impl(ctx, B.mn, B.lo, B.hi, B.key_off[0], B.key_off[B.n_records] - B.key_off[0]); },
-        [&] {                                              // the read and, where asked, the profile: in front of the side context's end
-            int rc = depth_read_impl(ctx, min_count, rows->data(), totals, nullptr);
-            if (!rc && profile) {
-                uint64_t n_rows = 0;
-                profile->rows.assign(n_ref, spsp_profile_row{});
-                rc = profile_impl(ctx, min_count, profile->min_keys, profile->max_rounds, profile->rows.data(), &n_rows, &profile->totals, nullptr);
-                profile->rows.resize(rc ? 0 : (size_t)n_rows);
-            }
-            return rc;
-        },
-        &t1);
+    DepthPass pass(ctx, n_ref, min_count, rows, totals, profile);
+    RecordsAsk ask;
+    ask.records_paths = reads_paths; ask.n_records_paths = n_reads; ask.rate = rate; ask.precision = precision; ask.out_prefix = out_prefix; ask.chatter = chatter;
+    RecordsOut out;
+    out.want_names = false;
+    int rc = records_files_road(run, "depth is", pass, ask, &out);
+    const double t1 = out.t1;
+    const uint64_t n_records = pass.n_records;
     if (rc) return rc;
     char* text = nullptr; uint64_t len = 0;
     if ((rc = spsp_depth_csv_host(rows->data(), paths, n_ref, precision, &text, &len))) return rc;

@@ -484,15 +484,12 @@ int records_extract_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, 
     return SPSP_OK;
 }
 
-int ExtractRun::on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_records) {
+int ExtractRun::on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_records, const uint8_t* keep) {
     int rc;
-    if (split) return split_text(side, d_text, n_text, n_records);
-    std::vector<uint8_t> keep(n_records ? n_records : 1, 0);
-    if ((rc = flags(n_records, keep.data()))) return rc;
     uint8_t* d_out = nullptr;
     uint64_t n_out = 0;
     // (the ingest has told the road n_records: the starts are made for as many, with no wait of their own)
-    if ((rc = records_extract_impl(side, d_text, n_text, nullptr, n_records, keep.data(), &d_out, &n_out, &n_kept, &fastq))) return rc;
+    if ((rc = records_extract_impl(side, d_text, n_text, nullptr, n_records, keep, &d_out, &n_out, &n_kept, &fastq))) return rc;
     n_rec = n_records;
     out.resize((size_t)n_out);
     if (n_out) SPSP_HIP(hipMemcpyAsync(out.data(), d_out, (size_t)n_out, hipMemcpyDeviceToHost, side->stream));   // only the kept bytes come back
@@ -503,13 +500,7 @@ int ExtractRun::on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, 
 int ExtractRun::write(spsp_ctx* ctx, const char* out_prefix, int chatter) {
     const std::string path = std::string(out_prefix) + "_extract" + tag + (fastq ? ".fq" : ".fa") + (gz ? ".gz" : "");
     const double t = now_s();
-    int rc = SPSP_OK;
-    if (gz) rc = spsp_write_gz_host(path.c_str(), out.data(), out.size(), 1);
-    else {
-        FILE* f = fopen(path.c_str(), "wb");
-        const bool wrote = f && fwrite(out.data(), 1, out.size(), f) == out.size();
-        if ((f && fclose(f) != 0) || !wrote) { set_error("cannot write '%s'", path.c_str()); rc = SPSP_ERR_IO; }
-    }
+    const int rc = write_bytes(path.c_str(), out.data(), out.size(), gz);
     ctx->stages.csv_gzip_s += now_s() - t;
     if (!rc && chatter) {
         printf("extract %s: %llu of %llu record(s) kept, %llu byte(s) written to %s\n", what, (unsigned long long)n_kept, (unsigned long long)n_rec,

@@ -1865,6 +1865,72 @@ int classify_check_args(uint32_t top, uint32_t min_keys, uint32_t num, uint32_t 
 
 // spsp_taxonomy.hip: likewise
 int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den) { return threshold_check("taxonomy", min_keys, num, den); }
+
+// What the record file drivers need no device for (spsp_classify.hip; DESIGN "What the record file drivers share")
+void record_names_host(const uint8_t* text, uint64_t n, bool fastq, std::vector<std::string>* names) {
+    uint64_t end = n;
+    while (end && (text[end - 1] == '\n' || text[end - 1] == '\r')) --end;   // (FASTQ: the content without its trailing blank lines)
+    uint64_t line = 0;
+    for (uint64_t pos = 0; pos < (fastq ? end : n); ++line) {
+        uint64_t stop = pos;
+        while (stop < n && text[stop] != '\n') ++stop;
+        const bool header = fastq ? line % 4 == 0 : text[pos] == '>';
+        if (header) {
+            uint64_t a = pos < stop ? pos + 1 : pos, z = a;   // (behind the '>' or '@')
+            while (z < stop && text[z] != ' ' && text[z] != '\t' && text[z] != '\r') ++z;
+            names->emplace_back((const char*)text + a, (size_t)(z - a));
+        }
+        pos = stop + 1;
+    }
+}
+
+std::vector<uint32_t> records_batch_bounds(uint32_t n_rec) {
+    std::vector<uint32_t> bounds;
+    for (uint64_t r = 0; r < n_rec; r += 65535u) bounds.push_back((uint32_t)r);
+    bounds.push_back(n_rec);
+    return bounds;
+}
+
+int write_bytes(const char* path, const uint8_t* data, uint64_t len, int gz) {
+    if (gz) return spsp_write_gz_host(path, data, len, 1);
+    FILE* f = fopen(path, "wb");
+    const bool wrote = f && fwrite(data, 1, (size_t)len, f) == len;
+    if ((f && fclose(f) != 0) || !wrote) { set_error("cannot write '%s'", path); return SPSP_ERR_IO; }
+    return SPSP_OK;
+}
+
+int record_files_check_args(const RecordFront& front, const RecordsAsk& ask) {
+    const int tax = front.taxonomy ? 1 : 0;
+    if (!front.ctx || !front.index_paths || !ask.records_paths || !ask.records_paths[0] || !ask.out_prefix || (tax && !front.lineages_path) ||
+        (front.paired && !ask.mates_path) || (ask.mode == kRmWindows && !ask.what)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (front.n_ref == 0 || front.n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", front.n_ref); return SPSP_ERR_ARG; }
+    int rc;
+    if ((rc = tax ? taxonomy_check_args(front.min_keys, front.num, front.den) : classify_check_args(front.top, front.min_keys, front.num, front.den))) return rc;
+    // (the word, before any file is read; a taxonomy's extract word names its node once the tree is)
+    if (ask.mode == kRmExtract && (rc = spsp_extract_word_check_host(ask.what, tax, tax ? 0xffffffffu : front.n_ref))) return rc;
+    if (ask.mode == kRmSplit && (rc = spsp_split_word_check_host(ask.what, tax))) return rc;
+    if (ask.mode == kRmWindows && (rc = spsp_windows_word_check_host(ask.what, tax))) return rc;
+    if (ask.mode == kRmWindows && (ask.window == 0 || ask.window > kWnMaxWidth)) {   // (against k: once the sketches' headers are read, behind the ingest)
+        set_error("windows: the width must be k .. %llu (width = %llu)", (unsigned long long)kWnMaxWidth, (unsigned long long)ask.window);
+        return SPSP_ERR_ARG;
+    }
+    return SPSP_OK;
+}
+
+int give_rows_all(const RowsGift* gifts, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+        if (!gifts[i].out) continue;
+        void* p = malloc(gifts[i].bytes ? gifts[i].bytes : 1);
+        if (!p) {
+            for (size_t j = 0; j < n; ++j) if (gifts[j].out) { if (j < i) free(*gifts[j].out); *gifts[j].out = nullptr; }
+            set_error("out of host memory");
+            return SPSP_ERR_NOMEM;
+        }
+        if (gifts[i].bytes) memcpy(p, gifts[i].rows, gifts[i].bytes);
+        *gifts[i].out = p;
+    }
+    return SPSP_OK;
+}
 }  // namespace spsp
 
 namespace {

@@ -561,58 +561,121 @@ int classify_check_args(uint32_t top, uint32_t min_keys, uint32_t num, uint32_t 
 int classify_index_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n_ref);
 int classify_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
                          uint32_t top, uint32_t min_keys, uint32_t num, uint32_t den, spsp_classify_record* records, spsp_classify_hit* hits);
-// the records path the classification and the depth pass share (spsp_classify.hip): a FASTA / FASTQ text ingested and scanned once
-// on `side`, a second context of ctx's device; the records' keys extracted there in batches of at most 65 535 records and handed to
-// on_batch, whose work is queued on ctx (spsp_wait_stream orders the two contexts around every batch: the keys of a batch are read
-// before the next extraction overwrites them).  names: null, or the records' names as the host reads them from the header lines --
-// then a text with another number of header lines than the device finds records is SPSP_ERR_FORMAT.  on_records is called once,
-// behind the scan, with the records' base offsets (n_rec + 1).  windows: null, or a windows run (spsp_windows.hip) -- behind the
-// ingest and in front of the scan every record is cut into windows on `side`, and the scan, the seams, the key extraction,
-// on_records and on_batch then see the WINDOWS as records; the header count is still held against the real records, whose offsets
-// and first_win the run keeps for the driver
+// the records path the record file drivers share (spsp_classify.hip): a FASTA / FASTQ text ingested and scanned once on a side
+// context, a second context of ctx's device; the records' keys extracted there in batches of at most 65 535 records and handed to
+// the pass's on_batch, whose work is queued on ctx (spsp_wait_stream orders the two contexts around every batch: the keys of a
+// batch are read before the next extraction overwrites them).  Three plain types carry a run: RecordsAsk, what the caller asked;
+// RecordPass, what differs between classify, taxonomy and depth; RecordsOut, what the road leaves behind for the driver
 struct RecordBatch { uint32_t first_record, n_records; const uint32_t* mn; const uint64_t *lo, *hi; const uint64_t* key_off; };   // key_off: host, n_records + 1
-// what a record file driver writes beside its CSVs when it is asked to (spsp_extract.hip).  on_text is the road's hook: behind a
-// file's last batch, with the text still in the side context's buffer, it has `flags` (the driver's: its rows -> keep[n_rec]) make
-// the flags, runs the extraction on `side` and brings the kept bytes to `out`.  write: <out_prefix>_extract.fa or .fq (by the
-// text's kind), gzip level 1 with ".gz" appended when gz, and with chatter the line of what was kept.  tag: "" for a records file
-// alone; "_1" and "_2" for the two mates of the paired form, whose files are <out_prefix>_extract_1.* and <out_prefix>_extract_2.*
-// The same hook in its second form, the split (spsp_split.hip; `split` set by the entry): `bins` (the driver's: its rows ->
-// bin[n_rec] and n_bins) takes the place of `flags`, on_text runs the split on `side` and brings every bin's slice to `out`, which
-// bin_off cuts.  bin_names (n_bins - 1) and last_name are the driver's, for the manifest.  extract_write then writes one file per
-// bin with records, <out_prefix>_split_<b><tag>.fa|fq[.gz], and <out_prefix>_split.csv.gz
+// what the caller asked of a record file driver: filled in by the entry, read by everything below it.  mode: what is written
+// beside the pass's CSVs -- nothing, the records a word names (extract), every record to the file of its bin (split) -- or in
+// their place, the records cut into windows (windows).  what: the word of extract and split, the call word of windows.
+// mates_path: null, or the second file of a paired run (records_paths[0] is the first then).  Depth and profile fill in the
+// paths, rate, precision, out_prefix and chatter
+enum RecordsMode { kRmPlain = 0, kRmExtract, kRmSplit, kRmWindows };
+struct RecordsAsk {
+    const char* const* records_paths = nullptr;
+    uint32_t n_records_paths = 0;
+    const char* mates_path = nullptr;
+    RecordsMode mode = kRmPlain;
+    const char* what = nullptr;
+    int gz = 1;
+    uint64_t window = 0;
+    int precision = 6;
+    const char* out_prefix = nullptr;
+    int chatter = 0;
+    double rate = 0;
+};
+// an entry's ask: records_path is the address of the entry's own argument, which outlives the call
+inline RecordsAsk records_ask(const char* const* records_path, const char* mates_path, RecordsMode mode, const char* what, int gz, uint64_t window, int precision,
+                              const char* out_prefix, int chatter, double rate) {
+    RecordsAsk ask;
+    ask.records_paths = records_path; ask.n_records_paths = 1; ask.mates_path = mates_path;
+    ask.mode = mode; ask.what = what; ask.gz = gz; ask.window = window;
+    ask.precision = precision; ask.out_prefix = out_prefix; ask.chatter = chatter; ask.rate = rate;
+    return ask;
+}
+// what a pass is to the road and to the driver's tails; classify, taxonomy and depth (which serves profile) implement it.
+// prelude: in front of the load (taxonomy: the lineage file, and extract's node against the tree).  on_index: once, behind the
+// index.  on_records: once per file (or pair of files), behind the scan, with the records' base offsets
+// (n_rec + 1; a pair: the mates' summed).  on_batch: a batch's keys, queued on ctx.  on_close: behind the last file, in front of
+// the side contexts' end.  keep_flags / bins: the pass's rows -> keep[n] of extract's word / bin[n] and n_bins of split's or
+// windows' word.  window_addends: window w's keys, hit keys and support.  bin_names (n_bins - 1) and last_name: for the manifest
+// and the windowed CSVs.  write_rows: the pass's two CSVs, made and written in the pass's own order.  say_rows: its one
+// chatter line.  A pass that has no rows to extract from (depth) keeps the refusals, which no entry reaches
+struct FilesRun;
+struct RecordPass {
+    virtual ~RecordPass() {}
+    virtual int prelude(const RecordsAsk&) { return SPSP_OK; }
+    virtual int on_index() { return SPSP_OK; }
+    virtual int on_records(uint32_t, const uint64_t*) { return SPSP_OK; }
+    virtual int on_batch(const RecordBatch&) { return SPSP_OK; }
+    virtual int on_close() { return SPSP_OK; }
+    virtual int keep_flags(const char*, uint32_t, uint8_t*) { return no_rows(); }
+    virtual int bins(const char*, uint32_t, uint32_t*, uint32_t*) { return no_rows(); }
+    virtual void window_addends(size_t, uint32_t*, uint32_t*, uint32_t*) {}
+    virtual const char* const* bin_names() { return nullptr; }
+    virtual const char* last_name() { return ""; }
+    virtual int write_rows(FilesRun&, const RecordsAsk&, const std::vector<std::string>&, double) { return SPSP_OK; }
+    virtual void say_rows(FilesRun&, const RecordsAsk&) {}
+    virtual size_t n_rows() { return 0; }
+    static int no_rows() { set_error("this pass has no per-record rows to extract from"); return SPSP_ERR_ARG; }
+};
+// what a record file driver writes beside its CSVs when it is asked to (spsp_extract.hip, spsp_split.hip): one text's cut, on its
+// side context.  The road asks the pass once per file (or pair of files) for keep[] or for bin[] and n_bins, behind the last
+// batch and with the text still in the side context's buffer, and hands the plain vector to on_text (the extraction: the kept
+// bytes to `out`) or split_text (every bin's slice to `out`, which bin_off cuts) of each run.  write: <out_prefix>_extract.fa or
+// .fq (by the text's kind), gzip level 1 with ".gz" appended when gz, and with chatter the line of what was kept.  tag: "" for a
+// records file alone; "_1" and "_2" for the two mates of the paired form, whose files are <out_prefix>_extract_1.* and _2.*
 struct ExtractRun {
     const char* what = nullptr;
     const char* tag = "";
     int gz = 1;
-    std::function<int(uint32_t, uint8_t*)> flags;
     bool fastq = false;
     uint64_t n_rec = 0, n_kept = 0;
     std::vector<uint8_t> out;
-    bool split = false;
-    std::function<int(uint32_t, uint32_t*, uint32_t*)> bins;
     uint32_t n_bins = 0;
     std::vector<uint64_t> bin_off, bin_records;
-    std::vector<const char*> bin_names;
-    const char* last_name = "";
     uint64_t bins_written = 0;
-    int on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_rec);
-    int split_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_rec);
+    int on_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_rec, const uint8_t* keep);
+    int split_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_rec, const uint32_t* bin, uint32_t n_bins);
     int write(spsp_ctx* ctx, const char* out_prefix, int chatter);
 };
-// spsp_split.hip: the files and the manifest of a split run (mates: null, or the second mate's run); spsp_host.cpp: a bin's file name
-int split_write(spsp_ctx* ctx, ExtractRun* run, ExtractRun* mates, const char* out_prefix, int chatter);
+// the windows run of a record file driver (spsp_windows.hip): the width; what the road leaves behind for the driver (first_win over
+// the file's real records and their offsets, beside the windows the passes saw as records)
+struct WindowsRun {
+    uint64_t window = 0;
+    std::vector<uint32_t> first_win;
+    std::vector<uint64_t> rec_off;
+    std::vector<spsp_segment_row> segments;
+    std::vector<spsp_mosaic_row> mosaic;
+};
+// what the road leaves behind for the driver and the entry.  names: the records' names as the host reads them from the header
+// lines (a pair: the mates' common names) -- then a text with another number of header lines than the device finds records is
+// SPSP_ERR_FORMAT; want_names == false (depth: many files, no rows): no names, no header count.  t1: run.end().  extract: the
+// one run, or the two mates'.  windows: behind the ingest and in front of the scan every record is cut into windows on the side
+// context, and the scan, the seams, the key extraction, on_records and on_batch then see the WINDOWS as records; the header
+// count is still held against the real records
+struct RecordsOut {
+    bool want_names = true;
+    std::vector<std::string> names;
+    double t1 = 0;
+    ExtractRun extract[2];
+    WindowsRun windows;
+    uint64_t n_kept(const RecordsAsk& ask) const { return ask.mode == kRmSplit ? extract[0].bins_written : extract[0].n_kept; }
+    uint64_t bytes_out() const { return extract[0].out.size() + extract[1].out.size(); }
+};
+// spsp_split.hip: the files and the manifest of a split run (mates: null, or the second mate's run; bin_names (n_bins - 1) and
+// last_name: the pass's); spsp_host.cpp: a bin's file name
+int split_write(spsp_ctx* ctx, ExtractRun* run, ExtractRun* mates, const char* const* bin_names, const char* last_name, const char* out_prefix, int chatter);
 std::string split_file_name(const char* prefix, uint32_t b, uint32_t n_bins, const char* last_name, const char* tag, const char* suffix);
-int records_text_batches(spsp_ctx* ctx, spsp_ctx* side, const spsp_params* p, const uint8_t* text, uint64_t n_text, const char* path,
-                         std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* extract = nullptr, struct WindowsRun* windows = nullptr);
-// the paired form (spsp_classify.hip): text[0] and text[1] hold the two mates of every pair, on a side context each; the union of
-// the two mates' keys per pair (spsp_union.hip) is what on_batch gets.  extract: null, or the two mates' runs
-int records_pair_batches(spsp_ctx* ctx, spsp_ctx* const* side, const spsp_params* p, const uint8_t* const* text, const uint64_t* n_text, const char* const* path,
-                         std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                         const std::function<int(const RecordBatch&)>& on_batch, ExtractRun* const* extract);
-// what a driver writes for its extraction: the one file of extract->write, or, with the mates' run, the two files of a paired run
-// and one line for both
-int extract_write(spsp_ctx* ctx, ExtractRun* extract, ExtractRun* extract_mates, const char* out_prefix, int chatter);
+// what needs no device (spsp_host.cpp).  record_names_host: the records' names as the host reads them from the text, the first
+// whitespace-delimited word of every header line -- FASTA: the lines that begin with '>'; FASTQ: every fourth line up to the
+// content's end, which begins with '@'.  records_batch_bounds: 0, 65 535, 131 070, ..., n_rec -- batch b = records [bounds[b],
+// bounds[b + 1]).  write_bytes: a file as it is, or gzip level 1 (the caller has appended ".gz")
+void record_names_host(const uint8_t* text, uint64_t n, bool fastq, std::vector<std::string>* names);
+std::vector<uint32_t> records_batch_bounds(uint32_t n_rec);
+int write_bytes(const char* path, const uint8_t* data, uint64_t len, int gz);
 // spsp_depth.hip: how many records hold each key of the index, and the per-reference statistics over those counts
 constexpr uint32_t kDpThreads = 256;                       // every depth kernel: 4 waves
 constexpr uint32_t kDpBins = 4096;                         // bins of one LDS histogram of k_dp_reduce: the last holds every count at or above kDpBins - 1
@@ -677,17 +740,27 @@ struct RecordWork {
 // holds it), work[r] and hit[r] added up per record.  d_off: the record offsets on the device.  The caller has cleared work and hit
 int classify_probe_launch(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* d_off, uint32_t n_rec,
                           uint64_t all_keys, uint32_t* d_kn, unsigned long long* d_work, uint32_t* d_hit);
-// the road of the four record file drivers (spsp_classify.hip): run.load(rate), the k == m refusal in the pass's words (what_is:
-// "classification is", "depth is"), one record rate, the decoding and the index, on_index behind it, then every records file read
-// and sent through records_text_batches on ONE second context (spsp_wait_stream(side, ctx) in front of every file: the last
-// file's keys have been read), on_close where all of that went well, the wait for ctx's stream and the second context's end;
-// *t1 = run.end().  names: null, or the records' names (one records file then).  mates_path: null, or the second file of a paired
-// run -- records_paths[0] and it go through records_pair_batches on two side contexts instead, with extract_mates beside extract
-struct FilesRun;
-int records_files_road(FilesRun& run, const char* what_is, const char* const* records_paths, uint32_t n_records_paths, double rate,
-                       const std::function<int()>& on_index, std::vector<std::string>* names, const std::function<int(uint32_t, const uint64_t*)>& on_records,
-                       const std::function<int(const RecordBatch&)>& on_batch, const std::function<int()>& on_close, double* t1,
-                       ExtractRun* extract = nullptr, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr, struct WindowsRun* windows = nullptr);
+// the road of the record file drivers (spsp_classify.hip): run.load(ask.rate), the k == m refusal in the pass's words (what_is:
+// "classification is", "depth is"), one record rate, the decoding and the index, pass.on_index behind it, then every records
+// file read and sent through its batches on ONE second context (spsp_wait_stream(side, ctx) in front of every file: the last
+// file's keys have been read) -- or, with ask.mates_path, records_paths[0] and it on two side contexts, the union of the two
+// mates' keys per pair (spsp_union.hip) being what on_batch gets -- pass.on_close where all of that went well, the wait for
+// ctx's stream and the side contexts' end; out->t1 = run.end()
+int records_files_road(FilesRun& run, const char* what_is, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out);
+// the one driver body behind classify and taxonomy (spsp_classify.hip): the runs' tags from the ask, the road, then windows mode's
+// tail (the pass's bins and addends, windows_write) or the pass's write_rows and, where asked, the extraction's or the split's
+// files; the pass's chatter line and the common rate's
+int record_files_run(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out);
+// the front of the ten file entries.  record_files_check_args (spsp_host.cpp), in this order: NULL arguments (lineages_path with
+// taxonomy, mates_path with paired, the word with windows), the reference count, the pass's thresholds, the word that belongs to
+// the mode, the windows' width.  record_files_entry (spsp_classify.hip): those, hipSetDevice, the pass's prelude, record_files_run
+struct RecordFront { spsp_ctx* ctx; const char* const* index_paths; const char* lineages_path; bool taxonomy, paired; uint32_t n_ref, top, min_keys, num, den; };
+int record_files_check_args(const RecordFront& front, const RecordsAsk& ask);
+int record_files_entry(const RecordFront& front, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out);
+// several row arrays given out as give_rows gives one; where a later one fails, every array already given is freed and every
+// pointer is null again.  An `out` that is null is passed over
+struct RowsGift { void** out; const void* rows; size_t bytes; };
+int give_rows_all(const RowsGift* gifts, size_t n);
 int taxonomy_check_args(uint32_t min_keys, uint32_t num, uint32_t den);
 int taxonomy_index_impl(spsp_ctx* ctx, const uint32_t* parent, uint32_t T, const uint32_t* ref_node, uint32_t n_ref, const uint32_t** key_nodes_out);
 int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_lo, const uint64_t* q_hi, const uint64_t* h_rec_off, uint32_t n_rec,
@@ -767,15 +840,6 @@ __host__ __device__ inline uint64_t wn_bases(uint64_t L, uint64_t n_win, uint32_
 // the windows of a text's records in the context's buffers, with one host wait (for the counts).  h_first_win: n_rec + 1
 int records_windows_impl(spsp_ctx* ctx, const uint8_t* d_bases, uint64_t n_bases, const uint64_t* d_rec_off, uint32_t n_rec, uint32_t k, uint64_t window, bool packed,
                          uint8_t** d_out, uint64_t* n_out, uint64_t** d_win_off, uint32_t* h_first_win, uint64_t* n_windows);
-// the windows run of a record file driver: the width; what the road leaves behind for the driver (first_win over the file's real
-// records and their offsets, beside the windows the passes saw as records)
-struct WindowsRun {
-    uint64_t window = 0;
-    std::vector<uint32_t> first_win;
-    std::vector<uint64_t> rec_off;
-    std::vector<spsp_segment_row> segments;
-    std::vector<spsp_mosaic_row> mosaic;
-};
 // what a windowed driver does behind the road (spsp_windows.hip): segments and mosaic rows from the windows' calls and addends
 // (spsp_windows_segments_host), both texts made before either file is written, <out_prefix>_segments.csv.gz and
 // <out_prefix>_mosaic.csv.gz, and with chatter the one line.  call_names: n_bins - 1

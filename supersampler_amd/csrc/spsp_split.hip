@@ -376,17 +376,16 @@ int records_split_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, co
     return SPSP_OK;
 }
 
-int ExtractRun::split_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_records) {
+int ExtractRun::split_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_text, uint32_t n_records, const uint32_t* bin, uint32_t bins) {
     int rc;
-    std::vector<uint32_t> bin(n_records ? n_records : 1, SPSP_SPLIT_DROP);
-    if ((rc = bins(n_records, bin.data(), &n_bins))) return rc;
+    n_bins = bins;
     if (n_bins == 0 || n_bins > kSpMaxBins) { set_error("split: n_bins must be 1 .. %u (n_bins = %u)", kSpMaxBins, n_bins); return SPSP_ERR_ARG; }
     bin_off.assign((size_t)n_bins + 1, 0);
     bin_records.assign(n_bins, 0);
     uint8_t* d_out = nullptr;
     uint64_t n_out = 0;
     // (the ingest has told the road n_records: the starts are made for as many, with no wait of their own)
-    if ((rc = records_split_impl(side, d_text, n_text, nullptr, n_records, bin.data(), n_bins, &d_out, &n_out, bin_off.data(), bin_records.data(), &fastq))) return rc;
+    if ((rc = records_split_impl(side, d_text, n_text, nullptr, n_records, bin, n_bins, &d_out, &n_out, bin_off.data(), bin_records.data(), &fastq))) return rc;
     n_rec = n_kept = n_records;
     out.resize((size_t)n_out);
     if (n_out) SPSP_HIP(hipMemcpyAsync(out.data(), d_out, (size_t)n_out, hipMemcpyDeviceToHost, side->stream));   // every kept byte comes back once
@@ -394,7 +393,7 @@ int ExtractRun::split_text(spsp_ctx* side, const uint8_t* d_text, uint64_t n_tex
     return SPSP_OK;
 }
 
-int split_write(spsp_ctx* ctx, ExtractRun* run, ExtractRun* mates, const char* out_prefix, int chatter) {
+int split_write(spsp_ctx* ctx, ExtractRun* run, ExtractRun* mates, const char* const* bin_names, const char* last_name, const char* out_prefix, int chatter) {
     const double t = now_s();
     ExtractRun* side[2] = {run, mates};
     std::string suffix[2];
@@ -408,23 +407,16 @@ int split_write(spsp_ctx* ctx, ExtractRun* run, ExtractRun* mates, const char* o
         ++run->bins_written;
         for (int s = 0; s < 2 && !rc; ++s) {
             if (!side[s]) continue;
-            const std::string path = split_file_name(out_prefix, b, run->n_bins, run->last_name, side[s]->tag, suffix[s].c_str());
-            const uint8_t* data = side[s]->out.data() + side[s]->bin_off[b];
-            const uint64_t len = side[s]->bin_off[b + 1] - side[s]->bin_off[b];
+            const std::string path = split_file_name(out_prefix, b, run->n_bins, last_name, side[s]->tag, suffix[s].c_str());
             written.push_back(path);
-            if (side[s]->gz) rc = spsp_write_gz_host(path.c_str(), data, len, 1);
-            else {
-                FILE* f = fopen(path.c_str(), "wb");
-                const bool wrote = f && fwrite(data, 1, (size_t)len, f) == len;
-                if ((f && fclose(f) != 0) || !wrote) { set_error("cannot write '%s'", path.c_str()); rc = SPSP_ERR_IO; }
-            }
+            rc = write_bytes(path.c_str(), side[s]->out.data() + side[s]->bin_off[b], side[s]->bin_off[b + 1] - side[s]->bin_off[b], side[s]->gz);
         }
     }
     ctx->stages.csv_gzip_s += now_s() - t;
     char* text = nullptr; uint64_t len = 0;
     if (!rc) {
         const char* slash = strrchr(out_prefix, '/');      // (the manifest names the files as they lie beside it)
-        rc = spsp_split_csv_host(slash ? slash + 1 : out_prefix, run->bin_names.data(), run->last_name, run->n_bins, run->bin_records.data(), run->bin_off.data(),
+        rc = spsp_split_csv_host(slash ? slash + 1 : out_prefix, bin_names, last_name, run->n_bins, run->bin_records.data(), run->bin_off.data(),
                                  suffix[0].c_str(), mates ? mates->bin_off.data() : nullptr, suffix[1].c_str(), &text, &len);
     }
     if (!rc) rc = write_csv_gz(ctx, text, len, out_prefix, "_split.csv.gz", now_s());

@@ -392,88 +392,77 @@ int taxonomy_device_impl(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q_
     return SPSP_OK;
 }
 
-// spsp_taxonomy_files behind its argument checks
-static int taxonomy_files(spsp_ctx* ctx, const char* const* paths, uint32_t n_ref, const char* records_path, const char* lineages_path, uint32_t min_keys,
-                          uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, std::vector<spsp_taxonomy_record>* recs,
-                          ExtractRun* extract, const char* mates_path = nullptr, ExtractRun* extract_mates = nullptr, WindowsRun* windows = nullptr,
-                          const char* window_word = nullptr) {
-    int rc;
-    // the lineage file first: a tree that cannot be read costs no loading
-    uint8_t* lin = nullptr; uint64_t n_lin = 0;
-    if ((rc = spsp_read_file_host(lineages_path, &lin, &n_lin))) return rc;
-    std::vector<uint32_t> ref_node(n_ref, 0);
+// taxonomy as a record pass: the tree of the lineage file (the pass owns its four arrays), the rows of all records (windows) on
+// the host, a batch's call into its stretch of them
+struct TaxonomyPass : RecordPass {
+    spsp_ctx* ctx;
+    uint32_t n_ref, min_keys, num, den;
+    const char* lineages_path;
+    std::vector<uint32_t> ref_node;
     uint32_t *parent = nullptr, *depth = nullptr, *size = nullptr, T = 0;
-    char* blob = nullptr; uint64_t blob_len = 0;
-    rc = spsp_taxonomy_lineages_host((const char*)lin, n_lin, n_ref, ref_node.data(), &parent, &depth, extract ? &size : nullptr, &blob, &blob_len, &T);
-    spsp_free(lin);
-    if (rc) return rc;
-    if (extract && !extract->split) {
+    char* blob = nullptr;
+    std::vector<const char*> node_names;
+    std::vector<spsp_taxonomy_record> recs;
+    explicit TaxonomyPass(const RecordFront& f) : ctx(f.ctx), n_ref(f.n_ref), min_keys(f.min_keys), num(f.num), den(f.den), lineages_path(f.lineages_path) {}
+    ~TaxonomyPass() override { spsp_free(parent); spsp_free(depth); spsp_free(size); spsp_free(blob); }
+    // the lineage file first: a tree that cannot be read costs no loading
+    int prelude(const RecordsAsk& ask) override {
+        int rc;
+        uint8_t* lin = nullptr; uint64_t n_lin = 0, blob_len = 0;
+        if ((rc = spsp_read_file_host(lineages_path, &lin, &n_lin))) return rc;
+        ref_node.assign(n_ref, 0);
+        const bool cuts = ask.mode == kRmExtract || ask.mode == kRmSplit;
+        rc = spsp_taxonomy_lineages_host((const char*)lin, n_lin, n_ref, ref_node.data(), &parent, &depth, cuts ? &size : nullptr, &blob, &blob_len, &T);
+        spsp_free(lin);
+        if (rc) return rc;
         // (the word's node against the tree: still before any sketch is read)
-        if ((rc = spsp_extract_word_check_host(extract->what, 1, T))) { spsp_free(parent); spsp_free(depth); spsp_free(size); spsp_free(blob); return rc; }
-        extract->flags = [&, size, T](uint32_t n_rec, uint8_t* keep) { return spsp_extract_flags_taxonomy_host(extract->what, recs->data(), n_rec, size, T, keep); };
+        if (ask.mode == kRmExtract && (rc = spsp_extract_word_check_host(ask.what, 1, T))) return rc;
+        node_names.resize(T);
+        for (uint64_t at = 0, t = 0; t < T; ++t) { node_names[t] = blob + at; at += strlen(blob + at) + 1; }
+        return SPSP_OK;
     }
-    std::vector<const char*> node_names(T);
-    for (uint64_t at = 0, t = 0; t < T; ++t) { node_names[t] = blob + at; at += strlen(blob + at) + 1; }
-    for (ExtractRun* e : {extract, extract_mates})
-        if (e && e->split) {                               // (the names the report prints: the nodes')
-            e->bins = [&, parent, depth, T](uint32_t n_rec, uint32_t* bin, uint32_t* n_bins) {
-                return spsp_split_bins_taxonomy_host(extract->what, recs->data(), n_rec, parent, depth, T, bin, n_bins);
-            };
-            e->bin_names = node_names;
-            e->last_name = "unclassified";
-        }
-    FilesRun run(ctx, paths, n_ref, chatter);
-    std::vector<std::string> names;
-    double t1 = 0;
-    rc = records_files_road(
-        run, "classification is", &records_path, 1, rate, [&] { return taxonomy_index_impl(ctx, parent, T, ref_node.data(), n_ref, nullptr); }, &names,
-        [&](uint32_t n_rec, const uint64_t* rec_off) {
-            recs->assign(n_rec, spsp_taxonomy_record{});
-            for (uint32_t r = 0; r < n_rec; ++r) (*recs)[r].length = rec_off[r + 1] - rec_off[r];
-            return SPSP_OK;
-        },
-        [&](const RecordBatch& B) { return taxonomy_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, min_keys, num, den, recs->data() + B.first_record); },
-        [] { return SPSP_OK; }, &t1, extract, mates_path, extract_mates, windows);
-    char *text = nullptr, *report = nullptr; uint64_t len = 0, report_len = 0;
-    if (!rc && windows) {
-        // the rows are the windows': their calls are the split's bins, and the two windowed CSVs take the per-record CSVs' place
-        const size_t n_win = recs->size();
-        std::vector<uint32_t> call(n_win ? n_win : 1, T), keys(call.size(), 0), hit_keys(call.size(), 0), support(call.size(), 0);
-        uint32_t n_bins = 0;
-        rc = spsp_split_bins_taxonomy_host(window_word, recs->data(), n_win, parent, depth, T, call.data(), &n_bins);
-        for (size_t w = 0; w < n_win; ++w) { keys[w] = (*recs)[w].keys; hit_keys[w] = (*recs)[w].hit_keys; support[w] = (*recs)[w].node != kTxNone ? (*recs)[w].clade : 0u; }
-        if (!rc) rc = windows_write(ctx, windows, run.keys.k, call, keys, hit_keys, support, n_bins, names, node_names.data(), "unclassified", precision, out_prefix, t1, chatter);
-        if (!rc && chatter) { say_common_rate(run.L, n_ref); fflush(stdout); }
-        spsp_free(parent); spsp_free(depth); spsp_free(size); spsp_free(blob);
-        return rc;
+    int on_index() override { return taxonomy_index_impl(ctx, parent, T, ref_node.data(), n_ref, nullptr); }
+    int on_records(uint32_t n_rec, const uint64_t* rec_off) override {
+        recs.assign(n_rec, spsp_taxonomy_record{});
+        for (uint32_t r = 0; r < n_rec; ++r) recs[r].length = rec_off[r + 1] - rec_off[r];
+        return SPSP_OK;
     }
-    if (!rc) {
+    int on_batch(const RecordBatch& B) override {
+        return taxonomy_device_impl(ctx, B.mn, B.lo, B.hi, B.key_off, B.n_records, min_keys, num, den, recs.data() + B.first_record);
+    }
+    int keep_flags(const char* what, uint32_t n, uint8_t* keep) override { return spsp_extract_flags_taxonomy_host(what, recs.data(), n, size, T, keep); }
+    int bins(const char* what, uint32_t n, uint32_t* bin, uint32_t* n_bins) override {
+        return spsp_split_bins_taxonomy_host(what, recs.data(), n, parent, depth, T, bin, n_bins);
+    }
+    void window_addends(size_t w, uint32_t* keys, uint32_t* hit_keys, uint32_t* support) override {
+        *keys = recs[w].keys; *hit_keys = recs[w].hit_keys;
+        *support = recs[w].node != kTxNone ? recs[w].clade : 0u;
+    }
+    const char* const* bin_names() override { return node_names.data(); }   // (the names the report prints: the nodes')
+    const char* last_name() override { return "unclassified"; }
+    size_t n_rows() override { return recs.size(); }
+    int write_rows(FilesRun&, const RecordsAsk& ask, const std::vector<std::string>& names, double t1) override {
+        int rc;
         std::vector<const char*> name_ptr(names.size());
         for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
+        char *text = nullptr, *report = nullptr; uint64_t len = 0, report_len = 0;
         // (both texts before either file: nothing is written where a row is refused)
-        if (!(rc = spsp_taxonomy_csv_host(recs->data(), recs->size(), name_ptr.data(), parent, T, node_names.data(), precision, &text, &len)))
-            rc = spsp_taxonomy_report_csv_host(recs->data(), recs->size(), parent, T, node_names.data(), ref_node.data(), n_ref, &report, &report_len);
+        if ((rc = spsp_taxonomy_csv_host(recs.data(), recs.size(), name_ptr.data(), parent, T, node_names.data(), ask.precision, &text, &len))) return rc;
+        if ((rc = spsp_taxonomy_report_csv_host(recs.data(), recs.size(), parent, T, node_names.data(), ref_node.data(), n_ref, &report, &report_len))) {
+            spsp_free(text);
+            return rc;
+        }
+        if ((rc = write_csv_gz(ctx, text, len, ask.out_prefix, "_taxonomy.csv.gz", t1))) { spsp_free(report); return rc; }   // (the text is taken over)
+        return write_csv_gz(ctx, report, report_len, ask.out_prefix, "_taxonomy_report.csv.gz", now_s());
     }
-    if (!rc) {
-        rc = write_csv_gz(ctx, text, len, out_prefix, "_taxonomy.csv.gz", t1);   // (the text is taken over)
-        text = nullptr;
-        const double t2 = now_s();
-        if (!rc) { rc = write_csv_gz(ctx, report, report_len, out_prefix, "_taxonomy_report.csv.gz", t2); report = nullptr; }
-        if (!rc && extract) rc = extract_write(ctx, extract, extract_mates, out_prefix, chatter);
-    }
-    if (!rc && chatter) {
+    void say_rows(FilesRun&, const RecordsAsk& ask) override {
         uint64_t called = 0, at_root = 0;
-        for (const spsp_taxonomy_record& r : *recs) { called += r.node != kTxNone; at_root += r.node == 0u; }
-        printf(mates_path ? "%zu pair(s) against %u reference(s) at %u node(s): %llu classified, %.3g of them at depth 0\n"
-                          : "%zu record(s) against %u reference(s) at %u node(s): %llu classified, %.3g of them at depth 0\n", recs->size(), n_ref, T, (unsigned long long)called,
+        for (const spsp_taxonomy_record& r : recs) { called += r.node != kTxNone; at_root += r.node == 0u; }
+        printf(ask.mates_path ? "%zu pair(s) against %u reference(s) at %u node(s): %llu classified, %.3g of them at depth 0\n"
+                              : "%zu record(s) against %u reference(s) at %u node(s): %llu classified, %.3g of them at depth 0\n", recs.size(), n_ref, T, (unsigned long long)called,
                called ? (double)at_root / (double)called : 0.0);
-        say_common_rate(run.L, n_ref);
-        fflush(stdout);
     }
-    spsp_free(text); spsp_free(report);
-    spsp_free(parent); spsp_free(depth); spsp_free(size); spsp_free(blob);
-    return rc;
-}
+};
 
 }  // namespace spsp
 
@@ -498,33 +487,22 @@ extern "C" int spsp_taxonomy_device(spsp_ctx* ctx, const void* d_q_minimizer, co
                                 num, den, records);
 }
 
-// spsp_taxonomy_files, spsp_taxonomy_files_extract and spsp_taxonomy_files_paired (what == nullptr: no extraction; mates_path ==
-// nullptr: one records file; paired: the entry is the paired one, which mates_path must not be missing from)
-static int taxonomy_files_entry(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
-                                uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
-                                spsp_taxonomy_record** records, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept, uint64_t* bytes_out,
-                                bool paired = false, const char* mates_path = nullptr, bool split = false) {
+// spsp_taxonomy_files, _extract, _paired and _split behind the filling of their ask: the outputs cleared, the front and the
+// driver, the rows handed out
+static int taxonomy_files_entry(const RecordFront& front, const RecordsAsk& ask, spsp_taxonomy_record** records, uint64_t* n_records, uint64_t* n_kept,
+                                uint64_t* bytes_out) {
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
     if (n_kept) *n_kept = 0;
     if (bytes_out) *bytes_out = 0;
-    if (!ctx || !index_paths || !records_path || !lineages_path || !out_prefix || (paired && !mates_path)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
-    int rc;
-    if ((rc = taxonomy_check_args(min_keys, num, den))) return rc;
-    if (what && (rc = split ? spsp_split_word_check_host(what, 1) : spsp_extract_word_check_host(what, 1, 0xffffffffu))) return rc;   // (the word, before any file is read; its node once the tree is)
-    SPSP_HIP(hipSetDevice(ctx->device));
-    std::vector<spsp_taxonomy_record> got;
-    ExtractRun extract, extract_mates;
-    extract.what = extract_mates.what = what; extract.gz = extract_mates.gz = gz; extract.split = extract_mates.split = split;
-    if (mates_path) { extract.tag = "_1"; extract_mates.tag = "_2"; }
-    if ((rc = taxonomy_files(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, &got,
-                             what ? &extract : nullptr, mates_path, what && mates_path ? &extract_mates : nullptr))) return rc;
-    if (n_kept) *n_kept = split ? extract.bins_written : extract.n_kept;
-    if (bytes_out) *bytes_out = extract.out.size() + extract_mates.out.size();
-    if (n_records) *n_records = got.size();
-    if (records && (rc = give_rows(got, records))) return rc;
-    return SPSP_OK;
+    TaxonomyPass pass(front);
+    RecordsOut out;
+    if (const int rc = record_files_entry(front, pass, ask, &out)) return rc;
+    if (n_kept) *n_kept = out.n_kept(ask);
+    if (bytes_out) *bytes_out = out.bytes_out();
+    if (n_records) *n_records = pass.recs.size();
+    const RowsGift gift{(void**)records, pass.recs.data(), pass.recs.size() * sizeof(spsp_taxonomy_record)};
+    return give_rows_all(&gift, 1);
 }
 
 extern "C" int spsp_taxonomy_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
@@ -538,68 +516,54 @@ extern "C" int spsp_taxonomy_files_windows(spsp_ctx* ctx, const char* const* ind
     if (n_windows) *n_windows = 0;
     if (n_records) *n_records = 0;
     if (n_segments) *n_segments = 0;
-    if (!ctx || !index_paths || !records_path || !lineages_path || !out_prefix || !what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    if (n_ref == 0 || n_ref > 65535) { set_error("a classification index takes 1 .. 65535 references (n = %u)", n_ref); return SPSP_ERR_ARG; }
-    int rc;
-    if ((rc = taxonomy_check_args(min_keys, num, den)) || (rc = spsp_windows_word_check_host(what, 1))) return rc;   // (before any file is read)
-    if (window == 0 || window > kWnMaxWidth) {             // (against k: once the sketches' headers are read, in front of the records file)
-        set_error("windows: the width must be k .. %llu (width = %llu)", (unsigned long long)kWnMaxWidth, (unsigned long long)window);
-        return SPSP_ERR_ARG;
-    }
-    SPSP_HIP(hipSetDevice(ctx->device));
-    std::vector<spsp_taxonomy_record> got;
-    WindowsRun run;
-    run.window = window;
-    if ((rc = taxonomy_files(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, &got, nullptr, nullptr,
-                             nullptr, &run, what))) return rc;
-    if (n_windows) *n_windows = got.size();
+    const RecordFront front{ctx, index_paths, lineages_path, true, false, n_ref, 0, min_keys, num, den};
+    TaxonomyPass pass(front);
+    RecordsOut out;
+    if (const int rc = record_files_entry(front, pass, records_ask(&records_path, nullptr, kRmWindows, what, 1, window, precision, out_prefix, chatter, rate), &out)) return rc;
+    const WindowsRun& run = out.windows;
+    if (n_windows) *n_windows = pass.recs.size();
     if (n_records) *n_records = run.mosaic.size();
     if (n_segments) *n_segments = run.segments.size();
-    void* given[3] = {};
-    if ((rows && (rc = give_rows(got, rows))) || (rows && !(given[0] = *rows)) || (first_win && (rc = give_rows(run.first_win, first_win))) ||
-        (first_win && !(given[1] = *first_win)) || (segments && (rc = give_rows(run.segments, segments))) || (segments && !(given[2] = *segments)) ||
-        (mosaic && (rc = give_rows(run.mosaic, mosaic)))) {
-        for (void* g : given) free(g);
-        if (rows) *rows = nullptr;
-        if (first_win) *first_win = nullptr;
-        if (segments) *segments = nullptr;
-        if (mosaic) *mosaic = nullptr;
-        return rc ? rc : (int)SPSP_ERR_NOMEM;
-    }
-    return SPSP_OK;
+    const RowsGift gifts[] = {{(void**)rows, pass.recs.data(), pass.recs.size() * sizeof(spsp_taxonomy_record)},
+                              {(void**)first_win, run.first_win.data(), run.first_win.size() * sizeof(uint32_t)},
+                              {(void**)segments, run.segments.data(), run.segments.size() * sizeof(spsp_segment_row)},
+                              {(void**)mosaic, run.mosaic.data(), run.mosaic.size() * sizeof(spsp_mosaic_row)}};
+    return give_rows_all(gifts, 4);
 }
 
 extern "C" int spsp_taxonomy_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
                                    uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
                                    spsp_taxonomy_record** records, uint64_t* n_records) {
-    return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
-                                nullptr, 1, nullptr, nullptr);
+    return taxonomy_files_entry({ctx, index_paths, lineages_path, true, false, n_ref, 0, min_keys, num, den},
+                                records_ask(&records_path, nullptr, kRmPlain, nullptr, 1, 0, precision, out_prefix, chatter, rate), records, n_records, nullptr, nullptr);
 }
 
 extern "C" int spsp_taxonomy_files_extract(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
                                            uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
                                            spsp_taxonomy_record** records, uint64_t* n_records, const char* what, int gz, uint64_t* n_kept,
                                            uint64_t* bytes_out) {
-    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
-                                what, gz, n_kept, bytes_out);
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }   // (in front of the clearing: DESIGN "What the record file drivers share")
+    return taxonomy_files_entry({ctx, index_paths, lineages_path, true, false, n_ref, 0, min_keys, num, den},
+                                records_ask(&records_path, nullptr, kRmExtract, what, gz, 0, precision, out_prefix, chatter, rate), records, n_records, n_kept, bytes_out);
 }
 
 extern "C" int spsp_taxonomy_files_paired(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
                                           const char* lineages_path, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix,
                                           int chatter, double rate, const char* what, int gz, spsp_taxonomy_record** records, uint64_t* n_records,
                                           uint64_t* n_kept, uint64_t* bytes_out) {
-    return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
-                                what, gz, n_kept, bytes_out, true, mates_path);
+    return taxonomy_files_entry({ctx, index_paths, lineages_path, true, true, n_ref, 0, min_keys, num, den},
+                                records_ask(&records_path, mates_path, what ? kRmExtract : kRmPlain, what, gz, 0, precision, out_prefix, chatter, rate), records, n_records,
+                                n_kept, bytes_out);
 }
 
 extern "C" int spsp_taxonomy_files_split(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* mates_path,
                                          const char* lineages_path, uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix,
                                          int chatter, double rate, const char* what, int gz, spsp_taxonomy_record** records, uint64_t* n_records,
                                          uint64_t* n_bins_written, uint64_t* bytes_out) {
-    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
-    return taxonomy_files_entry(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, records, n_records,
-                                what, gz, n_bins_written, bytes_out, false, mates_path, true);
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }   // (likewise)
+    return taxonomy_files_entry({ctx, index_paths, lineages_path, true, false, n_ref, 0, min_keys, num, den},
+                                records_ask(&records_path, mates_path, kRmSplit, what, gz, 0, precision, out_prefix, chatter, rate), records, n_records, n_bins_written,
+                                bytes_out);
 }
 
 extern "C" int spsp_taxonomy_stage_ms(spsp_ctx* ctx, double* ms) {
