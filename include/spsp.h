@@ -306,6 +306,25 @@ int spsp_fastq_clean_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, 
 int spsp_fastq_clean_packed_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_packed, uint64_t* n_bases,
                                    void** d_rec_off, uint32_t* n_rec);
 
+/* The batch form of the ingest, as spsp_sketch_files runs it, callable on its own (the tests hold it to exact bytes).
+ * slab: HOST bytes laid out as the file pipeline lays a batch out -- file 0 at offset 0, every file on a multiple of 4096,
+ * a FASTA text that is empty or starts with neither '>' nor 0xFF with one '>' forced in front (counted in text_len), '\n' from
+ * a file's end up to the next multiple of 4096 strictly behind it, where the next file starts; n_slab is where the last file's
+ * fill ends.  SPSP_BATCH_FASTQ: the file is read as FASTQ.  SPSP_BATCH_FAILED: the file could not be read, its region holds
+ * '\n' alone and it has no record.  Up to 256 files (more: SPSP_ERR_ARG).  Outputs as spsp_fasta_clean_device (packed != 0:
+ * as spsp_fasta_clean_packed_device), the records of all files in order, and two caller-owned host arrays:
+ * rec_base[n_slab / 4096], the ingest's record base per tile (at a file's first tile: 1 + the file's first record), and
+ * bad[n_files]: ~0, or (the file's first malformed record, numbered in the batch) << 8 | rule (1 header, 2 separator, 3 length,
+ * 4 truncated).  A malformed file keeps its records and fails no call. */
+typedef struct spsp_batch_file {
+    uint64_t off, text_len;
+    uint32_t flags, reserved;
+} spsp_batch_file;
+#define SPSP_BATCH_FASTQ 1u
+#define SPSP_BATCH_FAILED 2u
+int spsp_ingest_batch(spsp_ctx* ctx, const void* slab, uint64_t n_slab, const spsp_batch_file* files, uint32_t n_files, int packed,
+                      void** d_out, uint64_t* n_bases, void** d_rec_off, uint32_t* n_rec, uint32_t* rec_base, uint64_t* bad);
+
 typedef struct spsp_sketch_stats {
     uint64_t read_kmer, selected_kmer_number, selected_superkmer_number, count_maximal_skmer;
     uint64_t seen_kmers_at_reconstruction, seen_superkmers_at_reconstruction;

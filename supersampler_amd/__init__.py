@@ -101,6 +101,14 @@ class NeighbourRow(C.Structure):
 NEIGHBOUR_ROW_DTYPE = np.dtype([("sketch", "<u4"), ("rank", "<u4"), ("neighbour", "<u4"), ("reserved", "<u4"), ("shared", "<u8")])
 NEIGHBOUR_JACCARD, NEIGHBOUR_CONTAINMENT, NEIGHBOUR_CONTAINED = 0, 1, 2
 
+class BatchFile(C.Structure):
+    """spsp_batch_file: one file's place in the slab of spsp_ingest_batch (include/spsp.h)"""
+    _fields_ = [("off", C.c_uint64), ("text_len", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+BATCH_FASTQ, BATCH_FAILED = 1, 2
+
+
 class TreeRow(C.Structure):
     """spsp_tree_row: one merge of a collection's single-linkage tree (include/spsp.h)"""
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("size", C.c_uint32), ("reserved", C.c_uint32), ("shared", C.c_uint64)]
@@ -155,7 +163,7 @@ ABI_SYMBOLS = [
     "spsp_device_count", "spsp_create", "spsp_destroy", "spsp_last_error", "spsp_version", "spsp_free", "spsp_copy_to_host",
     "spsp_stream_create_cus", "spsp_stream_destroy", "spsp_set_cu_count", "spsp_pack_bases_device",
     "spsp_timing_enable", "spsp_timing_sample", "spsp_timing_read", "spsp_threshold_host", "spsp_scan", "spsp_scan_device", "spsp_scan_device_begin", "spsp_scan_device_end", "spsp_scan_tail_stream", "spsp_wait_dense", "spsp_wait_stream", "spsp_scan_hits_device", "spsp_count_superkmers_device", "spsp_compare",
-    "spsp_compare_device", "spsp_slot_bytes", "spsp_partition_keys_device", "spsp_compare_slots_device", "spsp_compare_device_begin", "spsp_compare_slots_device_begin", "spsp_compare_end", "spsp_fasta_clean_host", "spsp_fasta_clean_device", "spsp_fasta_clean_packed_device", "spsp_fastq_clean_device", "spsp_fastq_clean_packed_device", "spsp_sketch_text", "spsp_sketch_build_host", "spsp_sketch_parse_host", "spsp_sketch_decode_device", "spsp_sketch_keys_device", "spsp_sketch_keys_device_begin", "spsp_sketch_keys_device_end", "spsp_sketch_keys_big_genomes", "spsp_scan_output_wait", "spsp_compare_keys_unordered", "spsp_compare_forget", "spsp_sketch_chain_host",
+    "spsp_compare_device", "spsp_slot_bytes", "spsp_partition_keys_device", "spsp_compare_slots_device", "spsp_compare_device_begin", "spsp_compare_slots_device_begin", "spsp_compare_end", "spsp_fasta_clean_host", "spsp_fasta_clean_device", "spsp_fasta_clean_packed_device", "spsp_fastq_clean_device", "spsp_fastq_clean_packed_device", "spsp_ingest_batch", "spsp_sketch_text", "spsp_sketch_build_host", "spsp_sketch_parse_host", "spsp_sketch_decode_device", "spsp_sketch_keys_device", "spsp_sketch_keys_device_begin", "spsp_sketch_keys_device_end", "spsp_sketch_keys_big_genomes", "spsp_scan_output_wait", "spsp_compare_keys_unordered", "spsp_compare_forget", "spsp_sketch_chain_host",
     "spsp_csv_host", "spsp_csv_cells_host", "spsp_csv_cells_gz_host", "spsp_sort_csv_host", "spsp_read_file_host", "spsp_write_gz_host", "spsp_sketch_file", "spsp_compare_files", "spsp_compare_files_chatty", "spsp_stage_times_read", "spsp_measure_hbm_device", "spsp_sketch_files", "spsp_sketch_files_multi", "spsp_sketch_files_release", "spsp_compare_files_multi", "spsp_matrix_cells_device", "spsp_matrix_add_cells_device", "spsp_compare_cells_device", "spsp_compare_slots_cells_device",
     "spsp_keys_downsample_device", "spsp_sketch_header_host", "spsp_sketch_downsample_host", "spsp_compare_files_rate", "spsp_compare_files_multi_rate",
     "spsp_gather_device", "spsp_gather_csv_host", "spsp_gather_files",
@@ -245,6 +253,8 @@ def lib():
     L.spsp_fastq_clean_device.argtypes = [vp, vp, u64, P(vp), P(u64), P(vp), P(u32)]
     L.spsp_fastq_clean_packed_device.restype = i32
     L.spsp_fastq_clean_packed_device.argtypes = [vp, vp, u64, P(vp), P(u64), P(vp), P(u32)]
+    L.spsp_ingest_batch.restype = i32
+    L.spsp_ingest_batch.argtypes = [vp, vp, u64, P(BatchFile), u32, i32, P(vp), P(u64), P(vp), P(u32), vp, vp]
     L.spsp_sketch_text.restype = i32
     L.spsp_sketch_text.argtypes = [vp, P(Params), dbl, cp, u64, P(vp), P(u64), P(SketchStats)]
     L.spsp_sketch_build_host.restype = i32
@@ -1527,6 +1537,18 @@ class Context:
         b, o, nb, nr = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint32()
         _check(lib().spsp_fastq_clean_packed_device(self._h, d_text, n_text, C.byref(b), C.byref(nb), C.byref(o), C.byref(nr)))
         return b.value, nb.value, o.value, nr.value
+
+    def clean_batch(self, slab, files, packed=False):
+        """the batch form of the ingest: slab = host bytes laid out as the file pipeline lays a batch out, files = (offset,
+        text length, BATCH_* flags) per file -> (d_bases or d_packed, n_bases, d_rec_off, n_rec, rec_base np.uint32 per
+        tile, bad np.uint64 per file: ~0 or (first malformed record in the batch) << 8 | rule)"""
+        arr = (BatchFile * max(1, len(files)))(*[BatchFile(o, n, fl, 0) for o, n, fl in files])
+        rec_base = np.zeros(len(slab) // 4096 + 1, dtype=np.uint32)
+        bad = np.zeros(max(1, len(files)), dtype=np.uint64)
+        b, o, nb, nr = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint32()
+        _check(lib().spsp_ingest_batch(self._h, bytes(slab), len(slab), arr, len(files), 1 if packed else 0, C.byref(b), C.byref(nb),
+                                       C.byref(o), C.byref(nr), rec_base.ctypes.data, bad.ctypes.data))
+        return b.value, nb.value, o.value, nr.value, rec_base[:len(slab) // 4096], bad[:len(files)]
 
     def sketch_text(self, text, k=31, m=11, s=1000.0, abundance=1, flags=SPSP_SCAN_DEFAULT):
         """FASTA or FASTQ bytes (FASTQ: the first byte is '@') -> (payload, stats) with ingest, scan and gather on the GPU."""

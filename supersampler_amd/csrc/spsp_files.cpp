@@ -543,29 +543,14 @@ private:
             std::vector<uint64_t> bad;
             spsp::FastqLayout fq;
             if (std::any_of(s.files.begin(), s.files.end(), [](const PipeFile& f) { return !f.rc && f.fastq; })) {
-                tinfo.assign((size_t)n_tiles, 0u);
                 bad.assign(s.files.size(), ~0ull);
+                std::vector<spsp::BatchFile> described(s.files.size());
                 for (size_t j = 0; j < s.files.size(); ++j) {
                     const PipeFile& f = s.files[j];
-                    if (!f.laid) continue;
-                    uint64_t stop = s.total;                          // the next laid file's place
-                    for (size_t q = j + 1; q < s.files.size(); ++q) if (s.files[q].laid) { stop = s.files[q].off; break; }
-                    const uint64_t t_a = f.off / kSlabAlign, t_b = stop / kSlabAlign;
-                    const uint32_t id = (uint32_t)j << spsp::kTiFileShift;
-                    // a file that failed to read is all newlines by now: described as FASTQ without content, it holds no record
-                    const bool as_fq = f.rc || f.fastq;
-                    const uint64_t e = f.rc ? 0 : f.fq_end;
-                    for (uint64_t t = t_a; t < t_b; ++t) {
-                        uint32_t w = id | (t == t_a ? spsp::kTiStart : 0u);
-                        if (as_fq) {
-                            const uint64_t r0 = (t - t_a) * kSlabAlign;
-                            w |= spsp::kTiFastq | (f.fq_blank ? spsp::kTiBlankTail : 0u) |
-                                 (uint32_t)(e <= r0 ? 0 : std::min<uint64_t>(kSlabAlign, e - r0)) |
-                                 (e > r0 && e <= r0 + kSlabAlign ? spsp::kTiEnd : 0u);
-                        }
-                        tinfo[(size_t)t] = w;
-                    }
+                    spsp::BatchFile& b = described[j];
+                    b.off = f.off; b.laid = f.laid; b.failed = f.rc != SPSP_OK; b.fastq = f.fastq; b.fq_end = f.fq_end; b.fq_blank = f.fq_blank;
                 }
+                spsp::batch_tile_table(described.data(), described.size(), s.total, &tinfo);
                 fq.tile_info = tinfo.data(); fq.n_files = (uint32_t)s.files.size(); fq.bad = bad.data();
             }
             if ((r = spsp::clean_device_impl(ctx, ctx->i_text.as<uint8_t>(), s.total, &d_bases, &n_bases, &d_off, &n_rec, packed, fq.tile_info ? &fq : nullptr))) return r;

@@ -793,6 +793,31 @@ void fastq_tail(const uint8_t* text, uint64_t n, uint64_t* content_end, bool* bl
     *content_end = e;
     *blank_tail = nl && (uint64_t)(nl - text) + 1 < n;
 }
+void batch_tile_table(const BatchFile* files, size_t n_files, uint64_t total, std::vector<uint32_t>* tinfo) {
+    const uint64_t n_tiles = (total + kCleanTile - 1) / kCleanTile;
+    tinfo->assign((size_t)n_tiles, 0u);
+    for (size_t j = 0; j < n_files; ++j) {
+        const BatchFile& f = files[j];
+        if (!f.laid) continue;
+        uint64_t stop = total;                            // the next laid file's place
+        for (size_t q = j + 1; q < n_files; ++q) if (files[q].laid) { stop = files[q].off; break; }
+        const uint64_t t_a = f.off / kCleanTile, t_b = stop / kCleanTile;
+        const uint32_t id = (uint32_t)j << kTiFileShift;
+        // a file that failed to read is all newlines by now: described as FASTQ without content, it holds no record
+        const bool as_fq = f.failed || f.fastq;
+        const uint64_t e = f.failed ? 0 : f.fq_end;
+        for (uint64_t t = t_a; t < t_b; ++t) {
+            uint32_t w = id | (t == t_a ? kTiStart : 0u);
+            if (as_fq) {
+                const uint64_t r0 = (t - t_a) * kCleanTile;
+                w |= kTiFastq | (f.fq_blank ? kTiBlankTail : 0u) |
+                     (uint32_t)(e <= r0 ? 0 : std::min<uint64_t>(kCleanTile, e - r0)) |
+                     (e > r0 && e <= r0 + kCleanTile ? kTiEnd : 0u);
+            }
+            (*tinfo)[(size_t)t] = w;
+        }
+    }
+}
 const char* fastq_rule_name(uint32_t rule) {
     switch (rule) {
         case kFqBadHeader: return "its header line does not start with '@'";
@@ -1033,6 +1058,45 @@ int spsp_fastq_clean_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, 
 int spsp_fastq_clean_packed_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, void** d_packed, uint64_t* n_bases,
                                    void** d_rec_off, uint32_t* n_rec) {
     return fastq_clean_entry(ctx, d_text, n_text, d_packed, n_bases, d_rec_off, n_rec, true);
+}
+
+// A batch of files as the file pipeline ingests it, from a host slab that is laid out already: fastq_tail per FASTQ file, the
+// shared table builder, one upload, one ingest in the described (tile table) form whatever the files' formats
+int spsp_ingest_batch(spsp_ctx* ctx, const void* slab, uint64_t n_slab, const spsp_batch_file* files, uint32_t n_files, int packed,
+                      void** d_out, uint64_t* n_bases, void** d_rec_off, uint32_t* n_rec, uint32_t* rec_base, uint64_t* bad) {
+    if (!ctx || !slab || !files || !d_out || !n_bases || !d_rec_off || !n_rec || !rec_base || !bad) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_files > 256) { set_error("too many files in one ingest"); return SPSP_ERR_ARG; }
+    if (!n_files || !n_slab || n_slab % kCleanTile) { set_error("a batch is one file at least and whole 4 KiB tiles"); return SPSP_ERR_ARG; }
+    const uint8_t* text = (const uint8_t*)slab;
+    std::vector<BatchFile> described(n_files);
+    for (uint32_t j = 0; j < n_files; ++j) {
+        const spsp_batch_file& f = files[j];
+        const uint64_t stop = j + 1 < n_files ? files[j + 1].off : n_slab;
+        // the pipeline's layout: the first file at 0, every file on a tile, the next one on the first tile strictly behind its end
+        if ((j == 0 && f.off != 0) || f.off % kCleanTile || f.off >= n_slab || f.text_len >= n_slab - f.off ||
+            stop != (f.off + f.text_len + kCleanTile) / kCleanTile * kCleanTile) {
+            set_error("file %u is not laid out as the file pipeline lays a batch out", j);
+            return SPSP_ERR_ARG;
+        }
+        BatchFile& b = described[j];
+        b.off = f.off; b.laid = true; b.failed = (f.flags & SPSP_BATCH_FAILED) != 0; b.fastq = (f.flags & SPSP_BATCH_FASTQ) != 0;
+        if (b.fastq && !b.failed) fastq_tail(text + f.off, f.text_len, &b.fq_end, &b.fq_blank);
+    }
+    std::vector<uint32_t> tinfo;
+    batch_tile_table(described.data(), described.size(), n_slab, &tinfo);
+    SPSP_HIP(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = ctx->i_text.reserve((size_t)n_slab + 64))) return rc;
+    SPSP_HIP(hipMemcpyAsync(ctx->i_text.p, slab, (size_t)n_slab, hipMemcpyHostToDevice, ctx->stream));
+    FastqLayout fq;
+    fq.tile_info = tinfo.data(); fq.n_files = n_files; fq.bad = bad;
+    for (uint32_t j = 0; j < n_files; ++j) bad[j] = ~0ull;
+    uint8_t* b = nullptr; uint64_t* o = nullptr;
+    if ((rc = clean_device_impl(ctx, ctx->i_text.as<uint8_t>(), n_slab, &b, n_bases, &o, n_rec, packed != 0, &fq))) return rc;
+    SPSP_HIP(hipMemcpyAsync(rec_base, ctx->i_recbase.p, tinfo.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SPSP_HIP(hipStreamSynchronize(ctx->stream));
+    *d_out = b; *d_rec_off = o;
+    return SPSP_OK;
 }
 
 // FASTA or FASTQ text (host, gunzipped) -> sketch payload with ingest, scan and super-k-mer gather on the GPU:

@@ -959,6 +959,17 @@ struct FastqLayout {
 };
 // the content end of a FASTQ text (behind its last byte that is neither '\n' nor '\r') and whether a blank line follows it
 void fastq_tail(const uint8_t* text, uint64_t n, uint64_t* content_end, bool* blank_tail);
+// One file of a batch, as the table builder needs it: its place in the slab (a multiple of the 4 KiB tile), whether it has a
+// place at all, whether it failed behind the layout (its region is all newlines), its format and, for FASTQ, what fastq_tail says
+struct BatchFile {
+    uint64_t off = 0;
+    bool laid = false, failed = false, fastq = false;
+    uint64_t fq_end = 0;
+    bool fq_blank = false;
+};
+// the tile words (kTi*) of a batch of `total` bytes: tinfo gets one word per tile; files are in slab order, bits 16..23 of a
+// file's tiles hold its index in `files`
+void batch_tile_table(const BatchFile* files, size_t n_files, uint64_t total, std::vector<uint32_t>* tinfo);
 const char* fastq_rule_name(uint32_t rule);
 int clean_device_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint8_t** d_bases, uint64_t* n_bases,
                       uint64_t** d_rec_off, uint32_t* n_rec, bool pack = false, const FastqLayout* fq = nullptr);
