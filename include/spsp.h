@@ -348,6 +348,24 @@ int spsp_sketch_build_host(const spsp_params* p, double rate, const uint8_t* bas
 int spsp_sketch_text(spsp_ctx* ctx, const spsp_params* p, double rate, const char* text, uint64_t n_text,
                      uint8_t** payload, uint64_t* payload_len, spsp_sketch_stats* stats);
 
+/* The sketch builder on the device (spsp_build.hip) from host buffers, as spsp_scan is to spsp_scan_device: what
+ * spsp_sketch_build_host computes, for n_files files at once, whatever SPSP_BUILD or the number of k-mer places say.  The
+ * stream is as the scan writes it (`rec` counts over all files' records, `start` and `len` inside the record), file f's
+ * super-k-mers are sk[file_sk[f] .. file_sk[f + 1]).  packed != 0: the bases are first brought into the 2-bit words the
+ * ingest writes, and the builder reads those.  *payloads: every file's whole payload (header line with that file's selected
+ * k-mer number, then its buckets), back to back, file f at payload_off[f] .. payload_off[f + 1]; spsp_free() it.  counters:
+ * four per file -- actual_minimizer_number, seen_kmers_at_reconstruction, seen_superkmers_at_reconstruction,
+ * seen_max_superkmers_at_reconstruction.  n_sk == 0: header lines only.
+ * SPSP_ERR_ARG, before anything is launched and with nothing written: a NULL argument; parameters out of range; n_files == 0;
+ * rec_off that does not start at 0 or decreases; file_sk that does not start at 0, decreases or does not end at n_sk; a
+ * super-k-mer outside its record or shorter than k (spsp_sketch_build_host's message), with a minimizer >= 4^m, or with
+ * rev > 1.  The minimizer is NOT checked to be the k-mers' minimum, nor to occur in them: a k-mer that does not hold it is
+ * indexed with the place 255, as the reference's find() leaves it.  SPSP_ERR_OVERFLOW (the builder's own, passed through): more than 2^25 super-k-mers, 2^31 k-mer
+ * places or 4 GiB of payloads in one call. */
+int spsp_sketch_build_device(spsp_ctx* ctx, const spsp_params* p, double rate, const uint8_t* bases, const uint64_t* rec_off,
+                             uint32_t n_rec, const spsp_superkmer* sk, uint64_t n_sk, const uint32_t* file_sk, uint32_t n_files,
+                             int packed, uint8_t** payloads, uint64_t* payload_off, uint64_t* counters);
+
 /* Header + bucket reader of the comparator (Comparator.cpp:23-37, 78-92,
  * 186-260; strDecompressor utils.cpp:71-111): payload -> sorted distinct
  * (minimizer, canonical k-mer) keys. Arrays are spsp_free()d one by one. */

@@ -163,7 +163,7 @@ ABI_SYMBOLS = [
     "spsp_device_count", "spsp_create", "spsp_destroy", "spsp_last_error", "spsp_version", "spsp_free", "spsp_copy_to_host",
     "spsp_stream_create_cus", "spsp_stream_destroy", "spsp_set_cu_count", "spsp_pack_bases_device",
     "spsp_timing_enable", "spsp_timing_sample", "spsp_timing_read", "spsp_threshold_host", "spsp_scan", "spsp_scan_device", "spsp_scan_device_begin", "spsp_scan_device_end", "spsp_scan_tail_stream", "spsp_wait_dense", "spsp_wait_stream", "spsp_scan_hits_device", "spsp_count_superkmers_device", "spsp_compare",
-    "spsp_compare_device", "spsp_slot_bytes", "spsp_partition_keys_device", "spsp_compare_slots_device", "spsp_compare_device_begin", "spsp_compare_slots_device_begin", "spsp_compare_end", "spsp_fasta_clean_host", "spsp_fasta_clean_device", "spsp_fasta_clean_packed_device", "spsp_fastq_clean_device", "spsp_fastq_clean_packed_device", "spsp_ingest_batch", "spsp_sketch_text", "spsp_sketch_build_host", "spsp_sketch_parse_host", "spsp_sketch_decode_device", "spsp_sketch_keys_device", "spsp_sketch_keys_device_begin", "spsp_sketch_keys_device_end", "spsp_sketch_keys_big_genomes", "spsp_scan_output_wait", "spsp_compare_keys_unordered", "spsp_compare_forget", "spsp_sketch_chain_host",
+    "spsp_compare_device", "spsp_slot_bytes", "spsp_partition_keys_device", "spsp_compare_slots_device", "spsp_compare_device_begin", "spsp_compare_slots_device_begin", "spsp_compare_end", "spsp_fasta_clean_host", "spsp_fasta_clean_device", "spsp_fasta_clean_packed_device", "spsp_fastq_clean_device", "spsp_fastq_clean_packed_device", "spsp_ingest_batch", "spsp_sketch_text", "spsp_sketch_build_host", "spsp_sketch_build_device", "spsp_sketch_parse_host", "spsp_sketch_decode_device", "spsp_sketch_keys_device", "spsp_sketch_keys_device_begin", "spsp_sketch_keys_device_end", "spsp_sketch_keys_big_genomes", "spsp_scan_output_wait", "spsp_compare_keys_unordered", "spsp_compare_forget", "spsp_sketch_chain_host",
     "spsp_csv_host", "spsp_csv_cells_host", "spsp_csv_cells_gz_host", "spsp_sort_csv_host", "spsp_read_file_host", "spsp_write_gz_host", "spsp_sketch_file", "spsp_compare_files", "spsp_compare_files_chatty", "spsp_stage_times_read", "spsp_measure_hbm_device", "spsp_sketch_files", "spsp_sketch_files_multi", "spsp_sketch_files_release", "spsp_compare_files_multi", "spsp_matrix_cells_device", "spsp_matrix_add_cells_device", "spsp_compare_cells_device", "spsp_compare_slots_cells_device",
     "spsp_keys_downsample_device", "spsp_sketch_header_host", "spsp_sketch_downsample_host", "spsp_compare_files_rate", "spsp_compare_files_multi_rate",
     "spsp_gather_device", "spsp_gather_csv_host", "spsp_gather_files",
@@ -259,6 +259,8 @@ def lib():
     L.spsp_sketch_text.argtypes = [vp, P(Params), dbl, cp, u64, P(vp), P(u64), P(SketchStats)]
     L.spsp_sketch_build_host.restype = i32
     L.spsp_sketch_build_host.argtypes = [P(Params), dbl, vp, vp, u32, vp, u64, P(vp), P(u64), P(SketchStats)]
+    L.spsp_sketch_build_device.restype = i32
+    L.spsp_sketch_build_device.argtypes = [vp, P(Params), dbl, vp, vp, u32, vp, u64, vp, u32, i32, P(vp), vp, vp]
     L.spsp_sketch_parse_host.restype = i32
     L.spsp_sketch_parse_host.argtypes = [cp, u64, P(u32), P(u32), P(vp), P(vp), P(vp), P(u64)]
     L.spsp_sketch_chain_host.restype = i32
@@ -1556,6 +1558,26 @@ class Context:
         out, n, st = C.c_void_p(), C.c_uint64(), SketchStats()
         _check(lib().spsp_sketch_text(self._h, C.byref(p), float(s), text, len(text), C.byref(out), C.byref(n), C.byref(st)))
         return _take(out, n.value), {f: getattr(st, f) for f, _ in SketchStats._fields_}
+
+    def sketch_build_device(self, params, rate, bases, rec_off, superkmers, file_sk, packed=False):
+        """super-k-mer stream of len(file_sk) - 1 files (file f: superkmers[file_sk[f]:file_sk[f + 1]], `rec` counting over all
+        records) -> ([payload per file], [counter dict per file]) by the builder on the device (spsp_sketch_build_device)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        sk = np.ascontiguousarray(superkmers, dtype=SUPERKMER_DTYPE)
+        fsk = np.ascontiguousarray(file_sk, dtype=np.uint32)
+        n_files = len(fsk) - 1
+        out = C.c_void_p()
+        off = np.zeros(n_files + 1, dtype=np.uint64)
+        cnt = np.zeros(4 * n_files, dtype=np.uint64)
+        _check(lib().spsp_sketch_build_device(self._h, C.byref(params), float(rate), bases.ctypes.data, rec_off.ctypes.data, len(rec_off) - 1,
+                                              sk.ctypes.data, len(sk), fsk.ctypes.data, n_files, 1 if packed else 0, C.byref(out),
+                                              off.ctypes.data, cnt.ctypes.data))
+        data = _take(out, int(off[-1]))
+        names = ("actual_minimizer_number", "seen_kmers_at_reconstruction", "seen_superkmers_at_reconstruction",
+                 "seen_max_superkmers_at_reconstruction")
+        return ([data[int(off[f]):int(off[f + 1])] for f in range(n_files)],
+                [dict(zip(names, (int(x) for x in cnt[4 * f: 4 * f + 4]))) for f in range(n_files)])
 
     def sketch_fasta(self, text, k=31, m=11, s=1000.0, abundance=1, flags=SPSP_SCAN_DEFAULT):
         """FASTA bytes -> (payload, stats): clean -> GPU scan -> sketch builder."""

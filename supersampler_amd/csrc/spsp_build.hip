@@ -528,3 +528,79 @@ int sketch_build_device_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t*
 }
 
 }  // namespace spsp
+
+using namespace spsp;
+
+extern "C" {
+
+// The builder from host buffers, as spsp_scan is to spsp_scan_device: everything the kernels index with is checked here, in front
+// of the first launch -- the stream is the caller's, not a scan's.
+int spsp_sketch_build_device(spsp_ctx* ctx, const spsp_params* p, double rate, const uint8_t* bases, const uint64_t* rec_off, uint32_t n_rec,
+                             const spsp_superkmer* sk, uint64_t n_sk, const uint32_t* file_sk, uint32_t n_files, int packed, uint8_t** payloads,
+                             uint64_t* payload_off, uint64_t* counters) {
+    if (!ctx || !payloads || !payload_off || !counters) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!file_sk || (n_rec && !rec_off) || (n_sk && (!sk || !bases))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_files == 0) { set_error("n_files must be at least 1"); return SPSP_ERR_ARG; }
+    if (n_rec && rec_off[0] != 0) { set_error("rec_off[0] must be 0"); return SPSP_ERR_ARG; }
+    for (uint32_t r = 0; r < n_rec; ++r)
+        if (rec_off[r + 1] < rec_off[r]) { set_error("rec_off must be non-decreasing"); return SPSP_ERR_ARG; }
+    if (file_sk[0] != 0 || (uint64_t)file_sk[n_files] != n_sk) { set_error("file_sk must start at 0 and end at n_sk"); return SPSP_ERR_ARG; }
+    for (uint32_t f = 0; f < n_files; ++f)
+        if (file_sk[f + 1] < file_sk[f]) { set_error("file_sk must be non-decreasing"); return SPSP_ERR_ARG; }
+    const uint32_t mn_end = p->m >= 16 ? 0xffffffffu : (1u << (2 * p->m)) - 1u;      // the largest m-mer
+    for (uint64_t i = 0; i < n_sk; ++i) {
+        const spsp_superkmer& e = sk[i];
+        const uint64_t rlen = e.rec < n_rec ? rec_off[e.rec + 1] - rec_off[e.rec] : 0;
+        if (e.rec >= n_rec || e.len < p->k || e.start > rlen || e.len > rlen - e.start) {
+            set_error("super-k-mer %llu is outside its record", (unsigned long long)i);
+            return SPSP_ERR_ARG;
+        }
+        if (e.minimizer > mn_end) { set_error("super-k-mer %llu: its minimizer has more than m bases", (unsigned long long)i); return SPSP_ERR_ARG; }
+        if (e.rev > 1) { set_error("super-k-mer %llu: rev must be 0 or 1", (unsigned long long)i); return SPSP_ERR_ARG; }
+    }
+    std::vector<uint64_t> sel(n_files, 0);                                // selected_kmer_number per file, for its header line
+    for (uint32_t f = 0; f < n_files; ++f)
+        for (uint32_t i = file_sk[f]; i < file_sk[f + 1]; ++i) sel[f] += sk[i].len - p->k + 1;
+    std::vector<std::string> bodies(n_files);
+    std::vector<uint64_t> fst((size_t)n_files * 4, 0);
+    if (n_sk) {
+        const uint64_t n_bases = rec_off[n_rec];
+        SPSP_HIP(hipSetDevice(ctx->device));
+        if ((rc = ctx->bases.reserve((size_t)n_bases + 64)) || (rc = ctx->rec_off.reserve((size_t)(n_rec + 1) * 8)) ||
+            (rc = ctx->bl_sk.reserve((size_t)n_sk * sizeof(spsp_superkmer)))) return rc;
+        SPSP_HIP(hipMemcpyAsync(ctx->bases.p, bases, (size_t)n_bases, hipMemcpyHostToDevice, ctx->stream));
+        SPSP_HIP(hipMemcpyAsync(ctx->rec_off.p, rec_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        SPSP_HIP(hipMemcpyAsync(ctx->bl_sk.p, sk, (size_t)n_sk * sizeof(spsp_superkmer), hipMemcpyHostToDevice, ctx->stream));
+        const uint8_t* d_bases = ctx->bases.as<uint8_t>();
+        if (packed) {
+            // the ingest's form: a k-mer that ends on the last base starts in word (n_bases - k) / 16 and k_bld_places reads that
+            // word and four more, the last of them word (n_bases - 1) / 16 + 4 at most -- inside the 64 zero words behind the
+            // bases' own that pack_bases_impl and the ingest (clean_device_impl) both reserve
+            uint32_t* d_packed = nullptr;
+            if ((rc = pack_bases_impl(ctx, d_bases, n_bases, &d_packed))) return rc;
+            d_bases = reinterpret_cast<const uint8_t*>(d_packed);
+        }
+        if ((rc = sketch_build_device_impl(ctx, p, d_bases, packed != 0, ctx->rec_off.as<uint64_t>(), ctx->bl_sk.as<spsp_superkmer>(), n_sk, file_sk, n_files,
+                                           &bodies, &fst))) return rc;
+    }
+    std::string all;
+    std::vector<uint64_t> off(n_files + 1, 0);
+    for (uint32_t f = 0; f < n_files; ++f) {
+        std::string head;
+        sketch_header_line(p->k, p->m, sel[f], rate, head);
+        all += head;
+        all += bodies[f];
+        off[f + 1] = all.size();
+    }
+    uint8_t* out = (uint8_t*)malloc(all.size() + 1);
+    if (!out) { set_error("out of host memory"); return SPSP_ERR_NOMEM; }
+    memcpy(out, all.data(), all.size());
+    *payloads = out;
+    memcpy(payload_off, off.data(), off.size() * 8);
+    memcpy(counters, fst.data(), fst.size() * 8);
+    return SPSP_OK;
+}
+
+}  // extern "C"

@@ -263,7 +263,7 @@ struct spsp_ctx {
     uint32_t filter_skipped = 0;
     double filter_ratio = 1.0;   // records dealt into parts per owned key in the last filtered comparison (sizes the next one's parts)
     spsp::DevBuf x_cnt, x_off, x_begin, x_end, x_tot;   // key-partitioned exchange (spsp_compare.hip)
-    spsp::DevBuf bl_hist, bl_keys, bl_vals, bl_meta, bl_lo, bl_hi, bl_pmin, bl_pb, bl_slot, bl_first, bl_codes, bl_text, bl_outs, bl_out;   // sketch builder on the device (spsp_build.hip)
+    spsp::DevBuf bl_hist, bl_keys, bl_vals, bl_meta, bl_lo, bl_hi, bl_pmin, bl_pb, bl_slot, bl_first, bl_codes, bl_text, bl_outs, bl_out, bl_sk;   // sketch builder on the device (spsp_build.hip; bl_sk: the stream spsp_sketch_build_device uploads)
     spsp::DevBuf dc_text, dc_desc, dc_mn, dc_lo, dc_hi, dc_meta, dc_walk;   // bulk sketch decode (spsp_decode.hip)
     spsp::DevBuf a_cnt, a_off, a_mn, a_lo, a_hi, a_slot, a_slot_of, a_flags, a_seg;   // -a abundance pass (spsp_abund.hip)
     // genomes / sketches beyond the per-segment LDS forms (spsp_bigkeys.hip): output slices, the open-addressing table in HBM
