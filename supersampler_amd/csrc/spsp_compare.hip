@@ -187,19 +187,11 @@ __global__ __launch_bounds__(kRowThreads) void k_assign_rows(const uint64_t* __r
         if (sl < cap && table[sl] != 0) occ |= 1u << u;
     }
     const uint32_t cnt = __popc(occ);
-    uint32_t x = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) wave_sum[wid] = x;
-    __syncthreads();
-    uint32_t pre = 0, total = 0;
-    for (uint32_t w = 0; w < kRowThreads / 64; ++w) { if (w < wid) pre += wave_sum[w]; total += wave_sum[w]; }
+    uint32_t total;
+    const uint32_t pre = block_prefix_excl<kRowThreads / 64>(cnt, lane, wid, wave_sum, total);
     if (t == 0) s_base = total ? atomicAdd(n_rows, total) : 0u;
     __syncthreads();
-    uint32_t id = s_base + pre + x - cnt;
+    uint32_t id = s_base + pre;
 #pragma unroll
     for (int u = 0; u < kRowSlots; ++u)
         if (occ & (1u << u)) rowid[base_slot + (uint64_t)u * kRowThreads + t] = id++;
@@ -308,19 +300,11 @@ __global__ __launch_bounds__(kRowThreads) void k_assign_ranges(const uint32_t* _
         c[u] = sl < cap ? cnt[sl] : 0u;
         sum += c[u] ? list_u16(c[u]) : 0u;      // list = length word + ids, padded to whole 16-byte words
     }
-    uint32_t x = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) wave_sum[wid] = x;
-    __syncthreads();
-    uint32_t pre = 0, all = 0;
-    for (uint32_t w = 0; w < kRowThreads / 64; ++w) { if (w < wid) pre += wave_sum[w]; all += wave_sum[w]; }
+    uint32_t all;
+    const uint32_t pre = block_prefix_excl<kRowThreads / 64>(sum, lane, wid, wave_sum, all);
     if (t == 0) s_base = all ? atomicAdd(total, all) : 0u;
     __syncthreads();
-    uint32_t at = s_base + pre + x - sum;
+    uint32_t at = s_base + pre;
 #pragma unroll
     for (int u = 0; u < kRowSlots; ++u) {
         if (!c[u]) continue;
@@ -507,9 +491,7 @@ __global__ __launch_bounds__(T) void k_accumulate_sparse(const uint32_t* __restr
             // to by a binary search over the lanes' prefix (shuffles).
             if (__any(is_long)) {
                 const uint32_t nwp = is_long ? (len >> 3) : 0u;
-                uint32_t incl = nwp;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(incl, d); if (lane >= (uint32_t)d) incl += y; }
+                const uint32_t incl = wave_prefix_incl(nwp, lane);
                 const uint32_t excl = incl - nwp, total = __shfl(incl, 63);
                 auto locate = [&](uint32_t gw, uint32_t& r_, uint32_t& ln_, uint32_t& wi_) {
                     uint32_t lo = 0;
@@ -765,14 +747,7 @@ __global__ __launch_bounds__(1024) void k_row_order(const unsigned long long* __
     uint32_t c[8], sum = 0;
 #pragma unroll
     for (int u = 0; u < 8; ++u) { c[u] = hist[t * 8 + u]; sum += c[u]; }
-    uint32_t x = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d); if (lane >= (uint32_t)d) x += y; }
-    if (lane == 63) wave_sum[wid] = x;
-    __syncthreads();
-    uint32_t pre = 0;
-    for (uint32_t w = 0; w < wid; ++w) pre += wave_sum[w];
-    uint32_t at = pre + x - sum;
+    uint32_t at = block_prefix_excl<16>(sum, lane, wid, wave_sum);
 #pragma unroll
     for (int u = 0; u < 8; ++u) { hist[t * 8 + u] = at; at += c[u]; }
     __syncthreads();
@@ -966,9 +941,7 @@ __global__ __launch_bounds__(kScatThreads, 4) void k_parts_scatter_tiles(Keys K,
             const uint64_t j0 = sk_off[j], len = sk_off[j + 1] - j0, s_ = (info >> 32) & 0xffffu, T_ = info >> 48;
             a = (uint32_t)(j0 + s_ * len / T_); z = (uint32_t)(j0 + (s_ + 1) * len / T_);
         }
-        uint32_t incl = z - a;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(incl, d); if (lane >= (uint32_t)d) incl += y; }
+        const uint32_t incl = wave_prefix_incl(z - a, lane);
         s_a[t] = a; s_pre[t] = incl - (z - a);
         if (t == 63) s_pre[64] = incl;
     }
@@ -1223,7 +1196,7 @@ __global__ __launch_bounds__(kRowThreads) void k_spill_ranges(const uint32_t* __
                                                              uint32_t* __restrict__ flags) {
     if (flags[kCfSpillRecs] > room) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) flags[kCfPartOverflow] = 0;           // the overflowed parts are taken care of: the row sums may run
-    __shared__ uint32_t wave_sum[kRowThreads / 64], wave_cols[kRowThreads / 64];
+    __shared__ Sum2 s_wave[kRowThreads / 64];              // x: the lists' words, y: the columns
     __shared__ uint32_t s_base, s_cols;
     const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
     const uint64_t base_slot = ((uint64_t)blockIdx.x * kRowThreads + t) * kRowSlots;   // 16 consecutive slots per lane
@@ -1236,22 +1209,12 @@ __global__ __launch_bounds__(kRowThreads) void k_spill_ranges(const uint32_t* __
         if (c[u] >= t_bits) ++cols;
         else if (c[u] >= 2) sum += list_u16(c[u]);       // (a key of one holder takes part in no pair: no list)
     }
-    uint32_t x = sum, y = cols;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t x2 = __shfl_up(x, d), y2 = __shfl_up(y, d);
-        if (lane >= (uint32_t)d) { x += x2; y += y2; }
-    }
-    if (lane == 63) { wave_sum[wid] = x; wave_cols[wid] = y; }
-    __syncthreads();
-    uint32_t pre = 0, all = 0, pre_c = 0, all_c = 0;
-    for (uint32_t w = 0; w < kRowThreads / 64; ++w) {
-        if (w < wid) { pre += wave_sum[w]; pre_c += wave_cols[w]; }
-        all += wave_sum[w]; all_c += wave_cols[w];
-    }
+    Sum2 every;
+    const Sum2 before = block_prefix_excl<kRowThreads / 64>(Sum2{sum, cols}, lane, wid, s_wave, every);
+    const uint32_t all = every.x, all_c = every.y;
     if (t == 0) { s_base = all ? atomicAdd(&flags[kCfListsOut], all) : 0u; s_cols = all_c ? atomicAdd(&flags[kCfColsOut], all_c) : 0u; }
     __syncthreads();
-    uint32_t at = s_base + pre + x - sum, col = s_cols + pre_c + y - cols;
+    uint32_t at = s_base + before.x, col = s_cols + before.y;
     if ((all && s_base + all > ids_room) || (all_c && s_cols + all_c > max_cols)) { if (t == 0) atomicOr(&flags[kCfTableFull], 1u); return; }   // (cannot happen: sized from the count)
 #pragma unroll
     for (int u = 0; u < kRowSlots; ++u) {
@@ -2439,17 +2402,9 @@ __global__ __launch_bounds__(kPartThreads) void k_part_offsets(const uint32_t* _
     for (uint32_t base = 0; base < n; base += kPartThreads) {
         const uint32_t j = base + t;
         const uint32_t v = j < n ? cnt[(uint64_t)p * n + j] : 0u;
-        uint32_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63) wave_sum[wid] = x;
-        __syncthreads();
-        uint32_t pre = s_carry, all = 0;
-        for (uint32_t w = 0; w < kPartThreads / 64; ++w) { if (w < wid) pre += wave_sum[w]; all += wave_sum[w]; }
-        if (j < n) { off[(uint64_t)p * n + j] = pre + x - v; hdr[4 + j] = v; }
+        uint32_t all;
+        const uint32_t pre = s_carry + block_prefix_excl<kPartThreads / 64>(v, lane, wid, wave_sum, all);
+        if (j < n) { off[(uint64_t)p * n + j] = pre; hdr[4 + j] = v; }
         __syncthreads();
         if (t == 0) s_carry += all;
         __syncthreads();

@@ -292,14 +292,8 @@ __global__ __launch_bounds__(kSortThreads) void k_decode_sort(uint32_t* __restri
         if (i < n) first[u] = (i == 0 || s_mn[i] != s_mn[i - 1] || s_lo[i] != s_lo[i - 1] || (HAS_HI && s_hi[i] != s_hi[i - 1])) ? 1u : 0u;
         cnt += first[u];
     }
-    uint32_t x = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d); if (lane >= (uint32_t)d) x += y; }
-    if (lane == 63) wave_sum[wid] = x;
-    __syncthreads();
-    uint32_t pre = 0, all = 0;
-    for (uint32_t w = 0; w < kSortThreads / 64; ++w) { if (w < wid) pre += wave_sum[w]; all += wave_sum[w]; }
-    uint32_t rank = pre + x - cnt;
+    uint32_t all;
+    uint32_t rank = block_prefix_excl<kSortThreads / 64>(cnt, lane, wid, wave_sum, all);
 #pragma unroll
     for (uint32_t u = 0; u < PER; ++u) {
         const uint32_t i = t * PER + u;

@@ -170,15 +170,38 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// reductions over the wave: every lane gets the result
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+// The sums a scan may run over besides a 32- or 64-bit count: small records of whole dwords with += and -, summed field by field.
+struct ExSum { unsigned long long a; uint32_t b, c; };   // 16 bytes: bytes (or starts), runs, records kept (extract, split)
+struct __attribute__((packed, aligned(4))) Sum64x32 { unsigned long long a; uint32_t b; };   // 12 bytes: a 64-bit and a 32-bit count at once
+struct WnSum { unsigned long long bases, wins; };        // (windows)
+struct Sum2 { uint32_t x, y; };                          // two counts scanned at once
+__device__ __forceinline__ ExSum& operator+=(ExSum& p, const ExSum& q) { p.a += q.a; p.b += q.b; p.c += q.c; return p; }
+__device__ __forceinline__ ExSum operator-(ExSum p, const ExSum& q) { p.a -= q.a; p.b -= q.b; p.c -= q.c; return p; }
+__device__ __forceinline__ Sum64x32& operator+=(Sum64x32& p, const Sum64x32& q) { p.a += q.a; p.b += q.b; return p; }
+__device__ __forceinline__ Sum64x32 operator-(Sum64x32 p, const Sum64x32& q) { p.a -= q.a; p.b -= q.b; return p; }
+__device__ __forceinline__ WnSum& operator+=(WnSum& p, const WnSum& q) { p.bases += q.bases; p.wins += q.wins; return p; }
+__device__ __forceinline__ WnSum operator-(WnSum p, const WnSum& q) { p.bases -= q.bases; p.wins -= q.wins; return p; }
+__device__ __forceinline__ Sum2& operator+=(Sum2& p, const Sum2& q) { p.x += q.x; p.y += q.y; return p; }
+__device__ __forceinline__ Sum2 operator-(Sum2 p, const Sum2& q) { p.x -= q.x; p.y -= q.y; return p; }
+
+// v of the lane d below (UP) or of lane ^ d, a 32-bit shuffle per dword of T
+template <bool UP, class T>
+__device__ __forceinline__ T lane_get(T v, int d) {
+    static_assert(sizeof(T) % 4 == 0 && __is_trivially_copyable(T), "whole dwords");
+    if constexpr (__is_integral(T)) return UP ? __shfl_up(v, d) : __shfl_xor(v, d);
+    uint32_t w[sizeof(T) / 4];
+    __builtin_memcpy(w, &v, sizeof(T));
 #pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    for (uint32_t i = 0; i < sizeof(T) / 4; ++i) w[i] = UP ? __shfl_up(w[i], d) : __shfl_xor(w[i], d);
+    __builtin_memcpy(&v, w, sizeof(T));
     return v;
 }
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+
+// reductions over the wave: every lane gets the result
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    for (int d = 32; d; d >>= 1) v += lane_get<false>(v, d);
     return v;
 }
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
@@ -192,10 +215,74 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
     return v;
 }
 // the sum of v over the lanes up to and including this one
-__device__ __forceinline__ uint32_t wave_prefix_incl(uint32_t v, uint32_t lane) {
+template <class T>
+__device__ __forceinline__ T wave_prefix_incl(T v, uint32_t lane) {
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(v, d); if ((int)lane >= d) v += t; }
+    for (int d = 1; d < 64; d <<= 1) { const T t = lane_get<true>(v, d); if ((int)lane >= d) v += t; }
     return v;
+}
+
+// ---- What the prefix sums share (DESIGN "What the prefix sums share").  A workgroup of WAVES waves, lane = threadIdx.x & 63 and
+// wid = threadIdx.x >> 6 from the caller, s_wave: WAVES items of LDS.  Each has one barrier, behind the store to s_wave and in front
+// of its reads: whoever stores to s_wave again puts a barrier of their own in between.
+
+// the sum of v over the threads in front of this one; `total`: over all of them
+template <int WAVES, class T>
+__device__ __forceinline__ T block_prefix_excl(T v, uint32_t lane, uint32_t wid, T* s_wave) {
+    const T incl = wave_prefix_incl(v, lane);
+    if (lane == 63u) s_wave[wid] = incl;
+    __syncthreads();
+    T pre = incl - v;
+    for (uint32_t w = 0; w < wid; ++w) pre += s_wave[w];
+    return pre;
+}
+template <int WAVES, class T>
+__device__ __forceinline__ T block_prefix_excl(T v, uint32_t lane, uint32_t wid, T* s_wave, T& total) {
+    const T incl = wave_prefix_incl(v, lane);
+    if (lane == 63u) s_wave[wid] = incl;
+    __syncthreads();
+    T pre = incl - v, all{};
+#pragma unroll
+    for (uint32_t w = 0; w < (uint32_t)WAVES; ++w) { if (w < wid) pre += s_wave[w]; all += s_wave[w]; }
+    total = all;
+    return pre;
+}
+
+// the sum of v over the workgroup, in thread 0 (the others get what their wave's lanes hold: nothing to use)
+template <int WAVES, class T>
+__device__ __forceinline__ T block_sum(T v, T* s_wave) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T all{};
+    if (threadIdx.x == 0)
+        for (uint32_t w = 0; w < (uint32_t)WAVES; ++w) all += s_wave[w];
+    return all;
+}
+
+// One workgroup of 1 024: out[i] = the sum of in[0 .. i), and done(the sum of all).  A lane owns four consecutive items per round,
+// so a round covers 4 096 of them; the rounds in front are carried in LDS
+template <class T, class Done>
+__global__ __launch_bounds__(1024) void k_scan_items(const T* __restrict__ in, uint64_t n_items, T* __restrict__ out, Done done) {
+    __shared__ T s_wave[16];
+    __shared__ T s_carry;
+    const uint32_t t = threadIdx.x, lane = t & 63u, wid = t >> 6;
+    if (t == 0) s_carry = T{};
+    __syncthreads();
+    for (uint64_t base = 0; base < n_items; base += 4096ull) {   // (uniform)
+        const uint64_t i0 = base + (uint64_t)t * 4ull;
+        T me[4], sum{}, all;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { me[u] = i0 + u < n_items ? in[i0 + u] : T{}; sum += me[u]; }
+        T run = block_prefix_excl<16>(sum, lane, wid, s_wave, all);
+        run += s_carry;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { if (i0 + u < n_items) out[i0 + u] = run; run += me[u]; }
+        __syncthreads();
+        if (t == 0) s_carry += all;
+        __syncthreads();
+    }
+    if (t == 0) done(s_carry);
 }
 
 // the wave's words s[0 .. P) in LDS sorted ascending by a bitonic network; P a power of two >= 64, and what the lanes stored in

@@ -6,10 +6,10 @@
 //                '\n' nor '\r': what fastq_tail finds on the host) and where its last record ends (behind the first '\n' of the
 //                blank tail).  FASTA: both are n.  The words stay on the device: the launches behind it read them, no host wait.
 //   k_ex_tiles   per tile: FASTA the lines behind byte 0 that begin with '>' or 0xFF; FASTQ the newlines of the content.
-//   k_ex_scan    one workgroup: the exclusive scan of the tiles' sums (the same kernel scans the records' sums below).
+//   k_scan_items<ExSum>  one workgroup: the exclusive scan of the tiles' sums (spsp_device.h; it scans the records' sums below too).
 //   k_ex_starts  per tile: begin[] -- FASTA every start; FASTQ the byte behind every newline whose line index is a multiple of
 //                four ("line index mod 4 == 0" is decided here, behind the scan) -- and begin[n_rec], the last record's end.
-// Kept lengths and output offsets: k_ex_rec_tiles / k_ex_scan / k_ex_rec_write over tiles of 2 048 records.  A record adds its
+// Kept lengths and output offsets: k_ex_rec_tiles / k_scan_items / k_ex_rec_write over tiles of 2 048 records.  A record adds its
 // length when it is kept; consecutive kept records merge into RUNS (source start, output start), and the run table is what the
 // copy searches: one entry per run, not per record.  Every pair begin[r] <= begin[r + 1] <= n is checked there (a d_begin of the
 // caller's): a pair that fails adds nothing and raises the call's flag, so no run ever leaves the text.
@@ -72,19 +72,6 @@ __device__ __forceinline__ ExChunk ex_chunk(const uint8_t* __restrict__ text, ui
     return c;
 }
 
-// exclusive scan of one 32-bit count over the workgroup (lane order = byte order); *total: the workgroup's sum
-__device__ __forceinline__ uint32_t ex_block_scan(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    const uint32_t incl = wave_prefix_incl(v, lane);
-    if (lane == 63u) s_wave[wid] = incl;
-    __syncthreads();
-    uint32_t pre = 0, all = 0;
-    for (uint32_t w = 0; w < kExThreads / 64; ++w) { if (w < wid) pre += s_wave[w]; all += s_wave[w]; }
-    *total = all;
-    __syncthreads();
-    return pre + incl - v;
-}
-
 __global__ __launch_bounds__(kExThreads) void k_ex_tail(const uint8_t* __restrict__ text, uint64_t n, unsigned long long* __restrict__ words) {
     __shared__ unsigned long long s_best;
     const uint32_t t = threadIdx.x;
@@ -135,60 +122,16 @@ __global__ __launch_bounds__(kExThreads) void k_ex_tiles(const uint8_t* __restri
     __shared__ uint32_t s_wave[kExThreads / 64];
     const bool fastq = words[kExFastq] != 0ull;
     const ExChunk c = ex_chunk(text, n, words[kExLimit], (uint64_t)blockIdx.x * kExTile + (uint64_t)threadIdx.x * kExChunk, fastq);
-    uint32_t total;
-    (void)ex_block_scan((uint32_t)__popc(fastq ? c.nl : c.start), s_wave, &total);
+    const uint32_t total = block_sum<kExThreads / 64>((uint32_t)__popc(fastq ? c.nl : c.start), s_wave);
+    __syncthreads();
     if (threadIdx.x == 0) tiles[blockIdx.x] = ExSum{total, 0u, 0u};
 }
 
-// one workgroup: out[i] = the sums of in[0 .. i), totals[0] = all a, totals[1] = all b | all c << 32.  A lane owns four consecutive
-// items per round, so a round covers 4 096 of them
-__global__ __launch_bounds__(1024) void k_ex_scan(const ExSum* __restrict__ in, uint64_t n_items, ExSum* __restrict__ out,
-                                                  unsigned long long* __restrict__ totals) {
-    __shared__ unsigned long long s_a[16];
-    __shared__ uint32_t s_b[16], s_c[16];
-    __shared__ unsigned long long c_a;
-    __shared__ uint32_t c_b, c_c;
-    const uint32_t t = threadIdx.x, lane = t & 63u, wid = t >> 6;
-    if (t == 0) { c_a = 0ull; c_b = 0u; c_c = 0u; }
-    __syncthreads();
-    for (uint64_t base = 0; base < n_items; base += 4096ull) {   // (uniform)
-        const uint64_t i0 = base + (uint64_t)t * 4ull;
-        ExSum me[4];
-        unsigned long long a = 0;
-        uint32_t b = 0, c = 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            me[u] = i0 + u < n_items ? in[i0 + u] : ExSum{0ull, 0u, 0u};
-            a += me[u].a; b += me[u].b; c += me[u].c;
-        }
-        unsigned long long ax = a;
-        uint32_t bx = b, cx = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long ay = __shfl_up(ax, d);
-            const uint32_t by = __shfl_up(bx, d), cy = __shfl_up(cx, d);
-            if (lane >= (uint32_t)d) { ax += ay; bx += by; cx += cy; }
-        }
-        if (lane == 63u) { s_a[wid] = ax; s_b[wid] = bx; s_c[wid] = cx; }
-        __syncthreads();
-        unsigned long long ap = c_a, aall = 0;
-        uint32_t bp = c_b, cp = c_c, ball = 0, call = 0;
-        for (uint32_t w = 0; w < 16; ++w) {
-            if (w < wid) { ap += s_a[w]; bp += s_b[w]; cp += s_c[w]; }
-            aall += s_a[w]; ball += s_b[w]; call += s_c[w];
-        }
-        ap += ax - a; bp += bx - b; cp += cx - c;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (i0 + u < n_items) out[i0 + u] = ExSum{ap, bp, cp};
-            ap += me[u].a; bp += me[u].b; cp += me[u].c;
-        }
-        __syncthreads();
-        if (t == 0) { c_a += aall; c_b += ball; c_c += call; }
-        __syncthreads();
-    }
-    if (t == 0) { totals[0] = c_a; totals[1] = (unsigned long long)c_b | ((unsigned long long)c_c << 32); }
-}
+// what the item scan does with an ExSum total: totals[0] = all a, totals[1] = all b | all c << 32
+struct ExTotals {
+    unsigned long long* totals;
+    __device__ void operator()(const ExSum& s) const { totals[0] = s.a; totals[1] = (unsigned long long)s.b | ((unsigned long long)s.c << 32); }
+};
 
 // begin[] has room for cap + 1 entries: nothing is written behind them, whatever the text holds
 __global__ __launch_bounds__(kExThreads) void k_ex_starts(const uint8_t* __restrict__ text, uint64_t n, uint64_t n_tiles,
@@ -199,8 +142,8 @@ __global__ __launch_bounds__(kExThreads) void k_ex_starts(const uint8_t* __restr
     const uint64_t limit = words[kExLimit];
     const uint64_t p0 = (uint64_t)blockIdx.x * kExTile + (uint64_t)threadIdx.x * kExChunk;
     const ExChunk c = ex_chunk(text, n, limit, p0, fastq);
-    uint32_t total;
-    const uint32_t before = ex_block_scan((uint32_t)__popc(fastq ? c.nl : c.start), s_wave, &total);
+    const uint32_t before = block_prefix_excl<kExThreads / 64>((uint32_t)__popc(fastq ? c.nl : c.start), threadIdx.x & 63u, threadIdx.x >> 6, s_wave);
+    __syncthreads();
     if (blockIdx.x < n_tiles) {
         uint64_t g = base[blockIdx.x].a + before;          // FASTA: the starts, FASTQ: the newlines in front of this lane
         uint32_t rem = fastq ? c.nl : c.start;
@@ -253,21 +196,13 @@ __device__ __forceinline__ void ex_walk(const uint64_t* __restrict__ begin, cons
 
 __global__ __launch_bounds__(kExThreads) void k_ex_rec_tiles(const uint64_t* __restrict__ begin, const uint8_t* __restrict__ keep, uint32_t n_rec,
                                                              uint64_t n_text, ExSum* __restrict__ tiles, unsigned long long* __restrict__ words) {
-    __shared__ unsigned long long s_a[kExThreads / 64];
-    __shared__ uint32_t s_b[kExThreads / 64], s_c[kExThreads / 64];
+    __shared__ ExSum s_wave[kExThreads / 64];
     ExSum s;
     bool bad;
     ex_walk(begin, keep, n_rec, n_text, ((uint64_t)blockIdx.x * kExThreads + threadIdx.x) * kExRecsPerLane, s, bad, [](uint32_t, uint64_t, uint64_t) {});
     if (bad) atomicOr(words + kExBad, 2ull);
-    const unsigned long long a = wave_sum(s.a);
-    const uint32_t b = wave_sum(s.b), c = wave_sum(s.c);
-    if ((threadIdx.x & 63u) == 0u) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; s_c[threadIdx.x >> 6] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ExSum all{0ull, 0u, 0u};
-        for (uint32_t w = 0; w < kExThreads / 64; ++w) { all.a += s_a[w]; all.b += s_b[w]; all.c += s_c[w]; }
-        tiles[blockIdx.x] = all;
-    }
+    const ExSum all = block_sum<kExThreads / 64>(s, s_wave);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = all;
 }
 
 // run i: source bytes [run_src[i], ...) -> output bytes [run_dst[i], run_dst[i + 1]); run_dst[n_runs] = the source bytes kept
@@ -275,27 +210,15 @@ __global__ __launch_bounds__(kExThreads) void k_ex_rec_write(const uint8_t* __re
                                                              const uint8_t* __restrict__ keep, uint32_t n_rec, uint64_t n_tiles,
                                                              const ExSum* __restrict__ base, uint64_t* __restrict__ run_src, uint64_t* __restrict__ run_dst,
                                                              unsigned long long* __restrict__ words) {
-    __shared__ unsigned long long s_a[kExThreads / 64];
-    __shared__ uint32_t s_b[kExThreads / 64];
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    __shared__ Sum64x32 s_wave[kExThreads / 64];
     const uint64_t r0 = ((uint64_t)blockIdx.x * kExThreads + threadIdx.x) * kExRecsPerLane;
     ExSum s;
     bool bad;
     ex_walk(begin, keep, n_rec, n_text, r0, s, bad, [](uint32_t, uint64_t, uint64_t) {});
-    unsigned long long ax = s.a;
-    uint32_t bx = s.b;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long ay = __shfl_up(ax, d);
-        const uint32_t by = __shfl_up(bx, d);
-        if (lane >= (uint32_t)d) { ax += ay; bx += by; }
-    }
-    if (lane == 63u) { s_a[wid] = ax; s_b[wid] = bx; }
-    __syncthreads();
+    const Sum64x32 before = block_prefix_excl<kExThreads / 64>(Sum64x32{s.a, s.b}, threadIdx.x & 63u, threadIdx.x >> 6, s_wave);
     if (blockIdx.x < n_tiles) {
-        unsigned long long a0 = base[blockIdx.x].a + ax - s.a;
-        uint32_t b0 = base[blockIdx.x].b + bx - s.b;
-        for (uint32_t w = 0; w < wid; ++w) { a0 += s_a[w]; b0 += s_b[w]; }
+        const unsigned long long a0 = base[blockIdx.x].a + before.a;
+        const uint32_t b0 = base[blockIdx.x].b + before.b;
         ExSum again;
         ex_walk(begin, keep, n_rec, n_text, r0, again, bad, [=](uint32_t i, uint64_t src, uint64_t at) { run_src[b0 + i] = src; run_dst[b0 + i] = a0 + at; });
     }
@@ -379,8 +302,8 @@ int ex_count_launch(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint6
     hipLaunchKernelGGL(k_ex_tail, dim3(1), dim3(kExThreads), 0, ctx->stream, d_text, n_text, words);
     if (n_tiles) hipLaunchKernelGGL(k_ex_tiles, dim3((uint32_t)n_tiles), dim3(kExThreads), 0, ctx->stream, d_text, n_text, (const unsigned long long*)words,
                                     ctx->ex_tiles.as<ExSum>());
-    hipLaunchKernelGGL(k_ex_scan, dim3(1), dim3(1024), 0, ctx->stream, (const ExSum*)ctx->ex_tiles.as<ExSum>(), n_tiles, ctx->ex_bases.as<ExSum>(),
-                       words + kExUnits);
+    hipLaunchKernelGGL((k_scan_items<ExSum, ExTotals>), dim3(1), dim3(1024), 0, ctx->stream, (const ExSum*)ctx->ex_tiles.as<ExSum>(), n_tiles,
+                       ctx->ex_bases.as<ExSum>(), ExTotals{words + kExUnits});
     SPSP_HIP(hipGetLastError());
     return SPSP_OK;
 }
@@ -401,7 +324,7 @@ int ex_refuse_lines(uint64_t lines) {
 }
 
 int ex_scan_launch(spsp_ctx* ctx, const ExSum* d_in, uint64_t n_items, ExSum* d_out, unsigned long long* d_totals) {
-    hipLaunchKernelGGL(k_ex_scan, dim3(1), dim3(1024), 0, ctx->stream, d_in, n_items, d_out, d_totals);
+    hipLaunchKernelGGL((k_scan_items<ExSum, ExTotals>), dim3(1), dim3(1024), 0, ctx->stream, d_in, n_items, d_out, ExTotals{d_totals});
     SPSP_HIP(hipGetLastError());
     return SPSP_OK;
 }
@@ -453,8 +376,8 @@ int records_extract_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, 
     if (n_rec) SPSP_HIP(hipMemcpyAsync(keep, h_keep, n_rec, hipMemcpyHostToDevice, ctx->stream));
     if (n_rtiles) hipLaunchKernelGGL(k_ex_rec_tiles, dim3((uint32_t)n_rtiles), dim3(kExThreads), 0, ctx->stream, d_begin, (const uint8_t*)keep, n_rec, n_text,
                                      ctx->ex_tiles.as<ExSum>(), words);
-    hipLaunchKernelGGL(k_ex_scan, dim3(1), dim3(1024), 0, ctx->stream, (const ExSum*)ctx->ex_tiles.as<ExSum>(), n_rtiles, ctx->ex_bases.as<ExSum>(),
-                       words + kExSrc);
+    hipLaunchKernelGGL((k_scan_items<ExSum, ExTotals>), dim3(1), dim3(1024), 0, ctx->stream, (const ExSum*)ctx->ex_tiles.as<ExSum>(), n_rtiles,
+                       ctx->ex_bases.as<ExSum>(), ExTotals{words + kExSrc});
     hipLaunchKernelGGL(k_ex_rec_write, dim3((uint32_t)std::max<uint64_t>(n_rtiles, 1)), dim3(kExThreads), 0, ctx->stream, d_text, n_text, d_begin,
                        (const uint8_t*)keep, n_rec, n_rtiles, (const ExSum*)ctx->ex_bases.as<ExSum>(), run_src, run_dst, words);
     SPSP_HIP(hipGetLastError());

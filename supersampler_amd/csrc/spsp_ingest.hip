@@ -145,6 +145,8 @@ __device__ __forceinline__ uint32_t block_scan_transform(uint32_t t, uint32_t* s
     __syncthreads();
     return compose(pre, excl);
 }
+// (the additive scans of the write passes keep this form of their own, a second barrier behind it: k_mixed_write spills, and its
+// code is left as measured -- everywhere else it is block_prefix_excl, spsp_device.h)
 __device__ __forceinline__ uint32_t block_scan_add(uint32_t v, uint32_t* s_wave, uint32_t* total) {
     const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     uint32_t x = v;
@@ -177,14 +179,9 @@ __global__ __launch_bounds__(kCleanThreads) void k_clean_tiles(const uint8_t* __
     // only the three totals are needed: one packed 64-bit reduction (each count fits in 20 bits)
     unsigned long long packed = (unsigned long long)fixed | ((unsigned long long)extra << 20) |
                                 ((unsigned long long)__popc(c.drop_after) << 40);
-#pragma unroll
-    for (int d = 32; d; d >>= 1) packed += __shfl_xor(packed, d);
     __shared__ unsigned long long s_tot[kCleanThreads / 64];
-    if ((threadIdx.x & 63) == 0) s_tot[threadIdx.x >> 6] = packed;
-    __syncthreads();
+    const unsigned long long all = block_sum<kCleanThreads / 64>(packed, s_tot);
     if (threadIdx.x == 0) {
-        unsigned long long all = 0;
-        for (int w = 0; w < kCleanThreads / 64; ++w) all += s_tot[w];
         tiles[blockIdx.x] = TileSummary{tile_t, (uint32_t)(all & 0xFFFFFu), (uint32_t)((all >> 20) & 0xFFFFFu), (uint32_t)(all >> 40)};
     }
 }
@@ -197,8 +194,7 @@ __global__ __launch_bounds__(1024) void k_clean_scan(const TileSummary* __restri
                                                     uint32_t* __restrict__ entry_drop, uint64_t* __restrict__ out_off,
                                                     uint32_t* __restrict__ rec_base, uint64_t* __restrict__ totals) {
     __shared__ uint32_t s_t[16];
-    __shared__ unsigned long long s_k[16];
-    __shared__ uint32_t s_h[16];
+    __shared__ Sum64x32 s_kh[16];                           // a: survivors, b: headers
     __shared__ uint32_t c_t;
     __shared__ unsigned long long c_k;
     __shared__ uint32_t c_h;
@@ -239,31 +235,19 @@ __global__ __launch_bounds__(1024) void k_clean_scan(const TileSummary* __restri
             ksum += keep[u]; hsum += me[u].headers;
             state = compose(state, me[u].transform);
         }
-        unsigned long long kx = ksum;
-        uint32_t hx = hsum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long ky = __shfl_up(kx, d);
-            const uint32_t hy = __shfl_up(hx, d);
-            if (lane >= (uint32_t)d) { kx += ky; hx += hy; }
-        }
-        if (lane == 63) { s_k[wid] = kx; s_h[wid] = hx; }
-        __syncthreads();
-        unsigned long long kpre = c_k, kall = 0;
-        uint32_t hpre = c_h, hall = 0, tall = 0;
-        for (uint32_t w = 0; w < 16; ++w) {
-            if (w < wid) { kpre += s_k[w]; hpre += s_h[w]; }
-            kall += s_k[w]; hall += s_h[w]; tall = compose(tall, s_t[w]);
-        }
-        unsigned long long ko = kpre + kx - ksum;
-        uint32_t ho = hpre + hx - hsum;
+        Sum64x32 all;
+        const Sum64x32 before = block_prefix_excl<16>(Sum64x32{ksum, hsum}, lane, wid, s_kh, all);
+        uint32_t tall = 0;
+        for (uint32_t w = 0; w < 16; ++w) tall = compose(tall, s_t[w]);
+        unsigned long long ko = c_k + before.a;
+        uint32_t ho = c_h + before.b;
 #pragma unroll
         for (int u = 0; u < kScanTiles; ++u) {
             if (i0 + u < n_tiles) { entry_drop[i0 + u] = entry[u]; out_off[i0 + u] = ko; rec_base[i0 + u] = ho; }
             ko += keep[u]; ho += me[u].headers;
         }
         __syncthreads();
-        if (t == 0) { c_t = compose(c_t, tall); c_k += kall; c_h += hall; }
+        if (t == 0) { c_t = compose(c_t, tall); c_k += all.a; c_h += all.b; }
         __syncthreads();
     }
     if (t == 0) { totals[0] = c_k; totals[kHsIngestRecs - kHsIngestKept] = c_h; }

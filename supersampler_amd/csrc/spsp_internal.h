@@ -789,7 +789,7 @@ enum ExWord {
     kSpNlAt = 15,   // the split: the output byte that is the appended newline, or ~0
     kExWords = 16
 };
-struct ExSum { unsigned long long a; uint32_t b, c; };   // 16 bytes: bytes (or starts), runs, records kept
+struct ExSum;   // (spsp_device.h)
 // the launches of the starts, for the extraction and the split (spsp_extract.hip).  ex_front: the text's alignment and its tiles.
 // ex_count_launch: the tail, the tiles' sums and their scan -- everything that does not need n_rec -- with the call's words cleared
 // in front.  ex_starts_launch: begin[0 .. cap] in ctx->ex_begin.  ex_scan_launch: out[i] = the sums of in[0 .. i), totals[0] = all a,

@@ -128,14 +128,8 @@ __global__ __launch_bounds__(kKeySortThreads) void k_keys_sort(uint32_t* __restr
         }
         cnt += keep[u];
     }
-    uint32_t x = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d); if (lane >= (uint32_t)d) x += y; }
-    if (lane == 63) wave_sum[wid] = x;
-    __syncthreads();
-    uint32_t pre = 0, all = 0;
-    for (uint32_t w = 0; w < kKeySortThreads / 64; ++w) { if (w < wid) pre += wave_sum[w]; all += wave_sum[w]; }
-    uint32_t rank = pre + x - cnt;
+    uint32_t all;
+    uint32_t rank = block_prefix_excl<kKeySortThreads / 64>(cnt, lane, wid, wave_sum, all);
 #pragma unroll
     for (uint32_t u = 0; u < PER; ++u) {
         const uint32_t i = t * PER + u;
@@ -447,14 +441,8 @@ __global__ __launch_bounds__(kKeySortThreads) void k_keys_fused(const uint8_t* _
     uint32_t cnt = 0;
 #pragma unroll
     for (uint32_t u = 0; u < PER; ++u) cnt += keep[u];
-    uint32_t x = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d); if (lane >= (uint32_t)d) x += y; }
-    if (lane == 63) wave_sum[wid] = x;
-    __syncthreads();
-    uint32_t pre = 0, base = 0;
-    for (uint32_t w2 = 0; w2 < kKeySortThreads / 64; ++w2) { if (w2 < wid) pre += wave_sum[w2]; base += wave_sum[w2]; }
-    uint32_t at = r0 + pre + x - cnt;
+    uint32_t base;
+    uint32_t at = r0 + block_prefix_excl<kKeySortThreads / 64>(cnt, lane, wid, wave_sum, base);
 #pragma unroll
     for (uint32_t u = 0; u < PER; ++u) {
         const uint32_t r = id[u];

@@ -656,15 +656,11 @@ __global__ __launch_bounds__(64 * kPairWaves) void k_dense_single(const uint8_t*
 // out[i] = sum(in[0..i)), out[n] = total.  u32, single workgroup of 1024 lanes;
 // the arrays it runs over (tiles, hits) are tiny next to the dense pass.
 __global__ __launch_bounds__(1024) void k_exclusive_scan(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
-                                                        uint64_t n_max, const uint32_t* __restrict__ n_dev,
-                                                        uint64_t* __restrict__ total_host, uint32_t* __restrict__ total_dev) {
+                                                        uint64_t n, uint64_t* __restrict__ total_host, uint32_t* __restrict__ total_dev) {
     constexpr int E = 8;                       // consecutive elements per lane per round
     __shared__ uint32_t wave_sum[16];
     __shared__ uint32_t carry_s;
     const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    // n may only be known on the device (a count produced earlier on this stream)
-    uint64_t n = n_max;
-    if (n_dev) { const uint64_t v = *n_dev; n = v < n_max ? v : n_max; }
     if (t == 0) carry_s = 0;
     __syncthreads();
     for (uint64_t base = 0; base < n; base += 1024 * E) {
@@ -673,18 +669,10 @@ __global__ __launch_bounds__(1024) void k_exclusive_scan(const uint32_t* __restr
         uint32_t sum = 0;
 #pragma unroll
         for (int u = 0; u < E; ++u) { v[u] = i0 + u < n ? in[i0 + u] : 0u; sum += v[u]; }
-        uint32_t x = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63) wave_sum[wid] = x;
-        __syncthreads();
-        uint32_t pre = 0, all = 0;
-        for (uint32_t w = 0; w < 16; ++w) { if (w < wid) pre += wave_sum[w]; all += wave_sum[w]; }
+        uint32_t all;
+        const uint32_t pre = block_prefix_excl<16>(sum, lane, wid, wave_sum, all);
         const uint32_t carry = carry_s;
-        uint32_t run = carry + pre + x - sum;
+        uint32_t run = carry + pre;
 #pragma unroll
         for (int u = 0; u < E; ++u) { if (i0 + u < n) out[i0 + u] = run; run += v[u]; }
         __syncthreads();
@@ -728,18 +716,8 @@ __global__ __launch_bounds__(kSegThreads) void k_scan_segments(const uint32_t* _
             if (i0 + 2 < seg1) v.z = in[i0 + 2];
         }
         const uint32_t sum = v.x + v.y + v.z + v.w;
-        uint32_t x = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63) wave_sum[wid] = x;
-        __syncthreads();
-        uint32_t pre = s_carry, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kSegThreads / 64; ++w) { if (w < wid) pre += wave_sum[w]; all += wave_sum[w]; }
-        const uint32_t e0 = pre + x - sum;
+        uint32_t all;
+        const uint32_t e0 = s_carry + block_prefix_excl<kSegThreads / 64>(sum, lane, wid, wave_sum, all);
         const uint4 o = make_uint4(e0, e0 + v.x, e0 + v.x + v.y, e0 + v.x + v.y + v.z);
         if (i0 + 4 <= seg1) *reinterpret_cast<uint4*>(out + i0) = o;
         else {
@@ -767,12 +745,7 @@ __global__ __launch_bounds__(64) void k_scan_top(const uint32_t* __restrict__ se
     for (uint32_t base = 0; base < n_seg; base += 64) {
         const uint32_t i = base + lane;
         const uint32_t v = i < n_seg ? seg_sum[i] : 0u;
-        uint32_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
+        const uint32_t x = wave_prefix_incl(v, lane);
         if (i < n_seg) seg_off[i] = carry + x - v;
         carry += __shfl(x, 63);
     }
@@ -856,12 +829,7 @@ __global__ __launch_bounds__(kThreads) void k_expand(const uint8_t* __restrict__
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         cnt[h] = __popc(q[h].x) + __popc(q[h].y) + __popc(q[h].z) + __popc(q[h].w);
-        uint32_t x = cnt[h];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
+        const uint32_t x = wave_prefix_incl(cnt[h], lane);
         lrank[h] = total + x - cnt[h];
         total += __shfl(x, 63);
         // leave the bitmap all-zero behind us: the pair-table dense pass publishes hits with
@@ -1134,12 +1102,7 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(WaveLists L, uint32
     uint32_t own = 0, own_raw = 0;
     if (t < (uint32_t)kCompactWaves && w0 + t < n_lists) { own_raw = L.cnt[w0 + t]; own = own_raw < L.cap ? own_raw : L.cap; }
     if (wid == 0) {
-        uint32_t x = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
+        const uint32_t x = wave_prefix_incl(own, lane);
         s_pre[lane] = x - own;
         if (lane == 63) s_pre[64] = x;
         mx = own_raw > mx ? own_raw : mx;
@@ -1423,12 +1386,7 @@ __global__ __launch_bounds__(kResolveThreads) void k_resolve(const Hit* __restri
     }
     // write pass: offset = chunks before mine + waves of my chunk before mine + lanes of my wave before me
     const uint32_t c = h < hits_cap ? emit_count[h] : 0u;
-    uint32_t x = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= (uint32_t)d) x += y;
-    }
+    const uint32_t x = wave_prefix_incl(c, lane);
     // (n_super != 0: a third level, sums of 64 chunks made by k_super_sums between the passes -- with two levels a wave of an
     // input that is all hits summed 10^5 chunk sums, quadratic in the hits; few hits: two levels and no launch in between)
     const uint32_t wi = gw & 63u, ci = gw >> 6, si = ci >> 6;
@@ -1475,11 +1433,8 @@ __global__ __launch_bounds__(1024) void k_scan_block_sums(const uint32_t* __rest
     uint32_t sum = 0;
 #pragma unroll
     for (int u = 0; u < 8; ++u) sum += base + u < n ? in[base + u] : 0u;
-#pragma unroll
-    for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d);
-    if ((threadIdx.x & 63u) == 0) wave_sum[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) { uint32_t all = 0; for (uint32_t w = 0; w < 16; ++w) all += wave_sum[w]; sums[blockIdx.x] = all; }
+    const uint32_t all = block_sum<16>(sum, wave_sum);
+    if (threadIdx.x == 0) sums[blockIdx.x] = all;
 }
 __global__ __launch_bounds__(1024) void k_scan_blocks(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n,
                                                      const uint32_t* __restrict__ block_off) {
@@ -1489,14 +1444,7 @@ __global__ __launch_bounds__(1024) void k_scan_blocks(const uint32_t* __restrict
     uint32_t v[8], sum = 0;
 #pragma unroll
     for (int u = 0; u < 8; ++u) { v[u] = i0 + u < n ? in[i0 + u] : 0u; sum += v[u]; }
-    uint32_t x = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d); if (lane >= (uint32_t)d) x += y; }
-    if (lane == 63) wave_sum[wid] = x;
-    __syncthreads();
-    uint32_t pre = 0;
-    for (uint32_t w = 0; w < wid; ++w) pre += wave_sum[w];
-    uint32_t run = block_off[blockIdx.x] + pre + x - sum;
+    uint32_t run = block_off[blockIdx.x] + block_prefix_excl<16>(sum, lane, wid, wave_sum);
 #pragma unroll
     for (int u = 0; u < 8; ++u) { if (i0 + u < n) out[i0 + u] = run; run += v[u]; }
 }
@@ -1508,13 +1456,13 @@ int launch_scan_u32(spsp_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, uint64
         uint32_t* sums = ctx->scan_blocks.as<uint32_t>();
         uint32_t* offs = sums + blocks;                                  // [blocks + 1]: the scan's own total lands in offs[blocks]
         hipLaunchKernelGGL(k_scan_block_sums, dim3(blocks), dim3(1024), 0, ctx->stream, d_in, n, sums);
-        hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)sums, offs, (uint64_t)blocks, (const uint32_t*)nullptr,
+        hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)sums, offs, (uint64_t)blocks,
                            total_host, d_out + n);                       // out[n] = total, as the one-kernel form leaves it
         hipLaunchKernelGGL(k_scan_blocks, dim3(blocks), dim3(1024), 0, ctx->stream, d_in, d_out, n, (const uint32_t*)offs);
         SPSP_HIP(hipGetLastError());
         return SPSP_OK;
     }
-    hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, ctx->stream, d_in, d_out, n, (const uint32_t*)nullptr,
+    hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, ctx->stream, d_in, d_out, n,
                        total_host, (uint32_t*)nullptr);
     SPSP_HIP(hipGetLastError());
     return SPSP_OK;

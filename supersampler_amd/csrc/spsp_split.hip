@@ -60,48 +60,15 @@ __device__ __forceinline__ void sp_walk(const uint64_t* __restrict__ begin, cons
     }
 }
 
-// the exclusive scan of one 64-bit and one 32-bit count over the workgroup, lane order; s_a, s_b: a word per wave
-__device__ __forceinline__ void sp_block_scan(unsigned long long a, uint32_t b, unsigned long long* s_a, uint32_t* s_b, unsigned long long* a_before,
-                                              uint32_t* b_before) {
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    unsigned long long ax = a;
-    uint32_t bx = b;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long ay = __shfl_up(ax, d);
-        const uint32_t by = __shfl_up(bx, d);
-        if (lane >= (uint32_t)d) { ax += ay; bx += by; }
-    }
-    if (lane == 63u) { s_a[wid] = ax; s_b[wid] = bx; }
-    __syncthreads();
-    unsigned long long a0 = ax - a;
-    uint32_t b0 = bx - b;
-    for (uint32_t w = 0; w < wid; ++w) { a0 += s_a[w]; b0 += s_b[w]; }
-    *a_before = a0; *b_before = b0;
-}
-
-// the workgroup's sums as its tile's entry
-__device__ __forceinline__ void sp_tile_sum(const ExSum& s, ExSum* __restrict__ tile) {
-    __shared__ unsigned long long s_a[kExThreads / 64];
-    __shared__ uint32_t s_b[kExThreads / 64], s_c[kExThreads / 64];
-    const unsigned long long a = wave_sum(s.a);
-    const uint32_t b = wave_sum(s.b), c = wave_sum(s.c);
-    if ((threadIdx.x & 63u) == 0u) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; s_c[threadIdx.x >> 6] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ExSum all{0ull, 0u, 0u};
-        for (uint32_t w = 0; w < kExThreads / 64; ++w) { all.a += s_a[w]; all.b += s_b[w]; all.c += s_c[w]; }
-        *tile = all;
-    }
-}
-
 __global__ __launch_bounds__(kExThreads) void k_sp_rec_tiles(const uint64_t* __restrict__ begin, const uint32_t* __restrict__ bin, uint32_t n_rec, uint64_t n_text,
                                                              ExSum* __restrict__ tiles, unsigned long long* __restrict__ words) {
+    __shared__ ExSum s_wave[kExThreads / 64];
     ExSum s;
     bool bad;
     sp_walk(begin, bin, n_rec, n_text, ((uint64_t)blockIdx.x * kExThreads + threadIdx.x) * kExRecsPerLane, s, bad, [](uint32_t, uint64_t, uint64_t, uint32_t) {});
     if (bad) atomicOr(words + kExBad, 2ull);
-    sp_tile_sum(s, tiles + blockIdx.x);
+    const ExSum all = block_sum<kExThreads / 64>(s, s_wave);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = all;
 }
 
 // run i, in record order: source bytes [src[i], src[i] + pre[i + 1] - pre[i]), keys[i] = its bin, vals[i] = i; pre[n_runs] = the
@@ -110,18 +77,15 @@ __global__ __launch_bounds__(kExThreads) void k_sp_rec_write(const uint8_t* __re
                                                              const uint32_t* __restrict__ bin, uint32_t n_rec, uint64_t n_tiles, const ExSum* __restrict__ base,
                                                              uint32_t cap, uint64_t* __restrict__ src, uint64_t* __restrict__ pre, uint64_t* __restrict__ keys,
                                                              uint32_t* __restrict__ vals, unsigned long long* __restrict__ words) {
-    __shared__ unsigned long long s_a[kExThreads / 64];
-    __shared__ uint32_t s_b[kExThreads / 64];
+    __shared__ Sum64x32 s_wave[kExThreads / 64];
     const uint64_t r0 = ((uint64_t)blockIdx.x * kExThreads + threadIdx.x) * kExRecsPerLane;
     ExSum s;
     bool bad;
     sp_walk(begin, bin, n_rec, n_text, r0, s, bad, [](uint32_t, uint64_t, uint64_t, uint32_t) {});
-    unsigned long long a0;
-    uint32_t b0;
-    sp_block_scan(s.a, s.b, s_a, s_b, &a0, &b0);
+    const Sum64x32 before = block_prefix_excl<kExThreads / 64>(Sum64x32{s.a, s.b}, threadIdx.x & 63u, threadIdx.x >> 6, s_wave);
     if (blockIdx.x < n_tiles) {
-        a0 += base[blockIdx.x].a;
-        b0 += base[blockIdx.x].b;
+        const unsigned long long a0 = base[blockIdx.x].a + before.a;
+        const uint32_t b0 = base[blockIdx.x].b + before.b;
         ExSum again;
         sp_walk(begin, bin, n_rec, n_text, r0, again, bad, [=](uint32_t i, uint64_t from, uint64_t at, uint32_t bn) {
             const uint32_t run = b0 + i;
@@ -169,26 +133,25 @@ __device__ __forceinline__ unsigned long long sp_lens(const uint32_t* __restrict
 
 __global__ __launch_bounds__(kExThreads) void k_sp_len_tiles(const uint32_t* __restrict__ vals, const uint64_t* __restrict__ pre, uint32_t cap,
                                                              const unsigned long long* __restrict__ words, ExSum* __restrict__ tiles) {
+    __shared__ ExSum s_wave[kExThreads / 64];
     unsigned long long len[kExRecsPerLane];
     const uint32_t n_runs = sp_live_runs(words, cap);
     const ExSum s{sp_lens(vals, pre, n_runs, words[kExNl], ((uint64_t)blockIdx.x * kExThreads + threadIdx.x) * kExRecsPerLane, len), 0u, 0u};
-    sp_tile_sum(s, tiles + blockIdx.x);
+    const ExSum all = block_sum<kExThreads / 64>(s, s_wave);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = all;
 }
 
 // sorted run j: source bytes from run_src[j] on -> output bytes [run_dst[j], run_dst[j + 1]); run_dst[n_runs] = the output's bytes
 __global__ __launch_bounds__(kExThreads) void k_sp_dst_write(const uint32_t* __restrict__ vals, const uint64_t* __restrict__ pre, const uint64_t* __restrict__ src,
                                                              uint32_t cap, uint64_t n_tiles, const ExSum* __restrict__ base, uint64_t* __restrict__ run_src,
                                                              uint64_t* __restrict__ run_dst, unsigned long long* __restrict__ words) {
-    __shared__ unsigned long long s_a[kExThreads / 64];
-    __shared__ uint32_t s_b[kExThreads / 64];
+    __shared__ unsigned long long s_wave[kExThreads / 64];
     unsigned long long len[kExRecsPerLane];
     const uint32_t n_runs = sp_live_runs(words, cap);
     const unsigned long long nl = words[kExNl];
     const uint64_t j0 = ((uint64_t)blockIdx.x * kExThreads + threadIdx.x) * kExRecsPerLane;
     const unsigned long long sum = sp_lens(vals, pre, n_runs, nl, j0, len);
-    unsigned long long at;
-    uint32_t unused;
-    sp_block_scan(sum, 0u, s_a, s_b, &at, &unused);
+    unsigned long long at = block_prefix_excl<kExThreads / 64>(sum, threadIdx.x & 63u, threadIdx.x >> 6, s_wave);
     if (blockIdx.x < n_tiles) {
         at += base[blockIdx.x].a;
 #pragma unroll

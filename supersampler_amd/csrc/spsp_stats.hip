@@ -672,14 +672,8 @@ __global__ __launch_bounds__(kSegThreads) void k_seg_scan(const uint8_t* __restr
         uint32_t v[PER], sum = 0;
 #pragma unroll
         for (uint32_t u = 0; u < PER; ++u) { v[u] = s_cnt[t * PER + u]; sum += v[u]; }
-        uint32_t x = sum;
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t y = __shfl_up(x, dd); if (lane >= (uint32_t)dd) x += y; }
-        if (lane == 63) s_wave[t >> 6] = x;
-        __syncthreads();
-        uint32_t pre = 0, all = 0;
-        for (uint32_t w = 0; w < kSegThreads / 64; ++w) { if (w < (t >> 6)) pre += s_wave[w]; all += s_wave[w]; }
-        uint32_t run = pre + x - sum;
+        uint32_t all;
+        uint32_t run = block_prefix_excl<kSegThreads / 64>(sum, lane, t >> 6, s_wave, all);
 #pragma unroll
         for (uint32_t u = 0; u < PER; ++u) { s_cnt[t * PER + u] = run; run += v[u]; }
         if (!EMIT) { if (t == 0) tile_count[blockIdx.x] = all; return; }

@@ -4,7 +4,7 @@
 //
 // Counts, over tiles of 2 048 records (a lane walks eight):
 //   k_wn_tiles    per tile the windows and the expanded bases of its records; offsets that decrease or leave the bases raise the flag
-//   k_wn_scan     one workgroup: the exclusive 64-bit scan of the tiles' two sums, and the totals
+//   k_scan_items<WnSum>  one workgroup: the exclusive 64-bit scan of the tiles' two sums, and the totals (spsp_device.h)
 //   k_wn_records  per tile: first_win[r] and the output start of every record, and the closing entries
 // The host waits once, for the totals and first_win: they size everything behind.
 //   k_wn_windows  a lane per WINDOW: its record by binary search over first_win, then its output offset and its source start.  A
@@ -28,7 +28,6 @@ namespace spsp {
 namespace {
 
 enum WnWord { kWnBases = 0, kWnWins = 1, kWnBad = 2, kWnWords = 4 };   // the call's words on the device (64 bits each)
-struct WnSum { unsigned long long bases, wins; };
 static_assert(kWnStores * kWnThreads * 16 == kWnStretchBytes && kWnStretchPacked % 64 == 0 && kWnStretch % 16 == 0, "a stretch is whole 16-byte stores");
 
 // the records r0 .. r0 + 7 of one lane: their windows and expanded bases; on_rec(r, wins_before, bases_before) per record
@@ -56,84 +55,33 @@ __device__ __forceinline__ void wn_walk(const uint64_t* __restrict__ off, uint32
 
 __global__ __launch_bounds__(kWnThreads) void k_wn_tiles(const uint64_t* __restrict__ off, uint32_t n_rec, uint64_t n_bases, uint32_t k, uint64_t S,
                                                          WnSum* __restrict__ tiles, unsigned long long* __restrict__ words) {
-    __shared__ unsigned long long s_a[kWnThreads / 64], s_b[kWnThreads / 64];
+    __shared__ WnSum s_wave[kWnThreads / 64];
     WnSum s;
     bool bad;
     wn_walk(off, n_rec, n_bases, ((uint64_t)blockIdx.x * kWnThreads + threadIdx.x) * kWnRecsPerLane, k, S, s, bad, [](uint64_t, uint64_t, uint64_t) {});
     if (bad) atomicOr(words + kWnBad, 1ull);
-    const unsigned long long a = wave_sum(s.bases), b = wave_sum(s.wins);
-    if ((threadIdx.x & 63u) == 0u) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        WnSum all{0ull, 0ull};
-        for (uint32_t w = 0; w < kWnThreads / 64; ++w) { all.bases += s_a[w]; all.wins += s_b[w]; }
-        tiles[blockIdx.x] = all;
-    }
+    const WnSum all = block_sum<kWnThreads / 64>(s, s_wave);
+    if (threadIdx.x == 0) tiles[blockIdx.x] = all;
 }
 
-// one workgroup: out[i] = the sums of in[0 .. i); words[kWnBases], words[kWnWins] = the totals.  A lane owns four consecutive items
-__global__ __launch_bounds__(1024) void k_wn_scan(const WnSum* __restrict__ in, uint64_t n_items, WnSum* __restrict__ out, unsigned long long* __restrict__ words) {
-    __shared__ unsigned long long s_a[16], s_b[16];
-    __shared__ unsigned long long c_a, c_b;
-    const uint32_t t = threadIdx.x, lane = t & 63u, wid = t >> 6;
-    if (t == 0) { c_a = 0ull; c_b = 0ull; }
-    __syncthreads();
-    for (uint64_t base = 0; base < n_items; base += 4096ull) {   // (uniform)
-        const uint64_t i0 = base + (uint64_t)t * 4ull;
-        WnSum me[4];
-        unsigned long long a = 0, b = 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            me[u] = i0 + u < n_items ? in[i0 + u] : WnSum{0ull, 0ull};
-            a += me[u].bases; b += me[u].wins;
-        }
-        unsigned long long ax = a, bx = b;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long ay = __shfl_up(ax, d), by = __shfl_up(bx, d);
-            if (lane >= (uint32_t)d) { ax += ay; bx += by; }
-        }
-        if (lane == 63u) { s_a[wid] = ax; s_b[wid] = bx; }
-        __syncthreads();
-        unsigned long long ap = c_a, bp = c_b, aall = 0, ball = 0;
-        for (uint32_t w = 0; w < 16; ++w) {
-            if (w < wid) { ap += s_a[w]; bp += s_b[w]; }
-            aall += s_a[w]; ball += s_b[w];
-        }
-        ap += ax - a; bp += bx - b;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (i0 + u < n_items) out[i0 + u] = WnSum{ap, bp};
-            ap += me[u].bases; bp += me[u].wins;
-        }
-        __syncthreads();
-        if (t == 0) { c_a += aall; c_b += ball; }
-        __syncthreads();
-    }
-    if (t == 0) { words[kWnBases] = c_a; words[kWnWins] = c_b; }
-}
+// what the item scan does with a WnSum total
+struct WnTotals {
+    unsigned long long* words;
+    __device__ void operator()(const WnSum& s) const { words[kWnBases] = s.bases; words[kWnWins] = s.wins; }
+};
 
 // rec_first[r], rec_out[r]: record r's first window and where its windows' bases begin in the output; [n_rec]: the totals
 __global__ __launch_bounds__(kWnThreads) void k_wn_records(const uint64_t* __restrict__ off, uint32_t n_rec, uint64_t n_bases, uint32_t k, uint64_t S, uint64_t n_tiles,
                                                            const WnSum* __restrict__ base, const unsigned long long* __restrict__ words,
                                                            uint32_t* __restrict__ rec_first, uint64_t* __restrict__ rec_out) {
-    __shared__ unsigned long long s_a[kWnThreads / 64], s_b[kWnThreads / 64];
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    __shared__ WnSum s_wave[kWnThreads / 64];
     const uint64_t r0 = ((uint64_t)blockIdx.x * kWnThreads + threadIdx.x) * kWnRecsPerLane;
     WnSum s;
     bool bad;
     wn_walk(off, n_rec, n_bases, r0, k, S, s, bad, [](uint64_t, uint64_t, uint64_t) {});
-    unsigned long long ax = s.bases, bx = s.wins;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long ay = __shfl_up(ax, d), by = __shfl_up(bx, d);
-        if (lane >= (uint32_t)d) { ax += ay; bx += by; }
-    }
-    if (lane == 63u) { s_a[wid] = ax; s_b[wid] = bx; }
-    __syncthreads();
+    const WnSum before = block_prefix_excl<kWnThreads / 64>(s, threadIdx.x & 63u, threadIdx.x >> 6, s_wave);
     if (blockIdx.x < n_tiles) {
-        unsigned long long a0 = base[blockIdx.x].bases + ax - s.bases, b0 = base[blockIdx.x].wins + bx - s.wins;
-        for (uint32_t w = 0; w < wid; ++w) { a0 += s_a[w]; b0 += s_b[w]; }
+        const unsigned long long a0 = base[blockIdx.x].bases + before.bases, b0 = base[blockIdx.x].wins + before.wins;
         WnSum again;
         wn_walk(off, n_rec, n_bases, r0, k, S, again, bad, [=](uint64_t r, uint64_t wins, uint64_t bases) { rec_first[r] = (uint32_t)(b0 + wins); rec_out[r] = a0 + bases; });
     }
@@ -276,7 +224,7 @@ int records_windows_impl(spsp_ctx* ctx, const uint8_t* d_bases, uint64_t n_bases
     SPSP_HIP(hipMemsetAsync(words, 0, kWnWords * 8, ctx->stream));
     if ((rc = wn_mark(ctx, 0))) return rc;
     if (n_rtiles) hipLaunchKernelGGL(k_wn_tiles, dim3((uint32_t)n_rtiles), dim3(kWnThreads), 0, ctx->stream, d_rec_off, n_rec, n_bases, k, S, tiles, words);
-    hipLaunchKernelGGL(k_wn_scan, dim3(1), dim3(1024), 0, ctx->stream, (const WnSum*)tiles, n_rtiles, base, words);
+    hipLaunchKernelGGL((k_scan_items<WnSum, WnTotals>), dim3(1), dim3(1024), 0, ctx->stream, (const WnSum*)tiles, n_rtiles, base, WnTotals{words});
     hipLaunchKernelGGL(k_wn_records, dim3((uint32_t)std::max<uint64_t>(n_rtiles, 1)), dim3(kWnThreads), 0, ctx->stream, d_rec_off, n_rec, n_bases, k, S, n_rtiles,
                        (const WnSum*)base, (const unsigned long long*)words, rec_first, rec_out);
     SPSP_HIP(hipGetLastError());

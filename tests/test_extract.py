@@ -423,6 +423,29 @@ def test_one_record_per_tile_across_the_scans_lanes_and_rounds(ctx, tiles):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("tiles", [4095, 4096, 4097, 8193])
+def test_starts_behind_the_item_scans_rounds(ctx, tiles):
+    """the tiles' sums are scanned by one workgroup, 4 096 tiles a round, the rounds in front carried in LDS: a carry dropped or
+    doubled shifts every start behind tile 4096 (8192: the third round).  One long sequence line with short records planted in
+    the tiles on both sides of the rounds' seams; the starts against numpy ('>' at offset 0 or behind a newline)"""
+    T, _ = plan()
+    n = tiles * T + 777                                    # whole tiles and a partial last one
+    a = np.full(n, ord("A"), dtype=np.uint8)
+    a[:3] = np.frombuffer(b">h\n", dtype=np.uint8)
+    planted = b"\n>r\nAC\n>s\nG\n>t\n"
+    at = sorted({t for t in (0, 4095, 4096, 4097, 8191, 8192, tiles) if t <= tiles})
+    for t in at:
+        p = t * T + 100
+        a[p:p + len(planted)] = np.frombuffer(planted, dtype=np.uint8)
+    want = np.flatnonzero((a == ord(">")) & np.concatenate(([True], a[:-1] == ord("\n")))).astype(np.uint64)
+    assert len(want) == 1 + 3 * len(at) and sorted(set((want[1:] // T).tolist())) == at
+    d = Dev(a.tobytes())
+    d_begin, n_rec = ctx.records_extents_device(d.ptr, d.n)
+    assert n_rec == len(want)
+    assert np.array_equal(ctx.to_host(d_begin, n_rec + 1, np.uint64), np.concatenate((want, np.array([n], dtype=np.uint64))))
+
+
+@pytest.mark.gpu
 def test_the_copy_at_every_alignment_difference(ctx):
     """a dropped first record of 1 .. 16 bytes moves every kept byte by as many: all sixteen differences of source and output
     alignment (16: none)"""

@@ -399,6 +399,33 @@ def test_record_counts_around_the_counting_tile(ctx):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n_rec", [4095 * 2048, 4096 * 2048 + 1, 2 * 4096 * 2048 + 5])
+def test_records_behind_the_item_scans_rounds(ctx, n_rec):
+    """the record tiles' sums (2 048 records a tile) are scanned by one workgroup, 4 096 tiles a round, the rounds in front carried in
+    LDS: a carry dropped or doubled shifts first_win and the output offsets of every record behind record 4 096 x 2 048.  Empty
+    records, one window each, but a few of two windows and more on both sides of the rounds' seams; their counts are the host rule's"""
+    import torch
+    k, W, R = 31, 64, 4096 * 2048
+    at = sorted({r for r in (5, R - 1, R, 2 * R - 1, 2 * R, n_rec - 1) if r < n_rec})
+    lens = [65 + 70 * i for i in range(len(at))]
+    few_first, few_off = sp.records_windows(offsets(lens), k, W)
+    few = np.diff(few_first.astype(np.int64))
+    assert (few >= 2).all()
+    L = np.zeros(n_rec, dtype=np.int64)
+    L[at] = lens
+    n_win = np.ones(n_rec, dtype=np.int64)
+    n_win[at] = few
+    off = np.concatenate(([0], np.cumsum(L))).astype(np.uint64)
+    d = torch.from_numpy(np.concatenate([np.frombuffer(random_bases(np.random.default_rng(n_rec), int(off[-1])), np.uint8), np.zeros(HALO, np.uint8)])).cuda()
+    d_off = torch.from_numpy(off.view(np.int64)).cuda()
+    torch.cuda.synchronize()
+    out, n_out, d_win, first, n_windows = ctx.records_windows_device(d.data_ptr(), int(off[-1]), d_off.data_ptr(), n_rec, k, W)
+    want_first = np.concatenate(([0], np.cumsum(n_win)))
+    assert n_windows == int(want_first[-1]) and np.array_equal(first, want_first)
+    assert n_out == int((L + (n_win - 1) * (k - 1)).sum()) == int(few_off[-1])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("packed", [False, True])
 def test_one_record_of_many_stretches_among_one_window_records(ctx, packed):
     stretch = sp.windows_plan()["stretch_bases_packed" if packed else "stretch_bases"]
