@@ -204,6 +204,20 @@ int spsp_wait_stream(spsp_ctx* waiter, spsp_ctx* other);
  * when one m-mer occurs twice in a window (`dump`, :391-398).  Not needed for the sketch: a separate pass. */
 int spsp_count_superkmers_device(spsp_ctx* ctx, const spsp_params* p, const void* d_bases, uint64_t n_bases,
                                  const void* d_rec_off, uint32_t n_rec, uint64_t* total_superkmers);
+/* What the last scan collected on the context (spsp_scan_device, spsp_scan_device_end and every call that scans through
+ * them) and the last super-k-mer count did: both have two forms that give the same numbers, and a caller or a test that has
+ * to know which one answered reads it here.  Read-only; nothing is launched or waited for.
+ *   counts[0]  the form that gave the last collected scan's stream: 0 none yet, or an empty call; 1 the scan by segments
+ *              (thresholds of 0.8 x 2^64 and more, -s 1); 2 the product scan (dense + sparse passes); 3 the product scan after
+ *              the scan by segments counted and reported a chain that it did not finish (it left its tile's halo and the walk
+ *              behind it was refused or ran out)
+ *   counts[1]  the number of such unfinished chains that scan reported (0 unless counts[0] is 1 or 3)
+ *   counts[2]  the form that gave the last spsp_count_superkmers_device total (also the SPSP_SCAN_STATS pass of the sketch
+ *              calls): 0 none yet, or a call without a k-mer; 1 the count by segments and its tail kernel; 2 the chunk kernels
+ *              from the start; 3 the chunk kernels after the count by segments handed over (more chains left their halos than
+ *              the tail kernel has lanes)
+ *   counts[3]  the chains that left their tile's halo in that count (0 when counts[2] is 0 or 2) */
+int spsp_stats_counts(spsp_ctx* ctx, uint32_t* counts /* 4 */);
 
 /* Dense stage only (hash + threshold + hit bitmap), for the roofline
  * measurement: returns the number of m-mers with hash <= threshold. */

@@ -162,7 +162,7 @@ SUPERKMER_DTYPE = np.dtype([("rec", "<u4"), ("minimizer", "<u4"), ("start", "<u8
 ABI_SYMBOLS = [
     "spsp_device_count", "spsp_create", "spsp_destroy", "spsp_last_error", "spsp_version", "spsp_free", "spsp_copy_to_host",
     "spsp_stream_create_cus", "spsp_stream_destroy", "spsp_set_cu_count", "spsp_pack_bases_device",
-    "spsp_timing_enable", "spsp_timing_sample", "spsp_timing_read", "spsp_threshold_host", "spsp_scan", "spsp_scan_device", "spsp_scan_device_begin", "spsp_scan_device_end", "spsp_scan_tail_stream", "spsp_wait_dense", "spsp_wait_stream", "spsp_scan_hits_device", "spsp_count_superkmers_device", "spsp_compare",
+    "spsp_timing_enable", "spsp_timing_sample", "spsp_timing_read", "spsp_threshold_host", "spsp_scan", "spsp_scan_device", "spsp_scan_device_begin", "spsp_scan_device_end", "spsp_scan_tail_stream", "spsp_wait_dense", "spsp_wait_stream", "spsp_scan_hits_device", "spsp_count_superkmers_device", "spsp_stats_counts", "spsp_compare",
     "spsp_compare_device", "spsp_slot_bytes", "spsp_partition_keys_device", "spsp_compare_slots_device", "spsp_compare_device_begin", "spsp_compare_slots_device_begin", "spsp_compare_end", "spsp_fasta_clean_host", "spsp_fasta_clean_device", "spsp_fasta_clean_packed_device", "spsp_fastq_clean_device", "spsp_fastq_clean_packed_device", "spsp_ingest_batch", "spsp_sketch_text", "spsp_sketch_build_host", "spsp_sketch_build_device", "spsp_sketch_parse_host", "spsp_sketch_decode_device", "spsp_sketch_keys_device", "spsp_sketch_keys_device_begin", "spsp_sketch_keys_device_end", "spsp_sketch_keys_big_genomes", "spsp_scan_output_wait", "spsp_compare_keys_unordered", "spsp_compare_forget", "spsp_sketch_chain_host",
     "spsp_csv_host", "spsp_csv_cells_host", "spsp_csv_cells_gz_host", "spsp_sort_csv_host", "spsp_read_file_host", "spsp_write_gz_host", "spsp_sketch_file", "spsp_compare_files", "spsp_compare_files_chatty", "spsp_stage_times_read", "spsp_measure_hbm_device", "spsp_sketch_files", "spsp_sketch_files_multi", "spsp_sketch_files_release", "spsp_compare_files_multi", "spsp_matrix_cells_device", "spsp_matrix_add_cells_device", "spsp_compare_cells_device", "spsp_compare_slots_cells_device",
     "spsp_keys_downsample_device", "spsp_sketch_header_host", "spsp_sketch_downsample_host", "spsp_compare_files_rate", "spsp_compare_files_multi_rate",
@@ -293,6 +293,8 @@ def lib():
     L.spsp_sketch_decode_device.argtypes = [vp, P(cp), P(u64), u32, P(u32), P(u32), P(vp), P(vp), P(vp), P(u64)]
     L.spsp_count_superkmers_device.restype = i32
     L.spsp_count_superkmers_device.argtypes = [vp, P(Params), vp, u64, vp, u32, P(u64)]
+    L.spsp_stats_counts.restype = i32
+    L.spsp_stats_counts.argtypes = [vp, P(u32)]
     L.spsp_scan_tail_stream.restype = i32; L.spsp_scan_tail_stream.argtypes = [vp, i32, vp]
     L.spsp_stage_times_read.restype = i32; L.spsp_stage_times_read.argtypes = [vp, P(StageTimes), i32]
     L.spsp_sketch_files.restype = i32
@@ -1514,6 +1516,15 @@ class Context:
         n = C.c_uint64()
         _check(lib().spsp_count_superkmers_device(self._h, C.byref(params), d_bases, n_bases, d_rec_off, n_rec, C.byref(n)))
         return n.value
+
+    def stats_counts(self):
+        """spsp_stats_counts: which form answered -> dict(scan_form, scan_left: the last collected scan (0 none or empty, 1 by segments,
+        2 the product scan, 3 the product scan after the segment count left a chain unfinished) and the chains it reported;
+        count_form, count_chains: the last super-k-mer count (1 by segments, 2 the chunk kernels, 3 the chunk kernels after a
+        hand-over) and the chains that left their tile's halo)"""
+        counts = (C.c_uint32 * 4)()
+        _check(lib().spsp_stats_counts(self._h, counts))
+        return dict(zip(("scan_form", "scan_left", "count_form", "count_chains"), (int(c) for c in counts)))
 
     def clean_fasta_device(self, d_text, n_text):
         """raw FASTA text in HBM -> (d_bases, n_bases, d_rec_off, n_rec), context-owned device buffers."""

@@ -344,6 +344,10 @@ struct spsp_ctx {
     std::vector<hipEvent_t> pf_events;   // while timing is on: around the start, every pick and walk of a batch, and the reduction
     double pf_ms[4] = {};                // ... their milliseconds since spsp_profile_stage_ms last read them: start, picks, walks, reduction
     uint32_t pf_last[3] = {};            // the last call's rounds queued, rows and host waits (spsp_profile_counts hands them out)
+    // which form answered (spsp_stats_counts hands them out): the last collected scan's form (0 none or empty, 1 by segments, 2 the
+    // product scan, 3 the product scan after the segment count left a chain unfinished) and its kHsSegLeftTile; the last
+    // super-k-mer count's form (1 k_seg_count + k_seg_tail, 2 the chunk kernels from the start, 3 after a hand-over) and its kHsStatChains
+    uint32_t st_last[4] = {};
     // taxonomy (spsp_taxonomy.hip), on the classification's index: the tree (parent | size | ref_node), node(x) per distinct key,
     // the same per index entry where it was asked for.  Its calls work in the classification's per-call arrays above
     spsp::DevBuf tx_tree, tx_key_node, tx_entry_node;

@@ -1855,6 +1855,8 @@ int scan_end_impl(spsp_ctx* ctx, spsp_superkmer** d_out, uint64_t* n_out) {
     *d_out = nullptr; *n_out = 0;
     if (!J.pending) { set_error("no scan is pending on this context"); return SPSP_ERR_ARG; }
     J.pending = false;
+    ctx->st_last[0] = J.empty ? 0u : J.segments ? 1u : 2u;     // (spsp_stats_counts)
+    ctx->st_last[1] = 0;
     if (J.empty) return SPSP_OK;
     static const char* dbg_out = getenv("SPSP_DEBUG_OUT_CAP");
     static const char* dbg_budget = getenv("SPSP_DEBUG_LIST_BUDGET");   // test hook: bytes the grown hit lists may take
@@ -1863,6 +1865,7 @@ int scan_end_impl(spsp_ctx* ctx, spsp_superkmer** d_out, uint64_t* n_out) {
         SPSP_HIP(hipEventSynchronize(ctx->scan_done));
         const uint64_t n_em = (uint32_t)ctx->h_scalar[kHsSegEmitted];
         const uint32_t left_halo = (uint32_t)ctx->h_scalar[kHsSegLeftTile];
+        ctx->st_last[1] = left_halo;
         if (left_halo == 0) {
             if (n_em == 0) return SPSP_OK;
             if ((rc = ctx->scan_tmp.reserve((size_t)n_em * sizeof(spsp_superkmer) + 64))) return rc;
@@ -1875,6 +1878,7 @@ int scan_end_impl(spsp_ctx* ctx, spsp_superkmer** d_out, uint64_t* n_out) {
         }
         // a chain left its tile's halo (a long run without a reset: a homopolymer, a short-period repeat): the product scan
         J.segments = false;
+        ctx->st_last[0] = 3;
         if ((rc = scan_enqueue(ctx))) return rc;
     }
     for (int attempt = 0; attempt < 5; ++attempt) {

@@ -720,6 +720,7 @@ int count_superkmers_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_
                           uint32_t n_rec, uint64_t* total, bool packed, uint64_t base0, const uint32_t* h_file_rec, uint32_t n_files) {
     if (!h_file_rec) n_files = 1;
     for (uint32_t f = 0; f < n_files; ++f) total[f] = 0;
+    ctx->st_last[2] = ctx->st_last[3] = 0;                     // (spsp_stats_counts: 0 for a call that launches nothing)
     int rc = check_params(p);
     if (rc) return rc;
     if (n_rec == 0 || n_bases < p->k || n_files == 0) return SPSP_OK;
@@ -752,13 +753,16 @@ int count_superkmers_impl(spsp_ctx* ctx, const spsp_params* p, const uint8_t* d_
         SPSP_HIP(hipMemcpyAsync(back.data(), d_total, (size_t)n_files * 8, hipMemcpyDeviceToHost, ctx->stream));
         SPSP_HIP(hipMemcpyAsync(ctx->h_scalar + kHsStatChains, d_over_n, 4, hipMemcpyDeviceToHost, ctx->stream));
         SPSP_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->st_last[3] = (uint32_t)ctx->h_scalar[kHsStatChains];
         const uint32_t tail_lanes = dbg_stats && dbg_stats[0] == 't' ? 1u : kSegOverCap / 64;   // ("tiny": the hand-over to the chunk kernels, for tests)
         if ((uint32_t)ctx->h_scalar[kHsStatChains] <= tail_lanes) {          // (every chain handed on had its lane)
             for (uint32_t f = 0; f < n_files; ++f) total[f] = back[f];
+            ctx->st_last[2] = 1;
             return SPSP_OK;
         }
         SPSP_HIP(hipMemsetAsync(d_total, 0, (size_t)n_files * 8, ctx->stream));   // more long chains than lanes: the chunk kernels, from zero
-    }
+        ctx->st_last[2] = 3;
+    } else ctx->st_last[2] = 2;
     const uint32_t w = p->k - p->m + 1;
     const uint32_t lookback = 8 * w < 64 ? 64 : 8 * w;
     const uint32_t blocks = (uint32_t)((n_chunks + kStatThreads - 1) / kStatThreads);
@@ -818,4 +822,10 @@ extern "C" int spsp_count_superkmers_device(spsp_ctx* ctx, const spsp_params* p,
     if (!ctx || !p || !total_superkmers) { set_error("NULL argument"); return SPSP_ERR_ARG; }
     SPSP_HIP(hipSetDevice(ctx->device));
     return count_superkmers_impl(ctx, p, (const uint8_t*)d_bases, n_bases, (const uint64_t*)d_rec_off, n_rec, total_superkmers);
+}
+
+extern "C" int spsp_stats_counts(spsp_ctx* ctx, uint32_t* counts) {
+    if (!ctx || !counts) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    for (int i = 0; i < 4; ++i) counts[i] = ctx->st_last[i];
+    return SPSP_OK;
 }

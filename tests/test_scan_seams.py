@@ -39,7 +39,8 @@ What a wrong kernel would look like, and which case shows it:
         off by one: sparse
     a cached table or a learned capacity of an earlier call used by this one: test_one_context_over_many_calls
 
-The scan by segments, key extraction and ingest are not covered here; no test reads an environment hook."""
+The scan by segments (spsp_stats.hip: k_seg_scan, and the super-k-mer count beside it) has its seams in
+tests/test_segment_seams.py; no test of this file reads an environment hook."""
 import functools
 
 import numpy as np
