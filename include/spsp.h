@@ -1768,6 +1768,81 @@ int spsp_taxonomy_files_windows(spsp_ctx* ctx, const char* const* index_paths, u
                                 const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
                                 spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic);
 
+/* ------------------------------------------------- segments as sequence ---- */
+/* What follows the windows (not in the reference): single stray windows absorbed into the stretch around them, and chosen
+ * segments written out as FASTA from the cleaned bases the side context still holds.  Coordinates count kept BASES, as above.
+ * SMOOTHING.  q, an integer 0 .. 0x7fffffff; 0 changes nothing.  The RUNS of a record are the maximal runs of equal calls among
+ *   its windows (the segments of the unsmoothed calls; "none" is a call like any other).  A run is STRAY when it has at most q
+ *   windows, is neither the first nor the last run of its record, the runs on its two sides carry the same call as each other,
+ *   and each of those two has MORE than q windows.  Every stray run is decided on the unsmoothed runs (two stray runs are never
+ *   adjacent: a stray run's neighbours are longer than q), so the result is a property of the call vector and nothing is iterated.
+ *   A stray run's windows take their neighbours' call and their support becomes 0; keys and hit_keys stay.  Segments and mosaic
+ *   are what spsp_windows_segments_host makes of the smoothed vectors: `windows` counts the absorbed windows, `support` only the
+ *   windows that made the call themselves.  The windows' rows a driver hands out stay unsmoothed.
+ * SELECTION.  A word: all (every segment), called (with a call), none (without), call=<b> (whose call is b), not=<b> (whose call
+ *   is not b, the uncalled included), major (whose call is their record's mosaic major), minor (with a call other than none that
+ *   differs from their record's major).  b is the number the segments CSV prints, b < n_bins - 1.  A record without a major
+ *   selects nothing under major or minor.  A segment is written only if end - begin >= max(1, min_bases).
+ * TEXT.  <prefix>_segments.fa.gz (plain <prefix>_segments.fa where gzip is off): one FASTA record per selected segment in the
+ *   segments CSV's order.  Header: '>' name ':' begin + 1 '-' end ' ' call_name '\n' (1-based, inclusive; call_name as the CSV
+ *   prints it).  Body: the record's kept bases [begin, end), upper case ("ACTG"[code] of the packed form), SPSP_SEGMENTS_LINE
+ *   bases a line, every line ended by '\n': n bases are n + ceil(n / 80) bytes.  FASTQ input gives FASTA: the cleaned bases carry
+ *   no qualities. */
+#define SPSP_SEGMENTS_LINE 80u
+/* What the writer cuts at (either pointer may be NULL): the bases of a line, the output bytes one workgroup owns. */
+int spsp_segments_plan_host(uint32_t* line_bases, uint32_t* stretch_bytes);
+/* The smoothing, in place, over the windows of n_rec records (first_win: n_rec + 1).  *n_changed (may be NULL): the windows whose
+ * call changed.  SPSP_ERR_ARG naming the record for a call >= n_bins or a first_win that decreases; nothing is changed then. */
+int spsp_windows_smooth_host(uint32_t* call, uint32_t* support, const uint32_t* first_win /* n_rec + 1 */, uint32_t n_rec, uint32_t n_bins, uint32_t q,
+                             uint64_t* n_changed);
+/* Only the refusals of a selection: `what` is a word, or the command line's <word>:<min_bases> (a decimal below 2^63).  n_bins:
+ * 0 while the bins are not counted yet (then <b> is only held to be a decimal number), else b < n_bins - 1 is asked.  taxonomy:
+ * the bins are nodes (for the refusal's words only). */
+int spsp_segments_word_check_host(const char* what, int taxonomy, uint32_t n_bins);
+/* keep[i] = 1 where segment i is selected and has at least max(1, min_bases) bases, else 0; *n_kept and *n_bases (may be NULL):
+ * their number and their bases.  mosaic: the records' rows (major and minor read `major`).  SPSP_ERR_ARG for a refused word, a
+ * min_bases of 2^63 or more, a segment whose record or call is out of range or whose end lies in front of its begin. */
+int spsp_segments_select_host(const spsp_segment_row* segments, uint64_t n_segments, const spsp_mosaic_row* mosaic, uint32_t n_rec, uint32_t n_bins, const char* what,
+                              uint64_t min_bases, uint8_t* keep /* n_segments */, uint64_t* n_kept, uint64_t* n_bases);
+/* The text as plain loops over ASCII bases: the yardstick of the device writer.  bases: the cleaned bases of all records (n_bases
+ * of them, written upper-cased), rec_off: n_rec + 1; keep: NULL (every segment) or a flag per segment; the names as the CSV
+ * writers take them.  A segment that leaves its record is SPSP_ERR_ARG.  *text is released with spsp_free(). */
+int spsp_segments_fasta_host(const uint8_t* bases, uint64_t n_bases, const uint64_t* rec_off /* n_rec + 1 */, uint32_t n_rec, const spsp_segment_row* segments,
+                             uint64_t n_segments, const uint8_t* keep, const char* const* record_names, const char* const* call_names, const char* last_name,
+                             uint32_t n_bins, char** text, uint64_t* len);
+/* The writer on the device.  d_bases: the cleaned bases in HBM in either form the ingest writes (packed != 0: 2-bit words), 16-byte
+ * aligned, with the readable bytes behind that spsp_records_windows_device asks for.  Segment i is the h_len[i] >= 1 bases from
+ * global base offset h_src[i] on, behind the header h_headers[h_hdr_off[i] .. h_hdr_off[i + 1]) (the host makes the headers: only
+ * it holds the names).  The host prefix-sums header and body lengths; ONE upload carries the three tables and the headers; ONE
+ * launch, balanced by OUTPUT: a workgroup owns 16 KiB of the text, finds the segments that cross it by two binary searches, keeps
+ * their slice of the tables in LDS, and every lane writes whole 16-byte-aligned 16-byte stores.  A store inside one body holds
+ * at most one newline besides the body's last: 16 (or 15) source bases by two aligned loads and a byte shift (ASCII) or a funnel
+ * shift of two dwords expanded four letters at a time (packed), the newline put in by one byte permute; byte by byte where a
+ * store holds header bytes, spans segments or ends the text.  No host wait: *d_out (the context's, valid until its next call,
+ * whole stretches, zero behind *n_out) is ready behind the context's stream.  SPSP_ERR_ARG before any launch for a segment that
+ * leaves the bases or has no bases, and for header offsets that decrease. */
+int spsp_segments_write_device(spsp_ctx* ctx, const void* d_bases, uint64_t n_bases, int packed, const uint64_t* h_src /* n_seg */, const uint64_t* h_len /* n_seg */,
+                               const uint8_t* h_headers, const uint64_t* h_hdr_off /* n_seg + 1 */, uint64_t n_seg, void** d_out, uint64_t* n_out);
+/* While the context's timing is on a write records events around its launch; this reads the milliseconds added up since the last
+ * read and clears them (it waits for the context's stream). */
+int spsp_segments_stage_ms(spsp_ctx* ctx, double* ms /* 1: write */);
+/* The whole-file drivers: the arguments of the _windows entries plus smooth (q), segments_what (NULL: no text is written),
+ * segments_min and gz, and the outs n_changed (windows whose call the smoothing changed), n_written (segments written) and
+ * bytes_out (the text's bytes before gzip).  Behind the last batch the calls are smoothed, segments and mosaic made, the segments
+ * selected and written on the second context from the bases it still holds; every text is made before any file is written.  A
+ * refused word is refused before any file is read (call=<b> / not=<b>: once the bins are counted).  The two CSVs of a run with
+ * a word and smooth == 0 are those of the run without.  The _windows entries are these with smooth = 0 and no word. */
+int spsp_classify_files_segments(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                 uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window, const char* what,
+                                 spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
+                                 spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth, const char* segments_what,
+                                 uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out);
+int spsp_taxonomy_files_segments(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                 uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
+                                 const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
+                                 spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth, const char* segments_what,
+                                 uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out);
+
 #ifdef __cplusplus
 }
 #endif

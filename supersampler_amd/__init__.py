@@ -187,6 +187,8 @@ ABI_SYMBOLS = [
     "spsp_pairs_names_host", "spsp_union_plan_host", "spsp_records_union_device", "spsp_union_stage_ms", "spsp_classify_files_paired", "spsp_taxonomy_files_paired",
     "spsp_windows_plan_host", "spsp_records_windows_host", "spsp_windows_expand_host", "spsp_windows_segments_host", "spsp_segments_csv_host", "spsp_mosaic_csv_host",
     "spsp_windows_word_check_host", "spsp_records_windows_device", "spsp_windows_stage_ms", "spsp_classify_files_windows", "spsp_taxonomy_files_windows",
+    "spsp_segments_plan_host", "spsp_windows_smooth_host", "spsp_segments_word_check_host", "spsp_segments_select_host", "spsp_segments_fasta_host",
+    "spsp_segments_write_device", "spsp_segments_stage_ms", "spsp_classify_files_segments", "spsp_taxonomy_files_segments",
 ]
 
 _lib = None
@@ -538,6 +540,26 @@ def lib():
                                                   P(u64), P(vp)]
         L.spsp_taxonomy_files_windows.restype = i32
         L.spsp_taxonomy_files_windows.argtypes = [vp, P(cp), u32, cp, cp, u32, u32, u32, i32, cp, i32, dbl, u64, cp, P(vp), P(u64), P(vp), P(u64), P(vp), P(u64), P(vp)]
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_segments_write_device"):
+        L.spsp_segments_plan_host.restype = i32
+        L.spsp_segments_plan_host.argtypes = [P(u32), P(u32)]
+        L.spsp_windows_smooth_host.restype = i32
+        L.spsp_windows_smooth_host.argtypes = [vp, vp, vp, u32, u32, u32, P(u64)]
+        L.spsp_segments_word_check_host.restype = i32
+        L.spsp_segments_word_check_host.argtypes = [cp, i32, u32]
+        L.spsp_segments_select_host.restype = i32
+        L.spsp_segments_select_host.argtypes = [vp, u64, vp, u32, u32, cp, u64, vp, P(u64), P(u64)]
+        L.spsp_segments_fasta_host.restype = i32
+        L.spsp_segments_fasta_host.argtypes = [vp, u64, vp, u32, vp, u64, vp, P(cp), P(cp), cp, u32, P(vp), P(u64)]
+        L.spsp_segments_write_device.restype = i32
+        L.spsp_segments_write_device.argtypes = [vp, vp, u64, i32, vp, vp, vp, vp, u64, P(vp), P(u64)]
+        L.spsp_segments_stage_ms.restype = i32
+        L.spsp_segments_stage_ms.argtypes = [vp, P(dbl)]
+        tail = [u32, cp, u64, i32, P(u64), P(u64), P(u64)]
+        L.spsp_classify_files_segments.restype = i32
+        L.spsp_classify_files_segments.argtypes = L.spsp_classify_files_windows.argtypes + tail
+        L.spsp_taxonomy_files_segments.restype = i32
+        L.spsp_taxonomy_files_segments.argtypes = L.spsp_taxonomy_files_windows.argtypes + tail
     _lib = L
     return L
 
@@ -1195,6 +1217,67 @@ def _windows_result(first, n_rec, seg, n_seg, mos):
     return {"first_win": np.frombuffer(_take(first, (n_rec + 1) * 4), dtype=np.uint32).copy(),
             "segments": np.frombuffer(_take(seg, n_seg * SEGMENT_ROW_DTYPE.itemsize), dtype=SEGMENT_ROW_DTYPE).copy(),
             "mosaic": np.frombuffer(_take(mos, n_rec * MOSAIC_ROW_DTYPE.itemsize), dtype=MOSAIC_ROW_DTYPE).copy()}
+
+
+def segments_plan():
+    """spsp_segments_plan_host: what the segments' writer cuts at -> dict(line_bases, stretch_bytes)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_segments_plan_host(C.byref(a), C.byref(b)))
+    return {"line_bases": a.value, "stretch_bytes": b.value}
+
+
+def windows_smooth(call, support, first_win, n_bins, q):
+    """spsp_windows_smooth_host: a run of at most q windows between two runs of one call, each longer than q windows and in the same
+    record, takes that call and support 0 -> (call, support, n_changed); the arguments stay as they are"""
+    call = np.array(call, dtype=np.uint32)
+    support = np.array(support, dtype=np.uint32)
+    first_win = np.ascontiguousarray(first_win, dtype=np.uint32)
+    if len(first_win) < 1 or len(call) != len(support):
+        raise ValueError("windows_smooth: n_rec + 1 first windows, and one call and one support per window")
+    if len(first_win) > 1 and int(first_win.max()) > len(call):
+        raise ValueError("windows_smooth: first_win names windows that are not there")
+    n = C.c_uint64()
+    _check(lib().spsp_windows_smooth_host(call.ctypes.data if len(call) else None, support.ctypes.data if len(call) else None, first_win.ctypes.data, len(first_win) - 1,
+                                          n_bins, q, C.byref(n)))
+    return call, support, n.value
+
+
+def segments_word_check(what, taxonomy=False, n_bins=0):
+    """spsp_segments_word_check_host: only the refusals of a selection, a word or the command line's <word>:<min_bases>; n_bins: 0, or
+    the bins <b> is held against"""
+    _check(lib().spsp_segments_word_check_host(what.encode(), 1 if taxonomy else 0, n_bins))
+
+
+def segments_select(segments, mosaic, n_bins, what, min_bases=1):
+    """spsp_segments_select_host: -> (keep: np.uint8[n_segments], n_kept, n_bases)"""
+    segments = np.ascontiguousarray(segments, dtype=SEGMENT_ROW_DTYPE)
+    mosaic = np.ascontiguousarray(mosaic, dtype=MOSAIC_ROW_DTYPE)
+    keep = np.zeros(max(len(segments), 1), dtype=np.uint8)
+    n_kept, n_bases = C.c_uint64(), C.c_uint64()
+    _check(lib().spsp_segments_select_host(segments.ctypes.data if len(segments) else None, len(segments), mosaic.ctypes.data if len(mosaic) else None, len(mosaic), n_bins,
+                                           what.encode(), min_bases, keep.ctypes.data, C.byref(n_kept), C.byref(n_bases)))
+    return keep[:len(segments)], n_kept.value, n_bases.value
+
+
+def segments_fasta(bases, rec_off, segments, record_names, call_names, last_name, keep=None):
+    """spsp_segments_fasta_host: the text of <prefix>_segments.fa as plain loops over the ASCII bases of all records -> bytes.  keep:
+    None (every segment) or a flag per segment; call_names: n_bins - 1, last_name: the last bin's"""
+    bases = np.ascontiguousarray(np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else bases, dtype=np.uint8)
+    rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    segments = np.ascontiguousarray(segments, dtype=SEGMENT_ROW_DTYPE)
+    if len(rec_off) < 1 or len(rec_off) - 1 != len(record_names):
+        raise ValueError("segments_fasta: n_rec + 1 offsets and one name per record")
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if len(keep) != len(segments):
+            raise ValueError("segments_fasta: one flag per segment")
+    rn, _a = _paths_array(record_names)
+    cn, _b = _paths_array(call_names)
+    text, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_segments_fasta_host(bases.ctypes.data if len(bases) else None, len(bases), rec_off.ctypes.data, len(rec_off) - 1,
+                                          segments.ctypes.data if len(segments) else None, len(segments), keep.ctypes.data if keep is not None and len(keep) else None,
+                                          rn, cn, last_name.encode(), len(call_names) + 1, C.byref(text), C.byref(n)))
+    return _take(text, n.value)
 
 
 def windows_word_check(what, taxonomy):
@@ -2047,7 +2130,7 @@ class Context:
     union_plan = staticmethod(union_plan)
     pairs_names = staticmethod(pairs_names)
 
-    def _record_files(self, name, head, rest, outs, extract, gz, mates_path, split, window, window_call, default_call):
+    def _record_files(self, name, head, rest, outs, extract, gz, mates_path, split, window, window_call, default_call, smooth=0, segments=None, segments_min=1):
         """the ladder classify_files and taxonomy_files share: the mode's checks, then spsp_<name>_files, _extract, _paired, _split
         or _windows.  head: (ctx, paths, n_ref, records_path), behind which the mates' path goes; rest: the pass's own arguments up
         to rate; outs: the rows' outputs, the count last; default_call: the word a windowed run calls by where window_call is None"""
@@ -2062,10 +2145,19 @@ class Context:
             if extract is not None or split is not None or mates_path is not None:
                 raise ValueError("%s: window is not taken with extract, split or mates_path" % who)
             first, n_rec, seg, n_seg, mos = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_void_p()
-            _check(entry("_windows")(*head, *rest, window, (window_call or default_call).encode(), *refs, C.byref(first), C.byref(n_rec), C.byref(seg), C.byref(n_seg), C.byref(mos)))
+            common = (*head, *rest, window, (window_call or default_call).encode(), *refs, C.byref(first), C.byref(n_rec), C.byref(seg), C.byref(n_seg), C.byref(mos))
+            changed, written, text_bytes = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            if smooth or segments is not None or segments_min != 1:
+                if not 0 <= smooth <= 0x7FFFFFFF or not 0 <= segments_min < 1 << 64:
+                    raise ValueError("%s: smooth is 0 .. 2147483647, segments_min is not negative" % who)
+                _check(entry("_segments")(*common, smooth, None if segments is None else segments.encode(), segments_min, gz, C.byref(changed), C.byref(written),
+                                          C.byref(text_bytes)))
+            else:
+                _check(entry("_windows")(*common))
             self.last_windows = _windows_result(first, n_rec.value, seg, n_seg.value, mos)
-        elif window_call is not None:
-            raise ValueError("%s: window_call needs window" % who)
+            self.last_windows.update(changed=changed.value, written=written.value, bytes_out=text_bytes.value)
+        elif window_call is not None or smooth or segments is not None:
+            raise ValueError("%s: window_call, smooth and segments need window" % who)
         elif split is not None:
             if extract is not None:
                 raise ValueError("%s: split writes every record and extract one subset: one of the two" % who)
@@ -2081,7 +2173,7 @@ class Context:
             self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
 
     def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
-                       split=None, window=None, window_call=None):
+                       split=None, window=None, window_call=None, smooth=0, segments=None, segments_min=1):
         """spsp_classify_files: the sketch files of the references and a FASTA / FASTQ file of records (gzip or plain) ->
         <prefix>_classify.csv.gz, <prefix>_classify_summary.csv.gz and (records, hits[n, top]).  rate: as compare_files (0.0, a
         rate, or "auto"); sketches of different rates need one.  extract: a word (matched, unmatched, best=<j>, listed=<j>) --
@@ -2093,11 +2185,15 @@ class Context:
         self.last_split = dict(bins, records, bytes_out).  Not together with extract.  window: a width -- spsp_classify_files_windows:
         every record is cut into windows of that many bases, the returned rows are the WINDOWS', <prefix>_segments.csv.gz and
         <prefix>_mosaic.csv.gz take the per-record CSVs' place, and self.last_windows = dict(first_win, segments, mosaic);
-        window_call: the call word (best).  Not together with extract, split or mates_path"""
+        window_call: the call word (best).  Not together with extract, split or mates_path.  smooth: q -- with window
+        (spsp_classify_files_segments), a run of at most q windows between two longer runs of one call takes that call.  segments: a
+        word (all, called, none, call=<b>, not=<b>, major, minor) -- the segments it names of at least segments_min bases are written
+        as <prefix>_segments.fa (".gz" appended when gz), one FASTA record <name>:<begin + 1>-<end> each; last_windows gains changed
+        (windows the smoothing changed), written (segments) and bytes_out (the text's bytes)"""
         arr, _alive = _paths_array(paths)
         recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
         self._record_files("classify", (self._h, arr, len(paths), str(records_path).encode()), (top, min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate)),
-                           (recs, hits, n), extract, gz, mates_path, split, window, window_call, "best")
+                           (recs, hits, n), extract, gz, mates_path, split, window, window_call, "best", smooth, segments, segments_min)
         return (np.frombuffer(_take(recs, n.value * CLASSIFY_RECORD_DTYPE.itemsize), dtype=CLASSIFY_RECORD_DTYPE).copy(),
                 np.frombuffer(_take(hits, n.value * top * CLASSIFY_HIT_DTYPE.itemsize), dtype=CLASSIFY_HIT_DTYPE).copy().reshape(n.value, top))
 
@@ -2157,6 +2253,30 @@ class Context:
 
     windows_plan = staticmethod(windows_plan)
 
+    def segments_write_device(self, d_bases, n_bases, src, length, headers, hdr_off, packed=False):
+        """spsp_segments_write_device: the cleaned bases of a text in HBM (ASCII, or with packed the 2-bit words) and per segment its
+        global base offset, its bases and its header (headers[hdr_off[i]:hdr_off[i + 1]]) -> (d_out, n_out): the FASTA text in the
+        context's buffer, queued on its stream (to_host waits), valid until the context's next call"""
+        src = np.ascontiguousarray(src, dtype=np.uint64)
+        length = np.ascontiguousarray(length, dtype=np.uint64)
+        hdr_off = np.ascontiguousarray(hdr_off, dtype=np.uint64)
+        blob = np.frombuffer(bytes(headers), dtype=np.uint8)
+        if len(src) != len(length) or len(hdr_off) != len(src) + 1 or int(hdr_off[-1]) > len(blob):
+            raise ValueError("segments_write_device: one source and one length per segment, n_seg + 1 header offsets inside the headers")
+        out, n_out = C.c_void_p(), C.c_uint64()
+        _check(lib().spsp_segments_write_device(self._h, d_bases, n_bases, 1 if packed else 0, src.ctypes.data if len(src) else None,
+                                                length.ctypes.data if len(src) else None, blob.ctypes.data if len(blob) else None, hdr_off.ctypes.data, len(src),
+                                                C.byref(out), C.byref(n_out)))
+        return out.value, n_out.value
+
+    def segments_stage_ms(self):
+        """spsp_segments_stage_ms: with timing_enable() on, the milliseconds of the segments' writes since the last read -> dict(write)"""
+        ms = (C.c_double * 1)()
+        _check(lib().spsp_segments_stage_ms(self._h, ms))
+        return {"write": ms[0]}
+
+    segments_plan = staticmethod(segments_plan)
+
     def split_stage_ms(self):
         """spsp_split_stage_ms: with timing_enable() on, the milliseconds of the split calls' launches since the last read ->
         dict(starts, runs, order, offsets, copy)"""
@@ -2201,7 +2321,7 @@ class Context:
         return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
 
     def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
-                       split=None, window=None, window_call=None):
+                       split=None, window=None, window_call=None, smooth=0, segments=None, segments_min=1):
         """spsp_taxonomy_files: the sketch files of the references, a FASTA / FASTQ file of records (gzip or plain) and the lineage
         file of the references -> <prefix>_taxonomy.csv.gz, <prefix>_taxonomy_report.csv.gz and the records.  rate: as
         classify_files (0.0, a rate, or "auto"); sketches of different rates need one.  extract: a word (classified, unclassified,
@@ -2209,12 +2329,13 @@ class Context:
         appended when gz) as well; self.last_extract = dict(n_kept, bytes_out).  mates_path: as classify_files
         (spsp_taxonomy_files_paired).  split: a word (taxon, depth=<d>) -- spsp_taxonomy_files_split: every record goes to
         <prefix>_split_<t>.fa or .fq of its node (or _split_unclassified.*), as classify_files; self.last_split.  window,
-        window_call (taxon, depth=<d>): spsp_taxonomy_files_windows, as classify_files; self.last_windows"""
+        window_call (taxon, depth=<d>): spsp_taxonomy_files_windows, as classify_files; self.last_windows.  smooth, segments,
+        segments_min: spsp_taxonomy_files_segments, as classify_files (<b> is a node's number)"""
         arr, _alive = _paths_array(paths)
         recs, n = C.c_void_p(), C.c_uint64()
         self._record_files("taxonomy", (self._h, arr, len(paths), str(records_path).encode()),
                            (str(lineages_path).encode(), min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate)), (recs, n), extract, gz, mates_path, split,
-                           window, window_call, "taxon")
+                           window, window_call, "taxon", smooth, segments, segments_min)
         return np.frombuffer(_take(recs, n.value * TAXONOMY_RECORD_DTYPE.itemsize), dtype=TAXONOMY_RECORD_DTYPE).copy()
 
     def depth_begin(self):

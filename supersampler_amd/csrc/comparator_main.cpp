@@ -135,12 +135,16 @@ int main(int argc, char** argv) {
     bool split = false;
     string window_arg;               // -y <W>[:<word>]: with -X, every record is cut into windows of W bases and called stretch by stretch (not in the reference's option string)
     bool windows = false;
+    long long smooth_q = 0;          // -Q <q>: with -y, stray runs of up to q windows take their neighbours' call (not in the reference's option string)
+    bool smooth = false;
+    string segments_arg;             // -Z <what>[:<min_bases>]: with -y, the segments the word names are written as <prefix>_segments.fa.gz (likewise)
+    bool segments = false;
     vector<string> reads_files;      // -D <reads file> [-D <more> ...] [-W <min_count>]: neither letter is in the reference's option string
     bool dp_min_seen = false;
     long long dp_min_count = 1;
     bool profile = false;            // -B <min_keys>: the profile behind the depth of -D (not in the reference's option string either)
     long long pf_min_keys = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:j:y:")) != -1) {
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:j:y:Q:Z:")) != -1) {
         switch (ch) {
             case 'D': reads_files.push_back(optarg); break;
             case 'W': {
@@ -165,6 +169,14 @@ int main(int argc, char** argv) {
             case 'u': extract_plain = true; break;
             case 'j': split_what = optarg; split = true; break;
             case 'y': window_arg = optarg; windows = true; break;
+            case 'Q': {
+                char* e = nullptr;
+                smooth_q = strtoll(optarg, &e, 10);
+                if (e == optarg || *e || optarg[0] == '+' || smooth_q < 0 || smooth_q > 0x7fffffffll) { cout << "-Q takes the longest stray run that is absorbed, in windows, an integer in 0 .. 2147483647, not '" << optarg << "'" << endl; return 1; }
+                smooth = true;
+                break;
+            }
+            case 'Z': segments_arg = optarg; segments = true; break;
             case 'Y': {
                 char* e = nullptr;
                 cf_top = strtoll(optarg, &e, 10);
@@ -306,7 +318,7 @@ int main(int argc, char** argv) {
     if (split && !classify) { cout << "-j splits the records of -X <records file> into one file per reference or taxon: it needs -X" << endl; return 1; }
     if (split && extract) { cout << "-j writes every record and -F one subset of them: one of the two in a run" << endl; return 1; }
     if (split && spsp_split_word_check_host(split_what.c_str(), taxonomy ? 1 : 0) != SPSP_OK) { cout << "-j: " << spsp_last_error() << endl; return 1; }
-    if (extract_plain && !extract && !split) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
+    if (extract_plain && !extract && !split && !segments) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
     if (extract && spsp_extract_word_check_host(extract_what.c_str(), taxonomy ? 1 : 0, 0xffffffffu) != SPSP_OK) { cout << "-F: " << spsp_last_error() << endl; return 1; }
     long long window_width = 0;
     string window_word;
@@ -324,6 +336,16 @@ int main(int argc, char** argv) {
         }
         window_word = *e == ':' ? string(e + 1) : string(taxonomy ? "taxon" : "best");
         if (spsp_windows_word_check_host(window_word.c_str(), taxonomy ? 1 : 0) != SPSP_OK) { cout << "-y: " << spsp_last_error() << endl; return 1; }
+    }
+    if (smooth && !windows) { cout << "-Q absorbs stray windows into the segments of -y <W>: it needs -y" << endl; return 1; }
+    if (segments && !windows) { cout << "-Z writes segments of -y <W> out as FASTA: it needs -y" << endl; return 1; }
+    string segments_word;
+    unsigned long long segments_min = 1;
+    if (segments) {                                        // (<b> against the references: once they are counted, below)
+        if (spsp_segments_word_check_host(segments_arg.c_str(), taxonomy ? 1 : 0, 0) != SPSP_OK) { cout << "-Z: " << spsp_last_error() << endl; return 1; }
+        const size_t colon = segments_arg.find(':');
+        segments_word = segments_arg.substr(0, colon);
+        if (colon != string::npos) segments_min = strtoull(segments_arg.c_str() + colon + 1, nullptr, 10);
     }
     if (cf_opts && !classify) { cout << "-Y and -V belong to the classification of -X <records file>: they need -X" << endl; return 1; }
     if (classify && (query != "" || gather || cluster_opts || neighbours || prevalence || rep_opts || tree_opts || select_opts || accumulation || groups ||
@@ -384,6 +406,8 @@ int main(int argc, char** argv) {
              << "-u Write the records of -F, or the files of -j, plain, not gzipped" << endl
              << "-j Split the records of -X <records file> into <prefix>_split_<b>.fa.gz / .fq.gz, one file per reference (best; the rest in _split_unmatched) or, with -H, per node (taxon, depth=<d>; the rest in _split_unclassified), and <prefix>_split.csv.gz; with -x <prefix>_split_<b>_1.* and _2.*; -u writes them plain" << endl
              << "-y <W>[:<word>] Windows: cut every record of -X <records file> into windows of W bases (overlapping by k - 1), call each as a record (best; with -H: taxon, depth=<d>) and write <prefix>_segments.csv.gz (stretches with one call) and <prefix>_mosaic.csv.gz (one line per record) in the place of the per-record CSVs; positions count the bases A, C, G, T only" << endl
+             << "-Q <q> With -y: a run of at most q windows between two runs of one call, each longer than q windows, takes that call (its support counts as 0); 0 changes nothing" << endl
+             << "-Z <what>[:<min_bases>] With -y: write the segments the word names (all, called, none, call=<b>, not=<b>, major, minor) of at least min_bases bases as <prefix>_segments.fa.gz, one FASTA record <name>:<begin + 1>-<end> per segment, 80 bases a line; -u writes it plain" << endl
              << "-x Mates file: with -X <records file>, record p of the two files is one pair, classified by the keys of both mates; -F then writes <prefix>_extract_1.* and <prefix>_extract_2.*" << endl
              << "Ouput arguments:" << endl
              << "-m Minimum value to be output (0.0)" << endl
@@ -409,6 +433,10 @@ int main(int argc, char** argv) {
     for (auto& s : names) paths.push_back(s.c_str());
     if (extract && !taxonomy && spsp_extract_word_check_host(extract_what.c_str(), 0, (uint32_t)paths.size()) != SPSP_OK) {   // (<j> against the list: no device yet)
         cout << "-F: " << spsp_last_error() << endl;
+        return 1;
+    }
+    if (segments && !taxonomy && spsp_segments_word_check_host(segments_word.c_str(), 0, (uint32_t)paths.size() + 1) != SPSP_OK) {   // (likewise <b>)
+        cout << "-Z: " << spsp_last_error() << endl;
         return 1;
     }
     // Devices: every visible GPU when there is enough work to split (the comparison is dealt by key over one context per
@@ -452,13 +480,15 @@ int main(int argc, char** argv) {
         spsp_ctx* ctx = nullptr;
         int rc = spsp_create(devices[0], nullptr, &ctx);
         if (rc == SPSP_OK && windows && taxonomy)
-            rc = spsp_taxonomy_files_windows(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den,
-                                             (int)p, output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                                             nullptr, nullptr);
+            rc = spsp_taxonomy_files_segments(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den,
+                                              (int)p, output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr, (uint32_t)smooth_q, segments ? segments_word.c_str() : nullptr, segments_min, extract_plain ? 0 : 1, nullptr,
+                                              nullptr, nullptr);
         else if (rc == SPSP_OK && windows)
-            rc = spsp_classify_files_windows(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den, (int)p,
-                                             output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                             nullptr, nullptr);
+            rc = spsp_classify_files_segments(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den, (int)p,
+                                              output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr, (uint32_t)smooth_q, segments ? segments_word.c_str() : nullptr, segments_min, extract_plain ? 0 : 1, nullptr,
+                                              nullptr, nullptr);
         else if (rc == SPSP_OK && split && taxonomy)
             rc = spsp_taxonomy_files_split(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), paired ? mates_file.c_str() : nullptr, lineages_file.c_str(),
                                            (uint32_t)cf_min_keys, nb_num, nb_den, (int)p, output_name.c_str(), 1, rate, split_what.c_str(), extract_plain ? 0 : 1, nullptr,

@@ -504,6 +504,7 @@ struct TextSide {
             // context's windows buffer, in the form the ingest wrote).  The real records' offsets and first_win stay with the run
             windows->rec_off.assign((size_t)n_rec + 1, 0);
             windows->first_win.assign((size_t)n_rec + 1, 0);
+            windows->d_bases = d_bases; windows->n_bases = n_bases; windows->packed = packed;   // (the ingest's buffer: it stays as it is until the side context ends)
             SPSP_HIP(hipMemcpyAsync(windows->rec_off.data(), d_off, windows->rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));   // (the expansion waits)
             uint8_t* w_bases = nullptr; uint64_t* w_off = nullptr; uint64_t w_n = 0, n_win = 0;
             if ((rc = records_windows_impl(side, d_bases, n_bases, d_off, n_rec, p->k, windows->window, packed, &w_bases, &w_n, &w_off, windows->first_win.data(), &n_win)))
@@ -534,9 +535,20 @@ struct TextSide {
 
 // behind the last batch (every batch's rows are on the host: each record call waits), with the texts still in the side contexts'
 // buffers: the pass makes ONE flag or bin vector from its rows, and every text is cut by it
-static int cut_texts(RecordPass& pass, const RecordsAsk& ask, RecordsOut* out, TextSide* S, int n_sides) {
+static int cut_texts(spsp_ctx* ctx, uint32_t k, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out, TextSide* S, int n_sides) {
     int rc;
     const uint32_t n_rec = S[0].n_rec;
+    if (ask.mode == kRmWindows) {
+        // the rows are the windows': their calls are the split's bins.  Smoothing, segments, mosaic and the texts follow here, where
+        // the side context still holds the real records' bases for the segments' text
+        const size_t n_win = pass.n_rows();
+        std::vector<uint32_t> call(n_win ? n_win : 1, 0), keys(call.size(), 0), hit_keys(call.size(), 0), support(call.size(), 0);
+        uint32_t n_bins = 0;
+        if ((rc = pass.bins(ask.what, (uint32_t)n_win, call.data(), &n_bins))) return rc;
+        for (size_t w = 0; w < n_win; ++w) pass.window_addends(w, &keys[w], &hit_keys[w], &support[w]);
+        if ((rc = spsp_wait_stream(S[0].side, ctx))) return rc;
+        return windows_tail(S[0].side, &out->windows, ask, k, call, keys, hit_keys, support, n_bins, out->names, pass.bin_names(), pass.last_name());
+    }
     if (ask.mode == kRmSplit) {
         std::vector<uint32_t> bin(n_rec ? n_rec : 1, SPSP_SPLIT_DROP);
         uint32_t n_bins = 0;
@@ -616,7 +628,7 @@ static int records_text_batches(spsp_ctx* ctx, spsp_ctx* const* side, int n_side
         }
         if ((rc = pass.on_batch(B))) return rc;
     }
-    return cut_texts(pass, ask, out, S, n_sides);
+    return cut_texts(ctx, p->k, pass, ask, out, S, n_sides);
 }
 
 int records_files_road(FilesRun& run, const char* what_is, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out) {
@@ -680,14 +692,8 @@ int record_files_run(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_r
     int rc;
     if ((rc = records_files_road(run, "classification is", pass, ask, out))) return rc;
     if (ask.mode == kRmWindows) {
-        // the rows are the windows': their calls are the split's bins, and the two windowed CSVs take the per-record CSVs' place
-        const size_t n_win = pass.n_rows();
-        std::vector<uint32_t> call(n_win ? n_win : 1, 0), keys(call.size(), 0), hit_keys(call.size(), 0), support(call.size(), 0);
-        uint32_t n_bins = 0;
-        if ((rc = pass.bins(ask.what, (uint32_t)n_win, call.data(), &n_bins))) return rc;
-        for (size_t w = 0; w < n_win; ++w) pass.window_addends(w, &keys[w], &hit_keys[w], &support[w]);
-        if ((rc = windows_write(ctx, &out->windows, run.keys.k, call, keys, hit_keys, support, n_bins, out->names, pass.bin_names(), pass.last_name(), ask.precision,
-                                ask.out_prefix, out->t1, ask.chatter))) return rc;
+        // the texts were made behind the last batch; the two windowed CSVs take the per-record CSVs' place
+        if ((rc = windows_files(ctx, &out->windows, ask, out->t1))) return rc;
     } else if ((rc = pass.write_rows(run, ask, out->names, out->t1)) || (ask.mode != kRmPlain && (rc = extract_write(ctx, pass, ask, out)))) return rc;
     if (ask.chatter) {
         if (ask.mode != kRmWindows) pass.say_rows(run, ask);
@@ -828,32 +834,44 @@ extern "C" int spsp_classify_files_split(spsp_ctx* ctx, const char* const* index
                                 n_bins_written, bytes_out);
 }
 
-extern "C" int spsp_classify_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
-                                           uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
-                                           const char* what, spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win,
-                                           uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic) {
+extern "C" int spsp_classify_files_segments(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                            uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
+                                            const char* what, spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win,
+                                            uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth,
+                                            const char* segments_what, uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out) {
     if (rows) *rows = nullptr;
     if (hits) *hits = nullptr;
     if (first_win) *first_win = nullptr;
     if (segments) *segments = nullptr;
     if (mosaic) *mosaic = nullptr;
-    if (n_windows) *n_windows = 0;
-    if (n_records) *n_records = 0;
-    if (n_segments) *n_segments = 0;
+    for (uint64_t* n : {n_windows, n_records, n_segments, n_changed, n_written, bytes_out}) if (n) *n = 0;
     const RecordFront front{ctx, index_paths, nullptr, false, false, n_ref, top, min_keys, num, den};
     ClassifyPass pass(front);
     RecordsOut out;
-    if (const int rc = record_files_entry(front, pass, records_ask(&records_path, nullptr, kRmWindows, what, 1, window, precision, out_prefix, chatter, rate), &out)) return rc;
+    RecordsAsk ask = records_ask(&records_path, nullptr, kRmWindows, what, gz, window, precision, out_prefix, chatter, rate);
+    ask.smooth = smooth; ask.segments_what = segments_what; ask.segments_min = segments_min;
+    if (const int rc = record_files_entry(front, pass, ask, &out)) return rc;
     const WindowsRun& run = out.windows;
     if (n_windows) *n_windows = pass.recs.size();
     if (n_records) *n_records = run.mosaic.size();
     if (n_segments) *n_segments = run.segments.size();
+    if (n_changed) *n_changed = run.n_changed;
+    if (n_written) *n_written = run.n_written;
+    if (bytes_out) *bytes_out = run.fasta.size();
     const RowsGift gifts[] = {{(void**)rows, pass.recs.data(), pass.recs.size() * sizeof(spsp_classify_record)},
                               {(void**)hits, pass.hits.data(), pass.hits.size() * sizeof(spsp_classify_hit)},
                               {(void**)first_win, run.first_win.data(), run.first_win.size() * sizeof(uint32_t)},
                               {(void**)segments, run.segments.data(), run.segments.size() * sizeof(spsp_segment_row)},
                               {(void**)mosaic, run.mosaic.data(), run.mosaic.size() * sizeof(spsp_mosaic_row)}};
     return give_rows_all(gifts, 5);
+}
+
+extern "C" int spsp_classify_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                           uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
+                                           const char* what, spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win,
+                                           uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic) {
+    return spsp_classify_files_segments(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, window, what, rows, hits,
+                                        n_windows, first_win, n_records, segments, n_segments, mosaic, 0, nullptr, 1, 1, nullptr, nullptr, nullptr);
 }
 
 extern "C" int spsp_classify_stage_ms(spsp_ctx* ctx, double* ms) {

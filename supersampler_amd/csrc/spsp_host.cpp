@@ -1914,7 +1914,18 @@ int record_files_check_args(const RecordFront& front, const RecordsAsk& ask) {
         set_error("windows: the width must be k .. %llu (width = %llu)", (unsigned long long)kWnMaxWidth, (unsigned long long)ask.window);
         return SPSP_ERR_ARG;
     }
+    if (ask.mode != kRmWindows && (ask.smooth || ask.segments_what)) { set_error("segments: smoothing and the segments' text belong to a windowed run"); return SPSP_ERR_ARG; }
+    if (ask.smooth > 0x7fffffffu) { set_error("segments: the smoothing must be 0 .. 2147483647 (q = %u)", ask.smooth); return SPSP_ERR_ARG; }
+    // (the selection's word likewise; <b> of a taxonomy against the nodes once the tree is read, in the pass's prelude)
+    if (ask.segments_what && (rc = segments_ask_check(ask, tax, tax ? 0u : front.n_ref + 1))) return rc;
     return SPSP_OK;
+}
+
+int segments_ask_check(const RecordsAsk& ask, int taxonomy, uint32_t n_bins) {
+    if (!ask.segments_what) return SPSP_OK;
+    if (strchr(ask.segments_what, ':')) { set_error("segments: '%s' is no word (all, called, none, call=<b>, not=<b>, major, minor)", ask.segments_what); return SPSP_ERR_ARG; }
+    if (ask.segments_min >> 63) { set_error("segments: the least length must be below 2^63"); return SPSP_ERR_ARG; }
+    return spsp_segments_word_check_host(ask.segments_what, taxonomy, n_bins);
 }
 
 int give_rows_all(const RowsGift* gifts, size_t n) {
@@ -3556,4 +3567,192 @@ extern "C" int spsp_windows_word_check_host(const char* what, int taxonomy) {
         if (said.compare(0, 7, "split: ") == 0) spsp::set_error("windows: %s", said.c_str() + 7);
     }
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------- segments as sequence
+// The host forms behind the windows (the rule: include/spsp.h, "segments as sequence"): the smoothing of stray runs, the
+// selection's word and flags, and the FASTA text as plain loops, which the device writer is held against.
+
+extern "C" int spsp_segments_plan_host(uint32_t* line_bases, uint32_t* stretch_bytes) {
+    if (line_bases) *line_bases = spsp::kSgLine;
+    if (stretch_bytes) *stretch_bytes = spsp::kSgStretch;
+    return SPSP_OK;
+}
+
+extern "C" int spsp_windows_smooth_host(uint32_t* call, uint32_t* support, const uint32_t* first_win, uint32_t n_rec, uint32_t n_bins, uint32_t q, uint64_t* n_changed) {
+    using namespace spsp;
+    if (n_changed) *n_changed = 0;
+    if (!first_win || (n_rec && first_win[n_rec] && (!call || !support))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (q > 0x7fffffffu) { set_error("segments: the smoothing must be 0 .. 2147483647 (q = %u)", q); return SPSP_ERR_ARG; }
+    for (uint32_t r = 0; r < n_rec; ++r) {                 // (everything is held before anything is changed)
+        if (first_win[r] > first_win[r + 1]) { set_error("segments: first_win must not decrease (record %u)", r); return SPSP_ERR_ARG; }
+        for (uint32_t w = first_win[r]; w < first_win[r + 1]; ++w)
+            if (call[w] >= n_bins) { set_error("segments: record %u, window %u: call %u, n_bins = %u", r, w - first_win[r], call[w], n_bins); return SPSP_ERR_ARG; }
+    }
+    uint64_t changed = 0;
+    std::vector<uint32_t> start;                           // one record's runs: run j = windows [start[j], start[j + 1])
+    for (uint32_t r = 0; q && r < n_rec; ++r) {
+        const uint32_t w0 = first_win[r], w1 = first_win[r + 1];
+        start.clear();
+        for (uint32_t w = w0; w < w1; ++w) if (w == w0 || call[w] != call[w - 1]) start.push_back(w);
+        start.push_back(w1);
+        const size_t n_runs = start.size() - 1;
+        // the runs were found on the unsmoothed calls, and a changed run's neighbours are longer than q: they stay as they were
+        for (size_t j = 1; j + 1 < n_runs; ++j) {
+            const uint32_t len = start[j + 1] - start[j], left = start[j] - start[j - 1], right = start[j + 2] - start[j + 1];
+            if (len > q || left <= q || right <= q || call[start[j - 1]] != call[start[j + 1]]) continue;
+            for (uint32_t w = start[j]; w < start[j + 1]; ++w) { call[w] = call[start[j - 1]]; support[w] = 0; }
+            changed += len;
+        }
+    }
+    if (n_changed) *n_changed = changed;
+    return SPSP_OK;
+}
+
+namespace {
+
+enum SgWord { kSgAll, kSgCalled, kSgNone, kSgCall, kSgNot, kSgMajor, kSgMinor };
+
+// a decimal of digits alone that stays below `limit`
+bool sg_decimal(const char* s, uint64_t limit, uint64_t* v) {
+    if (!*s) return false;
+    uint64_t x = 0;
+    for (; *s; ++s) {
+        if (*s < '0' || *s > '9' || x > (limit - (uint64_t)(*s - '0')) / 10) return false;
+        x = x * 10 + (uint64_t)(*s - '0');
+    }
+    if (x >= limit) return false;
+    *v = x;
+    return true;
+}
+
+// what: a word, or <word>:<min_bases> where min is not null.  n_bins == 0: the bins are not counted yet
+int sg_word_for(const char* what, bool taxonomy, uint32_t n_bins, SgWord* word, uint32_t* b, uint64_t* min) {
+    using namespace spsp;
+    if (!what) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    std::string w = what;
+    const size_t colon = w.find(':');
+    if (colon != std::string::npos) {
+        uint64_t m = 0;
+        if (!min || !sg_decimal(w.c_str() + colon + 1, 1ull << 63, &m)) {
+            set_error("segments: '%s': the least length behind the ':' must be a decimal number below 2^63", what);
+            return SPSP_ERR_ARG;
+        }
+        *min = m;
+        w.resize(colon);
+    }
+    *b = 0;
+    if (w == "all") *word = kSgAll;
+    else if (w == "called") *word = kSgCalled;
+    else if (w == "none") *word = kSgNone;
+    else if (w == "major") *word = kSgMajor;
+    else if (w == "minor") *word = kSgMinor;
+    else if (w.compare(0, 5, "call=") == 0 || w.compare(0, 4, "not=") == 0) {
+        const bool is_call = w[0] == 'c';
+        uint64_t v = 0;
+        if (!sg_decimal(w.c_str() + (is_call ? 5 : 4), 0xffffffffull, &v)) { set_error("segments: '%s': <b> must be a decimal number", what); return SPSP_ERR_ARG; }
+        if (n_bins && v + 1 >= n_bins) {
+            set_error("segments: '%s': there are %u %s(s), numbered from 0", what, n_bins - 1, taxonomy ? "node" : "reference");
+            return SPSP_ERR_ARG;
+        }
+        *word = is_call ? kSgCall : kSgNot;
+        *b = (uint32_t)v;
+    } else {
+        set_error("segments: '%s' is no word (all, called, none, call=<b>, not=<b>, major, minor)", what);
+        return SPSP_ERR_ARG;
+    }
+    return SPSP_OK;
+}
+
+}  // namespace
+
+extern "C" int spsp_segments_word_check_host(const char* what, int taxonomy, uint32_t n_bins) {
+    SgWord word; uint32_t b = 0; uint64_t min = 1;
+    return sg_word_for(what, taxonomy != 0, n_bins, &word, &b, &min);
+}
+
+extern "C" int spsp_segments_select_host(const spsp_segment_row* segments, uint64_t n_segments, const spsp_mosaic_row* mosaic, uint32_t n_rec, uint32_t n_bins,
+                                         const char* what, uint64_t min_bases, uint8_t* keep, uint64_t* n_kept, uint64_t* n_bases) {
+    using namespace spsp;
+    if (n_kept) *n_kept = 0;
+    if (n_bases) *n_bases = 0;
+    if (!what || (n_segments && (!segments || !keep)) || (n_rec && !mosaic)) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    if (n_bins == 0) { set_error("segments: n_bins must be 1 or more"); return SPSP_ERR_ARG; }
+    if (min_bases >> 63) { set_error("segments: the least length must be below 2^63"); return SPSP_ERR_ARG; }
+    SgWord word; uint32_t b = 0;
+    if (const int rc = sg_word_for(what, false, n_bins, &word, &b, nullptr)) return rc;
+    const uint32_t none = n_bins - 1;
+    const uint64_t least = min_bases ? min_bases : 1;
+    for (uint64_t i = 0; i < n_segments; ++i) {
+        const spsp_segment_row& g = segments[i];
+        if (g.record >= n_rec || g.call >= n_bins || g.end < g.begin) {
+            set_error("segments: segment %llu names record %u or call %u out of range, or ends in front of its begin", (unsigned long long)i, g.record, g.call);
+            return SPSP_ERR_ARG;
+        }
+    }
+    uint64_t kept = 0, bases = 0;
+    for (uint64_t i = 0; i < n_segments; ++i) {
+        const spsp_segment_row& g = segments[i];
+        const uint32_t major = mosaic[g.record].major;
+        bool k = false;
+        switch (word) {
+            case kSgAll: k = true; break;
+            case kSgCalled: k = g.call != none; break;
+            case kSgNone: k = g.call == none; break;
+            case kSgCall: k = g.call == b; break;
+            case kSgNot: k = g.call != b; break;
+            case kSgMajor: k = major != SPSP_WINDOWS_ABSENT && g.call == major; break;
+            case kSgMinor: k = major != SPSP_WINDOWS_ABSENT && g.call != none && g.call != major; break;
+        }
+        k = k && g.end - g.begin >= least;
+        keep[i] = k ? 1 : 0;
+        if (k) { ++kept; bases += g.end - g.begin; }
+    }
+    if (n_kept) *n_kept = kept;
+    if (n_bases) *n_bases = bases;
+    return SPSP_OK;
+}
+
+namespace spsp {
+// '>' name ':' begin + 1 '-' end ' ' call_name '\n'
+void segment_header(const spsp_segment_row& g, const char* name, const char* const* call_names, const char* last_name, uint32_t n_bins, std::string* s) {
+    *s += ">";
+    *s += name;
+    *s += ":" + std::to_string(g.begin + 1) + "-" + std::to_string(g.end) + " ";
+    *s += g.call + 1 == n_bins ? last_name : call_names[g.call];
+    *s += "\n";
+}
+}  // namespace spsp
+
+extern "C" int spsp_segments_fasta_host(const uint8_t* bases, uint64_t n_bases, const uint64_t* rec_off, uint32_t n_rec, const spsp_segment_row* segments,
+                                        uint64_t n_segments, const uint8_t* keep, const char* const* record_names, const char* const* call_names,
+                                        const char* last_name, uint32_t n_bins, char** text, uint64_t* len) {
+    using namespace spsp;
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!text || !len || !last_name || !rec_off || (n_bases && !bases) || (n_segments && (!segments || !record_names)) || (n_bins > 1 && !call_names)) {
+        set_error("NULL argument");
+        return SPSP_ERR_ARG;
+    }
+    if (n_bins == 0) { set_error("segments: n_bins must be 1 or more"); return SPSP_ERR_ARG; }
+    for (uint32_t r = 0; r < n_rec; ++r)
+        if (rec_off[r] > rec_off[r + 1] || rec_off[r + 1] > n_bases) { set_error("segments: the offsets must not decrease and must end inside the bases (record %u)", r); return SPSP_ERR_ARG; }
+    std::string s;
+    for (uint64_t i = 0; i < n_segments; ++i) {
+        const spsp_segment_row& g = segments[i];
+        if (g.record >= n_rec || g.call >= n_bins || g.begin > g.end || g.end > rec_off[g.record + 1] - rec_off[g.record]) {
+            set_error("segments: segment %llu names record %u or call %u out of range, or leaves its record", (unsigned long long)i, g.record, g.call);
+            return SPSP_ERR_ARG;
+        }
+        if ((keep && !keep[i]) || g.begin == g.end) continue;
+        segment_header(g, record_names[g.record], call_names, last_name, n_bins, &s);
+        const uint8_t* at = bases + rec_off[g.record] + g.begin;
+        const uint64_t n = g.end - g.begin;
+        for (uint64_t p = 0; p < n; ++p) {
+            const uint8_t c = at[p];
+            s += (char)(c >= 'a' && c <= 'z' ? c - 32 : c);
+            if ((p + 1) % SPSP_SEGMENTS_LINE == 0 || p + 1 == n) s += '\n';
+        }
+    }
+    return give_text(s, text, len);
 }

@@ -374,6 +374,12 @@ struct spsp_ctx {
     spsp::DevBuf wn_words, wn_tiles, wn_rec, wn_off, wn_src, wn_out;
     hipEvent_t wn_ev[4] = {};            // while timing is on: in front of the count, the offsets, the copy, and behind it
     double wn_ms[3] = {};                // spsp_windows_stage_ms: count, offsets, copy
+    // segments as sequence (spsp_segments.hip): the call's upload (the three tables and the headers) and the text, whole stretches
+    spsp::DevBuf sg_tab, sg_out;
+    std::vector<uint8_t> sg_host;        // the upload's host copy: it stays until the next call, as the copy may still read it
+    hipEvent_t sg_ev[2] = {};            // while timing is on: in front of the launch and behind it
+    bool sg_marked = false;
+    double sg_ms = 0;                    // spsp_segments_stage_ms: the write
 };
 
 namespace spsp {
@@ -589,6 +595,11 @@ struct RecordsAsk {
     const char* out_prefix = nullptr;
     int chatter = 0;
     double rate = 0;
+    // a windowed run: stray runs of up to `smooth` windows are absorbed; segments_what: null, or the word that selects the segments
+    // written as <out_prefix>_segments.fa (".gz" appended when gz), those of at least max(1, segments_min) bases
+    uint32_t smooth = 0;
+    const char* segments_what = nullptr;
+    uint64_t segments_min = 1;
 };
 // an entry's ask: records_path is the address of the entry's own argument, which outlives the call
 inline RecordsAsk records_ask(const char* const* records_path, const char* mates_path, RecordsMode mode, const char* what, int gz, uint64_t window, int precision,
@@ -653,6 +664,18 @@ struct WindowsRun {
     std::vector<uint64_t> rec_off;
     std::vector<spsp_segment_row> segments;
     std::vector<spsp_mosaic_row> mosaic;
+    // the REAL records' cleaned bases on the side context, which TextSide::open replaces by the windows' for the scan: the ingest's
+    // own buffer, which nothing behind the ingest writes, in the form `packed` says
+    const uint8_t* d_bases = nullptr;
+    uint64_t n_bases = 0;
+    bool packed = false;
+    // what the tail behind the last batch leaves for the driver: the three texts (made before any file is written), the windows
+    // the smoothing changed, the segments selected and their bases
+    uint32_t k = 0, n_bins = 0;
+    std::string seg_csv, mos_csv;
+    std::vector<uint8_t> fasta;
+    bool want_fasta = false;
+    uint64_t n_changed = 0, n_written = 0, bases_written = 0;
 };
 // what the road leaves behind for the driver and the entry.  names: the records' names as the host reads them from the header
 // lines (a pair: the mates' common names) -- then a text with another number of header lines than the device finds records is
@@ -751,9 +774,9 @@ int classify_probe_launch(spsp_ctx* ctx, const uint32_t* q_mn, const uint64_t* q
 // mates' keys per pair (spsp_union.hip) being what on_batch gets -- pass.on_close where all of that went well, the wait for
 // ctx's stream and the side contexts' end; out->t1 = run.end()
 int records_files_road(FilesRun& run, const char* what_is, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out);
-// the one driver body behind classify and taxonomy (spsp_classify.hip): the runs' tags from the ask, the road, then windows mode's
-// tail (the pass's bins and addends, windows_write) or the pass's write_rows and, where asked, the extraction's or the split's
-// files; the pass's chatter line and the common rate's
+// the one driver body behind classify and taxonomy (spsp_classify.hip): the runs' tags from the ask, the road (windows mode: its
+// tail behind the last batch makes the texts, windows_tail), then windows_files or the pass's write_rows and, where asked, the
+// extraction's or the split's files; the pass's chatter line and the common rate's
 int record_files_run(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, RecordPass& pass, const RecordsAsk& ask, RecordsOut* out);
 // the front of the ten file entries.  record_files_check_args (spsp_host.cpp), in this order: NULL arguments (lineages_path with
 // taxonomy, mates_path with paired, the word with windows), the reference count, the pass's thresholds, the word that belongs to
@@ -844,12 +867,26 @@ __host__ __device__ inline uint64_t wn_bases(uint64_t L, uint64_t n_win, uint32_
 // the windows of a text's records in the context's buffers, with one host wait (for the counts).  h_first_win: n_rec + 1
 int records_windows_impl(spsp_ctx* ctx, const uint8_t* d_bases, uint64_t n_bases, const uint64_t* d_rec_off, uint32_t n_rec, uint32_t k, uint64_t window, bool packed,
                          uint8_t** d_out, uint64_t* n_out, uint64_t** d_win_off, uint32_t* h_first_win, uint64_t* n_windows);
-// what a windowed driver does behind the road (spsp_windows.hip): segments and mosaic rows from the windows' calls and addends
-// (spsp_windows_segments_host), both texts made before either file is written, <out_prefix>_segments.csv.gz and
-// <out_prefix>_mosaic.csv.gz, and with chatter the one line.  call_names: n_bins - 1
-int windows_write(spsp_ctx* ctx, WindowsRun* run, uint32_t k, const std::vector<uint32_t>& call, const std::vector<uint32_t>& keys, const std::vector<uint32_t>& hit_keys,
-                  const std::vector<uint32_t>& support, uint32_t n_bins, const std::vector<std::string>& names, const char* const* call_names, const char* last_name,
-                  int precision, const char* out_prefix, double t_csv, int chatter);
+// spsp_segments.hip: chosen segments written as FASTA from the cleaned bases (the rule: include/spsp.h, "segments as sequence").
+// What the kernel cuts at (spsp_segments_plan_host, spsp_host.cpp):
+constexpr uint32_t kSgLine = 80;                           // bases of a line (SPSP_SEGMENTS_LINE); a full line is kSgLine + 1 bytes
+constexpr uint32_t kSgThreads = 256;                       // k_sg_write: 4 waves
+constexpr uint32_t kSgStretch = 16384;                     // bytes of the text one workgroup owns: the extraction's schedule
+constexpr uint32_t kSgStores = kSgStretch / (kSgThreads * 16);   // rounds of 16-byte stores a workgroup makes
+constexpr uint32_t kSgLdsSegs = 512;                       // segments of a stretch whose table entries are kept in LDS (more: read from memory)
+// the text in the context's buffer, queued on its stream: one upload, one launch, no host wait
+int segments_write_impl(spsp_ctx* ctx, const uint8_t* d_bases, uint64_t n_bases, bool packed, const uint64_t* h_src, const uint64_t* h_len, const uint8_t* h_headers,
+                        const uint64_t* h_hdr_off, uint64_t n_seg, uint8_t** d_out, uint64_t* n_out);
+// the tail of a windowed run behind its last batch, with the side context still alive: the calls smoothed, segments and mosaic, the
+// two CSV texts, and where a word asks for it the selection, the headers, the write on `side` (ordered behind ctx by the caller)
+// and the copy back, with one wait.  Nothing is written to disk here: windows_files does that, every text being made
+int windows_tail(spsp_ctx* side, WindowsRun* run, const RecordsAsk& ask, uint32_t k, std::vector<uint32_t>& call, const std::vector<uint32_t>& keys,
+                 const std::vector<uint32_t>& hit_keys, std::vector<uint32_t>& support, uint32_t n_bins, const std::vector<std::string>& names,
+                 const char* const* call_names, const char* last_name);
+int windows_files(spsp_ctx* ctx, WindowsRun* run, const RecordsAsk& ask, double t_csv);
+// the selection of an ask held before any file is read (spsp_host.cpp); the header of one segment's FASTA record
+int segments_ask_check(const RecordsAsk& ask, int taxonomy, uint32_t n_bins);
+void segment_header(const spsp_segment_row& g, const char* name, const char* const* call_names, const char* last_name, uint32_t n_bins, std::string* s);
 // spsp_groups.hip: per-group core, exclusive and marker keys of a partitioned collection; with want_markers the marker keys of the
 // groups as n_groups sketches back to back in context-owned arrays
 int groups_device_impl(spsp_ctx* ctx, uint32_t k, const uint32_t* d_mn, const uint64_t* d_lo, const uint64_t* d_hi, const uint64_t* h_sk_off, uint32_t n,

@@ -417,6 +417,7 @@ struct TaxonomyPass : RecordPass {
         if (rc) return rc;
         // (the word's node against the tree: still before any sketch is read)
         if (ask.mode == kRmExtract && (rc = spsp_extract_word_check_host(ask.what, 1, T))) return rc;
+        if ((rc = segments_ask_check(ask, 1, T + 1))) return rc;   // (likewise <b> of a windowed run's selection: the bins are the nodes and "unclassified")
         node_names.resize(T);
         for (uint64_t at = 0, t = 0; t < T; ++t) { node_names[t] = blob + at; at += strlen(blob + at) + 1; }
         return SPSP_OK;
@@ -505,30 +506,42 @@ static int taxonomy_files_entry(const RecordFront& front, const RecordsAsk& ask,
     return give_rows_all(&gift, 1);
 }
 
-extern "C" int spsp_taxonomy_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
-                                           uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
-                                           const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
-                                           spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic) {
+extern "C" int spsp_taxonomy_files_segments(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                            uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                            uint64_t window, const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win,
+                                            uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth,
+                                            const char* segments_what, uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out) {
     if (rows) *rows = nullptr;
     if (first_win) *first_win = nullptr;
     if (segments) *segments = nullptr;
     if (mosaic) *mosaic = nullptr;
-    if (n_windows) *n_windows = 0;
-    if (n_records) *n_records = 0;
-    if (n_segments) *n_segments = 0;
+    for (uint64_t* n : {n_windows, n_records, n_segments, n_changed, n_written, bytes_out}) if (n) *n = 0;
     const RecordFront front{ctx, index_paths, lineages_path, true, false, n_ref, 0, min_keys, num, den};
     TaxonomyPass pass(front);
     RecordsOut out;
-    if (const int rc = record_files_entry(front, pass, records_ask(&records_path, nullptr, kRmWindows, what, 1, window, precision, out_prefix, chatter, rate), &out)) return rc;
+    RecordsAsk ask = records_ask(&records_path, nullptr, kRmWindows, what, gz, window, precision, out_prefix, chatter, rate);
+    ask.smooth = smooth; ask.segments_what = segments_what; ask.segments_min = segments_min;
+    if (const int rc = record_files_entry(front, pass, ask, &out)) return rc;
     const WindowsRun& run = out.windows;
     if (n_windows) *n_windows = pass.recs.size();
     if (n_records) *n_records = run.mosaic.size();
     if (n_segments) *n_segments = run.segments.size();
+    if (n_changed) *n_changed = run.n_changed;
+    if (n_written) *n_written = run.n_written;
+    if (bytes_out) *bytes_out = run.fasta.size();
     const RowsGift gifts[] = {{(void**)rows, pass.recs.data(), pass.recs.size() * sizeof(spsp_taxonomy_record)},
                               {(void**)first_win, run.first_win.data(), run.first_win.size() * sizeof(uint32_t)},
                               {(void**)segments, run.segments.data(), run.segments.size() * sizeof(spsp_segment_row)},
                               {(void**)mosaic, run.mosaic.data(), run.mosaic.size() * sizeof(spsp_mosaic_row)}};
     return give_rows_all(gifts, 4);
+}
+
+extern "C" int spsp_taxonomy_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                           uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
+                                           const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
+                                           spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic) {
+    return spsp_taxonomy_files_segments(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, window, what, rows,
+                                        n_windows, first_win, n_records, segments, n_segments, mosaic, 0, nullptr, 1, 1, nullptr, nullptr, nullptr);
 }
 
 extern "C" int spsp_taxonomy_files(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,

@@ -268,33 +268,6 @@ int records_windows_impl(spsp_ctx* ctx, const uint8_t* d_bases, uint64_t n_bases
     return SPSP_OK;
 }
 
-int windows_write(spsp_ctx* ctx, WindowsRun* run, uint32_t k, const std::vector<uint32_t>& call, const std::vector<uint32_t>& keys, const std::vector<uint32_t>& hit_keys,
-                  const std::vector<uint32_t>& support, uint32_t n_bins, const std::vector<std::string>& names, const char* const* call_names, const char* last_name,
-                  int precision, const char* out_prefix, double t_csv, int chatter) {
-    int rc;
-    const uint32_t n_rec = (uint32_t)(run->rec_off.size() - 1);
-    spsp_segment_row* segs = nullptr; uint64_t n_segs = 0;
-    run->mosaic.assign(n_rec, spsp_mosaic_row{});
-    spsp_mosaic_row none_row{};
-    if ((rc = spsp_windows_segments_host(call.data(), keys.data(), hit_keys.data(), support.data(), run->first_win.data(), run->rec_off.data(), n_rec, k, run->window,
-                                         n_bins, &segs, &n_segs, n_rec ? run->mosaic.data() : &none_row))) return rc;
-    run->segments.assign(segs, segs + n_segs);
-    spsp_free(segs);
-    std::vector<const char*> name_ptr(names.size());
-    for (size_t r = 0; r < names.size(); ++r) name_ptr[r] = names[r].c_str();
-    char *seg_text = nullptr, *mos_text = nullptr; uint64_t seg_len = 0, mos_len = 0;
-    if ((rc = spsp_segments_csv_host(run->segments.data(), n_segs, name_ptr.data(), n_rec, call_names, last_name, n_bins, &seg_text, &seg_len))) return rc;
-    if ((rc = spsp_mosaic_csv_host(run->mosaic.data(), n_rec, name_ptr.data(), call_names, last_name, n_bins, precision, &mos_text, &mos_len))) { free(seg_text); return rc; }
-    if ((rc = write_csv_gz(ctx, seg_text, seg_len, out_prefix, "_segments.csv.gz", t_csv))) { free(mos_text); return rc; }
-    if ((rc = write_csv_gz(ctx, mos_text, mos_len, out_prefix, "_mosaic.csv.gz", now_s())) || !chatter) return rc;
-    uint64_t mixed = 0;
-    for (const spsp_mosaic_row& m : run->mosaic) mixed += m.calls >= 2;
-    printf("%u record(s) in %u window(s) of %llu base(s): %llu segment(s), %llu record(s) with two or more calls\n", n_rec, run->first_win[n_rec],
-           (unsigned long long)run->window, (unsigned long long)n_segs, (unsigned long long)mixed);
-    fflush(stdout);
-    return SPSP_OK;
-}
-
 }  // namespace spsp
 
 using namespace spsp;
