@@ -1672,7 +1672,7 @@ int spsp_taxonomy_files_split(spsp_ctx* ctx, const char* const* index_paths, uin
  * between the ingest and the scan; the windows run as records through the unchanged scan, key extraction, classify and taxonomy
  * kernels; the answer comes back along the record as SEGMENTS and one MOSAIC line per record.
  * BASES.  A record r has L bases: the bases the ingest keeps (bytes outside ACGTacgt are deleted); `length` and every position
- * below count what is left.  Coordinates in the raw text where it holds Ns are not kept: that is this pass's limitation.
+ * below count what is left.  Positions in the raw text, where it holds Ns, are made from them afterwards: "raw coordinates" below.
  * WINDOWS.  A width W with k <= W <= 0x7fffffff (else SPSP_ERR_ARG); the step is S = W - (k - 1).
  *   n_win(r) = max(1, ceil((L - k + 1) / S)): a record of at most W bases is one window, a record shorter than k one window
  *   without keys, an empty record one empty window.
@@ -1842,6 +1842,84 @@ int spsp_taxonomy_files_segments(spsp_ctx* ctx, const char* const* index_paths, 
                                  const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
                                  spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth, const char* segments_what,
                                  uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out);
+
+/* ------------------------------------------------------- raw coordinates ---- */
+/* Segments lifted to the positions of the file the user holds (not in the reference).  Windows and segments count only the bases
+ * the ingest keeps; samtools faidx, bedtools and a genome browser count every sequence character of the record.  The map between
+ * the two is a rank / select over the raw text.  Integers only.
+ * SEQUENCE CHARACTERS.
+ *   FASTA: a byte is a sequence character if it lies on a line that does not begin a record, and its value is 0x21 .. 0x7e.  The
+ *   lines that begin a record are the extraction's rule: line 0 whatever it holds, and every line whose first byte is '>' or 0xFF.
+ *   The byte range 0x21 .. 0x7e is what samtools faidx counts (isgraph).  So '\n', '\r', blanks and tabs are not counted, and N,
+ *   IUPAC codes, lower case and '-' are.
+ *   FASTQ: the bytes 0x21 .. 0x7e of line 4r + 1.
+ *   raw_length[r] is the number of sequence characters of record r.
+ *   Every kept base is a sequence character.
+ * RECORDS.  A text is FASTQ when its first byte is '@', else FASTA.  FASTA: record 0 begins with the text (an empty text is one
+ *   empty record, as the ingest has it), and a record begins at every later line whose first byte is '>' or 0xFF.  FASTQ: record
+ *   r begins at line 4r, and a line 4r that is empty or begins with '\r' begins none: the blank lines behind the content, which
+ *   the ingest sets aside, add no record.  The lines are counted through them all the same; they hold no sequence character.
+ *   For every text the ingest accepts the records are the ingest's.
+ * RAW POSITION.  raw(r, p) is the number of sequence characters of record r in front of its kept base number p, for
+ *   0 <= p < L_r.  It is strictly increasing in p.  It equals p exactly when no other sequence character precedes the base.
+ * RAW INTERVAL OF A SEGMENT.  A segment [begin, end) with end > begin has the raw interval [raw(r, begin), raw(r, end - 1) + 1).
+ *   It is tight: it starts and ends on a kept base.  Ns between two segments belong to neither, since nothing was called on
+ *   them.  A segment without bases (an empty record) has no raw interval.
+ * BED.  <prefix>_segments.bed.gz (plain <prefix>_segments.bed where gzip is off): one line per segment that has bases, in the
+ *   segments CSV's order, tab-separated: name, raw_begin, raw_end, call_name, 0, ., segment, begin, end, windows, support -- BED6
+ *   and five columns; raw_begin is 0-based and raw_end exclusive, as BED has it; call_name is what the CSV prints, a tab inside it
+ *   written as a blank. */
+/* What the kernels cut at (either pointer may be NULL): the bytes of the text per workgroup and per lane (the ingest's). */
+int spsp_lift_plan_host(uint32_t* tile_bytes, uint32_t* chunk_bytes);
+/* The rule as plain loops: the yardstick of the device pass.  h_base[q]: GLOBAL kept-base indices (rec_off[r] + p, the numbering
+ * spsp_segments_write_device takes in h_src), non-decreasing, equal values allowed.  raw[q]: record-relative; rec[q] (may be
+ * NULL): the record that holds the base; raw_length (may be NULL): on entry *n_rec is the records it has room for, and a text
+ * that holds another number is SPSP_ERR_ARG; *n_rec: the records of the text.  SPSP_ERR_ARG for indices that decrease and for an
+ * index that is not below the text's kept bases; the outputs then hold nothing to use. */
+int spsp_records_lift_host(const uint8_t* text, uint64_t n, const uint64_t* h_base /* n_q */, uint64_t n_q, uint64_t* raw /* n_q, caller's */,
+                           uint32_t* rec /* n_q, may be NULL */, uint64_t* raw_length /* n_rec, may be NULL */, uint32_t* n_rec);
+/* The BED text.  raw_begin, raw_end: one per segment (read only for segments that have bases).  SPSP_ERR_ARG for a segment whose
+ * record or call is out of range, and for a raw interval shorter than the segment's bases.  *text is released with spsp_free(). */
+int spsp_segments_bed_host(const spsp_segment_row* segments, uint64_t n_segments, const uint64_t* raw_begin, const uint64_t* raw_end, const char* const* record_names,
+                           uint32_t n_rec, const char* const* call_names, const char* last_name, uint32_t n_bins, char** text, uint64_t* len);
+/* The pass on the device.  d_text: the raw text in HBM, 16-byte aligned as the extraction asks; n_bases: the kept bases the ingest
+ * counted for it; the arrays as above, in host memory.  Launches: per 4 KiB tile (a lane per 16-byte chunk) the line-state
+ * transform and, per state the tile may be entered in, its kept bases, sequence characters and record starts (FASTQ: the newline
+ * count takes the transform's place, so the line phase mod 4 is additive); one workgroup scan -> every tile's entry state and
+ * its prefixes K, S, R; the answer, a workgroup per tile: two binary searches over the uploaded indices name its queries,
+ * K[t] <= g < K[t + 1] (a tile without a kept base has none, so a query goes to the tile that holds its base), and a tile without
+ * queries leaves at once; the others rebuild the chunks' exclusive prefixes in LDS, a lane per query searches the 256 prefixes,
+ * finds the bit of the chunk's keep mask by popcounts and counts the sequence-mask bits below it; the same launch over R, with
+ * the queries' records as its queries, finds the sequence prefix at each of those records' starts (a lane per start of the
+ * tile, which answers the first query of its record; where raw_length is asked, once more for every record); a lane per query
+ * finds its record's first query and subtracts.  ONE upload, ONE host wait.  Work is balanced by input bytes.
+ * Loads are guarded by n_text; plain vector stores, no atomics.
+ * Refused with SPSP_ERR_ARG before any launch: a text that is not 16-byte aligned, indices that decrease, n_q > 0 with
+ * n_bases == 0, raw_length with room for no record.  Refused with SPSP_ERR_ARG behind the wait: an index >= n_bases, an n_bases
+ * that is not what the pass itself counts for the text, a record count that is not raw_length's room.  n_q == 0 launches nothing
+ * (and *n_rec is 0), unless raw_length is asked for. */
+int spsp_records_lift_device(spsp_ctx* ctx, const void* d_text, uint64_t n_text, uint64_t n_bases, const uint64_t* h_base /* n_q */, uint64_t n_q,
+                             uint64_t* raw /* n_q, caller's */, uint32_t* rec /* n_q, may be NULL */, uint64_t* raw_length /* n_rec, may be NULL */, uint32_t* n_rec);
+/* While the context's timing is on a lift records events between its launches; this reads the milliseconds added up since the
+ * last read and clears them. */
+int spsp_lift_stage_ms(spsp_ctx* ctx, double* ms /* 3: count, scan, answer */);
+/* The whole-file drivers: the arguments of the _segments entries plus raw, the outs raw_begin and raw_end (one per segment, 0 for
+ * a segment without bases; spsp_free; may be NULL; handed out only where raw is asked) and bed_bytes (the BED text's bytes before
+ * gzip; may be NULL).  With raw != 0, behind the last batch and the smoothing, the two ends of every segment that has bases go
+ * through ONE spsp_records_lift_device call on the second context, over the text it still holds, and <out_prefix>_segments.bed
+ * (".gz" appended when gz) is written beside the CSVs; every text is made before any file is written.  Both CSVs and the
+ * segments' FASTA of a run with raw are those of the run without.  The _segments entries are these with raw = 0. */
+int spsp_classify_files_raw(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys, uint32_t num,
+                            uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window, const char* what,
+                            spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records,
+                            spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth, const char* segments_what,
+                            uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out, int raw, uint64_t** raw_begin,
+                            uint64_t** raw_end, uint64_t* bed_bytes);
+int spsp_taxonomy_files_raw(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path, uint32_t min_keys,
+                            uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window, const char* what,
+                            spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win, uint64_t* n_records, spsp_segment_row** segments,
+                            uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth, const char* segments_what, uint64_t segments_min, int gz,
+                            uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out, int raw, uint64_t** raw_begin, uint64_t** raw_end, uint64_t* bed_bytes);
 
 #ifdef __cplusplus
 }

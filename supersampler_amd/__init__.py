@@ -189,6 +189,8 @@ ABI_SYMBOLS = [
     "spsp_windows_word_check_host", "spsp_records_windows_device", "spsp_windows_stage_ms", "spsp_classify_files_windows", "spsp_taxonomy_files_windows",
     "spsp_segments_plan_host", "spsp_windows_smooth_host", "spsp_segments_word_check_host", "spsp_segments_select_host", "spsp_segments_fasta_host",
     "spsp_segments_write_device", "spsp_segments_stage_ms", "spsp_classify_files_segments", "spsp_taxonomy_files_segments",
+    "spsp_lift_plan_host", "spsp_records_lift_host", "spsp_segments_bed_host", "spsp_records_lift_device", "spsp_lift_stage_ms", "spsp_classify_files_raw",
+    "spsp_taxonomy_files_raw",
 ]
 
 _lib = None
@@ -560,6 +562,22 @@ def lib():
         L.spsp_classify_files_segments.argtypes = L.spsp_classify_files_windows.argtypes + tail
         L.spsp_taxonomy_files_segments.restype = i32
         L.spsp_taxonomy_files_segments.argtypes = L.spsp_taxonomy_files_windows.argtypes + tail
+    if not LIB_OVERRIDDEN or hasattr(L, "spsp_records_lift_device"):
+        L.spsp_lift_plan_host.restype = i32
+        L.spsp_lift_plan_host.argtypes = [P(u32), P(u32)]
+        L.spsp_records_lift_host.restype = i32
+        L.spsp_records_lift_host.argtypes = [vp, u64, vp, u64, vp, vp, vp, P(u32)]
+        L.spsp_segments_bed_host.restype = i32
+        L.spsp_segments_bed_host.argtypes = [vp, u64, vp, vp, P(cp), u32, P(cp), cp, u32, P(vp), P(u64)]
+        L.spsp_records_lift_device.restype = i32
+        L.spsp_records_lift_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, vp, P(u32)]
+        L.spsp_lift_stage_ms.restype = i32
+        L.spsp_lift_stage_ms.argtypes = [vp, P(dbl)]
+        raw_tail = [i32, P(vp), P(vp), P(u64)]
+        L.spsp_classify_files_raw.restype = i32
+        L.spsp_classify_files_raw.argtypes = L.spsp_classify_files_segments.argtypes + raw_tail
+        L.spsp_taxonomy_files_raw.restype = i32
+        L.spsp_taxonomy_files_raw.argtypes = L.spsp_taxonomy_files_segments.argtypes + raw_tail
     _lib = L
     return L
 
@@ -1257,6 +1275,52 @@ def segments_select(segments, mosaic, n_bins, what, min_bases=1):
     _check(lib().spsp_segments_select_host(segments.ctypes.data if len(segments) else None, len(segments), mosaic.ctypes.data if len(mosaic) else None, len(mosaic), n_bins,
                                            what.encode(), min_bases, keep.ctypes.data, C.byref(n_kept), C.byref(n_bases)))
     return keep[:len(segments)], n_kept.value, n_bases.value
+
+
+def lift_plan():
+    """spsp_lift_plan_host: what the lift's kernels cut at -> dict(tile_bytes, chunk_bytes)"""
+    a, b = C.c_uint32(), C.c_uint32()
+    _check(lib().spsp_lift_plan_host(C.byref(a), C.byref(b)))
+    return {"tile_bytes": a.value, "chunk_bytes": b.value}
+
+
+def _lift_base(base):
+    base = np.ascontiguousarray(base, dtype=np.uint64)
+    if base.ndim != 1:
+        raise ValueError("lift: base is one global kept-base index per position")
+    return base
+
+
+def records_lift(text, base):
+    """spsp_records_lift_host: the rule "raw coordinates" as plain loops.  text: a FASTA / FASTQ text (bytes); base: GLOBAL kept-base
+    indices (rec_off[r] + p), non-decreasing -> (raw: np.uint64[n_q], record-relative positions among the record's sequence
+    characters; rec: np.uint32[n_q]; raw_length: np.uint64[n_rec], every record's sequence characters)"""
+    text = bytes(text)
+    base = _lift_base(base)
+    buf = (C.c_char * max(len(text), 1)).from_buffer_copy(text or b"\0")
+    n_q = len(base)
+    raw, rec = np.zeros(max(n_q, 1), dtype=np.uint64), np.zeros(max(n_q, 1), dtype=np.uint32)
+    n_rec = C.c_uint32(0)
+    _check(lib().spsp_records_lift_host(C.addressof(buf), len(text), None, 0, None, None, None, C.byref(n_rec)))   # the records first: raw_length's room
+    raw_length = np.zeros(n_rec.value, dtype=np.uint64)
+    _check(lib().spsp_records_lift_host(C.addressof(buf), len(text), base.ctypes.data if n_q else None, n_q, raw.ctypes.data, rec.ctypes.data, raw_length.ctypes.data,
+                                        C.byref(n_rec)))
+    return raw[:n_q], rec[:n_q], raw_length
+
+
+def segments_bed(segments, raw_begin, raw_end, record_names, call_names, last_name):
+    """spsp_segments_bed_host: the text of <prefix>_segments.bed -> bytes.  raw_begin, raw_end: one per segment"""
+    segments = np.ascontiguousarray(segments, dtype=SEGMENT_ROW_DTYPE)
+    raw_begin, raw_end = np.ascontiguousarray(raw_begin, dtype=np.uint64), np.ascontiguousarray(raw_end, dtype=np.uint64)
+    if len(raw_begin) != len(segments) or len(raw_end) != len(segments):
+        raise ValueError("segments_bed: one raw_begin and one raw_end per segment")
+    rn, _a = _paths_array(record_names)
+    cn, _b = _paths_array(call_names)
+    text, n = C.c_void_p(), C.c_uint64()
+    _check(lib().spsp_segments_bed_host(segments.ctypes.data if len(segments) else None, len(segments), raw_begin.ctypes.data if len(segments) else None,
+                                        raw_end.ctypes.data if len(segments) else None, rn, len(record_names), cn, last_name.encode(), len(call_names) + 1, C.byref(text),
+                                        C.byref(n)))
+    return _take(text, n.value)
 
 
 def segments_fasta(bases, rec_off, segments, record_names, call_names, last_name, keep=None):
@@ -2130,7 +2194,7 @@ class Context:
     union_plan = staticmethod(union_plan)
     pairs_names = staticmethod(pairs_names)
 
-    def _record_files(self, name, head, rest, outs, extract, gz, mates_path, split, window, window_call, default_call, smooth=0, segments=None, segments_min=1):
+    def _record_files(self, name, head, rest, outs, extract, gz, mates_path, split, window, window_call, default_call, smooth=0, segments=None, segments_min=1, raw=False):
         """the ladder classify_files and taxonomy_files share: the mode's checks, then spsp_<name>_files, _extract, _paired, _split
         or _windows.  head: (ctx, paths, n_ref, records_path), behind which the mates' path goes; rest: the pass's own arguments up
         to rate; outs: the rows' outputs, the count last; default_call: the word a windowed run calls by where window_call is None"""
@@ -2147,7 +2211,13 @@ class Context:
             first, n_rec, seg, n_seg, mos = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64(), C.c_void_p()
             common = (*head, *rest, window, (window_call or default_call).encode(), *refs, C.byref(first), C.byref(n_rec), C.byref(seg), C.byref(n_seg), C.byref(mos))
             changed, written, text_bytes = C.c_uint64(), C.c_uint64(), C.c_uint64()
-            if smooth or segments is not None or segments_min != 1:
+            raw_b, raw_e, bed_bytes = C.c_void_p(), C.c_void_p(), C.c_uint64()
+            if raw:
+                if not 0 <= smooth <= 0x7FFFFFFF or not 0 <= segments_min < 1 << 64:
+                    raise ValueError("%s: smooth is 0 .. 2147483647, segments_min is not negative" % who)
+                _check(entry("_raw")(*common, smooth, None if segments is None else segments.encode(), segments_min, gz, C.byref(changed), C.byref(written),
+                                     C.byref(text_bytes), 1, C.byref(raw_b), C.byref(raw_e), C.byref(bed_bytes)))
+            elif smooth or segments is not None or segments_min != 1:
                 if not 0 <= smooth <= 0x7FFFFFFF or not 0 <= segments_min < 1 << 64:
                     raise ValueError("%s: smooth is 0 .. 2147483647, segments_min is not negative" % who)
                 _check(entry("_segments")(*common, smooth, None if segments is None else segments.encode(), segments_min, gz, C.byref(changed), C.byref(written),
@@ -2156,8 +2226,12 @@ class Context:
                 _check(entry("_windows")(*common))
             self.last_windows = _windows_result(first, n_rec.value, seg, n_seg.value, mos)
             self.last_windows.update(changed=changed.value, written=written.value, bytes_out=text_bytes.value)
-        elif window_call is not None or smooth or segments is not None:
-            raise ValueError("%s: window_call, smooth and segments need window" % who)
+            if raw:
+                n_seg = len(self.last_windows["segments"])
+                self.last_windows.update(raw_begin=np.frombuffer(_take(raw_b, n_seg * 8), dtype=np.uint64).copy(),
+                                         raw_end=np.frombuffer(_take(raw_e, n_seg * 8), dtype=np.uint64).copy(), bed_bytes=bed_bytes.value)
+        elif window_call is not None or smooth or segments is not None or raw:
+            raise ValueError("%s: window_call, smooth, segments and raw need window" % who)
         elif split is not None:
             if extract is not None:
                 raise ValueError("%s: split writes every record and extract one subset: one of the two" % who)
@@ -2173,7 +2247,7 @@ class Context:
             self.last_extract = {"n_kept": kept.value, "bytes_out": out_bytes.value}
 
     def classify_files(self, paths, records_path, prefix, top=1, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
-                       split=None, window=None, window_call=None, smooth=0, segments=None, segments_min=1):
+                       split=None, window=None, window_call=None, smooth=0, segments=None, segments_min=1, raw=False):
         """spsp_classify_files: the sketch files of the references and a FASTA / FASTQ file of records (gzip or plain) ->
         <prefix>_classify.csv.gz, <prefix>_classify_summary.csv.gz and (records, hits[n, top]).  rate: as compare_files (0.0, a
         rate, or "auto"); sketches of different rates need one.  extract: a word (matched, unmatched, best=<j>, listed=<j>) --
@@ -2189,11 +2263,14 @@ class Context:
         (spsp_classify_files_segments), a run of at most q windows between two longer runs of one call takes that call.  segments: a
         word (all, called, none, call=<b>, not=<b>, major, minor) -- the segments it names of at least segments_min bases are written
         as <prefix>_segments.fa (".gz" appended when gz), one FASTA record <name>:<begin + 1>-<end> each; last_windows gains changed
-        (windows the smoothing changed), written (segments) and bytes_out (the text's bytes)"""
+        (windows the smoothing changed), written (segments) and bytes_out (the text's bytes).  raw: with window
+        (spsp_classify_files_raw), the segments' raw intervals -- positions among the sequence characters of the records file's own
+        records, N and lower case counted -- are made on the device and written as <prefix>_segments.bed (".gz" appended when gz);
+        last_windows gains raw_begin, raw_end (one per segment) and bed_bytes"""
         arr, _alive = _paths_array(paths)
         recs, hits, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
         self._record_files("classify", (self._h, arr, len(paths), str(records_path).encode()), (top, min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate)),
-                           (recs, hits, n), extract, gz, mates_path, split, window, window_call, "best", smooth, segments, segments_min)
+                           (recs, hits, n), extract, gz, mates_path, split, window, window_call, "best", smooth, segments, segments_min, raw)
         return (np.frombuffer(_take(recs, n.value * CLASSIFY_RECORD_DTYPE.itemsize), dtype=CLASSIFY_RECORD_DTYPE).copy(),
                 np.frombuffer(_take(hits, n.value * top * CLASSIFY_HIT_DTYPE.itemsize), dtype=CLASSIFY_HIT_DTYPE).copy().reshape(n.value, top))
 
@@ -2277,6 +2354,33 @@ class Context:
 
     segments_plan = staticmethod(segments_plan)
 
+    def records_lift_device(self, d_text, n_text, n_bases, base, n_rec=None):
+        """spsp_records_lift_device: the raw text in HBM (16-byte aligned), the kept bases the ingest counted for it, and GLOBAL
+        kept-base indices (rec_off[r] + p, non-decreasing) -> (raw: np.uint64[n_q], rec: np.uint32[n_q], raw_length:
+        np.uint64[n_rec], every record's sequence characters).  n_rec: the records the ingest counted, which is raw_length's room
+        (the lengths need it before the call's one wait); without it records_extents_device counts them first, one more call and
+        wait.  self.last_lift_records: the records the pass itself counted"""
+        base = _lift_base(base)
+        n_q = len(base)
+        raw, rec = np.zeros(max(n_q, 1), dtype=np.uint64), np.zeros(max(n_q, 1), dtype=np.uint32)
+        if n_rec is None:
+            n_rec = self.records_extents_device(d_text, n_text)[1]
+        raw_length = np.zeros(max(n_rec, 1), dtype=np.uint64)
+        room = C.c_uint32(n_rec)
+        _check(lib().spsp_records_lift_device(self._h, d_text, n_text, n_bases, base.ctypes.data if n_q else None, n_q, raw.ctypes.data, rec.ctypes.data,
+                                              raw_length.ctypes.data, C.byref(room)))
+        self.last_lift_records = room.value
+        return raw[:n_q], rec[:n_q], raw_length[:n_rec]
+
+    def lift_stage_ms(self):
+        """spsp_lift_stage_ms: with timing_enable() on, the milliseconds of the lift calls' launches since the last read ->
+        dict(count, scan, answer)"""
+        ms = (C.c_double * 3)()
+        _check(lib().spsp_lift_stage_ms(self._h, ms))
+        return dict(zip(("count", "scan", "answer"), ms))
+
+    lift_plan = staticmethod(lift_plan)
+
     def split_stage_ms(self):
         """spsp_split_stage_ms: with timing_enable() on, the milliseconds of the split calls' launches since the last read ->
         dict(starts, runs, order, offsets, copy)"""
@@ -2321,7 +2425,7 @@ class Context:
         return dict(zip(("probe", "route", "wave_form", "workgroup_form"), ms))
 
     def taxonomy_files(self, paths, records_path, lineages_path, prefix, min_keys=1, num=0, den=1, precision=6, rate=0.0, extract=None, gz=True, mates_path=None,
-                       split=None, window=None, window_call=None, smooth=0, segments=None, segments_min=1):
+                       split=None, window=None, window_call=None, smooth=0, segments=None, segments_min=1, raw=False):
         """spsp_taxonomy_files: the sketch files of the references, a FASTA / FASTQ file of records (gzip or plain) and the lineage
         file of the references -> <prefix>_taxonomy.csv.gz, <prefix>_taxonomy_report.csv.gz and the records.  rate: as
         classify_files (0.0, a rate, or "auto"); sketches of different rates need one.  extract: a word (classified, unclassified,
@@ -2330,12 +2434,13 @@ class Context:
         (spsp_taxonomy_files_paired).  split: a word (taxon, depth=<d>) -- spsp_taxonomy_files_split: every record goes to
         <prefix>_split_<t>.fa or .fq of its node (or _split_unclassified.*), as classify_files; self.last_split.  window,
         window_call (taxon, depth=<d>): spsp_taxonomy_files_windows, as classify_files; self.last_windows.  smooth, segments,
-        segments_min: spsp_taxonomy_files_segments, as classify_files (<b> is a node's number)"""
+        segments_min: spsp_taxonomy_files_segments, as classify_files (<b> is a node's number).  raw: spsp_taxonomy_files_raw, as
+        classify_files"""
         arr, _alive = _paths_array(paths)
         recs, n = C.c_void_p(), C.c_uint64()
         self._record_files("taxonomy", (self._h, arr, len(paths), str(records_path).encode()),
                            (str(lineages_path).encode(), min_keys, num, den, precision, prefix.encode(), 0, _rate_arg(rate)), (recs, n), extract, gz, mates_path, split,
-                           window, window_call, "taxon", smooth, segments, segments_min)
+                           window, window_call, "taxon", smooth, segments, segments_min, raw)
         return np.frombuffer(_take(recs, n.value * TAXONOMY_RECORD_DTYPE.itemsize), dtype=TAXONOMY_RECORD_DTYPE).copy()
 
     def depth_begin(self):

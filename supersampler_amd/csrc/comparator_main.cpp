@@ -139,12 +139,13 @@ int main(int argc, char** argv) {
     bool smooth = false;
     string segments_arg;             // -Z <what>[:<min_bases>]: with -y, the segments the word names are written as <prefix>_segments.fa.gz (likewise)
     bool segments = false;
+    bool raw_coords = false;         // -O: with -y, the segments in the records file's own coordinates as <prefix>_segments.bed.gz (-u: plain)
     vector<string> reads_files;      // -D <reads file> [-D <more> ...] [-W <min_count>]: neither letter is in the reference's option string
     bool dp_min_seen = false;
     long long dp_min_count = 1;
     bool profile = false;            // -B <min_keys>: the profile behind the depth of -D (not in the reference's option string either)
     long long pf_min_keys = 1;
-    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:j:y:Q:Z:")) != -1) {
+    while ((ch = getopt(argc, argv, "hdag:q:k:m:n:s:t:b:e:f:i:p:o:c:C:N:J:K:I:P:r:R:w:l:L:S:E:A:z:G:T:U:MX:Y:V:D:W:B:H:F:ux:j:y:Q:Z:O")) != -1) {
         switch (ch) {
             case 'D': reads_files.push_back(optarg); break;
             case 'W': {
@@ -177,6 +178,7 @@ int main(int argc, char** argv) {
                 break;
             }
             case 'Z': segments_arg = optarg; segments = true; break;
+            case 'O': raw_coords = true; break;
             case 'Y': {
                 char* e = nullptr;
                 cf_top = strtoll(optarg, &e, 10);
@@ -318,7 +320,7 @@ int main(int argc, char** argv) {
     if (split && !classify) { cout << "-j splits the records of -X <records file> into one file per reference or taxon: it needs -X" << endl; return 1; }
     if (split && extract) { cout << "-j writes every record and -F one subset of them: one of the two in a run" << endl; return 1; }
     if (split && spsp_split_word_check_host(split_what.c_str(), taxonomy ? 1 : 0) != SPSP_OK) { cout << "-j: " << spsp_last_error() << endl; return 1; }
-    if (extract_plain && !extract && !split && !segments) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
+    if (extract_plain && !extract && !split && !segments && !raw_coords) { cout << "-u writes the records of -F plain instead of gzipped: it needs -F" << endl; return 1; }
     if (extract && spsp_extract_word_check_host(extract_what.c_str(), taxonomy ? 1 : 0, 0xffffffffu) != SPSP_OK) { cout << "-F: " << spsp_last_error() << endl; return 1; }
     long long window_width = 0;
     string window_word;
@@ -339,6 +341,7 @@ int main(int argc, char** argv) {
     }
     if (smooth && !windows) { cout << "-Q absorbs stray windows into the segments of -y <W>: it needs -y" << endl; return 1; }
     if (segments && !windows) { cout << "-Z writes segments of -y <W> out as FASTA: it needs -y" << endl; return 1; }
+    if (raw_coords && !windows) { cout << "-O writes the segments of -y <W> in the coordinates of the records file as BED: it needs -y" << endl; return 1; }
     string segments_word;
     unsigned long long segments_min = 1;
     if (segments) {                                        // (<b> against the references: once they are counted, below)
@@ -408,6 +411,7 @@ int main(int argc, char** argv) {
              << "-y <W>[:<word>] Windows: cut every record of -X <records file> into windows of W bases (overlapping by k - 1), call each as a record (best; with -H: taxon, depth=<d>) and write <prefix>_segments.csv.gz (stretches with one call) and <prefix>_mosaic.csv.gz (one line per record) in the place of the per-record CSVs; positions count the bases A, C, G, T only" << endl
              << "-Q <q> With -y: a run of at most q windows between two runs of one call, each longer than q windows, takes that call (its support counts as 0); 0 changes nothing" << endl
              << "-Z <what>[:<min_bases>] With -y: write the segments the word names (all, called, none, call=<b>, not=<b>, major, minor) of at least min_bases bases as <prefix>_segments.fa.gz, one FASTA record <name>:<begin + 1>-<end> per segment, 80 bases a line; -u writes it plain" << endl
+             << "-O With -y: write the segments in the coordinates of the records file itself (counting N, IUPAC codes and lower case, as samtools faidx does) as <prefix>_segments.bed.gz: name, raw_begin, raw_end, call_name, 0, ., segment, begin, end, windows, support; -u writes it plain" << endl
              << "-x Mates file: with -X <records file>, record p of the two files is one pair, classified by the keys of both mates; -F then writes <prefix>_extract_1.* and <prefix>_extract_2.*" << endl
              << "Ouput arguments:" << endl
              << "-m Minimum value to be output (0.0)" << endl
@@ -480,15 +484,15 @@ int main(int argc, char** argv) {
         spsp_ctx* ctx = nullptr;
         int rc = spsp_create(devices[0], nullptr, &ctx);
         if (rc == SPSP_OK && windows && taxonomy)
-            rc = spsp_taxonomy_files_segments(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den,
-                                              (int)p, output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                                              nullptr, nullptr, (uint32_t)smooth_q, segments ? segments_word.c_str() : nullptr, segments_min, extract_plain ? 0 : 1, nullptr,
-                                              nullptr, nullptr);
+            rc = spsp_taxonomy_files_raw(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), lineages_file.c_str(), (uint32_t)cf_min_keys, nb_num, nb_den,
+                                         (int)p, output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, (uint32_t)smooth_q, segments ? segments_word.c_str() : nullptr, segments_min, extract_plain ? 0 : 1, nullptr,
+                                         nullptr, nullptr, raw_coords ? 1 : 0, nullptr, nullptr, nullptr);
         else if (rc == SPSP_OK && windows)
-            rc = spsp_classify_files_segments(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den, (int)p,
-                                              output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                              nullptr, nullptr, (uint32_t)smooth_q, segments ? segments_word.c_str() : nullptr, segments_min, extract_plain ? 0 : 1, nullptr,
-                                              nullptr, nullptr);
+            rc = spsp_classify_files_raw(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), (uint32_t)cf_top, (uint32_t)cf_min_keys, nb_num, nb_den, (int)p,
+                                         output_name.c_str(), 1, rate, (uint64_t)window_width, window_word.c_str(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, (uint32_t)smooth_q, segments ? segments_word.c_str() : nullptr, segments_min, extract_plain ? 0 : 1, nullptr,
+                                         nullptr, nullptr, raw_coords ? 1 : 0, nullptr, nullptr, nullptr);
         else if (rc == SPSP_OK && split && taxonomy)
             rc = spsp_taxonomy_files_split(ctx, paths.data(), (uint32_t)paths.size(), records_file.c_str(), paired ? mates_file.c_str() : nullptr, lineages_file.c_str(),
                                            (uint32_t)cf_min_keys, nb_num, nb_den, (int)p, output_name.c_str(), 1, rate, split_what.c_str(), extract_plain ? 0 : 1, nullptr,

@@ -287,7 +287,8 @@ void spsp_destroy(spsp_ctx* c) {
                       &c->pf_u, &c->pf_dead, &c->pf_assigned, &c->pf_state, &c->pf_rounds, &c->pf_rows,
                       &c->tx_tree, &c->tx_key_node, &c->tx_entry_node,
                       &c->ex_words, &c->ex_tiles, &c->ex_bases, &c->ex_begin, &c->ex_keep, &c->ex_runs, &c->ex_out, &c->sp_bin, &c->sp_runs, &c->sp_off,
-                      &c->un_mn, &c->un_lo, &c->un_hi, &c->un_work, &c->wn_words, &c->wn_tiles, &c->wn_rec, &c->wn_off, &c->wn_src, &c->wn_out, &c->sg_tab, &c->sg_out};
+                      &c->un_mn, &c->un_lo, &c->un_hi, &c->un_work, &c->wn_words, &c->wn_tiles, &c->wn_rec, &c->wn_off, &c->wn_src, &c->wn_out, &c->sg_tab, &c->sg_out,
+                      &c->lf_tiles, &c->lf_entry, &c->lf_pre, &c->lf_q, &c->lf_work, &c->lf_out};
     for (DevBuf* b : bufs) b->release();
     for (hipEvent_t& e : c->cf_clock.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (hipEvent_t& e : c->dp_events) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -298,6 +299,7 @@ void spsp_destroy(spsp_ctx* c) {
     for (hipEvent_t& e : c->sp_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (hipEvent_t& e : c->wn_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (hipEvent_t& e : c->sg_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    for (hipEvent_t& e : c->lf_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (auto* v : {&c->dp_add_used, &c->dp_add_spare})
         for (auto& ev : *v) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     devbuf_flush_retired();

@@ -504,6 +504,7 @@ struct TextSide {
             // context's windows buffer, in the form the ingest wrote).  The real records' offsets and first_win stay with the run
             windows->rec_off.assign((size_t)n_rec + 1, 0);
             windows->first_win.assign((size_t)n_rec + 1, 0);
+            windows->d_text = side->i_text.as<uint8_t>(); windows->n_text = n_text;   // (the upload above: read again by the lift behind the last batch)
             windows->d_bases = d_bases; windows->n_bases = n_bases; windows->packed = packed;   // (the ingest's buffer: it stays as it is until the side context ends)
             SPSP_HIP(hipMemcpyAsync(windows->rec_off.data(), d_off, windows->rec_off.size() * 8, hipMemcpyDeviceToHost, side->stream));   // (the expansion waits)
             uint8_t* w_bases = nullptr; uint64_t* w_off = nullptr; uint64_t w_n = 0, n_win = 0;
@@ -834,22 +835,25 @@ extern "C" int spsp_classify_files_split(spsp_ctx* ctx, const char* const* index
                                 n_bins_written, bytes_out);
 }
 
-extern "C" int spsp_classify_files_segments(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+extern "C" int spsp_classify_files_raw(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
                                             uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
                                             const char* what, spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win,
                                             uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth,
-                                            const char* segments_what, uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out) {
+                                            const char* segments_what, uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out, int raw,
+                                       uint64_t** raw_begin, uint64_t** raw_end, uint64_t* bed_bytes) {
     if (rows) *rows = nullptr;
     if (hits) *hits = nullptr;
     if (first_win) *first_win = nullptr;
     if (segments) *segments = nullptr;
     if (mosaic) *mosaic = nullptr;
-    for (uint64_t* n : {n_windows, n_records, n_segments, n_changed, n_written, bytes_out}) if (n) *n = 0;
+    if (raw_begin) *raw_begin = nullptr;
+    if (raw_end) *raw_end = nullptr;
+    for (uint64_t* n : {n_windows, n_records, n_segments, n_changed, n_written, bytes_out, bed_bytes}) if (n) *n = 0;
     const RecordFront front{ctx, index_paths, nullptr, false, false, n_ref, top, min_keys, num, den};
     ClassifyPass pass(front);
     RecordsOut out;
     RecordsAsk ask = records_ask(&records_path, nullptr, kRmWindows, what, gz, window, precision, out_prefix, chatter, rate);
-    ask.smooth = smooth; ask.segments_what = segments_what; ask.segments_min = segments_min;
+    ask.smooth = smooth; ask.segments_what = segments_what; ask.segments_min = segments_min; ask.raw = raw != 0;
     if (const int rc = record_files_entry(front, pass, ask, &out)) return rc;
     const WindowsRun& run = out.windows;
     if (n_windows) *n_windows = pass.recs.size();
@@ -858,12 +862,25 @@ extern "C" int spsp_classify_files_segments(spsp_ctx* ctx, const char* const* in
     if (n_changed) *n_changed = run.n_changed;
     if (n_written) *n_written = run.n_written;
     if (bytes_out) *bytes_out = run.fasta.size();
+    if (bed_bytes) *bed_bytes = run.bed.size();
     const RowsGift gifts[] = {{(void**)rows, pass.recs.data(), pass.recs.size() * sizeof(spsp_classify_record)},
                               {(void**)hits, pass.hits.data(), pass.hits.size() * sizeof(spsp_classify_hit)},
                               {(void**)first_win, run.first_win.data(), run.first_win.size() * sizeof(uint32_t)},
                               {(void**)segments, run.segments.data(), run.segments.size() * sizeof(spsp_segment_row)},
-                              {(void**)mosaic, run.mosaic.data(), run.mosaic.size() * sizeof(spsp_mosaic_row)}};
-    return give_rows_all(gifts, 5);
+                              {(void**)mosaic, run.mosaic.data(), run.mosaic.size() * sizeof(spsp_mosaic_row)},
+                              {(void**)(raw ? raw_begin : nullptr), run.raw_begin.data(), run.raw_begin.size() * 8},
+                              {(void**)(raw ? raw_end : nullptr), run.raw_end.data(), run.raw_end.size() * 8}};
+    return give_rows_all(gifts, 7);
+}
+
+extern "C" int spsp_classify_files_segments(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,
+                                            uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate, uint64_t window,
+                                            const char* what, spsp_classify_record** rows, spsp_classify_hit** hits, uint64_t* n_windows, uint32_t** first_win,
+                                            uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth,
+                                            const char* segments_what, uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out) {
+    return spsp_classify_files_raw(ctx, index_paths, n_ref, records_path, top, min_keys, num, den, precision, out_prefix, chatter, rate, window, what, rows, hits, n_windows,
+                                   first_win, n_records, segments, n_segments, mosaic, smooth, segments_what, segments_min, gz, n_changed, n_written, bytes_out, 0, nullptr,
+                                   nullptr, nullptr);
 }
 
 extern "C" int spsp_classify_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, uint32_t top, uint32_t min_keys,

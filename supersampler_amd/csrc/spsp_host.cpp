@@ -3756,3 +3756,93 @@ extern "C" int spsp_segments_fasta_host(const uint8_t* bases, uint64_t n_bases, 
     }
     return give_text(s, text, len);
 }
+
+// ---- raw coordinates (the rule: include/spsp.h, "raw coordinates")
+
+extern "C" int spsp_lift_plan_host(uint32_t* tile_bytes, uint32_t* chunk_bytes) {
+    if (tile_bytes) *tile_bytes = spsp::kLfTile;
+    if (chunk_bytes) *chunk_bytes = spsp::kLfChunk;
+    return SPSP_OK;
+}
+
+// the rule as plain loops, a line at a time
+extern "C" int spsp_records_lift_host(const uint8_t* text, uint64_t n, const uint64_t* h_base, uint64_t n_q, uint64_t* raw, uint32_t* rec, uint64_t* raw_length,
+                                      uint32_t* n_rec) {
+    using namespace spsp;
+    if (!n_rec || (n && !text) || (n_q && (!h_base || !raw))) { set_error("NULL argument"); return SPSP_ERR_ARG; }
+    const uint32_t cap = raw_length ? *n_rec : 0u;
+    *n_rec = 0;
+    for (uint64_t q = 1; q < n_q; ++q)
+        if (h_base[q] < h_base[q - 1]) { set_error("lift: the base indices must not decrease (index %llu)", (unsigned long long)q); return SPSP_ERR_ARG; }
+    const bool fastq = n > 0 && text[0] == '@';
+    std::vector<uint64_t> lens;
+    uint64_t kept = 0, seq = 0, q = 0, line = 0, p = 0;
+    while (p < n) {
+        const uint8_t* nl = (const uint8_t*)memchr(text + p, '\n', (size_t)(n - p));
+        const uint64_t e = nl ? (uint64_t)(nl - text) : n;
+        bool data;
+        if (fastq) {
+            // line 4r begins record r, unless it is empty (the blank tail of a text): it is no sequence line either way
+            if (line % 4 == 0 && line > 0 && text[p] != '\n' && text[p] != '\r') { lens.push_back(seq); seq = 0; }
+            data = line % 4 == 1;
+        } else {
+            const bool begins = line == 0 || text[p] == '>' || text[p] == 0xFFu;
+            if (begins && line > 0) { lens.push_back(seq); seq = 0; }
+            data = !begins;
+        }
+        if (data)
+            for (uint64_t i = p; i < e; ++i) {
+                const uint8_t c = text[i];
+                if (c < 0x21 || c > 0x7e) continue;
+                const uint8_t u = c & 0xDFu;
+                if (u == 'A' || u == 'C' || u == 'G' || u == 'T') {
+                    for (; q < n_q && h_base[q] == kept; ++q) { raw[q] = seq; if (rec) rec[q] = (uint32_t)lens.size(); }
+                    ++kept;
+                }
+                ++seq;
+            }
+        p = e + 1;
+        ++line;
+    }
+    lens.push_back(seq);
+    if (lens.size() > 0xfffffff0ull) { set_error("too many records for one call"); return SPSP_ERR_OVERFLOW; }
+    *n_rec = (uint32_t)lens.size();
+    if (q < n_q) { set_error("lift: base index %llu is not below the %llu bases", (unsigned long long)h_base[q], (unsigned long long)kept); return SPSP_ERR_ARG; }
+    if (raw_length) {
+        if (cap != *n_rec) { set_error("lift: the text holds %u record(s), raw_length has room for %u", *n_rec, cap); return SPSP_ERR_ARG; }
+        memcpy(raw_length, lens.data(), lens.size() * 8);
+    }
+    return SPSP_OK;
+}
+
+// name, raw_begin, raw_end, call_name, 0, ., segment, begin, end, windows, support -- BED6 and five columns, tab-separated
+extern "C" int spsp_segments_bed_host(const spsp_segment_row* segments, uint64_t n_segments, const uint64_t* raw_begin, const uint64_t* raw_end,
+                                      const char* const* record_names, uint32_t n_rec, const char* const* call_names, const char* last_name, uint32_t n_bins, char** text,
+                                      uint64_t* len) {
+    using namespace spsp;
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!text || !len || !last_name || (n_segments && (!segments || !record_names || !raw_begin || !raw_end)) || (n_bins > 1 && !call_names)) {
+        set_error("NULL argument");
+        return SPSP_ERR_ARG;
+    }
+    if (n_bins == 0) { set_error("segments: n_bins must be 1 or more"); return SPSP_ERR_ARG; }
+    std::string s;
+    for (uint64_t i = 0; i < n_segments; ++i) {
+        const spsp_segment_row& g = segments[i];
+        if (g.record >= n_rec || g.call >= n_bins || g.begin > g.end) {
+            set_error("segments: segment %llu names record %u or call %u out of range, or ends in front of its begin", (unsigned long long)i, g.record, g.call);
+            return SPSP_ERR_ARG;
+        }
+        if (g.begin == g.end) continue;                    // no bases: no raw interval
+        if (raw_end[i] <= raw_begin[i] || raw_end[i] - raw_begin[i] < g.end - g.begin) {
+            set_error("segments: the raw interval of segment %llu is shorter than its %llu base(s)", (unsigned long long)i, (unsigned long long)(g.end - g.begin));
+            return SPSP_ERR_ARG;
+        }
+        std::string call = g.call + 1 == n_bins ? last_name : call_names[g.call];
+        for (char& c : call) if (c == '\t') c = ' ';
+        s += std::string(record_names[g.record]) + "\t" + std::to_string(raw_begin[i]) + "\t" + std::to_string(raw_end[i]) + "\t" + call + "\t0\t.\t" +
+             std::to_string(g.segment) + "\t" + std::to_string(g.begin) + "\t" + std::to_string(g.end) + "\t" + std::to_string(g.windows) + "\t" + std::to_string(g.support) + "\n";
+    }
+    return give_text(s, text, len);
+}

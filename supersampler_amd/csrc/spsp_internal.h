@@ -380,6 +380,12 @@ struct spsp_ctx {
     hipEvent_t sg_ev[2] = {};            // while timing is on: in front of the launch and behind it
     bool sg_marked = false;
     double sg_ms = 0;                    // spsp_segments_stage_ms: the write
+    // raw coordinates (spsp_lift.hip): the tiles' summaries, their entry states, the prefixes K | S | R (n_tiles + 1 each), the
+    // uploaded indices, the work arrays (sequence rank, record and record start per query, then every record's start) and the
+    // outputs (raw, the lengths, the records as 32-bit words)
+    spsp::DevBuf lf_tiles, lf_entry, lf_pre, lf_q, lf_work, lf_out;
+    hipEvent_t lf_ev[4] = {};            // while timing is on: in front of the count, the scan, the answer, and behind it
+    double lf_ms[3] = {};                // spsp_lift_stage_ms: count, scan, answer
 };
 
 namespace spsp {
@@ -600,6 +606,8 @@ struct RecordsAsk {
     uint32_t smooth = 0;
     const char* segments_what = nullptr;
     uint64_t segments_min = 1;
+    // ... raw: the segments' raw intervals are made (one lift on the side context) and written as <out_prefix>_segments.bed
+    int raw = 0;
 };
 // an entry's ask: records_path is the address of the entry's own argument, which outlives the call
 inline RecordsAsk records_ask(const char* const* records_path, const char* mates_path, RecordsMode mode, const char* what, int gz, uint64_t window, int precision,
@@ -676,6 +684,15 @@ struct WindowsRun {
     std::vector<uint8_t> fasta;
     bool want_fasta = false;
     uint64_t n_changed = 0, n_written = 0, bases_written = 0;
+    // raw coordinates: the raw text on the side context (the ingest's upload, which nothing behind it writes: DESIGN 6zc); per
+    // segment its raw interval (0, 0 for a segment without bases), the BED text, the segments lifted and the sequence characters
+    // by which the raw intervals exceed the kept ones
+    const uint8_t* d_text = nullptr;
+    uint64_t n_text = 0;
+    bool want_bed = false;
+    std::vector<uint64_t> raw_begin, raw_end;
+    std::string bed;
+    uint64_t n_lifted = 0, raw_excess = 0;
 };
 // what the road leaves behind for the driver and the entry.  names: the records' names as the host reads them from the header
 // lines (a pair: the mates' common names) -- then a text with another number of header lines than the device finds records is
@@ -878,12 +895,20 @@ constexpr uint32_t kSgLdsSegs = 512;                       // segments of a stre
 int segments_write_impl(spsp_ctx* ctx, const uint8_t* d_bases, uint64_t n_bases, bool packed, const uint64_t* h_src, const uint64_t* h_len, const uint8_t* h_headers,
                         const uint64_t* h_hdr_off, uint64_t n_seg, uint8_t** d_out, uint64_t* n_out);
 // the tail of a windowed run behind its last batch, with the side context still alive: the calls smoothed, segments and mosaic, the
-// two CSV texts, and where a word asks for it the selection, the headers, the write on `side` (ordered behind ctx by the caller)
+// two CSV texts, where ask.raw is set the segments' ends through ONE records_lift_impl on `side` (its own wait) and the BED text,
+// and where a word asks for it the selection, the headers, the write on `side` (ordered behind ctx by the caller)
 // and the copy back, with one wait.  Nothing is written to disk here: windows_files does that, every text being made
 int windows_tail(spsp_ctx* side, WindowsRun* run, const RecordsAsk& ask, uint32_t k, std::vector<uint32_t>& call, const std::vector<uint32_t>& keys,
                  const std::vector<uint32_t>& hit_keys, std::vector<uint32_t>& support, uint32_t n_bins, const std::vector<std::string>& names,
                  const char* const* call_names, const char* last_name);
 int windows_files(spsp_ctx* ctx, WindowsRun* run, const RecordsAsk& ask, double t_csv);
+// spsp_lift.hip: kept-base indices lifted to positions among the sequence characters of the raw text (the rule: include/spsp.h,
+// "raw coordinates").  What the kernels cut at (spsp_lift_plan_host, spsp_host.cpp): the ingest's tile and chunk
+constexpr uint32_t kLfTile = 4096, kLfChunk = 16, kLfThreads = kLfTile / kLfChunk;
+// raw[q] (and rec[q], raw_length[r] where asked) in the caller's host arrays, with one host wait.  *n_rec: in, where raw_length
+// is given, the records it has room for; out, the records of the text
+int records_lift_impl(spsp_ctx* ctx, const uint8_t* d_text, uint64_t n_text, uint64_t n_bases, const uint64_t* h_base, uint64_t n_q, uint64_t* raw, uint32_t* rec,
+                      uint64_t* raw_length, uint32_t* n_rec);
 // the selection of an ask held before any file is read (spsp_host.cpp); the header of one segment's FASTA record
 int segments_ask_check(const RecordsAsk& ask, int taxonomy, uint32_t n_bins);
 void segment_header(const spsp_segment_row& g, const char* name, const char* const* call_names, const char* last_name, uint32_t n_bins, std::string* s);

@@ -229,6 +229,33 @@ int windows_tail(spsp_ctx* side, WindowsRun* run, const RecordsAsk& ask, uint32_
     if ((rc = spsp_mosaic_csv_host(run->mosaic.data(), n_rec, name_ptr.data(), call_names, last_name, n_bins, ask.precision, &mos_text, &mos_len))) return rc;
     run->mos_csv.assign(mos_text, (size_t)mos_len);
     free(mos_text);
+    run->want_bed = ask.raw != 0;
+    if (ask.raw) {
+        // the two ends of every segment that has bases, as global kept-base indices: ascending as they come, the segments being in
+        // record order and within a record in position order.  ONE lift over the raw text the side context still holds
+        std::vector<uint64_t> at;
+        at.reserve((size_t)n_segs * 2 + 1);
+        for (const spsp_segment_row& g : run->segments)
+            if (g.end > g.begin) { at.push_back(run->rec_off[g.record] + g.begin); at.push_back(run->rec_off[g.record] + g.end - 1); }
+        std::vector<uint64_t> lifted(at.size() + 1, 0);
+        uint32_t text_rec = 0;
+        if ((rc = records_lift_impl(side, run->d_text, run->n_text, run->n_bases, at.data(), at.size(), lifted.data(), nullptr, nullptr, &text_rec))) return rc;
+        run->raw_begin.assign((size_t)n_segs, 0); run->raw_end.assign((size_t)n_segs, 0);
+        run->n_lifted = 0; run->raw_excess = 0;
+        size_t j = 0;
+        for (uint64_t i = 0; i < n_segs; ++i) {
+            const spsp_segment_row& g = run->segments[i];
+            if (g.end == g.begin) continue;
+            run->raw_begin[i] = lifted[j]; run->raw_end[i] = lifted[j + 1] + 1; j += 2;
+            ++run->n_lifted;
+            run->raw_excess += (run->raw_end[i] - run->raw_begin[i]) - (g.end - g.begin);
+        }
+        char* bed_text = nullptr; uint64_t bed_len = 0;
+        if ((rc = spsp_segments_bed_host(run->segments.data(), n_segs, run->raw_begin.data(), run->raw_end.data(), name_ptr.data(), n_rec, call_names, last_name, n_bins,
+                                         &bed_text, &bed_len))) return rc;
+        run->bed.assign(bed_text, (size_t)bed_len);
+        free(bed_text);
+    }
     if (!ask.segments_what) return SPSP_OK;
     std::vector<uint8_t> keep(n_segs ? (size_t)n_segs : 1, 0);
     if ((rc = spsp_segments_select_host(run->segments.data(), n_segs, n_rec ? run->mosaic.data() : &none_row, n_rec, n_bins, ask.segments_what, ask.segments_min,
@@ -268,6 +295,14 @@ int windows_files(spsp_ctx* ctx, WindowsRun* run, const RecordsAsk& ask, double 
         ctx->stages.csv_gzip_s += now_s() - t;
         if (rc) return rc;
     }
+    std::string bed_path;
+    if (run->want_bed) {
+        bed_path = std::string(ask.out_prefix) + "_segments.bed" + (ask.gz ? ".gz" : "");
+        const double t = now_s();
+        rc = write_bytes(bed_path.c_str(), reinterpret_cast<const uint8_t*>(run->bed.data()), run->bed.size(), ask.gz);
+        ctx->stages.csv_gzip_s += now_s() - t;
+        if (rc) return rc;
+    }
     if (!ask.chatter) return SPSP_OK;
     const uint32_t n_rec = (uint32_t)(run->rec_off.size() - 1);
     uint64_t mixed = 0;
@@ -278,6 +313,9 @@ int windows_files(spsp_ctx* ctx, WindowsRun* run, const RecordsAsk& ask, double 
     if (run->want_fasta)
         printf("segments %s: %llu of %llu segment(s) written, %llu base(s), %llu byte(s) to %s\n", ask.segments_what, (unsigned long long)run->n_written,
                (unsigned long long)run->segments.size(), (unsigned long long)run->bases_written, (unsigned long long)run->fasta.size(), path.c_str());
+    if (run->want_bed)
+        printf("raw coordinates: %llu segment(s) lifted, their raw intervals %llu base(s) longer than the kept ones, %llu byte(s) to %s\n", (unsigned long long)run->n_lifted,
+               (unsigned long long)run->raw_excess, (unsigned long long)run->bed.size(), bed_path.c_str());
     fflush(stdout);
     return SPSP_OK;
 }

@@ -506,21 +506,24 @@ static int taxonomy_files_entry(const RecordFront& front, const RecordsAsk& ask,
     return give_rows_all(&gift, 1);
 }
 
-extern "C" int spsp_taxonomy_files_segments(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+extern "C" int spsp_taxonomy_files_raw(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
                                             uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
                                             uint64_t window, const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win,
                                             uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth,
-                                            const char* segments_what, uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out) {
+                                            const char* segments_what, uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out, int raw,
+                                       uint64_t** raw_begin, uint64_t** raw_end, uint64_t* bed_bytes) {
     if (rows) *rows = nullptr;
     if (first_win) *first_win = nullptr;
     if (segments) *segments = nullptr;
     if (mosaic) *mosaic = nullptr;
-    for (uint64_t* n : {n_windows, n_records, n_segments, n_changed, n_written, bytes_out}) if (n) *n = 0;
+    if (raw_begin) *raw_begin = nullptr;
+    if (raw_end) *raw_end = nullptr;
+    for (uint64_t* n : {n_windows, n_records, n_segments, n_changed, n_written, bytes_out, bed_bytes}) if (n) *n = 0;
     const RecordFront front{ctx, index_paths, lineages_path, true, false, n_ref, 0, min_keys, num, den};
     TaxonomyPass pass(front);
     RecordsOut out;
     RecordsAsk ask = records_ask(&records_path, nullptr, kRmWindows, what, gz, window, precision, out_prefix, chatter, rate);
-    ask.smooth = smooth; ask.segments_what = segments_what; ask.segments_min = segments_min;
+    ask.smooth = smooth; ask.segments_what = segments_what; ask.segments_min = segments_min; ask.raw = raw != 0;
     if (const int rc = record_files_entry(front, pass, ask, &out)) return rc;
     const WindowsRun& run = out.windows;
     if (n_windows) *n_windows = pass.recs.size();
@@ -529,11 +532,24 @@ extern "C" int spsp_taxonomy_files_segments(spsp_ctx* ctx, const char* const* in
     if (n_changed) *n_changed = run.n_changed;
     if (n_written) *n_written = run.n_written;
     if (bytes_out) *bytes_out = run.fasta.size();
+    if (bed_bytes) *bed_bytes = run.bed.size();
     const RowsGift gifts[] = {{(void**)rows, pass.recs.data(), pass.recs.size() * sizeof(spsp_taxonomy_record)},
                               {(void**)first_win, run.first_win.data(), run.first_win.size() * sizeof(uint32_t)},
                               {(void**)segments, run.segments.data(), run.segments.size() * sizeof(spsp_segment_row)},
-                              {(void**)mosaic, run.mosaic.data(), run.mosaic.size() * sizeof(spsp_mosaic_row)}};
-    return give_rows_all(gifts, 4);
+                              {(void**)mosaic, run.mosaic.data(), run.mosaic.size() * sizeof(spsp_mosaic_row)},
+                              {(void**)(raw ? raw_begin : nullptr), run.raw_begin.data(), run.raw_begin.size() * 8},
+                              {(void**)(raw ? raw_end : nullptr), run.raw_end.data(), run.raw_end.size() * 8}};
+    return give_rows_all(gifts, 6);
+}
+
+extern "C" int spsp_taxonomy_files_segments(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
+                                            uint32_t min_keys, uint32_t num, uint32_t den, int precision, const char* out_prefix, int chatter, double rate,
+                                            uint64_t window, const char* what, spsp_taxonomy_record** rows, uint64_t* n_windows, uint32_t** first_win,
+                                            uint64_t* n_records, spsp_segment_row** segments, uint64_t* n_segments, spsp_mosaic_row** mosaic, uint32_t smooth,
+                                            const char* segments_what, uint64_t segments_min, int gz, uint64_t* n_changed, uint64_t* n_written, uint64_t* bytes_out) {
+    return spsp_taxonomy_files_raw(ctx, index_paths, n_ref, records_path, lineages_path, min_keys, num, den, precision, out_prefix, chatter, rate, window, what, rows,
+                                   n_windows, first_win, n_records, segments, n_segments, mosaic, smooth, segments_what, segments_min, gz, n_changed, n_written, bytes_out, 0,
+                                   nullptr, nullptr, nullptr);
 }
 
 extern "C" int spsp_taxonomy_files_windows(spsp_ctx* ctx, const char* const* index_paths, uint32_t n_ref, const char* records_path, const char* lineages_path,
